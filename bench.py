@@ -17,7 +17,8 @@ N * designs * K / max-over-ranks time.  With N > 1 the line also carries "shard"
 m=131072) with the frequency rows of ONE design split over the ranks and the solver's own RCCL all-reduces
 per iteration (strong scaling) -- `--mode shard` makes that the primary metric instead.
 
-One JSON line on stdout (rank 0).
+One JSON line on stdout (rank 0).  `--dump-outputs DIR` also writes the taps, status and objective of every design of
+the last timed step to DIR as float64 .npy files, so that two builds can be compared output for output.
 """
 import argparse
 import gc
@@ -287,6 +288,35 @@ def pmc_traffic():
     return d
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, res):
+    """--dump-outputs: what the timed path handed its caller in the last timed step, as float64 .npy files under `path`.
+    res: the (h, status, info) tuples of that step in job order.  taps_real / taps_imag are (designs, n) (a failed design's
+    row is NaN), solved is 1.0 / 0.0 and pcost the objective per design.  Above 64 MB in all, a fixed seeded sample of the
+    designs is written, and design_index.npy names the rows kept."""
+    import numpy as np
+    n = max([len(h) for h, _, _ in res] + [0])
+    idx = np.arange(len(res))
+    per_design = 8 * (2 * n + 2)
+    if per_design * len(res) > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * len(res)) // per_design)
+        idx = np.sort(np.random.default_rng(0).choice(len(res), size=keep, replace=False))
+    taps = np.full((len(idx), n), np.nan, dtype=np.complex128)
+    for row, q in enumerate(idx):
+        h = np.asarray(res[q][0])
+        taps[row, :len(h)] = h
+    arrays = {"taps_real": taps.real.copy(), "taps_imag": taps.imag.copy(),
+              "solved": np.array([1.0 if res[q][1] == "Solved" else 0.0 for q in idx]),
+              "pcost": np.array([float(res[q][2].get("pcost", np.nan)) for q in idx])}
+    if len(idx) < len(res):
+        arrays["design_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -312,9 +342,13 @@ def main():
                     "reductions go through the host hook instead of its own RCCL communicator)")
     ap.add_argument("--dense", action="store_true", help="materialised trig matrix + dense MFMA Gram (opts.dense_trig) "
                     "instead of the default lattice (matrix-free) mode; one design per stream")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last step "
+                    "(taps, status, objective of every design) as float64 .npy files under DIR (rank 0)")
     ap.add_argument("--other-configs-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--device", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.other_configs_child:
         other_configs_child(args.device, max(1, args.streams))
         return
@@ -384,7 +418,7 @@ def main():
         dense = int(args.dense if dense is None else dense)
         f, a, d = mbfir.spec.spec_c13_bssfp(n)
         o = mbfir.make_opts(grid_m=grid_m, shard_rank=rank, shard_size=world, dense_trig=dense)
-        info = None
+        info = h = None
         for _ in range(warmup):
             mbfir.fir_ap_cvx(n, f, a, d, 0.1, 1e-3, opts=o, ctx=ctx, info=True)
         fence()
@@ -413,6 +447,7 @@ def main():
         sharded_ms = el / steps * 1e3
         chol_ms = info1["ms_chol"]                          # the factorisations of the unsharded solve = the replicated part
         amdahl = one_gpu_ms / (chol_ms + (one_gpu_ms - chol_ms) / world) if one_gpu_ms > 0 else None
+        last["res"] = [(h, status, info)]
         return {"metric": "FIR designs/sec, n=%d taps m=%d, frequency rows of one design sharded x%d (%s path)" % (n, grid_m, world, "dense" if dense else "lattice"),
                 "value": steps / el, "unit": "designs/s", "ms_per_design": sharded_ms, "scaling": "strong", "mode": "dense" if dense else "lattice",
                 "iters": info["iters"], "collectives_per_iteration": info["collectives"] / max(1, info["iters"]),
@@ -426,6 +461,7 @@ def main():
                         "triangle); the weak-scaling batch figure above (independent designs, no collective) is the mode that approaches N x",
                 "reductions": "ncclAllReduce on the solver stream (mbfir_comm_init)" if args.backend == "nccl" else "host hook (gloo rehearsal)"}
 
+    last = {}                                    # the results of the last timed step (--dump-outputs)
     shard_primary = args.mode == "shard" and world > 1
     if shard_primary:
         wire_shard(ctx)
@@ -436,6 +472,8 @@ def main():
                    "vs_baseline": None, "dtype": "f64", "data": "synthetic",
                    "config": {"workload": "S-C13 bSSFP spec, fir_ap_cvx(n=%d, obj=0.1, Peak=1e-3), grid_m=%d, rows sharded x%d"
                                           % (args.n, args.grid_m, world)}, "shard": res, "roofline": None, "cpu_baseline": None}
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last["res"])
             print(json.dumps(out), flush=True)
         for c in ctxs:
             c.close()
@@ -452,6 +490,7 @@ def main():
         for h, status, info in res:
             if status != "Solved":
                 raise RuntimeError("benchmark design did not solve: %r" % (info,))
+        last["res"] = res
         return [info for _, _, info in res]
 
     for _ in range(args.warmup):
@@ -488,6 +527,7 @@ def main():
         _, st_d, dense_info = mbfir.fir_ap_cvx(*jobs[0][1], ctx=ctx, info=True, opts=mbfir.make_opts(grid_m=args.grid_m, dense_trig=1))
         if st_d != "Solved":
             dense_info = None
+    timed_res = last["res"]
     out = None
     if rank == 0:
         iters = sum(i["iters"] for i in infos)
@@ -662,6 +702,8 @@ def main():
         if rank == 0:
             out["shard"] = shard_res
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, timed_res)
         print(json.dumps(out), flush=True)
     for c in ctxs:
         c.close()

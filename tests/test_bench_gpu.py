@@ -125,3 +125,22 @@ def test_plain_bench_with_gpus_2_starts_its_own_ranks():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0
+
+
+def test_bench_dumps_the_outputs_of_its_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the taps of every design of the last timed step as float64 .npy files, solved, with the
+    objective of each; `--steps` is the number of timed steps the line reports."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "0", "--n", "64", "--grid-m", "1024",
+                        "--designs", "8", "--lanes", "4", "--streams", "2", "--cpu-iters", "0", "--no-other-configs",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+    arrays = {name: np.load(out / (name + ".npy")) for name in ("taps_real", "taps_imag", "solved", "pcost")}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert arrays["taps_real"].shape == arrays["taps_imag"].shape == (8, 64)
+    assert np.all(arrays["solved"] == 1.0) and np.all(np.isfinite(arrays["taps_real"])) and np.all(np.isfinite(arrays["pcost"]))
+    assert np.abs(arrays["taps_real"]).max() > 0
+    assert not (out / "design_index.npy").exists()
