@@ -251,6 +251,31 @@ int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1
                 const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos,
                 const double* dx, const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
 
+/* ---- Root-flip search for the smallest peak (fir_flip_zero.m:56-102, rf_tools/mex5/minpeakrf.c) -----------------------
+ * Scores a whole candidate set of one beta polynomial on the device and keeps the best.  Candidate c has the n coefficients of
+ *     c0(x) * prod_{j < nz} (x - r_j),   r_j = zf[j] if factor j is flipped in c, else z[j]
+ * (c0: the n - nz coefficients of the roots that never flip, leading first; the factors are multiplied on in the order j = 0, 1, ..
+ * as the host fir_flip_zero does), then scaled:
+ *   scale_rule 0: sum(beta) = s_re + i s_im                                       (fir_flip_zero.m:83)
+ *   scale_rule 1: beta / max_k |FFT_nn(beta)_k| * bsf, nn = next power of two >= n, bsf = s_re in [0, 1]   (npoly.code.c, minpeakrf.c)
+ * and scored:
+ *   criterion 0: max_k |beta_k|
+ *   criterion 1: max_k |rf_k|, rf = ab2rf(b2a(beta), beta) as mbfir_b2rf computes it (b2a.m:15-32 with its 8 n padding and clip,
+ *                ab2rf.m:14-29) -- not b2a.code.c, which minpeakrf.c calls (power-of-two padding, conjugate convention)
+ * Candidates: masks != NULL: explicit, ceil(nz / 32) words per candidate, bit j of word j / 32 set = factor j flipped (nz <= 1023);
+ *   masks == NULL: c = 0 .. ncand-1 enumerated on the device (ncand <= 2^24): factor j flipped iff bit (enum_bits[j] >> 1) of c
+ *   equals enum_bits[j] & 1 (every source bit < 24); enum_bits == NULL is fir_flip_zero.m's combination_2power (:153-160): ncand must
+ *   be 2^nz and factor j is flipped iff bit (nz - 1 - j) of c is 0.
+ * Winner: the smallest peak; exactly equal peaks go to the lowest index, or the highest with tie_high = 1 (minpeakrf.c's `<=`); a
+ *   candidate with a non-finite peak never wins.  *winner receives its index, *winner_peak its peak, beta_re / beta_im (n each,
+ *   optional) its scaled coefficients, peaks (ncand, optional) every candidate's peak (inf where it is not finite).
+ * Limits: 2 <= n <= 1024 (minpeakrf.c's MAXN), 0 <= nz <= n - 1, ncand >= 1, else MBFIR_E_ARG.  Returns MBFIR_NUMERICAL (winner = -1)
+ * when no candidate has a finite peak. */
+int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
+                      const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
+                      int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
+                      double* beta_im, long* winner, double* winner_peak);
+
 /* Device kernel test hooks (need a GPU; host arrays in, host arrays out):
  *  mbfir_test_gram: T = A' diag(dk) A for nw weight vectors; A is m x nt row-major,
  *     d is nw x m, out is nw x nt x nt (full symmetric).

@@ -6,12 +6,17 @@
  *     op 1: (a, b)           rf = ab2rf(a, b)       -> o1 = rf                      (mbfir_ab2rf)
  *     op 2: (b)              rf = b2rf(b)           -> o1 = rf                      (mbfir_b2rf)
  *     op 3: (rf, g, x, mode) [a b] = abrm(rf, g, x) -> o1 = a, o2 = b; g may be []  (mbfir_abr)
+ *     op 4: (z, flip, bsf)   zmin = minpeakrf(z, flip, bsf) -> o1 = zmin            (mbfir_flip_search)
+ *           rf_tools/mex5/minpeakrf.c's rules (flip: nflip x 2 one-based indices, second column 0 = single root, else a
+ *           conjugate pair; singles take the low bits; start at z0's peak with index 0, replace on <=), scored through
+ *           mbfir_b2rf's chain; at most 24 flip units, no progress printing
  *
  * It is the reference's own gateways (rf_tools/mex5/b2a.c:31-68, cabc2rf.c, abrx.c:35-62) with the compute call
  * swapped for the C ABI: same plain double planes, no static scratch, no MAXN cap.  Shares nothing with
  * mbfir_mex.c but the context idiom.  Build:
  *   mex -R2017b matlab/mbfir_slr_mex.c -Iinclude -Lmultiband-rf-pulse-design_amd -lmbfir
  */
+#include <math.h>
 #include <string.h>
 #include "mex.h"
 #include "mbfir.h"
@@ -42,6 +47,76 @@ static void planes(const mxArray* v, size_t len, double* re, double* im) {
     const double* q = mxGetPi(v);
     for (i = 0; i < len; ++i) { re[i] = r[i]; im[i] = q ? q[i] : 0.0; }
 #endif
+}
+
+static void poly_mult(double* cr, double* ci, int deg, double zr, double zi) {     /* c(x) *= (x - z), deg = current degree */
+    int k;
+    for (k = deg + 1; k >= 1; --k) {
+        cr[k] -= zr * cr[k - 1] - zi * ci[k - 1];
+        ci[k] -= zr * ci[k - 1] + zi * cr[k - 1];
+    }
+}
+
+/* minpeakrf (op 4): z (n roots) in zr / zi, result in place */
+static int minpeakrf_op(int n, double* zr, double* zi, const double* fl, int nflip, double bsf) {
+    int i, j, u = 0, nf = 0, rc, deg;
+    long best = -1, start = -1;
+    double p0 = 0, pb = 0;
+    int* fac = (int*)mxCalloc(2 * (size_t)nflip + 1, sizeof(int));
+    int* bits = (int*)mxCalloc(2 * (size_t)nflip + 1, sizeof(int));
+    char* used = (char*)mxCalloc((size_t)n + 1, 1);
+    double* c = (double*)mxCalloc(4 * ((size_t)n + 1) + 8 * ((size_t)nflip + 1), sizeof(double));
+    double *cr = c, *ci = c + n + 1, *dr = ci + n + 1, *di = dr + n + 1, *fz = di + n + 1;
+    if (bsf < 0 || bsf > 1) mexErrMsgTxt("bsf not in 0..1");
+    if (nflip > 24) mexErrMsgTxt("more than 24 flip units");
+    for (i = 0; i < nflip; ++i) {                          /* singles first, then pairs (minpeakrf.c:80-91) */
+        int r1 = (int)fl[i] - 1, r2 = (int)fl[i + nflip] - 1;
+        if (r1 < 0 || r1 >= n || r2 < -1 || r2 >= n || fl[i] != (double)(r1 + 1)) mexErrMsgTxt("bad root index in flip");
+    }
+    for (i = 0; i < nflip; ++i) {
+        int r1 = (int)fl[i] - 1, r2 = (int)fl[i + nflip] - 1;
+        if (r2 >= 0) continue;
+        if (used[r1]) mexErrMsgTxt("a root is listed more than once in flip");
+        used[r1] = 1; fac[nf] = r1; bits[nf++] = (u++ << 1) | 1;
+    }
+    for (i = 0; i < nflip; ++i) {
+        int r1 = (int)fl[i] - 1, r2 = (int)fl[i + nflip] - 1;
+        if (r2 < 0) continue;
+        if (used[r1] || used[r2] || r1 == r2) mexErrMsgTxt("a root is listed more than once in flip");
+        used[r1] = used[r2] = 1;
+        if ((hypot(zr[r1], zi[r1]) - 1) / (hypot(zr[r2], zi[r2]) - 1) < 0) {     /* same side of the circle first (:97-103) */
+            double q = zr[r1] * zr[r1] + zi[r1] * zi[r1];
+            zr[r1] /= q; zi[r1] /= q;
+        }
+        fac[nf] = r1; bits[nf++] = (u << 1) | 1;           /* bit 1 flips the first root, bit 0 the second */
+        fac[nf] = r2; bits[nf++] = (u++ << 1) | 0;
+    }
+    cr[0] = 1; deg = 0;                                    /* z0's own peak: the start of the running minimum */
+    for (i = 0; i < n; ++i) poly_mult(cr, ci, deg++, zr[i], zi[i]);
+    rc = mbfir_flip_search(g_ctx, n + 1, 0, cr, ci, NULL, NULL, NULL, NULL, 1, NULL, NULL, 1, bsf, 0, 1, 1, &p0, NULL, NULL, &start, NULL);
+    if (rc != 0) return rc;
+    memset(c, 0, 2 * ((size_t)n + 1) * sizeof(double));
+    cr[0] = 1; deg = 0;
+    for (i = 0; i < n; ++i) if (!used[i]) poly_mult(cr, ci, deg++, zr[i], zi[i]);
+    for (j = 0; j < nf; ++j) {
+        double q = zr[fac[j]] * zr[fac[j]] + zi[fac[j]] * zi[fac[j]];
+        dr[j] = zr[fac[j]]; di[j] = zi[fac[j]];
+        fz[2 * j] = zr[fac[j]] / q; fz[2 * j + 1] = zi[fac[j]] / q;
+    }
+    for (j = 0; j < nf; ++j) { cr[deg + 1 + j] = 0; ci[deg + 1 + j] = 0; }
+    {
+        double* fr = (double*)mxCalloc((size_t)nf + 1, sizeof(double));
+        double* fi = (double*)mxCalloc((size_t)nf + 1, sizeof(double));
+        for (j = 0; j < nf; ++j) { fr[j] = fz[2 * j]; fi[j] = fz[2 * j + 1]; }
+        rc = mbfir_flip_search(g_ctx, n + 1, nf, cr, ci, dr, di, fr, fi, 1L << u, NULL, bits, 1, bsf, 0, 1, 1, NULL, NULL, NULL, &best, &pb);
+        mxFree(fr); mxFree(fi);
+    }
+    if (rc != 0) return rc;
+    if (!(pb <= p0)) best = 0;
+    for (j = 0; j < nf; ++j)
+        if (((best >> (bits[j] >> 1)) & 1) == (bits[j] & 1)) { zr[fac[j]] = fz[2 * j]; zi[fac[j]] = fz[2 * j + 1]; }
+    mxFree(fac); mxFree(bits); mxFree(used); mxFree(c);
+    return 0;
 }
 
 static double* out_plane(mxArray** slot, size_t len) {
@@ -75,7 +150,17 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         i2r = (double*)mxCalloc(n, sizeof(double)); i2i = (double*)mxCalloc(n, sizeof(double));
         planes(prhs[2], n, i2r, i2i);
     }
-    if (op == 3) {                                       /* abrm(rf, g, x, mode) */
+    if (op == 4) {                                       /* minpeakrf(z, flip, bsf) */
+        if (nrhs < 4 || (mxGetN(prhs[2]) != 2 && mxGetM(prhs[2]) > 0)) mexErrMsgTxt("minpeakrf: z, flip (nflip x 2), bsf expected");
+        if (n + 1 > 1024) mexErrMsgTxt("z vector too long");
+        o1r = out_plane(&plhs[0], n); o1i = out_plane(&plhs[1], n);
+        memcpy(o1r, i1r, n * sizeof(double)); memcpy(o1i, i1i, n * sizeof(double));
+#if MX_HAS_INTERLEAVED_COMPLEX
+        rc = minpeakrf_op((int)n, o1r, o1i, mxGetDoubles(prhs[2]), (int)mxGetM(prhs[2]), mxGetScalar(prhs[3]));
+#else
+        rc = minpeakrf_op((int)n, o1r, o1i, mxGetPr(prhs[2]), (int)mxGetM(prhs[2]), mxGetScalar(prhs[3]));
+#endif
+    } else if (op == 3) {                                /* abrm(rf, g, x, mode) */
         if (nrhs < 4) mexErrMsgTxt("abrm: rf, g, x expected");
         nx = veclen(prhs[3]);
         if (nx < 1) mexErrMsgTxt("abrm: empty x");

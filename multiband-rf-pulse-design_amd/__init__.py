@@ -99,6 +99,8 @@ SYMBOLS = {
     "mbfir_b2a": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_ab2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_b2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_flip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
+                                    C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _dp]),
     "mbfir_abr": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_bloch": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
                               _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp]),
@@ -419,6 +421,132 @@ def b2rf(bc, *, ctx=None):
     return rre + 1j * rim
 
 
+def _pack_masks(masks):
+    """nz x ncand 0/1 matrix (a column per candidate, fir_flip_zero's layout) -> ncand x ceil(nz / 32) uint32 words, bit j = row j."""
+    m = np.asarray(masks).astype(bool)
+    nz, num = m.shape
+    words = (nz + 31) // 32
+    pad = np.zeros((words * 32, num), dtype=np.uint64)
+    pad[:nz] = m
+    w = (pad.reshape(words, 32, num) << np.arange(32, dtype=np.uint64)[None, :, None]).sum(axis=1)
+    return np.ascontiguousarray(w.T.astype(np.uint32))
+
+
+def flip_search(c0, z, zf, *, masks=None, enum_bits=None, ncand=None, target=None, bsf=None, criterion="beta", tie_high=False,
+                return_peaks=False, ctx=None):
+    """Root-flip search on the device (mbfir_flip_search): candidate = poly c0 times prod_j (x - z_j or x - zf_j), scaled to
+    sum(beta) = target (fir_flip_zero.m:83) or npoly-normalised times bsf (minpeakrf.c), scored by its largest |beta_k|
+    (criterion "beta") or its largest |rf_k| through b2rf (criterion "rf").  Candidates: `masks` (nz x ncand 0/1, a column per
+    candidate, 1 = flipped), or all 2^nz in combination_2power order (fir_flip_zero.m:153-160), or, with `enum_bits` (nz ints) and
+    `ncand`, c = 0 .. ncand-1 with factor j flipped iff bit (enum_bits[j] >> 1) of c equals enum_bits[j] & 1.
+    Returns (winner's beta, winner's index, every candidate's peak or None)."""
+    ctx = ctx or get_context()
+    c0re, c0im = _split(c0)
+    zre, zim = _split(z)
+    fre, fim = _split(zf)
+    nz = len(zre)
+    if len(fre) != nz:
+        raise ValueError("flip_search: z and zf must have the same length")
+    n = len(c0re) + nz
+    if (target is None) == (bsf is None):
+        raise ValueError("flip_search: give exactly one of target (DC rule) and bsf (npoly rule)")
+    if criterion not in ("beta", "rf"):
+        raise ValueError("flip_search: criterion must be 'beta' or 'rf'")
+    mk, eb = None, None
+    if masks is not None:
+        mk = _pack_masks(np.asarray(masks).reshape(nz, -1))
+        ncand = mk.shape[0]
+    elif enum_bits is not None:
+        eb = np.ascontiguousarray(np.asarray(enum_bits, dtype=np.int32).ravel())
+        if len(eb) != nz or ncand is None:
+            raise ValueError("flip_search: enum_bits needs one entry per factor and ncand")
+    else:
+        if nz > 24:
+            raise ValueError("flip_search: all 2^nz candidates only up to nz = 24 (got %d)" % nz)
+        ncand = 2 ** nz
+    ncand = int(ncand)
+    pk = np.zeros(ncand) if return_peaks else None
+    bre, bim = np.zeros(n), np.zeros(n)
+    win, wp = C.c_long(-1), C.c_double(0)
+    if target is not None:
+        t = complex(target)
+        rule, sre, sim = 0, t.real, t.imag
+    else:
+        rule, sre, sim = 1, float(bsf), 0.0
+    rc = load_library().mbfir_flip_search(
+        ctx._h, n, nz, _ptr(c0re), _ptr(c0im), _ptr(zre), _ptr(zim), _ptr(fre), _ptr(fim), ncand,
+        mk.ctypes.data_as(C.POINTER(C.c_uint)) if mk is not None else None, eb.ctypes.data_as(_ip) if eb is not None else None,
+        rule, sre, sim, 1 if criterion == "rf" else 0, 1 if tie_high else 0, _ptr(pk) if pk is not None else None,
+        _ptr(bre), _ptr(bim), C.byref(win), C.byref(wp))
+    if rc == E_ARG:
+        raise ValueError("flip_search: arguments out of range (%s)" % ctx.last_error())
+    if rc != 0:
+        raise MbfirError("mbfir_flip_search failed (%d): %s" % (rc, ctx.last_error()))
+    return bre + 1j * bim, int(win.value), pk
+
+
+def _flip_root(z):
+    return z / (z.real ** 2 + z.imag ** 2)                # minpeakrf.c flip_root
+
+
+def minpeakrf(z, flip, bsf, *, ctx=None):
+    """`zmin = minpeakrf(z, flip, bsf)` (rf_tools/mex5/minpeakrf.c): of every combination of root flips, the roots whose beta
+    polynomial (npoly-normalised, times bsf) gives the smallest RF peak.  flip: nflip x 2 matrix of 1-based root indices, second
+    column 0 = a single root, otherwise a conjugate pair (bit 0 flips the second root, bit 1 the first; a pair on opposite sides of
+    the unit circle has its first root flipped before the search).  Singles take the low bits of the combination index, pairs the
+    next ones; the running minimum starts at the peak of the unflipped roots with index 0 and a candidate replaces it when its
+    peak is <= the minimum.  Scored on the device through this package's b2rf (b2a.m's 8 n padding), not b2a.code.c's.
+    Exhaustive up to 24 flip units (2^24 combinations)."""
+    z = np.asarray(z, dtype=np.complex128).ravel()
+    nroots = len(z)
+    if nroots + 1 > 1024:
+        raise ValueError("minpeakrf: z vector too long")
+    bsf = float(np.asarray(bsf).ravel()[0])
+    if not (0.0 <= bsf <= 1.0):
+        raise ValueError("minpeakrf: bsf not in 0..1")
+    fl = np.asarray(flip, dtype=np.float64)
+    if fl.size == 0:
+        fl = np.zeros((0, 2))
+    if fl.ndim != 2 or fl.shape[1] != 2:
+        raise ValueError("minpeakrf: flip must be an nflip x 2 matrix")
+    if np.any(fl != np.round(fl)) or np.any(fl[:, 0] < 1) or np.any(fl > nroots) or np.any(fl[:, 1] < 0):
+        raise ValueError("minpeakrf: bad root index in flip")
+    fl = fl.astype(np.int64)
+    singles = [int(r[0]) - 1 for r in fl if r[1] == 0]
+    pairs = [(int(r[0]) - 1, int(r[1]) - 1) for r in fl if r[1] != 0]
+    used = singles + [r for p in pairs for r in p]
+    if len(set(used)) != len(used):
+        raise ValueError("minpeakrf: a root is listed more than once in flip")
+    nflip = len(singles) + len(pairs)
+    if nflip > 24:
+        raise ValueError("minpeakrf: more than 24 flip units (2^24 combinations)")
+    z0 = z.copy()
+    for r1, r2 in pairs:                                    # same side of the unit circle first
+        if (abs(z[r1]) - 1) / (abs(z[r2]) - 1) < 0:
+            z0[r1] = _flip_root(z[r1])
+    fac, bits = [], []
+    for u, r in enumerate(singles):
+        fac.append(r)
+        bits.append((u << 1) | 1)
+    for u, (r1, r2) in enumerate(pairs, start=len(singles)):
+        fac += [r1, r2]
+        bits += [(u << 1) | 1, (u << 1) | 0]               # bit 1 flips the first, bit 0 the second
+    fixed = np.ones(nroots, dtype=bool)
+    fixed[fac] = False
+    from .flipzero import _poly
+    c0 = _poly(z0[fixed])
+    zr = z0[fac]
+    _, _, p0 = flip_search(_poly(z0), [], [], bsf=bsf, criterion="rf", return_peaks=True, ctx=ctx)
+    _, best, pk = flip_search(c0, zr, _flip_root(zr), enum_bits=bits, ncand=2 ** nflip, bsf=bsf, criterion="rf", tie_high=True,
+                              return_peaks=True, ctx=ctx)
+    idx = best if pk[best] <= p0[0] else 0
+    zmin = z0.copy()
+    for j, r in enumerate(fac):
+        if ((idx >> (bits[j] >> 1)) & 1) == (bits[j] & 1):
+            zmin[r] = _flip_root(z0[r])
+    return zmin
+
+
 def abrm(rf, g=None, x=None, *, hard_pulse=False, ctx=None):
     """`[a b] = abrm(rf, g, x)` (rf_tools/abrm.m): Cayley-Klein parameters of the pulse at positions x; with two
     arguments the second one is x.  hard_pulse=True simulates the model ab2rf inverts exactly instead."""
@@ -451,7 +579,7 @@ def rfscaleg(rf, t, gamma):
 from . import spec          # noqa: E402  (physical multiband description -> (f, a, d); host only)
 from . import io            # noqa: E402  (rfwrite / rfwrite_varian / signa)
 from .io import rfwrite, rfwrite_varian, signa   # noqa: E402
-from .flipzero import fir_flip_zero   # noqa: E402  (fir_flip_zero.m)
+from .flipzero import fir_flip_zero   # noqa: E402  (fir_flip_zero.m; its device search: flip_search above)
 from .dzrf import dzrf_mb, fir_upsample, rf_mrange_desired   # noqa: E402  (dzrf_mb.m driver)
 from .search import fir_ap, fir_qp, fir_min_order_linprog, fir_min_order_qprog_phs   # noqa: E402  (outer bisections)
 

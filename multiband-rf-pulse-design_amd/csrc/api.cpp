@@ -699,6 +699,27 @@ int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, c
         return MBFIR_E_ARG;
     MBFIR_TRY(ctx, ctx->solver->abr(n, rf_re, rf_im, g, nx, x, mode, a_re, a_im, b_re, b_im));
 }
+int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
+                      const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
+                      int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
+                      double* beta_im, long* winner, double* winner_peak) {
+    if (!ctx || n < 2 || n > 1024 || nz < 0 || nz > n - 1 || nz > 1023 || ncand < 1 || !c0_re || !c0_im || !winner ||
+        (nz > 0 && (!z_re || !z_im || !zf_re || !zf_im)) || (!beta_re) != (!beta_im) || (criterion != 0 && criterion != 1) ||
+        (scale_rule != 0 && scale_rule != 1) || (scale_rule == 1 && !(s_re >= 0.0 && s_re <= 1.0)))
+        return MBFIR_E_ARG;
+    if (!masks) {
+        if (ncand > (1L << 24)) return MBFIR_E_ARG;
+        if (!enum_bits && (nz > 24 || ncand != (1L << nz))) return MBFIR_E_ARG;
+        for (int j = 0; enum_bits && j < nz; ++j)
+            if (enum_bits[j] < 0 || (enum_bits[j] >> 1) >= 24) return MBFIR_E_ARG;
+    }
+    try {
+        *winner = ctx->solver->flip_search(n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re,
+                                           s_im, criterion, tie_high ? 1 : 0, peaks, beta_re, beta_im, winner_peak);
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+    if (*winner < 0) { ctx->err = "flip search: no candidate has a finite peak"; return MBFIR_NUMERICAL; }
+    return 0;
+}
 int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));
 }

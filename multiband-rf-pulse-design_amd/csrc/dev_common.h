@@ -175,6 +175,12 @@ void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work,
 void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
                     hipStream_t st);
 // Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:283-512).  step: ntime x 8 per-sample quantities.
+// Root-flip search (flip.hip): host side of mbfir_flip_search, arguments checked; returns the winner, -1 when no candidate has a
+// finite peak.
+long flip_search_run(int device, hipStream_t st, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
+                     const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
+                     const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
+                     double* beta_re, double* beta_im, double* winner_peak);
 void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode, double* mx,
                   double* my, double* mz, hipStream_t st);
 void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st);

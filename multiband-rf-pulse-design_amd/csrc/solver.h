@@ -88,6 +88,11 @@ public:
     void bloch(int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy, const double* gz,
                const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
                const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
+    // Root-flip search (flip.hip, mbfir_flip_search): returns the winner, -1 when no candidate has a finite peak.
+    long flip_search(int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
+                     const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
+                     int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
+                     double* beta_im, double* winner_peak);
     // kernel test hooks
     void test_gram(int m, int nt, int nw, const double* A, const double* d, double* out);
     void test_chol(int n, const double* H, double* out_l, double* out_m);

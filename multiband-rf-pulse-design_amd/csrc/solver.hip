@@ -4229,6 +4229,16 @@ void Solver::bloch(int ntime, const double* b1_re, const double* b1_im, const do
     MBFIR_HIP(hipGetLastError());
 }
 
+long Solver::flip_search(int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
+                         const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
+                         int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
+                         double* beta_im, double* winner_peak) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    return flip_search_run(S.device, S.st, n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re,
+                           s_im, criterion, tie_high, peaks, beta_re, beta_im, winner_peak);
+}
+
 // fp64 peak microbenchmarks (roofline denominators; the local hardware guide lists no fp64
 // matrix peak).  One wave per SIMD, 8 independent accumulators, operands in registers.
 __global__ __launch_bounds__(256) void k_peak_mfma(double* out, int iters) {

@@ -50,9 +50,13 @@ def fir_upsample(h, dt1, dt2):
 
 def dzrf_mb(n, dt, mb_cf, mb_range, mb_FA, mb_ripple, ptype="sat", ftype="ap_cvx", nucleus="C-13", flip_zero=0,
             downsampling=1, Peak=1e-3, dbg=0, min_order=0.9, min_tran=0.85, shift_f=0, name_cell=None, *,
-            opts=None, probes=1):
+            opts=None, probes=1, flip_criterion="beta", flip_candidates="reference", flip_seed=None):
     """Returns (rf_pulse, b, rf_spec, b_spec) like dzrf_mb.m; ([], [], rf_spec, b_spec) when the filter design
-    fails (dzrf_mb.m:216-218).  rf_pulse in Gauss, dt in ms, frequencies in kHz."""
+    fails (dzrf_mb.m:216-218).  rf_pulse in Gauss, dt in ms, frequencies in kHz.
+    flip_criterion / flip_candidates / flip_seed go to fir_flip_zero (criterion, candidates, seed) when flip_zero is set
+    ("rf" / "all": the device root-flip search).
+    The flip happens before fir_upsample (dzrf_mb.m:223-231), so with downsampling >= 2 the RF criterion scores the RF of the
+    design-rate beta, not of the upsampled one the pulse is made of."""
     import mbfir
     nucleus = nucleus or "C-13"
     if nucleus not in GAMMA:
@@ -125,7 +129,7 @@ def dzrf_mb(n, dt, mb_cf, mb_range, mb_FA, mb_ripple, ptype="sat", ftype="ap_cvx
         return np.zeros(0, dtype=np.complex128), np.zeros(0, dtype=np.complex128), rf_spec, b_spec
     b = np.asarray(b, dtype=np.complex128).ravel()[::-1]                                    # :220
     if flip_zero:                                                                           # :223-225
-        b = mbfir.fir_flip_zero(b, dbg)
+        b = mbfir.fir_flip_zero(b, dbg, seed=flip_seed, criterion=flip_criterion, candidates=flip_candidates)
     if downsampling >= 2:                                                                   # :228-231
         b = fir_upsample(b, dt, dt / downsampling)
     dt = dt / downsampling
