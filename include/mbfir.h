@@ -276,6 +276,44 @@ int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const 
                       int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
                       double* beta_im, long* winner, double* winner_peak);
 
+/* ---- Conventional SLR filters: Parks-McClellan and fmp (rf_tools/dzlp.m, dzmp.m, fmp.m) ----------------------------------------
+ * mbfir_remez_batch: `h = remez(numtaps - 1, edges, desired, weight)` as dzlp.m:13 and dzmp.m:16 call it, for njobs independent
+ *   designs in one launch (one workgroup each).  Real, symmetric, linear-phase filters only: type I (odd numtaps) and type II (even),
+ *   3 <= numtaps <= 2047.  edges: 2 nband band edges in [0, 1] (1 = Nyquist, MATLAB's convention), ascending, bands disjoint;
+ *   desired: the amplitude at both edges of each band (linear in between); weight: one positive weight per band; 1 <= nband <= 64.
+ *   type must be MBFIR_REMEZ_BANDPASS: Hilbert transformers and differentiators (antisymmetric taps) are rejected with MBFIR_E_ARG.
+ *   Grid: McClellan-Parks-Rabiner, density points per cosine term (opts->grid_density, 0 = 16), the grid rule of
+ *   scipy.signal.remez with the bands in Nyquist units; type II leaves omega = pi off the grid.  The exchange stops when the extremal
+ *   set no longer changes, or after opts->maxiter iterations (0 = 25).  Out: h (numtaps), ext (optional, the L + 1 final extremal
+ *   frequencies, L = (numtaps + 1) / 2 or numtaps / 2), status (MBFIR_REMEZ_*), iterations, delta (the weighted ripple of the last
+ *   iterate, signed).  MBFIR_REMEZ_MAXITER keeps the last iterate; it is never reported as converged.  Returns 0 when every design
+ *   ran (whatever its status), MBFIR_E_ARG naming the first bad job, MBFIR_E_HIP.
+ * mbfir_fmp: `hmp = fmp(h)` (rf_tools/fmp.m:12-23): the minimum-phase factor of an equiripple linear-phase filter of odd length
+ *   l <= 2047 (h_im may be NULL), (l + 1) / 2 complex taps out.  Even l is MBFIR_E_ARG (the reference prints and returns). */
+#define MBFIR_REMEZ_BANDPASS 0
+#define MBFIR_REMEZ_CONVERGED 0
+#define MBFIR_REMEZ_MAXITER 1
+#define MBFIR_REMEZ_FAILED 2
+typedef struct mbfir_remez_job {
+    int numtaps;
+    int nband;
+    int type;              /* MBFIR_REMEZ_BANDPASS */
+    const double* edges;   /* 2 nband */
+    const double* desired; /* 2 nband */
+    const double* weight;  /* nband */
+    double* h;             /* out: numtaps */
+    double* ext;           /* out, optional: L + 1 */
+    int status;            /* out */
+    int iterations;        /* out */
+    double delta;          /* out */
+} mbfir_remez_job;
+typedef struct mbfir_remez_opts {
+    int grid_density;      /* 0 -> 16 */
+    int maxiter;           /* 0 -> 25 */
+} mbfir_remez_opts;
+int mbfir_remez_batch(mbfir_ctx* ctx, mbfir_remez_job* jobs, int njobs, const mbfir_remez_opts* opts);
+int mbfir_fmp(mbfir_ctx* ctx, int l, const double* h_re, const double* h_im, double* out_re, double* out_im);
+
 /* Device kernel test hooks (need a GPU; host arrays in, host arrays out):
  *  mbfir_test_gram: T = A' diag(dk) A for nw weight vectors; A is m x nt row-major,
  *     d is nw x m, out is nw x nt x nt (full symmetric).

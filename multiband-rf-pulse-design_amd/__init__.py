@@ -68,6 +68,18 @@ class Job(C.Structure):
                 ("info", Info), ("z", C.POINTER(C.c_double)), ("z_cap", C.c_int), ("err", C.c_char * 128)]
 
 
+class RemezJob(C.Structure):
+    """struct mbfir_remez_job (include/mbfir.h)."""
+    _fields_ = [("numtaps", C.c_int), ("nband", C.c_int), ("type", C.c_int), ("edges", C.POINTER(C.c_double)),
+                ("desired", C.POINTER(C.c_double)), ("weight", C.POINTER(C.c_double)), ("h", C.POINTER(C.c_double)),
+                ("ext", C.POINTER(C.c_double)), ("status", C.c_int), ("iterations", C.c_int), ("delta", C.c_double)]
+
+
+class RemezOpts(C.Structure):
+    """struct mbfir_remez_opts (include/mbfir.h)."""
+    _fields_ = [("grid_density", C.c_int), ("maxiter", C.c_int)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -101,6 +113,8 @@ SYMBOLS = {
     "mbfir_b2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_flip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
                                     C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _dp]),
+    "mbfir_remez_batch": (C.c_int, [C.c_void_p, C.POINTER(RemezJob), C.c_int, C.POINTER(RemezOpts)]),
+    "mbfir_fmp": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_abr": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_bloch": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
                               _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp]),
@@ -582,6 +596,15 @@ from .io import rfwrite, rfwrite_varian, signa   # noqa: E402
 from .flipzero import fir_flip_zero   # noqa: E402  (fir_flip_zero.m; its device search: flip_search above)
 from .dzrf import dzrf_mb, fir_upsample, rf_mrange_desired   # noqa: E402  (dzrf_mb.m driver)
 from .search import fir_ap, fir_qp, fir_min_order_linprog, fir_min_order_qprog_phs   # noqa: E402  (outer bisections)
+from . import slrclassic    # noqa: E402  (conventional SLR pulses, dzrf.m and its designers; device remez and fmp)
+from .slrclassic import (remez, remez_batch, fmp, msinc, firls_lp, dzlp, dzls, dzmp, dzrf_batch,   # noqa: E402
+                         sim_rf_scale)
+# `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
+# sys.modules (`from mbfir.dzrf import dzrf_mb`), and the function carries that module's public names for attribute access.
+dzrf = slrclassic.dzrf
+for _n in ("dzrf_mb", "fir_upsample", "rf_mrange_desired"):
+    setattr(dzrf, _n, globals()[_n])
+del _n
 
 _WHICH = {"fir_ap_cvx": 0, "fir_qp_cvx": 1, "fir_linprog": 2, "fir_qprog_phs": 3}
 _pools = {}

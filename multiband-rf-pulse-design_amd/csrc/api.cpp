@@ -4,6 +4,7 @@
 #include "program.h"
 #include "solver.h"
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <algorithm>
 #include <cstdlib>
@@ -719,6 +720,43 @@ int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const 
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
     if (*winner < 0) { ctx->err = "flip search: no candidate has a finite peak"; return MBFIR_NUMERICAL; }
     return 0;
+}
+int mbfir_remez_batch(mbfir_ctx* ctx, mbfir_remez_job* jobs, int njobs, const mbfir_remez_opts* opts) {
+    if (!ctx) return MBFIR_E_ARG;
+    const int density = opts && opts->grid_density > 0 ? opts->grid_density : 16;
+    const int maxiter = opts && opts->maxiter > 0 ? opts->maxiter : 25;
+    if (!jobs || njobs < 1 || density > 1024 || maxiter > 10000) { ctx->err = "remez: bad batch or options"; return MBFIR_E_ARG; }
+    std::vector<RemezJobHost> hj(njobs);
+    for (int q = 0; q < njobs; ++q) {
+        mbfir_remez_job& j = jobs[q];
+        auto bad = [&](const char* why) { ctx->err = "remez job " + std::to_string(q) + ": " + why; return MBFIR_E_ARG; };
+        if (j.type != MBFIR_REMEZ_BANDPASS) return bad("only symmetric (bandpass) filters; no Hilbert or differentiator");
+        if (j.numtaps < 3 || j.numtaps > 2047) return bad("numtaps must be in [3, 2047]");
+        if (j.nband < 1 || j.nband > 64) return bad("nband must be in [1, 64]");
+        if (!j.edges || !j.desired || !j.weight || !j.h) return bad("null array");
+        for (int b = 0; b < 2 * j.nband; ++b) {
+            const double e = j.edges[b];
+            if (!(e >= 0.0 && e <= 1.0)) return bad("band edges must lie in [0, 1]");
+            if (b > 0 && !(e >= j.edges[b - 1])) return bad("band edges must ascend");
+            if ((b & 1) == 0 && b > 0 && !(e > j.edges[b - 1])) return bad("bands must not touch or overlap");
+            if (!std::isfinite(j.desired[b])) return bad("desired amplitude not finite");
+        }
+        for (int b = 0; b < j.nband; ++b)
+            if (!(j.weight[b] > 0.0) || !std::isfinite(j.weight[b])) return bad("weights must be positive and finite");
+        const int L = (j.numtaps & 1) ? (j.numtaps + 1) / 2 : j.numtaps / 2;
+        std::vector<int> cnt(j.nband);
+        if (remez_grid_counts(j.numtaps, j.nband, j.edges, density, cnt.data()) < L + 1) return bad("dense grid smaller than L + 1");
+        hj[q] = RemezJobHost{j.numtaps, j.nband, j.edges, j.desired, j.weight, j.h, j.ext, &j.status, &j.iterations, &j.delta};
+    }
+    MBFIR_TRY(ctx, ctx->solver->remez(njobs, hj.data(), density, maxiter));
+}
+int mbfir_fmp(mbfir_ctx* ctx, int l, const double* h_re, const double* h_im, double* out_re, double* out_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    if (l < 1 || l > 2047 || (l & 1) == 0 || !h_re || !out_re || !out_im) {
+        ctx->err = "fmp: filter length must be odd and at most 2047";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, ctx->solver->fmp(l, h_re, h_im, out_re, out_im));
 }
 int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));

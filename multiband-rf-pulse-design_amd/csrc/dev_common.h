@@ -185,4 +185,13 @@ void bloch_launch(const double* step, int ntime, const double* df, int nf, const
                   double* my, double* mz, hipStream_t st);
 void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st);
 
+// Batched Parks-McClellan exchange (remez.hip); RemezJobHost and remez_grid_counts are in solver.h.
+struct RemezJobHost;
+void remez_run(hipStream_t st, int njobs, const RemezJobHost* jobs, int density, int maxiter);
+
+// fmp.m (rf_tools/fmp.m:12-23) for odd l <= 2047: h (l complex, interleaved) -> (l + 1) / 2 complex taps (interleaved).  work holds
+// 6 * lp doubles, lp = 8 * 2^ceil(log2(l)).
+int fmp_lp(int l);
+void fmp_launch(const double* h_il, int l, double* work, double* hout, hipStream_t st);
+
 }  // namespace mbfir

@@ -53,6 +53,19 @@ struct SolveInfo {
     int gv_passes = 0, gtv_passes = 0;          // row-response passes G v and transposed passes G'v the solve launched (all iterations; a lock-step unit's count)
 };
 
+// Batched Parks-McClellan exchange (remez.hip): one workgroup per design, arguments checked by the caller.  status: 0 converged,
+// 1 maxiter reached (last iterate returned), 2 the exchange lost the alternation (no valid iterate).
+struct RemezJobHost {
+    int numtaps, nband;
+    const double *edges, *desired, *weight;    // 2 nband, 2 nband, nband
+    double* h;                                 // numtaps
+    double* ext;                               // L + 1 or null
+    int *status, *iterations;
+    double* delta;
+};
+// Dense-grid size and per-band point counts (counts: nband ints) of the grid k_remez builds.
+int remez_grid_counts(int numtaps, int nband, const double* edges, int density, int* counts);
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -93,6 +106,9 @@ public:
                      const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
                      int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
                      double* beta_im, double* winner_peak);
+    // Batched Parks-McClellan exchange (remez.hip, mbfir_remez_batch) and fmp.m (specfact.hip k_fmp, mbfir_fmp); arguments checked.
+    void remez(int njobs, const RemezJobHost* jobs, int density, int maxiter);
+    void fmp(int l, const double* h_re, const double* h_im, double* out_re, double* out_im);
     // kernel test hooks
     void test_gram(int m, int nt, int nw, const double* A, const double* d, double* out);
     void test_chol(int n, const double* H, double* out_l, double* out_m);

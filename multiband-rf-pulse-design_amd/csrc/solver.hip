@@ -4239,6 +4239,28 @@ long Solver::flip_search(int n, int nz, const double* c0_re, const double* c0_im
                            s_im, criterion, tie_high, peaks, beta_re, beta_im, winner_peak);
 }
 
+void Solver::remez(int njobs, const RemezJobHost* jobs, int density, int maxiter) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    remez_run(S.st, njobs, jobs, density, maxiter);
+}
+
+void Solver::fmp(int l, const double* h_re, const double* h_im, double* out_re, double* out_im) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int lp = fmp_lp(l), m = (l + 1) / 2;
+    std::vector<double> h(2 * (size_t)l), o(2 * (size_t)m);
+    for (int i = 0; i < l; ++i) { h[2 * i] = h_re[i]; h[2 * i + 1] = h_im ? h_im[i] : 0.0; }
+    DevBuf dh(h.size() * 8), dw(6 * (size_t)lp * 8), dout(o.size() * 8);
+    MBFIR_HIP(hipMemcpyAsync(dh.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, S.st));
+    fmp_launch(dh.as<double>(), l, dw.as<double>(), dout.as<double>(), S.st);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(o.data(), dout.p, o.size() * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    for (int i = 0; i < m; ++i) { out_re[i] = o[2 * i]; out_im[i] = o[2 * i + 1]; }
+}
+
 // fp64 peak microbenchmarks (roofline denominators; the local hardware guide lists no fp64
 // matrix peak).  One wave per SIMD, 8 independent accumulators, operands in registers.
 __global__ __launch_bounds__(256) void k_peak_mfma(double* out, int iters) {

@@ -112,4 +112,73 @@ void specfact_launch(const double* x, int n, double* work, double* hout, hipStre
     hipLaunchKernelGGL(k_specfact, dim3(nlanes), dim3(1024), 0, st, x, n, lp, loglp, reinterpret_cast<double2*>(work), hout, lane_bytes);
 }
 
+// fmp.m (rf_tools/fmp.m:12-23, called by dzmp.m): an equiripple linear-phase filter h (odd length l <= 2047) -> its minimum-phase
+// factor, (l + 1) / 2 taps.  The steps of K7 above from the spectrum on, with two differences: the zero-padded h itself is
+// transformed (:16-18), and the spectrum is lifted by its most negative real part before the root (:19,
+// hpfs = hpf - 1.000001 min(real(hpf))).  One workgroup, lp = 8 * 2^ceil(log2(l)) <= 16384.
+__global__ __launch_bounds__(1024) void k_fmp(const double2* __restrict__ h, int l, int lp, int loglp, double2* __restrict__ B0,
+                                              double* __restrict__ hout) {
+    __shared__ double sred[17];
+    double2* __restrict__ B1 = B0 + lp;
+    double2* __restrict__ B2 = B0 + 2 * lp;
+    const int tid = threadIdx.x, nt = blockDim.x;
+    const int pad_lo = (lp - l + 1) / 2;                 // ceil((lp-l)/2)                   :17
+    const int hlp = lp / 2;
+    for (int i = tid; i < lp; i += nt) {                 // B0 = fftshift(hp)                :17-18
+        const int t = ((i + hlp) & (lp - 1)) - pad_lo;
+        B0[i] = t >= 0 && t < l ? h[t] : make_double2(0, 0);
+    }
+    __syncthreads();
+    fft_inplace(B0, lp, loglp, -1);                      // hpf = fftshift(B0)               :18
+    double mn = INFINITY;                                // min(real(hpf)): exact whatever the order
+    for (int i = tid; i < lp; i += nt) mn = fmin(mn, B0[i].x);
+    mn = -block_max(-mn, sred);
+    const double lift = mn * 1.000001;                   // :19
+    for (int i = tid; i < lp; i += nt) {                 // xl = log(sqrt(abs(hpfs)))        :20, mag2mp.m
+        const double2 v = B0[(i + hlp) & (lp - 1)];
+        B1[i] = make_double2(log(sqrt(hypot(v.x - lift, v.y))), 0.0);
+    }
+    __syncthreads();
+    fft_inplace(B1, lp, loglp, -1);                      // xlf
+    for (int i = tid; i < lp; i += nt) {                 // keep DC and lp/2, double the positive, zero the negative
+        double2 v = B1[i];
+        if (i >= 1 && i < hlp) v = make_double2(2 * v.x, 2 * v.y);
+        else if (i > hlp) v = make_double2(0, 0);
+        B1[i] = v;
+    }
+    __syncthreads();
+    fft_inplace(B1, lp, loglp, +1);                      // xlaf * lp
+    const double inv = 1.0 / double(lp);
+    for (int i = tid; i < lp; i += nt) {                 // hpfmp = exp(xlaf)
+        const double2 v = B1[i];
+        double e = exp(v.x * inv), sn, cs;
+        sincos(v.y * inv, &sn, &cs);
+        B1[i] = make_double2(e * cs, e * sn);
+    }
+    __syncthreads();
+    for (int i = tid; i < lp; i += nt) {                 // fftshift(conj(hpfmp))            :21
+        const double2 v = B1[(i + hlp) & (lp - 1)];
+        B2[i] = make_double2(v.x, -v.y);
+    }
+    __syncthreads();
+    fft_inplace(B2, lp, loglp, +1);                      // hpmp = ifft(...)                 :21
+    for (int i = tid; i < (l + 1) / 2; i += nt) {        // hmp = hpmp(1:(l+1)/2)            :22
+        hout[2 * i] = B2[i].x * inv;
+        hout[2 * i + 1] = B2[i].y * inv;
+    }
+}
+
+int fmp_lp(int l) {
+    int p = 1;
+    while (p < l) p <<= 1;                               // 2^ceil(log2(l))                  :16
+    return 8 * p;
+}
+
+void fmp_launch(const double* h_il, int l, double* work, double* hout, hipStream_t st) {
+    int lp = fmp_lp(l), loglp = 0;
+    while ((1 << loglp) < lp) ++loglp;
+    hipLaunchKernelGGL(k_fmp, dim3(1), dim3(1024), 0, st, reinterpret_cast<const double2*>(h_il), l, lp, loglp,
+                       reinterpret_cast<double2*>(work), hout);
+}
+
 }  // namespace mbfir
