@@ -225,6 +225,12 @@ int mbfir_b2a(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, dou
 int mbfir_ab2rf(mbfir_ctx* ctx, int n, const double* a_re, const double* a_im, const double* b_re,
                 const double* b_im, double* rf_re, double* rf_im);
 int mbfir_b2rf(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
+/* mbfir_b2rf_batch: `rf(q, :) = b2rf(b(q, :))` for count independent polynomials of n taps in ONE launch, one workgroup each
+ *   (the inner loops of dzepse.m:39-49).  b and rf are row-major count x n planes (b_im may be NULL = 0); 2 <= n <= 2048,
+ *   count >= 1, else MBFIR_E_ARG.  The same chain as mbfir_b2rf (b2a.m:15-32 with its 8 n padding and max|bf| >= 1 rescale,
+ *   mag2mp.m:21-31, ab2rf.m:14-29) summed in another order: it agrees with mbfir_b2rf to rounding, not to the bit.  A pulse's
+ *   bits depend neither on count nor on its row: a row of a batch equals the same row alone. */
+int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
 
 /* ---- Forward simulation over off-resonance ----------------------------------------------
  * Cayley-Klein parameters (a, b) of the rotation an n-sample pulse produces at nx positions x
@@ -238,6 +244,12 @@ int mbfir_b2rf(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, do
  * abr.m's convention is b = -conj(b) of mode 0; mxy = 2 conj(a) b, mz = 1 - 2 |b|^2 (abr.m:11-14). */
 int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* g, int nx,
               const double* x, int mode, double* a_re, double* a_im, double* b_re, double* b_im);
+/* mbfir_abr2: `[a b] = abrm(rf, g, x, y)` of a 2D pulse (rf_tools/abrm.m:39-57): g = gx + i gy complex, one rotation about
+ *   (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample at every (x_k, y_j); a and b hold nx x ny entries, abrm's a(k, j) at
+ *   a[k * ny + j] (row-major).  gx NULL = 2 pi / n per sample as in mbfir_abr, gy NULL = 0.  abrm.m's joint rotation only
+ *   (mbfir_abr's mode 0); abr.m's convention is b = -conj(b) of this result (abr.m:26-32). */
+int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
+               const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im);
 
 /* Bloch-equation simulation with relaxation on the device: replaces the MEX bloch_simulation/blochC.c / blochH.c
  * (mexFunction :514-933 -> blochsimfz :422-512 -> blochsim :283-418, calcrotmat :171-236) that sim_rf_spectral.m:63-78

@@ -10,6 +10,10 @@
  *           rf_tools/mex5/minpeakrf.c's rules (flip: nflip x 2 one-based indices, second column 0 = single root, else a
  *           conjugate pair; singles take the low bits; start at z0's peak with index 0, replace on <=), scored through
  *           mbfir_b2rf's chain; at most 24 flip units, no progress printing
+ *     op 5: (B)              rf(q, :) = b2rf(B(q, :)) for every row of the count x n matrix B -> o1 = rf (count x n)
+ *           (mbfir_b2rf_batch: the inner loops of dzepse.m:39-49 in one launch)
+ *     op 6: (rf, g, x, y)    [a b] = abrm(rf, g, x, y), g complex (Re g = gx, Im g = gy; [] = 2 pi / n and 0)
+ *           -> o1 = a, o2 = b, each length(x) x length(y)                          (mbfir_abr2)
  *
  * It is the reference's own gateways (rf_tools/mex5/b2a.c:31-68, cabc2rf.c, abrx.c:35-62) with the compute call
  * swapped for the C ABI: same plain double planes, no static scratch, no MAXN cap.  Shares nothing with
@@ -119,13 +123,77 @@ static int minpeakrf_op(int n, double* zr, double* zi, const double* fl, int nfl
     return 0;
 }
 
-static double* out_plane(mxArray** slot, size_t len) {
-    *slot = mxCreateDoubleMatrix(1, len, mxREAL);
+static double* out_matrix(mxArray** slot, size_t m, size_t n) {
+    *slot = mxCreateDoubleMatrix(m, n, mxREAL);
 #if MX_HAS_INTERLEAVED_COMPLEX
     return mxGetDoubles(*slot);
 #else
     return mxGetPr(*slot);
 #endif
+}
+
+static double* out_plane(mxArray** slot, size_t len) {
+    return out_matrix(slot, 1, len);
+}
+
+/* column-major m x n (MATLAB) <-> row-major m x n (the C ABI) */
+static void transpose_cm(const double* src, size_t m, size_t n, double* dst) {
+    size_t i, j;
+    for (i = 0; i < m; ++i)
+        for (j = 0; j < n; ++j) dst[i * n + j] = src[i + j * m];
+}
+static void transpose_rm(const double* src, size_t m, size_t n, double* dst) {
+    size_t i, j;
+    for (i = 0; i < m; ++i)
+        for (j = 0; j < n; ++j) dst[i + j * m] = src[i * n + j];
+}
+
+/* b2rf of every row of B (op 5) */
+static int b2rf_rows_op(const mxArray* B, mxArray** plhs) {
+    size_t m = mxGetM(B), n = mxGetN(B), tot = m * n;
+    int rc;
+    double* w = (double*)mxCalloc(6 * tot, sizeof(double));
+    double *cr = w, *ci = w + tot, *br = w + 2 * tot, *bi = w + 3 * tot, *rr = w + 4 * tot, *ri = w + 5 * tot;
+    if (n < 2 || n > 2048 || m < 1) mexErrMsgTxt("b2rf rows: need 2..2048 columns and at least one row");
+    planes(B, tot, cr, ci);
+    transpose_cm(cr, m, n, br);
+    transpose_cm(ci, m, n, bi);
+    rc = mbfir_b2rf_batch(g_ctx, (int)n, (int)m, br, bi, rr, ri);
+    if (rc == 0) {
+        transpose_rm(rr, m, n, out_matrix(&plhs[0], m, n));
+        transpose_rm(ri, m, n, out_matrix(&plhs[1], m, n));
+    }
+    mxFree(w);
+    return rc;
+}
+
+/* abrm(rf, g, x, y) of a 2D pulse (op 6): rf n samples in rr / ri */
+static int abrm2_op(int n, const double* rr, const double* ri, const mxArray* g, const mxArray* xa, const mxArray* ya, mxArray** plhs) {
+    size_t nx = veclen(xa), ny = veclen(ya), tot, big;
+    int rc;
+    double *w, *gx = NULL, *gy = NULL, *x, *y, *ar, *ai, *bre, *bim;
+    if (nx < 1 || ny < 1) mexErrMsgTxt("abrm: empty x or y");
+    tot = nx * ny;
+    big = nx > ny ? nx : ny;
+    if ((size_t)n > big) big = (size_t)n;
+    w = (double*)mxCalloc(4 * big + 2 * (size_t)n + 4 * tot, sizeof(double));
+    x = w; y = w + big; ar = w + 4 * big + 2 * (size_t)n; ai = ar + tot; bre = ai + tot; bim = bre + tot;
+    planes(xa, nx, x, w + 2 * big);
+    planes(ya, ny, y, w + 2 * big);
+    if (!mxIsEmpty(g)) {
+        if (veclen(g) != (size_t)n) mexErrMsgTxt("abrm: g must have one entry per rf sample");
+        gx = w + 4 * big; gy = gx + n;
+        planes(g, (size_t)n, gx, gy);
+    }
+    rc = mbfir_abr2(g_ctx, n, rr, ri, gx, gy, (int)nx, x, (int)ny, y, ar, ai, bre, bim);
+    if (rc == 0) {
+        transpose_rm(ar, nx, ny, out_matrix(&plhs[0], nx, ny));
+        transpose_rm(ai, nx, ny, out_matrix(&plhs[1], nx, ny));
+        transpose_rm(bre, nx, ny, out_matrix(&plhs[2], nx, ny));
+        transpose_rm(bim, nx, ny, out_matrix(&plhs[3], nx, ny));
+    }
+    mxFree(w);
+    return rc;
 }
 
 void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -150,7 +218,12 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
         i2r = (double*)mxCalloc(n, sizeof(double)); i2i = (double*)mxCalloc(n, sizeof(double));
         planes(prhs[2], n, i2r, i2i);
     }
-    if (op == 4) {                                       /* minpeakrf(z, flip, bsf) */
+    if (op == 5) {                                       /* b2rf of every row of a matrix */
+        rc = b2rf_rows_op(prhs[1], plhs);
+    } else if (op == 6) {                                /* abrm(rf, g, x, y) */
+        if (nrhs < 5) mexErrMsgTxt("abrm: rf, g, x, y expected");
+        rc = abrm2_op((int)n, i1r, i1i, prhs[2], prhs[3], prhs[4], plhs);
+    } else if (op == 4) {                                /* minpeakrf(z, flip, bsf) */
         if (nrhs < 4 || (mxGetN(prhs[2]) != 2 && mxGetM(prhs[2]) > 0)) mexErrMsgTxt("minpeakrf: z, flip (nflip x 2), bsf expected");
         if (n + 1 > 1024) mexErrMsgTxt("z vector too long");
         o1r = out_plane(&plhs[0], n); o1i = out_plane(&plhs[1], n);

@@ -111,6 +111,8 @@ SYMBOLS = {
     "mbfir_b2a": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_ab2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_b2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_b2rf_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_abr2": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_flip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
                                     C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _dp]),
     "mbfir_remez_batch": (C.c_int, [C.c_void_p, C.POINTER(RemezJob), C.c_int, C.POINTER(RemezOpts)]),
@@ -435,6 +437,25 @@ def b2rf(bc, *, ctx=None):
     return rre + 1j * rim
 
 
+def b2rf_batch(B, *, ctx=None):
+    """`rf(q, :) = b2rf(B(q, :))` for every row of a (count, n) array in one device launch (mbfir_b2rf_batch), 2 <= n <= 2048.
+    Agrees with b2rf row by row to rounding; a row's result does not depend on the rest of the batch."""
+    B = np.asarray(B, dtype=np.complex128)
+    if B.ndim != 2:
+        raise ValueError("b2rf_batch: B must be a (count, n) array")
+    count, n = B.shape
+    if count < 1 or not 2 <= n <= 2048:
+        raise ValueError("b2rf_batch: need count >= 1 and 2 <= n <= 2048 (got %d x %d)" % (count, n))
+    ctx = ctx or get_context()
+    bre, bim = np.ascontiguousarray(B.real), np.ascontiguousarray(B.imag)
+    rre, rim = np.zeros((count, n)), np.zeros((count, n))
+    rc = load_library().mbfir_b2rf_batch(ctx._h, n, count, _ptr(bre), _ptr(bim), _ptr(rre), _ptr(rim))
+    if rc == E_ARG:
+        raise ValueError("b2rf_batch: %s" % ctx.last_error())
+    _check(ctx, rc)
+    return rre + 1j * rim
+
+
 def _pack_masks(masks):
     """nz x ncand 0/1 matrix (a column per candidate, fir_flip_zero's layout) -> ncand x ceil(nz / 32) uint32 words, bit j = row j."""
     m = np.asarray(masks).astype(bool)
@@ -561,10 +582,16 @@ def minpeakrf(z, flip, bsf, *, ctx=None):
     return zmin
 
 
-def abrm(rf, g=None, x=None, *, hard_pulse=False, ctx=None):
+def abrm(rf, g=None, x=None, y=None, *, hard_pulse=False, ctx=None):
     """`[a b] = abrm(rf, g, x)` (rf_tools/abrm.m): Cayley-Klein parameters of the pulse at positions x; with two
-    arguments the second one is x.  hard_pulse=True simulates the model ab2rf inverts exactly instead."""
+    arguments the second one is x.  hard_pulse=True simulates the model ab2rf inverts exactly instead.
+    `[a b] = abrm(rf, g, x, y)` (abrm.m:39-57): a 2D pulse, g complex (Re g the x gradient, Im g the y one), a and b of shape
+    (len(x), len(y)) (mbfir_abr2; abrm's joint rotation only)."""
     ctx = ctx or get_context()
+    if y is not None:
+        if x is None or hard_pulse:
+            raise ValueError("abrm: the 2D form takes rf, g, x, y (and no hard_pulse)")
+        return _abrm2(rf, g, x, y, ctx)
     if x is None:
         x, g = g, None
     rre, rim = _split(rf)
@@ -578,9 +605,31 @@ def abrm(rf, g=None, x=None, *, hard_pulse=False, ctx=None):
     return out[0] + 1j * out[1], out[2] + 1j * out[3]
 
 
-def abr(rf, g=None, x=None, *, ctx=None):
-    """`[a b] = abr(rf, g, x)` (rf_tools/abr.m:19-34): abrm with Le Roux's convention on beta, b = -conj(b)."""
-    a, b = abrm(rf, g, x, ctx=ctx)
+def _abrm2(rf, g, x, y, ctx):
+    rre, rim = _split(rf)
+    xv, yv = _vec(x), _vec(y)
+    if g is None:
+        gx = gy = None
+    else:
+        gre, gim = _split(g)
+        if len(gre) != len(rre):
+            raise ValueError("abrm: g must have one entry per rf sample")
+        gx, gy = gre, gim
+    if len(xv) < 1 or len(yv) < 1:
+        raise ValueError("abrm: x and y must not be empty")
+    out = [np.zeros((len(xv), len(yv))) for _ in range(4)]
+    rc = load_library().mbfir_abr2(ctx._h, len(rre), _ptr(rre), _ptr(rim), _ptr(gx) if gx is not None else None,
+                                   _ptr(gy) if gy is not None else None, len(xv), _ptr(xv), len(yv), _ptr(yv),
+                                   *[_ptr(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError("abrm: %s" % ctx.last_error())
+    _check(ctx, rc)
+    return out[0] + 1j * out[1], out[2] + 1j * out[3]
+
+
+def abr(rf, g=None, x=None, y=None, *, ctx=None):
+    """`[a b] = abr(rf, g, x[, y])` (rf_tools/abr.m:19-34): abrm with Le Roux's convention on beta, b = -conj(b)."""
+    a, b = abrm(rf, g, x, y, ctx=ctx)
     return a, -np.conj(b)
 
 
@@ -599,6 +648,9 @@ from .search import fir_ap, fir_qp, fir_min_order_linprog, fir_min_order_qprog_p
 from . import slrclassic    # noqa: E402  (conventional SLR pulses, dzrf.m and its designers; device remez and fmp)
 from .slrclassic import (remez, remez_batch, fmp, msinc, firls_lp, dzlp, dzls, dzmp, dzrf_batch,   # noqa: E402
                          sim_rf_scale)
+from . import epse          # noqa: E402  (dzepse.m spectral-spatial pulses and its helpers; device b2rf_batch)
+from .epse import (fftc, fftcp, dzbeta, verse, versec, ab2ex, ab2se, ab2inv, ab2sat, ab2st, dzepse,   # noqa: E402
+                   dzepse_batch)
 # `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
 # sys.modules (`from mbfir.dzrf import dzrf_mb`), and the function carries that module's public names for attribute access.
 dzrf = slrclassic.dzrf

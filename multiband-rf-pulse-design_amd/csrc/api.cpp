@@ -700,6 +700,23 @@ int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, c
         return MBFIR_E_ARG;
     MBFIR_TRY(ctx, ctx->solver->abr(n, rf_re, rf_im, g, nx, x, mode, a_re, a_im, b_re, b_im));
 }
+int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    if (n < 2 || n > 2048 || count < 1 || !b_re || !rf_re || !rf_im) {
+        ctx->err = "b2rf_batch: need 2 <= n <= 2048, count >= 1 and the b_re / rf arrays";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, ctx->solver->b2rf_batch(n, count, b_re, b_im, rf_re, rf_im));
+}
+int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
+               const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    if (n < 1 || nx < 1 || ny < 1 || (long)nx * ny > (1L << 30) || !rf_re || !rf_im || !x || !y || !a_re || !a_im || !b_re || !b_im) {
+        ctx->err = "abr2: need n, nx, ny >= 1 (nx ny <= 2^30) and the rf, x, y, a, b arrays";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, ctx->solver->abr2(n, rf_re, rf_im, gx, gy, nx, x, ny, y, a_re, a_im, b_re, b_im));
+}
 int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
                       const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
                       int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,

@@ -174,6 +174,13 @@ void specfact_launch(const double* x, int n, double* work, double* hout, hipStre
 void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work, double* a_il, hipStream_t st);
 void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
                     hipStream_t st);
+// Batched inverse SLR (slr.hip k_b2rf_batch; mbfir_b2rf_batch): count x n row-major host planes in and out (b_im may be null),
+// 2 <= n <= 2048, count >= 1; one workgroup per polynomial, one launch.
+void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const double* b_re, const double* b_im, double* rf_re,
+                        double* rf_im);
+// 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): nx x ny positions, outputs at k ny + j; gx null = 2 pi / n, gy null = 0.
+void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y, int ny,
+                     double* a_il, double* b_il, hipStream_t st);
 // Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:283-512).  step: ntime x 8 per-sample quantities.
 // Root-flip search (flip.hip): host side of mbfir_flip_search, arguments checked; returns the winner, -1 when no candidate has a
 // finite peak.

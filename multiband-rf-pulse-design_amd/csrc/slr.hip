@@ -4,6 +4,7 @@
 //           exact sincospi seed every 256 terms), elementwise steps in between
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
 #include "dev_common.h"
+#include <algorithm>
 
 namespace mbfir {
 
@@ -304,6 +305,224 @@ void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work,
 void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st) {
     if (n > SLR_MAXN) throw HipError("ab2rf: more than 2048 taps");
     hipLaunchKernelGGL(k_ab2rf, dim3(1), dim3(1024), 0, st, a_il, b_il, n, rf_il);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batched inverse SLR: count independent polynomials of n taps -> count RF pulses, rf = ab2rf(b2a(b), b) as the launches above
+// compute it (b2a.m:15-32 with its 8 n padding and the max|bf| >= 1 rescale, mag2mp.m:21-31, ab2rf.m:14-29), one workgroup per
+// polynomial (grid-stride over the batch), all in one launch.  The length-N = 8n transforms are direct, with k_dft_any's twiddles
+// (exact sincospi seed at every 256th term, rotation recurrence in between), but only over the terms that can be non-zero:
+//   bf   = fft(b, N)                 n inputs, N outputs
+//   xlfp = window(fft(xl))           N real inputs, outputs k <= N/2 (the window zeroes the rest)
+//   afa  = exp(ifft(xlfp))           N/2 + 1 inputs, N outputs
+//   aca  = fft(afa)(0 : n-1) / N     N inputs, n outputs (the only ones b2a.m keeps)
+// bf / xl / afa and xlfp live in a per-workgroup global scratch of 2N double2; b, alpha and the ab2rf ping-pong in LDS
+// (4 MAXN double2: A0 | B0 | A1 | B1, the DFT input tile borrowing A1 | B1 until the recursion starts).  Every reduction runs in a
+// fixed order inside the workgroup, so a pulse's bits depend on neither count nor its place in the batch.
+constexpr int B2RF_SEED = 256;
+
+// out(k), k < nout: sum_{j < nin} in[j] exp(sign 2 pi i j k / N), handed to emit(k, acc); tile: NT double2 of LDS
+template <int NT, bool REAL, class Emit>
+__device__ __forceinline__ void wg_dft(const double2* in, int nin, int N, int nout, int sign, double2* tile, Emit emit) {
+    const int tid = threadIdx.x;
+    for (int k0 = 0; k0 < nout; k0 += NT) {
+        const int k = k0 + tid;
+        const int kk = k < nout ? k : 0;
+        double sw, cw;
+        sincospi(2.0 * double(kk) / double(N), &sw, &cw);
+        sw *= sign;
+        double2 acc = make_double2(0, 0);
+        for (int j0 = 0; j0 < nin; j0 += NT) {
+            const int cnt = min(NT, nin - j0);
+            __syncthreads();
+            if (tid < cnt) tile[tid] = in[j0 + tid];
+            __syncthreads();
+            for (int q0 = 0; q0 < cnt; q0 += B2RF_SEED) {
+                const long ph = ((long)kk * (j0 + q0)) % N;          // exact phase of the run's first term
+                double s, c;
+                sincospi(2.0 * double(ph) / double(N), &s, &c);
+                s *= sign;
+                const int qe = min(cnt, q0 + B2RF_SEED);
+                for (int q = q0; q < qe; ++q) {
+                    const double2 v = tile[q];
+                    if (REAL) {
+                        acc.x += v.x * c;
+                        acc.y += v.x * s;
+                    } else {
+                        acc.x += v.x * c - v.y * s;
+                        acc.y += v.x * s + v.y * c;
+                    }
+                    const double cn = c * cw - s * sw;
+                    s = s * cw + c * sw;
+                    c = cn;
+                }
+            }
+        }
+        if (k < nout) emit(k, acc);
+    }
+}
+
+// b / rf: count x n double2 (row-major); work: gridDim.x x 2N double2
+template <int MAXN, int NT>
+__global__ __launch_bounds__(NT) void k_b2rf_batch(const double2* __restrict__ b, int n, int count, double2* __restrict__ work,
+                                                   double2* __restrict__ rf) {
+    __shared__ double2 L[4 * MAXN];
+    __shared__ double red[17];
+    __shared__ double2 cs[2];                             // (c, 0), s of the current recursion step
+    const int N = 8 * n, tid = threadIdx.x;
+    double2* A0 = L;
+    double2* B0 = L + MAXN;
+    double2* tile = L + 2 * MAXN;                         // NT <= 2 MAXN
+    double2* X0 = work + (size_t)blockIdx.x * 2 * N;
+    double2* X1 = X0 + N;
+    const double invN = 1.0 / N;
+    for (int p = blockIdx.x; p < count; p += gridDim.x) {
+        __syncthreads();                                  // the previous pulse's recursion is done with L
+        for (int i = tid; i < n; i += NT) B0[i] = b[(size_t)p * n + i];
+        double m = 0;
+        wg_dft<NT, false>(B0, n, N, N, -1, tile, [&](int k, double2 v) {         // bf = fft(bcp)         (b2a.m:22-23)
+            X0[k] = v;
+            m = fmax(m, hypot(v.x, v.y));
+        });
+        m = block_max(m, red);
+        const double sc = m >= 1.0 ? 1.0 / (1e-8 + m) : 1.0;                    // (b2a.m:25-28)
+        for (int k = tid; k < N; k += NT) {                                     // xl (mag2mp.m:24); each k is this thread's own
+            const double re = X0[k].x * sc, im = X0[k].y * sc;
+            X0[k] = make_double2(log(sqrt(1.0 - (re * re + im * im))), 0.0);
+        }
+        wg_dft<NT, true>(X0, N, N, N / 2 + 1, -1, tile, [&](int k, double2 v) {  // xlfp               (mag2mp.m:25-29)
+            const double g = (k == 0 || k == N / 2) ? 1.0 : 2.0;
+            X1[k] = make_double2(g * v.x, g * v.y);
+        });
+        wg_dft<NT, false>(X1, N / 2 + 1, N, N, +1, tile, [&](int k, double2 v) { // afa = exp(ifft(xlfp)) (mag2mp.m:30-31)
+            double s, c;
+            sincos(v.y * invN, &s, &c);
+            const double e = exp(v.x * invN);
+            X0[k] = make_double2(e * c, e * s);
+        });
+        wg_dft<NT, false>(X0, N, N, n, -1, tile, [&](int k, double2 v) {         // aca(n:-1:1)        (b2a.m:30-32)
+            A0[n - 1 - k] = make_double2(v.x * invN, v.y * invN);
+        });
+        __syncthreads();
+        // inverse SLR recursion (ab2rf.m:14-29), k_ab2rf's arithmetic
+        int cur = 0;
+        for (int i = n; i >= 1; --i) {
+            double2* Ac = L + 2 * cur * MAXN;
+            double2* Bc = Ac + MAXN;
+            double2* An = L + 2 * (cur ^ 1) * MAXN;
+            double2* Bn = An + MAXN;
+            if (tid == 0) {
+                const double2 ai = Ac[i - 1], bi = Bc[i - 1];
+                const double den = ai.x * ai.x + ai.y * ai.y;
+                const double2 q = make_double2((bi.x * ai.x + bi.y * ai.y) / den, (bi.y * ai.x - bi.x * ai.y) / den);   // b / a
+                const double c = sqrt(1.0 / (1.0 + (q.x * q.x + q.y * q.y)));
+                const double2 s = make_double2(c * q.x, -c * q.y);                                                      // conj(c b / a)
+                const double theta = atan2(hypot(s.x, s.y), c), psi = atan2(s.y, s.x);
+                rf[(size_t)p * n + i - 1] = make_double2(2 * theta * cos(psi), 2 * theta * sin(psi));
+                cs[0] = make_double2(c, 0);
+                cs[1] = s;
+            }
+            __syncthreads();
+            const double c = cs[0].x;
+            const double2 s = cs[1], ms = make_double2(-s.x, s.y);                                                      // -conj(s)
+            for (int k = tid; k < i; k += NT) {
+                const double2 ak = Ac[k], bk = Bc[k];
+                const double2 sb = cmul2(s, bk), msa = cmul2(ms, ak);
+                if (k >= 1) An[k - 1] = make_double2(c * ak.x + sb.x, c * ak.y + sb.y);     // ac = acn(2:i)
+                if (k < i - 1) Bn[k] = make_double2(msa.x + c * bk.x, msa.y + c * bk.y);    // bc = bcn(1:i-1)
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+    }
+}
+
+struct SlrBuf {
+    void* p = nullptr;
+    explicit SlrBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
+    ~SlrBuf() { if (p) hipFree(p); }
+    template <class T> T* as() { return reinterpret_cast<T*>(p); }
+};
+
+template <int MAXN, int NT>
+static void b2rf_batch_launch(int device, hipStream_t st, int n, int count, const double2* b, double2* rf) {
+    int ncu = 0, per = 0;
+    MBFIR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_b2rf_batch<MAXN, NT>, NT, 0));
+    const int grid = std::max(1, std::min(count, std::max(per, 1) * ncu));    // resident workgroups bound the scratch
+    SlrBuf work((size_t)grid * 2 * 8 * n * sizeof(double2));
+    hipLaunchKernelGGL((k_b2rf_batch<MAXN, NT>), dim3(grid), dim3(NT), 0, st, b, n, count, work.as<double2>(), rf);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipStreamSynchronize(st));                  // the scratch is freed on return
+}
+
+// Host side of mbfir_b2rf_batch (arguments checked): host planes in, host planes out.
+void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const double* b_re, const double* b_im, double* rf_re,
+                        double* rf_im) {
+    if (n < 2 || n > SLR_MAXN || count < 1) throw HipError("b2rf_batch: bad sizes");
+    const size_t tot = (size_t)n * count;
+    std::vector<double2> h(tot);
+    for (size_t i = 0; i < tot; ++i) h[i] = make_double2(b_re[i], b_im ? b_im[i] : 0.0);
+    SlrBuf db(tot * sizeof(double2)), drf(tot * sizeof(double2));
+    MBFIR_HIP(hipMemcpyAsync(db.p, h.data(), tot * sizeof(double2), hipMemcpyHostToDevice, st));
+    const double2* b = db.as<double2>();
+    double2* rf = drf.as<double2>();
+    if (n <= 128) b2rf_batch_launch<128, 256>(device, st, n, count, b, rf);
+    else if (n <= 512) b2rf_batch_launch<512, 256>(device, st, n, count, b, rf);
+    else if (n <= 1024) b2rf_batch_launch<1024, 512>(device, st, n, count, b, rf);
+    else b2rf_batch_launch<2048, 512>(device, st, n, count, b, rf);
+    MBFIR_HIP(hipMemcpyAsync(h.data(), drf.p, tot * sizeof(double2), hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    for (size_t i = 0; i < tot; ++i) { rf_re[i] = h[i].x; rf_im[i] = h[i].y; }
+}
+
+// 2D forward simulation, abrm.m:39-57: one thread per (x_k, y_j), output index k ny + j; one rotation about
+// (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample, k_abr's mode-0 arithmetic.  rf, gx, gy staged through LDS 256 samples at a time;
+// gx null = 2 pi / n per sample, gy null = 0.
+__global__ __launch_bounds__(256) void k_abr2(const double* __restrict__ rf_il, const double* __restrict__ gx,
+                                              const double* __restrict__ gy, int n, const double* __restrict__ x, int nx,
+                                              const double* __restrict__ y, int ny, double* __restrict__ a_il,
+                                              double* __restrict__ b_il) {
+    __shared__ double2 srf[256];
+    __shared__ double sgx[256], sgy[256];
+    const long i = (long)blockIdx.x * 256 + threadIdx.x, tot = (long)nx * ny;
+    const bool live = i < tot;
+    const long kx = live ? i / ny : 0;
+    const double xv = x[kx], yv = y[live ? i - kx * ny : 0];
+    double2 a = make_double2(1, 0), b = make_double2(0, 0);
+    const double g0 = 2.0 * M_PI / n;
+    for (int m0 = 0; m0 < n; m0 += 256) {
+        __syncthreads();
+        const int mm = m0 + threadIdx.x;
+        if (mm < n) {
+            srf[threadIdx.x] = make_double2(rf_il[2 * mm], rf_il[2 * mm + 1]);
+            sgx[threadIdx.x] = gx ? gx[mm] : g0;
+            sgy[threadIdx.x] = gy ? gy[mm] : 0.0;
+        }
+        __syncthreads();
+        const int cnt = min(256, n - m0);
+        for (int q = 0; q < cnt; ++q) {
+            const double2 r = srf[q];
+            const double om = xv * sgx[q] + yv * sgy[q];
+            const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
+            double sn, cs;
+            sincos(0.5 * phi, &sn, &cs);
+            const double inv = phi > 0 ? sn / phi : 0.0;
+            const double2 av = make_double2(cs, -om * inv);
+            const double2 bv = make_double2(r.y * inv, -r.x * inv);                 // -i (n1 + i n2) sin
+            const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
+                                            av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
+            const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
+                                            bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
+            a = an; b = bn;
+        }
+    }
+    if (live) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
+}
+void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y, int ny,
+                     double* a_il, double* b_il, hipStream_t st) {
+    hipLaunchKernelGGL(k_abr2, dim3(cdiv((long)nx * ny, 256)), dim3(256), 0, st, rf_il, gx, gy, n, x, nx, y, ny, a_il, b_il);
 }
 
 }  // namespace mbfir

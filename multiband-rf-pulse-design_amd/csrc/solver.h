@@ -96,6 +96,11 @@ public:
     // Forward simulation (slr.hip k_abr): a, b over nx positions; g null = 2 pi / n per sample; mode 0 abrm.m, 1 hard pulse.
     void abr(int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x, int mode,
              double* a_re, double* a_im, double* b_re, double* b_im);
+    // Batched inverse SLR (slr.hip k_b2rf_batch): count polynomials of n taps, row-major; b_im may be null.
+    void b2rf_batch(int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
+    // 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j; gx null = 2 pi / n, gy null = 0.
+    void abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
+              const double* y, double* a_re, double* a_im, double* b_re, double* b_im);
     // Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:422-512).  m*: in = initial magnetisation at the first
     // sample of every (frequency, position) block, out = the result; nfreq * npos * (mode & 2 ? ntime : 1) doubles each.
     void bloch(int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy, const double* gz,

@@ -4193,6 +4193,35 @@ void Solver::abr(int n, const double* rf_re, const double* rf_im, const double* 
     for (size_t i = 0; i < X; ++i) { a_re[i] = oa[2 * i]; a_im[i] = oa[2 * i + 1]; b_re[i] = ob[2 * i]; b_im[i] = ob[2 * i + 1]; }
 }
 
+void Solver::b2rf_batch(int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    slr_b2rf_batch_run(S.device, S.st, n, count, b_re, b_im, rf_re, rf_im);
+}
+
+void Solver::abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
+                  const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const size_t N = (size_t)n, P = (size_t)nx * ny;
+    DevBuf drf(2 * N * 8), dgx(N * 8), dgy(N * 8), dx((size_t)nx * 8), dy((size_t)ny * 8), da(2 * P * 8), db(2 * P * 8);
+    std::vector<double> h(2 * N), oa(2 * P), ob(2 * P);
+    for (size_t i = 0; i < N; ++i) { h[2 * i] = rf_re[i]; h[2 * i + 1] = rf_im[i]; }
+    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, S.st));
+    if (gx) MBFIR_HIP(hipMemcpyAsync(dgx.p, gx, N * 8, hipMemcpyHostToDevice, S.st));
+    if (gy) MBFIR_HIP(hipMemcpyAsync(dgy.p, gy, N * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dx.p, x, (size_t)nx * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dy.p, y, (size_t)ny * 8, hipMemcpyHostToDevice, S.st));
+    slr_abr2_launch(drf.as<double>(), gx ? dgx.as<double>() : nullptr, gy ? dgy.as<double>() : nullptr, n, dx.as<double>(), nx,
+                    dy.as<double>(), ny, da.as<double>(), db.as<double>(), S.st);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * P * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * P * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    for (size_t i = 0; i < P; ++i) { a_re[i] = oa[2 * i]; a_im[i] = oa[2 * i + 1]; b_re[i] = ob[2 * i]; b_im[i] = ob[2 * i + 1]; }
+}
+
 void Solver::bloch(int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy, const double* gz,
                    const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
                    const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
