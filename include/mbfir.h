@@ -232,6 +232,18 @@ int mbfir_b2rf(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, do
  *   bits depend neither on count nor on its row: a row of a batch equals the same row alone. */
 int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
 
+/* mbfir_slr2d_batch: the 2D inverse SLR of dzepse.m:39-49 for count complex m x n matrices r in one call (rows: spatial samples,
+ *   columns: spectral samples; r and the result row-major count x m x n planes, r_im may be NULL = 0).  Returns rn2, radians per
+ *   sample: stage 1 rn1(q, :) = b2rf(r(q, :)); per column theta = rn1(:, j) the hard-pulse beta
+ *   s = sin(|theta| / 2) exp(-i arg theta) (dzepse's sin(conj(theta) / 2) for a real theta) and
+ *   p2_j = fftcp(s, 2m)(m/2 + 1 : 3m/2) / 2m; stage 2 rn2(:, j) = conj(b2rf(p2_j)).  The b2rf steps are mbfir_b2rf_batch's; the
+ *   intermediates stay on the device (one upload, one download).  2 <= n <= 2048, 2 <= m <= 2048 with m even, count >= 1 and
+ *   count max(m, n) < 2^31, else MBFIR_E_ARG.  A matrix's bits depend neither on count nor on its place in the batch.
+ *   literal = 1 takes dzepse.m:45's s = sin(conj(theta) / 2) instead (dzepse's own stage-1 angles are not real: parity with it);
+ *   literal must be 0 or 1. */
+int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+                      double* out_im, int literal);
+
 /* ---- Forward simulation over off-resonance ----------------------------------------------
  * Cayley-Klein parameters (a, b) of the rotation an n-sample pulse produces at nx positions x
  * (rf in radians per sample; g: n per-sample gradient / time weights, NULL = 2 pi / n each, so that x counts

@@ -112,6 +112,7 @@ SYMBOLS = {
     "mbfir_ab2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_b2rf": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_b2rf_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_slr2d_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int]),
     "mbfir_abr2": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_flip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
                                     C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _dp]),
@@ -456,6 +457,30 @@ def b2rf_batch(B, *, ctx=None):
     return rre + 1j * rim
 
 
+def slr2d_batch(R, *, literal=False, ctx=None):
+    """The 2D inverse SLR of dzepse.m:39-49 for every matrix of a (count, m, n) complex array in one call (mbfir_slr2d_batch):
+    rows are spatial samples, columns spectral samples; 2 <= n <= 2048, 2 <= m <= 2048, m even.  Returns rn2 (count, m, n) in
+    radians per sample.  The middle stage takes the hard-pulse beta sin(|theta| / 2) exp(-i arg theta) of every stage-1 angle,
+    which is dzepse's sin(conj(theta) / 2) for a real theta; literal=True takes dzepse's form itself (its own stage-1 angles are
+    not real).  A matrix's result does not depend on the rest of the batch."""
+    R = np.asarray(R, dtype=np.complex128)
+    if R.ndim != 3:
+        raise ValueError("slr2d_batch: R must be a (count, m, n) array")
+    count, m, n = R.shape
+    if count < 1 or not 2 <= n <= 2048 or not 2 <= m <= 2048 or m % 2:
+        raise ValueError("slr2d_batch: need count >= 1, 2 <= n <= 2048 and an even 2 <= m <= 2048 (got %d x %d x %d)"
+                         % (count, m, n))
+    ctx = ctx or get_context()
+    rre, rim = np.ascontiguousarray(R.real), np.ascontiguousarray(R.imag)
+    ore, oim = np.zeros((count, m, n)), np.zeros((count, m, n))
+    rc = load_library().mbfir_slr2d_batch(ctx._h, m, n, count, _ptr(rre), _ptr(rim), _ptr(ore), _ptr(oim),
+                                                  int(bool(literal)))
+    if rc == E_ARG:
+        raise ValueError("slr2d_batch: %s" % ctx.last_error())
+    _check(ctx, rc)
+    return ore + 1j * oim
+
+
 def _pack_masks(masks):
     """nz x ncand 0/1 matrix (a column per candidate, fir_flip_zero's layout) -> ncand x ceil(nz / 32) uint32 words, bit j = row j."""
     m = np.asarray(masks).astype(bool)
@@ -651,6 +676,8 @@ from .slrclassic import (remez, remez_batch, fmp, msinc, firls_lp, dzlp, dzls, d
 from . import epse          # noqa: E402  (dzepse.m spectral-spatial pulses and its helpers; device b2rf_batch)
 from .epse import (fftc, fftcp, dzbeta, verse, versec, ab2ex, ab2se, ab2inv, ab2sat, ab2st, dzepse,   # noqa: E402
                    dzepse_batch)
+from . import ssmb          # noqa: E402  (multiband spectral-spatial pulses: dzrf_mb's spectral beta, device 2D SLR)
+from .ssmb import dzss_mb, dzss_mb_batch, fold_bands   # noqa: E402
 # `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
 # sys.modules (`from mbfir.dzrf import dzrf_mb`), and the function carries that module's public names for attribute access.
 dzrf = slrclassic.dzrf

@@ -708,6 +708,17 @@ int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const
     }
     MBFIR_TRY(ctx, ctx->solver->b2rf_batch(n, count, b_re, b_im, rf_re, rf_im));
 }
+int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+                      double* out_im, int literal) {
+    if (!ctx) return MBFIR_E_ARG;
+    if (n < 2 || n > 2048 || m < 2 || m > 2048 || m % 2 || count < 1 || (long)count * (m > n ? m : n) > 2147483647L || !r_re ||
+        !out_re || !out_im || (literal != 0 && literal != 1)) {
+        ctx->err = "slr2d_batch: need 2 <= n <= 2048, 2 <= m <= 2048 with m even, count >= 1 (count max(m, n) < 2^31), the "
+                   "r_re / out arrays and literal 0 or 1";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, ctx->solver->slr2d_batch(m, n, count, r_re, r_im, out_re, out_im, literal));
+}
 int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
                const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
     if (!ctx) return MBFIR_E_ARG;

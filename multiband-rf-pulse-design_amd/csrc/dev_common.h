@@ -178,6 +178,10 @@ void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x
 // 2 <= n <= 2048, count >= 1; one workgroup per polynomial, one launch.
 void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const double* b_re, const double* b_im, double* rf_re,
                         double* rf_im);
+// 2D inverse SLR (slr.hip k_b2rf_batch, k_slr2d_mid, k_slr2d_out; mbfir_slr2d_batch): count x m x n row-major host planes in and
+// out (r_im may be null), 2 <= m, n <= 2048, m even; one upload, one download.  literal: dzepse.m's sin(conj(theta) / 2) middle stage.
+void slr_slr2d_batch_run(int device, hipStream_t st, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+                         double* out_im, int literal);
 // 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): nx x ny positions, outputs at k ny + j; gx null = 2 pi / n, gy null = 0.
 void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y, int ny,
                      double* a_il, double* b_il, hipStream_t st);

@@ -477,6 +477,162 @@ void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const doub
     for (size_t i = 0; i < tot; ++i) { rf_re[i] = h[i].x; rf_im[i] = h[i].y; }
 }
 
+// ------------------------------------------------------------------------------------------------
+// 2D inverse SLR (dzepse.m:39-49) for count complex m x n matrices r (rows: spatial samples, columns: spectral samples), all on one
+// stream with the intermediates on the device:
+//   stage 1   rn1(q, :) = b2rf(r(q, :))                   k_b2rf_batch, count m polynomials of n taps
+//   middle    p2_j = fftcp(s_j, 2m)(m/2 : 3m/2 - 1) / 2m  k_slr2d_mid, s_j(q) = sin(|rn1(q, j)| / 2) exp(-i arg rn1(q, j))
+//                                                         (literal: dzepse.m:45's sin(conj(rn1(q, j)) / 2))
+//   stage 2   rf2(j, :) = b2rf(p2_j)                      k_b2rf_batch, count n polynomials of m taps
+//   rn2(q, j) = conj(rf2(j, q))                            k_slr2d_out
+// s is the beta of a hard pulse of angle |theta| about the axis arg theta; for a real theta it is dzepse's sin(conj(theta) / 2).
+// dzepse's own stage-1 angles are not real (its spatial profile carries a half-sample phase ramp), and there the two forms differ
+// by up to 4e-3 of max|rf|: `literal` selects dzepse's form, for parity with it.
+
+// The tiers of slr_b2rf_batch_run, split into sizing and an enqueue on a caller-owned scratch (no synchronisation).
+template <int MAXN, int NT>
+static int b2rf_tier_grid(int device, int count) {
+    int ncu = 0, per = 0;
+    MBFIR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
+    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_b2rf_batch<MAXN, NT>, NT, 0));
+    return std::max(1, std::min(count, std::max(per, 1) * ncu));
+}
+static int b2rf_batch_grid(int device, int n, int count) {
+    if (n <= 128) return b2rf_tier_grid<128, 256>(device, count);
+    if (n <= 512) return b2rf_tier_grid<512, 256>(device, count);
+    if (n <= 1024) return b2rf_tier_grid<1024, 512>(device, count);
+    return b2rf_tier_grid<2048, 512>(device, count);
+}
+// work: grid x 2 (8 n) double2
+static void b2rf_batch_enqueue(hipStream_t st, int grid, int n, int count, const double2* b, double2* work, double2* rf) {
+    if (n <= 128) hipLaunchKernelGGL((k_b2rf_batch<128, 256>), dim3(grid), dim3(256), 0, st, b, n, count, work, rf);
+    else if (n <= 512) hipLaunchKernelGGL((k_b2rf_batch<512, 256>), dim3(grid), dim3(256), 0, st, b, n, count, work, rf);
+    else if (n <= 1024) hipLaunchKernelGGL((k_b2rf_batch<1024, 512>), dim3(grid), dim3(512), 0, st, b, n, count, work, rf);
+    else hipLaunchKernelGGL((k_b2rf_batch<2048, 512>), dim3(grid), dim3(512), 0, st, b, n, count, work, rf);
+    MBFIR_HIP(hipGetLastError());
+}
+
+// Middle stage, one workgroup per (matrix, column) w = c n + j (grid-stride).  fftcp pads s with m/2 zeros on each side, so the
+// middle m samples of its centred 2m-point DFT are the direct centred sum over the m non-zero inputs:
+//   p2_j(r) = 1/2m sum_q s(q) exp(-2 pi i (q - m/2)(r - m/2) / 2m),  q, r = 0 .. m-1.
+// The twiddle index (q - m/2)(r - m/2) is reduced mod 2m in exact integer steps; the table holds exp(-i pi p / m) for p < m (one
+// sincospi each, in LDS), and p >= m is the negated entry p - m.  The column gather (m loads of stride n) is read once into LDS
+// against m^2 complex products; the output row p2_j is written contiguously, which is stage 2's row-major layout.
+template <int MAXM, int NT>
+__global__ __launch_bounds__(NT) void k_slr2d_mid(const double2* __restrict__ rn1, int m, int n, long total, int literal,
+                                                  double2* __restrict__ p2) {
+    __shared__ double2 tw[MAXM];
+    __shared__ double2 s[MAXM];
+    const int tid = threadIdx.x, M2 = 2 * m, half = m / 2;
+    for (int p = tid; p < m; p += NT) {
+        double sn, cs;
+        sincospi(double(p) / double(m), &sn, &cs);
+        tw[p] = make_double2(cs, -sn);
+    }
+    const double inv = 1.0 / double(M2);
+    for (long w = blockIdx.x; w < total; w += gridDim.x) {
+        const long c = w / n;
+        const double2* col = rn1 + (size_t)c * m * n + (w - c * n);
+        __syncthreads();                                  // the previous column's sums are done with s
+        for (int q = tid; q < m; q += NT) {
+            const double2 t = col[(size_t)q * n];
+            const double th = hypot(t.x, t.y);
+            double2 v = make_double2(0, 0);
+            if (literal) {                                    // sin(a + i b) = sin a cosh b + i cos a sinh b, a + i b = conj(t) / 2
+                double sa, ca;
+                sincos(0.5 * t.x, &sa, &ca);
+                v = make_double2(sa * cosh(0.5 * t.y), -(ca * sinh(0.5 * t.y)));
+            } else if (th > 0) {
+                const double sh = sin(0.5 * th);
+                v = make_double2(sh * (t.x / th), -(sh * (t.y / th)));
+            }
+            s[q] = v;
+        }
+        __syncthreads();
+        double2* out = p2 + (size_t)w * m;
+        for (int r = tid; r < m; r += NT) {
+            const int b = r - half;                                   // in [-m/2, m/2)
+            const int step = b < 0 ? b + M2 : b;                      // b mod 2m
+            int ph = (int)((((long)(-half) * b) % M2 + M2) % M2);     // (q - m/2)(r - m/2) mod 2m at q = 0
+            double2 acc = make_double2(0, 0);
+            for (int q = 0; q < m; ++q) {
+                const double2 v = s[q];
+                const bool neg = ph >= m;
+                const double2 e = tw[neg ? ph - m : ph];
+                const double ex = neg ? -e.x : e.x, ey = neg ? -e.y : e.y;
+                acc.x += v.x * ex - v.y * ey;
+                acc.y += v.x * ey + v.y * ex;
+                ph += step;
+                if (ph >= M2) ph -= M2;
+            }
+            out[r] = make_double2(acc.x * inv, acc.y * inv);
+        }
+    }
+}
+
+// rn2(c, q, j) = conj(rf2(c, j, q)): count n x m matrices -> m x n, 32 x 32 tiles through LDS so that both the reads and the
+// writes run along rows (grid-stride over the tiles).
+__global__ __launch_bounds__(256) void k_slr2d_out(const double2* __restrict__ rf2, int m, int n, long ntile, double2* __restrict__ rn2) {
+    __shared__ double2 t[32][33];
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int tm = (m + 31) / 32, tn = (n + 31) / 32;
+    for (long w = blockIdx.x; w < ntile; w += gridDim.x) {
+        const long c = w / ((long)tm * tn);
+        const int rest = (int)(w - c * tm * tn), bj = rest / tm, bq = rest - bj * tm;
+        const double2* src = rf2 + (size_t)c * n * m;
+        double2* dst = rn2 + (size_t)c * m * n;
+        __syncthreads();
+        for (int y = ty; y < 32; y += 8) {
+            const int j = 32 * bj + y, q = 32 * bq + tx;
+            if (j < n && q < m) t[y][tx] = src[(size_t)j * m + q];
+        }
+        __syncthreads();
+        for (int y = ty; y < 32; y += 8) {
+            const int q = 32 * bq + y, j = 32 * bj + tx;
+            if (q < m && j < n) {
+                const double2 v = t[tx][y];
+                dst[(size_t)q * n + j] = make_double2(v.x, -v.y);
+            }
+        }
+    }
+}
+
+template <int MAXM>
+static void slr2d_mid_enqueue(hipStream_t st, const double2* rn1, int m, int n, long total, int literal, double2* p2) {
+    const int grid = (int)std::min(total, 1L << 20);
+    hipLaunchKernelGGL((k_slr2d_mid<MAXM, 256>), dim3(grid), dim3(256), 0, st, rn1, m, n, total, literal, p2);
+    MBFIR_HIP(hipGetLastError());
+}
+
+// Host side of mbfir_slr2d_batch (arguments checked): host planes in (count x m x n row-major), host planes out (same layout).
+void slr_slr2d_batch_run(int device, hipStream_t st, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+                         double* out_im, int literal) {
+    if (n < 2 || n > SLR_MAXN || m < 2 || m > SLR_MAXN || m % 2 || count < 1 || (long)count * std::max(m, n) > INT32_MAX)
+        throw HipError("slr2d_batch: bad sizes");
+    const size_t tot = (size_t)m * n * count;
+    std::vector<double2> h(tot);
+    for (size_t i = 0; i < tot; ++i) h[i] = make_double2(r_re[i], r_im ? r_im[i] : 0.0);
+    const int rows1 = count * m, rows2 = count * n;
+    const int g1 = b2rf_batch_grid(device, n, rows1), g2 = b2rf_batch_grid(device, m, rows2);
+    SlrBuf d0(tot * sizeof(double2)), d1(tot * sizeof(double2));
+    SlrBuf work(std::max((size_t)g1 * 16 * n, (size_t)g2 * 16 * m) * sizeof(double2));
+    double2* x0 = d0.as<double2>();
+    double2* x1 = d1.as<double2>();
+    MBFIR_HIP(hipMemcpyAsync(x0, h.data(), tot * sizeof(double2), hipMemcpyHostToDevice, st));
+    b2rf_batch_enqueue(st, g1, n, rows1, x0, work.as<double2>(), x1);                 // rn1: count m rows of n
+    if (m <= 128) slr2d_mid_enqueue<128>(st, x1, m, n, rows2, literal, x0);           // p2: count n rows of m
+    else if (m <= 512) slr2d_mid_enqueue<512>(st, x1, m, n, rows2, literal, x0);
+    else slr2d_mid_enqueue<2048>(st, x1, m, n, rows2, literal, x0);
+    b2rf_batch_enqueue(st, g2, m, rows2, x0, work.as<double2>(), x1);                 // rf2: count n rows of m
+    const long ntile = (long)count * ((m + 31) / 32) * ((n + 31) / 32);
+    hipLaunchKernelGGL(k_slr2d_out, dim3((int)std::min(ntile, 1L << 20)), dim3(256), 0, st, x1, m, n, ntile, x0);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(h.data(), x0, tot * sizeof(double2), hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));                  // the buffers are freed on return
+    MBFIR_HIP(hipGetLastError());
+    for (size_t i = 0; i < tot; ++i) { out_re[i] = h[i].x; out_im[i] = h[i].y; }
+}
+
 // 2D forward simulation, abrm.m:39-57: one thread per (x_k, y_j), output index k ny + j; one rotation about
 // (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample, k_abr's mode-0 arithmetic.  rf, gx, gy staged through LDS 256 samples at a time;
 // gx null = 2 pi / n per sample, gy null = 0.

@@ -98,6 +98,8 @@ public:
              double* a_re, double* a_im, double* b_re, double* b_im);
     // Batched inverse SLR (slr.hip k_b2rf_batch): count polynomials of n taps, row-major; b_im may be null.
     void b2rf_batch(int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
+    // 2D inverse SLR (slr.hip, dzepse.m:39-49): count m x n matrices, row-major; r_im may be null; literal: dzepse's middle stage.
+    void slr2d_batch(int m, int n, int count, const double* r_re, const double* r_im, double* out_re, double* out_im, int literal);
     // 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j; gx null = 2 pi / n, gy null = 0.
     void abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
               const double* y, double* a_re, double* a_im, double* b_re, double* b_im);

@@ -4199,6 +4199,13 @@ void Solver::b2rf_batch(int n, int count, const double* b_re, const double* b_im
     slr_b2rf_batch_run(S.device, S.st, n, count, b_re, b_im, rf_re, rf_im);
 }
 
+void Solver::slr2d_batch(int m, int n, int count, const double* r_re, const double* r_im, double* out_re, double* out_im,
+                         int literal) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    slr_slr2d_batch_run(S.device, S.st, m, n, count, r_re, r_im, out_re, out_im, literal);
+}
+
 void Solver::abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
                   const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
     Impl& S = *impl;
