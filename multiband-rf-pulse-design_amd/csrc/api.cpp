@@ -2,6 +2,7 @@
 // Each entry point = host assembly (assemble.cpp) -> device IPM (solver.hip) -> tap extraction.
 #include "../../include/mbfir.h"
 #include "program.h"
+#include "pulse.h"
 #include "solver.h"
 #include <chrono>
 #include <cmath>
@@ -21,6 +22,7 @@ using namespace mbfir;
 
 struct mbfir_ctx {
     std::unique_ptr<Solver> solver;
+    int device = 0;                 // the solver's device, on which the pulse tools run too
     std::vector<double> last_x;
     std::string err;
     mbfir_allreduce_fn allreduce = nullptr;
@@ -272,6 +274,7 @@ mbfir_ctx* mbfir_create(int device_id) {
         install_fault_maps();                                  // (a profiler's handlers are installed at load: this one chains to them)
         mbfir_ctx* c = new mbfir_ctx();
         c->solver.reset(new Solver(device_id));
+        c->device = device_id;
         return c;
     } catch (const std::exception& e) {
         g_create_error = e.what();
@@ -675,7 +678,7 @@ int mbfir_test_specfact(mbfir_ctx* ctx, int n, const double* x, double* h_re, do
 }
 int mbfir_b2a(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, double* a_re, double* a_im) {
     if (!ctx || n < 1 || !b_re || !b_im || !a_re || !a_im) return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, ctx->solver->slr(n, b_re, b_im, nullptr, nullptr, a_re, a_im, nullptr, nullptr));
+    MBFIR_TRY(ctx, slr_run(ctx->device, ctx->solver->stream(), n, b_re, b_im, nullptr, nullptr, a_re, a_im, nullptr, nullptr));
 }
 int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
                 const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos,
@@ -683,22 +686,23 @@ int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1
     if (!ctx || ntime < 1 || nfreq < 1 || npos < 1 || !b1_re || !b1_im || !tsteps || !df || !mx || !my || !mz || mode < 0 || mode > 3 ||
         !(t1 > 0) || !(t2 > 0))
         return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, ctx->solver->bloch(ntime, b1_re, b1_im, gx, gy, gz, tsteps, t1, t2, nfreq, df, npos, dx, dy, dz, mode, gamma, mx, my, mz));
+    MBFIR_TRY(ctx, bloch_run(ctx->device, ctx->solver->stream(), ntime, b1_re, b1_im, gx, gy, gz, tsteps, t1, t2, nfreq, df, npos, dx,
+                             dy, dz, mode, gamma, mx, my, mz));
 }
 int mbfir_ab2rf(mbfir_ctx* ctx, int n, const double* a_re, const double* a_im, const double* b_re, const double* b_im,
                 double* rf_re, double* rf_im) {
     if (!ctx || n < 1 || n > 2048 || !a_re || !a_im || !b_re || !b_im || !rf_re || !rf_im) return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, ctx->solver->slr(n, b_re, b_im, a_re, a_im, nullptr, nullptr, rf_re, rf_im));
+    MBFIR_TRY(ctx, slr_run(ctx->device, ctx->solver->stream(), n, b_re, b_im, a_re, a_im, nullptr, nullptr, rf_re, rf_im));
 }
 int mbfir_b2rf(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
     if (!ctx || n < 1 || n > 2048 || !b_re || !b_im || !rf_re || !rf_im) return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, ctx->solver->slr(n, b_re, b_im, nullptr, nullptr, nullptr, nullptr, rf_re, rf_im));
+    MBFIR_TRY(ctx, slr_run(ctx->device, ctx->solver->stream(), n, b_re, b_im, nullptr, nullptr, nullptr, nullptr, rf_re, rf_im));
 }
 int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
               int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
     if (!ctx || n < 1 || nx < 1 || !rf_re || !rf_im || !x || !a_re || !a_im || !b_re || !b_im || (mode != 0 && mode != 1))
         return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, ctx->solver->abr(n, rf_re, rf_im, g, nx, x, mode, a_re, a_im, b_re, b_im));
+    MBFIR_TRY(ctx, abr_run(ctx->device, ctx->solver->stream(), n, rf_re, rf_im, g, nx, x, mode, a_re, a_im, b_re, b_im));
 }
 int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
     if (!ctx) return MBFIR_E_ARG;
@@ -706,7 +710,7 @@ int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const
         ctx->err = "b2rf_batch: need 2 <= n <= 2048, count >= 1 and the b_re / rf arrays";
         return MBFIR_E_ARG;
     }
-    MBFIR_TRY(ctx, ctx->solver->b2rf_batch(n, count, b_re, b_im, rf_re, rf_im));
+    MBFIR_TRY(ctx, slr_b2rf_batch_run(ctx->device, ctx->solver->stream(), n, count, b_re, b_im, rf_re, rf_im));
 }
 int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
                       double* out_im, int literal) {
@@ -717,7 +721,7 @@ int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_r
                    "r_re / out arrays and literal 0 or 1";
         return MBFIR_E_ARG;
     }
-    MBFIR_TRY(ctx, ctx->solver->slr2d_batch(m, n, count, r_re, r_im, out_re, out_im, literal));
+    MBFIR_TRY(ctx, slr_slr2d_batch_run(ctx->device, ctx->solver->stream(), m, n, count, r_re, r_im, out_re, out_im, literal));
 }
 int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
                const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
@@ -726,7 +730,7 @@ int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, 
         ctx->err = "abr2: need n, nx, ny >= 1 (nx ny <= 2^30) and the rf, x, y, a, b arrays";
         return MBFIR_E_ARG;
     }
-    MBFIR_TRY(ctx, ctx->solver->abr2(n, rf_re, rf_im, gx, gy, nx, x, ny, y, a_re, a_im, b_re, b_im));
+    MBFIR_TRY(ctx, abr2_run(ctx->device, ctx->solver->stream(), n, rf_re, rf_im, gx, gy, nx, x, ny, y, a_re, a_im, b_re, b_im));
 }
 int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
                       const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
@@ -743,8 +747,8 @@ int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const 
             if (enum_bits[j] < 0 || (enum_bits[j] >> 1) >= 24) return MBFIR_E_ARG;
     }
     try {
-        *winner = ctx->solver->flip_search(n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re,
-                                           s_im, criterion, tie_high ? 1 : 0, peaks, beta_re, beta_im, winner_peak);
+        *winner = flip_search_run(ctx->device, ctx->solver->stream(), n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks,
+                                  enum_bits, scale_rule, s_re, s_im, criterion, tie_high ? 1 : 0, peaks, beta_re, beta_im, winner_peak);
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
     if (*winner < 0) { ctx->err = "flip search: no candidate has a finite peak"; return MBFIR_NUMERICAL; }
     return 0;
@@ -776,7 +780,7 @@ int mbfir_remez_batch(mbfir_ctx* ctx, mbfir_remez_job* jobs, int njobs, const mb
         if (remez_grid_counts(j.numtaps, j.nband, j.edges, density, cnt.data()) < L + 1) return bad("dense grid smaller than L + 1");
         hj[q] = RemezJobHost{j.numtaps, j.nband, j.edges, j.desired, j.weight, j.h, j.ext, &j.status, &j.iterations, &j.delta};
     }
-    MBFIR_TRY(ctx, ctx->solver->remez(njobs, hj.data(), density, maxiter));
+    MBFIR_TRY(ctx, remez_run(ctx->device, ctx->solver->stream(), njobs, hj.data(), density, maxiter));
 }
 int mbfir_fmp(mbfir_ctx* ctx, int l, const double* h_re, const double* h_im, double* out_re, double* out_im) {
     if (!ctx) return MBFIR_E_ARG;
@@ -784,7 +788,7 @@ int mbfir_fmp(mbfir_ctx* ctx, int l, const double* h_re, const double* h_im, dou
         ctx->err = "fmp: filter length must be odd and at most 2047";
         return MBFIR_E_ARG;
     }
-    MBFIR_TRY(ctx, ctx->solver->fmp(l, h_re, h_im, out_re, out_im));
+    MBFIR_TRY(ctx, fmp_run(ctx->device, ctx->solver->stream(), l, h_re, h_im, out_re, out_im));
 }
 int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));

@@ -75,6 +75,24 @@ __device__ __forceinline__ void drain_stores() { asm volatile("s_waitcnt vmcnt(0
 inline int cdiv(long a, long b) { return int((a + b - 1) / b); }
 inline long round_up(long a, long b) { return ((a + b - 1) / b) * b; }
 
+// Device buffer (host side): at least 256 bytes, freed when it goes out of scope.
+struct DevBuf {
+    void* p = nullptr;
+    explicit DevBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
+    ~DevBuf() { if (p) hipFree(p); }
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    template <class T> T* as() { return reinterpret_cast<T*>(p); }
+};
+
+// Host staging of complex arrays: n split (re, im) planes <-> n interleaved (re, im) pairs.  A null im plane packs as zeros.
+inline void pack_cplx(size_t n, const double* re, const double* im, double2* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = make_double2(re[i], im ? im[i] : 0.0);
+}
+inline void unpack_cplx(size_t n, const double2* in, double* re, double* im) {
+    for (size_t i = 0; i < n; ++i) { re[i] = in[i].x; im[i] = in[i].y; }
+}
+
 // ---- kernels implemented in gram.hip / chol.hip / specfact.hip --------------------------------
 struct GramPlan {
     int ld = 0;        // padded column count of A1 (multiple of 128)
@@ -168,41 +186,5 @@ constexpr int DD_SYNC_LOST = CHOL_SYNC_LOST;
 // in hout[2n]).  work must hold 6*lp doubles, lp = 8*2^ceil(log2(2n-1)).
 int specfact_lp(int n);
 void specfact_launch(const double* x, int n, double* work, double* hout, hipStream_t st, int nlanes = 1, size_t lane_bytes = 0);
-
-// Inverse SLR (slr.hip; b2a.m:15-32, ab2rf.m:14-29).  b2a: work holds 48 n doubles; a_il / b_il / rf_il are
-// interleaved (re, im) device arrays of 2 n doubles.  ab2rf: n <= 2048.
-void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work, double* a_il, hipStream_t st);
-void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
-                    hipStream_t st);
-// Batched inverse SLR (slr.hip k_b2rf_batch; mbfir_b2rf_batch): count x n row-major host planes in and out (b_im may be null),
-// 2 <= n <= 2048, count >= 1; one workgroup per polynomial, one launch.
-void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const double* b_re, const double* b_im, double* rf_re,
-                        double* rf_im);
-// 2D inverse SLR (slr.hip k_b2rf_batch, k_slr2d_mid, k_slr2d_out; mbfir_slr2d_batch): count x m x n row-major host planes in and
-// out (r_im may be null), 2 <= m, n <= 2048, m even; one upload, one download.  literal: dzepse.m's sin(conj(theta) / 2) middle stage.
-void slr_slr2d_batch_run(int device, hipStream_t st, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
-                         double* out_im, int literal);
-// 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): nx x ny positions, outputs at k ny + j; gx null = 2 pi / n, gy null = 0.
-void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y, int ny,
-                     double* a_il, double* b_il, hipStream_t st);
-// Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:283-512).  step: ntime x 8 per-sample quantities.
-// Root-flip search (flip.hip): host side of mbfir_flip_search, arguments checked; returns the winner, -1 when no candidate has a
-// finite peak.
-long flip_search_run(int device, hipStream_t st, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
-                     const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
-                     const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
-                     double* beta_re, double* beta_im, double* winner_peak);
-void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode, double* mx,
-                  double* my, double* mz, hipStream_t st);
-void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st);
-
-// Batched Parks-McClellan exchange (remez.hip); RemezJobHost and remez_grid_counts are in solver.h.
-struct RemezJobHost;
-void remez_run(hipStream_t st, int njobs, const RemezJobHost* jobs, int density, int maxiter);
-
-// fmp.m (rf_tools/fmp.m:12-23) for odd l <= 2047: h (l complex, interleaved) -> (l + 1) / 2 complex taps (interleaved).  work holds
-// 6 * lp doubles, lp = 8 * 2^ceil(log2(l)).
-int fmp_lp(int l);
-void fmp_launch(const double* h_il, int l, double* work, double* hout, hipStream_t st);
 
 }  // namespace mbfir

@@ -19,6 +19,7 @@
 // Working set per candidate (double2): Y 8n, X 4n + 1, beta 2 x n (+ the tables 8n + nn when they fit): in LDS when it fits,
 // else in a per-workgroup global scratch (n up to 1024).
 #include "dev_common.h"
+#include "pulse.h"
 #include <algorithm>
 #include <cstring>
 
@@ -337,13 +338,6 @@ __global__ void k_flip_twiddles(double2* __restrict__ tw, int N, int nn) {
     }
 }
 
-struct DBuf {
-    void* p = nullptr;
-    explicit DBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
-    ~DBuf() { if (p) hipFree(p); }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 template <int kMode>
 int flip_blocks(int threads, size_t lds, int ncu) {
     if (lds > 65536)
@@ -356,19 +350,19 @@ int flip_blocks(int threads, size_t lds, int ncu) {
 }  // namespace
 
 // Host side of mbfir_flip_search (include/mbfir.h): arguments already checked.  Returns the winner (-1: no finite peak).
-long flip_search_run(int device, hipStream_t st, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
+long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
                      const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
                      double* beta_re, double* beta_im, double* winner_peak) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = 8 * n, n0 = n - nz, words = (nz + 31) / 32;
     int nn = 1;
     while (nn < n) nn <<= 1;
     std::vector<double2> hc(n0 + 2 * nz);
-    for (int k = 0; k < n0; ++k) hc[k] = make_double2(c0_re[k], c0_im[k]);
-    for (int j = 0; j < nz; ++j) {
-        hc[n0 + j] = make_double2(z_re[j], z_im[j]);
-        hc[n0 + nz + j] = make_double2(zf_re[j], zf_im[j]);
-    }
+    pack_cplx(n0, c0_re, c0_im, hc.data());
+    pack_cplx(nz, z_re, z_im, hc.data() + n0);
+    pack_cplx(nz, zf_re, zf_im, hc.data() + n0 + nz);
     std::vector<int> eb(nz > 0 ? nz : 1);
     for (int j = 0; j < nz; ++j) eb[j] = enum_bits ? enum_bits[j] : (nz - 1 - j) << 1;     // combination_2power (fir_flip_zero.m:153-160)
 
@@ -385,7 +379,7 @@ long flip_search_run(int device, hipStream_t st, int n, int nz, const double* c0
     if (mode == 2) maxb = std::min(maxb, 2 * ncu);                 // bounds the global scratch (229 KB per workgroup at n = 1024)
     const int nb = (int)std::max(1L, std::min<long>(ncand, std::max(maxb, 1)));
 
-    DBuf dc(hc.size() * 16), deb(eb.size() * 4), dtw(tabs), dm(masks ? (size_t)ncand * words * 4 : 4),
+    DevBuf dc(hc.size() * 16), deb(eb.size() * 4), dtw(tabs), dm(masks ? (size_t)ncand * words * 4 : 4),
         dpk(peaks ? (size_t)ncand * 8 : 8), dbp((size_t)nb * 8), dbi((size_t)nb * 8), dwin(16), dbeta((size_t)n * 16),
         dscr(mode == 2 ? (size_t)nb * (14 * n + 1) * 16 : 16);
     MBFIR_HIP(hipMemcpyAsync(dc.p, hc.data(), hc.size() * 16, hipMemcpyHostToDevice, st));
@@ -428,8 +422,7 @@ long flip_search_run(int device, hipStream_t st, int n, int nz, const double* c0
     double wp;
     memcpy(&wp, &hw[1], 8);
     if (winner_peak) *winner_peak = wp;
-    if (w >= 0 && beta_re)
-        for (int k = 0; k < n; ++k) { beta_re[k] = hb[k].x; beta_im[k] = hb[k].y; }
+    if (w >= 0 && beta_re) unpack_cplx(n, hb.data(), beta_re, beta_im);
     return w;
 }
 

@@ -1,0 +1,55 @@
+// Host side of the pulse tools (slr.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
+// (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
+// compiler.
+#pragma once
+
+namespace mbfir {
+
+// Inverse SLR (slr.hip; b2a.m:15-32, ab2rf.m:14-29).  b: n complex taps.  a_in null: a = b2a(b), else a = a_in.
+// a_out (optional) receives a; rf (optional) receives ab2rf(a, b), n <= 2048.
+void slr_run(int device, void* stream, int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
+             double* a_re, double* a_im, double* rf_re, double* rf_im);
+// Forward simulation (slr.hip k_abr): a, b over nx positions; g null = 2 pi / n per sample; mode 0 abrm.m, 1 hard pulse.
+void abr_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
+             int mode, double* a_re, double* a_im, double* b_re, double* b_im);
+// 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j; gx null = 2 pi / n, gy null = 0.
+void abr2_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
+              const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im);
+// Batched inverse SLR (slr.hip k_b2rf_batch): count x n row-major planes in and out (b_im may be null), 2 <= n <= 2048, count >= 1;
+// one workgroup per polynomial, one launch.
+void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double* b_re, const double* b_im, double* rf_re,
+                        double* rf_im);
+// 2D inverse SLR (slr.hip k_b2rf_batch, k_slr2d_mid, k_slr2d_out; dzepse.m:39-49): count x m x n row-major planes in and out
+// (r_im may be null), 2 <= m, n <= 2048, m even; one upload, one download.  literal: dzepse.m's sin(conj(theta) / 2) middle stage.
+void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+                         double* out_im, int literal);
+// Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:422-512).  m*: in = initial magnetisation at the first sample of
+// every (frequency, position) block, out = the result; nfreq * npos * (mode & 2 ? ntime : 1) doubles each.
+void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+               const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
+               const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
+// Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
+long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
+                     const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
+                     const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
+                     double* beta_re, double* beta_im, double* winner_peak);
+
+// Batched Parks-McClellan exchange (remez.hip): one workgroup per design.  status: 0 converged, 1 maxiter reached (last iterate
+// returned), 2 the exchange lost the alternation (no valid iterate).
+struct RemezJobHost {
+    int numtaps, nband;
+    const double *edges, *desired, *weight;    // 2 nband, 2 nband, nband
+    double* h;                                 // numtaps
+    double* ext;                               // L + 1 or null
+    int *status, *iterations;
+    double* delta;
+};
+// Dense-grid size and per-band point counts (counts: nband ints) of the grid k_remez builds.
+int remez_grid_counts(int numtaps, int nband, const double* edges, int density, int* counts);
+void remez_run(int device, void* stream, int njobs, const RemezJobHost* jobs, int density, int maxiter);
+
+// fmp.m (specfact.hip k_fmp): odd l <= 2047 taps of h (h_im may be null) -> (l + 1) / 2 minimum-phase taps.
+void fmp_run(int device, void* stream, int l, const double* h_re, const double* h_im, double* out_re, double* out_im);
+
+}  // namespace mbfir

@@ -5,7 +5,7 @@
 // scratch per design (offset table from the host): f, x, D, W, E (5 G doubles), two index lists (2 G ints), the next extremal
 // set (L + 1 ints) and the cosine table (2 L - 1 doubles).
 #include "dev_common.h"
-#include "solver.h"
+#include "pulse.h"
 #include <cstring>
 
 namespace mbfir {
@@ -309,13 +309,6 @@ __global__ __launch_bounds__(RZ_THREADS) void k_remez(const RemezJobDev* __restr
     }
 }
 
-struct DBuf {
-    void* p = nullptr;
-    explicit DBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
-    ~DBuf() { if (p) hipFree(p); }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 }  // namespace
 
 int remez_grid_counts(int numtaps, int nband, const double* edges, int density, int* counts) {
@@ -332,7 +325,9 @@ int remez_grid_counts(int numtaps, int nband, const double* edges, int density, 
     return G;
 }
 
-void remez_run(hipStream_t st, int njobs, const RemezJobHost* jobs, int density, int maxiter) {
+void remez_run(int device, void* stream, int njobs, const RemezJobHost* jobs, int density, int maxiter) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
     std::vector<RemezJobDev> jd(njobs);
     std::vector<double> bt;
     size_t scr = 0, outn = 0;
@@ -355,7 +350,7 @@ void remez_run(hipStream_t st, int njobs, const RemezJobHost* jobs, int density,
         d.out = (long)outn;
         outn += (size_t)h.numtaps + d.L + 1;
     }
-    DBuf djobs(jd.size() * sizeof(RemezJobDev)), dbands(bt.size() * 8), dscr(scr), dout(outn * 8), drec((size_t)njobs * 32);
+    DevBuf djobs(jd.size() * sizeof(RemezJobDev)), dbands(bt.size() * 8), dscr(scr), dout(outn * 8), drec((size_t)njobs * 32);
     MBFIR_HIP(hipMemcpyAsync(djobs.p, jd.data(), jd.size() * sizeof(RemezJobDev), hipMemcpyHostToDevice, st));
     MBFIR_HIP(hipMemcpyAsync(dbands.p, bt.data(), bt.size() * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_remez, dim3(njobs), dim3(RZ_THREADS), 0, st, djobs.as<RemezJobDev>(), dbands.as<double>(), dscr.as<char>(),

@@ -4,7 +4,9 @@
 //           exact sincospi seed every 256 terms), elementwise steps in between
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
 #include "dev_common.h"
+#include "pulse.h"
 #include <algorithm>
+#include <cmath>
 
 namespace mbfir {
 
@@ -181,8 +183,8 @@ __global__ __launch_bounds__(256) void k_abr(const double* __restrict__ rf_il, c
     }
     if (i < nx) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
 }
-void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
-                    hipStream_t st) {
+static void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
+                           hipStream_t st) {
     hipLaunchKernelGGL(k_abr, dim3(cdiv(nx, 256)), dim3(256), 0, st, rf_il, g, n, x, nx, mode, a_il, b_il);
 }
 
@@ -280,13 +282,13 @@ __global__ __launch_bounds__(256) void k_bloch(const double* __restrict__ step, 
     }
     if (live && !(mode & 2)) { mx[o0] = m[0]; my[o0] = m[1]; mz[o0] = m[2]; }
 }
-void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode, double* mx,
-                  double* my, double* mz, hipStream_t st) {
+static void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode,
+                         double* mx, double* my, double* mz, hipStream_t st) {
     hipLaunchKernelGGL(k_bloch, dim3(cdiv((long)nf * npos, 256)), dim3(256), 0, st, step, ntime, df, nf, pos3, npos, mode, mx, my, mz);
 }
 
 // work: 3 * 8n double2.  a_il / rf_il: device arrays of 2n doubles (interleaved).
-void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work, double* a_il, hipStream_t st) {
+static void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work, double* a_il, hipStream_t st) {
     const int N = 8 * n;
     double2* B0 = reinterpret_cast<double2*>(work);
     double2* B1 = B0 + N;
@@ -302,7 +304,7 @@ void slr_b2a_launch(const double* b_re, const double* b_im, int n, double* work,
     hipLaunchKernelGGL(k_dft_any, g, b, 0, st, B2, B1, N, -1, 1.0 / N);          // aca = fft(afa) / blp
     hipLaunchKernelGGL(k_slr_out, dim3(cdiv(n, 256)), b, 0, st, B1, n, a_il);
 }
-void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st) {
+static void slr_ab2rf_launch(const double* a_il, const double* b_il, int n, double* rf_il, hipStream_t st) {
     if (n > SLR_MAXN) throw HipError("ab2rf: more than 2048 taps");
     hipLaunchKernelGGL(k_ab2rf, dim3(1), dim3(1024), 0, st, a_il, b_il, n, rf_il);
 }
@@ -437,33 +439,28 @@ __global__ __launch_bounds__(NT) void k_b2rf_batch(const double2* __restrict__ b
     }
 }
 
-struct SlrBuf {
-    void* p = nullptr;
-    explicit SlrBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
-    ~SlrBuf() { if (p) hipFree(p); }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-
 template <int MAXN, int NT>
 static void b2rf_batch_launch(int device, hipStream_t st, int n, int count, const double2* b, double2* rf) {
     int ncu = 0, per = 0;
     MBFIR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
     MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_b2rf_batch<MAXN, NT>, NT, 0));
     const int grid = std::max(1, std::min(count, std::max(per, 1) * ncu));    // resident workgroups bound the scratch
-    SlrBuf work((size_t)grid * 2 * 8 * n * sizeof(double2));
+    DevBuf work((size_t)grid * 2 * 8 * n * sizeof(double2));
     hipLaunchKernelGGL((k_b2rf_batch<MAXN, NT>), dim3(grid), dim3(NT), 0, st, b, n, count, work.as<double2>(), rf);
     MBFIR_HIP(hipGetLastError());
     MBFIR_HIP(hipStreamSynchronize(st));                  // the scratch is freed on return
 }
 
 // Host side of mbfir_b2rf_batch (arguments checked): host planes in, host planes out.
-void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const double* b_re, const double* b_im, double* rf_re,
+void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double* b_re, const double* b_im, double* rf_re,
                         double* rf_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 2 || n > SLR_MAXN || count < 1) throw HipError("b2rf_batch: bad sizes");
     const size_t tot = (size_t)n * count;
     std::vector<double2> h(tot);
-    for (size_t i = 0; i < tot; ++i) h[i] = make_double2(b_re[i], b_im ? b_im[i] : 0.0);
-    SlrBuf db(tot * sizeof(double2)), drf(tot * sizeof(double2));
+    pack_cplx(tot, b_re, b_im, h.data());
+    DevBuf db(tot * sizeof(double2)), drf(tot * sizeof(double2));
     MBFIR_HIP(hipMemcpyAsync(db.p, h.data(), tot * sizeof(double2), hipMemcpyHostToDevice, st));
     const double2* b = db.as<double2>();
     double2* rf = drf.as<double2>();
@@ -474,7 +471,7 @@ void slr_b2rf_batch_run(int device, hipStream_t st, int n, int count, const doub
     MBFIR_HIP(hipMemcpyAsync(h.data(), drf.p, tot * sizeof(double2), hipMemcpyDeviceToHost, st));
     MBFIR_HIP(hipStreamSynchronize(st));
     MBFIR_HIP(hipGetLastError());
-    for (size_t i = 0; i < tot; ++i) { rf_re[i] = h[i].x; rf_im[i] = h[i].y; }
+    unpack_cplx(tot, h.data(), rf_re, rf_im);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -605,17 +602,19 @@ static void slr2d_mid_enqueue(hipStream_t st, const double2* rn1, int m, int n, 
 }
 
 // Host side of mbfir_slr2d_batch (arguments checked): host planes in (count x m x n row-major), host planes out (same layout).
-void slr_slr2d_batch_run(int device, hipStream_t st, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
+void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
                          double* out_im, int literal) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
     if (n < 2 || n > SLR_MAXN || m < 2 || m > SLR_MAXN || m % 2 || count < 1 || (long)count * std::max(m, n) > INT32_MAX)
         throw HipError("slr2d_batch: bad sizes");
     const size_t tot = (size_t)m * n * count;
     std::vector<double2> h(tot);
-    for (size_t i = 0; i < tot; ++i) h[i] = make_double2(r_re[i], r_im ? r_im[i] : 0.0);
+    pack_cplx(tot, r_re, r_im, h.data());
     const int rows1 = count * m, rows2 = count * n;
     const int g1 = b2rf_batch_grid(device, n, rows1), g2 = b2rf_batch_grid(device, m, rows2);
-    SlrBuf d0(tot * sizeof(double2)), d1(tot * sizeof(double2));
-    SlrBuf work(std::max((size_t)g1 * 16 * n, (size_t)g2 * 16 * m) * sizeof(double2));
+    DevBuf d0(tot * sizeof(double2)), d1(tot * sizeof(double2));
+    DevBuf work(std::max((size_t)g1 * 16 * n, (size_t)g2 * 16 * m) * sizeof(double2));
     double2* x0 = d0.as<double2>();
     double2* x1 = d1.as<double2>();
     MBFIR_HIP(hipMemcpyAsync(x0, h.data(), tot * sizeof(double2), hipMemcpyHostToDevice, st));
@@ -630,7 +629,7 @@ void slr_slr2d_batch_run(int device, hipStream_t st, int m, int n, int count, co
     MBFIR_HIP(hipMemcpyAsync(h.data(), x0, tot * sizeof(double2), hipMemcpyDeviceToHost, st));
     MBFIR_HIP(hipStreamSynchronize(st));                  // the buffers are freed on return
     MBFIR_HIP(hipGetLastError());
-    for (size_t i = 0; i < tot; ++i) { out_re[i] = h[i].x; out_im[i] = h[i].y; }
+    unpack_cplx(tot, h.data(), out_re, out_im);
 }
 
 // 2D forward simulation, abrm.m:39-57: one thread per (x_k, y_j), output index k ny + j; one rotation about
@@ -676,9 +675,125 @@ __global__ __launch_bounds__(256) void k_abr2(const double* __restrict__ rf_il, 
     }
     if (live) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
 }
-void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y, int ny,
-                     double* a_il, double* b_il, hipStream_t st) {
+static void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y,
+                            int ny, double* a_il, double* b_il, hipStream_t st) {
     hipLaunchKernelGGL(k_abr2, dim3(cdiv((long)nx * ny, 256)), dim3(256), 0, st, rf_il, gx, gy, n, x, nx, y, ny, a_il, b_il);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side of mbfir_b2a / mbfir_ab2rf / mbfir_b2rf, mbfir_abr, mbfir_abr2 and mbfir_bloch (pulse.h; arguments checked).
+
+void slr_run(int device, void* stream, int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
+             double* a_re, double* a_im, double* rf_re, double* rf_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t N = (size_t)n;
+    DevBuf db(2 * N * 8), dbil(2 * N * 8), da(2 * N * 8), drf(2 * N * 8), dw(a_in_re ? 8 : 48 * N * 8);
+    std::vector<double2> h(N);
+    MBFIR_HIP(hipMemcpyAsync(db.p, b_re, N * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(db.as<double>() + N, b_im, N * 8, hipMemcpyHostToDevice, st));
+    if (a_in_re) {
+        pack_cplx(N, a_in_re, a_in_im, h.data());
+        MBFIR_HIP(hipMemcpyAsync(da.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
+        MBFIR_HIP(hipStreamSynchronize(st));
+    } else {
+        slr_b2a_launch(db.as<double>(), db.as<double>() + N, n, dw.as<double>(), da.as<double>(), st);
+    }
+    if (a_re) {
+        MBFIR_HIP(hipMemcpyAsync(h.data(), da.p, 2 * N * 8, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipStreamSynchronize(st));
+        unpack_cplx(N, h.data(), a_re, a_im);
+    }
+    if (rf_re) {
+        std::vector<double2> hb(N);
+        pack_cplx(N, b_re, b_im, hb.data());
+        MBFIR_HIP(hipMemcpyAsync(dbil.p, hb.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
+        slr_ab2rf_launch(da.as<double>(), dbil.as<double>(), n, drf.as<double>(), st);
+        MBFIR_HIP(hipMemcpyAsync(h.data(), drf.p, 2 * N * 8, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipStreamSynchronize(st));
+        unpack_cplx(N, h.data(), rf_re, rf_im);
+    }
+    MBFIR_HIP(hipGetLastError());
+}
+
+void abr_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
+             int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t N = (size_t)n, X = (size_t)nx;
+    DevBuf drf(2 * N * 8), dg(N * 8), dx(X * 8), da(2 * X * 8), db(2 * X * 8);
+    std::vector<double2> h(N), oa(X), ob(X);
+    pack_cplx(N, rf_re, rf_im, h.data());
+    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
+    if (g) MBFIR_HIP(hipMemcpyAsync(dg.p, g, N * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dx.p, x, X * 8, hipMemcpyHostToDevice, st));
+    slr_abr_launch(drf.as<double>(), g ? dg.as<double>() : nullptr, n, dx.as<double>(), nx, mode, da.as<double>(), db.as<double>(), st);
+    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * X * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * X * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    unpack_cplx(X, oa.data(), a_re, a_im);
+    unpack_cplx(X, ob.data(), b_re, b_im);
+}
+
+void abr2_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
+              const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t N = (size_t)n, P = (size_t)nx * ny;
+    DevBuf drf(2 * N * 8), dgx(N * 8), dgy(N * 8), dx((size_t)nx * 8), dy((size_t)ny * 8), da(2 * P * 8), db(2 * P * 8);
+    std::vector<double2> h(N), oa(P), ob(P);
+    pack_cplx(N, rf_re, rf_im, h.data());
+    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
+    if (gx) MBFIR_HIP(hipMemcpyAsync(dgx.p, gx, N * 8, hipMemcpyHostToDevice, st));
+    if (gy) MBFIR_HIP(hipMemcpyAsync(dgy.p, gy, N * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dx.p, x, (size_t)nx * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dy.p, y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
+    slr_abr2_launch(drf.as<double>(), gx ? dgx.as<double>() : nullptr, gy ? dgy.as<double>() : nullptr, n, dx.as<double>(), nx,
+                    dy.as<double>(), ny, da.as<double>(), db.as<double>(), st);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * P * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * P * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    unpack_cplx(P, oa.data(), a_re, a_im);
+    unpack_cplx(P, ob.data(), b_re, b_im);
+}
+
+void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+               const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
+               const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const double TWOPI_REF = 6.283185;                       // blochC.c:6, the reference's truncated constant
+    const size_t nt = (size_t)ntime, npair = (size_t)nfreq * npos, nout = npair * ((mode & 2) ? nt : 1);
+    std::vector<double> step(nt * 8), pos(3 * (size_t)npos);
+    for (size_t t = 0; t < nt; ++t) {
+        const double dt = tsteps[t];
+        step[8 * t] = -b1_re[t] * gamma * dt;                // rotx  (blochC.c:332)
+        step[8 * t + 1] = b1_im[t] * gamma * dt;             // roty  (:333)
+        step[8 * t + 2] = (gx ? gx[t] : 0.0) * gamma * dt;   // gradient terms of rotz (:317-319, :330)
+        step[8 * t + 3] = (gy ? gy[t] : 0.0) * gamma * dt;
+        step[8 * t + 4] = (gz ? gz[t] : 0.0) * gamma * dt;
+        step[8 * t + 5] = TWOPI_REF * dt;
+        step[8 * t + 6] = std::exp(-dt / t1);                // :460-464
+        step[8 * t + 7] = std::exp(-dt / t2);
+    }
+    for (int p = 0; p < npos; ++p) { pos[3 * p] = dx ? dx[p] : 0.0; pos[3 * p + 1] = dy ? dy[p] : 0.0; pos[3 * p + 2] = dz ? dz[p] : 0.0; }
+    DevBuf dstep(step.size() * 8), dpos(pos.size() * 8), ddf((size_t)nfreq * 8), dmx(nout * 8), dmy(nout * 8), dmz(nout * 8);
+    MBFIR_HIP(hipMemcpyAsync(dstep.p, step.data(), step.size() * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(ddf.p, df, (size_t)nfreq * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dmx.p, mx, nout * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dmy.p, my, nout * 8, hipMemcpyHostToDevice, st));
+    MBFIR_HIP(hipMemcpyAsync(dmz.p, mz, nout * 8, hipMemcpyHostToDevice, st));
+    bloch_launch(dstep.as<double>(), ntime, ddf.as<double>(), nfreq, dpos.as<double>(), npos, mode, dmx.as<double>(), dmy.as<double>(),
+                 dmz.as<double>(), st);
+    MBFIR_HIP(hipMemcpyAsync(mx, dmx.p, nout * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(my, dmy.p, nout * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(mz, dmz.p, nout * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
 }
 
 }  // namespace mbfir

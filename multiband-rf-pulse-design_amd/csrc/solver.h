@@ -53,19 +53,6 @@ struct SolveInfo {
     int gv_passes = 0, gtv_passes = 0;          // row-response passes G v and transposed passes G'v the solve launched (all iterations; a lock-step unit's count)
 };
 
-// Batched Parks-McClellan exchange (remez.hip): one workgroup per design, arguments checked by the caller.  status: 0 converged,
-// 1 maxiter reached (last iterate returned), 2 the exchange lost the alternation (no valid iterate).
-struct RemezJobHost {
-    int numtaps, nband;
-    const double *edges, *desired, *weight;    // 2 nband, 2 nband, nband
-    double* h;                                 // numtaps
-    double* ext;                               // L + 1 or null
-    int *status, *iterations;
-    double* delta;
-};
-// Dense-grid size and per-band point counts (counts: nband ints) of the grid k_remez builds.
-int remez_grid_counts(int numtaps, int nband, const double* edges, int density, int* counts);
-
 class Solver {
 public:
     explicit Solver(int device);
@@ -89,33 +76,6 @@ public:
     // fir_ap_cvx tap extraction on the device from the solution left by the last solve() / lane of solve_lanes().
     void specfact_last(int n, double* h_re, double* h_im, int lane = 0);
     void set_solution(const std::vector<double>& x);
-    // Inverse SLR on the device (slr.hip).  b: n complex taps.  a_in null: a = b2a(b) (b2a.m:15-32), else a = a_in.
-    // a_out (optional) receives a; rf (optional) receives ab2rf(a, b) (ab2rf.m:14-29).
-    void slr(int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
-             double* a_re, double* a_im, double* rf_re, double* rf_im);
-    // Forward simulation (slr.hip k_abr): a, b over nx positions; g null = 2 pi / n per sample; mode 0 abrm.m, 1 hard pulse.
-    void abr(int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x, int mode,
-             double* a_re, double* a_im, double* b_re, double* b_im);
-    // Batched inverse SLR (slr.hip k_b2rf_batch): count polynomials of n taps, row-major; b_im may be null.
-    void b2rf_batch(int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im);
-    // 2D inverse SLR (slr.hip, dzepse.m:39-49): count m x n matrices, row-major; r_im may be null; literal: dzepse's middle stage.
-    void slr2d_batch(int m, int n, int count, const double* r_re, const double* r_im, double* out_re, double* out_im, int literal);
-    // 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j; gx null = 2 pi / n, gy null = 0.
-    void abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
-              const double* y, double* a_re, double* a_im, double* b_re, double* b_im);
-    // Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:422-512).  m*: in = initial magnetisation at the first
-    // sample of every (frequency, position) block, out = the result; nfreq * npos * (mode & 2 ? ntime : 1) doubles each.
-    void bloch(int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy, const double* gz,
-               const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
-               const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
-    // Root-flip search (flip.hip, mbfir_flip_search): returns the winner, -1 when no candidate has a finite peak.
-    long flip_search(int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
-                     const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
-                     int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
-                     double* beta_im, double* winner_peak);
-    // Batched Parks-McClellan exchange (remez.hip, mbfir_remez_batch) and fmp.m (specfact.hip k_fmp, mbfir_fmp); arguments checked.
-    void remez(int njobs, const RemezJobHost* jobs, int density, int maxiter);
-    void fmp(int l, const double* h_re, const double* h_im, double* out_re, double* out_im);
     // kernel test hooks
     void test_gram(int m, int nt, int nw, const double* A, const double* d, double* out);
     void test_chol(int n, const double* H, double* out_l, double* out_m);

@@ -3960,15 +3960,6 @@ void Solver::specfact_last(int n, double* h_re, double* h_im, int lane) {
     for (int i = 0; i < n; ++i) { h_re[i] = h[2 * i]; h_im[i] = h[2 * i + 1]; }
 }
 
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    explicit DevBuf(size_t bytes) { MBFIR_HIP(hipMalloc(&p, std::max<size_t>(bytes, 256))); }
-    ~DevBuf() { if (p) hipFree(p); }
-    template <class T> T* as() { return reinterpret_cast<T*>(p); }
-};
-}  // namespace
-
 void Solver::test_gram(int m, int nt, int nw, const double* A, const double* d, double* out) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
@@ -4139,162 +4130,6 @@ void Solver::test_specfact(int n, const double* x, double* h_re, double* h_im) {
     MBFIR_HIP(hipStreamSynchronize(S.st));
     MBFIR_HIP(hipGetLastError());
     for (int i = 0; i < n; ++i) { h_re[i] = h[2 * i]; h_im[i] = h[2 * i + 1]; }
-}
-
-void Solver::slr(int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
-                 double* a_re, double* a_im, double* rf_re, double* rf_im) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    const size_t N = (size_t)n;
-    DevBuf db(2 * N * 8), dbil(2 * N * 8), da(2 * N * 8), drf(2 * N * 8), dw(a_in_re ? 8 : 48 * N * 8);
-    std::vector<double> h(2 * N);
-    MBFIR_HIP(hipMemcpyAsync(db.p, b_re, N * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(db.as<double>() + N, b_im, N * 8, hipMemcpyHostToDevice, S.st));
-    if (a_in_re) {
-        for (size_t i = 0; i < N; ++i) { h[2 * i] = a_in_re[i]; h[2 * i + 1] = a_in_im[i]; }
-        MBFIR_HIP(hipMemcpyAsync(da.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, S.st));
-        MBFIR_HIP(hipStreamSynchronize(S.st));
-    } else {
-        slr_b2a_launch(db.as<double>(), db.as<double>() + N, n, dw.as<double>(), da.as<double>(), S.st);
-    }
-    if (a_re) {
-        MBFIR_HIP(hipMemcpyAsync(h.data(), da.p, 2 * N * 8, hipMemcpyDeviceToHost, S.st));
-        MBFIR_HIP(hipStreamSynchronize(S.st));
-        for (size_t i = 0; i < N; ++i) { a_re[i] = h[2 * i]; a_im[i] = h[2 * i + 1]; }
-    }
-    if (rf_re) {
-        std::vector<double> hb(2 * N);
-        for (size_t i = 0; i < N; ++i) { hb[2 * i] = b_re[i]; hb[2 * i + 1] = b_im[i]; }
-        MBFIR_HIP(hipMemcpyAsync(dbil.p, hb.data(), 2 * N * 8, hipMemcpyHostToDevice, S.st));
-        slr_ab2rf_launch(da.as<double>(), dbil.as<double>(), n, drf.as<double>(), S.st);
-        MBFIR_HIP(hipMemcpyAsync(h.data(), drf.p, 2 * N * 8, hipMemcpyDeviceToHost, S.st));
-        MBFIR_HIP(hipStreamSynchronize(S.st));
-        for (size_t i = 0; i < N; ++i) { rf_re[i] = h[2 * i]; rf_im[i] = h[2 * i + 1]; }
-    }
-    MBFIR_HIP(hipGetLastError());
-}
-
-void Solver::abr(int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x, int mode,
-                 double* a_re, double* a_im, double* b_re, double* b_im) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    const size_t N = (size_t)n, X = (size_t)nx;
-    DevBuf drf(2 * N * 8), dg(N * 8), dx(X * 8), da(2 * X * 8), db(2 * X * 8);
-    std::vector<double> h(2 * N), oa(2 * X), ob(2 * X);
-    for (size_t i = 0; i < N; ++i) { h[2 * i] = rf_re[i]; h[2 * i + 1] = rf_im[i]; }
-    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, S.st));
-    if (g) MBFIR_HIP(hipMemcpyAsync(dg.p, g, N * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dx.p, x, X * 8, hipMemcpyHostToDevice, S.st));
-    slr_abr_launch(drf.as<double>(), g ? dg.as<double>() : nullptr, n, dx.as<double>(), nx, mode, da.as<double>(), db.as<double>(), S.st);
-    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * X * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * X * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipStreamSynchronize(S.st));
-    MBFIR_HIP(hipGetLastError());
-    for (size_t i = 0; i < X; ++i) { a_re[i] = oa[2 * i]; a_im[i] = oa[2 * i + 1]; b_re[i] = ob[2 * i]; b_im[i] = ob[2 * i + 1]; }
-}
-
-void Solver::b2rf_batch(int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    slr_b2rf_batch_run(S.device, S.st, n, count, b_re, b_im, rf_re, rf_im);
-}
-
-void Solver::slr2d_batch(int m, int n, int count, const double* r_re, const double* r_im, double* out_re, double* out_im,
-                         int literal) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    slr_slr2d_batch_run(S.device, S.st, m, n, count, r_re, r_im, out_re, out_im, literal);
-}
-
-void Solver::abr2(int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx, const double* x, int ny,
-                  const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    const size_t N = (size_t)n, P = (size_t)nx * ny;
-    DevBuf drf(2 * N * 8), dgx(N * 8), dgy(N * 8), dx((size_t)nx * 8), dy((size_t)ny * 8), da(2 * P * 8), db(2 * P * 8);
-    std::vector<double> h(2 * N), oa(2 * P), ob(2 * P);
-    for (size_t i = 0; i < N; ++i) { h[2 * i] = rf_re[i]; h[2 * i + 1] = rf_im[i]; }
-    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, S.st));
-    if (gx) MBFIR_HIP(hipMemcpyAsync(dgx.p, gx, N * 8, hipMemcpyHostToDevice, S.st));
-    if (gy) MBFIR_HIP(hipMemcpyAsync(dgy.p, gy, N * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dx.p, x, (size_t)nx * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dy.p, y, (size_t)ny * 8, hipMemcpyHostToDevice, S.st));
-    slr_abr2_launch(drf.as<double>(), gx ? dgx.as<double>() : nullptr, gy ? dgy.as<double>() : nullptr, n, dx.as<double>(), nx,
-                    dy.as<double>(), ny, da.as<double>(), db.as<double>(), S.st);
-    MBFIR_HIP(hipGetLastError());
-    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * P * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * P * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipStreamSynchronize(S.st));
-    MBFIR_HIP(hipGetLastError());
-    for (size_t i = 0; i < P; ++i) { a_re[i] = oa[2 * i]; a_im[i] = oa[2 * i + 1]; b_re[i] = ob[2 * i]; b_im[i] = ob[2 * i + 1]; }
-}
-
-void Solver::bloch(int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy, const double* gz,
-                   const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
-                   const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    const double TWOPI_REF = 6.283185;                       // blochC.c:6, the reference's truncated constant
-    const size_t nt = (size_t)ntime, npair = (size_t)nfreq * npos, nout = npair * ((mode & 2) ? nt : 1);
-    std::vector<double> step(nt * 8), pos(3 * (size_t)npos);
-    for (size_t t = 0; t < nt; ++t) {
-        const double dt = tsteps[t];
-        step[8 * t] = -b1_re[t] * gamma * dt;                // rotx  (blochC.c:332)
-        step[8 * t + 1] = b1_im[t] * gamma * dt;             // roty  (:333)
-        step[8 * t + 2] = (gx ? gx[t] : 0.0) * gamma * dt;   // gradient terms of rotz (:317-319, :330)
-        step[8 * t + 3] = (gy ? gy[t] : 0.0) * gamma * dt;
-        step[8 * t + 4] = (gz ? gz[t] : 0.0) * gamma * dt;
-        step[8 * t + 5] = TWOPI_REF * dt;
-        step[8 * t + 6] = std::exp(-dt / t1);                // :460-464
-        step[8 * t + 7] = std::exp(-dt / t2);
-    }
-    for (int p = 0; p < npos; ++p) { pos[3 * p] = dx ? dx[p] : 0.0; pos[3 * p + 1] = dy ? dy[p] : 0.0; pos[3 * p + 2] = dz ? dz[p] : 0.0; }
-    DevBuf dstep(step.size() * 8), dpos(pos.size() * 8), ddf((size_t)nfreq * 8), dmx(nout * 8), dmy(nout * 8), dmz(nout * 8);
-    MBFIR_HIP(hipMemcpyAsync(dstep.p, step.data(), step.size() * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(ddf.p, df, (size_t)nfreq * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dmx.p, mx, nout * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dmy.p, my, nout * 8, hipMemcpyHostToDevice, S.st));
-    MBFIR_HIP(hipMemcpyAsync(dmz.p, mz, nout * 8, hipMemcpyHostToDevice, S.st));
-    bloch_launch(dstep.as<double>(), ntime, ddf.as<double>(), nfreq, dpos.as<double>(), npos, mode, dmx.as<double>(), dmy.as<double>(),
-                 dmz.as<double>(), S.st);
-    MBFIR_HIP(hipMemcpyAsync(mx, dmx.p, nout * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipMemcpyAsync(my, dmy.p, nout * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipMemcpyAsync(mz, dmz.p, nout * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipStreamSynchronize(S.st));
-    MBFIR_HIP(hipGetLastError());
-}
-
-long Solver::flip_search(int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
-                         const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
-                         int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
-                         double* beta_im, double* winner_peak) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    return flip_search_run(S.device, S.st, n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re,
-                           s_im, criterion, tie_high, peaks, beta_re, beta_im, winner_peak);
-}
-
-void Solver::remez(int njobs, const RemezJobHost* jobs, int density, int maxiter) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    remez_run(S.st, njobs, jobs, density, maxiter);
-}
-
-void Solver::fmp(int l, const double* h_re, const double* h_im, double* out_re, double* out_im) {
-    Impl& S = *impl;
-    MBFIR_HIP(hipSetDevice(S.device));
-    const int lp = fmp_lp(l), m = (l + 1) / 2;
-    std::vector<double> h(2 * (size_t)l), o(2 * (size_t)m);
-    for (int i = 0; i < l; ++i) { h[2 * i] = h_re[i]; h[2 * i + 1] = h_im ? h_im[i] : 0.0; }
-    DevBuf dh(h.size() * 8), dw(6 * (size_t)lp * 8), dout(o.size() * 8);
-    MBFIR_HIP(hipMemcpyAsync(dh.p, h.data(), h.size() * 8, hipMemcpyHostToDevice, S.st));
-    fmp_launch(dh.as<double>(), l, dw.as<double>(), dout.as<double>(), S.st);
-    MBFIR_HIP(hipGetLastError());
-    MBFIR_HIP(hipMemcpyAsync(o.data(), dout.p, o.size() * 8, hipMemcpyDeviceToHost, S.st));
-    MBFIR_HIP(hipStreamSynchronize(S.st));
-    MBFIR_HIP(hipGetLastError());
-    for (int i = 0; i < m; ++i) { out_re[i] = o[2 * i]; out_im[i] = o[2 * i + 1]; }
 }
 
 // fp64 peak microbenchmarks (roofline denominators; the local hardware guide lists no fp64

@@ -3,6 +3,7 @@
 // :264-284 (fmp2) and :294-304 (mag2mp).  Three FFTs of length lp = 8*2^ceil(log2(2n-1))
 // (<= 65536): one workgroup, in-place radix-2 on global scratch, twiddles by sincospi.
 #include "dev_common.h"
+#include "pulse.h"
 
 namespace mbfir {
 
@@ -168,17 +169,34 @@ __global__ __launch_bounds__(1024) void k_fmp(const double2* __restrict__ h, int
     }
 }
 
-int fmp_lp(int l) {
+static int fmp_lp(int l) {
     int p = 1;
     while (p < l) p <<= 1;                               // 2^ceil(log2(l))                  :16
     return 8 * p;
 }
 
-void fmp_launch(const double* h_il, int l, double* work, double* hout, hipStream_t st) {
+static void fmp_launch(const double* h_il, int l, double* work, double* hout, hipStream_t st) {
     int lp = fmp_lp(l), loglp = 0;
     while ((1 << loglp) < lp) ++loglp;
     hipLaunchKernelGGL(k_fmp, dim3(1), dim3(1024), 0, st, reinterpret_cast<const double2*>(h_il), l, lp, loglp,
                        reinterpret_cast<double2*>(work), hout);
+}
+
+// Host side of mbfir_fmp (pulse.h; arguments checked).
+void fmp_run(int device, void* stream, int l, const double* h_re, const double* h_im, double* out_re, double* out_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int lp = fmp_lp(l), m = (l + 1) / 2;
+    std::vector<double2> h(l), o(m);
+    pack_cplx(l, h_re, h_im, h.data());
+    DevBuf dh(h.size() * 16), dw(6 * (size_t)lp * 8), dout(o.size() * 16);
+    MBFIR_HIP(hipMemcpyAsync(dh.p, h.data(), h.size() * 16, hipMemcpyHostToDevice, st));
+    fmp_launch(dh.as<double>(), l, dw.as<double>(), dout.as<double>(), st);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(o.data(), dout.p, o.size() * 16, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    unpack_cplx(m, o.data(), out_re, out_im);
 }
 
 }  // namespace mbfir
