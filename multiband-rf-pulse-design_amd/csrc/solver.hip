@@ -123,6 +123,11 @@ constexpr int NPART = 1024;   // max blocks contributing to a reduction
 constexpr int SCAL_T = 256;   // threads of the one-workgroup-per-design folding kernels (a 1024-thread block has to wait for a
                               // whole CU when other units share the chip)
 constexpr int MAX_SWEEPS = 8;
+// the scalar slots: the auto-numbered ones end before the first norm block, each norm block holds n_0 .. n_MAX_SWEEPS
+static_assert(S_NPICK < S_RNA, "scalar slots: the auto-numbered slots run into S_RNA");
+static_assert(S_RNA + MAX_SWEEPS + 1 <= S_RNB && S_RNB + MAX_SWEEPS + 1 <= S_CG_RZ && S_RNC + MAX_SWEEPS + 1 <= S_SIGMAX,
+              "scalar slots: a block of residual norms overlaps the next slot");
+static_assert(S_SIGMAX < S_COUNT, "scalar slots: S_COUNT too small");
 constexpr int CAP_KMAX = 1024;   // strong directions the capacitance form of the extended-precision solve takes (S is CAP_KMAX^2; the one-pass M'(M b) goes to np = 1024)
 constexpr int MAX_LANES = 64, MASK_ROWS = MAX_SWEEPS + 4;
 constexpr int ROW_BEST = MAX_SWEEPS + 1;      // mask rows: 0 live, 1 .. MAX_SWEEPS sweep q, then: lanes with a new best iterate,
@@ -2066,6 +2071,62 @@ __global__ void k_finish_x(DProg P, const double* __restrict__ x, const double* 
 // ================================================================================================
 // host driver
 // ================================================================================================
+// The MBFIR_* switches of the solver's host code, read from the environment once per call of solve_lanes, shape_key and
+// max_lanes (tests change them between solves in one process).  Each default is the behaviour with the switch unset.
+struct SolveSwitches {
+    bool corrector = true;       // CORRECTOR=0: no centrality corrector (programs without orthant rows never run it)
+    bool corr_plain = true;      // CORR_PLAIN=0 (diagnostic): the corrector's solve with the refinement sweeps of the other solves
+    bool corr_guard = true;      // CORR_GUARD=0 (diagnostic): take a correction even where its unrefined solve leaves more of the dual equation than the iterate's own residual
+    bool corr_big = true;        // CORR_BIG=0 (diagnostic): correct the orthant rows alone, not the big cone's products (round 6's first form)
+    double polish_approach = POLISH_APPROACH;   // POLISH_APPROACH (>= 1, diagnostic): the final approach's factor on the tolerances
+    int polish_sweeps = POLISH_SWEEPS;          // POLISH_SWEEPS (0 .. MAX_SWEEPS, diagnostic): sweeps added in the final approach and the end game
+    double sigma_max_corr = SIGMA_MAX_CORR;     // SIGMA_MAX (0 .. 1, diagnostic): the cap on sigma where the corrector follows
+    int test_cap_kp = 0;         // TEST_CAP_KP (test hook): a single design pads its capacitance matrix S as a unit's largest lane would
+    int ar_chunks = 0;           // AR_CHUNKS (>= 1; 0: the build's own choice): collectives of a dense row-sharded build
+    int ar_overlap = 1;          // AR_OVERLAP: 1 the chunked all-reduce overlapped with the Gram product, 0 the assembled H summed, 2 (diagnostic) the chunked form without shards
+    int seg = 0;                 // SEG (8 .. SEGMAX; 0: from the lattice extent): lattice points per segment of the row evaluation
+    bool share_seeds = true;     // SHARE_SEEDS=0: every lane of a unit builds and reads its own seed tables
+    int cgrp = 4;                // CGRP (1 .. CGRP): chunks per block of the moment kernels
+    bool hetero = true;          // HETERO=0: round 3's rule, a unit holds designs of exactly one shape
+    bool hetero_orders = true;   // HETERO_ORDERS=0: round 4's rule, one order per unit
+    bool hetero_dense = true;    // HETERO_DENSE=0: the exact shape on the dense path
+    int ddform = -1;             // DDFORM: -1 unset (opts.dd_form decides), 0 "dd" the double-double form, 1 any other value the capacitance form
+    int dd_passes = 0;           // DD_PASSES (1 .. 8; 0: 3 in the capacitance form, 2 in the double-double one): refinement passes of the extended-precision solve
+    bool dd_lanes = true;        // DD_LANES=0: designs on the extended-precision path one at a time instead of lock-step units
+    bool dd_blockinv = true;     // DD_BLOCKINV=0: substitution instead of the inverses of the dd factor's diagonal blocks
+    bool hsolve = true;          // HSOLVE=0: the preconditioner as two triangular GEMVs instead of one pass over M
+    bool fuse = true;            // FUSE=0: the separate kernels of round 4 instead of the fused launches of round 5
+    bool graph = false;          // GRAPH=1: single designs replay the iteration from launch graphs
+    bool speculate = true;       // SPECULATE=0: the head of the next iteration goes out after the host's verdicts, not before
+    bool trace_host = false;     // TRACE_HOST (set): report where the host thread spends the solve
+    bool test_lose_flag = false; // TEST_LOSE_FLAG (set, test hook of chol.hip): no launch graphs
+    long max_lanes = 0;          // MAX_LANES (>= 1; 0: from memory and occupancy): lanes per unit
+    int chunk = 64;              // CHUNK (4 .. CHK): longest run of frequencies between two exact sincos seeds
+    int fold = -1;               // FOLD: -1 unset (fold unless the extended-precision solve is on), 0 / 1 every frequency on its own / +w and -w paired
+};
+static SolveSwitches read_switches() {
+    SolveSwitches w;
+    auto flag = [](const char* name, bool& v) { if (const char* ev = std::getenv(name)) v = std::atoi(ev) != 0; };
+    auto clamped = [](const char* name, int& v, int lo, int hi) { if (const char* ev = std::getenv(name)) v = std::max(lo, std::min(hi, std::atoi(ev))); };
+    flag("MBFIR_CORRECTOR", w.corrector); flag("MBFIR_CORR_PLAIN", w.corr_plain); flag("MBFIR_CORR_GUARD", w.corr_guard); flag("MBFIR_CORR_BIG", w.corr_big);
+    flag("MBFIR_SHARE_SEEDS", w.share_seeds); flag("MBFIR_HETERO", w.hetero); flag("MBFIR_HETERO_ORDERS", w.hetero_orders); flag("MBFIR_HETERO_DENSE", w.hetero_dense);
+    flag("MBFIR_DD_LANES", w.dd_lanes); flag("MBFIR_DD_BLOCKINV", w.dd_blockinv); flag("MBFIR_HSOLVE", w.hsolve); flag("MBFIR_FUSE", w.fuse);
+    flag("MBFIR_GRAPH", w.graph); flag("MBFIR_SPECULATE", w.speculate);
+    clamped("MBFIR_POLISH_SWEEPS", w.polish_sweeps, 0, MAX_SWEEPS); clamped("MBFIR_SEG", w.seg, 8, SEGMAX); clamped("MBFIR_CGRP", w.cgrp, 1, CGRP);
+    clamped("MBFIR_DD_PASSES", w.dd_passes, 1, 8); clamped("MBFIR_CHUNK", w.chunk, 4, CHK);
+    if (const char* ev = std::getenv("MBFIR_POLISH_APPROACH")) w.polish_approach = std::max(1.0, std::atof(ev));
+    if (const char* ev = std::getenv("MBFIR_SIGMA_MAX")) w.sigma_max_corr = std::max(0.0, std::min(1.0, std::atof(ev)));
+    if (const char* ev = std::getenv("MBFIR_TEST_CAP_KP")) w.test_cap_kp = std::atoi(ev);
+    if (const char* ev = std::getenv("MBFIR_AR_CHUNKS")) w.ar_chunks = std::max(1, std::atoi(ev));
+    if (const char* ev = std::getenv("MBFIR_AR_OVERLAP")) w.ar_overlap = std::atoi(ev);
+    if (const char* ev = std::getenv("MBFIR_DDFORM")) w.ddform = std::strcmp(ev, "dd") != 0 ? 1 : 0;
+    if (const char* ev = std::getenv("MBFIR_MAX_LANES")) w.max_lanes = std::max(1L, std::atol(ev));      // (experiments: tools/sweep_lanes.sh)
+    if (const char* ev = std::getenv("MBFIR_FOLD")) w.fold = std::atoi(ev) != 0;
+    w.trace_host = std::getenv("MBFIR_TRACE_HOST") != nullptr;
+    w.test_lose_flag = std::getenv("MBFIR_TEST_LOSE_FLAG") != nullptr;
+    return w;
+}
+
 // Host analysis for the lattice mode (DProg::trig): column delays on one unit-step lattice, at most
 // one column per (kind, lattice point), and a frequency grid made of equally spaced runs.
 struct LatticeInfo {
@@ -2084,10 +2145,8 @@ struct LatticeInfo {
 // share cos(w t) and differ in the sign of sin(w t), so every recurrence of the lattice kernels serves both -- the
 // moment sums take p(+w) + p(-w) on the cosine and p(+w) - p(-w) on the sine, a row response is C + S at +w and C - S
 // at -w.  A frequency without a partner (band edges, one-sided grids) is an entry with one side empty.
-static LatticeInfo analyse_lattice(const TrigProgram& Q, bool fold = true, int chunk_len = 64) {
+static LatticeInfo analyse_lattice(const TrigProgram& Q, bool fold, int chunk_len) {
     LatticeInfo L;
-    if (const char* ev = std::getenv("MBFIR_CHUNK")) chunk_len = std::max(4, std::min(CHK, std::atoi(ev)));
-    if (const char* ev = std::getenv("MBFIR_FOLD")) fold = std::atoi(ev) != 0;
     const int Nt = Q.Nt, Mf = Q.Mf;
     if (Nt <= 0 || Mf <= 0) return L;
     double tmin = Q.col_tau[0];
@@ -2188,6 +2247,151 @@ struct Arena {
     }
 };
 
+static double now_ms() {
+    using namespace std::chrono;
+    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
+}
+
+// Two programs can share a lock-step batch when every array the device holds for them has the same length and
+// the scalar structure the kernels are launched with is the same: dimensions, lattice extent and chunk count.
+// index structures + lattice analysis of one program, kept with the program (TrigProgram::prep) so that the batch
+// front end can compute them in its parallel assembly threads and the solve does not repeat them
+struct LanePrep {
+    bool fold = true, dense = false;
+    std::vector<int> f_ptr, f_rows, c_ptr, c_rows, yrows, rep;
+    LatticeInfo Lt;
+};
+// Host-side description of one lane (one design of a lock-step batch)
+struct LaneHost {
+    const TrigProgram* Q = nullptr;
+    TrigProgram local;                       // the row shard (sharded solves have one lane)
+    std::shared_ptr<const LanePrep> prep;    // its index structures (lane_prep)
+    LatticeInfo Lt;                          // its lattice analysis (a row-sharded solve may drop it: dense path on every rank)
+    double nrm_h = 1, nrm_c = 1, degree = 0;
+    // IPM state
+    int status = ST_MAXIT, nsweep = 0 /* sweeps the iteration's solves run */, nsweep_ctl = 0 /* ... of which the controller asks for (the rest: POLISH_SWEEPS) */, wall = 0;
+    bool live = true, have_best = false;
+    double best_merit = 1e300, rx_prev = 0;
+    SolveInfo info, best_info;
+    // end game (oracle/conic_ipm.py POLISH): the first iteration whose iterate met the stopping rule, the best such iterate's merit and report
+    // (its x / tau is in xbest: once an iterate has met the rule the reduced-accuracy candidate that buffer held is of no use)
+    int first_opt = -1;
+    double opt_merit = 1e300;
+    SolveInfo opt_info;
+    // extended-precision path: strong directions of the current iteration (0: the plain solve), iterations on it, its largest set
+    int dd_k = 0, dd_iters = 0, dd_kmax = 0;
+};
+
+static void index_structures(const TrigProgram& Q, LanePrep& L) {
+    const int R = Q.R, Nt = Q.Nt, Mf = Q.Mf;
+    L.f_ptr.assign(Mf + 1, 0); L.c_ptr.assign(Nt + 1, 0); L.f_rows.clear(); L.c_rows.clear(); L.yrows.clear();
+    for (int r = 0; r < R; ++r) {
+        if (Q.freq[r] >= 0) L.f_ptr[Q.freq[r] + 1]++;
+        if (Q.col[r] >= 0) L.c_ptr[Q.col[r] + 1]++;
+        if (Q.ey[3 * r] != 0 || Q.ey[3 * r + 1] != 0 || Q.ey[3 * r + 2] != 0) L.yrows.push_back(r);
+        if (Q.freq[r] >= 0 && r >= Q.l) {
+            int a = (r - Q.l) % 3;
+            if (r >= Q.l + 3 * Q.nq3 || a == 0) throw HipError("unsupported cone layout (trig row at cone position 0 / in big cone)");
+        }
+    }
+    for (int i = 0; i < Mf; ++i) L.f_ptr[i + 1] += L.f_ptr[i];
+    for (int j = 0; j < Nt; ++j) L.c_ptr[j + 1] += L.c_ptr[j];
+    L.f_rows.resize(L.f_ptr[Mf]); L.c_rows.resize(L.c_ptr[Nt]);
+    std::vector<int> fp(L.f_ptr.begin(), L.f_ptr.end() - 1), cp(L.c_ptr.begin(), L.c_ptr.end() - 1);
+    for (int r = 0; r < R; ++r) {
+        if (Q.freq[r] >= 0) L.f_rows[fp[Q.freq[r]]++] = r;
+        if (Q.col[r] >= 0) L.c_rows[cp[Q.col[r]]++] = r;
+    }
+}
+
+static std::shared_ptr<LanePrep> lane_prep(const TrigProgram& Q, const SolveOpts& o, const SolveSwitches& sw) {
+    const bool fold = o.ddkkt_theta <= 0, dense = o.dense_trig != 0;
+    if (Q.prep) {
+        auto have = std::static_pointer_cast<LanePrep>(Q.prep);
+        if (have->fold == fold && have->dense == dense) return have;
+    }
+    auto pr = std::make_shared<LanePrep>();
+    pr->fold = fold; pr->dense = dense;
+    index_structures(Q, *pr);
+    pr->rep = replicated_rows(Q);
+    if (!dense) pr->Lt = analyse_lattice(Q, sw.fold < 0 ? fold : sw.fold != 0, sw.chunk);
+    Q.prep = pr;
+    return pr;
+}
+
+// what unit planning hands on to the arena layout and the driver
+struct UnitPlan {
+    int n_max = 0, lp = 0;                   // the unit's largest order and its spectral-factorisation length
+    bool use_dd = false;                     // the extended-precision KKT solve is on
+    std::vector<std::vector<int>> tiles;     // every lane's Gram tile table (lane 0's chunk tables behind it)
+};
+
+// The verdict on one live lane after iteration `it` (mirrors oracle/conic_ipm.py): the refinement-sweep controller, the stopping
+// rule and the end game, the infeasibility tests, the reduced-accuracy candidate, max_iter and the numerical wall.  hs: the lane's
+// scalar row.  Updates the lane's host state (a lane that finishes is no longer live); returns whether the lane has a new best
+// iterate (xbest is then to take its x / tau -- also on a lane that this very iteration retires).
+static bool lane_verdict(LaneHost& L, const double* hs, const SolveOpts& o, int it, const SolveSwitches& sw) {
+    SolveInfo& info = L.info;
+    if (it > 0 && L.dd_k == 0) {                      // (iterations on the extended-precision path keep the count)
+        // refinement-sweep controller (mirrors oracle/conic_ipm.py next_sweeps): the norms were
+        // measured before each sweep of the two KKT solves of the previous iteration
+        const double tol = std::max(REFTOL * hs[S_NRMC], REFETA * L.rx_prev);   // ||rx|| of the iteration the norms belong to
+        int need = 0;
+        bool unconverged = false;
+        for (int slot : {int(S_RNA), int(S_RNB)}) {        // (the corrector's solve runs without sweeps and reports no norms)
+            int k = -1;
+            for (int q = 0; q <= std::min(L.nsweep, MAX_SWEEPS); ++q)      // n_0 .. n_nsweep
+                if (hs[slot + q] <= tol) { k = q; break; }
+            if (k < 0) unconverged = true;
+            else need = std::max(need, k);
+        }
+        L.nsweep_ctl = unconverged ? std::min(MAX_SWEEPS, L.nsweep + 1) : need;
+    }
+    L.rx_prev = hs[S_DRES] * hs[S_TAU] * hs[S_NRMC];
+    info.iters = it; info.pcost = hs[S_PCOST]; info.dcost = hs[S_DCOST]; info.gap = hs[S_GAP];
+    info.relgap = hs[S_RELGAP]; info.pres = hs[S_PRES]; info.dres = hs[S_DRES];
+    info.correctors = int(hs[S_NCORR]); info.correctors_taken = int(hs[S_NPICK]);
+    bool best = false;
+    auto finish = [&](int status) { L.status = status; L.live = false; return best; };
+    const bool finite = std::isfinite(hs[S_PRES]) && std::isfinite(hs[S_DRES]) && std::isfinite(hs[S_GAP]) && hs[S_TAU] > 0;
+    if (finite && hs[S_PRES] <= o.feastol && hs[S_DRES] <= o.feastol && (hs[S_GAP] <= o.abstol || hs[S_RELGAP] <= o.reltol)) {
+        // end game (mirrors oracle/conic_ipm.py): the iterate meets the stopping rule -- keep the best such iterate (xbest) and
+        // go on until the gap measures are POLISH times below the tolerances or POLISH_MAX more iterations have passed; the
+        // best iterate is the answer however the end game ends
+        const double merit_o = std::min(hs[S_RELGAP] / o.reltol, hs[S_GAP] / std::max(o.abstol, 1e-300));
+        if (L.first_opt < 0 || merit_o < L.opt_merit) {
+            L.opt_merit = merit_o; L.opt_info = info;
+            best = true;
+        }
+        if (L.first_opt < 0) L.first_opt = it;
+        if (hs[S_GAP] <= POLISH * o.abstol || hs[S_RELGAP] <= POLISH * o.reltol) return finish(ST_OPTIMAL);
+    }
+    if (L.first_opt >= 0 && it >= L.first_opt + POLISH_MAX) return finish(ST_OPTIMAL);      // (whether or not this iterate still meets the rule)
+    {   // what this iteration's solves run: the controller's count, POLISH_SWEEPS more in the final approach and the end game
+        const bool approach = finite && (hs[S_GAP] <= sw.polish_approach * o.abstol || hs[S_RELGAP] <= sw.polish_approach * o.reltol);
+        L.nsweep = std::min(MAX_SWEEPS, L.nsweep_ctl + ((approach || L.first_opt >= 0) ? sw.polish_sweeps : 0));
+    }
+    if (!finite) return finish(ST_NUMERICAL);
+    const bool collapsed = hs[S_KAPPA] / hs[S_TAU] >= 1e6;
+    if (L.first_opt < 0 && (hs[S_PINF] <= o.feastol || (collapsed && hs[S_PINF] <= 1e-5))) return finish(ST_PRIMAL_INFEASIBLE);
+    if (L.first_opt < 0 && (hs[S_DINF] <= o.feastol || (collapsed && hs[S_DINF] <= 1e-5))) return finish(ST_DUAL_INFEASIBLE);
+    if (L.first_opt < 0 && hs[S_PRES] <= INACC_FEAS && hs[S_DRES] <= INACC_FEAS) {
+        // best iterate for the reduced-accuracy exit: residuals within the reduced tolerance,
+        // smallest gap measure (mirrors oracle/conic_ipm.py)
+        double merit = std::min(hs[S_RELGAP], hs[S_GAP] / std::max(o.abstol, 1e-300) * o.reltol);
+        if (merit < L.best_merit) {
+            L.best_merit = merit; L.best_info = info; L.have_best = true;
+            best = true;
+        }
+    }
+    if (it == o.max_iter) return finish(ST_MAXIT);
+    // numerical wall (mirrors oracle/conic_ipm.py): the last factorisation replaced pivots and the
+    // residuals are out of the reduced-accuracy range, three iterations in a row
+    L.wall = (int(hs[S_CHOLFIX]) > 0 && (hs[S_PRES] > INACC_FEAS || hs[S_DRES] > INACC_FEAS)) ? L.wall + 1 : 0;
+    if (L.wall >= WALL_ITERS) return finish(ST_NUMERICAL);
+    return best;
+}
+
 struct Solver::Impl {
     int device = 0;
     hipStream_t st = nullptr;
@@ -2251,26 +2455,18 @@ struct Solver::Impl {
     double *bx2, *bz2, *dx2, *dz2, *gdx2, *gdxc, *xbest, *rx, *rz, *GTz, *Gx;
     double *dssa, *wdza, *lds, *bxc, *bzc, *dxc, *dzc, *ds, *dz, *scratch;
     double *kbx, *kbz, *kx, *kz, *kg, *kds, *kdz;        // centrality corrector: right-hand side (kbx stays zero), solution / candidate, its direction
-    bool corrector = true;       // one centrality corrector per iteration (MBFIR_CORRECTOR=0: off; programs without orthant rows never run it)
-    bool corr_plain = true;      // ... its solve is the Cholesky solve alone (MBFIR_CORR_PLAIN=0, a diagnostic: with the refinement sweeps of the other solves)
-    double sigma_max_corr = SIGMA_MAX_CORR;      // (MBFIR_SIGMA_MAX, read once per solve)
-    double polish_approach = POLISH_APPROACH;    // (MBFIR_POLISH_APPROACH, a diagnostic)
-    int polish_sweeps = POLISH_SWEEPS;           // (MBFIR_POLISH_SWEEPS, a diagnostic: 0 = the controller's count alone)
-    bool corr_big = true;        // ... the big cone's products are corrected too (MBFIR_CORR_BIG=0, a diagnostic: the orthant rows alone, round 6's first form)
-    bool corr_guard = true;      // ... and a correction whose unrefined solve leaves more of the dual equation than the iterate's own residual is dropped (MBFIR_CORR_GUARD=0, a diagnostic: taken regardless)
-    // dense row-sharded builds of a program with ONE weight matrix (fir_ap_cvx, fir_linprog): the Gram product goes in ar_chunks
+    SolveSwitches sw;            // the switches of the current solve (read once at its start: none is read in a per-iteration path)
+    // dense row-sharded builds of a program with ONE weight matrix (fir_ap_cvx, fir_linprog): the Gram product goes in sw.ar_chunks
     // launches and the all-reduce of chunk c's packed tiles runs on st2 while chunk c + 1 is computed; the small
     // ingredients (border products, y-y block) follow in one collective and every rank assembles and factorises the same H.
     // MBFIR_AR_OVERLAP=0: the assembled H is summed instead (packed lower triangle, after the build; the only form for programs
     // with three weight matrices, whose T is 3 x the size of H); =2 (diagnostic): the chunked form without shards, collectives skipped
-    int ar_overlap_mode = 1;
     bool ar_overlap = false;
     std::vector<GramChunk> gchunks;
     const int* chunk_tab = nullptr;
     double* Tp = nullptr;
     hipStream_t st2 = nullptr;
     std::vector<hipEvent_t> ovev;            // 2 per chunk: chunk folded (st), chunk summed (st2)
-    int test_cap_kp = 0, ar_chunks = 0;      // MBFIR_TEST_CAP_KP (test hook), MBFIR_AR_CHUNKS (collectives per dense row-sharded build): read ONCE per solve (not in per-iteration paths)
     double *partR, *partR2, *partN, *xout, *hout, *sfwork;
     int nbR = 0, nbN = 0, nbC = 0;
     // extended-precision KKT solve (ddkkt.inc): H = H_w + U'XU and its Cholesky factor in double-double.
@@ -2288,7 +2484,6 @@ struct Solver::Impl {
     double *capYt = nullptr, *capZt = nullptr, *capS = nullptr, *capMs = nullptr, *capW1 = nullptr, *capw = nullptr, *capPart = nullptr;
     int* capflag = nullptr;
     int dd_k = 0;                 // strong directions of the current iteration (0: plain double-precision solve)
-    int dd_iters = 0, dd_kmax_seen = 0;
 
     void ensure_arena(size_t bytes) {
         if (bytes <= ar.cap) { ar.reset(); return; }
@@ -2460,7 +2655,7 @@ struct Solver::Impl {
         if (P.trig) {
             dim3 g(cdiv(P.D1, MPTS), cdiv(P.nchunk, P.cgrp)), b(256);
             const dim3 gf(cdiv(P.nfold, 256));
-            if (fuse_fold) {
+            if (sw.fuse) {
                 if (P.quad) hipLaunchKernelGGL((k_trig_moments<2 * NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
                 else hipLaunchKernelGGL((k_trig_moments<NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
             } else if (P.quad) {
@@ -2491,8 +2686,7 @@ struct Solver::Impl {
     // all-reduces per iteration): the factors are bit-identical across the ranks (same moments, same deterministic
     // assembly and factorisation), the solves with them are local.
     bool lead_factor() const { return shard_size > 1 && P.trig; }
-    // launch fusions of round 5 (MBFIR_FUSE=0: the separate kernels; results are bit-identical either way -- tests/test_switches_gpu.py)
-    bool fuse_fold = true;
+    // (launch fusions of round 5, sw.fuse: results are bit-identical either way -- tests/test_switches_gpu.py)
     int* gt_cnt = nullptr;       // workgroups of the current k_gt_finish that are done (per lane; GtResid)
     // out = M' M (rhs + rhs2)
     template <int NV>
@@ -2523,7 +2717,7 @@ struct Solver::Impl {
         hsolve<NV>(bx, dx, tmpN);                                                           // M'M (bx + G' W^-2 bz)
         apply_G_winv2<NV>(dx, gdx, wbz, dz);
         double* r = rhsN;
-        if (fuse_fold && shard_size <= 1) apply_GT<NV>(dz, tmpN, 0, bx, r, slot);                       // G'dz ; r = bx - G'dz ; n_0
+        if (sw.fuse && shard_size <= 1) apply_GT<NV>(dz, tmpN, 0, bx, r, slot);                       // G'dz ; r = bx - G'dz ; n_0
         else {
         apply_GT<NV>(dz, tmpN);
         hipLaunchKernelGGL(k_resid_norm<NV>, g1, dim3(SCAL_T), 0, st, P, bx, tmpN, r, Sc, slot);      // r = bx - G'dz ; n_0
@@ -2532,9 +2726,9 @@ struct Solver::Impl {
         const int* live = P.mask;
         P.mask = mask_row(1);
         // z = M'M r and the start of the sweep (rz, beta, p): the partial vectors of the one-pass product are added by the kernel
-        // that starts the sweep (fuse_fold; otherwise k_hsolve_fold writes z and k_cg_start reads it)
+        // that starts the sweep (sw.fuse; otherwise k_hsolve_fold writes z and k_cg_start reads it)
         auto z_and_start = [&](int first) {
-            if (fuse_fold && fused_hsolve) {
+            if (sw.fuse && fused_hsolve) {
                 hsolve_launch(M, P.np, r, nullptr, tmpN2, partial, NV, P.LDV, st, nlanes, lane_bytes, P.mask, false);
                 hipLaunchKernelGGL(k_fold_cg_start<NV>, g1, dim3(1024), 0, st, P, Sc, r, partial, pN, first);
             } else {
@@ -2562,14 +2756,14 @@ struct Solver::Impl {
     // synchronisation (the count decides which solve runs).
     // Lock-step units (round 5): every live lane selects ITS strong set (its own cap, its own count); ks[b] <- the lane's count,
     // thetas[b] the lane's cap factor (raised x 100 for a lane whose set does not fit, as in its single solve).  Returns the largest.
+    // the selection's first step (k_dd_prep, and the big cone's row 0): returns the partial rows k_dd_select folds
+    int dd_prep_launch() {
+        hipLaunchKernelGGL(k_dd_prep, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, dl, w3, D, partR);
+        if (P.big) hipLaunchKernelGGL(k_dd_prep_big, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, D, partR);      // (row 0: see k_dd_prep)
+        return std::max(nbC, 1) + (P.big ? 1 : 0);
+    }
     int dd_prepare_lanes(const double theta0, int* ks, const bool* live) {
-        const int nb = std::max(nbC, 1);
-        hipLaunchKernelGGL(k_dd_prep, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, dl, w3, D, partR);
-        int nbp = nb;
-        if (P.big) {
-            hipLaunchKernelGGL(k_dd_prep_big, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, D, partR);      // (row 0: see k_dd_prep)
-            nbp += 1;
-        }
+        const int nb = std::max(nbC, 1), nbp = dd_prep_launch();
         for (int b = 0; b < nlanes; ++b) hostTheta[b] = theta0;
         const int kmax_fit = cap_form ? CAP_KMAX : DD_KMAX;
         for (int attempt = 0; attempt < 8; ++attempt) {
@@ -2595,13 +2789,7 @@ struct Solver::Impl {
     bool dd_unit = false;               // a lock-step unit on the extended-precision path (some of its lanes, some iterations)
     int dd_kp = 0;                      // ... the largest strong set of this iteration, rounded up to 64 (the unit's S is dd_kp x dd_kp)
     int dd_prepare(double theta) {
-        const int nb = std::max(nbC, 1);
-        hipLaunchKernelGGL(k_dd_prep, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, dl, w3, D, partR);
-        int nbp = nb;
-        if (P.big) {
-            hipLaunchKernelGGL(k_dd_prep_big, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, D, partR);      // (row 0: see k_dd_prep)
-            nbp += 1;
-        }
+        const int nb = std::max(nbC, 1), nbp = dd_prep_launch();
         for (int attempt = 0; attempt < 8; ++attempt) {
             if (attempt > 0) hipMemsetAsync(D.kcnt, 0, sizeof(int), st);        // (the first attempt's counter was cleared by k_dd_prep)
             hipLaunchKernelGGL(k_dd_select, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, dl, D, partR, nbp, theta, (const double*)nullptr);
@@ -2638,7 +2826,7 @@ struct Solver::Impl {
                 // y = H_w^-1 rhs_w ; zeta = S^-1 (U y - t) ; dx = y - Zt' zeta   (all double; zeta are the strong directions'
                 // multipliers X (U dx - t) themselves)
                 int kp = int(round_up(k, 64));
-                if (!dd_unit) kp = std::max(kp, test_cap_kp);                                    // test hook (MBFIR_TEST_CAP_KP, read at solve start): pad S as a unit's largest lane would
+                if (!dd_unit) kp = std::max(kp, sw.test_cap_kp);                                 // test hook: pad S as a unit's largest lane would
                 cap_add_launch(rhsN, tmpN2, Bl, P.N, P.np, P.LDV, NV, st, nlanes, lane_bytes, P.mask);                       // rhs_w
                 double* yv = tmpN2;                                                              // (free from here on; yN is hsolve's own intermediate)
                 hsolve<NV>(Bl, yv);                                                              // y
@@ -2825,7 +3013,7 @@ struct Solver::Impl {
             // while the later ones are still queued behind it (MBFIR_AR_CHUNKS; 1 = one collective)
             const long nb = P.np / 64, ntile = nb * (nb + 1) / 2;
             hipLaunchKernelGGL(k_pack_tril, dim3((unsigned)ntile), dim3(256), 0, st, H, P.np, M, 0);
-            const int chunks = int(std::min<long>(ar_chunks > 0 ? ar_chunks : 4, ntile));                    // (MBFIR_AR_CHUNKS, read once at solve start: every rank must issue the same number of collectives)
+            const int chunks = int(std::min<long>(sw.ar_chunks > 0 ? sw.ar_chunks : 4, ntile));              // (read once at solve start: every rank must issue the same number of collectives)
             for (int c = 0; c < chunks; ++c) {
                 const long lo = ntile * c / chunks, hi = ntile * (c + 1) / chunks;
                 allreduce(M + lo * 4096, (hi - lo) * 4096, 0);
@@ -2834,37 +3022,27 @@ struct Solver::Impl {
         }
         hipEvent_t c0 = timing ? next_event() : nullptr, c1 = timing ? next_event() : nullptr;
         P.dd_lane = nullptr; P.dl_plain = nullptr;
-        if (ddk > 0 && cap_form && dd_unit) {
-            // the lanes' H (capped weights on the lanes in the extended-precision mode, plain ones on the others) in one launch, then
-            // the capacitance matrices of the former: launches sized to the unit's largest strong set, a lane's own count read from its
-            // arena, its U / Yt / Zt rows and S rows beyond it zero resp. unit -- what a single solve padded to that size would hold
-            const int kp = dd_kp;
-            const int* mdd = mask_row(ROW_DD);
-            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, nullptr, nlanes, lane_bytes, P.mask);
+        if (ddk > 0 && cap_form) {
+            // capacitance form: the ordinary double-precision factorisation of H_w, then Yt = U M', Zt = Yt M, S = Yt Yt' + X^-1
+            // on the matrix cores and the same factorisation routine on S (kp x kp).  A unit (dd_unit): the lanes' H (capped weights
+            // on the lanes in the extended-precision mode, plain ones on the others) in one launch, then the capacitance matrices of
+            // the former: launches sized to the unit's largest strong set, a lane's own count read from its arena, its U / Yt / Zt
+            // rows and S rows beyond it zero resp. unit -- what a single solve padded to that size would hold
+            const int kp = dd_unit ? dd_kp : std::max(int(round_up(ddk, 64)), sw.test_cap_kp);
+            const size_t lb = dd_unit ? lane_bytes : 0;
+            const int* mdd = mask_row(ROW_DD);                // (one design: no masks)
+            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, nullptr, nlanes, lb, P.mask);
             P.mask = mdd;
-            hipLaunchKernelGGL(k_dd_rows, lane_grid(dim3(kp), nlanes), dim3(256), 0, st, P, D, P.np, -1);
+            hipLaunchKernelGGL(k_dd_rows, lane_grid(dim3(kp), nlanes), dim3(256), 0, st, P, D, P.np, dd_unit ? -1 : ddk);      // (one design: rows ddk .. kp-1 zero padding)
             P.mask = live_mask;
             hipEvent_t b0 = timing ? next_cap_event() : nullptr, b1 = timing ? next_cap_event() : nullptr;
             if (b0) hipEventRecord(b0, st);
-            cap_build_launch(D.U, kp, kp, P.np, M, D.sX, capYt, capZt, capS, capPart, st, nlanes, lane_bytes, mdd, D.kcnt);
-            if (b1) hipEventRecord(b1, st);
-            cap_flop_sum += 2.0 * (double(kp) * P.np * P.np + 0.5 * double(kp) * kp * P.np);
-            chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, nullptr, nullptr, c1, nlanes, lane_bytes, mdd);
-            cap_flag_add_launch(flag, capflag, st, nlanes, lane_bytes, mdd);
-        } else if (ddk > 0 && cap_form) {
-            // capacitance form: the ordinary double-precision factorisation of H_w, then Yt = U M', Zt = Yt M, S = Yt Yt' + X^-1
-            // on the matrix cores and the same factorisation routine on S (kp x kp)
-            const int kp = std::max(int(round_up(ddk, 64)), test_cap_kp);
-            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, nullptr, 1, 0, nullptr);
-            hipLaunchKernelGGL(k_dd_rows, lane_grid(dim3(kp), nlanes), dim3(256), 0, st, P, D, P.np, ddk);      // (rows ddk .. kp-1: zero padding)
-            hipEvent_t b0 = timing ? next_cap_event() : nullptr, b1 = timing ? next_cap_event() : nullptr;
-            if (b0) hipEventRecord(b0, st);
-            cap_build_launch(D.U, ddk, kp, P.np, M, D.sX, capYt, capZt, capS, capPart, st);
+            cap_build_launch(D.U, dd_unit ? kp : ddk, kp, P.np, M, D.sX, capYt, capZt, capS, capPart, st, nlanes, lb, mdd, dd_unit ? D.kcnt : nullptr);
             if (b1) hipEventRecord(b1, st);
             // Yt and Zt: kp x np x np / 2 multiply-adds each (triangular M); S: kp x kp x np / 2 (lower tiles)
             cap_flop_sum += 2.0 * (double(kp) * P.np * P.np + 0.5 * double(kp) * kp * P.np);
-            chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, nullptr, nullptr, c1, 1, 0, nullptr);
-            cap_flag_add_launch(flag, capflag, st);           // pivots replaced in either factorisation count (oracle: chol_fixes += nfs)
+            chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, nullptr, nullptr, c1, nlanes, lb, mdd);
+            cap_flag_add_launch(flag, capflag, st, nlanes, lb, mdd);      // pivots replaced in either factorisation count (oracle: chol_fixes += nfs)
         } else if (ddk > 0) {
             if (c0) hipEventRecord(c0, st);
             hipLaunchKernelGGL(k_dd_rows, lane_grid(dim3(ddk), nlanes), dim3(256), 0, st, P, D, P.np, ddk);
@@ -2876,16 +3054,622 @@ struct Solver::Impl {
             chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, c1, nlanes, lane_bytes, P.mask);
         }
     }
-    // events are recorded as (gram begin, gram end, chol begin, chol end) per build_H
-    void collect_times(double& gram_ms, double& chol_ms, int& builds) {
-        gram_ms = chol_ms = 0;
-        builds = int(evused / 4);
-        for (size_t i = 0; i + 3 < evused; i += 4) {
+    // events are recorded as (gram begin, gram end, chol begin, chol end) per build_H: the builds of evpool[lo, hi) added to
+    // gram_ms, chol_ms with the given sign; returns their number
+    int add_build_times(size_t lo, size_t hi, double sign, double& gram_ms, double& chol_ms) {
+        int builds = 0;
+        for (size_t i = lo; i + 3 < hi; i += 4, ++builds) {
             float a = 0, b = 0;
-            hipEventElapsedTime(&a, evpool[i], evpool[i + 1]);
-            hipEventElapsedTime(&b, evpool[i + 2], evpool[i + 3]);
-            gram_ms += a; chol_ms += b;
+            if (hipEventElapsedTime(&a, evpool[i], evpool[i + 1]) == hipSuccess) gram_ms += sign * a;
+            if (hipEventElapsedTime(&b, evpool[i + 2], evpool[i + 3]) == hipSuccess) chol_ms += sign * b;
         }
+        return builds;
+    }
+
+    // ---- the stages of Solver::solve_lanes ----------------------------------------------------------------------------------
+    // Lane preparation: every lane's program (its row shard when sharded), the WHOLE program's norms, index structures, lattice.
+    void prepare_lanes(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, std::vector<LaneHost>& LH) {
+        // ---- row sharding: this process keeps the frequencies i % size == rank (program.h) ----------
+        shard_rank = o.shard_size > 1 ? o.shard_rank : 0;
+        shard_size = o.shard_size > 1 ? o.shard_size : 1;
+        if (shard_size > 1 && !ar_fn && !comm) throw HipError("row-sharded solve without a communicator or an all-reduce hook");
+        if (comm && shard_size > 1 && (comm_size != shard_size || comm_rank != shard_rank))
+            throw HipError("row-sharded solve: shard_rank / shard_size differ from the RCCL communicator's");
+        n_collectives = 0; collective_bytes = 0;
+        n_gv = 0; n_gtv = 0;
+        if (shard_size > 1 && nlanes > 1) throw ShapeError("row-sharded solves run one design at a time");
+        for (int b = 0; b < nlanes; ++b) {
+            LaneHost& L = LH[b];
+            const TrigProgram& Qfull = *Qs[b];
+            if (shard_size > 1) { L.local = shard_program(Qfull, shard_rank, shard_size); L.Q = &L.local; }
+            else L.Q = &Qfull;
+            // constants of the WHOLE program (identical on every shard)
+            double nh = 0, nc = 0;
+            for (double v : Qfull.h) nh += v * v;
+            for (double v : Qfull.c) nc += v * v;
+            L.nrm_h = std::max(1.0, std::sqrt(nh)); L.nrm_c = std::max(1.0, std::sqrt(nc));
+            L.degree = double(Qfull.l + Qfull.nq3 + (Qfull.big ? 1 : 0));
+            // (the extended-precision KKT solve forms its strong rows from the exact w_i: its programs keep every frequency
+            // on its own so that the lattice operator and those rows see the same grid to the old 2 ulp)
+            L.prep = lane_prep(*L.Q, o, sw);
+            L.Lt = L.prep->Lt;
+            L.nsweep = o.refine; L.nsweep_ctl = o.refine;
+        }
+        if (shard_size > 1 && !o.dense_trig) {
+            // every rank must take the same path (it selects the sequence and the sizes of the collectives): the
+            // lattice path only if EVERY shard has the structure -- a min all-reduce of the local verdicts
+            ensure_arena(4096);
+            double* dv = reinterpret_cast<double*>(ar.base);
+            hostSc[0] = LH[0].Lt.ok ? -1.0 : 0.0;                // min(v) = -max(-v); the collective knows sum and max
+            MBFIR_HIP(hipMemcpyAsync(dv, hostSc, sizeof(double), hipMemcpyHostToDevice, st));
+            allreduce(dv, 1, 1);
+            MBFIR_HIP(hipMemcpyAsync(hostSc, dv, sizeof(double), hipMemcpyDeviceToHost, st));
+            MBFIR_HIP(hipStreamSynchronize(st));
+            if (hostSc[0] > -0.5) LH[0].Lt = LatticeInfo();      // somebody lacks it: dense path everywhere
+        }
+    }
+    // Unit planning: the lanes share one CLASS (designer, slack columns, cone kinds, lattice origin); their grids, row counts, chunk
+    // lists and orders may differ: arrays and launches are sized to the unit's maxima, every lane carries its
+    // own dimensions (DProg::dims).  Also the Gram plans and the unit's solve forms.
+    UnitPlan plan_unit(const std::vector<LaneHost>& LH, const SolveOpts& o) {
+        const TrigProgram& Q = *LH[0].Q;
+        const LatticeInfo& Lt = LH[0].Lt;
+        int Mf_max = Q.Mf, R_max = Q.R, l_max = Q.l, nyrows_max = int(LH[0].prep->yrows.size());
+        int Nt_max = Q.Nt, nq3_max = Q.nq3, big_max = Q.big, D1_max = Lt.D1, n_max = Q.n;
+        size_t nchunk_max = Lt.ch_start.size(), nfold_max = Lt.wf.size();
+        bool hetero = false, orders = false;
+        for (int b = 1; b < nlanes; ++b) {
+            const TrigProgram& Qb = *LH[b].Q;
+            const LatticeInfo& Lb = LH[b].Lt;
+            if (Qb.which != Q.which || Qb.Ne != Q.Ne || (Qb.nq3 > 0) != (Q.nq3 > 0) || (Qb.big > 0) != (Q.big > 0) || Qb.quad != Q.quad ||
+                Lb.ok != Lt.ok || (Lb.tmin == 0.0) != (Lt.tmin == 0.0))
+                throw ShapeError("lock-step batch: lanes differ in class (designer, slack columns, cone kinds, lattice origin at zero or not)");
+            if (Qb.n != Q.n || Qb.Nt != Q.Nt || Qb.nq3 != Q.nq3 || Qb.big != Q.big || Lb.D1 != Lt.D1 || Lb.tmin != Lt.tmin || LH[b].prep->c_rows.size() != LH[0].prep->c_rows.size())
+                hetero = orders = true;
+            if (Qb.Mf != Q.Mf || Qb.R != Q.R || Qb.l != Q.l || LH[b].prep->yrows.size() != LH[0].prep->yrows.size() || Lb.ch_start.size() != Lt.ch_start.size() ||
+                Lb.wf.size() != Lt.wf.size())
+                hetero = true;
+            Mf_max = std::max(Mf_max, Qb.Mf); R_max = std::max(R_max, Qb.R); l_max = std::max(l_max, Qb.l);
+            nyrows_max = std::max(nyrows_max, int(LH[b].prep->yrows.size()));
+            nchunk_max = std::max(nchunk_max, Lb.ch_start.size()); nfold_max = std::max(nfold_max, Lb.wf.size());
+            Nt_max = std::max(Nt_max, Qb.Nt); nq3_max = std::max(nq3_max, Qb.nq3); big_max = std::max(big_max, Qb.big);
+            D1_max = std::max(D1_max, Lb.D1); n_max = std::max(n_max, Qb.n);
+        }
+        auto seg_of = [this](int D1) { return sw.seg > 0 ? sw.seg : std::min(SEGMAX, std::max(64, int(round_up(cdiv(std::max(D1, 1), 16), 8)))); };
+        // what the per-lane dimensions do not cover: different ORDERS on the dense path (the row stride of A1 follows the order).
+        // Different band edges are fine there too since round 5: every lane runs its own Gram plan and folds its own split partials.
+        if (orders && (!Lt.ok || o.dense_trig)) throw ShapeError("lock-step batch: lanes differ in order (dense path)");
+        if (!sw.hetero && hetero) throw ShapeError("lock-step batch: lanes differ in shape (MBFIR_HETERO=0)");
+        // ---- sizes -----------------------------------------------------------------------------
+        UnitPlan U;
+        const int R = R_max, Nt = Nt_max, Ne = Q.Ne, N = Nt_max + Q.Ne, Mf = Mf_max;
+        const int nw = Q.quad ? 3 : 1;
+        // (dense row-sharded build with the chunked, overlapped all-reduce: see Impl::ar_overlap)
+        ar_overlap = !Lt.ok && nw == 1 && nlanes == 1 && ((shard_size > 1 && sw.ar_overlap != 0) || sw.ar_overlap == 2);
+        // (chunks: MBFIR_AR_CHUNKS, else one per 32 tiles, at most 8 -- below that a chunk's product is too short to hide a collective behind)
+        const int gtiles = gram_plan(Mf, Nt, nw).ntiles;
+        const int gfill = ar_overlap ? std::max(1, std::min(sw.ar_chunks > 0 ? sw.ar_chunks : std::min(8, gtiles / 32), gtiles)) : 1;
+        gp = gram_plan(Mf, Nt, nw, gfill);
+        gps.assign(nlanes, gp);
+        for (int b = 0; b < nlanes; ++b) {
+            gps[b] = gram_plan(LH[b].Q->Mf, Nt, nw, gfill);
+            gp.Mpad = std::max(gp.Mpad, gps[b].Mpad); gp.slab_doubles = std::max(gp.slab_doubles, gps[b].slab_doubles);
+        }
+        P.trig = Lt.ok ? 1 : 0;
+        P.D1 = D1_max; P.tmin = Lt.tmin; P.LDL = int(round_up(std::max(D1_max, 1), 64));
+        P.seg = seg_of(D1_max);
+        P.useg = 1;
+        if (Lt.ok) for (int b = 0; b < nlanes; ++b) P.useg = std::max(P.useg, cdiv(LH[b].Lt.D1, seg_of(LH[b].Lt.D1)));      // (launches: the most segments any lane has)
+        P.nchunk = int(nchunk_max); P.nfold = int(nfold_max);
+        P.seeds_shared = 0;
+        if (nlanes > 1 && Lt.ok && sw.share_seeds) {         // sweeps over Peak / ripple keep the grid: one seed table serves the unit
+            bool same = true;
+            for (int b = 1; b < nlanes && same; ++b) {
+                const LatticeInfo& Lb = LH[b].Lt;
+                same = Lb.D1 == Lt.D1 && Lb.tmin == Lt.tmin && Lb.wf == Lt.wf && Lb.ch_w0 == Lt.ch_w0 && Lb.ch_dw == Lt.ch_dw && Lb.ch_start == Lt.ch_start && Lb.ch_count == Lt.ch_count;
+            }
+            P.seeds_shared = same ? 1 : 0;
+        }
+        P.cgrp = sw.cgrp;    // (4 unless set: two pairs of interleaved chunks per block, for one design and for lanes alike -- the same sums in
+                             // both: half the partial-moment traffic of one pair per block -- with four units in flight the solver moves
+                             // 3 TB/s through HBM, and that, not the recurrences, is what the moment kernels then wait for)
+        P.LDM = int(round_up(3 * std::max(D1_max, 1), 256));
+        P.Nt = Nt; P.Ne = Ne; P.N = N; P.Mf = Mf; P.R = R; P.l = l_max; P.nq3 = nq3_max; P.big = big_max; P.quad = Q.quad;
+        P.ld = gp.ld; P.Mpad = gp.Mpad; P.np = int(round_up(N, 64));
+        P.LDV = int(round_up(std::max(P.ld, P.np), 128)); P.Rp = int(round_up(R, 64));
+        P.nyrows = nyrows_max;
+        P.mask = nullptr; P.lane_bytes = 0; P.dims = nullptr; P.Mown = P.Mpad;
+        P.own = shard_rank == 0 ? 1 : 0;                        // (1 when not sharded)
+        if (hetero) {
+            for (int b = 0; b < nlanes; ++b) {
+                const TrigProgram& Qb = *LH[b].Q;
+                const int d1 = LH[b].Lt.D1, sg = seg_of(d1);
+                hostDims[b] = LaneDims{Qb.Mf, Qb.R, Qb.l, int(LH[b].prep->yrows.size()), int(LH[b].Lt.wf.size()), int(LH[b].Lt.ch_start.size()),
+                                       Qb.Nt, Qb.Nt + Qb.Ne, Qb.nq3, Qb.big, d1, sg, LH[b].Lt.ok ? cdiv(d1, sg) : 1, gps[b].Mpad, LH[b].Lt.tmin};
+            }
+            MBFIR_HIP(hipMemcpyAsync(dimsT, hostDims, sizeof(LaneDims) * nlanes, hipMemcpyHostToDevice, st));
+            P.dims = dimsT;
+        }
+        nsplit_at = cdiv(P.Mpad, AT_ROWS);
+        nbR = cdiv(R, 256); nbN = cdiv(N, 256); nbC = cdiv(P.l + P.nq3, 256);
+        if (nbR + 1 > NPART * 64) throw HipError("problem too large for the reduction buffers");
+        U.n_max = n_max;
+        U.lp = Q.which == DES_AP ? specfact_lp(n_max) : 0;
+        for (int b = 0; b < nlanes; ++b) lane_n[b] = LH[b].Q->n;
+        U.tiles.resize(nlanes);
+        for (int b = 0; b < nlanes; ++b) { U.tiles[b].resize(gram_table_ints(gps[b])); gram_tiles_host(gps[b], U.tiles[b].data()); }
+        gchunks.clear();
+        if (ar_overlap) {              // the chunk tables ride behind the tile table
+            std::vector<int> ctab;
+            gram_chunk_tables(gps[0], gfill, ctab, gchunks);
+            U.tiles[0].insert(U.tiles[0].end(), ctab.begin(), ctab.end());
+        }
+        cap_form = sw.ddform < 0 ? o.dd_form == 0 : sw.ddform != 0;      // its capacitance form in plain double (capkkt.hip) or the double-double one
+        // extended-precision KKT solve (ddkkt.inc); lock-step units: in its capacitance form (round 5; the double-double kernels take one design)
+        if (o.ddkkt_theta > 0 && nlanes > 1 && !cap_form) throw ShapeError("lock-step batch: the double-double form of the extended-precision solve runs one design at a time");
+        U.use_dd = o.ddkkt_theta > 0 && shard_size <= 1;
+        dd_unit = U.use_dd && nlanes > 1;
+        dd_kp = 0;
+        // refinement passes around the extended-precision solve: two for the double-double form, THREE for the capacitance form (with
+        // two, a design of BASELINE config 3's batch lost its iterate near the end: DESIGN.md section 5)
+        dd_passes = sw.dd_passes > 0 ? sw.dd_passes : cap_form ? 3 : 2;
+        fused_hsolve = hsolve_fused_ok(P.np, 2) && sw.hsolve;
+        return U;
+    }
+    // Arena layout: the lanes' program arrays (one upload per lane) and the work buffers of ONE lane.  A measuring pass adds up the
+    // sizes; the lanes then sit lane_bytes apart in one arena, and the work buffers start zeroed.
+    void layout_arena(const std::vector<LaneHost>& LH, const UnitPlan& U) {
+        const size_t ld = P.ld, np = P.np, LDV = P.LDV, Rp = P.Rp, Mpad = P.Mpad;
+        const int nw = P.quad ? 3 : 1;
+        char* zero_from = nullptr;
+        size_t zero_bytes = 0;
+        auto place = [&]() {
+        // ---- upload the program (one copy per lane) ----------------------------------------------
+#define UPQ(T, member) upload<T>([&](int b) -> const std::vector<T>& { return LH[b].Q->member; })
+#define UPL(T, member) upload<T>([&](int b) -> const std::vector<T>& { return LH[b].member; })
+        P.w = UPQ(double, w); P.col_kind = UPQ(int, col_kind); P.col_tau = UPQ(double, col_tau);
+        P.col_scale = UPQ(double, col_scale); P.pcol = UPQ(int, pcol); P.psign = UPQ(double, psign);
+        P.c = UPQ(double, c); P.freq = UPQ(int, freq); P.col = UPQ(int, col); P.alpha = UPQ(double, alpha);
+        P.beta = UPQ(double, beta); P.ey = UPQ(double, ey); P.h = UPQ(double, h);
+        P.f_ptr = UPL(int, prep->f_ptr); P.f_rows = UPL(int, prep->f_rows); P.c_ptr = UPL(int, prep->c_ptr); P.c_rows = UPL(int, prep->c_rows);
+        P.yrows = UPL(int, prep->yrows); P.rep = UPL(int, prep->rep);
+        tile_ij = upload<int>([&](int b) -> const std::vector<int>& { return U.tiles[b]; });
+        P.lat = UPL(int, Lt.lat); P.lat_col = UPL(int, Lt.lat_col); P.lat_qcol = UPL(int, Lt.lat_qcol);
+        P.lat_scale = UPL(double, Lt.lat_scale); P.lat_qscale = UPL(double, Lt.lat_qscale);
+        P.ch_start = UPL(int, Lt.ch_start); P.ch_count = UPL(int, Lt.ch_count); P.ch_w0 = UPL(double, Lt.ch_w0); P.ch_dw = UPL(double, Lt.ch_dw);
+        P.fold_pos = UPL(int, Lt.fold_pos); P.fold_neg = UPL(int, Lt.fold_neg); P.wf = UPL(double, Lt.wf);
+#undef UPQ
+#undef UPL
+        if (!ar.measuring) flush_uploads();
+        // ---- work buffers ----------------------------------------------------------------------
+        zero_from = ar.base + ar.off;
+        A1 = ar.get<double>(P.trig ? 0 : Mpad * ld);
+        T = ar.get<double>(P.trig ? 0 : nw * ld * ld);
+        Tp = ar.get<double>(ar_overlap ? (size_t)gps[0].ntiles * 16384 : 0);
+        chunk_tab = ar_overlap ? tile_ij + gram_table_ints(gps[0]) : nullptr;
+        {
+            const size_t nch = std::max(P.nchunk, 1), d1 = std::max(P.D1, 1);
+            P.seed_tau = ar.get<double4>(P.trig ? nch * d1 : 1);
+            P.seed_h = ar.get<double4>(P.trig ? nch * (3 * d1 - 1) : 1);
+            P.seed_eval = ar.get<double4>(P.trig ? (size_t)P.useg * Mpad : 1);
+        }
+        Mom = ar.get<double>(18 * (size_t)P.LDM); MomB = ar.get<double>(12 * (size_t)P.LDM);
+        H = ar.get<double>(np * np); M = ar.get<double>(np * np); Mt = ar.get<double>(np * np); W1 = ar.get<double>(np * np + 65 * np);
+        Sc = ar.get<double>(S_COUNT); flag = ar.get<int>(4); gt_cnt = ar.get<int>(4); RB = ar.get<double>(16);
+        x = ar.get<double>(LDV); tmpN = ar.get<double>(2 * LDV); tmpN2 = ar.get<double>(2 * LDV);
+        rhsN = ar.get<double>(2 * LDV); yN = ar.get<double>(2 * LDV); pN = ar.get<double>(2 * LDV); bx2 = ar.get<double>(2 * LDV);
+        dx2 = ar.get<double>(2 * LDV); rx = ar.get<double>(LDV); GTz = ar.get<double>(LDV + 16);        /* + the mailbox of the residual sums, packed behind G'z */
+        bxc = ar.get<double>(LDV); dxc = ar.get<double>(LDV); qv = ar.get<double>(3 * LDV);
+        XX = ar.get<double>(4 * LDV); TT = ar.get<double>(6 * LDV); TT2 = ar.get<double>(4 * LDV); xout = ar.get<double>(LDV);
+        s = ar.get<double>(Rp); z = ar.get<double>(Rp); lam = ar.get<double>(Rp); dl = ar.get<double>(Rp);
+        wl = ar.get<double>(Rp); w3 = ar.get<double>(4 * (size_t)std::max(P.nq3, 1)); wbb = ar.get<double>(std::max(P.big, 1));
+        tmpR = ar.get<double>(2 * Rp); wbz = ar.get<double>(2 * Rp); wpR = ar.get<double>(2 * Rp); bz2 = ar.get<double>(2 * Rp); dz2 = ar.get<double>(2 * Rp);
+        gdx2 = ar.get<double>(2 * Rp); gdxc = ar.get<double>(Rp); xbest = ar.get<double>(LDV);
+        rz = ar.get<double>(Rp); Gx = ar.get<double>(Rp); dssa = ar.get<double>(Rp); wdza = ar.get<double>(Rp);
+        lds = ar.get<double>(Rp); bzc = ar.get<double>(Rp); dzc = ar.get<double>(Rp); ds = ar.get<double>(Rp);
+        dz = ar.get<double>(Rp); scratch = ar.get<double>(4 * (size_t)std::max(P.big, 1) + 8);
+        kbx = ar.get<double>(LDV); kbz = ar.get<double>(Rp); kx = ar.get<double>(LDV); kz = ar.get<double>(Rp); kg = ar.get<double>(Rp);
+        kds = ar.get<double>(Rp); kdz = ar.get<double>(Rp);
+        UU = ar.get<double>(4 * Mpad * (size_t)P.useg); PP = ar.get<double>(4 * Mpad); PPf = ar.get<double2>(6 * Mpad); Dw = ar.get<double>(9 * Mpad); BB = Dw + (size_t)nw * Mpad;       // border vectors right behind the nw weight vectors
+        partial = ar.get<double>(std::max(P.trig ? (size_t)cdiv(P.nchunk, P.cgrp) * 12 * P.LDM : (size_t)nsplit_at * 6 * ld,
+                                          std::max(hsolve_part_doubles(int(np)), hsolve_part_doubles(CAP_KMAX))));   // (also the partial vectors of the one-pass M'(M b), of H and of the capacitance matrix)
+        partR = ar.get<double>(4 * (size_t)(nbR + 2)); partR2 = ar.get<double>(4 * (size_t)(nbR + 2)); partN = ar.get<double>(4 * (size_t)(nbN + 2));
+        ddinv = nullptr;
+        if (U.use_dd) {
+            D.e3 = ar.get<double>(8 * (size_t)std::max(P.nq3, 1)); D.eb = ar.get<double>(8); D.whb = ar.get<double>(std::max(P.big, 1));
+            D.dlc = ar.get<double>(Rp); D.m3c = ar.get<double>(6 * (size_t)std::max(P.nq3, 1));
+            D.slotl = ar.get<int>(std::max(P.l, 1)); D.slot3 = ar.get<int>(3 * (size_t)std::max(P.nq3, 1)); D.slotb = ar.get<int>(2);
+            D.kcnt = ar.get<int>(1); D.skind = ar.get<int>(DD_KMAX); D.sidx = ar.get<int>(DD_KMAX); D.sdir = ar.get<int>(DD_KMAX);
+            ddtheta = ar.get<double>(MAX_LANES);
+            D.sX = ar.get<double>(DD_KMAX); D.U = ar.get<double>((size_t)DD_KMAX * np);
+            ddB = ar.get<double>(4 * LDV); ddtS = ar.get<double>(2 * (size_t)DD_KMAX); ddzeta = ar.get<double>(2 * (size_t)DD_KMAX);
+            ddri = ar.get<double>(2 * np); ddd0 = ar.get<double>(np);
+            ddflags = ar.get<int>(2 * np / 32 + 8);          // block flags of the multi-workgroup dd solve (zeroed with the arena)
+            ddinv = ar.get<double>(2 * np * 64);
+            if (!sw.dd_blockinv) ddinv = nullptr;
+            if (cap_form) {
+                capYt = ar.get<double>((size_t)CAP_KMAX * np); capZt = ar.get<double>((size_t)CAP_KMAX * np);
+                capS = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX); capMs = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX);
+                capW1 = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX + 65 * (size_t)CAP_KMAX); capw = ar.get<double>(2 * (size_t)DD_KMAX);
+                capflag = ar.get<int>(4);
+                capPart = ar.get<double>(cap_part_doubles(CAP_KMAX, int(np)));
+            }
+        }
+        hout = ar.get<double>(2 * (size_t)U.n_max + 8);
+        sfwork = ar.get<double>(6 * (size_t)std::max(U.lp, 1));
+        zero_bytes = size_t(ar.base + ar.off - zero_from);
+        slab = ar.get<double>(P.trig ? 0 : gp.slab_doubles);
+        };
+        // first pass: only add up the sizes of ONE lane; the lanes then sit lane_bytes apart in one arena
+        ar.measuring = true; ar.reset(); meas_lo = meas_hi = 0;
+        { char* keep = ar.base; ar.base = nullptr; place(); ar.base = keep; }
+        lane_bytes = (ar.off + 4095) & ~size_t(4095); ar.measuring = false;
+        ensure_arena(lane_bytes * nlanes + 4096);
+        pend.clear(); stage_lo = stage_hi = 0;
+        place();
+        P.lane_bytes = lane_bytes;
+        memset_lanes(zero_from, zero_bytes);
+    }
+    // ---- lane masks: row 0 = live lanes, rows q = 1..MAX_SWEEPS: lanes that run CG sweep q, ROW_DD / ROW_PL: the live lanes whose
+    // iteration runs the extended-precision / the plain solve.  mask_dev is what the device holds, mask_new what it is to hold.
+    std::vector<int> mask_dev, mask_new;
+    void push_masks(const std::vector<LaneHost>& LH) {
+        if (nlanes == 1) return;
+        for (int b = 0; b < nlanes; ++b) {
+            mask_new[b] = LH[b].live ? 1 : 0;
+            lane_live[b] = LH[b].live;
+            // (a lane whose iteration runs the extended-precision solve takes no part in the plain solve's sweeps)
+            for (int q = 1; q <= MAX_SWEEPS; ++q) mask_new[q * MAX_LANES + b] = (LH[b].live && LH[b].dd_k == 0 && LH[b].nsweep >= q) ? 1 : 0;
+            mask_new[ROW_DD * MAX_LANES + b] = (LH[b].live && LH[b].dd_k > 0) ? 1 : 0;
+            mask_new[ROW_PL * MAX_LANES + b] = (LH[b].live && LH[b].dd_k == 0) ? 1 : 0;
+        }
+        // rows [off, off + ints) to the device where they changed (most iterations change nothing: the copy is a launch of its own)
+        auto send = [&](size_t off, size_t ints) {
+            if (std::memcmp(mask_new.data() + off, mask_dev.data() + off, sizeof(int) * ints) == 0) return;
+            std::memcpy(hostMask + off, mask_new.data() + off, sizeof(int) * ints);
+            MBFIR_HIP(hipMemcpyAsync(maskT + off, hostMask + off, sizeof(int) * ints, hipMemcpyHostToDevice, st));
+            std::memcpy(mask_dev.data() + off, mask_new.data() + off, sizeof(int) * ints);
+        };
+        send(0, size_t(MAX_SWEEPS + 1) * MAX_LANES);
+        if (dd_unit) send(size_t(ROW_DD) * MAX_LANES, 2 * size_t(MAX_LANES));
+    }
+    // A1 (dense path) or the lattice seed tables, and every lane's initial scalars (norms, degree, tau = kappa = 1, cap on sigma)
+    void start_lanes(const std::vector<LaneHost>& LH) {
+        if (!P.trig) hipLaunchKernelGGL(k_build_A1, lane_grid(dim3(cdiv(P.Nt, 256), P.Mf), nlanes), dim3(256), 0, st, P, A1);
+        else {
+            const int seed_lanes = P.seeds_shared ? 1 : nlanes;
+            hipLaunchKernelGGL(k_build_seeds_m, lane_grid(dim3(cdiv(P.D1, 256), P.nchunk), seed_lanes), dim3(256), 0, st, P, 1.0, P.D1, 0.0, 0,
+                               const_cast<double4*>(P.seed_tau));
+            hipLaunchKernelGGL(k_build_seeds_m, lane_grid(dim3(cdiv(3 * P.D1 - 1, 256), P.nchunk), seed_lanes), dim3(256), 0, st, P, 0.0, P.D1, 2.0,
+                               2 * P.D1 - 1, const_cast<double4*>(P.seed_h));
+            hipLaunchKernelGGL(k_build_seeds_e, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), seed_lanes), dim3(256), 0, st, P, const_cast<double4*>(P.seed_eval));
+        }
+        std::vector<double> sc0((size_t)S_COUNT * nlanes, 0.0);
+        for (int b = 0; b < nlanes; ++b) {
+            double* q = sc0.data() + (size_t)b * S_COUNT;
+            q[S_NRMH] = LH[b].nrm_h; q[S_NRMC] = LH[b].nrm_c; q[S_DEG] = LH[b].degree; q[S_TAU] = 1.0; q[S_KAPPA] = 1.0;
+            q[S_SIGMAX] = (sw.corrector && LH[b].Q->l > 0 && LH[b].Q->big == 0) ? sw.sigma_max_corr : SIGMA_MAX;      // (not with a big cone: oracle/conic_ipm.py)
+            MBFIR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(Sc) + (size_t)b * lane_bytes, q, sizeof(double) * S_COUNT, hipMemcpyHostToDevice, st));
+        }
+    }
+    void cone_shift(double* v) {
+        const int nb = std::max(nbC, 1);
+        hipLaunchKernelGGL(k_cone_resid, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, v, partR);
+        if (P.big) hipLaunchKernelGGL(k_big_cone_resid, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, v, partR);
+        hipLaunchKernelGGL(k_cone_fold, lane_grid(dim3(1), nlanes), dim3(256), 0, st, partR, nb + (P.big ? 1 : 0), RB, lane_bytes, P.mask);
+        allreduce(RB, 1, 1);                          // max of the cone distances
+        allreduce(RB + 1, 1, 0);                      // sum of squares
+        hipLaunchKernelGGL(k_cone_shift, lane_grid(dim3(64), nlanes), dim3(256), 0, st, P, v, RB);
+    }
+    // initial point (W = I): x, s, z from the KKT solve of the initial right-hand sides, s and z shifted into their cones
+    void initial_point(int nsweep) {
+        hipLaunchKernelGGL(k_unit_scaling, lane_grid(dim3(cdiv(std::max(std::max(P.l, P.nq3), std::max(P.big, 1)), 256)), nlanes), dim3(256), 0, st,
+                           P, dl, wl, w3, wbb, Sc);
+        build_H();
+        hipLaunchKernelGGL(k_init_rhs, lane_grid(dim3(cdiv(std::max(P.N, P.R), 256)), nlanes), dim3(256), 0, st, P, bx2, bz2);
+        kkt_solve<2>(bx2, bz2, dx2, dz2, gdx2, nsweep, S_RNA);
+        copy_lanes(x, dx2, sizeof(double) * P.LDV);
+        hipLaunchKernelGGL(k_neg_copy_r, lane_grid(dim3(cdiv(P.R, 256)), nlanes), dim3(256), 0, st, P, dz2, s, -1.0);
+        cone_shift(s);
+        hipLaunchKernelGGL(k_neg_copy_r, lane_grid(dim3(cdiv(P.R, 256)), nlanes), dim3(256), 0, st, P, dz2 + P.Rp, z, 1.0);
+        cone_shift(z);
+    }
+    // the residual kernels of an iterate (everything up to the one copy + synchronisation per iteration)
+    void launch_residuals() {
+        // row-sharded: the four row sums (||rz||^2, s'z, h'z, ||Gx + s||^2) are folded into a mailbox directly behind G'z and
+        // summed over the ranks by the same all-reduce (they do not depend on G'z)
+        const bool sharded = shard_size > 1;
+        double* rmail = sharded ? GTz + P.LDV : RB;
+        if (P.trig) {                                     // G x rows are formed inside k_resid_rows
+            ++n_gv;
+            hipLaunchKernelGGL(k_trig_eval<1>, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), nlanes), dim3(256), 0, st, P, x, UU);
+            hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(nbR), nlanes), dim3(256), 0, st, P, nullptr, s, z, Sc, rz, bz2, partR, UU, x);
+        } else {
+            apply_G<1>(x, Gx);
+            hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(nbR), nlanes), dim3(256), 0, st, P, Gx, s, z, Sc, rz, bz2, partR, nullptr, nullptr);
+        }
+        if (sharded) hipLaunchKernelGGL(k_scal_resid, dim3(1), dim3(SCAL_T), 0, st, P, Sc, GTz, x, rx, bx2, partR, nbR, rmail, 0, (const int*)flag);
+        apply_GT<1>(z, GTz, sharded ? 5 : 0);
+        hipLaunchKernelGGL(k_scal_resid, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, GTz, x, rx, bx2, partR, nbR, rmail, sharded ? 1 : 2, (const int*)flag);
+    }
+    // The head of an iteration -- NT scaling, normal matrix, factorisation: everything that depends on the iterate (s, z) alone.
+    // On the extended-precision path it first takes every live lane's strong set (a host synchronisation).
+    void launch_head(std::vector<LaneHost>& LH, const SolveOpts& o) {
+        hipLaunchKernelGGL(k_scaling, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, s, z, dl, wl, w3, lam, bz2, wbz);
+        if (P.big) hipLaunchKernelGGL(k_big_scaling, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, s, z, wbb, lam, Sc);
+        int ks[MAX_LANES];
+        if (dd_unit) {
+            // every live lane its own strong set; then the masks of the two modes (the sweep rows follow: push_masks)
+            bool lv[MAX_LANES];
+            for (int b = 0; b < nlanes; ++b) lv[b] = LH[b].live;
+            dd_k = dd_prepare_lanes(o.ddkkt_theta, ks, lv);
+            dd_kp = int(round_up(std::max(dd_k, 1), 64));
+        } else {
+            ks[0] = dd_k = (o.ddkkt_theta > 0 && shard_size <= 1) ? dd_prepare(o.ddkkt_theta) : 0;
+        }
+        for (int b = 0; b < (dd_unit ? nlanes : 1); ++b) {
+            LH[b].dd_k = ks[b];
+            if (ks[b] > 0) { LH[b].dd_iters += 1; LH[b].dd_kmax = std::max(LH[b].dd_kmax, ks[b]); }
+        }
+        if (dd_unit) push_masks(LH);
+        build_H(dd_k);
+    }
+    // the KKT solve of one right-hand side block on every live lane: the extended-precision solve where the strong set is non-empty,
+    // the plain one with `nsweep` refinement sweeps elsewhere, each under its mask (every lane the sequence of its single solve)
+    template <int NV>
+    void solve_modes(bool dd_any, bool pl_any, const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot, int nsweep) {
+        const int* live_row = P.mask;
+        if (dd_any) {
+            if (dd_unit) P.mask = mask_row(ROW_DD);
+            kkt_solve_dd<NV>(bx, bz, dx, dz, gdx, slot);
+        }
+        if (pl_any) {
+            if (dd_unit) P.mask = mask_row(ROW_PL);
+            kkt_solve<NV>(bx, bz, dx, dz, gdx, nsweep, slot, true);  // W^-2 bz came with k_scaling / k_comb_rhs / k_corr_rhs
+        }
+        P.mask = live_row;
+    }
+    // the cone products of direction (xx2, zz2) with the predictor's z1 = dz2; row-sharded: summed over the ranks (k_scal_dtau).
+    // Returns the number of partial rows (unsharded: k_dir_post folds them itself)
+    int dots(const double* xx2, const double* zz2, int mode) {
+        hipLaunchKernelGGL(k_dots_r, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, dz2, zz2, partR);
+        int nb = std::max(nbC, 1);
+        if (P.big) {
+            hipLaunchKernelGGL(k_big_dots, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, dz2, zz2, scratch, partR);
+            nb += 1;
+        }
+        if (shard_size > 1) {
+            hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 0);
+            allreduce(RB, 3, 0);
+            hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 1);
+        }
+        return nb;
+    }
+    // the direction's ds / dz and step maxima; the maxima go to partR2 (k_dir_post reads the k_dots_r partials in partR while it
+    // writes them).  Returns the number of partial rows
+    int dir_post(const double* xx2, const double* zz2, const double* gg2, double* outA, double* outB, int mode, int ndots) {
+        int nb = std::max(nbC, 1);
+        hipLaunchKernelGGL(k_dir_post, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, wl, w3, lam, dz2, zz2, gdx2, gg2, rz, Sc, outA, outB,
+                           partR2, mode, shard_size > 1 ? nullptr : partR, ndots, xx2);
+        if (P.big) {
+            hipLaunchKernelGGL(k_big_dir_post, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, dz2, zz2, gdx2, gg2, rz, Sc, outA, outB,
+                               scratch, partR2, mode);
+            nb += 1;
+        }
+        return nb;
+    }
+    // k_scal_step on the step maxima of dir_post: row-sharded in two phases around an all-reduce, otherwise (where `unsharded`) in one
+    void scal_step(int mode, int nb, bool unsharded) {
+        if (shard_size > 1) {
+            hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 0);
+            allreduce(RB, 2, 1);
+            hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 1);
+        } else if (unsharded) {
+            hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 2);
+        }
+    }
+    // The body of an iteration: the head (unless it went out ahead of the verdicts), predictor, combined direction, update or corrector
+    void launch_iteration(std::vector<LaneHost>& LH, const SolveOpts& o, bool head_out, int nsweep, bool use_corr) {
+        if (!head_out) launch_head(LH, o);
+        const bool sharded = shard_size > 1;
+        const int nN = cdiv(std::max(P.N, P.R), 256);
+        bool dd_any = dd_k > 0, pl_any = dd_k == 0;
+        if (dd_unit) {
+            pl_any = false;
+            for (int b = 0; b < nlanes; ++b) pl_any = pl_any || (LH[b].live && LH[b].dd_k == 0);
+        }
+        // constant + affine systems in one batch: [x1 z1], [x2 z2]
+        solve_modes<2>(dd_any, pl_any, bx2, bz2, dx2, dz2, gdx2, S_RNA, nsweep);
+        double *x2a = dx2 + P.LDV, *z2a = dz2 + P.Rp, *g2a = gdx2 + P.Rp;
+        const int nd0 = dots(x2a, z2a, 0);
+        const int ns0 = dir_post(x2a, z2a, g2a, dssa, wdza, 0, nd0);
+        scal_step(0, ns0, false);
+        // combined direction (unsharded: sigma and bx are formed inside k_comb_rhs, and W^-2 bz comes with it)
+        hipLaunchKernelGGL(k_comb_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, lam, dssa, wdza, rz, Sc,
+                           lds, bzc, sharded ? nullptr : partR2, ns0, rx, bxc, dl, wbz);
+        if (P.big)
+            hipLaunchKernelGGL(k_big_comb_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, dssa, wdza, rz, Sc, lds, bzc, scratch);
+        solve_modes<1>(dd_any, pl_any, bxc, bzc, dxc, dzc, gdxc, S_RNB, nsweep);
+        const int nd1 = dots(dxc, dzc, 1);
+        const int ns1 = dir_post(dxc, dzc, gdxc, ds, dz, 1, nd1);
+        if (!use_corr) {
+            scal_step(1, ns1, !sw.fuse);                  // (sw.fuse: k_update forms the step length itself)
+            hipLaunchKernelGGL(k_update, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, x, ds, dz, s, z,
+                               (!sharded && sw.fuse) ? (const double*)partR2 : (const double*)nullptr, ns1);
+            return;
+        }
+        // ---- one centrality corrector (round 6; oracle/conic_ipm.py solve(): CORR_*) -------------------------------------------
+        // the step of the predictor-corrector direction is measured but not taken (k_scal_step mode 2); the orthant rows' products
+        // at the trial step alpha0 + CORR_DELTA, projected onto the box around sigma mu, give one more right-hand side for the
+        // factorisation at hand; the candidate (predictor-corrector + corrector solution) gets its own direction and step
+        // (mode 3: own dtau / dkappa slots), k_scal_step picks the longer step by CORR_ACCEPT and moves tau, kappa, k_update_pick
+        // moves x, s, z along the direction picked.  Every lane decides for itself.
+        // (extended-precision iterations: the corrector works on the orthant rows alone, with the usual passes: oracle/conic_ipm.py)
+        const int corr_cones = (!sw.corr_big || (!dd_unit && dd_any)) ? 0 : 1;                 // one design: this iteration's mode ...
+        const int* corr_ddm = (dd_unit && dd_any) ? mask_row(ROW_DD) : nullptr;               // ... a unit: lane by lane
+        scal_step(2, ns1, true);
+        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz);
+        if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, ds, dz, Sc, kbz, scratch, corr_cones, corr_ddm);
+        // the Cholesky solve and its residual norm (S_RNC), no sweeps (lanes on the extended-precision path: their usual passes)
+        solve_modes<1>(dd_any, pl_any, kbx, kbz, kx, kz, kg, S_RNC, sw.corr_plain ? 0 : nsweep);
+        hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
+        const int ndC = dots(kx, kz, 3);
+        const int nsC = dir_post(kx, kz, kg, kds, kdz, 3, ndC);
+        scal_step(sw.corr_guard ? 3 : 4, nsC, true);
+        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z);
+    }
+    // The host's verdicts on the iterate in hostSc; lanes with a new best iterate get xbest = x / tau.  Returns whether any lane goes on.
+    bool judge_lanes(std::vector<LaneHost>& LH, const SolveOpts& o, int it) {
+        bool any_live = false, any_best = false;
+        for (int b = 0; b < nlanes; ++b) hostMask[ROW_BEST * MAX_LANES + b] = 0;      // 1: the lane has a new best iterate
+        for (int b = 0; b < nlanes; ++b) {
+            LaneHost& L = LH[b];
+            if (!L.live) continue;
+            const double* hs = hostSc + (size_t)b * S_COUNT;
+            const int chol_fixes = int(hs[S_CHOLFIX]);
+            // a hand-off between workgroups inside the factorisation (or the extended-precision triangular solve) was
+            // lost: its bounded poll expired and the block went on with stale data -- the numbers are void
+            if (chol_fixes >= CHOL_SYNC_LOST) throw HipError("internal error: an in-launch hand-off of the KKT factorisation timed out (device flag never raised)");
+            if (o.verbose)
+                fprintf(stderr, "%s%3d pcost % .10e dcost % .10e gap %.2e pres %.1e dres %.1e k/t %.1e mu %.1e a %.3f sig %.1e sweeps %d chol %d%s\n",
+                        nlanes > 1 ? ("[" + std::to_string(b) + "] ").c_str() : "", it, hs[S_PCOST], hs[S_DCOST], hs[S_GAP], hs[S_PRES],
+                        hs[S_DRES], hs[S_KAPPA] / hs[S_TAU], hs[S_MU], hs[S_ALPHA], hs[S_SIGMA], L.nsweep, chol_fixes,
+                        L.dd_k > 0 ? [&] { char bf[200]; std::snprintf(bf, sizeof(bf), " | k %d refinement norms %.2e -> %.2e -> %.2e , %.2e -> %.2e -> %.2e", L.dd_k,
+                                       hs[S_RNA], hs[S_RNA + 1], dd_passes > 2 ? hs[S_RNA + 2] : 0.0, hs[S_RNB], hs[S_RNB + 1], dd_passes > 2 ? hs[S_RNB + 2] : 0.0);
+                                       return std::string(bf); }().c_str() : "");
+            if (lane_verdict(L, hs, o, it, sw)) {
+                hostMask[ROW_BEST * MAX_LANES + b] = 1;
+                any_best = true;
+            }
+            any_live = any_live || L.live;
+        }
+        if (any_best) {
+            // xbest = x / tau on the lanes with a new best iterate -- including a lane that max_iter (or the numerical
+            // wall) retires in this very iteration: its best_info is this iterate's, so xbest has to be as well (the
+            // new-best bits were cleared for every lane above and are set by the merit test alone, not by `live`)
+            if (nlanes > 1) {
+                MBFIR_HIP(hipMemcpyAsync(maskT + ROW_BEST * MAX_LANES, hostMask + ROW_BEST * MAX_LANES, sizeof(int) * MAX_LANES,
+                                         hipMemcpyHostToDevice, st));
+                P.mask = mask_row(ROW_BEST);
+            }
+            hipLaunchKernelGGL(k_finish_x, lane_grid(dim3(nbN), nlanes), dim3(256), 0, st, P, x, Sc, xbest);
+            P.mask = mask_row(0);
+        }
+        return any_live;
+    }
+    // ---- launch graphs (round 4, opt-in: MBFIR_GRAPH=1; single, unsharded designs without the extended-precision path; DESIGN.md
+    // section 5): the body of an iteration and the next iterate's residuals, captured once per refinement-sweep count and replayed
+    // with one hipGraphLaunch.  A graph holds its event pairs evpool[ev_lo, ev_hi) and what one replay adds to the solve's counters.
+    struct IterGraph { hipGraphExec_t exec = nullptr; size_t ev_lo = 0, ev_hi = 0; long chol_launches = 0, n_gv = 0, n_gtv = 0; };
+    std::map<int, IterGraph> graphs;         // per refinement-sweep count
+    const IterGraph* last_graph = nullptr;   // the replay whose phase timings are still to be read
+    double graph_ms_gram = 0, graph_ms_chol = 0;
+    int graph_builds = 0;
+    // replay the iteration of `nsweep` sweeps (captured on first use); false: this runtime does not capture the sequence
+    bool replay_graph(std::vector<LaneHost>& LH, const SolveOpts& o, int nsweep, bool use_corr) {
+        auto g = graphs.find(nsweep);
+        if (g == graphs.end()) {
+            IterGraph ig;
+            ig.ev_lo = evused;
+            const long chol0 = chol_launch_count, gv0 = n_gv, gtv0 = n_gtv;
+            hipGraph_t graph = nullptr;
+            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
+            if (e == hipSuccess) {
+                launch_iteration(LH, o, false, nsweep, use_corr);
+                launch_residuals();
+                e = hipStreamEndCapture(st, &graph);
+            }
+            if (e == hipSuccess) e = hipGraphInstantiate(&ig.exec, graph, nullptr, nullptr, 0);
+            if (graph) hipGraphDestroy(graph);
+            ig.ev_hi = evused;
+            ig.chol_launches = chol_launch_count - chol0; ig.n_gv = n_gv - gv0; ig.n_gtv = n_gtv - gtv0;
+            chol_launch_count = chol0; n_gv = gv0; n_gtv = gtv0;       // (counted per replay below; a capture runs nothing)
+            if (e != hipSuccess || !ig.exec) {
+                (void)hipGetLastError();
+                evused = ig.ev_lo;
+                return false;
+            }
+            g = graphs.emplace(nsweep, ig).first;
+        }
+        MBFIR_HIP(hipGraphLaunch(g->second.exec, st));
+        chol_launch_count += g->second.chol_launches; n_gv += g->second.n_gv; n_gtv += g->second.n_gtv;
+        last_graph = &g->second;
+        return true;
+    }
+    void drop_graphs() {
+        for (auto& g : graphs) hipGraphExecDestroy(g.second.exec);
+        graphs.clear(); last_graph = nullptr;
+        graph_ms_gram = graph_ms_chol = 0; graph_builds = 0;
+    }
+    // after the wait: the phase timings of the replay just finished
+    void read_graph_times() {
+        if (last_graph && timing) graph_builds += add_build_times(last_graph->ev_lo, last_graph->ev_hi, 1.0, graph_ms_gram, graph_ms_chol);
+        last_graph = nullptr;
+    }
+    // Finish: every lane's answer (the best iterate that met the stopping rule, a reduced-accuracy candidate, or x / tau) and report
+    void finish_lanes(std::vector<LaneHost>& LH, const SolveOpts& o, std::vector<std::vector<double>>& xouts, std::vector<SolveInfo>& infos,
+                      double t_begin, double t_assembled) {
+        P.mask = nullptr;                                         // the final x / tau of every lane, finished or not
+        hipLaunchKernelGGL(k_finish_x, lane_grid(dim3(nbN), nlanes), dim3(256), 0, st, P, x, Sc, xout);
+        xouts.assign(nlanes, std::vector<double>());
+        infos.assign(nlanes, SolveInfo());
+        for (int b = 0; b < nlanes; ++b) {
+            LaneHost& L = LH[b];
+            if (L.live) L.status = ST_MAXIT;
+            char* xo = reinterpret_cast<char*>(xout) + (size_t)b * lane_bytes;
+            if (L.first_opt >= 0) {
+                // an iterate met the stopping rule: the best of them (xbest) is the answer, however the end game ended -- its target,
+                // its iteration cap, max_iter, the numerical wall, a non-finite iterate
+                const SolveInfo last = L.info;
+                L.info = L.opt_info; L.info.iters = last.iters; L.info.correctors = last.correctors; L.info.correctors_taken = last.correctors_taken;
+                L.status = ST_OPTIMAL;
+                MBFIR_HIP(hipMemcpyAsync(xo, reinterpret_cast<char*>(xbest) + (size_t)b * lane_bytes, sizeof(double) * P.LDV, hipMemcpyDeviceToDevice, st));
+            } else if ((L.status == ST_MAXIT || L.status == ST_NUMERICAL) && L.have_best && L.best_info.pres <= INACC_FEAS &&
+                L.best_info.dres <= INACC_FEAS && (L.best_info.relgap <= INACC_GAP || L.best_info.gap <= o.abstol)) {
+                // the reference accepts CVX's 'Inaccurate/Solved' (fir_ap_cvx.m:176): reduced tolerances
+                const int keep_it = L.info.iters;
+                L.info = L.best_info; L.info.iters = keep_it;
+                L.status = ST_OPTIMAL_INACCURATE;
+                MBFIR_HIP(hipMemcpyAsync(xo, reinterpret_cast<char*>(xbest) + (size_t)b * lane_bytes, sizeof(double) * P.LDV, hipMemcpyDeviceToDevice, st));
+            }
+            const int Nb = L.Q->N();                              // (the lane's own unknowns: N is the unit's largest)
+            xouts[b].assign(Nb, 0.0);
+            MBFIR_HIP(hipMemcpyAsync(xouts[b].data(), xo, sizeof(double) * Nb, hipMemcpyDeviceToHost, st));
+        }
+        MBFIR_HIP(hipStreamSynchronize(st));
+        const double t_end = now_ms();
+        // every event pair of the pool once; a graph's pairs were read after every replay: its single reading gives way to those
+        double ms_gram = 0, ms_chol = 0;
+        int builds = add_build_times(0, evused, 1.0, ms_gram, ms_chol);
+        if (!graphs.empty()) {
+            for (auto& g : graphs) builds -= add_build_times(g.second.ev_lo, g.second.ev_hi, -1.0, ms_gram, ms_chol);
+            ms_gram += graph_ms_gram; ms_chol += graph_ms_chol; builds += graph_builds;
+        }
+        drop_graphs();
+        double ms_cap = 0;
+        for (size_t i = 0; i + 1 < capev_used; i += 2) { float t = 0; hipEventElapsedTime(&t, capev[i], capev[i + 1]); ms_cap += t; }
+        const int nw = P.quad ? 3 : 1;
+        for (int b = 0; b < nlanes; ++b) {
+            SolveInfo& info = infos[b];
+            info = LH[b].info;
+            info.status = LH[b].status;
+            info.ms_assemble = t_assembled - t_begin;
+            info.ms_solve = t_end - t_assembled;                  // of the whole lock-step batch
+            info.ms_gram = ms_gram; info.ms_chol = ms_chol; info.h_builds = builds;
+            info.n_freq = LH[b].Q->Mf; info.n_rows = LH[b].Q->R; info.n_unknowns = LH[b].Q->N();
+            info.lattice = P.trig;
+            info.lanes = nlanes;
+            info.collectives = int(n_collectives);
+            info.collective_bytes = collective_bytes;
+            info.gv_passes = int(n_gv); info.gtv_passes = int(n_gtv);
+            info.dd_iters = LH[b].dd_iters; info.dd_kmax = LH[b].dd_kmax;
+            info.dd_form = cap_form ? 0 : 1; info.cap_flop = cap_flop_sum; info.ms_cap = ms_cap;
+            info.chol_launches = int(chol_launch_count);
+            info.chol_flop = 2.0 / 3.0 * double(P.np) * double(P.np) * double(P.np);
+            info.gram_flop = P.trig ? double(3 * P.D1 - 1) * double(LH[b].Q->Mf) * (4.0 + 4.0 * nw)      // rotation + 2 fma per weight, per point and frequency
+                                    : double(nw) * double(P.Mf) * double(P.Nt) * double(P.Nt + 1);
+        }
+        nlanes_last = nlanes; taps_valid = false;
     }
 };
 
@@ -2973,81 +3757,9 @@ void Solver::comm_destroy() {
 }
 void Solver::set_allreduce(int (*fn)(void*, long, int, void*), void* user) { impl->ar_fn = fn; impl->ar_user = user; }
 
-static double now_ms() {
-    using namespace std::chrono;
-    return duration<double, std::milli>(steady_clock::now().time_since_epoch()).count();
-}
-
-// Host-side description of one lane (one design of a lock-step batch)
-struct LaneHost {
-    const TrigProgram* Q = nullptr;
-    TrigProgram local;                       // the row shard (sharded solves have one lane)
-    std::vector<int> f_ptr, f_rows, c_ptr, c_rows, yrows, rep;
-    LatticeInfo Lt;
-    double nrm_h = 1, nrm_c = 1, degree = 0;
-    // IPM state
-    int status = ST_MAXIT, nsweep = 0 /* sweeps the iteration's solves run */, nsweep_ctl = 0 /* ... of which the controller asks for (the rest: POLISH_SWEEPS) */, wall = 0, iters = 0;
-    bool live = true, have_best = false;
-    double best_merit = 1e300, rx_prev = 0;
-    SolveInfo info, best_info;
-    // end game (oracle/conic_ipm.py POLISH): the first iteration whose iterate met the stopping rule, the best such iterate's merit and report
-    // (its x / tau is in xbest: once an iterate has met the rule the reduced-accuracy candidate that buffer held is of no use)
-    int first_opt = -1;
-    double opt_merit = 1e300;
-    SolveInfo opt_info;
-    // extended-precision path: strong directions of the current iteration (0: the plain solve), iterations on it, its largest set
-    int dd_k = 0, dd_iters = 0, dd_kmax = 0;
-};
-
-static void index_structures(const TrigProgram& Q, LaneHost& L) {
-    const int R = Q.R, Nt = Q.Nt, Mf = Q.Mf;
-    L.f_ptr.assign(Mf + 1, 0); L.c_ptr.assign(Nt + 1, 0); L.f_rows.clear(); L.c_rows.clear(); L.yrows.clear();
-    for (int r = 0; r < R; ++r) {
-        if (Q.freq[r] >= 0) L.f_ptr[Q.freq[r] + 1]++;
-        if (Q.col[r] >= 0) L.c_ptr[Q.col[r] + 1]++;
-        if (Q.ey[3 * r] != 0 || Q.ey[3 * r + 1] != 0 || Q.ey[3 * r + 2] != 0) L.yrows.push_back(r);
-        if (Q.freq[r] >= 0 && r >= Q.l) {
-            int a = (r - Q.l) % 3;
-            if (r >= Q.l + 3 * Q.nq3 || a == 0) throw HipError("unsupported cone layout (trig row at cone position 0 / in big cone)");
-        }
-    }
-    for (int i = 0; i < Mf; ++i) L.f_ptr[i + 1] += L.f_ptr[i];
-    for (int j = 0; j < Nt; ++j) L.c_ptr[j + 1] += L.c_ptr[j];
-    L.f_rows.resize(L.f_ptr[Mf]); L.c_rows.resize(L.c_ptr[Nt]);
-    std::vector<int> fp(L.f_ptr.begin(), L.f_ptr.end() - 1), cp(L.c_ptr.begin(), L.c_ptr.end() - 1);
-    for (int r = 0; r < R; ++r) {
-        if (Q.freq[r] >= 0) L.f_rows[fp[Q.freq[r]]++] = r;
-        if (Q.col[r] >= 0) L.c_rows[cp[Q.col[r]]++] = r;
-    }
-}
-
-// Two programs can share a lock-step batch when every array the device holds for them has the same length and
-// the scalar structure the kernels are launched with is the same: dimensions, lattice extent and chunk count.
-// index structures + lattice analysis of one program, kept with the program (TrigProgram::prep) so that the batch
-// front end can compute them in its parallel assembly threads and the solve does not repeat them
-struct LanePrep {
-    bool fold = true, dense = false;
-    std::vector<int> f_ptr, f_rows, c_ptr, c_rows, yrows, rep;
-    LatticeInfo Lt;
-};
-static std::shared_ptr<LanePrep> lane_prep(const TrigProgram& Q, const SolveOpts& o) {
-    const bool fold = o.ddkkt_theta <= 0, dense = o.dense_trig != 0;
-    if (Q.prep) {
-        auto have = std::static_pointer_cast<LanePrep>(Q.prep);
-        if (have->fold == fold && have->dense == dense) return have;
-    }
-    auto pr = std::make_shared<LanePrep>();
-    pr->fold = fold; pr->dense = dense;
-    LaneHost L;
-    index_structures(Q, L);
-    pr->f_ptr.swap(L.f_ptr); pr->f_rows.swap(L.f_rows); pr->c_ptr.swap(L.c_ptr); pr->c_rows.swap(L.c_rows); pr->yrows.swap(L.yrows);
-    pr->rep = replicated_rows(Q);
-    if (!dense) pr->Lt = analyse_lattice(Q, fold);
-    Q.prep = pr;
-    return pr;
-}
 std::vector<long> Solver::shape_key(const TrigProgram& Q, const SolveOpts& o) {
-    const std::shared_ptr<LanePrep> pr = lane_prep(Q, o);
+    const SolveSwitches sw = read_switches();
+    const std::shared_ptr<LanePrep> pr = lane_prep(Q, o, sw);
     const LatticeInfo& Lt = pr->Lt;
     // (the lattice origin itself is a per-lane dimension since round 6 -- the centred delays of fir_qprog_phs / fir_qp_cvx move it with
     //  the order --; what a unit shares is whether it is ZERO: then the border moments ride the difference progression, build_H's one_pass)
@@ -3064,12 +3776,8 @@ std::vector<long> Solver::shape_key(const TrigProgram& Q, const SolveOpts& o) {
     // round 3's rule everywhere), the exact shape: grid, rows, chunks
     // (round 5: on the dense path the ORDER stays part of the key -- A1's row stride follows it --, the band edges no longer do)
     const bool dense = !Lt.ok || o.dense_trig;
-    bool exact = false;
-    if (const char* ev = std::getenv("MBFIR_HETERO")) exact = std::atoi(ev) == 0;
-    if (const char* ev = std::getenv("MBFIR_HETERO_DENSE")) exact = exact || (dense && std::atoi(ev) == 0);
-    int hetero_orders = 1;
-    if (const char* ev = std::getenv("MBFIR_HETERO_ORDERS")) hetero_orders = std::atoi(ev);
-    if (exact || dense || !hetero_orders) {                   // (round 4's rule: one order per unit)
+    const bool exact = !sw.hetero || (dense && !sw.hetero_dense);
+    if (exact || dense || !sw.hetero_orders) {                   // (round 4's rule: one order per unit)
         const long ord[] = {long(Q.n), long(Q.Nt), long(Q.nq3), long(Q.big), long(pr->c_rows.size()), long(Lt.D1)};
         key.insert(key.end(), std::begin(ord), std::end(ord));
     }
@@ -3083,7 +3791,8 @@ void Solver::test_fold(const double* w, int Mf, int fold, long* out) {
     TrigProgram Q;
     Q.Nt = 1; Q.Mf = Mf; Q.w.assign(w, w + Mf);
     Q.col_kind = {0}; Q.col_tau = {0.0}; Q.col_scale = {1.0}; Q.pcol = {0}; Q.psign = {0.0};
-    const LatticeInfo L = analyse_lattice(Q, fold != 0);
+    const SolveSwitches sw = read_switches();
+    const LatticeInfo L = analyse_lattice(Q, sw.fold < 0 ? fold != 0 : sw.fold != 0, sw.chunk);
     long pairs = 0, longest = 0, bad = 0;
     std::vector<int> seen(Mf, 0);
     double wmax = 1.0;
@@ -3109,21 +3818,18 @@ int Solver::max_lanes(const TrigProgram& Q, const SolveOpts& o) {
     if (o.shard_size > 1) return 1;
     // (round 5: the extended-precision solve takes lock-step units too, in its capacitance form -- every lane switches to it when
     //  ITS strong set is non-empty, as its single solve does; MBFIR_DD_LANES=0: one design at a time as before)
-    bool dd_lanes = o.ddkkt_theta > 0 && o.dd_form == 0;
-    if (const char* ev = std::getenv("MBFIR_DDFORM")) dd_lanes = dd_lanes && std::strcmp(ev, "dd") != 0;
-    if (const char* ev = std::getenv("MBFIR_DD_LANES")) dd_lanes = dd_lanes && std::atoi(ev) != 0;
+    const SolveSwitches sw = read_switches();
+    const bool dd_lanes = o.ddkkt_theta > 0 && o.dd_form == 0 && sw.ddform != 0 && sw.dd_lanes;
     if (o.ddkkt_theta > 0 && !dd_lanes) return 1;
     long np = round_up(Q.N(), 64);
-    if (!(o.dense_trig || !lane_prep(Q, o)->Lt.ok)) {        // (lattice path: designs of one size bucket share units -- shape_key -- and a unit
+    const bool lattice = !o.dense_trig && lane_prep(Q, o, sw)->Lt.ok;
+    if (lattice) {        // (lattice path: designs of one size bucket share units -- shape_key -- and a unit
         long bucket = 64;                                     //  is as large as its largest lane)
         while (bucket < np) bucket *= 2;
-        int hetero_orders = 1;
-        if (const char* ev = std::getenv("MBFIR_HETERO_ORDERS")) hetero_orders = std::atoi(ev);
-        if (const char* ev = std::getenv("MBFIR_HETERO")) hetero_orders = hetero_orders && std::atoi(ev) != 0;
-        if (hetero_orders) np = bucket;
+        if (sw.hetero_orders && sw.hetero) np = bucket;
     }
     long cap = std::min<long>(32, 16384 / np);
-    if (o.dense_trig || !lane_prep(Q, o)->Lt.ok) {
+    if (!lattice) {
         // dense path (opts.dense_trig, or a grid / column set without the lattice structure): every lane materialises
         // its trig matrix and owns a split-K slab -- at most ~2 GB of them per unit
         const GramPlan gp = gram_plan(Q.Mf, Q.Nt, Q.quad ? 3 : 1);
@@ -3131,7 +3837,7 @@ int Solver::max_lanes(const TrigProgram& Q, const SolveOpts& o) {
         cap = std::min<long>(cap, std::max<long>(1, long(2.0e9 / per_lane)));
     }
     if (o.ddkkt_theta > 0) cap = std::min<long>(cap, 16);                               // (~100 MB of strong rows and capacitance matrices per lane)
-    if (const char* ev = std::getenv("MBFIR_MAX_LANES")) cap = std::atol(ev);          // (experiments: tools/sweep_lanes.sh)
+    if (sw.max_lanes > 0) cap = sw.max_lanes;
     return int(std::max<long>(1, std::min<long>(MAX_LANES, cap)));
 }
 
@@ -3144,782 +3850,75 @@ int Solver::solve(const TrigProgram& Qfull, const SolveOpts& o, std::vector<doub
     return info.status;
 }
 
+// The interior-point method on a lock-step unit (a single design is a unit of one): the lanes and the unit planned, the arena laid
+// out, the initial point; then per iteration one scalar copy and one wait, the host's verdicts, and the iteration's launches.
 void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, std::vector<std::vector<double>>& xouts,
                          std::vector<SolveInfo>& infos) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
-    hipStream_t st = S.st;
     const double t_begin = now_ms();
     const int nlanes = int(Qs.size());
     if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
     S.nlanes = nlanes;
-    // ---- row sharding: this process keeps the frequencies i % size == rank (program.h) ----------
-    S.shard_rank = o.shard_size > 1 ? o.shard_rank : 0;
-    S.shard_size = o.shard_size > 1 ? o.shard_size : 1;
-    if (S.shard_size > 1 && !S.ar_fn && !S.comm) throw HipError("row-sharded solve without a communicator or an all-reduce hook");
-    if (S.comm && S.shard_size > 1 && (S.comm_size != S.shard_size || S.comm_rank != S.shard_rank))
-        throw HipError("row-sharded solve: shard_rank / shard_size differ from the RCCL communicator's");
-    S.n_collectives = 0; S.collective_bytes = 0;
-    S.n_gv = 0; S.n_gtv = 0;
-    S.corrector = true;
-    if (const char* ev = std::getenv("MBFIR_CORRECTOR")) S.corrector = std::atoi(ev) != 0;
-    S.corr_plain = true;
-    if (const char* ev = std::getenv("MBFIR_CORR_PLAIN")) S.corr_plain = std::atoi(ev) != 0;
-    S.corr_guard = true;
-    if (const char* ev = std::getenv("MBFIR_CORR_GUARD")) S.corr_guard = std::atoi(ev) != 0;
-    S.corr_big = true;
-    if (const char* ev = std::getenv("MBFIR_CORR_BIG")) S.corr_big = std::atoi(ev) != 0;
-    S.polish_approach = POLISH_APPROACH;
-    if (const char* ev = std::getenv("MBFIR_POLISH_APPROACH")) S.polish_approach = std::max(1.0, std::atof(ev));
-    S.polish_sweeps = POLISH_SWEEPS;
-    if (const char* ev = std::getenv("MBFIR_POLISH_SWEEPS")) S.polish_sweeps = std::max(0, std::min(MAX_SWEEPS, std::atoi(ev)));
-    S.sigma_max_corr = SIGMA_MAX_CORR;
-    if (const char* ev = std::getenv("MBFIR_SIGMA_MAX")) S.sigma_max_corr = std::max(0.0, std::min(1.0, std::atof(ev)));
-    S.test_cap_kp = 0;
-    if (const char* ev = std::getenv("MBFIR_TEST_CAP_KP")) S.test_cap_kp = std::atoi(ev);
-    S.ar_chunks = 0;         // 0: the build's own choice
-    if (const char* ev = std::getenv("MBFIR_AR_CHUNKS")) S.ar_chunks = std::max(1, std::atoi(ev));
-    S.ar_overlap_mode = 1;
-    if (const char* ev = std::getenv("MBFIR_AR_OVERLAP")) S.ar_overlap_mode = std::atoi(ev);
-    if (S.shard_size > 1 && nlanes > 1) throw ShapeError("row-sharded solves run one design at a time");
+    S.sw = read_switches();
     std::vector<LaneHost> LH(nlanes);
-    for (int b = 0; b < nlanes; ++b) {
-        LaneHost& L = LH[b];
-        const TrigProgram& Qfull = *Qs[b];
-        if (S.shard_size > 1) { L.local = shard_program(Qfull, S.shard_rank, S.shard_size); L.Q = &L.local; }
-        else L.Q = &Qfull;
-        // constants of the WHOLE program (identical on every shard)
-        double nh = 0, nc = 0;
-        for (double v : Qfull.h) nh += v * v;
-        for (double v : Qfull.c) nc += v * v;
-        L.nrm_h = std::max(1.0, std::sqrt(nh)); L.nrm_c = std::max(1.0, std::sqrt(nc));
-        L.degree = double(Qfull.l + Qfull.nq3 + (Qfull.big ? 1 : 0));
-        // (the extended-precision KKT solve forms its strong rows from the exact w_i: its programs keep every frequency
-        // on its own so that the lattice operator and those rows see the same grid to the old 2 ulp)
-        {
-            const std::shared_ptr<LanePrep> pr = lane_prep(*L.Q, o);
-            L.f_ptr = pr->f_ptr; L.f_rows = pr->f_rows; L.c_ptr = pr->c_ptr; L.c_rows = pr->c_rows; L.yrows = pr->yrows; L.rep = pr->rep;
-            L.Lt = pr->Lt;
-        }
-        L.nsweep = o.refine; L.nsweep_ctl = o.refine;
-    }
-    const TrigProgram& Q = *LH[0].Q;
-    const LatticeInfo& Lt = LH[0].Lt;
-    if (S.shard_size > 1 && !o.dense_trig) {
-        // every rank must take the same path (it selects the sequence and the sizes of the collectives): the
-        // lattice path only if EVERY shard has the structure -- a min all-reduce of the local verdicts
-        S.ensure_arena(4096);
-        double* dv = reinterpret_cast<double*>(S.ar.base);
-        S.hostSc[0] = LH[0].Lt.ok ? -1.0 : 0.0;                // min(v) = -max(-v); the collective knows sum and max
-        MBFIR_HIP(hipMemcpyAsync(dv, S.hostSc, sizeof(double), hipMemcpyHostToDevice, st));
-        S.allreduce(dv, 1, 1);
-        MBFIR_HIP(hipMemcpyAsync(S.hostSc, dv, sizeof(double), hipMemcpyDeviceToHost, st));
-        MBFIR_HIP(hipStreamSynchronize(st));
-        if (S.hostSc[0] > -0.5) LH[0].Lt = LatticeInfo();      // somebody lacks it: dense path everywhere
-    }
-    // ---- the unit: one CLASS (designer, order, unknowns, cones, lattice extent); within it the lanes' grids, row counts and
-    // chunk lists may differ (designs of one order with different band edges: the probes of fir_ap.m:63-106, sweeps over
-    // specs) -- arrays and launches are then sized to the unit's maxima and every lane carries its own dimensions (DProg::dims)
-    // (round 5: the ORDER may differ too -- the probes of a min-order search, fir_ap.m:143-176, ss/fir_min_order_linprog.m:98-145:
-    //  unknowns, cone counts, lattice extent and taps become per-lane dimensions like the six above; what stays common is the
-    //  designer, the slack columns, the kind of cones and the lattice's origin)
-    int Mf_max = Q.Mf, R_max = Q.R, l_max = Q.l, nyrows_max = int(LH[0].yrows.size());
-    int Nt_max = Q.Nt, nq3_max = Q.nq3, big_max = Q.big, D1_max = Lt.D1, n_max = Q.n;
-    size_t nchunk_max = Lt.ch_start.size(), nfold_max = Lt.wf.size();
-    bool hetero = false, orders = false;
-    for (int b = 1; b < nlanes; ++b) {
-        const TrigProgram& Qb = *LH[b].Q;
-        const LatticeInfo& Lb = LH[b].Lt;
-        if (Qb.which != Q.which || Qb.Ne != Q.Ne || (Qb.nq3 > 0) != (Q.nq3 > 0) || (Qb.big > 0) != (Q.big > 0) || Qb.quad != Q.quad ||
-            Lb.ok != Lt.ok || (Lb.tmin == 0.0) != (Lt.tmin == 0.0))
-            throw ShapeError("lock-step batch: lanes differ in class (designer, slack columns, cone kinds, lattice origin at zero or not)");
-        if (Qb.n != Q.n || Qb.Nt != Q.Nt || Qb.nq3 != Q.nq3 || Qb.big != Q.big || Lb.D1 != Lt.D1 || Lb.tmin != Lt.tmin || LH[b].c_rows.size() != LH[0].c_rows.size())
-            hetero = orders = true;
-        if (Qb.Mf != Q.Mf || Qb.R != Q.R || Qb.l != Q.l || LH[b].yrows.size() != LH[0].yrows.size() || Lb.ch_start.size() != Lt.ch_start.size() ||
-            Lb.wf.size() != Lt.wf.size())
-            hetero = true;
-        Mf_max = std::max(Mf_max, Qb.Mf); R_max = std::max(R_max, Qb.R); l_max = std::max(l_max, Qb.l);
-        nyrows_max = std::max(nyrows_max, int(LH[b].yrows.size()));
-        nchunk_max = std::max(nchunk_max, Lb.ch_start.size()); nfold_max = std::max(nfold_max, Lb.wf.size());
-        Nt_max = std::max(Nt_max, Qb.Nt); nq3_max = std::max(nq3_max, Qb.nq3); big_max = std::max(big_max, Qb.big);
-        D1_max = std::max(D1_max, Lb.D1); n_max = std::max(n_max, Qb.n);
-    }
-    auto seg_of = [](int D1) {
-        int sg = std::min(SEGMAX, std::max(64, int(round_up(cdiv(std::max(D1, 1), 16), 8))));
-        if (const char* ev = std::getenv("MBFIR_SEG")) sg = std::max(8, std::min(SEGMAX, std::atoi(ev)));
-        return sg;
-    };
-    // what the per-lane dimensions do not cover: different ORDERS on the dense path (the row stride of A1 follows the order).
-    // Different band edges are fine there too since round 5: every lane runs its own Gram plan and folds its own split partials.
-    if (orders && (!Lt.ok || o.dense_trig)) throw ShapeError("lock-step batch: lanes differ in order (dense path)");
-    if (std::getenv("MBFIR_HETERO") && std::atoi(std::getenv("MBFIR_HETERO")) == 0 && hetero) throw ShapeError("lock-step batch: lanes differ in shape (MBFIR_HETERO=0)");
-    // ---- sizes -----------------------------------------------------------------------------
-    const int R = R_max, Nt = Nt_max, Ne = Q.Ne, N = Nt_max + Q.Ne, Mf = Mf_max;
-    const int nw = Q.quad ? 3 : 1;
-    // (dense row-sharded build with the chunked, overlapped all-reduce: see Impl::ar_overlap_mode)
-    S.ar_overlap = !Lt.ok && nw == 1 && nlanes == 1 && ((S.shard_size > 1 && S.ar_overlap_mode != 0) || S.ar_overlap_mode == 2);
-    // (chunks: MBFIR_AR_CHUNKS, else one per 32 tiles, at most 8 -- below that a chunk's product is too short to hide a collective behind)
-    const int gtiles = gram_plan(Mf, Nt, nw).ntiles;
-    const int gfill = S.ar_overlap ? std::max(1, std::min(S.ar_chunks > 0 ? S.ar_chunks : std::min(8, gtiles / 32), gtiles)) : 1;
-    S.gp = gram_plan(Mf, Nt, nw, gfill);
-    S.gps.assign(nlanes, S.gp);
-    for (int b = 0; b < nlanes; ++b) {
-        S.gps[b] = gram_plan(LH[b].Q->Mf, Nt, nw, gfill);
-        S.gp.Mpad = std::max(S.gp.Mpad, S.gps[b].Mpad); S.gp.slab_doubles = std::max(S.gp.slab_doubles, S.gps[b].slab_doubles);
-    }
-    DProg& P = S.P;
-    P.trig = Lt.ok ? 1 : 0;
-    P.D1 = D1_max; P.tmin = Lt.tmin; P.LDL = int(round_up(std::max(D1_max, 1), 64));
-    P.seg = seg_of(D1_max);
-    P.useg = 1;
-    if (Lt.ok) for (int b = 0; b < nlanes; ++b) P.useg = std::max(P.useg, cdiv(LH[b].Lt.D1, seg_of(LH[b].Lt.D1)));      // (launches: the most segments any lane has)
-    P.nchunk = int(nchunk_max); P.nfold = int(nfold_max);
-    P.seeds_shared = 0;
-    if (nlanes > 1 && Lt.ok) {                               // sweeps over Peak / ripple keep the grid: one seed table serves the unit
-        bool same = true;
-        for (int b = 1; b < nlanes && same; ++b) {
-            const LatticeInfo& Lb = LH[b].Lt;
-            same = Lb.D1 == Lt.D1 && Lb.tmin == Lt.tmin && Lb.wf == Lt.wf && Lb.ch_w0 == Lt.ch_w0 && Lb.ch_dw == Lt.ch_dw && Lb.ch_start == Lt.ch_start && Lb.ch_count == Lt.ch_count;
-        }
-        P.seeds_shared = same ? 1 : 0;
-    }
-    if (const char* ev = std::getenv("MBFIR_SHARE_SEEDS")) P.seeds_shared = P.seeds_shared && std::atoi(ev) != 0;
-    P.cgrp = 4;          // two pairs of interleaved chunks per block, for one design and for lanes alike (the same sums in both):
-                         // half the partial-moment traffic of one pair per block -- with four units in flight the solver moves
-                         // 3 TB/s through HBM, and that, not the recurrences, is what the moment kernels then wait for
-    if (const char* ev = std::getenv("MBFIR_CGRP")) P.cgrp = std::max(1, std::min(CGRP, std::atoi(ev)));
-    P.LDM = int(round_up(3 * std::max(D1_max, 1), 256));
-    P.Nt = Nt; P.Ne = Ne; P.N = N; P.Mf = Mf; P.R = R; P.l = l_max; P.nq3 = nq3_max; P.big = big_max; P.quad = Q.quad;
-    P.ld = S.gp.ld; P.Mpad = S.gp.Mpad; P.np = int(round_up(N, 64));
-    P.LDV = int(round_up(std::max(P.ld, P.np), 128)); P.Rp = int(round_up(R, 64));
-    P.nyrows = nyrows_max;
-    P.mask = nullptr; P.lane_bytes = 0; P.dims = nullptr; P.Mown = P.Mpad;
-    P.own = S.shard_rank == 0 ? 1 : 0;                        // (1 when not sharded)
-    if (hetero) {
-        for (int b = 0; b < nlanes; ++b) {
-            const TrigProgram& Qb = *LH[b].Q;
-            const int d1 = LH[b].Lt.D1, sg = seg_of(d1);
-            S.hostDims[b] = LaneDims{Qb.Mf, Qb.R, Qb.l, int(LH[b].yrows.size()), int(LH[b].Lt.wf.size()), int(LH[b].Lt.ch_start.size()),
-                                     Qb.Nt, Qb.Nt + Qb.Ne, Qb.nq3, Qb.big, d1, sg, LH[b].Lt.ok ? cdiv(d1, sg) : 1, S.gps[b].Mpad, LH[b].Lt.tmin};
-        }
-        MBFIR_HIP(hipMemcpyAsync(S.dimsT, S.hostDims, sizeof(LaneDims) * nlanes, hipMemcpyHostToDevice, st));
-        P.dims = S.dimsT;
-    }
-    S.nsplit_at = cdiv(P.Mpad, AT_ROWS);
-    const int ncone = P.l + P.nq3;
-    S.nbR = cdiv(R, 256); S.nbN = cdiv(N, 256); S.nbC = cdiv(ncone, 256);
-    if (S.nbR + 1 > NPART * 64) throw HipError("problem too large for the reduction buffers");
-    const size_t ld = P.ld, np = P.np, LDV = P.LDV, Rp = P.Rp, Mpad = P.Mpad;
-    const int lp = Q.which == DES_AP ? specfact_lp(n_max) : 0;
-    for (int b = 0; b < nlanes; ++b) S.lane_n[b] = LH[b].Q->n;
-    std::vector<std::vector<int>> tiles(nlanes);
-    for (int b = 0; b < nlanes; ++b) { tiles[b].resize(gram_table_ints(S.gps[b])); gram_tiles_host(S.gps[b], tiles[b].data()); }
-    S.gchunks.clear();
-    if (S.ar_overlap) {              // the chunk tables ride behind the tile table
-        std::vector<int> ctab;
-        gram_chunk_tables(S.gps[0], gfill, ctab, S.gchunks);
-        tiles[0].insert(tiles[0].end(), ctab.begin(), ctab.end());
-    }
-    S.cap_form = o.dd_form == 0;                              // its capacitance form in plain double (capkkt.hip) or the double-double one
-    if (const char* ev = std::getenv("MBFIR_DDFORM")) S.cap_form = std::strcmp(ev, "dd") != 0;
-    // extended-precision KKT solve (ddkkt.inc); lock-step units: in its capacitance form (round 5; the double-double kernels take one design)
-    if (o.ddkkt_theta > 0 && nlanes > 1 && !S.cap_form) throw ShapeError("lock-step batch: the double-double form of the extended-precision solve runs one design at a time");
-    const bool use_dd = o.ddkkt_theta > 0 && S.shard_size <= 1;
-    S.dd_unit = use_dd && nlanes > 1;
-    S.dd_kp = 0;
-    // Refinement passes on the augmented system around the extended-precision solve: two for the double-double form, THREE for the
-    // capacitance form.  Measured on BASELINE config 3's family (tools/exp/c3_one_design.py): the first pass takes the residual of
-    // the constant system from ||c|| = 1e6 to 1e-8 early and to 1.2e-5 from k ~ 480 strong directions on (the lattice-built H_w
-    // against the exact operator: a floor of ~1e-11 relative), every further pass contracts it by ~2e-3.  With two passes one of the
-    // eight designs of the bench's batch (ripples x 1.02, k = 751 at mu = 3e-11) took a step of 0.006 at relgap 1.02e-8 and lost its
-    // iterate (NaN) in the next -- the oracle, whose H_w is the dense product, does not -- and had to be repeated in the
-    // double-double form (150 iterations instead of 74); with three it solves like the double-double form.  Cost: 0.135 -> 0.153 s alone.
-    S.dd_passes = S.cap_form ? 3 : 2;
-    if (const char* ev = std::getenv("MBFIR_DD_PASSES")) S.dd_passes = std::max(1, std::min(8, std::atoi(ev)));
-    S.fused_hsolve = hsolve_fused_ok(int(np), 2);
-    if (const char* ev = std::getenv("MBFIR_HSOLVE")) S.fused_hsolve = S.fused_hsolve && std::atoi(ev) != 0;       // 0: the two triangular GEMVs
-    S.fuse_fold = true;
-    if (const char* ev = std::getenv("MBFIR_FUSE")) S.fuse_fold = std::atoi(ev) != 0;                               // 0: the separate kernels of round 4
-    Arena& ar = S.ar;
-    char* zero_from = nullptr;
-    size_t zero_bytes = 0;
-    auto layout = [&]() {
-    // ---- upload the program (one copy per lane) ----------------------------------------------
-#define UPQ(T, member) S.upload<T>([&](int b) -> const std::vector<T>& { return LH[b].Q->member; })
-#define UPL(T, member) S.upload<T>([&](int b) -> const std::vector<T>& { return LH[b].member; })
-    P.w = UPQ(double, w); P.col_kind = UPQ(int, col_kind); P.col_tau = UPQ(double, col_tau);
-    P.col_scale = UPQ(double, col_scale); P.pcol = UPQ(int, pcol); P.psign = UPQ(double, psign);
-    P.c = UPQ(double, c); P.freq = UPQ(int, freq); P.col = UPQ(int, col); P.alpha = UPQ(double, alpha);
-    P.beta = UPQ(double, beta); P.ey = UPQ(double, ey); P.h = UPQ(double, h);
-    P.f_ptr = UPL(int, f_ptr); P.f_rows = UPL(int, f_rows); P.c_ptr = UPL(int, c_ptr); P.c_rows = UPL(int, c_rows);
-    P.yrows = UPL(int, yrows); P.rep = UPL(int, rep);
-    S.tile_ij = S.upload<int>([&](int b) -> const std::vector<int>& { return tiles[b]; });
-    P.lat = UPL(int, Lt.lat); P.lat_col = UPL(int, Lt.lat_col); P.lat_qcol = UPL(int, Lt.lat_qcol);
-    P.lat_scale = UPL(double, Lt.lat_scale); P.lat_qscale = UPL(double, Lt.lat_qscale);
-    P.ch_start = UPL(int, Lt.ch_start); P.ch_count = UPL(int, Lt.ch_count); P.ch_w0 = UPL(double, Lt.ch_w0); P.ch_dw = UPL(double, Lt.ch_dw);
-    P.fold_pos = UPL(int, Lt.fold_pos); P.fold_neg = UPL(int, Lt.fold_neg); P.wf = UPL(double, Lt.wf);
-#undef UPQ
-#undef UPL
-    if (!ar.measuring) S.flush_uploads();
-    // ---- work buffers ----------------------------------------------------------------------
-    zero_from = ar.base + ar.off;
-    S.A1 = ar.get<double>(P.trig ? 0 : Mpad * ld);
-    S.T = ar.get<double>(P.trig ? 0 : nw * ld * ld);
-    S.Tp = ar.get<double>(S.ar_overlap ? (size_t)S.gps[0].ntiles * 16384 : 0);
-    S.chunk_tab = S.ar_overlap ? S.tile_ij + gram_table_ints(S.gps[0]) : nullptr;
-    {
-        const size_t nch = std::max(P.nchunk, 1), d1 = std::max(P.D1, 1);
-        P.seed_tau = ar.get<double4>(P.trig ? nch * d1 : 1);
-        P.seed_h = ar.get<double4>(P.trig ? nch * (3 * d1 - 1) : 1);
-        P.seed_eval = ar.get<double4>(P.trig ? (size_t)P.useg * Mpad : 1);
-    }
-    S.Mom = ar.get<double>(18 * (size_t)P.LDM); S.MomB = ar.get<double>(12 * (size_t)P.LDM);
-    S.H = ar.get<double>(np * np); S.M = ar.get<double>(np * np); S.Mt = ar.get<double>(np * np); S.W1 = ar.get<double>(np * np + 65 * np);
-    S.Sc = ar.get<double>(S_COUNT); S.flag = ar.get<int>(4); S.gt_cnt = ar.get<int>(4); S.RB = ar.get<double>(16);
-    S.x = ar.get<double>(LDV); S.tmpN = ar.get<double>(2 * LDV); S.tmpN2 = ar.get<double>(2 * LDV);
-    S.rhsN = ar.get<double>(2 * LDV); S.yN = ar.get<double>(2 * LDV); S.pN = ar.get<double>(2 * LDV); S.bx2 = ar.get<double>(2 * LDV);
-    S.dx2 = ar.get<double>(2 * LDV); S.rx = ar.get<double>(LDV); S.GTz = ar.get<double>(LDV + 16);        /* + the mailbox of the residual sums, packed behind G'z */
-    S.bxc = ar.get<double>(LDV); S.dxc = ar.get<double>(LDV); S.qv = ar.get<double>(3 * LDV);
-    S.XX = ar.get<double>(4 * LDV); S.TT = ar.get<double>(6 * LDV); S.TT2 = ar.get<double>(4 * LDV); S.xout = ar.get<double>(LDV);
-    S.s = ar.get<double>(Rp); S.z = ar.get<double>(Rp); S.lam = ar.get<double>(Rp); S.dl = ar.get<double>(Rp);
-    S.wl = ar.get<double>(Rp); S.w3 = ar.get<double>(4 * (size_t)std::max(P.nq3, 1)); S.wbb = ar.get<double>(std::max(P.big, 1));
-    S.tmpR = ar.get<double>(2 * Rp); S.wbz = ar.get<double>(2 * Rp); S.wpR = ar.get<double>(2 * Rp); S.bz2 = ar.get<double>(2 * Rp); S.dz2 = ar.get<double>(2 * Rp);
-    S.gdx2 = ar.get<double>(2 * Rp); S.gdxc = ar.get<double>(Rp); S.xbest = ar.get<double>(LDV);
-    S.rz = ar.get<double>(Rp); S.Gx = ar.get<double>(Rp); S.dssa = ar.get<double>(Rp); S.wdza = ar.get<double>(Rp);
-    S.lds = ar.get<double>(Rp); S.bzc = ar.get<double>(Rp); S.dzc = ar.get<double>(Rp); S.ds = ar.get<double>(Rp);
-    S.dz = ar.get<double>(Rp); S.scratch = ar.get<double>(4 * (size_t)std::max(P.big, 1) + 8);
-    S.kbx = ar.get<double>(LDV); S.kbz = ar.get<double>(Rp); S.kx = ar.get<double>(LDV); S.kz = ar.get<double>(Rp); S.kg = ar.get<double>(Rp);
-    S.kds = ar.get<double>(Rp); S.kdz = ar.get<double>(Rp);
-    S.UU = ar.get<double>(4 * Mpad * (size_t)P.useg); S.PP = ar.get<double>(4 * Mpad); S.PPf = ar.get<double2>(6 * Mpad); S.Dw = ar.get<double>(9 * Mpad); S.BB = S.Dw + (size_t)nw * Mpad;       // border vectors right behind the nw weight vectors
-    S.partial = ar.get<double>(std::max(P.trig ? (size_t)cdiv(P.nchunk, P.cgrp) * 12 * P.LDM : (size_t)S.nsplit_at * 6 * ld,
-                                        std::max(hsolve_part_doubles(int(np)), hsolve_part_doubles(CAP_KMAX))));   // (also the partial vectors of the one-pass M'(M b), of H and of the capacitance matrix)
-    S.partR = ar.get<double>(4 * (size_t)(S.nbR + 2)); S.partR2 = ar.get<double>(4 * (size_t)(S.nbR + 2)); S.partN = ar.get<double>(4 * (size_t)(S.nbN + 2));
-    S.ddinv = nullptr;
-    if (use_dd) {
-        DDev& D = S.D;
-        D.e3 = ar.get<double>(8 * (size_t)std::max(P.nq3, 1)); D.eb = ar.get<double>(8); D.whb = ar.get<double>(std::max(P.big, 1));
-        D.dlc = ar.get<double>(Rp); D.m3c = ar.get<double>(6 * (size_t)std::max(P.nq3, 1));
-        D.slotl = ar.get<int>(std::max(P.l, 1)); D.slot3 = ar.get<int>(3 * (size_t)std::max(P.nq3, 1)); D.slotb = ar.get<int>(2);
-        D.kcnt = ar.get<int>(1); D.skind = ar.get<int>(DD_KMAX); D.sidx = ar.get<int>(DD_KMAX); D.sdir = ar.get<int>(DD_KMAX);
-        S.ddtheta = ar.get<double>(MAX_LANES);
-        D.sX = ar.get<double>(DD_KMAX); D.U = ar.get<double>((size_t)DD_KMAX * np);
-        S.ddB = ar.get<double>(4 * LDV); S.ddtS = ar.get<double>(2 * (size_t)DD_KMAX); S.ddzeta = ar.get<double>(2 * (size_t)DD_KMAX);
-        S.ddri = ar.get<double>(2 * np); S.ddd0 = ar.get<double>(np);
-        S.ddflags = ar.get<int>(2 * np / 32 + 8);          // block flags of the multi-workgroup dd solve (zeroed with the arena)
-        S.ddinv = ar.get<double>(2 * np * 64);
-        if (const char* ev = std::getenv("MBFIR_DD_BLOCKINV")) { if (std::atoi(ev) == 0) S.ddinv = nullptr; }
-        if (S.cap_form) {
-            S.capYt = ar.get<double>((size_t)CAP_KMAX * np); S.capZt = ar.get<double>((size_t)CAP_KMAX * np);
-            S.capS = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX); S.capMs = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX);
-            S.capW1 = ar.get<double>((size_t)CAP_KMAX * CAP_KMAX + 65 * (size_t)CAP_KMAX); S.capw = ar.get<double>(2 * (size_t)DD_KMAX);
-            S.capflag = ar.get<int>(4);
-            S.capPart = ar.get<double>(cap_part_doubles(CAP_KMAX, int(np)));
-        }
-    }
-    S.hout = ar.get<double>(2 * (size_t)n_max + 8);
-    S.sfwork = ar.get<double>(6 * (size_t)std::max(lp, 1));
-    zero_bytes = size_t(ar.base + ar.off - zero_from);
-    S.slab = ar.get<double>(P.trig ? 0 : S.gp.slab_doubles);
-    };
-    // first pass: only add up the sizes of ONE lane; the lanes then sit lane_bytes apart in one arena
-    ar.measuring = true; ar.reset();
-    S.meas_lo = S.meas_hi = 0;
-    { char* keep = ar.base; ar.base = nullptr; layout(); ar.base = keep; }
-    S.lane_bytes = (ar.off + 4095) & ~size_t(4095);
-    ar.measuring = false;
-    S.ensure_arena(S.lane_bytes * nlanes + 4096);
-    S.pend.clear(); S.stage_lo = S.stage_hi = 0;
-    layout();
-    P.lane_bytes = S.lane_bytes;
-    S.memset_lanes(zero_from, zero_bytes);
-    // ---- lane masks ------------------------------------------------------------------------
-    std::vector<int> dev_mask(size_t(MASK_ROWS) * MAX_LANES, -1), new_mask(size_t(MASK_ROWS) * MAX_LANES, 0);      // what the device holds / is to hold
-    auto push_masks = [&]() {                                 // row 0 = live lanes, rows q = 1..MAX_SWEEPS: lanes that run CG sweep q
-        if (nlanes == 1) return;
-        for (int b = 0; b < nlanes; ++b) {
-            new_mask[b] = LH[b].live ? 1 : 0;
-            S.lane_live[b] = LH[b].live;
-            // (a lane whose iteration runs the extended-precision solve takes no part in the plain solve's sweeps)
-            for (int q = 1; q <= MAX_SWEEPS; ++q) new_mask[q * MAX_LANES + b] = (LH[b].live && LH[b].dd_k == 0 && LH[b].nsweep >= q) ? 1 : 0;
-            new_mask[ROW_DD * MAX_LANES + b] = (LH[b].live && LH[b].dd_k > 0) ? 1 : 0;
-            new_mask[ROW_PL * MAX_LANES + b] = (LH[b].live && LH[b].dd_k == 0) ? 1 : 0;
-        }
-        // (most iterations change nothing: the copy is a launch of its own on the stream -- skipped then)
-        const size_t sweep_ints = size_t(MAX_SWEEPS + 1) * MAX_LANES, dd_off = size_t(ROW_DD) * MAX_LANES, dd_ints = 2 * size_t(MAX_LANES);
-        if (std::memcmp(new_mask.data(), dev_mask.data(), sizeof(int) * sweep_ints) != 0) {
-            std::memcpy(S.hostMask, new_mask.data(), sizeof(int) * sweep_ints);
-            MBFIR_HIP(hipMemcpyAsync(S.maskT, S.hostMask, sizeof(int) * sweep_ints, hipMemcpyHostToDevice, st));
-            std::memcpy(dev_mask.data(), new_mask.data(), sizeof(int) * sweep_ints);
-        }
-        if (S.dd_unit && std::memcmp(new_mask.data() + dd_off, dev_mask.data() + dd_off, sizeof(int) * dd_ints) != 0) {
-            std::memcpy(S.hostMask + dd_off, new_mask.data() + dd_off, sizeof(int) * dd_ints);
-            MBFIR_HIP(hipMemcpyAsync(S.maskT + dd_off, S.hostMask + dd_off, sizeof(int) * dd_ints, hipMemcpyHostToDevice, st));
-            std::memcpy(dev_mask.data() + dd_off, new_mask.data() + dd_off, sizeof(int) * dd_ints);
-        }
-    };
-    push_masks();
-    P.mask = S.mask_row(0);
-    // ---- build A1, norms -------------------------------------------------------------------
-    if (!P.trig) hipLaunchKernelGGL(k_build_A1, lane_grid(dim3(cdiv(Nt, 256), Mf), nlanes), dim3(256), 0, st, P, S.A1);
-    else {
-        const int seed_lanes = P.seeds_shared ? 1 : nlanes;
-        hipLaunchKernelGGL(k_build_seeds_m, lane_grid(dim3(cdiv(P.D1, 256), P.nchunk), seed_lanes), dim3(256), 0, st, P, 1.0, P.D1, 0.0, 0,
-                           const_cast<double4*>(P.seed_tau));
-        hipLaunchKernelGGL(k_build_seeds_m, lane_grid(dim3(cdiv(3 * P.D1 - 1, 256), P.nchunk), seed_lanes), dim3(256), 0, st, P, 0.0, P.D1, 2.0,
-                           2 * P.D1 - 1, const_cast<double4*>(P.seed_h));
-        hipLaunchKernelGGL(k_build_seeds_e, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), seed_lanes), dim3(256), 0, st, P, const_cast<double4*>(P.seed_eval));
-    }
-    std::vector<double> sc0((size_t)S_COUNT * nlanes, 0.0);
-    for (int b = 0; b < nlanes; ++b) {
-        double* q = sc0.data() + (size_t)b * S_COUNT;
-        q[S_NRMH] = LH[b].nrm_h; q[S_NRMC] = LH[b].nrm_c; q[S_DEG] = LH[b].degree; q[S_TAU] = 1.0; q[S_KAPPA] = 1.0;
-        q[S_SIGMAX] = (S.corrector && LH[b].Q->l > 0 && LH[b].Q->big == 0) ? S.sigma_max_corr : SIGMA_MAX;      // (not with a big cone: oracle/conic_ipm.py)
-        MBFIR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(S.Sc) + (size_t)b * S.lane_bytes, q, sizeof(double) * S_COUNT, hipMemcpyHostToDevice, st));
-    }
-    MBFIR_HIP(hipStreamSynchronize(st));
+    S.prepare_lanes(Qs, o, LH);
+    const UnitPlan U = S.plan_unit(LH, o);
+    S.layout_arena(LH, U);
+    S.mask_dev.assign(size_t(MASK_ROWS) * MAX_LANES, -1); S.mask_new.assign(size_t(MASK_ROWS) * MAX_LANES, 0);
+    S.push_masks(LH);
+    S.P.mask = S.mask_row(0);
+    S.start_lanes(LH);
+    MBFIR_HIP(hipStreamSynchronize(S.st));
     const double t_assembled = now_ms();
     S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
     S.timing = o.timing;
+    S.chol_launch_count = 0; S.dd_epoch = 0;
+    S.drop_graphs();
+    S.initial_point(o.refine);
 
     const bool sharded = S.shard_size > 1;
-    S.dd_iters = 0; S.dd_kmax_seen = 0; S.chol_launch_count = 0; S.dd_epoch = 0;
-    auto cone_shift = [&](double* v) {
-        const int nb = std::max(S.nbC, 1);
-        hipLaunchKernelGGL(k_cone_resid, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, v, S.partR);
-        if (P.big) hipLaunchKernelGGL(k_big_cone_resid, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, v, S.partR);
-        hipLaunchKernelGGL(k_cone_fold, lane_grid(dim3(1), nlanes), dim3(256), 0, st, S.partR, nb + (P.big ? 1 : 0), S.RB, S.lane_bytes, P.mask);
-        S.allreduce(S.RB, 1, 1);                          // max of the cone distances
-        S.allreduce(S.RB + 1, 1, 0);                      // sum of squares
-        hipLaunchKernelGGL(k_cone_shift, lane_grid(dim3(64), nlanes), dim3(256), 0, st, P, v, S.RB);
-    };
-    // ---- initial point (W = I) -------------------------------------------------------------
-    hipLaunchKernelGGL(k_unit_scaling, lane_grid(dim3(cdiv(std::max(std::max(P.l, P.nq3), std::max(P.big, 1)), 256)), nlanes), dim3(256), 0, st,
-                       P, S.dl, S.wl, S.w3, S.wbb, S.Sc);
-    S.build_H();
-    hipLaunchKernelGGL(k_init_rhs, lane_grid(dim3(cdiv(std::max(N, R), 256)), nlanes), dim3(256), 0, st, P, S.bx2, S.bz2);
-    int nsweep_max = o.refine;
-    S.kkt_solve<2>(S.bx2, S.bz2, S.dx2, S.dz2, S.gdx2, nsweep_max, S_RNA);
-    S.copy_lanes(S.x, S.dx2, sizeof(double) * LDV);
-    hipLaunchKernelGGL(k_neg_copy_r, lane_grid(dim3(cdiv(R, 256)), nlanes), dim3(256), 0, st, P, S.dz2, S.s, -1.0);
-    cone_shift(S.s);
-    hipLaunchKernelGGL(k_neg_copy_r, lane_grid(dim3(cdiv(R, 256)), nlanes), dim3(256), 0, st, P, S.dz2 + Rp, S.z, 1.0);
-    cone_shift(S.z);
-
-    int it = 0;
-    bool dd_now = false;
     // (every lane of a unit is the same designer: orthant rows in all of them or in none.  What is corrected: the orthant rows and,
     //  on the plain path, the big cone -- oracle/conic_ipm.py)
-    const bool use_corr = S.corrector && P.l > 0;
+    const bool use_corr = S.sw.corrector && S.P.l > 0;
     // MBFIR_TRACE_HOST=1: where the host thread of this unit spends the solve -- issuing launches, or waiting in the one
     // synchronisation per iteration (a stream whose host thread issues most of the time is launch-bound, not GPU-bound)
-    const bool trace_host = std::getenv("MBFIR_TRACE_HOST") != nullptr;
+    const bool trace_host = S.sw.trace_host;
     double host_issue_ms = 0, host_wait_ms = 0, t_issue0 = trace_host ? now_ms() : 0.0;
-    // the residual kernels of an iterate (everything up to the one copy + synchronisation per iteration)
-    auto launch_residuals = [&]() {
-        // residuals
-        // row-sharded: the four row sums (||rz||^2, s'z, h'z, ||Gx + s||^2) are folded into a mailbox directly behind G'z and
-        // summed over the ranks by the same all-reduce (they do not depend on G'z)
-        double* rmail = sharded ? S.GTz + LDV : S.RB;
-        if (P.trig) {                                     // G x rows are formed inside k_resid_rows
-            ++S.n_gv;
-            hipLaunchKernelGGL(k_trig_eval<1>, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), nlanes), dim3(256), 0, st, P, S.x, S.UU);
-            hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(S.nbR), nlanes), dim3(256), 0, st, P, nullptr, S.s, S.z, S.Sc, S.rz, S.bz2, S.partR, S.UU, S.x);
-        } else {
-            S.apply_G<1>(S.x, S.Gx);
-            hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(S.nbR), nlanes), dim3(256), 0, st, P, S.Gx, S.s, S.z, S.Sc, S.rz, S.bz2, S.partR, nullptr, nullptr);
-        }
-        if (sharded) hipLaunchKernelGGL(k_scal_resid, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, S.GTz, S.x, S.rx, S.bx2, S.partR, S.nbR, rmail, 0, (const int*)S.flag);
-        S.apply_GT<1>(S.z, S.GTz, sharded ? 5 : 0);
-        hipLaunchKernelGGL(k_scal_resid, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, S.Sc, S.GTz, S.x, S.rx, S.bx2, S.partR, S.nbR, rmail, sharded ? 1 : 2, (const int*)S.flag);
-    };
-    // ---- launch graphs (round 4, opt-in: MBFIR_GRAPH=1).  The host thread of ONE design spends 44 % of the solve issuing the ~80
-    // launches of an iteration (MBFIR_TRACE_HOST), so the body of an iteration (scaling, normal matrix, factorisation, both KKT
-    // solves, update, the next iterate's residuals) -- a fixed launch sequence for a given number of refinement sweeps -- can be
-    // captured once per sweep count and replayed with one hipGraphLaunch; the phase timings then come from the graph's event-record
-    // nodes, read after every replay.  Measured: bit-identical results and 1.01-1.08 x in latency (n = 64 ... 2048): dependent kernels
-    // in one stream cost ~4 us each whoever issues them -- a single design is bound by the GPU-side launch chain, not by the host.
-    // Not the default (capture from many concurrent contexts for <= 8 %); single, unsharded designs without the extended-precision path.
-    bool use_graph = nlanes == 1 && !use_dd && !sharded && !std::getenv("MBFIR_TEST_LOSE_FLAG") && std::getenv("MBFIR_GRAPH") &&
-                     std::atoi(std::getenv("MBFIR_GRAPH")) != 0;
-    struct IterGraph { hipGraphExec_t exec = nullptr; size_t ev_lo = 0, ev_hi = 0; long chol_launches = 0; };
-    std::map<int, IterGraph> graphs;
-    double graph_ms_gram = 0, graph_ms_chol = 0;
-    int graph_builds = 0;
-    const IterGraph* last_graph = nullptr;
-    launch_residuals();
-    // The head of the NEXT iteration -- NT scaling, normal matrix, factorisation: everything that depends on the iterate (s, z) alone --
-    // goes to the stream BEFORE the host has looked at this iterate's scalars (round 5): the host waits on an event behind the
-    // scalars' copy, not on the stream, so the GPU works on the head (~0.5 ms) while the host wakes up, takes its decisions
-    // (verdicts, sweep counts, masks) and issues the rest of the iteration behind it.  Before, the stream stood empty for that long
-    // every iteration (single design: ~100 us of a 780 us iteration; a lock-step unit alone: 1.46 ms wall for 1.33 ms of kernels).
-    // A lane the host then retires has had one scaling and factorisation too many (it runs under the previous iteration's masks):
-    // they touch nothing the result is read from.  Not with the extended-precision solve (its strong-set count needs the host
-    // mid-head), row-sharded solves and launch graphs.  MBFIR_SPECULATE=0 restores the old order.
-    bool speculate = !use_dd && !sharded && !use_graph;
-    if (const char* ev = std::getenv("MBFIR_SPECULATE")) speculate = speculate && std::atoi(ev) != 0;
-    auto launch_head = [&]() {
-        hipLaunchKernelGGL(k_scaling, lane_grid(dim3(std::max(S.nbC, 1)), nlanes), dim3(256), 0, st, P, S.s, S.z, S.dl, S.wl, S.w3, S.lam, S.bz2, S.wbz);
-        if (P.big) hipLaunchKernelGGL(k_big_scaling, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.s, S.z, S.wbb, S.lam, S.Sc);
-        if (S.dd_unit) {
-            // every live lane its own strong set; then the masks of the two modes (the sweep rows follow: push_masks)
-            int ks[MAX_LANES];
-            bool lv[MAX_LANES];
-            for (int b = 0; b < nlanes; ++b) lv[b] = LH[b].live;
-            S.dd_k = S.dd_prepare_lanes(o.ddkkt_theta, ks, lv);
-            for (int b = 0; b < nlanes; ++b) {
-                LH[b].dd_k = ks[b];
-                if (ks[b] > 0) { LH[b].dd_iters += 1; LH[b].dd_kmax = std::max(LH[b].dd_kmax, ks[b]); }
-            }
-            S.dd_kp = int(round_up(std::max(S.dd_k, 1), 64));
-            push_masks();
-        } else {
-            S.dd_k = use_dd ? S.dd_prepare(o.ddkkt_theta) : 0;
-            LH[0].dd_k = S.dd_k;
-            if (S.dd_k > 0) { LH[0].dd_iters += 1; LH[0].dd_kmax = std::max(LH[0].dd_kmax, S.dd_k); }
-        }
-        if (S.dd_k > 0) { S.dd_iters += 1; S.dd_kmax_seen = std::max(S.dd_kmax_seen, S.dd_k); }
-        dd_now = S.dd_k > 0;
-        S.build_H(S.dd_k);
-    };
+    bool use_graph = nlanes == 1 && !U.use_dd && !sharded && !S.sw.test_lose_flag && S.sw.graph;      // (see Impl::IterGraph)
+    S.launch_residuals();
+    // The head of the NEXT iteration goes to the stream BEFORE the host has looked at this iterate's scalars (round 5, DESIGN.md
+    // section 5): the host waits on an event behind the scalars' copy while the GPU works on the head.  A lane the host then retires
+    // has had one scaling and factorisation too many, which touch nothing the result is read from.  Not with the extended-precision
+    // solve (its strong-set count needs the host mid-head), row-sharded solves and launch graphs.
+    const bool speculate = !U.use_dd && !sharded && !use_graph && S.sw.speculate;
+    int it = 0;
     for (it = 0; it <= o.max_iter; ++it) {
-        MBFIR_HIP(hipMemcpy2DAsync(S.hostSc, sizeof(double) * S_COUNT, S.Sc, S.lane_bytes, sizeof(double) * S_COUNT, nlanes, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpy2DAsync(S.hostSc, sizeof(double) * S_COUNT, S.Sc, S.lane_bytes, sizeof(double) * S_COUNT, nlanes, hipMemcpyDeviceToHost, S.st));
         const bool head_out = speculate && it < o.max_iter;
         if (head_out) {
-            MBFIR_HIP(hipEventRecord(S.ev0, st));
-            launch_head();
+            MBFIR_HIP(hipEventRecord(S.ev0, S.st));
+            S.launch_head(LH, o);
         }
         const double t_sync0 = trace_host ? now_ms() : 0.0;
         if (head_out) MBFIR_HIP(hipEventSynchronize(S.ev0));
-        else MBFIR_HIP(hipStreamSynchronize(st));
+        else MBFIR_HIP(hipStreamSynchronize(S.st));
         if (trace_host) { const double t1 = now_ms(); host_issue_ms += t_sync0 - t_issue0; host_wait_ms += t1 - t_sync0; t_issue0 = t1; }
-        if (last_graph && S.timing) {                         // (gram begin, gram end, chol begin, chol end) of the replay just finished
-            for (size_t e = last_graph->ev_lo; e + 3 < last_graph->ev_hi; e += 4) {
-                float ga = 0, ch = 0;
-                if (hipEventElapsedTime(&ga, S.evpool[e], S.evpool[e + 1]) == hipSuccess) graph_ms_gram += ga;
-                if (hipEventElapsedTime(&ch, S.evpool[e + 2], S.evpool[e + 3]) == hipSuccess) graph_ms_chol += ch;
-                ++graph_builds;
-            }
-            last_graph = nullptr;
-        }
-        bool any_live = false, any_best = false;
-        for (int b = 0; b < nlanes; ++b) S.hostMask[ROW_BEST * MAX_LANES + b] = 0;      // 1: the lane has a new best iterate
-        for (int b = 0; b < nlanes; ++b) {
-            LaneHost& L = LH[b];
-            if (!L.live) continue;
-            const double* hs = S.hostSc + (size_t)b * S_COUNT;
-            const int chol_fixes = int(hs[S_CHOLFIX]);
-            // a hand-off between workgroups inside the factorisation (or the extended-precision triangular solve) was
-            // lost: its bounded poll expired and the block went on with stale data -- the numbers are void
-            if (chol_fixes >= CHOL_SYNC_LOST) throw HipError("internal error: an in-launch hand-off of the KKT factorisation timed out (device flag never raised)");
-            SolveInfo& info = L.info;
-            if (it > 0 && L.dd_k == 0) {                      // (iterations on the extended-precision path keep the count)
-                // refinement-sweep controller (mirrors oracle/conic_ipm.py next_sweeps): the norms were
-                // measured before each sweep of the two KKT solves of the previous iteration
-                const double tol = std::max(REFTOL * hs[S_NRMC], REFETA * L.rx_prev);   // ||rx|| of the iteration the norms belong to
-                int need = 0;
-                bool unconverged = false;
-                for (int slot : {int(S_RNA), int(S_RNB)}) {        // (the corrector's solve runs without sweeps and reports no norms)
-                    int k = -1;
-                    for (int q = 0; q <= std::min(L.nsweep, MAX_SWEEPS); ++q)      // n_0 .. n_nsweep
-                        if (hs[slot + q] <= tol) { k = q; break; }
-                    if (k < 0) unconverged = true;
-                    else need = std::max(need, k);
-                }
-                L.nsweep_ctl = unconverged ? std::min(MAX_SWEEPS, L.nsweep + 1) : need;
-            }
-            L.rx_prev = hs[S_DRES] * hs[S_TAU] * hs[S_NRMC];
-            info.iters = it; info.pcost = hs[S_PCOST]; info.dcost = hs[S_DCOST]; info.gap = hs[S_GAP];
-            info.relgap = hs[S_RELGAP]; info.pres = hs[S_PRES]; info.dres = hs[S_DRES];
-            info.correctors = int(hs[S_NCORR]); info.correctors_taken = int(hs[S_NPICK]);
-            if (o.verbose)
-                fprintf(stderr, "%s%3d pcost % .10e dcost % .10e gap %.2e pres %.1e dres %.1e k/t %.1e mu %.1e a %.3f sig %.1e sweeps %d chol %d%s\n",
-                        nlanes > 1 ? ("[" + std::to_string(b) + "] ").c_str() : "", it, hs[S_PCOST], hs[S_DCOST], hs[S_GAP], hs[S_PRES],
-                        hs[S_DRES], hs[S_KAPPA] / hs[S_TAU], hs[S_MU], hs[S_ALPHA], hs[S_SIGMA], L.nsweep, chol_fixes,
-                        L.dd_k > 0 ? [&] { char bf[200]; std::snprintf(bf, sizeof(bf), " | k %d refinement norms %.2e -> %.2e -> %.2e , %.2e -> %.2e -> %.2e", L.dd_k,
-                                       hs[S_RNA], hs[S_RNA + 1], S.dd_passes > 2 ? hs[S_RNA + 2] : 0.0, hs[S_RNB], hs[S_RNB + 1], S.dd_passes > 2 ? hs[S_RNB + 2] : 0.0);
-                                       return std::string(bf); }().c_str() : "");
-            auto finish = [&](int status) { L.status = status; L.live = false; };
-            const bool finite = std::isfinite(hs[S_PRES]) && std::isfinite(hs[S_DRES]) && std::isfinite(hs[S_GAP]) && hs[S_TAU] > 0;
-            if (finite && hs[S_PRES] <= o.feastol && hs[S_DRES] <= o.feastol && (hs[S_GAP] <= o.abstol || hs[S_RELGAP] <= o.reltol)) {
-                // end game (mirrors oracle/conic_ipm.py): the iterate meets the stopping rule -- keep the best such iterate (xbest) and
-                // go on until the gap measures are POLISH times below the tolerances or POLISH_MAX more iterations have passed; the
-                // best iterate is the answer however the end game ends
-                const double merit_o = std::min(hs[S_RELGAP] / o.reltol, hs[S_GAP] / std::max(o.abstol, 1e-300));
-                if (L.first_opt < 0 || merit_o < L.opt_merit) {
-                    L.opt_merit = merit_o; L.opt_info = info;
-                    S.hostMask[ROW_BEST * MAX_LANES + b] = 1;
-                    any_best = true;
-                }
-                if (L.first_opt < 0) L.first_opt = it;
-                if (hs[S_GAP] <= POLISH * o.abstol || hs[S_RELGAP] <= POLISH * o.reltol) { finish(ST_OPTIMAL); continue; }
-            }
-            if (L.first_opt >= 0 && it >= L.first_opt + POLISH_MAX) { finish(ST_OPTIMAL); continue; }      // (whether or not this iterate still meets the rule)
-            {   // what this iteration's solves run: the controller's count, POLISH_SWEEPS more in the final approach and the end game
-                const bool approach = finite && (hs[S_GAP] <= S.polish_approach * o.abstol || hs[S_RELGAP] <= S.polish_approach * o.reltol);
-                L.nsweep = std::min(MAX_SWEEPS, L.nsweep_ctl + ((approach || L.first_opt >= 0) ? S.polish_sweeps : 0));
-            }
-            if (!finite) { finish(ST_NUMERICAL); continue; }
-            const bool collapsed = hs[S_KAPPA] / hs[S_TAU] >= 1e6;
-            if (L.first_opt < 0 && (hs[S_PINF] <= o.feastol || (collapsed && hs[S_PINF] <= 1e-5))) { finish(ST_PRIMAL_INFEASIBLE); continue; }
-            if (L.first_opt < 0 && (hs[S_DINF] <= o.feastol || (collapsed && hs[S_DINF] <= 1e-5))) { finish(ST_DUAL_INFEASIBLE); continue; }
-            if (L.first_opt < 0 && hs[S_PRES] <= INACC_FEAS && hs[S_DRES] <= INACC_FEAS) {
-                // best iterate for the reduced-accuracy exit: residuals within the reduced tolerance,
-                // smallest gap measure (mirrors oracle/conic_ipm.py)
-                double merit = std::min(hs[S_RELGAP], hs[S_GAP] / std::max(o.abstol, 1e-300) * o.reltol);
-                if (merit < L.best_merit) {
-                    L.best_merit = merit; L.best_info = info; L.have_best = true;
-                    S.hostMask[ROW_BEST * MAX_LANES + b] = 1;
-                    any_best = true;
-                }
-            }
-            if (it == o.max_iter) { finish(ST_MAXIT); continue; }
-            // numerical wall (mirrors oracle/conic_ipm.py): the last factorisation replaced pivots and the
-            // residuals are out of the reduced-accuracy range, three iterations in a row
-            L.wall = (chol_fixes > 0 && (hs[S_PRES] > INACC_FEAS || hs[S_DRES] > INACC_FEAS)) ? L.wall + 1 : 0;
-            if (L.wall >= WALL_ITERS) { finish(ST_NUMERICAL); continue; }
-            any_live = true;
-        }
-        if (any_best) {
-            // xbest = x / tau on the lanes with a new best iterate -- including a lane that max_iter (or the numerical
-            // wall) retires in this very iteration: its best_info is this iterate's, so xbest has to be as well (the
-            // new-best bits were cleared for every lane above and are set by the merit test alone, not by `live`)
-            if (nlanes > 1) {
-                MBFIR_HIP(hipMemcpyAsync(S.maskT + ROW_BEST * MAX_LANES, S.hostMask + ROW_BEST * MAX_LANES, sizeof(int) * MAX_LANES,
-                                         hipMemcpyHostToDevice, st));
-                P.mask = S.mask_row(ROW_BEST);
-            }
-            hipLaunchKernelGGL(k_finish_x, lane_grid(dim3(S.nbN), nlanes), dim3(256), 0, st, P, S.x, S.Sc, S.xbest);
-            P.mask = S.mask_row(0);
-        }
-        if (!any_live) break;
-        nsweep_max = 0;
+        S.read_graph_times();
+        if (!S.judge_lanes(LH, o, it)) break;
+        int nsweep_max = 0;
         for (int b = 0; b < nlanes; ++b)
             if (LH[b].live) nsweep_max = std::max(nsweep_max, LH[b].nsweep);
-        push_masks();                                         // (a unit with opts.ddkkt pushes them again once the head knows the lanes' modes)
-        auto launch_body = [&]() {
-        // scaling + H (already on the stream when the head went out ahead of the host)
-        if (!head_out) launch_head();
-        // constant + affine systems in one batch: [x1 z1], [x2 z2]
-        // (a lock-step unit with opts.ddkkt: the lanes whose strong set is non-empty run the extended-precision solve, the others the
-        //  plain one, each under its mask -- every lane the sequence of its single solve)
-        bool dd_any = S.dd_k > 0, pl_any = S.dd_k == 0;
-        if (S.dd_unit) {
-            pl_any = false;
-            for (int b = 0; b < nlanes; ++b) pl_any = pl_any || (LH[b].live && LH[b].dd_k == 0);
-        }
-        const int* live_row = P.mask;
-        auto solve2 = [&](auto NVc, const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot, bool nosweep = false) {
-            constexpr int NVX = decltype(NVc)::value;
-            if (dd_any) {
-                if (S.dd_unit) P.mask = S.mask_row(ROW_DD);
-                S.kkt_solve_dd<NVX>(bx, bz, dx, dz, gdx, slot);
-            }
-            if (pl_any) {
-                if (S.dd_unit) P.mask = S.mask_row(ROW_PL);
-                S.kkt_solve<NVX>(bx, bz, dx, dz, gdx, nosweep ? 0 : nsweep_max, slot, true);  // W^-2 bz came with k_scaling / k_comb_rhs / k_corr_rhs
-            }
-            P.mask = live_row;
-        };
-        solve2(std::integral_constant<int, 2>(), S.bx2, S.bz2, S.dx2, S.dz2, S.gdx2, S_RNA);
-        double *x1 = S.dx2, *x2a = S.dx2 + LDV, *z1 = S.dz2, *z2a = S.dz2 + Rp, *g1 = S.gdx2, *g2a = S.gdx2 + Rp;
-        auto dots = [&](const double* xx2, const double* zz2, int mode) -> int {
-            hipLaunchKernelGGL(k_dots_r, lane_grid(dim3(std::max(S.nbC, 1)), nlanes), dim3(256), 0, st, P, S.wl, S.w3, z1, zz2, S.partR);
-            int nb = std::max(S.nbC, 1);
-            if (P.big) {
-                hipLaunchKernelGGL(k_big_dots, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.wbb, S.Sc, z1, zz2, S.scratch, S.partR);
-                nb += 1;
-            }
-            if (sharded) {
-                hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, x1, xx2, S.partR, nb, mode, S.RB, 0);
-                S.allreduce(S.RB, 3, 0);
-                hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, x1, xx2, S.partR, nb, mode, S.RB, 1);
-            }
-            return nb;                                     // unsharded: k_dir_post folds these partials itself
-        };
-        // step maxima go to partR2 (k_dir_post reads the k_dots_r partials in partR while it writes them);
-        // returns the number of partial rows; step_mode0_fused: the affine step length is left to k_comb_rhs
-        auto dir_post = [&](const double* xx2, const double* zz2, const double* gg2, double* outA, double* outB, int mode, int ndots) -> int {
-            int nb = std::max(S.nbC, 1);
-            hipLaunchKernelGGL(k_dir_post, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, S.wl, S.w3, S.lam, z1, zz2, g1, gg2, S.rz, S.Sc, outA, outB,
-                               S.partR2, mode, sharded ? nullptr : S.partR, ndots, xx2);
-            if (P.big) {
-                hipLaunchKernelGGL(k_big_dir_post, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.wbb, S.lam, z1, zz2, g1, gg2, S.rz, S.Sc, outA, outB,
-                                   S.scratch, S.partR2, mode);
-                nb += 1;
-            }
-            if (sharded) {
-                hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 0);
-                S.allreduce(S.RB, 2, 1);
-                hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 1);
-            } else if (mode == 1 && !S.fuse_fold) {
-                hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 2);
-            }
-            return nb;                                     // (fuse_fold: k_update forms the step length itself)
-        };
-        const int nd0 = dots(x2a, z2a, 0);
-        const int ns0 = dir_post(x2a, z2a, g2a, S.dssa, S.wdza, 0, nd0);
-        // combined direction (unsharded: sigma and bx are formed inside k_comb_rhs, and W^-2 bz comes with it)
-        hipLaunchKernelGGL(k_comb_rhs, lane_grid(dim3(std::max(S.nbC, 1)), nlanes), dim3(256), 0, st, P, S.wl, S.w3, S.lam, S.dssa, S.wdza, S.rz, S.Sc,
-                           S.lds, S.bzc, sharded ? nullptr : S.partR2, ns0, S.rx, S.bxc, S.dl, S.wbz);
-        if (P.big)
-            hipLaunchKernelGGL(k_big_comb_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.wbb, S.lam, S.dssa, S.wdza, S.rz, S.Sc, S.lds, S.bzc,
-                               S.scratch);
-        solve2(std::integral_constant<int, 1>(), S.bxc, S.bzc, S.dxc, S.dzc, S.gdxc, S_RNB);
-        const int nd1 = dots(S.dxc, S.dzc, 1);
-        // (extended-precision iterations: the corrector works on the orthant rows alone, with the usual passes: oracle/conic_ipm.py)
-        const int corr_cones = (!S.corr_big || (!S.dd_unit && dd_any)) ? 0 : 1;                              // one design: this iteration's mode ...
-        const int* corr_ddm = (S.dd_unit && dd_any) ? S.mask_row(ROW_DD) : nullptr;         // ... a unit: lane by lane
-        if (!use_corr) {
-            const int ns1 = dir_post(S.dxc, S.dzc, S.gdxc, S.ds, S.dz, 1, nd1);
-            hipLaunchKernelGGL(k_update, lane_grid(dim3(cdiv(std::max(N, R), 256)), nlanes), dim3(256), 0, st, P, S.Sc, x1, S.dxc, S.x, S.ds, S.dz, S.s, S.z,
-                               (!sharded && S.fuse_fold) ? (const double*)S.partR2 : (const double*)nullptr, ns1);
-            return;
-        }
-        // ---- one centrality corrector (round 6; oracle/conic_ipm.py solve(): CORR_*) -------------------------------------------
-        // the step of the predictor-corrector direction is measured but not taken (k_scal_step mode 2); the orthant rows' products
-        // at the trial step alpha0 + CORR_DELTA, projected onto the box around sigma mu, give one more right-hand side for the
-        // factorisation at hand; the candidate (predictor-corrector + corrector solution) gets its own direction and step
-        // (mode 3: own dtau / dkappa slots), k_scal_step picks the longer step by CORR_ACCEPT and moves tau, kappa, k_update_pick
-        // moves x, s, z along the direction picked.  Every lane decides for itself.
-        auto scal_step = [&](int mode, int nb) {
-            if (sharded) {
-                hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 0);
-                S.allreduce(S.RB, 2, 1);
-                hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 1);
-            } else {
-                hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, S.Sc, S.partR2, nb, mode, S.rx, S.bxc, S.RB, 2);
-            }
-        };
-        auto dir_post_c = [&](const double* xx2, const double* zz2, const double* gg2, double* outA, double* outB, int mode, int ndots) -> int {
-            int nb = std::max(S.nbC, 1);
-            hipLaunchKernelGGL(k_dir_post, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, S.wl, S.w3, S.lam, z1, zz2, g1, gg2, S.rz, S.Sc, outA, outB,
-                               S.partR2, mode, sharded ? nullptr : S.partR, ndots, xx2);
-            if (P.big) {
-                hipLaunchKernelGGL(k_big_dir_post, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.wbb, S.lam, z1, zz2, g1, gg2, S.rz, S.Sc, outA, outB,
-                                   S.scratch, S.partR2, mode);
-                nb += 1;
-            }
-            return nb;
-        };
-        const int nsA = dir_post_c(S.dxc, S.dzc, S.gdxc, S.ds, S.dz, 1, nd1);
-        scal_step(2, nsA);
-        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(S.nbC, 1)), nlanes), dim3(256), 0, st, P, S.wl, S.dl, S.lam, S.ds, S.dz, S.Sc, S.kbz, S.wbz);
-        if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, S.wbb, S.lam, S.ds, S.dz, S.Sc, S.kbz, S.scratch, corr_cones, corr_ddm);
-        solve2(std::integral_constant<int, 1>(), S.kbx, S.kbz, S.kx, S.kz, S.kg, S_RNC, S.corr_plain);     // the Cholesky solve and its residual norm (S_RNC), no sweeps (lanes on the extended-precision path: their usual passes)
-        hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(cdiv(std::max(N, R), 256)), nlanes), dim3(256), 0, st, P, S.dxc, S.dzc, S.gdxc, S.kx, S.kz, S.kg);
-        const int ndC = dots(S.kx, S.kz, 3);
-        const int nsC = dir_post_c(S.kx, S.kz, S.kg, S.kds, S.kdz, 3, ndC);
-        scal_step(S.corr_guard ? 3 : 4, nsC);
-        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(cdiv(std::max(N, R), 256)), nlanes), dim3(256), 0, st, P, S.Sc, x1, S.dxc, S.kx, S.x, S.ds, S.dz,
-                           S.kds, S.kdz, S.s, S.z);
-        };
-        if (use_graph) {
-            auto g = graphs.find(nsweep_max);
-            if (g == graphs.end()) {
-                IterGraph ig;
-                ig.ev_lo = S.evused;
-                const long chol0 = S.chol_launch_count;
-                hipGraph_t graph = nullptr;
-                hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-                if (e == hipSuccess) {
-                    launch_body();
-                    launch_residuals();
-                    e = hipStreamEndCapture(st, &graph);
-                }
-                if (e == hipSuccess) e = hipGraphInstantiate(&ig.exec, graph, nullptr, nullptr, 0);
-                if (graph) hipGraphDestroy(graph);
-                ig.ev_hi = S.evused;
-                ig.chol_launches = S.chol_launch_count - chol0;
-                S.chol_launch_count = chol0;                  // (counted per replay below)
-                if (e != hipSuccess || !ig.exec) {            // this runtime does not capture the sequence: go on eagerly
-                    (void)hipGetLastError();
-                    use_graph = false;
-                    S.evused = ig.ev_lo;
-                } else {
-                    g = graphs.emplace(nsweep_max, ig).first;
-                }
-            }
-            if (use_graph) {
-                MBFIR_HIP(hipGraphLaunch(g->second.exec, st));
-                S.chol_launch_count += g->second.chol_launches;
-                last_graph = &g->second;
-                continue;
-            }
-        }
-        launch_body();
-        launch_residuals();
+        S.push_masks(LH);                                     // (a unit with opts.ddkkt pushes them again once the head knows the lanes' modes)
+        use_graph = use_graph && S.replay_graph(LH, o, nsweep_max, use_corr);       // (false: this runtime does not capture the sequence)
+        if (use_graph) continue;
+        S.launch_iteration(LH, o, head_out, nsweep_max, use_corr);
+        S.launch_residuals();
     }
-    for (auto& g : graphs) hipGraphExecDestroy(g.second.exec);
-    P.mask = nullptr;                                         // the final x / tau of every lane, finished or not
-    hipLaunchKernelGGL(k_finish_x, lane_grid(dim3(S.nbN), nlanes), dim3(256), 0, st, P, S.x, S.Sc, S.xout);
-    xouts.assign(nlanes, std::vector<double>());
-    infos.assign(nlanes, SolveInfo());
-    for (int b = 0; b < nlanes; ++b) {
-        LaneHost& L = LH[b];
-        if (L.live) L.status = ST_MAXIT;
-        char* xo = reinterpret_cast<char*>(S.xout) + (size_t)b * S.lane_bytes;
-        if (L.first_opt >= 0) {
-            // an iterate met the stopping rule: the best of them (xbest) is the answer, however the end game ended -- its target,
-            // its iteration cap, max_iter, the numerical wall, a non-finite iterate
-            const SolveInfo last = L.info;
-            L.info = L.opt_info; L.info.iters = last.iters; L.info.correctors = last.correctors; L.info.correctors_taken = last.correctors_taken;
-            L.status = ST_OPTIMAL;
-            MBFIR_HIP(hipMemcpyAsync(xo, reinterpret_cast<char*>(S.xbest) + (size_t)b * S.lane_bytes, sizeof(double) * LDV, hipMemcpyDeviceToDevice, st));
-        } else if ((L.status == ST_MAXIT || L.status == ST_NUMERICAL) && L.have_best && L.best_info.pres <= INACC_FEAS &&
-            L.best_info.dres <= INACC_FEAS && (L.best_info.relgap <= INACC_GAP || L.best_info.gap <= o.abstol)) {
-            // the reference accepts CVX's 'Inaccurate/Solved' (fir_ap_cvx.m:176): reduced tolerances
-            const int keep_it = L.info.iters;
-            L.info = L.best_info; L.info.iters = keep_it;
-            L.status = ST_OPTIMAL_INACCURATE;
-            MBFIR_HIP(hipMemcpyAsync(xo, reinterpret_cast<char*>(S.xbest) + (size_t)b * S.lane_bytes, sizeof(double) * LDV, hipMemcpyDeviceToDevice, st));
-        }
-        const int Nb = L.Q->N();                              // (the lane's own unknowns: N is the unit's largest)
-        xouts[b].assign(Nb, 0.0);
-        MBFIR_HIP(hipMemcpyAsync(xouts[b].data(), xo, sizeof(double) * Nb, hipMemcpyDeviceToHost, st));
-    }
-    MBFIR_HIP(hipStreamSynchronize(st));
-    const double t_end = now_ms();
+    S.finish_lanes(LH, o, xouts, infos, t_begin, t_assembled);
     if (trace_host)
         fprintf(stderr, "[host] unit of %d lanes, %d iterations: issuing launches %.1f ms, waiting in the per-iteration sync %.1f ms (%.0f %% issuing)\n",
                 nlanes, it, host_issue_ms, host_wait_ms, 100.0 * host_issue_ms / std::max(host_issue_ms + host_wait_ms, 1e-9));
-    double ms_gram = 0, ms_chol = 0;
-    int builds = 0;
-    S.collect_times(ms_gram, ms_chol, builds);
-    if (!graphs.empty()) {
-        // the event pairs recorded eagerly (initial point, iterations before / without a graph) are in the pool before the graphs'
-        // own; collect_times has read every pair of the pool ONCE -- replace the graphs' single readings by the accumulated ones
-        for (auto& g : graphs)
-            for (size_t e = g.second.ev_lo; e + 3 < g.second.ev_hi; e += 4) {
-                float ga = 0, ch = 0;
-                if (hipEventElapsedTime(&ga, S.evpool[e], S.evpool[e + 1]) == hipSuccess) ms_gram -= ga;
-                if (hipEventElapsedTime(&ch, S.evpool[e + 2], S.evpool[e + 3]) == hipSuccess) ms_chol -= ch;
-                --builds;
-            }
-        ms_gram += graph_ms_gram; ms_chol += graph_ms_chol; builds += graph_builds;
-    }
-    double ms_cap = 0;
-    for (size_t i = 0; i + 1 < S.capev_used; i += 2) { float t = 0; hipEventElapsedTime(&t, S.capev[i], S.capev[i + 1]); ms_cap += t; }
-    for (int b = 0; b < nlanes; ++b) {
-        SolveInfo& info = infos[b];
-        info = LH[b].info;
-        info.status = LH[b].status;
-        info.ms_assemble = t_assembled - t_begin;
-        info.ms_solve = t_end - t_assembled;                  // of the whole lock-step batch
-        info.ms_gram = ms_gram; info.ms_chol = ms_chol; info.h_builds = builds;
-        info.n_freq = LH[b].Q->Mf; info.n_rows = LH[b].Q->R; info.n_unknowns = LH[b].Q->N();
-        info.lattice = P.trig;
-        info.lanes = nlanes;
-        info.collectives = int(S.n_collectives);
-        info.collective_bytes = S.collective_bytes;
-        info.gv_passes = int(S.n_gv); info.gtv_passes = int(S.n_gtv);
-        info.dd_iters = LH[b].dd_iters; info.dd_kmax = LH[b].dd_kmax;
-        info.dd_form = S.cap_form ? 0 : 1; info.cap_flop = S.cap_flop_sum; info.ms_cap = ms_cap;
-        info.chol_launches = int(S.chol_launch_count);
-        info.chol_flop = 2.0 / 3.0 * double(P.np) * double(P.np) * double(P.np);
-        info.gram_flop = P.trig ? double(3 * P.D1 - 1) * double(LH[b].Q->Mf) * (4.0 + 4.0 * nw)      // rotation + 2 fma per weight, per point and frequency
-                                : double(nw) * double(Mf) * double(Nt) * double(Nt + 1);
-    }
-    S.nlanes_last = nlanes; S.taps_valid = false;
 }
 
 }  // namespace mbfir
@@ -4098,7 +4097,7 @@ void Solver::test_ddsolve(int n, int k, const double* Hh, const double* U, const
     dd_syrk_launch(dU.as<double>(), int(np), dX.as<double>(), df.as<int>() + 1, int(np), dH.as<double>(), dHl.as<double>(), S.st);
     DevBuf dinv(2 * np * 64 * 8);
     double* dinvp = dinv.as<double>();
-    if (const char* ev = std::getenv("MBFIR_DD_BLOCKINV")) { if (std::atoi(ev) == 0) dinvp = nullptr; }
+    if (!read_switches().dd_blockinv) dinvp = nullptr;
     dd_chol_launch(dH.as<double>(), dHl.as<double>(), dLt.as<double>(), dLtl.as<double>(), dri.as<double>(), dri.as<double>() + np,
                    dd0.as<double>(), int(np), 1e-28, df.as<int>(), S.st, dinvp);
     DevBuf dflags(sizeof(int) * (2 * np / 32 + 8));

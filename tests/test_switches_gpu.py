@@ -256,6 +256,7 @@ def test_launch_graphs_replay_the_iteration_bit_for_bit(which, args, okw):
         h1, s1, i1 = fn(*args, info=True, opts=opts)
     assert s0 == s1 == "Solved" and i0["iters"] == i1["iters"] and i0["pcost"] == i1["pcost"] and np.array_equal(h0, h1)
     assert i1["builds"] == i0["builds"] and i1["ms_chol"] > 0 and i1["chol_launches"] == i0["chol_launches"]
+    assert i1["gv_passes"] == i0["gv_passes"] and i1["gtv_passes"] == i0["gtv_passes"]      # (a replay counts its passes like the eager iteration)
 
 
 
