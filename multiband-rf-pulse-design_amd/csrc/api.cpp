@@ -126,10 +126,9 @@ void taps_from_solution(Solver& solver, const TrigProgram& P, const std::vector<
     }
 }
 
-// Common driver: `asm_rc` is the assembly result, `post` maps the solution vector to taps.
-template <class Post>
-int run(mbfir_ctx* ctx, int asm_rc, const std::string& asm_err, TrigProgram& P, const mbfir_opts* opts,
-        mbfir_info* info, double t0, Post post) {
+// Common driver of one design: `asm_rc` / `asm_err` are the result of assembling `P`; on success the taps go to h_re / h_im.
+int run(mbfir_ctx* ctx, int asm_rc, const std::string& asm_err, const TrigProgram& P, const mbfir_opts* opts,
+        mbfir_info* info, double t0, double* h_re, double* h_im) {
     if (!ctx) return MBFIR_E_ARG;
     if (info) std::memset(info, 0, sizeof(*info));
     if (asm_rc != 0) {
@@ -190,7 +189,7 @@ int run(mbfir_ctx* ctx, int asm_rc, const std::string& asm_err, TrigProgram& P, 
         ctx->last_x = x;
         double t_solved = now_ms();
         int rc = status_to_rc(st);
-        if (rc == MBFIR_SOLVED) post(x);
+        if (rc == MBFIR_SOLVED) taps_from_solution(*ctx->solver, P, x, 0, h_re, h_im);
         fill_info(info, P, si, rc, t0, t_asm, t_solved, now_ms());
         return rc;
     } catch (const std::exception& e) {
@@ -199,6 +198,270 @@ int run(mbfir_ctx* ctx, int asm_rc, const std::string& asm_err, TrigProgram& P, 
         return MBFIR_E_HIP;
     }
 }
+
+// ---- batch of independent designs --------------------------------------------------------------
+// The jobs are assembled on the host, grouped by shape (Solver::shape_key: same dimensions, same lattice
+// structure) and cut into units of up to `lanes` designs.  A unit of one design runs as a single solve; a unit of
+// several runs in LOCK STEP on one context: one stream, one launch per phase with the design index as a grid
+// dimension, finished designs masked out (Solver::solve_lanes).  One host thread per context pulls units from a
+// shared counter, so units also overlap across the contexts' streams.  The dependency-chain phases of one design
+// (Cholesky panels, reductions) leave most of the chip idle; the other lanes' blocks fill it.
+int assemble_job(const mbfir_job& J, int grid_m, TrigProgram& P, std::string& e) {
+    switch (J.which) {
+        case DES_AP: return assemble_ap(J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params[1], grid_m, P, e);
+        case DES_QP: return assemble_qp(J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params + 1, int(J.params[3]), grid_m, P, e);
+        case DES_LINPROG: return assemble_linprog(J.n, J.nband, J.f, J.a, J.d, grid_m, P, e);
+        case DES_QPROG_PHS: {
+            std::vector<double> are(2 * J.nband), aim(2 * J.nband), dre(J.nband), dim(J.nband);
+            for (int i = 0; i < 2 * J.nband; ++i) { are[i] = J.a[2 * i]; aim[i] = J.a[2 * i + 1]; }
+            for (int i = 0; i < J.nband; ++i) { dre[i] = J.d[2 * i]; dim[i] = J.d[2 * i + 1]; }
+            return assemble_qprog_phs(J.n, J.nband, J.f, are.data(), aim.data(), dre.data(), dim.data(), grid_m, P, e);
+        }
+        default: e = "unknown designer"; return MBFIR_E_ARG;
+    }
+}
+
+// Assembled programs are a few MB of vectors each; giving them back to the allocator is 0.1-0.2 ms a piece (munmap).  The
+// workers do that for their unit while other units still run; the programs of the LAST unit to finish -- the one every
+// caller waits for -- are parked here and freed by the next batch's coordinator while its units run (or at unload).
+std::mutex g_parked_mu;
+std::vector<TrigProgram> g_parked;
+
+// One call of mbfir_solve_batch.  Round 2 assembled all jobs, then grouped, then started the units: 8 ms of a 265 ms headline
+// batch with the GPU idle, and the unit that decides the makespan (the tight-ripple designs at the head of a sweep) started
+// last of all.  Now the assembly threads take the jobs in order, and a coordinator (the calling thread) hands a unit to the
+// waiting contexts the moment its designs are there.  The units are formed SPECULATIVELY from neighbours in the job list on
+// the assumption that the batch has one shape (a sweep): the first design that differs from job 0, or fails to assemble,
+// ends the speculation, and what has not been handed out yet is grouped by shape.
+struct Batch {
+    mbfir_ctx* const* ctxs; int nctx;
+    mbfir_job* jobs; int njobs;
+    const mbfir_opts* opts;
+    double t0 = now_ms();
+    int lanes_cap = opts ? opts->lanes : 0;                    // 0 = automatic, 1 = never lock-step
+    // the assembly threads assemble every job; row-sharded and with lanes == 1 every unit is one design, assembled by its
+    // worker just before the solve (one program alive per context)
+    bool early = !(opts && opts->shard_size > 1) && lanes_cap != 1;
+    bool trace = std::getenv("MBFIR_TRACE_BATCH") != nullptr;
+    std::vector<TrigProgram> progs = std::vector<TrigProgram>(njobs);
+    std::vector<int> arc = std::vector<int>(njobs, 0);         // assembly result per job (its message is in jobs[q].err)
+    std::vector<std::vector<long>> keys = std::vector<std::vector<long>>(njobs);   // shape key, the shape's lane cap last
+    std::vector<char> assembled = std::vector<char>(njobs, 0);
+    std::vector<std::vector<int>> units;
+    std::atomic<int> next_asm{0};
+    size_t units_taken = 0, units_done = 0;
+    bool units_closed = false;
+    std::mutex mu;
+    std::condition_variable cv_asm, cv_units;
+    std::string thread_err;                                   // the first exception a thread let out
+
+    // job q into progs[q]; with early assembly its shape key too (CSR maps, lattice analysis: a sort of the grid) -- here,
+    // not in the serial grouping: 64 headline designs cost 40 ms there with the GPU idle; the structures stay with the program
+    void assemble(int q) {
+        std::string e;
+        jobs[q].err[0] = 0;
+        try {
+            arc[q] = assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e);
+            if (arc[q] == 0 && early) {
+                const SolveOpts so = to_opts(opts, progs[q].which);
+                keys[q] = Solver::shape_key(progs[q], so);
+                keys[q].push_back(Solver::max_lanes(progs[q], so));
+            }
+        } catch (const std::exception& ex) {                  // (host memory: the job is reported, the coordinator is not left waiting)
+            arc[q] = MBFIR_E_HIP; e = ex.what();
+        }
+        if (arc[q] != 0) std::snprintf(jobs[q].err, sizeof(jobs[q].err), "%s", e.c_str());
+    }
+    void assemble_loop() {
+        for (int q; (q = next_asm.fetch_add(1)) < njobs;) {
+            assemble(q);
+            { std::lock_guard<std::mutex> lk(mu); assembled[q] = 1; }
+            cv_asm.notify_all();
+        }
+    }
+    void wait_assembled(int lo, int hi) {
+        std::unique_lock<std::mutex> lk(mu);
+        cv_asm.wait(lk, [&] { for (int q = lo; q < hi; ++q) if (!assembled[q]) return false; return true; });
+    }
+    void push_unit(std::vector<int> u) {
+        { std::lock_guard<std::mutex> lk(mu); units.push_back(std::move(u)); }
+        cv_units.notify_one();
+    }
+
+    // ---- units: designs of one shape, up to `lanes` of them ------------------------------------------
+    // enough units to occupy every context, no more lanes per unit than the shape allows; an explicit request never
+    // exceeds what the shape allows
+    int lanes_per_unit(int cap, int G) const {
+        int per = std::min(cap, std::max(1, (G + nctx - 1) / nctx));
+        if (lanes_cap > 1) per = std::min(std::min(lanes_cap, cap), G);
+        return std::max(1, per);
+    }
+    // units of job 0's shape, each handed out as soon as its designs are assembled; returns how many jobs went out
+    int hand_out_first_shape() {
+        if (njobs == 0) return 0;
+        wait_assembled(0, 1);
+        if (arc[0] != 0) return 0;
+        const int per = lanes_per_unit(int(keys[0].back()), njobs);
+        int handed = 0;
+        while (handed < njobs) {
+            const int hi = std::min(njobs, handed + per);
+            wait_assembled(handed, hi);
+            for (int q = handed; q < hi; ++q)
+                if (arc[q] != 0 || keys[q] != keys[0]) return handed;
+            std::vector<int> u;
+            for (int q = handed; q < hi; ++q) u.push_back(q);
+            push_unit(std::move(u));
+            if (trace && handed == 0) std::fprintf(stderr, "[batch] first unit handed out at %.2f ms\n", now_ms() - t0);
+            handed = hi;
+        }
+        return handed;
+    }
+    // jobs [handed, njobs) by shape; which designs share a unit: neighbours in the job list (a sweep's neighbours tend to
+    // need similar iteration counts, so the lanes of a unit finish together)
+    void group_rest(int handed) {
+        std::map<std::vector<long>, std::vector<int>> groups;
+        for (int q = handed; q < njobs; ++q) {
+            if (arc[q] != 0) { push_unit({q}); continue; }                  // the single-design path reports the assembly error
+            groups[keys[q]].push_back(q);
+        }
+        for (auto& g : groups) {
+            const int G = int(g.second.size()), per = lanes_per_unit(int(g.first.back()), G);
+            for (int i = 0; i < G; i += per) push_unit(std::vector<int>(g.second.begin() + i, g.second.begin() + std::min(G, i + per)));
+        }
+    }
+    void coordinate() {
+        if (!early) {
+            for (int q = 0; q < njobs; ++q) push_unit({q});
+            return;
+        }
+        const int handed = hand_out_first_shape();
+        wait_assembled(handed, njobs);
+        if (trace) std::fprintf(stderr, "[batch] %d jobs assembled at %.2f ms\n", njobs, now_ms() - t0);
+        group_rest(handed);
+    }
+    // a context's worker: pulls units until the coordinator has closed the list
+    void work(int c) {
+        mbfir_ctx* ctx = ctxs[c];
+        for (;;) {
+            std::vector<int> U;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv_units.wait(lk, [&] { return units_taken < units.size() || units_closed; });
+                if (units_taken >= units.size()) break;
+                U = units[units_taken++];
+            }
+            if (U.size() == 1) solve_singles(ctx, U, {0});
+            else solve_lock_step(ctx, U);
+            release(U);
+        }
+    }
+    void solve_lock_step(mbfir_ctx* ctx, const std::vector<int>& U) {
+        std::vector<char> done(U.size(), 0);         // designs whose result is already out (a later error must not overwrite it)
+        try {
+            const double t_asm = now_ms();
+            std::vector<const TrigProgram*> Ps;
+            for (int q : U) Ps.push_back(&progs[q]);
+            std::vector<std::vector<double>> xs;
+            std::vector<SolveInfo> sis;
+            ctx->solver->solve_lanes(Ps, to_opts(opts, progs[U[0]].which), xs, sis);
+            const double t_solved = now_ms();
+            for (size_t b = 0; b < U.size(); ++b) {
+                mbfir_job& J = jobs[U[b]];
+                const int rc = status_to_rc(sis[b].status);
+                if (rc == MBFIR_NUMERICAL || sis[b].status == ST_OPTIMAL_INACCURATE) continue;   // single path: retries in extended precision
+                if (rc == MBFIR_SOLVED) taps_from_solution(*ctx->solver, progs[U[b]], xs[b], int(b), J.h_re, J.h_im);
+                fill_info(&J.info, progs[U[b]], sis[b], rc, t0, t_asm, t_solved, now_ms());
+                J.rc = rc;
+                ctx->last_x = xs[b];
+                report(ctx, U[b]);
+                done[b] = 1;
+            }
+        } catch (const std::exception& e) {
+            ctx->err = e.what();
+            // A ShapeError (the lock-step path does not take these programs as one unit) or a ResourceError (the unit did not
+            // get its device memory, lanes sized to the unit's maxima: ADVICE r4) is recoverable: one design at a time needs a
+            // lane's worth, and the single-design path reports its own verdict or error.  Any other error (a lost in-launch
+            // hand-off of the factorisation, a HIP error) is reported for every design of the unit that has no result yet,
+            // NOT retried -- the single-design path takes other kernels and would hide a defect of the lock-step ones behind
+            // a slow success.
+            if (!dynamic_cast<const ShapeError*>(&e) && !dynamic_cast<const ResourceError*>(&e)) {
+                for (size_t b = 0; b < U.size(); ++b) {
+                    if (done[b]) continue;
+                    mbfir_job& J = jobs[U[b]];
+                    std::memset(&J.info, 0, sizeof(J.info));
+                    J.info.status = MBFIR_E_HIP; J.info.lanes = int(U.size());
+                    J.rc = MBFIR_E_HIP;
+                    std::snprintf(J.err, sizeof(J.err), "lock-step unit of %d: %s", int(U.size()), e.what());
+                }
+                return;
+            }
+        }
+        solve_singles(ctx, U, done);
+    }
+    // the designs of unit U without a result (done[b] == 0) one at a time, each on its assembled program: run re-derives what
+    // a solve with other options needs (TrigProgram::prep is keyed by fold and dense path)
+    void solve_singles(mbfir_ctx* ctx, const std::vector<int>& U, const std::vector<char>& done) {
+        for (size_t b = 0; b < U.size(); ++b) {
+            if (done[b]) continue;
+            const int q = U[b];
+            mbfir_job& J = jobs[q];
+            const double t = now_ms();
+            if (!early) assemble(q);
+            J.rc = run(ctx, arc[q], J.err, progs[q], opts, &J.info, t, J.h_re, J.h_im);
+            report(ctx, q);
+        }
+    }
+    void report(mbfir_ctx* ctx, int q) {
+        mbfir_job& J = jobs[q];
+        if (J.rc < 0 && !J.err[0]) std::snprintf(J.err, sizeof(J.err), "%s", ctx->err.c_str());
+        if (J.z && J.z_cap > 0 && J.rc >= 0) {
+            const std::vector<double>& x = ctx->last_x;
+            std::memcpy(J.z, x.data(), sizeof(double) * std::min<size_t>(x.size(), size_t(J.z_cap)));
+        }
+    }
+    void release(const std::vector<int>& U) {
+        bool last;
+        { std::lock_guard<std::mutex> lk(mu); ++units_done; last = units_closed && units_done == units.size(); }
+        if (!last) { for (int q : U) progs[q] = TrigProgram(); return; }
+        std::lock_guard<std::mutex> lk(g_parked_mu);
+        for (int q : U) g_parked.push_back(std::move(progs[q]));
+    }
+    // a worker / assembler that throws (bad_alloc while parking programs, ...) must not take the process down
+    // (std::terminate from a thread's entry function): the first message is kept and the call returns MBFIR_E_HIP
+    template <class F>
+    void guarded(F&& body) {
+        try { body(); }
+        catch (const std::exception& e) { std::lock_guard<std::mutex> lk(mu); if (thread_err.empty()) thread_err = e.what(); }
+        catch (...) { std::lock_guard<std::mutex> lk(mu); if (thread_err.empty()) thread_err = "unknown exception in a batch thread"; }
+    }
+    // Starts the assembly threads and one worker per context, coordinates, joins; returns the first error, or "".  Thread
+    // creation can fail (EAGAIN: up to 16 + nctx threads per call): what was started is joined and the rest of the work is
+    // done by fewer threads -- in the limit by the calling thread alone (assembly inline, then the units one context after
+    // the other) -- instead of destroying joinable threads, which ends the process.
+    std::string run_threads() {
+        std::vector<std::thread> th;
+        const int nasm = early ? std::max(1, std::min(njobs, std::min(16, int(std::thread::hardware_concurrency())))) : 0;
+        const int nwork = std::max(1, std::min(nctx, njobs));
+        int started_asm = 0, started_work = 0;
+        try {
+            for (int i = 0; i < nasm; ++i) { th.emplace_back([this] { guarded([this] { assemble_loop(); }); }); ++started_asm; }
+            for (int c = 0; c < nwork; ++c) { th.emplace_back([this, c] { guarded([this, c] { work(c); }); }); ++started_work; }
+        } catch (const std::system_error&) {}
+        if (nasm > 0 && started_asm == 0) guarded([this] { assemble_loop(); });
+        std::string err;
+        try { coordinate(); } catch (const std::exception& e) { err = e.what(); }
+        { std::lock_guard<std::mutex> lk(mu); units_closed = true; }
+        cv_units.notify_all();
+        {
+            std::vector<TrigProgram> old;
+            { std::lock_guard<std::mutex> lk(g_parked_mu); old.swap(g_parked); }
+        }                                                                // (the previous batch's last programs, freed while the units run)
+        if (started_work == 0) guarded([this] { work(0); });
+        for (auto& t : th) t.join();
+        if (trace) std::fprintf(stderr, "[batch] %zu units, all done at %.2f ms\n", units.size(), now_ms() - t0);
+        return err.empty() ? thread_err : err;
+    }
+};
 
 }  // namespace
 
@@ -329,7 +592,7 @@ int mbfir_ap_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const doub
     TrigProgram P;
     std::string e;
     int rc = assemble_ap(n, nband, f, a, d, obj, peak, opts ? opts->grid_m : 0, P, e);
-    return run(ctx, rc, e, P, opts, info, t0, [&](const std::vector<double>& x) { taps_from_solution(*ctx->solver, P, x, 0, h_re, h_im); });
+    return run(ctx, rc, e, P, opts, info, t0, h_re, h_im);
 }
 
 int mbfir_qp_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const double* a, const double* d,
@@ -339,7 +602,7 @@ int mbfir_qp_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const doub
     TrigProgram P;
     std::string e;
     int rc = assemble_qp(n, nband, f, a, d, kquad, obj, nobj, opts ? opts->grid_m : 0, P, e);
-    return run(ctx, rc, e, P, opts, info, t0, [&](const std::vector<double>& x) { taps_from_solution(*ctx->solver, P, x, 0, h_re, h_im); });
+    return run(ctx, rc, e, P, opts, info, t0, h_re, h_im);
 }
 
 int mbfir_linprog_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const double* a, const double* d,
@@ -348,7 +611,7 @@ int mbfir_linprog_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const
     TrigProgram P;
     std::string e;
     int rc = assemble_linprog(n, nband, f, a, d, opts ? opts->grid_m : 0, P, e);
-    return run(ctx, rc, e, P, opts, info, t0, [&](const std::vector<double>& x) { taps_from_solution(*ctx->solver, P, x, 0, h_re, h_im); });
+    return run(ctx, rc, e, P, opts, info, t0, h_re, h_im);
 }
 
 int mbfir_qprog_phs_solve(mbfir_ctx* ctx, int n, int nband, const double* f, const double* ac_re,
@@ -358,287 +621,19 @@ int mbfir_qprog_phs_solve(mbfir_ctx* ctx, int n, int nband, const double* f, con
     TrigProgram P;
     std::string e;
     int rc = assemble_qprog_phs(n, nband, f, ac_re, ac_im, dc_re, dc_im, opts ? opts->grid_m : 0, P, e);
-    return run(ctx, rc, e, P, opts, info, t0, [&](const std::vector<double>& x) { taps_from_solution(*ctx->solver, P, x, 0, h_re, h_im); });
+    return run(ctx, rc, e, P, opts, info, t0, h_re, h_im);
 }
 
-// ---- batch of independent designs --------------------------------------------------------------
-// The jobs are assembled on the host, grouped by shape (Solver::shape_key: same dimensions, same lattice
-// structure) and cut into units of up to `lanes` designs.  A unit of one design runs as a single solve; a unit of
-// several runs in LOCK STEP on one context: one stream, one launch per phase with the design index as a grid
-// dimension, finished designs masked out (Solver::solve_lanes).  One host thread per context pulls units from a
-// shared counter, so units also overlap across the contexts' streams.  The dependency-chain phases of one design
-// (Cholesky panels, reductions) leave most of the chip idle; the other lanes' blocks fill it.
-static int one_job(mbfir_ctx* ctx, mbfir_job& J, const mbfir_opts* opts) {
-    switch (J.which) {
-        case DES_AP:
-            return mbfir_ap_solve(ctx, J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params[1], opts, J.h_re, J.h_im, &J.info);
-        case DES_QP:
-            return mbfir_qp_solve(ctx, J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params + 1, int(J.params[3]), opts, J.h_re, J.h_im, &J.info);
-        case DES_LINPROG:
-            return mbfir_linprog_solve(ctx, J.n, J.nband, J.f, J.a, J.d, opts, J.h_re, J.h_im, &J.info);
-        case DES_QPROG_PHS: {
-            std::vector<double> are(2 * J.nband), aim(2 * J.nband), dre(J.nband), dim(J.nband);
-            for (int i = 0; i < 2 * J.nband; ++i) { are[i] = J.a[2 * i]; aim[i] = J.a[2 * i + 1]; }
-            for (int i = 0; i < J.nband; ++i) { dre[i] = J.d[2 * i]; dim[i] = J.d[2 * i + 1]; }
-            return mbfir_qprog_phs_solve(ctx, J.n, J.nband, J.f, are.data(), aim.data(), dre.data(), dim.data(), opts, J.h_re, J.h_im, &J.info);
-        }
-        default: return MBFIR_E_ARG;
-    }
-}
-static int assemble_job(const mbfir_job& J, int grid_m, TrigProgram& P, std::string& e) {
-    switch (J.which) {
-        case DES_AP: return assemble_ap(J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params[1], grid_m, P, e);
-        case DES_QP: return assemble_qp(J.n, J.nband, J.f, J.a, J.d, J.params[0], J.params + 1, int(J.params[3]), grid_m, P, e);
-        case DES_LINPROG: return assemble_linprog(J.n, J.nband, J.f, J.a, J.d, grid_m, P, e);
-        case DES_QPROG_PHS: {
-            std::vector<double> are(2 * J.nband), aim(2 * J.nband), dre(J.nband), dim(J.nband);
-            for (int i = 0; i < 2 * J.nband; ++i) { are[i] = J.a[2 * i]; aim[i] = J.a[2 * i + 1]; }
-            for (int i = 0; i < J.nband; ++i) { dre[i] = J.d[2 * i]; dim[i] = J.d[2 * i + 1]; }
-            return assemble_qprog_phs(J.n, J.nband, J.f, are.data(), aim.data(), dre.data(), dim.data(), grid_m, P, e);
-        }
-        default: e = "unknown designer"; return MBFIR_E_ARG;
-    }
-}
-
-// Assembled programs are a few MB of vectors each; giving them back to the allocator is 0.1-0.2 ms a piece (munmap).  The
-// workers do that for their unit while other units still run; the programs of the LAST unit to finish -- the one every
-// caller waits for -- are parked here and freed by the next batch's coordinator while its units run (or at unload).
-static std::mutex g_parked_mu;
-static std::vector<TrigProgram> g_parked;
-
+// the batch of independent designs: see Batch above
 int mbfir_solve_batch(mbfir_ctx* const* ctxs, int nctx, mbfir_job* jobs, int njobs, const mbfir_opts* opts) {
     if (!ctxs || nctx < 1 || (!jobs && njobs > 0) || njobs < 0) return MBFIR_E_ARG;
     for (int c = 0; c < nctx; ++c)
         if (!ctxs[c]) return MBFIR_E_ARG;
-    const double t0 = now_ms();
-    const bool sharded = opts && opts->shard_size > 1;
-    int lanes_cap = opts && opts->lanes != 0 ? opts->lanes : 0;              // 0 = automatic, 1 = never lock-step
-    if (const char* ev = std::getenv("MBFIR_LANES")) lanes_cap = std::atoi(ev);
-    // ---- host assembly, in parallel; units start as soon as their designs are assembled -------------------
-    // Round 2 assembled all jobs, then grouped, then started the units: 8 ms of a 265 ms headline batch with the GPU idle,
-    // and the unit that decides the makespan (the tight-ripple designs at the head of a sweep) started last of all.  Now the
-    // assembly threads take the jobs in order, and a coordinator (the calling thread) hands a unit to the waiting contexts
-    // the moment its designs are there.  The units are formed SPECULATIVELY from neighbours in the job list on the
-    // assumption that the batch has one shape (a sweep): the first design that differs from job 0, or fails to assemble,
-    // ends the speculation, and what has not been handed out yet is grouped by shape as before.
-    std::vector<TrigProgram> progs(njobs);
-    std::vector<int> arc(njobs, 0);
-    std::vector<std::vector<long>> keys(njobs);
-    std::mutex mu;
-    std::condition_variable cv_asm, cv_units;
-    std::vector<char> assembled(njobs, 0);
-    std::vector<std::vector<int>> units;
-    size_t units_taken = 0, units_done = 0;
-    bool units_closed = false;
-    const bool trace = std::getenv("MBFIR_TRACE_BATCH") != nullptr;
-    std::atomic<int> next_asm(0);
-    auto asm_work = [&]() {
-        for (;;) {
-            const int q = next_asm.fetch_add(1);
-            if (q >= njobs) break;
-            std::string e;
-            jobs[q].err[0] = 0;
-            try {
-                arc[q] = sharded || lanes_cap == 1 ? 0 : assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e);
-                if (arc[q] == 0 && !(sharded || lanes_cap == 1)) {
-                    // the shape key (CSR maps, lattice analysis: a sort of the grid) here, not in the serial grouping loop:
-                    // 64 headline designs cost 40 ms there with the GPU idle; the structures stay with the program
-                    const SolveOpts so = to_opts(opts, progs[q].which);
-                    keys[q] = Solver::shape_key(progs[q], so);
-                    keys[q].push_back(Solver::max_lanes(progs[q], so));
-                }
-            } catch (const std::exception& ex) {               // (host memory: the job is reported, the coordinator is not left waiting)
-                arc[q] = MBFIR_E_HIP; e = ex.what();
-            }
-            if (arc[q] != 0) std::snprintf(jobs[q].err, sizeof(jobs[q].err), "%s", e.c_str());
-            { std::lock_guard<std::mutex> lk(mu); assembled[q] = 1; }
-            cv_asm.notify_all();
-        }
-    };
-    auto wait_assembled = [&](int lo, int hi) {
-        std::unique_lock<std::mutex> lk(mu);
-        cv_asm.wait(lk, [&] { for (int q = lo; q < hi; ++q) if (!assembled[q]) return false; return true; });
-    };
-    auto push_unit = [&](std::vector<int> u) {
-        { std::lock_guard<std::mutex> lk(mu); units.push_back(std::move(u)); }
-        cv_units.notify_one();
-    };
-    int order = 0;
-    if (const char* ev = std::getenv("MBFIR_UNIT_ORDER")) order = std::atoi(ev);
-    // ---- units: designs of one shape, up to `lanes` of them ------------------------------------------
-    auto coordinate = [&]() {
-        if (sharded || lanes_cap == 1) {
-            wait_assembled(0, njobs);
-            for (int q = 0; q < njobs; ++q) push_unit({q});
-            return;
-        }
-        // enough units to occupy every context, no more lanes per unit than the shape allows; an explicit request never
-        // exceeds what the shape allows
-        auto lanes_per_unit = [&](int cap, int G) {
-            int per = std::min(cap, std::max(1, (G + nctx - 1) / nctx));
-            if (lanes_cap > 1) per = std::min(std::min(lanes_cap, cap), G);
-            return std::max(1, per);
-        };
-        int handed = 0;                                            // jobs [0, handed) are in units already
-        if (njobs > 0 && order != 1) {
-            wait_assembled(0, 1);
-            if (arc[0] == 0) {
-                const int per = lanes_per_unit(int(keys[0].back()), njobs);
-                while (handed < njobs) {
-                    const int hi = std::min(njobs, handed + per);
-                    wait_assembled(handed, hi);
-                    bool same = true;
-                    for (int q = handed; q < hi && same; ++q) same = arc[q] == 0 && keys[q] == keys[0];
-                    if (!same) break;
-                    std::vector<int> u;
-                    for (int q = handed; q < hi; ++q) u.push_back(q);
-                    push_unit(std::move(u));
-                    if (trace && handed == 0) std::fprintf(stderr, "[batch] first unit handed out at %.2f ms\n", now_ms() - t0);
-                    handed = hi;
-                }
-            }
-        }
-        wait_assembled(handed, njobs);
-        if (trace) std::fprintf(stderr, "[batch] %d jobs assembled at %.2f ms\n", njobs, now_ms() - t0);
-        std::map<std::vector<long>, std::vector<int>> groups;
-        for (int q = handed; q < njobs; ++q) {
-            if (arc[q] != 0) { push_unit({q}); continue; }                  // the single-design path reports the assembly error
-            groups[keys[q]].push_back(q);
-        }
-        for (auto& g : groups) {
-            const int G = int(g.second.size()), per = lanes_per_unit(int(g.first.back()), G);
-            // Which designs share a unit: neighbours in the job list (a sweep's neighbours tend to need similar
-            // iteration counts, so the lanes of a unit finish together) or, MBFIR_UNIT_ORDER=1, dealt round-robin over
-            // the units (every unit gets its share of the slow designs: at the end of the batch all streams still
-            // have live lanes instead of one stream running the slow unit alone)
-            const int nunits = (G + per - 1) / per;
-            if (order == 1 && nunits > 1) {
-                std::vector<std::vector<int>> us(nunits);
-                for (int i = 0; i < G; ++i) us[i % nunits].push_back(g.second[i]);
-                for (auto& u : us) push_unit(u);
-            } else {
-                for (int i = 0; i < G; i += per) push_unit(std::vector<int>(g.second.begin() + i, g.second.begin() + std::min(G, i + per)));
-            }
-        }
-    };
-    auto work = [&](int c) {
-        mbfir_ctx* ctx = ctxs[c];
-        for (;;) {
-            std::vector<int> U;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv_units.wait(lk, [&] { return units_taken < units.size() || units_closed; });
-                if (units_taken >= units.size()) break;
-                U = units[units_taken++];
-            }
-            auto finish_job = [&](int q) {
-                mbfir_job& J = jobs[q];
-                if (J.rc < 0 && !J.err[0]) std::snprintf(J.err, sizeof(J.err), "%s", ctx->err.c_str());
-                if (J.z && J.z_cap > 0 && J.rc >= 0) {
-                    const std::vector<double>& x = ctx->last_x;
-                    std::memcpy(J.z, x.data(), sizeof(double) * std::min<size_t>(x.size(), size_t(J.z_cap)));
-                }
-            };
-            auto release_programs = [&]() {
-                bool last;
-                { std::lock_guard<std::mutex> lk(mu); ++units_done; last = units_closed && units_done == units.size(); }
-                if (!last) { for (int q : U) progs[q] = TrigProgram(); return; }
-                std::lock_guard<std::mutex> lk(g_parked_mu);
-                for (int q : U) g_parked.push_back(std::move(progs[q]));
-            };
-            if (U.size() == 1) {
-                jobs[U[0]].rc = one_job(ctx, jobs[U[0]], opts);
-                finish_job(U[0]);
-                release_programs();
-                continue;
-            }
-            std::vector<char> done(U.size(), 0);         // designs of the unit whose result is already out (a later error must not overwrite it)
-            try {
-                const double t_asm = now_ms();
-                std::vector<const TrigProgram*> Ps;
-                for (int q : U) Ps.push_back(&progs[q]);
-                std::vector<std::vector<double>> xs;
-                std::vector<SolveInfo> sis;
-                const SolveOpts so = to_opts(opts, progs[U[0]].which);
-                ctx->solver->solve_lanes(Ps, so, xs, sis);
-                const double t_solved = now_ms();
-                std::vector<int> redo;
-                for (size_t b = 0; b < U.size(); ++b) {
-                    mbfir_job& J = jobs[U[b]];
-                    const int rc = status_to_rc(sis[b].status);
-                    if (rc == MBFIR_NUMERICAL || sis[b].status == ST_OPTIMAL_INACCURATE) { redo.push_back(U[b]); continue; }   // single path: retries in extended precision
-                    if (rc == MBFIR_SOLVED) taps_from_solution(*ctx->solver, progs[U[b]], xs[b], int(b), J.h_re, J.h_im);
-                    fill_info(&J.info, progs[U[b]], sis[b], rc, t0, t_asm, t_solved, now_ms());
-                    J.rc = rc;
-                    ctx->last_x = xs[b];
-                    finish_job(U[b]);
-                    done[b] = 1;
-                }
-                for (size_t b = 0; b < U.size(); ++b) if (!done[b]) done[b] = 2;      // (the redo list: their single solves report for themselves)
-                for (int q : redo) { jobs[q].rc = one_job(ctx, jobs[q], opts); finish_job(q); }
-            } catch (const ShapeError& e) {
-                // the lock-step path does not take these programs as one unit: every design of it goes through the
-                // single-design path, which reports its own verdict or error
-                ctx->err = e.what();
-                for (size_t b = 0; b < U.size(); ++b) if (!done[b]) { const int q = U[b]; jobs[q].rc = one_job(ctx, jobs[q], opts); finish_job(q); }
-            } catch (const ResourceError& e) {
-                // the unit did not get its device memory (lanes sized to the unit's maxima: ADVICE r4): recoverable -- one design
-                // at a time needs a lane's worth
-                ctx->err = e.what();
-                for (size_t b = 0; b < U.size(); ++b) if (!done[b]) { const int q = U[b]; jobs[q].rc = one_job(ctx, jobs[q], opts); finish_job(q); }
-            } catch (const std::exception& e) {
-                // an internal or device error (a lost in-launch hand-off of the factorisation, a HIP error):
-                // reported for every design of the unit that has no result yet, NOT retried -- the single-design path takes other
-                // kernels and would hide a defect of the lock-step ones behind a slow success
-                ctx->err = e.what();
-                for (size_t b = 0; b < U.size(); ++b) {
-                    if (done[b] == 1) continue;
-                    const int q = U[b];
-                    std::memset(&jobs[q].info, 0, sizeof(jobs[q].info));
-                    jobs[q].info.status = MBFIR_E_HIP; jobs[q].info.lanes = int(U.size());
-                    jobs[q].rc = MBFIR_E_HIP;
-                    std::snprintf(jobs[q].err, sizeof(jobs[q].err), "lock-step unit of %d: %s", int(U.size()), e.what());
-                }
-            }
-            release_programs();
-        }
-    };
-    // a worker / assembler that throws (bad_alloc while parking programs, ...) must not take the process down
-    // (std::terminate from a thread's entry function): the first message is kept and the call returns MBFIR_E_HIP
-    std::string thread_err;
-    auto guarded = [&](auto&& body) {
-        try { body(); }
-        catch (const std::exception& e) { std::lock_guard<std::mutex> lk(mu); if (thread_err.empty()) thread_err = e.what(); }
-        catch (...) { std::lock_guard<std::mutex> lk(mu); if (thread_err.empty()) thread_err = "unknown exception in a batch thread"; }
-    };
-    std::vector<std::thread> th;
-    const int nasm = std::max(1, std::min(njobs, std::min(16, int(std::thread::hardware_concurrency()))));
-    const int nwork = std::max(1, std::min(nctx, njobs));
-    // Thread creation can fail (EAGAIN: up to 16 + nctx threads per call): what was started is joined and the rest of the
-    // work is done by fewer threads -- in the limit by the calling thread alone (assembly inline, then the units one context
-    // after the other) -- instead of destroying joinable threads, which ends the process.
-    int started_asm = 0, started_work = 0;
-    try {
-        for (int c = 0; c < nasm; ++c) { th.emplace_back([&] { guarded(asm_work); }); ++started_asm; }
-        for (int c = 0; c < nwork; ++c) { th.emplace_back([&, c] { guarded([&] { work(c); }); }); ++started_work; }
-    } catch (const std::system_error&) {}
-    if (started_asm == 0) guarded(asm_work);
-    std::string coord_err;
-    try { coordinate(); } catch (const std::exception& e) { coord_err = e.what(); }
-    { std::lock_guard<std::mutex> lk(mu); units_closed = true; }
-    cv_units.notify_all();
-    {
-        std::vector<TrigProgram> old;
-        { std::lock_guard<std::mutex> lk(g_parked_mu); old.swap(g_parked); }
-    }                                                                // (the previous batch's last programs, freed while the units run)
-    if (started_work == 0) guarded([&] { work(0); });
-    for (auto& t : th) t.join();
-    if (coord_err.empty() && !thread_err.empty()) coord_err = thread_err;
-    if (trace) std::fprintf(stderr, "[batch] %zu units, all done at %.2f ms\n", units.size(), now_ms() - t0);
-    if (!coord_err.empty()) {
+    const std::string err = Batch{ctxs, nctx, jobs, njobs, opts}.run_threads();
+    if (!err.empty()) {
         for (int q = 0; q < njobs; ++q) {                  // (host memory exhausted while forming units: nothing of the batch is reported)
             jobs[q].rc = MBFIR_E_HIP;
-            std::snprintf(jobs[q].err, sizeof(jobs[q].err), "%s", coord_err.c_str());
+            std::snprintf(jobs[q].err, sizeof(jobs[q].err), "%s", err.c_str());
         }
         return MBFIR_E_HIP;
     }

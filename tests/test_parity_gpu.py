@@ -84,19 +84,23 @@ def test_context_reuse_like_a_bisection():
 
 def test_batch_of_designs_matches_single_calls(golden):
     """mbfir_solve_batch: all four designers, feasible and infeasible jobs, 4 streams in flight; every
-    job must return what the single-design entry point returns (golden taps within the tolerance)."""
+    job must return what the single-design entry point returns (golden taps within the tolerance).  Once with the
+    default lanes and once with lanes=1, where every design is a unit of its own assembled by its worker."""
     names = sorted(CASES) * 2
-    res = mbfir.solve_batch([CASES[nm] for nm in names], streams=4, info=True)
-    assert len(res) == len(names)
-    for nm, (h, status, info) in zip(names, res):
-        g = golden[nm]
-        assert status == g["status"], nm
-        if status == "Solved":
-            hg = np.array(g["h"]["re"]) + 1j * np.array(g["h"]["im"])
-            assert relinf(h, hg) <= TAP_TOL, nm
-            assert abs(info["pcost"] - g["pcost"]) <= 1e-7 * max(1.0, abs(g["pcost"]))
-        else:
-            assert len(h) == 0
+    for lanes in (0, 1):
+        res = mbfir.solve_batch([CASES[nm] for nm in names], streams=4, info=True, opts=mbfir.make_opts(lanes=lanes))
+        assert len(res) == len(names)
+        for nm, (h, status, info) in zip(names, res):
+            g = golden[nm]
+            assert status == g["status"], (nm, lanes)
+            if status == "Solved":
+                hg = np.array(g["h"]["re"]) + 1j * np.array(g["h"]["im"])
+                assert relinf(h, hg) <= TAP_TOL, (nm, lanes)
+                assert abs(info["pcost"] - g["pcost"]) <= 1e-7 * max(1.0, abs(g["pcost"])), (nm, lanes)
+            else:
+                assert len(h) == 0, (nm, lanes)
+            if lanes == 1:
+                assert info["lanes"] == 1, nm
 
 
 def _check_ap_solution(n, f, a, d, obj, peak, grid_m, info, z):
