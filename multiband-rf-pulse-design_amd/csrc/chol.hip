@@ -1717,7 +1717,26 @@ __global__ void k_transpose(const double* __restrict__ M, double* __restrict__ M
     for (int r = threadIdx.y; r < 32; r += blockDim.y) Mt[(long)(bx + r) * np + by + threadIdx.x] = tile[threadIdx.x][r];
 }
 
-int chol_inv_launch(double* H, double* M, double* Mt, double* W1, int np, int* flag, hipStream_t st,
+void chol_set_lose_step(int lose, hipStream_t st) {
+    // the bound shrinks while a step is lost, so that the test takes a second.  The symbols are per device and the contexts of a batch
+    // call this from parallel host threads: the value each device holds is remembered per device, under a mutex.
+    static std::mutex lose_mu;
+    static int lose_now[64];
+    static bool lose_init = false;
+    int dev = 0;
+    hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(lose_mu);
+    if (!lose_init) { for (int& v : lose_now) v = -1; lose_init = true; }
+    if (dev >= 0 && dev < 64 && lose != lose_now[dev]) {
+        const int limit = lose >= 0 ? (1 << 14) : CHOL_SPIN_LIMIT_DEFAULT;
+        hipMemcpyToSymbolAsync(HIP_SYMBOL(g_chol_lose_step), &lose, sizeof(int), 0, hipMemcpyHostToDevice, st);
+        hipMemcpyToSymbolAsync(HIP_SYMBOL(g_chol_spin_limit), &limit, sizeof(int), 0, hipMemcpyHostToDevice, st);
+        hipStreamSynchronize(st);
+        lose_now[dev] = lose;
+    }
+}
+
+int chol_inv_launch(double* H, double* M, double* Mt, double* W1, int np, int* flag, hipStream_t st, int split, bool poison,
                     double* Lcopy, hipEvent_t e0, hipEvent_t e1, int nlanes, size_t lane_bytes, const int* mask) {
     int launches = 0;
     const int nblk = np / CB;
@@ -1732,36 +1751,13 @@ int chol_inv_launch(double* H, double* M, double* Mt, double* W1, int np, int* f
     a.Mt = Mt;
     // Lock-step batches split every step (see CholStep::phase): with several designs in flight the chip is no longer
     // empty, and the 4 * nrem row blocks of a step each repeating the 64-pivot factorisation of L_kk is what fills it.
-    // MBFIR_CHOL_SPLIT: 4 = the whole factorisation in ONE launch (k_chol_dag; default), 1 = one launch per step with
+    // split (MBFIR_CHOL_SPLIT, read by the caller): 4 = the whole factorisation in ONE launch (k_chol_dag; default), 1 = one launch per step with
     // the row blocks waiting for their lane's diagonal block on a flag, 2 = two launches per step, 0 = fused step
     // (every row block factorises L_kk itself; one launch per step).
-    // default: the single launch for lock-step batches and, from np = 4096 on, for single designs too (1.9 ms against 2.4 for
+    // default (split < 0): the single launch for lock-step batches and, from np = 4096 on, for single designs too (1.9 ms against 2.4 for
     // the split and 2.7 for the fused per-step form); one or two smaller designs keep the fused step, one launch per step
     // (every row block factorises L_kk itself: lowest latency -- 350 against 375 us at np = 1024)
-    int split = (nlanes >= 3 || np >= 4096) ? 4 : 0;
-    if (const char* ev = std::getenv("MBFIR_CHOL_SPLIT")) split = std::atoi(ev);
-    bool poison = false;
-    if (const char* ev = std::getenv("MBFIR_POISON")) poison = std::atoi(ev) != 0;
-    {   // test hook: lose the hand-off of one panel step (see g_chol_lose_step); the bound shrinks so that the test takes a second.
-        // The symbols are per device and the contexts of a batch call this from parallel host threads: the value each device
-        // holds is remembered per device, under a mutex.
-        static std::mutex lose_mu;
-        static int lose_now[64];
-        static bool lose_init = false;
-        int lose = -1;
-        if (const char* ev = std::getenv("MBFIR_TEST_LOSE_FLAG")) lose = std::atoi(ev);
-        int dev = 0;
-        hipGetDevice(&dev);
-        std::lock_guard<std::mutex> lk(lose_mu);
-        if (!lose_init) { for (int& v : lose_now) v = -1; lose_init = true; }
-        if (dev >= 0 && dev < 64 && lose != lose_now[dev]) {
-            const int limit = lose >= 0 ? (1 << 14) : CHOL_SPIN_LIMIT_DEFAULT;
-            hipMemcpyToSymbolAsync(HIP_SYMBOL(g_chol_lose_step), &lose, sizeof(int), 0, hipMemcpyHostToDevice, st);
-            hipMemcpyToSymbolAsync(HIP_SYMBOL(g_chol_spin_limit), &limit, sizeof(int), 0, hipMemcpyHostToDevice, st);
-            hipStreamSynchronize(st);
-            lose_now[dev] = lose;
-        }
-    }
+    if (split < 0) split = (nlanes >= 3 || np >= 4096) ? 4 : 0;
     if ((long)dag_cnt_ints(nblk) * 4 > ((long)np * np - (long)np) * 8) split = split == 4 ? (nlanes >= 3 ? 1 : 0) : split;   // (W1 too small: np = 64)
     const int nsync = split == 4 ? dag_cnt_ints(nblk) : nblk + 1;
     hipLaunchKernelGGL(k_chol_init, dim3(cdiv(std::max(np, nsync), 256), nlanes), dim3(256), 0, st, H, np, W1, flag, a.sync, nsync, lane_bytes, mask,

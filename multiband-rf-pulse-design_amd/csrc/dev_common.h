@@ -125,10 +125,15 @@ void gram_tiles_host(const GramPlan& gp, int* tile_ij);   // tile list + the XCD
 // W1 is a workspace of 66*np doubles.  flag[0] counts replaced (noise-level) pivots.
 // e0 / e1 (optional) are recorded right before / after the np/64 + 1 k_chol_step launches.
 // Lock-step batch: nlanes designs, the buffers of lane b at + b * lane_bytes, mask (nlanes ints or null) = lanes to do.
+// split: the form (MBFIR_CHOL_SPLIT: 4 one launch, 1 / 2 the split step in one / two launches per step, 0 the fused step; < 0 the
+// default for nlanes and np); poison (MBFIR_POISON): NaN in the diagonal-block images before the build.
 // Returns the number of k_chol_step launches it issued (one per panel step, two for lock-step batches).
-int chol_inv_launch(double* H, double* M, double* Mt, double* W1, int np, int* flag, hipStream_t st,
+int chol_inv_launch(double* H, double* M, double* Mt, double* W1, int np, int* flag, hipStream_t st, int split, bool poison,
                     double* Lcopy = nullptr, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr, int nlanes = 1,
                     size_t lane_bytes = 0, const int* mask = nullptr);   // on exit H is scratch; Lcopy (optional) receives L
+// test hook (MBFIR_TEST_LOSE_FLAG): the diagonal block of panel step `lose` (-1: none) does not raise its flag on the current
+// device; once per solve, before its factorisations are queued on st
+void chol_set_lose_step(int lose, hipStream_t st);
 
 // L (np x np, clean lower triangle) from a factored H, the diagonal-block images (W1 + np) and 1 / diag(L) (W1 + 65 np)
 __global__ void k_extract_L_pub(const double* __restrict__ H, int np, const double* __restrict__ Dfac,

@@ -31,7 +31,6 @@
 // Row-sharded solves: reductions are ncclAllReduce calls on the solver stream (run-time bound RCCL) or a host hook.
 #include "dev_common.h"
 #include <functional>
-#include <map>
 #include <mutex>
 #include <thread>
 #include "cone_dev.h"
@@ -111,7 +110,7 @@ enum {
 };
 constexpr double STEP = 0.99;
 constexpr double SIGMA_MAX = 0.25;   // cap of Mehrotra's centring parameter (oracle/conic_ipm.py SIGMA_MAX)
-constexpr double SIGMA_MAX_CORR = 0.05;      // ... where a centrality corrector follows the direction (oracle/conic_ipm.py SIGMA_MAX_CORR; MBFIR_SIGMA_MAX overrides it, a diagnostic)
+constexpr double SIGMA_MAX_CORR = 0.05;      // ... where a centrality corrector follows the direction (oracle/conic_ipm.py SIGMA_MAX_CORR)
 // one centrality corrector per iteration on the orthant rows (oracle/conic_ipm.py CORR_*)
 constexpr double CORR_DELTA = 0.5, CORR_BMIN = 0.1, CORR_BMAX = 10.0, CORR_ACCEPT = 1.01, CORR_ETA = 1.0;
 // end game: an iterate that meets the stopping rule is kept and the iteration goes on until the gap measures are POLISH times below
@@ -1468,7 +1467,8 @@ __global__ __launch_bounds__(1024) void k_scal_step(DProg P, double* __restrict_
             Sc[S_ALPHA0] = t == 0.0 ? 1.0 : fmin(1.0, STEP / t);
         } else {
             double a = t == 0.0 ? 1.0 : fmin(1.0, STEP / t);
-            if (mode >= 3) {                              // corrected against uncorrected direction (oracle/conic_ipm.py CORR_ACCEPT; mode 4, a diagnostic: without the residual guard)
+            if (mode >= 3) {                              // corrected against uncorrected direction (oracle/conic_ipm.py CORR_ACCEPT; mode 4, the form
+                                                          // without the residual guard, is no longer passed by the host: its term stays for the NOTE below)
                 // (its solve ran without refinement sweeps; what it leaves of the dual equation, ||G'dzk|| in S_RNC, must not exceed
                 //  CORR_ETA times the iterate's own ||rx|| = dres tau ||c|| -- or the absolute floor of the refinement)
                 const double a0 = Sc[S_ALPHA0];
@@ -2071,59 +2071,40 @@ __global__ void k_finish_x(DProg P, const double* __restrict__ x, const double* 
 // ================================================================================================
 // host driver
 // ================================================================================================
-// The MBFIR_* switches of the solver's host code, read from the environment once per call of solve_lanes, shape_key and
-// max_lanes (tests change them between solves in one process).  Each default is the behaviour with the switch unset.
+// The MBFIR_* switches of the solver's host code and of its factorisation, read from the environment once per call of solve_lanes,
+// shape_key, max_lanes and the factorisation's test hooks (tests change them between solves in one process).  Each default is the
+// behaviour with the switch unset.
 struct SolveSwitches {
     bool corrector = true;       // CORRECTOR=0: no centrality corrector (programs without orthant rows never run it)
-    bool corr_plain = true;      // CORR_PLAIN=0 (diagnostic): the corrector's solve with the refinement sweeps of the other solves
-    bool corr_guard = true;      // CORR_GUARD=0 (diagnostic): take a correction even where its unrefined solve leaves more of the dual equation than the iterate's own residual
-    bool corr_big = true;        // CORR_BIG=0 (diagnostic): correct the orthant rows alone, not the big cone's products (round 6's first form)
-    double polish_approach = POLISH_APPROACH;   // POLISH_APPROACH (>= 1, diagnostic): the final approach's factor on the tolerances
-    int polish_sweeps = POLISH_SWEEPS;          // POLISH_SWEEPS (0 .. MAX_SWEEPS, diagnostic): sweeps added in the final approach and the end game
-    double sigma_max_corr = SIGMA_MAX_CORR;     // SIGMA_MAX (0 .. 1, diagnostic): the cap on sigma where the corrector follows
+    bool corr_big = true;        // CORR_BIG=0: the corrector corrects the orthant rows alone and leaves the big cone's products alone
     int test_cap_kp = 0;         // TEST_CAP_KP (test hook): a single design pads its capacitance matrix S as a unit's largest lane would
     int ar_chunks = 0;           // AR_CHUNKS (>= 1; 0: the build's own choice): collectives of a dense row-sharded build
     int ar_overlap = 1;          // AR_OVERLAP: 1 the chunked all-reduce overlapped with the Gram product, 0 the assembled H summed, 2 (diagnostic) the chunked form without shards
-    int seg = 0;                 // SEG (8 .. SEGMAX; 0: from the lattice extent): lattice points per segment of the row evaluation
-    bool share_seeds = true;     // SHARE_SEEDS=0: every lane of a unit builds and reads its own seed tables
     int cgrp = 4;                // CGRP (1 .. CGRP): chunks per block of the moment kernels
-    bool hetero = true;          // HETERO=0: round 3's rule, a unit holds designs of exactly one shape
-    bool hetero_orders = true;   // HETERO_ORDERS=0: round 4's rule, one order per unit
-    bool hetero_dense = true;    // HETERO_DENSE=0: the exact shape on the dense path
     int ddform = -1;             // DDFORM: -1 unset (opts.dd_form decides), 0 "dd" the double-double form, 1 any other value the capacitance form
-    int dd_passes = 0;           // DD_PASSES (1 .. 8; 0: 3 in the capacitance form, 2 in the double-double one): refinement passes of the extended-precision solve
-    bool dd_lanes = true;        // DD_LANES=0: designs on the extended-precision path one at a time instead of lock-step units
     bool dd_blockinv = true;     // DD_BLOCKINV=0: substitution instead of the inverses of the dd factor's diagonal blocks
     bool hsolve = true;          // HSOLVE=0: the preconditioner as two triangular GEMVs instead of one pass over M
-    bool fuse = true;            // FUSE=0: the separate kernels of round 4 instead of the fused launches of round 5
-    bool graph = false;          // GRAPH=1: single designs replay the iteration from launch graphs
+    bool fuse = true;            // FUSE=0: folds, residual norm, CG start and step length as launches of their own instead of inside their neighbours
     bool speculate = true;       // SPECULATE=0: the head of the next iteration goes out after the host's verdicts, not before
     bool trace_host = false;     // TRACE_HOST (set): report where the host thread spends the solve
-    bool test_lose_flag = false; // TEST_LOSE_FLAG (set, test hook of chol.hip): no launch graphs
-    long max_lanes = 0;          // MAX_LANES (>= 1; 0: from memory and occupancy): lanes per unit
-    int chunk = 64;              // CHUNK (4 .. CHK): longest run of frequencies between two exact sincos seeds
     int fold = -1;               // FOLD: -1 unset (fold unless the extended-precision solve is on), 0 / 1 every frequency on its own / +w and -w paired
+    int chol_split = -1;         // CHOL_SPLIT: the factorisation's form (chol_inv_launch); -1 unset: its own choice per call
+    bool poison = false;         // POISON=1 (test switch): NaN in the factorisation's diagonal-block images before every build
+    int test_lose_flag = -1;     // TEST_LOSE_FLAG=k (test hook of chol.hip): the diagonal block of panel step k does not raise its flag; -1 none
 };
 static SolveSwitches read_switches() {
     SolveSwitches w;
     auto flag = [](const char* name, bool& v) { if (const char* ev = std::getenv(name)) v = std::atoi(ev) != 0; };
-    auto clamped = [](const char* name, int& v, int lo, int hi) { if (const char* ev = std::getenv(name)) v = std::max(lo, std::min(hi, std::atoi(ev))); };
-    flag("MBFIR_CORRECTOR", w.corrector); flag("MBFIR_CORR_PLAIN", w.corr_plain); flag("MBFIR_CORR_GUARD", w.corr_guard); flag("MBFIR_CORR_BIG", w.corr_big);
-    flag("MBFIR_SHARE_SEEDS", w.share_seeds); flag("MBFIR_HETERO", w.hetero); flag("MBFIR_HETERO_ORDERS", w.hetero_orders); flag("MBFIR_HETERO_DENSE", w.hetero_dense);
-    flag("MBFIR_DD_LANES", w.dd_lanes); flag("MBFIR_DD_BLOCKINV", w.dd_blockinv); flag("MBFIR_HSOLVE", w.hsolve); flag("MBFIR_FUSE", w.fuse);
-    flag("MBFIR_GRAPH", w.graph); flag("MBFIR_SPECULATE", w.speculate);
-    clamped("MBFIR_POLISH_SWEEPS", w.polish_sweeps, 0, MAX_SWEEPS); clamped("MBFIR_SEG", w.seg, 8, SEGMAX); clamped("MBFIR_CGRP", w.cgrp, 1, CGRP);
-    clamped("MBFIR_DD_PASSES", w.dd_passes, 1, 8); clamped("MBFIR_CHUNK", w.chunk, 4, CHK);
-    if (const char* ev = std::getenv("MBFIR_POLISH_APPROACH")) w.polish_approach = std::max(1.0, std::atof(ev));
-    if (const char* ev = std::getenv("MBFIR_SIGMA_MAX")) w.sigma_max_corr = std::max(0.0, std::min(1.0, std::atof(ev)));
-    if (const char* ev = std::getenv("MBFIR_TEST_CAP_KP")) w.test_cap_kp = std::atoi(ev);
+    auto number = [](const char* name, int& v) { if (const char* ev = std::getenv(name)) v = std::atoi(ev); };
+    flag("MBFIR_CORRECTOR", w.corrector); flag("MBFIR_CORR_BIG", w.corr_big); flag("MBFIR_DD_BLOCKINV", w.dd_blockinv);
+    flag("MBFIR_HSOLVE", w.hsolve); flag("MBFIR_FUSE", w.fuse); flag("MBFIR_SPECULATE", w.speculate); flag("MBFIR_POISON", w.poison);
+    number("MBFIR_TEST_CAP_KP", w.test_cap_kp); number("MBFIR_AR_OVERLAP", w.ar_overlap);
+    number("MBFIR_CHOL_SPLIT", w.chol_split); number("MBFIR_TEST_LOSE_FLAG", w.test_lose_flag);
+    if (const char* ev = std::getenv("MBFIR_CGRP")) w.cgrp = std::max(1, std::min(CGRP, std::atoi(ev)));
     if (const char* ev = std::getenv("MBFIR_AR_CHUNKS")) w.ar_chunks = std::max(1, std::atoi(ev));
-    if (const char* ev = std::getenv("MBFIR_AR_OVERLAP")) w.ar_overlap = std::atoi(ev);
     if (const char* ev = std::getenv("MBFIR_DDFORM")) w.ddform = std::strcmp(ev, "dd") != 0 ? 1 : 0;
-    if (const char* ev = std::getenv("MBFIR_MAX_LANES")) w.max_lanes = std::max(1L, std::atol(ev));      // (experiments: tools/sweep_lanes.sh)
     if (const char* ev = std::getenv("MBFIR_FOLD")) w.fold = std::atoi(ev) != 0;
     w.trace_host = std::getenv("MBFIR_TRACE_HOST") != nullptr;
-    w.test_lose_flag = std::getenv("MBFIR_TEST_LOSE_FLAG") != nullptr;
     return w;
 }
 
@@ -2140,12 +2121,14 @@ struct LatticeInfo {
     std::vector<int> fold_pos, fold_neg;
     std::vector<double> wf;
 };
-// chunk_len: longest run of frequencies one recurrence covers between two exact sincos seeds (<= CHK).
+// CHUNK_LEN: longest run of frequencies one recurrence covers between two exact sincos seeds.
 // fold: pair the frequencies +w / -w of a grid that is symmetric about 0 (linspace(-pi, pi, m) is, to 2 ulp): the two
 // share cos(w t) and differ in the sign of sin(w t), so every recurrence of the lattice kernels serves both -- the
 // moment sums take p(+w) + p(-w) on the cosine and p(+w) - p(-w) on the sine, a row response is C + S at +w and C - S
 // at -w.  A frequency without a partner (band edges, one-sided grids) is an entry with one side empty.
-static LatticeInfo analyse_lattice(const TrigProgram& Q, bool fold, int chunk_len) {
+constexpr int CHUNK_LEN = 64;
+static_assert(CHUNK_LEN <= CHK, "a chunk holds at most CHK frequencies");
+static LatticeInfo analyse_lattice(const TrigProgram& Q, bool fold) {
     LatticeInfo L;
     const int Nt = Q.Nt, Mf = Q.Mf;
     if (Nt <= 0 || Mf <= 0) return L;
@@ -2202,11 +2185,11 @@ static LatticeInfo analyse_lattice(const TrigProgram& Q, bool fold, int chunk_le
     }
     const int Nf = int(L.wf.size());
     const std::vector<double>& W = L.wf;
-    // Longest run from i (at most chunk_len points) that lies on the straight line through its END POINTS to within
+    // Longest run from i (at most CHUNK_LEN points) that lies on the straight line through its END POINTS to within
     // `tol`: a linspace run passes at full length (every point is within half an ulp of the exact line), where a step
     // estimated from the first two points drifts out of tolerance after ~30 points.  Shrink by halves on failure.
     for (int i = 0; i < Nf;) {
-        int cnt = std::min(chunk_len, Nf - i);
+        int cnt = std::min(CHUNK_LEN, Nf - i);
         double dwf = 0.0;
         for (;;) {
             dwf = cnt > 1 ? (W[i + cnt - 1] - W[i]) / (cnt - 1) : 0.0;
@@ -2314,7 +2297,7 @@ static std::shared_ptr<LanePrep> lane_prep(const TrigProgram& Q, const SolveOpts
     pr->fold = fold; pr->dense = dense;
     index_structures(Q, *pr);
     pr->rep = replicated_rows(Q);
-    if (!dense) pr->Lt = analyse_lattice(Q, sw.fold < 0 ? fold : sw.fold != 0, sw.chunk);
+    if (!dense) pr->Lt = analyse_lattice(Q, sw.fold < 0 ? fold : sw.fold != 0);
     Q.prep = pr;
     return pr;
 }
@@ -2330,7 +2313,7 @@ struct UnitPlan {
 // rule and the end game, the infeasibility tests, the reduced-accuracy candidate, max_iter and the numerical wall.  hs: the lane's
 // scalar row.  Updates the lane's host state (a lane that finishes is no longer live); returns whether the lane has a new best
 // iterate (xbest is then to take its x / tau -- also on a lane that this very iteration retires).
-static bool lane_verdict(LaneHost& L, const double* hs, const SolveOpts& o, int it, const SolveSwitches& sw) {
+static bool lane_verdict(LaneHost& L, const double* hs, const SolveOpts& o, int it) {
     SolveInfo& info = L.info;
     if (it > 0 && L.dd_k == 0) {                      // (iterations on the extended-precision path keep the count)
         // refinement-sweep controller (mirrors oracle/conic_ipm.py next_sweeps): the norms were
@@ -2368,8 +2351,8 @@ static bool lane_verdict(LaneHost& L, const double* hs, const SolveOpts& o, int 
     }
     if (L.first_opt >= 0 && it >= L.first_opt + POLISH_MAX) return finish(ST_OPTIMAL);      // (whether or not this iterate still meets the rule)
     {   // what this iteration's solves run: the controller's count, POLISH_SWEEPS more in the final approach and the end game
-        const bool approach = finite && (hs[S_GAP] <= sw.polish_approach * o.abstol || hs[S_RELGAP] <= sw.polish_approach * o.reltol);
-        L.nsweep = std::min(MAX_SWEEPS, L.nsweep_ctl + ((approach || L.first_opt >= 0) ? sw.polish_sweeps : 0));
+        const bool approach = finite && (hs[S_GAP] <= POLISH_APPROACH * o.abstol || hs[S_RELGAP] <= POLISH_APPROACH * o.reltol);
+        L.nsweep = std::min(MAX_SWEEPS, L.nsweep_ctl + ((approach || L.first_opt >= 0) ? POLISH_SWEEPS : 0));
     }
     if (!finite) return finish(ST_NUMERICAL);
     const bool collapsed = hs[S_KAPPA] / hs[S_TAU] >= 1e6;
@@ -2480,7 +2463,7 @@ struct Solver::Impl {
     // inverse Cholesky factor Ms (kp x kp, kp = k rounded up to 64, at most CAP_KMAX), W1s / flagS the workspace and pivot
     // counter of that factorisation, capw the right-hand side of the S solve
     bool cap_form = true;
-    int dd_passes = 2;           // refinement passes on the augmented system around the extended-precision solve (MBFIR_DD_PASSES, <= 8: the norm slots)
+    int dd_passes = 2;           // refinement passes on the augmented system around the extended-precision solve (<= 8: the norm slots)
     double *capYt = nullptr, *capZt = nullptr, *capS = nullptr, *capMs = nullptr, *capW1 = nullptr, *capw = nullptr, *capPart = nullptr;
     int* capflag = nullptr;
     int dd_k = 0;                 // strong directions of the current iteration (0: plain double-precision solve)
@@ -3031,7 +3014,7 @@ struct Solver::Impl {
             const int kp = dd_unit ? dd_kp : std::max(int(round_up(ddk, 64)), sw.test_cap_kp);
             const size_t lb = dd_unit ? lane_bytes : 0;
             const int* mdd = mask_row(ROW_DD);                // (one design: no masks)
-            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, nullptr, nlanes, lb, P.mask);
+            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, sw.chol_split, sw.poison, nullptr, c0, nullptr, nlanes, lb, P.mask);
             P.mask = mdd;
             hipLaunchKernelGGL(k_dd_rows, lane_grid(dim3(kp), nlanes), dim3(256), 0, st, P, D, P.np, dd_unit ? -1 : ddk);      // (one design: rows ddk .. kp-1 zero padding)
             P.mask = live_mask;
@@ -3041,7 +3024,7 @@ struct Solver::Impl {
             if (b1) hipEventRecord(b1, st);
             // Yt and Zt: kp x np x np / 2 multiply-adds each (triangular M); S: kp x kp x np / 2 (lower tiles)
             cap_flop_sum += 2.0 * (double(kp) * P.np * P.np + 0.5 * double(kp) * kp * P.np);
-            chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, nullptr, nullptr, c1, nlanes, lb, mdd);
+            chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, sw.chol_split, sw.poison, nullptr, nullptr, c1, nlanes, lb, mdd);
             cap_flag_add_launch(flag, capflag, st, nlanes, lb, mdd);      // pivots replaced in either factorisation count (oracle: chol_fixes += nfs)
         } else if (ddk > 0) {
             if (c0) hipEventRecord(c0, st);
@@ -3051,21 +3034,9 @@ struct Solver::Impl {
             if (c1) hipEventRecord(c1, st);
         } else {
             // (with the one-pass M'(M b) nobody reads the transpose: it is not written)
-            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, nullptr, c0, c1, nlanes, lane_bytes, P.mask);
+            chol_launch_count += chol_inv_launch(H, M, fused_hsolve ? nullptr : Mt, W1, P.np, flag, st, sw.chol_split, sw.poison, nullptr, c0, c1, nlanes, lane_bytes, P.mask);
         }
     }
-    // events are recorded as (gram begin, gram end, chol begin, chol end) per build_H: the builds of evpool[lo, hi) added to
-    // gram_ms, chol_ms with the given sign; returns their number
-    int add_build_times(size_t lo, size_t hi, double sign, double& gram_ms, double& chol_ms) {
-        int builds = 0;
-        for (size_t i = lo; i + 3 < hi; i += 4, ++builds) {
-            float a = 0, b = 0;
-            if (hipEventElapsedTime(&a, evpool[i], evpool[i + 1]) == hipSuccess) gram_ms += sign * a;
-            if (hipEventElapsedTime(&b, evpool[i + 2], evpool[i + 3]) == hipSuccess) chol_ms += sign * b;
-        }
-        return builds;
-    }
-
     // ---- the stages of Solver::solve_lanes ----------------------------------------------------------------------------------
     // Lane preparation: every lane's program (its row shard when sharded), the WHOLE program's norms, index structures, lattice.
     void prepare_lanes(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, std::vector<LaneHost>& LH) {
@@ -3135,11 +3106,10 @@ struct Solver::Impl {
             Nt_max = std::max(Nt_max, Qb.Nt); nq3_max = std::max(nq3_max, Qb.nq3); big_max = std::max(big_max, Qb.big);
             D1_max = std::max(D1_max, Lb.D1); n_max = std::max(n_max, Qb.n);
         }
-        auto seg_of = [this](int D1) { return sw.seg > 0 ? sw.seg : std::min(SEGMAX, std::max(64, int(round_up(cdiv(std::max(D1, 1), 16), 8)))); };
+        auto seg_of = [](int D1) { return std::min(SEGMAX, std::max(64, int(round_up(cdiv(std::max(D1, 1), 16), 8)))); };
         // what the per-lane dimensions do not cover: different ORDERS on the dense path (the row stride of A1 follows the order).
         // Different band edges are fine there too since round 5: every lane runs its own Gram plan and folds its own split partials.
         if (orders && (!Lt.ok || o.dense_trig)) throw ShapeError("lock-step batch: lanes differ in order (dense path)");
-        if (!sw.hetero && hetero) throw ShapeError("lock-step batch: lanes differ in shape (MBFIR_HETERO=0)");
         // ---- sizes -----------------------------------------------------------------------------
         UnitPlan U;
         const int R = R_max, Nt = Nt_max, Ne = Q.Ne, N = Nt_max + Q.Ne, Mf = Mf_max;
@@ -3162,7 +3132,7 @@ struct Solver::Impl {
         if (Lt.ok) for (int b = 0; b < nlanes; ++b) P.useg = std::max(P.useg, cdiv(LH[b].Lt.D1, seg_of(LH[b].Lt.D1)));      // (launches: the most segments any lane has)
         P.nchunk = int(nchunk_max); P.nfold = int(nfold_max);
         P.seeds_shared = 0;
-        if (nlanes > 1 && Lt.ok && sw.share_seeds) {         // sweeps over Peak / ripple keep the grid: one seed table serves the unit
+        if (nlanes > 1 && Lt.ok) {         // sweeps over Peak / ripple keep the grid: one seed table serves the unit
             bool same = true;
             for (int b = 1; b < nlanes && same; ++b) {
                 const LatticeInfo& Lb = LH[b].Lt;
@@ -3212,7 +3182,7 @@ struct Solver::Impl {
         dd_kp = 0;
         // refinement passes around the extended-precision solve: two for the double-double form, THREE for the capacitance form (with
         // two, a design of BASELINE config 3's batch lost its iterate near the end: DESIGN.md section 5)
-        dd_passes = sw.dd_passes > 0 ? sw.dd_passes : cap_form ? 3 : 2;
+        dd_passes = cap_form ? 3 : 2;
         fused_hsolve = hsolve_fused_ok(P.np, 2) && sw.hsolve;
         return U;
     }
@@ -3348,7 +3318,7 @@ struct Solver::Impl {
         for (int b = 0; b < nlanes; ++b) {
             double* q = sc0.data() + (size_t)b * S_COUNT;
             q[S_NRMH] = LH[b].nrm_h; q[S_NRMC] = LH[b].nrm_c; q[S_DEG] = LH[b].degree; q[S_TAU] = 1.0; q[S_KAPPA] = 1.0;
-            q[S_SIGMAX] = (sw.corrector && LH[b].Q->l > 0 && LH[b].Q->big == 0) ? sw.sigma_max_corr : SIGMA_MAX;      // (not with a big cone: oracle/conic_ipm.py)
+            q[S_SIGMAX] = (sw.corrector && LH[b].Q->l > 0 && LH[b].Q->big == 0) ? SIGMA_MAX_CORR : SIGMA_MAX;      // (not with a big cone: oracle/conic_ipm.py)
             MBFIR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(Sc) + (size_t)b * lane_bytes, q, sizeof(double) * S_COUNT, hipMemcpyHostToDevice, st));
         }
     }
@@ -3511,11 +3481,11 @@ struct Solver::Impl {
         hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz);
         if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, ds, dz, Sc, kbz, scratch, corr_cones, corr_ddm);
         // the Cholesky solve and its residual norm (S_RNC), no sweeps (lanes on the extended-precision path: their usual passes)
-        solve_modes<1>(dd_any, pl_any, kbx, kbz, kx, kz, kg, S_RNC, sw.corr_plain ? 0 : nsweep);
+        solve_modes<1>(dd_any, pl_any, kbx, kbz, kx, kz, kg, S_RNC, 0);
         hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
         const int ndC = dots(kx, kz, 3);
         const int nsC = dir_post(kx, kz, kg, kds, kdz, 3, ndC);
-        scal_step(sw.corr_guard ? 3 : 4, nsC, true);
+        scal_step(3, nsC, true);
         hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z);
     }
     // The host's verdicts on the iterate in hostSc; lanes with a new best iterate get xbest = x / tau.  Returns whether any lane goes on.
@@ -3537,7 +3507,7 @@ struct Solver::Impl {
                         L.dd_k > 0 ? [&] { char bf[200]; std::snprintf(bf, sizeof(bf), " | k %d refinement norms %.2e -> %.2e -> %.2e , %.2e -> %.2e -> %.2e", L.dd_k,
                                        hs[S_RNA], hs[S_RNA + 1], dd_passes > 2 ? hs[S_RNA + 2] : 0.0, hs[S_RNB], hs[S_RNB + 1], dd_passes > 2 ? hs[S_RNB + 2] : 0.0);
                                        return std::string(bf); }().c_str() : "");
-            if (lane_verdict(L, hs, o, it, sw)) {
+            if (lane_verdict(L, hs, o, it)) {
                 hostMask[ROW_BEST * MAX_LANES + b] = 1;
                 any_best = true;
             }
@@ -3556,55 +3526,6 @@ struct Solver::Impl {
             P.mask = mask_row(0);
         }
         return any_live;
-    }
-    // ---- launch graphs (round 4, opt-in: MBFIR_GRAPH=1; single, unsharded designs without the extended-precision path; DESIGN.md
-    // section 5): the body of an iteration and the next iterate's residuals, captured once per refinement-sweep count and replayed
-    // with one hipGraphLaunch.  A graph holds its event pairs evpool[ev_lo, ev_hi) and what one replay adds to the solve's counters.
-    struct IterGraph { hipGraphExec_t exec = nullptr; size_t ev_lo = 0, ev_hi = 0; long chol_launches = 0, n_gv = 0, n_gtv = 0; };
-    std::map<int, IterGraph> graphs;         // per refinement-sweep count
-    const IterGraph* last_graph = nullptr;   // the replay whose phase timings are still to be read
-    double graph_ms_gram = 0, graph_ms_chol = 0;
-    int graph_builds = 0;
-    // replay the iteration of `nsweep` sweeps (captured on first use); false: this runtime does not capture the sequence
-    bool replay_graph(std::vector<LaneHost>& LH, const SolveOpts& o, int nsweep, bool use_corr) {
-        auto g = graphs.find(nsweep);
-        if (g == graphs.end()) {
-            IterGraph ig;
-            ig.ev_lo = evused;
-            const long chol0 = chol_launch_count, gv0 = n_gv, gtv0 = n_gtv;
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed);
-            if (e == hipSuccess) {
-                launch_iteration(LH, o, false, nsweep, use_corr);
-                launch_residuals();
-                e = hipStreamEndCapture(st, &graph);
-            }
-            if (e == hipSuccess) e = hipGraphInstantiate(&ig.exec, graph, nullptr, nullptr, 0);
-            if (graph) hipGraphDestroy(graph);
-            ig.ev_hi = evused;
-            ig.chol_launches = chol_launch_count - chol0; ig.n_gv = n_gv - gv0; ig.n_gtv = n_gtv - gtv0;
-            chol_launch_count = chol0; n_gv = gv0; n_gtv = gtv0;       // (counted per replay below; a capture runs nothing)
-            if (e != hipSuccess || !ig.exec) {
-                (void)hipGetLastError();
-                evused = ig.ev_lo;
-                return false;
-            }
-            g = graphs.emplace(nsweep, ig).first;
-        }
-        MBFIR_HIP(hipGraphLaunch(g->second.exec, st));
-        chol_launch_count += g->second.chol_launches; n_gv += g->second.n_gv; n_gtv += g->second.n_gtv;
-        last_graph = &g->second;
-        return true;
-    }
-    void drop_graphs() {
-        for (auto& g : graphs) hipGraphExecDestroy(g.second.exec);
-        graphs.clear(); last_graph = nullptr;
-        graph_ms_gram = graph_ms_chol = 0; graph_builds = 0;
-    }
-    // after the wait: the phase timings of the replay just finished
-    void read_graph_times() {
-        if (last_graph && timing) graph_builds += add_build_times(last_graph->ev_lo, last_graph->ev_hi, 1.0, graph_ms_gram, graph_ms_chol);
-        last_graph = nullptr;
     }
     // Finish: every lane's answer (the best iterate that met the stopping rule, a reduced-accuracy candidate, or x / tau) and report
     void finish_lanes(std::vector<LaneHost>& LH, const SolveOpts& o, std::vector<std::vector<double>>& xouts, std::vector<SolveInfo>& infos,
@@ -3638,14 +3559,14 @@ struct Solver::Impl {
         }
         MBFIR_HIP(hipStreamSynchronize(st));
         const double t_end = now_ms();
-        // every event pair of the pool once; a graph's pairs were read after every replay: its single reading gives way to those
+        // the event pool holds (gram begin, gram end, chol begin, chol end) per build_H
         double ms_gram = 0, ms_chol = 0;
-        int builds = add_build_times(0, evused, 1.0, ms_gram, ms_chol);
-        if (!graphs.empty()) {
-            for (auto& g : graphs) builds -= add_build_times(g.second.ev_lo, g.second.ev_hi, -1.0, ms_gram, ms_chol);
-            ms_gram += graph_ms_gram; ms_chol += graph_ms_chol; builds += graph_builds;
+        int builds = 0;
+        for (size_t i = 0; i + 3 < evused; i += 4, ++builds) {
+            float a = 0, b = 0;
+            if (hipEventElapsedTime(&a, evpool[i], evpool[i + 1]) == hipSuccess) ms_gram += a;
+            if (hipEventElapsedTime(&b, evpool[i + 2], evpool[i + 3]) == hipSuccess) ms_chol += b;
         }
-        drop_graphs();
         double ms_cap = 0;
         for (size_t i = 0; i + 1 < capev_used; i += 2) { float t = 0; hipEventElapsedTime(&t, capev[i], capev[i + 1]); ms_cap += t; }
         const int nw = P.quad ? 3 : 1;
@@ -3772,18 +3693,11 @@ std::vector<long> Solver::shape_key(const TrigProgram& Q, const SolveOpts& o) {
     // (units on the extended-precision path: the split of the capacitance products over K follows np -- lanes of one np only)
     if (o.ddkkt_theta > 0) bucket = round_up(Q.N(), 64);
     std::vector<long> key{long(Q.which), bucket, long(Q.Ne), long(Q.nq3 > 0), long(Q.big > 0), long(Q.quad), long(Lt.ok), tbits};
-    // ... and, where the per-lane dimensions of a heterogeneous unit do not reach (dense path; MBFIR_HETERO=0:
-    // round 3's rule everywhere), the exact shape: grid, rows, chunks
-    // (round 5: on the dense path the ORDER stays part of the key -- A1's row stride follows it --, the band edges no longer do)
-    const bool dense = !Lt.ok || o.dense_trig;
-    const bool exact = !sw.hetero || (dense && !sw.hetero_dense);
-    if (exact || dense || !sw.hetero_orders) {                   // (round 4's rule: one order per unit)
+    // ... and on the dense path, where the per-lane dimensions of a heterogeneous unit do not reach, the ORDER: A1's row stride
+    // follows it (the band edges may differ there too)
+    if (!Lt.ok || o.dense_trig) {
         const long ord[] = {long(Q.n), long(Q.Nt), long(Q.nq3), long(Q.big), long(pr->c_rows.size()), long(Lt.D1)};
         key.insert(key.end(), std::begin(ord), std::end(ord));
-    }
-    if (exact) {
-        const long more[] = {long(Q.Mf), long(Q.R), long(Q.l), long(pr->f_rows.size()), long(pr->yrows.size()), long(Lt.ch_start.size()), long(Lt.wf.size())};
-        key.insert(key.end(), std::begin(more), std::end(more));
     }
     return key;
 }
@@ -3792,7 +3706,7 @@ void Solver::test_fold(const double* w, int Mf, int fold, long* out) {
     Q.Nt = 1; Q.Mf = Mf; Q.w.assign(w, w + Mf);
     Q.col_kind = {0}; Q.col_tau = {0.0}; Q.col_scale = {1.0}; Q.pcol = {0}; Q.psign = {0.0};
     const SolveSwitches sw = read_switches();
-    const LatticeInfo L = analyse_lattice(Q, sw.fold < 0 ? fold != 0 : sw.fold != 0, sw.chunk);
+    const LatticeInfo L = analyse_lattice(Q, sw.fold < 0 ? fold != 0 : sw.fold != 0);
     long pairs = 0, longest = 0, bad = 0;
     std::vector<int> seen(Mf, 0);
     double wmax = 1.0;
@@ -3816,17 +3730,17 @@ int Solver::max_lanes(const TrigProgram& Q, const SolveOpts& o) {
     // lock-step batches exist on the lattice path only; the extended-precision KKT solve (on by default for
     // fir_qp_cvx) and row-sharded solves run one design at a time
     if (o.shard_size > 1) return 1;
-    // (round 5: the extended-precision solve takes lock-step units too, in its capacitance form -- every lane switches to it when
-    //  ITS strong set is non-empty, as its single solve does; MBFIR_DD_LANES=0: one design at a time as before)
+    // (the extended-precision solve takes lock-step units in its capacitance form -- every lane switches to it when ITS strong set
+    //  is non-empty, as its single solve does)
     const SolveSwitches sw = read_switches();
-    const bool dd_lanes = o.ddkkt_theta > 0 && o.dd_form == 0 && sw.ddform != 0 && sw.dd_lanes;
+    const bool dd_lanes = o.ddkkt_theta > 0 && o.dd_form == 0 && sw.ddform != 0;
     if (o.ddkkt_theta > 0 && !dd_lanes) return 1;
     long np = round_up(Q.N(), 64);
     const bool lattice = !o.dense_trig && lane_prep(Q, o, sw)->Lt.ok;
     if (lattice) {        // (lattice path: designs of one size bucket share units -- shape_key -- and a unit
         long bucket = 64;                                     //  is as large as its largest lane)
         while (bucket < np) bucket *= 2;
-        if (sw.hetero_orders && sw.hetero) np = bucket;
+        np = bucket;
     }
     long cap = std::min<long>(32, 16384 / np);
     if (!lattice) {
@@ -3837,7 +3751,6 @@ int Solver::max_lanes(const TrigProgram& Q, const SolveOpts& o) {
         cap = std::min<long>(cap, std::max<long>(1, long(2.0e9 / per_lane)));
     }
     if (o.ddkkt_theta > 0) cap = std::min<long>(cap, 16);                               // (~100 MB of strong rows and capacitance matrices per lane)
-    if (sw.max_lanes > 0) cap = sw.max_lanes;
     return int(std::max<long>(1, std::min<long>(MAX_LANES, cap)));
 }
 
@@ -3861,6 +3774,7 @@ void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveO
     if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
     S.nlanes = nlanes;
     S.sw = read_switches();
+    chol_set_lose_step(S.sw.test_lose_flag, S.st);
     std::vector<LaneHost> LH(nlanes);
     S.prepare_lanes(Qs, o, LH);
     const UnitPlan U = S.plan_unit(LH, o);
@@ -3874,7 +3788,6 @@ void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveO
     S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
     S.timing = o.timing;
     S.chol_launch_count = 0; S.dd_epoch = 0;
-    S.drop_graphs();
     S.initial_point(o.refine);
 
     const bool sharded = S.shard_size > 1;
@@ -3885,13 +3798,12 @@ void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveO
     // synchronisation per iteration (a stream whose host thread issues most of the time is launch-bound, not GPU-bound)
     const bool trace_host = S.sw.trace_host;
     double host_issue_ms = 0, host_wait_ms = 0, t_issue0 = trace_host ? now_ms() : 0.0;
-    bool use_graph = nlanes == 1 && !U.use_dd && !sharded && !S.sw.test_lose_flag && S.sw.graph;      // (see Impl::IterGraph)
     S.launch_residuals();
     // The head of the NEXT iteration goes to the stream BEFORE the host has looked at this iterate's scalars (round 5, DESIGN.md
     // section 5): the host waits on an event behind the scalars' copy while the GPU works on the head.  A lane the host then retires
     // has had one scaling and factorisation too many, which touch nothing the result is read from.  Not with the extended-precision
-    // solve (its strong-set count needs the host mid-head), row-sharded solves and launch graphs.
-    const bool speculate = !U.use_dd && !sharded && !use_graph && S.sw.speculate;
+    // solve (its strong-set count needs the host mid-head) and row-sharded solves.
+    const bool speculate = !U.use_dd && !sharded && S.sw.speculate;
     int it = 0;
     for (it = 0; it <= o.max_iter; ++it) {
         MBFIR_HIP(hipMemcpy2DAsync(S.hostSc, sizeof(double) * S_COUNT, S.Sc, S.lane_bytes, sizeof(double) * S_COUNT, nlanes, hipMemcpyDeviceToHost, S.st));
@@ -3904,14 +3816,11 @@ void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveO
         if (head_out) MBFIR_HIP(hipEventSynchronize(S.ev0));
         else MBFIR_HIP(hipStreamSynchronize(S.st));
         if (trace_host) { const double t1 = now_ms(); host_issue_ms += t_sync0 - t_issue0; host_wait_ms += t1 - t_sync0; t_issue0 = t1; }
-        S.read_graph_times();
         if (!S.judge_lanes(LH, o, it)) break;
         int nsweep_max = 0;
         for (int b = 0; b < nlanes; ++b)
             if (LH[b].live) nsweep_max = std::max(nsweep_max, LH[b].nsweep);
         S.push_masks(LH);                                     // (a unit with opts.ddkkt pushes them again once the head knows the lanes' modes)
-        use_graph = use_graph && S.replay_graph(LH, o, nsweep_max, use_corr);       // (false: this runtime does not capture the sequence)
-        if (use_graph) continue;
         S.launch_iteration(LH, o, head_out, nsweep_max, use_corr);
         S.launch_residuals();
     }
@@ -3984,6 +3893,8 @@ void Solver::test_gram(int m, int nt, int nw, const double* A, const double* d, 
 void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
+    const SolveSwitches sw = read_switches();
+    chol_set_lose_step(sw.test_lose_flag, S.st);
     const size_t np = round_up(n, 64);
     std::vector<double> Hp(np * np, 0.0);
     for (size_t i = 0; i < np; ++i) Hp[i * np + i] = 1.0;
@@ -3999,11 +3910,11 @@ void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
         std::vector<double> H2(Hp);
         for (size_t i = 0; i < np; ++i) H2[i * np + i] = 2.0 * H2[i * np + i] + 1.0;
         MBFIR_HIP(hipMemcpyAsync(dH.p, H2.data(), np * np * 8, hipMemcpyHostToDevice, S.st));
-        chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st, nullptr);
+        chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st, sw.chol_split, sw.poison);
         MBFIR_HIP(hipStreamSynchronize(S.st));
     }
     MBFIR_HIP(hipMemcpyAsync(dH.p, Hp.data(), np * np * 8, hipMemcpyHostToDevice, S.st));
-    chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st,
+    chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st, sw.chol_split, sw.poison,
                     dL.as<double>());
     MBFIR_HIP(hipMemcpy2DAsync(out_l, (size_t)n * 8, dL.p, np * 8, (size_t)n * 8, n, hipMemcpyDeviceToHost, S.st));
     MBFIR_HIP(hipMemcpy2DAsync(out_m, (size_t)n * 8, dM.p, np * 8, (size_t)n * 8, n, hipMemcpyDeviceToHost, S.st));
@@ -4017,10 +3928,13 @@ void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
             if (Mh[i * np + j] != Mth[j * np + i]) throw HipError("test_chol: the stored transpose differs from the inverse factor");
 }
 
-// nlanes matrices factorised together, lanes lane_bytes apart in ONE arena like a lock-step batch's (H | M | Mt | W1 | flag)
+// nlanes matrices factorised together, lanes lane_bytes apart in ONE arena like a lock-step batch's (H | M | Mt | W1 | flag);
+// form >= 0 forces the factorisation's form (otherwise MBFIR_CHOL_SPLIT, or its own choice)
 void Solver::test_chol_lanes(int n, int nlanes, int form, const int* mask, const double* Hh, double* out_l, double* out_m) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
+    const SolveSwitches sw = read_switches();
+    chol_set_lose_step(sw.test_lose_flag, S.st);
     if (nlanes < 1 || nlanes > MAX_LANES) throw HipError("test_chol_lanes: bad lane count");
     const size_t np = round_up(n, 64);
     const size_t lane_doubles = 4 * np * np + 80 * np + 64, lane_bytes = lane_doubles * 8;
@@ -4030,9 +3944,6 @@ void Solver::test_chol_lanes(int n, int nlanes, int form, const int* mask, const
     double *dH = base, *dM = base + np * np, *dMt = dM + np * np, *dW = dMt + np * np;
     int* df = reinterpret_cast<int*>(dW + np * np + 70 * np);
     if (mask) MBFIR_HIP(hipMemcpyAsync(dmask.p, mask, sizeof(int) * nlanes, hipMemcpyHostToDevice, S.st));
-    const char* old = std::getenv("MBFIR_CHOL_SPLIT");
-    const std::string keep = old ? old : "";
-    if (form >= 0) setenv("MBFIR_CHOL_SPLIT", std::to_string(form).c_str(), 1);
     std::vector<double> Hp(np * np);
     // a different matrix first (later builds find the previous build's numbers in the buffers), then the ones asked for
     for (int pass = 0; pass < 2; ++pass) {
@@ -4045,10 +3956,10 @@ void Solver::test_chol_lanes(int n, int nlanes, int form, const int* mask, const
             MBFIR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(dH) + b * lane_bytes, Hp.data(), np * np * 8, hipMemcpyHostToDevice, S.st));
             MBFIR_HIP(hipStreamSynchronize(S.st));
         }
-        chol_inv_launch(dH, dM, dMt, dW, int(np), df, S.st, nullptr, nullptr, nullptr, nlanes, lane_bytes, mask ? dmask.as<int>() : nullptr);
+        chol_inv_launch(dH, dM, dMt, dW, int(np), df, S.st, form >= 0 ? form : sw.chol_split, sw.poison, nullptr, nullptr, nullptr, nlanes, lane_bytes,
+                        mask ? dmask.as<int>() : nullptr);
         MBFIR_HIP(hipStreamSynchronize(S.st));
     }
-    if (form >= 0) { if (old) setenv("MBFIR_CHOL_SPLIT", keep.c_str(), 1); else unsetenv("MBFIR_CHOL_SPLIT"); }
     MBFIR_HIP(hipGetLastError());
     std::vector<int> fl(1);
     for (int b = 0; b < nlanes; ++b) {
@@ -4196,6 +4107,8 @@ __global__ void k_fill_spd(double* H, int np, int n) {
 void Solver::test_time_kernels(int n, int m, int nt, int reps, double* ms_chol, double* ms_gram) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
+    const SolveSwitches sw = read_switches();
+    chol_set_lose_step(sw.test_lose_flag, S.st);
     const size_t np = round_up(n, 64);
     DevBuf dH(np * np * 8), dH0(np * np * 8), dM(np * np * 8), dMt(np * np * 8), dW((np * np + 65 * np) * 8), df(16);
     hipLaunchKernelGGL(k_fill_spd, dim3(cdiv((long)np * np, 256)), dim3(256), 0, S.st, dH0.as<double>(), int(np), n);
@@ -4203,7 +4116,7 @@ void Solver::test_time_kernels(int n, int m, int nt, int reps, double* ms_chol, 
     for (int r = 0; r < reps + 1; ++r) {
         MBFIR_HIP(hipMemcpyAsync(dH.p, dH0.p, np * np * 8, hipMemcpyDeviceToDevice, S.st));
         hipEventRecord(S.ev0, S.st);
-        chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st);
+        chol_inv_launch(dH.as<double>(), dM.as<double>(), dMt.as<double>(), dW.as<double>(), int(np), df.as<int>(), S.st, sw.chol_split, sw.poison);
         hipEventRecord(S.ev1, S.st);
         MBFIR_HIP(hipEventSynchronize(S.ev1));
         hipEventElapsedTime(&ms, S.ev0, S.ev1);

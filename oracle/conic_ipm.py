@@ -712,7 +712,7 @@ def solve(c, G, h, l, nq3=0, big=0, max_iter=200, feastol=1e-8, abstol=1e-10,
         # answers one iteration late: POLISH_SWEEPS more sweeps than it asks for, so that an iterate does not miss the stopping
         # rule by its dual residual when its gap is already there (fuzz seed 55, fir_qprog_phs: dres 5.7e-10 -> 1.7e-8 behind the
         # first iterate that met the rule; a 29-tap fir_qprog_phs: 1.1e-9 -> 9.5e-8 one iteration BEFORE, then the numerical wall).
-        # Measured on the device, one box (tools/gpu_polish_ab2.py): no extra sweeps 305.6 designs/s on the headline batch and 17 of
+        # Measured on the device, one box: no extra sweeps 305.6 designs/s on the headline batch and 17 of
         # 600 fuzz designs retried in extended precision; + 2 from a factor 1000 on: 271.1 and none; + 1 from a factor 30 on: 298.6, none.
         approach = finite and (gap <= POLISH_APPROACH * abstol or relgap <= POLISH_APPROACH * reltol)
         nsweep[0] = min(MAX_SWEEPS, nsweep_ctl + (POLISH_SWEEPS if (approach or first_opt is not None) else 0))

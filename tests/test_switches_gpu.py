@@ -2,13 +2,11 @@
 environment switch (read at solve time), and the switched-off form is the reference for the switched-on one.
 
   MBFIR_FOLD=0         every frequency on its own instead of the +w / -w pairs of the folded lattice kernels
-  MBFIR_SHARE_SEEDS=0  every lane builds and reads its own seed tables
   MBFIR_CHOL_SPLIT     4 (default for lock-step batches): the factorisation in one launch; 1: one launch per panel step with
                        the device flag; 2: the split step as two launches; 0: the fused single-design step
   MBFIR_POISON=1       NaN in the diagonal-block images before every build (a stale read shows deterministically)
   MBFIR_HSOLVE=0       the preconditioner M'(M b) as two triangular GEMVs on M and the stored M' instead of one pass over M
   MBFIR_CGRP=1         one chunk per block in the moment kernel (no interleaved pair)
-  MBFIR_DD_LANES=0     designs with the extended-precision solve (fir_qp_cvx's default) one per stream (rounds 2-4) instead of lock-step units
   MBFIR_FUSE=0         round 4's separate launches: k_freq_fold in front of the moment kernel, k_resid_norm behind k_gt_finish,
                        k_hsolve_fold + k_cg_start behind the one-pass M'(M b), k_scal_step in front of k_update (round 5 fused them
                        into their neighbours; the sums and their order are unchanged)
@@ -113,7 +111,7 @@ def test_lock_step_switches_are_bit_identical():
     published them would carry NaN into the factor (instead of the previous build's plausible numbers), so
     bit-identical taps under the poison show every in-launch hand-off of the image in order, deterministically."""
     base = _batch()
-    for kw in (dict(MBFIR_SHARE_SEEDS=0), dict(MBFIR_CHOL_SPLIT=1), dict(MBFIR_CHOL_SPLIT=2), dict(MBFIR_CHOL_SPLIT=0), dict(MBFIR_POISON=1),
+    for kw in (dict(MBFIR_CHOL_SPLIT=1), dict(MBFIR_CHOL_SPLIT=2), dict(MBFIR_CHOL_SPLIT=0), dict(MBFIR_POISON=1),
                dict(MBFIR_POISON=1, MBFIR_CHOL_SPLIT=1)):
         other = _batch(**kw)
         for (h0, _, i0), (h1, _, i1) in zip(base, other):
@@ -218,48 +216,6 @@ def test_eight_contexts_enter_the_extended_precision_path_at_once():
         one.close()
 
 
-def test_heterogeneous_units_equal_exact_shape_units():
-    """MBFIR_HETERO=0 is round 3's rule (a lock-step unit holds designs of exactly one shape; designs whose band edges differ run one
-    per stream), the default forms heterogeneous units.  Same results either way, bit for bit; the unit sizes
-    differ."""
-    from conftest import c13
-    f, a, d = c13(64)
-    jobs = []
-    for q in range(6):
-        fq = np.asarray(f, float).copy(); fq[0::2] -= 8e-4 * q; fq[1::2] += 8e-4 * q
-        jobs.append(("fir_ap_cvx", (64, list(fq), a, d, 0.1, 1e-3)))
-    out = {}
-    for mode in ("1", "0"):
-        ctx = mbfir.Context(0)
-        try:
-            with env(MBFIR_HETERO=mode):
-                out[mode] = mbfir.solve_batch(jobs, ctxs=[ctx], info=True, opts=mbfir.make_opts(lanes=6))
-        finally:
-            ctx.close()
-    # (a design that only meets the reduced tolerances inside a unit is redone alone -- extended-precision retry -- and reports lanes = 1)
-    assert sum(1 for r in out["1"] if r[2]["lanes"] == 6) >= 4 and max(r[2]["lanes"] for r in out["0"]) < 6
-    for (h1, s1, i1), (h0, s0, i0) in zip(out["1"], out["0"]):
-        assert s1 == s0 and i1["iters"] == i0["iters"] and i1["pcost"] == i0["pcost"] and np.array_equal(h1, h0)
-
-
-@pytest.mark.parametrize("which,args,okw", CASES)
-def test_launch_graphs_replay_the_iteration_bit_for_bit(which, args, okw):
-    """MBFIR_GRAPH=1 (opt-in): the body of an IPM iteration of a single design is captured into a launch graph per refinement-sweep
-    count and replayed (1.01-1.08 x in latency -- the GPU-side launch chain, not the host, bounds one design).
-    Same kernels, same order, same arguments: the results and the iteration count are identical, the phase timings (read from the
-    graph's event-record nodes) are there."""
-    fn = getattr(mbfir, which)
-    opts = mbfir.make_opts(**okw) if okw else None
-    with env(MBFIR_GRAPH=0, MBFIR_SPECULATE=0):          # (the eager path's speculative head of round 5 is one build more; see the test below)
-        h0, s0, i0 = fn(*args, info=True, opts=opts)
-    with env(MBFIR_GRAPH=1):
-        h1, s1, i1 = fn(*args, info=True, opts=opts)
-    assert s0 == s1 == "Solved" and i0["iters"] == i1["iters"] and i0["pcost"] == i1["pcost"] and np.array_equal(h0, h1)
-    assert i1["builds"] == i0["builds"] and i1["ms_chol"] > 0 and i1["chol_launches"] == i0["chol_launches"]
-    assert i1["gv_passes"] == i0["gv_passes"] and i1["gtv_passes"] == i0["gtv_passes"]      # (a replay counts its passes like the eager iteration)
-
-
-
 @pytest.mark.parametrize("which,args,okw", CASES)
 def test_speculative_head_changes_nothing_but_the_build_count(which, args, okw):
     """Round 5: the head of the next iteration (NT scaling, normal matrix, factorisation) is on the stream before the host has read
@@ -313,21 +269,6 @@ def test_fused_launches_change_no_bit_in_a_lock_step_batch():
     assert any(i["lanes"] == 5 for _, _, i in out["1"])
     for (h1, s1, i1), (h0, s0, i0) in zip(out["1"], out["0"]):
         assert s1 == s0 and i1["iters"] == i0["iters"] and i1["pcost"] == i0["pcost"] and np.array_equal(h1, h0)
-
-
-def test_extended_precision_units_against_one_design_per_stream():
-    """MBFIR_DD_LANES=0: the batch front end hands fir_qp_cvx designs (extended-precision solve on) out one per stream as before round 5;
-    the lock-step units give the same results bit for bit."""
-    base = ("fir_qp_cvx", (40, [-0.5, -0.3, -0.1, 0.1, 0.3, 0.5], [0, 0, 1, 1, 0, 0], [0.05, 0.05, 0.05], 5.0, 1e6))
-    jobs = [(base[0], base[1][:3] + ([v * (1 + 0.05 * q) for v in base[1][3]],) + base[1][4:]) for q in range(5)]
-    out = {}
-    for mode in ("0", "1"):
-        with env(MBFIR_DD_LANES=mode):
-            out[mode] = mbfir.solve_batch(jobs, info=True, opts=mbfir.make_opts(lanes=5))
-    assert all(i["lanes"] == 1 for _, _, i in out["0"]) and all(i["lanes"] == 5 for _, _, i in out["1"])
-    assert any(i["dd_iters"] > 0 for _, _, i in out["1"])
-    for (h1, s1, i1), (h0, s0, i0) in zip(out["1"], out["0"]):
-        assert s1 == s0 and i1["iters"] == i0["iters"] and i1["dd_iters"] == i0["dd_iters"] and i1["pcost"] == i0["pcost"] and np.array_equal(h1, h0)
 
 
 @pytest.mark.parametrize("which,args,okw", CASES)        # (the last one, fir_qprog_phs: orthant rows AND the big cone are corrected)

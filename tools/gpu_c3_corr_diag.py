@@ -7,7 +7,7 @@ n, m = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (512, 1638
 f, a, d = mbfir.spec.spec_h1_dualband(n)
 o = mbfir.make_opts(grid_m=m)
 mbfir.fir_qp_cvx(n, f, a, d, 120.0, 1e6, opts=o)
-for tag, env in (("default", {}), ("no guard", {"MBFIR_CORR_GUARD": "0"}), ("refined corrector solve", {"MBFIR_CORR_PLAIN": "0"}), ("corrector off", {"MBFIR_CORRECTOR": "0"})):
+for tag, env in (("default", {}), ("corrector off", {"MBFIR_CORRECTOR": "0"})):
     os.environ.update(env)
     t = time.time(); h, s, i = mbfir.fir_qp_cvx(n, f, a, d, 120.0, 1e6, opts=o, info=True); dt = time.time() - t
     for k in env: os.environ.pop(k)

@@ -10,7 +10,7 @@ for seed in [int(v) for v in sys.argv[1:]]:
     which, args = make_case(seed)
     ho, so, io = getattr(designers, which)(*args, info=True)
     print("seed %d %s n=%d   oracle: %s %d iterations, correctors %s/%s, pcost %.12e" % (seed, which, args[0], so, io["iters"], io.get("correctors_taken"), io.get("correctors"), io["pcost"]))
-    for tag, env in (("default", {}), ("no guard", {"MBFIR_CORR_GUARD": "0"}), ("refined", {"MBFIR_CORR_PLAIN": "0"}), ("off", {"MBFIR_CORRECTOR": "0"})):
+    for tag, env in (("default", {}), ("off", {"MBFIR_CORRECTOR": "0"})):
         os.environ.update(env)
         hg, sg, ig = getattr(mbfir, which)(*args, info=True)
         for k in env: os.environ.pop(k)

@@ -1,5 +1,4 @@
-"""Single-design latency at given sizes under the host-side switches: default (speculative head), MBFIR_GRAPH=1 (the iteration as a
-captured graph), MBFIR_SPECULATE=0 (neither)."""
+"""Single-design latency at given sizes under the host-side switches: default (speculative head), MBFIR_SPECULATE=0 (without it)."""
 import os, sys, time, warnings
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools")); warnings.filterwarnings("ignore")
@@ -8,7 +7,7 @@ from gpu_lanes import jobs_for
 for n, m in ((512, 16384), (200, 4096), (64, 1024)):
     job = jobs_for(n, 1)[0]
     o = mbfir.make_opts(grid_m=m)
-    for tag, env in (("default", {}), ("MBFIR_GRAPH=1", {"MBFIR_GRAPH": "1"}), ("MBFIR_SPECULATE=0", {"MBFIR_SPECULATE": "0"})):
+    for tag, env in (("default", {}), ("MBFIR_SPECULATE=0", {"MBFIR_SPECULATE": "0"})):
         os.environ.update(env)
         ts = []
         for rep in range(6):
