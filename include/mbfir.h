@@ -275,6 +275,47 @@ int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1
                 const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos,
                 const double* dx, const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
 
+/* ---- Batched simulation: many pulses x transmit-gain scales in one launch ----------------------------------------------------
+ * The pulses (and their grids) are concatenated; an offset table of count + 1 longs says where each item starts: item i owns
+ * entries off[i] .. off[i + 1] - 1, off[0] = 0, strictly ascending.  One upload, one launch, one download on the context's stream;
+ * one 256-thread workgroup per (pulse, scale, 256 points), the pulses with the most samples first.  A result's bits depend only on
+ * its own pulse, scale and point: not on the number of pulses, their order, or the other scales.
+ * mbfir_bloch_batch: mbfir_bloch for every (pulse p, scale s).
+ *   toff (npulse + 1): the samples of pulse p, ntime_p = toff[p + 1] - toff[p] >= 1, in b1_re / b1_im (Gauss) and gx / gy / gz
+ *     (G/cm; each NULL = 0 for every pulse).
+ *   tsoff (npulse + 1), tsteps: the intervals of pulse p in s, tsoff[p + 1] - tsoff[p] = 1 (one interval for every sample) or
+ *     ntime_p (end times are converted by the caller, as for mbfir_bloch).
+ *   t1, t2 (s, > 0), gamma (rad/s/G): npulse each.  E1 = exp(-dt / T1), E2 = exp(-dt / T2) per sample on the host, as mbfir_bloch.
+ *   nfgrid = 1 (one grid of off-resonances shared by every pulse) or npulse (grid p for pulse p); foff (nfgrid + 1) into df (Hz).
+ *   npgrid, poff (npgrid + 1), dx / dy / dz (cm; each NULL = 0): the positions, the same way.
+ *   scales (nscale >= 1): scale s multiplies b1 before the gamma dt product, rotx = ((-(b1_re s)) gamma) dt and roty =
+ *     ((b1_im s) gamma) dt, mbfir_bloch's products for the pulse b1 s: with s = 1 a pulse sees mbfir_bloch's per-sample values.
+ *   mode: mbfir_bloch's, for every pulse.
+ *   mx / my / mz: pulse p from O_p = sum_{q < p} nscale nf_q npos_q ntout_q (ntout = ntime with mode & 2, else 1), laid out
+ *     (scale, frequency, position[, time]) row-major: block (s, f, k) at O_p + ((s nf_p + f) npos_p + k) ntout_p.  On entry the
+ *     first entry of every block holds its initial magnetisation ([0 0 1] for equilibrium, as mbfir_bloch), on exit the result.
+ * mbfir_abr_batch: mbfir_abr for every (pulse p, scale s).  roff (npulse + 1) into rf_re / rf_im (radians per sample) and g (one
+ *   weight per sample; NULL = 2 pi / n_p for every sample of pulse p, mbfir_abr's default, which a caller with g for only some
+ *   pulses writes for the others); nxgrid = 1 or npulse, xoff (nxgrid + 1) into x; scale s multiplies rf; mode: mbfir_abr's (0
+ *   abrm.m, 1 the hard-pulse model).  a / b (re, im planes): pulse p from sum_{q < p} nscale nx_q, (scale, position) row-major.
+ * Both return MBFIR_E_ARG, with the reason in mbfir_last_error and no device work done, for: npulse < 1, nscale < 1, a pulse with
+ *   no samples, an offset table that does not start at 0 or does not ascend, an empty grid, a grid count neither 1 nor npulse, a
+ *   tsteps length neither 1 nor ntime_p, t1 or t2 not positive, a mode out of range, a required array NULL, and a total output
+ *   or workgroup count that overflows. */
+int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                      const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                      double* my, double* mz);
+int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                    int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
+                    double* a_im, double* b_re, double* b_im);
+/* mbfir_test_sim_blocks (host only): the workgroup table of the two calls above for pulses of ntime[p] samples and npoint[p]
+ *   points ((frequency, position) pairs, or positions) at nscale scales: 4 ints (pulse, scale, chunk, 0) per workgroup in launch
+ *   order into out (may be NULL).  Returns the number of workgroups; -1 for npulse or nscale < 1, an ntime or npoint < 1, or a
+ *   table of more than 2^31 - 1 workgroups. */
+long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out);
+
 /* ---- Root-flip search for the smallest peak (fir_flip_zero.m:56-102, rf_tools/mex5/minpeakrf.c) -----------------------
  * Scores a whole candidate set of one beta polynomial on the device and keeps the best.  Candidate c has the n coefficients of
  *     c0(x) * prod_{j < nz} (x - r_j),   r_j = zf[j] if factor j is flipped in c, else z[j]

@@ -84,6 +84,7 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
+_lp = C.POINTER(C.c_long)
 _lib = None
 
 # every symbol include/mbfir.h declares: name -> (restype, argtypes)
@@ -121,6 +122,11 @@ SYMBOLS = {
     "mbfir_abr": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_bloch": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int, _dp, C.c_int,
                               _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp]),
+    "mbfir_bloch_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
+                                    C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "mbfir_abr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp,
+                                  _dp]),
+    "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                  C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
     "mbfir_program_free": (None, [C.c_void_p]),
@@ -672,7 +678,7 @@ from .dzrf import dzrf_mb, fir_upsample, rf_mrange_desired   # noqa: E402  (dzrf
 from .search import fir_ap, fir_qp, fir_min_order_linprog, fir_min_order_qprog_phs   # noqa: E402  (outer bisections)
 from . import slrclassic    # noqa: E402  (conventional SLR pulses, dzrf.m and its designers; device remez and fmp)
 from .slrclassic import (remez, remez_batch, fmp, msinc, firls_lp, dzlp, dzls, dzmp, dzrf_batch,   # noqa: E402
-                         sim_rf_scale)
+                         sim_rf_scale, sim_rf_scale_batch)
 from . import epse          # noqa: E402  (dzepse.m spectral-spatial pulses and its helpers; device b2rf_batch)
 from .epse import (fftc, fftcp, dzbeta, verse, versec, ab2ex, ab2se, ab2inv, ab2sat, ab2st, dzepse,   # noqa: E402
                    dzepse_batch)
@@ -920,6 +926,166 @@ def bloch(b1, gr, tp, t1, t2, df, dp, mode=0, mx=None, my=None, mz=None, nucleus
                                            gamma, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])))
     shape = (nf, npos, nt) if ntout > 1 else (nf, npos)
     return tuple(o.reshape(shape) for o in out)
+
+
+# ---- batched simulators: many pulses x transmit-gain scales in one launch (mbfir_bloch_batch, mbfir_abr_batch) ----------------
+def _offsets(lengths):
+    """offset table of a concatenated list (C long): 0, then the running sums"""
+    return np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64))
+
+
+def _lptr(a):
+    return a.ctypes.data_as(_lp)
+
+
+def _per_pulse(v, npulse):
+    """A Python list of npulse arrays is one grid per pulse; anything else is one grid shared by every pulse."""
+    if isinstance(v, list) and len(v) == npulse and all(np.ndim(e) >= 1 for e in v):
+        return list(v)
+    return [v]
+
+
+def sim_block_table(ntime, npoint, nscale):
+    """The workgroups of bloch_batch / abr_batch in launch order (host only, mbfir_test_sim_blocks): one row (pulse, scale, chunk)
+    per 256-thread workgroup for pulses of ntime[p] samples and npoint[p] points at nscale scales, the longest pulses first."""
+    nt = np.ascontiguousarray(ntime, dtype=np.int32)
+    npt = np.ascontiguousarray(npoint, dtype=np.int64)
+    if len(nt) != len(npt):
+        raise ValueError("sim_block_table: ntime and npoint differ in length")
+    lib = load_library()
+    k = lib.mbfir_test_sim_blocks(len(nt), nt.ctypes.data_as(_ip), _lptr(npt), int(nscale), None)
+    if k < 0:
+        raise ValueError("sim_block_table: need pulses, nscale >= 1, every ntime and npoint >= 1")
+    out = np.zeros((k, 4), dtype=np.int32)
+    lib.mbfir_test_sim_blocks(len(nt), nt.ctypes.data_as(_ip), _lptr(npt), int(nscale), out.ctypes.data_as(_ip))
+    return out[:, :3]
+
+
+def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
+    """Many `bloch` simulations in one launch (mbfir_bloch_batch): every pulse at every transmit-gain scale.  Each pulse is
+    (b1, gr, tp, t1, t2, nucleus) with bloch's meaning of every field (tp a scalar interval, ntime intervals or ntime increasing
+    end times; nucleus 'C-13', 'H-1' or gamma in rad/s/G).  df (Hz) and dp (cm, (npos,) or (npos, 1..3)): one grid shared by
+    every pulse, or a Python list of one array per pulse.  Scale s multiplies b1.  m0: None (equilibrium) or (mx, my, mz), each
+    a scalar or (nf, npos) per pulse, the initial magnetisation at every scale.  Returns a list of (mx, my, mz) per pulse, each of
+    shape (S, nf, npos) or, with mode & 2, (S, nf, npos, ntime).  A pulse's bits depend neither on the other pulses nor on the
+    other scales."""
+    pulses, sc = list(pulses), _vec(scales)
+    if not pulses:
+        raise ValueError("bloch_batch: no pulses")
+    if len(sc) == 0:
+        raise ValueError("bloch_batch: the scale list is empty")
+    if mode not in (0, 1, 2, 3):
+        raise ValueError("bloch_batch: mode must be 0, 1, 2 or 3")
+    P, S, mode = len(pulses), len(sc), int(mode)
+    b1s, grs, tss, t1s, t2s, gams = [], [], [], [], [], []
+    for q, (b1, gr, tp, t1, t2, nucleus) in enumerate(pulses):
+        b1 = np.asarray(b1, dtype=np.complex128).ravel()
+        nt = len(b1)
+        if nt == 0:
+            raise ValueError("bloch_batch: pulse %d has no samples" % q)
+        gr = np.zeros((nt, 1)) if gr is None else np.asarray(gr, dtype=np.float64).reshape(nt, -1)
+        if gr.shape[1] > 3:
+            raise ValueError("bloch_batch: pulse %d has more than 3 gradient axes" % q)
+        tp = np.asarray(tp, dtype=np.float64).ravel()
+        if tp.size != 1 and tp.size != nt:
+            raise MbfirError("Time-point length differs from B1 length")
+        if tp.size > 1:
+            iv = np.diff(np.concatenate([[0.0], tp]))
+            tp = iv if np.all(iv > 0) else tp                      # increasing end times -> intervals, as bloch
+        b1s.append(b1)
+        grs.append(gr)
+        tss.append(tp)
+        t1s.append(float(t1))
+        t2s.append(float(t2))
+        gams.append(GAMMA_C13 if nucleus == "C-13" else GAMMA_H1 if nucleus == "H-1" else float(nucleus))
+    dfs = [_vec(v) for v in _per_pulse(df, P)]
+    dps = []
+    for v in _per_pulse(dp, P):
+        v = np.asarray(v, dtype=np.float64)
+        dps.append(v.reshape(-1, 1) if v.ndim < 2 else v)
+    if any(len(v) == 0 for v in dfs) or any(v.shape[0] == 0 or v.shape[1] > 3 for v in dps):
+        raise ValueError("bloch_batch: an empty grid, or positions with more than 3 axes")
+    nt = [len(b) for b in b1s]
+    nf = [len(dfs[0 if len(dfs) == 1 else q]) for q in range(P)]
+    npos = [dps[0 if len(dps) == 1 else q].shape[0] for q in range(P)]
+    ntout = [n if mode & 2 else 1 for n in nt]
+    ooff = _offsets([S * f * k * o for f, k, o in zip(nf, npos, ntout)])
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)]
+    for c, dflt in enumerate((0.0, 0.0, 1.0)):
+        for q in range(P):
+            v = dflt
+            if m0 is not None:
+                v = np.asarray(m0[c], dtype=np.float64)
+                v = v.reshape(nf[q], npos[q]) if v.size == nf[q] * npos[q] else np.broadcast_to(v, (nf[q], npos[q]))
+                v = v.ravel()
+            out[c][ooff[q]:ooff[q + 1]].reshape(S, nf[q] * npos[q], ntout[q])[:, :, 0] = v
+    gax, pax = max(g.shape[1] for g in grs), max(v.shape[1] for v in dps)
+    g3 = [_vec(np.concatenate([g[:, i] if i < g.shape[1] else np.zeros(len(g)) for g in grs])) if i < gax else None
+          for i in range(3)]
+    p3 = [_vec(np.concatenate([v[:, i] if i < v.shape[1] else np.zeros(v.shape[0]) for v in dps])) if i < pax else None
+          for i in range(3)]
+    b1 = np.concatenate(b1s)
+    ctx = ctx or get_context()
+    nul = C.cast(None, _dp)
+    rc = load_library().mbfir_bloch_batch(
+        ctx._h, P, _lptr(_offsets(nt)), _ptr(_vec(b1.real)), _ptr(_vec(b1.imag)), *[_ptr(g) if g is not None else nul for g in g3],
+        _lptr(_offsets([len(t) for t in tss])), _ptr(_vec(np.concatenate(tss))), _ptr(_vec(t1s)), _ptr(_vec(t2s)), _ptr(_vec(gams)),
+        len(dfs), _lptr(_offsets([len(v) for v in dfs])), _ptr(_vec(np.concatenate(dfs))),
+        len(dps), _lptr(_offsets([v.shape[0] for v in dps])), *[_ptr(p) if p is not None else nul for p in p3],
+        S, _ptr(sc), mode, *[_ptr(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = []
+    for q in range(P):
+        shape = (S, nf[q], npos[q], nt[q]) if mode & 2 else (S, nf[q], npos[q])
+        res.append(tuple(o[ooff[q]:ooff[q + 1]].reshape(shape) for o in out))
+    return res
+
+
+def abr_batch(pulses, x, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """Many `abrm` / `abr` simulations in one launch (mbfir_abr_batch): every pulse at every scale.  Each pulse is rf (radians per
+    sample; 2 pi / n per sample as in abrm) or a tuple (rf, g) with abrm's per-sample g.  x: one array shared by every pulse, or a
+    Python list of one array per pulse.  Scale s multiplies rf.  hard_pulse: abrm's hard-pulse model; convention 'abr' returns
+    abr.m's b = -conj(b).  Returns a list of (a, b) per pulse, each of shape (S, nx)."""
+    pulses, sc = list(pulses), _vec(scales)
+    if not pulses:
+        raise ValueError("abr_batch: no pulses")
+    if len(sc) == 0:
+        raise ValueError("abr_batch: the scale list is empty")
+    if convention not in ("abrm", "abr"):
+        raise ValueError("abr_batch: convention must be 'abrm' or 'abr'")
+    P, S = len(pulses), len(sc)
+    rfs, gs = [], []
+    for q, p in enumerate(pulses):
+        rf, g = p if isinstance(p, tuple) else (p, None)
+        rf = np.asarray(rf, dtype=np.complex128).ravel()
+        n = len(rf)
+        if n == 0:
+            raise ValueError("abr_batch: pulse %d has no samples" % q)
+        g = np.full(n, 2.0 * np.pi / n) if g is None else _vec(g)        # abrm's default, as the device forms it
+        if len(g) != n:
+            raise ValueError("abr_batch: g of pulse %d must have one entry per rf sample" % q)
+        rfs.append(rf)
+        gs.append(g)
+    xs = [_vec(v) for v in _per_pulse(x, P)]
+    if any(len(v) == 0 for v in xs):
+        raise ValueError("abr_batch: an empty x")
+    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
+    ooff = _offsets([S * k for k in nx])
+    out = [np.zeros(int(ooff[-1])) for _ in range(4)]
+    rf = np.concatenate(rfs)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_abr_batch(ctx._h, P, _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
+                                        _ptr(_vec(np.concatenate(gs))), len(xs), _lptr(_offsets([len(v) for v in xs])),
+                                        _ptr(_vec(np.concatenate(xs))), S, _ptr(sc), 1 if hard_pulse else 0, *[_ptr(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    a_all, b_all = out[0] + 1j * out[1], out[2] + 1j * out[3]
+    if convention == "abr":
+        b_all = -np.conj(b_all)
+    return [(a_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q]), b_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q])) for q in range(P)]
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

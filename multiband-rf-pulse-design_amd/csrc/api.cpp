@@ -789,6 +789,113 @@ int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));
 }
 
+// ---- batched simulators: every offset and size checked before any device work ---------------------------------------------
+// An offset table of count + 1 entries (count items of at least one and at most 2^31 - 1 entries each): null, or the reason.
+static const char* sim_offsets_bad(const long* off, int count) {
+    if (off[0] != 0) return "does not start at 0";
+    for (int i = 0; i < count; ++i) {
+        if (off[i + 1] == off[i]) return "has an empty item";
+        if (off[i + 1] < off[i]) return "descends";
+        if (off[i + 1] - off[i] > 2147483647L) return "has an item of more than 2^31 - 1 entries";
+    }
+    return nullptr;
+}
+// Output entries and workgroups of a batch (pulse p: npoint[p] points of ntout[p] entries at each of nscale scales): false when
+// a sum overflows, the output exceeds 2^56 entries or the launch 2^31 - 1 workgroups.
+static bool sim_sizes(int npulse, int nscale, const long* npoint, const long* ntout) {
+    long total = 0, nblk = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e, b;
+        if (__builtin_mul_overflow(npoint[p], (long)nscale, &e) || __builtin_mul_overflow(e, ntout[p], &e) ||
+            __builtin_add_overflow(total, e, &total) || __builtin_mul_overflow((npoint[p] + 255) / 256, (long)nscale, &b) ||
+            __builtin_add_overflow(nblk, b, &nblk))
+            return false;
+    }
+    return total <= (1L << 56) && nblk <= 2147483647L;
+}
+
+int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                      const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                      double* my, double* mz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_batch: " + why; return MBFIR_E_ARG; };
+    if (npulse < 1) return bad("no pulses");
+    if (nscale < 1) return bad("the scale list is empty");
+    if (mode < 0 || mode > 3) return bad("mode must be 0, 1, 2 or 3");
+    if ((nfgrid != 1 && nfgrid != npulse) || (npgrid != 1 && npgrid != npulse)) return bad("nfgrid and npgrid must be 1 or npulse");
+    if (!toff || !b1_re || !b1_im || !tsoff || !tsteps || !t1 || !t2 || !gamma || !foff || !df || !poff || !scales || !mx || !my || !mz)
+        return bad("a required array is null");
+    if (const char* why = sim_offsets_bad(toff, npulse)) {
+        for (int p = 0; p < npulse && toff[0] == 0; ++p) {
+            if (toff[p + 1] < toff[p]) break;
+            if (toff[p + 1] == toff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
+        }
+        return bad(std::string("inconsistent offsets: toff ") + why);
+    }
+    if (tsoff[0] != 0) return bad("inconsistent offsets: tsoff does not start at 0");
+    for (int p = 0; p < npulse; ++p) {
+        const long nt = toff[p + 1] - toff[p], nts = tsoff[p + 1] - tsoff[p];
+        if (nts != 1 && nts != nt)
+            return bad("tp of pulse " + std::to_string(p) + " has " + std::to_string(nts) + " entries, neither 1 nor its " +
+                       std::to_string(nt) + " samples");
+        if (!(t1[p] > 0) || !(t2[p] > 0)) return bad("t1 and t2 of pulse " + std::to_string(p) + " must be positive");
+    }
+    if (const char* why = sim_offsets_bad(foff, nfgrid)) return bad(std::string("inconsistent offsets: foff ") + why);
+    if (const char* why = sim_offsets_bad(poff, npgrid)) return bad(std::string("inconsistent offsets: poff ") + why);
+    std::vector<long> npoint(npulse), ntout(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        const int fg = nfgrid == 1 ? 0 : p, pg = npgrid == 1 ? 0 : p;
+        npoint[p] = (foff[fg + 1] - foff[fg]) * (poff[pg + 1] - poff[pg]);
+        ntout[p] = (mode & 2) ? toff[p + 1] - toff[p] : 1;
+    }
+    if (toff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                   gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, mode, mx, my, mz));
+}
+
+int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                    int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
+                    double* a_im, double* b_re, double* b_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "abr_batch: " + why; return MBFIR_E_ARG; };
+    if (npulse < 1) return bad("no pulses");
+    if (nscale < 1) return bad("the scale list is empty");
+    if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
+    if (nxgrid != 1 && nxgrid != npulse) return bad("nxgrid must be 1 or npulse");
+    if (!roff || !rf_re || !rf_im || !xoff || !x || !scales || !a_re || !a_im || !b_re || !b_im) return bad("a required array is null");
+    if (const char* why = sim_offsets_bad(roff, npulse)) {
+        for (int p = 0; p < npulse && roff[0] == 0; ++p) {
+            if (roff[p + 1] < roff[p]) break;
+            if (roff[p + 1] == roff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
+        }
+        return bad(std::string("inconsistent offsets: roff ") + why);
+    }
+    if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
+    std::vector<long> npoint(npulse), ntout(npulse, 1);
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p;
+        npoint[p] = xoff[xg + 1] - xoff[xg];
+    }
+    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, abr_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
+                                 mode, a_re, a_im, b_re, b_im));
+}
+
+long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {
+    if (npulse < 1 || nscale < 1 || !ntime || !npoint) return -1;
+    std::vector<long> ntout(npulse, 1);
+    for (int p = 0; p < npulse; ++p)
+        if (ntime[p] < 1 || npoint[p] < 1) return -1;
+    if (!sim_sizes(npulse, nscale, npoint, ntout.data())) return -1;
+    try {
+        return sim_block_table(npulse, ntime, npoint, nscale, reinterpret_cast<SimBlock*>(out));
+    } catch (const std::exception&) { return -1; }
+}
+
 int mbfir_test_time_kernels(mbfir_ctx* ctx, int n, int m, int nt, int reps, double* ms_chol, double* ms_gram) {
     MBFIR_TRY(ctx, ctx->solver->test_time_kernels(n, m, nt, reps, ms_chol, ms_gram));
 }

@@ -29,6 +29,23 @@ void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, cons
 void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
                const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
                const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
+// Work split of the batched simulators (slr.hip k_bloch_batch, k_abr_batch): one 256-thread workgroup per (pulse, scale, chunk of
+// 256 points); pulses in descending order of ntime (ties in list order), then scale, then chunk.  npoint: points per pulse
+// ((frequency, position) pairs, or positions).  Returns the table's length; writes the table to out when out is not null.
+struct SimBlock {
+    int pulse, scale, chunk, pad;
+};
+long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out);
+// Batched Bloch simulation (slr.hip k_bloch_batch) and forward simulation (k_abr_batch): P pulses x S scales, one upload, one
+// launch, one download.  Offsets and layouts as mbfir_bloch_batch / mbfir_abr_batch document them (include/mbfir.h).
+void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                     const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                     const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                     const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                     double* my, double* mz);
+void abr_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                   int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
+                   double* a_im, double* b_re, double* b_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

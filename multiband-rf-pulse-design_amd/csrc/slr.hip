@@ -7,6 +7,7 @@
 #include "pulse.h"
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace mbfir {
 
@@ -285,6 +286,160 @@ __global__ __launch_bounds__(256) void k_bloch(const double* __restrict__ step, 
 static void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode,
                          double* mx, double* my, double* mz, hipStream_t st) {
     hipLaunchKernelGGL(k_bloch, dim3(cdiv((long)nf * npos, 256)), dim3(256), 0, st, step, ntime, df, nf, pos3, npos, mode, mx, my, mz);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batched simulators: P pulses x S transmit-gain scales in one launch.  Workgroup blockIdx.x -> (pulse, scale, chunk of 256 points)
+// through the host-built block table (sim_block_table), the pulses with the most samples first.  Each workgroup stages only its
+// own pulse's samples through LDS, 256 at a time, and runs the per-sample arithmetic of its single-pulse twin (copied, not shared),
+// so a thread's bits depend only on its own (pulse, scale, point) and the fixed time order.
+
+// k_abr over the batch.  rf (interleaved) is scaled while it is staged; g holds one weight per sample of every pulse (the host
+// writes 2 pi / n where a pulse has none: the value k_abr computes for a null g).  Output: S x nx per pulse, scale-major.
+struct AbrPulseDev {
+    long r_off, x_off, o_off;     // first rf / g sample, first position, first output entry
+    int n, nx;
+};
+__global__ __launch_bounds__(256) void k_abr_batch(const double* __restrict__ rf_il, const double* __restrict__ g,
+                                                   const double* __restrict__ x, const double* __restrict__ scales,
+                                                   const AbrPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                   int mode, double* __restrict__ a_il, double* __restrict__ b_il) {
+    __shared__ double2 srf[256];
+    __shared__ double sg[256];
+    const SimBlock bk = blocks[blockIdx.x];
+    const AbrPulseDev P = pulses[bk.pulse];
+    const double sc = scales[bk.scale];
+    const int n = P.n, i = bk.chunk * 256 + threadIdx.x;
+    const double xv = i < P.nx ? x[P.x_off + i] : 0.0;
+    double2 a = make_double2(1, 0), b = make_double2(0, 0);
+    for (int m0 = 0; m0 < n; m0 += 256) {
+        __syncthreads();
+        const int mm = m0 + threadIdx.x;
+        if (mm < n) {
+            const long t = P.r_off + mm;
+            srf[threadIdx.x] = make_double2(rf_il[2 * t] * sc, rf_il[2 * t + 1] * sc);
+            sg[threadIdx.x] = g[t];
+        }
+        __syncthreads();
+        const int cnt = min(256, n - m0);
+        for (int q = 0; q < cnt; ++q) {
+            const double2 r = srf[q];
+            const double om = xv * sg[q];
+            double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
+            if (mode == 0) {
+                const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
+                double sn, cs;
+                sincos(0.5 * phi, &sn, &cs);
+                const double inv = phi > 0 ? sn / phi : 0.0;
+                av = make_double2(cs, -om * inv);
+                bv = make_double2(r.y * inv, -r.x * inv);                  // -i (n1 + i n2) sin
+                const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
+                                                av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
+                const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
+                                                bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
+                a = an; b = bn;
+            } else {
+                const double th = hypot(r.x, r.y);
+                double sn, cs, sz, cz;
+                sincos(0.5 * th, &sn, &cs);
+                sincos(-om, &sz, &cz);                                   // z^-1
+                const double2 zb = make_double2(cz * b.x - sz * b.y, cz * b.y + sz * b.x);
+                const double inv = th > 0 ? sn / th : 0.0;
+                const double2 S = make_double2(-r.y * inv, r.x * inv);    // i e^{i arg rf} sin(th/2)
+                const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
+                const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
+                a = an; b = bn;
+            }
+        }
+    }
+    if (i < P.nx) {
+        const long o = P.o_off + (long)bk.scale * P.nx + i;
+        a_il[2 * o] = a.x; a_il[2 * o + 1] = a.y; b_il[2 * o] = b.x; b_il[2 * o + 1] = b.y;
+    }
+}
+
+// k_bloch over the batch.  in[t] = (b1 re, b1 im, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2, dt) per sample of every
+// pulse.  The thread that stages sample t forms bloch_run's rotx = ((-(re s)) gamma) dt and roty = ((im s) gamma) dt for the
+// workgroup's scale s, so the LDS tile holds k_bloch's step[t] for the pulse b1 s.  m0: (x, y, z) of every (scale, frequency,
+// position) block of every pulse; output S x nf x npos x ntout per pulse, scale-major.
+constexpr int BLOCH_IN = 9;
+struct BlochPulseDev {
+    long t_off, f_off, p_off;     // first sample, first frequency, first position (3 doubles each)
+    long m_off, o_off;            // first m0 block, first output entry
+    int ntime, nf, npos, pad;
+    double gamma;
+};
+__global__ __launch_bounds__(256) void k_bloch_batch(const double* __restrict__ in, const double* __restrict__ df,
+                                                     const double* __restrict__ pos3, const double* __restrict__ scales,
+                                                     const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                     const double* __restrict__ m0, int mode, double* __restrict__ mx,
+                                                     double* __restrict__ my, double* __restrict__ mz) {
+    __shared__ double sst[BLOCH_CH][8];
+    const SimBlock bk = blocks[blockIdx.x];
+    const BlochPulseDev P = pulses[bk.pulse];
+    const double sc = scales[bk.scale], gamma = P.gamma;
+    const int ntime = P.ntime, npos = P.npos;
+    const long npair = (long)P.nf * npos, pair = (long)bk.chunk * 256 + threadIdx.x;
+    const bool live = pair < npair;
+    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
+    const double dfv = df[P.f_off + fi];
+    const double* pp = pos3 + 3 * (P.p_off + pi);
+    const double px = pp[0], py = pp[1], pz = pp[2];
+    const int ntout = (mode & 2) ? ntime : 1;
+    const long blk = (long)bk.scale * npair + pair, o0 = P.o_off + blk * ntout;
+    double m[3] = {0, 0, 1};
+    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
+    for (int pass = (mode & 1) ? 0 : 1; pass < 2; ++pass) {
+        if (pass == 1 && mode == 1) break;                               // steady state only
+        double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, B[3] = {0, 0, 0};
+        for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
+            __syncthreads();
+            const int cnt = min(BLOCH_CH, ntime - t0);
+            if ((int)threadIdx.x < cnt) {
+                const double* s = in + BLOCH_IN * (P.t_off + t0 + threadIdx.x);
+                const double dt = s[8];
+                sst[threadIdx.x][0] = ((-(s[0] * sc)) * gamma) * dt;      // rotx  (bloch_run of b1 s)
+                sst[threadIdx.x][1] = ((s[1] * sc) * gamma) * dt;         // roty
+                for (int e = 2; e < 8; ++e) sst[threadIdx.x][e] = s[e];
+            }
+            __syncthreads();
+            if (!live) continue;
+            for (int q = 0; q < cnt; ++q) {
+                const double* s = sst[q];
+                const double rotz = -((s[2] * px + s[3] * py + s[4] * pz) + dfv * s[5]);
+                Rot3 R;
+                bloch_rotmat(s[0], s[1], rotz, R);
+                const double e1 = s[6], e2 = s[7];
+                if (pass == 0) {
+                    double c[3], o[3];
+                    for (int j = 0; j < 3; ++j) {                        // A <- D R A, column by column
+                        c[0] = A[3 * j]; c[1] = A[3 * j + 1]; c[2] = A[3 * j + 2];
+                        rot_vec(R, c, o);
+                        A[3 * j] = e2 * o[0]; A[3 * j + 1] = e2 * o[1]; A[3 * j + 2] = e1 * o[2];
+                    }
+                    rot_vec(R, B, o);
+                    B[0] = e2 * o[0]; B[1] = e2 * o[1]; B[2] = e1 * o[2] + (1 - e1);
+                } else {
+                    double o[3];
+                    rot_vec(R, m, o);
+                    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
+                    if (mode & 2) { mx[o0 + t0 + q] = m[0]; my[o0 + t0 + q] = m[1]; mz[o0 + t0 + q] = m[2]; }
+                }
+            }
+        }
+        if (pass == 0 && live) {
+            // M = (I - A)^-1 B by the adjugate (the reference's invmat)
+            double K[9];
+            for (int e = 0; e < 9; ++e) K[e] = ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0) - A[e];
+            const double c00 = K[4] * K[8] - K[7] * K[5], c01 = K[7] * K[2] - K[1] * K[8], c02 = K[1] * K[5] - K[4] * K[2];
+            const double det = K[0] * c00 + K[3] * c01 + K[6] * c02;
+            const double inv[9] = {c00 / det, c01 / det, c02 / det,
+                                   (K[6] * K[5] - K[3] * K[8]) / det, (K[0] * K[8] - K[6] * K[2]) / det, (K[3] * K[2] - K[0] * K[5]) / det,
+                                   (K[3] * K[7] - K[6] * K[4]) / det, (K[6] * K[1] - K[0] * K[7]) / det, (K[0] * K[4] - K[3] * K[1]) / det};
+            for (int i = 0; i < 3; ++i) m[i] = inv[i] * B[0] + inv[3 + i] * B[1] + inv[6 + i] * B[2];
+        }
+    }
+    if (live && !(mode & 2)) { mx[o0] = m[0]; my[o0] = m[1]; mz[o0] = m[2]; }
 }
 
 // work: 3 * 8n double2.  a_il / rf_il: device arrays of 2n doubles (interleaved).
@@ -794,6 +949,170 @@ void bloch_run(int device, void* stream, int ntime, const double* b1_re, const d
     MBFIR_HIP(hipMemcpyAsync(mz, dmz.p, nout * 8, hipMemcpyDeviceToHost, st));
     MBFIR_HIP(hipStreamSynchronize(st));
     MBFIR_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side of mbfir_bloch_batch / mbfir_abr_batch (arguments checked by api.cpp): every input in one staging buffer of
+// 256-byte-aligned sections, one upload, one launch, one download.
+
+long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out) {
+    long k = 0;
+    for (int p = 0; p < npulse; ++p) k += (npoint[p] + 255) / 256 * nscale;
+    if (!out) return k;
+    // Longest pulses first: workgroups are handed out roughly in blockIdx order, and a long pulse's workgroups started last would
+    // run on alone after the short ones have drained (the longest-processing-time-first rule).
+    std::vector<int> order(npulse);
+    for (int p = 0; p < npulse; ++p) order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ntime[a] > ntime[b]; });
+    long w = 0;
+    for (int p : order) {
+        const long nch = (npoint[p] + 255) / 256;
+        for (int s = 0; s < nscale; ++s)
+            for (long c = 0; c < nch; ++c) out[w++] = SimBlock{p, s, int(c), 0};
+    }
+    return k;
+}
+
+namespace {
+struct Staging {                                          // host sections, each 256-byte aligned, uploaded with one copy
+    std::vector<char> h;
+    size_t add(size_t bytes) {
+        const size_t o = (h.size() + 255) & ~size_t(255);
+        h.resize(o + bytes);
+        return o;
+    }
+    template <class T> T* at(size_t o) { return reinterpret_cast<T*>(h.data() + o); }
+};
+}  // namespace
+
+void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                     const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                     const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                     const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                     double* my, double* mz) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const double TWOPI_REF = 6.283185;                       // blochC.c:6, as bloch_run
+    std::vector<BlochPulseDev> pd(npulse);
+    std::vector<int> nt(npulse);
+    std::vector<long> npair(npulse);
+    long M = 0, O = 0;                                       // m0 blocks, output entries
+    for (int p = 0; p < npulse; ++p) {
+        const int fg = nfgrid == 1 ? 0 : p, pg = npgrid == 1 ? 0 : p;
+        BlochPulseDev& d = pd[p];
+        d.t_off = toff[p]; d.f_off = foff[fg]; d.p_off = poff[pg]; d.m_off = M; d.o_off = O;
+        d.ntime = nt[p] = int(toff[p + 1] - toff[p]);
+        d.nf = int(foff[fg + 1] - foff[fg]);
+        d.npos = int(poff[pg + 1] - poff[pg]);
+        d.pad = 0;
+        d.gamma = gamma[p];
+        npair[p] = (long)d.nf * d.npos;
+        M += nscale * npair[p];
+        O += nscale * npair[p] * ((mode & 2) ? d.ntime : 1);
+    }
+    const long T = toff[npulse], F = foff[nfgrid], NP = poff[npgrid];
+    const long nblk = sim_block_table(npulse, nt.data(), npair.data(), nscale, nullptr);
+    Staging S;
+    const size_t o_in = S.add(T * BLOCH_IN * 8), o_df = S.add(F * 8), o_pos = S.add(NP * 24), o_sc = S.add((size_t)nscale * 8),
+                 o_m0 = S.add(M * 24), o_pd = S.add(npulse * sizeof(BlochPulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
+    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    double* in = S.at<double>(o_in);
+    for (int p = 0; p < npulse; ++p) {
+        const bool one = tsoff[p + 1] - tsoff[p] == 1;
+        const double g = gamma[p];
+        for (long t = toff[p]; t < toff[p + 1]; ++t) {
+            const double dt = tsteps[tsoff[p] + (one ? 0 : t - toff[p])];
+            double* s = in + BLOCH_IN * t;
+            s[0] = b1_re[t];
+            s[1] = b1_im[t];
+            s[2] = (gx ? gx[t] : 0.0) * g * dt;                  // bloch_run's gradient terms of rotz
+            s[3] = (gy ? gy[t] : 0.0) * g * dt;
+            s[4] = (gz ? gz[t] : 0.0) * g * dt;
+            s[5] = TWOPI_REF * dt;
+            s[6] = std::exp(-dt / t1[p]);
+            s[7] = std::exp(-dt / t2[p]);
+            s[8] = dt;
+        }
+    }
+    std::copy(df, df + F, S.at<double>(o_df));
+    double* pos = S.at<double>(o_pos);
+    for (long i = 0; i < NP; ++i) { pos[3 * i] = dx ? dx[i] : 0.0; pos[3 * i + 1] = dy ? dy[i] : 0.0; pos[3 * i + 2] = dz ? dz[i] : 0.0; }
+    std::copy(scales, scales + nscale, S.at<double>(o_sc));
+    double* m0 = S.at<double>(o_m0);
+    for (int p = 0; p < npulse; ++p) {
+        const long ntout = (mode & 2) ? nt[p] : 1;
+        for (long b = 0; b < nscale * npair[p]; ++b) {
+            const long o = pd[p].o_off + b * ntout, m = 3 * (pd[p].m_off + b);
+            m0[m] = mx[o]; m0[m + 1] = my[o]; m0[m + 2] = mz[o];
+        }
+    }
+    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(BlochPulseDev));
+    sim_block_table(npulse, nt.data(), npair.data(), nscale, S.at<SimBlock>(o_bk));
+    DevBuf dbuf(o_out + 3 * (size_t)O * 8);
+    char* base = dbuf.as<char>();
+    double* out = reinterpret_cast<double*>(base + o_out);
+    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_bloch_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_in),
+                       reinterpret_cast<const double*>(base + o_df), reinterpret_cast<const double*>(base + o_pos),
+                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const BlochPulseDev*>(base + o_pd),
+                       reinterpret_cast<const SimBlock*>(base + o_bk), reinterpret_cast<const double*>(base + o_m0), mode, out,
+                       out + O, out + 2 * O);
+    MBFIR_HIP(hipGetLastError());
+    std::vector<double> h(3 * (size_t)O);
+    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    std::copy(h.begin(), h.begin() + O, mx);
+    std::copy(h.begin() + O, h.begin() + 2 * O, my);
+    std::copy(h.begin() + 2 * O, h.end(), mz);
+}
+
+void abr_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                   int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
+                   double* a_im, double* b_re, double* b_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<AbrPulseDev> pd(npulse);
+    std::vector<int> nt(npulse);
+    std::vector<long> nx(npulse);
+    long O = 0;                                              // output entries of a (and of b)
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p;
+        pd[p] = AbrPulseDev{roff[p], xoff[xg], O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg])};
+        nt[p] = pd[p].n;
+        nx[p] = pd[p].nx;
+        O += nscale * nx[p];
+    }
+    const long R = roff[npulse], X = xoff[nxgrid];
+    const long nblk = sim_block_table(npulse, nt.data(), nx.data(), nscale, nullptr);
+    Staging S;
+    const size_t o_rf = S.add(R * 16), o_g = S.add(R * 8), o_x = S.add(X * 8), o_sc = S.add((size_t)nscale * 8),
+                 o_pd = S.add(npulse * sizeof(AbrPulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
+    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
+    double* gw = S.at<double>(o_g);
+    for (int p = 0; p < npulse; ++p)
+        for (long t = roff[p]; t < roff[p + 1]; ++t) gw[t] = g ? g[t] : 2.0 * M_PI / pd[p].n;     // k_abr's weight for a null g
+    std::copy(x, x + X, S.at<double>(o_x));
+    std::copy(scales, scales + nscale, S.at<double>(o_sc));
+    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(AbrPulseDev));
+    sim_block_table(npulse, nt.data(), nx.data(), nscale, S.at<SimBlock>(o_bk));
+    DevBuf dbuf(o_out + 4 * (size_t)O * 8);
+    char* base = dbuf.as<char>();
+    double2* out = reinterpret_cast<double2*>(base + o_out);    // a: O entries, then b: O entries
+    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_rf),
+                       reinterpret_cast<const double*>(base + o_g), reinterpret_cast<const double*>(base + o_x),
+                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const AbrPulseDev*>(base + o_pd),
+                       reinterpret_cast<const SimBlock*>(base + o_bk), mode, reinterpret_cast<double*>(out),
+                       reinterpret_cast<double*>(out + O));
+    MBFIR_HIP(hipGetLastError());
+    std::vector<double2> h(2 * (size_t)O);
+    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 16, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    unpack_cplx(O, h.data(), a_re, a_im);
+    unpack_cplx(O, h.data() + O, b_re, b_im);
 }
 
 }  // namespace mbfir

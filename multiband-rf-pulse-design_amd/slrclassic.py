@@ -276,3 +276,23 @@ def sim_rf_scale(rf, dt, scale=None, nucleus="C-13", f=None, bw=None, *, ctx=Non
         mxy[k] = np.asarray(mx).ravel() + 1j * np.asarray(my).ravel()
         mz[k] = np.asarray(m_z).ravel()
     return df, mxy, mz
+
+
+def sim_rf_scale_batch(pulses, dts, scale=None, nucleus="C-13", f=None, bw=None, *, ctx=None):
+    """sim_rf_scale of many pulses from one mbfir.bloch_batch call (every pulse at every scale in one launch).  pulses: rf arrays
+    (Gauss); dts: one sampling interval (ms) or one per pulse; f (band edges, kHz) and bw (kHz): one value, or a list with one per
+    pulse (None where a pulse takes the other).  Returns one (df, mxy, mz) per pulse, as sim_rf_scale returns it."""
+    if nucleus not in ("C-13", "H-1"):
+        raise ValueError("sim_rf_scale: nucleus must be 'H-1' or 'C-13'")
+    rfs = [np.asarray(rf, dtype=np.complex128).ravel() for rf in pulses]
+    P = len(rfs)
+    dts = np.broadcast_to(np.asarray(dts, dtype=np.float64), (P,))
+    fs = list(f) if isinstance(f, list) and len(f) == P and all(v is None or np.ndim(v) >= 1 for v in f) else [f] * P
+    bws = list(bw) if isinstance(bw, (list, tuple)) else [bw] * P
+    if len(bws) != P:
+        raise ValueError("sim_rf_scale: bw must be one value or one per pulse")
+    axes = [sim_rf_axis(fv, bv) for fv, bv in zip(fs, bws)]
+    scale = [0.8, 0.9, 1.0, 1.1, 1.2] if scale is None or len(scale) == 0 else list(scale)
+    res = _pkg.bloch_batch([(rf, np.zeros(len(rf)), dt * 1e-3, 1e3, 1e3, nucleus) for rf, dt in zip(rfs, dts)], axes, 0.0,
+                           scales=scale, ctx=ctx)
+    return [(df, mx[:, :, 0] + 1j * my[:, :, 0], m_z[:, :, 0]) for df, (mx, my, m_z) in zip(axes, res)]
