@@ -3,6 +3,9 @@
 //   b2a   : DFTs of length blp = 8 n (any n: direct O(blp^2) DFT, twiddles by rotation recurrence with an
 //           exact sincospi seed every 256 terms), elementwise steps in between
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
+// k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr / k_abr_batch / k_abr2 share abr_step: one definition each, so those
+// batch kernels equal their single-pulse twins by construction.  k_bloch / k_bloch_batch still hold the same loop nest twice (see
+// the note above k_bloch_batch).
 #include "dev_common.h"
 #include "pulse.h"
 #include <algorithm>
@@ -90,52 +93,96 @@ __global__ void k_slr_out(const double2* __restrict__ aca, int n, double* __rest
     if (i < n) { a_il[2 * i] = aca[n - 1 - i].x; a_il[2 * i + 1] = aca[n - 1 - i].y; }
 }
 
-// inverse SLR recursion; a_il / b_il / rf_il interleaved (re, im); n <= SLR_MAXN
-constexpr int SLR_MAXN = 2048;
-__global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il, const double* __restrict__ b_il, int n,
-                                                double* __restrict__ rf_il) {
-    __shared__ double2 A[2][SLR_MAXN], B[2][SLR_MAXN];
-    __shared__ double2 cs[2];                             // (c, 0), s
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        A[0][i] = make_double2(a_il[2 * i], a_il[2 * i + 1]);
-        B[0][i] = make_double2(b_il[2 * i], b_il[2 * i + 1]);
-    }
-    __syncthreads();
+// The n-step inverse SLR recursion (ab2rf.m:14-29) in one workgroup of NT threads, shared by k_ab2rf and k_b2rf_batch.  A / B: the
+// two polynomials in LDS, each with its ping-pong twin pp entries further on (the recursion starts in A / B, filled and synchronised
+// by the caller); cs: two double2 of LDS; rf: the n samples of the pulse.
+template <int NT>
+__device__ __forceinline__ void ab2rf_recursion(double2* A, double2* B, int pp, int n, double2* cs, double2* __restrict__ rf) {
+    const int tid = threadIdx.x;
     int cur = 0;
     for (int i = n; i >= 1; --i) {
-        if (threadIdx.x == 0) {
-            const double2 ai = A[cur][i - 1], bi = B[cur][i - 1];
+        const double2* Ac = A + cur * pp;
+        const double2* Bc = B + cur * pp;
+        double2* An = A + (cur ^ 1) * pp;
+        double2* Bn = B + (cur ^ 1) * pp;
+        if (tid == 0) {
+            const double2 ai = Ac[i - 1], bi = Bc[i - 1];
             const double den = ai.x * ai.x + ai.y * ai.y;
             const double2 q = make_double2((bi.x * ai.x + bi.y * ai.y) / den, (bi.y * ai.x - bi.x * ai.y) / den);   // b / a
             const double c = sqrt(1.0 / (1.0 + (q.x * q.x + q.y * q.y)));
             const double2 s = make_double2(c * q.x, -c * q.y);                                                      // conj(c b / a)
             const double theta = atan2(hypot(s.x, s.y), c), psi = atan2(s.y, s.x);
-            rf_il[2 * (i - 1)] = 2 * theta * cos(psi);
-            rf_il[2 * (i - 1) + 1] = 2 * theta * sin(psi);
+            rf[i - 1] = make_double2(2 * theta * cos(psi), 2 * theta * sin(psi));
             cs[0] = make_double2(c, 0);
             cs[1] = s;
         }
         __syncthreads();
         const double c = cs[0].x;
         const double2 s = cs[1], ms = make_double2(-s.x, s.y);                                                      // -conj(s)
-        const int nxt = cur ^ 1;
-        for (int k = threadIdx.x; k < i; k += blockDim.x) {
-            const double2 ak = A[cur][k], bk = B[cur][k];
+        for (int k = tid; k < i; k += NT) {
+            const double2 ak = Ac[k], bk = Bc[k];
             const double2 sb = cmul2(s, bk), msa = cmul2(ms, ak);
-            const double2 acn = make_double2(c * ak.x + sb.x, c * ak.y + sb.y);
-            const double2 bcn = make_double2(msa.x + c * bk.x, msa.y + c * bk.y);
-            if (k >= 1) A[nxt][k - 1] = acn;              // ac = acn(2:i)
-            if (k < i - 1) B[nxt][k] = bcn;               // bc = bcn(1:i-1)
+            if (k >= 1) An[k - 1] = make_double2(c * ak.x + sb.x, c * ak.y + sb.y);     // ac = acn(2:i)
+            if (k < i - 1) Bn[k] = make_double2(msa.x + c * bk.x, msa.y + c * bk.y);    // bc = bcn(1:i-1)
         }
         __syncthreads();
-        cur = nxt;
+        cur ^= 1;
     }
+}
+
+// inverse SLR recursion; a_il / b_il / rf_il interleaved (re, im), which is the double2 layout; n <= SLR_MAXN
+constexpr int SLR_MAXN = 2048;
+__global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il, const double* __restrict__ b_il, int n,
+                                                double* __restrict__ rf_il) {
+    __shared__ double2 A[2][SLR_MAXN], B[2][SLR_MAXN];
+    __shared__ double2 cs[2];                             // (c, 0), s
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        A[0][i] = make_double2(a_il[2 * i], a_il[2 * i + 1]);
+        B[0][i] = make_double2(b_il[2 * i], b_il[2 * i + 1]);
+    }
+    __syncthreads();
+    ab2rf_recursion<1024>(A[0], B[0], SLR_MAXN, n, cs, reinterpret_cast<double2*>(rf_il));
 }
 
 // Forward simulation of an RF pulse over off-resonance: Cayley-Klein parameters per position.
 //   mode 0: rf_tools/abrm.m:40-57 -- one rotation about (Re rf, Im rf, x g_m) per sample
 //   mode 1: the hard-pulse model the inverse SLR transform inverts exactly -- free precession by x g_m on beta, then
 //           the hard pulse of the sample
+// abr_step is one sample of either model for one position (r: the rf sample, om: the precession angle of the sample; mode is
+// uniform over the workgroup).  k_abr, k_abr_batch and k_abr2 (mode 0, om = x gx + y gy) all step through it.  The state goes in
+// and comes back by value: through references the kernels compile to other fused products (the compiler then promotes a and b to
+// registers only after inlining, in another order), and the results differ from before in the last bits.
+struct CayleyKlein {
+    double2 a, b;
+};
+__device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, double2 a, double2 b) {
+    double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
+    if (mode == 0) {
+        const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
+        double sn, cs;
+        sincos(0.5 * phi, &sn, &cs);
+        const double inv = phi > 0 ? sn / phi : 0.0;
+        av = make_double2(cs, -om * inv);
+        bv = make_double2(r.y * inv, -r.x * inv);                  // -i (n1 + i n2) sin
+        const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
+                                        av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
+        const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
+                                        bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
+        a = an; b = bn;
+    } else {
+        const double th = hypot(r.x, r.y);
+        double sn, cs, sz, cz;
+        sincos(0.5 * th, &sn, &cs);
+        sincos(-om, &sz, &cz);                                   // z^-1
+        const double2 zb = make_double2(cz * b.x - sz * b.y, cz * b.y + sz * b.x);
+        const double inv = th > 0 ? sn / th : 0.0;
+        const double2 S = make_double2(-r.y * inv, r.x * inv);    // i e^{i arg rf} sin(th/2)
+        const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
+        const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
+        a = an; b = bn;
+    }
+    return CayleyKlein{a, b};
+}
 // one thread per position, the pulse staged through LDS; g may be null (2 pi / n per sample).
 __global__ __launch_bounds__(256) void k_abr(const double* __restrict__ rf_il, const double* __restrict__ g, int n,
                                              const double* __restrict__ x, int nx, int mode, double* __restrict__ a_il,
@@ -153,33 +200,8 @@ __global__ __launch_bounds__(256) void k_abr(const double* __restrict__ rf_il, c
         __syncthreads();
         const int cnt = min(256, n - m0);
         for (int q = 0; q < cnt; ++q) {
-            const double2 r = srf[q];
-            const double om = xv * sg[q];
-            double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
-            if (mode == 0) {
-                const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
-                double sn, cs;
-                sincos(0.5 * phi, &sn, &cs);
-                const double inv = phi > 0 ? sn / phi : 0.0;
-                av = make_double2(cs, -om * inv);
-                bv = make_double2(r.y * inv, -r.x * inv);                  // -i (n1 + i n2) sin
-                const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
-                                                av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
-                const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
-                                                bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
-                a = an; b = bn;
-            } else {
-                const double th = hypot(r.x, r.y);
-                double sn, cs, sz, cz;
-                sincos(0.5 * th, &sn, &cs);
-                sincos(-om, &sz, &cz);                                   // z^-1
-                const double2 zb = make_double2(cz * b.x - sz * b.y, cz * b.y + sz * b.x);
-                const double inv = th > 0 ? sn / th : 0.0;
-                const double2 S = make_double2(-r.y * inv, r.x * inv);    // i e^{i arg rf} sin(th/2)
-                const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
-                const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
-                a = an; b = bn;
-            }
+            const CayleyKlein ck = abr_step(mode, srf[q], xv * sg[q], a, b);
+            a = ck.a; b = ck.b;
         }
     }
     if (i < nx) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
@@ -291,8 +313,12 @@ static void bloch_launch(const double* step, int ntime, const double* df, int nf
 // ------------------------------------------------------------------------------------------------
 // Batched simulators: P pulses x S transmit-gain scales in one launch.  Workgroup blockIdx.x -> (pulse, scale, chunk of 256 points)
 // through the host-built block table (sim_block_table), the pulses with the most samples first.  Each workgroup stages only its
-// own pulse's samples through LDS, 256 at a time, and runs the per-sample arithmetic of its single-pulse twin (copied, not shared),
-// so a thread's bits depend only on its own (pulse, scale, point) and the fixed time order.
+// own pulse's samples through LDS, 256 at a time, and runs the per-sample arithmetic of its single-pulse twin, so a thread's bits
+// depend only on its own (pulse, scale, point) and the fixed time order.  k_abr_batch calls k_abr's abr_step.  k_bloch_batch
+// repeats k_bloch's loop nest: every shared form tried (step and steady-state functions on array references; the whole loop nest
+// in one function with the state by value and the tile fill as a callable) kept the registers and the opcode counts but fused
+// other products, and the magnetisation moved in the last bits (3e-15 of the peak, 3e-13 in the steady-state modes).  Edit the two
+// copies alike; tests/test_simbatch_gpu.py asserts that they agree bit for bit.
 
 // k_abr over the batch.  rf (interleaved) is scaled while it is staged; g holds one weight per sample of every pulse (the host
 // writes 2 pi / n where a pulse has none: the value k_abr computes for a null g).  Output: S x nx per pulse, scale-major.
@@ -323,33 +349,8 @@ __global__ __launch_bounds__(256) void k_abr_batch(const double* __restrict__ rf
         __syncthreads();
         const int cnt = min(256, n - m0);
         for (int q = 0; q < cnt; ++q) {
-            const double2 r = srf[q];
-            const double om = xv * sg[q];
-            double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
-            if (mode == 0) {
-                const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
-                double sn, cs;
-                sincos(0.5 * phi, &sn, &cs);
-                const double inv = phi > 0 ? sn / phi : 0.0;
-                av = make_double2(cs, -om * inv);
-                bv = make_double2(r.y * inv, -r.x * inv);                  // -i (n1 + i n2) sin
-                const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
-                                                av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
-                const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
-                                                bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
-                a = an; b = bn;
-            } else {
-                const double th = hypot(r.x, r.y);
-                double sn, cs, sz, cz;
-                sincos(0.5 * th, &sn, &cs);
-                sincos(-om, &sz, &cz);                                   // z^-1
-                const double2 zb = make_double2(cz * b.x - sz * b.y, cz * b.y + sz * b.x);
-                const double inv = th > 0 ? sn / th : 0.0;
-                const double2 S = make_double2(-r.y * inv, r.x * inv);    // i e^{i arg rf} sin(th/2)
-                const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
-                const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
-                a = an; b = bn;
-            }
+            const CayleyKlein ck = abr_step(mode, srf[q], xv * sg[q], a, b);
+            a = ck.a; b = ck.b;
         }
     }
     if (i < P.nx) {
@@ -561,49 +562,29 @@ __global__ __launch_bounds__(NT) void k_b2rf_batch(const double2* __restrict__ b
             A0[n - 1 - k] = make_double2(v.x * invN, v.y * invN);
         });
         __syncthreads();
-        // inverse SLR recursion (ab2rf.m:14-29), k_ab2rf's arithmetic
-        int cur = 0;
-        for (int i = n; i >= 1; --i) {
-            double2* Ac = L + 2 * cur * MAXN;
-            double2* Bc = Ac + MAXN;
-            double2* An = L + 2 * (cur ^ 1) * MAXN;
-            double2* Bn = An + MAXN;
-            if (tid == 0) {
-                const double2 ai = Ac[i - 1], bi = Bc[i - 1];
-                const double den = ai.x * ai.x + ai.y * ai.y;
-                const double2 q = make_double2((bi.x * ai.x + bi.y * ai.y) / den, (bi.y * ai.x - bi.x * ai.y) / den);   // b / a
-                const double c = sqrt(1.0 / (1.0 + (q.x * q.x + q.y * q.y)));
-                const double2 s = make_double2(c * q.x, -c * q.y);                                                      // conj(c b / a)
-                const double theta = atan2(hypot(s.x, s.y), c), psi = atan2(s.y, s.x);
-                rf[(size_t)p * n + i - 1] = make_double2(2 * theta * cos(psi), 2 * theta * sin(psi));
-                cs[0] = make_double2(c, 0);
-                cs[1] = s;
-            }
-            __syncthreads();
-            const double c = cs[0].x;
-            const double2 s = cs[1], ms = make_double2(-s.x, s.y);                                                      // -conj(s)
-            for (int k = tid; k < i; k += NT) {
-                const double2 ak = Ac[k], bk = Bc[k];
-                const double2 sb = cmul2(s, bk), msa = cmul2(ms, ak);
-                if (k >= 1) An[k - 1] = make_double2(c * ak.x + sb.x, c * ak.y + sb.y);     // ac = acn(2:i)
-                if (k < i - 1) Bn[k] = make_double2(msa.x + c * bk.x, msa.y + c * bk.y);    // bc = bcn(1:i-1)
-            }
-            __syncthreads();
-            cur ^= 1;
-        }
+        ab2rf_recursion<NT>(A0, B0, 2 * MAXN, n, cs, rf + (size_t)p * n);
     }
 }
 
-template <int MAXN, int NT>
-static void b2rf_batch_launch(int device, hipStream_t st, int n, int count, const double2* b, double2* rf) {
+// The (MAXN, NT) tiers of k_b2rf_batch: f(kernel, NT) for the smallest tier that holds n taps
+template <class F>
+static auto with_b2rf_tier(int n, F f) {
+    if (n <= 128) return f(k_b2rf_batch<128, 256>, 256);
+    if (n <= 512) return f(k_b2rf_batch<512, 256>, 256);
+    if (n <= 1024) return f(k_b2rf_batch<1024, 512>, 512);
+    return f(k_b2rf_batch<2048, 512>, 512);
+}
+// Sizing, and an enqueue on a caller-owned scratch (no synchronisation).  The grid is what can be resident, which bounds the scratch.
+static int b2rf_batch_grid(int device, int n, int count) {
     int ncu = 0, per = 0;
     MBFIR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_b2rf_batch<MAXN, NT>, NT, 0));
-    const int grid = std::max(1, std::min(count, std::max(per, 1) * ncu));    // resident workgroups bound the scratch
-    DevBuf work((size_t)grid * 2 * 8 * n * sizeof(double2));
-    hipLaunchKernelGGL((k_b2rf_batch<MAXN, NT>), dim3(grid), dim3(NT), 0, st, b, n, count, work.as<double2>(), rf);
+    with_b2rf_tier(n, [&](auto kernel, int nt) { MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, nt, 0)); });
+    return std::max(1, std::min(count, std::max(per, 1) * ncu));
+}
+// work: grid x 2 (8 n) double2
+static void b2rf_batch_enqueue(hipStream_t st, int grid, int n, int count, const double2* b, double2* work, double2* rf) {
+    with_b2rf_tier(n, [&](auto kernel, int nt) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(nt), 0, st, b, n, count, work, rf); });
     MBFIR_HIP(hipGetLastError());
-    MBFIR_HIP(hipStreamSynchronize(st));                  // the scratch is freed on return
 }
 
 // Host side of mbfir_b2rf_batch (arguments checked): host planes in, host planes out.
@@ -617,14 +598,11 @@ void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double
     pack_cplx(tot, b_re, b_im, h.data());
     DevBuf db(tot * sizeof(double2)), drf(tot * sizeof(double2));
     MBFIR_HIP(hipMemcpyAsync(db.p, h.data(), tot * sizeof(double2), hipMemcpyHostToDevice, st));
-    const double2* b = db.as<double2>();
-    double2* rf = drf.as<double2>();
-    if (n <= 128) b2rf_batch_launch<128, 256>(device, st, n, count, b, rf);
-    else if (n <= 512) b2rf_batch_launch<512, 256>(device, st, n, count, b, rf);
-    else if (n <= 1024) b2rf_batch_launch<1024, 512>(device, st, n, count, b, rf);
-    else b2rf_batch_launch<2048, 512>(device, st, n, count, b, rf);
+    const int grid = b2rf_batch_grid(device, n, count);
+    DevBuf work((size_t)grid * 2 * 8 * n * sizeof(double2));
+    b2rf_batch_enqueue(st, grid, n, count, db.as<double2>(), work.as<double2>(), drf.as<double2>());
     MBFIR_HIP(hipMemcpyAsync(h.data(), drf.p, tot * sizeof(double2), hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipStreamSynchronize(st));                  // the buffers are freed on return
     MBFIR_HIP(hipGetLastError());
     unpack_cplx(tot, h.data(), rf_re, rf_im);
 }
@@ -640,29 +618,6 @@ void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double
 // s is the beta of a hard pulse of angle |theta| about the axis arg theta; for a real theta it is dzepse's sin(conj(theta) / 2).
 // dzepse's own stage-1 angles are not real (its spatial profile carries a half-sample phase ramp), and there the two forms differ
 // by up to 4e-3 of max|rf|: `literal` selects dzepse's form, for parity with it.
-
-// The tiers of slr_b2rf_batch_run, split into sizing and an enqueue on a caller-owned scratch (no synchronisation).
-template <int MAXN, int NT>
-static int b2rf_tier_grid(int device, int count) {
-    int ncu = 0, per = 0;
-    MBFIR_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device));
-    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_b2rf_batch<MAXN, NT>, NT, 0));
-    return std::max(1, std::min(count, std::max(per, 1) * ncu));
-}
-static int b2rf_batch_grid(int device, int n, int count) {
-    if (n <= 128) return b2rf_tier_grid<128, 256>(device, count);
-    if (n <= 512) return b2rf_tier_grid<512, 256>(device, count);
-    if (n <= 1024) return b2rf_tier_grid<1024, 512>(device, count);
-    return b2rf_tier_grid<2048, 512>(device, count);
-}
-// work: grid x 2 (8 n) double2
-static void b2rf_batch_enqueue(hipStream_t st, int grid, int n, int count, const double2* b, double2* work, double2* rf) {
-    if (n <= 128) hipLaunchKernelGGL((k_b2rf_batch<128, 256>), dim3(grid), dim3(256), 0, st, b, n, count, work, rf);
-    else if (n <= 512) hipLaunchKernelGGL((k_b2rf_batch<512, 256>), dim3(grid), dim3(256), 0, st, b, n, count, work, rf);
-    else if (n <= 1024) hipLaunchKernelGGL((k_b2rf_batch<1024, 512>), dim3(grid), dim3(512), 0, st, b, n, count, work, rf);
-    else hipLaunchKernelGGL((k_b2rf_batch<2048, 512>), dim3(grid), dim3(512), 0, st, b, n, count, work, rf);
-    MBFIR_HIP(hipGetLastError());
-}
 
 // Middle stage, one workgroup per (matrix, column) w = c n + j (grid-stride).  fftcp pads s with m/2 zeros on each side, so the
 // middle m samples of its centred 2m-point DFT are the direct centred sum over the m non-zero inputs:
@@ -788,7 +743,7 @@ void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, cons
 }
 
 // 2D forward simulation, abrm.m:39-57: one thread per (x_k, y_j), output index k ny + j; one rotation about
-// (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample, k_abr's mode-0 arithmetic.  rf, gx, gy staged through LDS 256 samples at a time;
+// (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample: abr_step in mode 0.  rf, gx, gy staged through LDS 256 samples at a time;
 // gx null = 2 pi / n per sample, gy null = 0.
 __global__ __launch_bounds__(256) void k_abr2(const double* __restrict__ rf_il, const double* __restrict__ gx,
                                               const double* __restrict__ gy, int n, const double* __restrict__ x, int nx,
@@ -813,19 +768,8 @@ __global__ __launch_bounds__(256) void k_abr2(const double* __restrict__ rf_il, 
         __syncthreads();
         const int cnt = min(256, n - m0);
         for (int q = 0; q < cnt; ++q) {
-            const double2 r = srf[q];
-            const double om = xv * sgx[q] + yv * sgy[q];
-            const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
-            double sn, cs;
-            sincos(0.5 * phi, &sn, &cs);
-            const double inv = phi > 0 ? sn / phi : 0.0;
-            const double2 av = make_double2(cs, -om * inv);
-            const double2 bv = make_double2(r.y * inv, -r.x * inv);                 // -i (n1 + i n2) sin
-            const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
-                                            av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
-            const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
-                                            bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
-            a = an; b = bn;
+            const CayleyKlein ck = abr_step(0, srf[q], xv * sgx[q] + yv * sgy[q], a, b);
+            a = ck.a; b = ck.b;
         }
     }
     if (live) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
@@ -915,26 +859,38 @@ void abr2_run(int device, void* stream, int n, const double* rf_re, const double
     unpack_cplx(P, ob.data(), b_re, b_im);
 }
 
+constexpr double TWOPI_REF = 6.283185;                      // blochC.c:6, the reference's truncated constant
+// s[0 .. 5]: entries 2 .. 7 of sample t's step row, as bloch_run and bloch_batch_run both stage them
+static void bloch_step_row(const double* gx, const double* gy, const double* gz, size_t t, double gamma, double dt, double t1,
+                           double t2, double* s) {
+    s[0] = (gx ? gx[t] : 0.0) * gamma * dt;                 // gradient terms of rotz (blochC.c:317-319, :330)
+    s[1] = (gy ? gy[t] : 0.0) * gamma * dt;
+    s[2] = (gz ? gz[t] : 0.0) * gamma * dt;
+    s[3] = TWOPI_REF * dt;
+    s[4] = std::exp(-dt / t1);                              // :460-464
+    s[5] = std::exp(-dt / t2);
+}
+// pos3 = (x, y, z) per position, a null axis as zeros
+static void bloch_fill_pos3(size_t npos, const double* dx, const double* dy, const double* dz, double* pos) {
+    for (size_t p = 0; p < npos; ++p) {
+        pos[3 * p] = dx ? dx[p] : 0.0; pos[3 * p + 1] = dy ? dy[p] : 0.0; pos[3 * p + 2] = dz ? dz[p] : 0.0;
+    }
+}
+
 void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
                const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
                const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const double TWOPI_REF = 6.283185;                       // blochC.c:6, the reference's truncated constant
     const size_t nt = (size_t)ntime, npair = (size_t)nfreq * npos, nout = npair * ((mode & 2) ? nt : 1);
     std::vector<double> step(nt * 8), pos(3 * (size_t)npos);
     for (size_t t = 0; t < nt; ++t) {
         const double dt = tsteps[t];
         step[8 * t] = -b1_re[t] * gamma * dt;                // rotx  (blochC.c:332)
         step[8 * t + 1] = b1_im[t] * gamma * dt;             // roty  (:333)
-        step[8 * t + 2] = (gx ? gx[t] : 0.0) * gamma * dt;   // gradient terms of rotz (:317-319, :330)
-        step[8 * t + 3] = (gy ? gy[t] : 0.0) * gamma * dt;
-        step[8 * t + 4] = (gz ? gz[t] : 0.0) * gamma * dt;
-        step[8 * t + 5] = TWOPI_REF * dt;
-        step[8 * t + 6] = std::exp(-dt / t1);                // :460-464
-        step[8 * t + 7] = std::exp(-dt / t2);
+        bloch_step_row(gx, gy, gz, t, gamma, dt, t1, t2, &step[8 * t + 2]);
     }
-    for (int p = 0; p < npos; ++p) { pos[3 * p] = dx ? dx[p] : 0.0; pos[3 * p + 1] = dy ? dy[p] : 0.0; pos[3 * p + 2] = dz ? dz[p] : 0.0; }
+    bloch_fill_pos3(npos, dx, dy, dz, pos.data());
     DevBuf dstep(step.size() * 8), dpos(pos.size() * 8), ddf((size_t)nfreq * 8), dmx(nout * 8), dmy(nout * 8), dmz(nout * 8);
     MBFIR_HIP(hipMemcpyAsync(dstep.p, step.data(), step.size() * 8, hipMemcpyHostToDevice, st));
     MBFIR_HIP(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 8, hipMemcpyHostToDevice, st));
@@ -992,7 +948,6 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
                      double* my, double* mz) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const double TWOPI_REF = 6.283185;                       // blochC.c:6, as bloch_run
     std::vector<BlochPulseDev> pd(npulse);
     std::vector<int> nt(npulse);
     std::vector<long> npair(npulse);
@@ -1025,18 +980,12 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
             double* s = in + BLOCH_IN * t;
             s[0] = b1_re[t];
             s[1] = b1_im[t];
-            s[2] = (gx ? gx[t] : 0.0) * g * dt;                  // bloch_run's gradient terms of rotz
-            s[3] = (gy ? gy[t] : 0.0) * g * dt;
-            s[4] = (gz ? gz[t] : 0.0) * g * dt;
-            s[5] = TWOPI_REF * dt;
-            s[6] = std::exp(-dt / t1[p]);
-            s[7] = std::exp(-dt / t2[p]);
+            bloch_step_row(gx, gy, gz, t, g, dt, t1[p], t2[p], s + 2);
             s[8] = dt;
         }
     }
     std::copy(df, df + F, S.at<double>(o_df));
-    double* pos = S.at<double>(o_pos);
-    for (long i = 0; i < NP; ++i) { pos[3 * i] = dx ? dx[i] : 0.0; pos[3 * i + 1] = dy ? dy[i] : 0.0; pos[3 * i + 2] = dz ? dz[i] : 0.0; }
+    bloch_fill_pos3(NP, dx, dy, dz, S.at<double>(o_pos));
     std::copy(scales, scales + nscale, S.at<double>(o_sc));
     double* m0 = S.at<double>(o_m0);
     for (int p = 0; p < npulse; ++p) {
