@@ -298,7 +298,13 @@ int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1
  *   weight per sample; NULL = 2 pi / n_p for every sample of pulse p, mbfir_abr's default, which a caller with g for only some
  *   pulses writes for the others); nxgrid = 1 or npulse, xoff (nxgrid + 1) into x; scale s multiplies rf; mode: mbfir_abr's (0
  *   abrm.m, 1 the hard-pulse model).  a / b (re, im planes): pulse p from sum_{q < p} nscale nx_q, (scale, position) row-major.
- * Both return MBFIR_E_ARG, with the reason in mbfir_last_error and no device work done, for: npulse < 1, nscale < 1, a pulse with
+ * mbfir_abr2_batch: mbfir_abr2 for every (pulse p, scale s), in both models.  roff (npulse + 1) into rf_re / rf_im and gx / gy (one
+ *   weight each per sample; gx NULL = 2 pi / n_p and gy NULL = 0 for every sample, mbfir_abr2's defaults); nxgrid and nygrid = 1
+ *   or npulse each, xoff (nxgrid + 1) into x and yoff (nygrid + 1) into y; scale s multiplies rf; mode 0: abrm.m:39-57, one
+ *   rotation about (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample, with mbfir_abr2's bits; mode 1: mbfir_abr's hard-pulse model
+ *   with the precession angle x_k gx_m + y_j gy_m.  a / b (re, im planes): pulse p from sum_{q < p} nscale nx_q ny_q, laid out
+ *   (scale, x, y) row-major: point (s, k, j) at ((s nx_p + k) ny_p + j).
+ * All three return MBFIR_E_ARG, with the reason in mbfir_last_error and no device work done, for: npulse < 1, nscale < 1, a pulse with
  *   no samples, an offset table that does not start at 0 or does not ascend, an empty grid, a grid count neither 1 nor npulse, a
  *   tsteps length neither 1 nor ntime_p, t1 or t2 not positive, a mode out of range, a required array NULL, and a total output
  *   or workgroup count that overflows. */
@@ -310,8 +316,11 @@ int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double
 int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
                     int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
                     double* a_im, double* b_re, double* b_im);
-/* mbfir_test_sim_blocks (host only): the workgroup table of the two calls above for pulses of ntime[p] samples and npoint[p]
- *   points ((frequency, position) pairs, or positions) at nscale scales: 4 ints (pulse, scale, chunk, 0) per workgroup in launch
+int mbfir_abr2_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                     const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                     int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im);
+/* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]
+ *   points ((frequency, position) pairs, positions, or nx ny points) at nscale scales: 4 ints (pulse, scale, chunk, 0) per workgroup in launch
  *   order into out (may be NULL).  Returns the number of workgroups; -1 for npulse or nscale < 1, an ntime or npoint < 1, or a
  *   table of more than 2^31 - 1 workgroups. */
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out);

@@ -126,6 +126,8 @@ SYMBOLS = {
                                     C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "mbfir_abr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp,
                                   _dp]),
+    "mbfir_abr2_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int, _dp,
+                                   C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                  C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
@@ -682,6 +684,8 @@ from .slrclassic import (remez, remez_batch, fmp, msinc, firls_lp, dzlp, dzls, d
 from . import epse          # noqa: E402  (dzepse.m spectral-spatial pulses and its helpers; device b2rf_batch)
 from .epse import (fftc, fftcp, dzbeta, verse, versec, ab2ex, ab2se, ab2inv, ab2sat, ab2st, dzepse,   # noqa: E402
                    dzepse_batch)
+from . import spiral        # noqa: E402  (dz2d.m / csg.m spiral 2D pulses and the k-space helpers; host only)
+from .spiral import csg, dz2d, dz2d_batch, ktog, ktos, gt2cm   # noqa: E402
 from . import ssmb          # noqa: E402  (multiband spectral-spatial pulses: dzrf_mb's spectral beta, device 2D SLR)
 from .ssmb import dzss_mb, dzss_mb_batch, fold_bands   # noqa: E402
 # `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
@@ -928,7 +932,7 @@ def bloch(b1, gr, tp, t1, t2, df, dp, mode=0, mx=None, my=None, mz=None, nucleus
     return tuple(o.reshape(shape) for o in out)
 
 
-# ---- batched simulators: many pulses x transmit-gain scales in one launch (mbfir_bloch_batch, mbfir_abr_batch) ----------------
+# ---- batched simulators: many pulses x transmit-gain scales in one launch (mbfir_bloch_batch, mbfir_abr[2]_batch) -------------
 def _offsets(lengths):
     """offset table of a concatenated list (C long): 0, then the running sums"""
     return np.ascontiguousarray(np.concatenate([[0], np.cumsum(np.asarray(lengths, dtype=np.int64))]).astype(np.int64))
@@ -1086,6 +1090,68 @@ def abr_batch(pulses, x, *, scales=(1.0,), hard_pulse=False, convention="abrm", 
     if convention == "abr":
         b_all = -np.conj(b_all)
     return [(a_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q]), b_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q])) for q in range(P)]
+
+
+def _grids(v, npulse, who, name):
+    """One array per pulse (a Python list of arrays, which must then have npulse entries) or one array shared by every pulse."""
+    if isinstance(v, list) and len(v) > 0 and all(np.ndim(e) >= 1 for e in v):
+        if len(v) != npulse:
+            raise ValueError("%s: %s has %d grids for %d pulses" % (who, name, len(v), npulse))
+        vs = [_vec(e) for e in v]
+    else:
+        vs = [_vec(v)]
+    if any(len(e) == 0 for e in vs):
+        raise ValueError("%s: an empty %s" % (who, name))
+    return vs
+
+
+def abr2_batch(pulses, x, y, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """Many 2D `abrm(rf, g, x, y)` / `abr` simulations in one launch (mbfir_abr2_batch): every pulse at every scale.  Each pulse is
+    rf (radians per sample; 2 pi / n per sample along x as in abrm) or a tuple (rf, g) with abrm's complex g (Re g the x gradient,
+    Im g the y one).  x and y: each one array shared by every pulse, or a Python list of one array per pulse.  Scale s multiplies
+    rf.  hard_pulse: the hard-pulse model (free precession by x Re g + y Im g, then the hard pulse of the sample) that the 2D
+    `abrm` does not offer; convention 'abr' returns abr.m's b = -conj(b).  Returns a list of (a, b) per pulse, each of shape
+    (S, nx, ny).  Without hard_pulse the bits are those of `abrm(rf * s, g, x, y)`."""
+    pulses, sc = list(pulses), _vec(scales)
+    if not pulses:
+        raise ValueError("abr2_batch: no pulses")
+    if len(sc) == 0:
+        raise ValueError("abr2_batch: the scale list is empty")
+    if convention not in ("abrm", "abr"):
+        raise ValueError("abr2_batch: convention must be 'abrm' or 'abr'")
+    P, S = len(pulses), len(sc)
+    rfs, gs = [], []
+    for q, p in enumerate(pulses):
+        rf, g = p if isinstance(p, tuple) else (p, None)
+        rf = np.asarray(rf, dtype=np.complex128).ravel()
+        n = len(rf)
+        if n == 0:
+            raise ValueError("abr2_batch: pulse %d has no samples" % q)
+        g = np.full(n, 2.0 * np.pi / n + 0j) if g is None else np.asarray(g, dtype=np.complex128).ravel()   # abrm's default
+        if len(g) != n:
+            raise ValueError("abr2_batch: g of pulse %d must have one entry per rf sample" % q)
+        rfs.append(rf)
+        gs.append(g)
+    xs, ys = _grids(x, P, "abr2_batch", "x"), _grids(y, P, "abr2_batch", "y")
+    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
+    ny = [len(ys[0 if len(ys) == 1 else q]) for q in range(P)]
+    ooff = _offsets([S * k * j for k, j in zip(nx, ny)])
+    out = [np.zeros(int(ooff[-1])) for _ in range(4)]
+    rf, g = np.concatenate(rfs), np.concatenate(gs)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_abr2_batch(ctx._h, P, _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
+                                         _ptr(_vec(g.real)), _ptr(_vec(g.imag)), len(xs), _lptr(_offsets([len(v) for v in xs])),
+                                         _ptr(_vec(np.concatenate(xs))), len(ys), _lptr(_offsets([len(v) for v in ys])),
+                                         _ptr(_vec(np.concatenate(ys))), S, _ptr(sc), 1 if hard_pulse else 0,
+                                         *[_ptr(o) for o in out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    a_all, b_all = out[0] + 1j * out[1], out[2] + 1j * out[3]
+    if convention == "abr":
+        b_all = -np.conj(b_all)
+    return [(a_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q], ny[q]), b_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q], ny[q]))
+            for q in range(P)]
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

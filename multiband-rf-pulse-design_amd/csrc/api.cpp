@@ -885,6 +885,37 @@ int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* 
                                  mode, a_re, a_im, b_re, b_im));
 }
 
+int mbfir_abr2_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                     const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                     int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "abr2_batch: " + why; return MBFIR_E_ARG; };
+    if (npulse < 1) return bad("no pulses");
+    if (nscale < 1) return bad("the scale list is empty");
+    if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
+    if ((nxgrid != 1 && nxgrid != npulse) || (nygrid != 1 && nygrid != npulse)) return bad("nxgrid and nygrid must be 1 or npulse");
+    if (!roff || !rf_re || !rf_im || !xoff || !x || !yoff || !y || !scales || !a_re || !a_im || !b_re || !b_im)
+        return bad("a required array is null");
+    if (const char* why = sim_offsets_bad(roff, npulse)) {
+        for (int p = 0; p < npulse && roff[0] == 0; ++p) {
+            if (roff[p + 1] < roff[p]) break;
+            if (roff[p + 1] == roff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
+        }
+        return bad(std::string("inconsistent offsets: roff ") + why);
+    }
+    if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
+    if (const char* why = sim_offsets_bad(yoff, nygrid)) return bad(std::string("inconsistent offsets: yoff ") + why);
+    std::vector<long> npoint(npulse), ntout(npulse, 1);
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p, yg = nygrid == 1 ? 0 : p;
+        npoint[p] = (xoff[xg + 1] - xoff[xg]) * (yoff[yg + 1] - yoff[yg]);      // each factor < 2^31
+    }
+    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, abr2_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid, yoff,
+                                  y, nscale, scales, mode, a_re, a_im, b_re, b_im));
+}
+
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {
     if (npulse < 1 || nscale < 1 || !ntime || !npoint) return -1;
     std::vector<long> ntout(npulse, 1);

@@ -29,9 +29,9 @@ void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, cons
 void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
                const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
                const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
-// Work split of the batched simulators (slr.hip k_bloch_batch, k_abr_batch): one 256-thread workgroup per (pulse, scale, chunk of
+// Work split of the batched simulators (slr.hip k_bloch_batch, k_abr_batch, k_abr2_batch): one 256-thread workgroup per (pulse, scale, chunk of
 // 256 points); pulses in descending order of ntime (ties in list order), then scale, then chunk.  npoint: points per pulse
-// ((frequency, position) pairs, or positions).  Returns the table's length; writes the table to out when out is not null.
+// ((frequency, position) pairs, positions, or (x, y) points).  Returns the table's length; writes the table to out when out is not null.
 struct SimBlock {
     int pulse, scale, chunk, pad;
 };
@@ -46,6 +46,12 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
 void abr_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
                    int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
                    double* a_im, double* b_re, double* b_im);
+// Batched 2D forward simulation (slr.hip k_abr2_batch): abr2_run's points for every (pulse, scale), mode 0 abrm.m, 1 the hard-pulse
+// model with the precession angle x gx + y gy.  Offsets and layout as mbfir_abr2_batch documents them; sim_block_table's npoint is
+// nx ny.
+void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                    const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                    int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

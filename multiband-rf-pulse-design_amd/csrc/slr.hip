@@ -3,8 +3,8 @@
 //   b2a   : DFTs of length blp = 8 n (any n: direct O(blp^2) DFT, twiddles by rotation recurrence with an
 //           exact sincospi seed every 256 terms), elementwise steps in between
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
-// k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr / k_abr_batch / k_abr2 share abr_step: one definition each, so those
-// batch kernels equal their single-pulse twins by construction.  k_bloch / k_bloch_batch still hold the same loop nest twice (see
+// k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr / k_abr_batch / k_abr2 / k_abr2_batch share abr_step: one definition each,
+// so those batch kernels equal their single-pulse twins by construction.  k_bloch / k_bloch_batch still hold the same loop nest twice (see
 // the note above k_bloch_batch).
 #include "dev_common.h"
 #include "pulse.h"
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il,
 //   mode 1: the hard-pulse model the inverse SLR transform inverts exactly -- free precession by x g_m on beta, then
 //           the hard pulse of the sample
 // abr_step is one sample of either model for one position (r: the rf sample, om: the precession angle of the sample; mode is
-// uniform over the workgroup).  k_abr, k_abr_batch and k_abr2 (mode 0, om = x gx + y gy) all step through it.  The state goes in
+// uniform over the workgroup).  k_abr, k_abr_batch, k_abr2 (mode 0, om = x gx + y gy) and k_abr2_batch all step through it.  The state goes in
 // and comes back by value: through references the kernels compile to other fused products (the compiler then promotes a and b to
 // registers only after inlining, in another order), and the results differ from before in the last bits.
 struct CayleyKlein {
@@ -779,6 +779,54 @@ static void slr_abr2_launch(const double* rf_il, const double* gx, const double*
     hipLaunchKernelGGL(k_abr2, dim3(cdiv((long)nx * ny, 256)), dim3(256), 0, st, rf_il, gx, gy, n, x, nx, y, ny, a_il, b_il);
 }
 
+// k_abr2 over the batch, both models: one workgroup per (pulse, scale, chunk of 256 points) through the block table of the other
+// batched simulators, point i = k ny + j at (x_k, y_j).  rf (interleaved) is scaled while it is staged; gx / gy hold one weight per
+// sample of every pulse (the host writes 2 pi / n and 0 where a pulse has none: the values k_abr2 forms for null gx / gy).  mode 1
+// is the hard-pulse model with the precession angle x gx + y gy.  Output: S x nx x ny per pulse, scale-major.
+// The precession angle is written as the fused form k_abr2 compiles to, fma(x, gx, y gy): with the runtime mode the compiler may
+// choose the other product for the fused multiply-add, and mode 0 has to give k_abr2's bits.
+struct Abr2PulseDev {
+    long r_off, x_off, y_off, o_off;     // first rf / gx / gy sample, first x, first y, first output entry
+    int n, nx, ny, pad;
+};
+__global__ __launch_bounds__(256) void k_abr2_batch(const double* __restrict__ rf_il, const double* __restrict__ gx,
+                                                    const double* __restrict__ gy, const double* __restrict__ x,
+                                                    const double* __restrict__ y, const double* __restrict__ scales,
+                                                    const Abr2PulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                    int mode, double* __restrict__ a_il, double* __restrict__ b_il) {
+    __shared__ double2 srf[256];
+    __shared__ double sgx[256], sgy[256];
+    const SimBlock bk = blocks[blockIdx.x];
+    const Abr2PulseDev P = pulses[bk.pulse];
+    const double sc = scales[bk.scale];
+    const int n = P.n, ny = P.ny;
+    const long i = (long)bk.chunk * 256 + threadIdx.x, tot = (long)P.nx * ny;
+    const bool live = i < tot;
+    const long kx = live ? i / ny : 0;
+    const double xv = x[P.x_off + kx], yv = y[P.y_off + (live ? i - kx * ny : 0)];
+    double2 a = make_double2(1, 0), b = make_double2(0, 0);
+    for (int m0 = 0; m0 < n; m0 += 256) {
+        __syncthreads();
+        const int mm = m0 + threadIdx.x;
+        if (mm < n) {
+            const long t = P.r_off + mm;
+            srf[threadIdx.x] = make_double2(rf_il[2 * t] * sc, rf_il[2 * t + 1] * sc);
+            sgx[threadIdx.x] = gx[t];
+            sgy[threadIdx.x] = gy[t];
+        }
+        __syncthreads();
+        const int cnt = min(256, n - m0);
+        for (int q = 0; q < cnt; ++q) {
+            const CayleyKlein ck = abr_step(mode, srf[q], fma(xv, sgx[q], yv * sgy[q]), a, b);
+            a = ck.a; b = ck.b;
+        }
+    }
+    if (live) {
+        const long o = P.o_off + (long)bk.scale * tot + i;
+        a_il[2 * o] = a.x; a_il[2 * o + 1] = a.y; b_il[2 * o] = b.x; b_il[2 * o + 1] = b.y;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_b2a / mbfir_ab2rf / mbfir_b2rf, mbfir_abr, mbfir_abr2 and mbfir_bloch (pulse.h; arguments checked).
 
@@ -908,7 +956,7 @@ void bloch_run(int device, void* stream, int ntime, const double* b1_re, const d
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side of mbfir_bloch_batch / mbfir_abr_batch (arguments checked by api.cpp): every input in one staging buffer of
+// Host side of mbfir_bloch_batch / mbfir_abr_batch / mbfir_abr2_batch (arguments checked by api.cpp): every input in one staging buffer of
 // 256-byte-aligned sections, one upload, one launch, one download.
 
 long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out) {
@@ -1053,6 +1101,61 @@ void abr_batch_run(int device, void* stream, int npulse, const long* roff, const
     hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_rf),
                        reinterpret_cast<const double*>(base + o_g), reinterpret_cast<const double*>(base + o_x),
                        reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const AbrPulseDev*>(base + o_pd),
+                       reinterpret_cast<const SimBlock*>(base + o_bk), mode, reinterpret_cast<double*>(out),
+                       reinterpret_cast<double*>(out + O));
+    MBFIR_HIP(hipGetLastError());
+    std::vector<double2> h(2 * (size_t)O);
+    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 16, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipStreamSynchronize(st));
+    MBFIR_HIP(hipGetLastError());
+    unpack_cplx(O, h.data(), a_re, a_im);
+    unpack_cplx(O, h.data() + O, b_re, b_im);
+}
+
+void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                    const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                    int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    std::vector<Abr2PulseDev> pd(npulse);
+    std::vector<int> nt(npulse);
+    std::vector<long> npt(npulse);
+    long O = 0;                                              // output entries of a (and of b)
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p, yg = nygrid == 1 ? 0 : p;
+        pd[p] = Abr2PulseDev{roff[p], xoff[xg], yoff[yg], O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg]),
+                             int(yoff[yg + 1] - yoff[yg]), 0};
+        nt[p] = pd[p].n;
+        npt[p] = (long)pd[p].nx * pd[p].ny;
+        O += nscale * npt[p];
+    }
+    const long R = roff[npulse], X = xoff[nxgrid], Y = yoff[nygrid];
+    const long nblk = sim_block_table(npulse, nt.data(), npt.data(), nscale, nullptr);
+    Staging S;
+    const size_t o_rf = S.add(R * 16), o_gx = S.add(R * 8), o_gy = S.add(R * 8), o_x = S.add(X * 8), o_y = S.add(Y * 8),
+                 o_sc = S.add((size_t)nscale * 8), o_pd = S.add(npulse * sizeof(Abr2PulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
+    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
+    double* gxw = S.at<double>(o_gx);
+    double* gyw = S.at<double>(o_gy);
+    for (int p = 0; p < npulse; ++p)
+        for (long t = roff[p]; t < roff[p + 1]; ++t) {
+            gxw[t] = gx ? gx[t] : 2.0 * M_PI / pd[p].n;         // k_abr2's weights for null gx / gy
+            gyw[t] = gy ? gy[t] : 0.0;
+        }
+    std::copy(x, x + X, S.at<double>(o_x));
+    std::copy(y, y + Y, S.at<double>(o_y));
+    std::copy(scales, scales + nscale, S.at<double>(o_sc));
+    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(Abr2PulseDev));
+    sim_block_table(npulse, nt.data(), npt.data(), nscale, S.at<SimBlock>(o_bk));
+    DevBuf dbuf(o_out + 4 * (size_t)O * 8);
+    char* base = dbuf.as<char>();
+    double2* out = reinterpret_cast<double2*>(base + o_out);    // a: O entries, then b: O entries
+    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_abr2_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_rf),
+                       reinterpret_cast<const double*>(base + o_gx), reinterpret_cast<const double*>(base + o_gy),
+                       reinterpret_cast<const double*>(base + o_x), reinterpret_cast<const double*>(base + o_y),
+                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const Abr2PulseDev*>(base + o_pd),
                        reinterpret_cast<const SimBlock*>(base + o_bk), mode, reinterpret_cast<double*>(out),
                        reinterpret_cast<double*>(out + O));
     MBFIR_HIP(hipGetLastError());
