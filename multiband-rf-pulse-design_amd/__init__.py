@@ -892,6 +892,20 @@ GAMMA_C13 = 6726.1          # rad/s/G, blochC.c:5
 GAMMA_H1 = 26754.0          # blochH.c:6
 
 
+def _bloch_pulse(b1, gr, tp, nucleus):
+    """One pulse as bloch takes it -> b1 (ntime,), gr (ntime, axes), tp as one interval or ntime intervals, gamma."""
+    b1 = np.asarray(b1, dtype=np.complex128).ravel()
+    nt = len(b1)
+    gr = np.zeros((nt, 1)) if gr is None else np.asarray(gr, dtype=np.float64).reshape(nt, -1)
+    tp = np.asarray(tp, dtype=np.float64).ravel()
+    if tp.size != 1 and tp.size != nt:
+        raise MbfirError("Time-point length differs from B1 length")
+    if tp.size > 1:
+        iv = np.diff(np.concatenate([[0.0], tp]))
+        tp = iv if np.all(iv > 0) else tp                       # increasing end times -> intervals (times2intervals)
+    return b1, gr, tp, GAMMA_C13 if nucleus == "C-13" else GAMMA_H1 if nucleus == "H-1" else float(nucleus)
+
+
 def bloch(b1, gr, tp, t1, t2, df, dp, mode=0, mx=None, my=None, mz=None, nucleus="C-13", ctx=None):
     """[mx, my, mz] = bloch(b1, gr, tp, t1, t2, df, dp, mode, mx, my, mz) of bloch_simulation/bloch.m:1-44 on the device
     (blochC for nucleus 'C-13', blochH for 'H-1', as sim_rf_spectral.m:53-60 picks them).  b1 complex (Gauss), gr (ntime,)
@@ -899,18 +913,10 @@ def bloch(b1, gr, tp, t1, t2, df, dp, mode=0, mx=None, my=None, mz=None, nucleus
     (blochC.c:649-681), df Hz, dp (npos,) or (npos, 1..3) cm.  Returns arrays of shape (nfreq, npos) or, with mode & 2,
     (nfreq, npos, ntime)."""
     ctx = ctx or get_context()
-    b1 = np.asarray(b1, dtype=np.complex128).ravel()
+    b1, gr, tp, gamma = _bloch_pulse(b1, gr, tp, nucleus)
     nt = len(b1)
-    gr = np.zeros((nt, 1)) if gr is None else np.asarray(gr, dtype=np.float64).reshape(nt, -1)
     g3 = [_vec(gr[:, i]) if i < gr.shape[1] else None for i in range(3)]
-    tp = np.asarray(tp, dtype=np.float64).ravel()
-    if tp.size == 1:
-        ts = np.full(nt, tp[0])
-    elif tp.size != nt:
-        raise MbfirError("Time-point length differs from B1 length")
-    else:
-        iv = np.diff(np.concatenate([[0.0], tp]))
-        ts = iv if np.all(iv > 0) else tp                       # increasing end times -> intervals (times2intervals)
+    ts = np.full(nt, tp[0]) if tp.size == 1 else tp
     df = _vec(df)
     dp = np.asarray(dp, dtype=np.float64)
     dp = dp.reshape(-1, 1) if dp.ndim < 2 else dp
@@ -922,7 +928,6 @@ def bloch(b1, gr, tp, t1, t2, df, dp, mode=0, mx=None, my=None, mz=None, nucleus
         o = np.zeros((nf * npos, ntout))
         o[:, 0] = dflt if init is None or np.size(init) != nf * npos else np.asarray(init, dtype=np.float64).ravel()
         out.append(np.ascontiguousarray(o))
-    gamma = GAMMA_C13 if nucleus == "C-13" else GAMMA_H1 if nucleus == "H-1" else float(nucleus)
     nul = C.cast(None, _dp)
     _check(ctx, load_library().mbfir_bloch(ctx._h, nt, _ptr(_vec(b1.real)), _ptr(_vec(b1.imag)),
                                            *[_ptr(g) if g is not None else nul for g in g3], _ptr(_vec(ts)), float(t1), float(t2),
@@ -983,25 +988,17 @@ def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
     P, S, mode = len(pulses), len(sc), int(mode)
     b1s, grs, tss, t1s, t2s, gams = [], [], [], [], [], []
     for q, (b1, gr, tp, t1, t2, nucleus) in enumerate(pulses):
-        b1 = np.asarray(b1, dtype=np.complex128).ravel()
-        nt = len(b1)
-        if nt == 0:
+        if np.size(b1) == 0:
             raise ValueError("bloch_batch: pulse %d has no samples" % q)
-        gr = np.zeros((nt, 1)) if gr is None else np.asarray(gr, dtype=np.float64).reshape(nt, -1)
+        b1, gr, tp, gamma = _bloch_pulse(b1, gr, tp, nucleus)
         if gr.shape[1] > 3:
             raise ValueError("bloch_batch: pulse %d has more than 3 gradient axes" % q)
-        tp = np.asarray(tp, dtype=np.float64).ravel()
-        if tp.size != 1 and tp.size != nt:
-            raise MbfirError("Time-point length differs from B1 length")
-        if tp.size > 1:
-            iv = np.diff(np.concatenate([[0.0], tp]))
-            tp = iv if np.all(iv > 0) else tp                      # increasing end times -> intervals, as bloch
         b1s.append(b1)
         grs.append(gr)
         tss.append(tp)
         t1s.append(float(t1))
         t2s.append(float(t2))
-        gams.append(GAMMA_C13 if nucleus == "C-13" else GAMMA_H1 if nucleus == "H-1" else float(nucleus))
+        gams.append(gamma)
     dfs = [_vec(v) for v in _per_pulse(df, P)]
     dps = []
     for v in _per_pulse(dp, P):
@@ -1047,6 +1044,19 @@ def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
     return res
 
 
+def _rf_g(pulse, q, who, gtype):
+    """A pulse of abr_batch / abr2_batch, rf or (rf, g) -> rf and g of dtype gtype, abrm's 2 pi / n per sample where it has none."""
+    rf, g = pulse if isinstance(pulse, tuple) else (pulse, None)
+    rf = np.asarray(rf, dtype=np.complex128).ravel()
+    n = len(rf)
+    if n == 0:
+        raise ValueError("%s: pulse %d has no samples" % (who, q))
+    g = np.full(n, 2.0 * np.pi / n, dtype=gtype) if g is None else np.asarray(g, dtype=gtype).ravel()
+    if len(g) != n:
+        raise ValueError("%s: g of pulse %d must have one entry per rf sample" % (who, q))
+    return rf, g
+
+
 def abr_batch(pulses, x, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
     """Many `abrm` / `abr` simulations in one launch (mbfir_abr_batch): every pulse at every scale.  Each pulse is rf (radians per
     sample; 2 pi / n per sample as in abrm) or a tuple (rf, g) with abrm's per-sample g.  x: one array shared by every pulse, or a
@@ -1060,18 +1070,7 @@ def abr_batch(pulses, x, *, scales=(1.0,), hard_pulse=False, convention="abrm", 
     if convention not in ("abrm", "abr"):
         raise ValueError("abr_batch: convention must be 'abrm' or 'abr'")
     P, S = len(pulses), len(sc)
-    rfs, gs = [], []
-    for q, p in enumerate(pulses):
-        rf, g = p if isinstance(p, tuple) else (p, None)
-        rf = np.asarray(rf, dtype=np.complex128).ravel()
-        n = len(rf)
-        if n == 0:
-            raise ValueError("abr_batch: pulse %d has no samples" % q)
-        g = np.full(n, 2.0 * np.pi / n) if g is None else _vec(g)        # abrm's default, as the device forms it
-        if len(g) != n:
-            raise ValueError("abr_batch: g of pulse %d must have one entry per rf sample" % q)
-        rfs.append(rf)
-        gs.append(g)
+    rfs, gs = zip(*[_rf_g(p, q, "abr_batch", np.float64) for q, p in enumerate(pulses)])
     xs = [_vec(v) for v in _per_pulse(x, P)]
     if any(len(v) == 0 for v in xs):
         raise ValueError("abr_batch: an empty x")
@@ -1120,18 +1119,7 @@ def abr2_batch(pulses, x, y, *, scales=(1.0,), hard_pulse=False, convention="abr
     if convention not in ("abrm", "abr"):
         raise ValueError("abr2_batch: convention must be 'abrm' or 'abr'")
     P, S = len(pulses), len(sc)
-    rfs, gs = [], []
-    for q, p in enumerate(pulses):
-        rf, g = p if isinstance(p, tuple) else (p, None)
-        rf = np.asarray(rf, dtype=np.complex128).ravel()
-        n = len(rf)
-        if n == 0:
-            raise ValueError("abr2_batch: pulse %d has no samples" % q)
-        g = np.full(n, 2.0 * np.pi / n + 0j) if g is None else np.asarray(g, dtype=np.complex128).ravel()   # abrm's default
-        if len(g) != n:
-            raise ValueError("abr2_batch: g of pulse %d must have one entry per rf sample" % q)
-        rfs.append(rf)
-        gs.append(g)
+    rfs, gs = zip(*[_rf_g(p, q, "abr2_batch", np.complex128) for q, p in enumerate(pulses)])
     xs, ys = _grids(x, P, "abr2_batch", "x"), _grids(y, P, "abr2_batch", "y")
     nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
     ny = [len(ys[0 if len(ys) == 1 else q]) for q in range(P)]

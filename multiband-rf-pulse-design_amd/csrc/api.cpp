@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <atomic>
 #include <condition_variable>
 #include <map>
@@ -675,15 +676,6 @@ int mbfir_b2a(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, dou
     if (!ctx || n < 1 || !b_re || !b_im || !a_re || !a_im) return MBFIR_E_ARG;
     MBFIR_TRY(ctx, slr_run(ctx->device, ctx->solver->stream(), n, b_re, b_im, nullptr, nullptr, a_re, a_im, nullptr, nullptr));
 }
-int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
-                const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos,
-                const double* dx, const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
-    if (!ctx || ntime < 1 || nfreq < 1 || npos < 1 || !b1_re || !b1_im || !tsteps || !df || !mx || !my || !mz || mode < 0 || mode > 3 ||
-        !(t1 > 0) || !(t2 > 0))
-        return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, bloch_run(ctx->device, ctx->solver->stream(), ntime, b1_re, b1_im, gx, gy, gz, tsteps, t1, t2, nfreq, df, npos, dx,
-                             dy, dz, mode, gamma, mx, my, mz));
-}
 int mbfir_ab2rf(mbfir_ctx* ctx, int n, const double* a_re, const double* a_im, const double* b_re, const double* b_im,
                 double* rf_re, double* rf_im) {
     if (!ctx || n < 1 || n > 2048 || !a_re || !a_im || !b_re || !b_im || !rf_re || !rf_im) return MBFIR_E_ARG;
@@ -692,12 +684,6 @@ int mbfir_ab2rf(mbfir_ctx* ctx, int n, const double* a_re, const double* a_im, c
 int mbfir_b2rf(mbfir_ctx* ctx, int n, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
     if (!ctx || n < 1 || n > 2048 || !b_re || !b_im || !rf_re || !rf_im) return MBFIR_E_ARG;
     MBFIR_TRY(ctx, slr_run(ctx->device, ctx->solver->stream(), n, b_re, b_im, nullptr, nullptr, nullptr, nullptr, rf_re, rf_im));
-}
-int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
-              int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
-    if (!ctx || n < 1 || nx < 1 || !rf_re || !rf_im || !x || !a_re || !a_im || !b_re || !b_im || (mode != 0 && mode != 1))
-        return MBFIR_E_ARG;
-    MBFIR_TRY(ctx, abr_run(ctx->device, ctx->solver->stream(), n, rf_re, rf_im, g, nx, x, mode, a_re, a_im, b_re, b_im));
 }
 int mbfir_b2rf_batch(mbfir_ctx* ctx, int n, int count, const double* b_re, const double* b_im, double* rf_re, double* rf_im) {
     if (!ctx) return MBFIR_E_ARG;
@@ -717,15 +703,6 @@ int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_r
         return MBFIR_E_ARG;
     }
     MBFIR_TRY(ctx, slr_slr2d_batch_run(ctx->device, ctx->solver->stream(), m, n, count, r_re, r_im, out_re, out_im, literal));
-}
-int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
-               const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
-    if (!ctx) return MBFIR_E_ARG;
-    if (n < 1 || nx < 1 || ny < 1 || (long)nx * ny > (1L << 30) || !rf_re || !rf_im || !x || !y || !a_re || !a_im || !b_re || !b_im) {
-        ctx->err = "abr2: need n, nx, ny >= 1 (nx ny <= 2^30) and the rf, x, y, a, b arrays";
-        return MBFIR_E_ARG;
-    }
-    MBFIR_TRY(ctx, abr2_run(ctx->device, ctx->solver->stream(), n, rf_re, rf_im, gx, gy, nx, x, ny, y, a_re, a_im, b_re, b_im));
 }
 int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
                       const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
@@ -789,7 +766,7 @@ int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));
 }
 
-// ---- batched simulators: every offset and size checked before any device work ---------------------------------------------
+// ---- forward simulators: every offset and size checked before any device work ----------------------------------------------
 // An offset table of count + 1 entries (count items of at least one and at most 2^31 - 1 entries each): null, or the reason.
 static const char* sim_offsets_bad(const long* off, int count) {
     if (off[0] != 0) return "does not start at 0";
@@ -813,6 +790,47 @@ static bool sim_sizes(int npulse, int nscale, const long* npoint, const long* nt
     }
     return total <= (1L << 56) && nblk <= 2147483647L;
 }
+// The offset table of the pulses themselves (named `name`): 0, or what bad returns for the first fault, an empty pulse by its index.
+static int sim_pulse_offsets_bad(const long* off, int npulse, const char* name, const std::function<int(const std::string&)>& bad) {
+    const char* why = sim_offsets_bad(off, npulse);
+    if (!why) return 0;
+    for (int p = 0; p < npulse && off[0] == 0 && off[p + 1] >= off[p]; ++p)
+        if (off[p + 1] == off[p]) return bad("pulse " + std::to_string(p) + " has no samples");
+    return bad(std::string("inconsistent offsets: ") + name + " " + why);
+}
+
+// The single-pulse calls, after their own checks, are the batch of one pulse (offset tables {0, n}) at one scale, 1.0.
+static const double SIM_ONE = 1.0;
+int mbfir_bloch(mbfir_ctx* ctx, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos,
+                const double* dx, const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
+    if (!ctx || ntime < 1 || nfreq < 1 || npos < 1 || !b1_re || !b1_im || !tsteps || !df || !mx || !my || !mz || mode < 0 || mode > 3 ||
+        !(t1 > 0) || !(t2 > 0))
+        return MBFIR_E_ARG;
+    const long toff[2] = {0, ntime}, foff[2] = {0, nfreq}, poff[2] = {0, npos}, npoint = (long)nfreq * npos, ntout = (mode & 2) ? ntime : 1;
+    if (!sim_sizes(1, 1, &npoint, &ntout)) return MBFIR_E_ARG;
+    MBFIR_TRY(ctx, bloch_batch_run(ctx->device, ctx->solver->stream(), 1, toff, b1_re, b1_im, gx, gy, gz, toff, tsteps, &t1, &t2, &gamma,
+                                   1, foff, df, 1, poff, dx, dy, dz, 1, &SIM_ONE, mode, mx, my, mz));
+}
+int mbfir_abr(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
+              int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
+    if (!ctx || n < 1 || nx < 1 || !rf_re || !rf_im || !x || !a_re || !a_im || !b_re || !b_im || (mode != 0 && mode != 1))
+        return MBFIR_E_ARG;
+    const long roff[2] = {0, n}, xoff[2] = {0, nx};
+    MBFIR_TRY(ctx, abr_batch_run(ctx->device, ctx->solver->stream(), 1, roff, rf_re, rf_im, g, 1, xoff, x, 1, &SIM_ONE, mode, a_re, a_im,
+                                 b_re, b_im));
+}
+int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
+               const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    if (n < 1 || nx < 1 || ny < 1 || (long)nx * ny > (1L << 30) || !rf_re || !rf_im || !x || !y || !a_re || !a_im || !b_re || !b_im) {
+        ctx->err = "abr2: need n, nx, ny >= 1 (nx ny <= 2^30) and the rf, x, y, a, b arrays";
+        return MBFIR_E_ARG;
+    }
+    const long roff[2] = {0, n}, xoff[2] = {0, nx}, yoff[2] = {0, ny};
+    MBFIR_TRY(ctx, abr2_batch_run(ctx->device, ctx->solver->stream(), 1, roff, rf_re, rf_im, gx, gy, 1, xoff, x, 1, yoff, y, 1, &SIM_ONE,
+                                  0, a_re, a_im, b_re, b_im));
+}
 
 int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                       const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
@@ -827,13 +845,7 @@ int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double
     if ((nfgrid != 1 && nfgrid != npulse) || (npgrid != 1 && npgrid != npulse)) return bad("nfgrid and npgrid must be 1 or npulse");
     if (!toff || !b1_re || !b1_im || !tsoff || !tsteps || !t1 || !t2 || !gamma || !foff || !df || !poff || !scales || !mx || !my || !mz)
         return bad("a required array is null");
-    if (const char* why = sim_offsets_bad(toff, npulse)) {
-        for (int p = 0; p < npulse && toff[0] == 0; ++p) {
-            if (toff[p + 1] < toff[p]) break;
-            if (toff[p + 1] == toff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
-        }
-        return bad(std::string("inconsistent offsets: toff ") + why);
-    }
+    if (const int e = sim_pulse_offsets_bad(toff, npulse, "toff", bad)) return e;
     if (tsoff[0] != 0) return bad("inconsistent offsets: tsoff does not start at 0");
     for (int p = 0; p < npulse; ++p) {
         const long nt = toff[p + 1] - toff[p], nts = tsoff[p + 1] - tsoff[p];
@@ -866,13 +878,7 @@ int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* 
     if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
     if (nxgrid != 1 && nxgrid != npulse) return bad("nxgrid must be 1 or npulse");
     if (!roff || !rf_re || !rf_im || !xoff || !x || !scales || !a_re || !a_im || !b_re || !b_im) return bad("a required array is null");
-    if (const char* why = sim_offsets_bad(roff, npulse)) {
-        for (int p = 0; p < npulse && roff[0] == 0; ++p) {
-            if (roff[p + 1] < roff[p]) break;
-            if (roff[p + 1] == roff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
-        }
-        return bad(std::string("inconsistent offsets: roff ") + why);
-    }
+    if (const int e = sim_pulse_offsets_bad(roff, npulse, "roff", bad)) return e;
     if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
     std::vector<long> npoint(npulse), ntout(npulse, 1);
     for (int p = 0; p < npulse; ++p) {
@@ -896,13 +902,7 @@ int mbfir_abr2_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double*
     if ((nxgrid != 1 && nxgrid != npulse) || (nygrid != 1 && nygrid != npulse)) return bad("nxgrid and nygrid must be 1 or npulse");
     if (!roff || !rf_re || !rf_im || !xoff || !x || !yoff || !y || !scales || !a_re || !a_im || !b_re || !b_im)
         return bad("a required array is null");
-    if (const char* why = sim_offsets_bad(roff, npulse)) {
-        for (int p = 0; p < npulse && roff[0] == 0; ++p) {
-            if (roff[p + 1] < roff[p]) break;
-            if (roff[p + 1] == roff[p]) return bad("pulse " + std::to_string(p) + " has no samples");
-        }
-        return bad(std::string("inconsistent offsets: roff ") + why);
-    }
+    if (const int e = sim_pulse_offsets_bad(roff, npulse, "roff", bad)) return e;
     if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
     if (const char* why = sim_offsets_bad(yoff, nygrid)) return bad(std::string("inconsistent offsets: yoff ") + why);
     std::vector<long> npoint(npulse), ntout(npulse, 1);

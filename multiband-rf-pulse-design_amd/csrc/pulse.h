@@ -10,12 +10,6 @@ namespace mbfir {
 // a_out (optional) receives a; rf (optional) receives ab2rf(a, b), n <= 2048.
 void slr_run(int device, void* stream, int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
              double* a_re, double* a_im, double* rf_re, double* rf_im);
-// Forward simulation (slr.hip k_abr): a, b over nx positions; g null = 2 pi / n per sample; mode 0 abrm.m, 1 hard pulse.
-void abr_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
-             int mode, double* a_re, double* a_im, double* b_re, double* b_im);
-// 2D forward simulation (slr.hip k_abr2, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j; gx null = 2 pi / n, gy null = 0.
-void abr2_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
-              const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im);
 // Batched inverse SLR (slr.hip k_b2rf_batch): count x n row-major planes in and out (b_im may be null), 2 <= n <= 2048, count >= 1;
 // one workgroup per polynomial, one launch.
 void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double* b_re, const double* b_im, double* rf_re,
@@ -24,11 +18,6 @@ void slr_b2rf_batch_run(int device, void* stream, int n, int count, const double
 // (r_im may be null), 2 <= m, n <= 2048, m even; one upload, one download.  literal: dzepse.m's sin(conj(theta) / 2) middle stage.
 void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, const double* r_re, const double* r_im, double* out_re,
                          double* out_im, int literal);
-// Bloch simulation with relaxation (slr.hip k_bloch; blochC.c:422-512).  m*: in = initial magnetisation at the first sample of
-// every (frequency, position) block, out = the result; nfreq * npos * (mode & 2 ? ntime : 1) doubles each.
-void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
-               const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
-               const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz);
 // Work split of the batched simulators (slr.hip k_bloch_batch, k_abr_batch, k_abr2_batch): one 256-thread workgroup per (pulse, scale, chunk of
 // 256 points); pulses in descending order of ntime (ties in list order), then scale, then chunk.  npoint: points per pulse
 // ((frequency, position) pairs, positions, or (x, y) points).  Returns the table's length; writes the table to out when out is not null.
@@ -36,8 +25,10 @@ struct SimBlock {
     int pulse, scale, chunk, pad;
 };
 long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out);
-// Batched Bloch simulation (slr.hip k_bloch_batch) and forward simulation (k_abr_batch): P pulses x S scales, one upload, one
-// launch, one download.  Offsets and layouts as mbfir_bloch_batch / mbfir_abr_batch document them (include/mbfir.h).
+// Bloch simulation with relaxation (slr.hip k_bloch_batch; blochC.c:422-512) and forward simulation (k_abr_batch; g null = 2 pi / n
+// per sample; mode 0 abrm.m, 1 hard pulse): P pulses x S scales, one upload, one launch, one download.  Offsets and layouts as
+// mbfir_bloch_batch / mbfir_abr_batch document them (include/mbfir.h).  m*: in = initial magnetisation at the first sample of
+// every (scale, frequency, position) block, out = the result.  mbfir_bloch and mbfir_abr call these with one pulse at scale 1.0.
 void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
@@ -46,9 +37,9 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
 void abr_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
                    int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
                    double* a_im, double* b_re, double* b_im);
-// Batched 2D forward simulation (slr.hip k_abr2_batch): abr2_run's points for every (pulse, scale), mode 0 abrm.m, 1 the hard-pulse
-// model with the precession angle x gx + y gy.  Offsets and layout as mbfir_abr2_batch documents them; sim_block_table's npoint is
-// nx ny.
+// 2D forward simulation (slr.hip k_abr2_batch, abrm.m:39-57): a, b at (x_k, y_j) -> index k ny + j for every (pulse, scale); gx null
+// = 2 pi / n, gy null = 0; mode 0 abrm.m, 1 the hard-pulse model with the precession angle x gx + y gy.  Offsets and layout as
+// mbfir_abr2_batch documents them; sim_block_table's npoint is nx ny.  mbfir_abr2 calls it with one pulse at scale 1.0.
 void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
                     const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                     int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im);

@@ -3,14 +3,14 @@
 //   b2a   : DFTs of length blp = 8 n (any n: direct O(blp^2) DFT, twiddles by rotation recurrence with an
 //           exact sincospi seed every 256 terms), elementwise steps in between
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
-// k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr / k_abr_batch / k_abr2 / k_abr2_batch share abr_step: one definition each,
-// so those batch kernels equal their single-pulse twins by construction.  k_bloch / k_bloch_batch still hold the same loop nest twice (see
-// the note above k_bloch_batch).
+// k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr_batch / k_abr2_batch share abr_step: one definition each.  The forward
+// simulators exist once, as batch kernels: a single pulse is the batch of one pulse at scale 1.0 (mbfir_abr, mbfir_abr2, mbfir_bloch).
 #include "dev_common.h"
 #include "pulse.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <optional>
 
 namespace mbfir {
 
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il,
 //   mode 1: the hard-pulse model the inverse SLR transform inverts exactly -- free precession by x g_m on beta, then
 //           the hard pulse of the sample
 // abr_step is one sample of either model for one position (r: the rf sample, om: the precession angle of the sample; mode is
-// uniform over the workgroup).  k_abr, k_abr_batch, k_abr2 (mode 0, om = x gx + y gy) and k_abr2_batch all step through it.  The state goes in
-// and comes back by value: through references the kernels compile to other fused products (the compiler then promotes a and b to
+// uniform over the workgroup).  k_abr_batch (om = x g) and k_abr2_batch (om = x gx + y gy) step through it.  The state goes in and
+// comes back by value: through references the kernels compile to other fused products (the compiler then promotes a and b to
 // registers only after inlining, in another order), and the results differ from before in the last bits.
 struct CayleyKlein {
     double2 a, b;
@@ -183,33 +183,6 @@ __device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, 
     }
     return CayleyKlein{a, b};
 }
-// one thread per position, the pulse staged through LDS; g may be null (2 pi / n per sample).
-__global__ __launch_bounds__(256) void k_abr(const double* __restrict__ rf_il, const double* __restrict__ g, int n,
-                                             const double* __restrict__ x, int nx, int mode, double* __restrict__ a_il,
-                                             double* __restrict__ b_il) {
-    __shared__ double2 srf[256];
-    __shared__ double sg[256];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const double xv = i < nx ? x[i] : 0.0;
-    double2 a = make_double2(1, 0), b = make_double2(0, 0);
-    const double g0 = 2.0 * M_PI / n;
-    for (int m0 = 0; m0 < n; m0 += 256) {
-        __syncthreads();
-        const int mm = m0 + threadIdx.x;
-        if (mm < n) { srf[threadIdx.x] = make_double2(rf_il[2 * mm], rf_il[2 * mm + 1]); sg[threadIdx.x] = g ? g[mm] : g0; }
-        __syncthreads();
-        const int cnt = min(256, n - m0);
-        for (int q = 0; q < cnt; ++q) {
-            const CayleyKlein ck = abr_step(mode, srf[q], xv * sg[q], a, b);
-            a = ck.a; b = ck.b;
-        }
-    }
-    if (i < nx) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
-}
-static void slr_abr_launch(const double* rf_il, const double* g, int n, const double* x, int nx, int mode, double* a_il, double* b_il,
-                           hipStream_t st) {
-    hipLaunchKernelGGL(k_abr, dim3(cdiv(nx, 256)), dim3(256), 0, st, rf_il, g, n, x, nx, mode, a_il, b_il);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Bloch-equation simulation with relaxation: bloch_simulation/blochC.c calcrotmat (:171-236),
@@ -217,7 +190,7 @@ static void slr_abr_launch(const double* rf_il, const double* g, int n, const do
 // two outer loops -- and the time loop inside; the per-sample quantities (rotation components of the pulse,
 // gradient, interval, E1, E2) are staged through LDS 256 samples at a time.
 //   mode bit 0: steady state (propagate A, B with M' = A M + B, then M = (I - A)^-1 B), bit 1: record every sample.
-// step[t] = (rotx, roty, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2); pos3 = (x, y, z) per position.
+// LDS row of sample t = (rotx, roty, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2); pos3 = (x, y, z) per position.
 struct Rot3 {
     double m[9];           // column-major like the reference: m[i + 3 j]
 };
@@ -247,81 +220,18 @@ __device__ __forceinline__ void rot_vec(const Rot3& R, const double v[3], double
     o[2] = R.m[2] * v[0] + R.m[5] * v[1] + R.m[8] * v[2];
 }
 constexpr int BLOCH_CH = 256;
-__global__ __launch_bounds__(256) void k_bloch(const double* __restrict__ step, int ntime, const double* __restrict__ df, int nf,
-                                               const double* __restrict__ pos3, int npos, int mode, double* __restrict__ mx,
-                                               double* __restrict__ my, double* __restrict__ mz) {
-    __shared__ double sst[BLOCH_CH][8];
-    const long pair = (long)blockIdx.x * 256 + threadIdx.x, npair = (long)nf * npos;
-    const bool live = pair < npair;
-    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
-    const double dfv = df[fi], px = pos3[3 * pi], py = pos3[3 * pi + 1], pz = pos3[3 * pi + 2];
-    const int ntout = (mode & 2) ? ntime : 1;
-    const long o0 = pair * ntout;
-    double m[3] = {0, 0, 1};
-    if (live) { m[0] = mx[o0]; m[1] = my[o0]; m[2] = mz[o0]; }          // initial magnetisation sits in the output (:826-841)
-    for (int pass = (mode & 1) ? 0 : 1; pass < 2; ++pass) {
-        if (pass == 1 && mode == 1) break;                               // steady state only
-        double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, B[3] = {0, 0, 0};
-        for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-            __syncthreads();
-            const int cnt = min(BLOCH_CH, ntime - t0);
-            for (int e = threadIdx.x; e < cnt * 8; e += 256) sst[e >> 3][e & 7] = step[(long)t0 * 8 + e];
-            __syncthreads();
-            if (!live) continue;
-            for (int q = 0; q < cnt; ++q) {
-                const double* s = sst[q];
-                const double rotz = -((s[2] * px + s[3] * py + s[4] * pz) + dfv * s[5]);
-                Rot3 R;
-                bloch_rotmat(s[0], s[1], rotz, R);
-                const double e1 = s[6], e2 = s[7];
-                if (pass == 0) {
-                    double c[3], o[3];
-                    for (int j = 0; j < 3; ++j) {                        // A <- D R A, column by column
-                        c[0] = A[3 * j]; c[1] = A[3 * j + 1]; c[2] = A[3 * j + 2];
-                        rot_vec(R, c, o);
-                        A[3 * j] = e2 * o[0]; A[3 * j + 1] = e2 * o[1]; A[3 * j + 2] = e1 * o[2];
-                    }
-                    rot_vec(R, B, o);
-                    B[0] = e2 * o[0]; B[1] = e2 * o[1]; B[2] = e1 * o[2] + (1 - e1);
-                } else {
-                    double o[3];
-                    rot_vec(R, m, o);
-                    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
-                    if (mode & 2) { mx[o0 + t0 + q] = m[0]; my[o0 + t0 + q] = m[1]; mz[o0 + t0 + q] = m[2]; }
-                }
-            }
-        }
-        if (pass == 0 && live) {
-            // M = (I - A)^-1 B by the adjugate (the reference's invmat)
-            double K[9];
-            for (int e = 0; e < 9; ++e) K[e] = ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0) - A[e];
-            const double c00 = K[4] * K[8] - K[7] * K[5], c01 = K[7] * K[2] - K[1] * K[8], c02 = K[1] * K[5] - K[4] * K[2];
-            const double det = K[0] * c00 + K[3] * c01 + K[6] * c02;
-            const double inv[9] = {c00 / det, c01 / det, c02 / det,
-                                   (K[6] * K[5] - K[3] * K[8]) / det, (K[0] * K[8] - K[6] * K[2]) / det, (K[3] * K[2] - K[0] * K[5]) / det,
-                                   (K[3] * K[7] - K[6] * K[4]) / det, (K[6] * K[1] - K[0] * K[7]) / det, (K[0] * K[4] - K[3] * K[1]) / det};
-            for (int i = 0; i < 3; ++i) m[i] = inv[i] * B[0] + inv[3 + i] * B[1] + inv[6 + i] * B[2];
-        }
-    }
-    if (live && !(mode & 2)) { mx[o0] = m[0]; my[o0] = m[1]; mz[o0] = m[2]; }
-}
-static void bloch_launch(const double* step, int ntime, const double* df, int nf, const double* pos3, int npos, int mode,
-                         double* mx, double* my, double* mz, hipStream_t st) {
-    hipLaunchKernelGGL(k_bloch, dim3(cdiv((long)nf * npos, 256)), dim3(256), 0, st, step, ntime, df, nf, pos3, npos, mode, mx, my, mz);
-}
 
 // ------------------------------------------------------------------------------------------------
 // Batched simulators: P pulses x S transmit-gain scales in one launch.  Workgroup blockIdx.x -> (pulse, scale, chunk of 256 points)
 // through the host-built block table (sim_block_table), the pulses with the most samples first.  Each workgroup stages only its
-// own pulse's samples through LDS, 256 at a time, and runs the per-sample arithmetic of its single-pulse twin, so a thread's bits
-// depend only on its own (pulse, scale, point) and the fixed time order.  k_abr_batch calls k_abr's abr_step.  k_bloch_batch
-// repeats k_bloch's loop nest: every shared form tried (step and steady-state functions on array references; the whole loop nest
-// in one function with the state by value and the tile fill as a callable) kept the registers and the opcode counts but fused
-// other products, and the magnetisation moved in the last bits (3e-15 of the peak, 3e-13 in the steady-state modes).  Edit the two
-// copies alike; tests/test_simbatch_gpu.py asserts that they agree bit for bit.
+// own pulse's samples through LDS, 256 at a time, so a thread's bits depend only on its own (pulse, scale, point) and the fixed
+// time order.  These are the only forward simulators: the single-pulse calls run them with one pulse at scale 1.0.  Four rules
+// fix the bits callers have had since the single-pulse kernels these replaced, and are kept for that reason: a pulse without g
+// gets 2 pi / n per sample (and gy = 0 in 2D), the 2D angle is fma(x, gx, y gy), the Bloch rotx is ((-(re s)) gamma) dt, and
+// E1 / E2 come from the host's exp.
 
-// k_abr over the batch.  rf (interleaved) is scaled while it is staged; g holds one weight per sample of every pulse (the host
-// writes 2 pi / n where a pulse has none: the value k_abr computes for a null g).  Output: S x nx per pulse, scale-major.
+// One thread per position.  rf (interleaved) is scaled while it is staged; g holds one weight per sample of every pulse (the host
+// writes 2 pi / n where a pulse has none).  Output: S x nx per pulse, scale-major.
 struct AbrPulseDev {
     long r_off, x_off, o_off;     // first rf / g sample, first position, first output entry
     int n, nx;
@@ -359,9 +269,9 @@ __global__ __launch_bounds__(256) void k_abr_batch(const double* __restrict__ rf
     }
 }
 
-// k_bloch over the batch.  in[t] = (b1 re, b1 im, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2, dt) per sample of every
-// pulse.  The thread that stages sample t forms bloch_run's rotx = ((-(re s)) gamma) dt and roty = ((im s) gamma) dt for the
-// workgroup's scale s, so the LDS tile holds k_bloch's step[t] for the pulse b1 s.  m0: (x, y, z) of every (scale, frequency,
+// in[t] = (b1 re, b1 im, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2, dt) per sample of every pulse.  The thread that
+// stages sample t forms rotx = ((-(re s)) gamma) dt and roty = ((im s) gamma) dt (blochC.c:332-333, products in this order) for
+// the workgroup's scale s, so the LDS tile holds the rows of the pulse b1 s.  m0: (x, y, z) of every (scale, frequency,
 // position) block of every pulse; output S x nf x npos x ntout per pulse, scale-major.
 constexpr int BLOCH_IN = 9;
 struct BlochPulseDev {
@@ -399,7 +309,7 @@ __global__ __launch_bounds__(256) void k_bloch_batch(const double* __restrict__ 
             if ((int)threadIdx.x < cnt) {
                 const double* s = in + BLOCH_IN * (P.t_off + t0 + threadIdx.x);
                 const double dt = s[8];
-                sst[threadIdx.x][0] = ((-(s[0] * sc)) * gamma) * dt;      // rotx  (bloch_run of b1 s)
+                sst[threadIdx.x][0] = ((-(s[0] * sc)) * gamma) * dt;      // rotx of the pulse b1 s
                 sst[threadIdx.x][1] = ((s[1] * sc) * gamma) * dt;         // roty
                 for (int e = 2; e < 8; ++e) sst[threadIdx.x][e] = s[e];
             }
@@ -742,49 +652,12 @@ void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, cons
     unpack_cplx(tot, h.data(), out_re, out_im);
 }
 
-// 2D forward simulation, abrm.m:39-57: one thread per (x_k, y_j), output index k ny + j; one rotation about
-// (Re rf, Im rf, x_k gx_m + y_j gy_m) per sample: abr_step in mode 0.  rf, gx, gy staged through LDS 256 samples at a time;
-// gx null = 2 pi / n per sample, gy null = 0.
-__global__ __launch_bounds__(256) void k_abr2(const double* __restrict__ rf_il, const double* __restrict__ gx,
-                                              const double* __restrict__ gy, int n, const double* __restrict__ x, int nx,
-                                              const double* __restrict__ y, int ny, double* __restrict__ a_il,
-                                              double* __restrict__ b_il) {
-    __shared__ double2 srf[256];
-    __shared__ double sgx[256], sgy[256];
-    const long i = (long)blockIdx.x * 256 + threadIdx.x, tot = (long)nx * ny;
-    const bool live = i < tot;
-    const long kx = live ? i / ny : 0;
-    const double xv = x[kx], yv = y[live ? i - kx * ny : 0];
-    double2 a = make_double2(1, 0), b = make_double2(0, 0);
-    const double g0 = 2.0 * M_PI / n;
-    for (int m0 = 0; m0 < n; m0 += 256) {
-        __syncthreads();
-        const int mm = m0 + threadIdx.x;
-        if (mm < n) {
-            srf[threadIdx.x] = make_double2(rf_il[2 * mm], rf_il[2 * mm + 1]);
-            sgx[threadIdx.x] = gx ? gx[mm] : g0;
-            sgy[threadIdx.x] = gy ? gy[mm] : 0.0;
-        }
-        __syncthreads();
-        const int cnt = min(256, n - m0);
-        for (int q = 0; q < cnt; ++q) {
-            const CayleyKlein ck = abr_step(0, srf[q], xv * sgx[q] + yv * sgy[q], a, b);
-            a = ck.a; b = ck.b;
-        }
-    }
-    if (live) { a_il[2 * i] = a.x; a_il[2 * i + 1] = a.y; b_il[2 * i] = b.x; b_il[2 * i + 1] = b.y; }
-}
-static void slr_abr2_launch(const double* rf_il, const double* gx, const double* gy, int n, const double* x, int nx, const double* y,
-                            int ny, double* a_il, double* b_il, hipStream_t st) {
-    hipLaunchKernelGGL(k_abr2, dim3(cdiv((long)nx * ny, 256)), dim3(256), 0, st, rf_il, gx, gy, n, x, nx, y, ny, a_il, b_il);
-}
-
-// k_abr2 over the batch, both models: one workgroup per (pulse, scale, chunk of 256 points) through the block table of the other
-// batched simulators, point i = k ny + j at (x_k, y_j).  rf (interleaved) is scaled while it is staged; gx / gy hold one weight per
-// sample of every pulse (the host writes 2 pi / n and 0 where a pulse has none: the values k_abr2 forms for null gx / gy).  mode 1
-// is the hard-pulse model with the precession angle x gx + y gy.  Output: S x nx x ny per pulse, scale-major.
-// The precession angle is written as the fused form k_abr2 compiles to, fma(x, gx, y gy): with the runtime mode the compiler may
-// choose the other product for the fused multiply-add, and mode 0 has to give k_abr2's bits.
+// 2D forward simulation (abrm.m:39-57), both models: one workgroup per (pulse, scale, chunk of 256 points) through the block table
+// of the other batched simulators, one thread per point i = k ny + j at (x_k, y_j).  rf (interleaved) is scaled while it is staged;
+// gx / gy hold one weight per sample of every pulse (the host writes 2 pi / n and 0 where a pulse has none).  mode 0 is one rotation
+// about (Re rf, Im rf, x gx + y gy) per sample, mode 1 the hard-pulse model with that precession angle.  Output: S x nx x ny per
+// pulse, scale-major.  The precession angle is defined as fma(x, gx, y gy): left as x gx + y gy the compiler may fuse the other
+// product, and callers' bits would move.
 struct Abr2PulseDev {
     long r_off, x_off, y_off, o_off;     // first rf / gx / gy sample, first x, first y, first output entry
     int n, nx, ny, pad;
@@ -828,7 +701,7 @@ __global__ __launch_bounds__(256) void k_abr2_batch(const double* __restrict__ r
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side of mbfir_b2a / mbfir_ab2rf / mbfir_b2rf, mbfir_abr, mbfir_abr2 and mbfir_bloch (pulse.h; arguments checked).
+// Host side of mbfir_b2a / mbfir_ab2rf / mbfir_b2rf (pulse.h; arguments checked).
 
 void slr_run(int device, void* stream, int n, const double* b_re, const double* b_im, const double* a_in_re, const double* a_in_im,
              double* a_re, double* a_im, double* rf_re, double* rf_im) {
@@ -863,101 +736,10 @@ void slr_run(int device, void* stream, int n, const double* b_re, const double* 
     MBFIR_HIP(hipGetLastError());
 }
 
-void abr_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* g, int nx, const double* x,
-             int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
-    MBFIR_HIP(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t N = (size_t)n, X = (size_t)nx;
-    DevBuf drf(2 * N * 8), dg(N * 8), dx(X * 8), da(2 * X * 8), db(2 * X * 8);
-    std::vector<double2> h(N), oa(X), ob(X);
-    pack_cplx(N, rf_re, rf_im, h.data());
-    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
-    if (g) MBFIR_HIP(hipMemcpyAsync(dg.p, g, N * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dx.p, x, X * 8, hipMemcpyHostToDevice, st));
-    slr_abr_launch(drf.as<double>(), g ? dg.as<double>() : nullptr, n, dx.as<double>(), nx, mode, da.as<double>(), db.as<double>(), st);
-    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * X * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * X * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
-    unpack_cplx(X, oa.data(), a_re, a_im);
-    unpack_cplx(X, ob.data(), b_re, b_im);
-}
-
-void abr2_run(int device, void* stream, int n, const double* rf_re, const double* rf_im, const double* gx, const double* gy, int nx,
-              const double* x, int ny, const double* y, double* a_re, double* a_im, double* b_re, double* b_im) {
-    MBFIR_HIP(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t N = (size_t)n, P = (size_t)nx * ny;
-    DevBuf drf(2 * N * 8), dgx(N * 8), dgy(N * 8), dx((size_t)nx * 8), dy((size_t)ny * 8), da(2 * P * 8), db(2 * P * 8);
-    std::vector<double2> h(N), oa(P), ob(P);
-    pack_cplx(N, rf_re, rf_im, h.data());
-    MBFIR_HIP(hipMemcpyAsync(drf.p, h.data(), 2 * N * 8, hipMemcpyHostToDevice, st));
-    if (gx) MBFIR_HIP(hipMemcpyAsync(dgx.p, gx, N * 8, hipMemcpyHostToDevice, st));
-    if (gy) MBFIR_HIP(hipMemcpyAsync(dgy.p, gy, N * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dx.p, x, (size_t)nx * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dy.p, y, (size_t)ny * 8, hipMemcpyHostToDevice, st));
-    slr_abr2_launch(drf.as<double>(), gx ? dgx.as<double>() : nullptr, gy ? dgy.as<double>() : nullptr, n, dx.as<double>(), nx,
-                    dy.as<double>(), ny, da.as<double>(), db.as<double>(), st);
-    MBFIR_HIP(hipGetLastError());
-    MBFIR_HIP(hipMemcpyAsync(oa.data(), da.p, 2 * P * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipMemcpyAsync(ob.data(), db.p, 2 * P * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
-    unpack_cplx(P, oa.data(), a_re, a_im);
-    unpack_cplx(P, ob.data(), b_re, b_im);
-}
-
-constexpr double TWOPI_REF = 6.283185;                      // blochC.c:6, the reference's truncated constant
-// s[0 .. 5]: entries 2 .. 7 of sample t's step row, as bloch_run and bloch_batch_run both stage them
-static void bloch_step_row(const double* gx, const double* gy, const double* gz, size_t t, double gamma, double dt, double t1,
-                           double t2, double* s) {
-    s[0] = (gx ? gx[t] : 0.0) * gamma * dt;                 // gradient terms of rotz (blochC.c:317-319, :330)
-    s[1] = (gy ? gy[t] : 0.0) * gamma * dt;
-    s[2] = (gz ? gz[t] : 0.0) * gamma * dt;
-    s[3] = TWOPI_REF * dt;
-    s[4] = std::exp(-dt / t1);                              // :460-464
-    s[5] = std::exp(-dt / t2);
-}
-// pos3 = (x, y, z) per position, a null axis as zeros
-static void bloch_fill_pos3(size_t npos, const double* dx, const double* dy, const double* dz, double* pos) {
-    for (size_t p = 0; p < npos; ++p) {
-        pos[3 * p] = dx ? dx[p] : 0.0; pos[3 * p + 1] = dy ? dy[p] : 0.0; pos[3 * p + 2] = dz ? dz[p] : 0.0;
-    }
-}
-
-void bloch_run(int device, void* stream, int ntime, const double* b1_re, const double* b1_im, const double* gx, const double* gy,
-               const double* gz, const double* tsteps, double t1, double t2, int nfreq, const double* df, int npos, const double* dx,
-               const double* dy, const double* dz, int mode, double gamma, double* mx, double* my, double* mz) {
-    MBFIR_HIP(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t nt = (size_t)ntime, npair = (size_t)nfreq * npos, nout = npair * ((mode & 2) ? nt : 1);
-    std::vector<double> step(nt * 8), pos(3 * (size_t)npos);
-    for (size_t t = 0; t < nt; ++t) {
-        const double dt = tsteps[t];
-        step[8 * t] = -b1_re[t] * gamma * dt;                // rotx  (blochC.c:332)
-        step[8 * t + 1] = b1_im[t] * gamma * dt;             // roty  (:333)
-        bloch_step_row(gx, gy, gz, t, gamma, dt, t1, t2, &step[8 * t + 2]);
-    }
-    bloch_fill_pos3(npos, dx, dy, dz, pos.data());
-    DevBuf dstep(step.size() * 8), dpos(pos.size() * 8), ddf((size_t)nfreq * 8), dmx(nout * 8), dmy(nout * 8), dmz(nout * 8);
-    MBFIR_HIP(hipMemcpyAsync(dstep.p, step.data(), step.size() * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dpos.p, pos.data(), pos.size() * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(ddf.p, df, (size_t)nfreq * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dmx.p, mx, nout * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dmy.p, my, nout * 8, hipMemcpyHostToDevice, st));
-    MBFIR_HIP(hipMemcpyAsync(dmz.p, mz, nout * 8, hipMemcpyHostToDevice, st));
-    bloch_launch(dstep.as<double>(), ntime, ddf.as<double>(), nfreq, dpos.as<double>(), npos, mode, dmx.as<double>(), dmy.as<double>(),
-                 dmz.as<double>(), st);
-    MBFIR_HIP(hipMemcpyAsync(mx, dmx.p, nout * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipMemcpyAsync(my, dmy.p, nout * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipMemcpyAsync(mz, dmz.p, nout * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
-}
-
 // ------------------------------------------------------------------------------------------------
-// Host side of mbfir_bloch_batch / mbfir_abr_batch / mbfir_abr2_batch (arguments checked by api.cpp): every input in one staging buffer of
-// 256-byte-aligned sections, one upload, one launch, one download.
+// Host side of the forward simulators (mbfir_bloch_batch / mbfir_abr_batch / mbfir_abr2_batch, and mbfir_bloch / mbfir_abr /
+// mbfir_abr2 as their batch of one; arguments checked by api.cpp): every input in one staging buffer of 256-byte-aligned sections,
+// one upload, one launch, one download.
 
 long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out) {
     long k = 0;
@@ -978,17 +760,47 @@ long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscal
 }
 
 namespace {
-struct Staging {                                          // host sections, each 256-byte aligned, uploaded with one copy
-    std::vector<char> h;
+// One call of a batched simulator.  The caller adds its own sections, then add_tables; fills its sections (at<T>: add moves
+// the buffer, so take pointers after the last add); uploads; launches nblk workgroups on the dev<T> addresses; downloads.
+struct Staging {
+    std::vector<char> h;                                  // host sections, each 256-byte aligned, uploaded with one copy
+    std::optional<DevBuf> buf;                            // the sections, then the output region
+    size_t o_sc = 0, o_pd = 0, o_bk = 0, o_out = 0;       // scales, per-pulse descriptors, block table; output region
+    long nblk = 0;
     size_t add(size_t bytes) {
         const size_t o = (h.size() + 255) & ~size_t(255);
         h.resize(o + bytes);
         return o;
     }
     template <class T> T* at(size_t o) { return reinterpret_cast<T*>(h.data() + o); }
+    template <class T> T* dev(size_t o) { return reinterpret_cast<T*>(buf->as<char>() + o); }
+    // The sections every simulator has, filled: pd = npulse descriptors of pd_size bytes; ntime / npoint as sim_block_table.
+    void add_tables(int npulse, const void* pd, size_t pd_size, const int* ntime, const long* npoint, int nscale,
+                    const double* scales) {
+        nblk = sim_block_table(npulse, ntime, npoint, nscale, nullptr);
+        o_sc = add((size_t)nscale * 8);
+        o_pd = add(npulse * pd_size);
+        o_bk = add(nblk * sizeof(SimBlock));
+        std::copy(scales, scales + nscale, at<double>(o_sc));
+        std::memcpy(at<char>(o_pd), pd, npulse * pd_size);
+        sim_block_table(npulse, ntime, npoint, nscale, at<SimBlock>(o_bk));
+    }
+    void upload(size_t out_bytes, hipStream_t st) {
+        const size_t up = h.size();
+        o_out = (up + 255) & ~size_t(255);
+        buf.emplace(o_out + out_bytes);
+        MBFIR_HIP(hipMemcpyAsync(buf->p, h.data(), up, hipMemcpyHostToDevice, st));
+    }
+    void download(void* out, size_t out_bytes, hipStream_t st) {     // after the launch
+        MBFIR_HIP(hipGetLastError());
+        MBFIR_HIP(hipMemcpyAsync(out, dev<char>(o_out), out_bytes, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipStreamSynchronize(st));
+        MBFIR_HIP(hipGetLastError());
+    }
 };
 }  // namespace
 
+constexpr double TWOPI_REF = 6.283185;                      // blochC.c:6, the reference's truncated constant
 void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
@@ -1014,11 +826,9 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
         O += nscale * npair[p] * ((mode & 2) ? d.ntime : 1);
     }
     const long T = toff[npulse], F = foff[nfgrid], NP = poff[npgrid];
-    const long nblk = sim_block_table(npulse, nt.data(), npair.data(), nscale, nullptr);
     Staging S;
-    const size_t o_in = S.add(T * BLOCH_IN * 8), o_df = S.add(F * 8), o_pos = S.add(NP * 24), o_sc = S.add((size_t)nscale * 8),
-                 o_m0 = S.add(M * 24), o_pd = S.add(npulse * sizeof(BlochPulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
-    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    const size_t o_in = S.add(T * BLOCH_IN * 8), o_df = S.add(F * 8), o_pos = S.add(NP * 24), o_m0 = S.add(M * 24);
+    S.add_tables(npulse, pd.data(), sizeof(BlochPulseDev), nt.data(), npair.data(), nscale, scales);
     double* in = S.at<double>(o_in);
     for (int p = 0; p < npulse; ++p) {
         const bool one = tsoff[p + 1] - tsoff[p] == 1;
@@ -1028,14 +838,21 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
             double* s = in + BLOCH_IN * t;
             s[0] = b1_re[t];
             s[1] = b1_im[t];
-            bloch_step_row(gx, gy, gz, t, g, dt, t1[p], t2[p], s + 2);
+            s[2] = (gx ? gx[t] : 0.0) * g * dt;                 // gradient terms of rotz (blochC.c:317-319, :330)
+            s[3] = (gy ? gy[t] : 0.0) * g * dt;
+            s[4] = (gz ? gz[t] : 0.0) * g * dt;
+            s[5] = TWOPI_REF * dt;
+            s[6] = std::exp(-dt / t1[p]);                       // :460-464
+            s[7] = std::exp(-dt / t2[p]);
             s[8] = dt;
         }
     }
     std::copy(df, df + F, S.at<double>(o_df));
-    bloch_fill_pos3(NP, dx, dy, dz, S.at<double>(o_pos));
-    std::copy(scales, scales + nscale, S.at<double>(o_sc));
-    double* m0 = S.at<double>(o_m0);
+    double* pos = S.at<double>(o_pos);                       // (x, y, z) per position, a null axis as zeros
+    for (long q = 0; q < NP; ++q) {
+        pos[3 * q] = dx ? dx[q] : 0.0; pos[3 * q + 1] = dy ? dy[q] : 0.0; pos[3 * q + 2] = dz ? dz[q] : 0.0;
+    }
+    double* m0 = S.at<double>(o_m0);                         // the initial magnetisation sits at the first sample of each output block
     for (int p = 0; p < npulse; ++p) {
         const long ntout = (mode & 2) ? nt[p] : 1;
         for (long b = 0; b < nscale * npair[p]; ++b) {
@@ -1043,22 +860,13 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
             m0[m] = mx[o]; m0[m + 1] = my[o]; m0[m + 2] = mz[o];
         }
     }
-    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(BlochPulseDev));
-    sim_block_table(npulse, nt.data(), npair.data(), nscale, S.at<SimBlock>(o_bk));
-    DevBuf dbuf(o_out + 3 * (size_t)O * 8);
-    char* base = dbuf.as<char>();
-    double* out = reinterpret_cast<double*>(base + o_out);
-    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_bloch_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_in),
-                       reinterpret_cast<const double*>(base + o_df), reinterpret_cast<const double*>(base + o_pos),
-                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const BlochPulseDev*>(base + o_pd),
-                       reinterpret_cast<const SimBlock*>(base + o_bk), reinterpret_cast<const double*>(base + o_m0), mode, out,
-                       out + O, out + 2 * O);
-    MBFIR_HIP(hipGetLastError());
+    S.upload(3 * (size_t)O * 8, st);
+    double* out = S.dev<double>(S.o_out);
+    hipLaunchKernelGGL(k_bloch_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_in), S.dev<const double>(o_df),
+                       S.dev<const double>(o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const SimBlock>(S.o_bk), S.dev<const double>(o_m0), mode, out, out + O, out + 2 * O);
     std::vector<double> h(3 * (size_t)O);
-    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 8, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
+    S.download(h.data(), h.size() * 8, st);
     std::copy(h.begin(), h.begin() + O, mx);
     std::copy(h.begin() + O, h.begin() + 2 * O, my);
     std::copy(h.begin() + 2 * O, h.end(), mz);
@@ -1081,33 +889,21 @@ void abr_batch_run(int device, void* stream, int npulse, const long* roff, const
         O += nscale * nx[p];
     }
     const long R = roff[npulse], X = xoff[nxgrid];
-    const long nblk = sim_block_table(npulse, nt.data(), nx.data(), nscale, nullptr);
     Staging S;
-    const size_t o_rf = S.add(R * 16), o_g = S.add(R * 8), o_x = S.add(X * 8), o_sc = S.add((size_t)nscale * 8),
-                 o_pd = S.add(npulse * sizeof(AbrPulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
-    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    const size_t o_rf = S.add(R * 16), o_g = S.add(R * 8), o_x = S.add(X * 8);
+    S.add_tables(npulse, pd.data(), sizeof(AbrPulseDev), nt.data(), nx.data(), nscale, scales);
     pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
     double* gw = S.at<double>(o_g);
     for (int p = 0; p < npulse; ++p)
-        for (long t = roff[p]; t < roff[p + 1]; ++t) gw[t] = g ? g[t] : 2.0 * M_PI / pd[p].n;     // k_abr's weight for a null g
+        for (long t = roff[p]; t < roff[p + 1]; ++t) gw[t] = g ? g[t] : 2.0 * M_PI / pd[p].n;     // a null g is 2 pi / n per sample
     std::copy(x, x + X, S.at<double>(o_x));
-    std::copy(scales, scales + nscale, S.at<double>(o_sc));
-    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(AbrPulseDev));
-    sim_block_table(npulse, nt.data(), nx.data(), nscale, S.at<SimBlock>(o_bk));
-    DevBuf dbuf(o_out + 4 * (size_t)O * 8);
-    char* base = dbuf.as<char>();
-    double2* out = reinterpret_cast<double2*>(base + o_out);    // a: O entries, then b: O entries
-    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_rf),
-                       reinterpret_cast<const double*>(base + o_g), reinterpret_cast<const double*>(base + o_x),
-                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const AbrPulseDev*>(base + o_pd),
-                       reinterpret_cast<const SimBlock*>(base + o_bk), mode, reinterpret_cast<double*>(out),
-                       reinterpret_cast<double*>(out + O));
-    MBFIR_HIP(hipGetLastError());
+    S.upload(4 * (size_t)O * 8, st);
+    double2* out = S.dev<double2>(S.o_out);                     // a: O entries, then b: O entries
+    hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_rf), S.dev<const double>(o_g),
+                       S.dev<const double>(o_x), S.dev<const double>(S.o_sc), S.dev<const AbrPulseDev>(S.o_pd),
+                       S.dev<const SimBlock>(S.o_bk), mode, reinterpret_cast<double*>(out), reinterpret_cast<double*>(out + O));
     std::vector<double2> h(2 * (size_t)O);
-    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 16, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
+    S.download(h.data(), h.size() * 16, st);
     unpack_cplx(O, h.data(), a_re, a_im);
     unpack_cplx(O, h.data() + O, b_re, b_im);
 }
@@ -1130,39 +926,27 @@ void abr2_batch_run(int device, void* stream, int npulse, const long* roff, cons
         O += nscale * npt[p];
     }
     const long R = roff[npulse], X = xoff[nxgrid], Y = yoff[nygrid];
-    const long nblk = sim_block_table(npulse, nt.data(), npt.data(), nscale, nullptr);
     Staging S;
-    const size_t o_rf = S.add(R * 16), o_gx = S.add(R * 8), o_gy = S.add(R * 8), o_x = S.add(X * 8), o_y = S.add(Y * 8),
-                 o_sc = S.add((size_t)nscale * 8), o_pd = S.add(npulse * sizeof(Abr2PulseDev)), o_bk = S.add(nblk * sizeof(SimBlock));
-    const size_t up = S.h.size(), o_out = (up + 255) & ~size_t(255);
+    const size_t o_rf = S.add(R * 16), o_gx = S.add(R * 8), o_gy = S.add(R * 8), o_x = S.add(X * 8), o_y = S.add(Y * 8);
+    S.add_tables(npulse, pd.data(), sizeof(Abr2PulseDev), nt.data(), npt.data(), nscale, scales);
     pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
     double* gxw = S.at<double>(o_gx);
     double* gyw = S.at<double>(o_gy);
     for (int p = 0; p < npulse; ++p)
         for (long t = roff[p]; t < roff[p + 1]; ++t) {
-            gxw[t] = gx ? gx[t] : 2.0 * M_PI / pd[p].n;         // k_abr2's weights for null gx / gy
+            gxw[t] = gx ? gx[t] : 2.0 * M_PI / pd[p].n;         // a null gx is 2 pi / n per sample, a null gy is 0
             gyw[t] = gy ? gy[t] : 0.0;
         }
     std::copy(x, x + X, S.at<double>(o_x));
     std::copy(y, y + Y, S.at<double>(o_y));
-    std::copy(scales, scales + nscale, S.at<double>(o_sc));
-    std::memcpy(S.h.data() + o_pd, pd.data(), npulse * sizeof(Abr2PulseDev));
-    sim_block_table(npulse, nt.data(), npt.data(), nscale, S.at<SimBlock>(o_bk));
-    DevBuf dbuf(o_out + 4 * (size_t)O * 8);
-    char* base = dbuf.as<char>();
-    double2* out = reinterpret_cast<double2*>(base + o_out);    // a: O entries, then b: O entries
-    MBFIR_HIP(hipMemcpyAsync(base, S.h.data(), up, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_abr2_batch, dim3((unsigned)nblk), dim3(256), 0, st, reinterpret_cast<const double*>(base + o_rf),
-                       reinterpret_cast<const double*>(base + o_gx), reinterpret_cast<const double*>(base + o_gy),
-                       reinterpret_cast<const double*>(base + o_x), reinterpret_cast<const double*>(base + o_y),
-                       reinterpret_cast<const double*>(base + o_sc), reinterpret_cast<const Abr2PulseDev*>(base + o_pd),
-                       reinterpret_cast<const SimBlock*>(base + o_bk), mode, reinterpret_cast<double*>(out),
+    S.upload(4 * (size_t)O * 8, st);
+    double2* out = S.dev<double2>(S.o_out);                     // a: O entries, then b: O entries
+    hipLaunchKernelGGL(k_abr2_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_rf), S.dev<const double>(o_gx),
+                       S.dev<const double>(o_gy), S.dev<const double>(o_x), S.dev<const double>(o_y), S.dev<const double>(S.o_sc),
+                       S.dev<const Abr2PulseDev>(S.o_pd), S.dev<const SimBlock>(S.o_bk), mode, reinterpret_cast<double*>(out),
                        reinterpret_cast<double*>(out + O));
-    MBFIR_HIP(hipGetLastError());
     std::vector<double2> h(2 * (size_t)O);
-    MBFIR_HIP(hipMemcpyAsync(h.data(), out, h.size() * 16, hipMemcpyDeviceToHost, st));
-    MBFIR_HIP(hipStreamSynchronize(st));
-    MBFIR_HIP(hipGetLastError());
+    S.download(h.data(), h.size() * 16, st);
     unpack_cplx(O, h.data(), a_re, a_im);
     unpack_cplx(O, h.data() + O, b_re, b_im);
 }

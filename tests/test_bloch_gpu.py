@@ -1,4 +1,6 @@
-"""Device forward simulation (mbfir_abr) and the dzrf_mb driver end to end on the GPU."""
+"""Device forward simulation (mbfir_abr, mbfir_abr2, mbfir_bloch) and the dzrf_mb driver end to end on the GPU."""
+import ctypes
+import importlib.util
 import json
 import os
 
@@ -180,3 +182,125 @@ def test_device_bloch_closes_the_loop_with_abr_as_sim_rf_spectral_runs_it():
         assert mx.shape == (2048, 1)
         assert np.abs(mx[:, 0] + 1j * my[:, 0] - 2 * av * np.conj(bv)).max() <= tol
         assert np.abs(mz[:, 0] - (1 - 2 * np.abs(bv) ** 2)).max() <= tol
+
+
+# ---- the single calls at the boundary shapes, against the CPU oracle ----------------------------------------------------------
+# mbfir_bloch / mbfir_abr / mbfir_abr2 run as the batch of one pulse at scale 1.0, so the shapes at which a 256-sample LDS tile or
+# a 256-point workgroup is exactly full, or one over, are pinned here against the oracle directly.
+TOL = 1e-12                                  # the bound of every device simulator against oracle/bloch.py in this file
+BLOCH_NT = [1, 256, 257]
+BLOCH_SHAPES = [(1, 1), (16, 16), (257, 1)]                    # (nf, npos): 1, 256 and 257 pairs
+BLOCH_SHAPES_RECORD = [(1, 1), (3, 2)]                         # the record modes: the output stays small
+
+
+def bloch_case(mode, nt, nf, npos, h1=False):
+    """b1, gr, intervals, t1, t2, df, pos, m0 of one mbfir.bloch call (H-1 case: one gradient and position axis)."""
+    rng = np.random.default_rng(1000 * mode + 10 * nt + nf + npos + h1)
+    b1 = (rng.standard_normal(nt) + 1j * rng.standard_normal(nt)) * 0.05      # G
+    gr = rng.standard_normal((nt, 1 if h1 else 3)) * 0.2                      # G/cm
+    ts = rng.uniform(2e-6, 6e-6, nt)                                          # s
+    t1, t2 = (2e-3, 1e-3) if mode & 1 else (0.08, 0.03)
+    df = np.linspace(-3000, 3000, nf) + rng.uniform(-10, 10)
+    pos = rng.standard_normal((npos, 1 if h1 else 3))
+    m0 = rng.standard_normal((nf, npos, 3)) * 0.3
+    return b1, gr, ts, t1, t2, df, pos, m0
+
+
+def bloch_cases():
+    """(mode, nt, nf, npos) of every case of test_single_bloch_at_the_boundary_shapes"""
+    return [(mode, nt, nf, npos) for mode in range(4) for nt in BLOCH_NT
+            for nf, npos in (BLOCH_SHAPES_RECORD if mode & 2 else BLOCH_SHAPES)]
+
+
+def steady_state_margin(b1, gr, ts, t1, t2, df, pos, gamma=bloch.GAMMA_C13):
+    """Smallest singular value of I - A over every (frequency, position), with the oracle alone: the pulse maps M to A M + B, so
+    B is the endpoint from M = 0 and the columns of A are the endpoints from the unit vectors, less B."""
+    nf, npos = len(df), len(pos)
+    end = [bloch.blochsimfz(b1, gr, ts, t1, t2, df, pos, 0, np.broadcast_to(v, (nf, npos, 3)), gamma=gamma)[:, :, 0, :]
+           for v in np.concatenate([np.zeros((1, 3)), np.eye(3)])]
+    A = np.stack([e - end[0] for e in end[1:]], -1)
+    return float(np.linalg.svd(np.eye(3) - A, compute_uv=False).min())
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3])
+def test_single_bloch_at_the_boundary_shapes(mode):
+    """mbfir.bloch with its in / out magnetisation against blochsimfz: pulse lengths 1, 256, 257 at 1, 256 and 257 pairs."""
+    for _, nt, nf, npos in [c for c in bloch_cases() if c[0] == mode]:
+        b1, gr, ts, t1, t2, df, pos, m0 = bloch_case(mode, nt, nf, npos)
+        if mode & 1:
+            assert steady_state_margin(b1, gr, ts, t1, t2, df, pos) > 1e-9
+        ref = bloch.blochsimfz(b1, gr, ts, t1, t2, df, pos, mode, m0)
+        mx, my, mz = mbfir.bloch(b1, gr, ts, t1, t2, df, pos, mode, m0[..., 0], m0[..., 1], m0[..., 2])
+        assert mx.shape == ((nf, npos, nt) if mode & 2 and nt > 1 else (nf, npos))
+        err = np.abs(np.stack([mx, my, mz], -1).reshape(ref.shape) - ref).max()
+        print("bloch mode %d, nt %d, (%d, %d): %.3g" % (mode, nt, nf, npos, err))
+        assert err <= TOL, (mode, nt, nf, npos)
+
+
+def test_single_bloch_h1_with_end_times():
+    b1, gr, ts, t1, t2, df, pos, m0 = bloch_case(0, 257, 16, 16, h1=True)
+    ref = bloch.blochsimfz(b1, gr, ts, t1, t2, df, pos[:, 0], 0, m0, gamma=bloch.GAMMA_H1)
+    mx, my, mz = mbfir.bloch(b1, gr[:, 0], np.cumsum(ts), t1, t2, df, pos[:, 0], 0, m0[..., 0], m0[..., 1], m0[..., 2], nucleus="H-1")
+    assert np.abs(np.stack([mx, my, mz], -1).reshape(ref.shape) - ref).max() <= TOL
+
+
+def _rf(rng, n):
+    return (rng.standard_normal(n) + 1j * rng.standard_normal(n)) * (np.pi / n)
+
+
+@pytest.mark.parametrize("hard_pulse", [False, True])
+def test_single_abrm_1d_at_the_boundary_shapes(hard_pulse):
+    """mbfir.abrm against the oracle, n and nx each 1, 256, 257; the oracle's hard-pulse model has no form with g."""
+    rng = np.random.default_rng(50 + hard_pulse)
+    for n in (1, 256, 257):
+        rf, g = _rf(rng, n), rng.uniform(0.5, 1.5, n) * 2 * np.pi / n
+        for nx in (1, 256, 257):
+            x = np.linspace(-n / 2 - 3, n / 2 + 3, nx)
+            a1, b1 = mbfir.abrm(rf, x, hard_pulse=hard_pulse)
+            a0, b0 = bloch.hard_pulse_ab(rf, x) if hard_pulse else bloch.abrm(rf, x)
+            assert a1.shape == (nx,) and max(np.abs(a1 - a0).max(), np.abs(b1 - b0).max()) <= TOL, (n, nx)
+            if not hard_pulse:
+                a1, b1 = mbfir.abrm(rf, g, x)
+                a0, b0 = bloch.abrm(rf, g, x)
+                assert max(np.abs(a1 - a0).max(), np.abs(b1 - b0).max()) <= TOL, (n, nx)
+
+
+def test_single_abrm_2d_at_the_boundary_shapes():
+    """mbfir.abrm(rf, g, x, y) against the NumPy restatement of tests/test_abr2batch_gpu.py (itself checked against the oracle
+    there), with g and without."""
+    spec = importlib.util.spec_from_file_location("abr2batch_gpu", os.path.join(os.path.dirname(__file__), "test_abr2batch_gpu.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rng = np.random.default_rng(60)
+    for n in (1, 257):
+        rf = _rf(rng, n)
+        g = rng.uniform(0.5, 1.5, n) * 2 * np.pi / n + 1j * rng.uniform(-1.5, 1.5, n) * 2 * np.pi / n
+        for nx, ny in ((1, 1), (16, 16), (257, 1), (1, 257)):
+            x, y = np.linspace(-n / 2 - 3, n / 2 + 3, nx), np.linspace(-n / 3, n / 3 + 1, ny)
+            for gv in (g, None):
+                a1, b1 = mbfir.abrm(rf, gv, x, y)
+                a0, b0 = mod.abr2_np(rf, gv, x, y)
+                assert a1.shape == (nx, ny) and max(np.abs(a1 - a0).max(), np.abs(b1 - b0).max()) <= TOL, (n, nx, ny, gv is None)
+
+
+def test_argument_errors_of_the_single_raw_calls_leave_the_context_usable():
+    ctx = mbfir.get_context()
+    lib, p = mbfir.load_library(), mbfir._ptr
+    nul = ctypes.cast(None, ctypes.POINTER(ctypes.c_double))
+    v = np.full(8, 0.01)
+    z, df, m = np.zeros(8), np.zeros(1), [np.array([0.0]), np.array([0.0]), np.array([1.0])]
+
+    def raw_bloch(mode=0, t1=0.1, df=p(df)):
+        return lib.mbfir_bloch(ctx._h, 8, p(v), p(z), nul, nul, nul, p(np.full(8, 4e-6)), t1, 0.1, 1, df, 1, nul, nul, nul, mode,
+                               mbfir.GAMMA_C13, *[p(o) for o in m])
+
+    assert raw_bloch(mode=4) == mbfir.E_ARG and raw_bloch(t1=0.0) == mbfir.E_ARG and raw_bloch(df=nul) == mbfir.E_ARG
+    out = [np.zeros(2) for _ in range(4)]
+    x = np.array([0.0, 1.0])
+    assert lib.mbfir_abr(ctx._h, 8, p(v), p(z), nul, 2, p(x), 2, *[p(o) for o in out]) == mbfir.E_ARG
+    assert lib.mbfir_abr2(ctx._h, 8, p(v), p(z), nul, nul, 2, p(x), 0, p(x), *[p(o) for o in out]) == mbfir.E_ARG
+    assert ctx.last_error().startswith("abr2: need")
+    assert raw_bloch() == 0 and m[2][0] < 1.0                                          # the context still works
+    assert lib.mbfir_abr(ctx._h, 8, p(v), p(z), nul, 2, p(x), 0, *[p(o) for o in out]) == 0
+    a0, b0 = bloch.abrm(v, x)
+    assert np.abs(out[0] + 1j * out[1] - a0).max() <= TOL and np.abs(out[2] + 1j * out[3] - b0).max() <= TOL
