@@ -319,6 +319,23 @@ int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* 
 int mbfir_abr2_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
                      const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                      int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im);
+/* ---- Adjoints of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples -----------------------------------------------
+ * The vector-Jacobian product of the forward call, in both models: the forward call's arguments, with the four output planes
+ * replaced by the cotangents of a and b in the same layout (ca, cb; dL = Re(conj(ca) da + conj(cb) db) for a real L, that is ca =
+ * dL/dRe a + i dL/dIm a), and two outputs of one entry per rf sample, g_re = dL/dRe rf and g_im = dL/dIm rf, laid out as rf_re /
+ * rf_im.  A sample's gradient is summed over the points of its pulse and over the scales (scale s contributes s times the gradient
+ * with respect to s rf); g / gx / gy, the grids and the scales are not differentiated.  One upload, two launches (the sweeps with
+ * one partial per workgroup and sample, then the sum of a pulse's partials over chunks and scales in index order), one download; no
+ * atomics, so a pulse's gradient bits depend only on the pulse, its grid and the scale list.  The argument checks and their
+ * MBFIR_E_ARG messages are those of the forward calls (a cotangent or gradient plane NULL is a required array NULL). */
+int mbfir_abr_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                        const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im, double* g_re,
+                        double* g_im);
+int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, const double* ca_re, const double* ca_im,
+                         const double* cb_re, const double* cb_im, double* g_re, double* g_im);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]
  *   points ((frequency, position) pairs, positions, or nx ny points) at nscale scales: 4 ints (pulse, scale, chunk, 0) per workgroup in launch
  *   order into out (may be NULL).  Returns the number of workgroups; -1 for npulse or nscale < 1, an ntime or npoint < 1, or a

@@ -128,6 +128,10 @@ SYMBOLS = {
                                   _dp]),
     "mbfir_abr2_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int, _dp,
                                    C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp, _dp,
+                                      _dp, _dp, _dp, _dp]),
+    "mbfir_abr2_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
+                                       _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                  C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
@@ -688,6 +692,7 @@ from . import spiral        # noqa: E402  (dz2d.m / csg.m spiral 2D pulses and t
 from .spiral import csg, dz2d, dz2d_batch, ktog, ktos, gt2cm   # noqa: E402
 from . import ssmb          # noqa: E402  (multiband spectral-spatial pulses: dzrf_mb's spectral beta, device 2D SLR)
 from .ssmb import dzss_mb, dzss_mb_batch, fold_bands   # noqa: E402
+from . import torchsim      # noqa: E402  (torch.autograd wrappers of abr_batch / abr2_batch; torch is imported on first use)
 # `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
 # sys.modules (`from mbfir.dzrf import dzrf_mb`), and the function carries that module's public names for attribute access.
 dzrf = slrclassic.dzrf
@@ -1057,38 +1062,88 @@ def _rf_g(pulse, q, who, gtype):
     return rf, g
 
 
+def _abr_args(who, pulses, x, scales, convention):
+    """The checked arguments of abr_batch and abr_vjp_batch: (scales, rf per pulse, g per pulse, grids, points per pulse)."""
+    pulses, sc = list(pulses), _vec(scales)
+    if not pulses:
+        raise ValueError("%s: no pulses" % who)
+    if len(sc) == 0:
+        raise ValueError("%s: the scale list is empty" % who)
+    if convention not in ("abrm", "abr"):
+        raise ValueError("%s: convention must be 'abrm' or 'abr'" % who)
+    P = len(pulses)
+    rfs, gs = zip(*[_rf_g(p, q, who, np.float64) for q, p in enumerate(pulses)])
+    xs = [_vec(v) for v in _per_pulse(x, P)]
+    if any(len(v) == 0 for v in xs):
+        raise ValueError("%s: an empty x" % who)
+    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
+    return sc, rfs, gs, xs, nx
+
+
+def _abr_call(fn, ctx, sc, rfs, gs, xs, hard_pulse, planes):
+    """mbfir_abr_batch or mbfir_abr_vjp_batch on the checked arguments; planes: the arrays after `mode`."""
+    rf = np.concatenate(rfs)
+    rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
+            _ptr(_vec(np.concatenate(gs))), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(sc),
+            _ptr(sc), 1 if hard_pulse else 0, *[_ptr(o) for o in planes])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+
+
 def abr_batch(pulses, x, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
     """Many `abrm` / `abr` simulations in one launch (mbfir_abr_batch): every pulse at every scale.  Each pulse is rf (radians per
     sample; 2 pi / n per sample as in abrm) or a tuple (rf, g) with abrm's per-sample g.  x: one array shared by every pulse, or a
     Python list of one array per pulse.  Scale s multiplies rf.  hard_pulse: abrm's hard-pulse model; convention 'abr' returns
     abr.m's b = -conj(b).  Returns a list of (a, b) per pulse, each of shape (S, nx)."""
-    pulses, sc = list(pulses), _vec(scales)
-    if not pulses:
-        raise ValueError("abr_batch: no pulses")
-    if len(sc) == 0:
-        raise ValueError("abr_batch: the scale list is empty")
-    if convention not in ("abrm", "abr"):
-        raise ValueError("abr_batch: convention must be 'abrm' or 'abr'")
-    P, S = len(pulses), len(sc)
-    rfs, gs = zip(*[_rf_g(p, q, "abr_batch", np.float64) for q, p in enumerate(pulses)])
-    xs = [_vec(v) for v in _per_pulse(x, P)]
-    if any(len(v) == 0 for v in xs):
-        raise ValueError("abr_batch: an empty x")
-    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
+    sc, rfs, gs, xs, nx = _abr_args("abr_batch", pulses, x, scales, convention)
+    P, S = len(rfs), len(sc)
     ooff = _offsets([S * k for k in nx])
     out = [np.zeros(int(ooff[-1])) for _ in range(4)]
-    rf = np.concatenate(rfs)
     ctx = ctx or get_context()
-    rc = load_library().mbfir_abr_batch(ctx._h, P, _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
-                                        _ptr(_vec(np.concatenate(gs))), len(xs), _lptr(_offsets([len(v) for v in xs])),
-                                        _ptr(_vec(np.concatenate(xs))), S, _ptr(sc), 1 if hard_pulse else 0, *[_ptr(o) for o in out])
-    if rc == E_ARG:
-        raise ValueError(ctx.last_error())
-    _check(ctx, rc)
+    _abr_call(load_library().mbfir_abr_batch, ctx, sc, rfs, gs, xs, hard_pulse, out)
     a_all, b_all = out[0] + 1j * out[1], out[2] + 1j * out[3]
     if convention == "abr":
         b_all = -np.conj(b_all)
     return [(a_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q]), b_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q])) for q in range(P)]
+
+
+def _cotangents(who, cot, shapes, convention):
+    """cot: one (ca, cb) per pulse in the shapes the forward call returns -> the four concatenated planes of the C call.  Under
+    convention 'abr' the forward call returns -conj(b), so its cotangent maps back as cb -> -conj(cb)."""
+    cot = list(cot)
+    if len(cot) != len(shapes):
+        raise ValueError("%s: %d cotangent pairs for %d pulses" % (who, len(cot), len(shapes)))
+    cas, cbs = [], []
+    for q, (pair, shape) in enumerate(zip(cot, shapes)):
+        if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+            raise ValueError("%s: the cotangent of pulse %d must be a pair (ca, cb)" % (who, q))
+        ca, cb = (np.asarray(v, dtype=np.complex128) for v in pair)
+        if ca.shape != shape or cb.shape != shape:
+            raise ValueError("%s: the cotangents of pulse %d have shapes %s and %s, the forward call returns %s"
+                             % (who, q, ca.shape, cb.shape, shape))
+        cas.append(ca.ravel())
+        cbs.append(cb.ravel())
+    ca, cb = np.concatenate(cas), np.concatenate(cbs)
+    if convention == "abr":
+        cb = -np.conj(cb)
+    return [_vec(ca.real), _vec(ca.imag), _vec(cb.real), _vec(cb.imag)]
+
+
+def abr_vjp_batch(pulses, x, cot, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The adjoint of abr_batch with respect to rf (mbfir_abr_vjp_batch): pulses, x, scales, hard_pulse and convention as for
+    abr_batch; cot: a list of (ca, cb) per pulse, the cotangents of the (a, b) that abr_batch returns, in their shapes (S, nx), with
+    ca = dL/dRe a + i dL/dIm a for a real L (torch's convention).  Returns a list of complex (n,) gradients dL/dRe rf + i dL/dIm rf,
+    summed over the points and the scales.  Deterministic: a pulse's gradient bits depend only on the pulse, its grid and the
+    scales.  g and x are not differentiated."""
+    sc, rfs, gs, xs, nx = _abr_args("abr_vjp_batch", pulses, x, scales, convention)
+    planes = _cotangents("abr_vjp_batch", cot, [(len(sc), k) for k in nx], convention)
+    roff = _offsets([len(r) for r in rfs])
+    grad = [np.zeros(int(roff[-1])) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_vjp_batch, ctx, sc, rfs, gs, xs, hard_pulse, planes + grad)
+    g_all = grad[0] + 1j * grad[1]
+    return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
 
 
 def _grids(v, npulse, who, name):
@@ -1104,6 +1159,36 @@ def _grids(v, npulse, who, name):
     return vs
 
 
+def _abr2_args(who, pulses, x, y, scales, convention):
+    """The checked arguments of abr2_batch and abr2_vjp_batch: (scales, rf per pulse, complex g per pulse, x grids, y grids, nx
+    per pulse, ny per pulse)."""
+    pulses, sc = list(pulses), _vec(scales)
+    if not pulses:
+        raise ValueError("%s: no pulses" % who)
+    if len(sc) == 0:
+        raise ValueError("%s: the scale list is empty" % who)
+    if convention not in ("abrm", "abr"):
+        raise ValueError("%s: convention must be 'abrm' or 'abr'" % who)
+    P = len(pulses)
+    rfs, gs = zip(*[_rf_g(p, q, who, np.complex128) for q, p in enumerate(pulses)])
+    xs, ys = _grids(x, P, who, "x"), _grids(y, P, who, "y")
+    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
+    ny = [len(ys[0 if len(ys) == 1 else q]) for q in range(P)]
+    return sc, rfs, gs, xs, ys, nx, ny
+
+
+def _abr2_call(fn, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes):
+    """mbfir_abr2_batch or mbfir_abr2_vjp_batch on the checked arguments; planes: the arrays after `mode`."""
+    rf, g = np.concatenate(rfs), np.concatenate(gs)
+    rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)), _ptr(_vec(g.real)),
+            _ptr(_vec(g.imag)), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(ys),
+            _lptr(_offsets([len(v) for v in ys])), _ptr(_vec(np.concatenate(ys))), len(sc), _ptr(sc), 1 if hard_pulse else 0,
+            *[_ptr(o) for o in planes])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+
+
 def abr2_batch(pulses, x, y, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
     """Many 2D `abrm(rf, g, x, y)` / `abr` simulations in one launch (mbfir_abr2_batch): every pulse at every scale.  Each pulse is
     rf (radians per sample; 2 pi / n per sample along x as in abrm) or a tuple (rf, g) with abrm's complex g (Re g the x gradient,
@@ -1111,35 +1196,31 @@ def abr2_batch(pulses, x, y, *, scales=(1.0,), hard_pulse=False, convention="abr
     rf.  hard_pulse: the hard-pulse model (free precession by x Re g + y Im g, then the hard pulse of the sample) that the 2D
     `abrm` does not offer; convention 'abr' returns abr.m's b = -conj(b).  Returns a list of (a, b) per pulse, each of shape
     (S, nx, ny).  Without hard_pulse the bits are those of `abrm(rf * s, g, x, y)`."""
-    pulses, sc = list(pulses), _vec(scales)
-    if not pulses:
-        raise ValueError("abr2_batch: no pulses")
-    if len(sc) == 0:
-        raise ValueError("abr2_batch: the scale list is empty")
-    if convention not in ("abrm", "abr"):
-        raise ValueError("abr2_batch: convention must be 'abrm' or 'abr'")
-    P, S = len(pulses), len(sc)
-    rfs, gs = zip(*[_rf_g(p, q, "abr2_batch", np.complex128) for q, p in enumerate(pulses)])
-    xs, ys = _grids(x, P, "abr2_batch", "x"), _grids(y, P, "abr2_batch", "y")
-    nx = [len(xs[0 if len(xs) == 1 else q]) for q in range(P)]
-    ny = [len(ys[0 if len(ys) == 1 else q]) for q in range(P)]
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args("abr2_batch", pulses, x, y, scales, convention)
+    P, S = len(rfs), len(sc)
     ooff = _offsets([S * k * j for k, j in zip(nx, ny)])
     out = [np.zeros(int(ooff[-1])) for _ in range(4)]
-    rf, g = np.concatenate(rfs), np.concatenate(gs)
     ctx = ctx or get_context()
-    rc = load_library().mbfir_abr2_batch(ctx._h, P, _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
-                                         _ptr(_vec(g.real)), _ptr(_vec(g.imag)), len(xs), _lptr(_offsets([len(v) for v in xs])),
-                                         _ptr(_vec(np.concatenate(xs))), len(ys), _lptr(_offsets([len(v) for v in ys])),
-                                         _ptr(_vec(np.concatenate(ys))), S, _ptr(sc), 1 if hard_pulse else 0,
-                                         *[_ptr(o) for o in out])
-    if rc == E_ARG:
-        raise ValueError(ctx.last_error())
-    _check(ctx, rc)
+    _abr2_call(load_library().mbfir_abr2_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, out)
     a_all, b_all = out[0] + 1j * out[1], out[2] + 1j * out[3]
     if convention == "abr":
         b_all = -np.conj(b_all)
     return [(a_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q], ny[q]), b_all[ooff[q]:ooff[q + 1]].reshape(S, nx[q], ny[q]))
             for q in range(P)]
+
+
+def abr2_vjp_batch(pulses, x, y, cot, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The adjoint of abr2_batch with respect to rf (mbfir_abr2_vjp_batch): as abr_vjp_batch, with abr2_batch's arguments and the
+    cotangents (ca, cb) of each pulse in the shape (S, nx, ny).  Returns a list of complex (n,) gradients; g, x and y are not
+    differentiated."""
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args("abr2_vjp_batch", pulses, x, y, scales, convention)
+    planes = _cotangents("abr2_vjp_batch", cot, [(len(sc), k, j) for k, j in zip(nx, ny)], convention)
+    roff = _offsets([len(r) for r in rfs])
+    grad = [np.zeros(int(roff[-1])) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_vjp_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes + grad)
+    g_all = grad[0] + 1j * grad[1]
+    return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

@@ -868,25 +868,51 @@ int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double
                                    gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, mode, mx, my, mz));
 }
 
+// The argument checks of mbfir_abr_batch / mbfir_abr2_batch, shared with their adjoints (who: the call's name in the message; two: the
+// 2D calls, which alone have y grids; arrays: the caller's own required arrays are all there).  0, or MBFIR_E_ARG with ctx->err set.
+// npoint (npulse entries) receives the points per pulse.
+static int abr_batch_check(mbfir_ctx* ctx, const char* who, bool two, int npulse, const long* roff, int nxgrid, const long* xoff,
+                           int nygrid, const long* yoff, int nscale, int mode, bool arrays, std::vector<long>& npoint) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (npulse < 1) return bad("no pulses");
+    if (nscale < 1) return bad("the scale list is empty");
+    if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
+    if ((nxgrid != 1 && nxgrid != npulse) || (two && nygrid != 1 && nygrid != npulse))
+        return bad(two ? "nxgrid and nygrid must be 1 or npulse" : "nxgrid must be 1 or npulse");
+    if (!arrays) return bad("a required array is null");
+    if (const int e = sim_pulse_offsets_bad(roff, npulse, "roff", bad)) return e;
+    if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
+    if (two)
+        if (const char* why = sim_offsets_bad(yoff, nygrid)) return bad(std::string("inconsistent offsets: yoff ") + why);
+    npoint.assign(npulse, 0);
+    std::vector<long> ntout(npulse, 1);
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p, yg = nygrid == 1 ? 0 : p;
+        npoint[p] = (xoff[xg + 1] - xoff[xg]) * (two ? yoff[yg + 1] - yoff[yg] : 1L);      // each factor < 2^31
+    }
+    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
+        return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+// The adjoints keep one partial per (workgroup, sample): false when their count overflows or exceeds 2^56.
+static bool vjp_partials_fit(int npulse, int nscale, const long* roff, const long* npoint) {
+    long total = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e;
+        if (__builtin_mul_overflow((npoint[p] + 255) / 256 * nscale, roff[p + 1] - roff[p], &e) ||
+            __builtin_add_overflow(total, e, &total))
+            return false;
+    }
+    return total <= (1L << 56);
+}
+
 int mbfir_abr_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
                     int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
                     double* a_im, double* b_re, double* b_im) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "abr_batch: " + why; return MBFIR_E_ARG; };
-    if (npulse < 1) return bad("no pulses");
-    if (nscale < 1) return bad("the scale list is empty");
-    if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
-    if (nxgrid != 1 && nxgrid != npulse) return bad("nxgrid must be 1 or npulse");
-    if (!roff || !rf_re || !rf_im || !xoff || !x || !scales || !a_re || !a_im || !b_re || !b_im) return bad("a required array is null");
-    if (const int e = sim_pulse_offsets_bad(roff, npulse, "roff", bad)) return e;
-    if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
-    std::vector<long> npoint(npulse), ntout(npulse, 1);
-    for (int p = 0; p < npulse; ++p) {
-        const int xg = nxgrid == 1 ? 0 : p;
-        npoint[p] = xoff[xg + 1] - xoff[xg];
-    }
-    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
-        return bad("the output size or the workgroup count overflows");
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales && a_re && a_im && b_re && b_im;
+    if (const int e = abr_batch_check(ctx, "abr_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays, npoint)) return e;
     MBFIR_TRY(ctx, abr_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
                                  mode, a_re, a_im, b_re, b_im));
 }
@@ -895,25 +921,47 @@ int mbfir_abr2_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double*
                      const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                      int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "abr2_batch: " + why; return MBFIR_E_ARG; };
-    if (npulse < 1) return bad("no pulses");
-    if (nscale < 1) return bad("the scale list is empty");
-    if (mode != 0 && mode != 1) return bad("mode must be 0 or 1");
-    if ((nxgrid != 1 && nxgrid != npulse) || (nygrid != 1 && nygrid != npulse)) return bad("nxgrid and nygrid must be 1 or npulse");
-    if (!roff || !rf_re || !rf_im || !xoff || !x || !yoff || !y || !scales || !a_re || !a_im || !b_re || !b_im)
-        return bad("a required array is null");
-    if (const int e = sim_pulse_offsets_bad(roff, npulse, "roff", bad)) return e;
-    if (const char* why = sim_offsets_bad(xoff, nxgrid)) return bad(std::string("inconsistent offsets: xoff ") + why);
-    if (const char* why = sim_offsets_bad(yoff, nygrid)) return bad(std::string("inconsistent offsets: yoff ") + why);
-    std::vector<long> npoint(npulse), ntout(npulse, 1);
-    for (int p = 0; p < npulse; ++p) {
-        const int xg = nxgrid == 1 ? 0 : p, yg = nygrid == 1 ? 0 : p;
-        npoint[p] = (xoff[xg + 1] - xoff[xg]) * (yoff[yg + 1] - yoff[yg]);      // each factor < 2^31
-    }
-    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
-        return bad("the output size or the workgroup count overflows");
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales && a_re && a_im && b_re && b_im;
+    if (const int e = abr_batch_check(ctx, "abr2_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays, npoint))
+        return e;
     MBFIR_TRY(ctx, abr2_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid, yoff,
                                   y, nscale, scales, mode, a_re, a_im, b_re, b_im));
+}
+
+int mbfir_abr_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                        const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im, double* g_re,
+                        double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales && ca_re && ca_im && cb_re && cb_im && g_re && g_im;
+    if (const int e = abr_batch_check(ctx, "abr_vjp_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays, npoint))
+        return e;
+    if (!vjp_partials_fit(npulse, nscale, roff, npoint.data())) {
+        ctx->err = "abr_vjp_batch: the output size or the workgroup count overflows";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, abr_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
+                                     mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im));
+}
+
+int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, const double* ca_re, const double* ca_im,
+                         const double* cb_re, const double* cb_im, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales && ca_re && ca_im && cb_re && cb_im && g_re && g_im;
+    if (const int e = abr_batch_check(ctx, "abr2_vjp_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (!vjp_partials_fit(npulse, nscale, roff, npoint.data())) {
+        ctx->err = "abr2_vjp_batch: the output size or the workgroup count overflows";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, abr2_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
+                                      yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im));
 }
 
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {

@@ -1,4 +1,4 @@
-// Host side of the pulse tools (slr.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// Host side of the pulse tools (slr.hip, simgrad.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
 // api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
 // (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
 // compiler.
@@ -43,6 +43,17 @@ void abr_batch_run(int device, void* stream, int npulse, const long* roff, const
 void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
                     const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                     int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im);
+// Adjoints of abr_batch_run / abr2_batch_run with respect to rf (simgrad.hip k_abr_vjp_batch, k_abr2_vjp_batch, k_abr_vjp_fold): the
+// forward call's inputs; c*: the cotangents of a and b in the forward outputs' layout (dL = Re(conj(ca) da + conj(cb) db)); g_re /
+// g_im: dL / d Re rf, dL / d Im rf per rf sample, summed over the pulse's points and scales.  One upload, two launches, one download.
+void abr_vjp_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                       const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                       const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im, double* g_re,
+                       double* g_im);
+void abr2_vjp_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                        const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                        const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
+                        const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

@@ -5,12 +5,12 @@
 //   ab2rf : the n-step inverse SLR recursion in one workgroup, the two polynomials in LDS (ping-pong)
 // k_ab2rf / k_b2rf_batch share ab2rf_recursion, and k_abr_batch / k_abr2_batch share abr_step: one definition each.  The forward
 // simulators exist once, as batch kernels: a single pulse is the batch of one pulse at scale 1.0 (mbfir_abr, mbfir_abr2, mbfir_bloch).
+// abr_step, the descriptors AbrPulseDev / Abr2PulseDev and the host Staging are in sim_dev.h, which simgrad.hip (the adjoints) shares.
 #include "dev_common.h"
 #include "pulse.h"
+#include "sim_dev.h"
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <optional>
 
 namespace mbfir {
 
@@ -144,46 +144,6 @@ __global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il,
     ab2rf_recursion<1024>(A[0], B[0], SLR_MAXN, n, cs, reinterpret_cast<double2*>(rf_il));
 }
 
-// Forward simulation of an RF pulse over off-resonance: Cayley-Klein parameters per position.
-//   mode 0: rf_tools/abrm.m:40-57 -- one rotation about (Re rf, Im rf, x g_m) per sample
-//   mode 1: the hard-pulse model the inverse SLR transform inverts exactly -- free precession by x g_m on beta, then
-//           the hard pulse of the sample
-// abr_step is one sample of either model for one position (r: the rf sample, om: the precession angle of the sample; mode is
-// uniform over the workgroup).  k_abr_batch (om = x g) and k_abr2_batch (om = x gx + y gy) step through it.  The state goes in and
-// comes back by value: through references the kernels compile to other fused products (the compiler then promotes a and b to
-// registers only after inlining, in another order), and the results differ from before in the last bits.
-struct CayleyKlein {
-    double2 a, b;
-};
-__device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, double2 a, double2 b) {
-    double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
-    if (mode == 0) {
-        const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
-        double sn, cs;
-        sincos(0.5 * phi, &sn, &cs);
-        const double inv = phi > 0 ? sn / phi : 0.0;
-        av = make_double2(cs, -om * inv);
-        bv = make_double2(r.y * inv, -r.x * inv);                  // -i (n1 + i n2) sin
-        const double2 an = make_double2(av.x * a.x - av.y * a.y - (bv.x * b.x + bv.y * b.y),
-                                        av.x * a.y + av.y * a.x - (bv.x * b.y - bv.y * b.x));
-        const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
-                                        bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
-        a = an; b = bn;
-    } else {
-        const double th = hypot(r.x, r.y);
-        double sn, cs, sz, cz;
-        sincos(0.5 * th, &sn, &cs);
-        sincos(-om, &sz, &cz);                                   // z^-1
-        const double2 zb = make_double2(cz * b.x - sz * b.y, cz * b.y + sz * b.x);
-        const double inv = th > 0 ? sn / th : 0.0;
-        const double2 S = make_double2(-r.y * inv, r.x * inv);    // i e^{i arg rf} sin(th/2)
-        const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
-        const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
-        a = an; b = bn;
-    }
-    return CayleyKlein{a, b};
-}
-
 // ------------------------------------------------------------------------------------------------
 // Bloch-equation simulation with relaxation: bloch_simulation/blochC.c calcrotmat (:171-236),
 // blochsim (:283-418), blochsimfz (:422-512).  One thread per (off-resonance, position) pair -- the reference's
@@ -232,10 +192,6 @@ constexpr int BLOCH_CH = 256;
 
 // One thread per position.  rf (interleaved) is scaled while it is staged; g holds one weight per sample of every pulse (the host
 // writes 2 pi / n where a pulse has none).  Output: S x nx per pulse, scale-major.
-struct AbrPulseDev {
-    long r_off, x_off, o_off;     // first rf / g sample, first position, first output entry
-    int n, nx;
-};
 __global__ __launch_bounds__(256) void k_abr_batch(const double* __restrict__ rf_il, const double* __restrict__ g,
                                                    const double* __restrict__ x, const double* __restrict__ scales,
                                                    const AbrPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
@@ -658,10 +614,6 @@ void slr_slr2d_batch_run(int device, void* stream, int m, int n, int count, cons
 // about (Re rf, Im rf, x gx + y gy) per sample, mode 1 the hard-pulse model with that precession angle.  Output: S x nx x ny per
 // pulse, scale-major.  The precession angle is defined as fma(x, gx, y gy): left as x gx + y gy the compiler may fuse the other
 // product, and callers' bits would move.
-struct Abr2PulseDev {
-    long r_off, x_off, y_off, o_off;     // first rf / gx / gy sample, first x, first y, first output entry
-    int n, nx, ny, pad;
-};
 __global__ __launch_bounds__(256) void k_abr2_batch(const double* __restrict__ rf_il, const double* __restrict__ gx,
                                                     const double* __restrict__ gy, const double* __restrict__ x,
                                                     const double* __restrict__ y, const double* __restrict__ scales,
@@ -759,47 +711,6 @@ long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscal
     return k;
 }
 
-namespace {
-// One call of a batched simulator.  The caller adds its own sections, then add_tables; fills its sections (at<T>: add moves
-// the buffer, so take pointers after the last add); uploads; launches nblk workgroups on the dev<T> addresses; downloads.
-struct Staging {
-    std::vector<char> h;                                  // host sections, each 256-byte aligned, uploaded with one copy
-    std::optional<DevBuf> buf;                            // the sections, then the output region
-    size_t o_sc = 0, o_pd = 0, o_bk = 0, o_out = 0;       // scales, per-pulse descriptors, block table; output region
-    long nblk = 0;
-    size_t add(size_t bytes) {
-        const size_t o = (h.size() + 255) & ~size_t(255);
-        h.resize(o + bytes);
-        return o;
-    }
-    template <class T> T* at(size_t o) { return reinterpret_cast<T*>(h.data() + o); }
-    template <class T> T* dev(size_t o) { return reinterpret_cast<T*>(buf->as<char>() + o); }
-    // The sections every simulator has, filled: pd = npulse descriptors of pd_size bytes; ntime / npoint as sim_block_table.
-    void add_tables(int npulse, const void* pd, size_t pd_size, const int* ntime, const long* npoint, int nscale,
-                    const double* scales) {
-        nblk = sim_block_table(npulse, ntime, npoint, nscale, nullptr);
-        o_sc = add((size_t)nscale * 8);
-        o_pd = add(npulse * pd_size);
-        o_bk = add(nblk * sizeof(SimBlock));
-        std::copy(scales, scales + nscale, at<double>(o_sc));
-        std::memcpy(at<char>(o_pd), pd, npulse * pd_size);
-        sim_block_table(npulse, ntime, npoint, nscale, at<SimBlock>(o_bk));
-    }
-    void upload(size_t out_bytes, hipStream_t st) {
-        const size_t up = h.size();
-        o_out = (up + 255) & ~size_t(255);
-        buf.emplace(o_out + out_bytes);
-        MBFIR_HIP(hipMemcpyAsync(buf->p, h.data(), up, hipMemcpyHostToDevice, st));
-    }
-    void download(void* out, size_t out_bytes, hipStream_t st) {     // after the launch
-        MBFIR_HIP(hipGetLastError());
-        MBFIR_HIP(hipMemcpyAsync(out, dev<char>(o_out), out_bytes, hipMemcpyDeviceToHost, st));
-        MBFIR_HIP(hipStreamSynchronize(st));
-        MBFIR_HIP(hipGetLastError());
-    }
-};
-}  // namespace
-
 constexpr double TWOPI_REF = 6.283185;                      // blochC.c:6, the reference's truncated constant
 void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
@@ -872,35 +783,43 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
     std::copy(h.begin() + 2 * O, h.end(), mz);
 }
 
+void abr_stage(AbrStaged& A, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g, int nxgrid,
+               const long* xoff, const double* x, int nscale, const double* scales) {
+    std::vector<AbrPulseDev> pd(npulse);
+    A.ntime.resize(npulse);
+    A.npoint.resize(npulse);
+    A.O = 0;
+    for (int p = 0; p < npulse; ++p) {
+        const int xg = nxgrid == 1 ? 0 : p;
+        pd[p] = AbrPulseDev{roff[p], xoff[xg], A.O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg])};
+        A.ntime[p] = pd[p].n;
+        A.npoint[p] = pd[p].nx;
+        A.O += nscale * A.npoint[p];
+    }
+    const long R = roff[npulse], X = xoff[nxgrid];
+    Staging& S = A.S;
+    A.o_rf = S.add(R * 16); A.o_g = S.add(R * 8); A.o_x = S.add(X * 8);
+    S.add_tables(npulse, pd.data(), sizeof(AbrPulseDev), A.ntime.data(), A.npoint.data(), nscale, scales);
+    pack_cplx(R, rf_re, rf_im, S.at<double2>(A.o_rf));
+    double* gw = S.at<double>(A.o_g);
+    for (int p = 0; p < npulse; ++p)
+        for (long t = roff[p]; t < roff[p + 1]; ++t) gw[t] = g ? g[t] : 2.0 * M_PI / pd[p].n;     // a null g is 2 pi / n per sample
+    std::copy(x, x + X, S.at<double>(A.o_x));
+}
+
 void abr_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
                    int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, double* a_re,
                    double* a_im, double* b_re, double* b_im) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    std::vector<AbrPulseDev> pd(npulse);
-    std::vector<int> nt(npulse);
-    std::vector<long> nx(npulse);
-    long O = 0;                                              // output entries of a (and of b)
-    for (int p = 0; p < npulse; ++p) {
-        const int xg = nxgrid == 1 ? 0 : p;
-        pd[p] = AbrPulseDev{roff[p], xoff[xg], O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg])};
-        nt[p] = pd[p].n;
-        nx[p] = pd[p].nx;
-        O += nscale * nx[p];
-    }
-    const long R = roff[npulse], X = xoff[nxgrid];
-    Staging S;
-    const size_t o_rf = S.add(R * 16), o_g = S.add(R * 8), o_x = S.add(X * 8);
-    S.add_tables(npulse, pd.data(), sizeof(AbrPulseDev), nt.data(), nx.data(), nscale, scales);
-    pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
-    double* gw = S.at<double>(o_g);
-    for (int p = 0; p < npulse; ++p)
-        for (long t = roff[p]; t < roff[p + 1]; ++t) gw[t] = g ? g[t] : 2.0 * M_PI / pd[p].n;     // a null g is 2 pi / n per sample
-    std::copy(x, x + X, S.at<double>(o_x));
+    AbrStaged A;
+    abr_stage(A, npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales);
+    Staging& S = A.S;
+    const long O = A.O;                                         // output entries of a (and of b)
     S.upload(4 * (size_t)O * 8, st);
     double2* out = S.dev<double2>(S.o_out);                     // a: O entries, then b: O entries
-    hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_rf), S.dev<const double>(o_g),
-                       S.dev<const double>(o_x), S.dev<const double>(S.o_sc), S.dev<const AbrPulseDev>(S.o_pd),
+    hipLaunchKernelGGL(k_abr_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(A.o_rf), S.dev<const double>(A.o_g),
+                       S.dev<const double>(A.o_x), S.dev<const double>(S.o_sc), S.dev<const AbrPulseDev>(S.o_pd),
                        S.dev<const SimBlock>(S.o_bk), mode, reinterpret_cast<double*>(out), reinterpret_cast<double*>(out + O));
     std::vector<double2> h(2 * (size_t)O);
     S.download(h.data(), h.size() * 16, st);
@@ -908,41 +827,50 @@ void abr_batch_run(int device, void* stream, int npulse, const long* roff, const
     unpack_cplx(O, h.data() + O, b_re, b_im);
 }
 
-void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
-                    const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
-                    int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
-    MBFIR_HIP(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
+void abr2_stage(Abr2Staged& A, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                int nscale, const double* scales) {
     std::vector<Abr2PulseDev> pd(npulse);
-    std::vector<int> nt(npulse);
-    std::vector<long> npt(npulse);
-    long O = 0;                                              // output entries of a (and of b)
+    A.ntime.resize(npulse);
+    A.npoint.resize(npulse);
+    A.O = 0;
     for (int p = 0; p < npulse; ++p) {
         const int xg = nxgrid == 1 ? 0 : p, yg = nygrid == 1 ? 0 : p;
-        pd[p] = Abr2PulseDev{roff[p], xoff[xg], yoff[yg], O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg]),
+        pd[p] = Abr2PulseDev{roff[p], xoff[xg], yoff[yg], A.O, int(roff[p + 1] - roff[p]), int(xoff[xg + 1] - xoff[xg]),
                              int(yoff[yg + 1] - yoff[yg]), 0};
-        nt[p] = pd[p].n;
-        npt[p] = (long)pd[p].nx * pd[p].ny;
-        O += nscale * npt[p];
+        A.ntime[p] = pd[p].n;
+        A.npoint[p] = (long)pd[p].nx * pd[p].ny;
+        A.O += nscale * A.npoint[p];
     }
     const long R = roff[npulse], X = xoff[nxgrid], Y = yoff[nygrid];
-    Staging S;
-    const size_t o_rf = S.add(R * 16), o_gx = S.add(R * 8), o_gy = S.add(R * 8), o_x = S.add(X * 8), o_y = S.add(Y * 8);
-    S.add_tables(npulse, pd.data(), sizeof(Abr2PulseDev), nt.data(), npt.data(), nscale, scales);
-    pack_cplx(R, rf_re, rf_im, S.at<double2>(o_rf));
-    double* gxw = S.at<double>(o_gx);
-    double* gyw = S.at<double>(o_gy);
+    Staging& S = A.S;
+    A.o_rf = S.add(R * 16); A.o_gx = S.add(R * 8); A.o_gy = S.add(R * 8); A.o_x = S.add(X * 8); A.o_y = S.add(Y * 8);
+    S.add_tables(npulse, pd.data(), sizeof(Abr2PulseDev), A.ntime.data(), A.npoint.data(), nscale, scales);
+    pack_cplx(R, rf_re, rf_im, S.at<double2>(A.o_rf));
+    double* gxw = S.at<double>(A.o_gx);
+    double* gyw = S.at<double>(A.o_gy);
     for (int p = 0; p < npulse; ++p)
         for (long t = roff[p]; t < roff[p + 1]; ++t) {
             gxw[t] = gx ? gx[t] : 2.0 * M_PI / pd[p].n;         // a null gx is 2 pi / n per sample, a null gy is 0
             gyw[t] = gy ? gy[t] : 0.0;
         }
-    std::copy(x, x + X, S.at<double>(o_x));
-    std::copy(y, y + Y, S.at<double>(o_y));
+    std::copy(x, x + X, S.at<double>(A.o_x));
+    std::copy(y, y + Y, S.at<double>(A.o_y));
+}
+
+void abr2_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                    const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
+                    int nscale, const double* scales, int mode, double* a_re, double* a_im, double* b_re, double* b_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Abr2Staged A;
+    abr2_stage(A, npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid, yoff, y, nscale, scales);
+    Staging& S = A.S;
+    const long O = A.O;                                         // output entries of a (and of b)
     S.upload(4 * (size_t)O * 8, st);
     double2* out = S.dev<double2>(S.o_out);                     // a: O entries, then b: O entries
-    hipLaunchKernelGGL(k_abr2_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_rf), S.dev<const double>(o_gx),
-                       S.dev<const double>(o_gy), S.dev<const double>(o_x), S.dev<const double>(o_y), S.dev<const double>(S.o_sc),
+    hipLaunchKernelGGL(k_abr2_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(A.o_rf), S.dev<const double>(A.o_gx),
+                       S.dev<const double>(A.o_gy), S.dev<const double>(A.o_x), S.dev<const double>(A.o_y), S.dev<const double>(S.o_sc),
                        S.dev<const Abr2PulseDev>(S.o_pd), S.dev<const SimBlock>(S.o_bk), mode, reinterpret_cast<double*>(out),
                        reinterpret_cast<double*>(out + O));
     std::vector<double2> h(2 * (size_t)O);

@@ -1,0 +1,92 @@
+"""torch.autograd wrappers of the device simulators: `abr` and `abr2` run mbfir.abr_batch / mbfir.abr2_batch on one pulse and are
+differentiable in rf, their backward being one mbfir.abr_vjp_batch / mbfir.abr2_vjp_batch call.  They work on
+complex128 tensors; the C ABI takes host pointers, so tensors go through host memory, and the results come back on rf's device.
+g, x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
+
+    rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
+    a, b = mbfir.torchsim.abr2(rf, g, x, y, scales=(0.9, 1.0, 1.1))        # (S, nx, ny) each, abr2_batch's bits
+    loss = ((2 * a.conj() * b - target).abs() ** 2).sum()
+    loss.backward()                                                       # rf.grad: abr2_vjp_batch's bits
+"""
+import functools
+
+import numpy as np
+
+
+def _host(v, dtype):
+    """A tensor, array or sequence as a host NumPy array (None stays None)."""
+    if v is None:
+        return None
+    if hasattr(v, "detach"):
+        v = v.detach().resolve_conj().resolve_neg().cpu().numpy()       # autograd hands lazily conjugated cotangents on
+    return np.asarray(v, dtype=dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _functions():
+    """The two autograd.Function classes, built when torch is first needed."""
+    import torch
+
+    import mbfir
+
+    def check(rf):
+        if not torch.is_tensor(rf) or rf.dtype != torch.complex128 or rf.dim() != 1:
+            raise ValueError("torchsim: rf must be a 1-D complex128 tensor")
+
+    def tensors(rf, arrays):
+        return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(rf.device) for v in arrays)
+
+    class Abr(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, rf, x, g, scales, hard_pulse):
+            check(rf)
+            ctx.args = (_host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse))
+            ctx.save_for_backward(rf)
+            x, g, scales, hard_pulse = ctx.args
+            rfh = _host(rf, np.complex128)
+            (a, b), = mbfir.abr_batch([rfh if g is None else (rfh, g)], x, scales=scales, hard_pulse=hard_pulse)
+            return tensors(rf, (a, b))
+
+        @staticmethod
+        def backward(ctx, ca, cb):
+            rf, = ctx.saved_tensors
+            x, g, scales, hard_pulse = ctx.args
+            rfh = _host(rf, np.complex128)
+            grad, = mbfir.abr_vjp_batch([rfh if g is None else (rfh, g)], x, [(_host(ca, np.complex128), _host(cb, np.complex128))],
+                                        scales=scales, hard_pulse=hard_pulse)
+            return tensors(rf, (grad,)) + (None, None, None, None)
+
+    class Abr2(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, rf, g, x, y, scales, hard_pulse):
+            check(rf)
+            ctx.args = (_host(g, np.complex128), _host(x, np.float64), _host(y, np.float64), tuple(scales), bool(hard_pulse))
+            ctx.save_for_backward(rf)
+            g, x, y, scales, hard_pulse = ctx.args
+            rfh = _host(rf, np.complex128)
+            (a, b), = mbfir.abr2_batch([rfh if g is None else (rfh, g)], x, y, scales=scales, hard_pulse=hard_pulse)
+            return tensors(rf, (a, b))
+
+        @staticmethod
+        def backward(ctx, ca, cb):
+            rf, = ctx.saved_tensors
+            g, x, y, scales, hard_pulse = ctx.args
+            rfh = _host(rf, np.complex128)
+            grad, = mbfir.abr2_vjp_batch([rfh if g is None else (rfh, g)], x, y,
+                                         [(_host(ca, np.complex128), _host(cb, np.complex128))], scales=scales, hard_pulse=hard_pulse)
+            return tensors(rf, (grad,)) + (None, None, None, None, None)
+
+    return Abr, Abr2
+
+
+def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
+    """(a, b) of mbfir.abr_batch([rf or (rf, g)], x, scales=scales, hard_pulse=hard_pulse), each of shape (S, nx), as tensors that
+    are differentiable in rf (a 1-D complex128 tensor).  x and g (real, one weight per sample; None: 2 pi / n) are constants."""
+    return _functions()[0].apply(rf, x, g, scales, hard_pulse)
+
+
+def abr2(rf, g, x, y, *, scales=(1.0,), hard_pulse=False):
+    """(a, b) of mbfir.abr2_batch([rf or (rf, g)], x, y, scales=scales, hard_pulse=hard_pulse), each of shape (S, nx, ny), as
+    tensors that are differentiable in rf (a 1-D complex128 tensor).  g (complex: Re the x gradient, Im the y one; None: 2 pi / n
+    along x), x and y are constants."""
+    return _functions()[1].apply(rf, g, x, y, scales, hard_pulse)
