@@ -336,6 +336,30 @@ int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                          const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
                          const double* y, int nscale, const double* scales, int mode, const double* ca_re, const double* ca_im,
                          const double* cb_re, const double* cb_im, double* g_re, double* g_im);
+/* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
+ * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
+ * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the
+ * forward call's four output planes and four more for the tangents.  (da, db) is the first-order change of (a, b) when rf moves
+ * along the direction: d/dt (a, b)(rf + t v) at t = 0, real-linear in v (scale s contributes the tangent along s v at s rf).  a /
+ * b: laid out as the forward call lays them out, with its bits; the four may be NULL together, and the primal is then not
+ * downloaded.  da / db (re, im planes): pulse p starts at ndir times its forward offset and is laid out (direction, scale, point)
+ * row-major, the point index as in the forward call.  g / gx / gy, the grids and the scales are not differentiated.  One upload,
+ * one launch (one workgroup per forward workgroup and group of mbfir_test_jvp_group() directions, which share each sample's
+ * trigonometry), one download; no atomics, and a tangent's bits depend only on its pulse, scale, point and direction: not on the
+ * batch, its order, ndir or the direction's place among the others.  The argument checks and their MBFIR_E_ARG messages are those of
+ * the forward calls (a v, da or db plane NULL, or some but not all of a / b NULL, is a required array NULL), then ndir < 1, then a
+ * direction array, tangent output or workgroup count that overflows; no device work is done before they pass. */
+int mbfir_abr_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int ndir,
+                        const double* v_re, const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im,
+                        double* da_re, double* da_im, double* db_re, double* db_im);
+int mbfir_abr2_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, int ndir, const double* v_re,
+                         const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im, double* da_re, double* da_im,
+                         double* db_re, double* db_im);
+/* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
+int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]
  *   points ((frequency, position) pairs, positions, or nx ny points) at nscale scales: 4 ints (pulse, scale, chunk, 0) per workgroup in launch
  *   order into out (may be NULL).  Returns the number of workgroups; -1 for npulse or nscale < 1, an ntime or npoint < 1, or a

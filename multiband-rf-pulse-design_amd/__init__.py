@@ -132,6 +132,11 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
                                        _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp,
+                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr2_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
+                                       _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_test_jvp_group": (C.c_int, []),
     "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
                                  C.POINTER(C.c_void_p), C.c_char_p, C.c_int]),
@@ -1081,11 +1086,12 @@ def _abr_args(who, pulses, x, scales, convention):
 
 
 def _abr_call(fn, ctx, sc, rfs, gs, xs, hard_pulse, planes):
-    """mbfir_abr_batch or mbfir_abr_vjp_batch on the checked arguments; planes: the arrays after `mode`."""
+    """mbfir_abr_batch, mbfir_abr_vjp_batch or mbfir_abr_jvp_batch on the checked arguments; planes: what follows `mode` (arrays,
+    and the tangent call's ndir)."""
     rf = np.concatenate(rfs)
     rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
             _ptr(_vec(np.concatenate(gs))), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(sc),
-            _ptr(sc), 1 if hard_pulse else 0, *[_ptr(o) for o in planes])
+            _ptr(sc), 1 if hard_pulse else 0, *[o if isinstance(o, int) else _ptr(o) for o in planes])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -1146,6 +1152,60 @@ def abr_vjp_batch(pulses, x, cot, *, scales=(1.0,), hard_pulse=False, convention
     return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
 
 
+def _tangents(who, tangents, rfs):
+    """tangents: per pulse a complex (n,) or (K, n) array, the same K for every pulse -> (K, whether the K axis is kept, the two
+    concatenated planes of the C call: direction-major within a pulse)."""
+    tangents = list(tangents)
+    if len(tangents) != len(rfs):
+        raise ValueError("%s: %d tangents for %d pulses" % (who, len(tangents), len(rfs)))
+    vs, lead = [], None
+    for q, (t, rf) in enumerate(zip(tangents, rfs)):
+        t = np.asarray(t, dtype=np.complex128)
+        if t.ndim not in (1, 2) or t.shape[-1] != len(rf) or t.shape[0] == 0:
+            raise ValueError("%s: the tangent of pulse %d has shape %s, not (%d,) or (K, %d)" % (who, q, t.shape, len(rf), len(rf)))
+        if lead is not None and t.shape[:-1] != lead:
+            raise ValueError("%s: the tangent of pulse %d has shape %s where pulse 0 has %s: every pulse takes the same K"
+                             % (who, q, t.shape, lead + (len(rfs[0]),)))
+        lead = t.shape[:-1]
+        vs.append(t.ravel())
+    K, keep = (lead[0], True) if lead else (1, False)
+    v = np.concatenate(vs)
+    return K, keep, [_vec(v.real), _vec(v.imag)]
+
+
+def _jvp_result(out, tan, ooff, K, keep, shapes, convention):
+    """The planes of a tangent call -> [((a, b), (da, db))] per pulse; shapes[q]: (S, nx[, ny])."""
+    a_all, b_all = out[0] + 1j * out[1], out[2] + 1j * out[3]
+    da_all, db_all = tan[0] + 1j * tan[1], tan[2] + 1j * tan[3]
+    if convention == "abr":
+        b_all, db_all = -np.conj(b_all), -np.conj(db_all)
+    res = []
+    for q, shape in enumerate(shapes):
+        lo, hi = int(ooff[q]), int(ooff[q + 1])
+        tshape = ((K,) if keep else ()) + shape
+        res.append(((a_all[lo:hi].reshape(shape), b_all[lo:hi].reshape(shape)),
+                    (da_all[K * lo:K * hi].reshape(tshape), db_all[K * lo:K * hi].reshape(tshape))))
+    return res
+
+
+def abr_jvp_batch(pulses, x, tangents, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The tangent of abr_batch with respect to rf (mbfir_abr_jvp_batch): pulses, x, scales, hard_pulse and convention as for
+    abr_batch; tangents: per pulse a complex direction of shape (n,), or K of them of shape (K, n), the same K for every pulse.
+    Returns a list of ((a, b), (da, db)) per pulse: (a, b) with abr_batch's bits, and (da, db) = d/dt (a, b)(rf + t v) at t = 0 for
+    each direction v, of shape (K, S, nx), without the K axis for a 1-D tangent.  Real-linear in v; under convention 'abr' the
+    tangent of the returned -conj(b) is -conj(db).  One launch, the directions sharing each sample's trigonometry; a tangent's bits
+    depend only on its pulse, scale, point and direction.  g and x are not differentiated."""
+    sc, rfs, gs, xs, nx = _abr_args("abr_jvp_batch", pulses, x, scales, convention)
+    K, keep, vplanes = _tangents("abr_jvp_batch", tangents, rfs)
+    S = len(sc)
+    ooff = _offsets([S * k for k in nx])
+    out = [np.zeros(int(ooff[-1])) for _ in range(4)]
+    tan = [np.zeros(K * int(ooff[-1])) for _ in range(4)]
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_jvp_batch, ctx, sc, rfs, gs, xs, hard_pulse, [K] + vplanes + out + tan)
+    return _jvp_result(out, tan, ooff, K, keep, [(S, k) for k in nx], convention)
+
+
 def _grids(v, npulse, who, name):
     """One array per pulse (a Python list of arrays, which must then have npulse entries) or one array shared by every pulse."""
     if isinstance(v, list) and len(v) > 0 and all(np.ndim(e) >= 1 for e in v):
@@ -1178,12 +1238,13 @@ def _abr2_args(who, pulses, x, y, scales, convention):
 
 
 def _abr2_call(fn, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes):
-    """mbfir_abr2_batch or mbfir_abr2_vjp_batch on the checked arguments; planes: the arrays after `mode`."""
+    """mbfir_abr2_batch, mbfir_abr2_vjp_batch or mbfir_abr2_jvp_batch on the checked arguments; planes: what follows `mode` (arrays,
+    and the tangent call's ndir)."""
     rf, g = np.concatenate(rfs), np.concatenate(gs)
     rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)), _ptr(_vec(g.real)),
             _ptr(_vec(g.imag)), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(ys),
             _lptr(_offsets([len(v) for v in ys])), _ptr(_vec(np.concatenate(ys))), len(sc), _ptr(sc), 1 if hard_pulse else 0,
-            *[_ptr(o) for o in planes])
+            *[o if isinstance(o, int) else _ptr(o) for o in planes])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -1221,6 +1282,25 @@ def abr2_vjp_batch(pulses, x, y, cot, *, scales=(1.0,), hard_pulse=False, conven
     _abr2_call(load_library().mbfir_abr2_vjp_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes + grad)
     g_all = grad[0] + 1j * grad[1]
     return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
+
+
+def abr2_jvp_batch(pulses, x, y, tangents, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The tangent of abr2_batch with respect to rf (mbfir_abr2_jvp_batch): as abr_jvp_batch, with abr2_batch's arguments; (da, db)
+    of each pulse have the shape (K, S, nx, ny), without the K axis for a 1-D tangent.  g, x and y are not differentiated."""
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args("abr2_jvp_batch", pulses, x, y, scales, convention)
+    K, keep, vplanes = _tangents("abr2_jvp_batch", tangents, rfs)
+    S = len(sc)
+    ooff = _offsets([S * k * j for k, j in zip(nx, ny)])
+    out = [np.zeros(int(ooff[-1])) for _ in range(4)]
+    tan = [np.zeros(K * int(ooff[-1])) for _ in range(4)]
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_jvp_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, [K] + vplanes + out + tan)
+    return _jvp_result(out, tan, ooff, K, keep, [(S, k, j) for k, j in zip(nx, ny)], convention)
+
+
+def jvp_group():
+    """The directions one workgroup of abr_jvp_batch / abr2_jvp_batch carries (mbfir_test_jvp_group)."""
+    return int(load_library().mbfir_test_jvp_group())
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

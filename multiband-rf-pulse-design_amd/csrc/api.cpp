@@ -964,6 +964,57 @@ int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                                       yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im));
 }
 
+// What the tangent calls check after abr_batch_check: ndir, and that ndir times the R rf samples, ndir times the forward output (at
+// most 2^56 entries each) and the forward workgroups times the direction groups (at most 2^31 - 1) fit.  0, or MBFIR_E_ARG with ctx->err set.
+static int jvp_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, long R, const long* npoint) {
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (ndir < 1) return bad("ndir must be at least 1");
+    long total = 0, nblk = 0;                                  // abr_batch_check has bounded both for one direction
+    for (int p = 0; p < npulse; ++p) {
+        total += npoint[p] * nscale;
+        nblk += (npoint[p] + 255) / 256 * nscale;
+    }
+    const long ngrp = (ndir + (long)jvp_group() - 1) / jvp_group();
+    if (R > (1L << 56) / ndir || total > (1L << 56) / ndir || nblk > 2147483647L / ngrp) return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_abr_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int ndir,
+                        const double* v_re, const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im,
+                        double* da_re, double* da_im, double* db_re, double* db_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool primal = (a_re && a_im && b_re && b_im) || (!a_re && !a_im && !b_re && !b_im);      // all four or none
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales && v_re && v_im && primal && da_re && da_im && db_re && db_im;
+    if (const int e = abr_batch_check(ctx, "abr_jvp_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays, npoint))
+        return e;
+    if (const int e = jvp_check(ctx, "abr_jvp_batch", npulse, nscale, ndir, roff[npulse], npoint.data())) return e;
+    MBFIR_TRY(ctx, abr_jvp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
+                                     mode, ndir, v_re, v_im, a_re, a_im, b_re, b_im, da_re, da_im, db_re, db_im));
+}
+
+int mbfir_abr2_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, int ndir, const double* v_re,
+                         const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im, double* da_re, double* da_im,
+                         double* db_re, double* db_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool primal = (a_re && a_im && b_re && b_im) || (!a_re && !a_im && !b_re && !b_im);
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales && v_re && v_im && primal && da_re && da_im &&
+                        db_re && db_im;
+    if (const int e = abr_batch_check(ctx, "abr2_jvp_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (const int e = jvp_check(ctx, "abr2_jvp_batch", npulse, nscale, ndir, roff[npulse], npoint.data())) return e;
+    MBFIR_TRY(ctx, abr2_jvp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
+                                      yoff, y, nscale, scales, mode, ndir, v_re, v_im, a_re, a_im, b_re, b_im, da_re, da_im, db_re,
+                                      db_im));
+}
+
+int mbfir_test_jvp_group(void) { return jvp_group(); }
+
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {
     if (npulse < 1 || nscale < 1 || !ntime || !npoint) return -1;
     std::vector<long> ntout(npulse, 1);

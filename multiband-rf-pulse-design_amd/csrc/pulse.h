@@ -1,4 +1,4 @@
-// Host side of the pulse tools (slr.hip, simgrad.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// Host side of the pulse tools (slr.hip, simgrad.hip, simjvp.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
 // api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
 // (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
 // compiler.
@@ -54,6 +54,20 @@ void abr2_vjp_batch_run(int device, void* stream, int npulse, const long* roff, 
                         const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
                         const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
                         const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im);
+// Tangents of abr_batch_run / abr2_batch_run with respect to rf (simjvp.hip k_abr_jvp_batch, k_abr2_jvp_batch): the forward call's
+// inputs and ndir >= 1 directions per pulse, direction k of pulse p at ndir roff[p] + k n_p of v_re / v_im.  a / b: the forward
+// call's outputs with its bits (all four null: not downloaded); da / db: pulse p from ndir times its forward offset, (direction,
+// scale, point) row-major.  One upload, one launch of jvp_group() directions per workgroup, one download.
+int jvp_group();
+void abr_jvp_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                       const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                       int ndir, const double* v_re, const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im,
+                       double* da_re, double* da_im, double* db_re, double* db_im);
+void abr2_jvp_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                        const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                        const long* yoff, const double* y, int nscale, const double* scales, int mode, int ndir, const double* v_re,
+                        const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im, double* da_re, double* da_im,
+                        double* db_re, double* db_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

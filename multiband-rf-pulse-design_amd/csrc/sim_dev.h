@@ -1,5 +1,6 @@
-// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch) and their adjoints (simgrad.hip) share: the step of
-// the forward model, the per-pulse descriptors, and the host staging of one call.  Moved here from slr.hip token for token.
+// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip) and their tangents
+// (simjvp.hip) share: the step of the forward model, the helpers of its derivative, the per-pulse descriptors, and the host staging
+// of one call.  Moved here from slr.hip and simgrad.hip token for token.
 #pragma once
 #include "dev_common.h"
 #include "pulse.h"
@@ -20,7 +21,14 @@ namespace mbfir {
 struct CayleyKlein {
     double2 a, b;
 };
-__device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, double2 a, double2 b) {
+// What a step computes from r and om alone: cs = cos(ph / 2) with ph = phi (mode 0) or |r| (mode 1), inv = sin(ph / 2) / ph (0 at
+// ph = 0), and sz, cz = sincos(-om) in mode 1.  The tangent kernels (simjvp.hip) take it from the step (KEEP) so that a sample's
+// trigonometry is computed once; abr_step drops it, and compiles to what it compiled to before the body moved here.
+struct AbrTrig {
+    double cs, ph, inv, sz, cz;
+};
+template <bool KEEP>
+__device__ __forceinline__ CayleyKlein abr_step_trig(int mode, double2 r, double om, double2 a, double2 b, AbrTrig& t) {
     double2 av, bv;                              // step: a' = av a - conj(bv) b ; b' = bv a + conj(av) b
     if (mode == 0) {
         const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
@@ -34,6 +42,7 @@ __device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, 
         const double2 bn = make_double2(bv.x * a.x - bv.y * a.y + (av.x * b.x + av.y * b.y),
                                         bv.x * a.y + bv.y * a.x + (av.x * b.y - av.y * b.x));
         a = an; b = bn;
+        if (KEEP) t = AbrTrig{cs, phi, inv, 0.0, 1.0};
     } else {
         const double th = hypot(r.x, r.y);
         double sn, cs, sz, cz;
@@ -45,8 +54,35 @@ __device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, 
         const double2 an = make_double2(cs * a.x - (S.x * zb.x + S.y * zb.y), cs * a.y - (S.x * zb.y - S.y * zb.x));
         const double2 bn = make_double2(S.x * a.x - S.y * a.y + cs * zb.x, S.x * a.y + S.y * a.x + cs * zb.y);
         a = an; b = bn;
+        if (KEEP) t = AbrTrig{cs, th, inv, sz, cz};
     }
     return CayleyKlein{a, b};
+}
+__device__ __forceinline__ CayleyKlein abr_step(int mode, double2 r, double om, double2 a, double2 b) {
+    AbrTrig t;
+    return abr_step_trig<false>(mode, r, om, a, b, t);
+}
+
+// Complex helpers of the derivative kernels (simgrad.hip, simjvp.hip).
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) {        // a b
+    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
+}
+__device__ __forceinline__ double2 cjmul(double2 a, double2 b) {       // conj(a) b
+    return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
+}
+__device__ __forceinline__ double redot(double2 a, double2 b) {        // Re(conj(a) b)
+    return a.x * b.x + a.y * b.y;
+}
+
+// inv = sin(phi / 2) / phi and D = (d inv / d phi) / phi = (cos(phi / 2) / 2 - inv) / phi^2 from sn, cs = sincos(phi / 2).  Below
+// 1e-4 the difference cancels and D is its series -1/24 + phi^2 / 960; phi = 0 (a zero rf sample at om = 0) gives the limits 1/2
+// and -1/24.  d inv / dp = D p for p = Re r, Im r.  half_sinc_d: D from an inv that is already there.
+__device__ __forceinline__ double half_sinc_d(double phi, double cs, double inv) {
+    return phi < 1e-4 ? -1.0 / 24.0 + phi * phi * (1.0 / 960.0) : (0.5 * cs - inv) / (phi * phi);
+}
+__device__ __forceinline__ void half_sinc(double phi, double sn, double cs, double& inv, double& D) {
+    inv = phi > 0 ? sn / phi : 0.5;
+    D = half_sinc_d(phi, cs, inv);
 }
 
 // Per-pulse descriptors of the 1D and the 2D simulators (and of their adjoints, whose cotangents lie where the outputs do).

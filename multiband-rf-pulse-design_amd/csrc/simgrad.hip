@@ -18,25 +18,7 @@
 
 namespace mbfir {
 
-__device__ __forceinline__ double2 cmul(double2 a, double2 b) {        // a b
-    return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
-}
-__device__ __forceinline__ double2 cjmul(double2 a, double2 b) {       // conj(a) b
-    return make_double2(a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x);
-}
-__device__ __forceinline__ double redot(double2 a, double2 b) {        // Re(conj(a) b)
-    return a.x * b.x + a.y * b.y;
-}
-
-// inv = sin(phi / 2) / phi and D = (d inv / d phi) / phi = (cos(phi / 2) / 2 - inv) / phi^2 from sn, cs = sincos(phi / 2).  Below
-// 1e-4 the difference cancels and D is its series -1/24 + phi^2 / 960; phi = 0 (a zero rf sample at om = 0) gives the limits 1/2
-// and -1/24.  d inv / dp = D p for p = Re r, Im r.
-__device__ __forceinline__ void half_sinc(double phi, double sn, double cs, double& inv, double& D) {
-    inv = phi > 0 ? sn / phi : 0.5;
-    D = phi < 1e-4 ? -1.0 / 24.0 + phi * phi * (1.0 / 960.0) : (0.5 * cs - inv) / (phi * phi);
-}
-
-// One sample backwards for one point: (a, b) = psi_m -> psi_{m-1}, (la, lb) = lambda_m -> lambda_{m-1}; returns the sample's
+// One sample backwards (cmul, cjmul, redot and half_sinc: sim_dev.h) for one point: (a, b) = psi_m -> psi_{m-1}, (la, lb) = lambda_m -> lambda_{m-1}; returns the sample's
 // contribution (dL / d Re r, dL / d Im r).  With u, v the state before the sample and X = conj(la) v, Y = conj(lb) u:
 //   mode 0: alpha = cs - i om inv, beta = -i r inv;  d alpha / dp = p kappa, kappa = -inv / 2 - i om D;
 //           d beta / dp = D p (-i r) + inv e_p, e = (-i, 1)   ->   g = r C + inv (Im(X + Y), Re(Y - X))

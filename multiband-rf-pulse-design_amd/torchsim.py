@@ -1,6 +1,7 @@
 """torch.autograd wrappers of the device simulators: `abr` and `abr2` run mbfir.abr_batch / mbfir.abr2_batch on one pulse and are
-differentiable in rf, their backward being one mbfir.abr_vjp_batch / mbfir.abr2_vjp_batch call.  They work on
-complex128 tensors; the C ABI takes host pointers, so tensors go through host memory, and the results come back on rf's device.
+differentiable in rf, their backward being one mbfir.abr_vjp_batch / mbfir.abr2_vjp_batch call and their
+forward-mode tangent one mbfir.abr_jvp_batch / mbfir.abr2_jvp_batch call with one direction (section 8l), so that
+torch.autograd.forward_ad dual tensors and torch.func.jvp pass through them.  They work on complex128 tensors; the C ABI takes host pointers, so tensors go through host memory, and the results come back on rf's device.
 g, x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
@@ -18,13 +19,19 @@ def _host(v, dtype):
     if v is None:
         return None
     if hasattr(v, "detach"):
+        import torch
+        if torch._C._functorch.is_functorch_wrapped_tensor(v):           # torch.func's transforms wrap what jvp receives: the
+            from torch._functorch.pyfunctorch import retrieve_current_functorch_interpreter          # values lie one level down
+            with retrieve_current_functorch_interpreter().lower():
+                return _host(torch._C._functorch.get_unwrapped(v), dtype)
         v = v.detach().resolve_conj().resolve_neg().cpu().numpy()       # autograd hands lazily conjugated cotangents on
     return np.asarray(v, dtype=dtype)
 
 
 @functools.lru_cache(maxsize=None)
 def _functions():
-    """The two autograd.Function classes, built when torch is first needed."""
+    """The two autograd.Function classes, built when torch is first needed.  forward and setup_context are separate, which
+    torch.func's transforms require; backward and jvp read what setup_context kept."""
     import torch
 
     import mbfir
@@ -38,14 +45,28 @@ def _functions():
 
     class Abr(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, rf, x, g, scales, hard_pulse):
+        def forward(rf, x, g, scales, hard_pulse):
             check(rf)
-            ctx.args = (_host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse))
-            ctx.save_for_backward(rf)
-            x, g, scales, hard_pulse = ctx.args
+            x, g, scales, hard_pulse = _host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse)
             rfh = _host(rf, np.complex128)
             (a, b), = mbfir.abr_batch([rfh if g is None else (rfh, g)], x, scales=scales, hard_pulse=hard_pulse)
             return tensors(rf, (a, b))
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            rf, x, g, scales, hard_pulse = inputs
+            ctx.args = (_host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse))
+            ctx.save_for_backward(rf)
+            ctx.save_for_forward(rf)
+
+        @staticmethod
+        def jvp(ctx, v, *_):
+            rf, = ctx.saved_tensors
+            x, g, scales, hard_pulse = ctx.args
+            rfh = _host(rf, np.complex128)
+            (_, tan), = mbfir.abr_jvp_batch([rfh if g is None else (rfh, g)], x, [_host(v, np.complex128)], scales=scales,
+                                            hard_pulse=hard_pulse)
+            return tensors(rf, tan)
 
         @staticmethod
         def backward(ctx, ca, cb):
@@ -58,14 +79,28 @@ def _functions():
 
     class Abr2(torch.autograd.Function):
         @staticmethod
-        def forward(ctx, rf, g, x, y, scales, hard_pulse):
+        def forward(rf, g, x, y, scales, hard_pulse):
             check(rf)
+            g, x, y = _host(g, np.complex128), _host(x, np.float64), _host(y, np.float64)
+            rfh = _host(rf, np.complex128)
+            (a, b), = mbfir.abr2_batch([rfh if g is None else (rfh, g)], x, y, scales=tuple(scales), hard_pulse=bool(hard_pulse))
+            return tensors(rf, (a, b))
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            rf, g, x, y, scales, hard_pulse = inputs
             ctx.args = (_host(g, np.complex128), _host(x, np.float64), _host(y, np.float64), tuple(scales), bool(hard_pulse))
             ctx.save_for_backward(rf)
+            ctx.save_for_forward(rf)
+
+        @staticmethod
+        def jvp(ctx, v, *_):
+            rf, = ctx.saved_tensors
             g, x, y, scales, hard_pulse = ctx.args
             rfh = _host(rf, np.complex128)
-            (a, b), = mbfir.abr2_batch([rfh if g is None else (rfh, g)], x, y, scales=scales, hard_pulse=hard_pulse)
-            return tensors(rf, (a, b))
+            (_, tan), = mbfir.abr2_jvp_batch([rfh if g is None else (rfh, g)], x, y, [_host(v, np.complex128)], scales=scales,
+                                             hard_pulse=hard_pulse)
+            return tensors(rf, tan)
 
         @staticmethod
         def backward(ctx, ca, cb):
