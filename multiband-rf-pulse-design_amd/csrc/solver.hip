@@ -649,6 +649,116 @@ __global__ __launch_bounds__(256) void k_trig_eval(DProg P, const double* __rest
         }
 }
 
+// One step of the rotation recurrence (c, s) <- (c cd - s sd, s cd + c sd) for the PAIRED kernels, with the fused products spelt out.
+// k_trig_eval and k_trig_moments leave the fusing to the compiler's contraction, which rounds one product of each sum on its own and
+// lets the other ride in the FMA -- and picked differently in the two: s cd fused in k_trig_eval (SFUSE = 0), c sd in k_trig_moments
+// (SFUSE = 1).  Which product is fused decides the last bit, and a single solve always runs the unpaired kernels, so each paired kernel
+// copies its twin's form here.  This is a copy, not a shared definition: if a compiler contracts the unpaired kernels otherwise,
+// tests/test_lanepair_gpu.py (unit against single solves, bitwise) fails and SFUSE has to follow.
+template <int SFUSE>
+__device__ __forceinline__ void rotate(double& c, double& s, double cd, double sd) {
+    const double cn = fma(c, cd, -(s * sd));
+    s = SFUSE ? fma(c, sd, s * cd) : fma(s, cd, c * sd);
+    c = cn;
+}
+// Lane pairs (k_trig_eval_pair, k_trig_moments_pair): the lanes of a lock-step unit that share grid and lattice (DProg::seeds_shared, no dims)
+// run the SAME (c, s) chains, so one block serves lanes 2z and 2z + 1 and every thread runs its chain once for both: operands,
+// LDS staging, accumulators and the order of each lane's accumulating FMAs stay the lane's own (results bit-identical to the unpaired kernels'),
+// the program tables that are equal across the pair (ch_*, fold_*, lat_*, seeds) are read from the pair's first lane.  A pair with
+// one lane masked off (or absent: odd lane count) runs the live lane alone (NL = 1) and touches nothing of the other.
+// Prologue: live[] per lane of the pair, P moved to the pair's first lane; returns false when both lanes are off.
+__device__ __forceinline__ bool pair_prologue(DProg& P, int nlanes, bool (&live)[2], size_t& off0) {
+    const int l0 = 2 * blockIdx.z;
+    live[0] = !P.mask || P.mask[l0];
+    live[1] = l0 + 1 < nlanes && (!P.mask || P.mask[l0 + 1]);
+    off0 = (size_t)l0 * P.lane_bytes;
+    if (!live[0] && !live[1]) return false;
+    if (l0) P.shift(off0);
+    return true;
+}
+template <class T>
+__device__ __forceinline__ T* byte_shift(T* p, size_t off) { return (T*)((const char*)p + off); }
+// the sums of trig_eval_lanes over the segment's n lattice points: NVC vectors (0: the run-time count NVV), one (c, s) chain for all NL lanes
+template <int NVVMAX, int NL, int NVC>
+__device__ __forceinline__ void trig_eval_sum(const double2 (*cf)[NVVMAX][SEGMAX], int n, int NVV, const double4 sd4, double (&ac)[NL][NVVMAX], double (&as)[NL][NVVMAX]) {
+    double c = sd4.x, s = sd4.y;
+    const double cw = sd4.z, sw = sd4.w;
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+    for (int v = 0; v < NVVMAX; ++v) ac[L][v] = as[L][v] = 0;
+#pragma unroll (8 / NL)
+    for (int m = 0; m < n; ++m) {
+#pragma unroll
+        for (int L = 0; L < NL; ++L)
+#pragma unroll
+        for (int v = 0; v < NVVMAX; ++v)
+            if (NVC ? v < NVC : v < NVV) { const double2 x = cf[L][v][m]; ac[L][v] += x.x * c; as[L][v] += x.y * s; }
+        rotate<0>(c, s, cw, sw);
+    }
+}
+// k_trig_eval's work for NL lanes in one block (vin[L], UU[L]: the lanes' own vectors; cf[L]: the lanes' own LDS images)
+template <int NV, int NL>
+__device__ __forceinline__ void trig_eval_lanes(const DProg& P, const double* const (&vin)[NL], double* const (&UU)[NL], double2 (*cf)[2 * NV][SEGMAX]) {
+    constexpr int NVVMAX = 2 * NV;
+    const int k = blockIdx.x * 256 + threadIdx.x, sg = blockIdx.y;
+    const int m0 = sg * P.seg, m1 = min(m0 + P.seg, P.D1);
+    const int NVV = P.quad ? 2 * NV : NV;
+    for (int e = threadIdx.x; e < 2 * (m1 - m0); e += 256) {
+        const int kind = e & 1, m = m0 + (e >> 1), le = kind * P.D1 + m;
+        const int j = P.lat_col[le], qj = P.quad ? P.lat_qcol[le] : -1;
+        const double sc = P.lat_scale[le], qs = P.quad ? P.lat_qscale[le] : 0.0;
+#pragma unroll
+        for (int L = 0; L < NL; ++L)
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            const double c1 = j >= 0 ? sc * vin[L][(long)q * P.LDV + j] : 0.0;
+            if (kind) cf[L][q][e >> 1].y = c1; else cf[L][q][e >> 1].x = c1;
+            if (P.quad) {
+                const double c2 = qj >= 0 ? qs * vin[L][(long)q * P.LDV + qj] : 0.0;
+                if (kind) cf[L][NV + q][e >> 1].y = c2; else cf[L][NV + q][e >> 1].x = c2;
+            }
+        }
+    }
+    __syncthreads();
+    if (k >= P.nfold) return;
+    const double4 sd4 = P.seed_eval[(long)sg * P.Mpad + k];
+    double ac[NL][NVVMAX], as[NL][NVVMAX];
+    // (a pair takes the vector count out of the loop: with two lanes' reads in flight the per-vector branches cost registers)
+    if (NL == 1) trig_eval_sum<NVVMAX, NL, 0>(cf, m1 - m0, NVV, sd4, ac, as);
+    else if (P.quad) trig_eval_sum<NVVMAX, NL, NVVMAX>(cf, m1 - m0, NVV, sd4, ac, as);
+    else trig_eval_sum<NVVMAX, NL, NV>(cf, m1 - m0, NVV, sd4, ac, as);
+    const int ip = P.fold_pos[k], in = P.fold_neg[k];
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+    for (int v = 0; v < NVVMAX; ++v)
+        if (v < NVV) {
+            double* u = UU[L] + ((long)sg * NVV + v) * P.Mpad;
+            if (ip >= 0) u[ip] = ac[L][v] + as[L][v];
+            if (in >= 0) u[in] = ac[L][v] - as[L][v];
+        }
+}
+// ... for the lanes 2z and 2z + 1 of a unit of nlanes (launch bounds: the waves per SIMD k_trig_eval gets; no spills -- DESIGN.md section 4)
+template <int NV>
+__global__ __launch_bounds__(256, 8) void k_trig_eval_pair(DProg P, const double* __restrict__ vin, double* __restrict__ UU, int nlanes) {
+    __shared__ double2 cf[2][2 * NV][SEGMAX];
+    bool live[2];
+    size_t off0;
+    if (!pair_prologue(P, nlanes, live, off0)) return;
+    const bool both = live[0] && live[1];
+    const size_t off1 = (both || !live[0]) ? P.lane_bytes : 0;                 // both: the pair's second lane; else: the live one
+    if (both) {
+        const double* const v2[2] = {byte_shift(vin, off0), byte_shift(vin, off0 + off1)};
+        double* const u2[2] = {byte_shift(UU, off0), byte_shift(UU, off0 + off1)};
+        trig_eval_lanes<NV, 2>(P, v2, u2, cf);
+    } else {
+        const double* const v1[1] = {byte_shift(vin, off0 + off1)};
+        double* const u1[1] = {byte_shift(UU, off0 + off1)};
+        trig_eval_lanes<NV, 1>(P, v1, u1, cf);
+    }
+}
+
 // seed tables for the recurrences below (once per design)
 // (the progressions start at ka * tmin and kb * tmin: the LANE's origin)
 __global__ void k_build_seeds_m(DProg P, double ka, int na, double kb, int nb, double4* __restrict__ seeds) {
@@ -780,6 +890,96 @@ __global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __
     for (int v = 0; v < NV; ++v) {
         partial[(((long)blockIdx.y * NV + v) * 2) * P.LDM + m] = ag[v];
         partial[(((long)blockIdx.y * NV + v) * 2 + 1) * P.LDM + m] = as[v];
+    }
+}
+
+// k_trig_moments<NV, true>'s work for NL lanes in one block (lane pairs, see k_trig_eval_pair): P holds the tables the lanes share, PL[L] the lane's own program (alpha, beta,
+// f_ptr, f_rows), rows[L] / partial[L] its vectors, pp[L] its LDS image; one (c, s) chain per chunk serves all NL lanes.
+template <int NV, int NL>
+__device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* const (&PL)[NL], const double4* __restrict__ seeds, int na,
+                                                   double* const (&partial)[NL], const double* const (&rows)[NL], double2 (*pp)[NV][CGRP][CHK]) {
+    constexpr int nb = 0;                                 // (G'v: one progression)
+    const int tid = threadIdx.x;
+    const int ch0 = blockIdx.y * P.cgrp;
+    for (int e = tid; e < P.cgrp * CHK; e += 256) {       // stage the operands of the group's chunks
+        const int cc = e / CHK, q = e - cc * CHK, ch = ch0 + cc;
+        const bool live = ch < P.nchunk && q < P.ch_count[ch < P.nchunk ? ch : 0];
+        const int k = live ? P.ch_start[ch] + q : 0;
+        const int kp = live ? P.fold_pos[k] : -1, kn = live ? P.fold_neg[k] : -1;
+#pragma unroll
+        for (int L = 0; L < NL; ++L) {
+            double a[NV], b[NV];
+            freq_operands<NV, true>(*PL[L], rows[L], kp, a);
+            freq_operands<NV, true>(*PL[L], rows[L], kn, b);
+#pragma unroll
+            for (int v = 0; v < NV; ++v) pp[L][v][cc][q] = make_double2(a[v] + b[v], a[v] - b[v]);
+        }
+    }
+    __syncthreads();
+    const int m = blockIdx.x * MPTS + tid;
+    if (m >= na + nb) return;
+    double ag[NL][NV], as[NL][NV];
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) ag[L][v] = as[L][v] = 0;
+    // two chunks at a time: their recurrences are independent chains, which is what keeps the fp64 pipe busy with the
+    // two or three waves per SIMD this grid has (operands past a chunk's end are staged as zeros)
+    for (int cl = 0; cl < P.cgrp; cl += 2) {
+        const int cha = ch0 + cl, chb = cha + 1;
+        if (cha >= P.nchunk) break;
+        const bool two = cl + 1 < P.cgrp && chb < P.nchunk;
+        const double4 sa = seeds[(long)cha * (na + nb) + m];
+        const double4 sb = two ? seeds[(long)chb * (na + nb) + m] : make_double4(0.0, 0.0, 0.0, 0.0);
+        double c0 = sa.x, s0 = sa.y, c1 = sb.x, s1 = sb.y;
+        const int cnt = max(P.ch_count[cha], two ? P.ch_count[chb] : 0);
+        const int clb = two ? cl + 1 : cl;                  // (a lone last chunk pairs with itself at zero weight: sb = 0)
+#pragma unroll (4 / NL)
+        for (int q = 0; q < cnt; ++q) {
+#pragma unroll
+            for (int L = 0; L < NL; ++L)
+#pragma unroll
+            for (int v = 0; v < NV; ++v) {
+                const double2 pa = pp[L][v][cl][q], pb = pp[L][v][clb][q];
+                ag[L][v] += pa.x * c0; as[L][v] += pa.y * s0;
+                ag[L][v] += pb.x * c1; as[L][v] += pb.y * s1;
+            }
+            rotate<1>(c0, s0, sa.z, sa.w);
+            rotate<1>(c1, s1, sb.z, sb.w);
+        }
+    }
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+        partial[L][(((long)blockIdx.y * NV + v) * 2) * P.LDM + m] = ag[L][v];
+        partial[L][(((long)blockIdx.y * NV + v) * 2 + 1) * P.LDM + m] = as[L][v];
+    }
+}
+// ... the FOLD form for the lanes 2z and 2z + 1 of a unit of nlanes with seeds_shared and without dims (seeds: the unit's one table; na: every
+// lane's), one or two operands (with four the registers allow fewer waves per SIMD than k_trig_moments<4, true> gets -- DESIGN.md section 4)
+template <int NV>
+__global__ __launch_bounds__(256, 8) void k_trig_moments_pair(DProg P, const double4* __restrict__ seeds, int na, double* __restrict__ partial,
+                                                              const double* __restrict__ rows, int nlanes) {
+    static_assert(NV <= 2, "k_trig_moments_pair: one or two operands");
+    __shared__ double2 pp[2][NV][CGRP][CHK];
+    bool live[2];
+    size_t off0;
+    if (!pair_prologue(P, nlanes, live, off0)) return;
+    const bool both = live[0] && live[1];
+    const size_t off1 = (both || !live[0]) ? P.lane_bytes : 0;                 // both: the pair's second lane; else: the live one
+    DProg Q = P;
+    Q.shift(off1);
+    if (both) {
+        const DProg* const p2[2] = {&P, &Q};
+        double* const o2[2] = {byte_shift(partial, off0), byte_shift(partial, off0 + off1)};
+        const double* const r2[2] = {byte_shift(rows, off0), byte_shift(rows, off0 + off1)};
+        trig_moments_lanes<NV, 2>(P, p2, seeds, na, o2, r2, pp);
+    } else {
+        const DProg* const p1[1] = {&Q};
+        double* const o1[1] = {byte_shift(partial, off0 + off1)};
+        const double* const r1[1] = {byte_shift(rows, off0 + off1)};
+        trig_moments_lanes<NV, 1>(P, p1, seeds, na, o1, r1, pp);
     }
 }
 
@@ -2091,6 +2291,7 @@ struct SolveSwitches {
     int chol_split = -1;         // CHOL_SPLIT: the factorisation's form (chol_inv_launch); -1 unset: its own choice per call
     bool poison = false;         // POISON=1 (test switch): NaN in the factorisation's diagonal-block images before every build
     int test_lose_flag = -1;     // TEST_LOSE_FLAG=k (test hook of chol.hip): the diagonal block of panel step k does not raise its flag; -1 none
+    bool lanepair = true;        // LANEPAIR=0: every lane of a unit runs the lattice recurrences of G'v and G v itself instead of one thread per pair of lanes
 };
 static SolveSwitches read_switches() {
     SolveSwitches w;
@@ -2098,6 +2299,7 @@ static SolveSwitches read_switches() {
     auto number = [](const char* name, int& v) { if (const char* ev = std::getenv(name)) v = std::atoi(ev); };
     flag("MBFIR_CORRECTOR", w.corrector); flag("MBFIR_CORR_BIG", w.corr_big); flag("MBFIR_DD_BLOCKINV", w.dd_blockinv);
     flag("MBFIR_HSOLVE", w.hsolve); flag("MBFIR_FUSE", w.fuse); flag("MBFIR_SPECULATE", w.speculate); flag("MBFIR_POISON", w.poison);
+    flag("MBFIR_LANEPAIR", w.lanepair);
     number("MBFIR_TEST_CAP_KP", w.test_cap_kp); number("MBFIR_AR_OVERLAP", w.ar_overlap);
     number("MBFIR_CHOL_SPLIT", w.chol_split); number("MBFIR_TEST_LOSE_FLAG", w.test_lose_flag);
     if (const char* ev = std::getenv("MBFIR_CGRP")) w.cgrp = std::max(1, std::min(CGRP, std::atoi(ev)));
@@ -2389,6 +2591,7 @@ struct Solver::Impl {
     int comm_size = 0, comm_rank = 0;
     long n_collectives = 0;      // issued by the current solve
     double collective_bytes = 0; // ... and the bytes they carried
+    long n_pair = 0;             // ... and how many of their lattice launches ran the paired kernels (k_trig_eval_pair, k_trig_moments_pair)
     long n_gv = 0, n_gtv = 0;    // passes over the frequency rows of the current solve: G v (apply_G / apply_G_winv2, the residual's row response), G'v (apply_GT)
     void allreduce(double* buf, long count, int op, hipStream_t on = nullptr) {
         if (shard_size <= 1) return;
@@ -2568,12 +2771,23 @@ struct Solver::Impl {
     }
 
     // ---- operators ----
+    // one thread runs the lattice recurrences of two lanes (k_trig_eval_pair, k_trig_moments_pair): the lanes of the unit share
+    // grid and lattice, have the same extents, and the solve is neither sharded nor on the extended-precision path
+    bool lane_pairs() const { return sw.lanepair && nlanes >= 2 && P.seeds_shared && !P.dims && shard_size == 1 && !dd_unit; }
+    template <int NV>
+    void trig_eval(const double* v) {
+        const dim3 g(cdiv(P.nfold, 256), P.useg);
+        if (lane_pairs()) {
+            ++n_pair;
+            hipLaunchKernelGGL(k_trig_eval_pair<NV>, lane_grid(g, cdiv(nlanes, 2)), dim3(256), 0, st, P, v, UU, nlanes);
+        } else hipLaunchKernelGGL(k_trig_eval<NV>, lane_grid(g, nlanes), dim3(256), 0, st, P, v, UU);
+    }
     template <int NV>
     void apply_G(const double* v, double* out) {
         const int NVV = P.quad ? 2 * NV : NV;
         ++n_gv;
         if (P.trig) {
-            hipLaunchKernelGGL(k_trig_eval<NV>, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), nlanes), dim3(256), 0, st, P, v, UU);
+            trig_eval<NV>(v);
             hipLaunchKernelGGL(k_rows_G<NV>, lane_grid(dim3(cdiv(P.R, 256)), nlanes), dim3(256), 0, st, P, UU, v, out);
             return;
         }
@@ -2594,7 +2808,7 @@ struct Solver::Impl {
     void apply_G_winv2(const double* v, double* gout, const double* sub, double* wout) {
         if (P.trig && !P.big) {
             ++n_gv;
-            hipLaunchKernelGGL(k_trig_eval<NV>, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), nlanes), dim3(256), 0, st, P, v, UU);
+            trig_eval<NV>(v);
             hipLaunchKernelGGL(k_rows_winv2<NV>, lane_grid(dim3(cdiv(P.l + P.nq3, 256)), nlanes), dim3(256), 0, st, P, UU, v, dl, w3, sub, gout, wout);
             return;
         }
@@ -2638,7 +2852,14 @@ struct Solver::Impl {
         if (P.trig) {
             dim3 g(cdiv(P.D1, MPTS), cdiv(P.nchunk, P.cgrp)), b(256);
             const dim3 gf(cdiv(P.nfold, 256));
-            if (sw.fuse) {
+            // (pairs up to two operands: with four, the paired kernel's registers allow fewer waves than the unpaired one's -- DESIGN.md section 4)
+            constexpr bool PAIR1 = NV <= 2, PAIR2 = 2 * NV <= 2;
+            if (sw.fuse && lane_pairs() && (P.quad ? PAIR2 : PAIR1)) {
+                const dim3 g2 = lane_grid(g, cdiv(nlanes, 2));
+                ++n_pair;
+                if constexpr (PAIR2) if (P.quad) hipLaunchKernelGGL(k_trig_moments_pair<2 * NV>, g2, b, 0, st, P, P.seed_tau, P.D1, partial, val, nlanes);
+                if constexpr (PAIR1) if (!P.quad) hipLaunchKernelGGL(k_trig_moments_pair<NV>, g2, b, 0, st, P, P.seed_tau, P.D1, partial, val, nlanes);
+            } else if (sw.fuse) {
                 if (P.quad) hipLaunchKernelGGL((k_trig_moments<2 * NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
                 else hipLaunchKernelGGL((k_trig_moments<NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
             } else if (P.quad) {
@@ -3047,7 +3268,7 @@ struct Solver::Impl {
         if (comm && shard_size > 1 && (comm_size != shard_size || comm_rank != shard_rank))
             throw HipError("row-sharded solve: shard_rank / shard_size differ from the RCCL communicator's");
         n_collectives = 0; collective_bytes = 0;
-        n_gv = 0; n_gtv = 0;
+        n_gv = 0; n_gtv = 0; n_pair = 0;
         if (shard_size > 1 && nlanes > 1) throw ShapeError("row-sharded solves run one design at a time");
         for (int b = 0; b < nlanes; ++b) {
             LaneHost& L = LH[b];
@@ -3582,7 +3803,7 @@ struct Solver::Impl {
             info.lanes = nlanes;
             info.collectives = int(n_collectives);
             info.collective_bytes = collective_bytes;
-            info.gv_passes = int(n_gv); info.gtv_passes = int(n_gtv);
+            info.gv_passes = int(n_gv); info.gtv_passes = int(n_gtv); info.pair_passes = int(n_pair);
             info.dd_iters = LH[b].dd_iters; info.dd_kmax = LH[b].dd_kmax;
             info.dd_form = cap_form ? 0 : 1; info.cap_flop = cap_flop_sum; info.ms_cap = ms_cap;
             info.chol_launches = int(chol_launch_count);
