@@ -114,7 +114,7 @@ typedef struct mbfir_info {
     int correctors_taken;/* ... and the iterations that took the corrected direction (its step was 1 % longer)         */
     int gv_passes;       /* passes over the frequency rows the solve launched, all iterations: row responses G v ...    */
     int gtv_passes;      /* ... and transposed products G'v (a two-vector pass counts once; a lock-step unit's count)    */
-    int pair_passes;     /* ... and how many of these passes ran the lattice kernels with one thread per PAIR of lanes   */
+    int pair_passes;     /* ... and how many lattice passes (these and the normal-matrix moment passes) ran one thread per PAIR of lanes */
 } mbfir_info;
 
 /* All-reduce hook for row-sharded solves (one process per GPU).  `buf` is a DEVICE pointer to

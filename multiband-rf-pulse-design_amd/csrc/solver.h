@@ -50,7 +50,7 @@ struct SolveInfo {
     int lanes = 1;          // designs that shared the lock-step batch (ms_* are those of the whole batch)
     int lattice = 0;        // 1: lattice (matrix-free) mode; gram_flop then counts the moment recurrences
     int correctors = 0, correctors_taken = 0;   // centrality-corrector solves of this design, and how many of the corrected directions were taken
-    int pair_passes = 0;                        // ... and those of them whose lattice kernels ran in the paired form (one thread per two lanes; 0 for a single design)
+    int pair_passes = 0;                        // lattice passes (G v, G'v, H-build moments) that ran in the paired form (one thread per two lanes; 0 for a single design)
     int gv_passes = 0, gtv_passes = 0;          // row-response passes G v and transposed passes G'v the solve launched (all iterations; a lock-step unit's count)
 };
 

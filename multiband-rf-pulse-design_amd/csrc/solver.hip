@@ -687,7 +687,7 @@ __device__ __forceinline__ void trig_eval_sum(const double2 (*cf)[NVVMAX][SEGMAX
     for (int L = 0; L < NL; ++L)
 #pragma unroll
     for (int v = 0; v < NVVMAX; ++v) ac[L][v] = as[L][v] = 0;
-#pragma unroll (8 / NL)
+#pragma unroll (NVVMAX == 2 ? 8 / NL : 8)              // (one vector per lane: the body under the 64-register bound; else k_trig_eval's)
     for (int m = 0; m < n; ++m) {
 #pragma unroll
         for (int L = 0; L < NL; ++L)
@@ -739,9 +739,10 @@ __device__ __forceinline__ void trig_eval_lanes(const DProg& P, const double* co
             if (in >= 0) u[in] = ac[L][v] - as[L][v];
         }
 }
-// ... for the lanes 2z and 2z + 1 of a unit of nlanes (launch bounds: the waves per SIMD k_trig_eval gets; no spills -- DESIGN.md section 4)
+// ... for the lanes 2z and 2z + 1 of a unit of nlanes (launch bounds: one vector per lane the waves per SIMD k_trig_eval gets; two vectors per lane
+// 4, which leaves the loop k_trig_eval's unroll and 88 registers; no spills -- DESIGN.md section 4)
 template <int NV>
-__global__ __launch_bounds__(256, 8) void k_trig_eval_pair(DProg P, const double* __restrict__ vin, double* __restrict__ UU, int nlanes) {
+__global__ __launch_bounds__(256, NV == 1 ? 8 : 4) void k_trig_eval_pair(DProg P, const double* __restrict__ vin, double* __restrict__ UU, int nlanes) {
     __shared__ double2 cf[2][2 * NV][SEGMAX];
     bool live[2];
     size_t off0;
@@ -893,30 +894,100 @@ __global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __
     }
 }
 
-// k_trig_moments<NV, true>'s work for NL lanes in one block (lane pairs, see k_trig_eval_pair): P holds the tables the lanes share, PL[L] the lane's own program (alpha, beta,
-// f_ptr, f_rows), rows[L] / partial[L] its vectors, pp[L] its LDS image; one (c, s) chain per chunk serves all NL lanes.
+// a product and a sum rounded on their own, whatever -ffp-contract says
+__device__ __forceinline__ double mul_rounded(double a, double b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ double add_rounded(double a, double b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+// The operands of one folded frequency (kp: its +w entry, kn: its -w entry; -1: none) for the NL lanes of a block: out[L][0] / out[L][1] are what
+// freq_operands<NV, true> gives lane L for kp / kn -- every sum over its own rows in the same qq order -- but the 2 NL gather chains
+// f_ptr -> f_rows -> alpha / beta / row run side by side: all index loads of a step, then all row loads, then the sums (a chain past its
+// end reads entry 0 and adds nothing).  One after the other, as four calls of freq_operands run them, they are 4 x 4 dependent loads in front of the barrier.
+// Like the rotation (rotate<>), the sums are a COPY of what the compiler made of freq_operands in k_trig_moments<NV, true>, read off its ISA:
+// the first operand accumulates by FMA, out[0] = fma(alpha, x0, out[0]); the second one (NV = 2: beta x0 of a quad program, alpha x1 otherwise --
+// the compiler selects between the two products, so neither rides in an FMA) adds a product that is rounded first.  With one row per
+// frequency the two forms agree (the sum starts at 0); with several (the half-planes of fir_qprog_phs) they differ in the last bit.
 template <int NV, int NL>
-__device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* const (&PL)[NL], const double4* __restrict__ seeds, int na,
+__device__ __forceinline__ void freq_operands_lanes(const DProg* const (&PL)[NL], const double* const (&rows)[NL], int kp, int kn, double (&out)[NL][2][NV]) {
+    static_assert(NV <= 2, "freq_operands_lanes: the sums are spelt out for one and two operands");
+    constexpr int NS = 2 * NL;                            // chain z: lane z / 2, sign z % 2
+    const bool quad = PL[0]->quad;
+    const int nv = quad ? NV / 2 : NV;
+    int q0[NS], cnt[NS], nmax = 0;
+#pragma unroll
+    for (int z = 0; z < NS; ++z) {
+        const int i = (z & 1) ? kn : kp;
+        const int* fp = PL[z >> 1]->f_ptr;
+        q0[z] = i >= 0 ? fp[i] : 0;
+        cnt[z] = i >= 0 ? fp[i + 1] - q0[z] : 0;
+        nmax = max(nmax, cnt[z]);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) out[z >> 1][z & 1][v] = 0;
+    }
+    if (nv == 0) return;                                  // (one operand of a quad program: freq_operands adds nothing either)
+    for (int t = 0; t < nmax; ++t) {
+        int r[NS];
+#pragma unroll
+        for (int z = 0; z < NS; ++z) r[z] = PL[z >> 1]->f_rows[t < cnt[z] ? q0[z] + t : 0];
+        double al[NS], be[NS], x[NS][NV];
+#pragma unroll
+        for (int z = 0; z < NS; ++z) {
+            const DProg& Q = *PL[z >> 1];
+            al[z] = Q.alpha[r[z]]; be[z] = Q.beta[r[z]];
+#pragma unroll
+            for (int v = 0; v < NV; ++v) x[z][v] = v < nv ? rows[z >> 1][(long)v * Q.Rp + r[z]] : 0.0;
+        }
+#pragma unroll
+        for (int z = 0; z < NS; ++z) {
+            const bool on = t < cnt[z];
+            double (&o)[NV] = out[z >> 1][z & 1];
+            const double a0 = fma(al[z], x[z][0], o[0]);
+            o[0] = on ? a0 : o[0];
+            if constexpr (NV == 2) {
+                const double p = quad ? mul_rounded(be[z], x[z][0]) : mul_rounded(al[z], x[z][1]);
+                const double a1 = add_rounded(o[1], p);
+                o[1] = on ? a1 : o[1];
+            }
+        }
+    }
+}
+// k_trig_moments<NV, FOLD>'s work for NL lanes in one block (lane pairs, see k_trig_eval_pair): P holds the tables the lanes share, PL[L] the lane's own
+// program (alpha, beta, f_ptr, f_rows), rows[L] (FOLD) or src[L] (the lane's folded operands PPf) / partial[L] its vectors, pp[L] its LDS image; one
+// (c, s) chain per chunk serves all NL lanes.  The seeds of the first two chunks are loaded in front of the staging, so they arrive while the operands
+// are gathered; the next two chunks' travel during the loop before.
+template <int NV, int NL, bool FOLD>
+__device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* const (&PL)[NL], const double2* const (&src)[NL], const double4* __restrict__ seeds, int na, int nb,
                                                    double* const (&partial)[NL], const double* const (&rows)[NL], double2 (*pp)[NV][CGRP][CHK]) {
-    constexpr int nb = 0;                                 // (G'v: one progression)
     const int tid = threadIdx.x;
     const int ch0 = blockIdx.y * P.cgrp;
+    const int m = blockIdx.x * MPTS + tid;
+    const auto seed = [&](int cc) {                       // (zero without the chunk: a lone last chunk pairs with zero weight)
+        return (m < na + nb && cc < P.cgrp && ch0 + cc < P.nchunk) ? seeds[(long)(ch0 + cc) * (na + nb) + m] : make_double4(0.0, 0.0, 0.0, 0.0);
+    };
+    double4 sa = seed(0), sb = seed(1);
     for (int e = tid; e < P.cgrp * CHK; e += 256) {       // stage the operands of the group's chunks
         const int cc = e / CHK, q = e - cc * CHK, ch = ch0 + cc;
         const bool live = ch < P.nchunk && q < P.ch_count[ch < P.nchunk ? ch : 0];
         const int k = live ? P.ch_start[ch] + q : 0;
-        const int kp = live ? P.fold_pos[k] : -1, kn = live ? P.fold_neg[k] : -1;
+        if constexpr (FOLD) {
+            double ab[NL][2][NV];
+            freq_operands_lanes<NV, NL>(PL, rows, live ? P.fold_pos[k] : -1, live ? P.fold_neg[k] : -1, ab);
 #pragma unroll
-        for (int L = 0; L < NL; ++L) {
-            double a[NV], b[NV];
-            freq_operands<NV, true>(*PL[L], rows[L], kp, a);
-            freq_operands<NV, true>(*PL[L], rows[L], kn, b);
+            for (int L = 0; L < NL; ++L)
 #pragma unroll
-            for (int v = 0; v < NV; ++v) pp[L][v][cc][q] = make_double2(a[v] + b[v], a[v] - b[v]);
+            for (int v = 0; v < NV; ++v) pp[L][v][cc][q] = make_double2(ab[L][0][v] + ab[L][1][v], ab[L][0][v] - ab[L][1][v]);
+        } else {
+#pragma unroll
+            for (int L = 0; L < NL; ++L)
+#pragma unroll
+            for (int v = 0; v < NV; ++v) pp[L][v][cc][q] = live ? src[L][(long)v * P.Mpad + k] : make_double2(0.0, 0.0);
         }
     }
     __syncthreads();
-    const int m = blockIdx.x * MPTS + tid;
     if (m >= na + nb) return;
     double ag[NL][NV], as[NL][NV];
 #pragma unroll
@@ -929,12 +1000,11 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
         const int cha = ch0 + cl, chb = cha + 1;
         if (cha >= P.nchunk) break;
         const bool two = cl + 1 < P.cgrp && chb < P.nchunk;
-        const double4 sa = seeds[(long)cha * (na + nb) + m];
-        const double4 sb = two ? seeds[(long)chb * (na + nb) + m] : make_double4(0.0, 0.0, 0.0, 0.0);
+        const double4 na4 = seed(cl + 2), nb4 = seed(cl + 3);
         double c0 = sa.x, s0 = sa.y, c1 = sb.x, s1 = sb.y;
         const int cnt = max(P.ch_count[cha], two ? P.ch_count[chb] : 0);
         const int clb = two ? cl + 1 : cl;                  // (a lone last chunk pairs with itself at zero weight: sb = 0)
-#pragma unroll (4 / NL)
+#pragma unroll (NV * NL > 4 ? 2 : 4)
         for (int q = 0; q < cnt; ++q) {
 #pragma unroll
             for (int L = 0; L < NL; ++L)
@@ -947,6 +1017,7 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
             rotate<1>(c0, s0, sa.z, sa.w);
             rotate<1>(c1, s1, sb.z, sb.w);
         }
+        sa = na4; sb = nb4;
     }
 #pragma unroll
     for (int L = 0; L < NL; ++L)
@@ -956,12 +1027,13 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
         partial[L][(((long)blockIdx.y * NV + v) * 2 + 1) * P.LDM + m] = as[L][v];
     }
 }
-// ... the FOLD form for the lanes 2z and 2z + 1 of a unit of nlanes with seeds_shared and without dims (seeds: the unit's one table; na: every
-// lane's), one or two operands (with four the registers allow fewer waves per SIMD than k_trig_moments<4, true> gets -- DESIGN.md section 4)
-template <int NV>
-__global__ __launch_bounds__(256, 8) void k_trig_moments_pair(DProg P, const double4* __restrict__ seeds, int na, double* __restrict__ partial,
-                                                              const double* __restrict__ rows, int nlanes) {
-    static_assert(NV <= 2, "k_trig_moments_pair: one or two operands");
+// ... for the lanes 2z and 2z + 1 of a unit of nlanes with seeds_shared and without dims (seeds: the unit's one table; na, nb: every lane's).
+// FOLD: the G'v form, operands gathered from `rows` (one or two operands: with four the registers allow fewer waves per SIMD than
+// k_trig_moments<4, true> gets); else the H-build form, operands from the lanes' `src` (PPf), both progressions.  DESIGN.md section 4.
+template <int NV, bool FOLD = true>
+__global__ __launch_bounds__(256, 4) void k_trig_moments_pair(DProg P, const double2* __restrict__ src, const double4* __restrict__ seeds, int na, int nb,
+                                                                       double* __restrict__ partial, const double* __restrict__ rows, int nlanes) {
+    static_assert(!FOLD || NV <= 2, "k_trig_moments_pair: G'v of one or two operands");
     __shared__ double2 pp[2][NV][CGRP][CHK];
     bool live[2];
     size_t off0;
@@ -972,14 +1044,16 @@ __global__ __launch_bounds__(256, 8) void k_trig_moments_pair(DProg P, const dou
     Q.shift(off1);
     if (both) {
         const DProg* const p2[2] = {&P, &Q};
+        const double2* const s2[2] = {FOLD ? nullptr : byte_shift(src, off0), FOLD ? nullptr : byte_shift(src, off0 + off1)};
         double* const o2[2] = {byte_shift(partial, off0), byte_shift(partial, off0 + off1)};
-        const double* const r2[2] = {byte_shift(rows, off0), byte_shift(rows, off0 + off1)};
-        trig_moments_lanes<NV, 2>(P, p2, seeds, na, o2, r2, pp);
+        const double* const r2[2] = {FOLD ? byte_shift(rows, off0) : nullptr, FOLD ? byte_shift(rows, off0 + off1) : nullptr};
+        trig_moments_lanes<NV, 2, FOLD>(P, p2, s2, seeds, na, nb, o2, r2, pp);
     } else {
         const DProg* const p1[1] = {&Q};
+        const double2* const s1[1] = {FOLD ? nullptr : byte_shift(src, off0 + off1)};
         double* const o1[1] = {byte_shift(partial, off0 + off1)};
-        const double* const r1[1] = {byte_shift(rows, off0 + off1)};
-        trig_moments_lanes<NV, 1>(P, p1, seeds, na, o1, r1, pp);
+        const double* const r1[1] = {FOLD ? byte_shift(rows, off0 + off1) : nullptr};
+        trig_moments_lanes<NV, 1, FOLD>(P, p1, s1, seeds, na, nb, o1, r1, pp);
     }
 }
 
@@ -2591,7 +2665,7 @@ struct Solver::Impl {
     int comm_size = 0, comm_rank = 0;
     long n_collectives = 0;      // issued by the current solve
     double collective_bytes = 0; // ... and the bytes they carried
-    long n_pair = 0;             // ... and how many of their lattice launches ran the paired kernels (k_trig_eval_pair, k_trig_moments_pair)
+    long n_pair = 0;             // ... and how many lattice passes ran the paired kernels (k_trig_eval_pair: every G v, the residual's included; k_trig_moments_pair: G'v, H-build moments)
     long n_gv = 0, n_gtv = 0;    // passes over the frequency rows of the current solve: G v (apply_G / apply_G_winv2, the residual's row response), G'v (apply_GT)
     void allreduce(double* buf, long count, int op, hipStream_t on = nullptr) {
         if (shard_size <= 1) return;
@@ -2771,7 +2845,7 @@ struct Solver::Impl {
     }
 
     // ---- operators ----
-    // one thread runs the lattice recurrences of two lanes (k_trig_eval_pair, k_trig_moments_pair): the lanes of the unit share
+    // one thread runs the lattice recurrences of two lanes (k_trig_eval_pair: G v; k_trig_moments_pair: G'v and the H-build's moments): the lanes of the unit share
     // grid and lattice, have the same extents, and the solve is neither sharded nor on the extended-precision path
     bool lane_pairs() const { return sw.lanepair && nlanes >= 2 && P.seeds_shared && !P.dims && shard_size == 1 && !dd_unit; }
     template <int NV>
@@ -2820,11 +2894,14 @@ struct Solver::Impl {
     // pp == nullptr: the folded operands are in PPf already (k_freq_blocks_fold)
     void moments_array(int nv, const double* pp, const double4* seeds, int na, int nb, double* out) {
         dim3 g(cdiv(na + nb, MPTS), cdiv(P.nchunk, P.cgrp)), b(256), gf(cdiv(P.nfold, 256));
+        const bool pair = lane_pairs();                    // (the H-build's moment pass: k_trig_moments_pair<NV, false>)
+        if (pair) ++n_pair;
         switch (nv) {
 #define MOM_CASE(NVX)                                                                                                          \
             case NVX:                                                                                                          \
                 if (pp) hipLaunchKernelGGL((k_freq_fold<NVX, false>), lane_grid(gf, nlanes), b, 0, st, P, pp, PPf);            \
-                hipLaunchKernelGGL((k_trig_moments<NVX>), lane_grid(g, nlanes), b, 0, st, P, PPf, seeds, na, nb, partial);     \
+                if (pair) hipLaunchKernelGGL((k_trig_moments_pair<NVX, false>), lane_grid(g, cdiv(nlanes, 2)), b, 0, st, P, PPf, seeds, na, nb, partial, (const double*)nullptr, nlanes); \
+                else hipLaunchKernelGGL((k_trig_moments<NVX>), lane_grid(g, nlanes), b, 0, st, P, PPf, seeds, na, nb, partial); \
                 break;
             MOM_CASE(1) MOM_CASE(2) MOM_CASE(3) MOM_CASE(4) MOM_CASE(6)
 #undef MOM_CASE
@@ -2857,8 +2934,8 @@ struct Solver::Impl {
             if (sw.fuse && lane_pairs() && (P.quad ? PAIR2 : PAIR1)) {
                 const dim3 g2 = lane_grid(g, cdiv(nlanes, 2));
                 ++n_pair;
-                if constexpr (PAIR2) if (P.quad) hipLaunchKernelGGL(k_trig_moments_pair<2 * NV>, g2, b, 0, st, P, P.seed_tau, P.D1, partial, val, nlanes);
-                if constexpr (PAIR1) if (!P.quad) hipLaunchKernelGGL(k_trig_moments_pair<NV>, g2, b, 0, st, P, P.seed_tau, P.D1, partial, val, nlanes);
+                if constexpr (PAIR2) if (P.quad) hipLaunchKernelGGL(k_trig_moments_pair<2 * NV>, g2, b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val, nlanes);
+                if constexpr (PAIR1) if (!P.quad) hipLaunchKernelGGL(k_trig_moments_pair<NV>, g2, b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val, nlanes);
             } else if (sw.fuse) {
                 if (P.quad) hipLaunchKernelGGL((k_trig_moments<2 * NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
                 else hipLaunchKernelGGL((k_trig_moments<NV, true>), lane_grid(g, nlanes), b, 0, st, P, (const double2*)nullptr, P.seed_tau, P.D1, 0, partial, val);
@@ -3573,7 +3650,7 @@ struct Solver::Impl {
         double* rmail = sharded ? GTz + P.LDV : RB;
         if (P.trig) {                                     // G x rows are formed inside k_resid_rows
             ++n_gv;
-            hipLaunchKernelGGL(k_trig_eval<1>, lane_grid(dim3(cdiv(P.nfold, 256), P.useg), nlanes), dim3(256), 0, st, P, x, UU);
+            trig_eval<1>(x);
             hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(nbR), nlanes), dim3(256), 0, st, P, nullptr, s, z, Sc, rz, bz2, partR, UU, x);
         } else {
             apply_G<1>(x, Gx);
