@@ -444,6 +444,28 @@ int mbfir_test_chol(mbfir_ctx* ctx, int n, const double* H, double* out_l, doubl
  *  count, otherwise the value of MBFIR_CHOL_SPLIT to use. */
 int mbfir_test_chol_lanes(mbfir_ctx* ctx, int n, int nlanes, int form, const int* mask, const double* H, double* out_l, double* out_m);
 int mbfir_test_specfact(mbfir_ctx* ctx, int n, const double* x, double* h_re, double* h_im);
+/*  mbfir_test_unit_ops: the operators of ONE lock-step unit -- the njobs designs of `jobs` as its lanes, a single design as a unit of
+ *  one -- at an iterate the caller chooses.  The unit is set up by the stages a solve runs (switches read from the environment, lanes,
+ *  plan, arena, masks, seed tables) and scaled as an iteration's head scales it; every product then goes through the solve's own
+ *  launch code, so the kernels, grids, pairings and templates are the ones a solve of this unit would launch.  Per lane b (host
+ *  arrays of njobs blocks; nv = 1 or 2 vectors per block; ldx >= the unit's largest N = n_unknowns, ldr >= its largest R = n_rows,
+ *  ldh = N rounded up to 64; entries past a lane's own N / R are ignored):
+ *    in:  v (nv x ldx, x-space), u and sub (nv x ldr, row space; sub may be NULL = 0), s and z (ldr each: a strictly interior
+ *         pair of the lane's cone -- l orthant rows, n_q3 cones of three rows, then the big cone), mask (njobs ints or NULL: a lane
+ *         with 0 is switched off, as a finished design is in a solve);
+ *    in / out: gv = G v and wgv = W^-2 G v - sub (nv x ldr), gtu = G'u (nv x ldx), H (ldh x ldh, row-major: the LOWER triangle of
+ *         G'W^-2 G as the normal-matrix build leaves it ahead of the factorisation, padding included; the lattice path writes
+ *         the lower 64 x 64 tiles only).  All four go to the device before the launches and come back after them: what a masked
+ *         lane's blocks held on entry they hold on exit.
+ *    report (16 longs): [0] lattice path, [1] passes that ran one thread per pair of lanes, [2] the build took its one-pass
+ *         branch, [3] D1 lattice points, [4] evaluation segments, [5] folded entries, [6] runs (chunks), [7] chunks per block,
+ *         [8] np = ldh, [9] folded entries of lane 0 with one side empty, [10] segment length, [11] heterogeneous unit (per-lane
+ *         dimensions), [12] one seed table serves the unit, [13] G v passes, [14] G'v passes, [15] lanes.  tmin: the lattice origin.
+ *  opts: grid_m and dense_trig as for a solve.  Row-sharded units and units on the extended-precision path (opts.ddkkt >= 0 for
+ *  fir_qp_cvx) are MBFIR_E_ARG.  The context stays usable for solves. */
+int mbfir_test_unit_ops(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int nv, int ldx, int ldr, int ldh,
+                        const double* v, const double* u, const double* sub, const double* s, const double* z, const int* mask,
+                        double* gv, double* gtu, double* wgv, double* H, long* report, double* tmin);
 /*  mbfir_test_fold: the host-side analysis of a frequency grid w[m] for the lattice kernels (no GPU, no context): pairs
  *  +w / -w (fold != 0), cuts the folded list into equally spaced runs.  out[6]: lattice usable, folded entries, pairs,
  *  runs, longest run, self-check failures (must be 0).  (Own addition; nothing in the reference corresponds.) */

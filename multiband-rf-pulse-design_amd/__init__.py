@@ -150,6 +150,8 @@ SYMBOLS = {
     "mbfir_test_chol": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "mbfir_test_chol_lanes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp]),
     "mbfir_test_specfact": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "mbfir_test_unit_ops": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int,
+                                      _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _lp, _dp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "mbfir_test_mfma_peak": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -719,15 +721,8 @@ def get_pool(streams=4, device=None):
     return _pools[key]
 
 
-def solve_batch(jobs, *, opts=None, streams=4, ctxs=None, info=False, solutions=False):
-    """Independent designs, `streams` in flight at a time on one GPU (mbfir_solve_batch): the shape of
-    the reference's outer loops -- the probes of a min-order / min-duration bisection, parameter sweeps.
-    jobs: sequence of (designer, args) with designer in {'fir_ap_cvx', 'fir_qp_cvx', 'fir_linprog',
-    'fir_qprog_phs'} and args the positional arguments of that function (n, f, a, d, ...).
-    Returns a list of (h, status) -- or (h, status, info) -- in job order, as the single calls return.
-    solutions=True appends the conic solution z of every job (mbfir_last_solution) to its tuple."""
-    ctxs = ctxs or get_pool(streams)
-    o = opts if opts is not None else make_opts()
+def _pack_jobs(jobs, solutions=False):
+    """(designer, args) pairs as an array of struct mbfir_job; `keep` holds the arrays the structs point into."""
     arr = (Job * len(jobs))()
     keep = []
     for q, (name, args) in enumerate(jobs):
@@ -765,6 +760,19 @@ def solve_batch(jobs, *, opts=None, streams=4, ctxs=None, info=False, solutions=
         J.f, J.a, J.d, J.h_re, J.h_im = _ptr(f), _ptr(a), _ptr(d), _ptr(hre), _ptr(him)
         for t in range(4):
             J.params[t] = params[t]
+    return arr, keep
+
+
+def solve_batch(jobs, *, opts=None, streams=4, ctxs=None, info=False, solutions=False):
+    """Independent designs, `streams` in flight at a time on one GPU (mbfir_solve_batch): the shape of
+    the reference's outer loops -- the probes of a min-order / min-duration bisection, parameter sweeps.
+    jobs: sequence of (designer, args) with designer in {'fir_ap_cvx', 'fir_qp_cvx', 'fir_linprog',
+    'fir_qprog_phs'} and args the positional arguments of that function (n, f, a, d, ...).
+    Returns a list of (h, status) -- or (h, status, info) -- in job order, as the single calls return.
+    solutions=True appends the conic solution z of every job (mbfir_last_solution) to its tuple."""
+    ctxs = ctxs or get_pool(streams)
+    o = opts if opts is not None else make_opts()
+    arr, keep = _pack_jobs(jobs, solutions)
     handles = (C.c_void_p * len(ctxs))(*[c._h for c in ctxs])
     load_library().mbfir_solve_batch(handles, len(ctxs), arr, len(jobs), C.byref(o))
     out = []
@@ -883,6 +891,50 @@ def test_chol(H, ctx=None):
     L, M = np.zeros((n, n)), np.zeros((n, n))
     _check(ctx, load_library().mbfir_test_chol(ctx._h, n, _ptr(H), _ptr(L), _ptr(M)))
     return L, M
+
+
+UNIT_OPS_REPORT = ("lattice", "pair_passes", "one_pass", "D1", "useg", "nfold", "nchunk", "cgrp", "np", "empty_side", "seg", "hetero",
+                   "seeds_shared", "gv_passes", "gtv_passes", "lanes")
+
+
+def test_unit_ops(jobs, v, u, s, z, *, sub=None, mask=None, opts=None, init=None, ctx=None):
+    """The operators of one lock-step unit at the iterate (s, z) (mbfir_test_unit_ops).  jobs: (designer, args) pairs as for
+    solve_batch, the lanes of the unit.  v: (lanes, nv, N) x-space vectors, u and sub: (lanes, nv, R) row-space vectors, s and z:
+    (lanes, R); a lane shorter than the unit's largest is zero-padded by the caller.  init: the four output arrays (gv, gtu, wgv, H)
+    as they go in (default NaN), so that what a masked lane returns can be compared with it.  Returns (gv, gtu, wgv, H, report):
+    G v and W^-2 G v - sub (lanes, nv, R), G'u (lanes, nv, N), H (lanes, np, np; the lower triangle is meaningful), report a dict
+    of UNIT_OPS_REPORT and tmin."""
+    ctx = ctx or get_context()
+    arr, keep = _pack_jobs(jobs)
+    v, u = np.ascontiguousarray(v, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+    s, z = np.ascontiguousarray(s, dtype=np.float64), np.ascontiguousarray(z, dtype=np.float64)
+    nl, nv, N = v.shape
+    R = u.shape[2]
+    if nl != len(jobs) or u.shape != (nl, nv, R) or s.shape != (nl, R) or z.shape != (nl, R):
+        raise ValueError("v, u, s, z have inconsistent shapes")
+    npad = -(-N // 64) * 64
+    if sub is not None:
+        sub = np.ascontiguousarray(sub, dtype=np.float64)
+        if sub.shape != u.shape:
+            raise ValueError("sub must have the shape of u")
+    if init is None:
+        init = (np.full((nl, nv, R), np.nan), np.full((nl, nv, N), np.nan), np.full((nl, nv, R), np.nan), np.full((nl, npad, npad), np.nan))
+    gv, gtu, wgv, H = [np.array(a, dtype=np.float64, order="C") for a in init]
+    if gv.shape != u.shape or gtu.shape != v.shape or wgv.shape != u.shape or H.shape != (nl, npad, npad):
+        raise ValueError("init arrays have the wrong shapes")
+    mk = (C.c_int * nl)(*[int(m) for m in mask]) if mask is not None else None
+    report = np.zeros(len(UNIT_OPS_REPORT), dtype=np.int64)
+    tmin = np.zeros(1)
+    o = opts if opts is not None else make_opts()
+    rc = load_library().mbfir_test_unit_ops(ctx._h, arr, nl, C.byref(o), nv, N, R, npad, _ptr(v), _ptr(u),
+                                            _ptr(sub) if sub is not None else None, _ptr(s), _ptr(z), mk, _ptr(gv), _ptr(gtu),
+                                            _ptr(wgv), _ptr(H), report.ctypes.data_as(_lp), _ptr(tmin))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    rep = {k: int(x) for k, x in zip(UNIT_OPS_REPORT, report)}
+    rep["tmin"] = float(tmin[0])
+    return gv, gtu, wgv, H, rep
 
 
 def test_chol_lanes(Hs, form=-1, mask=None, ctx=None):

@@ -659,6 +659,30 @@ int mbfir_test_chol(mbfir_ctx* ctx, int n, const double* H, double* out_l, doubl
 int mbfir_test_chol_lanes(mbfir_ctx* ctx, int n, int nlanes, int form, const int* mask, const double* H, double* out_l, double* out_m) {
     MBFIR_TRY(ctx, ctx->solver->test_chol_lanes(n, nlanes, form, mask, H, out_l, out_m));
 }
+int mbfir_test_unit_ops(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int nv, int ldx, int ldr, int ldh,
+                        const double* v, const double* u, const double* sub, const double* s, const double* z, const int* mask,
+                        double* gv, double* gtu, double* wgv, double* H, long* report, double* tmin) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_unit_ops: " + why; return MBFIR_E_ARG; };
+    if (!jobs || njobs < 1 || nv < 1 || nv > 2 || !v || !u || !s || !z || !gv || !gtu || !wgv || !H || !report || !tmin) return bad("bad argument");
+    try {
+        std::vector<TrigProgram> progs(njobs);
+        std::vector<const TrigProgram*> Ps;
+        for (int q = 0; q < njobs; ++q) {
+            std::string e;
+            if (assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e) != 0) return bad("job " + std::to_string(q) + ": " + e);
+            Ps.push_back(&progs[q]);
+        }
+        const SolveOpts so = to_opts(opts, progs[0].which);
+        if (so.shard_size > 1) return bad("row-sharded units are not taken");
+        if (so.ddkkt_theta > 0) return bad("units on the extended-precision path are not taken (opts.ddkkt = -1 for fir_qp_cvx)");
+        UnitOps io;
+        io.nv = nv; io.ldx = ldx; io.ldr = ldr; io.ldh = ldh; io.v = v; io.u = u; io.sub = sub; io.s = s; io.z = z; io.mask = mask;
+        io.gv = gv; io.gtu = gtu; io.wgv = wgv; io.H = H; io.report = report; io.tmin = tmin;
+        ctx->solver->test_unit_ops(Ps, so, io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll) {
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;

@@ -54,6 +54,19 @@ struct SolveInfo {
     int gv_passes = 0, gtv_passes = 0;          // row-response passes G v and transposed passes G'v the solve launched (all iterations; a lock-step unit's count)
 };
 
+// Arguments of Solver::test_unit_ops (mbfir_test_unit_ops of include/mbfir.h, which says what each array holds): host arrays of
+// nlanes blocks each; report: UNIT_OPS_REPORT longs, see the UO_* indices.
+struct UnitOps {
+    int nv = 1, ldx = 0, ldr = 0, ldh = 0;
+    const double *v = nullptr, *u = nullptr, *sub = nullptr, *s = nullptr, *z = nullptr;
+    const int* mask = nullptr;
+    double *gv = nullptr, *gtu = nullptr, *wgv = nullptr, *H = nullptr;
+    long* report = nullptr;
+    double* tmin = nullptr;
+};
+enum { UO_LATTICE = 0, UO_PAIR_PASSES, UO_ONE_PASS, UO_D1, UO_USEG, UO_NFOLD, UO_NCHUNK, UO_CGRP, UO_NP, UO_EMPTY_SIDE, UO_SEG,
+       UO_HETERO, UO_SEEDS_SHARED, UO_GV_PASSES, UO_GTV_PASSES, UO_LANES, UNIT_OPS_REPORT = 16 };
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -82,6 +95,9 @@ public:
     void test_chol(int n, const double* H, double* out_l, double* out_m);
     void test_chol_lanes(int n, int nlanes, int form, const int* mask, const double* H, double* out_l, double* out_m);
     void test_specfact(int n, const double* x, double* h_re, double* h_im);
+    // the operators of one lock-step unit (a unit of one included) at a caller's (s, z), through the stages and launch code of
+    // solve_lanes: G v, G'u, W^-2 G v - sub and the normal matrix as build_H leaves it ahead of its factorisation
+    void test_unit_ops(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitOps& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
     void test_mfma_peak(double* tf_mfma, double* tf_valu);

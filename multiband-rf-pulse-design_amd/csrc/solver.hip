@@ -3153,6 +3153,8 @@ struct Solver::Impl {
     }
     // ddk > 0: this iteration runs the extended-precision solve -- H_w from the capped weights (D.dlc, D.m3c),
     // then H = H_w + U'XU and its Cholesky factor in double-double
+    double* H_keep = nullptr;    // test_unit_ops: where build_H copies the lanes' H (np x np each, one after the other) ahead of the factorisation
+    bool h_one_pass = false;     // the last build_H took its one_pass branch
     void build_H(int ddk = 0) {
         double* yy_sum = nullptr;
         const double* dlw = ddk > 0 ? D.dlc : dl;
@@ -3163,6 +3165,7 @@ struct Solver::Impl {
         P.dl_plain = P.dd_lane ? dl : nullptr;
         const int nwv = P.quad ? 3 : 1, nvb = P.quad ? 2 * P.Ne : P.Ne;
         const bool one_pass = P.trig && P.Ne > 0 && P.tmin == 0.0 && nwv + nvb <= 4;
+        h_one_pass = one_pass;
         if (!one_pass) hipLaunchKernelGGL(k_freq_blocks, lane_grid(dim3(cdiv(P.Mf, 256)), nlanes), dim3(256), 0, st, P, dlw, w3, Dw, BB, m3c);
         hipEvent_t g0 = timing ? next_event() : nullptr, g1 = timing ? next_event() : nullptr;
         if (P.trig) {
@@ -3301,6 +3304,9 @@ struct Solver::Impl {
             }
             hipLaunchKernelGGL(k_pack_tril, dim3((unsigned)ntile), dim3(256), 0, st, H, P.np, M, 1);
         }
+        // (test_unit_ops: every lane's H as the factorisation is about to find it)
+        if (H_keep) MBFIR_HIP(hipMemcpy2DAsync(H_keep, sizeof(double) * P.np * P.np, H, nlanes > 1 ? lane_bytes : sizeof(double) * P.np * P.np,
+                                               sizeof(double) * P.np * P.np, nlanes, hipMemcpyDeviceToDevice, st));
         hipEvent_t c0 = timing ? next_event() : nullptr, c1 = timing ? next_event() : nullptr;
         P.dd_lane = nullptr; P.dl_plain = nullptr;
         if (ddk > 0 && cap_form) {
@@ -3620,6 +3626,21 @@ struct Solver::Impl {
             MBFIR_HIP(hipMemcpyAsync(reinterpret_cast<char*>(Sc) + (size_t)b * lane_bytes, q, sizeof(double) * S_COUNT, hipMemcpyHostToDevice, st));
         }
     }
+    // A unit up to its first launch that depends on an iterate: switches, lanes, plan, arena, masks (LH[b].live: all lanes in a
+    // solve), A1 / seed tables and the lanes' scalars.  LH: one entry per lane.
+    UnitPlan setup_unit(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, std::vector<LaneHost>& LH) {
+        nlanes = int(Qs.size());
+        sw = read_switches();
+        chol_set_lose_step(sw.test_lose_flag, st);
+        prepare_lanes(Qs, o, LH);
+        const UnitPlan U = plan_unit(LH, o);
+        layout_arena(LH, U);
+        mask_dev.assign(size_t(MASK_ROWS) * MAX_LANES, -1); mask_new.assign(size_t(MASK_ROWS) * MAX_LANES, 0);
+        push_masks(LH);
+        P.mask = mask_row(0);
+        start_lanes(LH);
+        return U;
+    }
     void cone_shift(double* v) {
         const int nb = std::max(nbC, 1);
         hipLaunchKernelGGL(k_cone_resid, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, v, partR);
@@ -3662,9 +3683,13 @@ struct Solver::Impl {
     }
     // The head of an iteration -- NT scaling, normal matrix, factorisation: everything that depends on the iterate (s, z) alone.
     // On the extended-precision path it first takes every live lane's strong set (a host synchronisation).
-    void launch_head(std::vector<LaneHost>& LH, const SolveOpts& o) {
+    // the NT scaling of the iterate (s, z)
+    void launch_scaling() {
         hipLaunchKernelGGL(k_scaling, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, s, z, dl, wl, w3, lam, bz2, wbz);
         if (P.big) hipLaunchKernelGGL(k_big_scaling, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, s, z, wbb, lam, Sc);
+    }
+    void launch_head(std::vector<LaneHost>& LH, const SolveOpts& o) {
+        launch_scaling();
         int ks[MAX_LANES];
         if (dd_unit) {
             // every live lane its own strong set; then the masks of the two modes (the sweep rows follow: push_masks)
@@ -4070,17 +4095,8 @@ void Solver::solve_lanes(const std::vector<const TrigProgram*>& Qs, const SolveO
     const double t_begin = now_ms();
     const int nlanes = int(Qs.size());
     if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
-    S.nlanes = nlanes;
-    S.sw = read_switches();
-    chol_set_lose_step(S.sw.test_lose_flag, S.st);
     std::vector<LaneHost> LH(nlanes);
-    S.prepare_lanes(Qs, o, LH);
-    const UnitPlan U = S.plan_unit(LH, o);
-    S.layout_arena(LH, U);
-    S.mask_dev.assign(size_t(MASK_ROWS) * MAX_LANES, -1); S.mask_new.assign(size_t(MASK_ROWS) * MAX_LANES, 0);
-    S.push_masks(LH);
-    S.P.mask = S.mask_row(0);
-    S.start_lanes(LH);
+    const UnitPlan U = S.setup_unit(Qs, o, LH);
     MBFIR_HIP(hipStreamSynchronize(S.st));
     const double t_assembled = now_ms();
     S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
@@ -4186,6 +4202,75 @@ void Solver::test_gram(int m, int nt, int nw, const double* A, const double* d, 
                                    (size_t)nt * 8, nt, hipMemcpyDeviceToHost, S.st));
     MBFIR_HIP(hipStreamSynchronize(S.st));
     MBFIR_HIP(hipGetLastError());
+}
+
+// The operators of one unit at a caller's iterate (include/mbfir.h: mbfir_test_unit_ops).  The unit is set up by the stages of
+// solve_lanes (setup_unit), scaled as launch_head scales it (launch_scaling), and every product goes through the solve's own launch
+// code: apply_G, apply_GT, apply_G_winv2, build_H(0).  The operands sit in work buffers the scaling does not write.
+void Solver::test_unit_ops(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, const UnitOps& io) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int nlanes = int(Qs.size()), nv = io.nv;
+    if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
+    if (nv < 1 || nv > 2) throw HipError("test_unit_ops: one or two vectors");
+    std::vector<LaneHost> LH(nlanes);
+    for (int b = 0; b < nlanes; ++b) LH[b].live = !io.mask || io.mask[b] != 0;
+    S.setup_unit(Qs, o, LH);
+    S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
+    S.timing = false;
+    S.chol_launch_count = 0; S.dd_epoch = 0;
+    S.taps_valid = false;
+    const DProg& P = S.P;
+    const size_t np2 = (size_t)P.np * P.np;
+    if (io.ldx < P.N || io.ldx > P.LDV || io.ldr < P.R || io.ldr > P.Rp || io.ldh != P.np)
+        throw HipError("test_unit_ops: ldx / ldr / ldh do not fit the unit (N " + std::to_string(P.N) + ", R " + std::to_string(P.R) + ", np " + std::to_string(P.np) + ")");
+    DevBuf keep(np2 * sizeof(double) * nlanes);
+    double *dv = S.dx2, *du = S.dz2, *dsub = S.gdx2, *dgv = S.tmpR, *dgtu = S.tmpN, *dwgv = S.wpR, *dgout = S.bz2;
+    const size_t xb = sizeof(double) * io.ldx, rb = sizeof(double) * io.ldr;
+    // host block of lane b <-> the lane's device vectors (nv vectors LDV or Rp apart)
+    auto lane = [&](double* p, int b) { return reinterpret_cast<double*>(reinterpret_cast<char*>(p) + (size_t)b * S.lane_bytes); };
+    auto up = [&](double* dst, size_t dpitch, const double* src, size_t row, int rows, int b) {
+        MBFIR_HIP(hipMemcpy2DAsync(lane(dst, b), dpitch * sizeof(double), src + (size_t)b * rows * (row / sizeof(double)), row, row, rows, hipMemcpyHostToDevice, S.st));
+    };
+    auto down = [&](double* dst, const double* src, size_t spitch, size_t row, int rows, int b) {
+        MBFIR_HIP(hipMemcpy2DAsync(dst + (size_t)b * rows * (row / sizeof(double)), row, lane(const_cast<double*>(src), b), spitch * sizeof(double), row, rows, hipMemcpyDeviceToHost, S.st));
+    };
+    for (int b = 0; b < nlanes; ++b) {
+        up(dv, P.LDV, io.v, xb, nv, b); up(du, P.Rp, io.u, rb, nv, b);
+        if (io.sub) up(dsub, P.Rp, io.sub, rb, nv, b);
+        up(S.s, P.Rp, io.s, rb, 1, b); up(S.z, P.Rp, io.z, rb, 1, b);
+        up(dgv, P.Rp, io.gv, rb, nv, b); up(dgtu, P.LDV, io.gtu, xb, nv, b); up(dwgv, P.Rp, io.wgv, rb, nv, b);
+        MBFIR_HIP(hipMemcpyAsync(lane(S.H, b), io.H + (size_t)b * np2, np2 * sizeof(double), hipMemcpyHostToDevice, S.st));
+    }
+    S.launch_scaling();
+    if (nv == 1) {
+        S.apply_G<1>(dv, dgv);
+        S.apply_GT<1>(du, dgtu);
+        S.apply_G_winv2<1>(dv, dgout, io.sub ? dsub : nullptr, dwgv);
+    } else {
+        S.apply_G<2>(dv, dgv);
+        S.apply_GT<2>(du, dgtu);
+        S.apply_G_winv2<2>(dv, dgout, io.sub ? dsub : nullptr, dwgv);
+    }
+    S.H_keep = keep.as<double>();
+    try { S.build_H(0); } catch (...) { S.H_keep = nullptr; throw; }
+    S.H_keep = nullptr;
+    for (int b = 0; b < nlanes; ++b) {
+        down(io.gv, dgv, P.Rp, rb, nv, b); down(io.gtu, dgtu, P.LDV, xb, nv, b); down(io.wgv, dwgv, P.Rp, rb, nv, b);
+        MBFIR_HIP(hipMemcpyAsync(io.H + (size_t)b * np2, keep.as<double>() + (size_t)b * np2, np2 * sizeof(double), hipMemcpyDeviceToHost, S.st));
+    }
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    const LatticeInfo& L0 = LH[0].Lt;
+    long empty = 0;
+    for (size_t k = 0; k < L0.wf.size(); ++k) empty += (L0.fold_pos[k] < 0 || L0.fold_neg[k] < 0) ? 1 : 0;
+    long* r = io.report;
+    for (int i = 0; i < UNIT_OPS_REPORT; ++i) r[i] = 0;
+    r[UO_LATTICE] = P.trig; r[UO_PAIR_PASSES] = S.n_pair; r[UO_ONE_PASS] = S.h_one_pass ? 1 : 0;
+    r[UO_D1] = P.D1; r[UO_USEG] = P.useg; r[UO_NFOLD] = P.nfold; r[UO_NCHUNK] = P.nchunk; r[UO_CGRP] = P.cgrp; r[UO_NP] = P.np;
+    r[UO_EMPTY_SIDE] = empty; r[UO_SEG] = P.seg; r[UO_HETERO] = P.dims ? 1 : 0; r[UO_SEEDS_SHARED] = P.seeds_shared;
+    r[UO_GV_PASSES] = S.n_gv; r[UO_GTV_PASSES] = S.n_gtv; r[UO_LANES] = nlanes;
+    *io.tmin = P.tmin;
 }
 
 void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
