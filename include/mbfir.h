@@ -359,6 +359,36 @@ int mbfir_abr2_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                          const double* y, int nscale, const double* scales, int mode, int ndir, const double* v_re,
                          const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im, double* da_re, double* da_im,
                          double* db_re, double* db_im);
+/* ---- Least-squares products of mbfir_abr_batch / mbfir_abr2_batch ---------------------------------------------------------------
+ * For a profile f(a, b) of the forward call's outputs, a real weight w >= 0 and a target t per output entry, the loss of a pulse is
+ * L = 1/2 sum w |f - t|^2 over its points and scales, and J = df / drf is the Jacobian of the profile with respect to the rf samples
+ * (real-linear, as in the tangent calls).  profile: 0 ex f = 2 conj(a) b, 1 se f = i b^2, 2 inv (sat) f = 1 - 2 |b|^2, 3 st
+ * f = i a^2.  The forward call's inputs come first, mode included; w (and t_re / t_im) are laid out as the forward call lays out a.
+ *   lsq: loss[npulse] receives L per pulse, g_re / g_im the gradient J^H W (f - t) = dL / d Re rf + i dL / d Im rf per rf sample.
+ *        t_im may be NULL (a real target); for profile 2, whose f is real, t_im is not read.
+ *   gn:  ndir >= 1 directions per pulse in v_re / v_im, laid out as mbfir_abr_jvp_batch lays them out; h_re / h_im receive the
+ *        Gauss-Newton products J^H W J v, pulse p from ndir roff[p], direction-major.
+ * Each is one upload, one sweep launch (one workgroup per forward workgroup, and for gn per direction) plus a fold, and one
+ * download of the n (ndir n) complex results per pulse and the losses: nothing of point size comes back.  No atomics: a pulse's
+ * g, L and H v bits depend only on the pulse, its grid, its weights, target or direction and the scale list, not on the batch, its
+ * order or ndir.  A point of weight 0 contributes exact zeros, and so does scale 0 to g and H v.  The argument checks and their
+ * MBFIR_E_ARG messages are those of the forward calls, then in this order: w, t_re, v_re, v_im or an output NULL ("a required array
+ * is null"); profile out of range; a negative or non-finite weight; ndir < 1; partials or a workgroup count that overflow.  No
+ * device work is done before they pass. */
+int mbfir_abr_lsq_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                        const double* w, const double* t_re, const double* t_im, double* loss, double* g_re, double* g_im);
+int mbfir_abr2_lsq_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                         const double* t_re, const double* t_im, double* loss, double* g_re, double* g_im);
+int mbfir_abr_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                       int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                       const double* w, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
+int mbfir_abr2_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                        const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                        const double* y, int nscale, const double* scales, int mode, int profile, const double* w, int ndir,
+                        const double* v_re, const double* v_im, double* h_re, double* h_im);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

@@ -136,6 +136,14 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
                                        _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp,
+                                      _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr2_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
+                                       _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp,
+                                     C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_abr2_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
+                                      _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_test_jvp_group": (C.c_int, []),
     "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
@@ -1348,6 +1356,127 @@ def abr2_jvp_batch(pulses, x, y, tangents, *, scales=(1.0,), hard_pulse=False, c
     ctx = ctx or get_context()
     _abr2_call(load_library().mbfir_abr2_jvp_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, [K] + vplanes + out + tan)
     return _jvp_result(out, tan, ooff, K, keep, [(S, k, j) for k, j in zip(nx, ny)], convention)
+
+
+# ---- least-squares products of abr_batch / abr2_batch: loss and gradient, Gauss-Newton products (mbfir_abr[2]_lsq / gn_batch) ---
+PROFILES = {"ex": 0, "se": 1, "inv": 2, "sat": 2, "st": 3}
+
+
+def _profile(who, profile):
+    if profile not in PROFILES:
+        raise ValueError("%s: profile must be one of 'ex', 'se', 'inv' ('sat') or 'st', not %r" % (who, profile))
+    return PROFILES[profile]
+
+
+def _weight_plane(who, weights, shapes):
+    """weights: per pulse a real array in the shape the forward call returns, or without its scale axis -> the concatenated plane"""
+    weights = list(weights)
+    if len(weights) != len(shapes):
+        raise ValueError("%s: %d weight arrays for %d pulses" % (who, len(weights), len(shapes)))
+    ws = []
+    for q, (w, shape) in enumerate(zip(weights, shapes)):
+        w = np.asarray(w, dtype=np.float64)
+        if w.shape != shape and w.shape != shape[1:]:
+            raise ValueError("%s: the weights of pulse %d have shape %s, not %s or %s" % (who, q, w.shape, shape, shape[1:]))
+        if not np.all(np.isfinite(w)) or np.any(w < 0):
+            raise ValueError("%s: a weight of pulse %d is negative or not finite" % (who, q))
+        ws.append(np.broadcast_to(w, shape).ravel())
+    return _vec(np.concatenate(ws))
+
+
+def _target_planes(who, targets, shapes, kind):
+    targets = list(targets)
+    if len(targets) != len(shapes):
+        raise ValueError("%s: %d targets for %d pulses" % (who, len(targets), len(shapes)))
+    ts = []
+    for q, (t, shape) in enumerate(zip(targets, shapes)):
+        t = np.asarray(t)
+        if t.shape != shape:
+            raise ValueError("%s: the target of pulse %d has shape %s, the forward call returns %s" % (who, q, t.shape, shape))
+        if kind == 2 and np.iscomplexobj(t) and np.any(t.imag != 0):
+            raise ValueError("%s: the profile 'inv' is real, the target of pulse %d is complex" % (who, q))
+        ts.append(t.astype(np.complex128).ravel())
+    t = np.concatenate(ts)
+    return [_vec(t.real), _vec(t.imag)]
+
+
+def _lsq_result(rfs, loss, grad):
+    roff = _offsets([len(r) for r in rfs])
+    g_all = grad[0] + 1j * grad[1]
+    return [(float(loss[q]), g_all[roff[q]:roff[q + 1]]) for q in range(len(rfs))]
+
+
+def _gn_result(rfs, K, keep, h):
+    roff = _offsets([len(r) for r in rfs])
+    h_all = h[0] + 1j * h[1]
+    return [h_all[K * roff[q]:K * roff[q + 1]].reshape((K, len(rfs[q])) if keep else (len(rfs[q]),)) for q in range(len(rfs))]
+
+
+def abr_lsq_batch(pulses, x, targets, weights, *, profile="ex", scales=(1.0,), hard_pulse=False, ctx=None):
+    """Loss and gradient of a weighted least-squares fit of abr_batch's profile, in one device call (mbfir_abr_lsq_batch): pulses,
+    x, scales and hard_pulse as for abr_batch, in the 'abrm' convention only (the profiles are those of ab2ex, ab2se, ab2inv /
+    ab2sat and ab2st on abrm's (a, b)).  profile: 'ex' f = 2 conj(a) b, 'se' f = i b^2, 'inv' (alias 'sat') f = 1 - 2 |b|^2, 'st'
+    f = i a^2.  targets: per pulse an array of the shape (S, nx) that abr_batch returns (real for 'inv'); weights: per pulse a real
+    array >= 0 of that shape, or of shape (nx,) for every scale.  Returns a list of (L, grad) per pulse: L = 1/2 sum w |f - t|^2
+    over the points and scales, and grad = dL/dRe rf + i dL/dIm rf, complex (n,).  Nothing of point size comes back from the
+    device.  Deterministic: a pulse's L and grad bits depend only on the pulse, its grid, target, weights and the scales."""
+    who = "abr_lsq_batch"
+    sc, rfs, gs, xs, nx = _abr_args(who, pulses, x, scales, "abrm")
+    kind = _profile(who, profile)
+    shapes = [(len(sc), k) for k in nx]
+    planes = [kind, _weight_plane(who, weights, shapes)] + _target_planes(who, targets, shapes, kind)
+    R = sum(len(r) for r in rfs)
+    loss, grad = np.zeros(len(rfs)), [np.zeros(R) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_lsq_batch, ctx, sc, rfs, gs, xs, hard_pulse, planes + [loss] + grad)
+    return _lsq_result(rfs, loss, grad)
+
+
+def abr2_lsq_batch(pulses, x, y, targets, weights, *, profile="ex", scales=(1.0,), hard_pulse=False, ctx=None):
+    """abr_lsq_batch for abr2_batch (mbfir_abr2_lsq_batch): targets of shape (S, nx, ny), weights of that shape or (nx, ny)."""
+    who = "abr2_lsq_batch"
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args(who, pulses, x, y, scales, "abrm")
+    kind = _profile(who, profile)
+    shapes = [(len(sc), k, j) for k, j in zip(nx, ny)]
+    planes = [kind, _weight_plane(who, weights, shapes)] + _target_planes(who, targets, shapes, kind)
+    R = sum(len(r) for r in rfs)
+    loss, grad = np.zeros(len(rfs)), [np.zeros(R) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_lsq_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes + [loss] + grad)
+    return _lsq_result(rfs, loss, grad)
+
+
+def abr_gn_batch(pulses, x, tangents, weights, *, profile="ex", scales=(1.0,), hard_pulse=False, ctx=None):
+    """Gauss-Newton products of the fit of abr_lsq_batch, in one device call (mbfir_abr_gn_batch): H v = J^H W J v for J = df / drf
+    (real-linear in v) and W the weights; arguments as for abr_lsq_batch ('abrm' convention only), with tangents as abr_jvp_batch
+    takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every pulse.  Returns per pulse a
+    complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real inner product Re sum conj(u) v.  A product's
+    bits depend only on its pulse, grid, weights, direction and the scales: not on the batch or the direction's place among K."""
+    who = "abr_gn_batch"
+    sc, rfs, gs, xs, nx = _abr_args(who, pulses, x, scales, "abrm")
+    kind = _profile(who, profile)
+    K, keep, vplanes = _tangents(who, tangents, rfs)
+    w = _weight_plane(who, weights, [(len(sc), k) for k in nx])
+    h = [np.zeros(K * sum(len(r) for r in rfs)) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_gn_batch, ctx, sc, rfs, gs, xs, hard_pulse, [kind, w, K] + vplanes + h)
+    return _gn_result(rfs, K, keep, h)
+
+
+def abr2_gn_batch(pulses, x, y, tangents, weights, *, profile="ex", scales=(1.0,), hard_pulse=False, ctx=None):
+    """abr_gn_batch for abr2_batch (mbfir_abr2_gn_batch): weights of shape (S, nx, ny) or (nx, ny)."""
+    who = "abr2_gn_batch"
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args(who, pulses, x, y, scales, "abrm")
+    kind = _profile(who, profile)
+    K, keep, vplanes = _tangents(who, tangents, rfs)
+    w = _weight_plane(who, weights, [(len(sc), k, j) for k, j in zip(nx, ny)])
+    h = [np.zeros(K * sum(len(r) for r in rfs)) for _ in range(2)]
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_gn_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, [kind, w, K] + vplanes + h)
+    return _gn_result(rfs, K, keep, h)
+
+
+from .refine import refine_batch   # noqa: E402  (batched Levenberg-Marquardt on the four calls above)
 
 
 def jvp_group():

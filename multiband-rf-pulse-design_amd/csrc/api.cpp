@@ -1037,6 +1037,97 @@ int mbfir_abr2_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                                       db_im));
 }
 
+// What the least-squares calls check after abr_batch_check, in this order: their own arrays, the profile, the O weights (O: the
+// forward call's output entries), ndir, and that ndir times the R rf samples, the partials (one per workgroup and sample, per
+// direction; at most 2^56 entries each) and the workgroups of the sweep and of the fold (at most 2^31 - 1 each) fit.  0, or
+// MBFIR_E_ARG with ctx->err set.
+static int gn_check(mbfir_ctx* ctx, const char* who, bool arrays, int profile, int npulse, int nscale, const double* w, int ndir,
+                    const long* roff, const long* npoint) {
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (!arrays) return bad("a required array is null");
+    if (profile < 0 || profile > 3) return bad("profile must be 0, 1, 2 or 3");
+    long O = 0, nblk = 0, nfold = 0;                           // abr_batch_check has bounded O and nblk
+    for (int p = 0; p < npulse; ++p) {
+        O += npoint[p] * nscale;
+        nblk += (npoint[p] + 255) / 256 * nscale;
+        nfold += (roff[p + 1] - roff[p] + 255) / 256;
+    }
+    for (long i = 0; i < O; ++i)
+        if (!(w[i] >= 0) || !std::isfinite(w[i])) return bad("a weight is negative or not finite");
+    if (ndir < 1) return bad("ndir must be at least 1");
+    if (!vjp_partials_fit(npulse, nscale, roff, npoint)) return bad("the output size or the workgroup count overflows");
+    long part = 0;                                             // one direction's partials: vjp_partials_fit has bounded them
+    for (int p = 0; p < npulse; ++p) part += (npoint[p] + 255) / 256 * nscale * (roff[p + 1] - roff[p]);
+    if (roff[npulse] > (1L << 56) / ndir || part > (1L << 56) / ndir || nblk > 2147483647L / ndir || nfold > 2147483647L / ndir)
+        return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_abr_lsq_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                        int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                        const double* w, const double* t_re, const double* t_im, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales;
+    if (const int e = abr_batch_check(ctx, "abr_lsq_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays, npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr_lsq_batch", w && t_re && loss && g_re && g_im, profile, npulse, nscale, w, 1, roff,
+                               npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, abr_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
+                                     mode, profile, w, t_re, profile == 2 ? nullptr : t_im, loss, g_re, g_im));
+}
+
+int mbfir_abr2_lsq_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                         const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                         const double* t_re, const double* t_im, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales;
+    if (const int e = abr_batch_check(ctx, "abr2_lsq_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr2_lsq_batch", w && t_re && loss && g_re && g_im, profile, npulse, nscale, w, 1, roff,
+                               npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, abr2_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
+                                      yoff, y, nscale, scales, mode, profile, w, t_re, profile == 2 ? nullptr : t_im, loss, g_re,
+                                      g_im));
+}
+
+int mbfir_abr_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                       int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                       const double* w, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales;
+    if (const int e = abr_batch_check(ctx, "abr_gn_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays, npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr_gn_batch", w && v_re && v_im && h_re && h_im, profile, npulse, nscale, w, ndir, roff,
+                               npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, abr_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales,
+                                    mode, profile, w, ndir, v_re, v_im, h_re, h_im));
+}
+
+int mbfir_abr2_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                        const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                        const double* y, int nscale, const double* scales, int mode, int profile, const double* w, int ndir,
+                        const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales;
+    if (const int e = abr_batch_check(ctx, "abr2_gn_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr2_gn_batch", w && v_re && v_im && h_re && h_im, profile, npulse, nscale, w, ndir, roff,
+                               npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, abr2_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
+                                     yoff, y, nscale, scales, mode, profile, w, ndir, v_re, v_im, h_re, h_im));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {

@@ -1,4 +1,4 @@
-// Host side of the pulse tools (slr.hip, simgrad.hip, simjvp.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// Host side of the pulse tools (slr.hip, simgrad.hip, simjvp.hip, simgn.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
 // api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
 // (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
 // compiler.
@@ -68,6 +68,25 @@ void abr2_jvp_batch_run(int device, void* stream, int npulse, const long* roff, 
                         const long* yoff, const double* y, int nscale, const double* scales, int mode, int ndir, const double* v_re,
                         const double* v_im, double* a_re, double* a_im, double* b_re, double* b_im, double* da_re, double* da_im,
                         double* db_re, double* db_im);
+// Least-squares products of abr_batch_run / abr2_batch_run (simgn.hip k_abr_lsq_batch, k_abr_gn_batch, their 2D twins, k_abr_gn_fold):
+// the forward call's inputs, the profile (0 ex, 1 se, 2 inv, 3 st), the weights and the targets (t_im may be null) or the ndir
+// directions (as abr_jvp_batch_run takes them) in the forward outputs' layout.  lsq: loss per pulse and the gradient per rf sample;
+// gn: J^H W J v, pulse p from ndir roff[p], direction-major.  One upload, two launches, one download of rf size.
+void abr_lsq_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                       const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                       int profile, const double* w, const double* t_re, const double* t_im, double* loss, double* g_re,
+                       double* g_im);
+void abr2_lsq_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                        const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                        const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                        const double* t_re, const double* t_im, double* loss, double* g_re, double* g_im);
+void abr_gn_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                      const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                      int profile, const double* w, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
+void abr2_gn_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                       const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                       const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                       int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

@@ -1,6 +1,7 @@
-// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip) and their tangents
-// (simjvp.hip) share: the step of the forward model, the helpers of its derivative, the per-pulse descriptors, and the host staging
-// of one call.  Moved here from slr.hip and simgrad.hip token for token.
+// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip), their tangents
+// (simjvp.hip) and their least-squares products (simgn.hip) share: the step of the forward model, the helpers and the steps of its
+// derivatives, the adjoint's reduction constants and fold, the per-pulse descriptors, and the host staging of one call.  Moved
+// here from slr.hip, simgrad.hip and simjvp.hip token for token.
 #pragma once
 #include "dev_common.h"
 #include "pulse.h"
@@ -83,6 +84,142 @@ __device__ __forceinline__ double half_sinc_d(double phi, double cs, double inv)
 __device__ __forceinline__ void half_sinc(double phi, double sn, double cs, double& inv, double& D) {
     inv = phi > 0 ? sn / phi : 0.5;
     D = half_sinc_d(phi, cs, inv);
+}
+
+// One sample backwards (cmul, cjmul, redot and half_sinc: sim_dev.h) for one point: (a, b) = psi_m -> psi_{m-1}, (la, lb) = lambda_m -> lambda_{m-1}; returns the sample's
+// contribution (dL / d Re r, dL / d Im r).  With u, v the state before the sample and X = conj(la) v, Y = conj(lb) u:
+//   mode 0: alpha = cs - i om inv, beta = -i r inv;  d alpha / dp = p kappa, kappa = -inv / 2 - i om D;
+//           d beta / dp = D p (-i r) + inv e_p, e = (-i, 1)   ->   g = r C + inv (Im(X + Y), Re(Y - X))
+//   mode 1: w = z^-1 v, S = i r inv;  d cs / dp = -p inv / 2;  dS / dp = D p (i r) + inv f_p, f = (i, -1)
+//                                                          ->   g = r C + inv (-Im(X + Y), Re(X - Y)), X = conj(la) w
+// where C = Re <lambda, (the part of dQ proportional to p) psi_{m-1}>.  i r inv is smooth at r = 0, where arg r is not.
+__device__ __forceinline__ double2 abr_vjp_step(int mode, double2 r, double om, double2& a, double2& b, double2& la, double2& lb) {
+    double sn, cs, inv, D;
+    if (mode == 0) {
+        const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
+        sincos(0.5 * phi, &sn, &cs);
+        half_sinc(phi, sn, cs, inv, D);
+        const double2 al = make_double2(cs, -om * inv), be = make_double2(r.y * inv, -r.x * inv);
+        const double2 bh = make_double2(r.y, -r.x), ka = make_double2(-0.5 * inv, -om * D);
+        const double2 ta = cjmul(al, a), tb = cjmul(be, b), tc = cmul(al, b), td = cmul(be, a);
+        const double2 u = make_double2(ta.x + tb.x, ta.y + tb.y), v = make_double2(tc.x - td.x, tc.y - td.y);
+        const double2 p1 = cmul(ka, u), p2 = cjmul(bh, v), p3 = cmul(bh, u), p4 = cjmul(ka, v);
+        const double2 t1 = make_double2(p1.x - D * p2.x, p1.y - D * p2.y), t2 = make_double2(D * p3.x + p4.x, D * p3.y + p4.y);
+        const double C = redot(la, t1) + redot(lb, t2);
+        const double2 X = cjmul(la, v), Y = cjmul(lb, u);
+        const double2 g = make_double2(r.x * C + inv * (X.y + Y.y), r.y * C + inv * (Y.x - X.x));
+        const double2 la1 = cjmul(al, la), la2 = cjmul(be, lb), lb1 = cmul(al, lb), lb2 = cmul(be, la);
+        la = make_double2(la1.x + la2.x, la1.y + la2.y);
+        lb = make_double2(lb1.x - lb2.x, lb1.y - lb2.y);
+        a = u; b = v;
+        return g;
+    }
+    const double th = hypot(r.x, r.y);
+    double sz, cz;
+    sincos(0.5 * th, &sn, &cs);
+    sincos(-om, &sz, &cz);                                         // z^-1 = cz + i sz
+    half_sinc(th, sn, cs, inv, D);
+    const double2 S = make_double2(-r.y * inv, r.x * inv), sh = make_double2(-r.y, r.x), zi = make_double2(cz, sz);
+    const double2 ta = cjmul(S, b), tb = cmul(S, a);
+    const double2 u = make_double2(cs * a.x + ta.x, cs * a.y + ta.y), w = make_double2(cs * b.x - tb.x, cs * b.y - tb.y);
+    const double2 p2 = cjmul(sh, w), p3 = cmul(sh, u);
+    const double2 t1 = make_double2(-0.5 * inv * u.x - D * p2.x, -0.5 * inv * u.y - D * p2.y);
+    const double2 t2 = make_double2(D * p3.x - 0.5 * inv * w.x, D * p3.y - 0.5 * inv * w.y);
+    const double C = redot(la, t1) + redot(lb, t2);
+    const double2 X = cjmul(la, w), Y = cjmul(lb, u);
+    const double2 g = make_double2(r.x * C - inv * (X.y + Y.y), r.y * C + inv * (X.x - Y.x));
+    const double2 l1 = cjmul(S, lb), l2 = cmul(S, la);
+    const double2 lw = make_double2(cs * lb.x - l2.x, cs * lb.y - l2.y);
+    la = make_double2(cs * la.x + l1.x, cs * la.y + l1.y);
+    lb = cjmul(zi, lw);                                            // conj(z^-1) = z
+    a = u; b = cjmul(zi, w);
+    return g;
+}
+
+// Reduction tile: VJP_T samples x (Re, Im) rows of 256 contributions.  A row is padded to 272 doubles, so that two consecutive
+// rows start 32 banks apart: the 32 lanes of an 8-byte read group (two rows x 16 lanes, below) then touch 64 distinct banks.
+constexpr int VJP_T = 8;
+constexpr int VJP_ROW = 256 + 16;
+
+// Per-pulse descriptor of the partials: part holds nscale x nch rows of n double2 from p_off, row (scale, chunk) at
+// (scale nch + chunk) n; the gradient of the pulse goes to r_off.
+struct VjpPulseDev {
+    long r_off, p_off;
+    int n, nch;
+};
+
+// sum_s scales[s] (sum_c part(s, c, m)) of sample m of one pulse, chunks then scales in index order: the body of k_abr_vjp_fold
+// (simgrad.hip), shared with the fold of the least-squares products (simgn.hip).
+__device__ __forceinline__ double2 abr_vjp_fold_sum(const double2* __restrict__ part, const VjpPulseDev& V,
+                                                    const double* __restrict__ scales, int nscale, int m) {
+    double2 g = make_double2(0, 0);
+    for (int s = 0; s < nscale; ++s) {
+        double2 t = make_double2(0, 0);
+        const double2* row = part + V.p_off + (long)s * V.nch * V.n + m;
+        for (int c = 0; c < V.nch; ++c) {
+            const double2 v = row[(long)c * V.n];
+            t.x += v.x; t.y += v.y;
+        }
+        const double sc = scales[s];
+        g.x += sc * t.x; g.y += sc * t.y;
+    }
+    return g;
+}
+
+// Directions per workgroup: the largest of 1, 2, 4, 8 without scratch at no less than the forward kernels' occupancy minus one wave
+// per SIMD (DESIGN 8l has the table).
+#ifndef JVP_K
+#define JVP_K 1
+#endif
+
+// One sample for the kcnt <= JVP_K tangents of one point: t = what abr_step_trig kept of the sample, (a, b) = psi_{m-1},
+// dr[k * 256] = s v_m of direction k (the LDS tile), (da[k], db[k]) = dpsi_{m-1} -> dpsi_m.  dQ[dr] is real-linear in dr and splits, as in the adjoint (simgrad.hip), into a part
+// proportional to rd = Re r Re dr + Im r Im dr, whose action on psi_{m-1} (T1, T2) every direction shares, and a part proportional
+// to inv:
+//   mode 0: d alpha = rd kappa, kappa = -inv / 2 - i om D;  d beta = D rd (-i r) + inv (-i dr)
+//           da' = alpha da - conj(beta) db + rd T1 - conj(e) b,  db' = beta da + conj(alpha) db + rd T2 + e a,  e = inv (-i dr)
+//   mode 1: z^-1 = cz + i sz, w = z^-1 b, dw = z^-1 db;  d cs = -rd inv / 2;  dS = D rd (i r) + inv (i dr)
+//           da' = cs da - conj(S) dw + rd T1 - conj(f) w,  db' = S da + cs dw + rd T2 + f a,  f = inv (i dr)
+__device__ __forceinline__ void abr_jvp_step(int mode, double2 r, double om, const AbrTrig& t, double2 a, double2 b,
+                                             const double2* dr, int kcnt, double2 (&da)[JVP_K], double2 (&db)[JVP_K]) {
+    const double cs = t.cs, inv = t.ph > 0 ? t.inv : 0.5, D = half_sinc_d(t.ph, cs, inv);      // half_sinc on the step's own quotient
+    if (mode == 0) {
+        const double2 al = make_double2(cs, -om * inv), be = make_double2(r.y * inv, -r.x * inv);
+        const double2 bh = make_double2(r.y, -r.x), ka = make_double2(-0.5 * inv, -om * D);
+        const double2 p1 = cmul(ka, a), p2 = cjmul(bh, b), p3 = cmul(bh, a), p4 = cjmul(ka, b);
+        const double2 T1 = make_double2(p1.x - D * p2.x, p1.y - D * p2.y), T2 = make_double2(D * p3.x + p4.x, D * p3.y + p4.y);
+#pragma unroll
+        for (int k = 0; k < JVP_K; ++k) {
+            if (k < kcnt) {
+                const double2 d = dr[k * 256];
+                const double rd = r.x * d.x + r.y * d.y;
+                const double2 e = make_double2(inv * d.y, -(inv * d.x));
+                const double2 q1 = cmul(al, da[k]), q2 = cjmul(be, db[k]), q3 = cmul(be, da[k]), q4 = cjmul(al, db[k]);
+                const double2 q5 = cjmul(e, b), q6 = cmul(e, a);
+                da[k] = make_double2(q1.x - q2.x + (rd * T1.x - q5.x), q1.y - q2.y + (rd * T1.y - q5.y));
+                db[k] = make_double2(q3.x + q4.x + (rd * T2.x + q6.x), q3.y + q4.y + (rd * T2.y + q6.y));
+            }
+        }
+        return;
+    }
+    const double2 S = make_double2(-r.y * inv, r.x * inv), sh = make_double2(-r.y, r.x), zi = make_double2(t.cz, t.sz);
+    const double2 w = cmul(zi, b);
+    const double2 p2 = cjmul(sh, w), p3 = cmul(sh, a);
+    const double2 T1 = make_double2(-0.5 * inv * a.x - D * p2.x, -0.5 * inv * a.y - D * p2.y);
+    const double2 T2 = make_double2(D * p3.x - 0.5 * inv * w.x, D * p3.y - 0.5 * inv * w.y);
+#pragma unroll
+    for (int k = 0; k < JVP_K; ++k) {
+        if (k < kcnt) {
+            const double2 d = dr[k * 256];
+            const double rd = r.x * d.x + r.y * d.y;
+            const double2 f = make_double2(-(inv * d.y), inv * d.x);
+            const double2 dw = cmul(zi, db[k]);
+            const double2 q2 = cjmul(S, dw), q3 = cmul(S, da[k]), q5 = cjmul(f, w), q6 = cmul(f, a);
+            const double2 dak = make_double2(cs * da[k].x - q2.x + (rd * T1.x - q5.x), cs * da[k].y - q2.y + (rd * T1.y - q5.y));
+            db[k] = make_double2(q3.x + cs * dw.x + (rd * T2.x + q6.x), q3.y + cs * dw.y + (rd * T2.y + q6.y));
+            da[k] = dak;
+        }
+    }
 }
 
 // Per-pulse descriptors of the 1D and the 2D simulators (and of their adjoints, whose cotangents lie where the outputs do).

@@ -10,75 +10,14 @@
 // block table, one thread per point.  The 256 contributions to a sample are summed in a fixed order (VJP_T samples at a time
 // through an LDS tile) into one partial per (workgroup, sample); k_abr_vjp_fold sums a pulse's partials over chunks, then over
 // scales (times s: the chain rule of r = s rf), in index order.  No atomics: a pulse's gradient bits depend only on the pulse, its
-// grid and the scale list.
+// grid and the scale list.  The step of the reverse sweep (abr_vjp_step), the tile's constants, the partials' descriptor and the
+// fold's sum live in sim_dev.h, which simgn.hip shares.
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
 #include <cmath>
 
 namespace mbfir {
-
-// One sample backwards (cmul, cjmul, redot and half_sinc: sim_dev.h) for one point: (a, b) = psi_m -> psi_{m-1}, (la, lb) = lambda_m -> lambda_{m-1}; returns the sample's
-// contribution (dL / d Re r, dL / d Im r).  With u, v the state before the sample and X = conj(la) v, Y = conj(lb) u:
-//   mode 0: alpha = cs - i om inv, beta = -i r inv;  d alpha / dp = p kappa, kappa = -inv / 2 - i om D;
-//           d beta / dp = D p (-i r) + inv e_p, e = (-i, 1)   ->   g = r C + inv (Im(X + Y), Re(Y - X))
-//   mode 1: w = z^-1 v, S = i r inv;  d cs / dp = -p inv / 2;  dS / dp = D p (i r) + inv f_p, f = (i, -1)
-//                                                          ->   g = r C + inv (-Im(X + Y), Re(X - Y)), X = conj(la) w
-// where C = Re <lambda, (the part of dQ proportional to p) psi_{m-1}>.  i r inv is smooth at r = 0, where arg r is not.
-__device__ __forceinline__ double2 abr_vjp_step(int mode, double2 r, double om, double2& a, double2& b, double2& la, double2& lb) {
-    double sn, cs, inv, D;
-    if (mode == 0) {
-        const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
-        sincos(0.5 * phi, &sn, &cs);
-        half_sinc(phi, sn, cs, inv, D);
-        const double2 al = make_double2(cs, -om * inv), be = make_double2(r.y * inv, -r.x * inv);
-        const double2 bh = make_double2(r.y, -r.x), ka = make_double2(-0.5 * inv, -om * D);
-        const double2 ta = cjmul(al, a), tb = cjmul(be, b), tc = cmul(al, b), td = cmul(be, a);
-        const double2 u = make_double2(ta.x + tb.x, ta.y + tb.y), v = make_double2(tc.x - td.x, tc.y - td.y);
-        const double2 p1 = cmul(ka, u), p2 = cjmul(bh, v), p3 = cmul(bh, u), p4 = cjmul(ka, v);
-        const double2 t1 = make_double2(p1.x - D * p2.x, p1.y - D * p2.y), t2 = make_double2(D * p3.x + p4.x, D * p3.y + p4.y);
-        const double C = redot(la, t1) + redot(lb, t2);
-        const double2 X = cjmul(la, v), Y = cjmul(lb, u);
-        const double2 g = make_double2(r.x * C + inv * (X.y + Y.y), r.y * C + inv * (Y.x - X.x));
-        const double2 la1 = cjmul(al, la), la2 = cjmul(be, lb), lb1 = cmul(al, lb), lb2 = cmul(be, la);
-        la = make_double2(la1.x + la2.x, la1.y + la2.y);
-        lb = make_double2(lb1.x - lb2.x, lb1.y - lb2.y);
-        a = u; b = v;
-        return g;
-    }
-    const double th = hypot(r.x, r.y);
-    double sz, cz;
-    sincos(0.5 * th, &sn, &cs);
-    sincos(-om, &sz, &cz);                                         // z^-1 = cz + i sz
-    half_sinc(th, sn, cs, inv, D);
-    const double2 S = make_double2(-r.y * inv, r.x * inv), sh = make_double2(-r.y, r.x), zi = make_double2(cz, sz);
-    const double2 ta = cjmul(S, b), tb = cmul(S, a);
-    const double2 u = make_double2(cs * a.x + ta.x, cs * a.y + ta.y), w = make_double2(cs * b.x - tb.x, cs * b.y - tb.y);
-    const double2 p2 = cjmul(sh, w), p3 = cmul(sh, u);
-    const double2 t1 = make_double2(-0.5 * inv * u.x - D * p2.x, -0.5 * inv * u.y - D * p2.y);
-    const double2 t2 = make_double2(D * p3.x - 0.5 * inv * w.x, D * p3.y - 0.5 * inv * w.y);
-    const double C = redot(la, t1) + redot(lb, t2);
-    const double2 X = cjmul(la, w), Y = cjmul(lb, u);
-    const double2 g = make_double2(r.x * C - inv * (X.y + Y.y), r.y * C + inv * (X.x - Y.x));
-    const double2 l1 = cjmul(S, lb), l2 = cmul(S, la);
-    const double2 lw = make_double2(cs * lb.x - l2.x, cs * lb.y - l2.y);
-    la = make_double2(cs * la.x + l1.x, cs * la.y + l1.y);
-    lb = cjmul(zi, lw);                                            // conj(z^-1) = z
-    a = u; b = cjmul(zi, w);
-    return g;
-}
-
-// Reduction tile: VJP_T samples x (Re, Im) rows of 256 contributions.  A row is padded to 272 doubles, so that two consecutive
-// rows start 32 banks apart: the 32 lanes of an 8-byte read group (two rows x 16 lanes, below) then touch 64 distinct banks.
-constexpr int VJP_T = 8;
-constexpr int VJP_ROW = 256 + 16;
-
-// Per-pulse descriptor of the partials: part holds nscale x nch rows of n double2 from p_off, row (scale, chunk) at
-// (scale nch + chunk) n; the gradient of the pulse goes to r_off.
-struct VjpPulseDev {
-    long r_off, p_off;
-    int n, nch;
-};
 
 // The sweeps of one workgroup (TWO_D: om = fma(x, gx, y gy) as k_abr2_batch forms it, else om = x g as k_abr_batch).  xv, yv:
 // the thread's point; live false: a thread past the end of the grid, which sweeps a point at the origin with zero cotangents and
@@ -179,18 +118,7 @@ __global__ __launch_bounds__(256) void k_abr_vjp_fold(const double2* __restrict_
     const VjpPulseDev V = vp[bk.pulse];
     const int m = bk.chunk * 256 + threadIdx.x;
     if (m >= V.n) return;
-    double2 g = make_double2(0, 0);
-    for (int s = 0; s < nscale; ++s) {
-        double2 t = make_double2(0, 0);
-        const double2* row = part + V.p_off + (long)s * V.nch * V.n + m;
-        for (int c = 0; c < V.nch; ++c) {
-            const double2 v = row[(long)c * V.n];
-            t.x += v.x; t.y += v.y;
-        }
-        const double sc = scales[s];
-        g.x += sc * t.x; g.y += sc * t.y;
-    }
-    grad[V.r_off + m] = g;
+    grad[V.r_off + m] = abr_vjp_fold_sum(part, V, scales, nscale, m);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -7,69 +7,13 @@
 // point.  The JVP_K tangents of a thread share the sample's sincos, inv, D and the primal state, which advances through abr_step's
 // body (abr_step_trig, which also hands out the sample's trigonometry) by value as in the forward kernels: the (a, b) written here (by the workgroups of group 0) have k_abr_batch / k_abr2_batch's bits.  Every
 // direction runs the same instructions on its own registers, so a tangent's bits depend only on its pulse, scale, point and
-// direction.
+// direction.  JVP_K and the step of the sweep (abr_jvp_step) live in sim_dev.h, which simgn.hip shares.
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
 #include <cmath>
 
 namespace mbfir {
-
-// Directions per workgroup: the largest of 1, 2, 4, 8 without scratch at no less than the forward kernels' occupancy minus one wave
-// per SIMD (DESIGN 8l has the table).
-#ifndef JVP_K
-#define JVP_K 1
-#endif
-
-// One sample for the kcnt <= JVP_K tangents of one point: t = what abr_step_trig kept of the sample, (a, b) = psi_{m-1},
-// dr[k * 256] = s v_m of direction k (the LDS tile), (da[k], db[k]) = dpsi_{m-1} -> dpsi_m.  dQ[dr] is real-linear in dr and splits, as in the adjoint (simgrad.hip), into a part
-// proportional to rd = Re r Re dr + Im r Im dr, whose action on psi_{m-1} (T1, T2) every direction shares, and a part proportional
-// to inv:
-//   mode 0: d alpha = rd kappa, kappa = -inv / 2 - i om D;  d beta = D rd (-i r) + inv (-i dr)
-//           da' = alpha da - conj(beta) db + rd T1 - conj(e) b,  db' = beta da + conj(alpha) db + rd T2 + e a,  e = inv (-i dr)
-//   mode 1: z^-1 = cz + i sz, w = z^-1 b, dw = z^-1 db;  d cs = -rd inv / 2;  dS = D rd (i r) + inv (i dr)
-//           da' = cs da - conj(S) dw + rd T1 - conj(f) w,  db' = S da + cs dw + rd T2 + f a,  f = inv (i dr)
-__device__ __forceinline__ void abr_jvp_step(int mode, double2 r, double om, const AbrTrig& t, double2 a, double2 b,
-                                             const double2* dr, int kcnt, double2 (&da)[JVP_K], double2 (&db)[JVP_K]) {
-    const double cs = t.cs, inv = t.ph > 0 ? t.inv : 0.5, D = half_sinc_d(t.ph, cs, inv);      // half_sinc on the step's own quotient
-    if (mode == 0) {
-        const double2 al = make_double2(cs, -om * inv), be = make_double2(r.y * inv, -r.x * inv);
-        const double2 bh = make_double2(r.y, -r.x), ka = make_double2(-0.5 * inv, -om * D);
-        const double2 p1 = cmul(ka, a), p2 = cjmul(bh, b), p3 = cmul(bh, a), p4 = cjmul(ka, b);
-        const double2 T1 = make_double2(p1.x - D * p2.x, p1.y - D * p2.y), T2 = make_double2(D * p3.x + p4.x, D * p3.y + p4.y);
-#pragma unroll
-        for (int k = 0; k < JVP_K; ++k) {
-            if (k < kcnt) {
-                const double2 d = dr[k * 256];
-                const double rd = r.x * d.x + r.y * d.y;
-                const double2 e = make_double2(inv * d.y, -(inv * d.x));
-                const double2 q1 = cmul(al, da[k]), q2 = cjmul(be, db[k]), q3 = cmul(be, da[k]), q4 = cjmul(al, db[k]);
-                const double2 q5 = cjmul(e, b), q6 = cmul(e, a);
-                da[k] = make_double2(q1.x - q2.x + (rd * T1.x - q5.x), q1.y - q2.y + (rd * T1.y - q5.y));
-                db[k] = make_double2(q3.x + q4.x + (rd * T2.x + q6.x), q3.y + q4.y + (rd * T2.y + q6.y));
-            }
-        }
-        return;
-    }
-    const double2 S = make_double2(-r.y * inv, r.x * inv), sh = make_double2(-r.y, r.x), zi = make_double2(t.cz, t.sz);
-    const double2 w = cmul(zi, b);
-    const double2 p2 = cjmul(sh, w), p3 = cmul(sh, a);
-    const double2 T1 = make_double2(-0.5 * inv * a.x - D * p2.x, -0.5 * inv * a.y - D * p2.y);
-    const double2 T2 = make_double2(D * p3.x - 0.5 * inv * w.x, D * p3.y - 0.5 * inv * w.y);
-#pragma unroll
-    for (int k = 0; k < JVP_K; ++k) {
-        if (k < kcnt) {
-            const double2 d = dr[k * 256];
-            const double rd = r.x * d.x + r.y * d.y;
-            const double2 f = make_double2(-(inv * d.y), inv * d.x);
-            const double2 dw = cmul(zi, db[k]);
-            const double2 q2 = cjmul(S, dw), q3 = cmul(S, da[k]), q5 = cjmul(f, w), q6 = cmul(f, a);
-            const double2 dak = make_double2(cs * da[k].x - q2.x + (rd * T1.x - q5.x), cs * da[k].y - q2.y + (rd * T1.y - q5.y));
-            db[k] = make_double2(q3.x + cs * dw.x + (rd * T2.x + q6.x), q3.y + cs * dw.y + (rd * T2.y + q6.y));
-            da[k] = dak;
-        }
-    }
-}
 
 // The sweep of one workgroup (TWO_D: om = fma(x, gx, y gy) as k_abr2_batch forms it, else om = x g as k_abr_batch), staged as the
 // forward kernels stage theirs: rf times the scale, the weights, and s v of the group's kcnt directions (vg: the first of them, n

@@ -1,0 +1,133 @@
+"""Batched Levenberg-Marquardt refinement of RF pulses against a target profile: the loop of
+examples/spiral2d_gauss_newton.py, run in lock step over many pulses on the fused device products.  Per pulse, with
+L = 1/2 sum w |f - t|^2, g = J^H W (f - t) and H = J^H W J (abr_lsq_batch / abr_gn_batch and their 2D twins):
+    each step solves (H + mu I) d = -g by conjugate gradients from d = 0 on the real form of rf, one gn call per CG iteration over
+    the pulses whose CG is still running (one direction each), and tries rf + d with one lsq call, which also returns the gradient
+    of the next step;  mu <- mu / 3 after a step that lowers L, mu <- 4 mu after one that does not (the step is then solved again);
+    the first mu is 1e-3 times the Rayleigh quotient <g, H g> / <g, g>.
+Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
+batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
+import importlib
+
+import numpy as np
+
+MU_MAX = 1e12          # a pulse whose mu grows past this gives up
+
+
+def _dot(u, v):
+    """the inner product of the real forms"""
+    return float((np.conj(u) * v).real.sum())
+
+
+def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False, iters=5, cg=8, mu0=None, rtol=1e-6, ctx=None):
+    """refine_batch(pulses, x, targets, weights, ...) for abr_batch's model, refine_batch(pulses, x, y, targets, weights, ...) for
+    abr2_batch's.  pulses: rf or (rf, g) each; x (and y): one grid shared by every pulse or a list of one per pulse; targets,
+    weights, profile, scales and hard_pulse as for abr_lsq_batch / abr2_lsq_batch.  iters: accepted steps per pulse at the most;
+    cg: CG iterations per step at the most, stopped once |residual|^2 <= rtol |g|^2; mu0: None (the Rayleigh quotient), a number,
+    or one number per pulse.  Returns (rfs, infos): the refined rf per pulse and a dict per pulse with 'losses' (L at the start and
+    after every accepted step), 'mu' (the last one), 'status' ('iters', 'converged': a zero gradient, or 'gave_up': mu past 1e12),
+    'refused' (steps that did not lower L) and 'calls' (the lsq and gn calls the pulse took part in)."""
+    mb = importlib.import_module(__package__)
+    if len(args) == 2:
+        two, y = False, None
+        targets, weights = args
+    elif len(args) == 3:
+        two = True
+        y, targets, weights = args
+    else:
+        raise ValueError("refine_batch: takes (pulses, x, targets, weights) or (pulses, x, y, targets, weights)")
+    pulses = list(pulses)
+    P = len(pulses)
+    if P == 0:
+        raise ValueError("refine_batch: no pulses")
+    targets, weights = list(targets), list(weights)
+    if len(targets) != P or len(weights) != P:
+        raise ValueError("refine_batch: %d targets and %d weight arrays for %d pulses" % (len(targets), len(weights), P))
+    if iters < 0 or cg < 1:
+        raise ValueError("refine_batch: iters must be at least 0 and cg at least 1")
+    gs = [p[1] if isinstance(p, tuple) else None for p in pulses]
+    rfs = [np.array(p[0] if isinstance(p, tuple) else p, dtype=np.complex128).ravel() for p in pulses]
+    kw = dict(profile=profile, scales=scales, hard_pulse=hard_pulse, ctx=ctx)
+
+    def grid(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P and all(np.ndim(e) >= 1 for e in v) else v
+
+    def pack(idx, rf_of):
+        return [rf_of[q] if gs[q] is None else (rf_of[q], gs[q]) for q in idx]
+
+    def lsq(idx, rf_of):
+        pos = (grid(x, idx), grid(y, idx)) if two else (grid(x, idx),)
+        fn = mb.abr2_lsq_batch if two else mb.abr_lsq_batch
+        for q in idx:
+            infos[q]["calls"]["lsq"] += 1
+        return fn(pack(idx, rf_of), *pos, [targets[q] for q in idx], [weights[q] for q in idx], **kw)
+
+    def gn(idx, v_of):
+        pos = (grid(x, idx), grid(y, idx)) if two else (grid(x, idx),)
+        fn = mb.abr2_gn_batch if two else mb.abr_gn_batch
+        for q in idx:
+            infos[q]["calls"]["gn"] += 1
+        return fn(pack(idx, rfs), *pos, [v_of[q] for q in idx], [weights[q] for q in idx], **kw)
+
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    every = list(range(P))
+    loss, grad, done = [0.0] * P, [None] * P, [0] * P
+    for q, (L, g) in zip(every, lsq(every, rfs)):
+        loss[q], grad[q] = L, g
+        infos[q]["losses"].append(L)
+    active = []
+    for q in every:
+        if iters == 0:
+            continue
+        if _dot(grad[q], grad[q]) == 0.0:
+            infos[q]["status"] = "converged"
+            continue
+        active.append(q)
+    mu = [None] * P
+    if mu0 is not None:
+        m = np.broadcast_to(np.asarray(mu0, dtype=np.float64), (P,))
+        mu = [float(v) for v in m]
+    need = [q for q in active if mu[q] is None]
+    if need:
+        for q, hg in zip(need, gn(need, grad)):
+            mu[q] = 1e-3 * _dot(grad[q], hg) / _dot(grad[q], grad[q])       # a Rayleigh quotient of H sets the scale of mu
+    while active:
+        d = {q: np.zeros_like(rfs[q]) for q in active}                      # CG on (H + mu I) d = -g from d = 0
+        r = {q: -grad[q] for q in active}
+        p = {q: r[q].copy() for q in active}
+        rr = {q: _dot(r[q], r[q]) for q in active}
+        gg = dict(rr)
+        ncg = {q: 0 for q in active}
+        while True:
+            run = [q for q in active if ncg[q] < cg and rr[q] > rtol * gg[q]]
+            if not run:
+                break
+            for q, hp in zip(run, gn(run, p)):
+                ap = hp + mu[q] * p[q]
+                alpha = rr[q] / _dot(p[q], ap)
+                d[q], r[q] = d[q] + alpha * p[q], r[q] - alpha * ap
+                rr[q], old = _dot(r[q], r[q]), rr[q]
+                p[q] = r[q] + (rr[q] / old) * p[q]
+                ncg[q] += 1
+        trial = {q: rfs[q] + d[q] for q in active}
+        still = []
+        for q, (L, g) in zip(active, lsq(active, trial)):
+            if L < loss[q]:
+                rfs[q], loss[q], grad[q], mu[q] = trial[q], L, g, mu[q] / 3
+                infos[q]["losses"].append(L)
+                done[q] += 1
+                if _dot(g, g) == 0.0:
+                    infos[q]["status"] = "converged"
+                elif done[q] < iters:
+                    still.append(q)
+            else:
+                mu[q] *= 4
+                infos[q]["refused"] += 1
+                if mu[q] > MU_MAX:
+                    infos[q]["status"] = "gave_up"
+                else:
+                    still.append(q)
+        active = still
+    for q in every:
+        infos[q]["mu"] = mu[q]
+    return rfs, infos
