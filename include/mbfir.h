@@ -389,6 +389,30 @@ int mbfir_abr2_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const doub
                         const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
                         const double* y, int nscale, const double* scales, int mode, int profile, const double* w, int ndir,
                         const double* v_re, const double* v_im, double* h_re, double* h_im);
+/* mbfir_abr_lm_step_batch / mbfir_abr2_lm_step_batch: one damped Gauss-Newton (Levenberg-Marquardt) step per pulse, solved on the
+ * device: conjugate gradients on (H + mu[p] I) d = b from d = 0 in the real inner product <u, v> = sum Re(conj(u) v), H = J^H W J
+ * as in mbfir_abr_gn_batch, at most cg iterations, while <r, r> > rtol <b, b>.  The arguments up to w are those of mbfir_abr_gn_batch
+ * / mbfir_abr2_gn_batch; b_re, b_im are laid out as rf is.  With t_re (and t_im; NULL for a real target) the loss and gradient of
+ * mbfir_abr_lsq_batch at rf + d are returned too; t_re and t_im both NULL: solve only, and loss, g_re, g_im may be NULL.
+ * Outputs per pulse: d, ncg (iterations done), rr (the last <r, r>), gg (<b, b>), status (0: the tolerance was reached, 1: the cap
+ * cg was reached, 2: breakdown, <p, (H + mu) p> not finite or not > 0; d, rr and ncg are then those before that iteration).
+ * One upload, a chain of launches (two per CG iteration), one download; the host reads nothing in between, so cg is also a launch
+ * count: all 2 cg launches are queued whatever rtol stops, the workgroups of a pulse that has stopped returning at once.  A pulse's outputs
+ * depend only on the pulse, its grid, weights, target, b, mu, cg, rtol and the scale list: not on the batch, its order, or when its
+ * neighbours stop.  The checks are those of mbfir_abr_gn_batch at ndir = 1 in their order, then: b, mu or a required output NULL
+ * ("a required array is null"); a negative or non-finite mu; cg < 0; a negative or NaN rtol; sections that overflow.  No device
+ * work is done before they pass. */
+int mbfir_abr_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                            int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                            const double* w, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                            const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                            int* status, double* loss, double* g_re, double* g_im);
+int mbfir_abr2_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                             const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                             const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                             const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* t_re,
+                             const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status,
+                             double* loss, double* g_re, double* g_im);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

@@ -144,6 +144,12 @@ SYMBOLS = {
                                      C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
                                       _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, C.c_int,
+                                          _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _ip, _dp, _dp,
+                                          _dp]),
+    "mbfir_abr2_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
+                                           _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, C.c_double, _dp, _dp, _dp, _dp, _ip,
+                                           _dp, _dp, _ip, _dp, _dp, _dp]),
     "mbfir_test_jvp_group": (C.c_int, []),
     "mbfir_test_sim_blocks": (C.c_long, [C.c_int, _ip, _lp, C.c_int, _ip]),
     "mbfir_assemble": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int,
@@ -1145,13 +1151,21 @@ def _abr_args(who, pulses, x, scales, convention):
     return sc, rfs, gs, xs, nx
 
 
+def _plane(o):
+    """An argument after `mode` of the batched abr calls: a float64 or int32 array as its pointer; an int, a float or None as it is.
+    Shared on purpose by every _abr_call / _abr2_call user: the calls before the lm step pass only arrays and ints, as before."""
+    if isinstance(o, np.ndarray):
+        return o.ctypes.data_as(_ip) if o.dtype == np.int32 else _ptr(o)
+    return o
+
+
 def _abr_call(fn, ctx, sc, rfs, gs, xs, hard_pulse, planes):
     """mbfir_abr_batch, mbfir_abr_vjp_batch or mbfir_abr_jvp_batch on the checked arguments; planes: what follows `mode` (arrays,
     and the tangent call's ndir)."""
     rf = np.concatenate(rfs)
     rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)),
             _ptr(_vec(np.concatenate(gs))), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(sc),
-            _ptr(sc), 1 if hard_pulse else 0, *[o if isinstance(o, int) else _ptr(o) for o in planes])
+            _ptr(sc), 1 if hard_pulse else 0, *[_plane(o) for o in planes])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -1304,7 +1318,7 @@ def _abr2_call(fn, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes):
     rc = fn(ctx._h, len(rfs), _lptr(_offsets([len(r) for r in rfs])), _ptr(_vec(rf.real)), _ptr(_vec(rf.imag)), _ptr(_vec(g.real)),
             _ptr(_vec(g.imag)), len(xs), _lptr(_offsets([len(v) for v in xs])), _ptr(_vec(np.concatenate(xs))), len(ys),
             _lptr(_offsets([len(v) for v in ys])), _ptr(_vec(np.concatenate(ys))), len(sc), _ptr(sc), 1 if hard_pulse else 0,
-            *[o if isinstance(o, int) else _ptr(o) for o in planes])
+            *[_plane(o) for o in planes])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -1476,7 +1490,96 @@ def abr2_gn_batch(pulses, x, y, tangents, weights, *, profile="ex", scales=(1.0,
     return _gn_result(rfs, K, keep, h)
 
 
-from .refine import refine_batch   # noqa: E402  (batched Levenberg-Marquardt on the four calls above)
+# ---- the Levenberg-Marquardt step solved on the device (mbfir_abr[2]_lm_step_batch) --------------------------------------------------
+LM_STATUS = ("rtol", "cg", "breakdown")
+
+
+def _lm_args(who, rfs, rhs, mu, cg, rtol):
+    """The checked right-hand sides, dampings, cap and tolerance -> (the two planes of rhs, mu per pulse, cg, rtol)."""
+    rhs = list(rhs)
+    if len(rhs) != len(rfs):
+        raise ValueError("%s: %d right-hand sides for %d pulses" % (who, len(rhs), len(rfs)))
+    bs = []
+    for q, (b, rf) in enumerate(zip(rhs, rfs)):
+        b = np.asarray(b, dtype=np.complex128)
+        if b.shape != (len(rf),):
+            raise ValueError("%s: the right-hand side of pulse %d has shape %s, not (%d,)" % (who, q, b.shape, len(rf)))
+        bs.append(b)
+    try:
+        m = _vec(np.broadcast_to(np.asarray(mu, dtype=np.float64), (len(rfs),)))
+    except ValueError:
+        raise ValueError("%s: mu must be a number or one number per pulse" % who) from None
+    if not np.all(np.isfinite(m)) or np.any(m < 0):
+        raise ValueError("%s: a damping mu is negative or not finite" % who)
+    if int(cg) != cg or cg < 0:
+        raise ValueError("%s: cg must be an integer, at least 0" % who)
+    if not rtol >= 0:
+        raise ValueError("%s: rtol is negative or not a number" % who)
+    b = np.concatenate(bs)
+    return [_vec(b.real), _vec(b.imag)], m, int(cg), float(rtol)
+
+
+def _lm_planes(who, kind, w, bplanes, m, cg, rtol, targets, shapes, rfs):
+    """What follows `mode` in the C call, and the output arrays: d (2), ncg, rr, gg, status, and with targets loss, grad (2)."""
+    P, R = len(rfs), sum(len(r) for r in rfs)
+    tplanes = [None, None] if targets is None else _target_planes(who, targets, shapes, kind)
+    out = [np.zeros(R), np.zeros(R), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
+    out += [None, None, None] if targets is None else [np.zeros(P), np.zeros(R), np.zeros(R)]
+    return [kind, w] + bplanes + [m, cg, C.c_double(rtol)] + tplanes + out, out
+
+
+def _lm_result(rfs, out):
+    roff = _offsets([len(r) for r in rfs])
+    d_all = out[0] + 1j * out[1]
+    res = []
+    for q in range(len(rfs)):
+        lo, hi = int(roff[q]), int(roff[q + 1])
+        info = dict(ncg=int(out[2][q]), rr=float(out[3][q]), gg=float(out[4][q]), status=LM_STATUS[int(out[5][q])])
+        if out[6] is not None:
+            info["loss"] = float(out[6][q])
+            info["grad"] = out[7][lo:hi] + 1j * out[8][lo:hi]
+        res.append((d_all[lo:hi], info))
+    return res
+
+
+def abr_lm_step_batch(pulses, x, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, profile="ex", scales=(1.0,), hard_pulse=False,
+                      ctx=None):
+    """One damped Gauss-Newton (Levenberg-Marquardt) step per pulse, solved on the device in one call (mbfir_abr_lm_step_batch):
+    conjugate gradients on (H + mu I) d = rhs from d = 0, H = J^H W J as abr_gn_batch applies it, in the inner product
+    <u, v> = sum Re(conj(u) v); at most cg iterations, while <r, r> > rtol <rhs, rhs>.  pulses, x, weights, profile, scales and
+    hard_pulse as for abr_gn_batch; rhs: per pulse a complex (n,) array; mu: a number >= 0 or one per pulse.  With targets (as for
+    abr_lsq_batch) the loss and gradient at rf + d come back too.  Returns a list of (d, info) per pulse: info holds 'ncg' (iterations
+    done), 'rr' (the last <r, r>), 'gg' (<rhs, rhs>) and 'status': 'rtol' (tolerance reached), 'cg' (the cap reached) or 'breakdown'
+    (<p, (H + mu) p> not finite or not > 0: d is the one before that iteration); with targets also 'loss' and 'grad', with the
+    bits of abr_lsq_batch at rf + d.  The host reads nothing between the iterations, so cg is also a launch count: all 2 cg
+    launches are queued, those of pulses that have stopped returning at once; keep cg at the iterations a step is worth.  Deterministic: a pulse's results depend only
+    on the pulse, its grid, weights, target, rhs, mu, cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    who = "abr_lm_step_batch"
+    sc, rfs, gs, xs, nx = _abr_args(who, pulses, x, scales, "abrm")
+    kind = _profile(who, profile)
+    shapes = [(len(sc), k) for k in nx]
+    bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
+    planes, out = _lm_planes(who, kind, _weight_plane(who, weights, shapes), bplanes, m, cg, rtol, targets, shapes, rfs)
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_lm_step_batch, ctx, sc, rfs, gs, xs, hard_pulse, planes)
+    return _lm_result(rfs, out)
+
+
+def abr2_lm_step_batch(pulses, x, y, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, profile="ex", scales=(1.0,),
+                       hard_pulse=False, ctx=None):
+    """abr_lm_step_batch for abr2_batch (mbfir_abr2_lm_step_batch): weights and targets as for abr2_gn_batch / abr2_lsq_batch."""
+    who = "abr2_lm_step_batch"
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args(who, pulses, x, y, scales, "abrm")
+    kind = _profile(who, profile)
+    shapes = [(len(sc), k, j) for k, j in zip(nx, ny)]
+    bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
+    planes, out = _lm_planes(who, kind, _weight_plane(who, weights, shapes), bplanes, m, cg, rtol, targets, shapes, rfs)
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_lm_step_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes)
+    return _lm_result(rfs, out)
+
+
+from .refine import refine_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

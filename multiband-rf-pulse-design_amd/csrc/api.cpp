@@ -1128,6 +1128,63 @@ int mbfir_abr2_gn_batch(mbfir_ctx* ctx, int npulse, const long* roff, const doub
                                      yoff, y, nscale, scales, mode, profile, w, ndir, v_re, v_im, h_re, h_im));
 }
 
+// What the Levenberg-Marquardt step checks after abr_batch_check and gn_check (at ndir = 1), in this order: its own arrays, mu, cg,
+// rtol, and that its per-sample sections (eight times the R rf samples, at most 2^56 entries) and the workgroups of the trial (at
+// most 2^31 - 1) fit.  0, or MBFIR_E_ARG with ctx->err set.
+static int lm_check(mbfir_ctx* ctx, const char* who, bool arrays, int npulse, const long* roff, const double* mu, int cg,
+                    double rtol) {
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (!arrays) return bad("a required array is null");
+    for (int p = 0; p < npulse; ++p)
+        if (!(mu[p] >= 0) || !std::isfinite(mu[p])) return bad("a damping mu is negative or not finite");
+    if (cg < 0) return bad("cg must be at least 0");
+    if (!(rtol >= 0)) return bad("rtol is negative or not a number");
+    if (roff[npulse] > (1L << 56) / 8 || (roff[npulse] + 255) / 256 > 2147483647L)
+        return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_abr_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                            int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode, int profile,
+                            const double* w, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                            const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                            int* status, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales;
+    if (const int e = abr_batch_check(ctx, "abr_lm_step_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr_lm_step_batch", w != nullptr, profile, npulse, nscale, w, 1, roff, npoint.data())) return e;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status &&
+                     (t_re ? loss && g_re && g_im : t_im == nullptr);
+    if (const int e = lm_check(ctx, "abr_lm_step_batch", own, npulse, roff, mu, cg, rtol)) return e;
+    MBFIR_TRY(ctx, abr_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale,
+                                         scales, mode, profile, w, b_re, b_im, mu, cg, rtol, t_re, profile == 2 ? nullptr : t_im,
+                                         d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im));
+}
+
+int mbfir_abr2_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
+                             const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
+                             const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
+                             const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* t_re,
+                             const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status,
+                             double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales;
+    if (const int e = abr_batch_check(ctx, "abr2_lm_step_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (const int e = gn_check(ctx, "abr2_lm_step_batch", w != nullptr, profile, npulse, nscale, w, 1, roff, npoint.data())) return e;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status &&
+                     (t_re ? loss && g_re && g_im : t_im == nullptr);
+    if (const int e = lm_check(ctx, "abr2_lm_step_batch", own, npulse, roff, mu, cg, rtol)) return e;
+    MBFIR_TRY(ctx, abr2_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x,
+                                          nygrid, yoff, y, nscale, scales, mode, profile, w, b_re, b_im, mu, cg, rtol, t_re,
+                                          profile == 2 ? nullptr : t_im, d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {

@@ -87,6 +87,19 @@ void abr2_gn_batch_run(int device, void* stream, int npulse, const long* roff, c
                        const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
                        const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
                        int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
+// The Levenberg-Marquardt step on the device (simgn.hip): CG on (H + mu I) d = b per pulse and, with t_re, the loss and gradient at
+// rf + d (loss, g_re, g_im may be null without one).
+void abr_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                           const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                           int profile, const double* w, const double* b_re, const double* b_im, const double* mu, int cg,
+                           double rtol, const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr,
+                           double* gg, int* status, double* loss, double* g_re, double* g_im);
+void abr2_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                            const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                            const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile,
+                            const double* w, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                            const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                            int* status, double* loss, double* g_re, double* g_im);
 // Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,

@@ -241,6 +241,152 @@ __global__ __launch_bounds__(256) void k_abr_gn_fold(const double2* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------
+// The Levenberg-Marquardt step on the device: conjugate gradients on (H + mu I) d = b per pulse, H p by the sweep of
+// k_abr_gn_batch on the device's own p, everything else of an iteration in k_lm_step; then, with a target, the loss and gradient at
+// rf + d by k_abr_lsq_batch.  Stages depend on each other through launch order alone.  A pulse whose CG has stopped has run = 0:
+// its workgroups of every later launch return at once, so its bits do not depend on how long its neighbours go on.
+struct LmState {
+    double rr, gg, mu;
+    int ncg, run, status, pad;         // status: 0 tolerance reached, 1 the cap cg reached, 2 breakdown
+};
+
+// The sum of one double per thread of the 256 by a fixed tree in LDS (sw: 256 doubles); every thread gets it.  No shuffles: a
+// second width of __shfl_down in this file changes how the compiler lowers the width-16 ones of abr_gn_sweeps in the shipped kernels.
+__device__ __forceinline__ double lm_block_sum(double s, double* sw) {
+    __syncthreads();                                              // sw is free again
+    sw[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) sw[threadIdx.x] += sw[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sw[0];
+}
+// <u, v> of the real forms, one sample, and v + al u: every product and sum rounded on its own (contraction off in these two
+// bodies; the round-to-nearest intrinsics of this platform are plain * and +, which the default contraction mode fuses), so that
+// the updates have the bits of the host loop's NumPy expressions on the same inputs.
+__device__ __forceinline__ double lm_redot(double2 u, double2 v) {
+#pragma clang fp contract(off)
+    return u.x * v.x + u.y * v.y;
+}
+__device__ __forceinline__ double2 lm_axpy(double al, double2 u, double2 v) {
+#pragma clang fp contract(off)
+    return make_double2(v.x + al * u.x, v.y + al * u.y);
+}
+__device__ __forceinline__ bool lm_goes_on(int ncg, int cg, double rr, double rtol, double gg) {
+    return ncg < cg && rr > rtol * gg;
+}
+
+// One workgroup per pulse: p holds b.  d = 0, r = b, rr = gg = <b, b>.  A thread owns the samples tid, tid + 256, ... in every
+// pass of this kernel and of k_lm_step, so the dots are summed in an order that n alone fixes and no pass reads another thread's.
+__global__ __launch_bounds__(256) void k_lm_init(const VjpPulseDev* __restrict__ vp, const double* __restrict__ mu, int cg,
+                                                 double rtol, const double2* __restrict__ p, double2* __restrict__ d,
+                                                 double2* __restrict__ r, LmState* __restrict__ st) {
+    __shared__ double sw[256];
+    const VjpPulseDev V = vp[blockIdx.x];
+    double s = 0;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const double2 b = p[V.r_off + m];
+        d[V.r_off + m] = make_double2(0, 0);
+        r[V.r_off + m] = b;
+        s += lm_redot(b, b);
+    }
+    const double gg = lm_block_sum(s, sw);
+    if (threadIdx.x == 0) {
+        const bool run = lm_goes_on(0, cg, gg, rtol, gg);
+        st[blockIdx.x] = LmState{gg, gg, mu[blockIdx.x], 0, run ? 1 : 0, gg > rtol * gg ? 1 : 0, 0};
+    }
+}
+
+// The sweeps of k_abr_gn_batch / k_abr2_gn_batch at ndir = 1 for the pulses that still run; the direction is the device's p.
+__global__ __launch_bounds__(256) void k_abr_lm_sweep(const double* __restrict__ rf_il, const double* __restrict__ g,
+                                                      const double* __restrict__ x, const double* __restrict__ scales,
+                                                      const AbrPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                      const VjpPulseDev* __restrict__ vp, int mode, int kind,
+                                                      const double* __restrict__ w, const double2* __restrict__ v,
+                                                      const LmState* __restrict__ st, double2* __restrict__ part) {
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    const AbrPulseDev P = pulses[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const int i = bk.chunk * 256 + threadIdx.x;
+    const bool live = i < P.nx;
+    const long o = P.o_off + (long)bk.scale * P.nx + (live ? i : 0);
+    abr_gn_sweeps<false, true>(rf_il, g, nullptr, v + P.r_off, P.r_off, P.n, scales[bk.scale], mode, kind,
+                               live ? x[P.x_off + i] : 0.0, 0.0, live, live ? w[o] : 0.0, make_double2(0, 0),
+                               part + V.p_off + ((long)bk.scale * V.nch + bk.chunk) * V.n, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_abr2_lm_sweep(const double* __restrict__ rf_il, const double* __restrict__ gx,
+                                                       const double* __restrict__ gy, const double* __restrict__ x,
+                                                       const double* __restrict__ y, const double* __restrict__ scales,
+                                                       const Abr2PulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                       const VjpPulseDev* __restrict__ vp, int mode, int kind,
+                                                       const double* __restrict__ w, const double2* __restrict__ v,
+                                                       const LmState* __restrict__ st, double2* __restrict__ part) {
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;
+    const Abr2PulseDev P = pulses[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const long i = (long)bk.chunk * 256 + threadIdx.x, tot = (long)P.nx * P.ny;
+    const bool live = i < tot;
+    const long kx = live ? i / P.ny : 0;
+    const long o = P.o_off + (long)bk.scale * tot + (live ? i : 0);
+    abr_gn_sweeps<true, true>(rf_il, gx, gy, v + P.r_off, P.r_off, P.n, scales[bk.scale], mode, kind, live ? x[P.x_off + kx] : 0.0,
+                              live ? y[P.y_off + (i - kx * P.ny)] : 0.0, live, live ? w[o] : 0.0, make_double2(0, 0),
+                              part + V.p_off + ((long)bk.scale * V.nch + bk.chunk) * V.n, nullptr);
+}
+
+// One CG iteration of one pulse per workgroup, after its sweep: H p by k_abr_gn_fold's sum of the partials, ap = H p + mu p (kept
+// in hp), pAp = <p, ap>; a pAp that is not finite or not > 0 stops the pulse with status 2 and nothing else changed; else
+// alpha = rr / pAp, d += alpha p, r -= alpha ap, rr' = <r, r>, p = r + (rr' / rr) p, and the next run flag.
+__global__ __launch_bounds__(256) void k_lm_step(const double2* __restrict__ part, const VjpPulseDev* __restrict__ vp,
+                                                 const double* __restrict__ scales, int nscale, int cg, double rtol,
+                                                 double2* __restrict__ p, double2* __restrict__ d, double2* __restrict__ r,
+                                                 double2* __restrict__ hp, LmState* __restrict__ st) {
+    __shared__ double sw[256];
+    const LmState S = st[blockIdx.x];
+    if (!S.run) return;
+    const VjpPulseDev V = vp[blockIdx.x];
+    double s = 0;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const double2 h = abr_vjp_fold_sum(part, V, scales, nscale, m), q = p[V.r_off + m], ap = lm_axpy(S.mu, q, h);
+        hp[V.r_off + m] = ap;
+        s += lm_redot(q, ap);
+    }
+    const double pap = lm_block_sum(s, sw);                      // every thread has read S before the sum's barriers
+    if (!(pap > 0) || !isfinite(pap)) {
+        if (threadIdx.x == 0) { st[blockIdx.x].run = 0; st[blockIdx.x].status = 2; }
+        return;
+    }
+    const double alpha = S.rr / pap;
+    s = 0;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const long t = V.r_off + m;
+        const double2 q = p[t], rn = lm_axpy(-alpha, hp[t], r[t]);
+        d[t] = lm_axpy(alpha, q, d[t]);
+        r[t] = rn;
+        s += lm_redot(rn, rn);
+    }
+    const double rr = lm_block_sum(s, sw), beta = rr / S.rr;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const long t = V.r_off + m;
+        p[t] = lm_axpy(beta, p[t], r[t]);
+    }
+    if (threadIdx.x == 0) {
+        const bool run = lm_goes_on(S.ncg + 1, cg, rr, rtol, S.gg);
+        st[blockIdx.x] = LmState{rr, S.gg, S.mu, S.ncg + 1, run ? 1 : 0, rr > rtol * S.gg ? 1 : 0, 0};
+    }
+}
+
+// trial = rf + d, sample by sample, for every pulse (a pulse that never ran has d = 0).
+__global__ __launch_bounds__(256) void k_lm_trial(const double2* __restrict__ rf, const double2* __restrict__ d, long R,
+                                                  double2* __restrict__ trial) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t < R) trial[t] = make_double2(rf[t].x + d[t].x, rf[t].y + d[t].y);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Host side of mbfir_abr_lsq_batch / mbfir_abr_gn_batch and their 2D twins (arguments checked by api.cpp): the forward call's staging
 // plus the weights, the targets or the directions, the partial descriptors and the two tables; one upload, two launches, one
 // download of the ndir R results (and the npulse losses).
@@ -397,6 +543,128 @@ void abr2_gn_batch_run(int device, void* stream, int npulse, const long* roff, c
                        S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp), mode, profile, S.dev<const double>(G.o_w),
                        S.dev<const double2>(G.o_v), ndir, o.part);
     gn_fold_download(S, G, o, nscale, npulse, false, st, nullptr, h_re, h_im);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side of mbfir_abr_lm_step_batch / mbfir_abr2_lm_step_batch (arguments checked by api.cpp): the forward staging and gn_stage at
+// ndir = 1 with b as the direction section, which is the device's p from then on; mu; one upload; k_lm_init, cg rounds of (sweep,
+// k_lm_step), and with a target k_lm_trial, the lsq sweep on the trial rf and the fold; one download.  The output region:
+//   d (R double2), the npulse states, [the gradient at rf + d (R double2), the npulse losses]      downloaded
+//   r, hp, the trial rf (R double2 each), the partials, the loss partials                          stay on the device
+namespace {
+struct LmArgs {
+    int npulse, nscale, cg;
+    const long* roff;
+    const double *w, *b_re, *b_im, *mu, *t_re, *t_im;
+    double rtol;
+    double *d_re, *d_im, *rr, *gg, *loss, *g_re, *g_im;
+    int *ncg, *status;
+};
+// sweep(G, p, state, part) and lsq(G, trial rf, part, lpart) launch the 1D or the 2D kernels on the staged sections.
+template <class Sweep, class Lsq>
+void lm_run(Staging& S, size_t o_rf, const std::vector<int>& ntime, const std::vector<long>& npoint, long O, const LmArgs& a,
+            hipStream_t st, Sweep sweep, Lsq lsq) {
+    const int npulse = a.npulse;
+    const long R = a.roff[npulse];
+    const bool trial = a.t_re != nullptr;
+    const GnSections G = gn_stage(S, npulse, a.roff, ntime, npoint, a.nscale, O, 1, a.w, a.t_re, a.t_im, a.b_re, a.b_im);
+    const size_t o_mu = S.add((size_t)npulse * 8);
+    std::copy(a.mu, a.mu + npulse, S.at<double>(o_mu));
+    auto pad16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    const size_t b_vec = (size_t)R * 16, b_st = pad16(npulse * sizeof(LmState)), b_loss = pad16((size_t)npulse * 8);
+    const size_t b_down = b_vec + b_st + (trial ? b_vec + b_loss : 0);
+    S.upload(b_down + 3 * b_vec + (size_t)G.npart * 16 + (size_t)G.nlp * 8, st);
+    char* out = S.dev<char>(S.o_out);
+    double2* d = reinterpret_cast<double2*>(out);
+    LmState* state = reinterpret_cast<LmState*>(out + b_vec);
+    double2* grad = reinterpret_cast<double2*>(out + b_vec + b_st);
+    double* loss = reinterpret_cast<double*>(out + 2 * b_vec + b_st);
+    double2* r = reinterpret_cast<double2*>(out + b_down);
+    double2 *hp = r + R, *trf = hp + R, *part = trf + R;
+    double* lpart = reinterpret_cast<double*>(part + G.npart);
+    double2* p = S.dev<double2>(G.o_v);
+    const VjpPulseDev* vp = S.dev<const VjpPulseDev>(G.o_vp);
+    hipLaunchKernelGGL(k_lm_init, dim3((unsigned)npulse), dim3(256), 0, st, vp, S.dev<const double>(o_mu), a.cg, a.rtol, p, d, r, state);
+    for (int k = 0; k < a.cg; ++k) {                              // rounds of a pulse that has stopped are early exits
+        sweep(G, p, state, part);
+        hipLaunchKernelGGL(k_lm_step, dim3((unsigned)npulse), dim3(256), 0, st, part, vp, S.dev<const double>(S.o_sc), a.nscale, a.cg,
+                           a.rtol, p, d, r, hp, state);
+    }
+    if (trial) {
+        hipLaunchKernelGGL(k_lm_trial, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, S.dev<const double2>(o_rf), d, R, trf);
+        lsq(G, reinterpret_cast<const double*>(trf), part, lpart);
+        hipLaunchKernelGGL(k_abr_gn_fold, dim3((unsigned)G.nfold), dim3(256), 0, st, part, vp, S.dev<const SimBlock>(G.o_fb),
+                           S.dev<const double>(S.o_sc), a.nscale, grad, lpart, S.dev<const long>(G.o_lp), loss);
+    }
+    std::vector<char> h(b_down);
+    S.download(h.data(), b_down, st);
+    unpack_cplx(R, reinterpret_cast<const double2*>(h.data()), a.d_re, a.d_im);
+    const LmState* hs = reinterpret_cast<const LmState*>(h.data() + b_vec);
+    for (int q = 0; q < npulse; ++q) {
+        a.rr[q] = hs[q].rr; a.gg[q] = hs[q].gg;
+        a.ncg[q] = hs[q].ncg; a.status[q] = hs[q].status;
+    }
+    if (trial) {
+        unpack_cplx(R, reinterpret_cast<const double2*>(h.data() + b_vec + b_st), a.g_re, a.g_im);
+        std::copy(reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st),
+                  reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st) + npulse, a.loss);
+    }
+}
+}  // namespace
+
+void abr_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                           const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                           int profile, const double* w, const double* b_re, const double* b_im, const double* mu, int cg,
+                           double rtol, const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr,
+                           double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    AbrStaged A;
+    abr_stage(A, npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale, scales);
+    Staging& S = A.S;
+    const LmArgs a{npulse, nscale, cg, roff, w, b_re, b_im, mu, t_re, t_im, rtol, d_re, d_im, rr, gg, loss, g_re, g_im, ncg, status};
+    lm_run(S, A.o_rf, A.ntime, A.npoint, A.O, a, st,
+           [&](const GnSections& G, const double2* p, const LmState* state, double2* part) {
+               hipLaunchKernelGGL(k_abr_lm_sweep, dim3((unsigned)G.nblk), dim3(256), 0, st, S.dev<const double>(A.o_rf),
+                                  S.dev<const double>(A.o_g), S.dev<const double>(A.o_x), S.dev<const double>(S.o_sc),
+                                  S.dev<const AbrPulseDev>(S.o_pd), S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp),
+                                  mode, profile, S.dev<const double>(G.o_w), p, state, part);
+           },
+           [&](const GnSections& G, const double* trf, double2* part, double* lpart) {
+               hipLaunchKernelGGL(k_abr_lsq_batch, dim3((unsigned)G.nblk), dim3(256), 0, st, trf, S.dev<const double>(A.o_g),
+                                  S.dev<const double>(A.o_x), S.dev<const double>(S.o_sc), S.dev<const AbrPulseDev>(S.o_pd),
+                                  S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(G.o_vp), S.dev<const long>(G.o_lp), mode,
+                                  profile, S.dev<const double>(G.o_w), S.dev<const double2>(G.o_t), part, lpart);
+           });
+}
+
+void abr2_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                            const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                            const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile,
+                            const double* w, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                            const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                            int* status, double* loss, double* g_re, double* g_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Abr2Staged A;
+    abr2_stage(A, npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid, yoff, y, nscale, scales);
+    Staging& S = A.S;
+    const LmArgs a{npulse, nscale, cg, roff, w, b_re, b_im, mu, t_re, t_im, rtol, d_re, d_im, rr, gg, loss, g_re, g_im, ncg, status};
+    lm_run(S, A.o_rf, A.ntime, A.npoint, A.O, a, st,
+           [&](const GnSections& G, const double2* p, const LmState* state, double2* part) {
+               hipLaunchKernelGGL(k_abr2_lm_sweep, dim3((unsigned)G.nblk), dim3(256), 0, st, S.dev<const double>(A.o_rf),
+                                  S.dev<const double>(A.o_gx), S.dev<const double>(A.o_gy), S.dev<const double>(A.o_x),
+                                  S.dev<const double>(A.o_y), S.dev<const double>(S.o_sc), S.dev<const Abr2PulseDev>(S.o_pd),
+                                  S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp), mode, profile,
+                                  S.dev<const double>(G.o_w), p, state, part);
+           },
+           [&](const GnSections& G, const double* trf, double2* part, double* lpart) {
+               hipLaunchKernelGGL(k_abr2_lsq_batch, dim3((unsigned)G.nblk), dim3(256), 0, st, trf, S.dev<const double>(A.o_gx),
+                                  S.dev<const double>(A.o_gy), S.dev<const double>(A.o_x), S.dev<const double>(A.o_y),
+                                  S.dev<const double>(S.o_sc), S.dev<const Abr2PulseDev>(S.o_pd), S.dev<const SimBlock>(S.o_bk),
+                                  S.dev<const VjpPulseDev>(G.o_vp), S.dev<const long>(G.o_lp), mode, profile,
+                                  S.dev<const double>(G.o_w), S.dev<const double2>(G.o_t), part, lpart);
+           });
 }
 
 }  // namespace mbfir

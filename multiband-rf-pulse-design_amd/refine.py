@@ -19,14 +19,17 @@ def _dot(u, v):
     return float((np.conj(u) * v).real.sum())
 
 
-def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False, iters=5, cg=8, mu0=None, rtol=1e-6, ctx=None):
+def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False, iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
+                 ctx=None):
     """refine_batch(pulses, x, targets, weights, ...) for abr_batch's model, refine_batch(pulses, x, y, targets, weights, ...) for
     abr2_batch's.  pulses: rf or (rf, g) each; x (and y): one grid shared by every pulse or a list of one per pulse; targets,
     weights, profile, scales and hard_pulse as for abr_lsq_batch / abr2_lsq_batch.  iters: accepted steps per pulse at the most;
     cg: CG iterations per step at the most, stopped once |residual|^2 <= rtol |g|^2; mu0: None (the Rayleigh quotient), a number,
     or one number per pulse.  Returns (rfs, infos): the refined rf per pulse and a dict per pulse with 'losses' (L at the start and
     after every accepted step), 'mu' (the last one), 'status' ('iters', 'converged': a zero gradient, or 'gave_up': mu past 1e12),
-    'refused' (steps that did not lower L) and 'calls' (the lsq and gn calls the pulse took part in)."""
+    'refused' (steps that did not lower L) and 'calls' (the lsq and gn calls the pulse took part in).  solver: 'host' runs the CG
+    recurrence here, one gn call per iteration; 'device' solves and tries each step in one abr_lm_step_batch / abr2_lm_step_batch
+    call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as a refused step."""
     mb = importlib.import_module(__package__)
     if len(args) == 2:
         two, y = False, None
@@ -45,6 +48,8 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
         raise ValueError("refine_batch: %d targets and %d weight arrays for %d pulses" % (len(targets), len(weights), P))
     if iters < 0 or cg < 1:
         raise ValueError("refine_batch: iters must be at least 0 and cg at least 1")
+    if solver not in ("host", "device"):
+        raise ValueError("refine_batch: solver must be 'host' or 'device', not %r" % (solver,))
     gs = [p[1] if isinstance(p, tuple) else None for p in pulses]
     rfs = [np.array(p[0] if isinstance(p, tuple) else p, dtype=np.complex128).ravel() for p in pulses]
     kw = dict(profile=profile, scales=scales, hard_pulse=hard_pulse, ctx=ctx)
@@ -69,7 +74,40 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
             infos[q]["calls"]["gn"] += 1
         return fn(pack(idx, rfs), *pos, [v_of[q] for q in idx], [weights[q] for q in idx], **kw)
 
-    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    def lm(idx):
+        """the step of every active pulse, solved and tried on the device: (rf + d, L and g there, whether CG broke down)"""
+        pos = (grid(x, idx), grid(y, idx)) if two else (grid(x, idx),)
+        fn = mb.abr2_lm_step_batch if two else mb.abr_lm_step_batch
+        for q in idx:
+            infos[q]["calls"]["lm"] += 1
+        res = fn(pack(idx, rfs), *pos, [-grad[q] for q in idx], [weights[q] for q in idx], [mu[q] for q in idx],
+                 targets=[targets[q] for q in idx], cg=cg, rtol=rtol, **kw)
+        return [(rfs[q] + d, i["loss"], i["grad"], i["status"] == "breakdown") for q, (d, i) in zip(idx, res)]
+
+    def host_steps(idx):
+        """the same on the host: CG on (H + mu I) d = -g from d = 0, one gn call per iteration, then one lsq call"""
+        d = {q: np.zeros_like(rfs[q]) for q in idx}
+        r = {q: -grad[q] for q in idx}
+        p = {q: r[q].copy() for q in idx}
+        rr = {q: _dot(r[q], r[q]) for q in idx}
+        gg = dict(rr)
+        ncg = {q: 0 for q in idx}
+        while True:
+            run = [q for q in idx if ncg[q] < cg and rr[q] > rtol * gg[q]]
+            if not run:
+                break
+            for q, hp in zip(run, gn(run, p)):
+                ap = hp + mu[q] * p[q]
+                alpha = rr[q] / _dot(p[q], ap)
+                d[q], r[q] = d[q] + alpha * p[q], r[q] - alpha * ap
+                rr[q], old = _dot(r[q], r[q]), rr[q]
+                p[q] = r[q] + (rr[q] / old) * p[q]
+                ncg[q] += 1
+        trial = {q: rfs[q] + d[q] for q in idx}
+        return [(trial[q], L, g, False) for q, (L, g) in zip(idx, lsq(idx, trial))]
+
+    calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
     every = list(range(P))
     loss, grad, done = [0.0] * P, [None] * P, [0] * P
     for q, (L, g) in zip(every, lsq(every, rfs)):
@@ -92,28 +130,10 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
         for q, hg in zip(need, gn(need, grad)):
             mu[q] = 1e-3 * _dot(grad[q], hg) / _dot(grad[q], grad[q])       # a Rayleigh quotient of H sets the scale of mu
     while active:
-        d = {q: np.zeros_like(rfs[q]) for q in active}                      # CG on (H + mu I) d = -g from d = 0
-        r = {q: -grad[q] for q in active}
-        p = {q: r[q].copy() for q in active}
-        rr = {q: _dot(r[q], r[q]) for q in active}
-        gg = dict(rr)
-        ncg = {q: 0 for q in active}
-        while True:
-            run = [q for q in active if ncg[q] < cg and rr[q] > rtol * gg[q]]
-            if not run:
-                break
-            for q, hp in zip(run, gn(run, p)):
-                ap = hp + mu[q] * p[q]
-                alpha = rr[q] / _dot(p[q], ap)
-                d[q], r[q] = d[q] + alpha * p[q], r[q] - alpha * ap
-                rr[q], old = _dot(r[q], r[q]), rr[q]
-                p[q] = r[q] + (rr[q] / old) * p[q]
-                ncg[q] += 1
-        trial = {q: rfs[q] + d[q] for q in active}
         still = []
-        for q, (L, g) in zip(active, lsq(active, trial)):
-            if L < loss[q]:
-                rfs[q], loss[q], grad[q], mu[q] = trial[q], L, g, mu[q] / 3
+        for q, (trial, L, g, broke) in zip(active, lm(active) if solver == "device" else host_steps(active)):
+            if L < loss[q] and not broke:
+                rfs[q], loss[q], grad[q], mu[q] = trial, L, g, mu[q] / 3
                 infos[q]["losses"].append(L)
                 done[q] += 1
                 if _dot(g, g) == 0.0:
