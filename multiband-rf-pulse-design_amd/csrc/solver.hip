@@ -419,16 +419,18 @@ __global__ __launch_bounds__(256) void k_atmulti(DProg P, const double* __restri
     }
 }
 
-// fold the split partials: TT[v][j] = sum_s partial[s][v][j].  Block = 64 columns x 16 split groups.
+// fold the split partials: TT[v][j] = sum_s partial[s][v][j].  Block = FPC columns x 16 split groups: 256 threads like k_gt_finish (a
+// 1024-thread block waits for a whole CU once other units share the chip); the 16 per-group sums and the sum over them keep their order.
 // dims != null (heterogeneous unit, lattice partials): the lane folds its OWN cdiv(nchunk, cgrp) partials -- the grouping of
 // the unrolled sums below depends on the count, and the lane's result has to be that of its single solve bit for bit
-__global__ __launch_bounds__(1024) void k_fold_partials(const double* __restrict__ partial, int nsplit, int nvv, int ld,
+constexpr int FPC = 16;
+__global__ __launch_bounds__(FPC * 16) void k_fold_partials(const double* __restrict__ partial, int nsplit, int nvv, int ld,
                                                         int ldo, double* __restrict__ TT, size_t lane_bytes, const int* lane_mask,
                                                         const LaneDims* __restrict__ dims, int cgrp) {
     LANES_RAW(lane_bytes, lane_mask, partial, TT);
     if (dims) nsplit = cgrp > 0 ? (dims[blockIdx.z].nchunk + cgrp - 1) / cgrp : (dims[blockIdx.z].Mown - cgrp - 1) / -cgrp;     // (cgrp < 0: dense path, -cgrp rows per split)
-    __shared__ double sh[16][65];
-    const int c = threadIdx.x, sg = threadIdx.y, j = blockIdx.x * 64 + c, v = blockIdx.y;
+    __shared__ double sh[16][FPC + 1];
+    const int c = threadIdx.x, sg = threadIdx.y, j = blockIdx.x * FPC + c, v = blockIdx.y;
     double t = 0;
     if (j < ld) {
         const double* p = partial + (long)v * ld + j;
@@ -678,6 +680,45 @@ __device__ __forceinline__ bool pair_prologue(DProg& P, int nlanes, bool (&live)
 }
 template <class T>
 __device__ __forceinline__ T* byte_shift(T* p, size_t off) { return (T*)((const char*)p + off); }
+// acc += x_LANE y with x_LANE the x of lane LANE of the thread's row of 16 lanes: the broadcast rides in the FMA (v_fmac_f64_dpp row_newbcast), the
+// same fused operation as acc = fma(x, y, acc).  Every lane of the row has to be active (a disabled source lane leaves acc as it was).
+// The s_nop in front of a block's first step covers the two wait states between a vector write of x and a DPP read, which the
+// compiler does not see through an asm statement.
+template <int LANE>
+__device__ __forceinline__ void fmac_row(double& acc, double x, double y) {
+    if constexpr (LANE == 0) asm("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(y));
+    else asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(x), "v"(y), "n"(LANE));
+}
+// Steps I ... 15 of a block of 16 lattice points of trig_eval_sum: lane r of every row of 16 holds the coefficients of point r
+template <int NVVMAX, int NL, int NVC, int I>
+__device__ __forceinline__ void eval_steps16(const double2 (&x)[NL][NVVMAX], double (&ac)[NL][NVVMAX], double (&as)[NL][NVVMAX], double& c, double& s, double cw, double sw) {
+    if constexpr (I < 16) {
+#pragma unroll
+        for (int L = 0; L < NL; ++L)
+#pragma unroll
+        for (int v = 0; v < NVC; ++v) { fmac_row<I>(ac[L][v], x[L][v].x, c); fmac_row<I>(as[L][v], x[L][v].y, s); }
+        rotate<0>(c, s, cw, sw);
+        eval_steps16<NVVMAX, NL, NVC, I + 1>(x, ac, as, c, s, cw, sw);
+    }
+}
+// trig_eval_sum for a pair with the vector count known (NVC > 0), in blocks of 16 points: one read per block and image instead of sixteen wave-uniform
+// ones, the points' coefficients by row broadcast (every lane of the wave active; cf zero from n to the end of its last block: fma(0, c, a) = a)
+template <int NVVMAX, int NL, int NVC>
+__device__ __forceinline__ void trig_eval_sum_rows(const double2 (*cf)[NVVMAX][SEGMAX], int n, const double4 sd4, double (&ac)[NL][NVVMAX], double (&as)[NL][NVVMAX]) {
+    double c = sd4.x, s = sd4.y;
+#pragma unroll
+    for (int L = 0; L < NL; ++L)
+#pragma unroll
+    for (int v = 0; v < NVVMAX; ++v) ac[L][v] = as[L][v] = 0;
+    for (int m0 = 0; m0 < n; m0 += 16) {
+        double2 x[NL][NVVMAX];
+#pragma unroll
+        for (int L = 0; L < NL; ++L)
+#pragma unroll
+        for (int v = 0; v < NVC; ++v) x[L][v] = cf[L][v][m0 + (threadIdx.x & 15)];
+        eval_steps16<NVVMAX, NL, NVC, 0>(x, ac, as, c, s, sd4.z, sd4.w);
+    }
+}
 // the sums of trig_eval_lanes over the segment's n lattice points: NVC vectors (0: the run-time count NVV), one (c, s) chain for all NL lanes
 template <int NVVMAX, int NL, int NVC>
 __device__ __forceinline__ void trig_eval_sum(const double2 (*cf)[NVVMAX][SEGMAX], int n, int NVV, const double4 sd4, double (&ac)[NL][NVVMAX], double (&as)[NL][NVVMAX]) {
@@ -720,14 +761,23 @@ __device__ __forceinline__ void trig_eval_lanes(const DProg& P, const double* co
             }
         }
     }
+    constexpr bool ROWB = NL == 2;                        // (the one-lane body keeps the run-time vector count and k_trig_eval's loop)
+    if (ROWB)                                             // (the row-broadcast sums run whole blocks of 16 points: zeros behind the segment's last one)
+        for (int e = 2 * (m1 - m0) + threadIdx.x; e < 2 * ((m1 - m0 + 15) & ~15); e += 256)
+#pragma unroll
+            for (int L = 0; L < NL; ++L)
+#pragma unroll
+            for (int v = 0; v < 2 * NV; ++v) { if (e & 1) cf[L][v][e >> 1].y = 0.0; else cf[L][v][e >> 1].x = 0.0; }
     __syncthreads();
-    if (k >= P.nfold) return;
-    const double4 sd4 = P.seed_eval[(long)sg * P.Mpad + k];
+    // (a pair keeps every lane of a wave that has a frequency: its sums take their coefficients from the lanes of a row; a frequency past the end runs on zero seeds)
+    if ((ROWB ? k - (int)(threadIdx.x & 63) : k) >= P.nfold) return;
+    const double4 sd4 = k < P.nfold ? P.seed_eval[(long)sg * P.Mpad + k] : make_double4(0.0, 0.0, 0.0, 0.0);
     double ac[NL][NVVMAX], as[NL][NVVMAX];
     // (a pair takes the vector count out of the loop: with two lanes' reads in flight the per-vector branches cost registers)
-    if (NL == 1) trig_eval_sum<NVVMAX, NL, 0>(cf, m1 - m0, NVV, sd4, ac, as);
-    else if (P.quad) trig_eval_sum<NVVMAX, NL, NVVMAX>(cf, m1 - m0, NVV, sd4, ac, as);
-    else trig_eval_sum<NVVMAX, NL, NV>(cf, m1 - m0, NVV, sd4, ac, as);
+    if constexpr (!ROWB) trig_eval_sum<NVVMAX, NL, 0>(cf, m1 - m0, NVV, sd4, ac, as);
+    else if (P.quad) trig_eval_sum_rows<NVVMAX, NL, NVVMAX>(cf, m1 - m0, sd4, ac, as);
+    else trig_eval_sum_rows<NVVMAX, NL, NV>(cf, m1 - m0, sd4, ac, as);
+    if (k >= P.nfold) return;
     const int ip = P.fold_pos[k], in = P.fold_neg[k];
 #pragma unroll
     for (int L = 0; L < NL; ++L)
@@ -740,7 +790,8 @@ __device__ __forceinline__ void trig_eval_lanes(const DProg& P, const double* co
         }
 }
 // ... for the lanes 2z and 2z + 1 of a unit of nlanes (launch bounds: one vector per lane the waves per SIMD k_trig_eval gets; two vectors per lane
-// 4, which leaves the loop k_trig_eval's unroll and 88 registers; no spills -- DESIGN.md section 4)
+// 4: the blocks of 16 points of both of its bodies, the four-vector one's sixteen coefficient registers included, take 128 registers; no spills --
+// DESIGN.md section 4)
 template <int NV>
 __global__ __launch_bounds__(256, NV == 1 ? 8 : 4) void k_trig_eval_pair(DProg P, const double* __restrict__ vin, double* __restrict__ UU, int nlanes) {
     __shared__ double2 cf[2][2 * NV][SEGMAX];
@@ -955,10 +1006,30 @@ __device__ __forceinline__ void freq_operands_lanes(const DProg* const (&PL)[NL]
         }
     }
 }
+// Steps I ... 15 of a block of 16 steps of trig_moments_lanes' loop: lane r of every row of 16 holds the operands of step r (pa: the first chunk's,
+// pb: the second one's); per lane and vector the four FMAs of a step in the loop's order, then the two rotations.
+template <int NV, int NL, int I>
+__device__ __forceinline__ void moment_steps16(const double2 (&pa)[NL][NV], const double2 (&pb)[NL][NV], double (&ag)[NL][NV], double (&as)[NL][NV],
+                                               double& c0, double& s0, double& c1, double& s1, const double4& sa, const double4& sb) {
+    if constexpr (I < 16) {
+#pragma unroll
+        for (int L = 0; L < NL; ++L)
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+            fmac_row<I>(ag[L][v], pa[L][v].x, c0); fmac_row<I>(as[L][v], pa[L][v].y, s0);
+            fmac_row<I>(ag[L][v], pb[L][v].x, c1); fmac_row<I>(as[L][v], pb[L][v].y, s1);
+        }
+        rotate<1>(c0, s0, sa.z, sa.w);
+        rotate<1>(c1, s1, sb.z, sb.w);
+        moment_steps16<NV, NL, I + 1>(pa, pb, ag, as, c0, s0, c1, s1, sa, sb);
+    }
+}
 // k_trig_moments<NV, FOLD>'s work for NL lanes in one block (lane pairs, see k_trig_eval_pair): P holds the tables the lanes share, PL[L] the lane's own
 // program (alpha, beta, f_ptr, f_rows), rows[L] (FOLD) or src[L] (the lane's folded operands PPf) / partial[L] its vectors, pp[L] its LDS image; one
 // (c, s) chain per chunk serves all NL lanes.  The seeds of the first two chunks are loaded in front of the staging, so they arrive while the operands
-// are gathered; the next two chunks' travel during the loop before.
+// are gathered; the next two chunks' travel during the loop before.  With one or two operands per lane the loop reads each operand from LDS in ONE lane
+// per row of 16 and hands it to the others inside the FMA (moment_steps16): read by every thread, the wave-uniform reads held the CU's one LDS pipe as
+// long as the FMAs held its four fp64 pipes, and the two did not overlap.
 template <int NV, int NL, bool FOLD>
 __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* const (&PL)[NL], const double2* const (&src)[NL], const double4* __restrict__ seeds, int na, int nb,
                                                    double* const (&partial)[NL], const double* const (&rows)[NL], double2 (*pp)[NV][CGRP][CHK]) {
@@ -988,7 +1059,10 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
         }
     }
     __syncthreads();
-    if (m >= na + nb) return;
+    // ROWB (one or two operands per lane): the loop takes its operands from the lanes of the thread's row instead of reading every one of them
+    // in every thread, so a wave with a point to compute keeps all its lanes (a point past the end runs on zero seeds and stores nothing)
+    constexpr bool ROWB = NV <= 2;
+    if ((ROWB ? m - (tid & 63) : m) >= na + nb) return;
     double ag[NL][NV], as[NL][NV];
 #pragma unroll
     for (int L = 0; L < NL; ++L)
@@ -1004,6 +1078,19 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
         double c0 = sa.x, s0 = sa.y, c1 = sb.x, s1 = sb.y;
         const int cnt = max(P.ch_count[cha], two ? P.ch_count[chb] : 0);
         const int clb = two ? cl + 1 : cl;                  // (a lone last chunk pairs with itself at zero weight: sb = 0)
+        if constexpr (ROWB) {
+            // blocks of 16 steps: lane r of a row loads the operands of step q0 + r (one read per block and image where the plain loop below
+            // has sixteen wave-uniform ones), the steps take them by row broadcast.  The last block runs past cnt on operands staged
+            // as zeros, like the shorter chunk of the two: fma(0, c, a) = a.
+            for (int q0 = 0; q0 < cnt; q0 += 16) {
+                double2 pa[NL][NV], pb[NL][NV];
+#pragma unroll
+                for (int L = 0; L < NL; ++L)
+#pragma unroll
+                for (int v = 0; v < NV; ++v) { pa[L][v] = pp[L][v][cl][q0 + (tid & 15)]; pb[L][v] = pp[L][v][clb][q0 + (tid & 15)]; }
+                moment_steps16<NV, NL, 0>(pa, pb, ag, as, c0, s0, c1, s1, sa, sb);
+            }
+        } else {
 #pragma unroll (NV * NL > 4 ? 2 : 4)
         for (int q = 0; q < cnt; ++q) {
 #pragma unroll
@@ -1017,8 +1104,10 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
             rotate<1>(c0, s0, sa.z, sa.w);
             rotate<1>(c1, s1, sb.z, sb.w);
         }
+        }
         sa = na4; sb = nb4;
     }
+    if (m >= na + nb) return;
 #pragma unroll
     for (int L = 0; L < NL; ++L)
 #pragma unroll
@@ -2907,7 +2996,7 @@ struct Solver::Impl {
 #undef MOM_CASE
             default: throw HipError("moments: unsupported vector count");
         }
-        hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.LDM, 64), 2 * nv), nlanes), dim3(64, 16), 0, st, partial, cdiv(P.nchunk, P.cgrp), 2 * nv, P.LDM, P.LDM, out, lane_bytes, P.mask, P.dims, P.cgrp);
+        hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.LDM, FPC), 2 * nv), nlanes), dim3(FPC, 16), 0, st, partial, cdiv(P.nchunk, P.cgrp), 2 * nv, P.LDM, P.LDM, out, lane_bytes, P.mask, P.dims, P.cgrp);
     }
     void atmulti_array(int nvv, const double* pp) {
         dim3 g(P.ld / 128, nsplit_at), b(64, 4);
@@ -3240,7 +3329,7 @@ struct Solver::Impl {
         if (P.Ne > 0) {
             int nvv = P.quad ? 2 * P.Ne : P.Ne;
             atmulti_array(nvv, BB);
-            hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.ld, 64), nvv), nlanes), dim3(64, 16), 0, st, partial, nsplit_at, nvv, P.ld, P.LDV, TT, lane_bytes, P.mask, P.dims, -AT_ROWS);
+            hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.ld, FPC), nvv), nlanes), dim3(FPC, 16), 0, st, partial, nsplit_at, nvv, P.ld, P.LDV, TT, lane_bytes, P.mask, P.dims, -AT_ROWS);
         }
         if (ar_overlap) {
             // the small ingredients in one collective (border products, and behind them the 3 x 3 y-y block as in the lattice
