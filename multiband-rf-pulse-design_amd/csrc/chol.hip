@@ -282,6 +282,40 @@ __device__ __forceinline__ void subst16x2(const double* __restrict__ Lz, const d
     vb[0] = b0 * dm0; vb[1] = b1 * dm1; vb[2] = b2 * dm2; vb[3] = b3 * dm3;
 }
 
+// Four right-hand sides per thread, for a task that already holds them in the matrix cores' accumulator layout: the D layout
+// of v_mfma_f64_16x16x4_f64 has the entries 16 i + (lane & 15) of ONE right-hand side in element r of the blocks i = 0 .. 3 (a DPP
+// row owns the four right-hand sides r = 0 .. 3), which is the layout subst16 wants -- no staging through LDS, and the image is
+// read once for four chains.  x[i][r]: entry lam + 16 i of chain r.  Same arithmetic per chain as subst16: bit-identical.
+template <int J>
+__device__ __forceinline__ void subst16x4_steps(const double* __restrict__ lz, double dm0, double dm1, double dm2, double dm3,
+                                                v4d& x0, v4d& x1, v4d& x2, v4d& x3) {
+    if constexpr (J < SUBST_STEPS) {
+        constexpr int I = J >> 4;
+        // (the image reads are kept near their steps, see subst16x2_steps; four chains hold twice the registers: within 4 steps)
+        if constexpr (J % 4 == 0 && J > 0) __builtin_amdgcn_sched_barrier(0);
+        const v4d cur = I == 0 ? x0 * dm0 : I == 1 ? x1 * dm1 : I == 2 ? x2 * dm2 : x3 * dm3;
+        v4d x;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) x[r] = row_bcast<(J & 15)>(cur[r]);
+        const double* lr = lz + J * ZLD;
+        if constexpr (I < 2) {
+            const double2 lo = *reinterpret_cast<const double2*>(lr);
+            if constexpr (I == 0) x0 -= x * lo.x;
+            x1 -= x * lo.y;
+        }
+        const double2 hi = *reinterpret_cast<const double2*>(lr + 32);
+        if constexpr (I < 3) x2 -= x * hi.x;
+        x3 -= x * hi.y;
+        subst16x4_steps<J + 1>(lz, dm0, dm1, dm2, dm3, x0, x1, x2, x3);
+    }
+}
+__device__ __forceinline__ void subst16x4(const double* __restrict__ Lz, const double* __restrict__ dinv, v4d (&x)[4]) {
+    const int lam = threadIdx.x & 15;
+    const double dm0 = dinv[lam], dm1 = dinv[lam + 16], dm2 = dinv[lam + 32], dm3 = dinv[lam + 48];
+    subst16x4_steps<0>(Lz + 2 * lam, dm0, dm1, dm2, dm3, x[0], x[1], x[2], x[3]);
+    x[0] *= dm0; x[1] *= dm1; x[2] *= dm2; x[3] *= dm3;
+}
+
 // ---- factorisation of the 64x64 diagonal block: four 16-column slabs -------------------------------
 // The trailing matrix lives in MFMA accumulators (the ten lower 16x16 tiles, dealt to the 4 waves by
 // the table below); per slab
@@ -1209,32 +1243,37 @@ __device__ __forceinline__ void trail_left2(const CholStep& a, int i, int j, int
 // accumulator registers (operands streamed through LDS, the next pair in flight behind the current product) -- the
 // updates the per-step forms apply one panel at a time as read-modify-writes of the inverse's trailing tiles, in the
 // same order and with the same arithmetic per update (first update writes the negated product, the others subtract) --
-// and then, when row r-1 of the inverse and the image of L_rr are there, does what minv_block does: the product with
-// L_r,r-1 (held in REGISTERS in the matrix cores' operand layout), two passes of 32 columns, two interleaved
-// substitutions per thread.  No inverse-update tasks, no read-modify-write traffic on the inverse at all.
+// and then, when row r-1 of the inverse and the image of L_rr are there, does what minv_block does -- the product with
+// L_r,r-1 and the substitution against L_rr, same arithmetic per entry -- on the TRANSPOSED tile: a wave owns the columns
+// 16 w .. 16 w + 15 and all 64 rows, M_r-1,j is the matrix cores' A operand (16 registers per lane, straight from global
+// memory), -L_r,r-1 the B operand (one LDS tile), so that the accumulators come out with a column's 64 rows along lane & 15:
+// the layout of the substitution (subst16x4: four columns per DPP row, no staging, one reading of the image).  The transpose
+// Mt is stored from the registers as they are, M itself through a wave-private 16 x 16 transposition.  No inverse-update
+// tasks, no read-modify-write traffic on the inverse at all.
 __device__ __forceinline__ void minv_strip(const CholStep& a, int j, double* smem) {
-    const int tid = task_tid(), lane = tid & 63, wv = tid >> 6;
+    const int tid = task_tid(), lane = tid & 63, wv = tid >> 6, lam = lane & 15, g4 = lane >> 4;
     const int np = a.np, r = a.k - 1;
     const long kr = (long)r * CB;
     double* M = a.M;
     double* Lz = smem + R0;
-    double(*Bs)[33] = reinterpret_cast<double(*)[33]>(smem + R1);          // 32 columns of M_r-1,j
-    double* Ct = smem + R1 + 64 * 33;                                      // staging [column][row], stride YLD, 32 columns
+    double* Ls = smem + R1;                                                // -L_r,r-1, 64 x YLD
+    double* Tw = smem + R2 + wv * (16 * 17);                               // the wave's 16 x 16 transposition, stride 17
     double* dinv = smem + R3;
     const DagCnt dc(a.cnt, a.nblk);
-    const int c = lane & 15;
-    double rold[2][2][4];                                 // R_rj in the layout of the two 32-column passes: [pass][half][q]
+    double(*X)[CLD] = reinterpret_cast<double(*)[CLD]>(smem + R1);         // R_rj on its way into the accumulators' layout: the SAME
+                                                                           // LDS as Ls, read out (and a barrier passed) before Ls is written
+    v4d acc[4];                                           // R_rj, then M_rj: acc[i][q] is row lam + 16 i, column 16 wv + g4 + 4 q
     if (j <= r - 2 && dag_ruform(a.nblk)) {
         // (nblk > 32)  R_rj as the inverse-update tasks left it
         if (tid == 0) wait_flag(dc.at(dc.ruver, r, j), r - j - 1, a.flag);
         __syncthreads();
+        load_block<true>(X, M + kr * np + (long)j * CB, np);
+        __syncthreads();
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    rold[ps][h][q] = ld_sc1(M + (kr + 16 * wv + (lane >> 4) + 4 * q) * np + (long)j * CB + 32 * ps + 16 * h + c);
+            for (int q = 0; q < 4; ++q) acc[i][q] = X[lam + 16 * i][16 * wv + g4 + 4 * q];
+        __syncthreads();                                  // R1 is free for -L_r,r-1
     } else if (j <= r - 2) {
         // ---- accumulate the panels j .. r-2 (their tiles of L and of the inverse were finished steps ago)
         const int npan = r - 1 - j;
@@ -1285,119 +1324,100 @@ __device__ __forceinline__ void minv_strip(const CholStep& a, int j, double* sme
             __syncthreads();                              // everybody is done reading P and Q
             PH(4)
         }
-        // accumulator layout -> the layout of the passes, through LDS
-        double(*X)[CLD] = reinterpret_cast<double(*)[CLD]>(smem + R1);
+        // the quadrants' accumulator layout -> the transposed tile's, through LDS
         acc_foreach(x, [&](int i, int jj, double& v) { X[i][jj] = v; });
         __syncthreads();
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) rold[ps][h][q] = X[16 * wv + (lane >> 4) + 4 * q][32 * ps + 16 * h + c];
-        __syncthreads();                                  // R0 / R1 are free for the image and the passes' staging
+            for (int q = 0; q < 4; ++q) acc[i][q] = X[lam + 16 * i][16 * wv + g4 + 4 * q];
+        __syncthreads();                                  // R0 / R1 are free for the image and -L_r,r-1
         PH(4)
     } else {
 #pragma unroll
-        for (int ps = 0; ps < 2; ++ps)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int t = 16 * wv + (lane >> 4) + 4 * q, cc = 32 * ps + 16 * h + c;
-                    rold[ps][h][q] = j == r ? (t == cc ? 1.0 : 0.0) : 0.0;       // identity on the diagonal tile, zero next to it
-                }
+            for (int q = 0; q < 4; ++q)                   // identity on the diagonal tile, zero next to it
+                acc[i][q] = (j == r && lam + 16 * i == 16 * wv + g4 + 4 * q) ? 1.0 : 0.0;
     }
     // ---- row r-1 of the inverse (this column), L_r,r-1 and the image of L_rr
     if (tid == 0) wait_flags(dc.img + r, 1, j < r ? dc.at(dc.rowdone, r - 1, r) : nullptr, 4, j < r ? dc.at(dc.msdone, r - 1, j) : nullptr, 4, a.flag);
     __syncthreads();
     PH(1)
+    double mf[16];                                        // M_r-1,j: rows 4 q + g4, column 16 wv + lam (the A operand of the transposed product)
     {
         const rsrc_t ri = make_rsrc(a.Dfac + kr * CB);
-        double2 t[8];
+        double2 t[8], lt[8];
 #pragma unroll
         for (int u = 0; u < 8; ++u) t[u] = ld2_sc1(ri, unsigned(2 * (tid + 256 * u) * 8));
+        if (j < r) {
+            const rsrc_t rl = make_rsrc(a.H + kr * np + kr - CB), rb = make_rsrc(M + (kr - CB) * np + (long)j * CB);
+#pragma unroll
+            for (int u = 0; u < 8; ++u) { const int e = tid + 256 * u; lt[u] = ld2_sc1(rl, unsigned(((e >> 5) * np + 2 * (e & 31)) * 8)); }
+            const unsigned voB = unsigned((g4 * np + 16 * wv + lam) * 8);
+#pragma unroll
+            for (int q = 0; q < 16; ++q) mf[q] = ldb_sc1(rb, voB, unsigned(4 * q * np * 8));
+        }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int e = tid + 256 * u;
             *reinterpret_cast<double2*>(Lz + (e >> 5) * ZLD + 2 * (e & 31)) = t[u];
         }
+        if (j < r) {                                      // negated (see mma64); the stride is odd: two 8-byte stores
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = tid + 256 * u;
+                Ls[(e >> 5) * YLD + 2 * (e & 31)] = -lt[u].x;
+                Ls[(e >> 5) * YLD + 2 * (e & 31) + 1] = -lt[u].y;
+            }
+        }
     }
     if (tid < CB) dinv[tid] = ld_sc1(a.dinvG + kr + tid);
-    double af[16];                                        // -L_r,r-1: row 16 wv + (lane & 15), columns 4 q + (lane >> 4) (negated: see mma64)
+    __syncthreads();                                      // Lz, dinv and -L_r,r-1 in place
+    PH(2)
     if (j < r) {
+        // acc' -= M_r-1,j' L_r,r-1': the products of minv_block's  acc -= L_r,r-1 M_r-1,j  entry by entry, in the same k order
 #pragma unroll
-        for (int q = 0; q < 16; ++q) af[q] = -ld_sc1(a.H + (kr + 16 * wv + (lane & 15)) * np + kr - CB + 4 * q + (lane >> 4));
-    } else {
+        for (int q = 0; q < CHOL_KSTEPS(16); ++q) {
+            double bf[4];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) af[q] = 0.0;
+            for (int i = 0; i < 4; ++i) bf[i] = Ls[(lam + 16 * i) * YLD + 4 * q + g4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(mf[q], bf[i], acc[i], 0, 0, 0);
+        }
     }
-    // 32 columns of M_r-1,j per pass; the next pass's are in flight behind the current pass's product and substitution
-    double bnext[8];
-    auto fetch = [&](int pass) {
-        const int c0 = 32 * pass;
+    PH(3)
+    subst16x4(Lz, dinv, acc);                             // chain q: column 16 wv + g4 + 4 q, its rows lam + 16 i in acc[i][q]
+    if (a.Mt) {                                           // the transpose for the second triangular GEMV: 16 lanes, 128 bytes of a row of Mt
+        double* dt = a.Mt + ((long)j * CB + 16 * wv + g4) * np + kr + lam;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int e = tid + 256 * u;
-            bnext[u] = j < r ? ld_sc1(M + (kr - CB + (e >> 5)) * np + (long)j * CB + c0 + (e & 31)) : 0.0;
-        }
-    };
-    fetch(0);
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int c0 = 32 * pass;
-        v4d acc[2];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[h][q] = rold[pass][h][q];
-        if (j < r) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { const int e = tid + 256 * u; Bs[e >> 5][e & 31] = bnext[u]; }
-        }
-        __syncthreads();                                  // Bs (and, first pass, Lz) in place; the previous pass is done with Ct
-        PH(2)
-        if (j < r) {
-#pragma unroll
-            for (int q = 0; q < CHOL_KSTEPS(16); ++q) {
-                const int kx = 4 * q + (lane >> 4);
-                acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[q], Bs[kx][c], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[q], Bs[kx][16 + c], acc[1], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int t = 16 * wv + (lane >> 4) + 4 * q;
-                Ct[(16 * h + c) * YLD + t] = acc[h][q];
-            }
-        if (pass == 0) fetch(1);                          // in flight behind the substitution
-        __syncthreads();
-        PH(3)
-        const int rho = tid >> 4, lam = tid & 15;
-        double va[4], vb[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { va[i] = Ct[rho * YLD + lam + 16 * i]; vb[i] = Ct[(16 + rho) * YLD + lam + 16 * i]; }
-        subst16x2(Lz, dinv, va, vb);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { Ct[rho * YLD + lam + 16 * i] = va[i]; Ct[(16 + rho) * YLD + lam + 16 * i] = vb[i]; }
-        __syncthreads();
-        {
-            const int t = tid >> 2, c8 = (tid & 3) * 8;  // row t of the tile, columns c0 + c8 .. + 7
-            const rsrc_t rm = make_rsrc(M + kr * np + (long)j * CB + c0);
-#pragma unroll
-            for (int u = 0; u < 8; u += 2)
-                dag_st2(rm, unsigned((t * np + c8 + u) * 8), make_double2(Ct[(c8 + u) * YLD + t], Ct[(c8 + u + 1) * YLD + t]));
-        }
-        if (a.Mt) {                                       // the transpose for the second triangular GEMV, straight from the staging tile
-            const int cr = tid >> 3, t8 = (tid & 7) * 8;  // 32 rows of Mt (columns of this pass) x 64 entries
-            double* dt = a.Mt + ((long)j * CB + c0 + cr) * np + kr + t8;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) dt[u] = Ct[cr * YLD + t8 + u];
-        }
-        PH(5)
+            for (int q = 0; q < 4; ++q) dt[(long)4 * q * np + 16 * i] = acc[i][q];
     }
+    {
+        // M_rj row-contiguous: the wave turns its 16 x 16 blocks (rows 16 i .., its 16 columns) round in its own LDS; 16 lanes
+        // then store 128 bytes of a row.  Wave-private: the LDS instructions of a wave execute in order, no barrier
+        const rsrc_t rm = make_rsrc(M + kr * np + (long)j * CB);
+        const unsigned voM = unsigned((g4 * np + 16 * wv + lam) * 8);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) Tw[(g4 + 4 * q) * 17 + lam] = acc[i][q];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            double v[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) v[s] = Tw[lam * 17 + g4 + 4 * s];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) dag_stb(rm, voM, unsigned((16 * i + 4 * s) * np * 8), v[s]);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
+    }
+    PH(5)
     drain_stores();
     __syncthreads();
     if (tid == 0) dag_add(dc.at(dc.msdone, r, j), 4);
@@ -1467,7 +1487,7 @@ __host__ __device__ inline DagStep dag_step(int nblk, int k) {
     // is slower: the row-after-row chain of the inverse gets links twice as long)
     s.nMS = k >= 1 ? k : 0;
                                                           // the k tiles of inverse row k - 1, one task each (its updates by the
-                                                          // panels before, then two 32-column passes): row r of the inverse waits
+                                                          // panels before, then the finishing stage): row r of the inverse waits
                                                           // for row r - 1, so more tiles per task would be a longer chain (measured:
                                                           // four tiles per task doubled the build)
     const bool ru = dag_ruform(nblk);
