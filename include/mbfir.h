@@ -529,6 +529,27 @@ int mbfir_test_fold(const double* w, int m, int fold, long* out);
  *     nfix receives the number of replaced pivots; Lh / Ll (optional, n x n) the Cholesky factor.            */
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll);
+/*  mbfir_test_capsolve: the capacitance form of the extended-precision KKT solve (capkkt.hip) stage by stage -- for nlanes
+ *  independent problems (H_w + U' diag(X) U) dx = (a + b) + U' diag(X) t, laid out as a lock-step unit lays its lanes out, exactly the
+ *  launches a solve issues: the factorisation of H_w (M = L^-1), Yt = U M', Zt = Yt M, S = Yt Yt' + X^-1, the factorisation of S
+ *  (Ms), the sum of the pivot counters; then one pass of the solve: rhs_w = a + b, y = M'(M rhs_w), w = U y - t, zeta = Ms'(Ms w),
+ *  dx = y - Zt' zeta.  One problem runs as a single design does, several as a unit (launches sized to kp, a lane's own count read
+ *  from its arena).  np = n rounded up to 64.  Per lane (host arrays of nlanes blocks):
+ *    in:  k (nlanes ints, 1 <= k[b] <= kp), kp (multiple of 64, <= 1024), H (n x n, SPD), U (kp x n; rows from k[b] on are ignored:
+ *         the device holds zero rows there), X (kp; entries from k[b] on ignored), a, b (nrhs x n), t (nrhs x kp; entries from k[b]
+ *         on ignored), nrhs 1 or 2, mask (nlanes ints or NULL: a lane with 0 is switched off), hsolve_form: y by the one-pass
+ *         kernel (1; np <= 1024), by the pair of triangular GEMVs (0), or as a solve of this size would choose (-1);
+ *    in / out: M (np x np), Yt, Zt (kp x np), S, Ms (kp x kp), rhs_w, y, dx (nrhs x np), w, zeta (nrhs x kp), flag (nlanes ints:
+ *         replaced pivots of both factorisations).  They go to the device as the caller filled them and come back after the
+ *         launches: what a masked lane's blocks held on entry they hold on exit.
+ *  Before the launches the hook writes NaN where the kernels claim not to read: the 64 x 64 tiles of M, S and Ms strictly above the
+ *  diagonal (they come back as NaN) and their mirror images in the stored transpose, the ignored entries of X and t, the padding of
+ *  a and b, the split-K slab and the other scratch vectors.  A bad argument is MBFIR_E_ARG with a message, before anything is
+ *  launched. */
+int mbfir_test_capsolve(mbfir_ctx* ctx, int n, int nlanes, const int* k, int kp, int nrhs, int hsolve_form, const int* mask,
+                        const double* H, const double* U, const double* X, const double* a, const double* b, const double* t,
+                        double* M, double* Yt, double* Zt, double* S, double* Ms, double* rhs_w, double* y, double* w,
+                        double* zeta, double* dx, int* flag);
 int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tflops_f64_mfma, double* tflops_f64_valu);
 /* Device time (ms per call, HIP events, averaged over reps) of the Cholesky+inverse phase on a random SPD
  * n x n matrix, and of the Gram launches on a random m x nt matrix -- kernel tuning aid. */

@@ -168,6 +168,8 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _lp, _dp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "mbfir_test_capsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
+                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "mbfir_test_mfma_peak": (C.c_int, [C.c_void_p, _dp, _dp]),
     "mbfir_test_time_kernels": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp]),
 }
@@ -1605,6 +1607,39 @@ def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):
     if factor:
         return xh, xl, nfix.value, np.tril(Lh), np.tril(Ll)
     return xh, xl, nfix.value
+
+
+CAP_SENTINEL = -7.25          # what test_capsolve's output arrays hold on entry (a masked lane's still hold it on return)
+CAPSOLVE_OUT = ("M", "Yt", "Zt", "S", "Ms", "rhs_w", "y", "w", "zeta", "dx")
+
+
+def test_capsolve(H, U, X, a, b, t, k, kp, *, nrhs=None, nlanes=None, mask=None, hsolve_form=-1, sentinel=CAP_SENTINEL, ctx=None):
+    """The capacitance form of the extended-precision KKT solve, stage by stage (mbfir_test_capsolve): nl problems
+    (H + U' diag(X) U) dx = (a + b) + U' diag(X) t run as one lock-step unit (one problem: as a single design).  H: (nl, n, n); U:
+    (nl, kp, n), X: (nl, kp), t: (nl, nrhs, kp), of which lane q's first k[q] rows / entries count; a, b: (nl, nrhs, n); kp: the
+    size the launches carry.  hsolve_form: 1 the one-pass M'(M b), 0 the GEMV pair, -1 a solve's own choice.  Returns a dict of the
+    padded per-lane intermediates CAPSOLVE_OUT -- M (nl, np, np), Yt, Zt (nl, kp, np), S, Ms (nl, kp, kp), rhs_w, y, dx (nl, nrhs,
+    np), w, zeta (nl, nrhs, kp) -- and "flag" (nl replaced-pivot counters), all pre-filled with `sentinel`.  The arguments are
+    checked by the library, not here: a bad one raises ValueError with its message."""
+    ctx = ctx or get_context()
+    H, U, X, a, b, t = [np.ascontiguousarray(v, dtype=np.float64) for v in (H, U, X, a, b, t)]
+    k = np.ascontiguousarray(k, dtype=np.int32).ravel()
+    nl = int(len(k) if nlanes is None else nlanes)
+    n, nv, kp = int(H.shape[-1]), int(a.shape[1] if nrhs is None else nrhs), int(kp)
+    npad, kq, nq, vq = -(-n // 64) * 64, max(kp, 1), max(nl, 1), max(nv, 1)
+    shapes = {"M": (nq, npad, npad), "Yt": (nq, kq, npad), "Zt": (nq, kq, npad), "S": (nq, kq, kq), "Ms": (nq, kq, kq),
+              "rhs_w": (nq, vq, npad), "y": (nq, vq, npad), "w": (nq, vq, kq), "zeta": (nq, vq, kq), "dx": (nq, vq, npad)}
+    out = {name: np.full(shapes[name], float(sentinel)) for name in CAPSOLVE_OUT}
+    flag = np.full(nq, -1, dtype=np.int32)
+    mk = (C.c_int * nq)(*[int(v) for v in mask]) if mask is not None else None
+    rc = load_library().mbfir_test_capsolve(ctx._h, n, nl, k.ctypes.data_as(_ip), kp, nv, int(hsolve_form), mk, _ptr(H), _ptr(U), _ptr(X),
+                                            _ptr(a), _ptr(b), _ptr(t), *[_ptr(out[name]) for name in CAPSOLVE_OUT],
+                                            flag.ctypes.data_as(_ip))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    out["flag"] = flag
+    return out
 
 
 def test_specfact(x, n, ctx=None):

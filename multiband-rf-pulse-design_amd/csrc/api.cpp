@@ -688,6 +688,31 @@ int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const doub
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;
     MBFIR_TRY(ctx, ctx->solver->test_ddsolve(n, k, H, U, X, nrhs, bh, bl, xh, xl, nfix, Lh, Ll));
 }
+int mbfir_test_capsolve(mbfir_ctx* ctx, int n, int nlanes, const int* k, int kp, int nrhs, int hsolve_form, const int* mask,
+                        const double* H, const double* U, const double* X, const double* a, const double* b, const double* t,
+                        double* M, double* Yt, double* Zt, double* S, double* Ms, double* rhs_w, double* y, double* w,
+                        double* zeta, double* dx, int* flag) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_capsolve: " + why; return MBFIR_E_ARG; };
+    // (nothing is allocated, copied or launched before every argument has passed)
+    if (n < 1) return bad("n < 1");
+    if (nlanes < 1 || nlanes > 16) return bad("nlanes must be 1 .. 16");
+    if (nrhs < 1 || nrhs > 2) return bad("nrhs must be 1 or 2");
+    if (kp < 64 || kp > 1024 || kp % 64 != 0) return bad("kp must be a multiple of 64, at most 1024");
+    if (!k || !H || !U || !X || !a || !b || !t || !M || !Yt || !Zt || !S || !Ms || !rhs_w || !y || !w || !zeta || !dx || !flag) return bad("null array");
+    for (int q = 0; q < nlanes; ++q)
+        if (k[q] < 1 || k[q] > kp) return bad("lane " + std::to_string(q) + ": k = " + std::to_string(k[q]) + " is not in 1 .. kp = " + std::to_string(kp));
+    if (hsolve_form < -1 || hsolve_form > 1) return bad("hsolve_form must be -1, 0 or 1");
+    if (hsolve_form == 1 && (n + 63) / 64 * 64 > 1024) return bad("the one-pass M'(M b) takes np <= 1024");
+    try {
+        CapSolveIO io;
+        io.n = n; io.nlanes = nlanes; io.kp = kp; io.nrhs = nrhs; io.hsolve_form = hsolve_form; io.k = k; io.mask = mask;
+        io.H = H; io.U = U; io.X = X; io.a = a; io.b = b; io.t = t;
+        io.M = M; io.Yt = Yt; io.Zt = Zt; io.S = S; io.Ms = Ms; io.rhs_w = rhs_w; io.y = y; io.w = w; io.zeta = zeta; io.dx = dx; io.flag = flag;
+        ctx->solver->test_capsolve(io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_fold(const double* w, int m, int fold, long* out) {
     if (!w || m < 1 || !out) return MBFIR_E_ARG;
     try { Solver::test_fold(w, m, fold, out); } catch (const std::exception&) { return MBFIR_E_HIP; }

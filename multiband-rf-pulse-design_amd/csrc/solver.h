@@ -67,6 +67,16 @@ struct UnitOps {
 enum { UO_LATTICE = 0, UO_PAIR_PASSES, UO_ONE_PASS, UO_D1, UO_USEG, UO_NFOLD, UO_NCHUNK, UO_CGRP, UO_NP, UO_EMPTY_SIDE, UO_SEG,
        UO_HETERO, UO_SEEDS_SHARED, UO_GV_PASSES, UO_GTV_PASSES, UO_LANES, UNIT_OPS_REPORT = 16 };
 
+// Arguments of Solver::test_capsolve (mbfir_test_capsolve of include/mbfir.h, which says what each array holds and checks them)
+struct CapSolveIO {
+    int n = 0, nlanes = 1, kp = 0, nrhs = 1, hsolve_form = -1;
+    const int *k = nullptr, *mask = nullptr;
+    const double *H = nullptr, *U = nullptr, *X = nullptr, *a = nullptr, *b = nullptr, *t = nullptr;
+    double *M = nullptr, *Yt = nullptr, *Zt = nullptr, *S = nullptr, *Ms = nullptr, *rhs_w = nullptr, *y = nullptr, *w = nullptr,
+           *zeta = nullptr, *dx = nullptr;
+    int* flag = nullptr;
+};
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -100,6 +110,9 @@ public:
     void test_unit_ops(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitOps& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
+    // the capacitance form of the extended-precision solve: the launches of its build and of one pass of its solve, for nlanes
+    // problems laid out as a lock-step unit lays them out, every intermediate returned
+    void test_capsolve(const CapSolveIO& io);
     void test_mfma_peak(double* tf_mfma, double* tf_valu);
     void test_time_kernels(int n, int m, int nt, int reps, double* ms_chol, double* ms_gram);
     void* stream() const;

@@ -4500,6 +4500,124 @@ void Solver::test_ddsolve(int n, int k, const double* Hh, const double* U, const
         for (int j = 0; j < n; ++j) { xh[(size_t)v * n + j] = B[v * ldv + j]; xl[(size_t)v * n + j] = Bl[v * ldv + j]; }
 }
 
+// The capacitance form of the extended-precision solve as build_H and one pass of kkt_solve_dd launch it (mbfir_test_capsolve checks
+// the arguments).  One arena per lane, lanes lane_bytes apart, kcnt and the pivot counters in the lane's arena, the mask in lane 0's.
+// A single problem runs as a single design does (no lane stride, no kcnt, the launches carry its own k); several run as a unit (the
+// launches carry kp, every lane reads its own count).  Before the launches NaN goes where the kernels claim not to read: the 64 x 64
+// tiles of M, S and Ms strictly above the diagonal and their mirror images in Mt, X[k .. kp), t[.][k .. kp), a / b[.][n .. np), the
+// split-K slab, the partial vectors of the one-pass M'(M b) and the GEMV pair's intermediate.  The output arrays go to the device
+// as the caller filled them and come back after the launches: what a masked lane's hold on return, it held on entry.
+void Solver::test_capsolve(const CapSolveIO& io) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const SolveSwitches sw = read_switches();
+    chol_set_lose_step(sw.test_lose_flag, S.st);
+    const int nl = io.nlanes, nv = io.nrhs, n = io.n, kp = io.kp;
+    const size_t np = round_up(n, 64), kq = size_t(kp), ldv = np, ldk = kq;
+    const bool fused = io.hsolve_form < 0 ? (hsolve_fused_ok(int(np), 2) && sw.hsolve) : io.hsolve_form == 1;      // (< 0: prepare_lanes' choice)
+    if (fused && !hsolve_fused_ok(int(np), nv)) throw HipError("test_capsolve: the one-pass M'(M b) does not take this size");
+    size_t top = 0;
+    auto take = [&](size_t c) { const size_t o = top; top += (c + 7) & ~size_t(7); return o; };
+    const size_t oH = take(np * np), oM = take(np * np), oMt = take(np * np), oW1 = take(np * np + 65 * np);
+    const size_t oU = take(kq * np), oX = take(kq), oYt = take(kq * np), oZt = take(kq * np), oS = take(kq * kq), oMs = take(kq * kq);
+    const size_t oW1s = take(kq * kq + 65 * kq), nPart = cap_part_doubles(kp, int(np)), oPart = take(nPart);
+    const size_t nHs = hsolve_part_doubles(int(std::max(fused ? np : size_t(0), kq))), oHs = take(nHs);
+    const size_t oA = take(2 * ldv), oB = take(2 * ldv), oRw = take(2 * ldv), oYn = take(2 * ldv), oY = take(2 * ldv), oDx = take(2 * ldv);
+    const size_t oT = take(2 * ldk), oW = take(2 * ldk), oZeta = take(2 * ldk), oInt = take(16 + MAX_LANES);
+    const size_t oSk = take(kq * kq);                       // S as the build left it (the factorisation works in place: its S is scratch on exit)
+    const size_t lane_bytes = top * 8;
+    enum { I_FLAG = 0, I_CAPFLAG = 4, I_KCNT = 8, I_MASK = 16 };
+    DevBuf arena(lane_bytes * nl);
+    double* base = arena.as<double>();
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::vector<double> img(top);
+    // (tile (I, J) of a q x q matrix, I < J: above the diagonal; below = its mirror image, what Mt keeps of it)
+    auto poison_tiles = [&](double* A, size_t q, bool above, bool below) {
+        for (size_t i = 0; i < q; ++i)
+            for (size_t j = 0; j < q; ++j)
+                if ((above && j / 64 > i / 64) || (below && j / 64 < i / 64)) A[i * q + j] = nan;
+    };
+    auto rows_in = [&](size_t o, size_t ld, const double* src, size_t rows, size_t cols, size_t keep) {       // rows x cols -> stride ld; NaN from `keep` to ld
+        for (size_t r = 0; r < rows; ++r)
+            for (size_t j = 0; j < ld; ++j) img[o + r * ld + j] = j < std::min(cols, keep) ? src[r * cols + j] : nan;
+    };
+    for (int b = 0; b < nl; ++b) {
+        const size_t kb = size_t(io.k[b]);
+        std::fill(img.begin(), img.end(), 0.0);
+        for (size_t i = 0; i < np; ++i) img[oH + i * np + i] = 1.0;
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < n; ++j) img[oH + i * np + j] = io.H[((size_t)b * n + i) * n + j];
+        std::copy(io.M + b * np * np, io.M + (b + 1) * np * np, img.begin() + oM);
+        poison_tiles(&img[oM], np, true, false);
+        poison_tiles(&img[oMt], np, true, true);            // (the factorisation writes the tiles above its diagonal, nobody the ones below)
+        for (size_t r = 0; r < kb; ++r)
+            for (int j = 0; j < n; ++j) img[oU + r * np + j] = io.U[((size_t)b * kq + r) * n + j];
+        rows_in(oX, kq, io.X + b * kq, 1, kq, kb);
+        std::copy(io.Yt + b * kq * np, io.Yt + (b + 1) * kq * np, img.begin() + oYt);
+        std::copy(io.Zt + b * kq * np, io.Zt + (b + 1) * kq * np, img.begin() + oZt);
+        std::copy(io.S + b * kq * kq, io.S + (b + 1) * kq * kq, img.begin() + oS);
+        std::copy(io.Ms + b * kq * kq, io.Ms + (b + 1) * kq * kq, img.begin() + oMs);
+        poison_tiles(&img[oS], kq, true, false);
+        poison_tiles(&img[oMs], kq, true, false);
+        std::fill(img.begin() + oPart, img.begin() + oPart + nPart, nan);
+        std::fill(img.begin() + oHs, img.begin() + oHs + nHs, nan);
+        std::fill(img.begin() + oYn, img.begin() + oYn + 2 * ldv, nan);
+        rows_in(oA, ldv, io.a + (size_t)b * nv * n, nv, n, n);
+        rows_in(oB, ldv, io.b + (size_t)b * nv * n, nv, n, n);
+        rows_in(oT, ldk, io.t + (size_t)b * nv * kq, nv, kq, kb);
+        const struct { size_t o, ld; double* p; } vecs[] = {{oRw, ldv, io.rhs_w}, {oY, ldv, io.y}, {oDx, ldv, io.dx}, {oW, ldk, io.w}, {oZeta, ldk, io.zeta}};
+        for (const auto& v : vecs) std::copy(v.p + (size_t)b * nv * v.ld, v.p + (size_t)(b + 1) * nv * v.ld, img.begin() + v.o);
+        int* ints = reinterpret_cast<int*>(&img[oInt]);
+        ints[I_FLAG] = io.flag[b]; ints[I_KCNT] = int(kb);
+        if (b == 0 && io.mask) for (int q = 0; q < nl; ++q) ints[I_MASK + q] = io.mask[q];
+        MBFIR_HIP(hipMemcpy(reinterpret_cast<char*>(base) + b * lane_bytes, img.data(), lane_bytes, hipMemcpyHostToDevice));
+    }
+    double *dH = base + oH, *dM = base + oM, *dMt = base + oMt, *dW1 = base + oW1, *dU = base + oU, *dX = base + oX, *dYt = base + oYt, *dZt = base + oZt;
+    double *dS = base + oS, *dMs = base + oMs, *dW1s = base + oW1s, *dPart = base + oPart, *dHs = base + oHs, *dA = base + oA, *dB = base + oB;
+    double *dRw = base + oRw, *dYn = base + oYn, *dY = base + oY, *dDx = base + oDx, *dT = base + oT, *dW = base + oW, *dZeta = base + oZeta;
+    int* dint = reinterpret_cast<int*>(base + oInt);
+    const int* mask = io.mask ? dint + I_MASK : nullptr;
+    const bool unit = nl > 1;
+    const size_t lb = unit ? lane_bytes : 0;
+    const int* kcnt = unit ? dint + I_KCNT : nullptr;
+    const int k = unit ? kp : io.k[0];
+    // build_H's capacitance branch
+    chol_inv_launch(dH, dM, fused ? nullptr : dMt, dW1, int(np), dint + I_FLAG, S.st, sw.chol_split, sw.poison, nullptr, nullptr, nullptr, nl, lb, mask);
+    cap_build_launch(dU, k, kp, int(np), dM, dX, dYt, dZt, dS, dPart, S.st, nl, lb, mask, kcnt);
+    MBFIR_HIP(hipMemcpy2DAsync(base + oSk, lane_bytes, dS, lane_bytes, kq * kq * 8, nl, hipMemcpyDeviceToDevice, S.st));
+    chol_inv_launch(dS, dMs, nullptr, dW1s, kp, dint + I_CAPFLAG, S.st, sw.chol_split, sw.poison, nullptr, nullptr, nullptr, nl, lb, mask);
+    cap_flag_add_launch(dint + I_FLAG, dint + I_CAPFLAG, S.st, nl, lb, mask);
+    // one pass of kkt_solve_dd's capacitance branch
+    cap_add_launch(dA, dB, dRw, n, int(np), int(ldv), nv, S.st, nl, lane_bytes, mask);
+    if (fused) {
+        hsolve_launch(dM, int(np), dRw, nullptr, dY, dHs, nv, int(ldv), S.st, nl, lane_bytes, mask);
+    } else {
+        trigemv_launch(dM, int(np), 0, dRw, dYn, nv, int(ldv), S.st, nullptr, nl, lane_bytes, mask);
+        trigemv_launch(dMt, int(np), 1, dYn, dY, nv, int(ldv), S.st, nullptr, nl, lane_bytes, mask);
+    }
+    cap_uy_launch(dU, k, kp, n, int(np), dY, int(ldv), dT, dW, int(ldk), nv, S.st, nl, lane_bytes, mask, kcnt);
+    hsolve_launch(dMs, kp, dW, nullptr, dZeta, dHs, nv, int(ldk), S.st, nl, lane_bytes, mask);
+    cap_dx_launch(dZt, k, n, int(np), dZeta, int(ldk), dY, dDx, int(ldv), nv, S.st, nl, lane_bytes, mask, kcnt);
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    for (int b = 0; b < nl; ++b) {
+        MBFIR_HIP(hipMemcpy(img.data(), reinterpret_cast<char*>(base) + b * lane_bytes, lane_bytes, hipMemcpyDeviceToHost));
+        std::copy(img.begin() + oM, img.begin() + oM + np * np, io.M + b * np * np);
+        std::copy(img.begin() + oYt, img.begin() + oYt + kq * np, io.Yt + b * kq * np);
+        std::copy(img.begin() + oZt, img.begin() + oZt + kq * np, io.Zt + b * kq * np);
+        std::copy(img.begin() + oSk, img.begin() + oSk + kq * kq, io.S + b * kq * kq);
+        std::copy(img.begin() + oMs, img.begin() + oMs + kq * kq, io.Ms + b * kq * kq);
+        const struct { size_t o, ld; double* p; } vecs[] = {{oRw, ldv, io.rhs_w}, {oY, ldv, io.y}, {oDx, ldv, io.dx}, {oW, ldk, io.w}, {oZeta, ldk, io.zeta}};
+        for (const auto& v : vecs) std::copy(img.begin() + v.o, img.begin() + v.o + nv * v.ld, v.p + (size_t)b * nv * v.ld);
+        io.flag[b] = reinterpret_cast<const int*>(&img[oInt])[I_FLAG];
+        if (fused || (io.mask && !io.mask[b])) continue;
+        // the stored transpose (what the second triangular GEMV read) against the inverse factor
+        for (size_t i = 0; i < np; ++i)
+            for (size_t j = 0; j <= i; ++j)
+                if (img[oM + i * np + j] != img[oMt + j * np + i]) throw HipError("test_capsolve: the stored transpose differs from the inverse factor");
+    }
+}
+
 void Solver::test_specfact(int n, const double* x, double* h_re, double* h_im) {
     Impl& S = *impl;
     MBFIR_HIP(hipSetDevice(S.device));
