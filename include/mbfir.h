@@ -520,6 +520,50 @@ int mbfir_test_specfact(mbfir_ctx* ctx, int n, const double* x, double* h_re, do
 int mbfir_test_unit_ops(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int nv, int ldx, int ldr, int ldh,
                         const double* v, const double* u, const double* sub, const double* s, const double* z, const int* mask,
                         double* gv, double* gtu, double* wgv, double* H, long* report, double* tmin);
+/*  mbfir_test_unit_cone: the cone stages of ONE iteration of a lock-step unit -- the njobs designs of `jobs` as its lanes, a single
+ *  design as a unit of one -- at an iterate the caller chooses.  The unit is set up as for mbfir_test_unit_ops.  Everything the three
+ *  KKT solves of an iteration would have produced is an INPUT, uploaded into the buffers the solves write; the hook then launches the
+ *  stages an iteration launches between its solves, in its order: NT scaling; predictor tail (dtau_a, dkappa_a, W^-1 ds_a, W dz_a,
+ *  step maxima); combined right-hand side (alpha_a, sigma, bx, lam \ (...), bz, W^-2 bz); combined tail (dtau, dkappa, ds, dz, step
+ *  maxima); then either the update (corrector = 0) or the corrector right-hand side (alpha_0, bz_k, W^-2 bz_k) and the corrector tail
+ *  (candidate sums, its dtau_c, dkappa_c, ds_k, dz_k, the pick, the update along the direction picked); last the initial point's cone
+ *  shift of one more vector.  form: 0 = the kernels a solve on one rank launches (MBFIR_FUSE and MBFIR_CORR_BIG read from the
+ *  environment), 1 = the two-phase folding kernels of a row-sharded solve (k_scal_dtau / k_scal_step phases 0 and 1, the all-reduce
+ *  between them being the identity).  ldx >= the unit's largest N, ldr >= its largest R, ldw = 4 max(n_q3, 1); rows are ordered as
+ *  the program's: l orthant rows, n_q3 cones of three rows, then the big cone; entries past a lane's own N / R are ignored.  Per
+ *  lane b (host arrays of njobs blocks):
+ *    in_r (13 + 1 rows of ldr): [0] s, [1] z (a strictly interior pair), [2] rz, [3..4] bz2 (the two right-hand sides whose W^-2
+ *         products the scaling fuses), [5] z1, [6] z2, [7] g1 = G x1, [8] g2 = G x2 (batch solve), [9] zc, [10] gc (combined solve),
+ *         [11] kz, [12] kg (corrector solve), [13] the vector of the cone shift;
+ *    in_x (6 rows of ldx): [0] x, [1] rx, [2] x1, [3] x2, [4] xc, [5] kx;
+ *    in_sc (8): tau, kappa, mu, S_RT (the residual of the tau equation), S_SIGMAX (cap on sigma), S_DRES, S_NRMC (||c||), S_RNC
+ *         (residual norm of the corrector solve);
+ *    mask (njobs ints or NULL): a lane with 0 is switched off, as a finished design is in a solve;
+ *    in / out -- out_r (22 rows of ldr): [0] dl = z/s, [1] wl = sqrt(s/z) (orthant rows only), [2] lam, [3..4] W^-2 bz2 (orthant and
+ *         3-row cones), [5] the big cone's w (w0, w1; `big` entries), [6] W^-1 ds_a, [7] W dz_a, [8] lds, [9] bz of the combined
+ *         system, [10] its W^-2 bz (orthant and 3-row cones), [11] ds, [12] dz, [13] bz_k, [14] its W^-2 (orthant and 3-row cones),
+ *         [15] z2 + kz, [16] g2 + kg, [17] ds_k, [18] dz_k, [19] s and [20] z after the update, [21] the shifted vector;
+ *         out_x (3 rows of ldx): [0] bx of the combined system, [1] xc + kx, [2] x after the update;
+ *         out_w3 (ldw): (eta, w0, w1, w2) per 3-row cone;
+ *         out_sc (7 snapshots of 24, taken after: scaling, predictor tail, combined right-hand side, combined tail, corrector
+ *         right-hand side, update / corrector tail, shift): [0] eta of the big cone, [1] tau, [2] kappa, [3] sigma, [4] alpha,
+ *         [5] alpha_a, [6] dtau, [7] dkappa, [8] dtau_a, [9] dkappa_a, [10] S_TMAX, [11] tau and [12] kappa as the fused update
+ *         reads them, [13] alpha_0, [14] dtau_c, [15] dkappa_c, [16] S_PICK, [17] S_NCORR, [18] S_NPICK, [19] w0 of the big cone,
+ *         [20] mu, [21..23] the mailbox RB[0..2].
+ *         Every out block goes to the device as the caller filled it, right before the stage that writes it, and comes back right
+ *         after that stage: entries no kernel writes (rows past the ones named above, padding) and ALL blocks of a masked lane hold
+ *         on exit what they held on entry; so do the blocks and snapshots of stages that did not run (corrector = 0: out_r
+ *         [13..18], out_x [1], snapshot 4).  The blocks a kernel updates IN PLACE (out_r [15], [16], [19], [20], [21], out_x [1], [2])
+ *         hold the lane's input on a live lane when their stage starts, so their entries past the lane's own N / R return the
+ *         input's padding; on a masked lane they too hold the caller's block.  out_sc of a masked lane is not written.
+ *    report (16 longs): [0] cone blocks, [1] l, [2] n_q3, [3] big, [4] N, [5] R (the unit's largest), [6] heterogeneous unit,
+ *         [7] lanes, [8] MBFIR_FUSE, [9] MBFIR_CORR_BIG, [10] form, [11] rows of step maxima the affine and [12] the combined
+ *         direction folded, [13] blocks of the update.
+ *  Row-sharded units and units on the extended-precision path (opts.ddkkt >= 0 for fir_qp_cvx) are MBFIR_E_ARG with a message, as
+ *  is a bad argument.  The context stays usable for solves. */
+int mbfir_test_unit_cone(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int form, int corrector, int ldx, int ldr,
+                         int ldw, const int* mask, const double* in_r, const double* in_x, const double* in_sc, double* out_r, double* out_x,
+                         double* out_w3, double* out_sc, long* report);
 /*  mbfir_test_fold: the host-side analysis of a frequency grid w[m] for the lattice kernels (no GPU, no context): pairs
  *  +w / -w (fold != 0), cuts the folded list into equally spaced runs.  out[6]: lattice usable, folded entries, pairs,
  *  runs, longest run, self-check failures (must be 0).  (Own addition; nothing in the reference corresponds.) */

@@ -166,6 +166,8 @@ SYMBOLS = {
     "mbfir_test_specfact": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "mbfir_test_unit_ops": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int,
                                       _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _lp, _dp]),
+    "mbfir_test_unit_cone": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                       _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _lp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "mbfir_test_capsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
@@ -951,6 +953,50 @@ def test_unit_ops(jobs, v, u, s, z, *, sub=None, mask=None, opts=None, init=None
     rep = {k: int(x) for k, x in zip(UNIT_OPS_REPORT, report)}
     rep["tmin"] = float(tmin[0])
     return gv, gtu, wgv, H, rep
+
+
+# the blocks of mbfir_test_unit_cone (include/mbfir.h): names of the rows of in_r / in_x / in_sc and out_r / out_x / out_sc
+UNIT_CONE_IN_R = ("s", "z", "rz", "bz2a", "bz2b", "z1", "z2", "g1", "g2", "zc", "gc", "kz", "kg", "shift")
+UNIT_CONE_IN_X = ("x", "rx", "x1", "x2", "xc", "kx")
+UNIT_CONE_IN_SC = ("tau", "kappa", "mu", "rt", "sigmax", "dres", "nrmc", "rnc")
+UNIT_CONE_OUT_R = ("dl", "wl", "lam", "wbz2a", "wbz2b", "wbb", "dssa", "wdza", "lds", "bzc", "wbzc", "ds", "dz", "kbz", "wbzk", "kzsum", "kgsum",
+                   "kds", "kdz", "s", "z", "shift")
+UNIT_CONE_OUT_X = ("bxc", "kxsum", "x")
+UNIT_CONE_SNAPS = ("scaling", "pred", "comb_rhs", "comb", "corr_rhs", "update", "shift")
+UNIT_CONE_SC = ("etab", "tau", "kappa", "sigma", "alpha", "alpha_a", "dtau", "dkap", "dtau_a", "dkap_a", "tmax", "tau0", "kap0", "alpha0",
+                "dtau_c", "dkap_c", "pick", "ncorr", "npick", "wb0", "mu", "rb0", "rb1", "rb2")
+UNIT_CONE_REPORT = ("cone_blocks", "l", "nq3", "big", "N", "R", "hetero", "lanes", "fuse", "corr_big", "form", "ns_affine", "ns_combined",
+                    "update_blocks")
+
+
+def test_unit_cone(jobs, in_r, in_x, in_sc, nq3, *, form=0, corrector=False, mask=None, opts=None, sentinel=np.nan, ctx=None):
+    """The cone stages of one iteration of a lock-step unit at a caller's iterate (mbfir_test_unit_cone, which says what every
+    block holds).  jobs: (designer, args) pairs, the lanes.  in_r: (lanes, 14, R), in_x: (lanes, 6, N), in_sc: (lanes, 8), rows
+    named by UNIT_CONE_IN_*; a lane shorter than the unit's largest is zero-padded by the caller; nq3: the unit's largest count of
+    3-row cones.  Every output block goes in
+    filled with `sentinel`.  Returns a dict: out_r (lanes, 22, R), out_x (lanes, 3, N), w3 (lanes, max(nq3, 1), 4), sc (lanes, 7,
+    24) -- rows named by UNIT_CONE_OUT_R / _OUT_X / _SNAPS x _SC -- and report (a dict of UNIT_CONE_REPORT)."""
+    ctx = ctx or get_context()
+    arr, keep = _pack_jobs(jobs)
+    in_r, in_x, in_sc = [np.ascontiguousarray(a, dtype=np.float64) for a in (in_r, in_x, in_sc)]
+    nl, R, N = len(jobs), in_r.shape[2], in_x.shape[2]
+    if in_r.shape != (nl, len(UNIT_CONE_IN_R), R) or in_x.shape != (nl, len(UNIT_CONE_IN_X), N) or in_sc.shape != (nl, len(UNIT_CONE_IN_SC)):
+        raise ValueError("in_r, in_x, in_sc have inconsistent shapes")
+    lib = load_library()
+    ldw = 4 * max(int(nq3), 1)
+    out_r = np.full((nl, len(UNIT_CONE_OUT_R), R), sentinel)
+    out_x = np.full((nl, len(UNIT_CONE_OUT_X), N), sentinel)
+    w3 = np.full((nl, ldw // 4, 4), sentinel)
+    sc = np.full((nl, len(UNIT_CONE_SNAPS), len(UNIT_CONE_SC)), sentinel)
+    mk = (C.c_int * nl)(*[int(m) for m in mask]) if mask is not None else None
+    report = np.zeros(16, dtype=np.int64)
+    o = opts if opts is not None else make_opts()
+    rc = lib.mbfir_test_unit_cone(ctx._h, arr, nl, C.byref(o), int(form), int(bool(corrector)), N, R, ldw, mk, _ptr(in_r), _ptr(in_x),
+                                  _ptr(in_sc), _ptr(out_r), _ptr(out_x), _ptr(w3), _ptr(sc), report.ctypes.data_as(_lp))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return dict(out_r=out_r, out_x=out_x, w3=w3, sc=sc, report={k: int(x) for k, x in zip(UNIT_CONE_REPORT, report)})
 
 
 def test_chol_lanes(Hs, form=-1, mask=None, ctx=None):

@@ -683,6 +683,32 @@ int mbfir_test_unit_ops(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const 
         return 0;
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
 }
+int mbfir_test_unit_cone(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int form, int corrector, int ldx, int ldr,
+                         int ldw, const int* mask, const double* in_r, const double* in_x, const double* in_sc, double* out_r, double* out_x,
+                         double* out_w3, double* out_sc, long* report) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_unit_cone: " + why; return MBFIR_E_ARG; };
+    if (!jobs || njobs < 1 || !in_r || !in_x || !in_sc || !out_r || !out_x || !out_w3 || !out_sc || !report) return bad("bad argument");
+    if (form < 0 || form > 1) return bad("form must be 0 (the form a solve on one rank runs) or 1 (two-phase)");
+    try {
+        std::vector<TrigProgram> progs(njobs);
+        std::vector<const TrigProgram*> Ps;
+        for (int q = 0; q < njobs; ++q) {
+            std::string e;
+            if (assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e) != 0) return bad("job " + std::to_string(q) + ": " + e);
+            Ps.push_back(&progs[q]);
+        }
+        const SolveOpts so = to_opts(opts, progs[0].which);
+        if (so.shard_size > 1) return bad("row-sharded units are not taken");
+        if (so.ddkkt_theta > 0) return bad("units on the extended-precision path are not taken (opts.ddkkt = -1 for fir_qp_cvx)");
+        UnitCone io;
+        io.form = form; io.corr = corrector != 0; io.ldx = ldx; io.ldr = ldr; io.ldw = ldw; io.mask = mask;
+        io.in_r = in_r; io.in_x = in_x; io.in_sc = in_sc; io.out_r = out_r; io.out_x = out_x; io.out_w3 = out_w3; io.out_sc = out_sc;
+        io.report = report;
+        ctx->solver->test_unit_cone(Ps, so, io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll) {
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;

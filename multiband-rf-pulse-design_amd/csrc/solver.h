@@ -67,6 +67,24 @@ struct UnitOps {
 enum { UO_LATTICE = 0, UO_PAIR_PASSES, UO_ONE_PASS, UO_D1, UO_USEG, UO_NFOLD, UO_NCHUNK, UO_CGRP, UO_NP, UO_EMPTY_SIDE, UO_SEG,
        UO_HETERO, UO_SEEDS_SHARED, UO_GV_PASSES, UO_GTV_PASSES, UO_LANES, UNIT_OPS_REPORT = 16 };
 
+// Arguments of Solver::test_unit_cone (mbfir_test_unit_cone of include/mbfir.h, which says what each block holds): host arrays of
+// nlanes blocks each.  in_r / out_r: UC_IN_R / UC_OUT_R rows of ldr, in_x / out_x: UC_IN_X / UC_OUT_X rows of ldx, out_w3: ldw,
+// in_sc: UC_IN_SC scalars, out_sc: UC_SNAPS snapshots of UC_SC scalars
+enum { UCR_S = 0, UCR_Z, UCR_RZ, UCR_BZ2 /* two rows */, UCR_Z1 = UCR_BZ2 + 2, UCR_Z2, UCR_G1, UCR_G2, UCR_ZC, UCR_GC, UCR_KZ, UCR_KG, UCR_SHIFT, UC_IN_R };
+enum { UCX_X = 0, UCX_RX, UCX_X1, UCX_X2, UCX_XC, UCX_KX, UC_IN_X };
+enum { UCO_DL = 0, UCO_WL, UCO_LAM, UCO_WBZ2 /* two rows */, UCO_WBB = UCO_WBZ2 + 2, UCO_DSSA, UCO_WDZA, UCO_LDS, UCO_BZC, UCO_WBZC, UCO_DS, UCO_DZ,
+       UCO_KBZ, UCO_WBZK, UCO_KZ, UCO_KG, UCO_KDS, UCO_KDZ, UCO_S, UCO_Z, UCO_SHIFT, UC_OUT_R };
+enum { UCOX_BXC = 0, UCOX_KX, UCOX_X, UC_OUT_X };
+enum { UCS_SCALING = 0, UCS_PRED, UCS_COMB_RHS, UCS_COMB, UCS_CORR_RHS, UCS_UPDATE, UCS_SHIFT, UC_SNAPS };
+enum { UC_IN_SC = 8, UC_SC = 24, UNIT_CONE_REPORT = 16 };
+struct UnitCone {
+    int form = 0, corr = 0, ldx = 0, ldr = 0, ldw = 0;
+    const int* mask = nullptr;
+    const double *in_r = nullptr, *in_x = nullptr, *in_sc = nullptr;
+    double *out_r = nullptr, *out_x = nullptr, *out_w3 = nullptr, *out_sc = nullptr;
+    long* report = nullptr;
+};
+
 // Arguments of Solver::test_capsolve (mbfir_test_capsolve of include/mbfir.h, which says what each array holds and checks them)
 struct CapSolveIO {
     int n = 0, nlanes = 1, kp = 0, nrhs = 1, hsolve_form = -1;
@@ -108,6 +126,9 @@ public:
     // the operators of one lock-step unit (a unit of one included) at a caller's (s, z), through the stages and launch code of
     // solve_lanes: G v, G'u, W^-2 G v - sub and the normal matrix as build_H leaves it ahead of its factorisation
     void test_unit_ops(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitOps& io);
+    // the cone stages of one iteration of a lock-step unit (a unit of one included) at a caller's iterate, through the stages of
+    // launch_iteration, with the caller's "solutions" in place of the KKT solves
+    void test_unit_cone(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitCone& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
     // the capacitance form of the extended-precision solve: the launches of its build and of one pass of its solve, for nlanes

@@ -3811,28 +3811,30 @@ struct Solver::Impl {
         }
         P.mask = live_row;
     }
-    // the cone products of direction (xx2, zz2) with the predictor's z1 = dz2; row-sharded: summed over the ranks (k_scal_dtau).
-    // Returns the number of partial rows (unsharded: k_dir_post folds them itself)
-    int dots(const double* xx2, const double* zz2, int mode) {
+    // the cone products of direction (xx2, zz2) with the predictor's z1 = dz2; two-phase form (row-sharded solves; test_unit_cone on
+    // request): folded by k_scal_dtau and summed over the ranks.  Returns the number of partial rows (otherwise k_dir_post folds them itself)
+    // (`two`: -1 = the form of this solve, two-phase where it is row-sharded; 0 / 1 as asked)
+    bool two_phase(int two) const { return two < 0 ? shard_size > 1 : two != 0; }
+    int dots(const double* xx2, const double* zz2, int mode, int two = -1) {
         hipLaunchKernelGGL(k_dots_r, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, dz2, zz2, partR);
         int nb = std::max(nbC, 1);
         if (P.big) {
             hipLaunchKernelGGL(k_big_dots, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, dz2, zz2, scratch, partR);
             nb += 1;
         }
-        if (shard_size > 1) {
-            hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 0);
+        if (two_phase(two)) {
+            hipLaunchKernelGGL(k_scal_dtau, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 0);
             allreduce(RB, 3, 0);
-            hipLaunchKernelGGL(k_scal_dtau, dim3(1), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 1);
+            hipLaunchKernelGGL(k_scal_dtau, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, dx2, xx2, partR, nb, mode, RB, 1);
         }
         return nb;
     }
     // the direction's ds / dz and step maxima; the maxima go to partR2 (k_dir_post reads the k_dots_r partials in partR while it
     // writes them).  Returns the number of partial rows
-    int dir_post(const double* xx2, const double* zz2, const double* gg2, double* outA, double* outB, int mode, int ndots) {
+    int dir_post(const double* xx2, const double* zz2, const double* gg2, double* outA, double* outB, int mode, int ndots, int two = -1) {
         int nb = std::max(nbC, 1);
         hipLaunchKernelGGL(k_dir_post, lane_grid(dim3(nb), nlanes), dim3(256), 0, st, P, wl, w3, lam, dz2, zz2, gdx2, gg2, rz, Sc, outA, outB,
-                           partR2, mode, shard_size > 1 ? nullptr : partR, ndots, xx2);
+                           partR2, mode, two_phase(two) ? nullptr : partR, ndots, xx2);
         if (P.big) {
             hipLaunchKernelGGL(k_big_dir_post, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, dz2, zz2, gdx2, gg2, rz, Sc, outA, outB,
                                scratch, partR2, mode);
@@ -3840,21 +3842,68 @@ struct Solver::Impl {
         }
         return nb;
     }
-    // k_scal_step on the step maxima of dir_post: row-sharded in two phases around an all-reduce, otherwise (where `unsharded`) in one
-    void scal_step(int mode, int nb, bool unsharded) {
-        if (shard_size > 1) {
-            hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 0);
+    // k_scal_step on the step maxima of dir_post: in the two-phase form around an all-reduce, otherwise (where `unsharded`) in one
+    void scal_step(int mode, int nb, bool unsharded, int two = -1) {
+        if (two_phase(two)) {
+            hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 0);
             allreduce(RB, 2, 1);
-            hipLaunchKernelGGL(k_scal_step, dim3(1), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 1);
+            hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 1);
         } else if (unsharded) {
             hipLaunchKernelGGL(k_scal_step, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, partR2, nb, mode, rx, bxc, RB, 2);
         }
     }
-    // The body of an iteration: the head (unless it went out ahead of the verdicts), predictor, combined direction, update or corrector
+    // ---- the cone stages of an iteration, between its KKT solves (launch_iteration; test_unit_cone runs the same stages with the
+    // solutions uploaded in place of the solves).  `two`: the two-phase form of the folding kernels.
+    // predictor tail: dtau / dkappa of the affine direction, its scaled ds / dz and step maxima (two-phase: also alpha_a, sigma, bx).
+    // Returns the number of rows of step maxima
+    int stage_pred_tail(bool two) {
+        double *x2a = dx2 + P.LDV, *z2a = dz2 + P.Rp, *g2a = gdx2 + P.Rp;
+        const int nd0 = dots(x2a, z2a, 0, two);
+        const int ns0 = dir_post(x2a, z2a, g2a, dssa, wdza, 0, nd0, two);
+        scal_step(0, ns0, false, two);
+        return ns0;
+    }
+    // combined right-hand side (one-phase: sigma and bx are formed inside k_comb_rhs; W^-2 bz comes with it)
+    void stage_comb_rhs(int ns0, bool two) {
+        hipLaunchKernelGGL(k_comb_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, lam, dssa, wdza, rz, Sc,
+                           lds, bzc, two ? nullptr : partR2, ns0, rx, bxc, dl, wbz);
+        if (P.big)
+            hipLaunchKernelGGL(k_big_comb_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, dssa, wdza, rz, Sc, lds, bzc, scratch);
+    }
+    // combined tail: dtau / dkappa, ds, dz and the step maxima of the combined direction.  Returns the number of rows of maxima
+    int stage_comb_tail(bool two) {
+        const int nd1 = dots(dxc, dzc, 1, two);
+        return dir_post(dxc, dzc, gdxc, ds, dz, 1, nd1, two);
+    }
+    int unknown_blocks() const { return cdiv(std::max(P.N, P.R), 256); }
+    // update along the combined direction (sw.fuse, one-phase: k_update forms the step length itself)
+    void stage_update(int ns1, bool two) {
+        scal_step(1, ns1, !sw.fuse, two);
+        hipLaunchKernelGGL(k_update, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, x, ds, dz, s, z,
+                           (!two && sw.fuse) ? (const double*)partR2 : (const double*)nullptr, ns1);
+    }
+    // corrector right-hand side: the step of the predictor-corrector direction is measured but not taken (k_scal_step mode 2); the
+    // orthant rows' products at the trial step alpha0 + CORR_DELTA, projected onto the box around sigma mu, give one more right-hand
+    // side for the factorisation at hand
+    void stage_corr_rhs(int ns1, int corr_cones, const int* corr_ddm, bool two) {
+        scal_step(2, ns1, true, two);
+        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz);
+        if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, ds, dz, Sc, kbz, scratch, corr_cones, corr_ddm);
+    }
+    // corrector tail: the candidate (predictor-corrector + corrector solution) gets its own direction and step (mode 3: own dtau /
+    // dkappa slots), k_scal_step picks the longer step by CORR_ACCEPT and moves tau, kappa, k_update_pick moves x, s, z along the
+    // direction picked.  Every lane decides for itself.
+    void stage_corr_tail(bool two) {
+        hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
+        const int ndC = dots(kx, kz, 3, two);
+        const int nsC = dir_post(kx, kz, kg, kds, kdz, 3, ndC, two);
+        scal_step(3, nsC, true, two);
+        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z);
+    }
+    // The body of an iteration: the head (unless it went out ahead of the verdicts), then the cone stages with the KKT solves in between
     void launch_iteration(std::vector<LaneHost>& LH, const SolveOpts& o, bool head_out, int nsweep, bool use_corr) {
         if (!head_out) launch_head(LH, o);
-        const bool sharded = shard_size > 1;
-        const int nN = cdiv(std::max(P.N, P.R), 256);
+        const bool two = two_phase(-1);
         bool dd_any = dd_k > 0, pl_any = dd_k == 0;
         if (dd_unit) {
             pl_any = false;
@@ -3862,43 +3911,19 @@ struct Solver::Impl {
         }
         // constant + affine systems in one batch: [x1 z1], [x2 z2]
         solve_modes<2>(dd_any, pl_any, bx2, bz2, dx2, dz2, gdx2, S_RNA, nsweep);
-        double *x2a = dx2 + P.LDV, *z2a = dz2 + P.Rp, *g2a = gdx2 + P.Rp;
-        const int nd0 = dots(x2a, z2a, 0);
-        const int ns0 = dir_post(x2a, z2a, g2a, dssa, wdza, 0, nd0);
-        scal_step(0, ns0, false);
-        // combined direction (unsharded: sigma and bx are formed inside k_comb_rhs, and W^-2 bz comes with it)
-        hipLaunchKernelGGL(k_comb_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, lam, dssa, wdza, rz, Sc,
-                           lds, bzc, sharded ? nullptr : partR2, ns0, rx, bxc, dl, wbz);
-        if (P.big)
-            hipLaunchKernelGGL(k_big_comb_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, dssa, wdza, rz, Sc, lds, bzc, scratch);
+        const int ns0 = stage_pred_tail(two);
+        stage_comb_rhs(ns0, two);
         solve_modes<1>(dd_any, pl_any, bxc, bzc, dxc, dzc, gdxc, S_RNB, nsweep);
-        const int nd1 = dots(dxc, dzc, 1);
-        const int ns1 = dir_post(dxc, dzc, gdxc, ds, dz, 1, nd1);
-        if (!use_corr) {
-            scal_step(1, ns1, !sw.fuse);                  // (sw.fuse: k_update forms the step length itself)
-            hipLaunchKernelGGL(k_update, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, x, ds, dz, s, z,
-                               (!sharded && sw.fuse) ? (const double*)partR2 : (const double*)nullptr, ns1);
-            return;
-        }
+        const int ns1 = stage_comb_tail(two);
+        if (!use_corr) { stage_update(ns1, two); return; }
         // ---- one centrality corrector (round 6; oracle/conic_ipm.py solve(): CORR_*) -------------------------------------------
-        // the step of the predictor-corrector direction is measured but not taken (k_scal_step mode 2); the orthant rows' products
-        // at the trial step alpha0 + CORR_DELTA, projected onto the box around sigma mu, give one more right-hand side for the
-        // factorisation at hand; the candidate (predictor-corrector + corrector solution) gets its own direction and step
-        // (mode 3: own dtau / dkappa slots), k_scal_step picks the longer step by CORR_ACCEPT and moves tau, kappa, k_update_pick
-        // moves x, s, z along the direction picked.  Every lane decides for itself.
         // (extended-precision iterations: the corrector works on the orthant rows alone, with the usual passes: oracle/conic_ipm.py)
         const int corr_cones = (!sw.corr_big || (!dd_unit && dd_any)) ? 0 : 1;                 // one design: this iteration's mode ...
         const int* corr_ddm = (dd_unit && dd_any) ? mask_row(ROW_DD) : nullptr;               // ... a unit: lane by lane
-        scal_step(2, ns1, true);
-        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz);
-        if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, ds, dz, Sc, kbz, scratch, corr_cones, corr_ddm);
+        stage_corr_rhs(ns1, corr_cones, corr_ddm, two);
         // the Cholesky solve and its residual norm (S_RNC), no sweeps (lanes on the extended-precision path: their usual passes)
         solve_modes<1>(dd_any, pl_any, kbx, kbz, kx, kz, kg, S_RNC, 0);
-        hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
-        const int ndC = dots(kx, kz, 3);
-        const int nsC = dir_post(kx, kz, kg, kds, kdz, 3, ndC);
-        scal_step(3, nsC, true);
-        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(nN), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z);
+        stage_corr_tail(two);
     }
     // The host's verdicts on the iterate in hostSc; lanes with a new best iterate get xbest = x / tau.  Returns whether any lane goes on.
     bool judge_lanes(std::vector<LaneHost>& LH, const SolveOpts& o, int it) {
@@ -4360,6 +4385,116 @@ void Solver::test_unit_ops(const std::vector<const TrigProgram*>& Qs, const Solv
     r[UO_EMPTY_SIDE] = empty; r[UO_SEG] = P.seg; r[UO_HETERO] = P.dims ? 1 : 0; r[UO_SEEDS_SHARED] = P.seeds_shared;
     r[UO_GV_PASSES] = S.n_gv; r[UO_GTV_PASSES] = S.n_gtv; r[UO_LANES] = nlanes;
     *io.tmin = P.tmin;
+}
+
+// The cone stages of one iteration at a caller's iterate (include/mbfir.h: mbfir_test_unit_cone).  The unit is set up by the stages
+// of solve_lanes (setup_unit); what the three KKT solves of an iteration would have produced is uploaded into the buffers they
+// write, and the stages of launch_iteration run between the uploads exactly as they run between the solves.  Every output buffer
+// holds the caller's sentinel when its stage starts and is read back when the stage ends (a later stage may write it again), the
+// scalars and the mailbox RB with it.
+void Solver::test_unit_cone(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, const UnitCone& io) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int nlanes = int(Qs.size());
+    if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
+    std::vector<LaneHost> LH(nlanes);
+    for (int b = 0; b < nlanes; ++b) LH[b].live = !io.mask || io.mask[b] != 0;
+    S.setup_unit(Qs, o, LH);
+    S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
+    S.timing = false;
+    S.chol_launch_count = 0; S.dd_epoch = 0;
+    S.taps_valid = false;
+    const DProg& P = S.P;
+    if (io.ldx < P.N || io.ldx > P.LDV || io.ldr < P.R || io.ldr > P.Rp || io.ldw != 4 * std::max(P.nq3, 1))
+        throw HipError("test_unit_cone: ldx / ldr / ldw do not fit the unit (N " + std::to_string(P.N) + ", R " + std::to_string(P.R) + ", n_q3 " + std::to_string(P.nq3) + ")");
+    const int two = io.form ? 1 : 0;
+    const size_t ldx = io.ldx, ldr = io.ldr, ldw = io.ldw;
+    auto lane = [&](const double* p, int b) { return reinterpret_cast<double*>(reinterpret_cast<char*>(const_cast<double*>(p)) + (size_t)b * S.lane_bytes); };
+    auto h2d = [&](double* dst, const double* src, size_t n, int b) { MBFIR_HIP(hipMemcpyAsync(lane(dst, b), src, n * sizeof(double), hipMemcpyHostToDevice, S.st)); };
+    auto d2h = [&](double* dst, const double* src, size_t n, int b) { MBFIR_HIP(hipMemcpyAsync(dst, lane(src, b), n * sizeof(double), hipMemcpyDeviceToHost, S.st)); };
+    auto in_r = [&](int b, int row) { return io.in_r + ((size_t)b * UC_IN_R + row) * ldr; };
+    auto in_x = [&](int b, int row) { return io.in_x + ((size_t)b * UC_IN_X + row) * ldx; };
+    auto out_r = [&](int b, int row) { return io.out_r + ((size_t)b * UC_OUT_R + row) * ldr; };
+    auto out_x = [&](int b, int row) { return io.out_x + ((size_t)b * UC_OUT_X + row) * ldx; };
+    // an output of a stage: device buffer, its block in out_r (space 0; `n` entries), out_x (1) or out_w3 (2); inplace: the live lanes'
+    // buffer holds an input of the stage, only the masked lanes get the sentinel
+    struct Out { double* dev; int space, row; bool inplace; size_t n; };
+    auto host_of = [&](const Out& q, int b) { return q.space == 0 ? out_r(b, q.row) : q.space == 1 ? out_x(b, q.row) : io.out_w3 + (size_t)b * ldw; };
+    auto R_ = [&](double* dev, int row, bool inplace = false) { return Out{dev, 0, row, inplace, ldr}; };
+    auto X_ = [&](double* dev, int row, bool inplace = false) { return Out{dev, 1, row, inplace, ldx}; };
+    auto before = [&](const std::vector<Out>& outs) {
+        for (int b = 0; b < nlanes; ++b)
+            for (const Out& q : outs)
+                if (!(q.inplace && LH[b].live)) h2d(q.dev, host_of(q, b), q.n, b);
+    };
+    std::vector<double> snap((size_t)UC_SNAPS * nlanes * (S_COUNT + 3), std::nan(""));
+    std::vector<char> snapped(UC_SNAPS, 0);
+    auto after = [&](const std::vector<Out>& outs, int k) {
+        for (int b = 0; b < nlanes; ++b) {
+            for (const Out& q : outs) d2h(host_of(q, b), q.dev, q.n, b);
+            double* h = snap.data() + ((size_t)k * nlanes + b) * (S_COUNT + 3);
+            d2h(h, S.Sc, S_COUNT, b); d2h(h + S_COUNT, S.RB, 3, b);
+        }
+        snapped[k] = 1;
+    };
+    // ---- inputs: the iterate, the residuals, the three solves' solutions, the scalars ------------------------------------------
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        h2d(S.s, in_r(b, UCR_S), ldr, b); h2d(S.z, in_r(b, UCR_Z), ldr, b); h2d(S.rz, in_r(b, UCR_RZ), ldr, b);
+        h2d(S.bz2, in_r(b, UCR_BZ2), ldr, b); h2d(S.bz2 + P.Rp, in_r(b, UCR_BZ2 + 1), ldr, b);
+        h2d(S.dz2, in_r(b, UCR_Z1), ldr, b); h2d(S.dz2 + P.Rp, in_r(b, UCR_Z2), ldr, b);
+        h2d(S.gdx2, in_r(b, UCR_G1), ldr, b); h2d(S.gdx2 + P.Rp, in_r(b, UCR_G2), ldr, b);
+        h2d(S.dzc, in_r(b, UCR_ZC), ldr, b); h2d(S.gdxc, in_r(b, UCR_GC), ldr, b);
+        h2d(S.kz, in_r(b, UCR_KZ), ldr, b); h2d(S.kg, in_r(b, UCR_KG), ldr, b);
+        h2d(S.tmpR, in_r(b, UCR_SHIFT), ldr, b);
+        h2d(S.x, in_x(b, UCX_X), ldx, b); h2d(S.rx, in_x(b, UCX_RX), ldx, b);
+        h2d(S.dx2, in_x(b, UCX_X1), ldx, b); h2d(S.dx2 + P.LDV, in_x(b, UCX_X2), ldx, b);
+        h2d(S.dxc, in_x(b, UCX_XC), ldx, b); h2d(S.kx, in_x(b, UCX_KX), ldx, b);
+        const double* sc = io.in_sc + (size_t)b * UC_IN_SC;
+        const int slot[UC_IN_SC] = {S_TAU, S_KAPPA, S_MU, S_RT, S_SIGMAX, S_DRES, S_NRMC, S_RNC};
+        for (int q = 0; q < UC_IN_SC; ++q) h2d(S.Sc + slot[q], sc + q, 1, b);
+    }
+    // ---- the stages of launch_iteration, the uploads above in place of its solves ---------------------------------------------------
+    std::vector<Out> outs = {R_(S.dl, UCO_DL), R_(S.wl, UCO_WL), R_(S.lam, UCO_LAM), R_(S.wbz, UCO_WBZ2), R_(S.wbz + P.Rp, UCO_WBZ2 + 1),
+                             Out{S.w3, 2, 0, false, ldw}, Out{S.wbb, 0, UCO_WBB, false, (size_t)std::max(P.big, 1)}};
+    before(outs); S.launch_scaling(); after(outs, UCS_SCALING);
+    outs = {R_(S.dssa, UCO_DSSA), R_(S.wdza, UCO_WDZA)};
+    if (two) outs.push_back(X_(S.bxc, UCOX_BXC));
+    before(outs); const int ns0 = S.stage_pred_tail(two); after(outs, UCS_PRED);
+    outs = {R_(S.lds, UCO_LDS), R_(S.bzc, UCO_BZC), R_(S.wbz, UCO_WBZC)};
+    if (!two) outs.push_back(X_(S.bxc, UCOX_BXC));
+    before(outs); S.stage_comb_rhs(ns0, two); after(outs, UCS_COMB_RHS);
+    outs = {R_(S.ds, UCO_DS), R_(S.dz, UCO_DZ)};
+    before(outs); const int ns1 = S.stage_comb_tail(two); after(outs, UCS_COMB);
+    const std::vector<Out> moved = {X_(S.x, UCOX_X, true), R_(S.s, UCO_S, true), R_(S.z, UCO_Z, true)};
+    if (!io.corr) {
+        before(moved); S.stage_update(ns1, two); after(moved, UCS_UPDATE);
+    } else {
+        outs = {R_(S.kbz, UCO_KBZ), R_(S.wbz, UCO_WBZK)};
+        before(outs); S.stage_corr_rhs(ns1, S.sw.corr_big ? 1 : 0, nullptr, two); after(outs, UCS_CORR_RHS);
+        outs = {X_(S.kx, UCOX_KX, true), R_(S.kz, UCO_KZ, true), R_(S.kg, UCO_KG, true), R_(S.kds, UCO_KDS), R_(S.kdz, UCO_KDZ)};
+        outs.insert(outs.end(), moved.begin(), moved.end());
+        before(outs); S.stage_corr_tail(two); after(outs, UCS_UPDATE);
+    }
+    outs = {R_(S.tmpR, UCO_SHIFT, true)};
+    before(outs); S.cone_shift(S.tmpR); after(outs, UCS_SHIFT);
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    // the scalars of every stage that ran, live lanes only (a masked lane's block stays the caller's)
+    const int pick[UC_SC - 3] = {S_ETAB, S_TAU, S_KAPPA, S_SIGMA, S_ALPHA, S_ALPHA_A, S_DTAU, S_DKAP, S_DTAU_A, S_DKAP_A, S_TMAX, S_TAU0, S_KAP0,
+                                 S_ALPHA0, S_DTAU_C, S_DKAP_C, S_PICK, S_NCORR, S_NPICK, S_WB0, S_MU};
+    for (int k = 0; k < UC_SNAPS; ++k)
+        for (int b = 0; b < nlanes; ++b) {
+            if (!snapped[k] || !LH[b].live) continue;
+            const double* h = snap.data() + ((size_t)k * nlanes + b) * (S_COUNT + 3);
+            double* d = io.out_sc + ((size_t)b * UC_SNAPS + k) * UC_SC;
+            for (int q = 0; q < UC_SC - 3; ++q) d[q] = h[pick[q]];
+            for (int q = 0; q < 3; ++q) d[UC_SC - 3 + q] = h[S_COUNT + q];
+        }
+    long* r = io.report;
+    for (int i = 0; i < UNIT_CONE_REPORT; ++i) r[i] = 0;
+    r[0] = std::max(S.nbC, 1); r[1] = P.l; r[2] = P.nq3; r[3] = P.big; r[4] = P.N; r[5] = P.R; r[6] = P.dims ? 1 : 0; r[7] = nlanes;
+    r[8] = S.sw.fuse ? 1 : 0; r[9] = S.sw.corr_big ? 1 : 0; r[10] = two; r[11] = ns0; r[12] = ns1; r[13] = S.unknown_blocks();
 }
 
 void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {

@@ -84,7 +84,7 @@ def program(fn, args, grid_m=0):
         lib.mbfir_program_free(out)
     assert R == l + 3 * nq3 + big and not np.any((freq >= 0) & (col >= 0))
     return dict(fn=fn, args=args, grid_m=grid_m, Nt=Nt, Ne=Ne, N=Nt + Ne, R=R, l=l, nq3=nq3, big=big, Mf=Mf, quad=bool(quad), w=w, tau=tau,
-                scale=scale, psign=psign, kind=kind, pcol=pcol, freq=freq, col=col, al=al, be=be, ey=ey)
+                scale=scale, psign=psign, kind=kind, pcol=pcol, freq=freq, col=col, al=al, be=be, ey=ey, h=h, c=c)
 
 
 def _rows_from_trig(P, A1, A2, dtype):
