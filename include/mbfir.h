@@ -564,6 +564,45 @@ int mbfir_test_unit_ops(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const 
 int mbfir_test_unit_cone(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int form, int corrector, int ldx, int ldr,
                          int ldw, const int* mask, const double* in_r, const double* in_x, const double* in_sc, double* out_r, double* out_x,
                          double* out_w3, double* out_sc, long* report);
+/*  mbfir_test_unit_kkt: the residual kernels of an iterate and the plain KKT solve [0 G'; G -W^2][dx; dz] = [bx; bz] of ONE lock-step
+ *  unit, group of launches by group of launches.  The unit is set up as for mbfir_test_unit_ops.  In this order:
+ *  (1) the residual kernels at the caller's (x, s, z, tau, kappa): form 0 as a solve on one rank launches them, form 1 the two-phase
+ *      form of a row-sharded solve (the all-reduce between the phases being the identity; the mailbox then sits behind G'z);
+ *  (2) mode 0: the caller's right-hand sides go into the buffers of the batch solve (nv = 2) or the combined solve (nv = 1) -- bx = bz =
+ *      NULL (nv = 2) keeps the two the residual kernels just wrote, (-c, -rx) and (h, s - rz) --, then the NT scaling and the build and
+ *      factorisation of H; then kkt_solve with the lanes' own sweep counts nsweep[b] in 0 .. 8 under the sweep masks.  wbz_ready (nv = 2):
+ *      the entry of an iteration's solves, W^-2 bz from the scaling's fused product and k_big_winv2; otherwise the winv2 entry.
+ *      two: the sweep's update in the two launches of a row-sharded solve.
+ *      mode 1: the initial point itself (unit scaling, build, k_init_rhs, the solve with nv = 2, the copies and the cone shifts).
+ *  Per lane b (host arrays of njobs blocks; ldx >= the unit's largest N, ldr >= its largest R, ldh = np, ldw = 4 max(n_q3, 1)):
+ *    s, z (ldr), x (ldx), tau_kappa (2), bx (nv x ldx), bz (nv x ldr), nsweep, mask (0: the lane is switched off);
+ *    in / out -- res_r (3 rows of ldr): rz, bz2[0], bz2[1]; res_x (4 rows of ldx): G'z, rx, bx2[0], bx2[1]; res_sc (24): S_RT, S_MU,
+ *         S_PCOST, S_DCOST, S_GAP, S_RELGAP, S_PRES, S_DRES, S_PINF, S_DINF, S_CX, S_HZ, S_SZ, S_CHOLFIX, then (out only) tau, kappa,
+ *         ||h||, ||c||, the degree, then the mailbox (5);
+ *         M (np x np): the inverse factor; flag: the pivot-replacement counter;
+ *         out_x (46 blocks of 2 x ldx): [0] G'W^-2 bz, [1] dx after the Cholesky solve, [2] G'dz, [3] r = bx - G'dz, [4 + 2 s], [5 + 2 s]
+ *         p and z of the s-th start (s = 0: before sweep 0; z only where the unfused form writes it), [20 + 3 q .. 22 + 3 q] Hp, dx, r of
+ *         sweep q, [44] dx and [45] r as the solve leaves them;
+ *         out_r (37 blocks of 2 x ldr): [0] W^-2 bz, [1] G dx, [2] dz after the Cholesky solve, [3 + 4 q .. 6 + 4 q] Gp, W^-2 Gp, gdx, dz
+ *         of sweep q, [35] gdx and [36] dz as the solve leaves them;
+ *         out_sc (18 snapshots of 13: after the residual of the Cholesky solve, after start s (8), after sweep q (8), at the end): the
+ *         solve's nine norm slots n_0 .. n_8, S_CG_RZ[2], S_CG_ALPHA[2];
+ *         init_r (7 rows of ldr; mode 1): dl, wl, the big cone's w, s, z, bz2[0], bz2[1]; init_x (3 rows of ldx): x, bx2[0], bx2[1];
+ *         init_w3 (ldw).
+ *         Every block goes to the device as the caller filled it right before the launches that write it and comes back right after
+ *         them: a masked lane returns every block as it was, rows past a lane's own N / R and the blocks of sweeps a lane does not run
+ *         hold the caller's values, as do the norm slots past the lane's count.  Blocks updated in place (dx, r, gdx, dz of a sweep,
+ *         p of a restart) are copied back for the lanes that run the sweep.
+ *    report (24 longs): [0] one-pass M'(M b), [1] MBFIR_FUSE, [2] form, [3] N, [4] R, [5] np, [6] big, [7] lanes, [8] heterogeneous,
+ *         [9] lattice path, [10] workgroups of k_gt_finish, [11] nv, [12] two, [13] wbz_ready, [14] mode, [15] largest sweep count,
+ *         [16] l, [17] n_q3, [18] row blocks of the residual kernel, [19] z is written, [20] G v and [21] G'v passes.
+ *  Row-sharded units and units on the extended-precision path are MBFIR_E_ARG with a message, as is a bad argument.  The context stays
+ *  usable for solves. */
+int mbfir_test_unit_kkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int mode, int form, int two, int wbz_ready,
+                        int nv, int ldx, int ldr, int ldh, int ldw, const int* mask, const int* nsweep, const double* s, const double* z,
+                        const double* x, const double* tau_kappa, const double* bx, const double* bz, double* res_r, double* res_x,
+                        double* res_sc, double* M, long* flag, double* out_x, double* out_r, double* out_sc, double* init_r, double* init_x,
+                        double* init_w3, long* report);
 /*  mbfir_test_fold: the host-side analysis of a frequency grid w[m] for the lattice kernels (no GPU, no context): pairs
  *  +w / -w (fold != 0), cuts the folded list into equally spaced runs.  out[6]: lattice usable, folded entries, pairs,
  *  runs, longest run, self-check failures (must be 0).  (Own addition; nothing in the reference corresponds.) */

@@ -168,6 +168,8 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _lp, _dp]),
     "mbfir_test_unit_cone": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                        _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _lp]),
+    "mbfir_test_unit_kkt": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts)] + [C.c_int] * 9 + [_ip, _ip] + [_dp] * 6 +
+                                     [_dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _lp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "mbfir_test_capsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
@@ -997,6 +999,68 @@ def test_unit_cone(jobs, in_r, in_x, in_sc, nq3, *, form=0, corrector=False, mas
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
     return dict(out_r=out_r, out_x=out_x, w3=w3, sc=sc, report={k: int(x) for k, x in zip(UNIT_CONE_REPORT, report)})
+
+
+# the blocks of mbfir_test_unit_kkt (include/mbfir.h)
+UNIT_KKT_RES_R = ("rz", "bz2a", "bz2b")
+UNIT_KKT_RES_X = ("gtz", "rx", "bx2a", "bx2b")
+UNIT_KKT_RES_SC = ("rt", "mu", "pcost", "dcost", "gap", "relgap", "pres", "dres", "pinf", "dinf", "cx", "hz", "sz", "cholfix", "tau", "kappa",
+                   "nrmh", "nrmc", "deg", "rb0", "rb1", "rb2", "rb3", "rb4")
+UNIT_KKT_OUT_X = (("gtwbz", "dxc", "gtdz", "rc") + tuple("%s%d" % (k, q) for q in range(8) for k in ("p", "z")) +
+                  tuple("%s%d" % (k, q) for q in range(8) for k in ("hp", "dx", "r")) + ("dx_end", "r_end"))
+UNIT_KKT_OUT_R = (("wbz", "gdxc", "dzc") + tuple("%s%d" % (k, q) for q in range(8) for k in ("gp", "wp", "gdx", "dz")) + ("gdx_end", "dz_end"))
+UNIT_KKT_SNAPS = ("resid",) + tuple("start%d" % q for q in range(8)) + tuple("step%d" % q for q in range(8)) + ("end",)
+UNIT_KKT_SC = tuple("n%d" % q for q in range(9)) + ("rz0", "rz1", "alpha0", "alpha1")
+UNIT_KKT_INIT_R = ("dl", "wl", "wbb", "s", "z", "bz2a", "bz2b")
+UNIT_KKT_INIT_X = ("x", "bx2a", "bx2b")
+UNIT_KKT_REPORT = ("fused_hsolve", "fuse", "form", "N", "R", "np", "big", "lanes", "hetero", "lattice", "gt_finish_blocks", "nv", "two",
+                   "wbz_ready", "initial", "nsweep_max", "l", "nq3", "resid_blocks", "z_written", "gv_passes", "gtv_passes")
+
+
+def test_unit_kkt(jobs, s, z, x, tau_kappa, nsweep, nq3, *, bx=None, bz=None, nv=2, initial=False, form=0, two=False, wbz_ready=False,
+                  mask=None, opts=None, sentinel=np.nan, ctx=None):
+    """The residual kernels and the plain KKT solve of a lock-step unit, group of launches by group (mbfir_test_unit_kkt, which says
+    what every block holds).  jobs: (designer, args) pairs, the lanes.  s, z: (lanes, R); x: (lanes, N); tau_kappa: (lanes, 2);
+    nsweep: the lanes' sweep counts; bx: (lanes, nv, N) and bz: (lanes, nv, R), or neither (nv = 2: the right-hand sides the
+    residual kernels leave); nq3: the unit's largest count of 3-row cones.  Every output block goes in filled with `sentinel`.
+    Returns a dict: res_r, res_x, res_sc, M (lanes, np, np), flag, out_x (lanes, 46, 2, N), out_r (lanes, 37, 2, R), sc (lanes, 18, 13),
+    init_r, init_x, w3 (initial=True), rows named by UNIT_KKT_*, and report (a dict of UNIT_KKT_REPORT)."""
+    ctx = ctx or get_context()
+    arr, keep = _pack_jobs(jobs)
+    s, z, x, tk = [np.ascontiguousarray(a, dtype=np.float64) for a in (s, z, x, tau_kappa)]
+    nl, R, N = len(jobs), s.shape[1], x.shape[1]
+    if s.shape != (nl, R) or z.shape != (nl, R) or x.shape != (nl, N) or tk.shape != (nl, 2) or len(nsweep) != nl:
+        raise ValueError("s, z, x, tau_kappa, nsweep have inconsistent shapes")
+    if (bx is None) != (bz is None):
+        raise ValueError("bx and bz go together")
+    if bx is not None:
+        bx, bz = np.ascontiguousarray(bx, dtype=np.float64), np.ascontiguousarray(bz, dtype=np.float64)
+        if bx.shape != (nl, nv, N) or bz.shape != (nl, nv, R):
+            raise ValueError("bx, bz have the wrong shapes")
+    npad = -(-N // 64) * 64
+    ldw = 4 * max(int(nq3), 1)
+    full = lambda *shape: np.full(shape, sentinel, dtype=np.float64)
+    o = dict(res_r=full(nl, len(UNIT_KKT_RES_R), R), res_x=full(nl, len(UNIT_KKT_RES_X), N), res_sc=full(nl, len(UNIT_KKT_RES_SC)),
+             M=full(nl, npad, npad), out_x=full(nl, len(UNIT_KKT_OUT_X), 2, N), out_r=full(nl, len(UNIT_KKT_OUT_R), 2, R),
+             sc=full(nl, len(UNIT_KKT_SNAPS), len(UNIT_KKT_SC)), init_r=full(nl, len(UNIT_KKT_INIT_R), R),
+             init_x=full(nl, len(UNIT_KKT_INIT_X), N), w3=full(nl, ldw // 4, 4))
+    flag = np.full(nl, -1, dtype=np.int64)
+    report = np.zeros(24, dtype=np.int64)
+    mk = (C.c_int * nl)(*[int(m) for m in mask]) if mask is not None else None
+    nsw = (C.c_int * nl)(*[int(q) for q in nsweep])
+    op = opts if opts is not None else make_opts()
+    rc = load_library().mbfir_test_unit_kkt(ctx._h, arr, nl, C.byref(op), int(bool(initial)), int(form), int(bool(two)), int(bool(wbz_ready)),
+                                            int(nv), N, R, npad, ldw, mk, nsw, _ptr(s), _ptr(z), _ptr(x), _ptr(tk),
+                                            _ptr(bx) if bx is not None else None, _ptr(bz) if bz is not None else None, _ptr(o["res_r"]),
+                                            _ptr(o["res_x"]), _ptr(o["res_sc"]), _ptr(o["M"]), flag.ctypes.data_as(_lp), _ptr(o["out_x"]),
+                                            _ptr(o["out_r"]), _ptr(o["sc"]), _ptr(o["init_r"]), _ptr(o["init_x"]), _ptr(o["w3"]),
+                                            report.ctypes.data_as(_lp))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    o["flag"] = flag
+    o["report"] = {k: int(v) for k, v in zip(UNIT_KKT_REPORT, report)}
+    return o
 
 
 def test_chol_lanes(Hs, form=-1, mask=None, ctx=None):

@@ -709,6 +709,45 @@ int mbfir_test_unit_cone(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const
         return 0;
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
 }
+int mbfir_test_unit_kkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int mode, int form, int two, int wbz_ready,
+                        int nv, int ldx, int ldr, int ldh, int ldw, const int* mask, const int* nsweep, const double* s, const double* z,
+                        const double* x, const double* tau_kappa, const double* bx, const double* bz, double* res_r, double* res_x,
+                        double* res_sc, double* M, long* flag, double* out_x, double* out_r, double* out_sc, double* init_r, double* init_x,
+                        double* init_w3, long* report) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_unit_kkt: " + why; return MBFIR_E_ARG; };
+    if (!jobs || njobs < 1 || !nsweep || !s || !z || !x || !tau_kappa || !res_r || !res_x || !res_sc || !M || !flag || !out_x || !out_r ||
+        !out_sc || !report)
+        return bad("bad argument");
+    if (mode < 0 || mode > 1) return bad("mode must be 0 (a solve of the caller's right-hand sides) or 1 (the initial point)");
+    if (form < 0 || form > 1) return bad("form must be 0 (the residual kernels of a solve on one rank) or 1 (two-phase)");
+    if (nv < 1 || nv > 2) return bad("one or two right-hand sides");
+    if (mode == 1 && (nv != 2 || wbz_ready || !init_r || !init_x || !init_w3)) return bad("the initial point solves two right-hand sides from the winv2 entry and needs the init blocks");
+    if (wbz_ready && nv != 2) return bad("wbz_ready goes with two right-hand sides");
+    if ((bx == nullptr) != (bz == nullptr)) return bad("bx and bz go together");
+    if (mode == 0 && !bx && nv != 2) return bad("the residual kernels leave two right-hand sides");
+    for (int b = 0; b < njobs; ++b)
+        if (nsweep[b] < 0 || nsweep[b] > 8) return bad("a sweep count outside 0 .. 8");
+    try {
+        std::vector<TrigProgram> progs(njobs);
+        std::vector<const TrigProgram*> Ps;
+        for (int q = 0; q < njobs; ++q) {
+            std::string e;
+            if (assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e) != 0) return bad("job " + std::to_string(q) + ": " + e);
+            Ps.push_back(&progs[q]);
+        }
+        const SolveOpts so = to_opts(opts, progs[0].which);
+        if (so.shard_size > 1) return bad("row-sharded units are not taken");
+        if (so.ddkkt_theta > 0) return bad("units on the extended-precision path are not taken (opts.ddkkt = -1 for fir_qp_cvx)");
+        UnitKkt io;
+        io.mode = mode; io.form = form; io.two = two; io.wbz_ready = wbz_ready; io.nv = nv; io.ldx = ldx; io.ldr = ldr; io.ldh = ldh; io.ldw = ldw;
+        io.mask = mask; io.nsweep = nsweep; io.s = s; io.z = z; io.x = x; io.tau_kappa = tau_kappa; io.bx = bx; io.bz = bz;
+        io.res_r = res_r; io.res_x = res_x; io.res_sc = res_sc; io.M = M; io.flag = flag; io.out_x = out_x; io.out_r = out_r; io.out_sc = out_sc;
+        io.init_r = init_r; io.init_x = init_x; io.init_w3 = init_w3; io.report = report;
+        ctx->solver->test_unit_kkt(Ps, so, io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll) {
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;

@@ -85,6 +85,22 @@ struct UnitCone {
     long* report = nullptr;
 };
 
+// Arguments of Solver::test_unit_kkt (mbfir_test_unit_kkt of include/mbfir.h, which says what each block holds): host arrays of
+// nlanes blocks each.  Blocks of out_x / out_r hold two vectors of ldx / ldr (the second stays the caller's where nv = 1).
+enum { UKX_T1 = 0, UKX_DX0, UKX_T4, UKX_R0, UKX_P /* + 2 s: p, z of start s = 0 .. 7 */, UKX_HP = UKX_P + 16 /* + 3 q: Hp, dx, r of sweep q */,
+       UKX_DX_END = UKX_HP + 24, UKX_R_END, UK_OUT_X };
+enum { UKR_WBZ = 0, UKR_GDX0, UKR_DZ0, UKR_GP /* + 4 q: Gp, W^-2 Gp, gdx, dz of sweep q */, UKR_GDX_END = UKR_GP + 32, UKR_DZ_END, UK_OUT_R };
+enum { UKS_RESID = 0, UKS_START /* + s */, UKS_STEP = UKS_START + 8 /* + q */, UKS_END = UKS_STEP + 8, UK_SNAPS };
+enum { UK_SC = 13 /* n_0 .. n_8, rz[2], alpha[2] */, UK_RES_SC = 24, UK_RES_X = 4, UK_RES_R = 3, UK_INIT_R = 7, UK_INIT_X = 3, UNIT_KKT_REPORT = 24 };
+struct UnitKkt {
+    int mode = 0 /* 1: initial_point */, form = 0, two = 0, wbz_ready = 0, nv = 2, ldx = 0, ldr = 0, ldh = 0, ldw = 0;
+    const int *mask = nullptr, *nsweep = nullptr;
+    const double *s = nullptr, *z = nullptr, *x = nullptr, *tau_kappa = nullptr, *bx = nullptr, *bz = nullptr;
+    double *res_r = nullptr, *res_x = nullptr, *res_sc = nullptr, *M = nullptr, *out_x = nullptr, *out_r = nullptr, *out_sc = nullptr,
+           *init_r = nullptr, *init_x = nullptr, *init_w3 = nullptr;
+    long *flag = nullptr, *report = nullptr;
+};
+
 // Arguments of Solver::test_capsolve (mbfir_test_capsolve of include/mbfir.h, which says what each array holds and checks them)
 struct CapSolveIO {
     int n = 0, nlanes = 1, kp = 0, nrhs = 1, hsolve_form = -1;
@@ -129,6 +145,9 @@ public:
     // the cone stages of one iteration of a lock-step unit (a unit of one included) at a caller's iterate, through the stages of
     // launch_iteration, with the caller's "solutions" in place of the KKT solves
     void test_unit_cone(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitCone& io);
+    // the residual kernels of an iterate and the plain KKT solve (or the initial point) of a lock-step unit at a caller's iterate and
+    // right-hand sides, every group of launches of kkt_solve read back through its observer
+    void test_unit_kkt(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitKkt& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
     // the capacitance form of the extended-precision solve: the launches of its build and of one pass of its solve, for nlanes

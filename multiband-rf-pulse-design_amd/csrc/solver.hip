@@ -122,6 +122,13 @@ constexpr int NPART = 1024;   // max blocks contributing to a reduction
 constexpr int SCAL_T = 256;   // threads of the one-workgroup-per-design folding kernels (a 1024-thread block has to wait for a
                               // whole CU when other units share the chip)
 constexpr int MAX_SWEEPS = 8;
+// kkt_solve's optional observer (test_unit_kkt): the groups of launches it is called after, in their order
+enum { KKT_ST_WBZ = 0, KKT_ST_GTWBZ, KKT_ST_HSOLVE, KKT_ST_GDX, KKT_ST_RESID, KKT_ST_START, KKT_ST_GP, KKT_ST_HP, KKT_ST_STEP, KKT_ST_RESTART };
+struct KktObserver {
+    std::function<void(int, int)> fn;
+    bool two_launch_cg = false;
+    void operator()(int stage, int sweep) const { fn(stage, sweep); }
+};
 // the scalar slots: the auto-numbered ones end before the first norm block, each norm block holds n_0 .. n_MAX_SWEEPS
 static_assert(S_NPICK < S_RNA, "scalar slots: the auto-numbered slots run into S_RNA");
 static_assert(S_RNA + MAX_SWEEPS + 1 <= S_RNB && S_RNB + MAX_SWEEPS + 1 <= S_CG_RZ && S_RNC + MAX_SWEEPS + 1 <= S_SIGMAX,
@@ -3075,23 +3082,30 @@ struct Solver::Impl {
     // through G (K1 + K3 passes) and M'M as preconditioner; dz and gdx are carried along, so the
     // dual equation G'dz = bx ends at the CG residual.  Residual norms n_0 (after the Cholesky solve)
     // .. n_nsweep go to Sc[slot ..] for the sweep controller.  Mirrors oracle/conic_ipm.py kkt_solve.
+    // obs (test_unit_kkt; null in every solve): called on the host after each group of launches below with the group's number
+    // (KKT_ST_*) and the sweep; obs->two_launch_cg runs the sweep's update in the row-sharded form on one rank
     template <int NV>
     void kkt_solve(const double* bx, const double* bz, double* dx, double* dz, double* gdx, int nsweep, int slot,
-                   bool wbz_ready = false) {
+                   bool wbz_ready = false, const KktObserver* obs = nullptr) {
         // lock-step batch: nsweep is the largest count over the live lanes; mask row q switches off the lanes that
         // need fewer than q sweeps
         const dim3 gR = lane_grid(dim3(cdiv(P.R, 256)), nlanes), g1 = lane_grid(dim3(1), nlanes), b256(256);
         if (!wbz_ready) winv2<NV>(bz, nullptr, wbz, 0);
         else if (P.big) hipLaunchKernelGGL(k_big_winv2<NV>, g1, dim3(1024), 0, st, P, wbb, Sc, bz, nullptr, wbz, 0);
+        if (obs) (*obs)(KKT_ST_WBZ, 0);
         apply_GT<NV>(wbz, tmpN);
+        if (obs) (*obs)(KKT_ST_GTWBZ, 0);
         hsolve<NV>(bx, dx, tmpN);                                                           // M'M (bx + G' W^-2 bz)
+        if (obs) (*obs)(KKT_ST_HSOLVE, 0);
         apply_G_winv2<NV>(dx, gdx, wbz, dz);
+        if (obs) (*obs)(KKT_ST_GDX, 0);
         double* r = rhsN;
         if (sw.fuse && shard_size <= 1) apply_GT<NV>(dz, tmpN, 0, bx, r, slot);                       // G'dz ; r = bx - G'dz ; n_0
         else {
         apply_GT<NV>(dz, tmpN);
         hipLaunchKernelGGL(k_resid_norm<NV>, g1, dim3(SCAL_T), 0, st, P, bx, tmpN, r, Sc, slot);      // r = bx - G'dz ; n_0
         }
+        if (obs) (*obs)(KKT_ST_RESID, 0);
         if (nsweep <= 0) return;
         const int* live = P.mask;
         P.mask = mask_row(1);
@@ -3107,17 +3121,22 @@ struct Solver::Impl {
             }
         };
         z_and_start(1);
+        if (obs) (*obs)(KKT_ST_START, 0);
+        const bool one_launch = shard_size == 1 && !(obs && obs->two_launch_cg);
         for (int it = 0; it < nsweep; ++it) {
             P.mask = mask_row(it + 1);
             apply_G_winv2<NV>(pN, tmpR, nullptr, wpR);                                      // G p, W^-2 G p
+            if (obs) (*obs)(KKT_ST_GP, it);
             apply_GT<NV>(wpR, tmpN);                                                        // H p
-            if (shard_size == 1) {
+            if (obs) (*obs)(KKT_ST_HP, it);
+            if (one_launch) {
                 hipLaunchKernelGGL(k_cg_step_update<NV>, gR, b256, 0, st, P, Sc, pN, tmpN, dx, r, slot + it + 1, tmpR, wpR, gdx, dz);
             } else {
                 hipLaunchKernelGGL(k_cg_step<NV>, g1, dim3(SCAL_T), 0, st, P, Sc, pN, tmpN, dx, r, slot + it + 1);   // alpha, dx, r, n_{it+1}
                 hipLaunchKernelGGL(k_cg_update_r<NV>, gR, b256, 0, st, P, Sc, tmpR, wpR, gdx, dz);
             }
-            if (it + 1 < nsweep) { P.mask = mask_row(it + 2); z_and_start(0); }
+            if (obs) (*obs)(KKT_ST_STEP, it);
+            if (it + 1 < nsweep) { P.mask = mask_row(it + 2); z_and_start(0); if (obs) (*obs)(KKT_ST_RESTART, it); }
         }
         P.mask = live;
     }
@@ -3740,12 +3759,12 @@ struct Solver::Impl {
         hipLaunchKernelGGL(k_cone_shift, lane_grid(dim3(64), nlanes), dim3(256), 0, st, P, v, RB);
     }
     // initial point (W = I): x, s, z from the KKT solve of the initial right-hand sides, s and z shifted into their cones
-    void initial_point(int nsweep) {
+    void initial_point(int nsweep, const KktObserver* obs = nullptr) {
         hipLaunchKernelGGL(k_unit_scaling, lane_grid(dim3(cdiv(std::max(std::max(P.l, P.nq3), std::max(P.big, 1)), 256)), nlanes), dim3(256), 0, st,
                            P, dl, wl, w3, wbb, Sc);
         build_H();
         hipLaunchKernelGGL(k_init_rhs, lane_grid(dim3(cdiv(std::max(P.N, P.R), 256)), nlanes), dim3(256), 0, st, P, bx2, bz2);
-        kkt_solve<2>(bx2, bz2, dx2, dz2, gdx2, nsweep, S_RNA);
+        kkt_solve<2>(bx2, bz2, dx2, dz2, gdx2, nsweep, S_RNA, false, obs);
         copy_lanes(x, dx2, sizeof(double) * P.LDV);
         hipLaunchKernelGGL(k_neg_copy_r, lane_grid(dim3(cdiv(P.R, 256)), nlanes), dim3(256), 0, st, P, dz2, s, -1.0);
         cone_shift(s);
@@ -3753,10 +3772,10 @@ struct Solver::Impl {
         cone_shift(z);
     }
     // the residual kernels of an iterate (everything up to the one copy + synchronisation per iteration)
-    void launch_residuals() {
+    void launch_residuals(int two = -1) {
         // row-sharded: the four row sums (||rz||^2, s'z, h'z, ||Gx + s||^2) are folded into a mailbox directly behind G'z and
         // summed over the ranks by the same all-reduce (they do not depend on G'z)
-        const bool sharded = shard_size > 1;
+        const bool sharded = two_phase(two);        // (`two`: as for dots() below; test_unit_kkt runs the two-phase form on one rank)
         double* rmail = sharded ? GTz + P.LDV : RB;
         if (P.trig) {                                     // G x rows are formed inside k_resid_rows
             ++n_gv;
@@ -3766,7 +3785,7 @@ struct Solver::Impl {
             apply_G<1>(x, Gx);
             hipLaunchKernelGGL(k_resid_rows, lane_grid(dim3(nbR), nlanes), dim3(256), 0, st, P, Gx, s, z, Sc, rz, bz2, partR, nullptr, nullptr);
         }
-        if (sharded) hipLaunchKernelGGL(k_scal_resid, dim3(1), dim3(SCAL_T), 0, st, P, Sc, GTz, x, rx, bx2, partR, nbR, rmail, 0, (const int*)flag);
+        if (sharded) hipLaunchKernelGGL(k_scal_resid, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, GTz, x, rx, bx2, partR, nbR, rmail, 0, (const int*)flag);
         apply_GT<1>(z, GTz, sharded ? 5 : 0);
         hipLaunchKernelGGL(k_scal_resid, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, Sc, GTz, x, rx, bx2, partR, nbR, rmail, sharded ? 1 : 2, (const int*)flag);
     }
@@ -4495,6 +4514,210 @@ void Solver::test_unit_cone(const std::vector<const TrigProgram*>& Qs, const Sol
     for (int i = 0; i < UNIT_CONE_REPORT; ++i) r[i] = 0;
     r[0] = std::max(S.nbC, 1); r[1] = P.l; r[2] = P.nq3; r[3] = P.big; r[4] = P.N; r[5] = P.R; r[6] = P.dims ? 1 : 0; r[7] = nlanes;
     r[8] = S.sw.fuse ? 1 : 0; r[9] = S.sw.corr_big ? 1 : 0; r[10] = two; r[11] = ns0; r[12] = ns1; r[13] = S.unknown_blocks();
+}
+
+// The residual kernels and the plain KKT solve of one unit at a caller's iterate (include/mbfir.h: mbfir_test_unit_kkt).  The unit
+// is set up by the stages of solve_lanes (setup_unit); launch_residuals, launch_scaling, build_H and kkt_solve (or initial_point) run
+// as a solve runs them, kkt_solve with an observer that enqueues the copies of what each group of launches wrote and sends the
+// caller's sentinels into the buffers the next group writes.  Nothing synchronises between the launches.
+void Solver::test_unit_kkt(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, const UnitKkt& io) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int nlanes = int(Qs.size()), nv = io.nv;
+    if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
+    std::vector<LaneHost> LH(nlanes);
+    for (int b = 0; b < nlanes; ++b) LH[b].live = !io.mask || io.mask[b] != 0;
+    S.setup_unit(Qs, o, LH);
+    S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
+    S.timing = false;
+    S.chol_launch_count = 0; S.dd_epoch = 0;
+    S.taps_valid = false;
+    const DProg& P = S.P;
+    if (io.ldx < P.N || io.ldx > P.LDV || io.ldr < P.R || io.ldr > P.Rp || io.ldh != P.np || io.ldw != 4 * std::max(P.nq3, 1))
+        throw HipError("test_unit_kkt: ldx / ldr / ldh / ldw do not fit the unit (N " + std::to_string(P.N) + ", R " + std::to_string(P.R) + ", np " +
+                       std::to_string(P.np) + ", n_q3 " + std::to_string(P.nq3) + ")");
+    const size_t ldx = io.ldx, ldr = io.ldr, np2 = (size_t)P.np * P.np;
+    const bool initial = io.mode == 1;
+    int ns_max = 0;
+    std::vector<int> ns(nlanes, 0);
+    for (int b = 0; b < nlanes; ++b) {
+        ns[b] = LH[b].live ? io.nsweep[b] : 0;
+        LH[b].nsweep = ns[b];
+        ns_max = std::max(ns_max, ns[b]);
+    }
+    auto lane = [&](const double* p, int b) { return reinterpret_cast<double*>(reinterpret_cast<char*>(const_cast<double*>(p)) + (size_t)b * S.lane_bytes); };
+    auto h2d = [&](double* dst, const double* src, size_t n, int b) { MBFIR_HIP(hipMemcpyAsync(lane(dst, b), src, n * sizeof(double), hipMemcpyHostToDevice, S.st)); };
+    auto d2h = [&](double* dst, const double* src, size_t n, int b) { MBFIR_HIP(hipMemcpyAsync(dst, lane(src, b), n * sizeof(double), hipMemcpyDeviceToHost, S.st)); };
+    // the solve's buffers: the batch solve's (two right-hand sides) or the combined solve's (one)
+    double *bx = nv == 2 ? S.bx2 : S.bxc, *bz = nv == 2 ? S.bz2 : S.bzc, *dx = nv == 2 ? S.dx2 : S.dxc, *dz = nv == 2 ? S.dz2 : S.dzc,
+           *gdx = nv == 2 ? S.gdx2 : S.gdxc;
+    const int slot = nv == 2 ? S_RNA : S_RNB;
+    // block `blk` of out_x (space 1) or out_r (space 0): nv vectors, LDV resp. Rp apart on the device
+    auto host_of = [&](int space, int b, int blk, int v) {
+        return space ? io.out_x + (((size_t)b * UK_OUT_X + blk) * 2 + v) * ldx : io.out_r + (((size_t)b * UK_OUT_R + blk) * 2 + v) * ldr;
+    };
+    struct Blk { double* dev; int space, blk; };
+    auto X_ = [&](double* dev, int blk) { return Blk{dev, 1, blk}; };
+    auto R_ = [&](double* dev, int blk) { return Blk{dev, 0, blk}; };
+    auto plant = [&](const std::vector<Blk>& bs) {
+        for (int b = 0; b < nlanes; ++b)
+            for (const Blk& q : bs)
+                for (int v = 0; v < nv; ++v) h2d(q.dev + (size_t)v * (q.space ? P.LDV : P.Rp), host_of(q.space, b, q.blk, v), q.space ? ldx : ldr, b);
+    };
+    // (in-place blocks: the lanes that run the sweep; fresh ones: every lane -- a lane the mask switches off returns the sentinel)
+    auto grab = [&](const std::vector<Blk>& bs, int need = -1) {
+        for (int b = 0; b < nlanes; ++b) {
+            if (need >= 0 && !(LH[b].live && ns[b] >= need)) continue;
+            for (const Blk& q : bs)
+                for (int v = 0; v < nv; ++v) d2h(host_of(q.space, b, q.blk, v), q.dev + (size_t)v * (q.space ? P.LDV : P.Rp), q.space ? ldx : ldr, b);
+        }
+    };
+    std::vector<double> snap((size_t)UK_SNAPS * nlanes * S_COUNT, 0.0);
+    std::vector<int> snap_need(UK_SNAPS, -1);               // a lane returns snapshot k if it runs at least that many sweeps
+    auto snapshot = [&](int k, int need) {
+        for (int b = 0; b < nlanes; ++b) d2h(snap.data() + ((size_t)k * nlanes + b) * S_COUNT, S.Sc, S_COUNT, b);
+        snap_need[k] = need;
+    };
+    // ---- the iterate, then the residual kernels ------------------------------------------------------------------------------------
+    const int res_pick[14] = {S_RT, S_MU, S_PCOST, S_DCOST, S_GAP, S_RELGAP, S_PRES, S_DRES, S_PINF, S_DINF, S_CX, S_HZ, S_SZ, S_CHOLFIX};
+    double* rmail = io.form ? S.GTz + P.LDV : S.RB;
+    for (int b = 0; b < nlanes; ++b) {
+        double* rr = io.res_r + (size_t)b * UK_RES_R * ldr;
+        double* rxh = io.res_x + (size_t)b * UK_RES_X * ldx;
+        const double* sc = io.res_sc + (size_t)b * UK_RES_SC;
+        if (LH[b].live) {
+            h2d(S.s, io.s + (size_t)b * ldr, ldr, b); h2d(S.z, io.z + (size_t)b * ldr, ldr, b); h2d(S.x, io.x + (size_t)b * ldx, ldx, b);
+            h2d(S.Sc + S_TAU, io.tau_kappa + 2 * (size_t)b, 1, b); h2d(S.Sc + S_KAPPA, io.tau_kappa + 2 * (size_t)b + 1, 1, b);
+        }
+        h2d(S.rz, rr, ldr, b); h2d(S.bz2, rr + ldr, ldr, b); h2d(S.bz2 + P.Rp, rr + 2 * ldr, ldr, b);
+        h2d(S.GTz, rxh, ldx, b); h2d(S.rx, rxh + ldx, ldx, b); h2d(S.bx2, rxh + 2 * ldx, ldx, b); h2d(S.bx2 + P.LDV, rxh + 3 * ldx, ldx, b);
+        for (int q = 0; q < 14; ++q) h2d(S.Sc + res_pick[q], sc + q, 1, b);
+        h2d(rmail, sc + 19, 5, b);
+    }
+    S.launch_residuals(io.form ? 1 : 0);
+    std::vector<double> res_snap((size_t)nlanes * (S_COUNT + 5), 0.0);
+    for (int b = 0; b < nlanes; ++b) {
+        double* rr = io.res_r + (size_t)b * UK_RES_R * ldr;
+        double* rxh = io.res_x + (size_t)b * UK_RES_X * ldx;
+        d2h(rr, S.rz, ldr, b); d2h(rr + ldr, S.bz2, ldr, b); d2h(rr + 2 * ldr, S.bz2 + P.Rp, ldr, b);
+        d2h(rxh, S.GTz, ldx, b); d2h(rxh + ldx, S.rx, ldx, b); d2h(rxh + 2 * ldx, S.bx2, ldx, b); d2h(rxh + 3 * ldx, S.bx2 + P.LDV, ldx, b);
+        d2h(res_snap.data() + (size_t)b * (S_COUNT + 5), S.Sc, S_COUNT, b);
+        d2h(res_snap.data() + (size_t)b * (S_COUNT + 5) + S_COUNT, rmail, 5, b);
+    }
+    // ---- the right-hand sides, the scaling and the factor; or the initial point's own ------------------------------------------------
+    // the norm slots and the sweep's scalars hold the sentinel (out_sc as the caller filled it) until a kernel writes them
+    for (int b = 0; b < nlanes; ++b) {
+        const double* sc = io.out_sc + (size_t)b * UK_SNAPS * UK_SC;
+        h2d(S.Sc + slot, sc, MAX_SWEEPS + 1, b); h2d(S.Sc + S_CG_RZ, sc + 9, 2, b); h2d(S.Sc + S_CG_ALPHA, sc + 11, 2, b);
+    }
+    KktObserver obs;
+    obs.two_launch_cg = io.two != 0;
+    const bool z_written = !(S.sw.fuse && S.fused_hsolve);
+    obs.fn = [&](int stage, int q) {
+        switch (stage) {
+            case KKT_ST_WBZ: grab({R_(S.wbz, UKR_WBZ)}); plant({X_(S.tmpN, UKX_T1)}); break;
+            case KKT_ST_GTWBZ: grab({X_(S.tmpN, UKX_T1)}); plant({X_(dx, UKX_DX0)}); break;
+            case KKT_ST_HSOLVE: grab({X_(dx, UKX_DX0)}); plant({R_(gdx, UKR_GDX0), R_(dz, UKR_DZ0)}); break;
+            case KKT_ST_GDX: grab({R_(gdx, UKR_GDX0), R_(dz, UKR_DZ0)}); plant({X_(S.tmpN, UKX_T4), X_(S.rhsN, UKX_R0)}); break;
+            case KKT_ST_RESID:
+                grab({X_(S.tmpN, UKX_T4), X_(S.rhsN, UKX_R0)}); snapshot(UKS_RESID, 0);
+                if (ns_max > 0) plant({X_(S.pN, UKX_P), X_(S.tmpN2, UKX_P + 1)});
+                break;
+            case KKT_ST_START:
+                grab({X_(S.pN, UKX_P)}); if (z_written) grab({X_(S.tmpN2, UKX_P + 1)});
+                snapshot(UKS_START, 1);
+                plant({R_(S.tmpR, UKR_GP), R_(S.wpR, UKR_GP + 1)});
+                break;
+            case KKT_ST_GP: grab({R_(S.tmpR, UKR_GP + 4 * q), R_(S.wpR, UKR_GP + 4 * q + 1)}); plant({X_(S.tmpN, UKX_HP + 3 * q)}); break;
+            case KKT_ST_HP: grab({X_(S.tmpN, UKX_HP + 3 * q)}); break;
+            case KKT_ST_STEP:
+                grab({X_(dx, UKX_HP + 3 * q + 1), X_(S.rhsN, UKX_HP + 3 * q + 2), R_(gdx, UKR_GP + 4 * q + 2), R_(dz, UKR_GP + 4 * q + 3)}, q + 1);
+                snapshot(UKS_STEP + q, q + 1);
+                if (q + 1 < ns_max) {
+                    plant({X_(S.tmpN2, UKX_P + 2 * (q + 1) + 1), R_(S.tmpR, UKR_GP + 4 * (q + 1)), R_(S.wpR, UKR_GP + 4 * (q + 1) + 1)});
+                    // (p is updated in place: a lane that does not start sweep q + 1 keeps the caller's block on the host)
+                }
+                break;
+            case KKT_ST_RESTART:
+                grab({X_(S.pN, UKX_P + 2 * (q + 1))}, q + 2); if (z_written) grab({X_(S.tmpN2, UKX_P + 2 * (q + 1) + 1)});
+                snapshot(UKS_START + q + 1, q + 2);
+                break;
+            default: break;
+        }
+    };
+    if (!initial) {
+        if (io.bx)
+            for (int b = 0; b < nlanes; ++b) {
+                if (!LH[b].live) continue;
+                for (int v = 0; v < nv; ++v) {
+                    h2d(bx + (size_t)v * P.LDV, io.bx + ((size_t)b * nv + v) * ldx, ldx, b);
+                    h2d(bz + (size_t)v * P.Rp, io.bz + ((size_t)b * nv + v) * ldr, ldr, b);
+                }
+            }
+        if (io.wbz_ready) plant({R_(S.wbz, UKR_WBZ)});
+        S.launch_scaling();
+        S.build_H(0);
+        if (!io.wbz_ready) plant({R_(S.wbz, UKR_WBZ)});
+        S.push_masks(LH);
+        if (nv == 2) S.kkt_solve<2>(bx, bz, dx, dz, gdx, ns_max, slot, io.wbz_ready != 0, &obs);
+        else S.kkt_solve<1>(bx, bz, dx, dz, gdx, ns_max, slot, false, &obs);
+    } else {
+        for (int b = 0; b < nlanes; ++b) {
+            double* ir = io.init_r + (size_t)b * UK_INIT_R * ldr;
+            h2d(S.dl, ir, ldr, b); h2d(S.wl, ir + ldr, ldr, b); h2d(S.wbb, ir + 2 * ldr, (size_t)std::max(P.big, 1), b);
+            h2d(S.w3, io.init_w3 + (size_t)b * io.ldw, io.ldw, b);
+            double* ix = io.init_x + (size_t)b * UK_INIT_X * ldx;
+            h2d(S.bz2, ir + 5 * ldr, ldr, b); h2d(S.bz2 + P.Rp, ir + 6 * ldr, ldr, b);
+            h2d(S.bx2, ix + ldx, ldx, b); h2d(S.bx2 + P.LDV, ix + 2 * ldx, ldx, b);
+            if (!LH[b].live) { h2d(S.s, ir + 3 * ldr, ldr, b); h2d(S.z, ir + 4 * ldr, ldr, b); h2d(S.x, ix, ldx, b); }
+        }
+        plant({R_(S.wbz, UKR_WBZ)});
+        S.push_masks(LH);
+        S.initial_point(ns_max, &obs);
+        for (int b = 0; b < nlanes; ++b) {
+            double* ir = io.init_r + (size_t)b * UK_INIT_R * ldr;
+            d2h(ir, S.dl, ldr, b); d2h(ir + ldr, S.wl, ldr, b); d2h(ir + 2 * ldr, S.wbb, (size_t)std::max(P.big, 1), b);
+            d2h(io.init_w3 + (size_t)b * io.ldw, S.w3, io.ldw, b);
+            double* ix = io.init_x + (size_t)b * UK_INIT_X * ldx;
+            d2h(ir + 3 * ldr, S.s, ldr, b); d2h(ir + 4 * ldr, S.z, ldr, b); d2h(ix, S.x, ldx, b);
+            d2h(ir + 5 * ldr, S.bz2, ldr, b); d2h(ir + 6 * ldr, S.bz2 + P.Rp, ldr, b);
+            d2h(ix + ldx, S.bx2, ldx, b); d2h(ix + 2 * ldx, S.bx2 + P.LDV, ldx, b);
+        }
+    }
+    // what the solve leaves: the inverse factor, the pivot counter, the solution and the residual
+    std::vector<int> fl(nlanes, 0);
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        MBFIR_HIP(hipMemcpyAsync(io.M + (size_t)b * np2, lane(S.M, b), np2 * sizeof(double), hipMemcpyDeviceToHost, S.st));
+        MBFIR_HIP(hipMemcpyAsync(&fl[b], reinterpret_cast<char*>(S.flag) + (size_t)b * S.lane_bytes, sizeof(int), hipMemcpyDeviceToHost, S.st));
+    }
+    grab({X_(dx, UKX_DX_END), X_(S.rhsN, UKX_R_END), R_(gdx, UKR_GDX_END), R_(dz, UKR_DZ_END)}, 0);
+    snapshot(UKS_END, 0);
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        io.flag[b] = fl[b];
+        const double* h = res_snap.data() + (size_t)b * (S_COUNT + 5);
+        double* d = io.res_sc + (size_t)b * UK_RES_SC;
+        const int more[5] = {S_TAU, S_KAPPA, S_NRMH, S_NRMC, S_DEG};
+        for (int q = 0; q < 14; ++q) d[q] = h[res_pick[q]];
+        for (int q = 0; q < 5; ++q) d[14 + q] = h[more[q]];
+        for (int q = 0; q < 5; ++q) d[19 + q] = h[S_COUNT + q];
+        for (int k = 0; k < UK_SNAPS; ++k) {
+            if (snap_need[k] < 0 || ns[b] < snap_need[k]) continue;
+            const double* hs = snap.data() + ((size_t)k * nlanes + b) * S_COUNT;
+            double* ds = io.out_sc + ((size_t)b * UK_SNAPS + k) * UK_SC;
+            for (int q = 0; q <= MAX_SWEEPS; ++q) ds[q] = hs[slot + q];
+            ds[9] = hs[S_CG_RZ]; ds[10] = hs[S_CG_RZ + 1]; ds[11] = hs[S_CG_ALPHA]; ds[12] = hs[S_CG_ALPHA + 1];
+        }
+    }
+    long* r = io.report;
+    for (int i = 0; i < UNIT_KKT_REPORT; ++i) r[i] = 0;
+    r[0] = S.fused_hsolve ? 1 : 0; r[1] = S.sw.fuse ? 1 : 0; r[2] = io.form ? 1 : 0; r[3] = P.N; r[4] = P.R; r[5] = P.np; r[6] = P.big;
+    r[7] = nlanes; r[8] = P.dims ? 1 : 0; r[9] = P.trig; r[10] = cdiv(P.Nt, GTC) + 1; r[11] = nv; r[12] = io.two ? 1 : 0;
+    r[13] = io.wbz_ready ? 1 : 0; r[14] = initial ? 1 : 0; r[15] = ns_max; r[16] = P.l; r[17] = P.nq3; r[18] = S.nbR; r[19] = z_written ? 1 : 0;
+    r[20] = S.n_gv; r[21] = S.n_gtv;
 }
 
 void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
