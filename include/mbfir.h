@@ -603,6 +603,45 @@ int mbfir_test_unit_kkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const 
                         const double* x, const double* tau_kappa, const double* bx, const double* bz, double* res_r, double* res_x,
                         double* res_sc, double* M, long* flag, double* out_x, double* out_r, double* out_sc, double* init_r, double* init_x,
                         double* init_w3, long* report);
+/*  mbfir_test_unit_ddkkt: the extended-precision path of an iteration (opts.ddkkt on) of ONE lock-step unit at the caller's iterate,
+ *  stage by stage.  The unit is set up as for mbfir_test_unit_ops.  In this order, as the head of an iteration and its solves launch
+ *  them: the NT scaling of (s, z); the selection of every live lane's strong set (eigen data, cap, strong set, its fixed order; the cap
+ *  raised x 100 and the selection repeated where a set does not fit -- the one host synchronisation); the lanes' mode masks; the capped
+ *  normal matrix with the strong rows U and its factorisation in the solve's own form (capacitance form by default, MBFIR_DDFORM=dd
+ *  the double-double one; a single design pads to MBFIR_TEST_CAP_KP); then (solve != 0) the solve of the caller's nv = 1 or 2
+ *  right-hand sides: the refinement passes of the extended-precision solve on the lanes with a non-empty strong set, the plain solve
+ *  with opts.refine sweeps on the others.
+ *  Per lane b (host arrays of njobs blocks; ldx >= the unit's largest N, ldr >= its largest R, ldh = np, ldw = 4 max(n_q3, 1), ldu: the
+ *  rows of U, Yt, Zt, S, Ms the caller has room for, 64 .. 3072):
+ *    in:  s, z (ldr), bx (nv x ldx), bz (nv x ldr), mask (0: the lane is switched off);
+ *    in / out, every live lane -- sel_r (4 rows of ldr): dl, dlc, the big cone's w, its what; sel_q (18 ldw / 4): w3 (4 per cone), e3 (8
+ *         per cone: lam_p, lam_0, lam_m, what), m3c (6 per cone); sel_sc (16): eb[0 .. 7], S_ETAB, the lane's final cap factor;
+ *         sel_part (ldp rows of 2): the partial rows (sum log typical weight, count) the selection folds, the big cone's row first, then
+ *         one per 256 orthant rows and 3-row cones -- the first min(ldp, rows) of them, the number of rows in lane_rep[3];
+ *         sel_i (ldr + 3 ldw / 4 + 3 ints): slotl, slot3, slotb, kcnt; strong_i (3 x 3072 ints): skind, sidx, sdir and strong_x (3072): sX,
+ *         over the lane's count; H (np x np): the normal matrix ahead of the factorisation; U (ldu x np): rows 0 .. min(kp, ldu) - 1,
+ *         sent to the device as the caller filled them before the rows are formed; M and Hf (np x np): the buffers M and H as the solve
+ *         leaves them (capacitance form: M the inverse factor; double-double form: Hf, M the high and low parts of the factor); flag;
+ *         end_x (2 x ldx): dx; end_r (2 blocks of 2 x ldr): dz, gdx; out_sc row 3: the norm slots at the end;
+ *    in / out, the lanes in the extended-precision mode -- Yt, Zt (ldu x np), S (ahead of its factorisation), Ms (ldu x ldu): the
+ *         capacitance form's, or all four NULL; per pass p < 3, blocks of two vectors:
+ *         out_x (9 of ldx): [0] G'dz, [1] r1 = bx - G'dz, [2] G'W_w^-2 r2, [3], [4] the right-hand side of the normal-equation solve
+ *         (double-double form: high, low; capacitance form: [4] rhs_w), [5] y (capacitance form), [6], [7] the solve's result (high;
+ *         low in the double-double form), [8] dx after the pass;
+ *         out_r (6 of ldr): [0] r2, [1] W_w^-2 r2, [2] G Bh, [3] W_w^-2 (G Bh - r2), [4] dz and [5] gdx after the pass;
+ *         out_k (3 of 3072): [0] t = e'r2 per strong slot, [1] U y - t (capacitance form), [2] zeta;
+ *         out_sc rows 0 .. 2 (9): the solve's norm slots after r1 of the pass.
+ *         Every block goes to the device as the caller filled it right before the launches that write it and comes back right after.
+ *    lane_rep (4 longs): [0] 0 switched off, 1 extended-precision mode, 2 plain mode, [1] the strong count, [2] selections run, [3] partial rows.
+ *    report (16 longs): [0] kp, [1] capacitance form, [2] passes, [3] lanes, [4] N, [5] R, [6] np, [7] l, [8] n_q3, [9] big, [10] the
+ *         largest strong count, [11] selections run, [12] nv, [13] solve, [14] heterogeneous, [15] sweeps of the plain mode.
+ *  MBFIR_E_ARG with a message, before anything is launched: a bad lane count, leading dimensions that do not fit, nv outside 1 .. 2, the
+ *  double-double form with more than one lane, a row-sharded context, a unit not on the extended-precision path. */
+int mbfir_test_unit_ddkkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int nv, int solve, int ldx, int ldr, int ldh,
+                          int ldw, int ldu, int ldp, const int* mask, const double* s, const double* z, const double* bx, const double* bz, double* sel_r,
+                          double* sel_q, double* sel_sc, double* sel_part, int* sel_i, int* strong_i, double* strong_x, double* H, double* U, double* M, double* Hf,
+                          double* Yt, double* Zt, double* S, double* Ms, long* flag, double* out_x, double* out_r, double* out_k, double* out_sc,
+                          double* end_x, double* end_r, long* lane_rep, long* report);
 /*  mbfir_test_fold: the host-side analysis of a frequency grid w[m] for the lattice kernels (no GPU, no context): pairs
  *  +w / -w (fold != 0), cuts the folded list into equally spaced runs.  out[6]: lattice usable, folded entries, pairs,
  *  runs, longest run, self-check failures (must be 0).  (Own addition; nothing in the reference corresponds.) */

@@ -170,6 +170,8 @@ SYMBOLS = {
                                        _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _lp]),
     "mbfir_test_unit_kkt": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts)] + [C.c_int] * 9 + [_ip, _ip] + [_dp] * 6 +
                                      [_dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, _dp, _dp, _lp]),
+    "mbfir_test_unit_ddkkt": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts)] + [C.c_int] * 8 + [_ip] + [_dp] * 8 + [_ip, _ip] +
+                                       [_dp] * 9 + [_lp] + [_dp] * 6 + [_lp, _lp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
     "mbfir_test_capsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
@@ -1060,6 +1062,64 @@ def test_unit_kkt(jobs, s, z, x, tau_kappa, nsweep, nq3, *, bx=None, bz=None, nv
     _check(ctx, rc)
     o["flag"] = flag
     o["report"] = {k: int(v) for k, v in zip(UNIT_KKT_REPORT, report)}
+    return o
+
+
+# the blocks of mbfir_test_unit_ddkkt (include/mbfir.h)
+UNIT_DDKKT_OUT_X = ("gtdz", "r1", "gtw", "rhs_h", "rhs_l", "y", "bh", "bl", "dx")
+UNIT_DDKKT_OUT_R = ("r2", "wbz", "gbh", "wbz2", "dz", "gdx")
+UNIT_DDKKT_OUT_K = ("ts", "capw", "zeta")
+UNIT_DDKKT_REPORT = ("kp", "cap_form", "passes", "lanes", "N", "R", "np", "l", "nq3", "big", "k_max", "attempts", "nv", "solve", "hetero",
+                     "nsweep_plain")
+DD_KMAX = 3072
+
+
+def test_unit_ddkkt(jobs, s, z, bx, bz, nq3, *, solve=True, ldu=64, cap_blocks=True, mask=None, opts=None, sentinel=np.nan, ctx=None):
+    """The extended-precision path of an iteration of a lock-step unit, stage by stage (mbfir_test_unit_ddkkt, which says what every
+    block holds).  jobs: (designer, args) pairs, the lanes.  s, z: (lanes, R); bx: (lanes, nv, N); bz: (lanes, nv, R); nq3: the unit's
+    largest count of 3-row cones; ldu: the rows of U (and of Yt, Zt, S, Ms with cap_blocks) to return.  Every output block goes in
+    filled with `sentinel` (the integer blocks with -9).  Returns a dict of the blocks, rows named by UNIT_DDKKT_*, with lane_rep
+    (lanes, 4) and report (a dict of UNIT_DDKKT_REPORT)."""
+    ctx = ctx or get_context()
+    arr, keep = _pack_jobs(jobs)
+    s, z, bx, bz = [np.ascontiguousarray(a, dtype=np.float64) for a in (s, z, bx, bz)]
+    nl, R = len(jobs), s.shape[1]
+    if bx.ndim != 3 or bz.ndim != 3:
+        raise ValueError("bx, bz: (lanes, nv, N) and (lanes, nv, R)")
+    nv, N = bx.shape[1], bx.shape[2]
+    if s.shape != (nl, R) or z.shape != (nl, R) or bx.shape != (nl, nv, N) or bz.shape != (nl, nv, R):
+        raise ValueError("s, z, bx, bz have inconsistent shapes")
+    npad = -(-N // 64) * 64
+    # (the blocks of unknowns are np wide: the capacitance form's vectors are, and what lies past N shows there)
+    bx, N = np.concatenate([bx, np.zeros((nl, nv, npad - N))], axis=2), npad
+    nq = max(int(nq3), 1)
+    ldu = int(ldu)
+    full = lambda *shape: np.full(shape, sentinel, dtype=np.float64)
+    ints = lambda *shape: np.full(shape, -9, dtype=np.int32)
+    ldp = -(-R // 256) + 2
+    o = dict(sel_r=full(nl, 4, R), sel_q=full(nl, 18 * nq), sel_sc=full(nl, 16), sel_part=full(nl, ldp, 2), sel_i=ints(nl, R + 3 * nq + 3), strong_i=ints(nl, 3, DD_KMAX),
+             strong_x=full(nl, DD_KMAX), H=full(nl, npad, npad), U=full(nl, ldu, npad), M=full(nl, npad, npad), Hf=full(nl, npad, npad),
+             out_x=full(nl, 3, len(UNIT_DDKKT_OUT_X), 2, N), out_r=full(nl, 3, len(UNIT_DDKKT_OUT_R), 2, R),
+             out_k=full(nl, 3, len(UNIT_DDKKT_OUT_K), 2, DD_KMAX), sc=full(nl, 4, 9), end_x=full(nl, 2, N), end_r=full(nl, 2, 2, R))
+    if cap_blocks:
+        o.update(Yt=full(nl, ldu, npad), Zt=full(nl, ldu, npad), S=full(nl, ldu, ldu), Ms=full(nl, ldu, ldu))
+    flag = np.full(nl, -1, dtype=np.int64)
+    lane_rep, report = np.zeros((nl, 4), dtype=np.int64), np.zeros(16, dtype=np.int64)
+    mk = (C.c_int * nl)(*[int(m) for m in mask]) if mask is not None else None
+    op = opts if opts is not None else make_opts(ddkkt=1)
+    ipt = lambda a: a.ctypes.data_as(_ip)
+    cb = lambda k: _ptr(o[k]) if cap_blocks else None
+    rc = load_library().mbfir_test_unit_ddkkt(ctx._h, arr, nl, C.byref(op), int(nv), int(bool(solve)), N, R, npad, 4 * nq, ldu, ldp, mk, _ptr(s), _ptr(z),
+                                              _ptr(bx), _ptr(bz), _ptr(o["sel_r"]), _ptr(o["sel_q"]), _ptr(o["sel_sc"]), _ptr(o["sel_part"]), ipt(o["sel_i"]),
+                                              ipt(o["strong_i"]), _ptr(o["strong_x"]), _ptr(o["H"]), _ptr(o["U"]), _ptr(o["M"]), _ptr(o["Hf"]),
+                                              cb("Yt"), cb("Zt"), cb("S"), cb("Ms"), flag.ctypes.data_as(_lp), _ptr(o["out_x"]), _ptr(o["out_r"]),
+                                              _ptr(o["out_k"]), _ptr(o["sc"]), _ptr(o["end_x"]), _ptr(o["end_r"]), lane_rep.ctypes.data_as(_lp),
+                                              report.ctypes.data_as(_lp))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    o["flag"], o["lane_rep"] = flag, lane_rep
+    o["report"] = {k: int(v) for k, v in zip(UNIT_DDKKT_REPORT, report)}
     return o
 
 

@@ -748,6 +748,52 @@ int mbfir_test_unit_kkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const 
         return 0;
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
 }
+int mbfir_test_unit_ddkkt(mbfir_ctx* ctx, const mbfir_job* jobs, int njobs, const mbfir_opts* opts, int nv, int solve, int ldx, int ldr, int ldh,
+                          int ldw, int ldu, int ldp, const int* mask, const double* s, const double* z, const double* bx, const double* bz, double* sel_r,
+                          double* sel_q, double* sel_sc, double* sel_part, int* sel_i, int* strong_i, double* strong_x, double* H, double* U, double* M, double* Hf,
+                          double* Yt, double* Zt, double* S, double* Ms, long* flag, double* out_x, double* out_r, double* out_k, double* out_sc,
+                          double* end_x, double* end_r, long* lane_rep, long* report) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_unit_ddkkt: " + why; return MBFIR_E_ARG; };
+    // (nothing is allocated, copied or launched before every argument has passed)
+    if (!jobs || !s || !z || !bx || !bz || !sel_r || !sel_q || !sel_sc || !sel_part || !sel_i || !strong_i || !strong_x || !H || !U || !M || !Hf || !flag ||
+        !out_x || !out_r || !out_k || !out_sc || !end_x || !end_r || !lane_rep || !report)
+        return bad("bad argument");
+    if ((Yt == nullptr) != (Zt == nullptr) || (Yt == nullptr) != (S == nullptr) || (Yt == nullptr) != (Ms == nullptr)) return bad("Yt, Zt, S and Ms go together");
+    if (njobs < 1 || njobs > 64) return bad("the lane count must be 1 .. 64");
+    if (nv < 1 || nv > 2) return bad("one or two right-hand sides");
+    if (ldx < 1 || ldr < 1 || ldh < 64 || ldh % 64 != 0 || ldx > ldh || ldw < 4 || ldw % 4 != 0 || ldu < 64 || ldu > DK_KMAX || ldp < 1)
+        return bad("leading dimensions: 1 <= ldx <= ldh = np, a multiple of 64; ldr >= 1; ldw = 4 max(n_q3, 1); 64 <= ldu <= 3072; ldp >= 1");
+    try {
+        std::vector<TrigProgram> progs(njobs);
+        std::vector<const TrigProgram*> Ps;
+        for (int q = 0; q < njobs; ++q) {
+            std::string e;
+            if (assemble_job(jobs[q], opts ? opts->grid_m : 0, progs[q], e) != 0) return bad("job " + std::to_string(q) + ": " + e);
+            Ps.push_back(&progs[q]);
+        }
+        const SolveOpts so = to_opts(opts, progs[0].which);
+        if (so.shard_size > 1) return bad("row-sharded units are not taken");
+        if (!(so.ddkkt_theta > 0)) return bad("the unit is not on the extended-precision path (opts.ddkkt = 1)");
+        const char* env = std::getenv("MBFIR_DDFORM");
+        const bool dd_form = env ? std::string(env) == "dd" : so.dd_form != 0;                 // (the solve's own choice: read_switches, plan_unit)
+        if (dd_form && njobs > 1) return bad("the double-double form of the extended-precision solve runs one design at a time");
+        for (int q = 0; q < njobs; ++q) {
+            const TrigProgram& T = *Ps[q];
+            const int N = T.Nt + T.Ne, R = T.l + 3 * T.nq3 + T.big;
+            if (ldx < N || ldr < R || ldh != int((N + 63) / 64 * 64) || ldw < 4 * T.nq3)
+                return bad("job " + std::to_string(q) + ": ldx / ldr / ldh / ldw do not fit the design (N " + std::to_string(N) + ", R " + std::to_string(R) + ")");
+        }
+        UnitDdKkt io;
+        io.nv = nv; io.solve = solve; io.ldx = ldx; io.ldr = ldr; io.ldh = ldh; io.ldw = ldw; io.ldu = ldu; io.ldp = ldp; io.mask = mask; io.s = s; io.z = z;
+        io.bx = bx; io.bz = bz; io.sel_r = sel_r; io.sel_q = sel_q; io.sel_sc = sel_sc; io.sel_part = sel_part; io.sel_i = sel_i; io.strong_i = strong_i;
+        io.strong_x = strong_x; io.H = H; io.U = U; io.M = M; io.Hf = Hf; io.Yt = Yt; io.Zt = Zt; io.S = S; io.Ms = Ms; io.flag = flag;
+        io.out_x = out_x; io.out_r = out_r; io.out_k = out_k; io.out_sc = out_sc; io.end_x = end_x; io.end_r = end_r; io.lane_rep = lane_rep;
+        io.report = report;
+        ctx->solver->test_unit_ddkkt(Ps, so, io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll) {
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;

@@ -101,6 +101,24 @@ struct UnitKkt {
     long *flag = nullptr, *report = nullptr;
 };
 
+// Arguments of Solver::test_unit_ddkkt (mbfir_test_unit_ddkkt of include/mbfir.h, which says what each block holds): host arrays of
+// nlanes blocks each.  out_x / out_r / out_k: DK_PASSES passes of DK_OUT_X / DK_OUT_R / DK_OUT_K blocks of two vectors of ldx / ldr /
+// DK_KMAX (the second stays the caller's where nv = 1)
+enum { DKX_GTDZ = 0, DKX_R1, DKX_GTW, DKX_RHS_H, DKX_RHS_L, DKX_Y, DKX_BH, DKX_BL, DKX_DX, DK_OUT_X };
+enum { DKR_R2 = 0, DKR_WBZ, DKR_GBH, DKR_WBZ2, DKR_DZ, DKR_GDX, DK_OUT_R };
+enum { DKK_TS = 0, DKK_CAPW, DKK_ZETA, DK_OUT_K };
+enum { DK_PASSES = 3, DK_SC = 9 /* n_0 .. n_8 */, DK_SEL_R = 4, DK_SEL_SC = 16, DK_KMAX = 3072, UNIT_DDKKT_REPORT = 16 };
+struct UnitDdKkt {
+    int nv = 2, solve = 1, ldx = 0, ldr = 0, ldh = 0, ldw = 0, ldu = 0, ldp = 0;
+    const int* mask = nullptr;
+    const double *s = nullptr, *z = nullptr, *bx = nullptr, *bz = nullptr;
+    double *sel_r = nullptr, *sel_q = nullptr, *sel_sc = nullptr, *sel_part = nullptr, *strong_x = nullptr;
+    int *sel_i = nullptr, *strong_i = nullptr;
+    double *H = nullptr, *U = nullptr, *M = nullptr, *Hf = nullptr, *Yt = nullptr, *Zt = nullptr, *S = nullptr, *Ms = nullptr;
+    double *out_x = nullptr, *out_r = nullptr, *out_k = nullptr, *out_sc = nullptr, *end_x = nullptr, *end_r = nullptr;
+    long *flag = nullptr, *lane_rep = nullptr, *report = nullptr;
+};
+
 // Arguments of Solver::test_capsolve (mbfir_test_capsolve of include/mbfir.h, which says what each array holds and checks them)
 struct CapSolveIO {
     int n = 0, nlanes = 1, kp = 0, nrhs = 1, hsolve_form = -1;
@@ -148,6 +166,9 @@ public:
     // the residual kernels of an iterate and the plain KKT solve (or the initial point) of a lock-step unit at a caller's iterate and
     // right-hand sides, every group of launches of kkt_solve read back through its observer
     void test_unit_kkt(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitKkt& io);
+    // the extended-precision path of a lock-step unit at a caller's iterate and right-hand sides: the selection of the strong sets, the
+    // capped normal matrix with its strong rows, and every group of launches of kkt_solve_dd read back through its observer
+    void test_unit_ddkkt(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitDdKkt& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
     // the capacitance form of the extended-precision solve: the launches of its build and of one pass of its solve, for nlanes

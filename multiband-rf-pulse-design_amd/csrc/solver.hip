@@ -129,6 +129,10 @@ struct KktObserver {
     bool two_launch_cg = false;
     void operator()(int stage, int sweep) const { fn(stage, sweep); }
 };
+// kkt_solve_dd's optional observer (test_unit_ddkkt; the same struct, called with the group and the pass): the groups of launches of
+// one pass in their order.  DD_ST_Y .. DD_ST_ZETAC: the capacitance form alone; DD_ST_ZETA: the double-double form alone
+enum { DD_ST_R1 = 0, DD_ST_R2, DD_ST_WBZ, DD_ST_GTW, DD_ST_RHS, DD_ST_Y, DD_ST_CAPW, DD_ST_ZETAC, DD_ST_SOLVE, DD_ST_GBH, DD_ST_WBZ2, DD_ST_ZETA,
+       DD_ST_ACCUM };
 // the scalar slots: the auto-numbered ones end before the first norm block, each norm block holds n_0 .. n_MAX_SWEEPS
 static_assert(S_NPICK < S_RNA, "scalar slots: the auto-numbered slots run into S_RNA");
 static_assert(S_RNA + MAX_SWEEPS + 1 <= S_RNB && S_RNB + MAX_SWEEPS + 1 <= S_CG_RZ && S_RNC + MAX_SWEEPS + 1 <= S_SIGMAX,
@@ -3169,11 +3173,13 @@ struct Solver::Impl {
                 if (ks[b] > kmax_fit) { fits = false; hostTheta[b] *= 100.0; }
                 kmax = std::max(kmax, ks[b]);
             }
+            dd_attempts = attempt + 1;
             if (fits) return kmax;
         }
         throw HipError("extended-precision solve: strong set does not fit");
     }
-    double hostTheta[MAX_LANES];
+    double hostTheta[MAX_LANES];        // the lanes' cap factors as the last selection used them
+    int dd_attempts = 0;                // ... and the number of selections it took
     double* ddtheta = nullptr;          // the lanes' cap factors (lane 0's arena; read unshifted)
     bool dd_unit = false;               // a lock-step unit on the extended-precision path (some of its lanes, some iterations)
     int dd_kp = 0;                      // ... the largest strong set of this iteration, rounded up to 64 (the unit's S is dd_kp x dd_kp)
@@ -3185,6 +3191,7 @@ struct Solver::Impl {
             hipLaunchKernelGGL(k_dd_order, dim3(1), dim3(1024), 0, st, P, D);
             MBFIR_HIP(hipMemcpyAsync(hostFlag + 1, D.kcnt, sizeof(int), hipMemcpyDeviceToHost, st));
             MBFIR_HIP(hipStreamSynchronize(st));
+            hostTheta[0] = theta; dd_attempts = attempt + 1;  // (test_unit_ddkkt reports them)
             if (hostFlag[1] <= (cap_form ? CAP_KMAX : DD_KMAX)) return hostFlag[1];
             theta *= 100.0;                                   // more strong directions than U has rows (or than S takes): raise the cap
         }
@@ -3193,8 +3200,10 @@ struct Solver::Impl {
     // [0 G'; G -W^2][dx; dz] = [bx; bz] by iterative refinement around the double-double normal-equation solve
     // (mirrors oracle/conic_ipm.py kkt_solve_dd, nref = 2).  Residual norms ||bx - G'dz|| before each pass go
     // to Sc[slot ..].
+    // obs (test_unit_ddkkt; null in every solve): called on the host after each group of launches below with the group's number
+    // (DD_ST_*) and the pass
     template <int NV>
-    void kkt_solve_dd(const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot) {
+    void kkt_solve_dd(const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot, const KktObserver* obs = nullptr) {
         const dim3 gC(std::max(nbC, 1)), b256(256);
         // (lock-step units: the launches carry the unit's largest strong set, every lane reads its own count from its arena)
         const int k = dd_unit ? dd_kp : dd_k;
@@ -3206,33 +3215,47 @@ struct Solver::Impl {
         for (int it = 0; it < dd_passes; ++it) {
             apply_GT<NV>(dz, tmpN);
             hipLaunchKernelGGL(k_resid_norm<NV>, lane_grid(dim3(1), nlanes), dim3(SCAL_T), 0, st, P, bx, tmpN, rhsN, Sc, slot + it);   // r1 = bx - G'dz
+            if (obs) (*obs)(DD_ST_R1, it);
             hipLaunchKernelGGL(k_dd_r2<NV>, lane_grid(gC, nlanes), b256, 0, st, P, D, dl, bz, gdx, dz, tmpR, ddtS);                  // r2, t
             if (P.big) hipLaunchKernelGGL(k_dd_r2_big<NV>, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, D, bz, gdx, dz, tmpR, ddtS, scratch);
+            if (obs) (*obs)(DD_ST_R2, it);
             hipLaunchKernelGGL(k_dd_winv2c<NV>, lane_grid(gC, nlanes), b256, 0, st, P, D, tmpR, (const double*)nullptr, wbz);
             if (P.big) hipLaunchKernelGGL(k_dd_winv2c_big<NV>, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, D, tmpR, (const double*)nullptr, wbz, scratch);
+            if (obs) (*obs)(DD_ST_WBZ, it);
             apply_GT<NV>(wbz, tmpN2);
+            if (obs) (*obs)(DD_ST_GTW, it);
             if (cap_form) {
                 // y = H_w^-1 rhs_w ; zeta = S^-1 (U y - t) ; dx = y - Zt' zeta   (all double; zeta are the strong directions'
                 // multipliers X (U dx - t) themselves)
                 int kp = int(round_up(k, 64));
                 if (!dd_unit) kp = std::max(kp, sw.test_cap_kp);                                 // test hook: pad S as a unit's largest lane would
                 cap_add_launch(rhsN, tmpN2, Bl, P.N, P.np, P.LDV, NV, st, nlanes, lane_bytes, P.mask);                       // rhs_w
+                if (obs) (*obs)(DD_ST_RHS, it);
                 double* yv = tmpN2;                                                              // (free from here on; yN is hsolve's own intermediate)
                 hsolve<NV>(Bl, yv);                                                              // y
+                if (obs) (*obs)(DD_ST_Y, it);
                 cap_uy_launch(D.U, k, kp, P.N, P.np, yv, P.LDV, ddtS, capw, DD_KMAX, NV, st, nlanes, lane_bytes, P.mask, kcnt);
+                if (obs) (*obs)(DD_ST_CAPW, it);
                 hsolve_launch(capMs, kp, capw, nullptr, ddzeta, partial, NV, DD_KMAX, st, nlanes, lane_bytes, P.mask);       // zeta
+                if (obs) (*obs)(DD_ST_ZETAC, it);
                 cap_dx_launch(capZt, k, P.N, P.np, ddzeta, DD_KMAX, yv, Bh, P.LDV, NV, st, nlanes, lane_bytes, P.mask, kcnt);      // the correction of this pass
             } else {
             hipLaunchKernelGGL(k_dd_rhs<NV>, lane_grid(dim3(cdiv(P.np, 16)), nlanes), b256, 0, st, P, D, k, rhsN, tmpN2, ddtS, Bh, Bl);
+            if (obs) (*obs)(DD_ST_RHS, it);
             dd_trsv_launch(H, M, Mt, W1, ddri, ddri + P.np, P.np, Bh, Bl, NV, P.LDV, st, ddflags, ++dd_epoch, flag, ddinv);
             }
+            if (obs) (*obs)(DD_ST_SOLVE, it);
             apply_G<NV>(Bh, wpR);
+            if (obs) (*obs)(DD_ST_GBH, it);
             hipLaunchKernelGGL(k_dd_winv2c<NV>, lane_grid(gC, nlanes), b256, 0, st, P, D, wpR, tmpR, wbz);
             if (P.big) hipLaunchKernelGGL(k_dd_winv2c_big<NV>, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, D, wpR, tmpR, wbz, scratch);
+            if (obs) (*obs)(DD_ST_WBZ2, it);
             if (!cap_form) hipLaunchKernelGGL(k_dd_zeta<NV>, lane_grid(dim3(k), nlanes), dim3(64), 0, st, P, D, Bh, Bl, ddtS, ddzeta);
+            if (obs && !cap_form) (*obs)(DD_ST_ZETA, it);
             hipLaunchKernelGGL(k_dd_accum<NV>, lane_grid(gC, nlanes), b256, 0, st, P, D, wbz, wpR, ddzeta, dz, gdx);
             if (P.big) hipLaunchKernelGGL(k_dd_accum_big<NV>, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, D, wbz, wpR, ddzeta, dz, gdx);
             hipLaunchKernelGGL(k_dd_accum_x<NV>, lane_grid(dim3(nbN), nlanes), b256, 0, st, P, Bh, dx);
+            if (obs) (*obs)(DD_ST_ACCUM, it);
         }
     }
     // H = G' W^-2 G from the current scaling, then Cholesky + inverse.  Timing events are pooled
@@ -3263,6 +3286,7 @@ struct Solver::Impl {
     // then H = H_w + U'XU and its Cholesky factor in double-double
     double* H_keep = nullptr;    // test_unit_ops: where build_H copies the lanes' H (np x np each, one after the other) ahead of the factorisation
     bool h_one_pass = false;     // the last build_H took its one_pass branch
+    double* capS_keep = nullptr; // test_unit_ddkkt: where build_H copies the lanes' capacitance matrices (kp x kp each) ahead of their factorisation
     void build_H(int ddk = 0) {
         double* yy_sum = nullptr;
         const double* dlw = ddk > 0 ? D.dlc : dl;
@@ -3434,6 +3458,9 @@ struct Solver::Impl {
             if (b0) hipEventRecord(b0, st);
             cap_build_launch(D.U, dd_unit ? kp : ddk, kp, P.np, M, D.sX, capYt, capZt, capS, capPart, st, nlanes, lb, mdd, dd_unit ? D.kcnt : nullptr);
             if (b1) hipEventRecord(b1, st);
+            // (test_unit_ddkkt: every lane's S as its factorisation is about to find it -- the factorisation works in place)
+            if (capS_keep) MBFIR_HIP(hipMemcpy2DAsync(capS_keep, sizeof(double) * kp * kp, capS, nlanes > 1 ? lane_bytes : sizeof(double) * kp * kp,
+                                                      sizeof(double) * kp * kp, nlanes, hipMemcpyDeviceToDevice, st));
             // Yt and Zt: kp x np x np / 2 multiply-adds each (triangular M); S: kp x kp x np / 2 (lower tiles)
             cap_flop_sum += 2.0 * (double(kp) * P.np * P.np + 0.5 * double(kp) * kp * P.np);
             chol_inv_launch(capS, capMs, nullptr, capW1, kp, capflag, st, sw.chol_split, sw.poison, nullptr, nullptr, c1, nlanes, lb, mdd);
@@ -3818,11 +3845,12 @@ struct Solver::Impl {
     // the KKT solve of one right-hand side block on every live lane: the extended-precision solve where the strong set is non-empty,
     // the plain one with `nsweep` refinement sweeps elsewhere, each under its mask (every lane the sequence of its single solve)
     template <int NV>
-    void solve_modes(bool dd_any, bool pl_any, const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot, int nsweep) {
+    void solve_modes(bool dd_any, bool pl_any, const double* bx, const double* bz, double* dx, double* dz, double* gdx, int slot, int nsweep,
+                     const KktObserver* dd_obs = nullptr) {
         const int* live_row = P.mask;
         if (dd_any) {
             if (dd_unit) P.mask = mask_row(ROW_DD);
-            kkt_solve_dd<NV>(bx, bz, dx, dz, gdx, slot);
+            kkt_solve_dd<NV>(bx, bz, dx, dz, gdx, slot, dd_obs);
         }
         if (pl_any) {
             if (dd_unit) P.mask = mask_row(ROW_PL);
@@ -4718,6 +4746,216 @@ void Solver::test_unit_kkt(const std::vector<const TrigProgram*>& Qs, const Solv
     r[7] = nlanes; r[8] = P.dims ? 1 : 0; r[9] = P.trig; r[10] = cdiv(P.Nt, GTC) + 1; r[11] = nv; r[12] = io.two ? 1 : 0;
     r[13] = io.wbz_ready ? 1 : 0; r[14] = initial ? 1 : 0; r[15] = ns_max; r[16] = P.l; r[17] = P.nq3; r[18] = S.nbR; r[19] = z_written ? 1 : 0;
     r[20] = S.n_gv; r[21] = S.n_gtv;
+}
+
+// The extended-precision path of one unit at a caller's iterate (include/mbfir.h: mbfir_test_unit_ddkkt).  The unit is set up by the
+// stages of solve_lanes (setup_unit); launch_scaling, dd_prepare / dd_prepare_lanes, push_masks, build_H(dd_k) and solve_modes run as
+// launch_head and launch_iteration run them, kkt_solve_dd with an observer that enqueues the copies of what each group of launches
+// wrote and sends the caller's sentinels into the buffers the next group writes -- on the lanes in the extended-precision mode alone:
+// a lane in the plain mode keeps W^-2 bz from the scaling in the buffer the other lanes' passes write.  The one synchronisation is the
+// selection's own.
+void Solver::test_unit_ddkkt(const std::vector<const TrigProgram*>& Qs, const SolveOpts& o, const UnitDdKkt& io) {
+    static_assert(DK_KMAX == DD_KMAX && DK_SC == MAX_SWEEPS + 1, "solver.h: the blocks of UnitDdKkt do not fit the solver's");
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int nlanes = int(Qs.size()), nv = io.nv;
+    if (nlanes < 1 || nlanes > MAX_LANES) throw ShapeError("lock-step batch: bad lane count");
+    std::vector<LaneHost> LH(nlanes);
+    for (int b = 0; b < nlanes; ++b) LH[b].live = !io.mask || io.mask[b] != 0;
+    S.setup_unit(Qs, o, LH);
+    S.evused = 0; S.capev_used = 0; S.cap_flop_sum = 0;
+    S.timing = false;
+    S.chol_launch_count = 0; S.dd_epoch = 0;
+    S.taps_valid = false;
+    const DProg& P = S.P;
+    const int nq = std::max(P.nq3, 1), nbig = std::max(P.big, 1), nl1 = std::max(P.l, 1);
+    if (io.ldx < P.N || io.ldx > P.LDV || io.ldr < P.R || io.ldr > P.Rp || io.ldh != P.np || io.ldw != 4 * nq || io.ldu < 64 || io.ldu > DD_KMAX || io.ldp < 1)
+        throw HipError("test_unit_ddkkt: ldx / ldr / ldh / ldw / ldu do not fit the unit (N " + std::to_string(P.N) + ", R " + std::to_string(P.R) + ", np " +
+                       std::to_string(P.np) + ", n_q3 " + std::to_string(P.nq3) + ", rows of U 64 .. " + std::to_string(DD_KMAX) + ")");
+    const size_t ldx = io.ldx, ldr = io.ldr, ldu = io.ldu, np = P.np, np2 = np * np, ldi = ldr + 3 * (size_t)nq + 3;
+    auto lane = [&](const void* p, int b) { return reinterpret_cast<char*>(const_cast<void*>(p)) + (size_t)b * S.lane_bytes; };
+    auto h2d = [&](const void* dst, const void* src, size_t bytes, int b) { MBFIR_HIP(hipMemcpyAsync(lane(dst, b), src, bytes, hipMemcpyHostToDevice, S.st)); };
+    auto d2h = [&](void* dst, const void* src, size_t bytes, int b) { MBFIR_HIP(hipMemcpyAsync(dst, lane(src, b), bytes, hipMemcpyDeviceToHost, S.st)); };
+    const size_t D8 = sizeof(double), I4 = sizeof(int);
+    double *bx = nv == 2 ? S.bx2 : S.bxc, *bz = nv == 2 ? S.bz2 : S.bzc, *dx = nv == 2 ? S.dx2 : S.dxc, *dz = nv == 2 ? S.dz2 : S.dzc,
+           *gdx = nv == 2 ? S.gdx2 : S.gdxc;
+    const int slot = nv == 2 ? S_RNA : S_RNB;
+    // ---- the iterate and the right-hand sides; the norm slots hold the caller's sentinel until a kernel writes them --------------------
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        h2d(S.s, io.s + (size_t)b * ldr, ldr * D8, b); h2d(S.z, io.z + (size_t)b * ldr, ldr * D8, b);
+        for (int v = 0; v < nv; ++v) {
+            h2d(bx + (size_t)v * P.LDV, io.bx + ((size_t)b * nv + v) * ldx, ldx * D8, b);
+            h2d(bz + (size_t)v * P.Rp, io.bz + ((size_t)b * nv + v) * ldr, ldr * D8, b);
+        }
+        h2d(S.Sc + slot, io.out_sc + (size_t)b * (DK_PASSES + 1) * DK_SC, (MAX_SWEEPS + 1) * D8, b);
+    }
+    // ---- the head of an iteration: scaling, strong sets (the one synchronisation), masks ------------------------------------------------
+    S.launch_scaling();
+    int ks[MAX_LANES] = {0};
+    if (S.dd_unit) {
+        bool lv[MAX_LANES];
+        for (int b = 0; b < nlanes; ++b) lv[b] = LH[b].live;
+        S.dd_k = S.dd_prepare_lanes(o.ddkkt_theta, ks, lv);
+        S.dd_kp = int(round_up(std::max(S.dd_k, 1), 64));
+    } else {
+        ks[0] = S.dd_k = S.dd_prepare(o.ddkkt_theta);
+    }
+    for (int b = 0; b < nlanes; ++b) LH[b].dd_k = LH[b].live ? ks[b] : 0;
+    S.push_masks(LH);
+    const bool dd_any = S.dd_k > 0;
+    bool pl_any = S.dd_k == 0;
+    if (S.dd_unit) {
+        pl_any = false;
+        for (int b = 0; b < nlanes; ++b) pl_any = pl_any || (LH[b].live && LH[b].dd_k == 0);
+    }
+    const int kp = !dd_any ? 0 : !S.cap_form ? S.dd_k : S.dd_unit ? S.dd_kp : std::max(int(round_up(S.dd_k, 64)), S.sw.test_cap_kp);
+    const size_t rows_u = std::min<size_t>(kp, ldu);
+    const int nbp = std::max(S.nbC, 1) + (P.big ? 1 : 0);
+    auto ddl = [&](int b) { return LH[b].live && LH[b].dd_k > 0; };
+    // what the selection left, every live lane
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        double* r = io.sel_r + (size_t)b * DK_SEL_R * ldr;
+        d2h(r, S.dl, nl1 * D8, b); d2h(r + ldr, S.D.dlc, nl1 * D8, b); d2h(r + 2 * ldr, S.wbb, nbig * D8, b); d2h(r + 3 * ldr, S.D.whb, nbig * D8, b);
+        double* q = io.sel_q + (size_t)b * 18 * nq;
+        d2h(q, S.w3, 4 * nq * D8, b); d2h(q + 4 * nq, S.D.e3, 8 * nq * D8, b); d2h(q + 12 * nq, S.D.m3c, 6 * nq * D8, b);
+        double* sc = io.sel_sc + (size_t)b * DK_SEL_SC;
+        d2h(sc, S.D.eb, 8 * D8, b); d2h(sc + 8, S.Sc + S_ETAB, D8, b);
+        // the partial rows of (sum log, count) the selection folds: the big cone's first, then k_dd_prep's blocks
+        d2h(io.sel_part + (size_t)b * 2 * io.ldp, S.partR, 2 * (size_t)std::min(nbp, io.ldp) * D8, b);
+        int* si = io.sel_i + (size_t)b * ldi;
+        d2h(si, S.D.slotl, nl1 * I4, b); d2h(si + ldr, S.D.slot3, 3 * nq * I4, b); d2h(si + ldr + 3 * nq, S.D.slotb, 2 * I4, b);
+        d2h(si + ldr + 3 * nq + 2, S.D.kcnt, I4, b);
+        const size_t kb = std::min(ks[b], DD_KMAX);
+        int* st = io.strong_i + (size_t)b * 3 * DD_KMAX;
+        d2h(st, S.D.skind, kb * I4, b); d2h(st + DD_KMAX, S.D.sidx, kb * I4, b); d2h(st + 2 * DD_KMAX, S.D.sdir, kb * I4, b);
+        d2h(io.strong_x + (size_t)b * DD_KMAX, S.D.sX, kb * D8, b);
+    }
+    // ---- the capped normal matrix: H ahead of the factorisation, the rows of U over the caller's sentinel, the capacitance matrices --------
+    DevBuf keep(np2 * D8 * nlanes), keepS(S.cap_form && dd_any ? (size_t)kp * kp * D8 * nlanes : 8);
+    if (dd_any)
+        for (int b = 0; b < nlanes; ++b)
+            if (LH[b].live) h2d(S.D.U, io.U + (size_t)b * ldu * np, rows_u * np * D8, b);
+    S.H_keep = keep.as<double>();
+    if (S.cap_form && dd_any) S.capS_keep = keepS.as<double>();
+    try { S.build_H(S.dd_k); } catch (...) { S.H_keep = nullptr; S.capS_keep = nullptr; throw; }
+    S.H_keep = nullptr; S.capS_keep = nullptr;
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        MBFIR_HIP(hipMemcpyAsync(io.H + (size_t)b * np2, keep.as<double>() + (size_t)b * np2, np2 * D8, hipMemcpyDeviceToHost, S.st));
+        if (dd_any) d2h(io.U + (size_t)b * ldu * np, S.D.U, rows_u * np * D8, b);
+        if (!(S.cap_form && ddl(b) && io.Yt)) continue;
+        d2h(io.Yt + (size_t)b * ldu * np, S.capYt, rows_u * np * D8, b); d2h(io.Zt + (size_t)b * ldu * np, S.capZt, rows_u * np * D8, b);
+        MBFIR_HIP(hipMemcpy2DAsync(io.S + (size_t)b * ldu * ldu, ldu * D8, keepS.as<double>() + (size_t)b * kp * kp, (size_t)kp * D8, rows_u * D8, rows_u,
+                                   hipMemcpyDeviceToHost, S.st));
+        MBFIR_HIP(hipMemcpy2DAsync(io.Ms + (size_t)b * ldu * ldu, ldu * D8, lane(S.capMs, b), (size_t)kp * D8, rows_u * D8, rows_u, hipMemcpyDeviceToHost, S.st));
+    }
+    // ---- the solve: kkt_solve_dd under ROW_DD with the observer, the plain kkt_solve under ROW_PL ------------------------------------------
+    struct Blk { double* dev; int space, blk; };            // space 0: rows (Rp apart), 1: unknowns (LDV apart), 2: strong slots (DD_KMAX apart)
+    auto X_ = [&](double* dev, int blk) { return Blk{dev, 1, blk}; };
+    auto R_ = [&](double* dev, int blk) { return Blk{dev, 0, blk}; };
+    auto K_ = [&](double* dev, int blk) { return Blk{dev, 2, blk}; };
+    auto host_of = [&](const Blk& q, int b, int pass, int v) {
+        const size_t lp = (size_t)b * DK_PASSES + pass;
+        return q.space == 1 ? io.out_x + (((lp * DK_OUT_X) + q.blk) * 2 + v) * ldx
+             : q.space == 0 ? io.out_r + (((lp * DK_OUT_R) + q.blk) * 2 + v) * ldr
+                            : io.out_k + (((lp * DK_OUT_K) + q.blk) * 2 + v) * (size_t)DD_KMAX;
+    };
+    auto dstride = [&](const Blk& q) { return q.space == 1 ? (size_t)P.LDV : q.space == 0 ? (size_t)P.Rp : (size_t)DD_KMAX; };
+    auto hlen = [&](const Blk& q) { return q.space == 1 ? ldx : q.space == 0 ? ldr : (size_t)DD_KMAX; };
+    auto plant = [&](int pass, const std::vector<Blk>& bs) {
+        if (pass >= DK_PASSES) return;
+        for (int b = 0; b < nlanes; ++b)
+            for (const Blk& q : bs)
+                for (int v = 0; ddl(b) && v < nv; ++v) h2d(q.dev + (size_t)v * dstride(q), host_of(q, b, pass, v), hlen(q) * D8, b);
+    };
+    auto grab = [&](int pass, const std::vector<Blk>& bs) {
+        if (pass >= DK_PASSES) return;
+        for (int b = 0; b < nlanes; ++b)
+            for (const Blk& q : bs)
+                for (int v = 0; ddl(b) && v < nv; ++v) d2h(host_of(q, b, pass, v), q.dev + (size_t)v * dstride(q), hlen(q) * D8, b);
+    };
+    double *Bh = S.ddB, *Bl = S.ddB + 2L * P.LDV;
+    const bool cap = S.cap_form;
+    KktObserver obs;
+    obs.fn = [&](int stage, int q) {
+        switch (stage) {
+            case DD_ST_R1:
+                grab(q, {X_(S.tmpN, DKX_GTDZ), X_(S.rhsN, DKX_R1)});
+                for (int b = 0; q < DK_PASSES && b < nlanes; ++b)
+                    if (ddl(b)) d2h(io.out_sc + ((size_t)b * (DK_PASSES + 1) + q) * DK_SC, S.Sc + slot, (MAX_SWEEPS + 1) * D8, b);
+                plant(q, {R_(S.tmpR, DKR_R2), K_(S.ddtS, DKK_TS)});
+                break;
+            case DD_ST_R2: grab(q, {R_(S.tmpR, DKR_R2), K_(S.ddtS, DKK_TS)}); plant(q, {R_(S.wbz, DKR_WBZ)}); break;
+            case DD_ST_WBZ: grab(q, {R_(S.wbz, DKR_WBZ)}); plant(q, {X_(S.tmpN2, DKX_GTW)}); break;
+            case DD_ST_GTW:
+                grab(q, {X_(S.tmpN2, DKX_GTW)});
+                if (cap) plant(q, {X_(Bl, DKX_RHS_L)}); else plant(q, {X_(Bh, DKX_RHS_H), X_(Bl, DKX_RHS_L)});
+                break;
+            case DD_ST_RHS:
+                if (cap) { grab(q, {X_(Bl, DKX_RHS_L)}); plant(q, {X_(S.tmpN2, DKX_Y)}); }
+                else grab(q, {X_(Bh, DKX_RHS_H), X_(Bl, DKX_RHS_L)});
+                break;
+            case DD_ST_Y: grab(q, {X_(S.tmpN2, DKX_Y)}); plant(q, {K_(S.capw, DKK_CAPW)}); break;
+            case DD_ST_CAPW: grab(q, {K_(S.capw, DKK_CAPW)}); plant(q, {K_(S.ddzeta, DKK_ZETA)}); break;
+            case DD_ST_ZETAC: grab(q, {K_(S.ddzeta, DKK_ZETA)}); plant(q, {X_(Bh, DKX_BH)}); break;
+            case DD_ST_SOLVE:
+                grab(q, {X_(Bh, DKX_BH)}); if (!cap) grab(q, {X_(Bl, DKX_BL)});
+                plant(q, {R_(S.wpR, DKR_GBH)});
+                break;
+            case DD_ST_GBH: grab(q, {R_(S.wpR, DKR_GBH)}); plant(q, {R_(S.wbz, DKR_WBZ2)}); break;
+            case DD_ST_WBZ2: grab(q, {R_(S.wbz, DKR_WBZ2)}); if (!cap) plant(q, {K_(S.ddzeta, DKK_ZETA)}); break;
+            case DD_ST_ZETA: grab(q, {K_(S.ddzeta, DKK_ZETA)}); break;
+            case DD_ST_ACCUM:
+                grab(q, {R_(dz, DKR_DZ), R_(gdx, DKR_GDX), X_(dx, DKX_DX)});
+                if (q + 1 < S.dd_passes) plant(q + 1, {X_(S.tmpN, DKX_GTDZ), X_(S.rhsN, DKX_R1)});
+                break;
+            default: break;
+        }
+    };
+    int ns_plain = 0;
+    for (int b = 0; b < nlanes; ++b)
+        if (LH[b].live) ns_plain = std::max(ns_plain, LH[b].nsweep);
+    if (io.solve) {
+        if (pl_any && nv == 1) {
+            // (the combined solve's W^-2 bz comes with k_comb_rhs in an iteration: here for the lanes in the plain mode)
+            const int* live_row = S.P.mask;
+            if (S.dd_unit) S.P.mask = S.mask_row(ROW_PL);
+            S.winv2<1>(bz, nullptr, S.wbz, 0);
+            S.P.mask = live_row;
+        }
+        if (dd_any) plant(0, {X_(S.tmpN, DKX_GTDZ), X_(S.rhsN, DKX_R1)});
+        if (nv == 2) S.solve_modes<2>(dd_any, pl_any, bx, bz, dx, dz, gdx, slot, ns_plain, &obs);
+        else S.solve_modes<1>(dd_any, pl_any, bx, bz, dx, dz, gdx, slot, ns_plain, &obs);
+    }
+    // what the solve leaves, every live lane: the factor (double-double form: its high and low parts), the pivot counter, the solution
+    std::vector<int> fl(nlanes, 0);
+    for (int b = 0; b < nlanes; ++b) {
+        if (!LH[b].live) continue;
+        d2h(io.M + (size_t)b * np2, S.M, np2 * D8, b); d2h(io.Hf + (size_t)b * np2, S.H, np2 * D8, b);
+        d2h(&fl[b], S.flag, I4, b);
+        if (!io.solve) continue;
+        for (int v = 0; v < nv; ++v) {
+            d2h(io.end_x + ((size_t)b * 2 + v) * ldx, dx + (size_t)v * P.LDV, ldx * D8, b);
+            d2h(io.end_r + (((size_t)b * 2 + 0) * 2 + v) * ldr, dz + (size_t)v * P.Rp, ldr * D8, b);
+            d2h(io.end_r + (((size_t)b * 2 + 1) * 2 + v) * ldr, gdx + (size_t)v * P.Rp, ldr * D8, b);
+        }
+        d2h(io.out_sc + ((size_t)b * (DK_PASSES + 1) + DK_PASSES) * DK_SC, S.Sc + slot, (MAX_SWEEPS + 1) * D8, b);
+    }
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+    for (int b = 0; b < nlanes; ++b) {
+        long* lr = io.lane_rep + 4 * (size_t)b;
+        lr[0] = !LH[b].live ? 0 : LH[b].dd_k > 0 ? 1 : 2; lr[1] = LH[b].dd_k; lr[2] = LH[b].live ? S.dd_attempts : 0; lr[3] = LH[b].live ? nbp : 0;
+        if (!LH[b].live) continue;
+        io.flag[b] = fl[b];
+        io.sel_sc[(size_t)b * DK_SEL_SC + 9] = S.hostTheta[b];
+    }
+    long* r = io.report;
+    for (int i = 0; i < UNIT_DDKKT_REPORT; ++i) r[i] = 0;
+    r[0] = kp; r[1] = cap ? 1 : 0; r[2] = S.dd_passes; r[3] = nlanes; r[4] = P.N; r[5] = P.R; r[6] = P.np; r[7] = P.l; r[8] = P.nq3; r[9] = P.big;
+    r[10] = S.dd_k; r[11] = S.dd_attempts; r[12] = nv; r[13] = io.solve ? 1 : 0; r[14] = P.dims ? 1 : 0; r[15] = ns_plain;
 }
 
 void Solver::test_chol(int n, const double* Hh, double* out_l, double* out_m) {
