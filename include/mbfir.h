@@ -337,6 +337,24 @@ int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                          const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff,
                          const double* y, int nscale, const double* scales, int mode, const double* ca_re, const double* ca_im,
                          const double* cb_re, const double* cb_im, double* g_re, double* g_im);
+/* ---- Adjoints of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples and the gradient waveform ----------------------
+ * mbfir_abr_vjp_batch / mbfir_abr2_vjp_batch with one more output (1D: gg) or two (2D: ggx, ggy) of one entry per rf sample, laid
+ * out as g / gx / gy: gg = dL/dg, ggx = dL/dgx, ggy = dL/dgy.  The precession angle of a sample at a point is x g (1D) or x gx +
+ * y gy (2D), so a sample's entry is the sum over the points of its pulse of the point's coordinate times dL/d(angle), summed over
+ * the scales without a factor (a scale multiplies rf, not g).  A NULL g / gx / gy is differentiated at its default (2 pi / n per
+ * sample; gy = 0) and the gradient is returned all the same.  g_re / g_im are the rf gradient of the calls above to rounding (the
+ * sums run in another order), not to the bit.  One upload, two launches (the sweeps with one partial per workgroup, sample and
+ * component; then the sum of a pulse's partials over chunks and scales in index order), one download; no atomics, so the bits of
+ * both gradients depend only on the pulse, its grid and the scale list.  Argument checks and MBFIR_E_ARG messages as above. */
+int mbfir_abr_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                            int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                            const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im, double* g_re,
+                            double* g_im, double* gg);
+int mbfir_abr2_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                             const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                             const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
+                             const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im,
+                             double* ggx, double* ggy);
 /* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
  * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
  * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the

@@ -132,6 +132,10 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
                                        _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
+                                          _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
+                                           C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp,
                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
@@ -1398,6 +1402,22 @@ def abr_vjp_batch(pulses, x, cot, *, scales=(1.0,), hard_pulse=False, convention
     return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
 
 
+def abr_vjp_rfg_batch(pulses, x, cot, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The adjoint of abr_batch with respect to rf and to the gradient waveform g (mbfir_abr_vjp_rfg_batch):
+    arguments as abr_vjp_batch.  Returns one (grad_rf, grad_g) per pulse: grad_rf as abr_vjp_batch returns it (equal to rounding,
+    not to the bit), and grad_g the real (n,) gradient dL/dg, the sum over the points of x times dL/d(x g), summed over the scales
+    without a factor (a scale multiplies rf, not g).  A pulse given without g is differentiated at the default 2 pi / n.
+    Deterministic as abr_vjp_batch.  x and the scales are not differentiated."""
+    sc, rfs, gs, xs, nx = _abr_args("abr_vjp_rfg_batch", pulses, x, scales, convention)
+    planes = _cotangents("abr_vjp_rfg_batch", cot, [(len(sc), k) for k in nx], convention)
+    roff = _offsets([len(r) for r in rfs])
+    grad = [np.zeros(int(roff[-1])) for _ in range(3)]
+    ctx = ctx or get_context()
+    _abr_call(load_library().mbfir_abr_vjp_rfg_batch, ctx, sc, rfs, gs, xs, hard_pulse, planes + grad)
+    g_all = grad[0] + 1j * grad[1]
+    return [(g_all[roff[q]:roff[q + 1]], grad[2][roff[q]:roff[q + 1]]) for q in range(len(rfs))]
+
+
 def _tangents(who, tangents, rfs):
     """tangents: per pulse a complex (n,) or (K, n) array, the same K for every pulse -> (K, whether the K axis is kept, the two
     concatenated planes of the C call: direction-major within a pulse)."""
@@ -1528,6 +1548,20 @@ def abr2_vjp_batch(pulses, x, y, cot, *, scales=(1.0,), hard_pulse=False, conven
     _abr2_call(load_library().mbfir_abr2_vjp_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes + grad)
     g_all = grad[0] + 1j * grad[1]
     return [g_all[roff[q]:roff[q + 1]] for q in range(len(rfs))]
+
+
+def abr2_vjp_rfg_batch(pulses, x, y, cot, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):
+    """The adjoint of abr2_batch with respect to rf and to the complex gradient waveform g (mbfir_abr2_vjp_rfg_batch): as
+    abr_vjp_rfg_batch, with abr2_vjp_batch's arguments.  grad_g is the complex (n,) dL/dgx + i dL/dgy = dL/dRe g + i dL/dIm g
+    (torch's convention for a complex input).  x, y and the scales are not differentiated."""
+    sc, rfs, gs, xs, ys, nx, ny = _abr2_args("abr2_vjp_rfg_batch", pulses, x, y, scales, convention)
+    planes = _cotangents("abr2_vjp_rfg_batch", cot, [(len(sc), k, j) for k, j in zip(nx, ny)], convention)
+    roff = _offsets([len(r) for r in rfs])
+    grad = [np.zeros(int(roff[-1])) for _ in range(4)]
+    ctx = ctx or get_context()
+    _abr2_call(load_library().mbfir_abr2_vjp_rfg_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes + grad)
+    g_all, gg_all = grad[0] + 1j * grad[1], grad[2] + 1j * grad[3]
+    return [(g_all[roff[q]:roff[q + 1]], gg_all[roff[q]:roff[q + 1]]) for q in range(len(rfs))]
 
 
 def abr2_jvp_batch(pulses, x, y, tangents, *, scales=(1.0,), hard_pulse=False, convention="abrm", ctx=None):

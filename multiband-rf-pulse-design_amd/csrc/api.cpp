@@ -1124,6 +1124,56 @@ int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
                                       yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im));
 }
 
+// The rf and g adjoints keep up to two double2 per (workgroup, sample): the rf pair and the g component(s).
+static bool vjp_rfg_partials_fit(int npulse, int nscale, const long* roff, const long* npoint) {
+    long total = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e;
+        if (__builtin_mul_overflow((npoint[p] + 255) / 256 * nscale, roff[p + 1] - roff[p], &e) ||
+            __builtin_add_overflow(total, e, &total))
+            return false;
+    }
+    return total <= (1L << 55);
+}
+
+int mbfir_abr_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* g,
+                            int nxgrid, const long* xoff, const double* x, int nscale, const double* scales, int mode,
+                            const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im, double* g_re,
+                            double* g_im, double* gg) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && scales && ca_re && ca_im && cb_re && cb_im && g_re && g_im && gg;
+    if (const int e = abr_batch_check(ctx, "abr_vjp_rfg_batch", false, npulse, roff, nxgrid, xoff, 1, nullptr, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (!vjp_rfg_partials_fit(npulse, nscale, roff, npoint.data())) {
+        ctx->err = "abr_vjp_rfg_batch: the output size or the workgroup count overflows";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, abr_vjp_rfg_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, g, nxgrid, xoff, x, nscale,
+                                         scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im, gg));
+}
+
+int mbfir_abr2_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                             const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                             const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
+                             const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im,
+                             double* ggx, double* ggy) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = roff && rf_re && rf_im && xoff && x && yoff && y && scales && ca_re && ca_im && cb_re && cb_im && g_re &&
+                        g_im && ggx && ggy;
+    if (const int e = abr_batch_check(ctx, "abr2_vjp_rfg_batch", true, npulse, roff, nxgrid, xoff, nygrid, yoff, nscale, mode, arrays,
+                                      npoint))
+        return e;
+    if (!vjp_rfg_partials_fit(npulse, nscale, roff, npoint.data())) {
+        ctx->err = "abr2_vjp_rfg_batch: the output size or the workgroup count overflows";
+        return MBFIR_E_ARG;
+    }
+    MBFIR_TRY(ctx, abr2_vjp_rfg_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x,
+                                          nygrid, yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im, ggx, ggy));
+}
+
 // What the tangent calls check after abr_batch_check: ndir, and that ndir times the R rf samples, ndir times the forward output (at
 // most 2^56 entries each) and the forward workgroups times the direction groups (at most 2^31 - 1) fit.  0, or MBFIR_E_ARG with ctx->err set.
 static int jvp_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, long R, const long* npoint) {

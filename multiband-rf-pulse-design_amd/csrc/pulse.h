@@ -1,4 +1,4 @@
-// Host side of the pulse tools (slr.hip, simgrad.hip, simjvp.hip, simgn.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// Host side of the pulse tools (slr.hip, simgrad.hip, simgradg.hip, simjvp.hip, simgn.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
 // api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
 // (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
 // compiler.
@@ -54,6 +54,18 @@ void abr2_vjp_batch_run(int device, void* stream, int npulse, const long* roff, 
                         const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
                         const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
                         const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im);
+// Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
+// k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
+// pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.
+void abr_vjp_rfg_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                           const double* g, int nxgrid, const long* xoff, const double* x, int nscale, const double* scales,
+                           int mode, const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im,
+                           double* g_re, double* g_im, double* gg);
+void abr2_vjp_rfg_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
+                            const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
+                            const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
+                            const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im,
+                            double* ggx, double* ggy);
 // Tangents of abr_batch_run / abr2_batch_run with respect to rf (simjvp.hip k_abr_jvp_batch, k_abr2_jvp_batch): the forward call's
 // inputs and ndir >= 1 directions per pulse, direction k of pulse p at ndir roff[p] + k n_p of v_re / v_im.  a / b: the forward
 // call's outputs with its bits (all four null: not downloaded); da / db: pulse p from ndir times its forward offset, (direction,

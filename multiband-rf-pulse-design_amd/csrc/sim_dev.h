@@ -1,5 +1,5 @@
-// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip), their tangents
-// (simjvp.hip) and their least-squares products (simgn.hip) share: the step of the forward model, the helpers and the steps of its
+// What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip, simgradg.hip), their
+// tangents (simjvp.hip) and their least-squares products (simgn.hip) share: the step of the forward model, the helpers and the steps of its
 // derivatives, the adjoint's reduction constants and fold, the per-pulse descriptors, and the host staging of one call.  Moved
 // here from slr.hip, simgrad.hip and simjvp.hip token for token.
 #pragma once
@@ -166,6 +166,68 @@ __device__ __forceinline__ double2 abr_vjp_fold_sum(const double2* __restrict__ 
     return g;
 }
 
+// abr_vjp_step plus the sample's contribution dom = dL / d om to the gradient waveform's adjoint (simgradg.hip).  Q_m
+// depends on om through
+//   mode 0: d alpha / d om = dal = -om inv / 2 - i (inv + om^2 D),  d beta / d om = dbe = D om (-i r)
+//           dom = Re( conj(la) (dal u - conj(dbe) v) + conj(lb) (dbe u + conj(dal) v) );  phi = 0 gives dal = -i / 2
+//   mode 1: only z^-1 = exp(-i om): dw / d om = -i w   ->   dom = Re( conj(la) (i conj(S) w) + conj(lb) (-i cs w) )
+// with u, v (w) the state before the sample and la, lb the multipliers after it, all of which the rf step already forms; no
+// further sincos.  The rf pair is abr_vjp_step's arithmetic restated.
+__device__ __forceinline__ double2 abr_vjp_step_g(int mode, double2 r, double om, double2& a, double2& b, double2& la, double2& lb,
+                                                  double& dom) {
+    double sn, cs, inv, D;
+    if (mode == 0) {
+        const double phi = sqrt(r.x * r.x + r.y * r.y + om * om);
+        sincos(0.5 * phi, &sn, &cs);
+        half_sinc(phi, sn, cs, inv, D);
+        const double2 al = make_double2(cs, -om * inv), be = make_double2(r.y * inv, -r.x * inv);
+        const double2 bh = make_double2(r.y, -r.x), ka = make_double2(-0.5 * inv, -om * D);
+        const double2 ta = cjmul(al, a), tb = cjmul(be, b), tc = cmul(al, b), td = cmul(be, a);
+        const double2 u = make_double2(ta.x + tb.x, ta.y + tb.y), v = make_double2(tc.x - td.x, tc.y - td.y);
+        const double2 p1 = cmul(ka, u), p2 = cjmul(bh, v), p3 = cmul(bh, u), p4 = cjmul(ka, v);
+        const double2 t1 = make_double2(p1.x - D * p2.x, p1.y - D * p2.y), t2 = make_double2(D * p3.x + p4.x, D * p3.y + p4.y);
+        const double C = redot(la, t1) + redot(lb, t2);
+        const double2 X = cjmul(la, v), Y = cjmul(lb, u);
+        const double2 g = make_double2(r.x * C + inv * (X.y + Y.y), r.y * C + inv * (Y.x - X.x));
+        const double Do = D * om;                                  // dbe = Do bh: p2 and p3 serve again
+        const double2 dal = make_double2(-0.5 * om * inv, -(inv + om * Do));
+        const double2 q1 = cmul(dal, u), q4 = cjmul(dal, v);
+        const double2 s1 = make_double2(q1.x - Do * p2.x, q1.y - Do * p2.y), s2 = make_double2(Do * p3.x + q4.x, Do * p3.y + q4.y);
+        dom = redot(la, s1) + redot(lb, s2);
+        const double2 la1 = cjmul(al, la), la2 = cjmul(be, lb), lb1 = cmul(al, lb), lb2 = cmul(be, la);
+        la = make_double2(la1.x + la2.x, la1.y + la2.y);
+        lb = make_double2(lb1.x - lb2.x, lb1.y - lb2.y);
+        a = u; b = v;
+        return g;
+    }
+    const double th = hypot(r.x, r.y);
+    double sz, cz;
+    sincos(0.5 * th, &sn, &cs);
+    sincos(-om, &sz, &cz);                                         // z^-1 = cz + i sz
+    half_sinc(th, sn, cs, inv, D);
+    const double2 S = make_double2(-r.y * inv, r.x * inv), sh = make_double2(-r.y, r.x), zi = make_double2(cz, sz);
+    const double2 ta = cjmul(S, b), tb = cmul(S, a);
+    const double2 u = make_double2(cs * a.x + ta.x, cs * a.y + ta.y), w = make_double2(cs * b.x - tb.x, cs * b.y - tb.y);
+    const double2 p2 = cjmul(sh, w), p3 = cmul(sh, u);
+    const double2 t1 = make_double2(-0.5 * inv * u.x - D * p2.x, -0.5 * inv * u.y - D * p2.y);
+    const double2 t2 = make_double2(D * p3.x - 0.5 * inv * w.x, D * p3.y - 0.5 * inv * w.y);
+    const double C = redot(la, t1) + redot(lb, t2);
+    const double2 X = cjmul(la, w), Y = cjmul(lb, u);
+    const double2 g = make_double2(r.x * C - inv * (X.y + Y.y), r.y * C + inv * (X.x - Y.x));
+    const double2 sw = cjmul(S, w);                                // i conj(S) w = (-sw.y, sw.x);  -i cs w = cs (w.y, -w.x)
+    dom = la.y * sw.x - la.x * sw.y + cs * (lb.x * w.y - lb.y * w.x);
+    const double2 l1 = cjmul(S, lb), l2 = cmul(S, la);
+    const double2 lw = make_double2(cs * lb.x - l2.x, cs * lb.y - l2.y);
+    la = make_double2(cs * la.x + l1.x, cs * la.y + l1.y);
+    lb = cjmul(zi, lw);                                            // conj(z^-1) = z
+    a = u; b = cjmul(zi, w);
+    return g;
+}
+
+// The reduction tile of the rf and g adjoint (simgradg.hip): VJG_T samples x four rows (Re, Im of the rf pair, x dom, y dom) of
+// VJP_ROW doubles: 16 rows like the rf adjoint's tile, so the same LDS and the same 16-lanes-per-row pass.
+constexpr int VJG_T = 4;
+
 // Directions per workgroup: the largest of 1, 2, 4, 8 without scratch at no less than the forward kernels' occupancy minus one wave
 // per SIMD (DESIGN 8l has the table).
 #ifndef JVP_K
@@ -294,5 +356,35 @@ struct Abr2Staged {
 void abr2_stage(Abr2Staged& A, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
                 const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                 int nscale, const double* scales);
+
+// The adjoint's sections of one call (simgrad.hip, simgradg.hip): the cotangents, the partial descriptors and the fold kernel's table.
+struct VjpSections {
+    size_t o_ca = 0, o_cb = 0, o_vp = 0, o_fb = 0;
+    long nfold = 0, npart = 0;                                  // workgroups of the fold; double2 entries of the partials
+};
+// Adds and fills the adjoint's sections of S (after the forward sections: pointers into S taken before this are stale).
+inline VjpSections vjp_stage(Staging& S, int npulse, const long* roff, const std::vector<int>& ntime,
+                             const std::vector<long>& npoint, int nscale, long O, const double* ca_re, const double* ca_im,
+                             const double* cb_re, const double* cb_im) {
+    VjpSections V;
+    std::vector<VjpPulseDev> vp(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        const int nch = int((npoint[p] + 255) / 256);
+        vp[p] = VjpPulseDev{roff[p], V.npart, ntime[p], nch};
+        V.npart += (long)nscale * nch * ntime[p];
+        V.nfold += (ntime[p] + 255) / 256;
+    }
+    V.o_ca = S.add((size_t)O * 16);
+    V.o_cb = S.add((size_t)O * 16);
+    V.o_vp = S.add(npulse * sizeof(VjpPulseDev));
+    V.o_fb = S.add(V.nfold * sizeof(SimBlock));
+    pack_cplx(O, ca_re, ca_im, S.at<double2>(V.o_ca));
+    pack_cplx(O, cb_re, cb_im, S.at<double2>(V.o_cb));
+    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(V.o_vp));
+    SimBlock* fb = S.at<SimBlock>(V.o_fb);
+    for (int p = 0; p < npulse; ++p)
+        for (int c = 0; c < (ntime[p] + 255) / 256; ++c) *fb++ = SimBlock{p, 0, c, 0};
+    return V;
+}
 
 }  // namespace mbfir

@@ -123,36 +123,9 @@ __global__ __launch_bounds__(256) void k_abr_vjp_fold(const double2* __restrict_
 
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_abr_vjp_batch / mbfir_abr2_vjp_batch (arguments checked by api.cpp): the forward call's staging plus the
-// cotangents, the partial descriptors and the fold kernel's table; one upload, two launches, one download.
+// cotangents, the partial descriptors and the fold kernel's table (vjp_stage, sim_dev.h); one upload, two launches, one download.
 
 namespace {
-struct VjpSections {
-    size_t o_ca = 0, o_cb = 0, o_vp = 0, o_fb = 0;
-    long nfold = 0, npart = 0;                                  // workgroups of the fold; double2 entries of the partials
-};
-// Adds and fills the adjoint's sections of S (after the forward sections: pointers into S taken before this are stale).
-VjpSections vjp_stage(Staging& S, int npulse, const long* roff, const std::vector<int>& ntime, const std::vector<long>& npoint,
-                      int nscale, long O, const double* ca_re, const double* ca_im, const double* cb_re, const double* cb_im) {
-    VjpSections V;
-    std::vector<VjpPulseDev> vp(npulse);
-    for (int p = 0; p < npulse; ++p) {
-        const int nch = int((npoint[p] + 255) / 256);
-        vp[p] = VjpPulseDev{roff[p], V.npart, ntime[p], nch};
-        V.npart += (long)nscale * nch * ntime[p];
-        V.nfold += (ntime[p] + 255) / 256;
-    }
-    V.o_ca = S.add((size_t)O * 16);
-    V.o_cb = S.add((size_t)O * 16);
-    V.o_vp = S.add(npulse * sizeof(VjpPulseDev));
-    V.o_fb = S.add(V.nfold * sizeof(SimBlock));
-    pack_cplx(O, ca_re, ca_im, S.at<double2>(V.o_ca));
-    pack_cplx(O, cb_re, cb_im, S.at<double2>(V.o_cb));
-    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(V.o_vp));
-    SimBlock* fb = S.at<SimBlock>(V.o_fb);
-    for (int p = 0; p < npulse; ++p)
-        for (int c = 0; c < (ntime[p] + 255) / 256; ++c) *fb++ = SimBlock{p, 0, c, 0};
-    return V;
-}
 // The second launch and the download: the output region is the gradient (R entries), then the partials.
 void vjp_fold_download(Staging& S, const VjpSections& V, long R, int nscale, hipStream_t st, double* g_re, double* g_im) {
     double2* grad = S.dev<double2>(S.o_out);

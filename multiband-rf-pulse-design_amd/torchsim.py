@@ -1,13 +1,18 @@
 """torch.autograd wrappers of the device simulators: `abr` and `abr2` run mbfir.abr_batch / mbfir.abr2_batch on one pulse and are
 differentiable in rf, their backward being one mbfir.abr_vjp_batch / mbfir.abr2_vjp_batch call and their
 forward-mode tangent one mbfir.abr_jvp_batch / mbfir.abr2_jvp_batch call with one direction (section 8l), so that
-torch.autograd.forward_ad dual tensors and torch.func.jvp pass through them.  They work on complex128 tensors; the C ABI takes host pointers, so tensors go through host memory, and the results come back on rf's device.
-g, x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
+torch.autograd.forward_ad dual tensors and torch.func.jvp pass through them.  They are also differentiable, in reverse mode, in the
+gradient waveform g when g is a tensor that requires grad (float64 in 1D, complex128 in 2D): the backward is then one
+mbfir.abr_vjp_rfg_batch / mbfir.abr2_vjp_rfg_batch call that returns both gradients (section 8o); when only rf requires grad it is
+the rf call, with its bits.  A forward-mode tangent for g raises NotImplementedError.  rf is a complex128 tensor; the C ABI takes
+host pointers, so tensors go through host memory, and the results come back on rf's device.
+x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
+    g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
     a, b = mbfir.torchsim.abr2(rf, g, x, y, scales=(0.9, 1.0, 1.1))        # (S, nx, ny) each, abr2_batch's bits
     loss = ((2 * a.conj() * b - target).abs() ** 2).sum()
-    loss.backward()                                                       # rf.grad: abr2_vjp_batch's bits
+    loss.backward()                                                       # rf.grad and g.grad = dL/dgx + i dL/dgy
 """
 import functools
 
@@ -40,13 +45,23 @@ def _functions():
         if not torch.is_tensor(rf) or rf.dtype != torch.complex128 or rf.dim() != 1:
             raise ValueError("torchsim: rf must be a 1-D complex128 tensor")
 
+    def check_g(g, dtype, name):
+        """g may be None, an array (a constant) or a tensor; one that requires grad must have the dtype its gradient comes in"""
+        if torch.is_tensor(g) and g.requires_grad and (g.dtype != dtype or g.dim() != 1):
+            raise ValueError("torchsim: a g that requires grad must be a 1-D %s tensor" % name)
+
     def tensors(rf, arrays):
         return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(rf.device) for v in arrays)
+
+    def no_g_tangent(vg):
+        if vg is not None:
+            raise NotImplementedError("torchsim: the forward-mode tangent with respect to g is not implemented (reverse mode is)")
 
     class Abr(torch.autograd.Function):
         @staticmethod
         def forward(rf, x, g, scales, hard_pulse):
             check(rf)
+            check_g(g, torch.float64, "float64")
             x, g, scales, hard_pulse = _host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse)
             rfh = _host(rf, np.complex128)
             (a, b), = mbfir.abr_batch([rfh if g is None else (rfh, g)], x, scales=scales, hard_pulse=hard_pulse)
@@ -56,11 +71,13 @@ def _functions():
         def setup_context(ctx, inputs, output):
             rf, x, g, scales, hard_pulse = inputs
             ctx.args = (_host(x, np.float64), _host(g, np.float64), tuple(scales), bool(hard_pulse))
+            ctx.g_like = (g.shape, g.device) if torch.is_tensor(g) else None          # where g's gradient goes
             ctx.save_for_backward(rf)
             ctx.save_for_forward(rf)
 
         @staticmethod
-        def jvp(ctx, v, *_):
+        def jvp(ctx, v, vx, vg, *_):
+            no_g_tangent(vg)
             rf, = ctx.saved_tensors
             x, g, scales, hard_pulse = ctx.args
             rfh = _host(rf, np.complex128)
@@ -73,14 +90,19 @@ def _functions():
             rf, = ctx.saved_tensors
             x, g, scales, hard_pulse = ctx.args
             rfh = _host(rf, np.complex128)
-            grad, = mbfir.abr_vjp_batch([rfh if g is None else (rfh, g)], x, [(_host(ca, np.complex128), _host(cb, np.complex128))],
-                                        scales=scales, hard_pulse=hard_pulse)
-            return tensors(rf, (grad,)) + (None, None, None, None)
+            pulses, cot = [rfh if g is None else (rfh, g)], [(_host(ca, np.complex128), _host(cb, np.complex128))]
+            if not ctx.needs_input_grad[2]:
+                grad, = mbfir.abr_vjp_batch(pulses, x, cot, scales=scales, hard_pulse=hard_pulse)
+                return tensors(rf, (grad,)) + (None, None, None, None)
+            (grad, gg), = mbfir.abr_vjp_rfg_batch(pulses, x, cot, scales=scales, hard_pulse=hard_pulse)
+            grad, = tensors(rf, (grad,)) if ctx.needs_input_grad[0] else (None,)
+            return grad, None, torch.from_numpy(gg.reshape(ctx.g_like[0])).to(ctx.g_like[1]), None, None
 
     class Abr2(torch.autograd.Function):
         @staticmethod
         def forward(rf, g, x, y, scales, hard_pulse):
             check(rf)
+            check_g(g, torch.complex128, "complex128")
             g, x, y = _host(g, np.complex128), _host(x, np.float64), _host(y, np.float64)
             rfh = _host(rf, np.complex128)
             (a, b), = mbfir.abr2_batch([rfh if g is None else (rfh, g)], x, y, scales=tuple(scales), hard_pulse=bool(hard_pulse))
@@ -90,11 +112,13 @@ def _functions():
         def setup_context(ctx, inputs, output):
             rf, g, x, y, scales, hard_pulse = inputs
             ctx.args = (_host(g, np.complex128), _host(x, np.float64), _host(y, np.float64), tuple(scales), bool(hard_pulse))
+            ctx.g_like = (g.shape, g.device) if torch.is_tensor(g) else None          # where g's gradient goes
             ctx.save_for_backward(rf)
             ctx.save_for_forward(rf)
 
         @staticmethod
-        def jvp(ctx, v, *_):
+        def jvp(ctx, v, vg, *_):
+            no_g_tangent(vg)
             rf, = ctx.saved_tensors
             g, x, y, scales, hard_pulse = ctx.args
             rfh = _host(rf, np.complex128)
@@ -107,21 +131,27 @@ def _functions():
             rf, = ctx.saved_tensors
             g, x, y, scales, hard_pulse = ctx.args
             rfh = _host(rf, np.complex128)
-            grad, = mbfir.abr2_vjp_batch([rfh if g is None else (rfh, g)], x, y,
-                                         [(_host(ca, np.complex128), _host(cb, np.complex128))], scales=scales, hard_pulse=hard_pulse)
-            return tensors(rf, (grad,)) + (None, None, None, None, None)
+            pulses, cot = [rfh if g is None else (rfh, g)], [(_host(ca, np.complex128), _host(cb, np.complex128))]
+            if not ctx.needs_input_grad[1]:
+                grad, = mbfir.abr2_vjp_batch(pulses, x, y, cot, scales=scales, hard_pulse=hard_pulse)
+                return tensors(rf, (grad,)) + (None, None, None, None, None)
+            (grad, gg), = mbfir.abr2_vjp_rfg_batch(pulses, x, y, cot, scales=scales, hard_pulse=hard_pulse)
+            grad, = tensors(rf, (grad,)) if ctx.needs_input_grad[0] else (None,)
+            return grad, torch.from_numpy(gg.reshape(ctx.g_like[0])).to(ctx.g_like[1]), None, None, None, None
 
     return Abr, Abr2
 
 
 def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
     """(a, b) of mbfir.abr_batch([rf or (rf, g)], x, scales=scales, hard_pulse=hard_pulse), each of shape (S, nx), as tensors that
-    are differentiable in rf (a 1-D complex128 tensor).  x and g (real, one weight per sample; None: 2 pi / n) are constants."""
+    are differentiable in rf (a 1-D complex128 tensor) and, in reverse mode, in g (real, one weight per sample; None: 2 pi / n) when g
+    is a 1-D float64 tensor that requires grad; any other g, and x, are constants."""
     return _functions()[0].apply(rf, x, g, scales, hard_pulse)
 
 
 def abr2(rf, g, x, y, *, scales=(1.0,), hard_pulse=False):
     """(a, b) of mbfir.abr2_batch([rf or (rf, g)], x, y, scales=scales, hard_pulse=hard_pulse), each of shape (S, nx, ny), as
-    tensors that are differentiable in rf (a 1-D complex128 tensor).  g (complex: Re the x gradient, Im the y one; None: 2 pi / n
-    along x), x and y are constants."""
+    tensors that are differentiable in rf (a 1-D complex128 tensor) and, in reverse mode, in g (complex: Re the x gradient, Im the
+    y one; None: 2 pi / n along x) when g is a 1-D complex128 tensor that requires grad, its gradient being dL/dgx + i dL/dgy; any
+    other g, x and y are constants."""
     return _functions()[1].apply(rf, g, x, y, scales, hard_pulse)
