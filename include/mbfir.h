@@ -463,6 +463,35 @@ int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const 
                       const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
                       int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
                       double* beta_im, long* winner, double* winner_peak);
+/* mbfir_test_flip_stages (test hook): mbfir_flip_search under two overrides, then every stage of selected candidates.
+ * 1. The search exactly as mbfir_flip_search launches it (one host body serves both): twiddles, the scoring launch, the arg-min over
+ *    the workgroups' bests, the pick launch.  Arguments up to tie_high, peaks (required here), beta_re / beta_im (required), winner
+ *    and winner_peak are mbfir_flip_search's.  force_mode: -1 the mode a search chooses, or 0 (working set and twiddles in LDS),
+ *    1 (twiddles from global memory), 2 (everything in the per-workgroup global scratch); a mode whose LDS does not fit the device is
+ *    MBFIR_E_ARG with a message, before any launch.  max_blocks: 0 as a search chooses, else a cap on the scoring launch's workgroups
+ *    (candidates beyond it are reached by the grid stride).  blk_p / blk_i (ncand each; report[2] are written): each workgroup's best
+ *    peak and its index (-1: none finite), the input of the arg-min.
+ * 2. One more scoring launch (same mode, threads and LDS) over the nsel candidates sel[] (0 <= nsel <= 1024, each < ncand; repeats
+ *    allowed) through the instantiation that also stores the stages.  Block s of each array belongs to sel[s]; complex values are
+ *    interleaved (re, im):
+ *      st_beta  n complex     the candidate after the build and the scale rule
+ *      st_bf    8n            |fft(beta, 8n)| after the clip scale (times 1 / (1e-8 + max) when max >= 1)
+ *      st_xl    8n            log(sqrt(1 - bf^2))
+ *      st_xlfp  4n + 1 complex  fft(xl)(0 : 4n) windowed (x 2 except at 0 and 4n)
+ *      st_afa   8n complex    exp(ifft(xlfp))
+ *      st_a     n complex     alpha, a = fft(afa)(0 : n-1) / 8n reversed
+ *      st_theta n             theta[i - 1] = atan2(|s_i|, c_i) of recursion step i = n .. 1 (|rf_i| = 2 theta_i)
+ *      st_peak  1             the candidate's peak as this launch scored it
+ *    With criterion 0 only st_beta and st_peak are written.  Nothing is written outside these sizes.
+ * report (8 longs): mode used, threads per workgroup, workgroups of the search's scoring launch, dynamic LDS bytes, scratch stride
+ *    (double2 per workgroup), the device's LDS limit per workgroup as read, nn, mask words per candidate.
+ * Returns as mbfir_flip_search (MBFIR_NUMERICAL with winner -1 when no candidate is finite: the blocks are still written). */
+int mbfir_test_flip_stages(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
+                           const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
+                           const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, int force_mode,
+                           int max_blocks, int nsel, const long* sel, double* peaks, double* blk_p, long* blk_i, double* beta_re,
+                           double* beta_im, long* winner, double* winner_peak, double* st_beta, double* st_bf, double* st_xl,
+                           double* st_xlfp, double* st_afa, double* st_a, double* st_theta, double* st_peak, long* report);
 
 /* ---- Conventional SLR filters: Parks-McClellan and fmp (rf_tools/dzlp.m, dzmp.m, fmp.m) ----------------------------------------
  * mbfir_remez_batch: `h = remez(numtaps - 1, edges, desired, weight)` as dzlp.m:13 and dzmp.m:16 call it, for njobs independent

@@ -117,6 +117,9 @@ SYMBOLS = {
     "mbfir_abr2": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_flip_search": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
                                     C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(C.c_long), _dp]),
+    "mbfir_test_flip_stages": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, C.c_long, C.POINTER(C.c_uint), _ip,
+                                         C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _lp, _dp, _dp, _lp,
+                                         _dp, _dp, _lp, _dp] + [_dp] * 8 + [_lp]),
     "mbfir_remez_batch": (C.c_int, [C.c_void_p, C.POINTER(RemezJob), C.c_int, C.POINTER(RemezOpts)]),
     "mbfir_fmp": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _dp]),
     "mbfir_abr": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -588,6 +591,67 @@ def flip_search(c0, z, zf, *, masks=None, enum_bits=None, ncand=None, target=Non
     if rc != 0:
         raise MbfirError("mbfir_flip_search failed (%d): %s" % (rc, ctx.last_error()))
     return bre + 1j * bim, int(win.value), pk
+
+
+def test_flip_stages(c0, z, zf, *, masks=None, enum_bits=None, ncand=None, target=None, bsf=None, criterion="rf", tie_high=False,
+                     force_mode=-1, max_blocks=0, sel=(), guard=0, fill=0.0, ctx=None):
+    """Test hook (mbfir_test_flip_stages): flip_search under a forced kernel mode and a cap on the workgroups, then every stage of the
+    candidates `sel` from one more launch.  Candidates and scale rule as flip_search (masks: nz x ncand).  Every output block is
+    allocated `guard` elements longer than the hook may write and pre-filled with `fill`; "raw" holds those flat arrays whole, so a
+    caller can see that nothing outside a block changed.  Returns a dict: status (0, or NUMERICAL when no candidate is finite), winner,
+    winner_peak, beta (the pick launch's), peaks, blk_p / blk_i (the launched workgroups'), report (dict), and per selected candidate
+    st_beta, st_bf, st_xl, st_xlfp, st_afa, st_a, st_theta, st_peak (with criterion "beta" only st_beta and st_peak are written)."""
+    ctx = ctx or get_context()
+    c0re, c0im = _split(c0)
+    zre, zim = _split(z)
+    fre, fim = _split(zf)
+    nz = len(zre)
+    n = len(c0re) + nz
+    if (target is None) == (bsf is None):
+        raise ValueError("test_flip_stages: give exactly one of target (DC rule) and bsf (npoly rule)")
+    mk, eb = None, None
+    if masks is not None:
+        m = np.asarray(masks)
+        ncand = m.shape[1] if m.ndim == 2 else m.size // max(nz, 1)
+        mk = _pack_masks(m.reshape(nz, ncand))
+    elif enum_bits is not None:
+        eb = np.ascontiguousarray(np.asarray(enum_bits, dtype=np.int32).ravel())
+    else:
+        ncand = 2 ** nz
+    ncand = int(ncand)
+    sel = np.ascontiguousarray(np.asarray(sel, dtype=np.int64).ravel())
+    ns = len(sel)
+    sizes = dict(peaks=ncand, blk_p=ncand, beta_re=n, beta_im=n, st_beta=2 * ns * n, st_bf=ns * 8 * n, st_xl=ns * 8 * n,
+                 st_xlfp=2 * ns * (4 * n + 1), st_afa=2 * ns * 8 * n, st_a=2 * ns * n, st_theta=ns * n, st_peak=ns)
+    raw = {k: np.full(v + guard, fill, dtype=np.float64) for k, v in sizes.items()}
+    raw["blk_i"] = np.full(ncand + guard, -7, dtype=np.int64)
+    raw["report"] = np.full(8 + guard, -7, dtype=np.int64)
+    win, wp = C.c_long(-7), C.c_double(0)
+    if target is not None:
+        t = complex(target)
+        rule, sre, sim = 0, t.real, t.imag
+    else:
+        rule, sre, sim = 1, float(bsf), 0.0
+    lp = lambda a: a.ctypes.data_as(_lp)                                            # noqa: E731
+    rc = load_library().mbfir_test_flip_stages(
+        ctx._h, n, nz, _ptr(c0re), _ptr(c0im), _ptr(zre), _ptr(zim), _ptr(fre), _ptr(fim), ncand,
+        mk.ctypes.data_as(C.POINTER(C.c_uint)) if mk is not None else None, eb.ctypes.data_as(_ip) if eb is not None else None,
+        rule, sre, sim, 1 if criterion == "rf" else 0, 1 if tie_high else 0, int(force_mode), int(max_blocks), ns, lp(sel),
+        _ptr(raw["peaks"]), _ptr(raw["blk_p"]), lp(raw["blk_i"]), _ptr(raw["beta_re"]), _ptr(raw["beta_im"]), C.byref(win), C.byref(wp),
+        *[_ptr(raw[k]) for k in ("st_beta", "st_bf", "st_xl", "st_xlfp", "st_afa", "st_a", "st_theta", "st_peak")], lp(raw["report"]))
+    if rc == E_ARG:
+        raise ValueError("test_flip_stages: %s" % ctx.last_error())
+    if rc not in (0, NUMERICAL):
+        raise MbfirError("mbfir_test_flip_stages failed (%d): %s" % (rc, ctx.last_error()))
+    rep = dict(zip(("mode", "threads", "blocks", "lds", "stride", "lds_limit", "nn", "words"), (int(v) for v in raw["report"][:8])))
+    cplx = lambda k, m: (raw[k][:2 * ns * m:2] + 1j * raw[k][1:2 * ns * m:2]).reshape(ns, m)   # noqa: E731
+    real = lambda k, m: raw[k][:ns * m].reshape(ns, m).copy()                       # noqa: E731
+    nb = rep["blocks"]
+    return dict(status=rc, winner=int(win.value), winner_peak=float(wp.value), beta=raw["beta_re"][:n] + 1j * raw["beta_im"][:n],
+                peaks=raw["peaks"][:ncand].copy(), blk_p=raw["blk_p"][:nb].copy(), blk_i=raw["blk_i"][:nb].copy(), report=rep,
+                st_beta=cplx("st_beta", n), st_bf=real("st_bf", 8 * n), st_xl=real("st_xl", 8 * n), st_xlfp=cplx("st_xlfp", 4 * n + 1),
+                st_afa=cplx("st_afa", 8 * n), st_a=cplx("st_a", n), st_theta=real("st_theta", n), st_peak=raw["st_peak"][:ns].copy(),
+                raw=raw, sizes=sizes)
 
 
 def _flip_root(z):

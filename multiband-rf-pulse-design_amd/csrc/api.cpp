@@ -16,6 +16,7 @@
 #include <map>
 #include <mutex>
 #include <memory>
+#include <stdexcept>
 #include <system_error>
 #include <thread>
 
@@ -864,24 +865,62 @@ int mbfir_slr2d_batch(mbfir_ctx* ctx, int m, int n, int count, const double* r_r
     }
     MBFIR_TRY(ctx, slr_slr2d_batch_run(ctx->device, ctx->solver->stream(), m, n, count, r_re, r_im, out_re, out_im, literal));
 }
+// the argument rules of mbfir_flip_search, shared with its test hook
+static bool flip_args_ok(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
+                         const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
+                         int scale_rule, double s_re, int criterion, const double* beta_re, const double* beta_im, const long* winner) {
+    if (!ctx || n < 2 || n > 1024 || nz < 0 || nz > n - 1 || nz > 1023 || ncand < 1 || !c0_re || !c0_im || !winner ||
+        (nz > 0 && (!z_re || !z_im || !zf_re || !zf_im)) || (!beta_re) != (!beta_im) || (criterion != 0 && criterion != 1) ||
+        (scale_rule != 0 && scale_rule != 1) || (scale_rule == 1 && !(s_re >= 0.0 && s_re <= 1.0)))
+        return false;
+    if (!masks) {
+        if (ncand > (1L << 24)) return false;
+        if (!enum_bits && (nz > 24 || ncand != (1L << nz))) return false;
+        for (int j = 0; enum_bits && j < nz; ++j)
+            if (enum_bits[j] < 0 || (enum_bits[j] >> 1) >= 24) return false;
+    }
+    return true;
+}
 int mbfir_flip_search(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re, const double* z_im,
                       const double* zf_re, const double* zf_im, long ncand, const unsigned* masks, const int* enum_bits,
                       int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks, double* beta_re,
                       double* beta_im, long* winner, double* winner_peak) {
-    if (!ctx || n < 2 || n > 1024 || nz < 0 || nz > n - 1 || nz > 1023 || ncand < 1 || !c0_re || !c0_im || !winner ||
-        (nz > 0 && (!z_re || !z_im || !zf_re || !zf_im)) || (!beta_re) != (!beta_im) || (criterion != 0 && criterion != 1) ||
-        (scale_rule != 0 && scale_rule != 1) || (scale_rule == 1 && !(s_re >= 0.0 && s_re <= 1.0)))
+    if (!flip_args_ok(ctx, n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re, criterion, beta_re,
+                      beta_im, winner))
         return MBFIR_E_ARG;
-    if (!masks) {
-        if (ncand > (1L << 24)) return MBFIR_E_ARG;
-        if (!enum_bits && (nz > 24 || ncand != (1L << nz))) return MBFIR_E_ARG;
-        for (int j = 0; enum_bits && j < nz; ++j)
-            if (enum_bits[j] < 0 || (enum_bits[j] >> 1) >= 24) return MBFIR_E_ARG;
-    }
     try {
         *winner = flip_search_run(ctx->device, ctx->solver->stream(), n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks,
                                   enum_bits, scale_rule, s_re, s_im, criterion, tie_high ? 1 : 0, peaks, beta_re, beta_im, winner_peak);
     } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+    if (*winner < 0) { ctx->err = "flip search: no candidate has a finite peak"; return MBFIR_NUMERICAL; }
+    return 0;
+}
+int mbfir_test_flip_stages(mbfir_ctx* ctx, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
+                           const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
+                           const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, int force_mode,
+                           int max_blocks, int nsel, const long* sel, double* peaks, double* blk_p, long* blk_i, double* beta_re,
+                           double* beta_im, long* winner, double* winner_peak, double* st_beta, double* st_bf, double* st_xl,
+                           double* st_xlfp, double* st_afa, double* st_a, double* st_theta, double* st_peak, long* report) {
+    if (!flip_args_ok(ctx, n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks, enum_bits, scale_rule, s_re, criterion, beta_re,
+                      beta_im, winner))
+        return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_flip_stages: " + why; return MBFIR_E_ARG; };
+    if (force_mode < -1 || force_mode > 2) return bad("force_mode must be -1, 0, 1 or 2");
+    if (max_blocks < 0) return bad("max_blocks must be 0 (as a search chooses) or a positive cap");
+    if (nsel < 0 || nsel > 1024) return bad("nsel must lie in [0, 1024]");
+    if (!peaks || !blk_p || !blk_i || !report || !beta_re) return bad("peaks, blk_p, blk_i, beta and report are required");
+    if (nsel > 0 && (!sel || !st_beta || !st_bf || !st_xl || !st_xlfp || !st_afa || !st_a || !st_theta || !st_peak))
+        return bad("sel and every stage block are required when nsel > 0");
+    for (int q = 0; q < nsel; ++q)
+        if (sel[q] < 0 || sel[q] >= ncand) return bad("sel[" + std::to_string(q) + "] is not a candidate index");
+    const FlipStages hook{force_mode, max_blocks, nsel, sel, blk_p, blk_i, st_beta, st_bf, st_xl, st_xlfp, st_afa, st_a, st_theta, st_peak,
+                          report};
+    try {
+        *winner = flip_search_run(ctx->device, ctx->solver->stream(), n, nz, c0_re, c0_im, z_re, z_im, zf_re, zf_im, ncand, masks,
+                                  enum_bits, scale_rule, s_re, s_im, criterion, tie_high ? 1 : 0, peaks, beta_re, beta_im, winner_peak,
+                                  &hook);
+    } catch (const std::invalid_argument& e) { return bad(e.what()); }
+    catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
     if (*winner < 0) { ctx->err = "flip search: no candidate has a finite peak"; return MBFIR_NUMERICAL; }
     return 0;
 }

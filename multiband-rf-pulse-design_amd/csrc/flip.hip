@@ -22,6 +22,9 @@
 #include "pulse.h"
 #include <algorithm>
 #include <cstring>
+#include <stdexcept>
+#include <string>
+#include <type_traits>
 
 namespace mbfir {
 
@@ -48,6 +51,31 @@ struct FlipParams {
     const long* pick;              // non-null: build candidate *pick only and write its beta to beta_out
     double2* beta_out;
 };
+
+// Stage stores of the test hook's extra launch (k_flip_score<kMode, true>, mbfir_test_flip_stages): workgroups stride over the nsel selected
+// candidates sel[s] and store block s of every array.  The search kernels are compiled without them (kDump = false).
+struct FlipDump {
+    const long* sel;
+    long nsel;
+    double2* beta;                 // n: after the build and scaling
+    double* bf;                    // 8n: |bf| after the clip scale
+    double* xl;                    // 8n
+    double2* xlfp;                 // 4n + 1: the windowed spectrum
+    double2* afa;                  // 8n
+    double2* a;                    // n
+    double* theta;                 // n: theta[i - 1] of recursion step i (|rf_i| = 2 theta_i)
+    double* peak;                  // 1
+};
+
+// What a kernel takes: the search's parameters alone, or with the stage stores behind them (the same kernarg layout up to there).
+struct FlipDumpParams : FlipParams { FlipDump d; };
+template <bool kDump> using FlipArgs = std::conditional_t<kDump, FlipDumpParams, FlipParams>;
+
+// the launch's work items and the candidate behind item s: every candidate, or the selected ones
+__device__ __forceinline__ long flip_count(const FlipParams& p) { return p.ncand; }
+__device__ __forceinline__ long flip_count(const FlipDumpParams& p) { return p.d.nsel; }
+__device__ __forceinline__ long flip_cand(const FlipParams&, long s) { return s; }
+__device__ __forceinline__ long flip_cand(const FlipDumpParams& p, long s) { return p.d.sel[s]; }
 
 constexpr int RED = 16;            // double2 of LDS for the block reductions (17 doubles used)
 
@@ -120,7 +148,9 @@ __device__ __forceinline__ double2* flip_build(const FlipParams& p, long c, doub
 }
 
 // max_k |rf_k| of rf = ab2rf(b2a(b), b); valid in thread 0.  Y: 8n, X: 4n + 1 double2 of working space.
-__device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double2* b, double2* Y, double2* X, double* red, const double2* tw) {
+template <bool kDump>
+__device__ __forceinline__ double flip_rf_peak(const FlipArgs<kDump>& p, const double2* b, double2* Y, double2* X, double* red, const double2* tw,
+                                               long s_) {
     const int n = p.n, N = 8 * n, T = blockDim.x, tid = threadIdx.x;
     double* Xd = reinterpret_cast<double*>(X);             // N reals
     // bf = fft(b, N); |bf| -> Xd, clip (b2a.m:24-28), xl = log(sqrt(1 - |bf|^2))
@@ -142,6 +172,7 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
     for (int k = tid; k < N; k += T) {
         const double a = Xd[k] * sc;
         Xd[k] = log(sqrt(1.0 - a * a));
+        if constexpr (kDump) { p.d.bf[s_ * N + k] = a; p.d.xl[s_ * N + k] = Xd[k]; }
     }
     __syncthreads();
     // xlf = fft(xl): sub-DFT q = m2 n + k1 over the samples 8 m1 + m2
@@ -174,6 +205,7 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
             }
             const double g = (k == 0 || k == 4 * n) ? 1.0 : 2.0;
             X[k] = make_double2(g * acc.x, g * acc.y);
+            if constexpr (kDump) p.d.xlfp[s_ * (4 * n + 1) + k] = X[k];
         }
     }
     __syncthreads();
@@ -209,6 +241,7 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
             sincos(im, &sn, &cs);
             const double e = exp(re);
             Y[mm] = make_double2(e * cs, e * sn);
+            if constexpr (kDump) p.d.afa[s_ * N + mm] = Y[mm];
         }
     }
     __syncthreads();
@@ -222,6 +255,7 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
             ph += k; ph -= ph >= N ? N : 0;
         }
         X[n - 1 - k] = make_double2(acc.x * invN, acc.y * invN);
+        if constexpr (kDump) p.d.a[s_ * n + n - 1 - k] = X[n - 1 - k];
     }
     __syncthreads();
     // inverse SLR recursion (ab2rf.m:14-29), polynomials ping-pong in Y; |rf_i| = 2 theta_i
@@ -239,6 +273,7 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
         if (tid == 0) {
             const double th = atan2(hypot(s.x, s.y), c);
             thmax = th <= thmax ? thmax : finite_or_inf(th);
+            if constexpr (kDump) p.d.theta[s_ * n + i - 1] = th;
         }
         const double2 ms = make_double2(-s.x, s.y);                        // -conj(s)
         const double2* Ac = A + cur * n;
@@ -257,9 +292,10 @@ __device__ __forceinline__ double flip_rf_peak(const FlipParams& p, const double
     return 2.0 * thmax;
 }
 
-// kMode 0: working set and twiddles in LDS; 1: working set in LDS, twiddles from global; 2: both in global memory
-template <int kMode>
-__global__ __launch_bounds__(256) void k_flip_score(FlipParams p) {
+// kMode 0: working set and twiddles in LDS; 1: working set in LDS, twiddles from global; 2: both in global memory.
+// kDump (a compile-time property, so the search kernels carry no trace of it): score the candidates p.d.sel[] and store every stage.
+template <int kMode, bool kDump>
+__global__ __launch_bounds__(256) void k_flip_score(FlipArgs<kDump> p) {
     extern __shared__ __attribute__((aligned(16))) double2 smem[];
     const int n = p.n, N = 8 * n, T = blockDim.x, tid = threadIdx.x;
     double* red = reinterpret_cast<double*>(smem);
@@ -274,33 +310,42 @@ __global__ __launch_bounds__(256) void k_flip_score(FlipParams p) {
         __syncthreads();
         tw = tl;
     }
-    if (p.pick) {                                          // the winner's beta
-        const long c = *p.pick;
-        if (c < 0) return;
-        const double2* b = flip_build(p, c, Bt, red, tw);
-        for (int k = tid; k < n; k += T) p.beta_out[k] = b[k];
-        return;
+    if constexpr (!kDump) {
+        if (p.pick) {                                      // the winner's beta
+            const long c = *p.pick;
+            if (c < 0) return;
+            const double2* b = flip_build(p, c, Bt, red, tw);
+            for (int k = tid; k < n; k += T) p.beta_out[k] = b[k];
+            return;
+        }
     }
     double bp = INFINITY;
     long bi = -1;
-    for (long c = blockIdx.x; c < p.ncand; c += gridDim.x) {
-        const double2* b = flip_build(p, c, Bt, red, tw);
+    for (long s = blockIdx.x; s < flip_count(p); s += gridDim.x) {                   // s: the candidate, or the selected one's place
+        const double2* b = flip_build(p, flip_cand(p, s), Bt, red, tw);
+        if constexpr (kDump)
+            for (int k = tid; k < n; k += T) p.d.beta[s * n + k] = b[k];
         double pk;
         if (p.criterion == 0) {
             double m = 0;
             for (int k = tid; k < n; k += T) m = fmax(m, finite_or_inf(hypot(b[k].x, b[k].y)));
             pk = block_max(m, red);
         } else {
-            pk = flip_rf_peak(p, b, Y, X, red, tw);
+            pk = flip_rf_peak<kDump>(p, b, Y, X, red, tw, s);
         }
         if (tid == 0) {
-            if (p.peaks) p.peaks[c] = pk;
-            const long ci = pk < INFINITY ? c : -1;
-            if (flip_better(pk, ci, bp, bi, p.tie_high)) { bp = pk; bi = ci; }
+            if constexpr (kDump) {
+                p.d.peak[s] = pk;
+            } else {
+                if (p.peaks) p.peaks[s] = pk;
+                const long ci = pk < INFINITY ? s : -1;
+                if (flip_better(pk, ci, bp, bi, p.tie_high)) { bp = pk; bi = ci; }
+            }
         }
         __syncthreads();                                   // the next candidate reuses the working set
     }
-    if (tid == 0) { p.blk_p[blockIdx.x] = bp; p.blk_i[blockIdx.x] = bi; }
+    if constexpr (!kDump)
+        if (tid == 0) { p.blk_p[blockIdx.x] = bp; p.blk_i[blockIdx.x] = bi; }
 }
 
 // arg-min over the workgroups' bests; (peak, index) is a total order, so the result does not depend on the reduction order
@@ -341,19 +386,61 @@ __global__ void k_flip_twiddles(double2* __restrict__ tw, int N, int nn) {
 template <int kMode>
 int flip_blocks(int threads, size_t lds, int ncu) {
     if (lds > 65536)
-        MBFIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flip_score<kMode>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        MBFIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_flip_score<kMode, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     int per = 0;
-    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_flip_score<kMode>, threads, lds));
+    MBFIR_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k_flip_score<kMode, false>, threads, lds));
     return per * ncu;
+}
+
+// The hook's part of flip_search_run: the report, the search launch's per-workgroup bests, and one more scoring launch over
+// hook.sel through the instantiation that stores every stage (same mode, threads and LDS; nbd workgroups).
+void flip_stage_launch(const FlipStages& hook, const FlipParams& p, int mode, int threads, size_t lds, int nb, int nbd, int ldsmax,
+                       hipStream_t st) {
+    const size_t n = p.n, N = 8 * n, ns = hook.nsel;
+    const long rep[8] = {mode, threads, nb, (long)lds, p.stride, ldsmax, p.nn, p.words};
+    std::copy(rep, rep + 8, hook.report);
+    MBFIR_HIP(hipMemcpyAsync(hook.blk_p, p.blk_p, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(hook.blk_i, p.blk_i, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    if (ns == 0) { MBFIR_HIP(hipStreamSynchronize(st)); return; }
+    const bool rf = p.criterion == 1;
+    DevBuf dsel(ns * 8), dbe(ns * n * 16), dbf(rf ? ns * N * 8 : 8), dxl(rf ? ns * N * 8 : 8), dxf(rf ? ns * (4 * n + 1) * 16 : 16),
+        daf(rf ? ns * N * 16 : 16), da(rf ? ns * n * 16 : 16), dth(rf ? ns * n * 8 : 8), dpk(ns * 8);
+    MBFIR_HIP(hipMemcpyAsync(dsel.p, hook.sel, ns * 8, hipMemcpyHostToDevice, st));
+    FlipDumpParams q{};
+    static_cast<FlipParams&>(q) = p;
+    q.peaks = nullptr;
+    q.d = FlipDump{dsel.as<long>(), (long)ns, dbe.as<double2>(), dbf.as<double>(), dxl.as<double>(), dxf.as<double2>(),
+                   daf.as<double2>(), da.as<double2>(), dth.as<double>(), dpk.as<double>()};
+    auto go = [&](auto kernel) {
+        if (lds > 65536)
+            MBFIR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kernel, dim3(nbd), dim3(threads), lds, st, q);
+    };
+    if (mode == 0) go(&k_flip_score<0, true>);
+    else if (mode == 1) go(&k_flip_score<1, true>);
+    else go(&k_flip_score<2, true>);
+    MBFIR_HIP(hipGetLastError());
+    MBFIR_HIP(hipMemcpyAsync(hook.beta, dbe.p, ns * n * 16, hipMemcpyDeviceToHost, st));
+    MBFIR_HIP(hipMemcpyAsync(hook.peak, dpk.p, ns * 8, hipMemcpyDeviceToHost, st));
+    if (rf) {
+        MBFIR_HIP(hipMemcpyAsync(hook.bf, dbf.p, ns * N * 8, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpyAsync(hook.xl, dxl.p, ns * N * 8, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpyAsync(hook.xlfp, dxf.p, ns * (4 * n + 1) * 16, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpyAsync(hook.afa, daf.p, ns * N * 16, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpyAsync(hook.a, da.p, ns * n * 16, hipMemcpyDeviceToHost, st));
+        MBFIR_HIP(hipMemcpyAsync(hook.theta, dth.p, ns * n * 8, hipMemcpyDeviceToHost, st));
+    }
+    MBFIR_HIP(hipStreamSynchronize(st));
 }
 
 }  // namespace
 
-// Host side of mbfir_flip_search (include/mbfir.h): arguments already checked.  Returns the winner (-1: no finite peak).
+// Host side of mbfir_flip_search and of mbfir_test_flip_stages (include/mbfir.h): arguments already checked.  Returns the winner
+// (-1: no finite peak).  hook == nullptr is the public call: mode and workgroups as computed here, no stage launch.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
                      const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
-                     double* beta_re, double* beta_im, double* winner_peak) {
+                     double* beta_re, double* beta_im, double* winner_peak, const FlipStages* hook) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int N = 8 * n, n0 = n - nz, words = (nz + 31) / 32;
@@ -375,13 +462,24 @@ long flip_search_run(int device, void* stream, int n, int nz, const double* c0_r
     size_t lds = red;
     if (red + work + tabs <= (size_t)ldsmax) { mode = 0; lds = red + work + tabs; }
     else if (red + work <= (size_t)ldsmax) { mode = 1; lds = red + work; }
+    if (hook && hook->force_mode >= 0) {
+        const size_t need = hook->force_mode == 0 ? red + work + tabs : hook->force_mode == 1 ? red + work : red;
+        if (need > (size_t)ldsmax)
+            throw std::invalid_argument("forced mode " + std::to_string(hook->force_mode) + " needs " + std::to_string(need) +
+                                        " bytes of LDS, the device gives " + std::to_string(ldsmax));
+        mode = hook->force_mode;
+        lds = need;
+    }
     int maxb = mode == 0 ? flip_blocks<0>(threads, lds, ncu) : mode == 1 ? flip_blocks<1>(threads, lds, ncu) : flip_blocks<2>(threads, lds, ncu);
     if (mode == 2) maxb = std::min(maxb, 2 * ncu);                 // bounds the global scratch (229 KB per workgroup at n = 1024)
+    if (hook && hook->max_blocks > 0) maxb = std::min(maxb, hook->max_blocks);
     const int nb = (int)std::max(1L, std::min<long>(ncand, std::max(maxb, 1)));
+    const int nsel = hook ? hook->nsel : 0;
+    const int nbd = std::max(1, std::min(nsel, std::max(maxb, 1)));  // workgroups of the stage launch
 
     DevBuf dc(hc.size() * 16), deb(eb.size() * 4), dtw(tabs), dm(masks ? (size_t)ncand * words * 4 : 4),
         dpk(peaks ? (size_t)ncand * 8 : 8), dbp((size_t)nb * 8), dbi((size_t)nb * 8), dwin(16), dbeta((size_t)n * 16),
-        dscr(mode == 2 ? (size_t)nb * (14 * n + 1) * 16 : 16);
+        dscr(mode == 2 ? (size_t)std::max(nb, nbd) * (14 * n + 1) * 16 : 16);
     MBFIR_HIP(hipMemcpyAsync(dc.p, hc.data(), hc.size() * 16, hipMemcpyHostToDevice, st));
     MBFIR_HIP(hipMemcpyAsync(deb.p, eb.data(), eb.size() * 4, hipMemcpyHostToDevice, st));
     if (masks) MBFIR_HIP(hipMemcpyAsync(dm.p, masks, (size_t)ncand * words * 4, hipMemcpyHostToDevice, st));
@@ -399,9 +497,9 @@ long flip_search_run(int device, void* stream, int n, int nz, const double* c0_r
     p.scratch = dscr.as<double2>(); p.stride = 14 * n + 1;
     p.pick = nullptr; p.beta_out = nullptr;
     auto launch = [&](int grid, const FlipParams& q) {
-        if (mode == 0) hipLaunchKernelGGL(k_flip_score<0>, dim3(grid), dim3(threads), lds, st, q);
-        else if (mode == 1) hipLaunchKernelGGL(k_flip_score<1>, dim3(grid), dim3(threads), lds, st, q);
-        else hipLaunchKernelGGL(k_flip_score<2>, dim3(grid), dim3(threads), lds, st, q);
+        if (mode == 0) hipLaunchKernelGGL((k_flip_score<0, false>), dim3(grid), dim3(threads), lds, st, q);
+        else if (mode == 1) hipLaunchKernelGGL((k_flip_score<1, false>), dim3(grid), dim3(threads), lds, st, q);
+        else hipLaunchKernelGGL((k_flip_score<2, false>), dim3(grid), dim3(threads), lds, st, q);
     };
     launch(nb, p);
     long* win_i = dwin.as<long>();
@@ -411,6 +509,7 @@ long flip_search_run(int device, void* stream, int n, int nz, const double* c0_r
     q.pick = win_i; q.beta_out = dbeta.as<double2>(); q.peaks = nullptr;
     launch(1, q);
     MBFIR_HIP(hipGetLastError());
+    if (hook) flip_stage_launch(*hook, p, mode, threads, lds, nb, nbd, ldsmax, st);
     long hw[2];
     std::vector<double2> hb(n);
     MBFIR_HIP(hipMemcpyAsync(hw, dwin.p, 16, hipMemcpyDeviceToHost, st));

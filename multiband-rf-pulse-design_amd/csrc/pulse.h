@@ -112,11 +112,22 @@ void abr2_lm_step_batch_run(int device, void* stream, int npulse, const long* ro
                             const double* w, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
                             const double* t_re, const double* t_im, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
                             int* status, double* loss, double* g_re, double* g_im);
-// Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.
+// What mbfir_test_flip_stages adds to a search (include/mbfir.h says what each block holds): the overrides, the selected candidates
+// and the host blocks the search's per-workgroup bests, the report and the stages go to (interleaved re, im where complex).
+struct FlipStages {
+    int force_mode, max_blocks, nsel;
+    const long* sel;
+    double* blk_p;
+    long* blk_i;
+    double *beta, *bf, *xl, *xlfp, *afa, *a, *theta, *peak;
+    long* report;
+};
+// Root-flip search (flip.hip): returns the winner, -1 when no candidate has a finite peak.  With `hook` the same launches under its
+// overrides, then the stage launch; a forced mode that does not fit the device's LDS throws std::invalid_argument before any launch.
 long flip_search_run(int device, void* stream, int n, int nz, const double* c0_re, const double* c0_im, const double* z_re,
                      const double* z_im, const double* zf_re, const double* zf_im, long ncand, const unsigned* masks,
                      const int* enum_bits, int scale_rule, double s_re, double s_im, int criterion, int tie_high, double* peaks,
-                     double* beta_re, double* beta_im, double* winner_peak);
+                     double* beta_re, double* beta_im, double* winner_peak, const FlipStages* hook = nullptr);
 
 // Batched Parks-McClellan exchange (remez.hip): one workgroup per design.  status: 0 converged, 1 maxiter reached (last iterate
 // returned), 2 the exchange lost the alternation (no valid iterate).
