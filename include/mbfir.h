@@ -355,6 +355,30 @@ int mbfir_abr2_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
                              const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
                              const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im,
                              double* ggx, double* ggy);
+/* ---- Adjoint of mbfir_bloch_batch with respect to the b1 samples and the initial magnetisation ----------------------------------
+ * The vector-Jacobian product of the end point (mode 0) of mbfir_bloch_batch, relaxation included: the forward call's input
+ * arguments up to nscale and scales (no mode: the steady state and the recorded trajectory are not differentiated), then
+ *   m0x / m0y / m0z: the initial magnetisation in the layout of the mode-0 outputs, block (s, f, k) of pulse p at O_p + (s nf_p + f)
+ *     npos_p + k with O_p = sum_{q < p} nscale nf_q npos_q; all three NULL = [0 0 1] everywhere.
+ *   cmx / cmy / cmz: the cotangents of mx / my / mz in the same layout, dL = sum cmx dmx + cmy dmy + cmz dmz.
+ *   g_re / g_im: one entry per b1 sample, laid out as b1_re / b1_im: dL/dRe b1 and dL/dIm b1, summed over the points of the pulse
+ *     and over the scales (scale s contributes s times the gradient with respect to s b1).
+ *   gm0x / gm0y / gm0z: dL/dm0 of every (scale, frequency, position) block, in the same layout; all three NULL = not wanted.
+ * gx / gy / gz, the intervals, t1, t2, the grids and the scales are not differentiated.  The step m_t = D_t R_t m_{t-1} + c_t is a
+ * contraction, so the reverse sweep never divides by E1 or E2: the forward sweep keeps m before every 8th sample in a device
+ * scratch array (3 ceil(ntime_p / 8) doubles per point and scale) and the reverse sweep steps each group of 8 samples forwards
+ * again from its checkpoint before it walks it backwards.  One upload, two launches (the sweeps with one partial per workgroup and
+ * sample, then the sum of a pulse's partials over chunks and scales in index order, times gamma dt), one download; no atomics, so a
+ * pulse's gradient bits depend only on the pulse, its grids, its cotangents and the scale list.  The argument checks and their
+ * MBFIR_E_ARG messages are those of mbfir_bloch_batch; further MBFIR_E_ARG cases, each with its reason in mbfir_last_error and no
+ * device work done: a cotangent or gradient plane NULL, m0x / m0y / m0z only partly given, gm0x / gm0y / gm0z only partly given.  A
+ * NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, const double* cmx, const double* cmy,
+                          const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y, double* gm0z);
 /* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
  * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
  * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the

@@ -135,6 +135,8 @@ SYMBOLS = {
                                       _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, C.c_int,
                                        _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "mbfir_bloch_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
+                                        C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 11),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -789,7 +791,7 @@ from . import spiral        # noqa: E402  (dz2d.m / csg.m spiral 2D pulses and t
 from .spiral import csg, dz2d, dz2d_batch, ktog, ktos, gt2cm   # noqa: E402
 from . import ssmb          # noqa: E402  (multiband spectral-spatial pulses: dzrf_mb's spectral beta, device 2D SLR)
 from .ssmb import dzss_mb, dzss_mb_batch, fold_bands   # noqa: E402
-from . import torchsim      # noqa: E402  (torch.autograd wrappers of abr_batch / abr2_batch; torch is imported on first use)
+from . import torchsim      # noqa: E402  (torch.autograd wrappers of abr_batch / abr2_batch / bloch_batch; torch is imported on first use)
 # `mbfir.dzrf` becomes the conventional designer (dzrf.m).  The module of dzrf_mb stays importable as `mbfir.dzrf` through
 # sys.modules (`from mbfir.dzrf import dzrf_mb`), and the function carries that module's public names for attribute access.
 dzrf = slrclassic.dzrf
@@ -1286,70 +1288,90 @@ def sim_block_table(ntime, npoint, nscale):
     return out[:, :3]
 
 
+class _BlochArgs:
+    """The checked arguments of bloch_batch and bloch_vjp_batch: the scales, the per-pulse sizes nt / nf / npos, and `head`, the
+    arguments of the C calls from npulse up to and including scales (the arrays they point to are kept in `keep`)."""
+
+    def __init__(self, who, pulses, df, dp, scales):
+        pulses, sc = list(pulses), _vec(scales)
+        if not pulses:
+            raise ValueError("%s: no pulses" % who)
+        if len(sc) == 0:
+            raise ValueError("%s: the scale list is empty" % who)
+        P = len(pulses)
+        b1s, grs, tss, t1s, t2s, gams = [], [], [], [], [], []
+        for q, (b1, gr, tp, t1, t2, nucleus) in enumerate(pulses):
+            if np.size(b1) == 0:
+                raise ValueError("%s: pulse %d has no samples" % (who, q))
+            b1, gr, tp, gamma = _bloch_pulse(b1, gr, tp, nucleus)
+            if gr.shape[1] > 3:
+                raise ValueError("%s: pulse %d has more than 3 gradient axes" % (who, q))
+            b1s.append(b1)
+            grs.append(gr)
+            tss.append(tp)
+            t1s.append(float(t1))
+            t2s.append(float(t2))
+            gams.append(gamma)
+        dfs = [_vec(v) for v in _per_pulse(df, P)]
+        dps = []
+        for v in _per_pulse(dp, P):
+            v = np.asarray(v, dtype=np.float64)
+            dps.append(v.reshape(-1, 1) if v.ndim < 2 else v)
+        if any(len(v) == 0 for v in dfs) or any(v.shape[0] == 0 or v.shape[1] > 3 for v in dps):
+            raise ValueError("%s: an empty grid, or positions with more than 3 axes" % who)
+        self.P, self.S, self.sc = P, len(sc), sc
+        self.nt = [len(b) for b in b1s]
+        self.nf = [len(dfs[0 if len(dfs) == 1 else q]) for q in range(P)]
+        self.npos = [dps[0 if len(dps) == 1 else q].shape[0] for q in range(P)]
+        gax, pax = max(g.shape[1] for g in grs), max(v.shape[1] for v in dps)
+        g3 = [_vec(np.concatenate([g[:, i] if i < g.shape[1] else np.zeros(len(g)) for g in grs])) if i < gax else None
+              for i in range(3)]
+        p3 = [_vec(np.concatenate([v[:, i] if i < v.shape[1] else np.zeros(v.shape[0]) for v in dps])) if i < pax else None
+              for i in range(3)]
+        b1 = np.concatenate(b1s)
+        nul = C.cast(None, _dp)
+        self.keep = [_offsets(self.nt), _vec(b1.real), _vec(b1.imag), g3, _offsets([len(t) for t in tss]), _vec(np.concatenate(tss)),
+                     _vec(t1s), _vec(t2s), _vec(gams), _offsets([len(v) for v in dfs]), _vec(np.concatenate(dfs)),
+                     _offsets([v.shape[0] for v in dps]), p3]
+        k = self.keep
+        self.head = [P, _lptr(k[0]), _ptr(k[1]), _ptr(k[2]), *[_ptr(g) if g is not None else nul for g in g3], _lptr(k[4]), _ptr(k[5]),
+                     _ptr(k[6]), _ptr(k[7]), _ptr(k[8]), len(dfs), _lptr(k[9]), _ptr(k[10]), len(dps), _lptr(k[11]),
+                     *[_ptr(p) if p is not None else nul for p in p3], self.S, _ptr(sc)]
+
+    def m0_planes(self, m0, ooff, ntout):
+        """Three planes of ooff[-1] zeros with the initial magnetisation (None: [0 0 1]) at the first entry of every (scale,
+        frequency, position) block of ntout[q] entries."""
+        out = [np.zeros(int(ooff[-1])) for _ in range(3)]
+        each = isinstance(m0, list) and len(m0) == self.P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
+        for c, dflt in enumerate((0.0, 0.0, 1.0)):
+            for q in range(self.P):
+                v, nf, npos = dflt, self.nf[q], self.npos[q]
+                if m0 is not None:
+                    v = np.asarray((m0[q] if each else m0)[c], dtype=np.float64)
+                    v = v.reshape(nf, npos) if v.size == nf * npos else np.broadcast_to(v, (nf, npos))
+                    v = v.ravel()
+                out[c][ooff[q]:ooff[q + 1]].reshape(self.S, nf * npos, ntout[q])[:, :, 0] = v
+        return out
+
+
 def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
     """Many `bloch` simulations in one launch (mbfir_bloch_batch): every pulse at every transmit-gain scale.  Each pulse is
     (b1, gr, tp, t1, t2, nucleus) with bloch's meaning of every field (tp a scalar interval, ntime intervals or ntime increasing
     end times; nucleus 'C-13', 'H-1' or gamma in rad/s/G).  df (Hz) and dp (cm, (npos,) or (npos, 1..3)): one grid shared by
     every pulse, or a Python list of one array per pulse.  Scale s multiplies b1.  m0: None (equilibrium) or (mx, my, mz), each
-    a scalar or (nf, npos) per pulse, the initial magnetisation at every scale.  Returns a list of (mx, my, mz) per pulse, each of
+    a scalar or (nf, npos) per pulse, the initial magnetisation at every scale, or a Python list of one such tuple per pulse.  Returns a list of (mx, my, mz) per pulse, each of
     shape (S, nf, npos) or, with mode & 2, (S, nf, npos, ntime).  A pulse's bits depend neither on the other pulses nor on the
     other scales."""
     pulses, sc = list(pulses), _vec(scales)
-    if not pulses:
-        raise ValueError("bloch_batch: no pulses")
-    if len(sc) == 0:
-        raise ValueError("bloch_batch: the scale list is empty")
-    if mode not in (0, 1, 2, 3):
+    if pulses and len(sc) and mode not in (0, 1, 2, 3):
         raise ValueError("bloch_batch: mode must be 0, 1, 2 or 3")
-    P, S, mode = len(pulses), len(sc), int(mode)
-    b1s, grs, tss, t1s, t2s, gams = [], [], [], [], [], []
-    for q, (b1, gr, tp, t1, t2, nucleus) in enumerate(pulses):
-        if np.size(b1) == 0:
-            raise ValueError("bloch_batch: pulse %d has no samples" % q)
-        b1, gr, tp, gamma = _bloch_pulse(b1, gr, tp, nucleus)
-        if gr.shape[1] > 3:
-            raise ValueError("bloch_batch: pulse %d has more than 3 gradient axes" % q)
-        b1s.append(b1)
-        grs.append(gr)
-        tss.append(tp)
-        t1s.append(float(t1))
-        t2s.append(float(t2))
-        gams.append(gamma)
-    dfs = [_vec(v) for v in _per_pulse(df, P)]
-    dps = []
-    for v in _per_pulse(dp, P):
-        v = np.asarray(v, dtype=np.float64)
-        dps.append(v.reshape(-1, 1) if v.ndim < 2 else v)
-    if any(len(v) == 0 for v in dfs) or any(v.shape[0] == 0 or v.shape[1] > 3 for v in dps):
-        raise ValueError("bloch_batch: an empty grid, or positions with more than 3 axes")
-    nt = [len(b) for b in b1s]
-    nf = [len(dfs[0 if len(dfs) == 1 else q]) for q in range(P)]
-    npos = [dps[0 if len(dps) == 1 else q].shape[0] for q in range(P)]
+    A = _BlochArgs("bloch_batch", pulses, df, dp, sc)
+    P, S, mode, nt, nf, npos = A.P, A.S, int(mode), A.nt, A.nf, A.npos
     ntout = [n if mode & 2 else 1 for n in nt]
     ooff = _offsets([S * f * k * o for f, k, o in zip(nf, npos, ntout)])
-    out = [np.zeros(int(ooff[-1])) for _ in range(3)]
-    for c, dflt in enumerate((0.0, 0.0, 1.0)):
-        for q in range(P):
-            v = dflt
-            if m0 is not None:
-                v = np.asarray(m0[c], dtype=np.float64)
-                v = v.reshape(nf[q], npos[q]) if v.size == nf[q] * npos[q] else np.broadcast_to(v, (nf[q], npos[q]))
-                v = v.ravel()
-            out[c][ooff[q]:ooff[q + 1]].reshape(S, nf[q] * npos[q], ntout[q])[:, :, 0] = v
-    gax, pax = max(g.shape[1] for g in grs), max(v.shape[1] for v in dps)
-    g3 = [_vec(np.concatenate([g[:, i] if i < g.shape[1] else np.zeros(len(g)) for g in grs])) if i < gax else None
-          for i in range(3)]
-    p3 = [_vec(np.concatenate([v[:, i] if i < v.shape[1] else np.zeros(v.shape[0]) for v in dps])) if i < pax else None
-          for i in range(3)]
-    b1 = np.concatenate(b1s)
+    out = A.m0_planes(m0, ooff, ntout)
     ctx = ctx or get_context()
-    nul = C.cast(None, _dp)
-    rc = load_library().mbfir_bloch_batch(
-        ctx._h, P, _lptr(_offsets(nt)), _ptr(_vec(b1.real)), _ptr(_vec(b1.imag)), *[_ptr(g) if g is not None else nul for g in g3],
-        _lptr(_offsets([len(t) for t in tss])), _ptr(_vec(np.concatenate(tss))), _ptr(_vec(t1s)), _ptr(_vec(t2s)), _ptr(_vec(gams)),
-        len(dfs), _lptr(_offsets([len(v) for v in dfs])), _ptr(_vec(np.concatenate(dfs))),
-        len(dps), _lptr(_offsets([v.shape[0] for v in dps])), *[_ptr(p) if p is not None else nul for p in p3],
-        S, _ptr(sc), mode, *[_ptr(o) for o in out])
+    rc = load_library().mbfir_bloch_batch(ctx._h, *A.head, mode, *[_ptr(o) for o in out])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -1358,6 +1380,50 @@ def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
         shape = (S, nf[q], npos[q], nt[q]) if mode & 2 else (S, nf[q], npos[q])
         res.append(tuple(o[ooff[q]:ooff[q + 1]].reshape(shape) for o in out))
     return res
+
+
+def bloch_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=False, ctx=None):
+    """The adjoint of bloch_batch's end point (mode 0) with respect to b1 and the initial magnetisation, relaxation included
+    (mbfir_bloch_vjp_batch): pulses, df, dp, scales and m0 as for bloch_batch; cot: one (cmx, cmy, cmz) per pulse,
+    the cotangents of the (mx, my, mz) that bloch_batch returns, each of shape (S, nf, npos).  Returns a list of complex (ntime,)
+    gradients dL/dRe b1 + i dL/dIm b1, summed over the points and the scales; with grad_m0, a list of (grad_b1, (gmx, gmy, gmz)),
+    the second being dL/dm0 of every (scale, frequency, position), each of shape (S, nf, npos) (one m0 serves every scale: its
+    gradient is their sum over the scales).  Deterministic: a pulse's gradient bits depend only on the pulse, its grids, its
+    cotangents and the scales.  gr, tp, t1, t2, df and dp are not differentiated."""
+    A = _BlochArgs("bloch_vjp_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    cot = list(cot)
+    if len(cot) != P:
+        raise ValueError("bloch_vjp_batch: %d cotangent triples for %d pulses" % (len(cot), P))
+    planes = [[], [], []]
+    for q, tri in enumerate(cot):
+        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+            raise ValueError("bloch_vjp_batch: the cotangent of pulse %d must be a triple (cmx, cmy, cmz)" % q)
+        tri = [np.asarray(v, dtype=np.float64) for v in tri]
+        shape = (S, nf[q], npos[q])
+        if any(v.shape != shape for v in tri):
+            raise ValueError("bloch_vjp_batch: the cotangents of pulse %d have shapes %s, %s and %s, the forward call returns %s"
+                             % ((q,) + tuple(v.shape for v in tri) + (shape,)))
+        for c in range(3):
+            planes[c].append(tri[c].ravel())
+    cm = [_vec(np.concatenate(p)) for p in planes]
+    ooff, toff = _offsets([S * f * k for f, k in zip(nf, npos)]), _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    m0p = [nul] * 3 if m0 is None else A.m0_planes(m0, ooff, [1] * P)
+    grad = [np.zeros(int(toff[-1])) for _ in range(2)]
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_vjp_batch(ctx._h, *A.head, *[_plane(v) if m0 is not None else v for v in m0p],
+                                              *[_ptr(v) for v in cm], _ptr(grad[0]), _ptr(grad[1]),
+                                              *[_ptr(v) if grad_m0 else v for v in gm])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all = grad[0] + 1j * grad[1]
+    res = [g_all[toff[q]:toff[q + 1]] for q in range(P)]
+    if not grad_m0:
+        return res
+    return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
 
 
 def _rf_g(pulse, q, who, gtype):

@@ -1031,19 +1031,17 @@ int mbfir_abr2(mbfir_ctx* ctx, int n, const double* rf_re, const double* rf_im, 
                                   0, a_re, a_im, b_re, b_im));
 }
 
-int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
-                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
-                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
-                      const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
-                      double* my, double* mz) {
-    if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_batch: " + why; return MBFIR_E_ARG; };
+// The argument checks of mbfir_bloch_batch, shared with its adjoint (who: the call's name in the message; arrays: the caller's own
+// required arrays are all there).  0, or MBFIR_E_ARG with ctx->err set.  npoint (npulse entries) receives the points per pulse.
+static int bloch_batch_check(mbfir_ctx* ctx, const char* who, int npulse, const long* toff, const long* tsoff, const double* t1,
+                             const double* t2, int nfgrid, const long* foff, int npgrid, const long* poff, int nscale, int mode,
+                             bool arrays, std::vector<long>& npoint) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     if (npulse < 1) return bad("no pulses");
     if (nscale < 1) return bad("the scale list is empty");
     if (mode < 0 || mode > 3) return bad("mode must be 0, 1, 2 or 3");
     if ((nfgrid != 1 && nfgrid != npulse) || (npgrid != 1 && npgrid != npulse)) return bad("nfgrid and npgrid must be 1 or npulse");
-    if (!toff || !b1_re || !b1_im || !tsoff || !tsteps || !t1 || !t2 || !gamma || !foff || !df || !poff || !scales || !mx || !my || !mz)
-        return bad("a required array is null");
+    if (!arrays) return bad("a required array is null");
     if (const int e = sim_pulse_offsets_bad(toff, npulse, "toff", bad)) return e;
     if (tsoff[0] != 0) return bad("inconsistent offsets: tsoff does not start at 0");
     for (int p = 0; p < npulse; ++p) {
@@ -1055,7 +1053,8 @@ int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double
     }
     if (const char* why = sim_offsets_bad(foff, nfgrid)) return bad(std::string("inconsistent offsets: foff ") + why);
     if (const char* why = sim_offsets_bad(poff, npgrid)) return bad(std::string("inconsistent offsets: poff ") + why);
-    std::vector<long> npoint(npulse), ntout(npulse);
+    npoint.assign(npulse, 0);
+    std::vector<long> ntout(npulse);
     for (int p = 0; p < npulse; ++p) {
         const int fg = nfgrid == 1 ? 0 : p, pg = npgrid == 1 ? 0 : p;
         npoint[p] = (foff[fg + 1] - foff[fg]) * (poff[pg + 1] - poff[pg]);
@@ -1063,6 +1062,20 @@ int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double
     }
     if (toff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
         return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_bloch_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                      const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                      const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                      const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                      double* my, double* mz) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && mx && my && mz;
+    if (const int e = bloch_batch_check(ctx, "bloch_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, mode,
+                                        arrays, npoint))
+        return e;
     MBFIR_TRY(ctx, bloch_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
                                    gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, mode, mx, my, mz));
 }
@@ -1161,6 +1174,42 @@ int mbfir_abr2_vjp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
     }
     MBFIR_TRY(ctx, abr2_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
                                       yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im));
+}
+
+// The Bloch adjoint keeps 3 x 256 checkpoint doubles per (workgroup, group of 8 samples): false when their count overflows or
+// exceeds 2^56.
+static bool bloch_checkpoints_fit(int npulse, int nscale, const long* toff, const long* npoint) {
+    long total = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e;
+        if (__builtin_mul_overflow((npoint[p] + 255) / 256 * nscale, (toff[p + 1] - toff[p] + 7) / 8 * 768, &e) ||
+            __builtin_add_overflow(total, e, &total))
+            return false;
+    }
+    return total <= (1L << 56);
+}
+
+int mbfir_bloch_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, const double* cmx, const double* cmy,
+                          const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y, double* gm0z) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_vjp_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_vjp_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (!cmx || !cmy || !cmz || !g_re || !g_im) return bad("a cotangent or gradient plane is null");
+    if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    if ((gm0x || gm0y || gm0z) && !(gm0x && gm0y && gm0z)) return bad("gm0x, gm0y and gm0z are given together or not at all");
+    if (!vjp_partials_fit(npulse, nscale, toff, npoint.data()) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                       gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, cmx, cmy,
+                                       cmz, g_re, g_im, gm0x, gm0y, gm0z));
 }
 
 // The rf and g adjoints keep up to two double2 per (workgroup, sample): the rf pair and the g component(s).

@@ -1,4 +1,4 @@
-// Host side of the pulse tools (slr.hip, simgrad.hip, simgradg.hip, simjvp.hip, simgn.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
+// Host side of the pulse tools (slr.hip, simgrad.hip, simgradg.hip, simjvp.hip, simgn.hip, blochgrad.hip, flip.hip, remez.hip, specfact.hip): RF-pulse operations beside the conic solver, called by
 // api.cpp with its arguments checked.  Every runner takes host arrays in and out, makes `device` current first, runs on `stream`
 // (a hipStream_t), returns once the results are on the host, and throws HipError.  No HIP headers: api.cpp is built by the host
 // compiler.
@@ -54,6 +54,18 @@ void abr2_vjp_batch_run(int device, void* stream, int npulse, const long* roff, 
                         const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
                         const long* yoff, const double* y, int nscale, const double* scales, int mode, const double* ca_re,
                         const double* ca_im, const double* cb_re, const double* cb_im, double* g_re, double* g_im);
+// Adjoint of bloch_batch_run's end point (mode 0) with respect to b1 and the initial magnetisation (blochgrad.hip k_bloch_vjp_batch,
+// k_bloch_vjp_fold): the forward call's inputs; m0*: the initial magnetisation in the layout of the mode-0 outputs (all null: [0 0
+// 1]); cm*: the cotangents of mx / my / mz in that layout; g_re / g_im: dL / d Re b1, dL / d Im b1 per sample, summed over the
+// pulse's points and scales; gm0*: dL / d m0 per (scale, frequency, position) (all null: not downloaded).  One upload, two launches,
+// one download.
+void bloch_vjp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                         const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                         const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                         int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                         const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
+                         const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
+                         double* gm0z);
 // Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
 // k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
 // pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.

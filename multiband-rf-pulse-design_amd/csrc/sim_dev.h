@@ -1,7 +1,8 @@
 // What the batched Cayley-Klein simulators (slr.hip: k_abr_batch, k_abr2_batch), their adjoints (simgrad.hip, simgradg.hip), their
 // tangents (simjvp.hip) and their least-squares products (simgn.hip) share: the step of the forward model, the helpers and the steps of its
 // derivatives, the adjoint's reduction constants and fold, the per-pulse descriptors, and the host staging of one call.  Moved
-// here from slr.hip, simgrad.hip and simjvp.hip token for token.
+// here from slr.hip, simgrad.hip and simjvp.hip token for token.  Further down: what the Bloch simulator with relaxation
+// (k_bloch_batch) shares with its adjoint (blochgrad.hip).
 #pragma once
 #include "dev_common.h"
 #include "pulse.h"
@@ -356,6 +357,66 @@ struct Abr2Staged {
 void abr2_stage(Abr2Staged& A, int npulse, const long* roff, const double* rf_re, const double* rf_im, const double* gx,
                 const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                 int nscale, const double* scales);
+
+// What the Bloch simulator with relaxation (slr.hip k_bloch_batch) and its adjoint (blochgrad.hip) share, moved here from slr.hip
+// token for token: the rotation of one sample (bloch_simulation/blochC.c calcrotmat :171-236), the staged row, the per-pulse
+// descriptor, and the host staging of one call.
+struct Rot3 {
+    double m[9];           // column-major like the reference: m[i + 3 j]
+};
+__device__ __forceinline__ void bloch_rotmat(double nx, double ny, double nz, Rot3& R) {
+    const double phi = sqrt(nx * nx + ny * ny + nz * nz);
+    if (phi == 0.0) {
+        R.m[0] = 1; R.m[1] = 0; R.m[2] = 0; R.m[3] = 0; R.m[4] = 1; R.m[5] = 0; R.m[6] = 0; R.m[7] = 0; R.m[8] = 1;
+        return;
+    }
+    double sn, cp;
+    sincos(0.5 * phi, &sn, &cp);
+    const double sp = sn / phi;
+    const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
+    R.m[0] = ar * ar - ai * ai - br * br + bi * bi;
+    R.m[1] = -2 * ar * ai - 2 * br * bi;
+    R.m[2] = -2 * ar * br + 2 * ai * bi;
+    R.m[3] = 2 * ar * ai - 2 * br * bi;
+    R.m[4] = ar * ar - ai * ai + br * br - bi * bi;
+    R.m[5] = -2 * ai * br - 2 * ar * bi;
+    R.m[6] = 2 * ar * br + 2 * ai * bi;
+    R.m[7] = 2 * ar * bi - 2 * ai * br;
+    R.m[8] = ar * ar + ai * ai - br * br - bi * bi;
+}
+__device__ __forceinline__ void rot_vec(const Rot3& R, const double v[3], double o[3]) {
+    o[0] = R.m[0] * v[0] + R.m[3] * v[1] + R.m[6] * v[2];
+    o[1] = R.m[1] * v[0] + R.m[4] * v[1] + R.m[7] * v[2];
+    o[2] = R.m[2] * v[0] + R.m[5] * v[1] + R.m[8] * v[2];
+}
+constexpr int BLOCH_CH = 256;
+// in[t] = (b1 re, b1 im, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2, dt) per sample of every pulse (k_bloch_batch says how
+// a workgroup turns it into its LDS rows).
+constexpr int BLOCH_IN = 9;
+struct BlochPulseDev {
+    long t_off, f_off, p_off;     // first sample, first frequency, first position (3 doubles each)
+    long m_off, o_off;            // first m0 block, first output entry
+    int ntime, nf, npos, pad;
+    double gamma;
+};
+
+// The inputs of one mbfir_bloch_batch call, staged and filled (slr.hip): the sample rows, the grids, the initial magnetisation
+// and Staging's tables.  The forward call uploads this as it is; the adjoint adds its own sections first.  m0x / m0y / m0z: the
+// initial magnetisation at the first entry of every (scale, frequency, position) block of the outputs' layout under `mode` (all
+// three null: [0 0 1]).  ntime / npair: per pulse, as sim_block_table takes them; M: m0 blocks; O: output entries of one plane.
+struct BlochStaged {
+    Staging S;
+    size_t o_in = 0, o_df = 0, o_pos = 0, o_m0 = 0;
+    std::vector<BlochPulseDev> pd;
+    std::vector<int> ntime;
+    std::vector<long> npair;
+    long M = 0, O = 0;
+};
+void bloch_stage(BlochStaged& B, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                 const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                 const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                 const double* dy, const double* dz, int nscale, const double* scales, int mode, const double* m0x,
+                 const double* m0y, const double* m0z);
 
 // The adjoint's sections of one call (simgrad.hip, simgradg.hip): the cotangents, the partial descriptors and the fold kernel's table.
 struct VjpSections {

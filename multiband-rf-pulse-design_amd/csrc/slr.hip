@@ -151,35 +151,8 @@ __global__ __launch_bounds__(1024) void k_ab2rf(const double* __restrict__ a_il,
 // gradient, interval, E1, E2) are staged through LDS 256 samples at a time.
 //   mode bit 0: steady state (propagate A, B with M' = A M + B, then M = (I - A)^-1 B), bit 1: record every sample.
 // LDS row of sample t = (rotx, roty, gx, gy, gz (each * gamma * dt), dt * TWOPI, e1, e2); pos3 = (x, y, z) per position.
-struct Rot3 {
-    double m[9];           // column-major like the reference: m[i + 3 j]
-};
-__device__ __forceinline__ void bloch_rotmat(double nx, double ny, double nz, Rot3& R) {
-    const double phi = sqrt(nx * nx + ny * ny + nz * nz);
-    if (phi == 0.0) {
-        R.m[0] = 1; R.m[1] = 0; R.m[2] = 0; R.m[3] = 0; R.m[4] = 1; R.m[5] = 0; R.m[6] = 0; R.m[7] = 0; R.m[8] = 1;
-        return;
-    }
-    double sn, cp;
-    sincos(0.5 * phi, &sn, &cp);
-    const double sp = sn / phi;
-    const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
-    R.m[0] = ar * ar - ai * ai - br * br + bi * bi;
-    R.m[1] = -2 * ar * ai - 2 * br * bi;
-    R.m[2] = -2 * ar * br + 2 * ai * bi;
-    R.m[3] = 2 * ar * ai - 2 * br * bi;
-    R.m[4] = ar * ar - ai * ai + br * br - bi * bi;
-    R.m[5] = -2 * ai * br - 2 * ar * bi;
-    R.m[6] = 2 * ar * br + 2 * ai * bi;
-    R.m[7] = 2 * ar * bi - 2 * ai * br;
-    R.m[8] = ar * ar + ai * ai - br * br - bi * bi;
-}
-__device__ __forceinline__ void rot_vec(const Rot3& R, const double v[3], double o[3]) {
-    o[0] = R.m[0] * v[0] + R.m[3] * v[1] + R.m[6] * v[2];
-    o[1] = R.m[1] * v[0] + R.m[4] * v[1] + R.m[7] * v[2];
-    o[2] = R.m[2] * v[0] + R.m[5] * v[1] + R.m[8] * v[2];
-}
-constexpr int BLOCH_CH = 256;
+// Rot3, bloch_rotmat, rot_vec, BLOCH_CH, BLOCH_IN, BlochPulseDev and the host staging (bloch_stage) are in sim_dev.h, which blochgrad.hip
+// (the adjoint) shares.
 
 // ------------------------------------------------------------------------------------------------
 // Batched simulators: P pulses x S transmit-gain scales in one launch.  Workgroup blockIdx.x -> (pulse, scale, chunk of 256 points)
@@ -229,13 +202,6 @@ __global__ __launch_bounds__(256) void k_abr_batch(const double* __restrict__ rf
 // stages sample t forms rotx = ((-(re s)) gamma) dt and roty = ((im s) gamma) dt (blochC.c:332-333, products in this order) for
 // the workgroup's scale s, so the LDS tile holds the rows of the pulse b1 s.  m0: (x, y, z) of every (scale, frequency,
 // position) block of every pulse; output S x nf x npos x ntout per pulse, scale-major.
-constexpr int BLOCH_IN = 9;
-struct BlochPulseDev {
-    long t_off, f_off, p_off;     // first sample, first frequency, first position (3 doubles each)
-    long m_off, o_off;            // first m0 block, first output entry
-    int ntime, nf, npos, pad;
-    double gamma;
-};
 __global__ __launch_bounds__(256) void k_bloch_batch(const double* __restrict__ in, const double* __restrict__ df,
                                                      const double* __restrict__ pos3, const double* __restrict__ scales,
                                                      const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
@@ -691,7 +657,8 @@ void slr_run(int device, void* stream, int n, const double* b_re, const double* 
 // ------------------------------------------------------------------------------------------------
 // Host side of the forward simulators (mbfir_bloch_batch / mbfir_abr_batch / mbfir_abr2_batch, and mbfir_bloch / mbfir_abr /
 // mbfir_abr2 as their batch of one; arguments checked by api.cpp): every input in one staging buffer of 256-byte-aligned sections,
-// one upload, one launch, one download.
+// one upload, one launch, one download.  The staging functions (bloch_stage, abr_stage, abr2_stage) are shared with the derivative
+// calls' files, which add their own sections.
 
 long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscale, SimBlock* out) {
     long k = 0;
@@ -712,16 +679,17 @@ long sim_block_table(int npulse, const int* ntime, const long* npoint, int nscal
 }
 
 constexpr double TWOPI_REF = 6.283185;                      // blochC.c:6, the reference's truncated constant
-void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
-                     const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
-                     const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
-                     const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
-                     double* my, double* mz) {
-    MBFIR_HIP(hipSetDevice(device));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    std::vector<BlochPulseDev> pd(npulse);
-    std::vector<int> nt(npulse);
-    std::vector<long> npair(npulse);
+void bloch_stage(BlochStaged& B, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                 const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                 const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                 const double* dy, const double* dz, int nscale, const double* scales, int mode, const double* m0x,
+                 const double* m0y, const double* m0z) {
+    std::vector<BlochPulseDev>& pd = B.pd;
+    std::vector<int>& nt = B.ntime;
+    std::vector<long>& npair = B.npair;
+    pd.resize(npulse);
+    nt.resize(npulse);
+    npair.resize(npulse);
     long M = 0, O = 0;                                       // m0 blocks, output entries
     for (int p = 0; p < npulse; ++p) {
         const int fg = nfgrid == 1 ? 0 : p, pg = npgrid == 1 ? 0 : p;
@@ -736,9 +704,12 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
         M += nscale * npair[p];
         O += nscale * npair[p] * ((mode & 2) ? d.ntime : 1);
     }
+    B.M = M;
+    B.O = O;
     const long T = toff[npulse], F = foff[nfgrid], NP = poff[npgrid];
-    Staging S;
-    const size_t o_in = S.add(T * BLOCH_IN * 8), o_df = S.add(F * 8), o_pos = S.add(NP * 24), o_m0 = S.add(M * 24);
+    Staging& S = B.S;
+    const size_t o_in = B.o_in = S.add(T * BLOCH_IN * 8), o_df = B.o_df = S.add(F * 8), o_pos = B.o_pos = S.add(NP * 24),
+                 o_m0 = B.o_m0 = S.add(M * 24);
     S.add_tables(npulse, pd.data(), sizeof(BlochPulseDev), nt.data(), npair.data(), nscale, scales);
     double* in = S.at<double>(o_in);
     for (int p = 0; p < npulse; ++p) {
@@ -768,14 +739,28 @@ void bloch_batch_run(int device, void* stream, int npulse, const long* toff, con
         const long ntout = (mode & 2) ? nt[p] : 1;
         for (long b = 0; b < nscale * npair[p]; ++b) {
             const long o = pd[p].o_off + b * ntout, m = 3 * (pd[p].m_off + b);
-            m0[m] = mx[o]; m0[m + 1] = my[o]; m0[m + 2] = mz[o];
+            m0[m] = m0x ? m0x[o] : 0.0; m0[m + 1] = m0x ? m0y[o] : 0.0; m0[m + 2] = m0x ? m0z[o] : 1.0;
         }
     }
+}
+
+void bloch_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                     const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                     const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                     const double* dx, const double* dy, const double* dz, int nscale, const double* scales, int mode, double* mx,
+                     double* my, double* mz) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    BlochStaged B;
+    bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                nscale, scales, mode, mx, my, mz);
+    Staging& S = B.S;
+    const long O = B.O;
     S.upload(3 * (size_t)O * 8, st);
     double* out = S.dev<double>(S.o_out);
-    hipLaunchKernelGGL(k_bloch_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(o_in), S.dev<const double>(o_df),
-                       S.dev<const double>(o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
-                       S.dev<const SimBlock>(S.o_bk), S.dev<const double>(o_m0), mode, out, out + O, out + 2 * O);
+    hipLaunchKernelGGL(k_bloch_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(B.o_in), S.dev<const double>(B.o_df),
+                       S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const SimBlock>(S.o_bk), S.dev<const double>(B.o_m0), mode, out, out + O, out + 2 * O);
     std::vector<double> h(3 * (size_t)O);
     S.download(h.data(), h.size() * 8, st);
     std::copy(h.begin(), h.begin() + O, mx);

@@ -7,6 +7,8 @@ mbfir.abr_vjp_rfg_batch / mbfir.abr2_vjp_rfg_batch call that returns both gradie
 the rf call, with its bits.  A forward-mode tangent for g raises NotImplementedError.  rf is a complex128 tensor; the C ABI takes
 host pointers, so tensors go through host memory, and the results come back on rf's device.
 x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
+`bloch` runs mbfir.bloch_batch on one pulse (the Bloch simulation with T1 / T2, end point) and is differentiable in reverse mode in
+b1 and in the initial magnetisation m0, its backward being one mbfir.bloch_vjp_batch call (section 8p).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -140,6 +142,66 @@ def _functions():
             return grad, torch.from_numpy(gg.reshape(ctx.g_like[0])).to(ctx.g_like[1]), None, None, None, None
 
     return Abr, Abr2
+
+
+@functools.lru_cache(maxsize=None)
+def _bloch_function():
+    """The autograd.Function of `bloch`, built when torch is first needed (forward and setup_context separate, as above)."""
+    import torch
+
+    import mbfir
+
+    class Bloch(torch.autograd.Function):
+        @staticmethod
+        def forward(b1, m0, pulse, df, dp, scales):
+            if not torch.is_tensor(b1) or b1.dtype != torch.complex128 or b1.dim() != 1:
+                raise ValueError("torchsim: b1 must be a 1-D complex128 tensor")
+            if torch.is_tensor(m0) and m0.requires_grad and (m0.dtype != torch.float64 or m0.dim() != 3 or m0.shape[0] != 3):
+                raise ValueError("torchsim: an m0 that requires grad must be a float64 tensor of shape (3, nf, npos)")
+            m0h = _host(m0, np.float64)
+            res, = mbfir.bloch_batch([(_host(b1, np.complex128),) + pulse], df, dp, scales=scales,
+                                     m0=None if m0h is None else tuple(m0h))
+            return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(b1.device) for v in res)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, m0, pulse, df, dp, scales = inputs
+            ctx.args = (_host(m0, np.float64), pulse, df, dp, scales)
+            ctx.m0_like = (m0.shape, m0.device) if torch.is_tensor(m0) else None          # where m0's gradient goes
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch is not implemented (reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, cx, cy, cz):
+            b1, = ctx.saved_tensors
+            m0h, pulse, df, dp, scales = ctx.args
+            want_m0 = ctx.needs_input_grad[1]
+            cot = tuple(_host(c, np.float64) for c in (cx, cy, cz))
+            res, = mbfir.bloch_vjp_batch([(_host(b1, np.complex128),) + pulse], df, dp, [cot], scales=scales,
+                                         m0=None if m0h is None else tuple(m0h), grad_m0=want_m0)
+            grad, gm = res if want_m0 else (res, None)
+            gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if ctx.needs_input_grad[0] else None
+            if want_m0:                                                 # one m0 serves every scale: its gradient is their sum
+                gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
+            return gb, gm, None, None, None, None
+
+    return Bloch
+
+
+def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None):
+    """(mx, my, mz) of mbfir.bloch_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, scales=scales, m0=m0), the end point of the Bloch
+    simulation with relaxation, each a float64 tensor of shape (S, nf, npos) with bloch_batch's bits.  Differentiable in reverse mode
+    in b1 (a 1-D complex128 tensor) and in m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient
+    is summed over the scales); the backward is one mbfir.bloch_vjp_batch call.  Any other m0 ((mx, my, mz) or
+    an array of shape (3, nf, npos); None: equilibrium), gr, tp, t1, t2, df and dp are constants.  A forward-mode tangent raises
+    NotImplementedError."""
+    pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
+    if m0 is not None and not hasattr(m0, "detach"):
+        m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
+    return _bloch_function().apply(b1, m0, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
 
 
 def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
