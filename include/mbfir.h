@@ -379,6 +379,33 @@ int mbfir_bloch_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                           const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                           const double* m0x, const double* m0y, const double* m0z, const double* cmx, const double* cmy,
                           const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y, double* gm0z);
+/* ---- Tangent of mbfir_bloch_batch with respect to the b1 samples and the initial magnetisation -----------------------------------
+ * The Jacobian-vector product of the end point (mode 0) of mbfir_bloch_batch, relaxation included: the forward call's input
+ * arguments up to nscale and scales (no mode), then
+ *   m0x / m0y / m0z: the initial magnetisation, as mbfir_bloch_vjp_batch takes it; all three NULL = [0 0 1] everywhere.
+ *   ndir >= 1 and v_re / v_im: the b1 directions, direction-major within a pulse: sample t of direction k of pulse p at ndir toff[p] +
+ *     k ntime_p + t.
+ *   dm0x / dm0y / dm0z: the directions of the initial magnetisation; pulse p starts at ndir times its forward output offset O_p and
+ *     is laid out (direction, scale, point) row-major, the point index as in the forward call; all three NULL = zero.
+ *   mx / my / mz: laid out as the forward call's mode-0 outputs, with its bits; all three NULL = not downloaded.
+ *   dmx / dmy / dmz: the tangents, laid out as dm0: d/de m(b1 + e v, m0 + e dm0) at e = 0 for every direction, real-linear in (v,
+ *     dm0); scale s contributes the tangent along s v at s b1, and a scale of 0 contributes the m0 part alone.
+ * gx / gy / gz, the intervals, t1, t2, the grids and the scales are not differentiated.  One upload, one launch (one workgroup per
+ * forward workgroup and group of mbfir_test_bloch_jvp_group() directions, which share each sample's trigonometry and rotation),
+ * one download; no atomics, and a tangent's bits depend only on its pulse, scale, point and direction: not on the batch, its order,
+ * ndir or the direction's place among the others.  The argument checks and their MBFIR_E_ARG messages are those of
+ * mbfir_bloch_batch; further MBFIR_E_ARG cases, each with its reason in mbfir_last_error, in this order: a v or dm plane NULL; m0,
+ * dm0 or mx / my / mz only partly given; ndir < 1; a direction array, tangent output or workgroup count that overflows.  No device
+ * work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, int ndir, const double* v_re, const double* v_im,
+                          const double* dm0x, const double* dm0y, const double* dm0z, double* mx, double* my, double* mz,
+                          double* dmx, double* dmy, double* dmz);
+/* mbfir_test_bloch_jvp_group (host only): the directions one workgroup of the call above carries (a compile-time constant). */
+int mbfir_test_bloch_jvp_group(void);
 /* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
  * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
  * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the

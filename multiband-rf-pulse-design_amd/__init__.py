@@ -137,6 +137,9 @@ SYMBOLS = {
                                        _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_bloch_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 11),
+    "mbfir_bloch_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
+                                        C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 3 + [C.c_int] + [_dp] * 11),
+    "mbfir_test_bloch_jvp_group": (C.c_int, []),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -1289,7 +1292,7 @@ def sim_block_table(ntime, npoint, nscale):
 
 
 class _BlochArgs:
-    """The checked arguments of bloch_batch and bloch_vjp_batch: the scales, the per-pulse sizes nt / nf / npos, and `head`, the
+    """The checked arguments of bloch_batch, bloch_vjp_batch and bloch_jvp_batch: the scales, the per-pulse sizes nt / nf / npos, and `head`, the
     arguments of the C calls from npulse up to and including scales (the arrays they point to are kept in `keep`)."""
 
     def __init__(self, who, pulses, df, dp, scales):
@@ -1424,6 +1427,56 @@ def bloch_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=Fals
     if not grad_m0:
         return res
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
+
+
+def bloch_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), m0=None, tangents_m0=None, ctx=None):
+    """The tangent of bloch_batch's end point (mode 0) with respect to b1 and the initial magnetisation, relaxation included
+    (mbfir_bloch_jvp_batch): pulses, df, dp, scales and m0 as for bloch_batch; tangents: per pulse a complex
+    direction of b1 of shape (n,), or K of them of shape (K, n), the same K for every pulse; tangents_m0: None (m0 does not move) or
+    per pulse a triple (dmx, dmy, dmz), each broadcastable to (K, nf, npos): the direction of m0 that goes with each b1 direction,
+    the same at every scale, as m0 is.  Returns a list of ((mx, my, mz), (dmx, dmy, dmz)) per pulse: the primal of shape (S, nf,
+    npos) with bloch_batch's bits, and d/de m(b1 + e v, m0 + e dm0) at e = 0 for each direction, of shape (K, S, nf, npos), without
+    the K axis for a 1-D tangent.  Real-linear in (v, dm0).  One launch, the directions sharing each sample's trigonometry and
+    rotation; a tangent's bits depend only on its pulse, scale, point and direction.  gr, tp, t1, t2, df and dp are not
+    differentiated."""
+    A = _BlochArgs("bloch_jvp_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    K, keep, vplanes = _tangents("bloch_jvp_batch", tangents, [range(n) for n in A.nt])
+    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+    nul = C.cast(None, _dp)
+    dm0 = [nul] * 3
+    if tangents_m0 is not None:
+        tangents_m0 = list(tangents_m0)
+        if len(tangents_m0) != P:
+            raise ValueError("bloch_jvp_batch: %d m0 tangent triples for %d pulses" % (len(tangents_m0), P))
+        planes = [[], [], []]
+        for q, tri in enumerate(tangents_m0):
+            if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+                raise ValueError("bloch_jvp_batch: the m0 tangent of pulse %d must be a triple (dmx, dmy, dmz)" % q)
+            for c in range(3):
+                v = np.asarray(tri[c], dtype=np.float64)
+                try:
+                    v = np.broadcast_to(v, (K, nf[q], npos[q]))
+                except ValueError:
+                    raise ValueError("bloch_jvp_batch: an m0 tangent of pulse %d has shape %s, which does not broadcast to %s"
+                                     % (q, v.shape, (K, nf[q], npos[q]))) from None
+                planes[c].append(np.broadcast_to(v[:, None], (K, S, nf[q], npos[q])).ravel())
+        dm0 = [_vec(np.concatenate(p)) for p in planes]
+    m0p = [nul] * 3 if m0 is None else A.m0_planes(m0, ooff, [1] * P)
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)]
+    tan = [np.zeros(K * int(ooff[-1])) for _ in range(3)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_jvp_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], K, *[_ptr(v) for v in vplanes],
+                                              *[_plane(v) for v in dm0], *[_ptr(v) for v in out], *[_ptr(v) for v in tan])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = []
+    for q in range(P):
+        lo, hi, shape = int(ooff[q]), int(ooff[q + 1]), (S, nf[q], npos[q])
+        res.append((tuple(o[lo:hi].reshape(shape) for o in out),
+                    tuple(t[K * lo:K * hi].reshape(((K,) if keep else ()) + shape) for t in tan)))
+    return res
 
 
 def _rf_g(pulse, q, who, gtype):
@@ -1921,6 +1974,11 @@ from .refine import refine_batch   # noqa: E402  (batched Levenberg-Marquardt on
 def jvp_group():
     """The directions one workgroup of abr_jvp_batch / abr2_jvp_batch carries (mbfir_test_jvp_group)."""
     return int(load_library().mbfir_test_jvp_group())
+
+
+def bloch_jvp_group():
+    """The directions one workgroup of bloch_jvp_batch carries (mbfir_test_bloch_jvp_group)."""
+    return int(load_library().mbfir_test_bloch_jvp_group())
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

@@ -1262,9 +1262,11 @@ int mbfir_abr2_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
                                           nygrid, yoff, y, nscale, scales, mode, ca_re, ca_im, cb_re, cb_im, g_re, g_im, ggx, ggy));
 }
 
-// What the tangent calls check after abr_batch_check: ndir, and that ndir times the R rf samples, ndir times the forward output (at
-// most 2^56 entries each) and the forward workgroups times the direction groups (at most 2^31 - 1) fit.  0, or MBFIR_E_ARG with ctx->err set.
-static int jvp_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, long R, const long* npoint) {
+// What the tangent calls check after abr_batch_check (bloch_batch_check): ndir, and that ndir times the R rf samples, ndir times the
+// forward output (at most 2^56 entries each) and the forward workgroups times the direction groups (group: the directions one
+// workgroup carries; at most 2^31 - 1) fit.  0, or MBFIR_E_ARG with ctx->err set.
+static int jvp_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, long R, const long* npoint,
+                     int group = jvp_group()) {
     auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     if (ndir < 1) return bad("ndir must be at least 1");
     long total = 0, nblk = 0;                                  // abr_batch_check has bounded both for one direction
@@ -1272,7 +1274,7 @@ static int jvp_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, in
         total += npoint[p] * nscale;
         nblk += (npoint[p] + 255) / 256 * nscale;
     }
-    const long ngrp = (ndir + (long)jvp_group() - 1) / jvp_group();
+    const long ngrp = (ndir + (long)group - 1) / group;
     if (R > (1L << 56) / ndir || total > (1L << 56) / ndir || nblk > 2147483647L / ngrp) return bad("the output size or the workgroup count overflows");
     return 0;
 }
@@ -1309,6 +1311,30 @@ int mbfir_abr2_jvp_batch(mbfir_ctx* ctx, int npulse, const long* roff, const dou
     MBFIR_TRY(ctx, abr2_jvp_batch_run(ctx->device, ctx->solver->stream(), npulse, roff, rf_re, rf_im, gx, gy, nxgrid, xoff, x, nygrid,
                                       yoff, y, nscale, scales, mode, ndir, v_re, v_im, a_re, a_im, b_re, b_im, da_re, da_im, db_re,
                                       db_im));
+}
+
+int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, int ndir, const double* v_re, const double* v_im,
+                          const double* dm0x, const double* dm0y, const double* dm0z, double* mx, double* my, double* mz,
+                          double* dmx, double* dmy, double* dmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_jvp_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_jvp_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (!v_re || !v_im || !dmx || !dmy || !dmz) return bad("a direction or tangent plane is null");
+    if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    if ((dm0x || dm0y || dm0z) && !(dm0x && dm0y && dm0z)) return bad("dm0x, dm0y and dm0z are given together or not at all");
+    if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
+    if (const int e = jvp_check(ctx, "bloch_jvp_batch", npulse, nscale, ndir, toff[npulse], npoint.data(), bloch_jvp_group())) return e;
+    MBFIR_TRY(ctx, bloch_jvp_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                       gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, ndir, v_re,
+                                       v_im, dm0x, dm0y, dm0z, mx, my, mz, dmx, dmy, dmz));
 }
 
 // What the least-squares calls check after abr_batch_check, in this order: their own arrays, the profile, the O weights (O: the
@@ -1460,6 +1486,7 @@ int mbfir_abr2_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
 }
 
 int mbfir_test_jvp_group(void) { return jvp_group(); }
+int mbfir_test_bloch_jvp_group(void) { return bloch_jvp_group(); }
 
 long mbfir_test_sim_blocks(int npulse, const int* ntime, const long* npoint, int nscale, int* out) {
     if (npulse < 1 || nscale < 1 || !ntime || !npoint) return -1;

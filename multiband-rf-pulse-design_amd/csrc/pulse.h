@@ -66,6 +66,19 @@ void bloch_vjp_batch_run(int device, void* stream, int npulse, const long* toff,
                          const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
                          const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
                          double* gm0z);
+// Tangent of bloch_batch_run's end point (mode 0) with respect to b1 and the initial magnetisation (blochjvp.hip k_bloch_jvp_batch):
+// the forward call's inputs and m0* as above; ndir >= 1 directions per pulse, direction k of pulse p at ndir toff[p] + k n_p of v_re
+// / v_im; dm0*: the m0 directions, pulse p from ndir times its forward output offset, (direction, scale, point) row-major (all
+// null: zero); m*: the forward call's outputs with its bits (all null: not downloaded); dm*: laid out as dm0.  One upload, one
+// launch of bloch_jvp_group() directions per workgroup, one download.
+int bloch_jvp_group();
+void bloch_jvp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                         const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                         const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                         int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                         const double* scales, const double* m0x, const double* m0y, const double* m0z, int ndir, const double* v_re,
+                         const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z, double* mx, double* my,
+                         double* mz, double* dmx, double* dmy, double* dmz);
 // Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
 // k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
 // pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.

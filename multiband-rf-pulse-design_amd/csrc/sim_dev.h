@@ -334,6 +334,17 @@ struct Staging {
     }
 };
 
+// The block table of the tangent calls (simjvp.hip, blochjvp.hip) as a new section of S, after add_tables: the forward table with
+// every entry repeated once per direction group, the group number in SimBlock::pad.  Returns the section's offset.
+inline size_t sim_group_table(Staging& S, int ngrp) {
+    const size_t o_jb = S.add(S.nblk * ngrp * sizeof(SimBlock));
+    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
+    SimBlock* jb = S.at<SimBlock>(o_jb);
+    for (long w = 0; w < S.nblk; ++w)
+        for (int q = 0; q < ngrp; ++q) *jb++ = SimBlock{fb[w].pulse, fb[w].scale, fb[w].chunk, q};
+    return o_jb;
+}
+
 // The inputs of one mbfir_abr_batch / mbfir_abr2_batch call, staged and filled (slr.hip): rf interleaved, the gradient weights with
 // their defaults written out (a null g or gx is 2 pi / n per sample, a null gy is 0), the grids, and Staging's tables.  The forward
 // calls upload this as it is; the adjoints add their own sections first.  ntime / npoint: per pulse, as sim_block_table takes them;
@@ -358,20 +369,29 @@ void abr2_stage(Abr2Staged& A, int npulse, const long* roff, const double* rf_re
                 const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid, const long* yoff, const double* y,
                 int nscale, const double* scales);
 
-// What the Bloch simulator with relaxation (slr.hip k_bloch_batch) and its adjoint (blochgrad.hip) share, moved here from slr.hip
-// token for token: the rotation of one sample (bloch_simulation/blochC.c calcrotmat :171-236), the staged row, the per-pulse
+// What the Bloch simulator with relaxation (slr.hip k_bloch_batch), its adjoint (blochgrad.hip) and its tangent (blochjvp.hip)
+// share, moved here from slr.hip token for token: the rotation of one sample (bloch_simulation/blochC.c calcrotmat :171-236), the staged row, the per-pulse
 // descriptor, and the host staging of one call.
 struct Rot3 {
     double m[9];           // column-major like the reference: m[i + 3 j]
 };
-__device__ __forceinline__ void bloch_rotmat(double nx, double ny, double nz, Rot3& R) {
+// What a rotation computes from its angle alone: phi, sn, cp = sincos(phi / 2).  The tangent kernel (blochjvp.hip) takes it from
+// the rotation (KEEP) so that a sample's trigonometry is computed once; bloch_rotmat drops it, and compiles to what it compiled to
+// before the body became a template.
+struct BlochTrig {
+    double phi, sn, cp;
+};
+template <bool KEEP>
+__device__ __forceinline__ void bloch_rotmat_trig(double nx, double ny, double nz, Rot3& R, BlochTrig& t) {
     const double phi = sqrt(nx * nx + ny * ny + nz * nz);
     if (phi == 0.0) {
         R.m[0] = 1; R.m[1] = 0; R.m[2] = 0; R.m[3] = 0; R.m[4] = 1; R.m[5] = 0; R.m[6] = 0; R.m[7] = 0; R.m[8] = 1;
+        if (KEEP) t = BlochTrig{0.0, 0.0, 1.0};
         return;
     }
     double sn, cp;
     sincos(0.5 * phi, &sn, &cp);
+    if (KEEP) t = BlochTrig{phi, sn, cp};
     const double sp = sn / phi;
     const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
     R.m[0] = ar * ar - ai * ai - br * br + bi * bi;
@@ -383,6 +403,10 @@ __device__ __forceinline__ void bloch_rotmat(double nx, double ny, double nz, Ro
     R.m[6] = 2 * ar * br + 2 * ai * bi;
     R.m[7] = 2 * ar * bi - 2 * ai * br;
     R.m[8] = ar * ar + ai * ai - br * br - bi * bi;
+}
+__device__ __forceinline__ void bloch_rotmat(double nx, double ny, double nz, Rot3& R) {
+    BlochTrig t;
+    bloch_rotmat_trig<false>(nx, ny, nz, R, t);
 }
 __device__ __forceinline__ void rot_vec(const Rot3& R, const double v[3], double o[3]) {
     o[0] = R.m[0] * v[0] + R.m[3] * v[1] + R.m[6] * v[2];

@@ -132,12 +132,8 @@ JvpSections jvp_stage(Staging& S, long R, int ndir, const double* v_re, const do
     const int ngrp = (ndir + JVP_K - 1) / JVP_K;
     J.nblk = S.nblk * ngrp;
     J.o_v = S.add((size_t)ndir * R * 16);
-    J.o_jb = S.add(J.nblk * sizeof(SimBlock));
+    J.o_jb = sim_group_table(S, ngrp);
     pack_cplx((size_t)ndir * R, v_re, v_im, S.at<double2>(J.o_v));
-    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
-    SimBlock* jb = S.at<SimBlock>(J.o_jb);
-    for (long w = 0; w < S.nblk; ++w)
-        for (int q = 0; q < ngrp; ++q) *jb++ = SimBlock{fb[w].pulse, fb[w].scale, fb[w].chunk, q};
     return J;
 }
 // The output region: da, db (ndir O entries each), then a, b (O each), which are downloaded only when the caller wants them.

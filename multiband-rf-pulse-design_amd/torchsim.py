@@ -8,7 +8,8 @@ the rf call, with its bits.  A forward-mode tangent for g raises NotImplementedE
 host pointers, so tensors go through host memory, and the results come back on rf's device.
 x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
 `bloch` runs mbfir.bloch_batch on one pulse (the Bloch simulation with T1 / T2, end point) and is differentiable in reverse mode in
-b1 and in the initial magnetisation m0, its backward being one mbfir.bloch_vjp_batch call (section 8p).
+b1 and in the initial magnetisation m0, its backward being one mbfir.bloch_vjp_batch call (section 8p); with forward_mode=True it
+also has the forward-mode tangent in both, one mbfir.bloch_jvp_batch call with one direction (section 8q).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -146,7 +147,8 @@ def _functions():
 
 @functools.lru_cache(maxsize=None)
 def _bloch_function():
-    """The autograd.Function of `bloch`, built when torch is first needed (forward and setup_context separate, as above)."""
+    """The two autograd.Function classes of `bloch` (reverse mode only; with a forward-mode tangent), built when torch is first
+    needed (forward and setup_context separate, as above)."""
     import torch
 
     import mbfir
@@ -188,20 +190,42 @@ def _bloch_function():
                 gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
             return gb, gm, None, None, None, None
 
-    return Bloch
+    class BlochForward(Bloch):
+        """Bloch with a forward-mode tangent: the same forward and backward, plus a jvp that is one mbfir.bloch_jvp_batch call with
+        one direction, in b1 and, when m0 is a tensor with a tangent, in m0."""
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            Bloch.setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+
+        @staticmethod
+        def jvp(ctx, v, vm0, *_):
+            b1, = ctx.saved_tensors
+            m0h, pulse, df, dp, scales = ctx.args
+            b1h = _host(b1, np.complex128)
+            vh = np.zeros_like(b1h) if v is None else _host(v, np.complex128)
+            dm0 = None if vm0 is None else [tuple(_host(vm0, np.float64))]
+            (_, tan), = mbfir.bloch_jvp_batch([(b1h,) + pulse], df, dp, [vh], scales=scales,
+                                              m0=None if m0h is None else tuple(m0h), tangents_m0=dm0)
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in tan)
+
+    return Bloch, BlochForward
 
 
-def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None):
+def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None, forward_mode=False):
     """(mx, my, mz) of mbfir.bloch_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, scales=scales, m0=m0), the end point of the Bloch
     simulation with relaxation, each a float64 tensor of shape (S, nf, npos) with bloch_batch's bits.  Differentiable in reverse mode
     in b1 (a 1-D complex128 tensor) and in m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient
     is summed over the scales); the backward is one mbfir.bloch_vjp_batch call.  Any other m0 ((mx, my, mz) or
     an array of shape (3, nf, npos); None: equilibrium), gr, tp, t1, t2, df and dp are constants.  A forward-mode tangent raises
-    NotImplementedError."""
+    NotImplementedError unless forward_mode is set: then torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as
+    well, the tangent in b1 and in a tensor m0 being one mbfir.bloch_jvp_batch call with one direction (section 8q)."""
     pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
-    return _bloch_function().apply(b1, m0, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
+    fn = _bloch_function()[1 if forward_mode else 0]
+    return fn.apply(b1, m0, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
 
 
 def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
