@@ -406,6 +406,38 @@ int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                           double* dmx, double* dmy, double* dmz);
 /* mbfir_test_bloch_jvp_group (host only): the directions one workgroup of the call above carries (a compile-time constant). */
 int mbfir_test_bloch_jvp_group(void);
+/* ---- Least-squares products of mbfir_bloch_batch ----------------------------------------------------------------------------------
+ * For the end point (mx, my, mz) of mbfir_bloch_batch (mode 0), relaxation included, weights (wx, wy, wz) >= 0 and targets (tx, ty,
+ * tz) per output entry, the loss of a pulse is L = 1/2 sum w_c (m_c - t_c)^2 over c = x, y, z, its points and its scales, and J =
+ * dm / db1 is the Jacobian of the end point with respect to the b1 samples (real-linear, as in mbfir_bloch_jvp_batch).  The end
+ * point is its own profile: there is no profile argument.  The forward call's input arguments up to nscale and scales come first
+ * (no mode), then m0x / m0y / m0z as mbfir_bloch_vjp_batch takes them (all three NULL = [0 0 1] everywhere), then wx / wy / wz
+ * (and tx / ty / tz), laid out as the mode-0 outputs.
+ *   lsq: loss[npulse] receives L per pulse, g_re / g_im (laid out as b1) the gradient J' W (m - t) = dL/dRe b1 + i dL/dIm b1.
+ *   gn:  ndir >= 1 directions per pulse in v_re / v_im, laid out as mbfir_bloch_jvp_batch lays them out; h_re / h_im receive the
+ *        Gauss-Newton products sum_s s J_s' W_s J_s (s v), pulse p from ndir toff[p], direction-major.
+ * Each is one upload, one sweep launch (one workgroup per forward workgroup, and for gn per direction: mbfir_bloch_vjp_batch's two
+ * sweeps with the cotangent w (m - t), or w dm of a tangent carried through the forward sweep, formed at the point) plus a fold,
+ * and one download of the n (ndir n) complex results per pulse and the losses: nothing of point size comes back; the partials and
+ * the checkpoints stay on the device.  No atomics: a pulse's g, L and H v bits depend only on the pulse, its grids, its weights,
+ * target or direction, m0 and the scale list, not on the batch, its order or ndir.  A point of weight 0 contributes exact zeros,
+ * and so does scale 0 to g and H v.  dL/dm0 and m0 directions are not part of these calls.  The argument checks and their
+ * MBFIR_E_ARG messages are those of mbfir_bloch_batch, then in this order, each with its reason in mbfir_last_error: a weight,
+ * target, direction or output plane NULL; m0x / m0y / m0z only partly given; a negative or non-finite weight; ndir < 1; partials,
+ * checkpoints or a workgroup count that overflow.  No device work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
+                          const double* wz, const double* tx, const double* ty, const double* tz, double* loss, double* g_re,
+                          double* g_im);
+int mbfir_bloch_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                         const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                         const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                         const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                         const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
+                         const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
 /* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
  * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
  * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the

@@ -140,6 +140,10 @@ SYMBOLS = {
     "mbfir_bloch_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 3 + [C.c_int] + [_dp] * 11),
     "mbfir_test_bloch_jvp_group": (C.c_int, []),
+    "mbfir_bloch_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
+                                        C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
+    "mbfir_bloch_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
+                                       C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 6 + [C.c_int] + [_dp] * 4),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -1479,6 +1483,80 @@ def bloch_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), m0=None, tangent
     return res
 
 
+def _bloch_planes(who, what, triples, A, weights=False):
+    """triples: per pulse (x, y, z), each of shape (S, nf, npos), or (nf, npos) for every scale, or a scalar -> the three
+    concatenated planes of the C call in the layout of bloch_batch's mode-0 outputs"""
+    triples = list(triples)
+    if len(triples) != A.P:
+        raise ValueError("%s: %d %s triples for %d pulses" % (who, len(triples), what, A.P))
+    planes = [[], [], []]
+    for q, tri in enumerate(triples):
+        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+            raise ValueError("%s: the %ss of pulse %d must be a triple (x, y, z)" % (who, what, q))
+        shape = (A.S, A.nf[q], A.npos[q])
+        for c in range(3):
+            v = np.asarray(tri[c], dtype=np.float64)
+            if v.shape != shape and v.shape != shape[1:] and v.shape != ():
+                raise ValueError("%s: a %s of pulse %d has shape %s, not %s, %s or a scalar" % (who, what, q, v.shape, shape, shape[1:]))
+            if weights and (not np.all(np.isfinite(v)) or np.any(v < 0)):
+                raise ValueError("%s: a weight of pulse %d is negative or not finite" % (who, q))
+            planes[c].append(np.broadcast_to(v, shape).ravel())
+    return [_vec(np.concatenate(p)) for p in planes]
+
+
+def _bloch_m0(A, m0):
+    """The m0 of the least-squares calls: three NULLs, or the planes of the mode-0 layout (arrays: the caller keeps them alive)"""
+    if m0 is None:
+        return [C.cast(None, _dp)] * 3
+    return A.m0_planes(m0, _offsets([A.S * f * k for f, k in zip(A.nf, A.npos)]), [1] * A.P)
+
+
+def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):
+    """Loss and gradient of a weighted least-squares fit of bloch_batch's end point (mode 0), relaxation included, in one device
+    call (mbfir_bloch_lsq_batch): pulses, df, dp, scales and m0 as for bloch_batch.  targets and weights: per
+    pulse a triple (x, y, z) for (mx, my, mz), each entry of the shape (S, nf, npos) that bloch_batch returns, or (nf, npos) for
+    every scale, or a scalar (weights >= 0).  Returns a list of (L, grad) per pulse: L = 1/2 sum w_c (m_c - t_c)^2 over the three
+    components, the points and the scales, and grad = dL/dRe b1 + i dL/dIm b1, complex (ntime,).  Nothing of point size comes back
+    from the device.  Deterministic: a pulse's L and grad bits depend only on the pulse, its grids, targets, weights, m0 and the
+    scales.  gr, tp, t1, t2, df, dp and m0 are not differentiated."""
+    who = "bloch_lsq_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    t = _bloch_planes(who, "target", targets, A)
+    T = sum(A.nt)
+    loss, grad = np.zeros(A.P), [np.zeros(T) for _ in range(2)]
+    m0p = _bloch_m0(A, m0)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_lsq_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + t], _ptr(loss),
+                                              _ptr(grad[0]), _ptr(grad[1]))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _lsq_result([range(n) for n in A.nt], loss, grad)
+
+
+def bloch_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), m0=None, ctx=None):
+    """Gauss-Newton products of the fit of bloch_lsq_batch, in one device call (mbfir_bloch_gn_batch): H v = sum_s s J_s' W_s J_s
+    (s v) for J = dm / db1 (real-linear in v) and W the weights; arguments as for bloch_lsq_batch, with tangents as bloch_jvp_batch
+    takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every pulse.  Returns per pulse a
+    complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real inner product Re sum conj(u) v.  A product's
+    bits depend only on its pulse, grids, weights, direction, m0 and the scales: not on the batch or the direction's place among K."""
+    who = "bloch_gn_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    rfs = [range(n) for n in A.nt]
+    K, keep, vplanes = _tangents(who, tangents, rfs)
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
+    m0p = _bloch_m0(A, m0)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_gn_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w], K,
+                                             *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _gn_result(rfs, K, keep, h)
+
+
 def _rf_g(pulse, q, who, gtype):
     """A pulse of abr_batch / abr2_batch, rf or (rf, g) -> rf and g of dtype gtype, abrm's 2 pi / n per sample where it has none."""
     rf, g = pulse if isinstance(pulse, tuple) else (pulse, None)
@@ -1968,7 +2046,7 @@ def abr2_lm_step_batch(pulses, x, y, rhs, weights, mu, *, targets=None, cg=8, rt
     return _lm_result(rfs, out)
 
 
-from .refine import refine_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
+from .refine import refine_batch, refine_bloch_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

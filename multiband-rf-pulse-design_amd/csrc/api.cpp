@@ -1337,6 +1337,82 @@ int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                                        v_im, dm0x, dm0y, dm0z, mx, my, mz, dmx, dmy, dmz));
 }
 
+// What the Bloch least-squares calls check after bloch_batch_check, in this order: their own planes (what: the message of a null
+// one), m0, the 3 O weights (O: the forward call's output entries), ndir, and that ndir times the T b1 samples, the partials (one per
+// workgroup and sample, per direction) and the checkpoints (at most 2^56 entries each) and the workgroups of the sweep and of the
+// fold (at most 2^31 - 1 each) fit.  0, or MBFIR_E_ARG with ctx->err set.
+static int bloch_gn_check(mbfir_ctx* ctx, const char* who, bool planes, const char* what, const double* m0x, const double* m0y,
+                          const double* m0z, int npulse, int nscale, const double* wx, const double* wy, const double* wz, int ndir,
+                          const long* toff, const long* npoint) {
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (!planes) return bad(what);
+    if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    long O = 0, nblk = 0, nfold = 0;                           // bloch_batch_check has bounded O and nblk
+    for (int p = 0; p < npulse; ++p) {
+        O += npoint[p] * nscale;
+        nblk += (npoint[p] + 255) / 256 * nscale;
+        nfold += (toff[p + 1] - toff[p] + 255) / 256;
+    }
+    for (const double* w : {wx, wy, wz})
+        for (long i = 0; i < O; ++i)
+            if (!(w[i] >= 0) || !std::isfinite(w[i])) return bad("a weight is negative or not finite");
+    if (ndir < 1) return bad("ndir must be at least 1");
+    if (!vjp_partials_fit(npulse, nscale, toff, npoint) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint))
+        return bad("the output size or the workgroup count overflows");
+    long part = 0, cks = 0;                                    // one direction's partials and checkpoints: bounded just above
+    for (int p = 0; p < npulse; ++p) {
+        part += (npoint[p] + 255) / 256 * nscale * (toff[p + 1] - toff[p]);
+        cks += (npoint[p] + 255) / 256 * nscale * ((toff[p + 1] - toff[p] + 7) / 8 * 768);
+    }
+    if (toff[npulse] > (1L << 56) / ndir || part > (1L << 56) / ndir || cks > (1L << 56) / ndir || nblk > 2147483647L / ndir ||
+        nfold > 2147483647L / ndir)
+        return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_bloch_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                          const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
+                          const double* wz, const double* tx, const double* ty, const double* tz, double* loss, double* g_re,
+                          double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, "bloch_lsq_batch", wx && wy && wz && tx && ty && tz && loss && g_re && g_im,
+                                     "a weight, target, loss or gradient plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, 1,
+                                     toff, npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, bloch_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                       gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz, tx,
+                                       ty, tz, loss, g_re, g_im));
+}
+
+int mbfir_bloch_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                         const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                         const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                         const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                         const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
+                         const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, "bloch_gn_batch", wx && wy && wz && v_re && v_im && h_re && h_im,
+                                     "a weight, direction or product plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, ndir,
+                                     toff, npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, bloch_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                      gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz,
+                                      ndir, v_re, v_im, h_re, h_im));
+}
+
 // What the least-squares calls check after abr_batch_check, in this order: their own arrays, the profile, the O weights (O: the
 // forward call's output entries), ndir, and that ndir times the R rf samples, the partials (one per workgroup and sample, per
 // direction; at most 2^56 entries each) and the workgroups of the sweep and of the fold (at most 2^31 - 1 each) fit.  0, or

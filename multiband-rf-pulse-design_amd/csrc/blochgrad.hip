@@ -8,6 +8,7 @@
 // The step is a contraction: undoing it would divide by e1 and e2 and amplify rounding by exp(T / T2), so m_{t-1} is never
 // recovered from m_t.  The forward sweep writes m to a scratch array before every VJP_T-th sample; the reverse sweep, per group of
 // VJP_T samples, steps the group's states forwards again from its checkpoint into registers and then walks the group backwards.
+// The steps (bloch_fwd_step, bloch_vjp_step) and the checkpoints' descriptor are in sim_dev.h, shared with blochgn.hip.
 // k_bloch_vjp_batch: one 256-thread workgroup per (pulse, scale, chunk of 256 points) from the forward call's block table, one
 // thread per point, the sample rows staged through LDS as k_bloch_batch stages them.  The 256 contributions to a sample are summed
 // in a fixed order through the VJP_T x VJP_ROW tile of the rf adjoints (simgrad.hip) into one partial per (workgroup, sample);
@@ -20,62 +21,6 @@
 #include <cmath>
 
 namespace mbfir {
-
-// One forward sample for one point, k_bloch_batch's arithmetic: s = the sample's LDS row, (px, py, pz, dfv) = the point.
-__device__ __forceinline__ double bloch_rotz(const double* s, double px, double py, double pz, double dfv) {
-    return -((s[2] * px + s[3] * py + s[4] * pz) + dfv * s[5]);
-}
-__device__ __forceinline__ void bloch_fwd_step(const double* s, double rotz, double m[3]) {
-    Rot3 R;
-    bloch_rotmat(s[0], s[1], rotz, R);
-    const double e1 = s[6], e2 = s[7];
-    double o[3];
-    rot_vec(R, m, o);
-    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
-}
-
-// One sample backwards for one point: mp = m_{t-1}, l = lambda_t -> lambda_{t-1}; returns (dL / d rotx, dL / d roty) of the sample.
-// R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) = (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi.
-// With T = (D l) mp' and G_k = sum_ij T_ij dR_ij / dk for k = ar, ai, br, bi, and d ar / dp = -(sp / 2) p, d sp / dp = D p
-// (half_sinc, sim_dev.h: the series below phi = 1e-4, the limits 1/2 and -1/24 at phi = 0):
-//     dL / d nx = nx C - sp G_bi,  dL / d ny = ny C + sp G_br,  C = -(sp / 2) G_ar + D (-nz G_ai + ny G_br - nx G_bi)
-// At phi = 0 this is the generator: (ar, ai, br, bi) = (1, 0, 0, 0), and the rotation below is the identity, as the forward step's.
-__device__ __forceinline__ double2 bloch_vjp_step(const double* s, double nz, const double mp[3], double l[3]) {
-    const double nx = s[0], ny = s[1], e1 = s[6], e2 = s[7];
-    const double phi = sqrt(nx * nx + ny * ny + nz * nz);
-    double sn, cp, sp, D;
-    sincos(0.5 * phi, &sn, &cp);
-    half_sinc(phi, sn, cp, sp, D);
-    const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
-    const double d0 = e2 * l[0], d1 = e2 * l[1], d2 = e1 * l[2];
-    const double T00 = d0 * mp[0], T01 = d0 * mp[1], T02 = d0 * mp[2];
-    const double T10 = d1 * mp[0], T11 = d1 * mp[1], T12 = d1 * mp[2];
-    const double T20 = d2 * mp[0], T21 = d2 * mp[1], T22 = d2 * mp[2];
-    const double a01 = T01 - T10, a02 = T02 - T20, a12 = T12 - T21;          // antisymmetric and symmetric parts
-    const double s01 = T01 + T10, s02 = T02 + T20, s12 = T12 + T21;
-    const double Gar = 2 * (ar * (T00 + T11 + T22) + ai * a01 + br * a02 + bi * a12);
-    const double Gai = 2 * (ai * (T22 - T00 - T11) + ar * a01 + bi * s02 - br * s12);
-    const double Gbr = 2 * (br * (T11 - T00 - T22) - bi * s01 + ar * a02 - ai * s12);
-    const double Gbi = 2 * (bi * (T00 - T11 - T22) - br * s01 + ai * s02 + ar * a12);
-    const double C = -0.5 * sp * Gar + D * (ny * Gbr - nz * Gai - nx * Gbi);
-    const double2 g = make_double2(nx * C - sp * Gbi, ny * C + sp * Gbr);
-    // lambda_{t-1} = R' (D l): R' is R's transpose, entry (i, j) of R at m[i + 3 j] in bloch_rotmat
-    const double r00 = ar * ar - ai * ai - br * br + bi * bi, r10 = -2 * ar * ai - 2 * br * bi, r20 = -2 * ar * br + 2 * ai * bi;
-    const double r01 = 2 * ar * ai - 2 * br * bi, r11 = ar * ar - ai * ai + br * br - bi * bi, r21 = -2 * ai * br - 2 * ar * bi;
-    const double r02 = 2 * ar * br + 2 * ai * bi, r12 = 2 * ar * bi - 2 * ai * br, r22 = ar * ar + ai * ai - br * br - bi * bi;
-    l[0] = r00 * d0 + r10 * d1 + r20 * d2;
-    l[1] = r01 * d0 + r11 * d1 + r21 * d2;
-    l[2] = r02 * d0 + r12 * d1 + r22 * d2;
-    return g;
-}
-
-// Per-pulse descriptor of the checkpoints: workgroup (scale, chunk) of the pulse owns ng = ceil(n / VJP_T) groups of 3 x 256
-// doubles from c_off + (scale nch + chunk) ng 768, component c of group k of thread tid at (3 k + c) 256 + tid.
-struct BlochCkDev {
-    long c_off;
-    int ng, pad;
-};
-constexpr int BLOCH_CK = 3 * 256;
 
 // Cotangents cx / cy / cz lie where k_bloch_batch writes mx / my / mz in mode 0: S x nf x npos per pulse, scale-major; gx / gy / gz
 // (dL / d m0) the same.  part: one double2 (sum of dL / d rotx, sum of dL / d roty) per (workgroup, sample), VjpPulseDev's layout.

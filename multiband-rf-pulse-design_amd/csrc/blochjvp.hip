@@ -5,7 +5,7 @@
 //     dnx = ((-(Re v_t s)) gamma) dt_t,   dny = ((Im v_t s) gamma) dt_t          (formed as rotx / roty are formed from b1)
 // one forward sweep, no reduction over points; c_t has no tangent.  k_bloch_jvp_batch: one 256-thread workgroup per (pulse, scale,
 // chunk of 256 points, group of BJVP_K directions): the forward kernel's block table times the direction groups, one thread per
-// point.  The BJVP_K tangents of a thread share the sample's sincos, sp, D, the rotation and the three vectors U, Vx, Vy below.
+// point.  The BJVP_K tangents of a thread share the sample's sincos, sp, D, the rotation and the three vectors U, Vx, Vy (bloch_jvp_shared, sim_dev.h).
 // The primal state advances through bloch_rotmat's body (bloch_rotmat_trig, which also hands out the sample's trigonometry) and
 // rot_vec as in k_bloch_batch: the (mx, my, mz) written here (by the workgroups of group 0) have k_bloch_batch's bits.  Every
 // direction runs the same instructions on its own registers, so a tangent's bits depend only on its pulse, scale, point and
@@ -22,36 +22,6 @@ namespace mbfir {
 #ifndef BJVP_K
 #define BJVP_K 8
 #endif
-
-// What the directions of one point share at one sample.  R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) =
-// (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi, and along dn = (dnx, dny, 0), with d sp = D (n.dn) (half_sinc),
-//     d ar = -(sp/2)(n.dn),  d ai = -nz D (n.dn),  d br = ny D (n.dn) + sp dny,  d bi = -nx D (n.dn) - sp dnx
-// so that dR[dn] m = (n.dn) U + dnx Vx + dny Vy: U is the derivative of the quadratic form along (-(sp/2), -nz D, ny D, -nx D)
-// applied to m, Vx the one along d bi = -sp, Vy the one along d br = sp.  At phi = 0 (ar, ai, br, bi) = (1, 0, 0, 0), sp = 1/2:
-// Vx = (0, -mz, my), Vy = (mz, 0, -mx), the generators, and n.dn = 0.
-struct BlochJvpShared {
-    double U[3], Vx[3], Vy[3];
-};
-__device__ __forceinline__ void bloch_jvp_shared(double nx, double ny, double nz, const BlochTrig& t, const double m[3],
-                                                 BlochJvpShared& W) {
-    double sp, D;
-    half_sinc(t.phi, t.sn, t.cp, sp, D);
-    const double ar = t.cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
-    const double dar = -0.5 * sp, dai = -nz * D, dbr = ny * D, dbi = -nx * D;
-    const double p0 = ar * dar, p1 = ai * dai, p2 = br * dbr, p3 = bi * dbi;
-    const double aai = dar * ai + ar * dai, bb = dbr * bi + br * dbi, abr = dar * br + ar * dbr, abi = dar * bi + ar * dbi;
-    const double ib = dai * bi + ai * dbi, ir = dai * br + ai * dbr;
-    W.U[0] = 2 * ((p0 - p1 - p2 + p3) * m[0] + (aai - bb) * m[1] + (abr + ib) * m[2]);
-    W.U[1] = 2 * ((-aai - bb) * m[0] + (p0 - p1 + p2 - p3) * m[1] + (abi - ir) * m[2]);
-    W.U[2] = 2 * ((ib - abr) * m[0] + (-ir - abi) * m[1] + (p0 + p1 - p2 - p3) * m[2]);
-    const double f = 2 * sp;
-    W.Vx[0] = -f * (bi * m[0] - br * m[1] + ai * m[2]);
-    W.Vx[1] = -f * (ar * m[2] - br * m[0] - bi * m[1]);
-    W.Vx[2] = -f * (ai * m[0] - ar * m[1] - bi * m[2]);
-    W.Vy[0] = f * (ar * m[2] - br * m[0] - bi * m[1]);
-    W.Vy[1] = f * (br * m[1] - bi * m[0] - ai * m[2]);
-    W.Vy[2] = -f * (ar * m[0] + ai * m[1] + br * m[2]);
-}
 
 // in, df, pos3, scales, pulses, m0: k_bloch_batch's.  blocks: SimBlock with pad = the direction group.  v (interleaved): direction k
 // of pulse p at ndir t_off + k ntime.  dm0 (three planes of ndir O entries from dm0, null: zero) and dmx / dmy / dmz: pulse p from

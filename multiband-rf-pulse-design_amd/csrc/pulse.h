@@ -124,6 +124,25 @@ void abr2_gn_batch_run(int device, void* stream, int npulse, const long* roff, c
                        const double* gx, const double* gy, int nxgrid, const long* xoff, const double* x, int nygrid,
                        const long* yoff, const double* y, int nscale, const double* scales, int mode, int profile, const double* w,
                        int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
+// Least-squares products of bloch_batch_run's end point (mode 0; blochgn.hip k_bloch_lsq_batch, k_bloch_gn_batch, k_bloch_gn_fold): the
+// forward call's inputs, m0 as bloch_vjp_batch_run takes it, the weights (wx, wy, wz) and the targets (tx, ty, tz) or the ndir
+// directions (as bloch_jvp_batch_run takes them) in the forward outputs' layout.  lsq: loss per pulse and the gradient per b1
+// sample; gn: sum_s s J_s' W_s J_s (s v), pulse p from ndir toff[p], direction-major.  One upload, two launches, one download of
+// b1 size; the partials and the checkpoints stay on the device.
+void bloch_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                         const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                         const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                         int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                         const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
+                         const double* wy, const double* wz, const double* tx, const double* ty, const double* tz, double* loss,
+                         double* g_re, double* g_im);
+void bloch_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                        const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                        const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                        int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                        const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
+                        const double* wy, const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re,
+                        double* h_im);
 // The Levenberg-Marquardt step on the device (simgn.hip): CG on (H + mu I) d = b per pulse and, with t_re, the loss and gradient at
 // rf + d (loss, g_re, g_im may be null without one).
 void abr_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,

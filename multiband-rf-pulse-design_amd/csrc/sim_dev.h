@@ -424,6 +424,94 @@ struct BlochPulseDev {
     double gamma;
 };
 
+// What the adjoint (blochgrad.hip), the tangent (blochjvp.hip) and the least-squares products (blochgn.hip) share, moved here from
+// blochgrad.hip and blochjvp.hip token for token.
+// One forward sample for one point, k_bloch_batch's arithmetic: s = the sample's LDS row, (px, py, pz, dfv) = the point.
+__device__ __forceinline__ double bloch_rotz(const double* s, double px, double py, double pz, double dfv) {
+    return -((s[2] * px + s[3] * py + s[4] * pz) + dfv * s[5]);
+}
+__device__ __forceinline__ void bloch_fwd_step(const double* s, double rotz, double m[3]) {
+    Rot3 R;
+    bloch_rotmat(s[0], s[1], rotz, R);
+    const double e1 = s[6], e2 = s[7];
+    double o[3];
+    rot_vec(R, m, o);
+    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
+}
+
+// One sample backwards for one point: mp = m_{t-1}, l = lambda_t -> lambda_{t-1}; returns (dL / d rotx, dL / d roty) of the sample.
+// R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) = (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi.
+// With T = (D l) mp' and G_k = sum_ij T_ij dR_ij / dk for k = ar, ai, br, bi, and d ar / dp = -(sp / 2) p, d sp / dp = D p
+// (half_sinc, sim_dev.h: the series below phi = 1e-4, the limits 1/2 and -1/24 at phi = 0):
+//     dL / d nx = nx C - sp G_bi,  dL / d ny = ny C + sp G_br,  C = -(sp / 2) G_ar + D (-nz G_ai + ny G_br - nx G_bi)
+// At phi = 0 this is the generator: (ar, ai, br, bi) = (1, 0, 0, 0), and the rotation below is the identity, as the forward step's.
+__device__ __forceinline__ double2 bloch_vjp_step(const double* s, double nz, const double mp[3], double l[3]) {
+    const double nx = s[0], ny = s[1], e1 = s[6], e2 = s[7];
+    const double phi = sqrt(nx * nx + ny * ny + nz * nz);
+    double sn, cp, sp, D;
+    sincos(0.5 * phi, &sn, &cp);
+    half_sinc(phi, sn, cp, sp, D);
+    const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
+    const double d0 = e2 * l[0], d1 = e2 * l[1], d2 = e1 * l[2];
+    const double T00 = d0 * mp[0], T01 = d0 * mp[1], T02 = d0 * mp[2];
+    const double T10 = d1 * mp[0], T11 = d1 * mp[1], T12 = d1 * mp[2];
+    const double T20 = d2 * mp[0], T21 = d2 * mp[1], T22 = d2 * mp[2];
+    const double a01 = T01 - T10, a02 = T02 - T20, a12 = T12 - T21;          // antisymmetric and symmetric parts
+    const double s01 = T01 + T10, s02 = T02 + T20, s12 = T12 + T21;
+    const double Gar = 2 * (ar * (T00 + T11 + T22) + ai * a01 + br * a02 + bi * a12);
+    const double Gai = 2 * (ai * (T22 - T00 - T11) + ar * a01 + bi * s02 - br * s12);
+    const double Gbr = 2 * (br * (T11 - T00 - T22) - bi * s01 + ar * a02 - ai * s12);
+    const double Gbi = 2 * (bi * (T00 - T11 - T22) - br * s01 + ai * s02 + ar * a12);
+    const double C = -0.5 * sp * Gar + D * (ny * Gbr - nz * Gai - nx * Gbi);
+    const double2 g = make_double2(nx * C - sp * Gbi, ny * C + sp * Gbr);
+    // lambda_{t-1} = R' (D l): R' is R's transpose, entry (i, j) of R at m[i + 3 j] in bloch_rotmat
+    const double r00 = ar * ar - ai * ai - br * br + bi * bi, r10 = -2 * ar * ai - 2 * br * bi, r20 = -2 * ar * br + 2 * ai * bi;
+    const double r01 = 2 * ar * ai - 2 * br * bi, r11 = ar * ar - ai * ai + br * br - bi * bi, r21 = -2 * ai * br - 2 * ar * bi;
+    const double r02 = 2 * ar * br + 2 * ai * bi, r12 = 2 * ar * bi - 2 * ai * br, r22 = ar * ar + ai * ai - br * br - bi * bi;
+    l[0] = r00 * d0 + r10 * d1 + r20 * d2;
+    l[1] = r01 * d0 + r11 * d1 + r21 * d2;
+    l[2] = r02 * d0 + r12 * d1 + r22 * d2;
+    return g;
+}
+
+// Per-pulse descriptor of the checkpoints: workgroup (scale, chunk) of the pulse owns ng = ceil(n / VJP_T) groups of 3 x 256
+// doubles from c_off + (scale nch + chunk) ng 768, component c of group k of thread tid at (3 k + c) 256 + tid.
+struct BlochCkDev {
+    long c_off;
+    int ng, pad;
+};
+constexpr int BLOCH_CK = 3 * 256;
+
+// What the directions of one point share at one sample.  R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) =
+// (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi, and along dn = (dnx, dny, 0), with d sp = D (n.dn) (half_sinc),
+//     d ar = -(sp/2)(n.dn),  d ai = -nz D (n.dn),  d br = ny D (n.dn) + sp dny,  d bi = -nx D (n.dn) - sp dnx
+// so that dR[dn] m = (n.dn) U + dnx Vx + dny Vy: U is the derivative of the quadratic form along (-(sp/2), -nz D, ny D, -nx D)
+// applied to m, Vx the one along d bi = -sp, Vy the one along d br = sp.  At phi = 0 (ar, ai, br, bi) = (1, 0, 0, 0), sp = 1/2:
+// Vx = (0, -mz, my), Vy = (mz, 0, -mx), the generators, and n.dn = 0.
+struct BlochJvpShared {
+    double U[3], Vx[3], Vy[3];
+};
+__device__ __forceinline__ void bloch_jvp_shared(double nx, double ny, double nz, const BlochTrig& t, const double m[3],
+                                                 BlochJvpShared& W) {
+    double sp, D;
+    half_sinc(t.phi, t.sn, t.cp, sp, D);
+    const double ar = t.cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
+    const double dar = -0.5 * sp, dai = -nz * D, dbr = ny * D, dbi = -nx * D;
+    const double p0 = ar * dar, p1 = ai * dai, p2 = br * dbr, p3 = bi * dbi;
+    const double aai = dar * ai + ar * dai, bb = dbr * bi + br * dbi, abr = dar * br + ar * dbr, abi = dar * bi + ar * dbi;
+    const double ib = dai * bi + ai * dbi, ir = dai * br + ai * dbr;
+    W.U[0] = 2 * ((p0 - p1 - p2 + p3) * m[0] + (aai - bb) * m[1] + (abr + ib) * m[2]);
+    W.U[1] = 2 * ((-aai - bb) * m[0] + (p0 - p1 + p2 - p3) * m[1] + (abi - ir) * m[2]);
+    W.U[2] = 2 * ((ib - abr) * m[0] + (-ir - abi) * m[1] + (p0 + p1 - p2 - p3) * m[2]);
+    const double f = 2 * sp;
+    W.Vx[0] = -f * (bi * m[0] - br * m[1] + ai * m[2]);
+    W.Vx[1] = -f * (ar * m[2] - br * m[0] - bi * m[1]);
+    W.Vx[2] = -f * (ai * m[0] - ar * m[1] - bi * m[2]);
+    W.Vy[0] = f * (ar * m[2] - br * m[0] - bi * m[1]);
+    W.Vy[1] = f * (br * m[1] - bi * m[0] - ai * m[2]);
+    W.Vy[2] = -f * (ar * m[0] + ai * m[1] + br * m[2]);
+}
+
 // The inputs of one mbfir_bloch_batch call, staged and filled (slr.hip): the sample rows, the grids, the initial magnetisation
 // and Staging's tables.  The forward call uploads this as it is; the adjoint adds its own sections first.  m0x / m0y / m0z: the
 // initial magnetisation at the first entry of every (scale, frequency, position) block of the outputs' layout under `mode` (all

@@ -5,6 +5,7 @@ L = 1/2 sum w |f - t|^2, g = J^H W (f - t) and H = J^H W J (abr_lsq_batch / abr_
     the pulses whose CG is still running (one direction each), and tries rf + d with one lsq call, which also returns the gradient
     of the next step;  mu <- mu / 3 after a step that lowers L, mu <- 4 mu after one that does not (the step is then solved again);
     the first mu is 1e-3 times the Rayleigh quotient <g, H g> / <g, g>.
+refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch / bloch_gn_batch, the Bloch model with relaxation.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -74,7 +75,7 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
             infos[q]["calls"]["gn"] += 1
         return fn(pack(idx, rfs), *pos, [v_of[q] for q in idx], [weights[q] for q in idx], **kw)
 
-    def lm(idx):
+    def lm(idx, grad, mu):
         """the step of every active pulse, solved and tried on the device: (rf + d, L and g there, whether CG broke down)"""
         pos = (grid(x, idx), grid(y, idx)) if two else (grid(x, idx),)
         fn = mb.abr2_lm_step_batch if two else mb.abr_lm_step_batch
@@ -84,30 +85,46 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
                  targets=[targets[q] for q in idx], cg=cg, rtol=rtol, **kw)
         return [(rfs[q] + d, i["loss"], i["grad"], i["status"] == "breakdown") for q, (d, i) in zip(idx, res)]
 
-    def host_steps(idx):
-        """the same on the host: CG on (H + mu I) d = -g from d = 0, one gn call per iteration, then one lsq call"""
-        d = {q: np.zeros_like(rfs[q]) for q in idx}
-        r = {q: -grad[q] for q in idx}
-        p = {q: r[q].copy() for q in idx}
-        rr = {q: _dot(r[q], r[q]) for q in idx}
-        gg = dict(rr)
-        ncg = {q: 0 for q in idx}
-        while True:
-            run = [q for q in idx if ncg[q] < cg and rr[q] > rtol * gg[q]]
-            if not run:
-                break
-            for q, hp in zip(run, gn(run, p)):
-                ap = hp + mu[q] * p[q]
-                alpha = rr[q] / _dot(p[q], ap)
-                d[q], r[q] = d[q] + alpha * p[q], r[q] - alpha * ap
-                rr[q], old = _dot(r[q], r[q]), rr[q]
-                p[q] = r[q] + (rr[q] / old) * p[q]
-                ncg[q] += 1
-        trial = {q: rfs[q] + d[q] for q in idx}
-        return [(trial[q], L, g, False) for q, (L, g) in zip(idx, lsq(idx, trial))]
-
     calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
     infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
+    if solver == "device":
+        step = lm
+    else:
+        def step(idx, grad, mu):
+            return _host_steps(idx, rfs, grad, mu, lsq, gn, cg, rtol)
+    return _lm_loop(rfs, infos, lsq, gn, step, iters, mu0)
+
+
+def _host_steps(idx, rfs, grad, mu, lsq, gn, cg, rtol):
+    """The step of every pulse of idx on the host: CG on (H + mu I) d = -g from d = 0, one gn call per iteration over the pulses
+    whose CG still runs, then one lsq call at rf + d -> [(rf + d, L and g there, False)]"""
+    d = {q: np.zeros_like(rfs[q]) for q in idx}
+    r = {q: -grad[q] for q in idx}
+    p = {q: r[q].copy() for q in idx}
+    rr = {q: _dot(r[q], r[q]) for q in idx}
+    gg = dict(rr)
+    ncg = {q: 0 for q in idx}
+    while True:
+        run = [q for q in idx if ncg[q] < cg and rr[q] > rtol * gg[q]]
+        if not run:
+            break
+        for q, hp in zip(run, gn(run, p)):
+            ap = hp + mu[q] * p[q]
+            alpha = rr[q] / _dot(p[q], ap)
+            d[q], r[q] = d[q] + alpha * p[q], r[q] - alpha * ap
+            rr[q], old = _dot(r[q], r[q]), rr[q]
+            p[q] = r[q] + (rr[q] / old) * p[q]
+            ncg[q] += 1
+    trial = {q: rfs[q] + d[q] for q in idx}
+    return [(trial[q], L, g, False) for q, (L, g) in zip(idx, lsq(idx, trial))]
+
+
+def _lm_loop(rfs, infos, lsq, gn, step, iters, mu0):
+    """The lock-step Levenberg-Marquardt loop of refine_batch and refine_bloch_batch, from the first loss to the end.  rfs: the
+    pulses' samples, replaced in place by the accepted trials; lsq(idx, rf_of) -> [(L, g)] and gn(idx, v_of) -> [H v] for the
+    pulses idx (gn at the current rfs); step(idx, grad, mu) -> [(trial, L and g at the trial, whether the solve broke down)].
+    Returns (rfs, infos)."""
+    P = len(rfs)
     every = list(range(P))
     loss, grad, done = [0.0] * P, [None] * P, [0] * P
     for q, (L, g) in zip(every, lsq(every, rfs)):
@@ -131,7 +148,7 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
             mu[q] = 1e-3 * _dot(grad[q], hg) / _dot(grad[q], grad[q])       # a Rayleigh quotient of H sets the scale of mu
     while active:
         still = []
-        for q, (trial, L, g, broke) in zip(active, lm(active) if solver == "device" else host_steps(active)):
+        for q, (trial, L, g, broke) in zip(active, step(active, grad, mu)):
             if L < loss[q] and not broke:
                 rfs[q], loss[q], grad[q], mu[q] = trial, L, g, mu[q] / 3
                 infos[q]["losses"].append(L)
@@ -151,3 +168,49 @@ def refine_batch(pulses, x, *args, profile="ex", scales=(1.0,), hard_pulse=False
     for q in every:
         infos[q]["mu"] = mu[q]
     return rfs, infos
+
+
+def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, iters=5, cg=8, mu0=None, rtol=1e-6, ctx=None):
+    """refine_batch(solver='host') for bloch_batch's model, relaxation included: the same lock-step Levenberg-Marquardt
+    / CG loop on bloch_lsq_batch and bloch_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, of which only b1 changes; df, dp:
+    one grid shared by every pulse or a list of one per pulse; targets, weights, scales and m0 (None, one (mx, my, mz), or a list
+    of one per pulse) as for bloch_lsq_batch; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch
+    does.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    mb = importlib.import_module(__package__)
+    pulses = list(pulses)
+    P = len(pulses)
+    if P == 0:
+        raise ValueError("refine_bloch_batch: no pulses")
+    targets, weights = list(targets), list(weights)
+    if len(targets) != P or len(weights) != P:
+        raise ValueError("refine_bloch_batch: %d target and %d weight triples for %d pulses" % (len(targets), len(weights), P))
+    if iters < 0 or cg < 1:
+        raise ValueError("refine_bloch_batch: iters must be at least 0 and cg at least 1")
+    rest = [tuple(p[1:]) for p in pulses]
+    b1s = [np.array(p[0], dtype=np.complex128).ravel() for p in pulses]
+    each = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
+
+    def grid(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P and all(np.ndim(e) >= 1 for e in v) else v
+
+    def args(idx, b1_of):
+        return [(b1_of[q],) + rest[q] for q in idx], grid(df, idx), grid(dp, idx)
+
+    def kw(idx):
+        return dict(scales=scales, m0=[m0[q] for q in idx] if each else m0, ctx=ctx)
+
+    def lsq(idx, b1_of):
+        for q in idx:
+            infos[q]["calls"]["lsq"] += 1
+        return mb.bloch_lsq_batch(*args(idx, b1_of), [targets[q] for q in idx], [weights[q] for q in idx], **kw(idx))
+
+    def gn(idx, v_of):
+        for q in idx:
+            infos[q]["calls"]["gn"] += 1
+        return mb.bloch_gn_batch(*args(idx, b1s), [v_of[q] for q in idx], [weights[q] for q in idx], **kw(idx))
+
+    def step(idx, grad, mu):
+        return _host_steps(idx, b1s, grad, mu, lsq, gn, cg, rtol)
+
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    return _lm_loop(b1s, infos, lsq, gn, step, iters, mu0)
