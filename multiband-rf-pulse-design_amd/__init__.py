@@ -144,6 +144,9 @@ SYMBOLS = {
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                        C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 6 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                            _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 9 + [C.c_int, C.c_double] +
+                                           [_dp] * 5 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -2043,6 +2046,34 @@ def abr2_lm_step_batch(pulses, x, y, rhs, weights, mu, *, targets=None, cg=8, rt
     planes, out = _lm_planes(who, kind, _weight_plane(who, weights, shapes), bplanes, m, cg, rtol, targets, shapes, rfs)
     ctx = ctx or get_context()
     _abr2_call(load_library().mbfir_abr2_lm_step_batch, ctx, sc, rfs, gs, xs, ys, hard_pulse, planes)
+    return _lm_result(rfs, out)
+
+
+def bloch_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), m0=None, ctx=None):
+    """abr_lm_step_batch for bloch_batch's model, relaxation included (mbfir_bloch_lm_step_batch): conjugate
+    gradients on (H + mu I) d = rhs from d = 0, H = sum_s s J_s' W_s J_s (s .) as bloch_gn_batch applies it, solved on the device in
+    one call.  pulses, df, dp, weights, scales and m0 as for bloch_gn_batch; rhs: per pulse a complex (n,) array; mu: a number >= 0
+    or one per pulse; cg and rtol as for abr_lm_step_batch.  With targets (as for bloch_lsq_batch) the loss and gradient at b1 + d
+    come back too, with the bits of bloch_lsq_batch there.  Returns a list of (d, info) per pulse: info holds 'ncg', 'rr', 'gg' and
+    'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.  The host reads nothing between the iterations, so
+    cg is also a launch count.  Deterministic: a pulse's results depend only on the pulse, its grids, weights, targets, m0, rhs, mu,
+    cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    who = "bloch_lm_step_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    rfs = [range(n) for n in A.nt]
+    bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    t = [None] * 3 if targets is None else _bloch_planes(who, "target", targets, A)
+    P, T = A.P, sum(A.nt)
+    out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
+    out += [None, None, None] if targets is None else [np.zeros(P), np.zeros(T), np.zeros(T)]
+    m0p = _bloch_m0(A, m0)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_lm_step_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + bplanes], _ptr(m),
+                                                  cg, C.c_double(rtol), *[_plane(v) for v in t + out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
     return _lm_result(rfs, out)
 
 

@@ -1561,6 +1561,53 @@ int mbfir_abr2_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
                                           profile == 2 ? nullptr : t_im, d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im));
 }
 
+// What the Bloch Levenberg-Marquardt step checks after bloch_batch_check and bloch_gn_check (at ndir = 1), in this order: its own
+// arrays, the targets, mu, cg, rtol, and that its per-sample sections (the five vectors and the trial rows: fewer than sixteen
+// double2 per b1 sample, at most 2^56 entries) and the workgroups of the trial (at most 2^31 - 1) fit.  bloch_gn_check's bounds
+// on the checkpoints (96 doubles per sample) and on the fold's workgroups are the tighter ones today: the last check states what
+// this call's own sections need and does not rely on them.
+static int bloch_lm_check(mbfir_ctx* ctx, const char* who, bool arrays, bool targets_ok, int npulse, const long* toff,
+                          const double* mu, int cg, double rtol) {
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (!arrays) return bad("a required array is null");
+    if (!targets_ok) return bad("tx, ty and tz are given together or not at all");
+    for (int p = 0; p < npulse; ++p)
+        if (!(mu[p] >= 0) || !std::isfinite(mu[p])) return bad("a damping mu is negative or not finite");
+    if (cg < 0) return bad("cg must be at least 0");
+    if (!(rtol >= 0)) return bad("rtol is negative or not a number");
+    if (toff[npulse] > (1L << 56) / 16 || (toff[npulse] + 255) / 256 > 2147483647L)
+        return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_bloch_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                              const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                              const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                              const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                              int nscale, const double* scales, const double* m0x, const double* m0y, const double* m0z,
+                              const double* wx, const double* wy, const double* wz, const double* b_re, const double* b_im,
+                              const double* mu, int cg, double rtol, const double* tx, const double* ty, const double* tz,
+                              double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                              double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, "bloch_lm_step_batch", wx && wy && wz, "a weight, direction or product plane is null", m0x,
+                                     m0y, m0z, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
+        return e;
+    const bool targets = tx || ty || tz;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
+    if (const int e = bloch_lm_check(ctx, "bloch_lm_step_batch", own, !targets || (tx && ty && tz), npulse, toff, mu, cg, rtol))
+        return e;
+    MBFIR_TRY(ctx, bloch_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                           t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx,
+                                           wy, wz, b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
+                                           g_im));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 int mbfir_test_bloch_jvp_group(void) { return bloch_jvp_group(); }
 

@@ -240,11 +240,165 @@ __global__ __launch_bounds__(256) void k_bloch_gn_fold(const double2* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// The Levenberg-Marquardt step on the device, the Bloch twin of simgn.hip's: conjugate gradients on
+// (H + mu I) d = b per pulse, H p by the sweep of k_bloch_gn_batch on the device's own p, everything else of an iteration in
+// k_bloch_lm_step; then, with targets, the loss and gradient at b1 + d by k_bloch_lsq_batch on the trial's input rows.  k_lm_init
+// (simgn.hip) starts it.  Stages depend on each other through launch order alone; LmState, lm_block_sum, lm_redot, lm_axpy and
+// lm_goes_on are sim_dev.h's.
+
+// The sweeps of k_bloch_gn_batch at ndir = 1 for the pulses that still run: the forward call's block table, the direction the
+// device's p (laid out as b1 is).
+__global__ __launch_bounds__(256) void k_bloch_lm_sweep(const double* __restrict__ in, const double* __restrict__ df,
+                                                        const double* __restrict__ pos3, const double* __restrict__ scales,
+                                                        const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                        const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+                                                        const double* __restrict__ m0, const double* __restrict__ w, long O,
+                                                        const double2* __restrict__ v, const LmState* __restrict__ st,
+                                                        double2* __restrict__ part, double* ck) {
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    const BlochPulseDev P = pulses[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    BlochGnPoint G = bloch_gn_point(bk, P, df, pos3, m0);
+    const long wg = (long)bk.scale * V.nch + bk.chunk;
+    double wv[3] = {0, 0, 0};
+    const double tv[3] = {0, 0, 0};
+    if (G.live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
+    bloch_gn_sweeps<true>(in, v + P.t_off, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, G.live, G.m, wv, tv,
+                          part + V.p_off + wg * V.n, ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, nullptr);
+}
+
+// k_lm_step (simgn.hip) with H p of sample t formed as k_bloch_gn_fold forms it: one CG iteration of one pulse per workgroup, after
+// its sweep.  H p = (-(f X), f Y), (X, Y) = abr_vjp_fold_sum of the partials and f = gamma dt_t; ap = H p + mu p (kept in hp),
+// pAp = <p, ap>; a pAp that is not finite or not > 0 stops the pulse with status 2 and nothing else changed; else alpha = rr / pAp,
+// d += alpha p, r -= alpha ap, rr' = <r, r>, p = r + (rr' / rr) p, and the next run flag.  A thread owns the samples tid, tid + 256,
+// ... in every pass, as in k_lm_init.
+__global__ __launch_bounds__(256) void k_bloch_lm_step(const double2* __restrict__ part, const VjpPulseDev* __restrict__ vp,
+                                                       const double* __restrict__ scales, int nscale,
+                                                       const double* __restrict__ in, const BlochPulseDev* __restrict__ pulses,
+                                                       int cg, double rtol, double2* __restrict__ p, double2* __restrict__ d,
+                                                       double2* __restrict__ r, double2* __restrict__ hp,
+                                                       LmState* __restrict__ st) {
+    __shared__ double sw[256];
+    const LmState S = st[blockIdx.x];
+    if (!S.run) return;
+    const VjpPulseDev V = vp[blockIdx.x];
+    const BlochPulseDev P = pulses[blockIdx.x];
+    double s = 0;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const double2 g = abr_vjp_fold_sum(part, V, scales, nscale, m);
+        const double f = P.gamma * in[BLOCH_IN * (P.t_off + m) + 8];
+        const double2 h = make_double2(-(f * g.x), f * g.y), q = p[V.r_off + m], ap = lm_axpy(S.mu, q, h);
+        hp[V.r_off + m] = ap;
+        s += lm_redot(q, ap);
+    }
+    const double pap = lm_block_sum(s, sw);                      // every thread has read S before the sum's barriers
+    if (!(pap > 0) || !isfinite(pap)) {
+        if (threadIdx.x == 0) { st[blockIdx.x].run = 0; st[blockIdx.x].status = 2; }
+        return;
+    }
+    const double alpha = S.rr / pap;
+    s = 0;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const long t = V.r_off + m;
+        const double2 q = p[t], rn = lm_axpy(-alpha, hp[t], r[t]);
+        d[t] = lm_axpy(alpha, q, d[t]);
+        r[t] = rn;
+        s += lm_redot(rn, rn);
+    }
+    const double rr = lm_block_sum(s, sw), beta = rr / S.rr;
+    for (int m = threadIdx.x; m < V.n; m += 256) {
+        const long t = V.r_off + m;
+        p[t] = lm_axpy(beta, p[t], r[t]);
+    }
+    if (threadIdx.x == 0) {
+        const bool run = lm_goes_on(S.ncg + 1, cg, rr, rtol, S.gg);
+        st[blockIdx.x] = LmState{rr, S.gg, S.mu, S.ncg + 1, run ? 1 : 0, rr > rtol * S.gg ? 1 : 0, 0};
+    }
+}
+
+// The trial's input rows, sample by sample, for every pulse (a pulse that never ran has d = 0): entries 0 and 1 are b1 + d, one
+// addition each; entries 2 to 8 are copied.
+__global__ __launch_bounds__(256) void k_bloch_lm_trial(const double* __restrict__ in, const double2* __restrict__ d, long T,
+                                                        double* __restrict__ trial) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= T) return;
+    const double* s = in + BLOCH_IN * t;
+    double* o = trial + BLOCH_IN * t;
+    o[0] = s[0] + d[t].x;
+    o[1] = s[1] + d[t].y;
+    for (int e = 2; e < BLOCH_IN; ++e) o[e] = s[e];
+}
+
+// ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_lsq_batch / mbfir_bloch_gn_batch (arguments checked by api.cpp): the forward call's staging (bloch_stage,
 // mode 0) plus the weights, the targets or the directions, the descriptors and the two tables; one upload, two launches, one
 // download of the ndir T results (and the npulse losses).  The output region is the results (ndir T double2), the losses (padded
 // to a whole double2), then the partials, the loss partials and the checkpoints, which stay on the device.
 namespace {
+// The sections the least-squares calls add to the forward staging, filled (pointers into B.S taken before this are stale), and the
+// sizes of what stays on the device.  tg null: no targets; v_re null: no directions, and the sweep's table is the forward one.
+struct BlochGnSections {
+    size_t o_w = 0, o_t = 0, o_v = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0, o_jb = 0;
+    long npart = 0, nck = 0, nlp = 0, nfold = 0;        // double2 partials, checkpoint doubles, loss partials, workgroups of the fold
+};
+BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int nscale, const double* const w[3],
+                               const double* const tg[3], int ndir, const double* v_re, const double* v_im) {
+    Staging& S = B.S;
+    BlochGnSections G;
+    const long O = B.O, T = toff[npulse];
+    std::vector<VjpPulseDev> vp((size_t)npulse * ndir);
+    std::vector<BlochCkDev> ck((size_t)npulse * ndir);
+    std::vector<long> lp(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        const int n = B.ntime[p], nch = int((B.npair[p] + 255) / 256), ng = (n + VJP_T - 1) / VJP_T;
+        lp[p] = G.nlp;
+        G.nlp += (long)nscale * nch;
+        for (int k = 0; k < ndir; ++k) {
+            vp[(size_t)p * ndir + k] = VjpPulseDev{ndir * toff[p] + (long)k * n, G.npart, n, nch};
+            ck[(size_t)p * ndir + k] = BlochCkDev{G.nck, ng, 0};
+            G.npart += (long)nscale * nch * n;
+            G.nck += (long)nscale * nch * ng * BLOCH_CK;
+        }
+        G.nfold += (long)ndir * ((n + 255) / 256);
+    }
+    G.o_w = S.add((size_t)O * 24);
+    if (tg) G.o_t = S.add((size_t)O * 24);
+    if (v_re) G.o_v = S.add((size_t)ndir * T * 16);
+    G.o_vp = S.add(vp.size() * sizeof(VjpPulseDev));
+    G.o_ck = S.add(ck.size() * sizeof(BlochCkDev));
+    G.o_lp = S.add(npulse * sizeof(long));
+    G.o_fb = S.add(G.nfold * sizeof(SimBlock));
+    G.o_jb = v_re ? sim_group_table(S, ndir) : S.o_bk;
+    for (int c = 0; c < 3; ++c) {
+        std::copy(w[c], w[c] + O, S.at<double>(G.o_w) + c * O);
+        if (tg) std::copy(tg[c], tg[c] + O, S.at<double>(G.o_t) + c * O);
+    }
+    if (v_re) pack_cplx((size_t)ndir * T, v_re, v_im, S.at<double2>(G.o_v));
+    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(G.o_vp));
+    std::copy(ck.begin(), ck.end(), S.at<BlochCkDev>(G.o_ck));
+    std::copy(lp.begin(), lp.end(), S.at<long>(G.o_lp));
+    SimBlock* fb = S.at<SimBlock>(G.o_fb);
+    for (int p = 0; p < npulse; ++p)
+        for (int k = 0; k < ndir; ++k)
+            for (int c = 0; c < (B.ntime[p] + 255) / 256; ++c) *fb++ = SimBlock{p * ndir + k, 0, c, p};
+    return G;
+}
+// k_bloch_lsq_batch on the input rows `in` (the staged ones, or a trial's) and the fold into grad and loss.
+void bloch_lsq_launch(BlochStaged& B, const BlochGnSections& G, int nscale, const double* in, double2* part, double* cks,
+                      double* lpart, double2* grad, double* loss, hipStream_t st) {
+    Staging& S = B.S;
+    hipLaunchKernelGGL(k_bloch_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+                       S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(G.o_vp), S.dev<const BlochCkDev>(G.o_ck),
+                       S.dev<const long>(G.o_lp), S.dev<const double>(B.o_m0), S.dev<const double>(G.o_w),
+                       S.dev<const double>(G.o_t), B.O, part, cks, lpart);
+    hipLaunchKernelGGL(k_bloch_gn_fold, dim3((unsigned)G.nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(G.o_vp),
+                       S.dev<const SimBlock>(G.o_fb), S.dev<const double>(S.o_sc), nscale, in, S.dev<const BlochPulseDev>(S.o_pd),
+                       grad, lpart, S.dev<const long>(G.o_lp), loss);
+}
+
 void bloch_gn_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                   const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1, const double* t2,
                   const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
@@ -258,63 +412,27 @@ void bloch_gn_run(int device, void* stream, int npulse, const long* toff, const 
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     Staging& S = B.S;
-    const long O = B.O, T = toff[npulse];
-    std::vector<VjpPulseDev> vp((size_t)npulse * ndir);
-    std::vector<BlochCkDev> ck((size_t)npulse * ndir);
-    std::vector<long> lp(npulse);
-    long npart = 0, nck = 0, nlp = 0, nfold = 0;        // double2 partials, checkpoint doubles, loss partials, workgroups of the fold
-    for (int p = 0; p < npulse; ++p) {
-        const int n = B.ntime[p], nch = int((B.npair[p] + 255) / 256), ng = (n + VJP_T - 1) / VJP_T;
-        lp[p] = nlp;
-        nlp += (long)nscale * nch;
-        for (int k = 0; k < ndir; ++k) {
-            vp[(size_t)p * ndir + k] = VjpPulseDev{ndir * toff[p] + (long)k * n, npart, n, nch};
-            ck[(size_t)p * ndir + k] = BlochCkDev{nck, ng, 0};
-            npart += (long)nscale * nch * n;
-            nck += (long)nscale * nch * ng * BLOCH_CK;
-        }
-        nfold += (long)ndir * ((n + 255) / 256);
-    }
-    const size_t o_w = S.add((size_t)O * 24), o_t = lsq ? S.add((size_t)O * 24) : 0, o_v = lsq ? 0 : S.add((size_t)ndir * T * 16),
-                 o_vp = S.add(vp.size() * sizeof(VjpPulseDev)), o_ck = S.add(ck.size() * sizeof(BlochCkDev)),
-                 o_lp = S.add(npulse * sizeof(long)), o_fb = S.add(nfold * sizeof(SimBlock)),
-                 o_jb = lsq ? S.o_bk : sim_group_table(S, ndir);
-    for (int c = 0; c < 3; ++c) {
-        std::copy(w[c], w[c] + O, S.at<double>(o_w) + c * O);
-        if (lsq) std::copy(tg[c], tg[c] + O, S.at<double>(o_t) + c * O);
-    }
-    if (!lsq) pack_cplx((size_t)ndir * T, v_re, v_im, S.at<double2>(o_v));
-    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(o_vp));
-    std::copy(ck.begin(), ck.end(), S.at<BlochCkDev>(o_ck));
-    std::copy(lp.begin(), lp.end(), S.at<long>(o_lp));
-    SimBlock* fb = S.at<SimBlock>(o_fb);
-    for (int p = 0; p < npulse; ++p)
-        for (int k = 0; k < ndir; ++k)
-            for (int c = 0; c < (B.ntime[p] + 255) / 256; ++c) *fb++ = SimBlock{p * ndir + k, 0, c, p};
-    const long R = (long)ndir * T, nl = lsq ? (npulse + 1) / 2 : 0;      // double2 entries of the results and of the losses
-    S.upload(((size_t)R + nl + npart) * 16 + ((size_t)(lsq ? nlp : 0) + nck) * 8, st);
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, tg, ndir, v_re, v_im);
+    const long O = B.O;
+    const long R = (long)ndir * toff[npulse], nl = lsq ? (npulse + 1) / 2 : 0;      // double2 entries of the results and of the losses
+    S.upload(((size_t)R + nl + G.npart) * 16 + ((size_t)(lsq ? G.nlp : 0) + G.nck) * 8, st);
     double2* res = S.dev<double2>(S.o_out);
     double* dloss = reinterpret_cast<double*>(res + R);
     double2* part = res + R + nl;
-    double* lpart = reinterpret_cast<double*>(part + npart);
-    double* cks = lpart + (lsq ? nlp : 0);
-    const double* wd = S.dev<const double>(o_w);
-    if (lsq)
-        hipLaunchKernelGGL(k_bloch_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, S.dev<const double>(B.o_in),
-                           S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc),
-                           S.dev<const BlochPulseDev>(S.o_pd), S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(o_vp),
-                           S.dev<const BlochCkDev>(o_ck), S.dev<const long>(o_lp), S.dev<const double>(B.o_m0), wd,
-                           S.dev<const double>(o_t), O, part, cks, lpart);
-    else
+    double* lpart = reinterpret_cast<double*>(part + G.npart);
+    double* cks = lpart + (lsq ? G.nlp : 0);
+    if (lsq) {
+        bloch_lsq_launch(B, G, nscale, S.dev<const double>(B.o_in), part, cks, lpart, res, dloss, st);
+    } else {
         hipLaunchKernelGGL(k_bloch_gn_batch, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, S.dev<const double>(B.o_in),
                            S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc),
-                           S.dev<const BlochPulseDev>(S.o_pd), S.dev<const SimBlock>(o_jb), S.dev<const VjpPulseDev>(o_vp),
-                           S.dev<const BlochCkDev>(o_ck), S.dev<const double>(B.o_m0), wd, O, S.dev<const double2>(o_v), ndir, part,
-                           cks);
-    hipLaunchKernelGGL(k_bloch_gn_fold, dim3((unsigned)nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(o_vp),
-                       S.dev<const SimBlock>(o_fb), S.dev<const double>(S.o_sc), nscale, S.dev<const double>(B.o_in),
-                       S.dev<const BlochPulseDev>(S.o_pd), res, lsq ? lpart : nullptr, S.dev<const long>(o_lp),
-                       lsq ? dloss : nullptr);
+                           S.dev<const BlochPulseDev>(S.o_pd), S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp),
+                           S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(B.o_m0), S.dev<const double>(G.o_w), O,
+                           S.dev<const double2>(G.o_v), ndir, part, cks);
+        hipLaunchKernelGGL(k_bloch_gn_fold, dim3((unsigned)G.nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(G.o_vp),
+                           S.dev<const SimBlock>(G.o_fb), S.dev<const double>(S.o_sc), nscale, S.dev<const double>(B.o_in),
+                           S.dev<const BlochPulseDev>(S.o_pd), res, nullptr, S.dev<const long>(G.o_lp), nullptr);
+    }
     std::vector<double2> h((size_t)R + nl);
     S.download(h.data(), h.size() * 16, st);
     unpack_cplx(R, h.data(), o_re, o_im);
@@ -345,6 +463,79 @@ void bloch_gn_batch_run(int device, void* stream, int npulse, const long* toff, 
     const double* const w[3] = {wx, wy, wz};
     bloch_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff,
                  dx, dy, dz, nscale, scales, m0x, m0y, m0z, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im);
+}
+
+// Host side of mbfir_bloch_lm_step_batch (arguments checked by api.cpp): the forward staging and bloch_gn_stage at ndir = 1 with b as
+// the direction section, which is the device's p from then on; mu; one upload; k_lm_init, cg rounds of (k_bloch_lm_sweep,
+// k_bloch_lm_step), and with targets k_bloch_lm_trial, the lsq sweep on the trial rows and the fold; one download.  The output region:
+//   d (T double2), the npulse states, [the gradient at b1 + d (T double2), the npulse losses]            downloaded
+//   r, hp (T double2 each), the trial rows (9 T doubles), the partials, the loss partials, the checkpoints   stay on the device
+// The partials and the checkpoints are those of one direction, reused by every round and by the trial's lsq sweep.
+void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
+                             const double* wy, const double* wz, const double* b_re, const double* b_im, const double* mu, int cg,
+                             double rtol, const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
+                             double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool trial = tx != nullptr;
+    const double* const w[3] = {wx, wy, wz};
+    const double* const tg[3] = {tx, ty, tz};
+    BlochStaged B;
+    bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                nscale, scales, 0, m0x, m0y, m0z);
+    Staging& S = B.S;
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im);
+    const size_t o_mu = S.add((size_t)npulse * 8);
+    std::copy(mu, mu + npulse, S.at<double>(o_mu));
+    const long T = toff[npulse];
+    auto pad16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    const size_t b_vec = (size_t)T * 16, b_st = pad16(npulse * sizeof(LmState)), b_loss = pad16((size_t)npulse * 8);
+    const size_t b_down = b_vec + b_st + (trial ? b_vec + b_loss : 0), b_rows = pad16((size_t)T * BLOCH_IN * 8);
+    S.upload(b_down + 2 * b_vec + b_rows + (size_t)G.npart * 16 + ((size_t)G.nlp + G.nck) * 8, st);
+    char* out = S.dev<char>(S.o_out);
+    double2* d = reinterpret_cast<double2*>(out);
+    LmState* state = reinterpret_cast<LmState*>(out + b_vec);
+    double2* grad = reinterpret_cast<double2*>(out + b_vec + b_st);
+    double* dloss = reinterpret_cast<double*>(out + 2 * b_vec + b_st);
+    double2* r = reinterpret_cast<double2*>(out + b_down);
+    double2* hp = r + T;
+    double* rows = reinterpret_cast<double*>(hp + T);
+    double2* part = reinterpret_cast<double2*>(reinterpret_cast<char*>(rows) + b_rows);
+    double* lpart = reinterpret_cast<double*>(part + G.npart);
+    double* cks = lpart + G.nlp;
+    double2* p = S.dev<double2>(G.o_v);
+    const VjpPulseDev* vp = S.dev<const VjpPulseDev>(G.o_vp);
+    const double* in = S.dev<const double>(B.o_in);
+    lm_init_launch(st, npulse, vp, S.dev<const double>(o_mu), cg, rtol, p, d, r, state);
+    for (int k = 0; k < cg; ++k) {                                // rounds of a pulse that has stopped are early exits
+        hipLaunchKernelGGL(k_bloch_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+                           S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                           S.dev<const SimBlock>(G.o_jb), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(B.o_m0),
+                           S.dev<const double>(G.o_w), B.O, p, state, part, cks);
+        hipLaunchKernelGGL(k_bloch_lm_step, dim3((unsigned)npulse), dim3(256), 0, st, part, vp, S.dev<const double>(S.o_sc), nscale, in,
+                           S.dev<const BlochPulseDev>(S.o_pd), cg, rtol, p, d, r, hp, state);
+    }
+    if (trial) {
+        hipLaunchKernelGGL(k_bloch_lm_trial, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, in, d, T, rows);
+        bloch_lsq_launch(B, G, nscale, rows, part, cks, lpart, grad, dloss, st);
+    }
+    std::vector<char> h(b_down);
+    S.download(h.data(), b_down, st);
+    unpack_cplx(T, reinterpret_cast<const double2*>(h.data()), d_re, d_im);
+    const LmState* hs = reinterpret_cast<const LmState*>(h.data() + b_vec);
+    for (int q = 0; q < npulse; ++q) {
+        rr[q] = hs[q].rr; gg[q] = hs[q].gg;
+        ncg[q] = hs[q].ncg; status[q] = hs[q].status;
+    }
+    if (trial) {
+        unpack_cplx(T, reinterpret_cast<const double2*>(h.data() + b_vec + b_st), g_re, g_im);
+        std::copy(reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st),
+                  reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st) + npulse, loss);
+    }
 }
 
 }  // namespace mbfir

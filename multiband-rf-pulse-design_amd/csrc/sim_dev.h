@@ -530,6 +530,45 @@ void bloch_stage(BlochStaged& B, int npulse, const long* toff, const double* b1_
                  const double* dy, const double* dz, int nscale, const double* scales, int mode, const double* m0x,
                  const double* m0y, const double* m0z);
 
+// What the Levenberg-Marquardt steps on the device share (simgn.hip DESIGN 8n, blochgn.hip DESIGN 8s), moved here from simgn.hip
+// token for token.  A pulse whose CG has stopped has run = 0: its workgroups of every later launch return at once, so its bits do
+// not depend on how long its neighbours go on.
+struct LmState {
+    double rr, gg, mu;
+    int ncg, run, status, pad;         // status: 0 tolerance reached, 1 the cap cg reached, 2 breakdown
+};
+
+// The sum of one double per thread of the 256 by a fixed tree in LDS (sw: 256 doubles); every thread gets it.  No shuffles: a
+// second width of __shfl_down in simgn.hip changed how the compiler lowers the width-16 ones of abr_gn_sweeps in the shipped kernels
+// (DESIGN 8n), and bloch_gn_sweeps of blochgn.hip has the same width-16 pass.
+__device__ __forceinline__ double lm_block_sum(double s, double* sw) {
+    __syncthreads();                                              // sw is free again
+    sw[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) sw[threadIdx.x] += sw[threadIdx.x + o];
+        __syncthreads();
+    }
+    return sw[0];
+}
+// <u, v> of the real forms, one sample, and v + al u: every product and sum rounded on its own (contraction off in these two
+// bodies; the round-to-nearest intrinsics of this platform are plain * and +, which the default contraction mode fuses), so that
+// the updates have the bits of the host loop's NumPy expressions on the same inputs.
+__device__ __forceinline__ double lm_redot(double2 u, double2 v) {
+#pragma clang fp contract(off)
+    return u.x * v.x + u.y * v.y;
+}
+__device__ __forceinline__ double2 lm_axpy(double al, double2 u, double2 v) {
+#pragma clang fp contract(off)
+    return make_double2(v.x + al * u.x, v.y + al * u.y);
+}
+__device__ __forceinline__ bool lm_goes_on(int ncg, int cg, double rr, double rtol, double gg) {
+    return ncg < cg && rr > rtol * gg;
+}
+// Launches k_lm_init (simgn.hip) on npulse workgroups: p holds b; d = 0, r = b, rr = gg = <b, b> and the first run flag.
+void lm_init_launch(hipStream_t st, int npulse, const VjpPulseDev* vp, const double* mu, int cg, double rtol, const double2* p,
+                    double2* d, double2* r, LmState* state);
+
 // The adjoint's sections of one call (simgrad.hip, simgradg.hip): the cotangents, the partial descriptors and the fold kernel's table.
 struct VjpSections {
     size_t o_ca = 0, o_cb = 0, o_vp = 0, o_fb = 0;

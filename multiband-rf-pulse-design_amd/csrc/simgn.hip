@@ -245,37 +245,8 @@ __global__ __launch_bounds__(256) void k_abr_gn_fold(const double2* __restrict__
 // k_abr_gn_batch on the device's own p, everything else of an iteration in k_lm_step; then, with a target, the loss and gradient at
 // rf + d by k_abr_lsq_batch.  Stages depend on each other through launch order alone.  A pulse whose CG has stopped has run = 0:
 // its workgroups of every later launch return at once, so its bits do not depend on how long its neighbours go on.
-struct LmState {
-    double rr, gg, mu;
-    int ncg, run, status, pad;         // status: 0 tolerance reached, 1 the cap cg reached, 2 breakdown
-};
-
-// The sum of one double per thread of the 256 by a fixed tree in LDS (sw: 256 doubles); every thread gets it.  No shuffles: a
-// second width of __shfl_down in this file changes how the compiler lowers the width-16 ones of abr_gn_sweeps in the shipped kernels.
-__device__ __forceinline__ double lm_block_sum(double s, double* sw) {
-    __syncthreads();                                              // sw is free again
-    sw[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) sw[threadIdx.x] += sw[threadIdx.x + o];
-        __syncthreads();
-    }
-    return sw[0];
-}
-// <u, v> of the real forms, one sample, and v + al u: every product and sum rounded on its own (contraction off in these two
-// bodies; the round-to-nearest intrinsics of this platform are plain * and +, which the default contraction mode fuses), so that
-// the updates have the bits of the host loop's NumPy expressions on the same inputs.
-__device__ __forceinline__ double lm_redot(double2 u, double2 v) {
-#pragma clang fp contract(off)
-    return u.x * v.x + u.y * v.y;
-}
-__device__ __forceinline__ double2 lm_axpy(double al, double2 u, double2 v) {
-#pragma clang fp contract(off)
-    return make_double2(v.x + al * u.x, v.y + al * u.y);
-}
-__device__ __forceinline__ bool lm_goes_on(int ncg, int cg, double rr, double rtol, double gg) {
-    return ncg < cg && rr > rtol * gg;
-}
+// LmState, the fixed LDS tree lm_block_sum, the uncontracted lm_redot / lm_axpy and lm_goes_on are in sim_dev.h, shared with the
+// Bloch twin of this step (blochgn.hip).
 
 // One workgroup per pulse: p holds b.  d = 0, r = b, rr = gg = <b, b>.  A thread owns the samples tid, tid + 256, ... in every
 // pass of this kernel and of k_lm_step, so the dots are summed in an order that n alone fixes and no pass reads another thread's.
@@ -296,6 +267,11 @@ __global__ __launch_bounds__(256) void k_lm_init(const VjpPulseDev* __restrict__
         const bool run = lm_goes_on(0, cg, gg, rtol, gg);
         st[blockIdx.x] = LmState{gg, gg, mu[blockIdx.x], 0, run ? 1 : 0, gg > rtol * gg ? 1 : 0, 0};
     }
+}
+
+void lm_init_launch(hipStream_t st, int npulse, const VjpPulseDev* vp, const double* mu, int cg, double rtol, const double2* p,
+                    double2* d, double2* r, LmState* state) {
+    hipLaunchKernelGGL(k_lm_init, dim3((unsigned)npulse), dim3(256), 0, st, vp, mu, cg, rtol, p, d, r, state);
 }
 
 // The sweeps of k_abr_gn_batch / k_abr2_gn_batch at ndir = 1 for the pulses that still run; the direction is the device's p.
@@ -584,7 +560,7 @@ void lm_run(Staging& S, size_t o_rf, const std::vector<int>& ntime, const std::v
     double* lpart = reinterpret_cast<double*>(part + G.npart);
     double2* p = S.dev<double2>(G.o_v);
     const VjpPulseDev* vp = S.dev<const VjpPulseDev>(G.o_vp);
-    hipLaunchKernelGGL(k_lm_init, dim3((unsigned)npulse), dim3(256), 0, st, vp, S.dev<const double>(o_mu), a.cg, a.rtol, p, d, r, state);
+    lm_init_launch(st, npulse, vp, S.dev<const double>(o_mu), a.cg, a.rtol, p, d, r, state);
     for (int k = 0; k < a.cg; ++k) {                              // rounds of a pulse that has stopped are early exits
         sweep(G, p, state, part);
         hipLaunchKernelGGL(k_lm_step, dim3((unsigned)npulse), dim3(256), 0, st, part, vp, S.dev<const double>(S.o_sc), a.nscale, a.cg,

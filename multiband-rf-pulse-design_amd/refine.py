@@ -5,7 +5,8 @@ L = 1/2 sum w |f - t|^2, g = J^H W (f - t) and H = J^H W J (abr_lsq_batch / abr_
     the pulses whose CG is still running (one direction each), and tries rf + d with one lsq call, which also returns the gradient
     of the next step;  mu <- mu / 3 after a step that lowers L, mu <- 4 mu after one that does not (the step is then solved again);
     the first mu is 1e-3 times the Rayleigh quotient <g, H g> / <g, g>.
-refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch / bloch_gn_batch, the Bloch model with relaxation.
+refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch / bloch_gn_batch, the Bloch model with relaxation,
+or with solver='device' each step as one bloch_lm_step_batch call.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -170,12 +171,15 @@ def _lm_loop(rfs, infos, lsq, gn, step, iters, mu0):
     return rfs, infos
 
 
-def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, iters=5, cg=8, mu0=None, rtol=1e-6, ctx=None):
-    """refine_batch(solver='host') for bloch_batch's model, relaxation included: the same lock-step Levenberg-Marquardt
-    / CG loop on bloch_lsq_batch and bloch_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, of which only b1 changes; df, dp:
+def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
+                       ctx=None):
+    """refine_batch for bloch_batch's model, relaxation included: the same lock-step Levenberg-Marquardt / CG loop
+    on bloch_lsq_batch and bloch_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, of which only b1 changes; df, dp:
     one grid shared by every pulse or a list of one per pulse; targets, weights, scales and m0 (None, one (mx, my, mz), or a list
     of one per pulse) as for bloch_lsq_batch; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch
-    does.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    does.  solver: 'host' runs the CG recurrence on the host, one bloch_gn_batch call per iteration; 'device' solves and tries each
+    step in one bloch_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as a
+    refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
     mb = importlib.import_module(__package__)
     pulses = list(pulses)
     P = len(pulses)
@@ -186,6 +190,8 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
         raise ValueError("refine_bloch_batch: %d target and %d weight triples for %d pulses" % (len(targets), len(weights), P))
     if iters < 0 or cg < 1:
         raise ValueError("refine_bloch_batch: iters must be at least 0 and cg at least 1")
+    if solver not in ("host", "device"):
+        raise ValueError("refine_bloch_batch: solver must be 'host' or 'device', not %r" % (solver,))
     rest = [tuple(p[1:]) for p in pulses]
     b1s = [np.array(p[0], dtype=np.complex128).ravel() for p in pulses]
     each = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
@@ -209,8 +215,17 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
             infos[q]["calls"]["gn"] += 1
         return mb.bloch_gn_batch(*args(idx, b1s), [v_of[q] for q in idx], [weights[q] for q in idx], **kw(idx))
 
+    def lm(idx, grad, mu):
+        """the step of every active pulse, solved and tried on the device: (b1 + d, L and g there, whether CG broke down)"""
+        for q in idx:
+            infos[q]["calls"]["lm"] += 1
+        res = mb.bloch_lm_step_batch(*args(idx, b1s), [-grad[q] for q in idx], [weights[q] for q in idx], [mu[q] for q in idx],
+                                     targets=[targets[q] for q in idx], cg=cg, rtol=rtol, **kw(idx))
+        return [(b1s[q] + d, i["loss"], i["grad"], i["status"] == "breakdown") for q, (d, i) in zip(idx, res)]
+
     def step(idx, grad, mu):
         return _host_steps(idx, b1s, grad, mu, lsq, gn, cg, rtol)
 
-    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
-    return _lm_loop(b1s, infos, lsq, gn, step, iters, mu0)
+    calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
+    return _lm_loop(b1s, infos, lsq, gn, lm if solver == "device" else step, iters, mu0)
