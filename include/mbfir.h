@@ -357,7 +357,7 @@ int mbfir_abr2_vjp_rfg_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
                              double* ggx, double* ggy);
 /* ---- Adjoint of mbfir_bloch_batch with respect to the b1 samples and the initial magnetisation ----------------------------------
  * The vector-Jacobian product of the end point (mode 0) of mbfir_bloch_batch, relaxation included: the forward call's input
- * arguments up to nscale and scales (no mode: the steady state and the recorded trajectory are not differentiated), then
+ * arguments up to nscale and scales (no mode: the steady state is differentiated by mbfir_bloch_ss_vjp_batch below, the recorded trajectory is not), then
  *   m0x / m0y / m0z: the initial magnetisation in the layout of the mode-0 outputs, block (s, f, k) of pulse p at O_p + (s nf_p + f)
  *     npos_p + k with O_p = sum_{q < p} nscale nf_q npos_q; all three NULL = [0 0 1] everywhere.
  *   cmx / cmy / cmz: the cotangents of mx / my / mz in the same layout, dL = sum cmx dmx + cmy dmy + cmz dmz.
@@ -406,6 +406,39 @@ int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                           double* dmx, double* dmy, double* dmz);
 /* mbfir_test_bloch_jvp_group (host only): the directions one workgroup of the call above carries (a compile-time constant). */
 int mbfir_test_bloch_jvp_group(void);
+/* ---- Adjoint and tangent of mbfir_bloch_batch's steady state with respect to the b1 samples ---------------------------------------
+ * Mode 1 of mbfir_bloch_batch returns the fixed point M = (I - A)^-1 B of one period m -> A m + B of the pulse (for balanced SSFP:
+ * the pulse plus the dead time of one repetition).  A and B depend on b1 and dM = (I - A)^-1 dF at m0 = M, where dF is the
+ * derivative of the mode-0 end point with m0 held fixed; so the adjoint is mbfir_bloch_vjp_batch's from m0 = M with the end
+ * cotangent (I - A)^-T c, and the tangent is (I - A)^-1 times mbfir_bloch_jvp_batch's from m0 = M with dm0 = 0, each fused into one
+ * kernel that starts with mode 1's own sweep.  Both take the forward call's input arguments up to nscale and scales (no mode and no
+ * m0: the steady state does not depend on m0, and there is no dL/dm0), then
+ *   vjp: cmx / cmy / cmz, the cotangents of the mode-1 outputs in their layout (S x nf x npos per pulse, as the mode-0 layout of
+ *        mbfir_bloch_vjp_batch); g_re / g_im as there; mx / my / mz receive M with mode 1's bits, all three NULL = not downloaded.
+ *   jvp: ndir >= 1 and v_re / v_im, then mx / my / mz (M; all three NULL = not downloaded) and dmx / dmy / dmz, all laid out as
+ *        mbfir_bloch_jvp_batch lays them out; a workgroup carries mbfir_test_bloch_ss_jvp_group() directions.
+ * One upload and one download each; the adjoint runs two launches (the second is the fold of mbfir_bloch_vjp_batch), the tangent
+ * one.  No atomics: the bits depend only on the pulse, its grids, its cotangents or direction and the scale list.  The error of M
+ * and of both products grows with kappa = ||(I - A)^-1||, about T1 / TR.  There is no guard on det(I - A): where mode 1 itself is
+ * not finite (T1 so long that E1 rounds to 1) the derivatives are not finite either.  gx / gy / gz, the intervals, t1, t2, the
+ * grids and the scales are not differentiated.  The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_batch;
+ * further MBFIR_E_ARG cases, each with its reason in mbfir_last_error and no device work done: a cotangent, gradient, direction or
+ * tangent plane NULL; mx / my / mz only partly given; ndir < 1; a partial, checkpoint, output or workgroup count that overflows.  A
+ * NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_ss_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* cmx, const double* cmy, const double* cmz, double* g_re, double* g_im,
+                             double* mx, double* my, double* mz);
+int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, int ndir, const double* v_re, const double* v_im, double* mx, double* my,
+                             double* mz, double* dmx, double* dmy, double* dmz);
+/* mbfir_test_bloch_ss_jvp_group (host only): the directions one workgroup of the tangent above carries (a compile-time constant). */
+int mbfir_test_bloch_ss_jvp_group(void);
 /* ---- Least-squares products of mbfir_bloch_batch ----------------------------------------------------------------------------------
  * For the end point (mx, my, mz) of mbfir_bloch_batch (mode 0), relaxation included, weights (wx, wy, wz) >= 0 and targets (tx, ty,
  * tz) per output entry, the loss of a pulse is L = 1/2 sum w_c (m_c - t_c)^2 over c = x, y, z, its points and its scales, and J =

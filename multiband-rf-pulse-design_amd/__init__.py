@@ -140,6 +140,11 @@ SYMBOLS = {
     "mbfir_bloch_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 3 + [C.c_int] + [_dp] * 11),
     "mbfir_test_bloch_jvp_group": (C.c_int, []),
+    "mbfir_bloch_ss_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                           _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 8),
+    "mbfir_bloch_ss_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                           _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [C.c_int] + [_dp] * 8),
+    "mbfir_test_bloch_ss_jvp_group": (C.c_int, []),
     "mbfir_bloch_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
@@ -1392,6 +1397,25 @@ def bloch_batch(pulses, df, dp, *, scales=(1.0,), mode=0, m0=None, ctx=None):
     return res
 
 
+def _bloch_cotangents(who, cot, A):
+    """cot: per pulse (cmx, cmy, cmz), each of shape (S, nf, npos) -> the three concatenated planes of the C call"""
+    cot = list(cot)
+    if len(cot) != A.P:
+        raise ValueError("%s: %d cotangent triples for %d pulses" % (who, len(cot), A.P))
+    planes = [[], [], []]
+    for q, tri in enumerate(cot):
+        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+            raise ValueError("%s: the cotangent of pulse %d must be a triple (cmx, cmy, cmz)" % (who, q))
+        tri = [np.asarray(v, dtype=np.float64) for v in tri]
+        shape = (A.S, A.nf[q], A.npos[q])
+        if any(v.shape != shape for v in tri):
+            raise ValueError("%s: the cotangents of pulse %d have shapes %s, %s and %s, the forward call returns %s"
+                             % ((who, q) + tuple(v.shape for v in tri) + (shape,)))
+        for c in range(3):
+            planes[c].append(tri[c].ravel())
+    return [_vec(np.concatenate(p)) for p in planes]
+
+
 def bloch_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=False, ctx=None):
     """The adjoint of bloch_batch's end point (mode 0) with respect to b1 and the initial magnetisation, relaxation included
     (mbfir_bloch_vjp_batch): pulses, df, dp, scales and m0 as for bloch_batch; cot: one (cmx, cmy, cmz) per pulse,
@@ -1402,21 +1426,7 @@ def bloch_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=Fals
     cotangents and the scales.  gr, tp, t1, t2, df and dp are not differentiated."""
     A = _BlochArgs("bloch_vjp_batch", pulses, df, dp, scales)
     P, S, nf, npos = A.P, A.S, A.nf, A.npos
-    cot = list(cot)
-    if len(cot) != P:
-        raise ValueError("bloch_vjp_batch: %d cotangent triples for %d pulses" % (len(cot), P))
-    planes = [[], [], []]
-    for q, tri in enumerate(cot):
-        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
-            raise ValueError("bloch_vjp_batch: the cotangent of pulse %d must be a triple (cmx, cmy, cmz)" % q)
-        tri = [np.asarray(v, dtype=np.float64) for v in tri]
-        shape = (S, nf[q], npos[q])
-        if any(v.shape != shape for v in tri):
-            raise ValueError("bloch_vjp_batch: the cotangents of pulse %d have shapes %s, %s and %s, the forward call returns %s"
-                             % ((q,) + tuple(v.shape for v in tri) + (shape,)))
-        for c in range(3):
-            planes[c].append(tri[c].ravel())
-    cm = [_vec(np.concatenate(p)) for p in planes]
+    cm = _bloch_cotangents("bloch_vjp_batch", cot, A)
     ooff, toff = _offsets([S * f * k for f, k in zip(nf, npos)]), _offsets(A.nt)
     nul = C.cast(None, _dp)
     m0p = [nul] * 3 if m0 is None else A.m0_planes(m0, ooff, [1] * P)
@@ -1475,6 +1485,63 @@ def bloch_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), m0=None, tangent
     ctx = ctx or get_context()
     rc = load_library().mbfir_bloch_jvp_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], K, *[_ptr(v) for v in vplanes],
                                               *[_plane(v) for v in dm0], *[_ptr(v) for v in out], *[_ptr(v) for v in tan])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = []
+    for q in range(P):
+        lo, hi, shape = int(ooff[q]), int(ooff[q + 1]), (S, nf[q], npos[q])
+        res.append((tuple(o[lo:hi].reshape(shape) for o in out),
+                    tuple(t[K * lo:K * hi].reshape(((K,) if keep else ()) + shape) for t in tan)))
+    return res
+
+
+def bloch_ss_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), steady=False, ctx=None):
+    """The adjoint of bloch_batch's steady state (mode 1) with respect to b1 (mbfir_bloch_ss_vjp_batch): pulses
+    (each one period: for balanced SSFP the pulse plus the dead time of one repetition), df, dp and scales as for bloch_batch; cot:
+    one (cmx, cmy, cmz) per pulse, the cotangents of the (mx, my, mz) that bloch_batch(mode=1) returns, each of shape (S, nf, npos).
+    Returns a list of complex (ntime,) gradients dL/dRe b1 + i dL/dIm b1, summed over the points and the scales; with steady, a list
+    of (grad_b1, (mx, my, mz)), the second being the steady state itself with bloch_batch(mode=1)'s bits, each of shape (S, nf,
+    npos).  One upload, two launches, one download.  The steady state does not depend on m0: there is no m0 and no dL/dm0.
+    Deterministic: a pulse's gradient bits depend only on the pulse, its grids, its cotangents and the scales.  The error grows with
+    ||(I - A)^-1||, about T1 / TR; where the steady state itself is not finite, the gradient is not either.  gr, tp, t1, t2, df and
+    dp are not differentiated."""
+    A = _BlochArgs("bloch_ss_vjp_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    cm = _bloch_cotangents("bloch_ss_vjp_batch", cot, A)
+    ooff, toff = _offsets([S * f * k for f, k in zip(nf, npos)]), _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    grad = [np.zeros(int(toff[-1])) for _ in range(2)]
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)] if steady else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_vjp_batch(ctx._h, *A.head, *[_ptr(v) for v in cm], _ptr(grad[0]), _ptr(grad[1]),
+                                                 *[_ptr(v) if steady else v for v in out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all = grad[0] + 1j * grad[1]
+    res = [g_all[toff[q]:toff[q + 1]] for q in range(P)]
+    if not steady:
+        return res
+    return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in out)) for q in range(P)]
+
+
+def bloch_ss_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), ctx=None):
+    """The tangent of bloch_batch's steady state (mode 1) with respect to b1 (mbfir_bloch_ss_jvp_batch): pulses,
+    df, dp and scales as for bloch_batch; tangents: per pulse a complex direction of b1 of shape (n,), or K of them of shape (K, n),
+    the same K for every pulse.  Returns a list of ((mx, my, mz), (dmx, dmy, dmz)) per pulse: the steady state of shape (S, nf,
+    npos) with bloch_batch(mode=1)'s bits, and d/de M(b1 + e v) at e = 0 for each direction, of shape (K, S, nf, npos), without the K
+    axis for a 1-D tangent.  Real-linear in v.  One launch; a tangent's bits depend only on its pulse, scale, point and direction.
+    gr, tp, t1, t2, df and dp are not differentiated."""
+    A = _BlochArgs("bloch_ss_jvp_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    K, keep, vplanes = _tangents("bloch_ss_jvp_batch", tangents, [range(n) for n in A.nt])
+    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)]
+    tan = [np.zeros(K * int(ooff[-1])) for _ in range(3)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_jvp_batch(ctx._h, *A.head, K, *[_ptr(v) for v in vplanes], *[_ptr(v) for v in out],
+                                                 *[_ptr(v) for v in tan])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2083,6 +2150,11 @@ from .refine import refine_batch, refine_bloch_batch   # noqa: E402  (batched Le
 def jvp_group():
     """The directions one workgroup of abr_jvp_batch / abr2_jvp_batch carries (mbfir_test_jvp_group)."""
     return int(load_library().mbfir_test_jvp_group())
+
+
+def bloch_ss_jvp_group():
+    """The directions one workgroup of bloch_ss_jvp_batch carries (mbfir_test_bloch_ss_jvp_group)."""
+    return int(load_library().mbfir_test_bloch_ss_jvp_group())
 
 
 def bloch_jvp_group():

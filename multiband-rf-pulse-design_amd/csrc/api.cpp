@@ -1337,6 +1337,58 @@ int mbfir_bloch_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                                        v_im, dm0x, dm0y, dm0z, mx, my, mz, dmx, dmy, dmz));
 }
 
+// The steady state's derivatives (blochss.hip): mbfir_bloch_batch's checks at mode 1, then the call's own planes, then
+// the counts of the adjoint (partials, checkpoints) or of the tangent (jvp_check, and one plane of (I - A)^-1 per workgroup).
+int mbfir_bloch_ss_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* cmx, const double* cmy, const double* cmz, double* g_re, double* g_im,
+                             double* mx, double* my, double* mz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_vjp_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_vjp_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+                                        arrays, npoint))
+        return e;
+    if (!cmx || !cmy || !cmz || !g_re || !g_im) return bad("a cotangent or gradient plane is null");
+    if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
+    if (!vjp_partials_fit(npulse, nscale, toff, npoint.data()) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                          t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, cmx, cmy, cmz, g_re,
+                                          g_im, mx, my, mz));
+}
+
+int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, int ndir, const double* v_re, const double* v_im, double* mx, double* my,
+                             double* mz, double* dmx, double* dmy, double* dmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_jvp_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_jvp_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+                                        arrays, npoint))
+        return e;
+    if (!v_re || !v_im || !dmx || !dmy || !dmz) return bad("a direction or tangent plane is null");
+    if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
+    if (const int e = jvp_check(ctx, "bloch_ss_jvp_batch", npulse, nscale, ndir, toff[npulse], npoint.data(), bloch_ss_jvp_group()))
+        return e;
+    long nblk = 0;                                              // jvp_check has bounded it times the direction groups by 2^31 - 1
+    for (int p = 0; p < npulse; ++p) nblk += (npoint[p] + 255) / 256 * nscale;
+    if (nblk * ((ndir + (long)bloch_ss_jvp_group() - 1) / bloch_ss_jvp_group()) > (1L << 56) / 2304)
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_jvp_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                          t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ndir, v_re, v_im, mx,
+                                          my, mz, dmx, dmy, dmz));
+}
+
+int mbfir_test_bloch_ss_jvp_group(void) { return bloch_ss_jvp_group(); }
+
 // What the Bloch least-squares calls check after bloch_batch_check, in this order: their own planes (what: the message of a null
 // one), m0, the 3 O weights (O: the forward call's output entries), ndir, and that ndir times the T b1 samples, the partials (one per
 // workgroup and sample, per direction) and the checkpoints (at most 2^56 entries each) and the workgroups of the sweep and of the

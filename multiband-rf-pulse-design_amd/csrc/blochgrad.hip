@@ -136,6 +136,12 @@ __global__ __launch_bounds__(256) void k_bloch_vjp_fold(const double2* __restric
     grad[V.r_off + t] = make_double2(-(f * g.x), f * g.y);
 }
 
+// Launches k_bloch_vjp_fold on nfold workgroups for the callers outside this file (blochss.hip).
+void bloch_vjp_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
+                           const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* grad) {
+    hipLaunchKernelGGL(k_bloch_vjp_fold, dim3((unsigned)nfold), dim3(256), 0, st, part, vp, blocks, scales, nscale, in, pulses, grad);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_vjp_batch (arguments checked by api.cpp): the forward call's staging (bloch_stage, mode 0) plus the
 // cotangents, the partial and checkpoint descriptors and the fold kernel's table; one upload, two launches, one download.  The

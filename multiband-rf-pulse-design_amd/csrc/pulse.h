@@ -79,6 +79,24 @@ void bloch_jvp_batch_run(int device, void* stream, int npulse, const long* toff,
                          const double* scales, const double* m0x, const double* m0y, const double* m0z, int ndir, const double* v_re,
                          const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z, double* mx, double* my,
                          double* mz, double* dmx, double* dmy, double* dmz);
+// Adjoint and tangent of bloch_batch_run's steady state (mode 1) with respect to b1 (blochss.hip k_bloch_ss_vjp_batch,
+// k_bloch_ss_jvp_batch): the forward call's inputs; cm*: the cotangents of the mode-1 outputs in their layout; g_re /
+// g_im as above; m*: the steady state with mode 1's bits (all null: not downloaded); v, dm*: as bloch_jvp_batch_run's.  There is no
+// m0: the steady state does not depend on it.  The adjoint: one upload, two launches (the second is k_bloch_vjp_fold), one
+// download; the tangent: one upload, one launch of bloch_ss_jvp_group() directions per workgroup, one download.
+void bloch_ss_vjp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* cmx, const double* cmy, const double* cmz, double* g_re, double* g_im,
+                            double* mx, double* my, double* mz);
+int bloch_ss_jvp_group();
+void bloch_ss_jvp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, int ndir, const double* v_re, const double* v_im, double* mx, double* my,
+                            double* mz, double* dmx, double* dmy, double* dmz);
 // Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
 // k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
 // pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.

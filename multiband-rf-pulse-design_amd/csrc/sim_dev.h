@@ -482,6 +482,11 @@ struct BlochCkDev {
 };
 constexpr int BLOCH_CK = 3 * 256;
 
+// Launches k_bloch_vjp_fold (blochgrad.hip) on nfold workgroups: the fold of the steady state's adjoint (blochss.hip) is the
+// transient adjoint's.
+void bloch_vjp_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
+                           const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* grad);
+
 // What the directions of one point share at one sample.  R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) =
 // (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi, and along dn = (dnx, dny, 0), with d sp = D (n.dn) (half_sinc),
 //     d ar = -(sp/2)(n.dn),  d ai = -nz D (n.dn),  d br = ny D (n.dn) + sp dny,  d bi = -nx D (n.dn) - sp dnx

@@ -9,7 +9,9 @@ host pointers, so tensors go through host memory, and the results come back on r
 x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
 `bloch` runs mbfir.bloch_batch on one pulse (the Bloch simulation with T1 / T2, end point) and is differentiable in reverse mode in
 b1 and in the initial magnetisation m0, its backward being one mbfir.bloch_vjp_batch call (section 8p); with forward_mode=True it
-also has the forward-mode tangent in both, one mbfir.bloch_jvp_batch call with one direction (section 8q).
+also has the forward-mode tangent in both, one mbfir.bloch_jvp_batch call with one direction (section 8q).  With steady_state=True
+it returns the steady state of the period instead (bloch_batch mode 1), differentiable in b1 through mbfir.bloch_ss_vjp_batch and
+mbfir.bloch_ss_jvp_batch (section 8t).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -210,18 +212,72 @@ def _bloch_function():
                                               m0=None if m0h is None else tuple(m0h), tangents_m0=dm0)
             return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in tan)
 
-    return Bloch, BlochForward
+    class BlochSteady(torch.autograd.Function):
+        """The steady state (bloch_batch mode 1): the backward is one mbfir.bloch_ss_vjp_batch call."""
+
+        @staticmethod
+        def forward(b1, pulse, df, dp, scales):
+            if not torch.is_tensor(b1) or b1.dtype != torch.complex128 or b1.dim() != 1:
+                raise ValueError("torchsim: b1 must be a 1-D complex128 tensor")
+            res, = mbfir.bloch_batch([(_host(b1, np.complex128),) + pulse], df, dp, scales=scales, mode=1)
+            return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(b1.device) for v in res)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, pulse, df, dp, scales = inputs
+            ctx.args = (pulse, df, dp, scales)
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch is not implemented (reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, cx, cy, cz):
+            b1, = ctx.saved_tensors
+            pulse, df, dp, scales = ctx.args
+            cot = tuple(_host(c, np.float64) for c in (cx, cy, cz))
+            grad, = mbfir.bloch_ss_vjp_batch([(_host(b1, np.complex128),) + pulse], df, dp, [cot], scales=scales)
+            return torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device), None, None, None, None
+
+    class BlochSteadyForward(BlochSteady):
+        """BlochSteady with a forward-mode tangent: a jvp that is one mbfir.bloch_ss_jvp_batch call with one direction."""
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            BlochSteady.setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+
+        @staticmethod
+        def jvp(ctx, v, *_):
+            b1, = ctx.saved_tensors
+            pulse, df, dp, scales = ctx.args
+            b1h = _host(b1, np.complex128)
+            vh = np.zeros_like(b1h) if v is None else _host(v, np.complex128)
+            (_, tan), = mbfir.bloch_ss_jvp_batch([(b1h,) + pulse], df, dp, [vh], scales=scales)
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in tan)
+
+    return Bloch, BlochForward, BlochSteady, BlochSteadyForward
 
 
-def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None, forward_mode=False):
+def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None, forward_mode=False, steady_state=False):
     """(mx, my, mz) of mbfir.bloch_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, scales=scales, m0=m0), the end point of the Bloch
     simulation with relaxation, each a float64 tensor of shape (S, nf, npos) with bloch_batch's bits.  Differentiable in reverse mode
     in b1 (a 1-D complex128 tensor) and in m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient
     is summed over the scales); the backward is one mbfir.bloch_vjp_batch call.  Any other m0 ((mx, my, mz) or
     an array of shape (3, nf, npos); None: equilibrium), gr, tp, t1, t2, df and dp are constants.  A forward-mode tangent raises
     NotImplementedError unless forward_mode is set: then torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as
-    well, the tangent in b1 and in a tensor m0 being one mbfir.bloch_jvp_batch call with one direction (section 8q)."""
+    well, the tangent in b1 and in a tensor m0 being one mbfir.bloch_jvp_batch call with one direction (section 8q).
+    With steady_state the result is the steady state of the period b1 instead, bloch_batch(mode=1) with its bits (for balanced SSFP
+    the period is the pulse plus the dead time of one repetition): differentiable in b1, the backward being one
+    mbfir.bloch_ss_vjp_batch call and, with forward_mode, the tangent one mbfir.bloch_ss_jvp_batch call (section 8t).  The steady
+    state does not depend on m0: an m0 other than None raises ValueError."""
     pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
+    if steady_state:
+        if m0 is not None:
+            raise ValueError("torchsim: the steady state does not depend on m0; pass m0=None with steady_state")
+        fn = _bloch_function()[3 if forward_mode else 2]
+        return fn.apply(b1, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
     fn = _bloch_function()[1 if forward_mode else 0]
