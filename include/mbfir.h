@@ -471,6 +471,38 @@ int mbfir_bloch_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const dou
                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                          const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
                          const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im);
+/* ---- Least-squares products of the steady state of mbfir_bloch_batch ----------------------------------------------------------------
+ * For the steady state M = (mx, my, mz) of mbfir_bloch_batch (mode 1), weights (wx, wy, wz) >= 0 and targets (tx, ty, tz) per output
+ * entry, the loss of a pulse is L = 1/2 sum w_c (M_c - t_c)^2 over c = x, y, z, its points and its scales, and J = dM / db1 is the
+ * Jacobian of the steady state with respect to the b1 samples (real-linear, as in mbfir_bloch_ss_jvp_batch).  The forward call's
+ * input arguments up to nscale and scales come first (no mode, and no m0: the steady state does not depend on it), then wx / wy / wz
+ * (and tx / ty / tz), laid out as the mode-1 outputs.
+ *   lsq: loss[npulse] receives L per pulse, g_re / g_im (laid out as b1) the gradient sum_s s J_s' W_s (M_s - t_s) = dL/dRe b1 + i
+ *        dL/dIm b1; mx / my / mz (all three NULL: not wanted) receive M with mbfir_bloch_batch's bits.  The residual is formed from
+ *        that M: targets equal to mode 1's own output give L = 0 and g = 0 exactly.
+ *   gn:  ndir >= 1 directions per pulse in v_re / v_im, laid out as mbfir_bloch_jvp_batch lays them out; h_re / h_im receive the
+ *        Gauss-Newton products sum_s s J_s' W_s J_s (s v), pulse p from ndir toff[p], direction-major.
+ * Each is one upload, one sweep launch (one workgroup per forward workgroup, and for gn per direction) plus a fold, and one download
+ * of the n (ndir n) complex results per pulse and the losses: nothing of point size comes back unless M is asked for.  No atomics:
+ * a pulse's L, g and H v bits depend only on the pulse, its grids, its weights, target or direction and the scale list, not on the
+ * batch, its order or ndir.  A point of weight 0 contributes exact zeros, and so does scale 0 to g and H v.  No guard on det(I - A).
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_batch at mode 1, then in this order, each with its
+ * reason in mbfir_last_error: a weight, target, direction or output plane NULL; mx / my / mz only partly given; a negative or
+ * non-finite weight; ndir < 1; partials, checkpoints, inverse planes or a workgroup count that overflow.  No device work is done
+ * before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_ss_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
+                             const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
+                             double* mz);
+int mbfir_bloch_ss_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
+                            const double* v_im, double* h_re, double* h_im);
 /* ---- Tangents of mbfir_abr_batch / mbfir_abr2_batch with respect to the rf samples ----------------------------------------------
  * The Jacobian-vector product of the forward call, in both models: the forward call's inputs, then ndir >= 1 directions for every
  * pulse in v_re / v_im, direction-major within a pulse (sample m of direction k of pulse p at ndir roff[p] + k n_p + m), then the

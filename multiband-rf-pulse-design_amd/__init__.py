@@ -145,6 +145,10 @@ SYMBOLS = {
     "mbfir_bloch_ss_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                            _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [C.c_int] + [_dp] * 8),
     "mbfir_test_bloch_ss_jvp_group": (C.c_int, []),
+    "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                           _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
+    "mbfir_bloch_ss_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                          _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 3 + [C.c_int] + [_dp] * 4),
     "mbfir_bloch_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
@@ -1621,6 +1625,59 @@ def bloch_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), m0=None,
     ctx = ctx or get_context()
     rc = load_library().mbfir_bloch_gn_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w], K,
                                              *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _gn_result(rfs, K, keep, h)
+
+
+def bloch_ss_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), steady=False, ctx=None):
+    """Loss and gradient of a weighted least-squares fit of bloch_batch's steady state (mode 1) in one device call
+    (mbfir_bloch_ss_lsq_batch): pulses (each one period), df, dp and scales as for bloch_ss_vjp_batch; targets and
+    weights as for bloch_lsq_batch: per pulse a triple (x, y, z) for (mx, my, mz), each entry of the shape (S, nf, npos) that
+    bloch_batch(mode=1) returns, or (nf, npos) for every scale, or a scalar (weights >= 0).  Returns a list of (L, grad) per pulse:
+    L = 1/2 sum w_c (M_c - t_c)^2 over the three components, the points and the scales, and grad = dL/dRe b1 + i dL/dIm b1, complex
+    (ntime,); with steady, a list of (L, grad, (mx, my, mz)), the last being the steady state with bloch_batch(mode=1)'s bits, of
+    which the residual is formed.  Without steady nothing of point size comes back from the device.  There is no m0.  Deterministic:
+    a pulse's L and grad bits depend only on the pulse, its grids, targets, weights and the scales.  The error grows with
+    ||(I - A)^-1||, about T1 / TR.  gr, tp, t1, t2, df and dp are not differentiated."""
+    who = "bloch_ss_lsq_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    t = _bloch_planes(who, "target", targets, A)
+    T = sum(A.nt)
+    loss, grad = np.zeros(P), [np.zeros(T) for _ in range(2)]
+    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)] if steady else [C.cast(None, _dp)] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_lsq_batch(ctx._h, *A.head, *[_ptr(v) for v in w + t], _ptr(loss), _ptr(grad[0]),
+                                                 _ptr(grad[1]), *[_ptr(v) if steady else v for v in out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = _lsq_result([range(n) for n in A.nt], loss, grad)
+    if not steady:
+        return res
+    return [res[q] + (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in out),) for q in range(P)]
+
+
+def bloch_ss_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), ctx=None):
+    """Gauss-Newton products of the fit of bloch_ss_lsq_batch, in one device call (mbfir_bloch_ss_gn_batch): H v = sum_s s J_s' W_s
+    J_s (s v) for J = dM / db1 of the steady state (real-linear in v) and W the weights; arguments as for bloch_ss_lsq_batch, with
+    tangents as bloch_ss_jvp_batch takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every
+    pulse.  Returns per pulse a complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real inner product Re
+    sum conj(u) v.  A product's bits depend only on its pulse, grids, weights, direction and the scales: not on the batch or the
+    direction's place among K."""
+    who = "bloch_ss_gn_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    rfs = [range(n) for n in A.nt]
+    K, keep, vplanes = _tangents(who, tangents, rfs)
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_gn_batch(ctx._h, *A.head, *[_ptr(v) for v in w], K, *[_ptr(v) for v in vplanes], _ptr(h[0]),
+                                                _ptr(h[1]))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)

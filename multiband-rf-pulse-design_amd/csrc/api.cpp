@@ -1465,6 +1465,58 @@ int mbfir_bloch_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const dou
                                       ndir, v_re, v_im, h_re, h_im));
 }
 
+// The steady state's least-squares products (blochssgn.hip): mbfir_bloch_batch's checks at mode 1, then the call's own
+// planes, M given whole or not at all, then bloch_gn_check's (no m0): the weights, ndir, the partials, the checkpoints and the
+// workgroup counts; gn also one plane of (I - A)^-1 per workgroup, as mbfir_bloch_ss_jvp_batch bounds it.
+int mbfir_bloch_ss_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
+                             const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
+                             double* mz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_lsq_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+                                        arrays, npoint))
+        return e;
+    if (!(wx && wy && wz && tx && ty && tz && loss && g_re && g_im)) return bad("a weight, target, loss or gradient plane is null");
+    if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
+    if (const int e = bloch_gn_check(ctx, "bloch_ss_lsq_batch", true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff,
+                                     npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, bloch_ss_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                          t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, tx, ty, tz,
+                                          loss, g_re, g_im, mx, my, mz));
+}
+
+int mbfir_bloch_ss_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
+                            const double* v_im, double* h_re, double* h_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_gn_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+                                        arrays, npoint))
+        return e;
+    if (!(wx && wy && wz && v_re && v_im && h_re && h_im)) return bad("a weight, direction or product plane is null");
+    if (const int e = bloch_gn_check(ctx, "bloch_ss_gn_batch", true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, ndir, toff,
+                                     npoint.data()))
+        return e;
+    long nblk = 0;                                              // bloch_gn_check has bounded it times ndir by 2^31 - 1
+    for (int p = 0; p < npulse; ++p) nblk += (npoint[p] + 255) / 256 * nscale;
+    if (nblk * ndir > (1L << 56) / 2304) return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                         t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, ndir, v_re,
+                                         v_im, h_re, h_im));
+}
+
 // What the least-squares calls check after abr_batch_check, in this order: their own arrays, the profile, the O weights (O: the
 // forward call's output entries), ndir, and that ndir times the R rf samples, the partials (one per workgroup and sample, per
 // direction; at most 2^56 entries each) and the workgroups of the sweep and of the fold (at most 2^31 - 1 each) fit.  0, or

@@ -336,13 +336,8 @@ __global__ __launch_bounds__(256) void k_bloch_lm_trial(const double* __restrict
 // mode 0) plus the weights, the targets or the directions, the descriptors and the two tables; one upload, two launches, one
 // download of the ndir T results (and the npulse losses).  The output region is the results (ndir T double2), the losses (padded
 // to a whole double2), then the partials, the loss partials and the checkpoints, which stay on the device.
-namespace {
 // The sections the least-squares calls add to the forward staging, filled (pointers into B.S taken before this are stale), and the
 // sizes of what stays on the device.  tg null: no targets; v_re null: no directions, and the sweep's table is the forward one.
-struct BlochGnSections {
-    size_t o_w = 0, o_t = 0, o_v = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0, o_jb = 0;
-    long npart = 0, nck = 0, nlp = 0, nfold = 0;        // double2 partials, checkpoint doubles, loss partials, workgroups of the fold
-};
 BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int nscale, const double* const w[3],
                                const double* const tg[3], int ndir, const double* v_re, const double* v_im) {
     Staging& S = B.S;
@@ -385,6 +380,14 @@ BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int
             for (int c = 0; c < (B.ntime[p] + 255) / 256; ++c) *fb++ = SimBlock{p * ndir + k, 0, c, p};
     return G;
 }
+// Launches k_bloch_gn_fold on nfold workgroups: the fold of the steady state's products (blochssgn.hip) is this one.
+void bloch_gn_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
+                          const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* out,
+                          const double* lpart, const long* lp, double* loss) {
+    hipLaunchKernelGGL(k_bloch_gn_fold, dim3((unsigned)nfold), dim3(256), 0, st, part, vp, blocks, scales, nscale, in, pulses, out, lpart,
+                       lp, loss);
+}
+namespace {
 // k_bloch_lsq_batch on the input rows `in` (the staged ones, or a trial's) and the fold into grad and loss.
 void bloch_lsq_launch(BlochStaged& B, const BlochGnSections& G, int nscale, const double* in, double2* part, double* cks,
                       double* lpart, double2* grad, double* loss, hipStream_t st) {

@@ -97,6 +97,24 @@ void bloch_ss_jvp_batch_run(int device, void* stream, int npulse, const long* to
                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                             const double* scales, int ndir, const double* v_re, const double* v_im, double* mx, double* my,
                             double* mz, double* dmx, double* dmy, double* dmz);
+// Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
+// blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
+// the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1
+// sample and, when wanted, the steady state with mode 1's bits (m* all null: not downloaded); gn: sum_s s J_s' W_s J_s (s v).  One
+// upload, two launches, one download.
+void bloch_ss_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
+                            const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
+                            double* mz);
+void bloch_ss_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                           const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                           const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                           int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                           const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
+                           const double* v_im, double* h_re, double* h_im);
 // Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
 // k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
 // pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.

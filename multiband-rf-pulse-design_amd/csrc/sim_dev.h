@@ -517,6 +517,67 @@ __device__ __forceinline__ void bloch_jvp_shared(double nx, double ny, double nz
     W.Vy[2] = -f * (ar * m[0] + ai * m[1] + br * m[2]);
 }
 
+// Pass 0 of the steady state (blochss.hip DESIGN 8t, blochssgn.hip DESIGN 8u), moved here from blochss.hip token for token.
+constexpr int BLOCH_SSINV = 9 * 256;                 // doubles of (I - A)^-1 per workgroup of the tangent
+
+// Stages the rows t0 .. of the pulse b1 s into sst, as k_bloch_batch stages them.
+__device__ __forceinline__ void bloch_ss_stage(double (*sst)[8], const double* __restrict__ in, long t_off, int ntime, int t0, double sc,
+                                               double gamma) {
+    __syncthreads();
+    const int cnt = min(BLOCH_CH, ntime - t0), tid = threadIdx.x;
+    if (tid < cnt) {
+        const double* s = in + BLOCH_IN * (t_off + t0 + tid);
+        const double dt = s[8];
+        sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                      // rotx of the pulse b1 s, as k_bloch_batch forms it
+        sst[tid][1] = ((s[1] * sc) * gamma) * dt;                         // roty
+        for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
+    }
+    __syncthreads();
+}
+
+// R c for a column c of A with the fused products that k_bloch_batch's pass 0 compiles to: there the compiler rounds the middle
+// product of a row, R_i1 c_1, and fuses the outer two onto it, whereas rot_vec on its own (and pass 0's own B update) rounds the
+// first.  Written out so that M has mode 1's bits (tests/test_blochss_gpu.py holds the two equal).
+__device__ __forceinline__ void bloch_ss_rot_col(const Rot3& R, const double c[3], double o[3]) {
+    for (int i = 0; i < 3; ++i) o[i] = fma(R.m[6 + i], c[2], fma(R.m[i], c[0], R.m[3 + i] * c[1]));
+}
+
+// Pass 0 of k_bloch_batch for one point, statement by statement: (A, B) over the samples, inv = (I - A)^-1 by the adjugate
+// (column-major), m = inv B.  Leaves the pulse's last tile staged.
+__device__ __forceinline__ void bloch_ss_pass0(double (*sst)[8], const double* __restrict__ in, long t_off, int ntime, double sc,
+                                               double gamma, double px, double py, double pz, double dfv, double (&inv)[9],
+                                               double (&m)[3]) {
+    double A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, B[3] = {0, 0, 0};
+    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
+        bloch_ss_stage(sst, in, t_off, ntime, t0, sc, gamma);
+        const int cnt = min(BLOCH_CH, ntime - t0);
+        for (int q = 0; q < cnt; ++q) {
+            const double* s = sst[q];
+            const double rotz = -((s[2] * px + s[3] * py + s[4] * pz) + dfv * s[5]);
+            Rot3 R;
+            bloch_rotmat(s[0], s[1], rotz, R);
+            const double e1 = s[6], e2 = s[7];
+            double c[3], o[3];
+            for (int j = 0; j < 3; ++j) {                                 // A <- D R A, column by column
+                c[0] = A[3 * j]; c[1] = A[3 * j + 1]; c[2] = A[3 * j + 2];
+                bloch_ss_rot_col(R, c, o);
+                A[3 * j] = e2 * o[0]; A[3 * j + 1] = e2 * o[1]; A[3 * j + 2] = e1 * o[2];
+            }
+            rot_vec(R, B, o);
+            B[0] = e2 * o[0]; B[1] = e2 * o[1]; B[2] = e1 * o[2] + (1 - e1);
+        }
+    }
+    double K[9];
+    for (int e = 0; e < 9; ++e) K[e] = ((e == 0 || e == 4 || e == 8) ? 1.0 : 0.0) - A[e];
+    const double c00 = K[4] * K[8] - K[7] * K[5], c01 = K[7] * K[2] - K[1] * K[8], c02 = K[1] * K[5] - K[4] * K[2];
+    const double det = K[0] * c00 + K[3] * c01 + K[6] * c02;
+    const double iv[9] = {c00 / det, c01 / det, c02 / det,
+                          (K[6] * K[5] - K[3] * K[8]) / det, (K[0] * K[8] - K[6] * K[2]) / det, (K[3] * K[2] - K[0] * K[5]) / det,
+                          (K[3] * K[7] - K[6] * K[4]) / det, (K[6] * K[1] - K[0] * K[7]) / det, (K[0] * K[4] - K[3] * K[1]) / det};
+    for (int i = 0; i < 3; ++i) m[i] = iv[i] * B[0] + iv[3 + i] * B[1] + iv[6 + i] * B[2];
+    for (int e = 0; e < 9; ++e) inv[e] = iv[e];
+}
+
 // The inputs of one mbfir_bloch_batch call, staged and filled (slr.hip): the sample rows, the grids, the initial magnetisation
 // and Staging's tables.  The forward call uploads this as it is; the adjoint adds its own sections first.  m0x / m0y / m0z: the
 // initial magnetisation at the first entry of every (scale, frequency, position) block of the outputs' layout under `mode` (all
@@ -534,6 +595,19 @@ void bloch_stage(BlochStaged& B, int npulse, const long* toff, const double* b1_
                  const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
                  const double* dy, const double* dz, int nscale, const double* scales, int mode, const double* m0x,
                  const double* m0y, const double* m0z);
+
+// The sections the Bloch least-squares calls add to the forward staging (blochgn.hip bloch_gn_stage, moved here token for token so
+// that blochssgn.hip stages through it too), and the sizes of what stays on the device.
+struct BlochGnSections {
+    size_t o_w = 0, o_t = 0, o_v = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0, o_jb = 0;
+    long npart = 0, nck = 0, nlp = 0, nfold = 0;        // double2 partials, checkpoint doubles, loss partials, workgroups of the fold
+};
+BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int nscale, const double* const w[3],
+                               const double* const tg[3], int ndir, const double* v_re, const double* v_im);
+// Launches k_bloch_gn_fold (blochgn.hip) on nfold workgroups; lpart, lp, loss as the kernel takes them (loss null: no loss sum).
+void bloch_gn_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
+                          const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* out,
+                          const double* lpart, const long* lp, double* loss);
 
 // What the Levenberg-Marquardt steps on the device share (simgn.hip DESIGN 8n, blochgn.hip DESIGN 8s), moved here from simgn.hip
 // token for token.  A pulse whose CG has stopped has run = 0: its workgroups of every later launch return at once, so its bits do

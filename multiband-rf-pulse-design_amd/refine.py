@@ -6,7 +6,8 @@ L = 1/2 sum w |f - t|^2, g = J^H W (f - t) and H = J^H W J (abr_lsq_batch / abr_
     of the next step;  mu <- mu / 3 after a step that lowers L, mu <- 4 mu after one that does not (the step is then solved again);
     the first mu is 1e-3 times the Rayleigh quotient <g, H g> / <g, g>.
 refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch / bloch_gn_batch, the Bloch model with relaxation,
-or with solver='device' each step as one bloch_lm_step_batch call.
+or with solver='device' each step as one bloch_lm_step_batch call, or with steady_state=True on bloch_ss_lsq_batch /
+bloch_ss_gn_batch, the steady state of the period.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -172,19 +173,25 @@ def _lm_loop(rfs, infos, lsq, gn, step, iters, mu0):
 
 
 def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
-                       ctx=None):
+                       steady_state=False, ctx=None):
     """refine_batch for bloch_batch's model, relaxation included: the same lock-step Levenberg-Marquardt / CG loop
     on bloch_lsq_batch and bloch_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, of which only b1 changes; df, dp:
     one grid shared by every pulse or a list of one per pulse; targets, weights, scales and m0 (None, one (mx, my, mz), or a list
     of one per pulse) as for bloch_lsq_batch; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch
     does.  solver: 'host' runs the CG recurrence on the host, one bloch_gn_batch call per iteration; 'device' solves and tries each
     step in one bloch_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as a
-    refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    refused step.  steady_state: fit the steady state of the period (bloch_batch's mode 1) instead of the end point, on
+    bloch_ss_lsq_batch and bloch_ss_gn_batch; each pulse is then one period, targets and weights lie as mode 1's outputs
+    do, there is no m0, and the solver is 'host'.  A pulse refined in a batch has the bits of the same pulse refined alone."""
     mb = importlib.import_module(__package__)
     pulses = list(pulses)
     P = len(pulses)
     if P == 0:
         raise ValueError("refine_bloch_batch: no pulses")
+    if steady_state and m0 is not None:
+        raise ValueError("refine_bloch_batch: the steady state does not depend on m0; with steady_state, m0 must be None")
+    if steady_state and solver == "device":
+        raise ValueError("refine_bloch_batch: the steady-state device step is not built; with steady_state, solver must be 'host'")
     targets, weights = list(targets), list(weights)
     if len(targets) != P or len(weights) != P:
         raise ValueError("refine_bloch_batch: %d target and %d weight triples for %d pulses" % (len(targets), len(weights), P))
@@ -203,17 +210,21 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
         return [(b1_of[q],) + rest[q] for q in idx], grid(df, idx), grid(dp, idx)
 
     def kw(idx):
+        if steady_state:
+            return dict(scales=scales, ctx=ctx)
         return dict(scales=scales, m0=[m0[q] for q in idx] if each else m0, ctx=ctx)
 
     def lsq(idx, b1_of):
         for q in idx:
             infos[q]["calls"]["lsq"] += 1
-        return mb.bloch_lsq_batch(*args(idx, b1_of), [targets[q] for q in idx], [weights[q] for q in idx], **kw(idx))
+        fn = mb.bloch_ss_lsq_batch if steady_state else mb.bloch_lsq_batch
+        return fn(*args(idx, b1_of), [targets[q] for q in idx], [weights[q] for q in idx], **kw(idx))
 
     def gn(idx, v_of):
         for q in idx:
             infos[q]["calls"]["gn"] += 1
-        return mb.bloch_gn_batch(*args(idx, b1s), [v_of[q] for q in idx], [weights[q] for q in idx], **kw(idx))
+        fn = mb.bloch_ss_gn_batch if steady_state else mb.bloch_gn_batch
+        return fn(*args(idx, b1s), [v_of[q] for q in idx], [weights[q] for q in idx], **kw(idx))
 
     def lm(idx, grad, mu):
         """the step of every active pulse, solved and tried on the device: (b1 + d, L and g there, whether CG broke down)"""
