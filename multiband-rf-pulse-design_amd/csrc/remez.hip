@@ -1,10 +1,12 @@
 // Batched Parks-McClellan (Remez exchange) on the device for dzlp.m / dzmp.m: real symmetric type I (odd) and type II (even)
 // filters of 3 to 2047 taps, one workgroup of 256 threads per design, the whole exchange inside one launch.  Grid, barycentric
-// solve, exchange and tap recovery are described in DESIGN.md section 8e.  Everything is fp64 and every reduction runs in a fixed
-// order, so a design gives the same bits alone or inside any batch.  LDS: x, gamma, C (3 x 1025 doubles) and small slots; global
-// scratch per design (offset table from the host): f, x, D, W, E (5 G doubles), two index lists (2 G ints), the next extremal
-// set (L + 1 ints) and the cosine table (2 L - 1 doubles).
+// solve, exchange and tap recovery are described in DESIGN.md section 8e.  The exchange is fp64, the tap recovery double-double,
+// and every reduction runs in a fixed order, so a design gives the same bits alone or inside any batch.  LDS: x, gamma, C and, for
+// the tap recovery, the low parts of gamma and C (5 x 1025 doubles) and small slots; global scratch per design (offset table from
+// the host): f, x, D, W, E (5 G doubles), two index lists (2 G ints), the next extremal set (L + 1 ints) and the cosine table
+// (2 L - 1 doubles).
 #include "dev_common.h"
+#include "dd_dev.h"
 #include "pulse.h"
 #include <cstring>
 
@@ -70,6 +72,25 @@ __device__ __forceinline__ double bary(double x, const double* sx, const double*
     return h >= 0 ? sc[h] : num / den;
 }
 
+// The same interpolant with double-double weights (sg, sgl), node values (sc, scl), differences and sums.  For the tap recovery
+// only: where the extremal set leaves a transition band empty the terms cancel, and fp64 weights and sums
+// leave about 1e-14 in the taps, which a weight ratio of 1e4 turns into more than 1e-8 |delta| of the certificate.
+__device__ __forceinline__ double bary_dd(double x, const double* sx, const double* sg, const double* sgl, const double* sc,
+                                          const double* scl, int n1) {
+    dd num = dd_make(0.0), den = dd_make(0.0);
+    int h = -1;
+    for (int k = 0; k < n1; ++k) {
+        const dd d = two_sum(x, -sx[k]);                     // exact
+        h = d.h == 0.0 ? k : h;
+        const dd tg = dd_div(dd_make(sg[k], sgl[k]), d);
+        den = dd_add(den, tg);
+        num = dd_add(num, dd_mul(tg, dd_make(sc[k], scl[k])));
+    }
+    if (h >= 0) return sc[h] + scl[h];
+    const dd q = dd_div(num, den);
+    return q.h + q.l;
+}
+
 // Candidate test of grid point j in pass 1: a local extremum of E inside its band with |E| >= |delta|.
 __device__ __forceinline__ bool is_extremum(const double* E, const int* bstart, int nb_plus1, int j, double adelta) {
     const double e = E[j];
@@ -126,11 +147,13 @@ __device__ int compact(int n, const int* src, int* out, int* sscan, Keep keep) {
 __global__ __launch_bounds__(RZ_THREADS) void k_remez(const RemezJobDev* __restrict__ jobs, const double* __restrict__ bands,
                                                      char* __restrict__ scratch, double* __restrict__ out, double* __restrict__ rec) {
     __shared__ double sx[RZ_LMAX + 1], sg[RZ_LMAX + 1], sc[RZ_LMAX + 1];
+    __shared__ double sgl[RZ_LMAX + 1], scl[RZ_LMAX + 1];    // low parts of gamma and C in the tap recovery (double-double)
     __shared__ int sext[RZ_LMAX + 1];
     __shared__ int sscan[RZ_THREADS + 1];
     __shared__ int sbs[65];                                  // band starts (nband <= 64) and G
     __shared__ double sred[RZ_THREADS / 64 + 17];
     __shared__ double sdd[2 * RZ_THREADS];                   // double-double partial sums of sum gamma D
+    __shared__ double sdd2[2 * RZ_THREADS];                  // and, in the tap recovery, of sum gamma (-1)^k / W
     __shared__ int sflag[4];
 
     const RemezJobDev J = jobs[blockIdx.x];
@@ -262,14 +285,73 @@ __global__ __launch_bounds__(RZ_THREADS) void k_remez(const RemezJobDev* __restr
     }
 
     // ---- taps from P on the cosine grid ----------------------------------------------------------------------
+    // The weights of the last solved set once more in double-double (exact differences, exponent pulled out every 16 factors as
+    // above), then delta and the node values from these weights, for bary_dd.  Delta has to be redone with them: the interpolant
+    // through D - (-1)^k delta / W has degree L - 1 only for the delta of its own weights, and the fp64 delta would leave a
+    // degree-L part of the size of its own error.  The delta reported is the iteration's fp64 one, which the exchange used.
+    {
+        int emax_loc = -100000;
+        int* sex = S.alt;                                    // (the candidate lists are no longer needed)
+        for (int k = tid; k < n1; k += RZ_THREADS) {
+            const double xk = sx[k];
+            dd p = dd_make(1.0);
+            int ex = 0;
+            for (int j0 = 0; j0 < n1; j0 += 16) {
+                const int j1 = min(n1, j0 + 16);
+                for (int j = j0; j < j1; ++j)
+                    if (j != k) { const dd d = two_sum(xk, -sx[j]); p = dd_mul(p, dd_make(2.0 * d.h, 2.0 * d.l)); }
+                int e;
+                p.h = frexp(p.h, &e);
+                p.l = ldexp(p.l, -e);
+                ex += e;
+            }
+            const dd g = dd_div(dd_make(1.0), p);
+            sg[k] = g.h;
+            sgl[k] = g.l;
+            sex[k] = -ex;
+            emax_loc = max(emax_loc, -ex);
+        }
+        const int emax = int(block_max(double(emax_loc), sred));
+        for (int k = tid; k < n1; k += RZ_THREADS) {
+            sg[k] = ldexp(sg[k], sex[k] - emax);
+            sgl[k] = ldexp(sgl[k], sex[k] - emax);
+        }
+        __syncthreads();
+        dd nm = dd_make(0.0), dn = dd_make(0.0);
+        for (int k = tid; k < n1; k += RZ_THREADS) {
+            const int g = sext[k];
+            const dd gk = dd_make(sg[k], sgl[k]);
+            nm = dd_add(nm, dd_mul_d(gk, S.D[g]));
+            const dd q = dd_div(gk, dd_make(S.W[g]));
+            dn = (k & 1) ? dd_sub(dn, q) : dd_add(dn, q);
+        }
+        sdd[tid] = nm.h; sdd[RZ_THREADS + tid] = nm.l;
+        sdd2[tid] = dn.h; sdd2[RZ_THREADS + tid] = dn.l;
+        __syncthreads();
+        if (tid == 0) {                                      // fixed order
+            dd a = dd_make(0.0), b = dd_make(0.0);
+            for (int t = 0; t < RZ_THREADS; ++t) {
+                a = dd_add(a, dd_make(sdd[t], sdd[RZ_THREADS + t]));
+                b = dd_add(b, dd_make(sdd2[t], sdd2[RZ_THREADS + t]));
+            }
+            const dd q = dd_div(a, b);
+            sred[0] = q.h; sred[1] = q.l;
+        }
+        __syncthreads();
+        const dd dl = dd_make(sred[0], sred[1]);
+        for (int k = tid; k < n1; k += RZ_THREADS) {
+            const int g = sext[k];
+            const dd q = dd_div(dl, dd_make(S.W[g]));
+            const dd c = (k & 1) ? dd_add(dd_make(S.D[g]), q) : dd_sub(dd_make(S.D[g]), q);
+            sc[k] = c.h; scl[k] = c.l;
+        }
+        __syncthreads();
+    }
     const int M = 2 * L - 1;
     double* P = S.D;                                         // D and W are no longer needed
     double* a = S.W;
     for (int m = tid; m < M; m += RZ_THREADS) S.cs[m] = cospi(2.0 * double(m) / double(M));
-    for (int j = tid; j < L; j += RZ_THREADS) {
-        int hit;
-        P[j] = bary(cospi(2.0 * double(j) / double(M)), sx, sg, sc, n1, &hit);
-    }
+    for (int j = tid; j < L; j += RZ_THREADS) P[j] = bary_dd(cospi(2.0 * double(j) / double(M)), sx, sg, sgl, sc, scl, n1);
     __syncthreads();
     for (int k = tid; k < L; k += RZ_THREADS) {
         double s = 0.0;

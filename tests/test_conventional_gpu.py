@@ -1,6 +1,5 @@
 """Conventional SLR designers on the device: the batched Parks-McClellan exchange against SciPy's designs and against the
 alternation certificate, fmp against its NumPy restatement, and the dzrf chain (tests/golden/conventional.json)."""
-import importlib.util
 import json
 import os
 
@@ -8,6 +7,7 @@ import numpy as np
 import pytest
 
 import mbfir
+import remez_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -36,50 +36,10 @@ def spec(d):
     return d["numtaps"], d["edges"], d["desired"], d["weight"]
 
 
-# ---- the certificate, on the host restatement of the grid in the fixture generator ------------------------------
-def _generator():
-    path = os.path.join(ROOT, "tests", "golden", "make_golden_conventional.py")
-    sp = importlib.util.spec_from_file_location("make_golden_conventional", path)
-    mod = importlib.util.module_from_spec(sp)
-    sp.loader.exec_module(mod)
-    return mod
-
-
-gold = _generator()
-dense_grid, amplitude = gold.grid, gold.amplitude
-
-
-def weighted_error(h, f, numtaps, edges, desired, weight):
-    """E = W (D - A) at frequencies f (Nyquist units), A from the taps, D / W of the band each f lies in."""
-    f = np.asarray(f, dtype=np.float64)
-    A = amplitude(h, f)
-    D, W = np.zeros(len(f)), np.zeros(len(f))
-    for b in range(len(weight)):
-        lo, hi = edges[2 * b], edges[2 * b + 1]
-        m = (f >= lo) & (f <= hi)
-        D[m] = desired[2 * b] + (desired[2 * b + 1] - desired[2 * b]) * ((f[m] - lo) / (hi - lo) if hi > lo else 0)
-        W[m] = weight[b]
-    return W * (D - A)
-
-
-# The certificate resolves |E| to 1e-8 |delta|.  The taps are rebuilt in fp64 from the interpolant sampled on the cosine grid, and
-# that sampling carries about 1e-13 absolute error where the extremal set leaves gaps (transition bands); weighted by W / delta it
-# reaches 5.8e-9 |delta| on the device for lp519_w300 (W = 300) and the sloped design, 3.0e-9 for a NumPy fp64 restatement of
-# the same algorithm (DESIGN.md section 8e).  Every other fixture stays below 1e-9.
-CERT_TOL = 1e-8
-
-
-def certify(h, info, numtaps, edges, desired, weight, tol=CERT_TOL):
-    """Optimality on the grid, from the taps alone: the L + 1 returned frequencies alternate with |E| = |delta|, and no grid
-    point exceeds |delta|."""
-    L, f, D, W, B = dense_grid(numtaps, edges, desired, weight)
-    ad = abs(info["delta"])
-    Ee = weighted_error(h, info["ext"], numtaps, edges, desired, weight)
-    assert len(Ee) == L + 1
-    assert np.all(np.abs(np.abs(Ee) - ad) <= tol * ad), np.abs(np.abs(Ee) - ad).max() / ad
-    assert np.all(np.sign(Ee[1:]) != np.sign(Ee[:-1]))
-    E = W * (D - amplitude(h, f))
-    assert np.abs(E).max() <= ad * (1 + tol), np.abs(E).max() / ad - 1
+# ---- the certificate (tests/remez_ref.py), on the host restatement of the grid in the fixture generator ---------------
+gold = remez_ref.gold
+dense_grid, amplitude = remez_ref.dense_grid, remez_ref.amplitude
+weighted_error, certify, CERT_TOL = remez_ref.weighted_error, remez_ref.certify, remez_ref.CERT_TOL
 
 
 # ---- remez ----------------------------------------------------------------------------------------------------
