@@ -4,14 +4,15 @@ sample of TR - T after each pulse, T1 = 30 s, T2 = 2 s, 17 points per band, tran
 weighted least squares in (mx, my, mz), which the fused products take as it is: the targets are the designed pulse's own steady state
 at gain 1.0 inside the lactate band, at every gain (so that the excitation does not move with the gain), and (0, 0, 1) in the four
 bands left alone, with unit weights.  Two optimisers run from the designed period on the same loss:
-    mbfir.refine_bloch_batch(steady_state=True): CG on (H + mu I) d = -g with one bloch_ss_gn_batch call per iteration and one
-        bloch_ss_lsq_batch call per trial step;
+    mbfir.refine_bloch_ss_batch: CG on (H + mu I) d = -g with one bloch_ss_gn_batch call per iteration and one bloch_ss_lsq_batch
+        call per trial step (--solver host, the default), or every step solved and tried in one bloch_ss_lm_step_batch call
+        (--solver device: the same losses to the printed digits in a fraction of the device calls);
     torch.optim.LBFGS with a strong-Wolfe line search, its closure one bloch_ss_lsq_batch call.
 Both move every sample of the period: the two halves are not tied to b and -b and the dead-time samples are free, which the report
 shows (a tied design takes the chain rule g_b = g[first half] - g[second half] instead, as bssfp_steady_refine.py's autograd does).
 Prints the losses, the worst in-band ranges per band and gain, and the device calls each optimiser made.  No plots.
 
-    python examples/bssfp_steady_lm.py [--iters 6] [--cg 8] [--steps 20] [--tr 6.0] [--t1 30] [--t2 2]
+    python examples/bssfp_steady_lm.py [--iters 6] [--cg 8] [--steps 20] [--tr 6.0] [--t1 30] [--t2 2] [--solver host]
 """
 import argparse
 import os
@@ -30,6 +31,7 @@ ap.add_argument("--steps", type=int, default=20, help="L-BFGS iterations")
 ap.add_argument("--tr", type=float, default=6.0, help="ms")
 ap.add_argument("--t1", type=float, default=30.0, help="s")
 ap.add_argument("--t2", type=float, default=2.0, help="s")
+ap.add_argument("--solver", choices=("host", "device"), default="host", help="where the Levenberg-Marquardt step is solved")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -95,8 +97,8 @@ print("steady state of %d samples (%.2f ms) in TR %.2f ms, T1 %.0f s, T2 %.1f s,
       " designed steady state at gain 1.0 in %s, (0, 0, 1) elsewhere" % (nrf, nrf * dt, args.tr, args.t1, args.t2, K, names[sel]))
 report("designed", period0)
 
-(b_lm,), (info,) = mbfir.refine_bloch_batch([(period0,) + rest], df, 0.0, [target], [weight], scales=scales, iters=args.iters, cg=args.cg,
-                                            steady_state=True)
+(b_lm,), (info,) = mbfir.refine_bloch_ss_batch([(period0,) + rest], df, 0.0, [target], [weight], scales=scales, iters=args.iters,
+                                               cg=args.cg, solver=args.solver)
 print("Levenberg-Marquardt: losses %s; status %s, %d refused, last mu %.3g; device calls %s"
       % (" ".join("%.6g" % v for v in info["losses"]), info["status"], info["refused"], info["mu"], info["calls"]))
 report("Levenberg-Marquardt, %d steps" % (len(info["losses"]) - 1), b_lm)

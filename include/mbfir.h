@@ -603,6 +603,29 @@ int mbfir_bloch_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, cons
                               const double* mu, int cg, double rtol, const double* tx, const double* ty, const double* tz,
                               double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
                               double* g_im);
+/* mbfir_bloch_ss_lm_step_batch: the step above for the steady state of the period (mbfir_bloch_batch's mode 1): conjugate gradients
+ * on (H + mu[p] I) d = b from d = 0, H = sum_s s J_s' W_s J_s (s .) as in mbfir_bloch_ss_gn_batch at the call's b1, weights and
+ * scales, at most cg iterations, while <r, r> > rtol <b, b>.  The arguments up to wx, wy, wz are those of mbfir_bloch_ss_gn_batch
+ * (there is no m0); b_re, b_im are laid out as b1 is.  With tx, ty, tz the loss and gradient of mbfir_bloch_ss_lsq_batch at b1 + d
+ * (one IEEE addition per part) are returned too, with that call's bits; all three NULL: solve only, and loss, g_re, g_im may be
+ * NULL.  Outputs per pulse as for mbfir_bloch_lm_step_batch: d, ncg, rr, gg, status (0: the tolerance was reached, 1: the cap cg
+ * was reached, 2: breakdown).  H p has the bits of mbfir_bloch_ss_gn_batch on the same p.  b1 is fixed within the solve, so
+ * (I - A)^-1 and M of a pulse are computed once per call, not once per iteration.  One upload, a chain of launches (one, then two
+ * per CG iteration), one download; the host reads nothing in between, so cg is also a launch count.  The partials and the
+ * checkpoints of one direction serve every iteration and the trial; they, r, H p, (I - A)^-1, M and the trial's input rows stay
+ * on the device.  No guard on det(I - A).  A pulse's outputs depend only on the pulse, its grids, weights, targets, b, mu, cg, rtol
+ * and the scale list: not on the batch, its order, or when its neighbours stop.  The checks are those of mbfir_bloch_batch at mode
+ * 1 and of mbfir_bloch_ss_gn_batch at ndir = 1 in their order and with their messages, then: b, mu or a required output NULL ("a
+ * required array is null"); tx, ty, tz only partly given; a negative or non-finite mu; cg < 0; a negative or NaN rtol; sections,
+ * planes or a workgroup count that overflow.  No device work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                 const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                 const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                 const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                 const double* dz, int nscale, const double* scales, const double* wx, const double* wy,
+                                 const double* wz, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                                 const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
+                                 double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

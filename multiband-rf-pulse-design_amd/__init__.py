@@ -156,6 +156,9 @@ SYMBOLS = {
     "mbfir_bloch_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                             _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 9 + [C.c_int, C.c_double] +
                                            [_dp] * 5 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "mbfir_bloch_ss_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 6 + [C.c_int, C.c_double] +
+                                              [_dp] * 5 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -2201,7 +2204,35 @@ def bloch_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8,
     return _lm_result(rfs, out)
 
 
-from .refine import refine_batch, refine_bloch_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
+def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), ctx=None):
+    """bloch_lm_step_batch for the steady state of the period, bloch_batch's mode 1 (mbfir_bloch_ss_lm_step_batch, DESIGN section
+    8v): conjugate gradients on (H + mu I) d = rhs from d = 0, H = sum_s s J_s' W_s J_s (s .) as bloch_ss_gn_batch applies it, solved
+    on the device in one call.  pulses (each one period), df, dp, weights and scales as for bloch_ss_gn_batch; rhs: per pulse a
+    complex (n,) array; mu: a number >= 0 or one per pulse; cg and rtol as for abr_lm_step_batch.  With targets (as for
+    bloch_ss_lsq_batch) the loss and gradient at b1 + d come back too, with the bits of bloch_ss_lsq_batch there.  Returns a list of
+    (d, info) per pulse: info holds 'ncg', 'rr', 'gg' and 'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.
+    There is no m0.  b1 is fixed within the solve, so (I - A)^-1 and the steady state are computed once per call.  The host reads
+    nothing between the iterations, so cg is also a launch count.  Deterministic: a pulse's results depend only on the pulse, its
+    grids, weights, targets, rhs, mu, cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    who = "bloch_ss_lm_step_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    rfs = [range(n) for n in A.nt]
+    bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
+    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    t = [None] * 3 if targets is None else _bloch_planes(who, "target", targets, A)
+    P, T = A.P, sum(A.nt)
+    out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
+    out += [None, None, None] if targets is None else [np.zeros(P), np.zeros(T), np.zeros(T)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_lm_step_batch(ctx._h, *A.head, *[_ptr(v) for v in w + bplanes], _ptr(m), cg, C.c_double(rtol),
+                                                     *[_plane(v) for v in t + out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _lm_result(rfs, out)
+
+
+from .refine import refine_batch, refine_bloch_batch, refine_bloch_ss_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

@@ -1712,6 +1712,39 @@ int mbfir_bloch_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, cons
                                            g_im));
 }
 
+// The steady state's step (blochssgn.hip): mbfir_bloch_batch's checks at mode 1, bloch_gn_check's at ndir = 1 (no m0),
+// bloch_lm_check's, and one plane of (I - A)^-1 and M (12 x 256 doubles) per forward workgroup.
+int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                 const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                 const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                 const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                 const double* dz, int nscale, const double* scales, const double* wx, const double* wy,
+                                 const double* wz, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                                 const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
+                                 double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_lm_step_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        1, arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, "bloch_ss_lm_step_batch", wx && wy && wz, "a weight, direction or product plane is null",
+                                     nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
+        return e;
+    const bool targets = tx || ty || tz;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
+    if (const int e = bloch_lm_check(ctx, "bloch_ss_lm_step_batch", own, !targets || (tx && ty && tz), npulse, toff, mu, cg, rtol))
+        return e;
+    long nblk = 0;                                              // bloch_gn_check has bounded it by 2^31 - 1
+    for (int p = 0; p < npulse; ++p) nblk += (npoint[p] + 255) / 256 * nscale;
+    if (nblk > (1L << 56) / 3072) return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                              t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz,
+                                              b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
+                                              g_im));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 int mbfir_test_bloch_jvp_group(void) { return bloch_jvp_group(); }
 

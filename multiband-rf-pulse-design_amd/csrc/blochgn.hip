@@ -387,6 +387,17 @@ void bloch_gn_fold_launch(hipStream_t st, long nfold, const double2* part, const
     hipLaunchKernelGGL(k_bloch_gn_fold, dim3((unsigned)nfold), dim3(256), 0, st, part, vp, blocks, scales, nscale, in, pulses, out, lpart,
                        lp, loss);
 }
+// Launch k_bloch_lm_step on npulse workgroups and k_bloch_lm_trial on the T samples: the steady state's step (blochssgn.hip) folds
+// the same partials and tries the same rows.
+void bloch_lm_step_launch(hipStream_t st, int npulse, const double2* part, const VjpPulseDev* vp, const double* scales, int nscale,
+                          const double* in, const BlochPulseDev* pulses, int cg, double rtol, double2* p, double2* d, double2* r,
+                          double2* hp, LmState* state) {
+    hipLaunchKernelGGL(k_bloch_lm_step, dim3((unsigned)npulse), dim3(256), 0, st, part, vp, scales, nscale, in, pulses, cg, rtol, p, d, r,
+                       hp, state);
+}
+void bloch_lm_trial_launch(hipStream_t st, const double* in, const double2* d, long T, double* trial) {
+    hipLaunchKernelGGL(k_bloch_lm_trial, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, in, d, T, trial);
+}
 namespace {
 // k_bloch_lsq_batch on the input rows `in` (the staged ones, or a trial's) and the fold into grad and loss.
 void bloch_lsq_launch(BlochStaged& B, const BlochGnSections& G, int nscale, const double* in, double2* part, double* cks,

@@ -18,6 +18,8 @@
 // and H v through the fold's factor, and its loss (M = [0 0 1]) is counted.  No guard on det(I - A).
 // LDS: the staged rows (16 KB) and the reduction tile (34 KB).  The staged (dnx, dny) row of gn is live only in the forward sweep
 // and the tile only after it, so the row lies in the tile's storage.
+// The Levenberg-Marquardt step solved on the device with these products (k_bloch_ss_lm_prep, k_bloch_ss_lm_sweep and
+// the host side of mbfir_bloch_ss_lm_step_batch) follows the two kernels.
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
@@ -243,6 +245,121 @@ __global__ __launch_bounds__(256) void k_bloch_ss_gn_batch(const double* __restr
 }
 
 // ------------------------------------------------------------------------------------------------
+// The Levenberg-Marquardt step of the steady state on the device, the twin of blochgn.hip's: conjugate
+// gradients on (H + mu I) d = b per pulse, H p by the sweep of k_bloch_ss_gn_batch on the device's own p, everything else of an
+// iteration in k_bloch_lm_step (blochgn.hip, unchanged); then, with targets, the loss and gradient at b1 + d by
+// k_bloch_ss_lsq_batch on the trial's input rows.  b1 is fixed within one solve, so pass 0 runs once per call, in
+// k_bloch_ss_lm_prep, and every round reads its (I - A)^-1 and M back as the doubles they are.  Stages depend on each other
+// through launch order alone.
+constexpr int BLOCH_SSLM_PLANE = BLOCH_SSINV + 3 * 256;      // doubles per forward workgroup: (I - A)^-1 as sinv holds it, then M
+
+// Pass 0 of the pulses that run: the forward call's block table.  A thread writes its inv to the columns 0 .. 8 of its
+// workgroup's plane, as k_bloch_ss_gn_batch writes sinv, and its M to the columns 9 .. 11; k_bloch_ss_lm_sweep's thread of the same
+// workgroup and index reads them back, nobody else.
+__global__ __launch_bounds__(256) void k_bloch_ss_lm_prep(const double* __restrict__ in, const double* __restrict__ df,
+                                                          const double* __restrict__ pos3, const double* __restrict__ scales,
+                                                          const BlochPulseDev* __restrict__ pulses,
+                                                          const SimBlock* __restrict__ blocks, const LmState* __restrict__ st,
+                                                          double* __restrict__ plane) {
+    __shared__ double sst[BLOCH_CH][8];
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    const BlochPulseDev P = pulses[bk.pulse];
+    const BlochSsPoint G = bloch_ss_point(bk, P, df, pos3);
+    double* wpl = plane + (long)blockIdx.x * BLOCH_SSLM_PLANE + threadIdx.x;
+    double inv[9], m[3];
+    bloch_ss_pass0(sst, in, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, inv, m);
+    for (int e = 0; e < 9; ++e) wpl[e * 256] = inv[e];
+    for (int e = 0; e < 3; ++e) wpl[(9 + e) * 256] = m[e];
+}
+
+// k_bloch_ss_gn_batch at ndir = 1 for the pulses that still run, pass 0 taken from k_bloch_ss_lm_prep's plane: the forward call's
+// block table, the direction the device's p (laid out as b1 is).  The forward loop stages every tile itself, as the shipped one
+// does; the loop, the cotangent and the reverse sweep are the shipped kernel's statements.
+__global__ __launch_bounds__(256) void k_bloch_ss_lm_sweep(const double* __restrict__ in, const double* __restrict__ df,
+                                                           const double* __restrict__ pos3, const double* __restrict__ scales,
+                                                           const BlochPulseDev* __restrict__ pulses,
+                                                           const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp,
+                                                           const BlochCkDev* __restrict__ cks, const double* __restrict__ w, long O,
+                                                           const double2* __restrict__ v, const LmState* __restrict__ st,
+                                                           double2* __restrict__ part, double* ck,
+                                                           const double* __restrict__ plane) {
+    __shared__ double sst[BLOCH_CH][8];
+    __shared__ __align__(16) double red[2 * VJP_T * VJP_ROW];
+    static_assert(BLOCH_CH % VJP_T == 0, "a group of samples lies within one staged tile");
+    static_assert(sizeof(double2) * BLOCH_CH <= sizeof(double) * 2 * VJP_T * VJP_ROW, "the direction row fits in the tile");
+    double2* sdn = reinterpret_cast<double2*>(red);                   // (dnx, dny) of the staged rows: forward sweep only
+    const int tid = threadIdx.x;
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    const BlochPulseDev P = pulses[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    const double sc = scales[bk.scale], gamma = P.gamma;
+    const int ntime = P.ntime;
+    const BlochSsPoint G = bloch_ss_point(bk, P, df, pos3);
+    const double px = G.px, py = G.py, pz = G.pz, dfv = G.dfv;
+    const bool live = G.live;
+    const long wg = (long)bk.scale * V.nch + bk.chunk;
+    const double2* vd = v + P.t_off;
+    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
+    const double* wpl = plane + (long)blockIdx.x * BLOCH_SSLM_PLANE + tid;
+    double m[3], dm[3] = {0, 0, 0};
+    for (int e = 0; e < 3; ++e) m[e] = wpl[(9 + e) * 256];               // M of pass 0, written by this thread of the prep launch
+    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
+        __syncthreads();
+        const int cnt = min(BLOCH_CH, ntime - t0);
+        if (tid < cnt) {
+            const double* s = in + BLOCH_IN * (P.t_off + t0 + tid);
+            const double dt = s[8];
+            sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                  // rotx of the pulse b1 s, as k_bloch_batch forms it
+            sst[tid][1] = ((s[1] * sc) * gamma) * dt;                     // roty
+            for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
+            const double2 d = vd[t0 + tid];
+            sdn[tid] = make_double2(((-(d.x * sc)) * gamma) * dt, ((d.y * sc) * gamma) * dt);      // as k_bloch_jvp_batch stages it
+        }
+        __syncthreads();
+        for (int q = 0; q < cnt; ++q) {
+            if ((q & (VJP_T - 1)) == 0) {                                 // m before sample t0 + q: the group's checkpoint
+                double* c = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
+                c[0] = m[0]; c[256] = m[1]; c[512] = m[2];
+            }
+            const double* s = sst[q];
+            const double rotz = bloch_rotz(s, px, py, pz, dfv);
+            Rot3 R;
+            BlochTrig tr;
+            bloch_rotmat_trig<true>(s[0], s[1], rotz, R, tr);
+            const double e1 = s[6], e2 = s[7];
+            BlochJvpShared W;
+            bloch_jvp_shared(s[0], s[1], rotz, tr, m, W);
+            const double2 dn = sdn[q];
+            const double nd = s[0] * dn.x + s[1] * dn.y;
+            double o[3];
+            rot_vec(R, dm, o);
+            dm[0] = e2 * (o[0] + (nd * W.U[0] + dn.x * W.Vx[0] + dn.y * W.Vy[0]));
+            dm[1] = e2 * (o[1] + (nd * W.U[1] + dn.x * W.Vx[1] + dn.y * W.Vy[1]));
+            dm[2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
+            rot_vec(R, m, o);
+            m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
+        }
+    }
+    double l[3];
+    {
+        double inv[9], wv[3] = {0, 0, 0};
+        for (int e = 0; e < 9; ++e) inv[e] = wpl[e * 256];
+        if (live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
+        double c[3];
+        for (int i = 0; i < 3; ++i) {
+            const double d = inv[i] * dm[0] + inv[3 + i] * dm[1] + inv[6 + i] * dm[2];      // dM = inv d
+            c[i] = live ? wv[i] * d : 0.0;
+        }
+        for (int j = 0; j < 3; ++j) l[j] = inv[3 * j] * c[0] + inv[3 * j + 1] * c[1] + inv[3 * j + 2] * c[2];      // lambda = inv' c
+    }
+    __syncthreads();                                                      // the direction row is read no more: the tile is free
+    bloch_ss_reverse(sst, red, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, live, l, part + V.p_off + wg * V.n, wck);
+}
+
+// ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_ss_lsq_batch / mbfir_bloch_ss_gn_batch (arguments checked by api.cpp): the forward call's staging
 // (bloch_stage at mode 1, no m0) plus the sections of bloch_gn_stage; one upload, two launches, one download of the ndir T results
 // (and the npulse losses, and M when it is wanted).  The output region is the results (ndir T double2), the losses (padded to a
@@ -327,6 +444,91 @@ void bloch_ss_gn_batch_run(int device, void* stream, int npulse, const long* tof
     const double* const w[3] = {wx, wy, wz};
     bloch_ss_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid,
                     poff, dx, dy, dz, nscale, scales, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im, nullptr, nullptr, nullptr);
+}
+
+// Host side of mbfir_bloch_ss_lm_step_batch (arguments checked by api.cpp): the forward staging at mode 1 and bloch_gn_stage at
+// ndir = 1 with b as the direction section, which is the device's p from then on; mu; one upload; k_lm_init, k_bloch_ss_lm_prep, cg
+// rounds of (k_bloch_ss_lm_sweep, k_bloch_lm_step), and with targets k_bloch_lm_trial, k_bloch_ss_lsq_batch on the trial rows (its
+// pass 0 is at b1 + d and its own) and the fold; one download.  The output region:
+//   d (T double2), the npulse states, [the gradient at b1 + d (T double2), the npulse losses]                      downloaded
+//   r, hp (T double2 each), the trial rows (9 T doubles), the partials, the loss partials, the checkpoints, the planes   stay on the device
+// The partials and the checkpoints are those of one direction, reused by every round and by the trial's lsq sweep.
+void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const double* wx, const double* wy, const double* wz,
+                                const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* tx,
+                                const double* ty, const double* tz, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                                int* status, double* loss, double* g_re, double* g_im) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const bool trial = tx != nullptr;
+    const double* const w[3] = {wx, wy, wz};
+    const double* const tg[3] = {tx, ty, tz};
+    BlochStaged B;
+    bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                nscale, scales, 1, nullptr, nullptr, nullptr);
+    Staging& S = B.S;
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im);
+    const size_t o_mu = S.add((size_t)npulse * 8);
+    std::copy(mu, mu + npulse, S.at<double>(o_mu));
+    const long T = toff[npulse];
+    auto pad16 = [](size_t b) { return (b + 15) & ~size_t(15); };
+    const size_t b_vec = (size_t)T * 16, b_st = pad16(npulse * sizeof(LmState)), b_loss = pad16((size_t)npulse * 8);
+    const size_t b_down = b_vec + b_st + (trial ? b_vec + b_loss : 0), b_rows = pad16((size_t)T * BLOCH_IN * 8);
+    S.upload(b_down + 2 * b_vec + b_rows + (size_t)G.npart * 16 +
+                 ((size_t)G.nlp + G.nck + (size_t)S.nblk * BLOCH_SSLM_PLANE) * 8,
+             st);
+    char* out = S.dev<char>(S.o_out);
+    double2* d = reinterpret_cast<double2*>(out);
+    LmState* state = reinterpret_cast<LmState*>(out + b_vec);
+    double2* grad = reinterpret_cast<double2*>(out + b_vec + b_st);
+    double* dloss = reinterpret_cast<double*>(out + 2 * b_vec + b_st);
+    double2* r = reinterpret_cast<double2*>(out + b_down);
+    double2* hp = r + T;
+    double* rows = reinterpret_cast<double*>(hp + T);
+    double2* part = reinterpret_cast<double2*>(reinterpret_cast<char*>(rows) + b_rows);
+    double* lpart = reinterpret_cast<double*>(part + G.npart);
+    double* cks = lpart + G.nlp;
+    double* plane = cks + G.nck;
+    double2* p = S.dev<double2>(G.o_v);
+    const VjpPulseDev* vp = S.dev<const VjpPulseDev>(G.o_vp);
+    const double* in = S.dev<const double>(B.o_in);
+    lm_init_launch(st, npulse, vp, S.dev<const double>(o_mu), cg, rtol, p, d, r, state);
+    hipLaunchKernelGGL(k_bloch_ss_lm_prep, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+                       S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const SimBlock>(S.o_bk), state, plane);      // cg = 0: no pulse runs, every workgroup returns at once
+    for (int k = 0; k < cg; ++k) {                                // rounds of a pulse that has stopped are early exits
+        hipLaunchKernelGGL(k_bloch_ss_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+                           S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                           S.dev<const SimBlock>(G.o_jb), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(G.o_w), B.O, p,
+                           state, part, cks, plane);
+        bloch_lm_step_launch(st, npulse, part, vp, S.dev<const double>(S.o_sc), nscale, in, S.dev<const BlochPulseDev>(S.o_pd), cg,
+                             rtol, p, d, r, hp, state);
+    }
+    if (trial) {
+        bloch_lm_trial_launch(st, in, d, T, rows);
+        hipLaunchKernelGGL(k_bloch_ss_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, rows, S.dev<const double>(B.o_df),
+                           S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
+                           S.dev<const SimBlock>(S.o_bk), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const long>(G.o_lp),
+                           S.dev<const double>(G.o_w), S.dev<const double>(G.o_t), B.O, part, cks, lpart, nullptr, nullptr, nullptr);
+        bloch_gn_fold_launch(st, G.nfold, part, vp, S.dev<const SimBlock>(G.o_fb), S.dev<const double>(S.o_sc), nscale, rows,
+                             S.dev<const BlochPulseDev>(S.o_pd), grad, lpart, S.dev<const long>(G.o_lp), dloss);
+    }
+    std::vector<char> h(b_down);
+    S.download(h.data(), b_down, st);
+    unpack_cplx(T, reinterpret_cast<const double2*>(h.data()), d_re, d_im);
+    const LmState* hs = reinterpret_cast<const LmState*>(h.data() + b_vec);
+    for (int q = 0; q < npulse; ++q) {
+        rr[q] = hs[q].rr; gg[q] = hs[q].gg;
+        ncg[q] = hs[q].ncg; status[q] = hs[q].status;
+    }
+    if (trial) {
+        unpack_cplx(T, reinterpret_cast<const double2*>(h.data() + b_vec + b_st), g_re, g_im);
+        std::copy(reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st),
+                  reinterpret_cast<const double*>(h.data() + 2 * b_vec + b_st) + npulse, loss);
+    }
 }
 
 }  // namespace mbfir

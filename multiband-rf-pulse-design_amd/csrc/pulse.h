@@ -203,6 +203,18 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
                              const double* wy, const double* wz, const double* b_re, const double* b_im, const double* mu, int cg,
                              double rtol, const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
                              double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im);
+// The Levenberg-Marquardt step of the steady state on the device (blochssgn.hip k_bloch_ss_lm_prep, k_bloch_ss_lm_sweep with
+// blochgn.hip's k_bloch_lm_step, k_bloch_lm_trial and simgn.hip's k_lm_init): CG on (H + mu I) d = b per pulse, H as
+// bloch_ss_gn_batch_run applies it, and, with tx / ty / tz, the loss and gradient of bloch_ss_lsq_batch_run at b1 + d (loss, g_re,
+// g_im may be null without them).  No m0.
+void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const double* wx, const double* wy, const double* wz,
+                                const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* tx,
+                                const double* ty, const double* tz, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
+                                int* status, double* loss, double* g_re, double* g_im);
 // What mbfir_test_flip_stages adds to a search (include/mbfir.h says what each block holds): the overrides, the selected candidates
 // and the host blocks the search's per-workgroup bests, the report and the stages go to (interleaved re, im where complex).
 struct FlipStages {

@@ -647,6 +647,12 @@ __device__ __forceinline__ bool lm_goes_on(int ncg, int cg, double rr, double rt
 // Launches k_lm_init (simgn.hip) on npulse workgroups: p holds b; d = 0, r = b, rr = gg = <b, b> and the first run flag.
 void lm_init_launch(hipStream_t st, int npulse, const VjpPulseDev* vp, const double* mu, int cg, double rtol, const double2* p,
                     double2* d, double2* r, LmState* state);
+// Launch k_bloch_lm_step (blochgn.hip) on npulse workgroups, one CG iteration of every running pulse from the partials of its sweep,
+// and k_bloch_lm_trial on the T samples, the input rows at b1 + d; arguments as the kernels take them.
+void bloch_lm_step_launch(hipStream_t st, int npulse, const double2* part, const VjpPulseDev* vp, const double* scales, int nscale,
+                          const double* in, const BlochPulseDev* pulses, int cg, double rtol, double2* p, double2* d, double2* r,
+                          double2* hp, LmState* state);
+void bloch_lm_trial_launch(hipStream_t st, const double* in, const double2* d, long T, double* trial);
 
 // The adjoint's sections of one call (simgrad.hip, simgradg.hip): the cotangents, the partial descriptors and the fold kernel's table.
 struct VjpSections {

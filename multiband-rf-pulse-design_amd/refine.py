@@ -7,7 +7,8 @@ L = 1/2 sum w |f - t|^2, g = J^H W (f - t) and H = J^H W J (abr_lsq_batch / abr_
     the first mu is 1e-3 times the Rayleigh quotient <g, H g> / <g, g>.
 refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch / bloch_gn_batch, the Bloch model with relaxation,
 or with solver='device' each step as one bloch_lm_step_batch call, or with steady_state=True on bloch_ss_lsq_batch /
-bloch_ss_gn_batch, the steady state of the period.
+bloch_ss_gn_batch, the steady state of the period; refine_bloch_ss_batch is that loop with both solvers, the device one
+taking each step as one bloch_ss_lm_step_batch call.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -182,23 +183,45 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
     step in one bloch_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as a
     refused step.  steady_state: fit the steady state of the period (bloch_batch's mode 1) instead of the end point, on
     bloch_ss_lsq_batch and bloch_ss_gn_batch; each pulse is then one period, targets and weights lie as mode 1's outputs
-    do, there is no m0, and the solver is 'host'.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    do, there is no m0, and the solver is 'host' (refine_bloch_ss_batch has both solvers).  A pulse refined in a batch has the bits
+    of the same pulse refined alone."""
+    return _refine_bloch("refine_bloch_batch", False, pulses, df, dp, targets, weights, scales, m0, iters, cg, mu0, rtol, solver,
+                         steady_state, ctx)
+
+
+def refine_bloch_ss_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
+                          ctx=None):
+    """refine_bloch_batch(steady_state=True) with both solvers: the lock-step Levenberg-Marquardt / CG loop on the
+    steady state of the period, bloch_batch's mode 1.  pulses: (b1, gr, tp, t1, t2, nucleus) each, one period, of which only b1
+    changes; df, dp, targets, weights and scales as for bloch_ss_lsq_batch; iters, cg, mu0 and rtol as for refine_batch; there is no
+    m0.  Returns (b1s, infos) as refine_batch does.  solver: 'host' runs the CG recurrence on the host, one bloch_ss_gn_batch call
+    per iteration, and returns the bits and the 'calls' of refine_bloch_batch(steady_state=True); 'device' solves and tries each
+    step in one bloch_ss_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as
+    a refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    return _refine_bloch("refine_bloch_ss_batch", True, pulses, df, dp, targets, weights, scales, None, iters, cg, mu0, rtol, solver,
+                         True, ctx)
+
+
+def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, iters, cg, mu0, rtol, solver, steady_state, ctx):
+    """The body of refine_bloch_batch and refine_bloch_ss_batch; who: the entry point, for the messages; ss_device: whether the
+    steady state's device step may be taken."""
     mb = importlib.import_module(__package__)
     pulses = list(pulses)
     P = len(pulses)
     if P == 0:
-        raise ValueError("refine_bloch_batch: no pulses")
+        raise ValueError("%s: no pulses" % who)
     if steady_state and m0 is not None:
-        raise ValueError("refine_bloch_batch: the steady state does not depend on m0; with steady_state, m0 must be None")
-    if steady_state and solver == "device":
-        raise ValueError("refine_bloch_batch: the steady-state device step is not built; with steady_state, solver must be 'host'")
+        raise ValueError("%s: the steady state does not depend on m0; with steady_state, m0 must be None" % who)
+    if steady_state and solver == "device" and not ss_device:
+        raise ValueError("%s: the steady-state device step is not built into this entry point; call refine_bloch_ss_batch(..., "
+                         "solver='device')" % who)
     targets, weights = list(targets), list(weights)
     if len(targets) != P or len(weights) != P:
-        raise ValueError("refine_bloch_batch: %d target and %d weight triples for %d pulses" % (len(targets), len(weights), P))
+        raise ValueError("%s: %d target and %d weight triples for %d pulses" % (who, len(targets), len(weights), P))
     if iters < 0 or cg < 1:
-        raise ValueError("refine_bloch_batch: iters must be at least 0 and cg at least 1")
+        raise ValueError("%s: iters must be at least 0 and cg at least 1" % who)
     if solver not in ("host", "device"):
-        raise ValueError("refine_bloch_batch: solver must be 'host' or 'device', not %r" % (solver,))
+        raise ValueError("%s: solver must be 'host' or 'device', not %r" % (who, solver))
     rest = [tuple(p[1:]) for p in pulses]
     b1s = [np.array(p[0], dtype=np.complex128).ravel() for p in pulses]
     each = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
@@ -230,8 +253,9 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
         """the step of every active pulse, solved and tried on the device: (b1 + d, L and g there, whether CG broke down)"""
         for q in idx:
             infos[q]["calls"]["lm"] += 1
-        res = mb.bloch_lm_step_batch(*args(idx, b1s), [-grad[q] for q in idx], [weights[q] for q in idx], [mu[q] for q in idx],
-                                     targets=[targets[q] for q in idx], cg=cg, rtol=rtol, **kw(idx))
+        fn = mb.bloch_ss_lm_step_batch if steady_state else mb.bloch_lm_step_batch
+        res = fn(*args(idx, b1s), [-grad[q] for q in idx], [weights[q] for q in idx], [mu[q] for q in idx],
+                 targets=[targets[q] for q in idx], cg=cg, rtol=rtol, **kw(idx))
         return [(b1s[q] + d, i["loss"], i["grad"], i["status"] == "breakdown") for q, (d, i) in zip(idx, res)]
 
     def step(idx, grad, mu):
