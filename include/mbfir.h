@@ -379,6 +379,28 @@ int mbfir_bloch_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                           const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                           const double* m0x, const double* m0y, const double* m0z, const double* cmx, const double* cmy,
                           const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y, double* gm0z);
+/* ---- Adjoint of mbfir_bloch_batch with respect to b1, the initial magnetisation, the gradient waveform and the off-resonance -------
+ * mbfir_bloch_vjp_batch with four more outputs after its own arguments:
+ *   ggx / ggy / ggz: one entry per sample of every pulse, laid out as gx / gy / gz: dL/dgx, dL/dgy, dL/dgz.  The axis component of
+ *     a sample's rotation at a point is -((gx x + gy y + gz z) gamma dt + df TWOPI dt), so a sample's entry is -(gamma dt) times the
+ *     sum over the points of its pulse of the point's coordinate times dL/d(that component), summed over the scales without a factor
+ *     (a scale multiplies b1, not the gradient).  All three are required; a NULL input plane gx / gy / gz (an axis no pulse plays) is
+ *     differentiated at zero and its gradient is returned all the same: it is zero only where the positions lack that axis too.
+ *   gdf: dL/ddf of every (scale, frequency, position) in the layout of gm0x, -sum_t (TWOPI dt_t) dL/d(axis component); the caller
+ *     sums over whatever shares an off-resonance.  NULL = not wanted: it is then neither formed nor downloaded.
+ * g_re / g_im and gm0x / gm0y / gm0z are those of mbfir_bloch_vjp_batch to rounding (the sums run over other sub-groups of the same
+ * order), not promised to the bit.  tp, t1, t2, the positions and the scales are not differentiated.  The checkpoints, the launch
+ * shape and the staging are mbfir_bloch_vjp_batch's; one upload, two launches (the sweeps with one partial per workgroup, sample and
+ * component; then the sum of a pulse's partials over chunks and scales in index order, times gamma dt), one download; no atomics,
+ * so the bits of every result depend only on the pulse, its grids, its cotangents and the scale list.  Argument checks and
+ * MBFIR_E_ARG messages as mbfir_bloch_vjp_batch's, and one more case: a NULL ggx, ggy or ggz.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
+                             const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
+                             double* gm0z, double* ggx, double* ggy, double* ggz, double* gdf);
 /* ---- Tangent of mbfir_bloch_batch with respect to the b1 samples and the initial magnetisation -----------------------------------
  * The Jacobian-vector product of the end point (mode 0) of mbfir_bloch_batch, relaxation included: the forward call's input
  * arguments up to nscale and scales (no mode), then

@@ -137,6 +137,8 @@ SYMBOLS = {
                                        _dp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_bloch_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 11),
+    "mbfir_bloch_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                           _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 15),
     "mbfir_bloch_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp,
                                         C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 3 + [C.c_int] + [_dp] * 11),
     "mbfir_test_bloch_jvp_group": (C.c_int, []),
@@ -1451,6 +1453,45 @@ def bloch_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=Fals
     if not grad_m0:
         return res
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
+
+
+def bloch_vjp_gr_batch(pulses, df, dp, cot, *, scales=(1.0,), m0=None, grad_m0=False, grad_df=False, ctx=None):
+    """The adjoint of bloch_batch's end point (mode 0) with respect to b1, the gradient waveform gr and, on request, the initial
+    magnetisation and the off-resonance df, relaxation included (mbfir_bloch_vjp_gr_batch): arguments as
+    bloch_vjp_batch.  Returns one (grad_b1, grad_gr) per pulse: grad_b1 as bloch_vjp_batch returns it (equal to rounding, not
+    promised to the bit), and grad_gr real of shape (ntime, 3), column a = dL/dg_a in the units of gr, summed over the points and
+    over the scales without a factor (a scale multiplies b1, not gr); a column whose axis the pulse does not play is the derivative
+    at a zero gradient, and is zero only where the positions lack that axis too.  With grad_m0 and / or grad_df further members
+    follow in that order: (gmx, gmy, gmz) as bloch_vjp_batch returns it, and grad_df of shape (S, nf, npos), dL/ddf per scale,
+    frequency and position: the caller sums over whatever shares an off-resonance.  Deterministic: the bits of every result depend
+    only on the pulse, its grids, its cotangents and the scales.  tp, t1, t2, dp and the scales are not differentiated."""
+    A = _BlochArgs("bloch_vjp_gr_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    cm = _bloch_cotangents("bloch_vjp_gr_batch", cot, A)
+    ooff, toff = _offsets([S * f * k for f, k in zip(nf, npos)]), _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    m0p = [nul] * 3 if m0 is None else A.m0_planes(m0, ooff, [1] * P)
+    grad = [np.zeros(int(toff[-1])) for _ in range(5)]                  # Re, Im of b1; gx, gy, gz
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    gd = np.zeros(int(ooff[-1])) if grad_df else nul
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_vjp_gr_batch(ctx._h, *A.head, *[_plane(v) if m0 is not None else v for v in m0p],
+                                                 *[_ptr(v) for v in cm], _ptr(grad[0]), _ptr(grad[1]),
+                                                 *[_ptr(v) if grad_m0 else v for v in gm], *[_ptr(v) for v in grad[2:]],
+                                                 _ptr(gd) if grad_df else gd)
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all, gg = grad[0] + 1j * grad[1], np.stack(grad[2:], 1)
+    res = []
+    for q in range(P):
+        out = (g_all[toff[q]:toff[q + 1]], gg[toff[q]:toff[q + 1]])
+        if grad_m0:
+            out += (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm),)
+        if grad_df:
+            out += (gd[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]),)
+        res.append(out)
+    return res
 
 
 def bloch_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), m0=None, tangents_m0=None, ctx=None):

@@ -1212,6 +1212,43 @@ int mbfir_bloch_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                                        cmz, g_re, g_im, gm0x, gm0y, gm0z));
 }
 
+// The Bloch b1 and gr adjoint keeps five doubles per (workgroup, sample): the rf pair and the three g components.
+static bool bloch_gr_partials_fit(int npulse, int nscale, const long* toff, const long* npoint) {
+    long total = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e;
+        if (__builtin_mul_overflow((npoint[p] + 255) / 256 * nscale, toff[p + 1] - toff[p], &e) ||
+            __builtin_add_overflow(total, e, &total))
+            return false;
+    }
+    return total <= (1L << 54);
+}
+
+int mbfir_bloch_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                             const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
+                             const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
+                             double* gm0z, double* ggx, double* ggy, double* ggz, double* gdf) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_vjp_gr_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_vjp_gr_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (!cmx || !cmy || !cmz || !g_re || !g_im) return bad("a cotangent or gradient plane is null");
+    if (!ggx || !ggy || !ggz) return bad("a plane of the gradient waveform's gradient (ggx, ggy, ggz) is null");
+    if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    if ((gm0x || gm0y || gm0z) && !(gm0x && gm0y && gm0z)) return bad("gm0x, gm0y and gm0z are given together or not at all");
+    if (!bloch_gr_partials_fit(npulse, nscale, toff, npoint.data()) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_vjp_gr_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                          t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, cmx,
+                                          cmy, cmz, g_re, g_im, gm0x, gm0y, gm0z, ggx, ggy, ggz, gdf));
+}
+
 // The rf and g adjoints keep up to two double2 per (workgroup, sample): the rf pair and the g component(s).
 static bool vjp_rfg_partials_fit(int npulse, int nscale, const long* roff, const long* npoint) {
     long total = 0;

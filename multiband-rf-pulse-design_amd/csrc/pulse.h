@@ -66,6 +66,17 @@ void bloch_vjp_batch_run(int device, void* stream, int npulse, const long* toff,
                          const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
                          const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
                          double* gm0z);
+// bloch_vjp_batch_run plus the adjoint with respect to the gradient waveform and the off-resonance (blochgradg.hip
+// k_bloch_vjp_gr_batch, k_bloch_vjp_gr_fold): ggx / ggy / ggz: dL / d gx, gy, gz per sample, laid out as gx / gy / gz, summed over
+// the pulse's points and scales without a factor (a null gx / gy / gz is differentiated at zero); gdf: dL / d df per (scale,
+// frequency, position) in gm0x's layout (null: not formed).  One upload, two launches, one download.
+void bloch_vjp_gr_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* cmx,
+                            const double* cmy, const double* cmz, double* g_re, double* g_im, double* gm0x, double* gm0y,
+                            double* gm0z, double* ggx, double* ggy, double* ggz, double* gdf);
 // Tangent of bloch_batch_run's end point (mode 0) with respect to b1 and the initial magnetisation (blochjvp.hip k_bloch_jvp_batch):
 // the forward call's inputs and m0* as above; ndir >= 1 directions per pulse, direction k of pulse p at ndir toff[p] + k n_p of v_re
 // / v_im; dm0*: the m0 directions, pulse p from ndir times its forward output offset, (direction, scale, point) row-major (all

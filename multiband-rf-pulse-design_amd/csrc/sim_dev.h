@@ -474,6 +474,44 @@ __device__ __forceinline__ double2 bloch_vjp_step(const double* s, double nz, co
     return g;
 }
 
+// bloch_vjp_step plus the sample's dL / d rotz, the third member of the pair above (blochgradg.hip): ai = -nz sp, so
+//     dL / d nz = nz C - sp G_ai
+// with C, sp and G_ai as the rf pair forms them; no further sincos.  At phi = 0 it is the generator T_10 - T_01.  The rf pair and
+// the multiplier are bloch_vjp_step's arithmetic restated.  Returns (dL / d rotx, dL / d roty, dL / d rotz).
+__device__ __forceinline__ double3 bloch_vjp_step_z(const double* s, double nz, const double mp[3], double l[3]) {
+    const double nx = s[0], ny = s[1], e1 = s[6], e2 = s[7];
+    const double phi = sqrt(nx * nx + ny * ny + nz * nz);
+    double sn, cp, sp, D;
+    sincos(0.5 * phi, &sn, &cp);
+    half_sinc(phi, sn, cp, sp, D);
+    const double ar = cp, ai = -nz * sp, br = ny * sp, bi = -nx * sp;
+    const double d0 = e2 * l[0], d1 = e2 * l[1], d2 = e1 * l[2];
+    const double T00 = d0 * mp[0], T01 = d0 * mp[1], T02 = d0 * mp[2];
+    const double T10 = d1 * mp[0], T11 = d1 * mp[1], T12 = d1 * mp[2];
+    const double T20 = d2 * mp[0], T21 = d2 * mp[1], T22 = d2 * mp[2];
+    const double a01 = T01 - T10, a02 = T02 - T20, a12 = T12 - T21;          // antisymmetric and symmetric parts
+    const double s01 = T01 + T10, s02 = T02 + T20, s12 = T12 + T21;
+    const double Gar = 2 * (ar * (T00 + T11 + T22) + ai * a01 + br * a02 + bi * a12);
+    const double Gai = 2 * (ai * (T22 - T00 - T11) + ar * a01 + bi * s02 - br * s12);
+    const double Gbr = 2 * (br * (T11 - T00 - T22) - bi * s01 + ar * a02 - ai * s12);
+    const double Gbi = 2 * (bi * (T00 - T11 - T22) - br * s01 + ai * s02 + ar * a12);
+    const double C = -0.5 * sp * Gar + D * (ny * Gbr - nz * Gai - nx * Gbi);
+    const double3 g = make_double3(nx * C - sp * Gbi, ny * C + sp * Gbr, nz * C - sp * Gai);
+    const double r00 = ar * ar - ai * ai - br * br + bi * bi, r10 = -2 * ar * ai - 2 * br * bi, r20 = -2 * ar * br + 2 * ai * bi;
+    const double r01 = 2 * ar * ai - 2 * br * bi, r11 = ar * ar - ai * ai + br * br - bi * bi, r21 = -2 * ai * br - 2 * ar * bi;
+    const double r02 = 2 * ar * br + 2 * ai * bi, r12 = 2 * ar * bi - 2 * ai * br, r22 = ar * ar + ai * ai - br * br - bi * bi;
+    l[0] = r00 * d0 + r10 * d1 + r20 * d2;
+    l[1] = r01 * d0 + r11 * d1 + r21 * d2;
+    l[2] = r02 * d0 + r12 * d1 + r22 * d2;
+    return g;
+}
+
+// The reduction tile of the b1 and gradient-waveform adjoint (blochgradg.hip): a group of VJP_T samples is walked in sub-groups of
+// BGR_T samples x five rows (the rf pair, px dz, py dz, pz dz) of VJP_ROW doubles: 15 of the 16 rows of the rf adjoint's tile, so
+// the same LDS and the same 16-lanes-per-row pass; the sixteenth row is summed and never stored.
+constexpr int BGR_T = 3;
+constexpr int BGR_ROWS = 5;
+
 // Per-pulse descriptor of the checkpoints: workgroup (scale, chunk) of the pulse owns ng = ceil(n / VJP_T) groups of 3 x 256
 // doubles from c_off + (scale nch + chunk) ng 768, component c of group k of thread tid at (3 k + c) 256 + tid.
 struct BlochCkDev {

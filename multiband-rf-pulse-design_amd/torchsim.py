@@ -9,7 +9,10 @@ host pointers, so tensors go through host memory, and the results come back on r
 x, y and the scales are constants of the graph.  torch is imported on first use, not with the package.
 `bloch` runs mbfir.bloch_batch on one pulse (the Bloch simulation with T1 / T2, end point) and is differentiable in reverse mode in
 b1 and in the initial magnetisation m0, its backward being one mbfir.bloch_vjp_batch call (section 8p); with forward_mode=True it
-also has the forward-mode tangent in both, one mbfir.bloch_jvp_batch call with one direction (section 8q).  With steady_state=True
+also has the forward-mode tangent in both, one mbfir.bloch_jvp_batch call with one direction (section 8q).  It is also
+differentiable, in reverse mode, in the gradient waveform gr and in the off-resonance df when they are float64 tensors that require
+grad: the backward is then one mbfir.bloch_vjp_gr_batch call for every gradient that is wanted (section 8w); when neither does it is
+the b1 call, with its bits.  A forward-mode tangent for gr or df raises NotImplementedError.  With steady_state=True
 it returns the steady state of the period instead (bloch_batch mode 1), differentiable in b1 through mbfir.bloch_ss_vjp_batch and
 mbfir.bloch_ss_jvp_batch (section 8t).
 
@@ -157,21 +160,28 @@ def _bloch_function():
 
     class Bloch(torch.autograd.Function):
         @staticmethod
-        def forward(b1, m0, pulse, df, dp, scales):
+        def forward(b1, m0, gr, df, rest, dp, scales):
             if not torch.is_tensor(b1) or b1.dtype != torch.complex128 or b1.dim() != 1:
                 raise ValueError("torchsim: b1 must be a 1-D complex128 tensor")
             if torch.is_tensor(m0) and m0.requires_grad and (m0.dtype != torch.float64 or m0.dim() != 3 or m0.shape[0] != 3):
                 raise ValueError("torchsim: an m0 that requires grad must be a float64 tensor of shape (3, nf, npos)")
+            if torch.is_tensor(gr) and gr.requires_grad and (gr.dtype != torch.float64 or gr.dim() not in (1, 2) or
+                                                             (gr.dim() == 2 and gr.shape[1] > 3)):
+                raise ValueError("torchsim: a gr that requires grad must be a float64 tensor of shape (n,) or (n, 1..3)")
+            if torch.is_tensor(df) and df.requires_grad and (df.dtype != torch.float64 or df.dim() != 1):
+                raise ValueError("torchsim: a df that requires grad must be a float64 tensor of shape (nf,)")
             m0h = _host(m0, np.float64)
-            res, = mbfir.bloch_batch([(_host(b1, np.complex128),) + pulse], df, dp, scales=scales,
-                                     m0=None if m0h is None else tuple(m0h))
+            res, = mbfir.bloch_batch([(_host(b1, np.complex128), _host(gr, np.float64)) + rest], _host(df, np.float64), dp,
+                                     scales=scales, m0=None if m0h is None else tuple(m0h))
             return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(b1.device) for v in res)
 
         @staticmethod
         def setup_context(ctx, inputs, output):
-            b1, m0, pulse, df, dp, scales = inputs
-            ctx.args = (_host(m0, np.float64), pulse, df, dp, scales)
+            b1, m0, gr, df, rest, dp, scales = inputs
+            ctx.args = (_host(m0, np.float64), (_host(gr, np.float64),) + rest, _host(df, np.float64), dp, scales)
             ctx.m0_like = (m0.shape, m0.device) if torch.is_tensor(m0) else None          # where m0's gradient goes
+            ctx.gr_like = (gr.shape, gr.device) if torch.is_tensor(gr) else None          # and gr's, and df's
+            ctx.df_like = (df.shape, df.device) if torch.is_tensor(df) else None
             ctx.save_for_backward(b1)
 
         @staticmethod
@@ -182,15 +192,26 @@ def _bloch_function():
         def backward(ctx, cx, cy, cz):
             b1, = ctx.saved_tensors
             m0h, pulse, df, dp, scales = ctx.args
-            want_m0 = ctx.needs_input_grad[1]
+            want_m0, want_gr, want_df = ctx.needs_input_grad[1:4]
             cot = tuple(_host(c, np.float64) for c in (cx, cy, cz))
-            res, = mbfir.bloch_vjp_batch([(_host(b1, np.complex128),) + pulse], df, dp, [cot], scales=scales,
-                                         m0=None if m0h is None else tuple(m0h), grad_m0=want_m0)
-            grad, gm = res if want_m0 else (res, None)
+            pulses, m0a = [(_host(b1, np.complex128),) + pulse], None if m0h is None else tuple(m0h)
+            ggr = gdf = None
+            if not (want_gr or want_df):                                # the b1 call, with its bits
+                res, = mbfir.bloch_vjp_batch(pulses, df, dp, [cot], scales=scales, m0=m0a, grad_m0=want_m0)
+                grad, gm = res if want_m0 else (res, None)
+            else:                                                       # one call for every gradient that is wanted (section 8w)
+                res, = mbfir.bloch_vjp_gr_batch(pulses, df, dp, [cot], scales=scales, m0=m0a, grad_m0=want_m0, grad_df=want_df)
+                grad, gm = res[0], res[2] if want_m0 else None
+                if want_gr:                                             # cut to the axes gr has
+                    shape, dev = ctx.gr_like
+                    k = shape[1] if len(shape) == 2 else 1
+                    ggr = torch.from_numpy(np.ascontiguousarray(res[1][:, :k]).reshape(shape)).to(dev)
+                if want_df:                                             # one df serves every scale and position: their sum
+                    gdf = torch.from_numpy(np.ascontiguousarray(res[-1].sum(axis=(0, 2))).reshape(ctx.df_like[0])).to(ctx.df_like[1])
             gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if ctx.needs_input_grad[0] else None
             if want_m0:                                                 # one m0 serves every scale: its gradient is their sum
                 gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
-            return gb, gm, None, None, None, None
+            return gb, gm, ggr, gdf, None, None, None
 
     class BlochForward(Bloch):
         """Bloch with a forward-mode tangent: the same forward and backward, plus a jvp that is one mbfir.bloch_jvp_batch call with
@@ -202,7 +223,10 @@ def _bloch_function():
             ctx.save_for_forward(inputs[0])
 
         @staticmethod
-        def jvp(ctx, v, vm0, *_):
+        def jvp(ctx, v, vm0, vgr, vdf, *_):
+            if vgr is not None or vdf is not None:
+                raise NotImplementedError("torchsim: the forward-mode tangent with respect to gr or df is not implemented "
+                                          "(reverse mode is)")
             b1, = ctx.saved_tensors
             m0h, pulse, df, dp, scales = ctx.args
             b1h = _host(b1, np.complex128)
@@ -265,15 +289,19 @@ def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None,
     simulation with relaxation, each a float64 tensor of shape (S, nf, npos) with bloch_batch's bits.  Differentiable in reverse mode
     in b1 (a 1-D complex128 tensor) and in m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient
     is summed over the scales); the backward is one mbfir.bloch_vjp_batch call.  Any other m0 ((mx, my, mz) or
-    an array of shape (3, nf, npos); None: equilibrium), gr, tp, t1, t2, df and dp are constants.  A forward-mode tangent raises
+    an array of shape (3, nf, npos); None: equilibrium), tp, t1, t2 and dp are constants.  gr and df are constants too unless they
+    are float64 tensors that require grad, gr of shape (n,) or (n, 1..3) and df of shape (nf,) (another dtype or shape raises
+    ValueError): then they are differentiated in reverse mode as well, gr's gradient cut to its shape and df's summed over the
+    scales and positions, and the backward is one mbfir.bloch_vjp_gr_batch call (section 8w); a forward-mode tangent for either
+    raises NotImplementedError, and with steady_state they stay constants.  A forward-mode tangent raises
     NotImplementedError unless forward_mode is set: then torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as
     well, the tangent in b1 and in a tensor m0 being one mbfir.bloch_jvp_batch call with one direction (section 8q).
     With steady_state the result is the steady state of the period b1 instead, bloch_batch(mode=1) with its bits (for balanced SSFP
     the period is the pulse plus the dead time of one repetition): differentiable in b1, the backward being one
     mbfir.bloch_ss_vjp_batch call and, with forward_mode, the tangent one mbfir.bloch_ss_jvp_batch call (section 8t).  The steady
     state does not depend on m0: an m0 other than None raises ValueError."""
-    pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
     if steady_state:
+        pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
         if m0 is not None:
             raise ValueError("torchsim: the steady state does not depend on m0; pass m0=None with steady_state")
         fn = _bloch_function()[3 if forward_mode else 2]
@@ -281,7 +309,9 @@ def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None,
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
     fn = _bloch_function()[1 if forward_mode else 0]
-    return fn.apply(b1, m0, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
+    gr = gr if hasattr(gr, "detach") else _host(gr, np.float64)       # a tensor stays an input of the graph
+    df = df if hasattr(df, "detach") else _host(df, np.float64)
+    return fn.apply(b1, m0, gr, df, (_host(tp, np.float64), float(t1), float(t2), nucleus), _host(dp, np.float64), tuple(scales))
 
 
 def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
