@@ -461,6 +461,31 @@ int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const
                              double* mz, double* dmx, double* dmy, double* dmz);
 /* mbfir_test_bloch_ss_jvp_group (host only): the directions one workgroup of the tangent above carries (a compile-time constant). */
 int mbfir_test_bloch_ss_jvp_group(void);
+/* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
+ * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
+ * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent
+ * (I - A)^-T c, fused into one kernel that starts with mode 1's own sweep:
+ *   ggx / ggy / ggz: one entry per sample of every pulse, laid out as gx / gy / gz: dL/dgx, dL/dgy, dL/dgz, summed over the points
+ *     of the pulse and over the scales without a factor (a scale multiplies b1, not the gradient).  All three are required; a NULL
+ *     input plane gx / gy / gz (an axis no pulse plays) is differentiated at zero and its gradient is returned all the same.
+ *   gdf: dL/ddf of every (scale, frequency, position), S x nf x npos per pulse in the layout of the cotangents; the caller sums
+ *     over whatever shares an off-resonance.  NULL = not wanted: it is then neither formed nor downloaded.
+ * There is no m0 and no dL/dm0.  g_re / g_im are those of mbfir_bloch_ss_vjp_batch to rounding (the sums run over other sub-groups
+ * of the same order), not promised to the bit; mx / my / mz receive M with mode 1's bits.  tp, t1, t2, the positions and the scales
+ * are not differentiated.  The error grows with kappa = ||(I - A)^-1|| as mbfir_bloch_ss_vjp_batch's does, dL/ddf's with its
+ * square; there is no guard on det(I - A).  The launch shape, staging and checkpoints are mbfir_bloch_ss_vjp_batch's; one upload,
+ * two launches (the three sweeps with one partial per workgroup, sample and component; then the fold of mbfir_bloch_vjp_gr_batch),
+ * one download; no atomics, so the bits of every result depend only on the pulse, its grids, its cotangents and the scale list.
+ * Argument checks and MBFIR_E_ARG messages as mbfir_bloch_ss_vjp_batch's (a cotangent or gradient plane NULL; mx / my / mz only
+ * partly given; a partial or checkpoint count that overflows), and one more case: a NULL ggx, ggy or ggz.  Each names
+ * bloch_ss_vjp_gr_batch in mbfir_last_error and no device work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_ss_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const double* cmx, const double* cmy, const double* cmz,
+                                double* g_re, double* g_im, double* mx, double* my, double* mz, double* ggx, double* ggy,
+                                double* ggz, double* gdf);
 /* ---- Least-squares products of mbfir_bloch_batch ----------------------------------------------------------------------------------
  * For the end point (mx, my, mz) of mbfir_bloch_batch (mode 0), relaxation included, weights (wx, wy, wz) >= 0 and targets (tx, ty,
  * tz) per output entry, the loss of a pulse is L = 1/2 sum w_c (m_c - t_c)^2 over c = x, y, z, its points and its scales, and J =

@@ -147,6 +147,8 @@ SYMBOLS = {
     "mbfir_bloch_ss_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                            _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [C.c_int] + [_dp] * 8),
     "mbfir_test_bloch_ss_jvp_group": (C.c_int, []),
+    "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                              _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                            _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -1572,6 +1574,44 @@ def bloch_ss_vjp_batch(pulses, df, dp, cot, *, scales=(1.0,), steady=False, ctx=
     if not steady:
         return res
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in out)) for q in range(P)]
+
+
+def bloch_ss_vjp_gr_batch(pulses, df, dp, cot, *, scales=(1.0,), grad_df=False, steady=False, ctx=None):
+    """The adjoint of bloch_batch's steady state (mode 1) with respect to b1, the gradient waveform gr and, on request, the
+    off-resonance df (mbfir_bloch_ss_vjp_gr_batch): arguments as bloch_ss_vjp_batch.  Returns one (grad_b1,
+    grad_gr) per pulse: grad_b1 as bloch_ss_vjp_batch returns it (equal to rounding, not promised to the bit), and grad_gr real of
+    shape (ntime, 3), column a = dL/dg_a in the units of gr, summed over the points and over the scales without a factor (a scale
+    multiplies b1, not gr); a column whose axis the pulse does not play is the derivative at a zero gradient.  With grad_df and / or
+    steady further members follow in that order: grad_df of shape (S, nf, npos), dL/ddf per scale, frequency and position (the
+    caller sums over whatever shares an off-resonance), and (mx, my, mz), the steady state itself with bloch_batch(mode=1)'s bits.
+    One upload, two launches, one download.  There is no m0 and no dL/dm0.  Deterministic: the bits of every result depend only on
+    the pulse, its grids, its cotangents and the scales.  The error grows with ||(I - A)^-1||, about T1 / TR, grad_df's with its
+    square.  tp, t1, t2, dp and the scales are not differentiated."""
+    A = _BlochArgs("bloch_ss_vjp_gr_batch", pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    cm = _bloch_cotangents("bloch_ss_vjp_gr_batch", cot, A)
+    ooff, toff = _offsets([S * f * k for f, k in zip(nf, npos)]), _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    grad = [np.zeros(int(toff[-1])) for _ in range(5)]                  # Re, Im of b1; gx, gy, gz
+    out = [np.zeros(int(ooff[-1])) for _ in range(3)] if steady else [nul] * 3
+    gd = np.zeros(int(ooff[-1])) if grad_df else nul
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_ss_vjp_gr_batch(ctx._h, *A.head, *[_ptr(v) for v in cm], _ptr(grad[0]), _ptr(grad[1]),
+                                                    *[_ptr(v) if steady else v for v in out], *[_ptr(v) for v in grad[2:]],
+                                                    _ptr(gd) if grad_df else gd)
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all, gg = grad[0] + 1j * grad[1], np.stack(grad[2:], 1)
+    res = []
+    for q in range(P):
+        r = (g_all[toff[q]:toff[q + 1]], gg[toff[q]:toff[q + 1]])
+        if grad_df:
+            r += (gd[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]),)
+        if steady:
+            r += (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in out),)
+        res.append(r)
+    return res
 
 
 def bloch_ss_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), ctx=None):

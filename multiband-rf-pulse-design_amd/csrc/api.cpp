@@ -1398,6 +1398,32 @@ int mbfir_bloch_ss_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const
                                           g_im, mx, my, mz));
 }
 
+// The steady state's adjoint in b1, gr and df (blochssg.hip): mbfir_bloch_ss_vjp_batch's checks, the planes of dL / dgr
+// and the counts of mbfir_bloch_vjp_gr_batch.
+int mbfir_bloch_ss_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const double* cmx, const double* cmy, const double* cmz,
+                                double* g_re, double* g_im, double* mx, double* my, double* mz, double* ggx, double* ggy,
+                                double* ggz, double* gdf) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_vjp_gr_batch: ") + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, "bloch_ss_vjp_gr_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        1, arrays, npoint))
+        return e;
+    if (!cmx || !cmy || !cmz || !g_re || !g_im) return bad("a cotangent or gradient plane is null");
+    if (!ggx || !ggy || !ggz) return bad("a plane of the gradient waveform's gradient (ggx, ggy, ggz) is null");
+    if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
+    if (!bloch_gr_partials_fit(npulse, nscale, toff, npoint.data()) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_vjp_gr_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                             t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, cmx, cmy, cmz,
+                                             g_re, g_im, mx, my, mz, ggx, ggy, ggz, gdf));
+}
+
 int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                              const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                              const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,

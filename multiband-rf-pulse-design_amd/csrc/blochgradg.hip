@@ -173,6 +173,14 @@ __global__ __launch_bounds__(1024) void k_bloch_vjp_gr_fold(const double2* __res
     gg[a * T + V.r_off + t] = -(f * g);
 }
 
+// Launches k_bloch_vjp_gr_fold on nfold workgroups for the callers outside this file (blochssg.hip).
+void bloch_vjp_gr_fold_launch(hipStream_t st, long nfold, const double2* part, const double* gpart, long npart, const VjpPulseDev* vp,
+                              const SimBlock* blocks, const double* scales, int nscale, const double* in,
+                              const BlochPulseDev* pulses, double2* grad, double* gg, long T) {
+    hipLaunchKernelGGL(k_bloch_vjp_gr_fold, dim3((unsigned)nfold), dim3(256, 4), 0, st, part, gpart, npart, vp, blocks, scales, nscale,
+                       in, pulses, grad, gg, T);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_vjp_gr_batch (arguments checked by api.cpp): the staging of bloch_vjp_batch_run; one upload, two
 // launches, one download.  The output region is the b1 gradient (T double2), the three planes of dL / d g (3 T doubles), dL / d df

@@ -101,6 +101,16 @@ void bloch_ss_vjp_batch_run(int device, void* stream, int npulse, const long* to
                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                             const double* scales, const double* cmx, const double* cmy, const double* cmz, double* g_re, double* g_im,
                             double* mx, double* my, double* mz);
+// bloch_ss_vjp_batch_run plus the adjoint with respect to the gradient waveform and the off-resonance (blochssg.hip
+// k_bloch_ss_vjp_gr_batch, with blochgradg.hip's k_bloch_vjp_gr_fold): ggx / ggy / ggz and gdf as
+// bloch_vjp_gr_batch_run's, gdf in the cotangents' layout (null: not formed).  One upload, two launches, one download.
+void bloch_ss_vjp_gr_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                               const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                               int nscale, const double* scales, const double* cmx, const double* cmy, const double* cmz,
+                               double* g_re, double* g_im, double* mx, double* my, double* mz, double* ggx, double* ggy, double* ggz,
+                               double* gdf);
 int bloch_ss_jvp_group();
 void bloch_ss_jvp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,

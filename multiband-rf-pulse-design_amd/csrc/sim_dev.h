@@ -524,6 +524,11 @@ constexpr int BLOCH_CK = 3 * 256;
 // transient adjoint's.
 void bloch_vjp_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
                            const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* grad);
+// Launches k_bloch_vjp_gr_fold (blochgradg.hip) on nfold workgroups: the fold of the steady state's adjoint in b1 and gr
+// (blochssg.hip) is the transient adjoint's.
+void bloch_vjp_gr_fold_launch(hipStream_t st, long nfold, const double2* part, const double* gpart, long npart, const VjpPulseDev* vp,
+                              const SimBlock* blocks, const double* scales, int nscale, const double* in,
+                              const BlochPulseDev* pulses, double2* grad, double* gg, long T);
 
 // What the directions of one point share at one sample.  R is quadratic in the Cayley-Klein parameters (ar, ai, br, bi) =
 // (cos(phi/2), -nz sp, ny sp, -nx sp), sp = sin(phi/2) / phi, and along dn = (dnx, dny, 0), with d sp = D (n.dn) (half_sinc),

@@ -14,7 +14,7 @@ differentiable, in reverse mode, in the gradient waveform gr and in the off-reso
 grad: the backward is then one mbfir.bloch_vjp_gr_batch call for every gradient that is wanted (section 8w); when neither does it is
 the b1 call, with its bits.  A forward-mode tangent for gr or df raises NotImplementedError.  With steady_state=True
 it returns the steady state of the period instead (bloch_batch mode 1), differentiable in b1 through mbfir.bloch_ss_vjp_batch and
-mbfir.bloch_ss_jvp_batch (section 8t).
+mbfir.bloch_ss_jvp_batch (section 8t) and, in reverse mode, in gr and df through mbfir.bloch_ss_vjp_gr_batch (section 8x).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -39,6 +39,12 @@ def _host(v, dtype):
                 return _host(torch._C._functorch.get_unwrapped(v), dtype)
         v = v.detach().resolve_conj().resolve_neg().cpu().numpy()       # autograd hands lazily conjugated cotangents on
     return np.asarray(v, dtype=dtype)
+
+
+def _has_tangent(v):
+    """Whether the tensor v carries a forward-mode tangent (a torch.autograd.forward_ad dual tensor, or what torch.func.jvp hands on)"""
+    import torch
+    return torch.autograd.forward_ad.unpack_dual(v).tangent is not None
 
 
 @functools.lru_cache(maxsize=None)
@@ -281,7 +287,81 @@ def _bloch_function():
             (_, tan), = mbfir.bloch_ss_jvp_batch([(b1h,) + pulse], df, dp, [vh], scales=scales)
             return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in tan)
 
-    return Bloch, BlochForward, BlochSteady, BlochSteadyForward
+    class BlochSteadyG(torch.autograd.Function):
+        """The steady state with gr and / or df as inputs of the graph: the forward is BlochSteady's, the backward one
+        mbfir.bloch_ss_vjp_gr_batch call for every gradient that is wanted."""
+
+        @staticmethod
+        def forward(b1, gr, df, rest, dp, scales):
+            if not torch.is_tensor(b1) or b1.dtype != torch.complex128 or b1.dim() != 1:
+                raise ValueError("torchsim: b1 must be a 1-D complex128 tensor")
+            if torch.is_tensor(gr) and gr.requires_grad and (gr.dtype != torch.float64 or gr.dim() not in (1, 2) or
+                                                             (gr.dim() == 2 and gr.shape[1] > 3)):
+                raise ValueError("torchsim: a gr that requires grad must be a float64 tensor of shape (n,) or (n, 1..3)")
+            if torch.is_tensor(df) and df.requires_grad and (df.dtype != torch.float64 or df.dim() != 1):
+                raise ValueError("torchsim: a df that requires grad must be a float64 tensor of shape (nf,)")
+            res, = mbfir.bloch_batch([(_host(b1, np.complex128), _host(gr, np.float64)) + rest], _host(df, np.float64), dp,
+                                     scales=scales, mode=1)
+            return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(b1.device) for v in res)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, gr, df, rest, dp, scales = inputs
+            ctx.args = ((_host(gr, np.float64),) + rest, _host(df, np.float64), dp, scales)
+            ctx.gr_like = (gr.shape, gr.device) if torch.is_tensor(gr) else None          # where gr's gradient goes, and df's
+            ctx.df_like = (df.shape, df.device) if torch.is_tensor(df) else None
+            ctx.out_shape = tuple(output[0].shape)                       # of a cotangent that arrives as None (BlochSteadyGForward)
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch is not implemented (reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, cx, cy, cz):
+            b1, = ctx.saved_tensors
+            pulse, df, dp, scales = ctx.args
+            want_gr, want_df = ctx.needs_input_grad[1:3]
+            cot = tuple(np.zeros(ctx.out_shape) if c is None else _host(c, np.float64) for c in (cx, cy, cz))
+            pulses = [(_host(b1, np.complex128),) + pulse]
+            ggr = gdf = None
+            if not (want_gr or want_df):                                # the b1 call, with its bits
+                grad, = mbfir.bloch_ss_vjp_batch(pulses, df, dp, [cot], scales=scales)
+            else:
+                res, = mbfir.bloch_ss_vjp_gr_batch(pulses, df, dp, [cot], scales=scales, grad_df=want_df)
+                grad = res[0]
+                if want_gr:                                             # cut to the axes gr has
+                    shape, dev = ctx.gr_like
+                    k = shape[1] if len(shape) == 2 else 1
+                    ggr = torch.from_numpy(np.ascontiguousarray(res[1][:, :k]).reshape(shape)).to(dev)
+                if want_df:                                             # one df serves every scale and position: their sum
+                    gdf = torch.from_numpy(np.ascontiguousarray(res[2].sum(axis=(0, 2))).reshape(ctx.df_like[0])).to(ctx.df_like[1])
+            gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if ctx.needs_input_grad[0] else None
+            return gb, ggr, gdf, None, None, None
+
+    class BlochSteadyGForward(BlochSteadyG):
+        """BlochSteadyG with the forward-mode tangent in b1, one mbfir.bloch_ss_jvp_batch call with one direction; a tangent for gr
+        or df raises NotImplementedError."""
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            BlochSteadyG.setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+            ctx.set_materialize_grads(False)                            # a gr or df without a tangent arrives as None, not as zeros
+
+        @staticmethod
+        def jvp(ctx, v, vgr, vdf, *_):
+            if vgr is not None or vdf is not None:
+                raise NotImplementedError("torchsim: the forward-mode tangent with respect to gr or df is not implemented "
+                                          "(reverse mode is)")
+            b1, = ctx.saved_tensors
+            pulse, df, dp, scales = ctx.args
+            b1h = _host(b1, np.complex128)
+            vh = np.zeros_like(b1h) if v is None else _host(v, np.complex128)
+            (_, tan), = mbfir.bloch_ss_jvp_batch([(b1h,) + pulse], df, dp, [vh], scales=scales)
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in tan)
+
+    return Bloch, BlochForward, BlochSteady, BlochSteadyForward, BlochSteadyG, BlochSteadyGForward
 
 
 def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None, forward_mode=False, steady_state=False):
@@ -293,17 +373,26 @@ def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None,
     are float64 tensors that require grad, gr of shape (n,) or (n, 1..3) and df of shape (nf,) (another dtype or shape raises
     ValueError): then they are differentiated in reverse mode as well, gr's gradient cut to its shape and df's summed over the
     scales and positions, and the backward is one mbfir.bloch_vjp_gr_batch call (section 8w); a forward-mode tangent for either
-    raises NotImplementedError, and with steady_state they stay constants.  A forward-mode tangent raises
+    raises NotImplementedError.  A forward-mode tangent raises
     NotImplementedError unless forward_mode is set: then torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as
     well, the tangent in b1 and in a tensor m0 being one mbfir.bloch_jvp_batch call with one direction (section 8q).
     With steady_state the result is the steady state of the period b1 instead, bloch_batch(mode=1) with its bits (for balanced SSFP
     the period is the pulse plus the dead time of one repetition): differentiable in b1, the backward being one
-    mbfir.bloch_ss_vjp_batch call and, with forward_mode, the tangent one mbfir.bloch_ss_jvp_batch call (section 8t).  The steady
-    state does not depend on m0: an m0 other than None raises ValueError."""
+    mbfir.bloch_ss_vjp_batch call and, with forward_mode, the tangent one mbfir.bloch_ss_jvp_batch call (section 8t).  A gr or df
+    that is a float64 tensor requiring grad (shapes and ValueErrors as above) is differentiated in reverse mode there too, gr's
+    gradient cut to its shape and df's summed over the scales and positions: the backward is then one mbfir.bloch_ss_vjp_gr_batch
+    call for every gradient that is wanted (section 8x), and a forward-mode tangent for gr or df raises NotImplementedError; when
+    neither requires grad the calls are the b1 ones, with their bits.  The steady state does not depend on m0: an m0 other than
+    None raises ValueError."""
     if steady_state:
-        pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
         if m0 is not None:
             raise ValueError("torchsim: the steady state does not depend on m0; pass m0=None with steady_state")
+        if any(hasattr(v, "detach") and (v.requires_grad or _has_tangent(v)) for v in (gr, df)):      # inputs of the graph (section 8x)
+            fn = _bloch_function()[5 if forward_mode else 4]
+            gr = gr if hasattr(gr, "detach") else _host(gr, np.float64)
+            df = df if hasattr(df, "detach") else _host(df, np.float64)
+            return fn.apply(b1, gr, df, (_host(tp, np.float64), float(t1), float(t2), nucleus), _host(dp, np.float64), tuple(scales))
+        pulse = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
         fn = _bloch_function()[3 if forward_mode else 2]
         return fn.apply(b1, pulse, _host(df, np.float64), _host(dp, np.float64), tuple(scales))
     if m0 is not None and not hasattr(m0, "detach"):
