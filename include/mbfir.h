@@ -461,6 +461,52 @@ int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const
                              double* mz, double* dmx, double* dmy, double* dmz);
 /* mbfir_test_bloch_ss_jvp_group (host only): the directions one workgroup of the tangent above carries (a compile-time constant). */
 int mbfir_test_bloch_ss_jvp_group(void);
+/* ---- The echo-by-echo transient of a pulse train ----------------------------------------------------------------------------------
+ * Each pulse of the call is one period, exactly as mbfir_bloch_batch takes it (dead time as zero-b1 samples with their own
+ * interval); a train plays it ntr_p times, repetition k at gains[k] exp(i phi_k) b1, gradients and timing the same every repetition.
+ * With (A, B) the period's propagator m -> A m + B at RF amplitude scale x gain and RF phase 0, (A_e, B_e) that of its first
+ * echo_p samples, Z(th) = [[cos th, -sin th, 0], [sin th, cos th, 0], [0, 0, 1]] and m_0 = m0, per point
+ *     u = Z(+phi_k) m_k,   echo_k = Z(-phi_k) (A_e u + meq B_e)   (demod != 0: without the leading Z(-phi_k)),
+ *     m_{k+1} = Z(-phi_k) (A u + meq B).
+ * meq scales every recovery term (1 - E1): 1 is mbfir_bloch's convention, 0 the hyperpolarised limit, in which the train is linear
+ * in m0.  mbfir_bloch_train_batch takes mbfir_bloch_batch's input arguments up to nscale and scales, then
+ *   ntr (npulse): the repetitions of pulse p, >= 1.
+ *   roff (npulse + 1) into cosphi / sinphi / gidx: roff[p + 1] - roff[p] = ntr_p; entry roff[p] + k holds cos phi_k, sin phi_k and
+ *     the index of repetition k's gain among the pulse's distinct gains.  The caller forms the cosines and sines in double.
+ *   goff (npulse + 1) into gains: the ngain_p = goff[p + 1] - goff[p] distinct gains of pulse p, 1 <= ngain_p <= ntr_p.  The
+ *     propagators are formed once per (scale, distinct gain), at the amplitude scales[s] * gains[g] (one double product).
+ *   echo (npulse): the echo sample of pulse p in [0, ntime_p]; 0 gives (A_e, B_e) = (I, 0) and ntime_p gives (A, B).
+ *   meq (npulse), demod.
+ *   m0x / m0y / m0z: as mbfir_bloch_vjp_batch takes them; all three NULL = [0 0 1] everywhere.
+ *   ex / ey / ez: the echoes, pulse p from sum_{q < p} nscale ntr_q nf_q npos_q, laid out (scale, repetition, frequency, position)
+ *     row-major; all three NULL = not downloaded.
+ *   fx / fy / fz: m after the last repetition in the layout of mbfir_bloch_batch's mode-0 outputs; all three NULL = not downloaded.
+ * One upload, two launches, one download: the first launch sweeps the period's samples once per (pulse, scale, distinct gain, 256
+ * points) and leaves the 24 doubles of (A, B, A_e, B_e) per point in a device workspace; the second walks the repetitions, one
+ * workgroup per (pulse, scale, 256 points).  No atomics: a result's bits depend only on its own pulse, scale, point and train, and
+ * the first n echoes of a train are those of the train cut after n repetitions.
+ * mbfir_bloch_prop_batch is the first launch alone, at gain 1: after scales it takes echo (npulse) and returns a / ae (9 doubles,
+ * column-major: entry (i, j) at i + 3 j) and b / be (3 doubles, at meq = 1) of every (scale, frequency, position), block (s, f, k)
+ * of pulse p at 9 (or 3) times O_p + (s nf_p + f) npos_p + k with O_p = sum_{q < p} nscale nf_q npos_q.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_batch (a train table, echo, meq or, for
+ * mbfir_bloch_prop_batch, an output NULL is a required array NULL); further MBFIR_E_ARG cases, each with its reason in
+ * mbfir_last_error and no device work done: ntr < 1; roff or goff inconsistent with ntr; echo outside [0, ntime]; a gain index
+ * outside [0, ngain); a gain, cosine, sine or meq that is not finite; m0, the echo planes or the final planes only partly given, or
+ * neither output wanted; a workspace, output or workgroup count that overflows.  A refused call leaves the context usable.  A NULL
+ * context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                            const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                            const int* ntr, const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                            const long* goff, const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                            const double* m0y, const double* m0z, double* ex, double* ey, double* ez, double* fx, double* fy,
+                            double* fz);
+int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                           const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                           const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                           const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                           const int* echo, double* a, double* b, double* ae, double* be);
 /* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
  * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
  * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent

@@ -147,6 +147,11 @@ SYMBOLS = {
     "mbfir_bloch_ss_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                            _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [C.c_int] + [_dp] * 8),
     "mbfir_test_bloch_ss_jvp_group": (C.c_int, []),
+    "mbfir_bloch_train_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                          _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                         [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 9),
+    "mbfir_bloch_prop_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                         _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_ip] + [_dp] * 4),
     "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -1667,6 +1672,133 @@ def _bloch_m0(A, m0):
     if m0 is None:
         return [C.cast(None, _dp)] * 3
     return A.m0_planes(m0, _offsets([A.S * f * k for f, k in zip(A.nf, A.npos)]), [1] * A.P)
+
+
+# ---- pulse trains: the echo-by-echo transient of N repetitions of a period (mbfir_bloch_train_batch) ----------
+def _train_ints(who, what, v, P, default=None):
+    """ntr / echo: None (the default per pulse), an int for every pulse, or a list of one int per pulse -> a list of P ints"""
+    if v is None:
+        return list(default)
+    if isinstance(v, (list, tuple, np.ndarray)):
+        if len(v) != P:
+            raise ValueError("%s: %d values of %s for %d pulses" % (who, len(v), what, P))
+        v = list(v)
+    else:
+        v = [v] * P
+    if any(int(e) != e for e in v):
+        raise ValueError("%s: %s must be an integer" % (who, what))
+    return [int(e) for e in v]
+
+
+def _train_echo(who, echo, A):
+    echo = _train_ints(who, "echo", echo, A.P, A.nt)
+    for q, (e, n) in enumerate(zip(echo, A.nt)):
+        if e < 0 or e > n:
+            raise ValueError("%s: echo of pulse %d must lie in [0, ntime]" % (who, q))
+    return np.ascontiguousarray(echo, dtype=np.int32)
+
+
+def _train_tables(who, what, v, ntr, increment):
+    """phases / gains: a scalar (increment: phi_k = k v; else the value of every repetition), an array of ntr values for every
+    pulse, or a Python list of one array per pulse -> a list of P float64 arrays of ntr[q] values"""
+    P = len(ntr)
+    each = _per_pulse(v, P)
+    out = []
+    for q, n in enumerate(ntr):
+        e = np.asarray(each[0 if len(each) == 1 else q], dtype=np.float64)
+        if e.ndim == 0:
+            e = np.arange(n) * float(e) if increment else np.full(n, float(e))
+        e = e.ravel()
+        if len(e) != n:
+            raise ValueError("%s: %s of pulse %d has %d entries for its %d repetitions" % (who, what, q, len(e), n))
+        out.append(e)
+    return out
+
+
+def bloch_train_batch(pulses, df, dp, ntr, *, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False,
+                      final=False, ctx=None):
+    """The echo-by-echo transient of pulse trains (mbfir_bloch_train_batch).  Each pulse is one period, exactly
+    as bloch_batch takes it (dead time as zero-b1 samples with their own tp); a train plays it ntr times (an int, or a list of one
+    int per pulse), repetition k at gains[k] exp(i phases[k]) b1 with the gradients and the timing of the period.  phases: a scalar
+    increment D, phi_k = k D (the default pi is alternating bSSFP), an array of ntr phases in radians, or a Python list of one such
+    array per pulse.  gains: a scalar, an array of ntr values (a catalysation ramp, a variable-flip-angle schedule), or a Python
+    list of one array per pulse.  echo: the sample index in [0, ntime] after which the echo is read, an int or a list of one per
+    pulse; None = ntime, the state at the end of each repetition.  df, dp, scales and m0 as for bloch_batch.  meq (a scalar or one
+    per pulse) scales every recovery term (1 - E1): 1 is bloch's convention, 0 the hyperpolarised limit, in which the train is
+    linear in m0.  demod: return the echoes in the frame of each repetition's RF phase.  Returns, per pulse, (mx, my, mz) of shape
+    (S, ntr, nf, npos); with final, ((mx, my, mz), (fx, fy, fz)), the second being the magnetisation after the last repetition, of
+    shape (S, nf, npos), which a following train takes as m0.  The period is swept once per (scale, distinct gain); a repetition
+    then costs about sixty flops per point.  Deterministic: a result's bits depend only on its pulse, scale, point and train, and
+    the first n echoes of a train are those of the train cut after n repetitions."""
+    who = "bloch_train_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    ntr = _train_ints(who, "ntr", ntr, P)
+    for q, n in enumerate(ntr):
+        if n < 1:
+            raise ValueError("%s: ntr of pulse %d must be at least 1" % (who, q))
+    ech = _train_echo(who, echo, A)
+    ph, gn = _train_tables(who, "phases", phases, ntr, True), _train_tables(who, "gains", gains, ntr, False)
+    if not all(np.all(np.isfinite(g)) for g in gn):
+        raise ValueError("%s: a gain is not finite" % who)
+    if not all(np.all(np.isfinite(p)) for p in ph):
+        raise ValueError("%s: a cosine or sine of the phase table is not finite" % who)
+    mq = _vec(meq)
+    if mq.size not in (1, P):
+        raise ValueError("%s: %d values of meq for %d pulses" % (who, mq.size, P))
+    mq = np.ascontiguousarray(np.broadcast_to(mq, (P,)))
+    for q in range(P):
+        if not np.isfinite(mq[q]):
+            raise ValueError("%s: meq of pulse %d is not finite" % (who, q))
+    uniq = [np.unique(g, return_inverse=True) for g in gn]             # the distinct gains and every repetition's index among them
+    phi = np.concatenate(ph)
+    cs, sn = _vec(np.cos(phi)), _vec(np.sin(phi))
+    gidx = np.ascontiguousarray(np.concatenate([u[1].ravel() for u in uniq]), dtype=np.int32)
+    gains_d = _vec(np.concatenate([u[0] for u in uniq]))
+    ntr_a, roff, goff = np.ascontiguousarray(ntr, dtype=np.int32), _offsets(ntr), _offsets([len(u[0]) for u in uniq])
+    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+    eoff = _offsets([S * n * f * k for n, f, k in zip(ntr, nf, npos)])
+    m0p = _bloch_m0(A, m0)
+    out = [np.zeros(int(eoff[-1])) for _ in range(3)]
+    fin = [np.zeros(int(ooff[-1])) for _ in range(3)] if final else [C.cast(None, _dp)] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_batch(ctx._h, *A.head, ntr_a.ctypes.data_as(_ip), _lptr(roff), _ptr(cs), _ptr(sn),
+                                                gidx.ctypes.data_as(_ip), _lptr(goff), _ptr(gains_d), ech.ctypes.data_as(_ip),
+                                                _ptr(mq), int(bool(demod)), *[_plane(v) for v in m0p], *[_ptr(v) for v in out],
+                                                *[_plane(v) for v in fin])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = []
+    for q in range(P):
+        e = tuple(o[eoff[q]:eoff[q + 1]].reshape(S, ntr[q], nf[q], npos[q]) for o in out)
+        res.append((e, tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in fin)) if final else e)
+    return res
+
+
+def bloch_prop_batch(pulses, df, dp, *, echo=None, scales=(1.0,), ctx=None):
+    """The propagators of one period (mbfir_bloch_prop_batch, the first launch of bloch_train_batch on its own): pulses, df, dp,
+    scales and echo as for bloch_train_batch.  Returns, per pulse, (A, B, Ae, Be): one period is m -> A m + B at RF phase 0 (B at
+    meq = 1), its first `echo` samples m -> Ae m + Be; A and Ae of shape (S, nf, npos, 3, 3), B and Be of shape (S, nf, npos, 3).
+    Periods compose on the host: (A2, B2) after (A1, B1) is (A2 A1, A2 B1 + B2)."""
+    who = "bloch_prop_batch"
+    A = _BlochArgs(who, pulses, df, dp, scales)
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    ech = _train_echo(who, echo, A)
+    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+    O = int(ooff[-1])
+    a, b, ae, be = np.zeros(9 * O), np.zeros(3 * O), np.zeros(9 * O), np.zeros(3 * O)
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_prop_batch(ctx._h, *A.head, ech.ctypes.data_as(_ip), _ptr(a), _ptr(b), _ptr(ae), _ptr(be))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = []
+    for q in range(P):
+        lo, hi, shape = int(ooff[q]), int(ooff[q + 1]), (S, nf[q], npos[q])
+        mat = lambda v: v[9 * lo:9 * hi].reshape(shape + (3, 3)).swapaxes(-1, -2)          # column-major: entry (i, j) at i + 3 j
+        res.append((mat(a), b[3 * lo:3 * hi].reshape(shape + (3,)), mat(ae), be[3 * lo:3 * hi].reshape(shape + (3,))))
+    return res
 
 
 def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):

@@ -1452,6 +1452,95 @@ int mbfir_bloch_ss_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const
 
 int mbfir_test_bloch_ss_jvp_group(void) { return bloch_ss_jvp_group(); }
 
+// The pulse train (blochtrain.hip).  What both calls check after bloch_batch_check: echo (per pulse) within [0, ntime],
+// and that the propagators' planes (24 doubles per point and combination, ncomb[p] = nscale ngain_p combinations) and their
+// workgroups fit.
+static int bloch_prop_check(mbfir_ctx* ctx, const char* who, int npulse, const long* toff, const int* echo, const long* ncomb,
+                            const long* npoint) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    for (int p = 0; p < npulse; ++p)
+        if (echo[p] < 0 || echo[p] > toff[p + 1] - toff[p])
+            return bad("echo of pulse " + std::to_string(p) + " must lie in [0, ntime]");
+    long total = 0, nblk = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e, b;
+        if (__builtin_mul_overflow(npoint[p], ncomb[p] * 24, &e) || __builtin_add_overflow(total, e, &total) ||
+            __builtin_mul_overflow((npoint[p] + 255) / 256, ncomb[p], &b) || __builtin_add_overflow(nblk, b, &nblk))
+            return bad("the output size or the workgroup count overflows");
+    }
+    if (total > (1L << 56) || nblk > 2147483647L) return bad("the output size or the workgroup count overflows");
+    return 0;
+}
+
+int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                            const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                            const int* ntr, const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                            const long* goff, const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                            const double* m0y, const double* m0z, double* ex, double* ey, double* ez, double* fx, double* fy,
+                            double* fz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_batch_check(ctx, "bloch_train_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    for (int p = 0; p < npulse; ++p)
+        if (ntr[p] < 1) return bad("ntr of pulse " + std::to_string(p) + " must be at least 1");
+    if (roff[0] != 0 || goff[0] != 0) return bad("inconsistent offsets: roff or goff does not start at 0");
+    std::vector<long> ncomb(npulse), ntout(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        if (roff[p + 1] - roff[p] != ntr[p])
+            return bad("inconsistent offsets: roff of pulse " + std::to_string(p) + " does not span its ntr repetitions");
+        const long G = goff[p + 1] - goff[p];
+        if (G < 1 || G > ntr[p]) return bad("pulse " + std::to_string(p) + " needs between 1 and ntr distinct gains");
+        ncomb[p] = G * nscale;
+        ntout[p] = ntr[p];
+    }
+    if (const int e = bloch_prop_check(ctx, "bloch_train_batch", npulse, toff, echo, ncomb.data(), npoint.data())) return e;
+    // the sizes before the tables are read: a table is as long as ntr says
+    if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
+        return bad("the output size or the workgroup count overflows");
+    for (int p = 0; p < npulse; ++p)
+        for (long k = roff[p]; k < roff[p + 1]; ++k)
+            if (gidx[k] < 0 || gidx[k] >= goff[p + 1] - goff[p])
+                return bad("a gain index of pulse " + std::to_string(p) + " lies outside [0, ngain)");
+    for (long g = 0; g < goff[npulse]; ++g)
+        if (!std::isfinite(gains[g])) return bad("a gain is not finite");
+    for (long k = 0; k < roff[npulse]; ++k)
+        if (!std::isfinite(cosphi[k]) || !std::isfinite(sinphi[k])) return bad("a cosine or sine of the phase table is not finite");
+    for (int p = 0; p < npulse; ++p)
+        if (!std::isfinite(meq[p])) return bad("meq of pulse " + std::to_string(p) + " is not finite");
+    if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    if ((ex || ey || ez) && !(ex && ey && ez)) return bad("the echo planes are given together or not at all");
+    if ((fx || fy || fz) && !(fx && fy && fz)) return bad("the final planes are given together or not at all");
+    if (!ex && !fx) return bad("neither the echo planes nor the final planes are wanted");
+    MBFIR_TRY(ctx, bloch_train_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                         t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff, cosphi,
+                                         sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ex, ey, ez, fx, fy, fz));
+}
+
+int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                           const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                           const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                           const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                           const int* echo, double* a, double* b, double* ae, double* be) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && echo && a &&
+                        b && ae && be;
+    if (const int e = bloch_batch_check(ctx, "bloch_prop_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    std::vector<long> ncomb(npulse, nscale);
+    if (const int e = bloch_prop_check(ctx, "bloch_prop_batch", npulse, toff, echo, ncomb.data(), npoint.data())) return e;
+    MBFIR_TRY(ctx, bloch_prop_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                        t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, echo, a, b, ae, be));
+}
+
 // What the Bloch least-squares calls check after bloch_batch_check, in this order: their own planes (what: the message of a null
 // one), m0, the 3 O weights (O: the forward call's output entries), ndir, and that ndir times the T b1 samples, the partials (one per
 // workgroup and sample, per direction) and the checkpoints (at most 2^56 entries each) and the workgroups of the sweep and of the

@@ -118,6 +118,26 @@ void bloch_ss_jvp_batch_run(int device, void* stream, int npulse, const long* to
                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                             const double* scales, int ndir, const double* v_re, const double* v_im, double* mx, double* my,
                             double* mz, double* dmx, double* dmy, double* dmz);
+// The echo-by-echo transient of a pulse train (blochtrain.hip k_bloch_train_prop, k_bloch_train_run): the forward call's
+// inputs, each pulse one period; per pulse ntr repetitions whose (cos phi, sin phi, gain index) lie at roff[p] .. of cosphi /
+// sinphi / gidx, its distinct gains at goff[p] .. goff[p + 1] - 1 of gains, the echo sample and meq; m0* as bloch_vjp_batch_run's;
+// e*: the echoes, S x ntr x nf x npos per pulse (all null: not downloaded); f*: m after the last repetition in the layout of the
+// mode-0 outputs (all null: not downloaded).  One upload, two launches, one download.  bloch_prop_batch_run is the first launch
+// alone at gain 1: a / ae (9, column-major) and b / be (3) per (scale, frequency, position), pulse p from 9 (or 3) times its mode-0
+// output offset.
+void bloch_train_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                           const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                           const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                           int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                           const double* scales, const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                           const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                           const double* m0x, const double* m0y, const double* m0z, double* ex, double* ey, double* ez, double* fx,
+                           double* fy, double* fz);
+void bloch_prop_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                          const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                          const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                          int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                          const double* scales, const int* echo, double* a, double* b, double* ae, double* be);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1
