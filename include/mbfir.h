@@ -507,6 +507,37 @@ int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const d
                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
                            const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                            const int* echo, double* a, double* b, double* ae, double* be);
+/* ---- Adjoint of the pulse train with respect to b1 and the initial magnetisation ----------------------------------------------------
+ * The vector-Jacobian product of mbfir_bloch_train_batch's echoes and final state: for the loss
+ *     L = sum_k <ce_k, echo_k> + <cf, m_N>
+ * the gradient dL/dRe b1 + i dL/dIm b1 of the period's samples, summed over the points, the scales and the repetitions (repetition k
+ * plays gains[k] exp(i phi_k) b1: the chain rule through that product is included), and dL/dm0.  It takes
+ * mbfir_bloch_train_batch's arguments through demod and m0x / m0y / m0z, then
+ *   cex / cey / cez: the cotangents of the echoes, laid out as ex / ey / ez (with demod != 0: of the demodulated echoes); all
+ *     three NULL = none.
+ *   cfx / cfy / cfz: the cotangents of the final state, laid out as fx / fy / fz; all three NULL = none.  Not both triples NULL.
+ *   g_re / g_im: one entry per sample of every pulse, laid out as b1_re / b1_im.
+ *   gmx / gmy / gmz: dL/dm0 of every (scale, frequency, position) in the layout of the final planes; all three NULL = not wanted.
+ *     dL/dm0 depends neither on m0 nor on meq, and has the same bits for any of them.
+ * One upload, four launches, one download: the forward call's propagator launch; the repetitions walked forwards (a checkpoint
+ * before every eighth) and backwards, which leaves the cotangents of the 24 doubles of (A, B, A_e, B_e) per (scale, distinct gain,
+ * point) in a device workspace; the period's samples swept forwards and backwards once per (pulse, scale, distinct gain, 64
+ * points), the four columns of [A | B] on the four wavefronts of a workgroup; and the fold over chunks and combinations.  No
+ * atomics: a pulse's gradient bits depend only on the pulse, its grids, its train, its cotangents and the scale list.  The gains,
+ * the phases, gr, tp, t1, t2, df, the positions and meq are not differentiated.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with
+ * its reason in mbfir_last_error and no device work done: a cotangent triple or gmx / gmy / gmz only partly given; both cotangent
+ * triples NULL; g_re or g_im NULL; a partial, checkpoint, workspace or workgroup count that overflows.  A refused call leaves the
+ * context usable.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
+                                const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
 /* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
  * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
  * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent

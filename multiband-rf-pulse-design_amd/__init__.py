@@ -152,6 +152,9 @@ SYMBOLS = {
                                          [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 9),
     "mbfir_bloch_prop_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                          _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_ip] + [_dp] * 4),
+    "mbfir_bloch_train_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                              _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                             [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
     "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -1715,6 +1718,44 @@ def _train_tables(who, what, v, ntr, increment):
     return out
 
 
+class _TrainArgs:
+    """The arguments that bloch_train_batch and its adjoint share, checked and laid out for the C calls: A (_BlochArgs), ntr (a list),
+    tail (the C arguments from ntr through demod), ooff (the final planes' offsets) and eoff (the echo planes')"""
+
+    def __init__(self, who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod):
+        A = _BlochArgs(who, pulses, df, dp, scales)
+        P, S, nf, npos = A.P, A.S, A.nf, A.npos
+        ntr = _train_ints(who, "ntr", ntr, P)
+        for q, n in enumerate(ntr):
+            if n < 1:
+                raise ValueError("%s: ntr of pulse %d must be at least 1" % (who, q))
+        ech = _train_echo(who, echo, A)
+        ph, gn = _train_tables(who, "phases", phases, ntr, True), _train_tables(who, "gains", gains, ntr, False)
+        if not all(np.all(np.isfinite(g)) for g in gn):
+            raise ValueError("%s: a gain is not finite" % who)
+        if not all(np.all(np.isfinite(p)) for p in ph):
+            raise ValueError("%s: a cosine or sine of the phase table is not finite" % who)
+        mq = _vec(meq)
+        if mq.size not in (1, P):
+            raise ValueError("%s: %d values of meq for %d pulses" % (who, mq.size, P))
+        mq = np.ascontiguousarray(np.broadcast_to(mq, (P,)))
+        for q in range(P):
+            if not np.isfinite(mq[q]):
+                raise ValueError("%s: meq of pulse %d is not finite" % (who, q))
+        uniq = [np.unique(g, return_inverse=True) for g in gn]             # the distinct gains and every repetition's index among them
+        phi = np.concatenate(ph)
+        cs, sn = _vec(np.cos(phi)), _vec(np.sin(phi))
+        gidx = np.ascontiguousarray(np.concatenate([u[1].ravel() for u in uniq]), dtype=np.int32)
+        gains_d = _vec(np.concatenate([u[0] for u in uniq]))
+        ntr_a, roff, goff = np.ascontiguousarray(ntr, dtype=np.int32), _offsets(ntr), _offsets([len(u[0]) for u in uniq])
+        ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
+        eoff = _offsets([S * n * f * k for n, f, k in zip(ntr, nf, npos)])
+        self.A, self.ntr, self.ooff, self.eoff = A, ntr, ooff, eoff
+        self._keep = (ntr_a, roff, cs, sn, gidx, goff, gains_d, ech, mq)                     # the arrays behind the pointers
+        self.tail = [ntr_a.ctypes.data_as(_ip), _lptr(roff), _ptr(cs), _ptr(sn), gidx.ctypes.data_as(_ip), _lptr(goff), _ptr(gains_d),
+                     ech.ctypes.data_as(_ip), _ptr(mq), int(bool(demod))]
+
+
 def bloch_train_batch(pulses, df, dp, ntr, *, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False,
                       final=False, ctx=None):
     """The echo-by-echo transient of pulse trains (mbfir_bloch_train_batch).  Each pulse is one period, exactly
@@ -1730,41 +1771,14 @@ def bloch_train_batch(pulses, df, dp, ntr, *, phases=np.pi, gains=1.0, echo=None
     shape (S, nf, npos), which a following train takes as m0.  The period is swept once per (scale, distinct gain); a repetition
     then costs about sixty flops per point.  Deterministic: a result's bits depend only on its pulse, scale, point and train, and
     the first n echoes of a train are those of the train cut after n repetitions."""
-    who = "bloch_train_batch"
-    A = _BlochArgs(who, pulses, df, dp, scales)
+    Tn = _TrainArgs("bloch_train_batch", pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff, eoff = Tn.A, Tn.ntr, Tn.ooff, Tn.eoff
     P, S, nf, npos = A.P, A.S, A.nf, A.npos
-    ntr = _train_ints(who, "ntr", ntr, P)
-    for q, n in enumerate(ntr):
-        if n < 1:
-            raise ValueError("%s: ntr of pulse %d must be at least 1" % (who, q))
-    ech = _train_echo(who, echo, A)
-    ph, gn = _train_tables(who, "phases", phases, ntr, True), _train_tables(who, "gains", gains, ntr, False)
-    if not all(np.all(np.isfinite(g)) for g in gn):
-        raise ValueError("%s: a gain is not finite" % who)
-    if not all(np.all(np.isfinite(p)) for p in ph):
-        raise ValueError("%s: a cosine or sine of the phase table is not finite" % who)
-    mq = _vec(meq)
-    if mq.size not in (1, P):
-        raise ValueError("%s: %d values of meq for %d pulses" % (who, mq.size, P))
-    mq = np.ascontiguousarray(np.broadcast_to(mq, (P,)))
-    for q in range(P):
-        if not np.isfinite(mq[q]):
-            raise ValueError("%s: meq of pulse %d is not finite" % (who, q))
-    uniq = [np.unique(g, return_inverse=True) for g in gn]             # the distinct gains and every repetition's index among them
-    phi = np.concatenate(ph)
-    cs, sn = _vec(np.cos(phi)), _vec(np.sin(phi))
-    gidx = np.ascontiguousarray(np.concatenate([u[1].ravel() for u in uniq]), dtype=np.int32)
-    gains_d = _vec(np.concatenate([u[0] for u in uniq]))
-    ntr_a, roff, goff = np.ascontiguousarray(ntr, dtype=np.int32), _offsets(ntr), _offsets([len(u[0]) for u in uniq])
-    ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
-    eoff = _offsets([S * n * f * k for n, f, k in zip(ntr, nf, npos)])
     m0p = _bloch_m0(A, m0)
     out = [np.zeros(int(eoff[-1])) for _ in range(3)]
     fin = [np.zeros(int(ooff[-1])) for _ in range(3)] if final else [C.cast(None, _dp)] * 3
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_batch(ctx._h, *A.head, ntr_a.ctypes.data_as(_ip), _lptr(roff), _ptr(cs), _ptr(sn),
-                                                gidx.ctypes.data_as(_ip), _lptr(goff), _ptr(gains_d), ech.ctypes.data_as(_ip),
-                                                _ptr(mq), int(bool(demod)), *[_plane(v) for v in m0p], *[_ptr(v) for v in out],
+    rc = load_library().mbfir_bloch_train_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], *[_ptr(v) for v in out],
                                                 *[_plane(v) for v in fin])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
@@ -1799,6 +1813,68 @@ def bloch_prop_batch(pulses, df, dp, *, echo=None, scales=(1.0,), ctx=None):
         mat = lambda v: v[9 * lo:9 * hi].reshape(shape + (3, 3)).swapaxes(-1, -2)          # column-major: entry (i, j) at i + 3 j
         res.append((mat(a), b[3 * lo:3 * hi].reshape(shape + (3,)), mat(ae), be[3 * lo:3 * hi].reshape(shape + (3,))))
     return res
+
+
+def _train_cotangents(who, what, cot, A, lead):
+    """cot: None, or per pulse (cx, cy, cz), each of shape (S,) + lead[q] + (nf, npos) -> None or the three concatenated planes"""
+    if cot is None:
+        return None
+    cot = list(cot)
+    if len(cot) != A.P:
+        raise ValueError("%s: %d %s cotangent triples for %d pulses" % (who, len(cot), what, A.P))
+    planes = [[], [], []]
+    for q, tri in enumerate(cot):
+        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+            raise ValueError("%s: the %s cotangent of pulse %d must be a triple (cx, cy, cz)" % (who, what, q))
+        tri = [np.asarray(v, dtype=np.float64) for v in tri]
+        shape = (A.S,) + lead[q] + (A.nf[q], A.npos[q])
+        if any(v.shape != shape for v in tri):
+            raise ValueError("%s: the %s cotangents of pulse %d have shapes %s, %s and %s, the forward call returns %s"
+                             % ((who, what, q) + tuple(v.shape for v in tri) + (shape,)))
+        for c in range(3):
+            planes[c].append(tri[c].ravel())
+    return [_vec(np.concatenate(p)) for p in planes]
+
+
+def bloch_train_vjp_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
+                          meq=1.0, demod=False, grad_m0=False, ctx=None):
+    """The adjoint of bloch_train_batch with respect to b1 and the initial magnetisation (mbfir_bloch_train_vjp_batch, DESIGN
+    section 8z): pulses, df, dp, ntr, phases, gains, echo, scales, m0, meq and demod as for bloch_train_batch.  cot: None, or one
+    (cx, cy, cz) per pulse, the cotangents of the echoes that bloch_train_batch returns, each of shape (S, ntr, nf, npos);
+    cot_final: None, or one (cx, cy, cz) per pulse, the cotangents of the final state, each of shape (S, nf, npos); not both None.
+    Returns a list of complex (ntime,) gradients dL/dRe b1 + i dL/dIm b1 of the period's samples, summed over the points, the
+    scales and the repetitions (repetition k plays gains[k] exp(i phases[k]) b1: that factor's chain rule is included); with
+    grad_m0, a list of (grad_b1, (gmx, gmy, gmz)), the second being dL/dm0 of every (scale, frequency, position), each of shape
+    (S, nf, npos) (one m0 serves every scale: its gradient is their sum over the scales).  One upload, four launches, one
+    download; the cost is a small multiple of the forward train's.  Deterministic: a pulse's gradient bits depend only on the
+    pulse, its grids, its train, its cotangents and the scales, and dL/dm0 has the same bits for any m0 and any meq.  The gains,
+    the phases, gr, tp, t1, t2, df, dp and meq are not differentiated."""
+    who = "bloch_train_vjp_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff, eoff = Tn.A, Tn.ntr, Tn.ooff, Tn.eoff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if cot is None and cot_final is None:
+        raise ValueError("%s: neither echo cotangents nor final cotangents are given" % who)
+    ce = _train_cotangents(who, "echo", cot, A, [(n,) for n in ntr])
+    cf = _train_cotangents(who, "final", cot_final, A, [()] * P)
+    toff = _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    m0p = _bloch_m0(A, m0)
+    grad = [np.zeros(int(toff[-1])) for _ in range(2)]
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_vjp_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p],
+                                                    *([nul] * 3 if ce is None else [_ptr(v) for v in ce]),
+                                                    *([nul] * 3 if cf is None else [_ptr(v) for v in cf]), _ptr(grad[0]),
+                                                    _ptr(grad[1]), *[_plane(v) for v in gm])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all = grad[0] + 1j * grad[1]
+    res = [g_all[toff[q]:toff[q + 1]] for q in range(P)]
+    if not grad_m0:
+        return res
+    return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
 
 
 def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):

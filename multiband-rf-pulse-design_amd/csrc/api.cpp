@@ -1472,26 +1472,22 @@ static int bloch_prop_check(mbfir_ctx* ctx, const char* who, int npulse, const l
     return 0;
 }
 
-int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
-                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
-                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
-                            const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
-                            const int* ntr, const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
-                            const long* goff, const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
-                            const double* m0y, const double* m0z, double* ex, double* ey, double* ez, double* fx, double* fy,
-                            double* fz) {
-    if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_batch: " + why; return MBFIR_E_ARG; };
-    std::vector<long> npoint;
-    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
-                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_batch_check(ctx, "bloch_train_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
-                                        arrays, npoint))
+// What the train and its adjoint check, in this order: bloch_batch_check, ntr, the offsets, the distinct gains, bloch_prop_check, the
+// echo planes' size and the workgroups, the tables' values, meq and m0.  npoint and ncomb (npulse entries each) receive the points
+// and the (scale, distinct gain) combinations per pulse.
+static int bloch_train_check(mbfir_ctx* ctx, const char* who, int npulse, const long* toff, const long* tsoff, const double* t1,
+                             const double* t2, int nfgrid, const long* foff, int npgrid, const long* poff, int nscale, bool arrays,
+                             const int* ntr, const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                             const long* goff, const double* gains, const int* echo, const double* meq, const double* m0x,
+                             const double* m0y, const double* m0z, std::vector<long>& npoint, std::vector<long>& ncomb) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0, arrays, npoint))
         return e;
     for (int p = 0; p < npulse; ++p)
         if (ntr[p] < 1) return bad("ntr of pulse " + std::to_string(p) + " must be at least 1");
     if (roff[0] != 0 || goff[0] != 0) return bad("inconsistent offsets: roff or goff does not start at 0");
-    std::vector<long> ncomb(npulse), ntout(npulse);
+    std::vector<long> ntout(npulse);
+    ncomb.assign(npulse, 0);
     for (int p = 0; p < npulse; ++p) {
         if (roff[p + 1] - roff[p] != ntr[p])
             return bad("inconsistent offsets: roff of pulse " + std::to_string(p) + " does not span its ntr repetitions");
@@ -1500,7 +1496,7 @@ int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const 
         ncomb[p] = G * nscale;
         ntout[p] = ntr[p];
     }
-    if (const int e = bloch_prop_check(ctx, "bloch_train_batch", npulse, toff, echo, ncomb.data(), npoint.data())) return e;
+    if (const int e = bloch_prop_check(ctx, who, npulse, toff, echo, ncomb.data(), npoint.data())) return e;
     // the sizes before the tables are read: a table is as long as ntr says
     if (roff[npulse] > (1L << 56) || !sim_sizes(npulse, nscale, npoint.data(), ntout.data()))
         return bad("the output size or the workgroup count overflows");
@@ -1515,12 +1511,79 @@ int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const 
     for (int p = 0; p < npulse; ++p)
         if (!std::isfinite(meq[p])) return bad("meq of pulse " + std::to_string(p) + " is not finite");
     if ((m0x || m0y || m0z) && !(m0x && m0y && m0z)) return bad("m0x, m0y and m0z are given together or not at all");
+    return 0;
+}
+
+int mbfir_bloch_train_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
+                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                            const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                            const int* ntr, const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                            const long* goff, const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                            const double* m0y, const double* m0z, double* ex, double* ey, double* ez, double* fx, double* fy,
+                            double* fz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
+        return e;
     if ((ex || ey || ez) && !(ex && ey && ez)) return bad("the echo planes are given together or not at all");
     if ((fx || fy || fz) && !(fx && fy && fz)) return bad("the final planes are given together or not at all");
     if (!ex && !fx) return bad("neither the echo planes nor the final planes are wanted");
     MBFIR_TRY(ctx, bloch_train_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
                                          t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff, cosphi,
                                          sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ex, ey, ez, fx, fy, fz));
+}
+
+// The train's adjoint (blochtrainvjp.hip) keeps one double2 partial per (combination, chunk of 64 points, sample), 3 x 256
+// checkpoint doubles per (scale, chunk of 256 points, group of 8 repetitions) and per (combination, chunk of 64 points, group of 8
+// samples), and launches one workgroup per (combination, chunk of 64 points): false when a count overflows, exceeds 2^56 or, for
+// the workgroups, 2^31 - 1.
+static bool bloch_train_vjp_fits(int npulse, int nscale, const long* toff, const int* ntr, const long* ncomb, const long* npoint) {
+    long part = 0, ckr = 0, ckp = 0, nwg = 0;
+    for (int p = 0; p < npulse; ++p) {
+        const long n = toff[p + 1] - toff[p], nch = (npoint[p] + 255) / 256, nch64 = (npoint[p] + 63) / 64;
+        long w, a, b, c;
+        if (__builtin_mul_overflow(ncomb[p], nch64, &w) || __builtin_add_overflow(nwg, w, &nwg) ||
+            __builtin_mul_overflow(w, n, &a) || __builtin_add_overflow(part, a, &part) ||
+            __builtin_mul_overflow(w, (n + 7) / 8 * 768, &b) || __builtin_add_overflow(ckp, b, &ckp) ||
+            __builtin_mul_overflow(nch * nscale, ((long)ntr[p] + 7) / 8 * 768, &c) || __builtin_add_overflow(ckr, c, &ckr))
+            return false;
+    }
+    return part <= (1L << 56) && ckr <= (1L << 56) && ckp <= (1L << 56) && nwg <= 2147483647L;
+}
+
+int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
+                                const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_vjp_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_vjp_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
+        return e;
+    if ((cex || cey || cez) && !(cex && cey && cez)) return bad("the echo cotangents are given together or not at all");
+    if ((cfx || cfy || cfz) && !(cfx && cfy && cfz)) return bad("the final cotangents are given together or not at all");
+    if (!cex && !cfx) return bad("neither echo cotangents nor final cotangents are given");
+    if (!g_re || !g_im) return bad("a gradient plane is null");
+    if ((gmx || gmy || gmz) && !(gmx && gmy && gmz)) return bad("gmx, gmy and gmz are given together or not at all");
+    if (!bloch_train_vjp_fits(npulse, nscale, toff, ntr, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_train_vjp_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                             t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
+                                             cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, cex, cey, cez, cfx,
+                                             cfy, cfz, g_re, g_im, gmx, gmy, gmz));
 }
 
 int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,

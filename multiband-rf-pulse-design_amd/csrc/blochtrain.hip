@@ -10,24 +10,14 @@
 //   k_bloch_train_run:  per (scale, point) walks the repetitions, about sixty flops each.
 // The 24 doubles of a (combination, point) lie plane by plane, [combination][entry][point], so both kernels read and write them
 // coalesced.  cos phi_k, sin phi_k, the distinct gains and the products scale x gain are formed on the host in float64: they are
-// inputs of the recursion, like E1 and E2.  There is no matrix inverse here and no bit relation to mode 1.
+// inputs of the recursion, like E1 and E2.  There is no matrix inverse here and no bit relation to mode 1.  The descriptor, the
+// repetition's helpers and the staging are in sim_dev.h, shared with the train's adjoint (blochtrainvjp.hip).
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
 #include <cmath>
 
 namespace mbfir {
-
-constexpr int TRAIN_ENT = 24;                  // A (9), B (3), A_e (9), B_e (3), column-major like Rot3
-
-// Per-pulse descriptor of a train.  Combination c = scale ngain + gain of the pulse has its amplitude at amp[a_off + c] and its
-// planes from w_off + c 24 npair; repetition k has (cos, sin, gain index) at r_off + k; the echoes go to e_off + (scale ntr + k) npair
-// + point.
-struct TrainPulseDev {
-    long w_off, a_off, r_off, e_off;
-    int ntr, ngain, echo, pad;
-    double meq;
-};
 
 // blocks: (pulse, combination, chunk).  ws receives the planes.
 __global__ __launch_bounds__(256) void k_bloch_train_prop(const double* __restrict__ in, const double* __restrict__ df,
@@ -84,25 +74,6 @@ __global__ __launch_bounds__(256) void k_bloch_train_prop(const double* __restri
     for (int e = 0; e < 9; ++e) w[(12 + e) * npair] = Ae[e];
 #pragma unroll
     for (int e = 0; e < 3; ++e) w[(21 + e) * npair] = Be[e];
-}
-
-// M v + meq b for a column-major M, every product and sum where it is written (explicit fma, contraction off), so that a
-// repetition has the same bits whether its planes were hoisted out of the loop or loaded inside it.
-__device__ __forceinline__ void train_affine(const double* M, const double* b, double meq, const double v[3], double o[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = fma(meq, b[i], fma(M[6 + i], v[2], fma(M[3 + i], v[1], M[i] * v[0])));
-}
-// Z(+phi) v and Z(-phi) v about z from (c, s) = (cos phi, sin phi), in place.
-__device__ __forceinline__ void train_zp(double c, double s, double v[3]) {
-#pragma clang fp contract(off)
-    const double x = fma(c, v[0], -(s * v[1])), y = fma(s, v[0], c * v[1]);
-    v[0] = x; v[1] = y;
-}
-__device__ __forceinline__ void train_zm(double c, double s, double v[3]) {
-#pragma clang fp contract(off)
-    const double x = fma(c, v[0], s * v[1]), y = fma(c, v[1], -(s * v[0]));
-    v[0] = x; v[1] = y;
 }
 
 // blocks: (pulse, scale, chunk), the forward simulators' table.  rep = (cos phi_k, sin phi_k) and gidx = the gain index of every
@@ -172,14 +143,6 @@ __global__ __launch_bounds__(256) void k_bloch_train_run(const double* __restric
 // (bloch_stage, mode 0: m0 per (scale, frequency, position)) plus the amplitudes, the train descriptors, the repetition tables and
 // the propagator kernel's block table; one upload, the launches, one download.  The output region is the echo planes (3 E), the
 // final planes (3 O), then the propagators' planes, which stay on the device unless the caller is mbfir_bloch_prop_batch.
-namespace {
-struct TrainStaged {
-    BlochStaged B;
-    size_t o_amp = 0, o_tr = 0, o_rep = 0, o_gi = 0, o_pb = 0;
-    long E = 0, W = 0, nprop = 0;                              // echo entries per plane, workspace doubles, workgroups of kernel 1
-    std::vector<TrainPulseDev> tr;
-};
-
 void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws) {
     Staging& S = Ts.B.S;
     hipLaunchKernelGGL(k_bloch_train_prop, dim3((unsigned)Ts.nprop), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
@@ -231,7 +194,6 @@ void train_stage(TrainStaged& Ts, int npulse, int nscale, const double* scales, 
             for (int k = 0; k < nch; ++k) *pb++ = SimBlock{p, c, k, 0};
     }
 }
-}  // namespace
 
 void bloch_train_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,

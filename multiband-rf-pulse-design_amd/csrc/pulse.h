@@ -138,6 +138,19 @@ void bloch_prop_batch_run(int device, void* stream, int npulse, const long* toff
                           const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
                           int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                           const double* scales, const int* echo, double* a, double* b, double* ae, double* be);
+// Adjoint of bloch_train_batch_run with respect to b1 and m0 (blochtrainvjp.hip k_bloch_train_run_vjp, k_bloch_train_prop_vjp,
+// k_bloch_train_vjp_fold after blochtrain.hip's k_bloch_train_prop): the forward call's inputs, the cotangents of the
+// echoes (ce*: all null = none) and of the final state (cf*: all null = none) where the forward call writes them; g_*: the gradient
+// per b1 sample; gm*: dL / d m0 in the final planes' layout (all null: not downloaded).  One upload, four launches, one download.
+void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                               int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                               const double* scales, const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                               const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                               const double* m0x, const double* m0y, const double* m0z, const double* cex, const double* cey,
+                               const double* cez, const double* cfx, const double* cfy, const double* cfz, double* g_re, double* g_im,
+                               double* gmx, double* gmy, double* gmz);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1

@@ -639,6 +639,51 @@ void bloch_stage(BlochStaged& B, int npulse, const long* toff, const double* b1_
                  const double* dy, const double* dz, int nscale, const double* scales, int mode, const double* m0x,
                  const double* m0y, const double* m0z);
 
+// What the pulse train (blochtrain.hip) shares with its adjoint (blochtrainvjp.hip), moved here from
+// blochtrain.hip token for token: the planes' count, the per-pulse descriptor, the helpers of one repetition and the host staging.
+constexpr int TRAIN_ENT = 24;                  // A (9), B (3), A_e (9), B_e (3), column-major like Rot3
+
+// Per-pulse descriptor of a train.  Combination c = scale ngain + gain of the pulse has its amplitude at amp[a_off + c] and its
+// planes from w_off + c 24 npair; repetition k has (cos, sin, gain index) at r_off + k; the echoes go to e_off + (scale ntr + k) npair
+// + point.
+struct TrainPulseDev {
+    long w_off, a_off, r_off, e_off;
+    int ntr, ngain, echo, pad;
+    double meq;
+};
+
+// M v + meq b for a column-major M, every product and sum where it is written (explicit fma, contraction off), so that a
+// repetition has the same bits whether its planes were hoisted out of the loop or loaded inside it.
+__device__ __forceinline__ void train_affine(const double* M, const double* b, double meq, const double v[3], double o[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = fma(meq, b[i], fma(M[6 + i], v[2], fma(M[3 + i], v[1], M[i] * v[0])));
+}
+// Z(+phi) v and Z(-phi) v about z from (c, s) = (cos phi, sin phi), in place.
+__device__ __forceinline__ void train_zp(double c, double s, double v[3]) {
+#pragma clang fp contract(off)
+    const double x = fma(c, v[0], -(s * v[1])), y = fma(s, v[0], c * v[1]);
+    v[0] = x; v[1] = y;
+}
+__device__ __forceinline__ void train_zm(double c, double s, double v[3]) {
+#pragma clang fp contract(off)
+    const double x = fma(c, v[0], s * v[1]), y = fma(c, v[1], -(s * v[0]));
+    v[0] = x; v[1] = y;
+}
+
+struct TrainStaged {
+    BlochStaged B;
+    size_t o_amp = 0, o_tr = 0, o_rep = 0, o_gi = 0, o_pb = 0;
+    long E = 0, W = 0, nprop = 0;                              // echo entries per plane, workspace doubles, workgroups of kernel 1
+    std::vector<TrainPulseDev> tr;
+};
+// blochtrain.hip: the train's sections of one call after bloch_stage (arguments as bloch_train_batch_run's), and the launch of
+// k_bloch_train_prop on them, which leaves the propagators' planes in ws.
+void train_stage(TrainStaged& Ts, int npulse, int nscale, const double* scales, const int* ntr, const long* roff,
+                 const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                 const double* meq);
+void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws);
+
 // The sections the Bloch least-squares calls add to the forward staging (blochgn.hip bloch_gn_stage, moved here token for token so
 // that blochssgn.hip stages through it too), and the sizes of what stays on the device.
 struct BlochGnSections {

@@ -15,6 +15,8 @@ grad: the backward is then one mbfir.bloch_vjp_gr_batch call for every gradient 
 the b1 call, with its bits.  A forward-mode tangent for gr or df raises NotImplementedError.  With steady_state=True
 it returns the steady state of the period instead (bloch_batch mode 1), differentiable in b1 through mbfir.bloch_ss_vjp_batch and
 mbfir.bloch_ss_jvp_batch (section 8t) and, in reverse mode, in gr and df through mbfir.bloch_ss_vjp_gr_batch (section 8x).
+`bloch_train` runs mbfir.bloch_train_batch on one period (the echo-by-echo transient of a pulse train) and is differentiable in
+reverse mode in b1 and in m0, its backward being one mbfir.bloch_train_vjp_batch call (section 8z).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -401,6 +403,74 @@ def bloch(b1, gr, tp, t1, t2, df, dp, *, nucleus="C-13", scales=(1.0,), m0=None,
     gr = gr if hasattr(gr, "detach") else _host(gr, np.float64)       # a tensor stays an input of the graph
     df = df if hasattr(df, "detach") else _host(df, np.float64)
     return fn.apply(b1, m0, gr, df, (_host(tp, np.float64), float(t1), float(t2), nucleus), _host(dp, np.float64), tuple(scales))
+
+
+@functools.lru_cache(maxsize=None)
+def _train_function():
+    """The autograd.Function class of `bloch_train`, built when torch is first needed (forward and setup_context separate, as
+    above).  kw: the constants of the train as a tuple of (name, value) pairs."""
+    import torch
+
+    import mbfir
+
+    class BlochTrain(torch.autograd.Function):
+        @staticmethod
+        def forward(b1, m0, rest, df, dp, ntr, kw, final):
+            if not torch.is_tensor(b1) or b1.dtype != torch.complex128 or b1.dim() != 1:
+                raise ValueError("torchsim: b1 must be a 1-D complex128 tensor")
+            if torch.is_tensor(m0) and m0.requires_grad and (m0.dtype != torch.float64 or m0.dim() != 3 or m0.shape[0] != 3):
+                raise ValueError("torchsim: an m0 that requires grad must be a float64 tensor of shape (3, nf, npos)")
+            m0h = _host(m0, np.float64)
+            res, = mbfir.bloch_train_batch([(_host(b1, np.complex128),) + rest], df, dp, ntr, m0=None if m0h is None else tuple(m0h),
+                                           final=final, **dict(kw))
+            planes = res[0] + res[1] if final else res
+            return tuple(torch.from_numpy(np.ascontiguousarray(v)).to(b1.device) for v in planes)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, m0, rest, df, dp, ntr, kw, final = inputs
+            ctx.args = (_host(m0, np.float64), rest, df, dp, ntr, kw, final)
+            ctx.m0_like = (m0.shape, m0.device) if torch.is_tensor(m0) else None          # where m0's gradient goes
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch_train is not implemented (reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, *cots):
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            want_m0 = ctx.needs_input_grad[1]
+            cot = tuple(_host(c, np.float64) for c in cots)
+            res, = mbfir.bloch_train_vjp_batch([(_host(b1, np.complex128),) + rest], df, dp, ntr, [cot[:3]],
+                                               cot_final=[cot[3:]] if final else None, m0=None if m0h is None else tuple(m0h),
+                                               grad_m0=want_m0, **dict(kw))
+            grad, gm = res if want_m0 else (res, None)
+            gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if ctx.needs_input_grad[0] else None
+            if want_m0:                                                 # one m0 serves every scale: its gradient is their sum
+                gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
+            return gb, gm, None, None, None, None, None, None
+
+    return BlochTrain
+
+
+def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
+                meq=1.0, demod=False, final=False):
+    """The echoes (mx, my, mz) of mbfir.bloch_train_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, ntr, ...), each a float64 tensor
+    of shape (S, ntr, nf, npos) with bloch_train_batch's bits; with final, ((mx, my, mz), (fx, fy, fz)), the second being the state
+    after the last repetition, each of shape (S, nf, npos).  Differentiable in reverse mode in b1 (a 1-D complex128 tensor) and in
+    m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient is summed over the scales); the
+    backward is one mbfir.bloch_train_vjp_batch call.  Every other argument is a constant of the graph: gr, tp,
+    t1, t2, df, dp, ntr, the phases, the gains, echo, the scales, meq, and an m0 given as (mx, my, mz), as an array of shape (3, nf,
+    npos) or as None (equilibrium).  A forward-mode tangent raises NotImplementedError."""
+    if m0 is not None and not hasattr(m0, "detach"):
+        m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
+    kw =(("phases", _host(phases, np.float64)), ("gains", _host(gains, np.float64)), ("echo", echo), ("scales", tuple(scales)),
+          ("meq", float(meq)), ("demod", bool(demod)))
+    rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
+    out = _train_function().apply(b1, m0, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw, bool(final))
+    return (out[:3], out[3:]) if final else out
 
 
 def abr(rf, x, g=None, *, scales=(1.0,), hard_pulse=False):
