@@ -538,6 +538,41 @@ int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
                                 const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
                                 const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
                                 const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+/* ---- Tangent of the pulse train with respect to b1 and the initial magnetisation ----------------------------------------------------
+ * The Jacobian-vector product of mbfir_bloch_train_batch's echoes and final state: d/de of both at (b1 + e v, m0 + e dm0), e = 0,
+ * for ndir directions per pulse (repetition k plays gains[k] exp(i phi_k) (b1 + e v): the chain rule through that product is
+ * included).  It takes mbfir_bloch_train_batch's arguments through demod and m0x / m0y / m0z, then
+ *   ndir: the directions per pulse, at least 1.
+ *   v_re / v_im: direction k of pulse p at ndir toff[p] + k n_p + t, as mbfir_bloch_jvp_batch's.
+ *   dm0x / dm0y / dm0z: the m0 directions, pulse p from ndir times its final-plane offset, (direction, scale, frequency, position)
+ *     row-major; all three NULL = zero.
+ *   ex / ey / ez, fx / fy / fz: the echoes and the final state with mbfir_bloch_train_batch's bits; either triple all NULL = not
+ *     downloaded.
+ *   dex / dey / dez: the tangent echoes, pulse p from ndir times its echo offset, (direction, scale, repetition, frequency,
+ *     position) row-major (with demod != 0: of the demodulated echoes); all three NULL = not wanted.
+ *   dfx / dfy / dfz: the tangent of the final state, laid out as dm0; all three NULL = not wanted.  Not both tangent triples NULL.
+ * One upload, three launches, one download: the forward call's propagator launch; the period's samples swept once per (pulse,
+ * scale, distinct gain, 64 points, group of mbfir_test_bloch_train_jvp_group(0) directions), which leaves the tangents of the 24
+ * doubles of (A, B, A_e, B_e) per direction in a device workspace; and the repetitions, per (scale, 256 points, group of
+ * mbfir_test_bloch_train_jvp_group(1) directions).  No atomics and no reduction: a tangent's bits depend only on its pulse, scale,
+ * point, train and direction.  The gains, the phases, gr, tp, t1, t2, df, the positions and meq are not differentiated.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with
+ * its reason in mbfir_last_error and no device work done: v_re or v_im NULL; a triple only partly given; both tangent triples NULL;
+ * ndir < 1; ndir times the samples, the echoes or the workspace, or a workgroup count, that overflows.  A refused call leaves the
+ * context usable.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ndir,
+                                const double* v_re, const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z,
+                                double* ex, double* ey, double* ez, double* fx, double* fy, double* fz, double* dex, double* dey,
+                                double* dez, double* dfx, double* dfy, double* dfz);
+/* mbfir_test_bloch_train_jvp_group (host only): the directions one workgroup of the call above carries, in the period's kernel
+ * (which = 0) and in the repetitions' kernel (which != 0); compile-time constants. */
+int mbfir_test_bloch_train_jvp_group(int which);
 /* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
  * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
  * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent

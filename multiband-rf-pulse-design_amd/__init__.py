@@ -155,6 +155,10 @@ SYMBOLS = {
     "mbfir_bloch_train_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
+    "mbfir_bloch_train_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                              _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                             [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 17),
+    "mbfir_test_bloch_train_jvp_group": (C.c_int, [C.c_int]),
     "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -1877,6 +1881,77 @@ def bloch_train_vjp_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
 
 
+def _train_tangents_m0(who, tangents_m0, A, K):
+    """tangents_m0: per pulse a triple (dmx, dmy, dmz), each broadcastable to (K, nf, npos), the same at every scale -> the three
+    concatenated planes of the C call, (direction, scale, frequency, position) per pulse"""
+    tangents_m0 = list(tangents_m0)
+    if len(tangents_m0) != A.P:
+        raise ValueError("%s: %d m0 tangent triples for %d pulses" % (who, len(tangents_m0), A.P))
+    planes = [[], [], []]
+    for q, tri in enumerate(tangents_m0):
+        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+            raise ValueError("%s: the m0 tangent of pulse %d must be a triple (dmx, dmy, dmz)" % (who, q))
+        shape = (K, A.nf[q], A.npos[q])
+        for c in range(3):
+            v = np.asarray(tri[c], dtype=np.float64)
+            try:
+                v = np.broadcast_to(v, shape)
+            except ValueError:
+                raise ValueError("%s: an m0 tangent of pulse %d has shape %s, which does not broadcast to %s"
+                                 % (who, q, v.shape, shape)) from None
+            planes[c].append(np.broadcast_to(v[:, None], (K, A.S) + shape[1:]).ravel())
+    return [_vec(np.concatenate(p)) for p in planes]
+
+
+def bloch_train_jvp_batch(pulses, df, dp, ntr, tangents, *, tangents_m0=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,),
+                          m0=None, meq=1.0, demod=False, echoes=True, final=False, primal=False, ctx=None):
+    """The tangent of bloch_train_batch with respect to b1 and the initial magnetisation (mbfir_bloch_train_jvp_batch, DESIGN
+    section 8aa): pulses, df, dp, ntr, phases, gains, echo, scales, m0, meq and demod as for bloch_train_batch.  tangents: per pulse a
+    complex direction of the period's b1 of shape (n,), or K of them of shape (K, n), the same K for every pulse (repetition k plays
+    gains[k] exp(i phases[k]) (b1 + e v): that factor's chain rule is included); tangents_m0: None (m0 does not move) or per pulse
+    a triple (dmx, dmy, dmz), each broadcastable to (K, nf, npos): the direction of m0 that goes with each b1 direction, the same at
+    every scale, as m0 is.  Returns, per pulse, the tangent echoes (dex, dey, dez), d/de of the echoes at e = 0, each of shape (K, S,
+    ntr, nf, npos), without the K axis for a 1-D tangent; with final, ((dex, dey, dez), (dfx, dfy, dfz)), the second being the
+    tangent of the state after the last repetition, each of shape (K, S, nf, npos); with echoes=False (which requires final) the
+    final tangents alone.  With primal, per pulse (primal, tangent), the primal being what bloch_train_batch returns for the same
+    final (with echoes=False: its final state alone), with its bits.  Real-linear in (v, dm0).  One upload, three launches, one
+    download; a tangent's bits depend only on its pulse, scale, point, train and direction.  The gains, the phases, gr, tp, t1, t2,
+    df, dp and meq are not differentiated."""
+    who = "bloch_train_jvp_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff, eoff = Tn.A, Tn.ntr, Tn.ooff, Tn.eoff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if not echoes and not final:
+        raise ValueError("%s: echoes=False requires final=True: neither the tangent echoes nor the final tangents are wanted" % who)
+    K, keep, vplanes = _tangents(who, tangents, [range(n) for n in A.nt])
+    nul = C.cast(None, _dp)
+    dm0 = [nul] * 3 if tangents_m0 is None else _train_tangents_m0(who, tangents_m0, A, K)
+    m0p = _bloch_m0(A, m0)
+    E, O = int(eoff[-1]), int(ooff[-1])
+    pe = [np.zeros(E) for _ in range(3)] if primal and echoes else [nul] * 3
+    pf = [np.zeros(O) for _ in range(3)] if primal and final else [nul] * 3
+    te = [np.zeros(K * E) for _ in range(3)] if echoes else [nul] * 3
+    tf = [np.zeros(K * O) for _ in range(3)] if final else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_jvp_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], K, *[_ptr(v) for v in vplanes],
+                                                    *[_plane(v) for v in dm0], *[_plane(v) for v in pe], *[_plane(v) for v in pf],
+                                                    *[_plane(v) for v in te], *[_plane(v) for v in tf])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+
+    def pick(ev, fv, k, lead, q):
+        """The echo and final planes of pulse q, k directions in front with the axes `lead` -> what the flags ask for"""
+        e = tuple(v[k * eoff[q]:k * eoff[q + 1]].reshape(lead + (S, ntr[q], nf[q], npos[q])) for v in ev) if echoes else None
+        f = tuple(v[k * ooff[q]:k * ooff[q + 1]].reshape(lead + (S, nf[q], npos[q])) for v in fv) if final else None
+        return (e, f) if echoes and final else e if echoes else f
+    res = []
+    for q in range(P):
+        tan = pick(te, tf, K, (K,) if keep else (), q)
+        res.append((pick(pe, pf, 1, (), q), tan) if primal else tan)
+    return res
+
+
 def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):
     """Loss and gradient of a weighted least-squares fit of bloch_batch's end point (mode 0), relaxation included, in one device
     call (mbfir_bloch_lsq_batch): pulses, df, dp, scales and m0 as for bloch_batch.  targets and weights: per
@@ -2537,6 +2612,13 @@ def bloch_ss_jvp_group():
 def bloch_jvp_group():
     """The directions one workgroup of bloch_jvp_batch carries (mbfir_test_bloch_jvp_group)."""
     return int(load_library().mbfir_test_bloch_jvp_group())
+
+
+def bloch_train_jvp_group():
+    """The directions one workgroup of bloch_train_jvp_batch carries (mbfir_test_bloch_train_jvp_group): (in the period's kernel, in
+    the repetitions' kernel)."""
+    lib = load_library()
+    return int(lib.mbfir_test_bloch_train_jvp_group(0)), int(lib.mbfir_test_bloch_train_jvp_group(1))
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

@@ -151,6 +151,23 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
                                const double* m0x, const double* m0y, const double* m0z, const double* cex, const double* cey,
                                const double* cez, const double* cfx, const double* cfy, const double* cfz, double* g_re, double* g_im,
                                double* gmx, double* gmy, double* gmz);
+// Tangent of bloch_train_batch_run with respect to b1 and m0 (blochtrainjvp.hip k_bloch_train_prop_jvp, k_bloch_train_run_jvp after
+// blochtrain.hip's k_bloch_train_prop): the forward call's inputs; ndir >= 1 directions per pulse, v and dm0* as
+// bloch_jvp_batch_run's; e* / f*: the forward call's outputs with its bits (either triple all null: not downloaded); de*: the
+// tangent echoes, pulse p from ndir times its echo offset, (direction, scale, repetition, point) row-major; df*: the tangent of the
+// final state, laid out as dm0 (either triple all null: not wanted, not both).  One upload, three launches, one download.
+// bloch_train_jvp_group(0 / 1): the directions one workgroup of the period's / the repetitions' kernel carries.
+int bloch_train_jvp_group(int which);
+void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                               int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                               const double* scales, const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                               const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                               const double* m0x, const double* m0y, const double* m0z, int ndir, const double* v_re,
+                               const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z, double* ex, double* ey,
+                               double* ez, double* fx, double* fy, double* fz, double* dex, double* dey, double* dez, double* dfx,
+                               double* dfy, double* dfz);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1

@@ -670,6 +670,18 @@ __device__ __forceinline__ void train_zm(double c, double s, double v[3]) {
     const double x = fma(c, v[0], s * v[1]), y = fma(c, v[1], -(s * v[0]));
     v[0] = x; v[1] = y;
 }
+// The tangent of train_affine (blochtrainjvp.hip): M du + dM u + meq db for column-major M and dM, one chain of fma
+// from the first product M[i] du[0] (contraction off), so that a tangent's bits depend neither on where its planes were loaded nor
+// on its place in a direction group.
+__device__ __forceinline__ void train_affine_jvp(const double* M, const double* dM, const double* db, double meq, const double u[3],
+                                                 const double du[3], double o[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double lin = fma(M[6 + i], du[2], fma(M[3 + i], du[1], M[i] * du[0]));
+        o[i] = fma(meq, db[i], fma(dM[6 + i], u[2], fma(dM[3 + i], u[1], fma(dM[i], u[0], lin))));
+    }
+}
 
 struct TrainStaged {
     BlochStaged B;

@@ -16,7 +16,8 @@ the b1 call, with its bits.  A forward-mode tangent for gr or df raises NotImple
 it returns the steady state of the period instead (bloch_batch mode 1), differentiable in b1 through mbfir.bloch_ss_vjp_batch and
 mbfir.bloch_ss_jvp_batch (section 8t) and, in reverse mode, in gr and df through mbfir.bloch_ss_vjp_gr_batch (section 8x).
 `bloch_train` runs mbfir.bloch_train_batch on one period (the echo-by-echo transient of a pulse train) and is differentiable in
-reverse mode in b1 and in m0, its backward being one mbfir.bloch_train_vjp_batch call (section 8z).
+reverse mode in b1 and in m0, its backward being one mbfir.bloch_train_vjp_batch call (section 8z); with forward_mode=True it also
+has the forward-mode tangent in both, one mbfir.bloch_train_jvp_batch call with one direction (section 8aa).
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -455,21 +456,53 @@ def _train_function():
     return BlochTrain
 
 
+@functools.lru_cache(maxsize=None)
+def _train_forward_function():
+    """BlochTrain with a forward-mode tangent: the same forward and backward, plus a jvp that is one mbfir.bloch_train_jvp_batch
+    call with one direction, in b1 and, when m0 is a tensor with a tangent, in m0."""
+    import torch
+
+    import mbfir
+
+    class BlochTrainForward(_train_function()):
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            _train_function().setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+
+        @staticmethod
+        def jvp(ctx, v, vm0, *_):
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            b1h = _host(b1, np.complex128)
+            vh = np.zeros_like(b1h) if v is None else _host(v, np.complex128)
+            dm0 = None if vm0 is None else [tuple(_host(vm0, np.float64))]
+            tan, = mbfir.bloch_train_jvp_batch([(b1h,) + rest], df, dp, ntr, [vh], tangents_m0=dm0,
+                                               m0=None if m0h is None else tuple(m0h), final=final, **dict(kw))
+            planes = tan[0] + tan[1] if final else tan
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in planes)
+
+    return BlochTrainForward
+
+
 def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
-                meq=1.0, demod=False, final=False):
+                meq=1.0, demod=False, final=False, forward_mode=False):
     """The echoes (mx, my, mz) of mbfir.bloch_train_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, ntr, ...), each a float64 tensor
     of shape (S, ntr, nf, npos) with bloch_train_batch's bits; with final, ((mx, my, mz), (fx, fy, fz)), the second being the state
     after the last repetition, each of shape (S, nf, npos).  Differentiable in reverse mode in b1 (a 1-D complex128 tensor) and in
     m0 when that is a float64 tensor of shape (3, nf, npos) that requires grad (its gradient is summed over the scales); the
     backward is one mbfir.bloch_train_vjp_batch call.  Every other argument is a constant of the graph: gr, tp,
     t1, t2, df, dp, ntr, the phases, the gains, echo, the scales, meq, and an m0 given as (mx, my, mz), as an array of shape (3, nf,
-    npos) or as None (equilibrium).  A forward-mode tangent raises NotImplementedError."""
+    npos) or as None (equilibrium).  A forward-mode tangent raises NotImplementedError unless forward_mode is set: then
+    torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as well, the tangent in b1 and in a tensor m0 being one
+    mbfir.bloch_train_jvp_batch call with one direction (section 8aa)."""
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
     kw =(("phases", _host(phases, np.float64)), ("gains", _host(gains, np.float64)), ("echo", echo), ("scales", tuple(scales)),
           ("meq", float(meq)), ("demod", bool(demod)))
     rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
-    out = _train_function().apply(b1, m0, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw, bool(final))
+    fn = _train_forward_function() if forward_mode else _train_function()
+    out = fn.apply(b1, m0, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw, bool(final))
     return (out[:3], out[3:]) if final else out
 
 
