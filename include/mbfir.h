@@ -573,6 +573,51 @@ int mbfir_bloch_train_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
 /* mbfir_test_bloch_train_jvp_group (host only): the directions one workgroup of the call above carries, in the period's kernel
  * (which = 0) and in the repetitions' kernel (which != 0); compile-time constants. */
 int mbfir_test_bloch_train_jvp_group(int which);
+
+/* ---- Fused least-squares and Gauss-Newton products of the pulse train -------------------------------------------------------------
+ * For the loss, per pulse,
+ *   L = 1/2 sum_s sum_k rw_k sum_points sum_c w_c (echo_{k,c} - t_c)^2 + 1/2 sum_s sum_points sum_c wf_c (m_{N,c} - tf_c)^2
+ * with echo and m_N what mbfir_bloch_train_batch returns under the same demod, mbfir_bloch_train_lsq_batch returns L, its gradient
+ * dL/dRe b1 + i dL/dIm b1 of the period's samples (mbfir_bloch_train_vjp_batch's conventions for scales and gains) and on request
+ * dL/dm0; mbfir_bloch_train_gn_batch returns H v = J' W J v for ndir directions of the period's b1, J the Jacobian of (echoes, final
+ * state) in b1 and W the weights, rw included.  Neither the echoes nor their cotangents ever leave the device.  Both take
+ * mbfir_bloch_train_batch's arguments through demod and m0x / m0y / m0z, then
+ *   ebcast: 0 = the echo planes below lie as the echoes do (S x ntr x nf x npos per pulse); 1 = they lie as the final planes do
+ *           (S x nf x npos per pulse) and are used at every repetition;
+ *   wx / wy / wz, tx / ty / tz (lsq) or wx / wy / wz (gn): the echo weights (>= 0, finite) and targets; all NULL = no echo term;
+ *   rw: one factor >= 0 per repetition, laid out as cosphi (pulse p from roff[p]); NULL = ones;
+ *   wfx .. tfz (lsq) or wfx / wfy / wfz (gn): the final weights and targets, laid out as the final planes; all NULL = no final term;
+ *   lsq: loss (npulse), g_re / g_im (the gradient per b1 sample), gmx / gmy / gmz (dL/dm0, the final planes' layout; all NULL = not
+ *        wanted);
+ *   gn:  ndir >= 1, v_re / v_im (direction k of pulse p at ndir toff[p] + k ntime_p, as mbfir_bloch_train_jvp_batch takes them),
+ *        h_re / h_im (the products, the same layout).
+ * At least one of the two terms must be present.  No atomics: a pulse's loss, gradient and products depend only on the pulse, its
+ * grids, its train, its planes and the scale list, and a direction's product depends neither on ndir nor on its place among the
+ * directions.  Targets equal to mbfir_bloch_train_batch's own output give L = 0 and a gradient of exact zeros.  The gains, the
+ * phases, gr, tp, t1, t2, df, the positions, meq and the scales are not differentiated; m0 is not a variable of gn.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with a
+ * message beginning "bloch_train_lsq_batch:" / "bloch_train_gn_batch:": ebcast outside {0, 1}, a partly given sextuple or triple,
+ * both terms absent, a NULL output or direction plane, ndir < 1, a negative or non-finite weight or rw, sizes that overflow.
+ * A NULL ctx returns MBFIR_E_ARG. */
+int mbfir_bloch_train_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
+                                const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                const double* tfz, double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                               const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                               int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                               const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                               const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                               const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz, int ndir,
+                               const double* v_re, const double* v_im, double* h_re, double* h_im);
 /* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
  * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
  * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent

@@ -159,6 +159,12 @@ SYMBOLS = {
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 17),
     "mbfir_test_bloch_train_jvp_group": (C.c_int, [C.c_int]),
+    "mbfir_bloch_train_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                              _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                             [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 19),
+    "mbfir_bloch_train_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                              _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                             [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 7 + [C.c_int] + [_dp] * 4),
     "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -2051,6 +2057,136 @@ def bloch_ss_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), ctx=N
     return _gn_result(rfs, K, keep, h)
 
 
+def _train_echo_planes(who, A, ntr, weights, targets):
+    """The echo term of the train's fused calls.  weights / targets (None: no targets, the products): per pulse a triple whose entries
+    are shaped (S, ntr, nf, npos), or (S, nf, npos) / (nf, npos) / a scalar for every repetition -> (ebcast, weight planes, target
+    planes): the broadcast form (the planes laid out as the final state's) when no pulse gives a repetition axis."""
+    sets = [("weight", weights)] + ([("target", targets)] if targets is not None else [])
+    arrs = []
+    for what, triples in sets:
+        triples = list(triples)
+        if len(triples) != A.P:
+            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(triples), what, A.P))
+        per = []
+        for q, tri in enumerate(triples):
+            if not isinstance(tri, (tuple, list)) or len(tri) != 3:
+                raise ValueError("%s: the %ss of pulse %d must be a triple (x, y, z)" % (who, what, q))
+            full = (A.S, ntr[q], A.nf[q], A.npos[q])
+            short = (A.S, A.nf[q], A.npos[q])
+            vs = [np.asarray(v, dtype=np.float64) for v in tri]
+            for v in vs:
+                if v.shape not in (full, short, short[1:], ()):
+                    raise ValueError("%s: a %s of pulse %d has shape %s, not %s, %s, %s or a scalar"
+                                     % (who, what, q, v.shape, full, short, short[1:]))
+                if what == "weight" and (not np.all(np.isfinite(v)) or np.any(v < 0)):
+                    raise ValueError("%s: a weight of pulse %d is negative or not finite" % (who, q))
+            per.append(vs)
+        arrs.append(per)
+    ebcast = not any(v.ndim == 4 for per in arrs for vs in per for v in vs)
+    out = []
+    for per in arrs:
+        planes = [[], [], []]
+        for q, vs in enumerate(per):
+            short = (A.S, A.nf[q], A.npos[q])
+            for c, v in enumerate(vs):
+                if ebcast:
+                    planes[c].append(np.broadcast_to(v, short).ravel())
+                else:
+                    v = v if v.ndim == 4 else np.broadcast_to(v, short)[:, None]
+                    planes[c].append(np.broadcast_to(v, (A.S, ntr[q]) + short[1:]).ravel())
+        out.append([_vec(np.concatenate(p)) for p in planes])
+    return int(ebcast), out[0], out[1] if targets is not None else None
+
+
+def _train_rep_weights(who, rep_weights, ntr):
+    """rep_weights: None, an array of ntr factors for every pulse, or a Python list of one array per pulse -> None or the table"""
+    if rep_weights is None:
+        return None
+    rw = np.concatenate(_train_tables(who, "rep_weights", rep_weights, ntr, False))
+    if not np.all(np.isfinite(rw)) or np.any(rw < 0):
+        raise ValueError("%s: a repetition weight is negative or not finite" % who)
+    return _vec(rw)
+
+
+def bloch_train_lsq_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
+                          phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, grad_m0=False, ctx=None):
+    """Loss and gradient of a weighted least-squares fit of bloch_train_batch's echoes and final state in one device call
+    (mbfir_bloch_train_lsq_batch): pulses, df, dp, ntr, phases, gains, echo, scales, m0, meq and demod as for
+    bloch_train_batch.  targets and weights: per pulse a triple (x, y, z) whose entries have the echoes' shape (S, ntr, nf, npos), or
+    (S, nf, npos) / (nf, npos) / a scalar for every repetition (weights >= 0); when no pulse gives a repetition axis only point-sized
+    planes go up to the device.  Both None: no echo term.  rep_weights: None, or a factor >= 0 per repetition (an array of ntr
+    values, or a list of one array per pulse): zeros leave echoes out of the fit.  targets_final / weights_final: None, or per
+    pulse a triple as bloch_lsq_batch takes them, for the state after the last repetition.  Returns a list of (L, grad) per pulse,
+    L = 1/2 sum_k rw_k sum w_c (echo_kc - t_c)^2 + 1/2 sum wf_c (m_Nc - tf_c)^2 over the components, the points and the scales, and
+    grad = dL/dRe b1 + i dL/dIm b1 of the period's samples, complex (ntime,), with bloch_train_vjp_batch's conventions; with
+    grad_m0, (L, grad, (gmx, gmy, gmz)), dL/dm0 of shape (S, nf, npos) each.  Nothing echo-sized comes back from the device.
+    Deterministic: a pulse's bits depend only on the pulse, its grids, its train, its planes and the scales; targets equal to
+    bloch_train_batch's own output give L == 0.0 and a gradient of exact zeros."""
+    who = "bloch_train_lsq_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if (targets is None) != (weights is None):
+        raise ValueError("%s: targets and weights are given together or not at all" % who)
+    if (targets_final is None) != (weights_final is None):
+        raise ValueError("%s: targets_final and weights_final are given together or not at all" % who)
+    if targets is None and targets_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    nul = C.cast(None, _dp)
+    eb, w, t = (0, [nul] * 3, [nul] * 3) if targets is None else _train_echo_planes(who, A, ntr, weights, targets)
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    T = sum(A.nt)
+    loss, grad = np.zeros(P), [np.zeros(T) for _ in range(2)]
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_lsq_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
+                                                    *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+                                                    *[_plane(v) for v in wf + tf], _ptr(loss), _ptr(grad[0]), _ptr(grad[1]),
+                                                    *[_plane(v) for v in gm])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    res = _lsq_result([range(n) for n in A.nt], loss, grad)
+    if not grad_m0:
+        return res
+    return [res[q] + (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm),) for q in range(P)]
+
+
+def bloch_train_gn_batch(pulses, df, dp, ntr, tangents, weights, *, rep_weights=None, weights_final=None, phases=np.pi, gains=1.0,
+                         echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+    """Gauss-Newton products of the fit of bloch_train_lsq_batch in one device call (mbfir_bloch_train_gn_batch):
+    H v = J' W J v for J the Jacobian of (echoes, final state) in the period's b1 (real-linear in v, the scales' and gains' chain
+    rule included) and W the weights, rep_weights included; arguments as for bloch_train_lsq_batch without the targets, tangents as
+    bloch_train_jvp_batch takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every pulse.
+    weights None: no echo term.  Returns per pulse a complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real
+    inner product Re sum conj(u) v.  A product's bits depend only on its pulse, grids, train, weights, direction and the scales:
+    not on the batch, on K or on the direction's place among K.  m0 is not a variable."""
+    who = "bloch_train_gn_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr = Tn.A, Tn.ntr
+    if weights is None and weights_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    rfs = [range(n) for n in A.nt]
+    K, keep, vplanes = _tangents(who, tangents, rfs)
+    nul = C.cast(None, _dp)
+    eb, w, _ = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None)
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_gn_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w],
+                                                   _plane(nul if rw is None else rw), *[_plane(v) for v in wf], K,
+                                                   *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _gn_result(rfs, K, keep, h)
+
+
 def _rf_g(pulse, q, who, gtype):
     """A pulse of abr_batch / abr2_batch, rf or (rf, g) -> rf and g of dtype gtype, abrm's 2 pi / n per sample where it has none."""
     rf, g = pulse if isinstance(pulse, tuple) else (pulse, None)
@@ -2596,7 +2732,7 @@ def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg
     return _lm_result(rfs, out)
 
 
-from .refine import refine_batch, refine_bloch_batch, refine_bloch_ss_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
+from .refine import refine_batch, refine_bloch_batch, refine_bloch_ss_batch, refine_bloch_train_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

@@ -1646,6 +1646,124 @@ int mbfir_bloch_train_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
 
 int mbfir_test_bloch_train_jvp_group(int which) { return bloch_train_jvp_group(which); }
 
+// The train's fused products (blochtraingn.hip).  What both calls check after bloch_train_check, in this order: ebcast,
+// the echo and final planes given whole or not at all and not both absent, the outputs, then (bloch_train_gn_check) the sizes, before
+// any plane is read: the adjoint's partials, checkpoints and workgroups (bloch_train_vjp_fits) and, per direction, the planes' tangents and
+// cotangents, the partials, the run's checkpoints (two states) and the workgroups: MBFIR_E_ARG when a count overflows, exceeds 2^56
+// or, for the workgroups, 2^31 - 1; last the weights and rw, non-negative and finite.
+static int bloch_train_gn_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, const long* toff, const int* ntr,
+                                const long* roff, const long* ncomb, const long* npoint, int ebcast, const double* const w[3],
+                                const double* rw, const double* const wf[3]) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    long E = 0, O = 0;
+    for (int p = 0; p < npulse; ++p) {
+        E += npoint[p] * nscale * ntr[p];                                 // bloch_train_check has bounded both
+        O += npoint[p] * nscale;
+    }
+    auto neg = [](const double* v, long n) {
+        for (long i = 0; i < n; ++i)
+            if (!(v[i] >= 0) || !std::isfinite(v[i])) return true;
+        return false;
+    };
+    if (!bloch_train_vjp_fits(npulse, nscale, toff, ntr, ncomb, npoint)) return bad("the output size or the workgroup count overflows");
+    long wsp = 0, part = 0, ckr = 0, wgr = 0, wgf = 0;
+    for (int p = 0; p < npulse; ++p) {
+        const long n = toff[p + 1] - toff[p], nch = (npoint[p] + 255) / 256, nch64 = (npoint[p] + 63) / 64;
+        long a, b, c, d, f;
+        if (__builtin_mul_overflow(npoint[p], ncomb[p] * 24, &a) || __builtin_mul_overflow(a, (long)ndir, &a) ||
+            __builtin_add_overflow(wsp, a, &wsp) || __builtin_mul_overflow(ncomb[p] * nch64, n, &b) ||
+            __builtin_mul_overflow(b, (long)ndir, &b) || __builtin_add_overflow(part, b, &part) ||
+            __builtin_mul_overflow(nch * nscale, ((long)ntr[p] + 7) / 8 * 1536, &c) || __builtin_mul_overflow(c, (long)ndir, &c) ||
+            __builtin_add_overflow(ckr, c, &ckr) || __builtin_mul_overflow(nch * nscale, (long)ndir, &d) ||
+            __builtin_add_overflow(wgr, d, &wgr) || __builtin_mul_overflow((n + 255) / 256, (long)ndir, &f) ||
+            __builtin_add_overflow(wgf, f, &wgf))
+            return bad("the output size or the workgroup count overflows");
+    }
+    if (toff[npulse] > (1L << 56) / ndir || wsp > (1L << 56) || part > (1L << 56) || ckr > (1L << 56) || wgr > 2147483647L ||
+        wgf > 2147483647L)
+        return bad("the output size or the workgroup count overflows");
+    for (int c = 0; c < 3; ++c)
+        if ((w[0] && neg(w[c], ebcast ? O : E)) || (wf[0] && neg(wf[c], O))) return bad("a weight is negative or not finite");
+    if (rw && neg(rw, roff[npulse])) return bad("a repetition weight is negative or not finite");
+    return 0;
+}
+
+int mbfir_bloch_train_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
+                                const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                const double* tfz, double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lsq_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && wz && tx && ty && tz;
+    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && wfz && tfx && tfy && tfz;
+    if (any_e && !all_e) return bad("the echo weights and targets are given together or not at all");
+    if (any_f && !all_f) return bad("the final weights and targets are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    if (!loss || !g_re || !g_im) return bad("a loss or gradient plane is null");
+    if ((gmx || gmy || gmz) && !(gmx && gmy && gmz)) return bad("gmx, gmy and gmz are given together or not at all");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const t[3] = {tx, ty, tz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    const double* const tf[3] = {tfx, tfy, tfz};
+    if (const int e = bloch_train_gn_check(ctx, "bloch_train_lsq_batch", npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
+                                           npoint.data(), ebcast, w, rw, wf))
+        return e;
+    MBFIR_TRY(ctx, bloch_train_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                             t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
+                                             cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, t, rw, wf,
+                                             tf, loss, g_re, g_im, gmx, gmy, gmz));
+}
+
+int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                               const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                               int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                               const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                               const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                               const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz, int ndir,
+                               const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_gn_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
+    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    if (!v_re || !v_im || !h_re || !h_im) return bad("a direction or product plane is null");
+    if (ndir < 1) return bad("ndir must be at least 1");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    if (const int e = bloch_train_gn_check(ctx, "bloch_train_gn_batch", npulse, nscale, ndir, toff, ntr, roff, ncomb.data(),
+                                           npoint.data(), ebcast, w, rw, wf))
+        return e;
+    if (!bloch_train_jvp_fits(npulse, nscale, ndir, toff, ntr, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_train_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                            t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
+                                            cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, rw, wf, ndir,
+                                            v_re, v_im, h_re, h_im));
+}
+
 int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,

@@ -251,6 +251,35 @@ __global__ __launch_bounds__(256) void k_bloch_train_run_jvp(
 // when wanted, then what stays on the device: the primal planes and the tangent planes.
 int bloch_train_jvp_group(int which) { return which ? TJVP_RUN_K : TJVP_K; }
 
+// The period tangent's table: k_bloch_train_prop_vjp's (the longest periods first, chunks of 64 points), once per direction group
+size_t train_jvp_table(TrainStaged& Ts, int nscale, int ndir, long& nwg) {
+    BlochStaged& B = Ts.B;
+    Staging& S = B.S;
+    const int npulse = (int)Ts.tr.size(), ngp = (ndir + TJVP_K - 1) / TJVP_K;
+    nwg = 0;
+    for (int p = 0; p < npulse; ++p) nwg += (B.npair[p] + 63) / 64 * nscale * Ts.tr[p].ngain * ngp;
+    const size_t o_qb = S.add(nwg * sizeof(SimBlock));
+    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
+    SimBlock* qb = S.at<SimBlock>(o_qb);
+    for (long w = 0; w < S.nblk; ++w) {
+        if (fb[w].scale != 0 || fb[w].chunk != 0) continue;               // the first workgroup of each pulse, in launch order
+        const int p = fb[w].pulse;
+        const int ncomb = nscale * Ts.tr[p].ngain, nch = int((B.npair[p] + 63) / 64);
+        for (int c = 0; c < ncomb; ++c)
+            for (int k = 0; k < nch; ++k)
+                for (int g = 0; g < ngp; ++g) *qb++ = SimBlock{p, c, k, g};
+    }
+    return o_qb;
+}
+
+void train_launch_prop_jvp(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, size_t o_v, int ndir, double* dws) {
+    Staging& S = Ts.B.S;
+    hipLaunchKernelGGL(k_bloch_train_prop_jvp, dim3((unsigned)nwg), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
+                       S.dev<const double>(Ts.B.o_df), S.dev<const double>(Ts.B.o_pos), S.dev<const double>(Ts.o_amp),
+                       S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_qb),
+                       S.dev<const double2>(o_v), ndir, dws);
+}
+
 void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
@@ -270,11 +299,8 @@ void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long*
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
     Staging& S = B.S;
     const size_t O = (size_t)B.O, E = (size_t)Ts.E, NO = (size_t)ndir * O, NE = (size_t)ndir * E, V = (size_t)ndir * toff[npulse];
-    const int ngp = (ndir + TJVP_K - 1) / TJVP_K, ngr = (ndir + TJVP_RUN_K - 1) / TJVP_RUN_K;
-    long nwg = 0;                                                         // workgroups of the period's tangent
-    for (int p = 0; p < npulse; ++p) nwg += (B.npair[p] + 63) / 64 * nscale * Ts.tr[p].ngain * ngp;
-    const size_t o_v = S.add(V * 16), o_d = dm0x ? S.add(3 * NO * 8) : 0, o_jb = sim_group_table(S, ngr),
-                 o_qb = S.add(nwg * sizeof(SimBlock));
+    const int ngr = (ndir + TJVP_RUN_K - 1) / TJVP_RUN_K;
+    const size_t o_v = S.add(V * 16), o_d = dm0x ? S.add(3 * NO * 8) : 0, o_jb = sim_group_table(S, ngr);
     pack_cplx(V, v_re, v_im, S.at<double2>(o_v));
     if (dm0x) {
         double* d = S.at<double>(o_d);
@@ -282,17 +308,8 @@ void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long*
         std::copy(dm0y, dm0y + NO, d + NO);
         std::copy(dm0z, dm0z + NO, d + 2 * NO);
     }
-    // the period tangent's table: k_bloch_train_prop_vjp's (the longest periods first, chunks of 64 points), once per direction group
-    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
-    SimBlock* qb = S.at<SimBlock>(o_qb);
-    for (long w = 0; w < S.nblk; ++w) {
-        if (fb[w].scale != 0 || fb[w].chunk != 0) continue;               // the first workgroup of each pulse, in launch order
-        const int p = fb[w].pulse;
-        const int ncomb = nscale * Ts.tr[p].ngain, nch = int((B.npair[p] + 63) / 64);
-        for (int c = 0; c < ncomb; ++c)
-            for (int k = 0; k < nch; ++k)
-                for (int g = 0; g < ngp; ++g) *qb++ = SimBlock{p, c, k, g};
-    }
+    long nwg = 0;                                                         // workgroups of the period's tangent
+    const size_t o_qb = train_jvp_table(Ts, nscale, ndir, nwg);
     const size_t te = dex ? 3 * NE : 0, tf = dfx ? 3 * NO : 0, pe = ex ? 3 * E : 0, pf = fx ? 3 * O : 0, W = (size_t)Ts.W;
     S.upload((te + tf + pe + pf + W + (size_t)ndir * W) * 8, st);
     double* out = S.dev<double>(S.o_out);
@@ -303,10 +320,7 @@ void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long*
     double* ws = dpf + pf;
     double* dws = ws + W;
     train_launch_prop(Ts, st, ws);
-    hipLaunchKernelGGL(k_bloch_train_prop_jvp, dim3((unsigned)nwg), dim3(256), 0, st, S.dev<const double>(B.o_in),
-                       S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(Ts.o_amp),
-                       S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_qb),
-                       S.dev<const double2>(o_v), ndir, dws);
+    train_launch_prop_jvp(Ts, st, o_qb, nwg, o_v, ndir, dws);
     hipLaunchKernelGGL(k_bloch_train_run_jvp, dim3((unsigned)(S.nblk * ngr)), dim3(256), 0, st, ws, dws,
                        S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi), S.dev<const BlochPulseDev>(S.o_pd),
                        S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_jb), S.dev<const double>(B.o_m0),

@@ -24,9 +24,6 @@
 
 namespace mbfir {
 
-constexpr int TRV_T = 8;                       // repetitions per checkpoint group of the run adjoint
-static_assert(256 % TRV_T == 0, "a group of repetitions lies within one staged tile of the repetition table");
-
 // blocks: the forward table (pulse, scale, chunk of 256 points).  ws: the propagators' planes; cw: their cotangents, the same layout,
 // zero on entry.  cex.. (null: no echo cotangents) lie where the echoes do, cfx.. (null: none) and gmx.. (null: not wanted) where
 // the final planes do.  ck: the checkpoints, BlochCkDev's layout with groups of TRV_T repetitions.
@@ -290,6 +287,57 @@ __global__ __launch_bounds__(256) void k_bloch_train_vjp_fold(const double2* __r
 // plus the cotangents, the partial and checkpoint descriptors and the tables of the period adjoint and of the fold; one upload,
 // four launches, one download.  The output region is the gradient (T double2), dL / d m0 (3 O doubles), then what stays on the
 // device: the propagators' planes, their cotangents, the partials and the two kernels' checkpoints.
+TrainVjpSections train_vjp_stage(TrainStaged& Ts, int npulse, const long* toff, int nscale, const int* ntr) {
+    BlochStaged& B = Ts.B;
+    Staging& S = B.S;
+    TrainVjpSections V;
+    std::vector<VjpPulseDev> vp(npulse);
+    std::vector<BlochCkDev> ckr(npulse), ckp(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        const int n = B.ntime[p], nch = int((B.npair[p] + 255) / 256), nch64 = int((B.npair[p] + 63) / 64);
+        const int ngr = (ntr[p] + TRV_T - 1) / TRV_T, ngp = (n + VJP_T - 1) / VJP_T;
+        const long ncomb = (long)nscale * Ts.tr[p].ngain;
+        vp[p] = VjpPulseDev{toff[p], V.npart, n, nch64};
+        ckr[p] = BlochCkDev{V.nckr, ngr, 0};
+        ckp[p] = BlochCkDev{V.nckp, ngp, 0};
+        V.npart += ncomb * nch64 * n;
+        V.nckr += (long)nscale * nch * ngr * BLOCH_CK;
+        V.nckp += ncomb * nch64 * ngp * BLOCH_CK;
+        V.nwg += ncomb * nch64;
+        V.nfold += (n + 255) / 256;
+    }
+    V.o_vp = S.add(npulse * sizeof(VjpPulseDev));
+    V.o_ckr = S.add(npulse * sizeof(BlochCkDev));
+    V.o_ckp = S.add(npulse * sizeof(BlochCkDev));
+    V.o_vb = S.add(V.nwg * sizeof(SimBlock));
+    V.o_fb = S.add(V.nfold * sizeof(SimBlock));
+    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(V.o_vp));
+    std::copy(ckr.begin(), ckr.end(), S.at<BlochCkDev>(V.o_ckr));
+    std::copy(ckp.begin(), ckp.end(), S.at<BlochCkDev>(V.o_ckp));
+    // the period adjoint's table: k_bloch_train_prop's order (the longest periods first) with chunks of 64 points
+    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
+    SimBlock* vb = S.at<SimBlock>(V.o_vb);
+    for (long w = 0; w < S.nblk; ++w) {
+        if (fb[w].scale != 0 || fb[w].chunk != 0) continue;               // the first workgroup of each pulse, in launch order
+        const int p = fb[w].pulse;
+        const int ncomb = nscale * Ts.tr[p].ngain;
+        for (int c = 0; c < ncomb; ++c)
+            for (int k = 0; k < vp[p].nch; ++k) *vb++ = SimBlock{p, c, k, 0};
+    }
+    SimBlock* ob = S.at<SimBlock>(V.o_fb);
+    for (int p = 0; p < npulse; ++p)
+        for (int k = 0; k < (B.ntime[p] + 255) / 256; ++k) *ob++ = SimBlock{p, 0, k, 0};
+    return V;
+}
+
+void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck) {
+    Staging& S = Ts.B.S;
+    hipLaunchKernelGGL(k_bloch_train_prop_vjp, dim3((unsigned)V.nwg), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
+                       S.dev<const double>(Ts.B.o_df), S.dev<const double>(Ts.B.o_pos), S.dev<const double>(Ts.o_amp),
+                       S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(V.o_vb),
+                       S.dev<const VjpPulseDev>(V.o_vp), S.dev<const BlochCkDev>(V.o_ckp), cw, part, ck);
+}
+
 void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
@@ -308,26 +356,7 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
     Staging& S = B.S;
     const long O = B.O, T = toff[npulse], E = Ts.E;
-    std::vector<VjpPulseDev> vp(npulse);
-    std::vector<BlochCkDev> ckr(npulse), ckp(npulse);
-    long npart = 0, nckr = 0, nckp = 0, nfold = 0, nwg = 0;     // double2 partials, checkpoint doubles of the two kernels, workgroups
-    for (int p = 0; p < npulse; ++p) {
-        const int n = B.ntime[p], nch = int((B.npair[p] + 255) / 256), nch64 = int((B.npair[p] + 63) / 64);
-        const int ngr = (ntr[p] + TRV_T - 1) / TRV_T, ngp = (n + VJP_T - 1) / VJP_T;
-        const long ncomb = (long)nscale * Ts.tr[p].ngain;
-        vp[p] = VjpPulseDev{toff[p], npart, n, nch64};
-        ckr[p] = BlochCkDev{nckr, ngr, 0};
-        ckp[p] = BlochCkDev{nckp, ngp, 0};
-        npart += ncomb * nch64 * n;
-        nckr += (long)nscale * nch * ngr * BLOCH_CK;
-        nckp += ncomb * nch64 * ngp * BLOCH_CK;
-        nwg += ncomb * nch64;
-        nfold += (n + 255) / 256;
-    }
-    const size_t o_ce = S.add(cex ? (size_t)E * 24 : 0), o_cf = S.add(cfx ? (size_t)O * 24 : 0),
-                 o_vp = S.add(npulse * sizeof(VjpPulseDev)), o_ckr = S.add(npulse * sizeof(BlochCkDev)),
-                 o_ckp = S.add(npulse * sizeof(BlochCkDev)), o_vb = S.add(nwg * sizeof(SimBlock)),
-                 o_fb = S.add(nfold * sizeof(SimBlock));
+    const size_t o_ce = S.add(cex ? (size_t)E * 24 : 0), o_cf = S.add(cfx ? (size_t)O * 24 : 0);
     if (cex) {
         double* c = S.at<double>(o_ce);
         std::copy(cex, cex + E, c);
@@ -340,22 +369,8 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
         std::copy(cfy, cfy + O, c + O);
         std::copy(cfz, cfz + O, c + 2 * O);
     }
-    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(o_vp));
-    std::copy(ckr.begin(), ckr.end(), S.at<BlochCkDev>(o_ckr));
-    std::copy(ckp.begin(), ckp.end(), S.at<BlochCkDev>(o_ckp));
-    // the period adjoint's table: k_bloch_train_prop's order (the longest periods first) with chunks of 64 points
-    const SimBlock* fb = S.at<SimBlock>(S.o_bk);
-    SimBlock* vb = S.at<SimBlock>(o_vb);
-    for (long w = 0; w < S.nblk; ++w) {
-        if (fb[w].scale != 0 || fb[w].chunk != 0) continue;               // the first workgroup of each pulse, in launch order
-        const int p = fb[w].pulse;
-        const int ncomb = nscale * Ts.tr[p].ngain;
-        for (int c = 0; c < ncomb; ++c)
-            for (int k = 0; k < vp[p].nch; ++k) *vb++ = SimBlock{p, c, k, 0};
-    }
-    SimBlock* ob = S.at<SimBlock>(o_fb);
-    for (int p = 0; p < npulse; ++p)
-        for (int k = 0; k < (B.ntime[p] + 255) / 256; ++k) *ob++ = SimBlock{p, 0, k, 0};
+    const TrainVjpSections V = train_vjp_stage(Ts, npulse, toff, nscale, ntr);
+    const long npart = V.npart, nckr = V.nckr, nckp = V.nckp;
     const size_t O3 = ((size_t)O * 3 + 1) & ~size_t(1);          // an even count: the partials after it stay 16-byte aligned
     const size_t W = (size_t)Ts.W;
     S.upload(((size_t)T * 2 + O3 + 2 * W + (size_t)npart * 2 + (size_t)nckr + (size_t)nckp) * 8, st);
@@ -373,16 +388,13 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
     const bool want_m0 = gmx != nullptr;
     hipLaunchKernelGGL(k_bloch_train_run_vjp, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
                        S.dev<const int>(Ts.o_gi), S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr),
-                       S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(o_ckr), S.dev<const double>(B.o_m0), demod, ced,
+                       S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr), S.dev<const double>(B.o_m0), demod, ced,
                        ced ? ced + E : nullptr, ced ? ced + 2 * E : nullptr, cfd, cfd ? cfd + O : nullptr,
                        cfd ? cfd + 2 * O : nullptr, ck1, cw, want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr,
                        want_m0 ? gm + 2 * O : nullptr);
-    hipLaunchKernelGGL(k_bloch_train_prop_vjp, dim3((unsigned)nwg), dim3(256), 0, st, S.dev<const double>(B.o_in),
-                       S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(Ts.o_amp),
-                       S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_vb),
-                       S.dev<const VjpPulseDev>(o_vp), S.dev<const BlochCkDev>(o_ckp), cw, part, ck2);
-    hipLaunchKernelGGL(k_bloch_train_vjp_fold, dim3((unsigned)nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(o_vp),
-                       S.dev<const SimBlock>(o_fb), S.dev<const double>(Ts.o_amp), S.dev<const TrainPulseDev>(Ts.o_tr), nscale,
+    train_launch_prop_vjp(Ts, V, st, cw, part, ck2);
+    hipLaunchKernelGGL(k_bloch_train_vjp_fold, dim3((unsigned)V.nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(V.o_vp),
+                       S.dev<const SimBlock>(V.o_fb), S.dev<const double>(Ts.o_amp), S.dev<const TrainPulseDev>(Ts.o_tr), nscale,
                        S.dev<const double>(B.o_in), S.dev<const BlochPulseDev>(S.o_pd), grad);
     std::vector<double> h((size_t)T * 2 + (want_m0 ? (size_t)O * 3 : 0));
     S.download(h.data(), h.size() * 8, st);

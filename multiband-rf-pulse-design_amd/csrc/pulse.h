@@ -168,6 +168,31 @@ void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long*
                                const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z, double* ex, double* ey,
                                double* ez, double* fx, double* fy, double* fz, double* dex, double* dey, double* dez, double* dfx,
                                double* dfy, double* dfz);
+// Fused least-squares and Gauss-Newton products of bloch_train_batch_run (blochtraingn.hip k_bloch_train_run_lsq,
+// k_bloch_train_run_gn, k_bloch_train_gn_fold with the shipped k_bloch_train_prop, k_bloch_train_prop_jvp and k_bloch_train_prop_vjp;
+// DESIGN 8ab): the forward call's inputs; w / t: the echo weights and targets (w[0] null: no echo term), laid out as the echoes
+// (ebcast 0) or as the final planes and used at every repetition (ebcast 1); rw (null: ones): one factor per repetition, laid out as
+// cosphi; wf / tf: the final weights and targets (wf[0] null: no final term).  lsq: loss per pulse, the gradient per b1 sample,
+// gm* = dL / dm0 (all null: not downloaded).  gn: ndir directions per pulse as bloch_train_jvp_batch_run takes them, h_* = J' W J v
+// in the same layout.  One upload, one download; nothing echo-sized comes down.
+void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                               int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                               const double* scales, const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                               const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                               const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
+                               const double* const t[3], const double* rw, const double* const wf[3], const double* const tf[3],
+                               double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                              const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                              const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                              int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                              const double* scales, const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                              const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                              const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
+                              const double* rw, const double* const wf[3], int ndir, const double* v_re, const double* v_im,
+                              double* h_re, double* h_im);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1

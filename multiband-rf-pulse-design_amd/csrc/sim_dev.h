@@ -696,6 +696,27 @@ void train_stage(TrainStaged& Ts, int npulse, int nscale, const double* scales, 
                  const double* meq);
 void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws);
 
+// What the train's adjoint (blochtrainvjp.hip) shares with the fused products (blochtraingn.hip), moved here
+// from blochtrainvjp.hip token for token.
+constexpr int TRV_T = 8;                       // repetitions per checkpoint group of the run adjoint
+static_assert(256 % TRV_T == 0, "a group of repetitions lies within one staged tile of the repetition table");
+
+// The host side of the adjoint's tables (blochtrainvjp.hip train_vjp_stage): the partial and checkpoint descriptors, the table of the
+// period adjoint (k_bloch_train_prop's order with chunks of 64 points) and the table of the fold, as sections of the staging, and
+// the sizes of what stays on the device.
+struct TrainVjpSections {
+    size_t o_vp = 0, o_ckr = 0, o_ckp = 0, o_vb = 0, o_fb = 0;
+    long npart = 0, nckr = 0, nckp = 0, nfold = 0, nwg = 0;     // double2 partials, checkpoint doubles of the two kernels, workgroups
+};
+TrainVjpSections train_vjp_stage(TrainStaged& Ts, int npulse, const long* toff, int nscale, const int* ntr);
+// Launches k_bloch_train_prop_vjp (blochtrainvjp.hip) on the staged table: cw the planes' cotangents, part and ck its partials and
+// checkpoints.  Launches on one stream are ordered, so one checkpoint region serves any number of them.
+void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck);
+// The table of the period's tangent (blochtrainjvp.hip): k_bloch_train_prop_vjp's order, once per direction group; nwg receives its
+// workgroups.  train_launch_prop_jvp launches k_bloch_train_prop_jvp on it: v the packed directions' section, dws the tangent planes.
+size_t train_jvp_table(TrainStaged& Ts, int nscale, int ndir, long& nwg);
+void train_launch_prop_jvp(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, size_t o_v, int ndir, double* dws);
+
 // The sections the Bloch least-squares calls add to the forward staging (blochgn.hip bloch_gn_stage, moved here token for token so
 // that blochssgn.hip stages through it too), and the sizes of what stays on the device.
 struct BlochGnSections {

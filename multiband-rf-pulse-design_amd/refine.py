@@ -9,6 +9,7 @@ refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch
 or with solver='device' each step as one bloch_lm_step_batch call, or with steady_state=True on bloch_ss_lsq_batch /
 bloch_ss_gn_batch, the steady state of the period; refine_bloch_ss_batch is that loop with both solvers, the device one
 taking each step as one bloch_ss_lm_step_batch call.
+refine_bloch_train_batch runs the loop on bloch_train_lsq_batch / bloch_train_gn_batch, the echoes of a pulse train.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -264,3 +265,70 @@ def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, 
     calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
     infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
     return _lm_loop(b1s, infos, lsq, gn, lm if solver == "device" else step, iters, mu0)
+
+
+def refine_bloch_train_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
+                             phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, iters=5, cg=8, mu0=None,
+                             rtol=1e-6, solver="host", ctx=None):
+    """refine_batch for bloch_train_batch's model: the same lock-step Levenberg-Marquardt / CG loop on
+    bloch_train_lsq_batch and bloch_train_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, one period, of which only b1
+    changes; df, dp: one grid shared by every pulse or a list of one per pulse; ntr, targets, weights, rep_weights, targets_final,
+    weights_final, phases, gains, echo, scales, m0, meq and demod as for bloch_train_lsq_batch, what is given per pulse as a Python
+    list of one entry per pulse; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch does.  solver:
+    'host' runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration; there is no device step yet.  A pulse
+    refined in a batch has the bits of the same pulse refined alone."""
+    who = "refine_bloch_train_batch"
+    mb = importlib.import_module(__package__)
+    pulses = list(pulses)
+    P = len(pulses)
+    if P == 0:
+        raise ValueError("%s: no pulses" % who)
+    if solver == "device":
+        raise ValueError("%s: the train has no device step; solver must be 'host'" % who)
+    if solver != "host":
+        raise ValueError("%s: solver must be 'host', not %r" % (who, solver))
+    if iters < 0 or cg < 1:
+        raise ValueError("%s: iters must be at least 0 and cg at least 1" % who)
+    if targets is None and targets_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
+        if v is not None and len(list(v)) != P:
+            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+    rest = [tuple(p[1:]) for p in pulses]
+    b1s = [np.array(p[0], dtype=np.complex128).ravel() for p in pulses]
+    each_m0 = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
+
+    def grid(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P and all(np.ndim(e) >= 1 for e in v) else v
+
+    def pick(v, idx):
+        """a keyword given per pulse (a Python list of P entries) -> the entries of idx; anything else serves every pulse"""
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P else v
+
+    def sub(v, idx):
+        return None if v is None else [v[q] for q in idx]
+
+    def kw(idx):
+        return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=pick(phases, idx),
+                    gains=pick(gains, idx), echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+
+    def args(idx, b1_of):
+        return [(b1_of[q],) + rest[q] for q in idx], grid(df, idx), grid(dp, idx), pick(ntr, idx)
+
+    def lsq(idx, b1_of):
+        for q in idx:
+            infos[q]["calls"]["lsq"] += 1
+        return mb.bloch_train_lsq_batch(*args(idx, b1_of), sub(targets, idx), sub(weights, idx), targets_final=sub(targets_final, idx),
+                                        **kw(idx))
+
+    def gn(idx, v_of):
+        for q in idx:
+            infos[q]["calls"]["gn"] += 1
+        return mb.bloch_train_gn_batch(*args(idx, b1s), [v_of[q] for q in idx], sub(weights, idx), **kw(idx))
+
+    def step(idx, grad, mu):
+        return _host_steps(idx, b1s, grad, mu, lsq, gn, cg, rtol)
+
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    return _lm_loop(b1s, infos, lsq, gn, step, iters, mu0)
