@@ -10,9 +10,11 @@ rep_weights leaves the first --skip echoes of the transient out.  refine_bloch_t
 dead-time samples included (bssfp_train_refine.py moves the pulse's samples only): the peak |b1| line shows what that costs.
 Prints the figures of bssfp_train_refine.py before and after, whose "largest deviation" line is the one to set against its L-BFGS
 result at the same --tr, --ntr and --weight, and the losses and device calls of the fit.  The figures are a result, not a
-criterion.  No plots.
+criterion.  No plots.  --solver host (the default) runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration
+(56 device calls at the defaults); --solver device solves and tries every step in one bloch_train_lm_step_batch call
+(mbfir.refine_bloch_train_lm_batch).  The last line counts the device calls of the fit.
 
-    python examples/bssfp_train_lm.py [--tr 6.0] [--ntr 64] [--iters 5] [--cg 8] [--weight 10] [--skip 8]
+    python examples/bssfp_train_lm.py [--tr 6.0] [--ntr 64] [--iters 5] [--cg 8] [--weight 10] [--skip 8] [--solver host|device]
 """
 import argparse
 import os
@@ -33,6 +35,7 @@ ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--cg", type=int, default=8)
 ap.add_argument("--weight", type=float, default=10.0)
 ap.add_argument("--skip", type=int, default=8)
+ap.add_argument("--solver", choices=("host", "device"), default="host")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -92,10 +95,12 @@ on = np.zeros((S, nf, 1))
 on[:, lac] = 1.0
 target = (ex[:, args.skip:].mean(1) * on, ey[:, args.skip:].mean(1) * on, 0.0)       # the mean demodulated echo, per (gain, point)
 t0 = time.perf_counter()
-(b1_lm,), (info,) = mbfir.refine_bloch_train_batch([pulse(b1)], df, dp, N, [target], [(on, on, 0.0)], rep_weights=rw,
-                                                    targets_final=[(0.0, 0.0, 1.0)], weights_final=[(0.0, 0.0, args.weight * (1 - on))],
-                                                    demod=True, iters=args.iters, cg=args.cg, **kw)
+(b1_lm,), (info,) = mbfir.refine_bloch_train_lm_batch([pulse(b1)], df, dp, N, [target], [(on, on, 0.0)], rep_weights=rw,
+                                                       targets_final=[(0.0, 0.0, 1.0)],
+                                                       weights_final=[(0.0, 0.0, args.weight * (1 - on))], demod=True,
+                                                       iters=args.iters, cg=args.cg, solver=args.solver, **kw)
 ms = (time.perf_counter() - t0) * 1e3
-print("Levenberg-Marquardt: %d accepted steps, %d refused, losses %s, calls %s, %.1f ms" %
-      (len(info["losses"]) - 1, info["refused"], " ".join("%.6g" % v for v in info["losses"]), info["calls"], ms))
+print("Levenberg-Marquardt (%s solver): %d accepted steps, %d refused, losses %s, calls %s: %d device calls, %.1f ms" %
+      (args.solver, len(info["losses"]) - 1, info["refused"], " ".join("%.6g" % v for v in info["losses"]), info["calls"],
+       sum(info["calls"].values()), ms))
 report("after Levenberg-Marquardt on the fused products", b1_lm)

@@ -830,6 +830,38 @@ int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, c
                                  const double* wz, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
                                  const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
                                  double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im);
+/* mbfir_bloch_train_lm_step_batch: the step above for the echoes of a pulse train (mbfir_bloch_train_batch): conjugate
+ * gradients on (H + mu[p] I) d = b from d = 0, H = J' W J as in mbfir_bloch_train_gn_batch at the call's b1, train, weights, rw and
+ * scales (echo term, final term, the scales' and gains' chain rule), at most cg iterations, while <r, r> > rtol <b, b>.  The
+ * arguments up to wfx, wfy, wfz are those of mbfir_bloch_train_gn_batch; b_re, b_im are laid out as b1 is.  tx, ty, tz: the echo
+ * targets, laid out as the echo weights are under ebcast; tfx, tfy, tfz: the final targets.  With targets the loss and gradient of
+ * mbfir_bloch_train_lsq_batch at b1 + d (one IEEE addition per part) are returned too, with that call's bits; all six NULL: solve
+ * only, and loss, g_re, g_im may be NULL.  Outputs per pulse as for mbfir_bloch_lm_step_batch: d, ncg, rr, gg, status (0: the
+ * tolerance was reached, 1: the cap cg was reached, 2: breakdown).  H p has the bits of mbfir_bloch_train_gn_batch on the same p.
+ * b1 is fixed within the solve, so the propagators' planes and the checkpoints of the period adjoint's forward half are computed
+ * once per call.  One upload, a chain of launches (three, then a memset and four per CG iteration, six and a memset for the
+ * trial), one download; the host reads nothing in between, so cg is also a launch count.  The tangent planes, the cotangent planes,
+ * the partials and the checkpoints of one direction serve every iteration and the trial; they, r, H p, the primal planes and the
+ * trial's input rows stay on the device.  A pulse's outputs depend only on the pulse, its grids, its train, weights, targets, m0, b,
+ * mu, cg, rtol and the scale list: not on the batch, its order, or when its neighbours stop.  The checks are those of
+ * mbfir_bloch_train_batch and of mbfir_bloch_train_gn_batch at ndir = 1 (ebcast, the weights, the sizes) in their order and with
+ * their messages, then: b, mu or a required output NULL ("a required array is null"); a negative or non-finite mu; cg < 0; a
+ * negative or NaN rtol; sections that overflow; then, with a message beginning "bloch_train_lm_step_batch:", a target triple only
+ * partly given, a target for a term that has no weights, or, when a target is given, none for a term that has weights.  No device
+ * work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                    const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                    const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                    const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                    const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                    const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                    const double* m0z, int ebcast, const double* wx, const double* wy, const double* wz,
+                                    const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* b_re,
+                                    const double* b_im, const double* mu, int cg, double rtol, const double* tx, const double* ty,
+                                    const double* tz, const double* tfx, const double* tfy, const double* tfz, double* d_re,
+                                    double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                                    double* g_im);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

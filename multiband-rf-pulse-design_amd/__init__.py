@@ -181,6 +181,10 @@ SYMBOLS = {
     "mbfir_bloch_ss_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                                _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 6 + [C.c_int, C.c_double] +
                                               [_dp] * 5 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "mbfir_bloch_train_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
+                                                  _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                 [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 7 +
+                                                 [_dp] * 3 + [C.c_int, C.c_double] + [_dp] * 8 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -2732,7 +2736,57 @@ def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg
     return _lm_result(rfs, out)
 
 
-from .refine import refine_batch, refine_bloch_batch, refine_bloch_ss_batch, refine_bloch_train_batch   # noqa: E402  (batched Levenberg-Marquardt on the calls above)
+def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=None, rep_weights=None, targets_final=None,
+                              weights_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, cg=8,
+                              rtol=1e-6, ctx=None):
+    """bloch_lm_step_batch for the echoes of a pulse train, bloch_train_batch's model (mbfir_bloch_train_lm_step_batch, DESIGN section
+    8ac): conjugate gradients on (H + mu I) d = rhs from d = 0, H = J' W J as bloch_train_gn_batch applies it (echo term, rep_weights,
+    final term, the scales' and gains' chain rule), solved on the device in one call.  pulses (each one period), df, dp, ntr,
+    weights, rep_weights, weights_final, phases, gains, echo, scales, m0, meq and demod as for bloch_train_gn_batch; rhs: per pulse a
+    complex (n,) array; mu: a number >= 0 or one per pulse; cg and rtol as for abr_lm_step_batch.  With targets and / or
+    targets_final (as for bloch_train_lsq_batch: one for every term that has weights) the loss and gradient at b1 + d come back too,
+    with the bits of bloch_train_lsq_batch there.  Returns a list of (d, info) per pulse: info holds 'ncg', 'rr', 'gg' and 'status'
+    ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.  b1 is fixed within the solve, so the propagators' planes
+    and the checkpoints of the period's adjoint are computed once per call.  The host reads nothing between the iterations, so cg is
+    also a launch count.  Deterministic: a pulse's results depend only on the pulse, its grids, its train, weights, targets, m0, rhs,
+    mu, cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    who = "bloch_train_lm_step_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr = Tn.A, Tn.ntr
+    if weights is None and weights_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    if targets is not None and weights is None:
+        raise ValueError("%s: targets are given for an echo term that has no weights" % who)
+    if targets_final is not None and weights_final is None:
+        raise ValueError("%s: targets_final are given for a final term that has no weights" % who)
+    trial = targets is not None or targets_final is not None
+    if trial and ((weights is not None and targets is None) or (weights_final is not None and targets_final is None)):
+        raise ValueError("%s: with targets, every term that has weights needs its own" % who)
+    rfs = [range(n) for n in A.nt]
+    bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
+    nul = C.cast(None, _dp)
+    eb, w, t = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets)
+    t = [nul] * 3 if t is None else t
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    P, T = A.P, sum(A.nt)
+    out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
+    out += [np.zeros(P), np.zeros(T), np.zeros(T)] if trial else [None, None, None]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_lm_step_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
+                                                        *[_plane(v) for v in w], _plane(nul if rw is None else rw),
+                                                        *[_plane(v) for v in wf], *[_ptr(v) for v in bplanes], _ptr(m), cg,
+                                                        C.c_double(rtol), *[_plane(v) for v in t + tf + out])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    return _lm_result(rfs, out)
+
+
+from .refine import (refine_batch, refine_bloch_batch, refine_bloch_ss_batch, refine_bloch_train_batch,   # noqa: E402  (batched
+                     refine_bloch_train_lm_batch)                                                          # Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

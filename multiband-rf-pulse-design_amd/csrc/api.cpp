@@ -2138,6 +2138,59 @@ int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, c
                                               g_im));
 }
 
+// The train's step (blochtrainlm.hip): bloch_train_check, the checks of mbfir_bloch_train_gn_batch at ndir = 1 with their
+// messages and order (ebcast, the weights, the sizes), bloch_lm_check's for its own arrays, mu, cg and rtol, then the targets:
+// each triple whole or absent, and, when any is given, one for every term that has weights and none for a term that has not.
+int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                    const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                    const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                    const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                    const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                    const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                    const double* m0z, int ebcast, const double* wx, const double* wy, const double* wz,
+                                    const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* b_re,
+                                    const double* b_im, const double* mu, int cg, double rtol, const double* tx, const double* ty,
+                                    const double* tz, const double* tfx, const double* tfy, const double* tfz, double* d_re,
+                                    double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                                    double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lm_step_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
+    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    if (const int e = bloch_train_gn_check(ctx, "bloch_train_lm_step_batch", npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
+                                           npoint.data(), ebcast, w, rw, wf))
+        return e;
+    if (!bloch_train_jvp_fits(npulse, nscale, 1, toff, ntr, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    const bool tg_e = tx || ty || tz, tg_f = tfx || tfy || tfz, targets = tg_e || tg_f;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
+    if (const int e = bloch_lm_check(ctx, "bloch_train_lm_step_batch", own, true, npulse, toff, mu, cg, rtol)) return e;
+    if (tg_e && !(tx && ty && tz)) return bad("tx, ty and tz are given together or not at all");
+    if (tg_f && !(tfx && tfy && tfz)) return bad("tfx, tfy and tfz are given together or not at all");
+    if ((tg_e && !any_e) || (tg_f && !any_f)) return bad("a target is given for a term that has no weights");
+    if (targets && ((any_e && !tg_e) || (any_f && !tg_f))) return bad("a term that has weights has no target while the other has one");
+    const double* const t[3] = {tx, ty, tz};
+    const double* const tf[3] = {tfx, tfy, tfz};
+    MBFIR_TRY(ctx, bloch_train_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                 tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
+                                                 roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, rw,
+                                                 wf, b_re, b_im, mu, cg, rtol, t, tf, d_re, d_im, ncg, rr, gg, status, loss, g_re,
+                                                 g_im));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 int mbfir_test_bloch_jvp_group(void) { return bloch_jvp_group(); }
 

@@ -143,9 +143,9 @@ __global__ __launch_bounds__(256) void k_bloch_train_run(const double* __restric
 // (bloch_stage, mode 0: m0 per (scale, frequency, position)) plus the amplitudes, the train descriptors, the repetition tables and
 // the propagator kernel's block table; one upload, the launches, one download.  The output region is the echo planes (3 E), the
 // final planes (3 O), then the propagators' planes, which stay on the device unless the caller is mbfir_bloch_prop_batch.
-void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws) {
+void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws, const double* in) {
     Staging& S = Ts.B.S;
-    hipLaunchKernelGGL(k_bloch_train_prop, dim3((unsigned)Ts.nprop), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
+    hipLaunchKernelGGL(k_bloch_train_prop, dim3((unsigned)Ts.nprop), dim3(256), 0, st, in ? in : S.dev<const double>(Ts.B.o_in),
                        S.dev<const double>(Ts.B.o_df), S.dev<const double>(Ts.B.o_pos), S.dev<const double>(Ts.o_amp),
                        S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(Ts.o_pb), ws);
 }

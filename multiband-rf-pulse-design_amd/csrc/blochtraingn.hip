@@ -23,11 +23,8 @@
 
 namespace mbfir {
 
-// Whether k_bloch_train_run_gn keeps the planes and their cotangents in registers over the whole walk when the pulse has one
-// distinct gain, as k_bloch_train_run_vjp does.  DESIGN 8ab has the table of candidates.
-#ifndef TGN_HOIST
-#define TGN_HOIST 0
-#endif
+// k_bloch_train_run_gn's body and its switch TGN_HOIST are in sim_dev.h (bloch_train_run_gn_body), shared with the device
+// Levenberg-Marquardt step (blochtrainlm.hip).
 
 // blocks, ws, cw, cks, ck, gmx..: k_bloch_train_run_vjp's.  rw (null: ones): the repetitions' factors, laid out as rep.  we / te
 // (null: no echo term): the echo weights and targets, three planes PE entries apart, pulse p from e_off (ebcast 0) or o_off
@@ -207,166 +204,8 @@ __global__ __launch_bounds__(256) void k_bloch_train_run_gn(
     const SimBlock* __restrict__ blocks, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0, int demod, int ebcast,
     int ndir, const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long WT, long CK, double* ck,
     double* cw) {
-    __shared__ double2 scs[256];
-    __shared__ double srw[256];
-    __shared__ int sgi[256];
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const int ntr = Tr.ntr, G = Tr.ngain, dir = bk.pad;
-    const double meq = Tr.meq;
-    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
-    const bool live = pair < npair;
-    const long blk = (long)bk.scale * npair + pair;
-    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
-    const double* wb = ws + Tr.w_off + comb0;
-    // direction dir of the scale's first combination; a combination is ndir directions of TRAIN_ENT npair doubles
-    const double* db = dws + (long)ndir * Tr.w_off + ((long)bk.scale * G * ndir + dir) * TRAIN_ENT * npair + (live ? pair : 0);
-    const long gstr = (long)TRAIN_ENT * npair, dgstr = (long)ndir * gstr;
-    double* cb = cw + (long)dir * WT + Tr.w_off + comb0;
-    const long nch = (npair + 255) / 256;
-    double* wck = ck + 2 * ((long)dir * CK + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK) + tid;
-    const bool hoist = TGN_HOIST && G == 1;
-    double m[3] = {0, 0, 1}, dm[3] = {0, 0, 0}, W[TRAIN_ENT], acc[TRAIN_ENT];
-    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
-#pragma unroll
-    for (int e = 0; e < TRAIN_ENT; ++e) acc[e] = 0;
-    if (hoist) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
-    }
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int cnt = min(256, ntr - k0);
-        if (tid < cnt) {
-            scs[tid] = rep[Tr.r_off + k0 + tid];
-            sgi[tid] = gidx[Tr.r_off + k0 + tid];
-            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
-        }
-        __syncthreads();
-    };
-    // (m_k, dm_k) -> (m_{k+1}, dm_{k+1}) from (u_k, du_k) (in v, dv), with the planes of the repetition in W[0 .. 11] and its tangent
-    // planes at dg, as k_bloch_train_run_jvp steps them
-    auto advance = [&](double c, double s, const double* dg, double v[3], double dv[3]) {
-        double dW[12], n[3], dn[3];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) dW[e] = dg[e * npair];
-        train_affine_jvp(W, dW, dW + 9, meq, v, dv, dn);
-        train_zm(c, s, dn);
-        train_affine(W, W + 9, meq, v, n);
-        train_zm(c, s, n);
-        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
-        dv[0] = dn[0]; dv[1] = dn[1]; dv[2] = dn[2];
-    };
-    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints of m and dm
-        stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (TRV_T - 1)) == 0) {                                 // (m, dm) before repetition k0 + q
-                double* w = wck + (long)((k0 + q) / TRV_T) * (2 * BLOCH_CK);
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-                w[768] = dm[0]; w[1024] = dm[1]; w[1280] = dm[2];
-            }
-            if (!hoist) {
-                const double* wg = wb + (long)sgi[q] * gstr;
-#pragma unroll
-                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-            }
-            train_zp(scs[q].x, scs[q].y, m);
-            train_zp(scs[q].x, scs[q].y, dm);
-            advance(scs[q].x, scs[q].y, db + (long)sgi[q] * dgstr, m, dm);
-        }
-    }
-    double l[3] = {0, 0, 0};
-    if (live && wf) {                                                     // lambda_N = wf dm_N
-        const long o = P.o_off + blk;
-        l[0] = wf[o] * dm[0]; l[1] = wf[PO + o] * dm[1]; l[2] = wf[2 * PO + o] * dm[2];
-    }
-    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
-    const double* wp = we ? we + eo : nullptr;
-    const int klast = (ntr - 1) / 256 * 256;
-    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
-        if (k0 != klast) stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
-            const int ge = min(g0 + TRV_T, cnt);
-            double us[TRV_T][3], dus[TRV_T][3], mm[3], dmm[3];            // (u, du) of repetition k0 + g0 + j
-            const double* w = wck + (long)((k0 + g0) / TRV_T) * (2 * BLOCH_CK);
-            mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
-            dmm[0] = w[768]; dmm[1] = w[1024]; dmm[2] = w[1280];
-#pragma unroll
-            for (int j = 0; j < TRV_T; ++j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    train_zp(c, s, mm);
-                    train_zp(c, s, dmm);
-                    us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
-                    dus[j][0] = dmm[0]; dus[j][1] = dmm[1]; dus[j][2] = dmm[2];
-                    if (g0 + j + 1 < ge) {
-                        if (!hoist) {
-                            const double* wg = wb + (long)sgi[g0 + j] * gstr;
-#pragma unroll
-                            for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-                        }
-                        advance(c, s, db + (long)sgi[g0 + j] * dgstr, mm, dmm);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = TRV_T - 1; j >= 0; --j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    const long go = (long)sgi[g0 + j] * gstr;
-                    if (!hoist) {
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) { W[e] = wb[go + e * npair]; acc[e] = 0; }
-                    }
-                    const double* u = us[j];
-                    double a[3] = {l[0], l[1], l[2]};
-                    train_zp(c, s, a);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        acc[i] += a[i] * u[0]; acc[3 + i] += a[i] * u[1]; acc[6 + i] += a[i] * u[2];
-                        acc[9 + i] += meq * a[i];
-                        l[i] = W[3 * i] * a[0] + W[3 * i + 1] * a[1] + W[3 * i + 2] * a[2];           // A' a
-                    }
-                    if (wp) {
-                        const long ko = (long)(k0 + g0 + j) * kstr;
-                        const double rk = srw[g0 + j];
-                        const double* dk = db + (long)sgi[g0 + j] * dgstr + 12 * npair;
-                        double dW[12], ae[3];
-#pragma unroll
-                        for (int e = 0; e < 12; ++e) dW[e] = dk[e * npair];
-                        train_affine_jvp(W + 12, dW, dW + 9, meq, u, dus[j], ae);      // decho, as k_bloch_train_run_jvp forms it
-                        if (!demod) train_zm(c, s, ae);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) ae[i] = rk * (wp[ko + i * PE] * ae[i]);       // ce_k = rw_k w decho_k
-                        if (!demod) train_zp(c, s, ae);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            acc[12 + i] += ae[i] * u[0]; acc[15 + i] += ae[i] * u[1]; acc[18 + i] += ae[i] * u[2];
-                            acc[21 + i] += meq * ae[i];
-                            l[i] += W[12 + 3 * i] * ae[0] + W[13 + 3 * i] * ae[1] + W[14 + 3 * i] * ae[2];       // A_e' ae
-                        }
-                    }
-                    train_zm(c, s, l);
-                    if (!hoist) {                                         // the thread's own column of the repetition's gain
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) cb[go + e * npair] += acc[e];
-                    }
-                }
-            }
-        }
-    }
-    if (!live) return;
-    if (hoist) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) cb[e * npair] = acc[e];
-    }
+    bloch_train_run_gn_body(blocks[blockIdx.x], ws, dws, rep, gidx, rw, pulses, trains, cks, m0, demod, ebcast, ndir, we, PE, wf, PO, WT, CK, ck,
+                            cw);
 }
 
 // out[ndir r_off + d n + t] = k_bloch_train_vjp_fold's value from direction d's partials (part + d NP): one thread per sample, one
@@ -405,13 +244,6 @@ __global__ __launch_bounds__(256) void k_bloch_train_gn_fold(const double2* __re
 // per direction, the loss partials and the checkpoints.
 namespace {
 
-struct TrainGnCall {
-    TrainStaged Ts;
-    TrainVjpSections V;
-    size_t o_we = 0, o_te = 0, o_rw = 0, o_wf = 0, o_tf = 0, o_lp = 0, o_gf = 0;
-    long PE = 0, nlp = 0, ngf = 0;
-};
-
 size_t add_triple(Staging& S, const double* x, const double* y, const double* z, long n) {
     const size_t o = S.add(x ? (size_t)n * 24 : 0);
     if (x) {
@@ -422,6 +254,8 @@ size_t add_triple(Staging& S, const double* x, const double* y, const double* z,
     }
     return o;
 }
+
+}  // namespace
 
 // The sections after train_stage: t* null for gn.
 void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
@@ -453,7 +287,33 @@ void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, c
             for (int k = 0; k < (B.ntime[p] + 255) / 256; ++k) *gf++ = SimBlock{p, d, k, 0};
 }
 
-}  // namespace
+// k_bloch_train_run_lsq on the staged sections of Cl with the planes ws, and k_bloch_train_gn_fold at one direction with the loss sum,
+// on the input rows `in` (null: the staged ones): the launches of bloch_train_lsq_batch_run, which the device step's trial repeats.
+void train_launch_run_lsq(TrainGnCall& Cl, hipStream_t st, int demod, int ebcast, bool echo, bool rep, bool fin, const double* ws,
+                          double* ck, double* cw, double* gm, double* lpart) {
+    TrainStaged& Ts = Cl.Ts;
+    BlochStaged& B = Ts.B;
+    Staging& S = B.S;
+    const TrainVjpSections& V = Cl.V;
+    const long O = B.O;
+    hipLaunchKernelGGL(k_bloch_train_run_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
+                       S.dev<const int>(Ts.o_gi), rep ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr),
+                       S.dev<const long>(Cl.o_lp), S.dev<const double>(B.o_m0), demod, ebcast,
+                       echo ? S.dev<const double>(Cl.o_we) : nullptr, echo ? S.dev<const double>(Cl.o_te) : nullptr, Cl.PE,
+                       fin ? S.dev<const double>(Cl.o_wf) : nullptr, fin ? S.dev<const double>(Cl.o_tf) : nullptr, O, ck, cw,
+                       gm, gm ? gm + O : nullptr, gm ? gm + 2 * O : nullptr, lpart);
+}
+void train_launch_lsq_fold(TrainGnCall& Cl, hipStream_t st, int nscale, const double2* part, const double* in, double2* grad,
+                           const double* lpart, double* loss) {
+    TrainStaged& Ts = Cl.Ts;
+    Staging& S = Ts.B.S;
+    const TrainVjpSections& V = Cl.V;
+    hipLaunchKernelGGL(k_bloch_train_gn_fold, dim3((unsigned)Cl.ngf), dim3(256), 0, st, part, V.npart,
+                       S.dev<const VjpPulseDev>(V.o_vp), S.dev<const SimBlock>(Cl.o_gf), S.dev<const double>(Ts.o_amp),
+                       S.dev<const TrainPulseDev>(Ts.o_tr), nscale, 1, in ? in : S.dev<const double>(Ts.B.o_in),
+                       S.dev<const BlochPulseDev>(S.o_pd), grad, lpart, S.dev<const long>(Cl.o_lp), loss);
+}
 
 void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
@@ -491,18 +351,10 @@ void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long*
     double* ck2 = ck1 + V.nckr;
     MBFIR_HIP(hipMemsetAsync(cw, 0, W * 8, st));                 // upload does not zero the output region
     train_launch_prop(Ts, st, ws);
-    hipLaunchKernelGGL(k_bloch_train_run_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
-                       S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
-                       S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr),
-                       S.dev<const long>(Cl.o_lp), S.dev<const double>(B.o_m0), demod, ebcast,
-                       w[0] ? S.dev<const double>(Cl.o_we) : nullptr, w[0] ? S.dev<const double>(Cl.o_te) : nullptr, Cl.PE,
-                       wf[0] ? S.dev<const double>(Cl.o_wf) : nullptr, wf[0] ? S.dev<const double>(Cl.o_tf) : nullptr, O, ck1, cw,
-                       want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr, want_m0 ? gm + 2 * O : nullptr, lpart);
+    train_launch_run_lsq(Cl, st, demod, ebcast, w[0] != nullptr, rw != nullptr, wf[0] != nullptr, ws, ck1, cw, want_m0 ? gm : nullptr,
+                         lpart);
     train_launch_prop_vjp(Ts, V, st, cw, part, ck2);
-    hipLaunchKernelGGL(k_bloch_train_gn_fold, dim3((unsigned)Cl.ngf), dim3(256), 0, st, part, V.npart,
-                       S.dev<const VjpPulseDev>(V.o_vp), S.dev<const SimBlock>(Cl.o_gf), S.dev<const double>(Ts.o_amp),
-                       S.dev<const TrainPulseDev>(Ts.o_tr), nscale, 1, S.dev<const double>(B.o_in),
-                       S.dev<const BlochPulseDev>(S.o_pd), grad, lpart, S.dev<const long>(Cl.o_lp), dloss);
+    train_launch_lsq_fold(Cl, st, nscale, part, nullptr, grad, lpart, dloss);
     std::vector<double> h((size_t)T * 2 + NL + O3);
     S.download(h.data(), h.size() * 8, st);
     unpack_cplx(T, reinterpret_cast<const double2*>(h.data()), g_re, g_im);

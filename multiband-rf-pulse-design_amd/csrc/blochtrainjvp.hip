@@ -26,10 +26,8 @@ namespace mbfir {
 
 // Directions per workgroup of the two kernels: the largest of 1, 2, 4, 8 without scratch at no less than the matching forward
 // kernel's occupancy minus one wave per SIMD (k_bloch_train_prop: 4, k_bloch_train_run: 5; DESIGN 8aa has the table).  The
-// repetitions' kernel keeps the 24 primal planes in registers, which leaves room for one direction at four waves.
-#ifndef TJVP_K
-#define TJVP_K 4
-#endif
+// repetitions' kernel keeps the 24 primal planes in registers, which leaves room for one direction at four waves.  TJVP_K (4) is
+// in sim_dev.h with the period's body, which the device Levenberg-Marquardt step (blochtrainlm.hip) shares.
 #ifndef TJVP_RUN_K
 #define TJVP_RUN_K 1
 #endif
@@ -42,97 +40,7 @@ __global__ __launch_bounds__(256) void k_bloch_train_prop_jvp(const double* __re
                                                               const TrainPulseDev* __restrict__ trains,
                                                               const SimBlock* __restrict__ blocks, const double2* __restrict__ v,
                                                               int ndir, double* __restrict__ dws) {
-    __shared__ double sst[BLOCH_CH][8];
-    __shared__ double2 sdn[TJVP_K][BLOCH_CH];
-    const int tid = threadIdx.x, col = tid >> 6, lane = tid & 63;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const double sc = amp[Tr.a_off + bk.scale], gamma = P.gamma;
-    const int ntime = P.ntime, npos = P.npos, echo = Tr.echo;
-    const int k0 = bk.pad * TJVP_K, kcnt = min(TJVP_K, ndir - k0);
-    const long npair = (long)P.nf * npos, pair = (long)bk.chunk * 64 + lane;
-    const bool live = pair < npair;
-    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
-    const double dfv = df[P.f_off + fi];
-    const double* pp = pos3 + 3 * (P.p_off + pi);
-    const double px = pp[0], py = pp[1], pz = pp[2];
-    const bool rec = col == 3;                                            // uniform over the wavefront
-    const int ent = rec ? 9 : 3 * col;                                    // the column's first entry among A (9), B (3)
-    const double2* vg = v + (long)ndir * P.t_off + (long)k0 * ntime;      // the group's first direction
-    // the column of direction k0 of the combination; a direction is TRAIN_ENT npair doubles
-    double* w = dws + (long)ndir * Tr.w_off + ((long)bk.scale * ndir + k0) * TRAIN_ENT * npair + (long)ent * npair + (live ? pair : 0);
-    const long dstr = (long)TRAIN_ENT * npair;
-    double m[3] = {col == 0 ? 1.0 : 0.0, col == 1 ? 1.0 : 0.0, col == 2 ? 1.0 : 0.0}, dm[TJVP_K][3];
-#pragma unroll
-    for (int k = 0; k < TJVP_K; ++k) dm[k][0] = dm[k][1] = dm[k][2] = 0;
-    if (echo == 0 && live) {                                              // (A_e, B_e) = (I, 0) has no tangent
-#pragma unroll
-        for (int k = 0; k < TJVP_K; ++k)
-            if (k < kcnt) {
-                double* o = w + k * dstr + 12 * npair;
-                o[0] = 0; o[npair] = 0; o[2 * npair] = 0;
-            }
-    }
-    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-        __syncthreads();
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        if (tid < cnt) {
-            const double* s = in + BLOCH_IN * (P.t_off + t0 + tid);
-            const double dt = s[8];
-            sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                  // rotx of the pulse b1 amp, as k_bloch_train_prop forms it
-            sst[tid][1] = ((s[1] * sc) * gamma) * dt;                     // roty
-            for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
-#pragma unroll
-            for (int k = 0; k < TJVP_K; ++k)
-                if (k < kcnt) {
-                    const double2 d = vg[(long)k * ntime + t0 + tid];
-                    sdn[k][tid] = make_double2(((-(d.x * sc)) * gamma) * dt, ((d.y * sc) * gamma) * dt);      // (dnx, dny)
-                }
-        }
-        __syncthreads();
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            const double* s = sst[q];
-            const double rotz = bloch_rotz(s, px, py, pz, dfv);
-            Rot3 R;
-            BlochTrig tr;
-            bloch_rotmat_trig<true>(s[0], s[1], rotz, R, tr);
-            const double e1 = s[6], e2 = s[7];
-            BlochJvpShared W;
-            bloch_jvp_shared(s[0], s[1], rotz, tr, m, W);
-#pragma unroll
-            for (int k = 0; k < TJVP_K; ++k)
-                if (k < kcnt) {
-                    const double2 dn = sdn[k][q];
-                    const double nd = s[0] * dn.x + s[1] * dn.y;
-                    double o[3];
-                    rot_vec(R, dm[k], o);
-                    dm[k][0] = e2 * (o[0] + (nd * W.U[0] + dn.x * W.Vx[0] + dn.y * W.Vy[0]));
-                    dm[k][1] = e2 * (o[1] + (nd * W.U[1] + dn.x * W.Vx[1] + dn.y * W.Vy[1]));
-                    dm[k][2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
-                }
-            double o[3];
-            rot_vec(R, m, o);
-            m[0] = e2 * o[0]; m[1] = e2 * o[1];
-            if (rec) m[2] = e1 * o[2] + (1 - e1); else m[2] = e1 * o[2];
-            if (t0 + q + 1 == echo) {                                     // uniform over the workgroup: (dA_e, dB_e)
-#pragma unroll
-                for (int k = 0; k < TJVP_K; ++k)
-                    if (k < kcnt) {
-                        double* oe = w + k * dstr + 12 * npair;
-                        oe[0] = dm[k][0]; oe[npair] = dm[k][1]; oe[2 * npair] = dm[k][2];
-                    }
-            }
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int k = 0; k < TJVP_K; ++k)
-        if (k < kcnt) {
-            double* o = w + k * dstr;
-            o[0] = dm[k][0]; o[npair] = dm[k][1]; o[2 * npair] = dm[k][2];
-        }
+    bloch_train_prop_jvp_body(blocks[blockIdx.x], in, df, pos3, amp, pulses, trains, v, ndir, dws);
 }
 
 // blocks: the forward table (pulse, scale, chunk of 256 points) times the direction groups (pad).  ws: the primal planes; dws: the

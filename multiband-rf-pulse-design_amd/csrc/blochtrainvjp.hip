@@ -166,16 +166,6 @@ __global__ __launch_bounds__(256) void k_bloch_train_run_vjp(
     if (gmx) { const long o = P.o_off + blk; gmx[o] = l[0]; gmy[o] = l[1]; gmz[o] = l[2]; }
 }
 
-// bloch_fwd_step without the recovery term: a column of A.
-__device__ __forceinline__ void bloch_hom_step(const double* s, double rotz, double m[3]) {
-    Rot3 R;
-    bloch_rotmat(s[0], s[1], rotz, R);
-    const double e1 = s[6], e2 = s[7];
-    double o[3];
-    rot_vec(R, m, o);
-    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2];
-}
-
 // blocks: (pulse, combination, chunk of 64 points), k_bloch_train_prop's order.  cw: the cotangents of the planes from the run
 // adjoint.  part: one double2 (sum of dL / d rotx, sum of dL / d roty) per (workgroup, sample), VjpPulseDev's layout with the
 // combinations in place of the scales and nch = chunks of 64 points.  ck: the checkpoints, BlochCkDev's layout.
@@ -189,80 +179,12 @@ __global__ __launch_bounds__(256) void k_bloch_train_prop_vjp(const double* __re
     __shared__ double sst[BLOCH_CH][8];
     __shared__ double red[2 * VJP_T * VJP_ROW];
     static_assert(BLOCH_CH % VJP_T == 0, "a group of samples lies within one staged tile");
-    const int tid = threadIdx.x, col = tid >> 6, lane = tid & 63;
     const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const VjpPulseDev V = vp[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const double sc = amp[Tr.a_off + bk.scale], gamma = P.gamma;
-    const int ntime = P.ntime, npos = P.npos, echo = Tr.echo;
-    const long npair = (long)P.nf * npos, pair = (long)bk.chunk * 64 + lane;
-    const bool live = pair < npair;                                       // a thread past the end of the grid sweeps the first point
-    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
-    const double dfv = df[P.f_off + fi];
-    const double* pp = pos3 + 3 * (P.p_off + pi);
-    const double px = pp[0], py = pp[1], pz = pp[2];
-    const long wg = (long)bk.scale * V.nch + bk.chunk;                    // the workgroup among its pulse's
-    double2* wpart = part + V.p_off + wg * V.n;
-    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
-    const bool rec = col == 3;                                            // uniform over the wavefront
-    double m[3] = {col == 0 ? 1.0 : 0.0, col == 1 ? 1.0 : 0.0, col == 2 ? 1.0 : 0.0}, l[3] = {0, 0, 0}, le[3] = {0, 0, 0};
-    if (live) {
-        const double* c = cw + Tr.w_off + (long)bk.scale * TRAIN_ENT * npair + pair;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { l[i] = c[(3 * col + i) * npair]; le[i] = c[(12 + 3 * col + i) * npair]; }
-    }
-    const int tlast = (ntime - 1) / BLOCH_CH * BLOCH_CH;
-    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-        bloch_ss_stage(sst, in, P.t_off, ntime, t0, sc, gamma);
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (VJP_T - 1)) == 0) {                                 // the column before sample t0 + q: the group's checkpoint
-                double* w = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-            }
-            const double* s = sst[q];
-            const double rz = bloch_rotz(s, px, py, pz, dfv);
-            if (rec) bloch_fwd_step(s, rz, m); else bloch_hom_step(s, rz, m);
-        }
-    }
-    const int row = tid >> 4, ln = tid & 15;                              // reduction: 16 lanes per row of the tile
-    for (int t0 = tlast; t0 >= 0; t0 -= BLOCH_CH) {
-        if (t0 != tlast) bloch_ss_stage(sst, in, P.t_off, ntime, t0, sc, gamma);      // the forward sweep left the last tile staged
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        for (int g0 = (cnt - 1) / VJP_T * VJP_T; g0 >= 0; g0 -= VJP_T) {
-            const int ge = min(g0 + VJP_T, cnt);
-            double ms[VJP_T][3];                                          // ms[j] = the column before sample t0 + g0 + j
-            const double* w = wck + (long)((t0 + g0) / VJP_T) * BLOCH_CK;
-            ms[0][0] = w[0]; ms[0][1] = w[256]; ms[0][2] = w[512];
-#pragma unroll
-            for (int j = 1; j < VJP_T; ++j) {
-                ms[j][0] = ms[j - 1][0]; ms[j][1] = ms[j - 1][1]; ms[j][2] = ms[j - 1][2];
-                if (g0 + j < ge) {
-                    const double* s = sst[g0 + j - 1];
-                    const double rz = bloch_rotz(s, px, py, pz, dfv);
-                    if (rec) bloch_fwd_step(s, rz, ms[j]); else bloch_hom_step(s, rz, ms[j]);
-                }
-            }
-#pragma unroll
-            for (int j = VJP_T - 1; j >= 0; --j) {
-                if (g0 + j < ge) {
-                    if (t0 + g0 + j + 1 == echo) { l[0] += le[0]; l[1] += le[1]; l[2] += le[2]; }      // the state after `echo` samples
-                    const double* s = sst[g0 + j];
-                    const double2 c = bloch_vjp_step(s, bloch_rotz(s, px, py, pz, dfv), ms[j], l);
-                    red[(2 * j) * VJP_ROW + tid] = live ? c.x : 0.0;
-                    red[(2 * j + 1) * VJP_ROW + tid] = live ? c.y : 0.0;
-                }
-            }
-            __syncthreads();
-            double sum = 0;                                               // row = 2 (sample - g0) + (0: rotx, 1: roty); rows past ge are not stored
-            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
-            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
-            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + t0 + g0)[row] = sum;
-            __syncthreads();
-        }
-    }
+    const TrainPropVjpThread C = bloch_train_prop_vjp_thread(bk, df, pos3, amp, pulses, trains, vp, cks, part, ck);
+    double l[3] = {0, 0, 0}, le[3] = {0, 0, 0};
+    bloch_train_prop_vjp_seed(C, bk, cw, l, le);
+    bloch_train_prop_vjp_forward(C, sst, in);
+    bloch_train_prop_vjp_backward(C, sst, red, in, l, le);
 }
 
 // grad[t_off + t] = (-(gamma dt_t) X, +(gamma dt_t) Y), (X, Y) = sum_c amp_c (sum over chunks of part(c, chunk, t)), chunks then
@@ -330,9 +252,10 @@ TrainVjpSections train_vjp_stage(TrainStaged& Ts, int npulse, const long* toff, 
     return V;
 }
 
-void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck) {
+void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck,
+                           const double* in) {
     Staging& S = Ts.B.S;
-    hipLaunchKernelGGL(k_bloch_train_prop_vjp, dim3((unsigned)V.nwg), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
+    hipLaunchKernelGGL(k_bloch_train_prop_vjp, dim3((unsigned)V.nwg), dim3(256), 0, st, in ? in : S.dev<const double>(Ts.B.o_in),
                        S.dev<const double>(Ts.B.o_df), S.dev<const double>(Ts.B.o_pos), S.dev<const double>(Ts.o_amp),
                        S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(V.o_vb),
                        S.dev<const VjpPulseDev>(V.o_vp), S.dev<const BlochCkDev>(V.o_ckp), cw, part, ck);

@@ -694,7 +694,7 @@ struct TrainStaged {
 void train_stage(TrainStaged& Ts, int npulse, int nscale, const double* scales, const int* ntr, const long* roff,
                  const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
                  const double* meq);
-void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws);
+void train_launch_prop(TrainStaged& Ts, hipStream_t st, double* ws, const double* in = nullptr);
 
 // What the train's adjoint (blochtrainvjp.hip) shares with the fused products (blochtraingn.hip), moved here
 // from blochtrainvjp.hip token for token.
@@ -710,12 +710,444 @@ struct TrainVjpSections {
 };
 TrainVjpSections train_vjp_stage(TrainStaged& Ts, int npulse, const long* toff, int nscale, const int* ntr);
 // Launches k_bloch_train_prop_vjp (blochtrainvjp.hip) on the staged table: cw the planes' cotangents, part and ck its partials and
-// checkpoints.  Launches on one stream are ordered, so one checkpoint region serves any number of them.
-void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck);
+// checkpoints.  Launches on one stream are ordered, so one checkpoint region serves any number of them.  in (here and in
+// train_launch_prop): the input rows on the device, null for the staged ones; the device step's trial passes the rows at b1 + d.
+void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck,
+                           const double* in = nullptr);
 // The table of the period's tangent (blochtrainjvp.hip): k_bloch_train_prop_vjp's order, once per direction group; nwg receives its
 // workgroups.  train_launch_prop_jvp launches k_bloch_train_prop_jvp on it: v the packed directions' section, dws the tangent planes.
 size_t train_jvp_table(TrainStaged& Ts, int nscale, int ndir, long& nwg);
 void train_launch_prop_jvp(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, size_t o_v, int ndir, double* dws);
+
+// The sections the train's fused calls add after train_stage and train_vjp_stage (blochtraingn.hip train_gn_stage, t* null for gn):
+// the weights and targets, the repetitions' factors, the loss partials' offsets and the fold's table; nlp loss partials, ngf
+// workgroups of the fold.  train_launch_run_lsq and train_launch_lsq_fold launch k_bloch_train_run_lsq and k_bloch_train_gn_fold (one
+// direction, with the loss sum) on them; echo / rep / fin: whether the echo term, rw and the final term were staged.
+struct TrainGnCall {
+    TrainStaged Ts;
+    TrainVjpSections V;
+    size_t o_we = 0, o_te = 0, o_rw = 0, o_wf = 0, o_tf = 0, o_lp = 0, o_gf = 0;
+    long PE = 0, nlp = 0, ngf = 0;
+};
+void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
+                    const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
+                    const double* const tf[3]);
+void train_launch_run_lsq(TrainGnCall& Cl, hipStream_t st, int demod, int ebcast, bool echo, bool rep, bool fin, const double* ws,
+                          double* ck, double* cw, double* gm, double* lpart);
+void train_launch_lsq_fold(TrainGnCall& Cl, hipStream_t st, int nscale, const double2* part, const double* in, double2* grad,
+                           const double* lpart, double* loss);
+
+// What the train's device Levenberg-Marquardt step (blochtrainlm.hip) shares with the kernels it is made of: the bodies
+// of k_bloch_train_prop_jvp (blochtrainjvp.hip), k_bloch_train_run_gn (blochtraingn.hip) and the two halves of k_bloch_train_prop_vjp
+// (blochtrainvjp.hip), moved here token for token with the workgroup's table entry as an argument.  The shipped kernels call them;
+// the step's kernels call them behind the run flag, so H p has the shipped product's bits.
+// Directions per workgroup of the period's tangent (blochtrainjvp.hip says how it was chosen; DESIGN 8aa has the table).
+#ifndef TJVP_K
+#define TJVP_K 4
+#endif
+// Whether k_bloch_train_run_gn keeps the planes and their cotangents in registers over the whole walk when the pulse has one
+// distinct gain, as k_bloch_train_run_vjp does.  DESIGN 8ab has the table of candidates.
+#ifndef TGN_HOIST
+#define TGN_HOIST 0
+#endif
+
+// bloch_fwd_step without the recovery term: a column of A.
+__device__ __forceinline__ void bloch_hom_step(const double* s, double rotz, double m[3]) {
+    Rot3 R;
+    bloch_rotmat(s[0], s[1], rotz, R);
+    const double e1 = s[6], e2 = s[7];
+    double o[3];
+    rot_vec(R, m, o);
+    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2];
+}
+
+// k_bloch_train_prop_jvp for the workgroup bk = (pulse, combination, chunk of 64 points, direction group).
+__device__ __forceinline__ void bloch_train_prop_jvp_body(const SimBlock bk, const double* __restrict__ in,
+                                                          const double* __restrict__ df, const double* __restrict__ pos3,
+                                                          const double* __restrict__ amp, const BlochPulseDev* __restrict__ pulses,
+                                                          const TrainPulseDev* __restrict__ trains, const double2* __restrict__ v,
+                                                          int ndir, double* __restrict__ dws) {
+    __shared__ double sst[BLOCH_CH][8];
+    __shared__ double2 sdn[TJVP_K][BLOCH_CH];
+    const int tid = threadIdx.x, col = tid >> 6, lane = tid & 63;
+    const BlochPulseDev P = pulses[bk.pulse];
+    const TrainPulseDev Tr = trains[bk.pulse];
+    const double sc = amp[Tr.a_off + bk.scale], gamma = P.gamma;
+    const int ntime = P.ntime, npos = P.npos, echo = Tr.echo;
+    const int k0 = bk.pad * TJVP_K, kcnt = min(TJVP_K, ndir - k0);
+    const long npair = (long)P.nf * npos, pair = (long)bk.chunk * 64 + lane;
+    const bool live = pair < npair;
+    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
+    const double dfv = df[P.f_off + fi];
+    const double* pp = pos3 + 3 * (P.p_off + pi);
+    const double px = pp[0], py = pp[1], pz = pp[2];
+    const bool rec = col == 3;                                            // uniform over the wavefront
+    const int ent = rec ? 9 : 3 * col;                                    // the column's first entry among A (9), B (3)
+    const double2* vg = v + (long)ndir * P.t_off + (long)k0 * ntime;      // the group's first direction
+    // the column of direction k0 of the combination; a direction is TRAIN_ENT npair doubles
+    double* w = dws + (long)ndir * Tr.w_off + ((long)bk.scale * ndir + k0) * TRAIN_ENT * npair + (long)ent * npair + (live ? pair : 0);
+    const long dstr = (long)TRAIN_ENT * npair;
+    double m[3] = {col == 0 ? 1.0 : 0.0, col == 1 ? 1.0 : 0.0, col == 2 ? 1.0 : 0.0}, dm[TJVP_K][3];
+#pragma unroll
+    for (int k = 0; k < TJVP_K; ++k) dm[k][0] = dm[k][1] = dm[k][2] = 0;
+    if (echo == 0 && live) {                                              // (A_e, B_e) = (I, 0) has no tangent
+#pragma unroll
+        for (int k = 0; k < TJVP_K; ++k)
+            if (k < kcnt) {
+                double* o = w + k * dstr + 12 * npair;
+                o[0] = 0; o[npair] = 0; o[2 * npair] = 0;
+            }
+    }
+    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
+        __syncthreads();
+        const int cnt = min(BLOCH_CH, ntime - t0);
+        if (tid < cnt) {
+            const double* s = in + BLOCH_IN * (P.t_off + t0 + tid);
+            const double dt = s[8];
+            sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                  // rotx of the pulse b1 amp, as k_bloch_train_prop forms it
+            sst[tid][1] = ((s[1] * sc) * gamma) * dt;                     // roty
+            for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
+#pragma unroll
+            for (int k = 0; k < TJVP_K; ++k)
+                if (k < kcnt) {
+                    const double2 d = vg[(long)k * ntime + t0 + tid];
+                    sdn[k][tid] = make_double2(((-(d.x * sc)) * gamma) * dt, ((d.y * sc) * gamma) * dt);      // (dnx, dny)
+                }
+        }
+        __syncthreads();
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            const double* s = sst[q];
+            const double rotz = bloch_rotz(s, px, py, pz, dfv);
+            Rot3 R;
+            BlochTrig tr;
+            bloch_rotmat_trig<true>(s[0], s[1], rotz, R, tr);
+            const double e1 = s[6], e2 = s[7];
+            BlochJvpShared W;
+            bloch_jvp_shared(s[0], s[1], rotz, tr, m, W);
+#pragma unroll
+            for (int k = 0; k < TJVP_K; ++k)
+                if (k < kcnt) {
+                    const double2 dn = sdn[k][q];
+                    const double nd = s[0] * dn.x + s[1] * dn.y;
+                    double o[3];
+                    rot_vec(R, dm[k], o);
+                    dm[k][0] = e2 * (o[0] + (nd * W.U[0] + dn.x * W.Vx[0] + dn.y * W.Vy[0]));
+                    dm[k][1] = e2 * (o[1] + (nd * W.U[1] + dn.x * W.Vx[1] + dn.y * W.Vy[1]));
+                    dm[k][2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
+                }
+            double o[3];
+            rot_vec(R, m, o);
+            m[0] = e2 * o[0]; m[1] = e2 * o[1];
+            if (rec) m[2] = e1 * o[2] + (1 - e1); else m[2] = e1 * o[2];
+            if (t0 + q + 1 == echo) {                                     // uniform over the workgroup: (dA_e, dB_e)
+#pragma unroll
+                for (int k = 0; k < TJVP_K; ++k)
+                    if (k < kcnt) {
+                        double* oe = w + k * dstr + 12 * npair;
+                        oe[0] = dm[k][0]; oe[npair] = dm[k][1]; oe[2 * npair] = dm[k][2];
+                    }
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int k = 0; k < TJVP_K; ++k)
+        if (k < kcnt) {
+            double* o = w + k * dstr;
+            o[0] = dm[k][0]; o[npair] = dm[k][1]; o[2 * npair] = dm[k][2];
+        }
+}
+
+// k_bloch_train_run_gn for the workgroup bk = (pulse, scale, chunk of 256 points, direction).
+__device__ __forceinline__ void bloch_train_run_gn_body(
+    const SimBlock bk, const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep,
+    const int* __restrict__ gidx, const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses,
+    const TrainPulseDev* __restrict__ trains, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0, int demod, int ebcast,
+    int ndir, const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long WT, long CK, double* ck,
+    double* cw) {
+    __shared__ double2 scs[256];
+    __shared__ double srw[256];
+    __shared__ int sgi[256];
+    const int tid = threadIdx.x;
+    const BlochPulseDev P = pulses[bk.pulse];
+    const TrainPulseDev Tr = trains[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    const int ntr = Tr.ntr, G = Tr.ngain, dir = bk.pad;
+    const double meq = Tr.meq;
+    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
+    const bool live = pair < npair;
+    const long blk = (long)bk.scale * npair + pair;
+    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
+    const double* wb = ws + Tr.w_off + comb0;
+    // direction dir of the scale's first combination; a combination is ndir directions of TRAIN_ENT npair doubles
+    const double* db = dws + (long)ndir * Tr.w_off + ((long)bk.scale * G * ndir + dir) * TRAIN_ENT * npair + (live ? pair : 0);
+    const long gstr = (long)TRAIN_ENT * npair, dgstr = (long)ndir * gstr;
+    double* cb = cw + (long)dir * WT + Tr.w_off + comb0;
+    const long nch = (npair + 255) / 256;
+    double* wck = ck + 2 * ((long)dir * CK + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK) + tid;
+    const bool hoist = TGN_HOIST && G == 1;
+    double m[3] = {0, 0, 1}, dm[3] = {0, 0, 0}, W[TRAIN_ENT], acc[TRAIN_ENT];
+    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
+#pragma unroll
+    for (int e = 0; e < TRAIN_ENT; ++e) acc[e] = 0;
+    if (hoist) {
+#pragma unroll
+        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
+    }
+    auto stage = [&](int k0) {
+        __syncthreads();
+        const int cnt = min(256, ntr - k0);
+        if (tid < cnt) {
+            scs[tid] = rep[Tr.r_off + k0 + tid];
+            sgi[tid] = gidx[Tr.r_off + k0 + tid];
+            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
+        }
+        __syncthreads();
+    };
+    // (m_k, dm_k) -> (m_{k+1}, dm_{k+1}) from (u_k, du_k) (in v, dv), with the planes of the repetition in W[0 .. 11] and its tangent
+    // planes at dg, as k_bloch_train_run_jvp steps them
+    auto advance = [&](double c, double s, const double* dg, double v[3], double dv[3]) {
+        double dW[12], n[3], dn[3];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) dW[e] = dg[e * npair];
+        train_affine_jvp(W, dW, dW + 9, meq, v, dv, dn);
+        train_zm(c, s, dn);
+        train_affine(W, W + 9, meq, v, n);
+        train_zm(c, s, n);
+        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
+        dv[0] = dn[0]; dv[1] = dn[1]; dv[2] = dn[2];
+    };
+    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints of m and dm
+        stage(k0);
+        const int cnt = min(256, ntr - k0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            if ((q & (TRV_T - 1)) == 0) {                                 // (m, dm) before repetition k0 + q
+                double* w = wck + (long)((k0 + q) / TRV_T) * (2 * BLOCH_CK);
+                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
+                w[768] = dm[0]; w[1024] = dm[1]; w[1280] = dm[2];
+            }
+            if (!hoist) {
+                const double* wg = wb + (long)sgi[q] * gstr;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
+            }
+            train_zp(scs[q].x, scs[q].y, m);
+            train_zp(scs[q].x, scs[q].y, dm);
+            advance(scs[q].x, scs[q].y, db + (long)sgi[q] * dgstr, m, dm);
+        }
+    }
+    double l[3] = {0, 0, 0};
+    if (live && wf) {                                                     // lambda_N = wf dm_N
+        const long o = P.o_off + blk;
+        l[0] = wf[o] * dm[0]; l[1] = wf[PO + o] * dm[1]; l[2] = wf[2 * PO + o] * dm[2];
+    }
+    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
+    const double* wp = we ? we + eo : nullptr;
+    const int klast = (ntr - 1) / 256 * 256;
+    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
+        if (k0 != klast) stage(k0);
+        const int cnt = min(256, ntr - k0);
+        if (!live) continue;
+        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
+            const int ge = min(g0 + TRV_T, cnt);
+            double us[TRV_T][3], dus[TRV_T][3], mm[3], dmm[3];            // (u, du) of repetition k0 + g0 + j
+            const double* w = wck + (long)((k0 + g0) / TRV_T) * (2 * BLOCH_CK);
+            mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
+            dmm[0] = w[768]; dmm[1] = w[1024]; dmm[2] = w[1280];
+#pragma unroll
+            for (int j = 0; j < TRV_T; ++j) {
+                if (g0 + j < ge) {
+                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                    train_zp(c, s, mm);
+                    train_zp(c, s, dmm);
+                    us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
+                    dus[j][0] = dmm[0]; dus[j][1] = dmm[1]; dus[j][2] = dmm[2];
+                    if (g0 + j + 1 < ge) {
+                        if (!hoist) {
+                            const double* wg = wb + (long)sgi[g0 + j] * gstr;
+#pragma unroll
+                            for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
+                        }
+                        advance(c, s, db + (long)sgi[g0 + j] * dgstr, mm, dmm);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = TRV_T - 1; j >= 0; --j) {
+                if (g0 + j < ge) {
+                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                    const long go = (long)sgi[g0 + j] * gstr;
+                    if (!hoist) {
+#pragma unroll
+                        for (int e = 0; e < TRAIN_ENT; ++e) { W[e] = wb[go + e * npair]; acc[e] = 0; }
+                    }
+                    const double* u = us[j];
+                    double a[3] = {l[0], l[1], l[2]};
+                    train_zp(c, s, a);
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) {
+                        acc[i] += a[i] * u[0]; acc[3 + i] += a[i] * u[1]; acc[6 + i] += a[i] * u[2];
+                        acc[9 + i] += meq * a[i];
+                        l[i] = W[3 * i] * a[0] + W[3 * i + 1] * a[1] + W[3 * i + 2] * a[2];           // A' a
+                    }
+                    if (wp) {
+                        const long ko = (long)(k0 + g0 + j) * kstr;
+                        const double rk = srw[g0 + j];
+                        const double* dk = db + (long)sgi[g0 + j] * dgstr + 12 * npair;
+                        double dW[12], ae[3];
+#pragma unroll
+                        for (int e = 0; e < 12; ++e) dW[e] = dk[e * npair];
+                        train_affine_jvp(W + 12, dW, dW + 9, meq, u, dus[j], ae);      // decho, as k_bloch_train_run_jvp forms it
+                        if (!demod) train_zm(c, s, ae);
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) ae[i] = rk * (wp[ko + i * PE] * ae[i]);       // ce_k = rw_k w decho_k
+                        if (!demod) train_zp(c, s, ae);
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) {
+                            acc[12 + i] += ae[i] * u[0]; acc[15 + i] += ae[i] * u[1]; acc[18 + i] += ae[i] * u[2];
+                            acc[21 + i] += meq * ae[i];
+                            l[i] += W[12 + 3 * i] * ae[0] + W[13 + 3 * i] * ae[1] + W[14 + 3 * i] * ae[2];       // A_e' ae
+                        }
+                    }
+                    train_zm(c, s, l);
+                    if (!hoist) {                                         // the thread's own column of the repetition's gain
+#pragma unroll
+                        for (int e = 0; e < TRAIN_ENT; ++e) cb[go + e * npair] += acc[e];
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+    if (hoist) {
+#pragma unroll
+        for (int e = 0; e < TRAIN_ENT; ++e) cb[e * npair] = acc[e];
+    }
+}
+
+// The thread of k_bloch_train_prop_vjp: wave = column of [A | B], lane = point, for the workgroup bk = (pulse, combination, chunk of
+// 64 points) of the period adjoint's table.
+struct TrainPropVjpThread {
+    BlochPulseDev P;
+    TrainPulseDev Tr;
+    double sc, gamma, dfv, px, py, pz;
+    int ntime, echo, col;
+    long npair, pair;
+    bool live, rec;
+    double2* wpart;
+    double* wck;
+};
+__device__ __forceinline__ TrainPropVjpThread bloch_train_prop_vjp_thread(
+    const SimBlock bk, const double* __restrict__ df, const double* __restrict__ pos3, const double* __restrict__ amp,
+    const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains, const VjpPulseDev* __restrict__ vp,
+    const BlochCkDev* __restrict__ cks, double2* __restrict__ part, double* ck) {
+    TrainPropVjpThread C;
+    const int tid = threadIdx.x, col = tid >> 6, lane = tid & 63;
+    const BlochPulseDev P = pulses[bk.pulse];
+    const TrainPulseDev Tr = trains[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    const double sc = amp[Tr.a_off + bk.scale], gamma = P.gamma;
+    const int ntime = P.ntime, npos = P.npos, echo = Tr.echo;
+    const long npair = (long)P.nf * npos, pair = (long)bk.chunk * 64 + lane;
+    const bool live = pair < npair;                                       // a thread past the end of the grid sweeps the first point
+    const int fi = live ? int(pair / npos) : 0, pi = live ? int(pair - (long)fi * npos) : 0;
+    const double dfv = df[P.f_off + fi];
+    const double* pp = pos3 + 3 * (P.p_off + pi);
+    const double px = pp[0], py = pp[1], pz = pp[2];
+    const long wg = (long)bk.scale * V.nch + bk.chunk;                    // the workgroup among its pulse's
+    double2* wpart = part + V.p_off + wg * V.n;
+    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
+    const bool rec = col == 3;                                            // uniform over the wavefront
+    C.P = P; C.Tr = Tr; C.sc = sc; C.gamma = gamma; C.dfv = dfv; C.px = px; C.py = py; C.pz = pz;
+    C.ntime = ntime; C.echo = echo; C.col = col; C.npair = npair; C.pair = pair; C.live = live; C.rec = rec;
+    C.wpart = wpart; C.wck = wck;
+    return C;
+}
+// The column's cotangents from the run adjoint's planes: l at the end of the period, le at the state after `echo` samples.
+__device__ __forceinline__ void bloch_train_prop_vjp_seed(const TrainPropVjpThread& C, const SimBlock bk, const double* __restrict__ cw,
+                                                          double l[3], double le[3]) {
+    const int col = C.col;
+    const long npair = C.npair, pair = C.pair;
+    const TrainPulseDev& Tr = C.Tr;
+    if (C.live) {
+        const double* c = cw + Tr.w_off + (long)bk.scale * TRAIN_ENT * npair + pair;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { l[i] = c[(3 * col + i) * npair]; le[i] = c[(12 + 3 * col + i) * npair]; }
+    }
+}
+// The forward half: the checkpoints of the primal column, which depend on b1 alone.  Leaves the pulse's last tile staged.
+__device__ __forceinline__ void bloch_train_prop_vjp_forward(const TrainPropVjpThread& C, double (*sst)[8],
+                                                             const double* __restrict__ in) {
+    const BlochPulseDev& P = C.P;
+    const double sc = C.sc, gamma = C.gamma, px = C.px, py = C.py, pz = C.pz, dfv = C.dfv;
+    const int ntime = C.ntime, col = C.col;
+    const bool rec = C.rec;
+    double* wck = C.wck;
+    double m[3] = {col == 0 ? 1.0 : 0.0, col == 1 ? 1.0 : 0.0, col == 2 ? 1.0 : 0.0};
+    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
+        bloch_ss_stage(sst, in, P.t_off, ntime, t0, sc, gamma);
+        const int cnt = min(BLOCH_CH, ntime - t0);
+        for (int q = 0; q < cnt; ++q) {
+            if ((q & (VJP_T - 1)) == 0) {                                 // the column before sample t0 + q: the group's checkpoint
+                double* w = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
+                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
+            }
+            const double* s = sst[q];
+            const double rz = bloch_rotz(s, px, py, pz, dfv);
+            if (rec) bloch_fwd_step(s, rz, m); else bloch_hom_step(s, rz, m);
+        }
+    }
+}
+// The backward half, the pulse's last tile being staged in sst and the checkpoints written: the partials of (l, le) into wpart.
+__device__ __forceinline__ void bloch_train_prop_vjp_backward(const TrainPropVjpThread& C, double (*sst)[8], double* red,
+                                                              const double* __restrict__ in, double l[3], const double le[3]) {
+    const BlochPulseDev& P = C.P;
+    const double sc = C.sc, gamma = C.gamma, px = C.px, py = C.py, pz = C.pz, dfv = C.dfv;
+    const int ntime = C.ntime, echo = C.echo, tid = threadIdx.x;
+    const bool rec = C.rec, live = C.live;
+    double2* wpart = C.wpart;
+    const double* wck = C.wck;
+    const int tlast = (ntime - 1) / BLOCH_CH * BLOCH_CH;
+    const int row = tid >> 4, ln = tid & 15;                              // reduction: 16 lanes per row of the tile
+    for (int t0 = tlast; t0 >= 0; t0 -= BLOCH_CH) {
+        if (t0 != tlast) bloch_ss_stage(sst, in, P.t_off, ntime, t0, sc, gamma);      // the forward sweep left the last tile staged
+        const int cnt = min(BLOCH_CH, ntime - t0);
+        for (int g0 = (cnt - 1) / VJP_T * VJP_T; g0 >= 0; g0 -= VJP_T) {
+            const int ge = min(g0 + VJP_T, cnt);
+            double ms[VJP_T][3];                                          // ms[j] = the column before sample t0 + g0 + j
+            const double* w = wck + (long)((t0 + g0) / VJP_T) * BLOCH_CK;
+            ms[0][0] = w[0]; ms[0][1] = w[256]; ms[0][2] = w[512];
+#pragma unroll
+            for (int j = 1; j < VJP_T; ++j) {
+                ms[j][0] = ms[j - 1][0]; ms[j][1] = ms[j - 1][1]; ms[j][2] = ms[j - 1][2];
+                if (g0 + j < ge) {
+                    const double* s = sst[g0 + j - 1];
+                    const double rz = bloch_rotz(s, px, py, pz, dfv);
+                    if (rec) bloch_fwd_step(s, rz, ms[j]); else bloch_hom_step(s, rz, ms[j]);
+                }
+            }
+#pragma unroll
+            for (int j = VJP_T - 1; j >= 0; --j) {
+                if (g0 + j < ge) {
+                    if (t0 + g0 + j + 1 == echo) { l[0] += le[0]; l[1] += le[1]; l[2] += le[2]; }      // the state after `echo` samples
+                    const double* s = sst[g0 + j];
+                    const double2 c = bloch_vjp_step(s, bloch_rotz(s, px, py, pz, dfv), ms[j], l);
+                    red[(2 * j) * VJP_ROW + tid] = live ? c.x : 0.0;
+                    red[(2 * j + 1) * VJP_ROW + tid] = live ? c.y : 0.0;
+                }
+            }
+            __syncthreads();
+            double sum = 0;                                               // row = 2 (sample - g0) + (0: rotx, 1: roty); rows past ge are not stored
+            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
+            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
+            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + t0 + g0)[row] = sum;
+            __syncthreads();
+        }
+    }
+}
 
 // The sections the Bloch least-squares calls add to the forward staging (blochgn.hip bloch_gn_stage, moved here token for token so
 // that blochssgn.hip stages through it too), and the sizes of what stays on the device.

@@ -9,7 +9,9 @@ refine_bloch_batch runs the same loop (_lm_loop, _host_steps) on bloch_lsq_batch
 or with solver='device' each step as one bloch_lm_step_batch call, or with steady_state=True on bloch_ss_lsq_batch /
 bloch_ss_gn_batch, the steady state of the period; refine_bloch_ss_batch is that loop with both solvers, the device one
 taking each step as one bloch_ss_lm_step_batch call.
-refine_bloch_train_batch runs the loop on bloch_train_lsq_batch / bloch_train_gn_batch, the echoes of a pulse train.
+refine_bloch_train_batch runs the loop on bloch_train_lsq_batch / bloch_train_gn_batch, the echoes of a pulse train (DESIGN 8ab);
+refine_bloch_train_lm_batch is that loop with both solvers, the device one taking each step as one bloch_train_lm_step_batch call
+(DESIGN 8ac).
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -275,18 +277,42 @@ def refine_bloch_train_batch(pulses, df, dp, ntr, targets, weights, *, rep_weigh
     changes; df, dp: one grid shared by every pulse or a list of one per pulse; ntr, targets, weights, rep_weights, targets_final,
     weights_final, phases, gains, echo, scales, m0, meq and demod as for bloch_train_lsq_batch, what is given per pulse as a Python
     list of one entry per pulse; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch does.  solver:
-    'host' runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration; there is no device step yet.  A pulse
-    refined in a batch has the bits of the same pulse refined alone."""
-    who = "refine_bloch_train_batch"
+    'host' runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration; this entry point has no device step
+    (refine_bloch_train_lm_batch has both solvers).  A pulse refined in a batch has the bits of the same pulse refined
+    alone."""
+    return _refine_bloch_train("refine_bloch_train_batch", False, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final,
+                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx)
+
+
+def refine_bloch_train_lm_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
+                                phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, iters=5, cg=8,
+                                mu0=None, rtol=1e-6, solver="host", ctx=None):
+    """refine_bloch_train_batch with both solvers: the lock-step Levenberg-Marquardt / CG loop on the echoes of a
+    pulse train; arguments and return value as for refine_bloch_train_batch.  solver: 'host' runs the CG recurrence on the host, one
+    bloch_train_gn_batch call per iteration, and returns the bits and the 'calls' of refine_bloch_train_batch; 'device' solves and
+    tries each step in one bloch_train_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG
+    breakdown counting as a refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    return _refine_bloch_train("refine_bloch_train_lm_batch", True, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final,
+                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx)
+
+
+def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final, weights_final, phases,
+                        gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx):
+    """The body of refine_bloch_train_batch and refine_bloch_train_lm_batch; who: the entry point, for the messages; device_ok:
+    whether the device step may be taken."""
     mb = importlib.import_module(__package__)
     pulses = list(pulses)
     P = len(pulses)
     if P == 0:
         raise ValueError("%s: no pulses" % who)
-    if solver == "device":
-        raise ValueError("%s: the train has no device step; solver must be 'host'" % who)
-    if solver != "host":
-        raise ValueError("%s: solver must be 'host', not %r" % (who, solver))
+    if not device_ok:
+        if solver == "device":
+            raise ValueError("%s: the train has no device step in this entry point; solver must be 'host' (call "
+                             "refine_bloch_train_lm_batch(..., solver='device'))" % who)
+        if solver != "host":
+            raise ValueError("%s: solver must be 'host', not %r" % (who, solver))
+    elif solver not in ("host", "device"):
+        raise ValueError("%s: solver must be 'host' or 'device', not %r" % (who, solver))
     if iters < 0 or cg < 1:
         raise ValueError("%s: iters must be at least 0 and cg at least 1" % who)
     if targets is None and targets_final is None:
@@ -327,8 +353,18 @@ def refine_bloch_train_batch(pulses, df, dp, ntr, targets, weights, *, rep_weigh
             infos[q]["calls"]["gn"] += 1
         return mb.bloch_train_gn_batch(*args(idx, b1s), [v_of[q] for q in idx], sub(weights, idx), **kw(idx))
 
+    def lm(idx, grad, mu):
+        """the step of every active pulse, solved and tried on the device: (b1 + d, L and g there, whether CG broke down)"""
+        for q in idx:
+            infos[q]["calls"]["lm"] += 1
+        res = mb.bloch_train_lm_step_batch(*args(idx, b1s), [-grad[q] for q in idx], sub(weights, idx), [mu[q] for q in idx],
+                                           targets=sub(targets, idx), targets_final=sub(targets_final, idx), cg=cg, rtol=rtol,
+                                           **kw(idx))
+        return [(b1s[q] + d, i["loss"], i["grad"], i["status"] == "breakdown") for q, (d, i) in zip(idx, res)]
+
     def step(idx, grad, mu):
         return _host_steps(idx, b1s, grad, mu, lsq, gn, cg, rtol)
 
-    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
-    return _lm_loop(b1s, infos, lsq, gn, step, iters, mu0)
+    calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
+    return _lm_loop(b1s, infos, lsq, gn, lm if solver == "device" else step, iters, mu0)
