@@ -106,7 +106,9 @@ enum {
     S_ALPHA0, S_DTAU_C, S_DKAP_C, S_PICK, S_NCORR, S_NPICK,
     S_RNA = 40 /* 9 residual norms, batch solve */, S_RNB = 49 /* 9 residual norms, combined solve */,
     S_CG_RZ = 58 /* 2 */, S_CG_ALPHA = 60 /* 2 */, S_CG_BETA = 62 /* 2 */,
-    S_RNC = 64 /* 9 residual norms, corrector solve */, S_SIGMAX = 76 /* the cap on Mehrotra's sigma of this solve: SIGMA_MAX, or SIGMA_MAX_CORR where the centrality corrector runs */, S_COUNT = 80
+    S_RNC = 64 /* 9 residual norms, corrector solve */,
+    S_DTAU0 = 73 /* dtau, dkappa of the uncorrected direction as k_dir_post (mode 1) left them: k_update_pick's blocks read these while block 0 publishes the picked ones */, S_DKAP0 = 74,
+    S_SIGMAX = 76 /* the cap on Mehrotra's sigma of this solve: SIGMA_MAX, or SIGMA_MAX_CORR where the centrality corrector runs */, S_COUNT = 80
 };
 constexpr double STEP = 0.99;
 constexpr double SIGMA_MAX = 0.25;   // cap of Mehrotra's centring parameter (oracle/conic_ipm.py SIGMA_MAX)
@@ -137,7 +139,9 @@ enum { DD_ST_R1 = 0, DD_ST_R2, DD_ST_WBZ, DD_ST_GTW, DD_ST_RHS, DD_ST_Y, DD_ST_C
 static_assert(S_NPICK < S_RNA, "scalar slots: the auto-numbered slots run into S_RNA");
 static_assert(S_RNA + MAX_SWEEPS + 1 <= S_RNB && S_RNB + MAX_SWEEPS + 1 <= S_CG_RZ && S_RNC + MAX_SWEEPS + 1 <= S_SIGMAX,
               "scalar slots: a block of residual norms overlaps the next slot");
-static_assert(S_SIGMAX < S_COUNT, "scalar slots: S_COUNT too small");
+static_assert(S_RNC + MAX_SWEEPS + 1 <= S_DTAU0 && S_DTAU0 < S_DKAP0 && S_DKAP0 < S_SIGMAX, "scalar slots: S_DTAU0 / S_DKAP0 overlap their neighbours");
+static_assert(S_RNA < S_COUNT && S_RNB < S_COUNT && S_CG_BETA + 2 <= S_COUNT && S_RNC < S_COUNT && S_DKAP0 < S_COUNT && S_SIGMAX < S_COUNT,
+              "scalar slots: S_COUNT too small");
 constexpr int CAP_KMAX = 1024;   // strong directions the capacitance form of the extended-precision solve takes (S is CAP_KMAX^2; the one-pass M'(M b) goes to np = 1024)
 constexpr int MAX_LANES = 64, MASK_ROWS = MAX_SWEEPS + 4;
 constexpr int ROW_BEST = MAX_SWEEPS + 1;      // mask rows: 0 live, 1 .. MAX_SWEEPS sweep q, then: lanes with a new best iterate,
@@ -437,13 +441,18 @@ __global__ __launch_bounds__(256) void k_atmulti(DProg P, const double* __restri
 constexpr int FPC = 16;
 __global__ __launch_bounds__(FPC * 16) void k_fold_partials(const double* __restrict__ partial, int nsplit, int nvv, int ld,
                                                         int ldo, double* __restrict__ TT, size_t lane_bytes, const int* lane_mask,
-                                                        const LaneDims* __restrict__ dims, int cgrp) {
+                                                        const LaneDims* __restrict__ dims, int cgrp, int vtrim = 1 << 30, int jtrim = 0) {
     LANES_RAW(lane_bytes, lane_mask, partial, TT);
     if (dims) nsplit = cgrp > 0 ? (dims[blockIdx.z].nchunk + cgrp - 1) / cgrp : (dims[blockIdx.z].Mown - cgrp - 1) / -cgrp;     // (cgrp < 0: dense path, -cgrp rows per split)
+    // (the H-build's border moments: the rows from vtrim on are read at the columns below jtrim = D1 alone, and the moment kernel's blocks
+    //  past D1 have not written their partials -- trim_border --, so nothing is folded or stored there)
+    if (dims && vtrim < nvv) jtrim = dims[blockIdx.z].D1;
     __shared__ double sh[16][FPC + 1];
     const int c = threadIdx.x, sg = threadIdx.y, j = blockIdx.x * FPC + c, v = blockIdx.y;
+    if (v >= vtrim && blockIdx.x * FPC >= jtrim) return;
+    const bool on = j < ld && (v < vtrim || j < jtrim);   // (the block that straddles jtrim leaves out its columns past it)
     double t = 0;
-    if (j < ld) {
+    if (on) {
         const double* p = partial + (long)v * ld + j;
         const long ss = (long)nvv * ld;
         int s = sg;
@@ -455,7 +464,7 @@ __global__ __launch_bounds__(FPC * 16) void k_fold_partials(const double* __rest
     }
     sh[sg][c] = t;
     __syncthreads();
-    if (sg == 0 && j < ld) {
+    if (sg == 0 && on) {
         double a = 0;
 #pragma unroll
         for (int q = 0; q < 16; ++q) a += sh[q][c];
@@ -668,6 +677,8 @@ __global__ __launch_bounds__(256) void k_trig_eval(DProg P, const double* __rest
 // (SFUSE = 1).  Which product is fused decides the last bit, and a single solve always runs the unpaired kernels, so each paired kernel
 // copies its twin's form here.  This is a copy, not a shared definition: if a compiler contracts the unpaired kernels otherwise,
 // tests/test_lanepair_gpu.py (unit against single solves, bitwise) fails and SFUSE has to follow.
+// (k_trig_moments itself now calls rotate<1> too: its body is instantiated twice per kernel -- all operands, and the full-length
+//  ones alone where the border moments are not read -- and the two have to round alike.)
 template <int SFUSE>
 __device__ __forceinline__ void rotate(double& c, double& s, double cd, double sd) {
     const double cn = fma(c, cd, -(s * sd));
@@ -895,13 +906,18 @@ __global__ __launch_bounds__(256) void k_freq_fold(DProg P, const double* __rest
 }
 // FOLD (round 5: one launch less per G'v): the folded operands are formed HERE from the row vector `rows` -- what k_freq_fold<NV, true>
 // would have written to src (same sums, same order) -- by every block for the 256 frequencies of its chunk group.
-template <int NV, bool FOLD = false>
-__global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __restrict__ src, const double4* __restrict__ seeds,
-                                                      int na, int nb, double* __restrict__ partial, const double* __restrict__ rows = nullptr) {
-    if (!P.seeds_shared && blockIdx.z) seeds = reinterpret_cast<const double4*>(reinterpret_cast<const char*>(seeds) + (size_t)blockIdx.z * P.lane_bytes);
-    LANES(P, src, partial, rows);
-    if (P.dims) { na = P.D1; nb = nb ? 2 * P.D1 - 1 : 0; }      // (the launch carries the unit's largest extent: the lane's own)
-    __shared__ double2 pp[NV][CGRP][CHK];                 // (pe, po)
+// Border moments only where they are read (the H-build's one-pass form: `nfull` full-length operands in front, the border operands
+// behind them, all on the progressions (na = D1, nb = 2 D1 - 1)): k_assemble_H_lat reads the border moments at the points m < D1 alone
+// -- the two-pass form runs them over (D1, 0) --, so a block whose points all lie at m >= na runs the body with the first NVA = nfull
+// operands: it stages, accumulates and stores those, every one by the instructions and in the order of the full body (the operands
+// share the (c, s) chains and nothing else), in the partial layout of the launch's NV.  The block that straddles na does all operands.
+// The border rows of `partial` keep stale words at m >= na past those blocks; k_fold_partials folds those rows over the columns m < na alone.
+template <int NV>
+__device__ __forceinline__ bool trim_border(int nfull, int na) { return NV > 1 && nfull == 1 && int(blockIdx.x) * MPTS >= na; }
+template <int NV, int NVA, bool FOLD>
+__device__ __forceinline__ void trig_moments_body(const DProg& P, const double2* __restrict__ src, const double4* __restrict__ seeds, int na, int nb,
+                                                  double* __restrict__ partial, const double* __restrict__ rows, double2 (*pp)[CGRP][CHK]) {
+    static_assert(NVA == NV || !FOLD, "trig_moments_body: the trimmed form is the H-build's");
     const int tid = threadIdx.x;
     const int ch0 = blockIdx.y * P.cgrp;
     for (int e = tid; e < P.cgrp * CHK; e += 256) {       // stage the operands of the group's chunks
@@ -913,18 +929,18 @@ __global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __
             freq_operands<NV, true>(P, rows, live ? P.fold_pos[k] : -1, a);
             freq_operands<NV, true>(P, rows, live ? P.fold_neg[k] : -1, b);
 #pragma unroll
-            for (int v = 0; v < NV; ++v) pp[v][cc][q] = make_double2(a[v] + b[v], a[v] - b[v]);
+            for (int v = 0; v < NVA; ++v) pp[v][cc][q] = make_double2(a[v] + b[v], a[v] - b[v]);
         } else {
 #pragma unroll
-        for (int v = 0; v < NV; ++v) pp[v][cc][q] = live ? src[(long)v * P.Mpad + k] : make_double2(0.0, 0.0);
+        for (int v = 0; v < NVA; ++v) pp[v][cc][q] = live ? src[(long)v * P.Mpad + k] : make_double2(0.0, 0.0);
         }
     }
     __syncthreads();
     const int m = blockIdx.x * MPTS + tid;
     if (m >= na + nb) return;
-    double ag[NV], as[NV];
+    double ag[NVA], as[NVA];
 #pragma unroll
-    for (int v = 0; v < NV; ++v) ag[v] = as[v] = 0;
+    for (int v = 0; v < NVA; ++v) ag[v] = as[v] = 0;
     // two chunks at a time: their recurrences are independent chains, which is what keeps the fp64 pipe busy with the
     // two or three waves per SIMD this grid has (operands past a chunk's end are staged as zeros)
     for (int cl = 0; cl < P.cgrp; cl += 2) {
@@ -939,21 +955,36 @@ __global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __
 #pragma unroll 4
         for (int q = 0; q < cnt; ++q) {
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
+            for (int v = 0; v < NVA; ++v) {
                 const double2 pa = pp[v][cl][q], pb = pp[v][clb][q];
                 ag[v] += pa.x * c0; as[v] += pa.y * s0;
                 ag[v] += pb.x * c1; as[v] += pb.y * s1;
             }
-            const double n0 = c0 * sa.z - s0 * sa.w, n1 = c1 * sb.z - s1 * sb.w;
-            s0 = s0 * sa.z + c0 * sa.w; s1 = s1 * sb.z + c1 * sb.w;
-            c0 = n0; c1 = n1;
+            // (the form the compiler's contraction gave this recurrence, spelt out since the body has two instantiations per kernel:
+            //  the trimmed blocks' chains must round as the others' do)
+            rotate<1>(c0, s0, sa.z, sa.w);
+            rotate<1>(c1, s1, sb.z, sb.w);
         }
     }
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
+    for (int v = 0; v < NVA; ++v) {
         partial[(((long)blockIdx.y * NV + v) * 2) * P.LDM + m] = ag[v];
         partial[(((long)blockIdx.y * NV + v) * 2 + 1) * P.LDM + m] = as[v];
     }
+}
+
+template <int NV, bool FOLD = false>
+__global__ __launch_bounds__(256) void k_trig_moments(DProg P, const double2* __restrict__ src, const double4* __restrict__ seeds,
+                                                      int na, int nb, double* __restrict__ partial, const double* __restrict__ rows = nullptr,
+                                                      int nfull = NV) {
+    if (!P.seeds_shared && blockIdx.z) seeds = reinterpret_cast<const double4*>(reinterpret_cast<const char*>(seeds) + (size_t)blockIdx.z * P.lane_bytes);
+    LANES(P, src, partial, rows);
+    if (P.dims) { na = P.D1; nb = nb ? 2 * P.D1 - 1 : 0; }      // (the launch carries the unit's largest extent: the lane's own)
+    __shared__ double2 pp[NV][CGRP][CHK];                 // (pe, po)
+    if constexpr (!FOLD && NV > 1) {
+        if (trim_border<NV>(nfull, na)) { trig_moments_body<NV, 1, FOLD>(P, src, seeds, na, nb, partial, rows, pp); return; }
+    }
+    trig_moments_body<NV, NV, FOLD>(P, src, seeds, na, nb, partial, rows, pp);
 }
 
 // a product and a sum rounded on their own, whatever -ffp-contract says
@@ -1041,9 +1072,11 @@ __device__ __forceinline__ void moment_steps16(const double2 (&pa)[NL][NV], cons
 // are gathered; the next two chunks' travel during the loop before.  With one or two operands per lane the loop reads each operand from LDS in ONE lane
 // per row of 16 and hands it to the others inside the FMA (moment_steps16): read by every thread, the wave-uniform reads held the CU's one LDS pipe as
 // long as the FMAs held its four fp64 pipes, and the two did not overlap.
-template <int NV, int NL, bool FOLD>
+// (NVA: the operands the block works on, the first NVA of the layout's NV -- see trim_border)
+template <int NV, int NL, bool FOLD, int NVA = NV>
 __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* const (&PL)[NL], const double2* const (&src)[NL], const double4* __restrict__ seeds, int na, int nb,
                                                    double* const (&partial)[NL], const double* const (&rows)[NL], double2 (*pp)[NV][CGRP][CHK]) {
+    static_assert(NVA == NV || !FOLD, "trig_moments_lanes: the trimmed form is the H-build's");
     const int tid = threadIdx.x;
     const int ch0 = blockIdx.y * P.cgrp;
     const int m = blockIdx.x * MPTS + tid;
@@ -1066,7 +1099,7 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
 #pragma unroll
             for (int L = 0; L < NL; ++L)
 #pragma unroll
-            for (int v = 0; v < NV; ++v) pp[L][v][cc][q] = live ? src[L][(long)v * P.Mpad + k] : make_double2(0.0, 0.0);
+            for (int v = 0; v < NVA; ++v) pp[L][v][cc][q] = live ? src[L][(long)v * P.Mpad + k] : make_double2(0.0, 0.0);
         }
     }
     __syncthreads();
@@ -1074,11 +1107,11 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
     // in every thread, so a wave with a point to compute keeps all its lanes (a point past the end runs on zero seeds and stores nothing)
     constexpr bool ROWB = NV <= 2;
     if ((ROWB ? m - (tid & 63) : m) >= na + nb) return;
-    double ag[NL][NV], as[NL][NV];
+    double ag[NL][NVA], as[NL][NVA];
 #pragma unroll
     for (int L = 0; L < NL; ++L)
 #pragma unroll
-    for (int v = 0; v < NV; ++v) ag[L][v] = as[L][v] = 0;
+    for (int v = 0; v < NVA; ++v) ag[L][v] = as[L][v] = 0;
     // two chunks at a time: their recurrences are independent chains, which is what keeps the fp64 pipe busy with the
     // two or three waves per SIMD this grid has (operands past a chunk's end are staged as zeros)
     for (int cl = 0; cl < P.cgrp; cl += 2) {
@@ -1094,12 +1127,12 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
             // has sixteen wave-uniform ones), the steps take them by row broadcast.  The last block runs past cnt on operands staged
             // as zeros, like the shorter chunk of the two: fma(0, c, a) = a.
             for (int q0 = 0; q0 < cnt; q0 += 16) {
-                double2 pa[NL][NV], pb[NL][NV];
+                double2 pa[NL][NVA], pb[NL][NVA];
 #pragma unroll
                 for (int L = 0; L < NL; ++L)
 #pragma unroll
-                for (int v = 0; v < NV; ++v) { pa[L][v] = pp[L][v][cl][q0 + (tid & 15)]; pb[L][v] = pp[L][v][clb][q0 + (tid & 15)]; }
-                moment_steps16<NV, NL, 0>(pa, pb, ag, as, c0, s0, c1, s1, sa, sb);
+                for (int v = 0; v < NVA; ++v) { pa[L][v] = pp[L][v][cl][q0 + (tid & 15)]; pb[L][v] = pp[L][v][clb][q0 + (tid & 15)]; }
+                moment_steps16<NVA, NL, 0>(pa, pb, ag, as, c0, s0, c1, s1, sa, sb);
             }
         } else {
 #pragma unroll (NV * NL > 4 ? 2 : 4)
@@ -1107,7 +1140,7 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
 #pragma unroll
             for (int L = 0; L < NL; ++L)
 #pragma unroll
-            for (int v = 0; v < NV; ++v) {
+            for (int v = 0; v < NVA; ++v) {
                 const double2 pa = pp[L][v][cl][q], pb = pp[L][v][clb][q];
                 ag[L][v] += pa.x * c0; as[L][v] += pa.y * s0;
                 ag[L][v] += pb.x * c1; as[L][v] += pb.y * s1;
@@ -1122,7 +1155,7 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
 #pragma unroll
     for (int L = 0; L < NL; ++L)
 #pragma unroll
-    for (int v = 0; v < NV; ++v) {
+    for (int v = 0; v < NVA; ++v) {
         partial[L][(((long)blockIdx.y * NV + v) * 2) * P.LDM + m] = ag[L][v];
         partial[L][(((long)blockIdx.y * NV + v) * 2 + 1) * P.LDM + m] = as[L][v];
     }
@@ -1132,7 +1165,8 @@ __device__ __forceinline__ void trig_moments_lanes(const DProg& P, const DProg* 
 // k_trig_moments<4, true> gets); else the H-build form, operands from the lanes' `src` (PPf), both progressions.  DESIGN.md section 4.
 template <int NV, bool FOLD = true>
 __global__ __launch_bounds__(256, 4) void k_trig_moments_pair(DProg P, const double2* __restrict__ src, const double4* __restrict__ seeds, int na, int nb,
-                                                                       double* __restrict__ partial, const double* __restrict__ rows, int nlanes) {
+                                                                       double* __restrict__ partial, const double* __restrict__ rows, int nlanes,
+                                                                       int nfull = NV) {
     static_assert(!FOLD || NV <= 2, "k_trig_moments_pair: G'v of one or two operands");
     __shared__ double2 pp[2][NV][CGRP][CHK];
     bool live[2];
@@ -1147,12 +1181,18 @@ __global__ __launch_bounds__(256, 4) void k_trig_moments_pair(DProg P, const dou
         const double2* const s2[2] = {FOLD ? nullptr : byte_shift(src, off0), FOLD ? nullptr : byte_shift(src, off0 + off1)};
         double* const o2[2] = {byte_shift(partial, off0), byte_shift(partial, off0 + off1)};
         const double* const r2[2] = {FOLD ? byte_shift(rows, off0) : nullptr, FOLD ? byte_shift(rows, off0 + off1) : nullptr};
+        if constexpr (!FOLD && NV > 1) {
+            if (trim_border<NV>(nfull, na)) { trig_moments_lanes<NV, 2, FOLD, 1>(P, p2, s2, seeds, na, nb, o2, r2, pp); return; }
+        }
         trig_moments_lanes<NV, 2, FOLD>(P, p2, s2, seeds, na, nb, o2, r2, pp);
     } else {
         const DProg* const p1[1] = {&Q};
         const double2* const s1[1] = {FOLD ? nullptr : byte_shift(src, off0 + off1)};
         double* const o1[1] = {byte_shift(partial, off0 + off1)};
         const double* const r1[1] = {FOLD ? byte_shift(rows, off0 + off1) : nullptr};
+        if constexpr (!FOLD && NV > 1) {
+            if (trim_border<NV>(nfull, na)) { trig_moments_lanes<NV, 1, FOLD, 1>(P, p1, s1, seeds, na, nb, o1, r1, pp); return; }
+        }
         trig_moments_lanes<NV, 1, FOLD>(P, p1, s1, seeds, na, nb, o1, r1, pp);
     }
 }
@@ -1175,6 +1215,48 @@ __device__ __forceinline__ double fold_partials(const double* part, int nb, int 
         a = is_max ? fmax(a, v) : a + v;
     }
     return is_max ? block_max(a, sh) : block_sum(a, sh);
+}
+// K block reductions in ONE barrier sequence (the prologues of the cone kernels ran one block_sum / block_max after the other): column k
+// goes through the wave tree and then over the waves in their order exactly as in block_sum / block_max -- thread k does the walk
+// thread 0 does there --, so every result has the bits of its own call.  sh: K rows of 17 doubles; results valid in every thread
+template <int K>
+__device__ __forceinline__ void block_reduce_k(double (&v)[K], bool is_max, double (*sh)[17]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = is_max ? wave_max(v[k]) : wave_sum(v[k]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) sh[k][wv] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double* q = sh[threadIdx.x];
+        double t = is_max ? q[0] : 0.0 + q[0];
+        for (int i = 1; i < nw; ++i) t = is_max ? fmax(t, q[i]) : t + q[i];
+        q[16] = t;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) v[k] = sh[k][16];
+}
+// fold_partials of the K columns c0 .. c0 + K - 1 in one pass over the partial rows (each thread walks its rows in fold_partials' order)
+template <int K>
+__device__ __forceinline__ void fold_partials_k(const double* part, int nb, int nc, int c0, bool is_max, double (&a)[K], double (*sh)[17]) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) a[k] = is_max ? -1e300 : 0.0;
+    for (int b = threadIdx.x; b < nb; b += blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const double v = part[(long)b * nc + c0 + k];
+            a[k] = is_max ? fmax(a[k], v) : a[k] + v;
+        }
+    }
+    block_reduce_k<K>(a, is_max, sh);
+}
+// the step to the boundary from the folded maxima (k_scal_step's arithmetic, shared by the kernels that form it themselves)
+__device__ __forceinline__ double step_bound(double ts, double tz, double tau, double kap, double dtau, double dkap) {
+    return fmax(0.0, fmax(fmax(ts, tz), fmax(-dtau / tau, -dkap / kap)));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1503,29 +1585,29 @@ __global__ __launch_bounds__(1024) void k_cg_start(DProg P, double* __restrict__
 // The same behind the one-pass z = M'M r (round 5: one launch instead of k_hsolve_fold + k_cg_start): 1024 threads add the
 // HS_PARTS partial vectors of k_hsolve in k_hsolve_fold's order (thread (w, t) the entry j = t + 256 w), then the first 256 do
 // k_cg_start's sums -- thread t over its four entries in w order, the block sum of 256 threads -- with z from LDS: the same bits.
+// One workgroup per vector (grid (NV, 1, lanes), vector v = blockIdx.x: the vectors share nothing -- their own partials, p, r and
+// S_CG_RZ + v --, so two workgroups do side by side what one did one after the other); a grid of one workgroup does all NV.
 template <int NV>
 __global__ __launch_bounds__(1024) void k_fold_cg_start(DProg P, double* __restrict__ Sc, const double* __restrict__ r,
                                                         const double* __restrict__ part, double* __restrict__ p, int first) {
     LANES(P, Sc, r, part, p);
-    __shared__ double zs[NV][1024];
+    __shared__ double zs[1024];
     __shared__ double sh[17];
     const int t = threadIdx.x;
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
+    const bool act = t < SCAL_T;                              // (the 768 others only keep the barriers company)
+    const int lane = t & 63, wv = t >> 6;
+    const int v0 = gridDim.x > 1 ? blockIdx.x : 0, v1 = gridDim.x > 1 ? blockIdx.x + 1 : NV;
+    for (int v = v0; v < v1; ++v) {
         double x[HS_PARTS];
 #pragma unroll
         for (int g = 0; g < HS_PARTS; ++g) x[g] = t < P.np ? part[((long)g * NV + v) * P.np + t] : 0.0;
         double s = 0;
 #pragma unroll
         for (int g = 0; g < HS_PARTS; ++g) s += x[g];
-        zs[v][t] = s;
-    }
-    __syncthreads();
-    const bool act = t < SCAL_T;                              // (the 768 others only keep the barriers company)
-    const int lane = t & 63, wv = t >> 6;
-    for (int v = 0; v < NV; ++v) {
+        zs[t] = s;                                            // (a grid of one: the barrier that ends the vector before has freed zs)
+        __syncthreads();
         double a = 0;
-        if (act) for (int j = t; j < P.N; j += SCAL_T) a += r[(long)v * P.LDV + j] * zs[v][j];
+        if (act) for (int j = t; j < P.N; j += SCAL_T) a += r[(long)v * P.LDV + j] * zs[j];
         a = wave_sum(a);                                      // block_sum of the first 256 threads
         __syncthreads();
         if (act && lane == 0) sh[wv] = a;
@@ -1537,7 +1619,7 @@ __global__ __launch_bounds__(1024) void k_fold_cg_start(DProg P, double* __restr
         const double beta = first ? 0.0 : (rz_old > 0 ? rz_new / rz_old : 0.0);
         if (act) for (int j = t; j < P.N; j += SCAL_T) {
             const long o = (long)v * P.LDV + j;
-            p[o] = first ? zs[v][j] : zs[v][j] + beta * p[o];
+            p[o] = first ? zs[j] : zs[j] + beta * p[o];
         }
         __syncthreads();
         if (t == 0) Sc[S_CG_RZ + v] = rz_new;
@@ -1631,23 +1713,35 @@ __global__ __launch_bounds__(256) void k_cg_step_update(DProg P, double* __restr
     if (threadIdx.x == 0) Sc[slot] = m;
 }
 // dots needed for dtau: c'x1, c'x2 (N space) ; h'z1, h'z2, ||W z1||^2 (R space)
+// ADD (the corrector's tail, one-phase, programs without a big cone: one launch less): k_corr_add comes first -- the candidate
+// xk = x2c + xk, zk = z2c + zk, gk = g2c + gk is formed in place, every thread its own LP row or its cone's three rows (these are all
+// the rows there are without a big cone), the N-space vector by a grid-stride loop -- and the sums take the new zk as z2
+template <bool ADD>
 __global__ __launch_bounds__(256) void k_dots_r(DProg P, const double* __restrict__ wl, const double* __restrict__ w3,
                                                 const double* __restrict__ z1, const double* __restrict__ z2,
-                                                double* __restrict__ part) {
-    LANES(P, wl, w3, z1, z2, part);
+                                                double* __restrict__ part, const double* __restrict__ x2c,
+                                                const double* __restrict__ z2c, const double* __restrict__ g2c,
+                                                double* __restrict__ xk, double* __restrict__ zk, double* __restrict__ gk) {
+    LANES(P, wl, w3, z1, z2, part, x2c, z2c, g2c, xk, zk, gk);
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     double v[3] = {0, 0, 0};
+    if (ADD) for (int j = t; j < P.N; j += gridDim.x * blockDim.x) xk[j] = x2c[j] + xk[j];
     if (t < P.l) {
-        v[0] = P.h[t] * z1[t]; v[1] = P.h[t] * z2[t];
+        double zt;
+        if (ADD) { zt = z2c[t] + zk[t]; zk[t] = zt; gk[t] = g2c[t] + gk[t]; } else zt = z2[t];
+        v[0] = P.h[t] * z1[t]; v[1] = P.h[t] * zt;
         double wz = wl[t] * z1[t];
         v[2] = wz * wz;
         if (!P.own && P.rep[t]) v[0] = v[1] = v[2] = 0.0;
     } else if (t < P.l + P.nq3) {
         int c = t - P.l, r = P.l + 3 * c;
         Soc3 W = load_w3(w3, c);
-        double zz[3] = {z1[r], z1[r + 1], z1[r + 2]}, wz[3];
+        double zz[3] = {z1[r], z1[r + 1], z1[r + 2]}, wz[3], zt[3];
+        for (int a = 0; a < 3; ++a) {
+            if (ADD) { zt[a] = z2c[r + a] + zk[r + a]; zk[r + a] = zt[a]; gk[r + a] = g2c[r + a] + gk[r + a]; } else zt[a] = z2[r + a];
+        }
         soc3_apply(W, zz, wz, false);
-        for (int a = 0; a < 3; ++a) { v[0] += P.h[r + a] * z1[r + a]; v[1] += P.h[r + a] * z2[r + a]; v[2] += wz[a] * wz[a]; }
+        for (int a = 0; a < 3; ++a) { v[0] += P.h[r + a] * z1[r + a]; v[1] += P.h[r + a] * zt[a]; v[2] += wz[a] * wz[a]; }
         if (!P.own && P.rep[r]) v[0] = v[1] = v[2] = 0.0;
     }
     // (programs with the big cone: its partial row comes FIRST, the block partials behind it -- positions that do not move with the
@@ -1746,9 +1840,10 @@ __global__ __launch_bounds__(256) void k_dir_post(DProg P, const double* __restr
         }
         dtau = (dkc / tau - bt + cx2 + hz2) / den;
         if (blockIdx.x == 0 && threadIdx.x == 0) {
+            const double dkap = (dkc - kap * dtau) / tau;
             Sc[mode == 0 ? S_DTAU_A : mode == 3 ? S_DTAU_C : S_DTAU] = dtau;
-            Sc[mode == 0 ? S_DKAP_A : mode == 3 ? S_DKAP_C : S_DKAP] = (dkc - kap * dtau) / tau;
-            if (mode == 1) { Sc[S_TAU0] = tau; Sc[S_KAP0] = kap; }
+            Sc[mode == 0 ? S_DKAP_A : mode == 3 ? S_DKAP_C : S_DKAP] = dkap;
+            if (mode == 1) { Sc[S_TAU0] = tau; Sc[S_KAP0] = kap; Sc[S_DTAU0] = dtau; Sc[S_DKAP0] = dkap; }
         }
     } else {
         dtau = mode == 0 ? Sc[S_DTAU_A] : mode == 3 ? Sc[S_DTAU_C] : Sc[S_DTAU];
@@ -1885,11 +1980,11 @@ __global__ __launch_bounds__(256) void k_comb_rhs(DProg P, const double* __restr
     int t = blockIdx.x * blockDim.x + threadIdx.x;
     double sigma;
     if (spart) {
-        __shared__ double sh[17];
-        const double ts = fold_partials(spart, nsp, 2, 0, true, sh);
-        const double tz = fold_partials(spart, nsp, 2, 1, true, sh);
+        __shared__ double sh[2][17];
+        double tm[2];
+        fold_partials_k<2>(spart, nsp, 2, 0, true, tm, sh);      // (both maxima in one pass and one barrier sequence)
         const double tau = Sc[S_TAU], kap = Sc[S_KAPPA];
-        const double tt = fmax(0.0, fmax(fmax(ts, tz), fmax(-Sc[S_DTAU_A] / tau, -Sc[S_DKAP_A] / kap)));
+        const double tt = step_bound(tm[0], tm[1], tau, kap, Sc[S_DTAU_A], Sc[S_DKAP_A]);
         const double a = tt == 0.0 ? 1.0 : fmin(1.0, 1.0 / tt);
         sigma = fmin((1 - a) * (1 - a) * (1 - a), Sc[S_SIGMAX]);
         if (blockIdx.x == 0) {
@@ -1985,12 +2080,41 @@ __global__ __launch_bounds__(256) void k_update(DProg P, double* __restrict__ Sc
 }
 // the same after a centrality corrector: k_scal_step (mode 3) has chosen between the two directions (S_PICK), set alpha, dtau
 // and moved tau, kappa
-__global__ __launch_bounds__(256) void k_update_pick(DProg P, const double* __restrict__ Sc, const double* __restrict__ x1,
+// part != null (one-phase, sw.fuse: one launch less): the pick and the step are formed HERE -- k_scal_step's fold of the corrected
+// direction's maxima and its scalar arithmetic (mode 3), by every block for itself; block 0 publishes what mode 3 publishes.  What block 0
+// overwrites the blocks read from the snapshots k_dir_post (mode 1) left: tau, kappa in S_TAU0 / S_KAP0, the uncorrected dtau, dkappa in
+// S_DTAU0 / S_DKAP0 (nothing has moved tau or kappa since).  The pick is ONE value, pickd, behind a barrier the optimiser cannot see
+// through: the step, dtau, the direction moved along and the stored S_PICK / S_NPICK all come from it and cannot disagree (see the NOTE
+// at k_scal_step)
+__global__ __launch_bounds__(256) void k_update_pick(DProg P, double* __restrict__ Sc, const double* __restrict__ x1,
                          const double* __restrict__ x2, const double* __restrict__ x2k, double* __restrict__ x,
                          const double* __restrict__ ds, const double* __restrict__ dz, const double* __restrict__ dsk,
-                         const double* __restrict__ dzk, double* __restrict__ s, double* __restrict__ z) {
-    LANES(P, Sc, x1, x2, x2k, x, ds, dz, dsk, dzk, s, z);
+                         const double* __restrict__ dzk, double* __restrict__ s, double* __restrict__ z,
+                         const double* __restrict__ part, int nb) {
+    LANES(P, Sc, x1, x2, x2k, x, ds, dz, dsk, dzk, s, z, part);
     int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (part) {
+        __shared__ double sh[2][17];
+        double tm[2];
+        fold_partials_k<2>(part, nb, 2, 0, true, tm, sh);
+        const double tau = Sc[S_TAU0], kap = Sc[S_KAP0], dtauc = Sc[S_DTAU_C], dkapc = Sc[S_DKAP_C];
+        const double tt = step_bound(tm[0], tm[1], tau, kap, dtauc, dkapc);
+        const double ac = tt == 0.0 ? 1.0 : fmin(1.0, STEP / tt);
+        const double a0 = Sc[S_ALPHA0];
+        const double tolk = fmax(REFTOL * Sc[S_NRMC], CORR_ETA * Sc[S_DRES] * tau * Sc[S_NRMC]);
+        double pickd = (ac >= CORR_ACCEPT * a0 && Sc[S_RNC] <= tolk) ? 1.0 : 0.0;
+        asm volatile("" : "+v"(pickd));
+        const bool pick = pickd != 0.0;
+        const double a = pick ? ac : a0, dtau = pick ? dtauc : Sc[S_DTAU0], dkap = pick ? dkapc : Sc[S_DKAP0];
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            Sc[S_TMAX] = tt; Sc[S_PICK] = pickd; Sc[S_NCORR] += 1.0;
+            if (pick) { Sc[S_DTAU] = dtau; Sc[S_DKAP] = dkap; Sc[S_NPICK] += pickd; }
+            Sc[S_ALPHA] = a; Sc[S_TAU] = tau + a * dtau; Sc[S_KAPPA] = kap + a * dkap;
+        }
+        if (t < P.N) x[t] += a * ((pick ? x2k[t] : x2[t]) + dtau * x1[t]);
+        if (t < P.R) { s[t] += a * (pick ? dsk[t] : ds[t]); z[t] += a * (pick ? dzk[t] : dz[t]); }
+        return;
+    }
     const double a = Sc[S_ALPHA], dtau = Sc[S_DTAU];
     const bool pick = Sc[S_PICK] != 0.0;
     if (t < P.N) x[t] += a * ((pick ? x2k[t] : x2[t]) + dtau * x1[t]);
@@ -2009,12 +2133,27 @@ __device__ __forceinline__ void corr_target(double e1, double e2, double mut, do
 }
 __global__ __launch_bounds__(256) void k_corr_rhs(DProg P, const double* __restrict__ wl, const double* __restrict__ dl,
                                                   const double* __restrict__ lam, const double* __restrict__ ds,
-                                                  const double* __restrict__ dz, const double* __restrict__ Sc,
-                                                  double* __restrict__ bz, double* __restrict__ wbz) {
-    LANES(P, wl, dl, lam, ds, dz, Sc, bz, wbz);
+                                                  const double* __restrict__ dz, double* __restrict__ Sc,
+                                                  double* __restrict__ bz, double* __restrict__ wbz,
+                                                  const double* __restrict__ part, int nb) {
+    LANES(P, wl, dl, lam, ds, dz, Sc, bz, wbz, part);
     int t = blockIdx.x * blockDim.x + threadIdx.x;
+    // part != null (one-phase, sw.fuse: one launch less): the trial step is formed HERE -- k_scal_step's fold of the k_dir_post maxima and
+    // its scalar arithmetic (mode 2), by every block for itself (none of the scalars it reads is written in this kernel); block 0
+    // publishes S_TMAX and S_ALPHA0, which k_big_corr_rhs reads behind this kernel
+    double alpha0;
+    if (part) {
+        __shared__ double sh[2][17];
+        double tm[2];
+        fold_partials_k<2>(part, nb, 2, 0, true, tm, sh);
+        const double tt = step_bound(tm[0], tm[1], Sc[S_TAU], Sc[S_KAPPA], Sc[S_DTAU], Sc[S_DKAP]);
+        alpha0 = tt == 0.0 ? 1.0 : fmin(1.0, STEP / tt);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { Sc[S_TMAX] = tt; Sc[S_ALPHA0] = alpha0; }
+    } else {
+        alpha0 = Sc[S_ALPHA0];
+    }
     if (t < P.l) {
-        const double at = fmin(1.0, Sc[S_ALPHA0] + CORR_DELTA), mut = Sc[S_SIGMA] * Sc[S_MU];
+        const double at = fmin(1.0, alpha0 + CORR_DELTA), mut = Sc[S_SIGMA] * Sc[S_MU];
         const double l = lam[t], w = wl[t];
         const double dss = ds[t] / w, wdz = w * dz[t];
         const double v = (l + at * dss) * (l + at * wdz);
@@ -2459,6 +2598,7 @@ struct SolveSwitches {
     bool dd_blockinv = true;     // DD_BLOCKINV=0: substitution instead of the inverses of the dd factor's diagonal blocks
     bool hsolve = true;          // HSOLVE=0: the preconditioner as two triangular GEMVs instead of one pass over M
     bool fuse = true;            // FUSE=0: folds, residual norm, CG start and step length as launches of their own instead of inside their neighbours
+                                 // (the corrector's trial step, candidate sum and pick included; the H-build's border moments over all points)
     bool speculate = true;       // SPECULATE=0: the head of the next iteration goes out after the host's verdicts, not before
     bool trace_host = false;     // TRACE_HOST (set): report where the host thread spends the solve
     int fold = -1;               // FOLD: -1 unset (fold unless the extended-precision solve is on), 0 / 1 every frequency on its own / +w and -w paired
@@ -2992,7 +3132,10 @@ struct Solver::Impl {
     // border products of the H assembly: partial = A1' * BB (BB is a per-frequency array)
     // lattice mode: moments of per-frequency arrays on the progressions (t0a, na), (t0b, nb)
     // pp == nullptr: the folded operands are in PPf already (k_freq_blocks_fold)
-    void moments_array(int nv, const double* pp, const double4* seeds, int na, int nb, double* out) {
+    // nfull (0: all): the operands in front that are read over the whole of (na, nb); those behind are read at the points m < na alone and the
+    // blocks past na leave them out (trim_border); k_fold_partials folds their rows over the columns below na alone, `out` keeps stale words past them
+    void moments_array(int nv, const double* pp, const double4* seeds, int na, int nb, double* out, int nfull = 0) {
+        if (nfull <= 0) nfull = nv;
         dim3 g(cdiv(na + nb, MPTS), cdiv(P.nchunk, P.cgrp)), b(256), gf(cdiv(P.nfold, 256));
         const bool pair = lane_pairs();                    // (the H-build's moment pass: k_trig_moments_pair<NV, false>)
         if (pair) ++n_pair;
@@ -3000,14 +3143,15 @@ struct Solver::Impl {
 #define MOM_CASE(NVX)                                                                                                          \
             case NVX:                                                                                                          \
                 if (pp) hipLaunchKernelGGL((k_freq_fold<NVX, false>), lane_grid(gf, nlanes), b, 0, st, P, pp, PPf);            \
-                if (pair) hipLaunchKernelGGL((k_trig_moments_pair<NVX, false>), lane_grid(g, cdiv(nlanes, 2)), b, 0, st, P, PPf, seeds, na, nb, partial, (const double*)nullptr, nlanes); \
-                else hipLaunchKernelGGL((k_trig_moments<NVX>), lane_grid(g, nlanes), b, 0, st, P, PPf, seeds, na, nb, partial); \
+                if (pair) hipLaunchKernelGGL((k_trig_moments_pair<NVX, false>), lane_grid(g, cdiv(nlanes, 2)), b, 0, st, P, PPf, seeds, na, nb, partial, (const double*)nullptr, nlanes, nfull); \
+                else hipLaunchKernelGGL((k_trig_moments<NVX>), lane_grid(g, nlanes), b, 0, st, P, PPf, seeds, na, nb, partial, (const double*)nullptr, nfull); \
                 break;
             MOM_CASE(1) MOM_CASE(2) MOM_CASE(3) MOM_CASE(4) MOM_CASE(6)
 #undef MOM_CASE
             default: throw HipError("moments: unsupported vector count");
         }
-        hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.LDM, FPC), 2 * nv), nlanes), dim3(FPC, 16), 0, st, partial, cdiv(P.nchunk, P.cgrp), 2 * nv, P.LDM, P.LDM, out, lane_bytes, P.mask, P.dims, P.cgrp);
+        hipLaunchKernelGGL(k_fold_partials, lane_grid(dim3(cdiv(P.LDM, FPC), 2 * nv), nlanes), dim3(FPC, 16), 0, st, partial, cdiv(P.nchunk, P.cgrp), 2 * nv, P.LDM, P.LDM, out, lane_bytes, P.mask, P.dims, P.cgrp,
+                           nfull < nv ? 2 * nfull : 1 << 30, na);
     }
     void atmulti_array(int nvv, const double* pp) {
         dim3 g(P.ld / 128, nsplit_at), b(64, 4);
@@ -3118,7 +3262,8 @@ struct Solver::Impl {
         auto z_and_start = [&](int first) {
             if (sw.fuse && fused_hsolve) {
                 hsolve_launch(M, P.np, r, nullptr, tmpN2, partial, NV, P.LDV, st, nlanes, lane_bytes, P.mask, false);
-                hipLaunchKernelGGL(k_fold_cg_start<NV>, g1, dim3(1024), 0, st, P, Sc, r, partial, pN, first);
+                // (one workgroup per vector; the row-sharded form keeps the one workgroup it had)
+                hipLaunchKernelGGL(k_fold_cg_start<NV>, lane_grid(dim3(shard_size <= 1 ? NV : 1), nlanes), dim3(1024), 0, st, P, Sc, r, partial, pN, first);
             } else {
                 hsolve<NV>(r, tmpN2);
                 hipLaunchKernelGGL(k_cg_start<NV>, g1, dim3(SCAL_T), 0, st, P, Sc, r, tmpN2, pN, first);
@@ -3307,7 +3452,9 @@ struct Solver::Impl {
                 // delays start at 0: the border moments sit on the difference progression, one moment launch does both,
                 // and the per-frequency blocks go straight into its folded operands (no Dw / BB round trip)
                 hipLaunchKernelGGL(k_freq_blocks_fold, lane_grid(dim3(cdiv(P.nfold, 256)), nlanes), dim3(256), 0, st, P, dlw, w3, m3c, nwv + nvb, PPf);
-                moments_array(nwv + nvb, nullptr, P.seed_h, P.D1, 2 * P.D1 - 1, Mom);
+                // (the border operands, behind the nwv weight operands, only where k_assemble_H_lat reads their moments: sw.fuse, unsharded --
+                //  a row-sharded build all-reduces the whole of Mom)
+                moments_array(nwv + nvb, nullptr, P.seed_h, P.D1, 2 * P.D1 - 1, Mom, (sw.fuse && shard_size <= 1) ? nwv : 0);
                 momb = Mom + 2L * nwv * P.LDM;
             } else {
                 moments_array(nwv, Dw, P.seed_h, P.D1, 2 * P.D1 - 1, Mom);
@@ -3862,8 +4009,14 @@ struct Solver::Impl {
     // request): folded by k_scal_dtau and summed over the ranks.  Returns the number of partial rows (otherwise k_dir_post folds them itself)
     // (`two`: -1 = the form of this solve, two-phase where it is row-sharded; 0 / 1 as asked)
     bool two_phase(int two) const { return two < 0 ? shard_size > 1 : two != 0; }
-    int dots(const double* xx2, const double* zz2, int mode, int two = -1) {
-        hipLaunchKernelGGL(k_dots_r, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, dz2, zz2, partR);
+    // (add_corr: the corrector's candidate is formed by the same launch, in place in kx / kz / kg -- k_dots_r<true> in place of k_corr_add)
+    int dots(const double* xx2, const double* zz2, int mode, int two = -1, bool add_corr = false) {
+        const double* none = nullptr;
+        if (add_corr)
+            hipLaunchKernelGGL(k_dots_r<true>, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, dz2, none, partR, dxc, dzc, gdxc, kx, kz, kg);
+        else
+            hipLaunchKernelGGL(k_dots_r<false>, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, w3, dz2, zz2, partR, none, none, none,
+                               (double*)nullptr, (double*)nullptr, (double*)nullptr);
         int nb = std::max(nbC, 1);
         if (P.big) {
             hipLaunchKernelGGL(k_big_dots, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, Sc, dz2, zz2, scratch, partR);
@@ -3933,19 +4086,24 @@ struct Solver::Impl {
     // orthant rows' products at the trial step alpha0 + CORR_DELTA, projected onto the box around sigma mu, give one more right-hand
     // side for the factorisation at hand
     void stage_corr_rhs(int ns1, int corr_cones, const int* corr_ddm, bool two) {
-        scal_step(2, ns1, true, two);
-        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz);
+        const bool fused = sw.fuse && !two;          // (the trial step is formed inside k_corr_rhs)
+        if (!fused) scal_step(2, ns1, true, two);
+        hipLaunchKernelGGL(k_corr_rhs, lane_grid(dim3(std::max(nbC, 1)), nlanes), dim3(256), 0, st, P, wl, dl, lam, ds, dz, Sc, kbz, wbz,
+                           fused ? (const double*)partR2 : (const double*)nullptr, ns1);
         if (P.big) hipLaunchKernelGGL(k_big_corr_rhs, lane_grid(dim3(1), nlanes), dim3(1024), 0, st, P, wbb, lam, ds, dz, Sc, kbz, scratch, corr_cones, corr_ddm);
     }
     // corrector tail: the candidate (predictor-corrector + corrector solution) gets its own direction and step (mode 3: own dtau /
     // dkappa slots), k_scal_step picks the longer step by CORR_ACCEPT and moves tau, kappa, k_update_pick moves x, s, z along the
     // direction picked.  Every lane decides for itself.
     void stage_corr_tail(bool two) {
-        hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
-        const int ndC = dots(kx, kz, 3, two);
+        const bool fused = sw.fuse && !two;          // (k_corr_add inside k_dots_r -- without a big cone, whose rows have no thread there --, the pick inside k_update_pick)
+        const bool add_in_dots = fused && !P.big;
+        if (!add_in_dots) hipLaunchKernelGGL(k_corr_add, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, dxc, dzc, gdxc, kx, kz, kg);
+        const int ndC = dots(kx, kz, 3, two, add_in_dots);
         const int nsC = dir_post(kx, kz, kg, kds, kdz, 3, ndC, two);
-        scal_step(3, nsC, true, two);
-        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z);
+        if (!fused) scal_step(3, nsC, true, two);
+        hipLaunchKernelGGL(k_update_pick, lane_grid(dim3(unknown_blocks()), nlanes), dim3(256), 0, st, P, Sc, dx2, dxc, kx, x, ds, dz, kds, kdz, s, z,
+                           fused ? (const double*)partR2 : (const double*)nullptr, nsC);
     }
     // The body of an iteration: the head (unless it went out ahead of the verdicts), then the cone stages with the KKT solves in between
     void launch_iteration(std::vector<LaneHost>& LH, const SolveOpts& o, bool head_out, int nsweep, bool use_corr) {
