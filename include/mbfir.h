@@ -976,6 +976,27 @@ int mbfir_test_chol(mbfir_ctx* ctx, int n, const double* H, double* out_l, doubl
  *  count, otherwise the value of MBFIR_CHOL_SPLIT to use. */
 int mbfir_test_chol_lanes(mbfir_ctx* ctx, int n, int nlanes, int form, const int* mask, const double* H, double* out_l, double* out_m);
 int mbfir_test_specfact(mbfir_ctx* ctx, int n, const double* x, double* h_re, double* h_im);
+/*  mbfir_test_specfact_stages (test hook): the tap extraction's kernels through the instantiations that also store what the chain
+ *  overwrites in place -- the same arithmetic, launched as production launches it.
+ *    kind 0: k_specfact on nlanes (1 .. 64) inputs in ONE launch with a lane stride, as a lock-step unit of one order is factorised;
+ *            n = the order (1 .. 4096), in_re = nlanes blocks of 2n - 1 reals (the designers' x), in_im ignored.
+ *    kind 1: k_fmp on one filter; n = its odd length (<= 2047), in_re / in_im its taps (in_im may be NULL), nlanes = 1.
+ *  Everything lives in one device arena of nlanes lanes of `stride` doubles, filled with `fill` before the inputs go in and copied
+ *  back whole into raw (nlanes * stride doubles).  A lane holds eight blocks, each followed by at least `guard` doubles that nothing
+ *  may write (rounded up so that every block starts on 16 bytes); `extra` more doubles end the lane.  Complex blocks are interleaved
+ *  (re, im) and in the kernel's own storage order, lp = 8 * 2^ceil(log2(l)) the transform length:
+ *      0 in     2n - 1 reals (kind 0) / n complex (kind 1)
+ *      1 work   3 lp complex: B0, B1, B2 as the kernel leaves them
+ *      2 h      the taps: n complex (kind 0), (n + 1) / 2 complex (kind 1)
+ *      3 hpf    lp complex: B0 after the first transform (bin k of the transform of fftshift(hp))
+ *      4 xl     lp reals: log(sqrt(|hpf - lift|)), entry i from bin (i + lp / 2) mod lp
+ *      5 xlfp   lp complex: the transform of xl after the window (x 2 on 1 .. lp/2 - 1, 0 above lp/2)
+ *      6 a      lp complex: exp(ifft(xlfp))
+ *      7 lift   1 real: what is subtracted from real(hpf) (kind 1: 1.000001 min real(hpf); kind 0: 0)
+ *  layout (18 longs, always written): lp, stride, the eight block offsets within a lane, the eight block sizes (all in doubles).
+ *  With raw NULL only layout is written and no device work is done, so a caller can size raw.  Bad arguments: MBFIR_E_ARG. */
+int mbfir_test_specfact_stages(mbfir_ctx* ctx, int kind, int n, int nlanes, const double* in_re, const double* in_im, int guard,
+                               double fill, long extra, long* layout, double* raw);
 /*  mbfir_test_unit_ops: the operators of ONE lock-step unit -- the njobs designs of `jobs` as its lanes, a single design as a unit of
  *  one -- at an iterate the caller chooses.  The unit is set up by the stages a solve runs (switches read from the environment, lanes,
  *  plan, arena, masks, seed tables) and scaled as an iteration's head scales it; every product then goes through the solve's own

@@ -221,6 +221,7 @@ SYMBOLS = {
     "mbfir_test_chol": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "mbfir_test_chol_lanes": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, _dp, _dp]),
     "mbfir_test_specfact": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
+    "mbfir_test_specfact_stages": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_double, C.c_long, _lp, _dp]),
     "mbfir_test_unit_ops": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int,
                                       _dp, _dp, _dp, _dp, _dp, _ip, _dp, _dp, _dp, _dp, _lp, _dp]),
     "mbfir_test_unit_cone": (C.c_int, [C.c_void_p, C.POINTER(Job), C.c_int, C.POINTER(Opts), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -2870,6 +2871,49 @@ def test_specfact(x, n, ctx=None):
     hre, him = np.zeros(n), np.zeros(n)
     _check(ctx, load_library().mbfir_test_specfact(ctx._h, int(n), _ptr(x), _ptr(hre), _ptr(him)))
     return hre + 1j * him
+
+
+SPECFACT_BLOCKS = ("in", "work", "h", "hpf", "xl", "xlfp", "a", "lift")
+
+
+def test_specfact_stages(inp, n=None, *, kind=0, guard=0, fill=0.0, extra=0, ctx=None):
+    """Test hook (mbfir_test_specfact_stages): k_specfact (kind 0: inp = nlanes x (2n - 1) reals, one launch with a lane stride) or
+    k_fmp (kind 1: inp = an odd number of real or complex taps) through the instantiation that also stores the stages.  Every block
+    of the device arena is followed by `guard` doubles of `fill`, `extra` more end each lane.  Returns a dict: lp, lift (per lane),
+    st_hpf, st_xl, st_xlfp, st_a, st_h (nlanes x ..., the kernel's own storage order), and to see that nothing outside a block
+    changed: raw (nlanes x stride, the arena as the device left it), offsets and sizes (per block name, in doubles)."""
+    ctx = ctx or get_context()
+    if kind == 0:
+        x = np.ascontiguousarray(np.atleast_2d(np.asarray(inp, dtype=np.float64)))
+        nlanes = x.shape[0]
+        n = (x.shape[1] + 1) // 2 if n is None else int(n)
+        if x.ndim != 2 or x.shape[1] != 2 * n - 1:
+            raise ValueError("test_specfact_stages: kind 0 takes nlanes x (2n - 1) reals")
+        re, im, ntaps = x.ravel(), None, n
+    else:
+        h = np.asarray(inp).ravel()
+        re = np.ascontiguousarray(h.real, dtype=np.float64)
+        im = np.ascontiguousarray(h.imag, dtype=np.float64) if np.iscomplexobj(h) else None
+        nlanes, n = 1, len(re)
+        ntaps = (n + 1) // 2
+    lay = np.zeros(18, dtype=np.int64)
+    call = lambda raw: load_library().mbfir_test_specfact_stages(                    # noqa: E731
+        ctx._h, int(kind), int(n), int(nlanes), _ptr(re), _ptr(im) if im is not None else None, int(guard), float(fill), int(extra),
+        lay.ctypes.data_as(_lp), raw)
+    rc = call(None)
+    if rc == 0:
+        raw = np.zeros(nlanes * int(lay[1]), dtype=np.float64)
+        rc = call(_ptr(raw))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    lp = int(lay[0])
+    raw = raw.reshape(nlanes, int(lay[1]))
+    off = dict(zip(SPECFACT_BLOCKS, (int(v) for v in lay[2:10])))
+    size = dict(zip(SPECFACT_BLOCKS, (int(v) for v in lay[10:18])))
+    cplx = lambda k, m: raw[:, off[k]:off[k] + 2 * m:2] + 1j * raw[:, off[k] + 1:off[k] + 2 * m:2]   # noqa: E731
+    return dict(lp=lp, lift=raw[:, off["lift"]].copy(), st_hpf=cplx("hpf", lp), st_xl=raw[:, off["xl"]:off["xl"] + lp].copy(),
+                st_xlfp=cplx("xlfp", lp), st_a=cplx("a", lp), st_h=cplx("h", ntaps), raw=raw, offsets=off, sizes=size)
 
 
 def time_kernels(n=1024, m=16394, nt=1023, reps=20, ctx=None):

@@ -961,6 +961,18 @@ int mbfir_fmp(mbfir_ctx* ctx, int l, const double* h_re, const double* h_im, dou
     }
     MBFIR_TRY(ctx, fmp_run(ctx->device, ctx->solver->stream(), l, h_re, h_im, out_re, out_im));
 }
+int mbfir_test_specfact_stages(mbfir_ctx* ctx, int kind, int n, int nlanes, const double* in_re, const double* in_im, int guard,
+                               double fill, long extra, long* layout, double* raw) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_specfact_stages: " + why; return MBFIR_E_ARG; };
+    if (kind != 0 && kind != 1) return bad("kind must be 0 (k_specfact) or 1 (k_fmp)");
+    if (kind == 0 && (n < 1 || n > 4096)) return bad("n must lie in [1, 4096] (lp <= 65536)");
+    if (kind == 1 && (n < 1 || n > 2047 || (n & 1) == 0)) return bad("filter length must be odd and at most 2047");
+    if (nlanes < 1 || nlanes > 64 || (kind == 1 && nlanes != 1)) return bad("nlanes must lie in [1, 64], and be 1 for k_fmp");
+    if (guard < 0 || guard > 65536 || extra < 0 || extra > 1048576) return bad("guard must lie in [0, 65536], extra in [0, 1048576]");
+    if (!layout || (raw && !in_re)) return bad("layout is required, and the input when raw is given");
+    MBFIR_TRY(ctx, specfact_stages_run(ctx->device, ctx->solver->stream(), kind, n, nlanes, in_re, in_im, guard, fill, extra, layout, raw));
+}
 int mbfir_test_mfma_peak(mbfir_ctx* ctx, double* tf_mfma, double* tf_valu) {
     MBFIR_TRY(ctx, ctx->solver->test_mfma_peak(tf_mfma, tf_valu));
 }

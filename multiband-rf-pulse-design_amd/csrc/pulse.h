@@ -360,5 +360,9 @@ void remez_run(int device, void* stream, int njobs, const RemezJobHost* jobs, in
 
 // fmp.m (specfact.hip k_fmp): odd l <= 2047 taps of h (h_im may be null) -> (l + 1) / 2 minimum-phase taps.
 void fmp_run(int device, void* stream, int l, const double* h_re, const double* h_im, double* out_re, double* out_im);
+// mbfir_test_specfact_stages (specfact.hip): k_specfact (kind 0, n = order) or k_fmp (kind 1, n = filter length) through the
+// instantiation that stores its stages, on one guarded device arena.  layout (18 longs) is always written; raw null: nothing else.
+void specfact_stages_run(int device, void* stream, int kind, int n, int nlanes, const double* in_re, const double* in_im, int guard,
+                         double fill, long extra, long* layout, double* raw);
 
 }  // namespace mbfir
