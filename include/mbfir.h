@@ -523,8 +523,8 @@ int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const d
  * before every eighth) and backwards, which leaves the cotangents of the 24 doubles of (A, B, A_e, B_e) per (scale, distinct gain,
  * point) in a device workspace; the period's samples swept forwards and backwards once per (pulse, scale, distinct gain, 64
  * points), the four columns of [A | B] on the four wavefronts of a workgroup; and the fold over chunks and combinations.  No
- * atomics: a pulse's gradient bits depend only on the pulse, its grids, its train, its cotangents and the scale list.  The gains,
- * the phases, gr, tp, t1, t2, df, the positions and meq are not differentiated.
+ * atomics: a pulse's gradient bits depend only on the pulse, its grids, its train, its cotangents and the scale list.  gr, tp,
+ * t1, t2, df, the positions and meq are not differentiated (the gains and the phases: mbfir_bloch_train_vjp_sched_batch).
  * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with
  * its reason in mbfir_last_error and no device work done: a cotangent triple or gmx / gmy / gmz only partly given; both cotangent
  * triples NULL; g_re or g_im NULL; a partial, checkpoint, workspace or workgroup count that overflows.  A refused call leaves the
@@ -538,6 +538,38 @@ int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
                                 const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
                                 const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
                                 const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+/* ---- Adjoint of the pulse train with respect to its schedule: the gain and the RF phase of every repetition ------------------------
+ * For the loss of mbfir_bloch_train_vjp_batch, L = sum_k <ce_k, echo_k> + <cf, m_N>, the gradients dL/dgains[k] and dL/dphi_k of
+ * every repetition k (repetition k plays gains[k] exp(i phi_k) b1), both summed over the scales and the points, and dL/dm0.  It
+ * takes mbfir_bloch_train_vjp_batch's arguments through cfz, then
+ *   ggain / gphi: one entry per repetition of every pulse, laid out as cosphi; either NULL = not wanted, not both.  The gradient
+ *     is per repetition: repetitions that share a gain value share their planes, and each still has its own dL/dgains[k].
+ *     dL/dphi_k is the derivative with respect to the angle phi_k of which the table holds (cos phi_k, sin phi_k), the two moved
+ *     together along the circle; it is not a derivative with respect to the table's entries.
+ *   gmx / gmy / gmz: dL/dm0 as mbfir_bloch_train_vjp_batch returns it, with its bits; all three NULL = not wanted.
+ * A gain of exactly 0 is an ordinary repetition with a finite derivative: d amplitude / d gain is the scale, and nothing is divided
+ * by a gain.  One upload, three launches and the fold, one download: the forward call's propagator launch; the tangent of the
+ * period along its own b1 once per (pulse, scale, distinct gain, 64 points), which leaves the derivative of the 24 doubles of (A, B,
+ * A_e, B_e) in the gain in a device workspace (skipped when ggain is NULL); the repetitions walked forwards (a checkpoint before
+ * every eighth) and backwards, which contracts the multiplier with those derivatives and with the generator of the z-rotations
+ * and leaves one partial per (scale, 256 points, repetition); and the fold over chunks and scales.  There is no reverse sweep
+ * over the period's samples.  No atomics: a pulse's gradient bits depend only on the pulse, its grids, its train, its cotangents and
+ * the scale list, and not on which of ggain, gphi and gm* are wanted.  b1, gr, tp, t1, t2, df, the positions and meq are not
+ * differentiated here.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with
+ * its reason in mbfir_last_error and no device work done: both ggain and gphi NULL; a cotangent triple or gmx / gmy / gmz only
+ * partly given; both cotangent triples NULL; a partial, checkpoint, workspace or workgroup count that overflows.  A refused call
+ * leaves the context usable.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_vjp_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, const double* cex, const double* cey, const double* cez,
+                                      const double* cfx, const double* cfy, const double* cfz, double* ggain, double* gphi,
+                                      double* gmx, double* gmy, double* gmz);
 /* ---- Tangent of the pulse train with respect to b1 and the initial magnetisation ----------------------------------------------------
  * The Jacobian-vector product of mbfir_bloch_train_batch's echoes and final state: d/de of both at (b1 + e v, m0 + e dm0), e = 0,
  * for ndir directions per pulse (repetition k plays gains[k] exp(i phi_k) (b1 + e v): the chain rule through that product is

@@ -155,6 +155,9 @@ SYMBOLS = {
     "mbfir_bloch_train_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
+    "mbfir_bloch_train_vjp_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
+                                                    _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                   [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
     "mbfir_bloch_train_jvp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 17),
@@ -1862,8 +1865,8 @@ def bloch_train_vjp_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np
     grad_m0, a list of (grad_b1, (gmx, gmy, gmz)), the second being dL/dm0 of every (scale, frequency, position), each of shape
     (S, nf, npos) (one m0 serves every scale: its gradient is their sum over the scales).  One upload, four launches, one
     download; the cost is a small multiple of the forward train's.  Deterministic: a pulse's gradient bits depend only on the
-    pulse, its grids, its train, its cotangents and the scales, and dL/dm0 has the same bits for any m0 and any meq.  The gains,
-    the phases, gr, tp, t1, t2, df, dp and meq are not differentiated."""
+    pulse, its grids, its train, its cotangents and the scales, and dL/dm0 has the same bits for any m0 and any meq.  gr, tp,
+    t1, t2, df, dp and meq are not differentiated (the gains and the phases: bloch_train_vjp_sched_batch)."""
     who = "bloch_train_vjp_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr, ooff, eoff = Tn.A, Tn.ntr, Tn.ooff, Tn.eoff
@@ -1890,6 +1893,53 @@ def bloch_train_vjp_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np
     if not grad_m0:
         return res
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
+
+
+def bloch_train_vjp_sched_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,),
+                                m0=None, meq=1.0, demod=False, grad_gains=True, grad_phases=True, grad_m0=False, ctx=None):
+    """The adjoint of bloch_train_batch with respect to its schedule, the gain and the RF phase of every repetition
+    (mbfir_bloch_train_vjp_sched_batch): every argument through demod as for bloch_train_vjp_batch, the loss
+    being L = sum_k <cot_k, echo_k> + <cot_final, m_N>.  Returns, per pulse, (grad_gains, grad_phases): dL/dgains[k] and
+    dL/dphases[k] (per radian) of every repetition, float64 of shape (ntr,), summed over the scales and the points; None in the
+    place of one that was not asked for (not both).  With grad_m0 a third item (gmx, gmy, gmz), dL/dm0 of shape (S, nf, npos) with
+    bloch_train_vjp_batch's bits.  The gradients are per repetition whatever form the schedule was given in: repetitions that
+    share a gain value still have one entry each, and a scalar `gains` (every repetition at g) or a scalar `phases` increment D
+    (phi_k = k D) yields ntr entries g[k], through which the scalar's own derivative follows by the chain rule, dL/dg = sum_k g[k]
+    and dL/dD = sum_k k g[k].  A gain of exactly 0 has a finite derivative.  One upload, three launches and a fold (the period is
+    swept once more per (scale, distinct gain) for the gains, not at all for the phases), one download: cheaper than
+    bloch_train_vjp_batch, which sweeps the period backwards as well.  Deterministic: a pulse's bits depend only on the pulse, its
+    grids, its train, its cotangents and the scales, not on what else was asked for.  b1, gr, tp, t1, t2, df, dp and meq are not
+    differentiated here."""
+    who = "bloch_train_vjp_sched_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if cot is None and cot_final is None:
+        raise ValueError("%s: neither echo cotangents nor final cotangents are given" % who)
+    if not grad_gains and not grad_phases:
+        raise ValueError("%s: neither the gradient in the gains nor the gradient in the phases is wanted" % who)
+    ce = _train_cotangents(who, "echo", cot, A, [(n,) for n in ntr])
+    cf = _train_cotangents(who, "final", cot_final, A, [()] * P)
+    roff = _offsets(ntr)
+    nul = C.cast(None, _dp)
+    m0p = _bloch_m0(A, m0)
+    gg = np.zeros(int(roff[-1])) if grad_gains else None
+    gp = np.zeros(int(roff[-1])) if grad_phases else None
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_vjp_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p],
+                                                          *([nul] * 3 if ce is None else [_ptr(v) for v in ce]),
+                                                          *([nul] * 3 if cf is None else [_ptr(v) for v in cf]),
+                                                          nul if gg is None else _ptr(gg), nul if gp is None else _ptr(gp),
+                                                          *[_plane(v) for v in gm])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    cut = lambda v, q: None if v is None else v[roff[q]:roff[q + 1]].copy()
+    res = [(cut(gg, q), cut(gp, q)) for q in range(P)]
+    if not grad_m0:
+        return res
+    return [res[q] + (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm),) for q in range(P)]
 
 
 def _train_tangents_m0(who, tangents_m0, A, K):

@@ -1598,6 +1598,56 @@ int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
                                              cfy, cfz, g_re, g_im, gmx, gmy, gmz));
 }
 
+// The train's adjoint in its schedule (blochtrainsched.hip) keeps one double2 partial per (scale, chunk of 256 points,
+// repetition), 3 x 256 checkpoint doubles per (scale, chunk of 256 points, group of 8 repetitions) and the propagators' planes
+// twice (bloch_prop_check has bounded them once), and launches one workgroup per (combination, chunk of 64 points): false when a
+// count overflows, exceeds 2^56 or, for the workgroups, 2^31 - 1.
+static bool bloch_train_sched_fits(int npulse, int nscale, const int* ntr, const long* ncomb, const long* npoint) {
+    long part = 0, ckr = 0, nwg = 0, ws = 0;
+    for (int p = 0; p < npulse; ++p) {
+        const long nch = (npoint[p] + 255) / 256, nch64 = (npoint[p] + 63) / 64;
+        long w, a, c, e;
+        if (__builtin_mul_overflow(ncomb[p], nch64, &w) || __builtin_add_overflow(nwg, w, &nwg) ||
+            __builtin_mul_overflow(nch * nscale, (long)ntr[p], &a) || __builtin_add_overflow(part, a, &part) ||
+            __builtin_mul_overflow(nch * nscale, ((long)ntr[p] + 7) / 8 * 768, &c) || __builtin_add_overflow(ckr, c, &ckr) ||
+            __builtin_mul_overflow(npoint[p], ncomb[p] * 48, &e) || __builtin_add_overflow(ws, e, &ws))
+            return false;
+    }
+    return part <= (1L << 56) && ckr <= (1L << 56) && ws <= (1L << 56) && nwg <= 2147483647L;
+}
+
+int mbfir_bloch_train_vjp_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, const double* cex, const double* cey, const double* cez,
+                                      const double* cfx, const double* cfy, const double* cfz, double* ggain, double* gphi,
+                                      double* gmx, double* gmy, double* gmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_vjp_sched_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_vjp_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if ((cex || cey || cez) && !(cex && cey && cez)) return bad("the echo cotangents are given together or not at all");
+    if ((cfx || cfy || cfz) && !(cfx && cfy && cfz)) return bad("the final cotangents are given together or not at all");
+    if (!cex && !cfx) return bad("neither echo cotangents nor final cotangents are given");
+    if (!ggain && !gphi) return bad("neither the gradient in the gains nor the gradient in the phases is wanted");
+    if ((gmx || gmy || gmz) && !(gmx && gmy && gmz)) return bad("gmx, gmy and gmz are given together or not at all");
+    if (!bloch_train_sched_fits(npulse, nscale, ntr, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_train_vjp_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                   tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
+                                                   ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, cex,
+                                                   cey, cez, cfx, cfy, cfz, ggain, gphi, gmx, gmy, gmz));
+}
+
 // The train's tangent (blochtrainjvp.hip) reads ndir directions of the samples, writes ndir tangents of the echoes and of
 // the final state, keeps ndir x 24 doubles per (combination, point) and launches one workgroup per (combination, chunk of 64 points,
 // group of bloch_train_jvp_group(0) directions) and per (scale, chunk of 256 points, group of bloch_train_jvp_group(1)): false when

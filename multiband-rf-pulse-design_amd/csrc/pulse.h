@@ -151,6 +151,21 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
                                const double* m0x, const double* m0y, const double* m0z, const double* cex, const double* cey,
                                const double* cez, const double* cfx, const double* cfy, const double* cfz, double* g_re, double* g_im,
                                double* gmx, double* gmy, double* gmz);
+// Adjoint of bloch_train_batch_run with respect to the gain and the RF phase of every repetition (blochtrainsched.hip
+// k_bloch_train_prop_dgain, k_bloch_train_run_sched, k_bloch_train_sched_fold after blochtrain.hip's k_bloch_train_prop):
+// bloch_train_vjp_batch_run's inputs; ggain / gphi: one entry per repetition, laid out as cosphi (either null: not wanted, not
+// both); gm*: dL / d m0 with bloch_train_vjp_batch_run's bits (all null: not downloaded).  One upload, three launches and the fold
+// (two when ggain is null), one download.
+void bloch_train_vjp_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                     const double* m0z, const double* cex, const double* cey, const double* cez, const double* cfx,
+                                     const double* cfy, const double* cfz, double* ggain, double* gphi, double* gmx, double* gmy,
+                                     double* gmz);
 // Tangent of bloch_train_batch_run with respect to b1 and m0 (blochtrainjvp.hip k_bloch_train_prop_jvp, k_bloch_train_run_jvp after
 // blochtrain.hip's k_bloch_train_prop): the forward call's inputs; ndir >= 1 directions per pulse, v and dm0* as
 // bloch_jvp_batch_run's; e* / f*: the forward call's outputs with its bits (either triple all null: not downloaded); de*: the

@@ -17,7 +17,9 @@ it returns the steady state of the period instead (bloch_batch mode 1), differen
 mbfir.bloch_ss_jvp_batch (section 8t) and, in reverse mode, in gr and df through mbfir.bloch_ss_vjp_gr_batch (section 8x).
 `bloch_train` runs mbfir.bloch_train_batch on one period (the echo-by-echo transient of a pulse train) and is differentiable in
 reverse mode in b1 and in m0, its backward being one mbfir.bloch_train_vjp_batch call (section 8z); with forward_mode=True it also
-has the forward-mode tangent in both, one mbfir.bloch_train_jvp_batch call with one direction (section 8aa).
+has the forward-mode tangent in both, one mbfir.bloch_train_jvp_batch call with one direction (section 8aa).  Its gains and phases
+may be float64 tensors of shape (ntr,) that require grad: the backward then has one mbfir.bloch_train_vjp_sched_batch call for the
+schedule's per-repetition gradients (section 8ad); a forward-mode tangent in the schedule raises NotImplementedError.
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -485,6 +487,75 @@ def _train_forward_function():
     return BlochTrainForward
 
 
+def _in_graph(v):
+    """Whether v is a tensor that autograd follows: one that requires grad, a forward-mode dual or a torch.func-wrapped tensor"""
+    if not hasattr(v, "detach"):
+        return False
+    import torch
+    return bool(v.requires_grad or torch._C._functorch.is_functorch_wrapped_tensor(v)
+                or torch.autograd.forward_ad.unpack_dual(v).tangent is not None)
+
+
+@functools.lru_cache(maxsize=None)
+def _train_sched_function():
+    """BlochTrain with the schedule in the graph: gains and phases (each a float64 tensor of shape (ntr,), or a constant) are inputs.
+    The backward is one mbfir.bloch_train_vjp_sched_batch call when either needs a gradient and the shipped
+    mbfir.bloch_train_vjp_batch call when b1 or m0 does.  kw: the train's other constants."""
+    import torch
+
+    import mbfir
+
+    def table(v, ntr, what):
+        if torch.is_tensor(v) and v.requires_grad and (v.dtype != torch.float64 or v.shape != (ntr,)):
+            raise ValueError("torchsim: %s that require grad must be a float64 tensor of shape (ntr,)" % what)
+        return _host(v, np.float64)
+
+    class BlochTrainSched(torch.autograd.Function):
+        @staticmethod
+        def forward(b1, m0, gains, phases, rest, df, dp, ntr, kw, final):
+            gh, ph = table(gains, ntr, "gains"), table(phases, ntr, "phases")
+            return _train_function().forward(b1, m0, rest, df, dp, ntr, kw + (("gains", gh), ("phases", ph)), final)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, m0, gains, phases, rest, df, dp, ntr, kw, final = inputs
+            kw = kw + (("gains", _host(gains, np.float64)), ("phases", _host(phases, np.float64)))
+            ctx.args = (_host(m0, np.float64), rest, df, dp, ntr, kw, final)
+            ctx.m0_like = (m0.shape, m0.device) if torch.is_tensor(m0) else None
+            ctx.sched_like = tuple(v.device if torch.is_tensor(v) else None for v in (gains, phases))
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch_train in the gains and the phases is not "
+                                      "implemented (reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, *cots):
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            want_b1, want_m0, want_g, want_p = ctx.needs_input_grad[:4]
+            cot = tuple(_host(c, np.float64) for c in cots)
+            args = ([(_host(b1, np.complex128),) + rest], df, dp, ntr, [cot[:3]])
+            kws = dict(kw, cot_final=[cot[3:]] if final else None, m0=None if m0h is None else tuple(m0h))
+            gb = gm = gg = gp = None
+            if want_g or want_p:
+                res, = mbfir.bloch_train_vjp_sched_batch(*args, grad_gains=want_g, grad_phases=want_p, **kws)
+                if want_g:
+                    gg = torch.from_numpy(np.ascontiguousarray(res[0])).to(ctx.sched_like[0])
+                if want_p:
+                    gp = torch.from_numpy(np.ascontiguousarray(res[1])).to(ctx.sched_like[1])
+            if want_b1 or want_m0:
+                res, = mbfir.bloch_train_vjp_batch(*args, grad_m0=want_m0, **kws)
+                grad, gm = res if want_m0 else (res, None)
+                gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if want_b1 else None
+                if want_m0:                                             # one m0 serves every scale: its gradient is their sum
+                    gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
+            return gb, gm, gg, gp, None, None, None, None, None, None
+
+    return BlochTrainSched
+
+
 def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
                 meq=1.0, demod=False, final=False, forward_mode=False):
     """The echoes (mx, my, mz) of mbfir.bloch_train_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, ntr, ...), each a float64 tensor
@@ -495,9 +566,18 @@ def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi
     t1, t2, df, dp, ntr, the phases, the gains, echo, the scales, meq, and an m0 given as (mx, my, mz), as an array of shape (3, nf,
     npos) or as None (equilibrium).  A forward-mode tangent raises NotImplementedError unless forward_mode is set: then
     torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as well, the tangent in b1 and in a tensor m0 being one
-    mbfir.bloch_train_jvp_batch call with one direction (section 8aa)."""
+    mbfir.bloch_train_jvp_batch call with one direction (section 8aa).  gains and phases may also be float64 tensors of shape
+    (ntr,) that require grad: the schedule is then differentiated in reverse mode, per repetition, by one
+    mbfir.bloch_train_vjp_sched_batch call (section 8ad), next to the call for b1 and m0 when those need gradients too; a
+    forward-mode tangent in the schedule raises NotImplementedError."""
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
+    if any(_in_graph(v) for v in (gains, phases)):
+        kw = (("echo", echo), ("scales", tuple(scales)), ("meq", float(meq)), ("demod", bool(demod)))
+        rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
+        out = _train_sched_function().apply(b1, m0, gains, phases, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw,
+                                            bool(final))
+        return (out[:3], out[3:]) if final else out
     kw =(("phases", _host(phases, np.float64)), ("gains", _host(gains, np.float64)), ("echo", echo), ("scales", tuple(scales)),
           ("meq", float(meq)), ("demod", bool(demod)))
     rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
