@@ -605,6 +605,40 @@ int mbfir_bloch_train_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
 /* mbfir_test_bloch_train_jvp_group (host only): the directions one workgroup of the call above carries, in the period's kernel
  * (which = 0) and in the repetitions' kernel (which != 0); compile-time constants. */
 int mbfir_test_bloch_train_jvp_group(int which);
+/* ---- Tangent of the pulse train with respect to its schedule: the gain and the RF phase of every repetition ------------------------
+ * The Jacobian-vector product of mbfir_bloch_train_batch's echoes and final state: d/de of both at (gains + e dgain, phi + e dphi,
+ * m0 + e dm0), e = 0, for ndir directions per pulse (repetition k plays gains[k] exp(i phi_k) b1).  It takes
+ * mbfir_bloch_train_jvp_batch's arguments through m0x / m0y / m0z and ndir, then
+ *   dgain / dphi: the directions of the gains and of the phases (per radian, of the angle phi_k of which the table holds the cosine
+ *     and the sine), direction k of pulse p at ndir roff[p] + k ntr_p + repetition; either NULL = that part does not move.  A
+ *     direction is per repetition: repetitions that share a gain value still move separately.
+ *   dm0x / dm0y / dm0z, ex .. fz, dex .. dfz: as mbfir_bloch_train_jvp_batch's.
+ * With the ntr unit directions of the gains followed by the ntr of the phases one call returns the whole Jacobian of the echoes in
+ * the schedule.  A gain of exactly 0 is an ordinary repetition: nothing is divided by a gain.  One upload, three launches (two
+ * when dgain is NULL), one download: the forward call's propagator launch; the tangent of the period along its own b1 once per
+ * (pulse, scale, distinct gain, 64 points), as mbfir_bloch_train_vjp_sched_batch runs it, whatever ndir is: the workspace is twice
+ * the forward call's; and the repetitions, per (scale, 256 points, group of mbfir_test_bloch_train_sched_jvp_group() directions).
+ * There is no sweep over the period's samples per direction.  No atomics and no reduction: a tangent's bits depend only on its
+ * pulse, scale, point, train and direction, not on ndir, on its place among the directions or on which of dgain, dphi and dm0 are
+ * given (a NULL part is a part of zeros).  b1, gr, tp, t1, t2, df, the positions and meq are not differentiated here.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with
+ * its reason in mbfir_last_error and no device work done: a triple only partly given; dgain, dphi and the dm0 triple all NULL; both
+ * tangent triples NULL; ndir < 1; ndir times the repetitions or the echoes, the workspace, or a workgroup count, that overflows.  A
+ * refused call leaves the context usable.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_jvp_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, int ndir, const double* dgain, const double* dphi,
+                                      const double* dm0x, const double* dm0y, const double* dm0z, double* ex, double* ey, double* ez,
+                                      double* fx, double* fy, double* fz, double* dex, double* dey, double* dez, double* dfx,
+                                      double* dfy, double* dfz);
+/* mbfir_test_bloch_train_sched_jvp_group (host only): the directions one workgroup of the call above carries; a compile-time
+ * constant. */
+int mbfir_test_bloch_train_sched_jvp_group(void);
 
 /* ---- Fused least-squares and Gauss-Newton products of the pulse train -------------------------------------------------------------
  * For the loss, per pulse,

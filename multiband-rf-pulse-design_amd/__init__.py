@@ -162,6 +162,11 @@ SYMBOLS = {
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 17),
     "mbfir_test_bloch_train_jvp_group": (C.c_int, [C.c_int]),
+    "mbfir_bloch_train_jvp_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
+                                                    _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                   [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] +
+                                                   [_dp] * 17),
+    "mbfir_test_bloch_train_sched_jvp_group": (C.c_int, []),
     "mbfir_bloch_train_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 19),
@@ -2013,6 +2018,116 @@ def bloch_train_jvp_batch(pulses, df, dp, ntr, tangents, *, tangents_m0=None, ph
     return res
 
 
+def _train_tangents_sched(who, what, v, ntr):
+    """tangents_gains / tangents_phases: per pulse a float64 direction of shape (ntr,) or (K, ntr) -> (K, keep, a list of (K, ntr)
+    arrays); keep: whether the result has the K axis"""
+    v = list(v)
+    if len(v) != len(ntr):
+        raise ValueError("%s: %d %s tangents for %d pulses" % (who, len(v), what, len(ntr)))
+    out, K, keep = [], None, False
+    for q, (d, n) in enumerate(zip(v, ntr)):
+        d = np.asarray(d)
+        if np.iscomplexobj(d):
+            raise ValueError("%s: the %s tangent of pulse %d is complex; a schedule's direction is real" % (who, what, q))
+        d = np.asarray(d, dtype=np.float64)
+        if d.ndim not in (1, 2) or d.shape[-1] != n:
+            raise ValueError("%s: the %s tangent of pulse %d has shape %s, not (%d,) or (K, %d)" % (who, what, q, d.shape, n, n))
+        if q == 0:
+            keep, K = d.ndim == 2, d.shape[0] if d.ndim == 2 else 1
+        elif (d.ndim == 2) != keep or (keep and d.shape[0] != K):
+            raise ValueError("%s: the %s tangent of pulse %d has shape %s; every pulse takes the same K" % (who, what, q, d.shape))
+        if K < 1:
+            raise ValueError("%s: no directions" % who)
+        out.append(d.reshape(K, n))
+    return K, keep, out
+
+
+def bloch_train_jvp_sched_batch(pulses, df, dp, ntr, *, tangents_gains=None, tangents_phases=None, tangents_m0=None, phases=np.pi,
+                                gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, echoes=True, final=False,
+                                primal=False, ctx=None):
+    """The tangent of bloch_train_batch with respect to its schedule, the gain and the RF phase of every repetition, and the initial
+    magnetisation (mbfir_bloch_train_jvp_sched_batch): pulses, df, dp, ntr, phases, gains, echo, scales, m0, meq
+    and demod as for bloch_train_batch.  tangents_gains / tangents_phases: None (that part does not move) or per pulse a float64
+    direction of shape (ntr,), or K of them of shape (K, ntr), the same K for every pulse and for both; the phases' direction is per
+    radian.  A direction is per repetition whatever form the schedule was given in: for a scalar `gains` g pass np.ones(ntr), for a
+    scalar `phases` increment D pass np.arange(ntr).  tangents_m0: as bloch_train_jvp_batch's.  Not all three None.  Returns what
+    bloch_train_jvp_batch returns, with the same shapes and the same echoes / final / primal rules.  With the 2 ntr unit directions
+    the result is the whole Jacobian (bloch_train_jacobian_sched_batch).  A gain of exactly 0 is an ordinary case.  One upload, three
+    launches (two without tangents_gains), one download: the period is swept once more per (scale, distinct gain) whatever K is,
+    and a direction costs two 3 x 3 products per repetition and point.  Real-linear in the direction; a tangent's bits depend only
+    on its pulse, scale, point, train and direction, not on K, on its place among the directions or on which parts are None.  b1,
+    gr, tp, t1, t2, df, dp and meq are not differentiated here."""
+    who = "bloch_train_jvp_sched_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff, eoff = Tn.A, Tn.ntr, Tn.ooff, Tn.eoff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if not echoes and not final:
+        raise ValueError("%s: echoes=False requires final=True: neither the tangent echoes nor the final tangents are wanted" % who)
+    if tangents_gains is None and tangents_phases is None and tangents_m0 is None:
+        raise ValueError("%s: no direction is given: tangents_gains, tangents_phases and tangents_m0 are all None" % who)
+    K, keep, parts = None, False, []
+    for what, v in (("gains", tangents_gains), ("phases", tangents_phases)):
+        if v is None:
+            parts.append(None)
+            continue
+        k, kp, d = _train_tangents_sched(who, what, v, ntr)
+        if K is not None and (k, kp) != (K, keep):
+            raise ValueError("%s: %d directions of the phases for %d of the gains" % (who, k, K))
+        K, keep = k, kp
+        parts.append(_vec(np.concatenate([x.ravel() for x in d])))
+    if K is None:                                                                # m0 alone: K from its leading axis
+        lead = np.asarray(list(tangents_m0)[0][0]) if len(list(tangents_m0)) else np.zeros(())
+        keep = lead.ndim == 3
+        K = lead.shape[0] if keep else 1
+    nul = C.cast(None, _dp)
+    dm0 = [nul] * 3 if tangents_m0 is None else _train_tangents_m0(who, tangents_m0, A, K)
+    m0p = _bloch_m0(A, m0)
+    E, O = int(eoff[-1]), int(ooff[-1])
+    pe = [np.zeros(E) for _ in range(3)] if primal and echoes else [nul] * 3
+    pf = [np.zeros(O) for _ in range(3)] if primal and final else [nul] * 3
+    te = [np.zeros(K * E) for _ in range(3)] if echoes else [nul] * 3
+    tf = [np.zeros(K * O) for _ in range(3)] if final else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_jvp_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], K,
+                                                          *[nul if v is None else _ptr(v) for v in parts], *[_plane(v) for v in dm0],
+                                                          *[_plane(v) for v in pe], *[_plane(v) for v in pf],
+                                                          *[_plane(v) for v in te], *[_plane(v) for v in tf])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+
+    def pick(ev, fv, k, lead, q):
+        """The echo and final planes of pulse q, k directions in front with the axes `lead` -> what the flags ask for"""
+        e = tuple(v[k * eoff[q]:k * eoff[q + 1]].reshape(lead + (S, ntr[q], nf[q], npos[q])) for v in ev) if echoes else None
+        f = tuple(v[k * ooff[q]:k * ooff[q + 1]].reshape(lead + (S, nf[q], npos[q])) for v in fv) if final else None
+        return (e, f) if echoes and final else e if echoes else f
+    res = []
+    for q in range(P):
+        tan = pick(te, tf, K, (K,) if keep else (), q)
+        res.append((pick(pe, pf, 1, (), q), tan) if primal else tan)
+    return res
+
+
+def bloch_train_jacobian_sched_batch(pulses, df, dp, ntr, **kw):
+    """The whole Jacobian of bloch_train_batch in its schedule: one bloch_train_jvp_sched_batch call with the 2 ntr unit directions,
+    the ntr of the gains first, then the ntr of the phases (per radian).  The pulses of a call share ntr (an int).  Keywords as
+    bloch_train_jvp_sched_batch's, without the tangents.  Returns what that call returns, the leading axis of length 2 ntr: row j <
+    ntr is d/dgains[j], row ntr + j is d/dphases[j]."""
+    who = "bloch_train_jacobian_sched_batch"
+    for k in ("tangents_gains", "tangents_phases", "tangents_m0"):
+        if k in kw:
+            raise ValueError("%s: %s is not an argument: the directions are the unit directions of the schedule" % (who, k))
+    P = len(list(pulses))
+    n = _train_ints(who, "ntr", ntr, P)
+    if P == 0 or any(e != n[0] for e in n):
+        raise ValueError("%s: the pulses of a call must share ntr" % who)
+    if n[0] < 1:
+        raise ValueError("%s: ntr of pulse 0 must be at least 1" % who)
+    eye, zero = np.eye(n[0]), np.zeros((n[0], n[0]))
+    return bloch_train_jvp_sched_batch(pulses, df, dp, ntr, tangents_gains=[np.concatenate([eye, zero])] * P,
+                                       tangents_phases=[np.concatenate([zero, eye])] * P, **kw)
+
+
 def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):
     """Loss and gradient of a weighted least-squares fit of bloch_batch's end point (mode 0), relaxation included, in one device
     call (mbfir_bloch_lsq_batch): pulses, df, dp, scales and m0 as for bloch_batch.  targets and weights: per
@@ -2860,6 +2975,11 @@ def bloch_train_jvp_group():
     the repetitions' kernel)."""
     lib = load_library()
     return int(lib.mbfir_test_bloch_train_jvp_group(0)), int(lib.mbfir_test_bloch_train_jvp_group(1))
+
+
+def bloch_train_sched_jvp_group():
+    """The directions one workgroup of bloch_train_jvp_sched_batch carries (mbfir_test_bloch_train_sched_jvp_group)."""
+    return int(load_library().mbfir_test_bloch_train_sched_jvp_group())
 
 
 def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):

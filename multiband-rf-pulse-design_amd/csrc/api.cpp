@@ -1708,6 +1708,67 @@ int mbfir_bloch_train_jvp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
 
 int mbfir_test_bloch_train_jvp_group(int which) { return bloch_train_jvp_group(which); }
 
+// The train's tangent in its schedule (blochtrainschedjvp.hip) reads ndir directions of the repetitions, writes ndir
+// tangents of the echoes and of the final state, keeps the propagators' planes twice whatever ndir is (bloch_prop_check has bounded
+// them once) and launches one workgroup per (combination, chunk of 64 points) and per (scale, chunk of 256 points, group of
+// bloch_train_sched_jvp_group() directions): false when a count overflows, exceeds 2^56 or, for the workgroups, 2^31 - 1.
+static bool bloch_train_sched_jvp_fits(int npulse, int nscale, int ndir, const int* ntr, const long* roff, const long* ncomb,
+                                       const long* npoint) {
+    const long ngr = (ndir + (long)bloch_train_sched_jvp_group() - 1) / bloch_train_sched_jvp_group();
+    long ech = 0, fin = 0, wsp = 0, wgp = 0, wgr = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long e, f, w, a, b;
+        if (__builtin_mul_overflow(npoint[p] * nscale, (long)ntr[p], &e) || __builtin_mul_overflow(e, (long)ndir, &e) ||
+            __builtin_add_overflow(ech, e, &ech) || __builtin_mul_overflow(npoint[p] * nscale, (long)ndir, &f) ||
+            __builtin_add_overflow(fin, f, &fin) || __builtin_mul_overflow(npoint[p], ncomb[p] * 48, &w) ||
+            __builtin_add_overflow(wsp, w, &wsp) || __builtin_mul_overflow((npoint[p] + 63) / 64, ncomb[p], &a) ||
+            __builtin_add_overflow(wgp, a, &wgp) || __builtin_mul_overflow((npoint[p] + 255) / 256 * nscale, ngr, &b) ||
+            __builtin_add_overflow(wgr, b, &wgr))
+            return false;
+    }
+    return roff[npulse] <= (1L << 56) / ndir && ech <= (1L << 56) && fin <= (1L << 56) && wsp <= (1L << 56) &&
+           wgp <= 2147483647L && wgr <= 2147483647L;
+}
+
+int mbfir_bloch_train_jvp_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, int ndir, const double* dgain, const double* dphi,
+                                      const double* dm0x, const double* dm0y, const double* dm0z, double* ex, double* ey, double* ez,
+                                      double* fx, double* fy, double* fz, double* dex, double* dey, double* dez, double* dfx,
+                                      double* dfy, double* dfz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_jvp_sched_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_jvp_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if ((dm0x || dm0y || dm0z) && !(dm0x && dm0y && dm0z)) return bad("dm0x, dm0y and dm0z are given together or not at all");
+    if ((ex || ey || ez) && !(ex && ey && ez)) return bad("the echo planes are given together or not at all");
+    if ((fx || fy || fz) && !(fx && fy && fz)) return bad("the final planes are given together or not at all");
+    if ((dex || dey || dez) && !(dex && dey && dez)) return bad("the tangent echo planes are given together or not at all");
+    if ((dfx || dfy || dfz) && !(dfx && dfy && dfz)) return bad("the tangent final planes are given together or not at all");
+    if (!dgain && !dphi && !dm0x) return bad("no direction is given: dgain, dphi and the m0 directions are all null");
+    if (!dex && !dfx) return bad("neither the tangent echo planes nor the tangent final planes are wanted");
+    if (ndir < 1) return bad("ndir must be at least 1");
+    if (!bloch_train_sched_jvp_fits(npulse, nscale, ndir, ntr, roff, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_train_jvp_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                   tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
+                                                   ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ndir,
+                                                   dgain, dphi, dm0x, dm0y, dm0z, ex, ey, ez, fx, fy, fz, dex, dey, dez, dfx, dfy,
+                                                   dfz));
+}
+
+int mbfir_test_bloch_train_sched_jvp_group() { return bloch_train_sched_jvp_group(); }
+
 // The train's fused products (blochtraingn.hip).  What both calls check after bloch_train_check, in this order: ebcast,
 // the echo and final planes given whole or not at all and not both absent, the outputs, then (bloch_train_gn_check) the sizes, before
 // any plane is read: the adjoint's partials, checkpoints and workgroups (bloch_train_vjp_fits) and, per direction, the planes' tangents and

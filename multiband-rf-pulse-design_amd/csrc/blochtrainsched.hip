@@ -307,6 +307,14 @@ __global__ __launch_bounds__(256) void k_bloch_train_sched_fold(const double2* _
     out[V.r_off + k] = g;
 }
 
+void train_launch_prop_dgain(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, double* dws) {
+    Staging& S = Ts.B.S;
+    hipLaunchKernelGGL(k_bloch_train_prop_dgain, dim3((unsigned)nwg), dim3(256), 0, st, S.dev<const double>(Ts.B.o_in),
+                       S.dev<const double>(Ts.B.o_df), S.dev<const double>(Ts.B.o_pos), S.dev<const double>(Ts.o_amp),
+                       S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr),
+                       S.dev<const SimBlock>(o_qb), dws);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_train_vjp_sched_batch (arguments checked by api.cpp): the forward train's staging (bloch_stage,
 // train_stage) plus the cotangents, the partial and checkpoint descriptors and the tables of the period's tangent and of the fold;
@@ -377,11 +385,7 @@ void bloch_train_vjp_sched_batch_run(int device, void* stream, int npulse, const
     double* dws = want_g ? ws + W : nullptr;
     double* ck = ws + W + (want_g ? W : 0);
     train_launch_prop(Ts, st, ws);
-    if (want_g)
-        hipLaunchKernelGGL(k_bloch_train_prop_dgain, dim3((unsigned)nwg), dim3(256), 0, st, S.dev<const double>(B.o_in),
-                           S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(Ts.o_amp),
-                           S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr),
-                           S.dev<const SimBlock>(o_qb), dws);
+    if (want_g) train_launch_prop_dgain(Ts, st, o_qb, nwg, dws);
     const double* ced = cex ? S.dev<const double>(o_ce) : nullptr;
     const double* cfd = cfx ? S.dev<const double>(o_cf) : nullptr;
     hipLaunchKernelGGL(k_bloch_train_run_sched, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, S.dev<const double2>(Ts.o_rep),

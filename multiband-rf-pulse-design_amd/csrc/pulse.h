@@ -183,6 +183,22 @@ void bloch_train_jvp_batch_run(int device, void* stream, int npulse, const long*
                                const double* v_im, const double* dm0x, const double* dm0y, const double* dm0z, double* ex, double* ey,
                                double* ez, double* fx, double* fy, double* fz, double* dex, double* dey, double* dez, double* dfx,
                                double* dfy, double* dfz);
+// Tangent of bloch_train_batch_run with respect to the gain and the RF phase of every repetition and to m0 (blochtrainschedjvp.hip
+// k_bloch_train_run_sched_jvp after blochtrain.hip's k_bloch_train_prop and blochtrainsched.hip's k_bloch_train_prop_dgain; DESIGN
+// 8ae): bloch_train_jvp_batch_run's arguments with dgain / dphi in place of v: direction k of pulse p at ndir roff[p] + k ntr_p
+// (either null: that part does not move).  One upload, three launches (two when dgain is null), one download.
+// bloch_train_sched_jvp_group(): the directions one workgroup of the repetitions' kernel carries.
+int bloch_train_sched_jvp_group();
+void bloch_train_jvp_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                     const double* m0z, int ndir, const double* dgain, const double* dphi, const double* dm0x,
+                                     const double* dm0y, const double* dm0z, double* ex, double* ey, double* ez, double* fx, double* fy,
+                                     double* fz, double* dex, double* dey, double* dez, double* dfx, double* dfy, double* dfz);
 // Fused least-squares and Gauss-Newton products of bloch_train_batch_run (blochtraingn.hip k_bloch_train_run_lsq,
 // k_bloch_train_run_gn, k_bloch_train_gn_fold with the shipped k_bloch_train_prop, k_bloch_train_prop_jvp and k_bloch_train_prop_vjp;
 // DESIGN 8ab): the forward call's inputs; w / t: the echo weights and targets (w[0] null: no echo term), laid out as the echoes

@@ -718,6 +718,9 @@ void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream
 // workgroups.  train_launch_prop_jvp launches k_bloch_train_prop_jvp on it: v the packed directions' section, dws the tangent planes.
 size_t train_jvp_table(TrainStaged& Ts, int nscale, int ndir, long& nwg);
 void train_launch_prop_jvp(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, size_t o_v, int ndir, double* dws);
+// Launches k_bloch_train_prop_dgain (blochtrainsched.hip) on train_jvp_table's table of one direction: dws receives the planes'
+// tangents in the gain, laid out as the primal planes.  Shared by the schedule's adjoint and its tangent (blochtrainschedjvp.hip).
+void train_launch_prop_dgain(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, double* dws);
 
 // The sections the train's fused calls add after train_stage and train_vjp_stage (blochtraingn.hip train_gn_stage, t* null for gn):
 // the weights and targets, the repetitions' factors, the loss partials' offsets and the fold's table; nlp loss partials, ngf

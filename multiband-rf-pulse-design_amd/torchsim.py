@@ -19,7 +19,8 @@ mbfir.bloch_ss_jvp_batch (section 8t) and, in reverse mode, in gr and df through
 reverse mode in b1 and in m0, its backward being one mbfir.bloch_train_vjp_batch call (section 8z); with forward_mode=True it also
 has the forward-mode tangent in both, one mbfir.bloch_train_jvp_batch call with one direction (section 8aa).  Its gains and phases
 may be float64 tensors of shape (ntr,) that require grad: the backward then has one mbfir.bloch_train_vjp_sched_batch call for the
-schedule's per-repetition gradients (section 8ad); a forward-mode tangent in the schedule raises NotImplementedError.
+schedule's per-repetition gradients (section 8ad); with forward_mode=True the schedule has its forward-mode tangent as well, one
+mbfir.bloch_train_jvp_sched_batch call with one direction (section 8ae), and without it such a tangent raises NotImplementedError.
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -556,6 +557,56 @@ def _train_sched_function():
     return BlochTrainSched
 
 
+@functools.lru_cache(maxsize=None)
+def _train_sched_forward_function():
+    """BlochTrainSched with a forward-mode tangent: the same forward and backward, plus a jvp that is one
+    mbfir.bloch_train_jvp_sched_batch call with one direction for the tangents of the gains, the phases and m0
+    and, when b1 has a tangent too, one mbfir.bloch_train_jvp_batch call; the tangent is linear, so the two results are summed, m0's
+    tangent going to one of the calls only.  Each call is asked only for what has a tangent."""
+    import torch
+
+    import mbfir
+
+    base = _train_sched_function()
+
+    class BlochTrainSchedForward(base):
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            base.setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+            ctx.out_like = tuple((o.shape, o.device) for o in output)
+            ctx.set_materialize_grads(False)                            # an input without a tangent arrives as None, not as zeros
+
+        @staticmethod
+        def backward(ctx, *cots):                                       # the parent's, on the zeros it would have been handed
+            cots = tuple(torch.zeros(s, dtype=torch.float64, device=d) if c is None else c for c, (s, d) in zip(cots, ctx.out_like))
+            return base.backward(ctx, *cots)
+
+        @staticmethod
+        def jvp(ctx, v, vm0, vg, vp, *_):
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            pulses = [(_host(b1, np.complex128),) + rest]
+            kws = dict(kw, m0=None if m0h is None else tuple(m0h), final=final)
+            dm0 = None if vm0 is None else [tuple(_host(vm0, np.float64))]
+            sched = vg is not None or vp is not None or (dm0 is not None and v is None)
+            planes = None
+            if sched:
+                tan, = mbfir.bloch_train_jvp_sched_batch(pulses, df, dp, ntr,
+                                                         tangents_gains=None if vg is None else [_host(vg, np.float64)],
+                                                         tangents_phases=None if vp is None else [_host(vp, np.float64)],
+                                                         tangents_m0=dm0, **kws)
+                planes = tan[0] + tan[1] if final else tan
+            if v is not None:
+                tan, = mbfir.bloch_train_jvp_batch(pulses, df, dp, ntr, [_host(v, np.complex128)], tangents_m0=None if sched else dm0,
+                                                   **kws)
+                more = tan[0] + tan[1] if final else tan
+                planes = more if planes is None else tuple(a + b for a, b in zip(planes, more))
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in planes)
+
+    return BlochTrainSchedForward
+
+
 def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
                 meq=1.0, demod=False, final=False, forward_mode=False):
     """The echoes (mx, my, mz) of mbfir.bloch_train_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, ntr, ...), each a float64 tensor
@@ -568,15 +619,17 @@ def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi
     torch.func.jvp and torch.autograd.forward_ad dual tensors pass through as well, the tangent in b1 and in a tensor m0 being one
     mbfir.bloch_train_jvp_batch call with one direction (section 8aa).  gains and phases may also be float64 tensors of shape
     (ntr,) that require grad: the schedule is then differentiated in reverse mode, per repetition, by one
-    mbfir.bloch_train_vjp_sched_batch call (section 8ad), next to the call for b1 and m0 when those need gradients too; a
-    forward-mode tangent in the schedule raises NotImplementedError."""
+    mbfir.bloch_train_vjp_sched_batch call (section 8ad), next to the call for b1 and m0 when those need gradients too.  A
+    forward-mode tangent in the schedule raises NotImplementedError unless forward_mode is set: then the tangent in the gains, the
+    phases and m0 is one mbfir.bloch_train_jvp_sched_batch call with one direction (section 8ae), summed with one
+    mbfir.bloch_train_jvp_batch call when b1 has a tangent too; reverse mode keeps its calls and its bits."""
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
     if any(_in_graph(v) for v in (gains, phases)):
         kw = (("echo", echo), ("scales", tuple(scales)), ("meq", float(meq)), ("demod", bool(demod)))
         rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
-        out = _train_sched_function().apply(b1, m0, gains, phases, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw,
-                                            bool(final))
+        fn = _train_sched_forward_function() if forward_mode else _train_sched_function()
+        out = fn.apply(b1, m0, gains, phases, rest, _host(df, np.float64), _host(dp, np.float64), int(ntr), kw, bool(final))
         return (out[:3], out[3:]) if final else out
     kw =(("phases", _host(phases, np.float64)), ("gains", _host(gains, np.float64)), ("echo", echo), ("scales", tuple(scales)),
           ("meq", float(meq)), ("demod", bool(demod)))
