@@ -684,6 +684,54 @@ int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, con
                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
                                const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz, int ndir,
                                const double* v_re, const double* v_im, double* h_re, double* h_im);
+/* ---- Fused least-squares and Gauss-Newton products of the pulse train's schedule ----------------------------------------------------
+ * The loss L of the two calls above with the gain and the RF phase of every repetition as the variable (repetition k plays
+ * gains[k] exp(i phi_k) b1).  mbfir_bloch_train_lsq_sched_batch takes mbfir_bloch_train_lsq_batch's arguments through wfx .. tfz,
+ * then the outputs
+ *   loss (npulse); ggain / gphi: dL/dgains[k] and dL/dphi_k (per radian) of every repetition, laid out as cosphi (roff[npulse]
+ *     doubles each; either NULL = not wanted, not both), what mbfir_bloch_train_vjp_sched_batch returns at the cotangents
+ *     ce_k = rw_k w (echo_k - t), cf = wf (m_N - tf); gmx / gmy / gmz: dL/dm0 in the final planes' layout (all NULL = not wanted).
+ * mbfir_bloch_train_gn_sched_batch takes mbfir_bloch_train_gn_batch's arguments through wfx / wfy / wfz (weights without targets),
+ * then
+ *   ndir >= 1; dgain / dphi: the directions, laid out as mbfir_bloch_train_jvp_sched_batch takes them (direction k of pulse p at
+ *     ndir roff[p] + k ntr_p; either NULL = zeros, not both); hgain / hphi: the two halves of H v = J' W J v in the same layout
+ *     (either NULL = not wanted, not both), J the Jacobian of (echoes, final state) in (gains, phases), W the weights, rw included.
+ * Neither the echoes, their tangents nor their cotangents leave the device: what comes back is 2 ntr numbers per pulse and
+ * direction.  One upload, three launches and a fold, one download; the period is swept once more per (scale, distinct gain) only
+ * when a gains direction or a gains output is asked for, and the workspace is twice the forward call's whatever ndir is.  With
+ * the 2 ntr unit directions one gn call returns the dense normal matrix of the schedule, rows as directions.  No atomics: a
+ * pulse's loss, gradient and products depend only on the pulse, its grids, its train, its planes and the scale list; a
+ * direction's product depends neither on ndir, nor on its place among the directions, nor on whether an all-zero half was passed
+ * as NULL; a wanted half does not depend on whether the other was asked for.  Targets equal to mbfir_bloch_train_batch's own
+ * output give L = 0 and gradients of exact zeros.  m0 is not a variable of gn; b1, gr, tp, t1, t2, df, the positions, meq and the
+ * scales are not differentiated.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_batch; further MBFIR_E_ARG cases, each with a
+ * message beginning "bloch_train_lsq_sched_batch:" / "bloch_train_gn_sched_batch:" and no device work done: ebcast outside {0, 1}, a
+ * partly given sextuple or triple, both terms absent, both outputs NULL, both direction parts NULL, ndir < 1, sizes that overflow
+ * (the workspace, and the partials, checkpoints and workgroups times ndir), a negative or non-finite weight or rw.  A refused call
+ * leaves the context usable.  A NULL ctx returns MBFIR_E_ARG. */
+int mbfir_bloch_train_lsq_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                      const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
+                                      const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                      const double* tfz, double* loss, double* ggain, double* gphi, double* gmx, double* gmy,
+                                      double* gmz);
+int mbfir_bloch_train_gn_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                     const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                     const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                     const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz,
+                                     int ndir, const double* dgain, const double* dphi, double* hgain, double* hphi);
 /* ---- Adjoint of mbfir_bloch_batch's steady state with respect to b1, the gradient waveform and the off-resonance -------------------
  * mbfir_bloch_ss_vjp_batch with four more outputs after its own 31 arguments.  dM = (I - A)^-1 dF at m0 = M holds for every
  * parameter of the period, so these are mbfir_bloch_vjp_gr_batch's outputs on the sweep started from m0 = M with the end cotangent

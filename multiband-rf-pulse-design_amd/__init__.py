@@ -173,6 +173,14 @@ SYMBOLS = {
     "mbfir_bloch_train_gn_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 7 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_train_lsq_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
+                                                    _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                   [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] +
+                                                   [_dp] * 19),
+    "mbfir_bloch_train_gn_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
+                                                   _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                  [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] +
+                                                  [_dp] * 7 + [C.c_int] + [_dp] * 4),
     "mbfir_bloch_ss_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 12),
     "mbfir_bloch_ss_lsq_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
@@ -2357,6 +2365,163 @@ def bloch_train_gn_batch(pulses, df, dp, ntr, tangents, weights, *, rep_weights=
     return _gn_result(rfs, K, keep, h)
 
 
+def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
+                                phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, grad_gains=True,
+                                grad_phases=True, grad_m0=False, ctx=None):
+    """Loss and gradient in the schedule of a weighted least-squares fit of bloch_train_batch's echoes and final state in one device
+    call (mbfir_bloch_train_lsq_sched_batch): every argument through demod as for bloch_train_lsq_batch, the loss
+    being that call's L.  Returns a list of (L, grad_gains, grad_phases) per pulse: dL/dgains[k] and dL/dphases[k] (per radian) of
+    every repetition, float64 of shape (ntr,), summed over the scales and the points, what bloch_train_vjp_sched_batch returns at the
+    cotangents rw_k w (echo_k - t) and wf (m_N - tf); None in the place of a half that was not asked for (not both).  With grad_m0 a
+    fourth item (gmx, gmy, gmz), dL/dm0 of shape (S, nf, npos).  The gradients are per repetition whatever form the schedule was
+    given in (bloch_train_vjp_sched_batch says how a scalar's own derivative follows).  Nothing echo-sized comes back from the
+    device, and with point-sized targets and weights nothing echo-sized goes up.  The period is swept once more per (scale,
+    distinct gain) for the gains, not at all for the phases.  Deterministic: a pulse's bits depend only on the pulse, its grids, its
+    train, its planes and the scales, and a wanted half does not depend on whether the other was asked for; targets equal to
+    bloch_train_batch's own output give L == 0.0 and gradients of exact zeros."""
+    who = "bloch_train_lsq_sched_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if (targets is None) != (weights is None):
+        raise ValueError("%s: targets and weights are given together or not at all" % who)
+    if (targets_final is None) != (weights_final is None):
+        raise ValueError("%s: targets_final and weights_final are given together or not at all" % who)
+    if targets is None and targets_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    if not grad_gains and not grad_phases:
+        raise ValueError("%s: neither the gradient in the gains nor the gradient in the phases is wanted" % who)
+    nul = C.cast(None, _dp)
+    eb, w, t = (0, [nul] * 3, [nul] * 3) if targets is None else _train_echo_planes(who, A, ntr, weights, targets)
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    roff = _offsets(ntr)
+    loss = np.zeros(P)
+    gg = np.zeros(int(roff[-1])) if grad_gains else None
+    gp = np.zeros(int(roff[-1])) if grad_phases else None
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_lsq_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
+                                                          *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+                                                          *[_plane(v) for v in wf + tf], _ptr(loss),
+                                                          nul if gg is None else _ptr(gg), nul if gp is None else _ptr(gp),
+                                                          *[_plane(v) for v in gm])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    cut = lambda v, q: None if v is None else v[roff[q]:roff[q + 1]].copy()
+    res = [(float(loss[q]), cut(gg, q), cut(gp, q)) for q in range(P)]
+    if not grad_m0:
+        return res
+    return [res[q] + (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm),) for q in range(P)]
+
+
+def bloch_train_gn_sched_batch(pulses, df, dp, ntr, weights, *, tangents_gains=None, tangents_phases=None, rep_weights=None,
+                               weights_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False,
+                               prod_gains=None, prod_phases=None, ctx=None):
+    """Gauss-Newton products of the fit of bloch_train_lsq_sched_batch in one device call (mbfir_bloch_train_gn_sched_batch, DESIGN
+    section 8af): H v = J' W J v for J the Jacobian of (echoes, final state) in the schedule (gains, phases) and W the weights,
+    rep_weights included; arguments as for bloch_train_lsq_sched_batch without the targets.  tangents_gains / tangents_phases: as
+    bloch_train_jvp_sched_batch takes them, None (that half of v is zero; not both) or per pulse a float64 direction of shape (ntr,),
+    or K of them of shape (K, ntr), the same K for every pulse and for both; the phases' direction is per radian.  prod_gains /
+    prod_phases: which halves of H v are wanted; None = the halves that have directions (not both False).  weights None: no echo
+    term.  Returns per pulse (hg, hp), float64 of shape (ntr,) or (K, ntr), None in the place of a half that was not asked for.
+    With the 2 ntr unit directions the rows are the dense normal matrix (bloch_train_normal_sched_batch).  H is symmetric positive
+    semidefinite.  The period is swept once more per (scale, distinct gain) only when a gains direction or the gains half is asked
+    for.  A product's bits depend only on its pulse, grids, train, weights, direction and the scales: not on the batch, on K, on
+    the direction's place among K, on whether an all-zero half was passed as None, or on whether the other half was asked for.  m0
+    is not a variable."""
+    who = "bloch_train_gn_sched_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr = Tn.A, Tn.ntr
+    P = A.P
+    if weights is None and weights_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    if tangents_gains is None and tangents_phases is None:
+        raise ValueError("%s: no direction is given: tangents_gains and tangents_phases are both None" % who)
+    K, keep, parts = None, False, []
+    for what, v in (("gains", tangents_gains), ("phases", tangents_phases)):
+        if v is None:
+            parts.append(None)
+            continue
+        k, kp, d = _train_tangents_sched(who, what, v, ntr)
+        if K is not None and (k, kp) != (K, keep):
+            raise ValueError("%s: %d directions of the phases for %d of the gains" % (who, k, K))
+        K, keep = k, kp
+        parts.append(_vec(np.concatenate([x.ravel() for x in d])))
+    want_g = tangents_gains is not None if prod_gains is None else bool(prod_gains)
+    want_p = tangents_phases is not None if prod_phases is None else bool(prod_phases)
+    if not want_g and not want_p:
+        raise ValueError("%s: neither the product's gains half nor its phases half is wanted" % who)
+    nul = C.cast(None, _dp)
+    eb, w, _ = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None)
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    roff = _offsets(ntr)
+    hg = np.zeros(K * int(roff[-1])) if want_g else None
+    hp = np.zeros(K * int(roff[-1])) if want_p else None
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_gn_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
+                                                         *[_plane(v) for v in w], _plane(nul if rw is None else rw),
+                                                         *[_plane(v) for v in wf], K, *[nul if v is None else _ptr(v) for v in parts],
+                                                         nul if hg is None else _ptr(hg), nul if hp is None else _ptr(hp))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+
+    def cut(v, q):
+        if v is None:
+            return None
+        h = v[K * roff[q]:K * roff[q + 1]].reshape(K, ntr[q]).copy()
+        return h if keep else h[0]
+    return [(cut(hg, q), cut(hp, q)) for q in range(P)]
+
+
+def _sched_vary(who, vary):
+    """vary -> (gains?, phases?), gains first whatever the order given"""
+    vary = (vary,) if isinstance(vary, str) else tuple(vary)
+    if not vary or any(v not in ("gains", "phases") for v in vary) or len(set(vary)) != len(vary):
+        raise ValueError("%s: vary must name 'gains', 'phases' or both, once each, not %r" % (who, vary))
+    return "gains" in vary, "phases" in vary
+
+
+def bloch_train_normal_sched_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), rep_weights=None,
+                                   targets_final=None, weights_final=None, **kw):
+    """Loss, gradient and dense Gauss-Newton matrix of the fit of bloch_train_lsq_sched_batch in the schedule:
+    one bloch_train_lsq_sched_batch call and one bloch_train_gn_sched_batch call with the n unit directions, n = ntr x len(vary), the
+    gains first.  The pulses of a call share ntr (an int).  vary: ("gains", "phases"), ("gains",) or ("phases",); without "gains" the
+    period's tangent is never launched.  Keywords as bloch_train_lsq_sched_batch's, without the grad_ flags.  Returns per pulse
+    (L, g, H): g float64 of length n, H of shape (n, n), row j the product H e_j as the device returned it (symmetric to rounding;
+    the caller symmetrises)."""
+    who = "bloch_train_normal_sched_batch"
+    for k in ("grad_gains", "grad_phases", "grad_m0", "tangents_gains", "tangents_phases", "prod_gains", "prod_phases"):
+        if k in kw:
+            raise ValueError("%s: %s is not an argument: vary says which part of the schedule moves" % (who, k))
+    vg, vp = _sched_vary(who, vary)
+    pulses = list(pulses)
+    P = len(pulses)
+    n = _train_ints(who, "ntr", ntr, P)
+    if P == 0 or any(e != n[0] for e in n):
+        raise ValueError("%s: the pulses of a call must share ntr" % who)
+    if n[0] < 1:
+        raise ValueError("%s: ntr of pulse 0 must be at least 1" % who)
+    N = n[0]
+    lsq = bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, rep_weights=rep_weights, targets_final=targets_final,
+                                      weights_final=weights_final, grad_gains=vg, grad_phases=vp, **kw)
+    eye, zero = np.eye(N), np.zeros((N, N))
+    dg = [np.concatenate([eye, zero]) if vp else eye] * P if vg else None
+    dp_ = [np.concatenate([zero, eye]) if vg else eye] * P if vp else None
+    gn = bloch_train_gn_sched_batch(pulses, df, dp, ntr, weights, tangents_gains=dg, tangents_phases=dp_, rep_weights=rep_weights,
+                                    weights_final=weights_final, prod_gains=vg, prod_phases=vp, **kw)
+    out = []
+    for (L, gg, gp), (hg, hp) in zip(lsq, gn):
+        out.append((L, np.concatenate([v for v in (gg, gp) if v is not None]), np.concatenate([v for v in (hg, hp) if v is not None], 1)))
+    return out
+
+
 def _rf_g(pulse, q, who, gtype):
     """A pulse of abr_batch / abr2_batch, rf or (rf, g) -> rf and g of dtype gtype, abrm's 2 pi / n per sample where it has none."""
     rf, g = pulse if isinstance(pulse, tuple) else (pulse, None)
@@ -2952,7 +3117,7 @@ def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=
 
 
 from .refine import (refine_batch, refine_bloch_batch, refine_bloch_ss_batch, refine_bloch_train_batch,   # noqa: E402  (batched
-                     refine_bloch_train_lm_batch)                                                          # Levenberg-Marquardt on the calls above)
+                     refine_bloch_train_lm_batch, refine_bloch_train_sched_batch)                          # Levenberg-Marquardt on the calls above)
 
 
 def jvp_group():

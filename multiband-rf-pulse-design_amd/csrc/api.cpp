@@ -1887,6 +1887,131 @@ int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, con
                                             v_re, v_im, h_re, h_im));
 }
 
+// The fused products of the train's schedule (blochtrainschedgn.hip).  What both calls check after bloch_train_check, in
+// this order: ebcast, the echo and final planes given whole or not at all and not both absent, the outputs, the directions and ndir,
+// then (bloch_train_sched_gn_check) the sizes, before any plane is read: the propagators' planes twice (bloch_prop_check has bounded
+// them once) and, times the directions, one double2 partial per (scale, chunk of 256 points, repetition), 3 x 256 checkpoint doubles
+// per state (one for lsq, two for gn) and (scale, chunk of 256 points, group of 8 repetitions), the workgroups of the run and of
+// the fold, and the directions' entries: MBFIR_E_ARG when a count overflows, exceeds 2^56 or, for the workgroups, 2^31 - 1; last
+// the weights and rw, non-negative and finite.
+static int bloch_train_sched_gn_check(mbfir_ctx* ctx, const char* who, int npulse, int nscale, int ndir, int states, const int* ntr,
+                                      const long* roff, const long* ncomb, const long* npoint, int ebcast, const double* const w[3],
+                                      const double* rw, const double* const wf[3]) {
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    long E = 0, O = 0;
+    for (int p = 0; p < npulse; ++p) {
+        E += npoint[p] * nscale * ntr[p];                                 // bloch_train_check has bounded both
+        O += npoint[p] * nscale;
+    }
+    auto neg = [](const double* v, long n) {
+        for (long i = 0; i < n; ++i)
+            if (!(v[i] >= 0) || !std::isfinite(v[i])) return true;
+        return false;
+    };
+    long wsp = 0, part = 0, ckr = 0, wgp = 0, wgr = 0, wgf = 0;
+    for (int p = 0; p < npulse; ++p) {
+        const long nch = (npoint[p] + 255) / 256, nch64 = (npoint[p] + 63) / 64;
+        long a, b, c, d, e, f;
+        if (__builtin_mul_overflow(npoint[p], ncomb[p] * 48, &a) || __builtin_add_overflow(wsp, a, &wsp) ||
+            __builtin_mul_overflow(nch * nscale, (long)ntr[p], &b) || __builtin_mul_overflow(b, (long)ndir, &b) ||
+            __builtin_add_overflow(part, b, &part) ||
+            __builtin_mul_overflow(nch * nscale, ((long)ntr[p] + 7) / 8 * 768 * states, &c) ||
+            __builtin_mul_overflow(c, (long)ndir, &c) || __builtin_add_overflow(ckr, c, &ckr) ||
+            __builtin_mul_overflow(ncomb[p], nch64, &d) || __builtin_add_overflow(wgp, d, &wgp) ||
+            __builtin_mul_overflow(nch * nscale, (long)ndir, &e) || __builtin_add_overflow(wgr, e, &wgr) ||
+            __builtin_mul_overflow(((long)ntr[p] + 255) / 256, (long)ndir, &f) || __builtin_add_overflow(wgf, f, &wgf))
+            return bad("the output size or the workgroup count overflows");
+    }
+    if (roff[npulse] > (1L << 56) / ndir || wsp > (1L << 56) || part > (1L << 56) || ckr > (1L << 56) || wgp > 2147483647L ||
+        wgr > 2147483647L || wgf > 2147483647L)
+        return bad("the output size or the workgroup count overflows");
+    for (int c = 0; c < 3; ++c)
+        if ((w[0] && neg(w[c], ebcast ? O : E)) || (wf[0] && neg(wf[c], O))) return bad("a weight is negative or not finite");
+    if (rw && neg(rw, roff[npulse])) return bad("a repetition weight is negative or not finite");
+    return 0;
+}
+
+int mbfir_bloch_train_lsq_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                      const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                      const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
+                                      const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                      const double* tfz, double* loss, double* ggain, double* gphi, double* gmx, double* gmy,
+                                      double* gmz) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lsq_sched_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_lsq_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && wz && tx && ty && tz;
+    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && wfz && tfx && tfy && tfz;
+    if (any_e && !all_e) return bad("the echo weights and targets are given together or not at all");
+    if (any_f && !all_f) return bad("the final weights and targets are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    if (!loss) return bad("the loss plane is null");
+    if (!ggain && !gphi) return bad("neither the gradient in the gains nor the gradient in the phases is wanted");
+    if ((gmx || gmy || gmz) && !(gmx && gmy && gmz)) return bad("gmx, gmy and gmz are given together or not at all");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const t[3] = {tx, ty, tz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    const double* const tf[3] = {tfx, tfy, tfz};
+    if (const int e = bloch_train_sched_gn_check(ctx, "bloch_train_lsq_sched_batch", npulse, nscale, 1, 1, ntr, roff, ncomb.data(),
+                                                 npoint.data(), ebcast, w, rw, wf))
+        return e;
+    MBFIR_TRY(ctx, bloch_train_lsq_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                   tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
+                                                   ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z,
+                                                   ebcast, w, t, rw, wf, tf, loss, ggain, gphi, gmx, gmy, gmz));
+}
+
+int mbfir_bloch_train_gn_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                     const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                     const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                     const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz,
+                                     int ndir, const double* dgain, const double* dphi, double* hgain, double* hphi) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_gn_sched_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_gn_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
+    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    if (!hgain && !hphi) return bad("neither the product's gains half nor its phases half is wanted");
+    if (!dgain && !dphi) return bad("no direction is given: dgain and dphi are both null");
+    if (ndir < 1) return bad("ndir must be at least 1");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    if (const int e = bloch_train_sched_gn_check(ctx, "bloch_train_gn_sched_batch", npulse, nscale, ndir, 2, ntr, roff, ncomb.data(),
+                                                 npoint.data(), ebcast, w, rw, wf))
+        return e;
+    MBFIR_TRY(ctx, bloch_train_gn_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                  tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
+                                                  ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast,
+                                                  w, rw, wf, ndir, dgain, dphi, hgain, hphi));
+}
+
 int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                            const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
                            const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,

@@ -98,28 +98,8 @@ __global__ __launch_bounds__(256) void k_bloch_train_prop_dgain(const double* __
     w[0] = dm[0]; w[npair] = dm[1]; w[2 * npair] = dm[2];
 }
 
-// a . (M (J u) - J n) for a column-major M and n = M u + meq b: a repetition's share of dL / dphi through one of its two maps.
-// Every product and sum where it is written (contraction off), so that the share has the same bits whatever else the call wants.
-__device__ __forceinline__ double train_sched_dphi(const double* M, const double a[3], const double u[3], const double n[3]) {
-#pragma clang fp contract(off)
-    double p = fma(a[1], n[0], -(a[0] * n[1]));                           // -a . J n
-    p = -p;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p = fma(a[i], fma(M[3 + i], u[0], -(M[i] * u[1])), p);
-    return p;
-}
-// a . (M (J u)) alone: the demodulated echo is not turned back, so it has no J n term.
-__device__ __forceinline__ double train_sched_dphi_demod(const double* M, const double a[3], const double u[3]) {
-#pragma clang fp contract(off)
-    double p = 0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) p = fma(a[i], fma(M[3 + i], u[0], -(M[i] * u[1])), p);
-    return p;
-}
-__device__ __forceinline__ double train_sched_dot(const double a[3], const double v[3]) {
-#pragma clang fp contract(off)
-    return fma(a[2], v[2], fma(a[1], v[1], a[0] * v[0]));
-}
+// train_sched_dphi, train_sched_dphi_demod and train_sched_dot, a repetition's shares of the two contractions, are in sim_dev.h,
+// shared with the fused products of the schedule (blochtrainschedgn.hip).
 
 // blocks: the forward table (pulse, scale, chunk of 256 points).  ws: the propagators' planes; dws: their tangents in the gain (null:
 // the gains' gradient is not wanted and its half of every partial is zero).  cex.. / cfx.. / gmx.. / ck: k_bloch_train_run_vjp's.

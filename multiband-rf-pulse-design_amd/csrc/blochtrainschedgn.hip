@@ -1,0 +1,642 @@
+// Fused least-squares and Gauss-Newton products of the pulse train's schedule: 8ab's loss with the gain and the RF phase
+// of every repetition as the variable.  In blochtrainsched.hip's and blochtrainschedjvp.hip's notation, per pulse,
+//     L = 1/2 sum_s sum_k rw_k sum_points sum_c w_c (echo_{k,c} - t_c)^2 + 1/2 sum_s sum_points sum_c wf_c (m_{N,c} - tf_c)^2
+//     lsq: L, dL / dgains[k], dL / dphases[k] (per radian): 8ad's contraction at ce_k = rw_k w (echo_k - t), cf = wf (m_N - tf)
+//     gn:  H v = J' W J v for v = (dg, dp): 8ae's recursion along v from dm_0 = 0 gives decho_k and dm_N; 8ad's contraction at
+//          ce_k = rw_k w decho_k, cf = wf dm_N, taken at the primal u_k
+// Everything between the echoes (or their tangents) and the cotangents is pointwise and the thread that owns the point holds every
+// operand, so nothing echo-sized is written or read: what comes down is 2 ntr numbers per pulse (and direction) and the loss.
+//   k_bloch_train_run_sched_lsq: k_bloch_train_run_sched's launch shape, table, forward walk and checkpoints.  On the way back the
+//                                echo of repetition k is formed from the recomputed u_k with k_bloch_train_run's statements, the
+//                                residual, ce_k and the thread's share of the loss as in k_bloch_train_run_lsq, then
+//                                k_bloch_train_run_sched's two contractions and its reduction through the VJP_T x 2 tile.  The loss
+//                                goes through a fixed tree in LDS (lm_block_sum) to one partial per (scale, chunk).
+//   k_bloch_train_run_sched_gn:  the forward table times the directions, one direction per workgroup.  The forward walk carries
+//                                (m, dm) with train_sj_in / train_sj_map as k_bloch_train_run_sched_jvp does and checkpoints both;
+//                                the backward walk recomputes (u_k, du_k), forms decho_k, ce_k = rw_k (w decho_k), lambda_N = wf dm_N,
+//                                and contracts at the primal u_k into direction d's own partials.
+//   k_bloch_train_sched_gn_fold: k_bloch_train_sched_fold's sum (chunks, then scales, in index order) per (pulse, direction), and the
+//                                loss partials of a pulse in index order.
+// The propagators' planes come from the shipped k_bloch_train_prop, their tangents in the gain from the shipped
+// k_bloch_train_prop_dgain, which is skipped when neither a gains direction nor a gains output is asked for: the workspace is 2 W
+// doubles whatever the number of directions.  No atomics.
+#include "dev_common.h"
+#include "pulse.h"
+#include "sim_dev.h"
+#include <cmath>
+
+namespace mbfir {
+
+// Whether k_bloch_train_run_sched_gn keeps the 24 planes and their 24 tangents in registers over the whole walk when the pulse has
+// one distinct gain.  0: twelve of each are loaded where a repetition needs them, as TGN_HOIST = 0 and k_bloch_train_run_sched_jvp
+// do.  DESIGN 8af has the resource table of both.
+#ifndef TSGN_HOIST
+#define TSGN_HOIST 0
+#endif
+
+// o = M' a for a column-major M: a multiplier's step back through one of a repetition's two maps.  Every product and sum where it
+// is written (contraction off), so that a product's bits do not depend on what surrounds the statement.
+__device__ __forceinline__ void train_sg_back(const double* M, const double a[3], double o[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = fma(M[3 * i + 2], a[2], fma(M[3 * i + 1], a[1], M[3 * i] * a[0]));
+}
+
+// blocks, ws, dws (null: the gains' half of every partial is zero), rep, gidx, vp, cks, ck, part, gmx ..: k_bloch_train_run_sched's.
+// rw (null: ones), we / te (null: no echo term), PE, wf / tf (null: no final term), PO, ebcast, lp, lpart: k_bloch_train_run_lsq's.
+__global__ __launch_bounds__(256) void k_bloch_train_run_sched_lsq(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const long* __restrict__ lp, const double* __restrict__ m0, int demod, int ebcast, const double* __restrict__ we,
+    const double* __restrict__ te, long PE, const double* __restrict__ wf, const double* __restrict__ tf, long PO, double* ck,
+    double2* __restrict__ part, double* __restrict__ gmx, double* __restrict__ gmy, double* __restrict__ gmz,
+    double* __restrict__ lpart) {
+    __shared__ double2 scs[256];
+    __shared__ double srw[256];
+    __shared__ int sgi[256];
+    __shared__ double red[2 * VJP_T * VJP_ROW];
+    static_assert(TRV_T == VJP_T, "a group of repetitions fills the tile's VJP_T x 2 rows");
+    const int tid = threadIdx.x;
+    const SimBlock bk = blocks[blockIdx.x];
+    const BlochPulseDev P = pulses[bk.pulse];
+    const TrainPulseDev Tr = trains[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    const int ntr = Tr.ntr, G = Tr.ngain;
+    const double meq = Tr.meq;
+    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
+    const bool live = pair < npair;                                       // a thread past the end of the grid: the barriers only
+    const long blk = (long)bk.scale * npair + pair;
+    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
+    const double* wb = ws + Tr.w_off + comb0;
+    const double* db = dws ? dws + Tr.w_off + comb0 : nullptr;
+    const long nch = (npair + 255) / 256;
+    double* wck = ck + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK + tid;
+    double2* wpart = part + V.p_off + ((long)bk.scale * nch + bk.chunk) * ntr;
+    const int row = tid >> 4, ln = tid & 15;                              // reduction: 16 lanes per row of the tile
+    double m[3] = {0, 0, 1}, W[TRAIN_ENT], dW[TRAIN_ENT];
+    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
+#pragma unroll
+    for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = 0;
+    if (G == 1) {                                                         // one distinct gain: the planes are loaded once
+#pragma unroll
+        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
+        if (db) {
+#pragma unroll
+            for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[e * npair];
+        }
+    }
+    auto stage = [&](int k0) {
+        __syncthreads();
+        const int cnt = min(256, ntr - k0);
+        if (tid < cnt) {
+            scs[tid] = rep[Tr.r_off + k0 + tid];
+            sgi[tid] = gidx[Tr.r_off + k0 + tid];
+            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
+        }
+        __syncthreads();
+    };
+    // m_k -> m_{k+1} from u_k = Z(+phi_k) m_k (in v), with the planes of the repetition in W[0 .. 11]
+    auto advance = [&](double c, double s, double v[3]) {
+        double n[3];
+        train_affine(W, W + 9, meq, v, n);
+        train_zm(c, s, n);
+        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
+    };
+    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints
+        stage(k0);
+        const int cnt = min(256, ntr - k0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            if ((q & (TRV_T - 1)) == 0) {                                 // m before repetition k0 + q
+                double* w = wck + (long)((k0 + q) / TRV_T) * BLOCH_CK;
+                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
+            }
+            if (G != 1) {
+                const double* wg = wb + (long)sgi[q] * TRAIN_ENT * npair;
+#pragma unroll
+                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
+            }
+            train_zp(scs[q].x, scs[q].y, m);
+            advance(scs[q].x, scs[q].y, m);
+        }
+    }
+    double l[3] = {0, 0, 0}, ls = 0;
+    if (live && wf) {                                                     // lambda_N = wf (m_N - tf), and the final loss
+        const long o = P.o_off + blk;
+        const double w0 = wf[o], w1 = wf[PO + o], w2 = wf[2 * PO + o];
+        const double r0 = m[0] - tf[o], r1 = m[1] - tf[PO + o], r2 = m[2] - tf[2 * PO + o];
+        l[0] = w0 * r0; l[1] = w1 * r1; l[2] = w2 * r2;
+        ls = 0.5 * (w0 * (r0 * r0) + w1 * (r1 * r1) + w2 * (r2 * r2));
+    }
+    // the weights and targets of repetition k at wp[k kstr], tp[k kstr]
+    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
+    const double* wp = we ? we + eo : nullptr;
+    const double* tp = we ? te + eo : nullptr;
+    const int klast = (ntr - 1) / 256 * 256;
+    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
+        if (k0 != klast) stage(k0);                                       // the forward walk left the last tile staged
+        const int cnt = min(256, ntr - k0);
+        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
+            const int ge = min(g0 + TRV_T, cnt);
+            if (live) {
+                double us[TRV_T][3], mm[3];                               // us[j] = u of repetition k0 + g0 + j
+                const double* w = wck + (long)((k0 + g0) / TRV_T) * BLOCH_CK;
+                mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
+#pragma unroll
+                for (int j = 0; j < TRV_T; ++j) {
+                    if (g0 + j < ge) {
+                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                        train_zp(c, s, mm);
+                        us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
+                        if (g0 + j + 1 < ge) {
+                            if (G != 1) {
+                                const double* wg = wb + (long)sgi[g0 + j] * TRAIN_ENT * npair;
+#pragma unroll
+                                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
+                            }
+                            advance(c, s, mm);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = TRV_T - 1; j >= 0; --j) {
+                    if (g0 + j < ge) {
+                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                        const long go = (long)sgi[g0 + j] * TRAIN_ENT * npair;
+                        if (G != 1) {
+#pragma unroll
+                            for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[go + e * npair];
+                            if (db) {
+#pragma unroll
+                                for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[go + e * npair];
+                            }
+                        }
+                        const double* u = us[j];
+                        double a[3] = {l[0], l[1], l[2]}, n[3], dn[3];
+                        train_zp(c, s, a);
+                        train_affine(W, W + 9, meq, u, n);
+                        train_affine(dW, dW + 9, meq, u, dn);
+                        double gp = train_sched_dphi(W, a, u, n), gg = train_sched_dot(a, dn);
+                        train_sg_back(W, a, l);                           // A' a
+                        if (wp) {
+                            const long ko = (long)(k0 + g0 + j) * kstr;
+                            const double rk = srw[g0 + j];
+                            double e[3], ae[3], le[3];
+                            train_affine(W + 12, W + 21, meq, u, n);      // ne, and the echo as k_bloch_train_run forms it
+                            e[0] = n[0]; e[1] = n[1]; e[2] = n[2];
+                            if (!demod) train_zm(c, s, e);
+                            double q2 = 0;
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) {
+                                const double wi = wp[ko + i * PE], r = e[i] - tp[ko + i * PE];
+                                ae[i] = rk * (wi * r);                    // ce_k = rw_k w r
+                                q2 += wi * (r * r);
+                            }
+                            ls += rk * (0.5 * q2);
+                            if (!demod) train_zp(c, s, ae);
+                            train_affine(dW + 12, dW + 21, meq, u, dn);
+                            gg += train_sched_dot(ae, dn);
+                            gp += demod ? train_sched_dphi_demod(W + 12, ae, u) : train_sched_dphi(W + 12, ae, u, n);
+                            train_sg_back(W + 12, ae, le);                // A_e' ae
+                            l[0] += le[0]; l[1] += le[1]; l[2] += le[2];
+                        }
+                        train_zm(c, s, l);
+                        red[(2 * j) * VJP_ROW + tid] = gg;
+                        red[(2 * j + 1) * VJP_ROW + tid] = gp;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < TRV_T; ++j)
+                    if (g0 + j < ge) { red[(2 * j) * VJP_ROW + tid] = 0.0; red[(2 * j + 1) * VJP_ROW + tid] = 0.0; }
+            }
+            __syncthreads();
+            double sum = 0;                                               // row = 2 (repetition - g0) + (0: gain, 1: phase); rows past ge are not stored
+            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
+            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
+            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + k0 + g0)[row] = sum;
+            __syncthreads();
+        }
+    }
+    const double sum = lm_block_sum(live ? ls : 0.0, red);                // 256 doubles of the tile, free after the last group
+    if (tid == 0) lpart[lp[bk.pulse] + (long)bk.scale * nch + bk.chunk] = sum;
+    if (live && gmx) { const long o = P.o_off + blk; gmx[o] = l[0]; gmy[o] = l[1]; gmz[o] = l[2]; }
+}
+
+// blocks: the forward table times the directions (pad).  dws (null: no gains direction and no gains output), rep, gidx, m0, demod:
+// k_bloch_train_run_sched_jvp's; dgain / dphi (either null: zeros): direction d of a pulse at ndir r_off + d ntr.  rw, we, PE, wf,
+// PO, ebcast: k_bloch_train_run_gn's.  ck: direction d's checkpoints from 2 d CK, a group 2 x 3 x 256 doubles (m, then dm); part:
+// direction d's partials from d NP, laid out as k_bloch_train_run_sched's.
+__global__ __launch_bounds__(256) void k_bloch_train_run_sched_gn(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const double* __restrict__ m0, const double* __restrict__ dgain, const double* __restrict__ dphi, int demod, int ebcast, int ndir,
+    const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long CK, long NP, double* ck,
+    double2* __restrict__ part) {
+    __shared__ double2 scs[256];
+    __shared__ double2 sdr[256];                                          // (dg_k, dp_k) of the workgroup's direction
+    __shared__ double srw[256];
+    __shared__ int sgi[256];
+    __shared__ double red[2 * VJP_T * VJP_ROW];
+    static_assert(TRV_T == VJP_T, "a group of repetitions fills the tile's VJP_T x 2 rows");
+    const int tid = threadIdx.x;
+    const SimBlock bk = blocks[blockIdx.x];
+    const BlochPulseDev P = pulses[bk.pulse];
+    const TrainPulseDev Tr = trains[bk.pulse];
+    const VjpPulseDev V = vp[bk.pulse];
+    const BlochCkDev K = cks[bk.pulse];
+    const int ntr = Tr.ntr, G = Tr.ngain, dir = bk.pad;
+    const double meq = Tr.meq;
+    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
+    const bool live = pair < npair;                                       // a thread past the end of the grid: the barriers only
+    const long blk = (long)bk.scale * npair + pair;
+    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
+    const double* wb = ws + Tr.w_off + comb0;
+    const double* db = dws ? dws + Tr.w_off + comb0 : nullptr;
+    const long gstr = (long)TRAIN_ENT * npair;
+    const long nch = (npair + 255) / 256;
+    double* wck = ck + 2 * ((long)dir * CK + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK) + tid;
+    double2* wpart = part + (long)dir * NP + V.p_off + ((long)bk.scale * nch + bk.chunk) * ntr;
+    const long sbase = (long)ndir * Tr.r_off + (long)dir * ntr;           // the direction's first repetition in dgain / dphi
+    const int row = tid >> 4, ln = tid & 15;
+    const bool hoist = TSGN_HOIST && G == 1;
+    double m[3] = {0, 0, 1}, dm[3] = {0, 0, 0}, W[TRAIN_ENT], dW[TRAIN_ENT];
+    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
+#pragma unroll
+    for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = 0;
+    if (hoist) {
+#pragma unroll
+        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
+        if (db) {
+#pragma unroll
+            for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[e * npair];
+        }
+    }
+    auto stage = [&](int k0) {
+        __syncthreads();
+        const int cnt = min(256, ntr - k0);
+        if (tid < cnt) {
+            const long o = sbase + k0 + tid;
+            scs[tid] = rep[Tr.r_off + k0 + tid];
+            sgi[tid] = gidx[Tr.r_off + k0 + tid];
+            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
+            sdr[tid] = make_double2(dgain ? dgain[o] : 0.0, dphi ? dphi[o] : 0.0);
+        }
+        __syncthreads();
+    };
+    // the state's half of the planes of the gain at go, and of their tangents, into W[0 .. 11] and dW[0 .. 11]
+    auto load_state = [&](long go) {
+        if (hoist) return;
+#pragma unroll
+        for (int e = 0; e < 12; ++e) W[e] = wb[go + e * npair];
+        if (db) {
+#pragma unroll
+            for (int e = 0; e < 12; ++e) dW[e] = db[go + e * npair];
+        }
+    };
+    // (m_k, dm_k) -> (m_{k+1}, dm_{k+1}) from (u_k, du_k) (in v, dv), as k_bloch_train_run_sched_jvp steps them
+    auto advance = [&](double c, double s, double2 d, double v[3], double dv[3]) {
+        double n[3], gn[3], dn[3];
+        train_affine(W, W + 9, meq, v, n);
+        train_affine(dW, dW + 9, meq, v, gn);                             // dA u + meq dB (zeros without the tangent planes)
+        train_sj_map(W, gn, n, d.x, d.y, true, dv, dn);
+        train_zm(c, s, dn);
+        train_zm(c, s, n);
+        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
+        dv[0] = dn[0]; dv[1] = dn[1]; dv[2] = dn[2];
+    };
+    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints of m and dm
+        stage(k0);
+        const int cnt = min(256, ntr - k0);
+        if (!live) continue;
+        for (int q = 0; q < cnt; ++q) {
+            if ((q & (TRV_T - 1)) == 0) {                                 // (m, dm) before repetition k0 + q
+                double* w = wck + (long)((k0 + q) / TRV_T) * (2 * BLOCH_CK);
+                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
+                w[768] = dm[0]; w[1024] = dm[1]; w[1280] = dm[2];
+            }
+            const double c = scs[q].x, s = scs[q].y;
+            load_state((long)sgi[q] * gstr);
+            train_zp(c, s, m);
+            train_sj_in(c, s, sdr[q].y, m, dm);
+            advance(c, s, sdr[q], m, dm);
+        }
+    }
+    double l[3] = {0, 0, 0};
+    if (live && wf) {                                                     // lambda_N = wf dm_N
+        const long o = P.o_off + blk;
+        l[0] = wf[o] * dm[0]; l[1] = wf[PO + o] * dm[1]; l[2] = wf[2 * PO + o] * dm[2];
+    }
+    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
+    const double* wp = we ? we + eo : nullptr;
+    const int klast = (ntr - 1) / 256 * 256;
+    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
+        if (k0 != klast) stage(k0);                                       // the forward walk left the last tile staged
+        const int cnt = min(256, ntr - k0);
+        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
+            const int ge = min(g0 + TRV_T, cnt);
+            if (live) {
+                double us[TRV_T][3], dus[TRV_T][3], mm[3], dmm[3];        // (u, du) of repetition k0 + g0 + j
+                const double* w = wck + (long)((k0 + g0) / TRV_T) * (2 * BLOCH_CK);
+                mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
+                dmm[0] = w[768]; dmm[1] = w[1024]; dmm[2] = w[1280];
+#pragma unroll
+                for (int j = 0; j < TRV_T; ++j) {
+                    if (g0 + j < ge) {
+                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                        const double2 d = sdr[g0 + j];
+                        train_zp(c, s, mm);
+                        train_sj_in(c, s, d.y, mm, dmm);
+                        us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
+                        dus[j][0] = dmm[0]; dus[j][1] = dmm[1]; dus[j][2] = dmm[2];
+                        if (g0 + j + 1 < ge) {
+                            load_state((long)sgi[g0 + j] * gstr);
+                            advance(c, s, d, mm, dmm);
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = TRV_T - 1; j >= 0; --j) {
+                    if (g0 + j < ge) {
+                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
+                        const long go = (long)sgi[g0 + j] * gstr;
+                        const double* u = us[j];
+                        double gg = 0, gp = 0, le[3] = {0, 0, 0};
+                        if (wp) {                                         // the echo's half first: its planes are dead before the state's
+                            const long ko = (long)(k0 + g0 + j) * kstr;
+                            const double rk = srw[g0 + j];
+                            const double2 d = sdr[g0 + j];
+                            if (!hoist) {
+#pragma unroll
+                                for (int e = 12; e < TRAIN_ENT; ++e) W[e] = wb[go + e * npair];
+                                if (db) {
+#pragma unroll
+                                    for (int e = 12; e < TRAIN_ENT; ++e) dW[e] = db[go + e * npair];
+                                }
+                            }
+                            double ne[3], ge3[3], ae[3];
+                            train_affine(W + 12, W + 21, meq, u, ne);
+                            train_affine(dW + 12, dW + 21, meq, u, ge3);  // dA_e u + meq dB_e
+                            train_sj_map(W + 12, ge3, ne, d.x, d.y, !demod, dus[j], ae);      // decho, as k_bloch_train_run_sched_jvp forms it
+                            if (!demod) train_zm(c, s, ae);
+#pragma unroll
+                            for (int i = 0; i < 3; ++i) ae[i] = rk * (wp[ko + i * PE] * ae[i]);       // ce_k = rw_k w decho_k
+                            if (!demod) train_zp(c, s, ae);
+                            gg = train_sched_dot(ae, ge3);
+                            gp = demod ? train_sched_dphi_demod(W + 12, ae, u) : train_sched_dphi(W + 12, ae, u, ne);
+                            train_sg_back(W + 12, ae, le);                // A_e' ae
+                        }
+                        load_state(go);
+                        double a[3] = {l[0], l[1], l[2]}, n[3], dn[3];
+                        train_zp(c, s, a);
+                        train_affine(W, W + 9, meq, u, n);
+                        train_affine(dW, dW + 9, meq, u, dn);
+                        gp += train_sched_dphi(W, a, u, n);
+                        gg += train_sched_dot(a, dn);
+                        train_sg_back(W, a, l);                           // A' a
+                        l[0] += le[0]; l[1] += le[1]; l[2] += le[2];
+                        train_zm(c, s, l);
+                        red[(2 * j) * VJP_ROW + tid] = gg;
+                        red[(2 * j + 1) * VJP_ROW + tid] = gp;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < TRV_T; ++j)
+                    if (g0 + j < ge) { red[(2 * j) * VJP_ROW + tid] = 0.0; red[(2 * j + 1) * VJP_ROW + tid] = 0.0; }
+            }
+            __syncthreads();
+            double sum = 0;                                               // row = 2 (repetition - g0) + (0: gain, 1: phase); rows past ge are not stored
+            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
+            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
+            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + k0 + g0)[row] = sum;
+            __syncthreads();
+        }
+    }
+}
+
+// out[ndir r_off + d n + k] = k_bloch_train_sched_fold's value from direction d's partials (part + d NP): one thread per repetition,
+// one workgroup per (pulse, direction, 256 repetitions) from its own table (SimBlock: pulse, direction, chunk of repetitions).  lsq
+// (loss not null, ndir = 1): the first thread of a pulse's first workgroup also sums the pulse's nscale nch loss partials in index
+// order.
+__global__ __launch_bounds__(256) void k_bloch_train_sched_gn_fold(const double2* __restrict__ part, long NP,
+                                                                   const VjpPulseDev* __restrict__ vp,
+                                                                   const SimBlock* __restrict__ blocks, int nscale, int ndir,
+                                                                   double2* __restrict__ out, const double* __restrict__ lpart,
+                                                                   const long* __restrict__ lp, double* __restrict__ loss) {
+    const SimBlock bk = blocks[blockIdx.x];
+    const VjpPulseDev V = vp[bk.pulse];
+    const int k = bk.chunk * 256 + threadIdx.x;
+    if (loss && bk.scale == 0 && k == 0) {
+        const double* q = lpart + lp[bk.pulse];
+        const long nw = (long)nscale * V.nch;
+        double s = 0;
+        for (long i = 0; i < nw; ++i) s += q[i];
+        loss[bk.pulse] = s;
+    }
+    if (k >= V.n) return;
+    double2 g = make_double2(0, 0);
+    for (int s = 0; s < nscale; ++s) {
+        double2 t = make_double2(0, 0);
+        const double2* rw = part + (long)bk.scale * NP + V.p_off + (long)s * V.nch * V.n + k;
+        for (int c = 0; c < V.nch; ++c) {
+            const double2 v = rw[(long)c * V.n];
+            t.x += v.x; t.y += v.y;
+        }
+        g.x += t.x; g.y += t.y;
+    }
+    out[(long)ndir * V.r_off + (long)bk.scale * V.n + k] = g;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Host side of mbfir_bloch_train_lsq_sched_batch and mbfir_bloch_train_gn_sched_batch (arguments checked by api.cpp): the forward
+// train's staging (bloch_stage, train_stage), the weights and targets, the partial and checkpoint descriptors, the loss partials'
+// offsets, the tables of the period's tangent and of the fold and, for gn, the directions and the forward table times the
+// directions; one upload, the launches, one download.  The output region is what comes down (the gradient halves or the products as
+// double2, the loss, dL / dm0), then what stays on the device: the partials per direction, the loss partials, the primal planes,
+// their tangents in the gain and the checkpoints per direction.
+namespace {
+
+size_t add_triple(Staging& S, const double* const v[3], long n) {
+    const size_t o = S.add(v[0] ? (size_t)n * 24 : 0);
+    if (v[0]) {
+        double* d = S.at<double>(o);
+        for (int c = 0; c < 3; ++c) std::copy(v[c], v[c] + n, d + (size_t)c * n);
+    }
+    return o;
+}
+
+// The sections both calls add after train_stage; t* null for gn.
+struct SchedGnCall {
+    TrainStaged Ts;
+    size_t o_we = 0, o_te = 0, o_rw = 0, o_wf = 0, o_tf = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0;
+    long PE = 0, npart = 0, nck = 0, nlp = 0, nfold = 0;      // per direction: double2 partials, checkpoint doubles of one state
+};
+
+void sched_gn_stage(SchedGnCall& Cl, int npulse, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
+                    const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
+                    const double* const tf[3]) {
+    TrainStaged& Ts = Cl.Ts;
+    BlochStaged& B = Ts.B;
+    Staging& S = B.S;
+    Cl.PE = ebcast ? B.O : Ts.E;
+    Cl.o_we = add_triple(S, w, Cl.PE);
+    Cl.o_te = add_triple(S, t, Cl.PE);
+    Cl.o_wf = add_triple(S, wf, B.O);
+    Cl.o_tf = add_triple(S, tf, B.O);
+    Cl.o_rw = S.add(rw ? (size_t)roff[npulse] * 8 : 0);
+    if (rw) std::copy(rw, rw + roff[npulse], S.at<double>(Cl.o_rw));
+    std::vector<VjpPulseDev> vp(npulse);
+    std::vector<BlochCkDev> ckr(npulse);
+    std::vector<long> lp(npulse);
+    for (int p = 0; p < npulse; ++p) {
+        const int nch = int((B.npair[p] + 255) / 256), ngr = (ntr[p] + TRV_T - 1) / TRV_T;
+        vp[p] = VjpPulseDev{roff[p], Cl.npart, ntr[p], nch};
+        ckr[p] = BlochCkDev{Cl.nck, ngr, 0};
+        lp[p] = Cl.nlp;
+        Cl.npart += (long)nscale * nch * ntr[p];
+        Cl.nck += (long)nscale * nch * ngr * BLOCH_CK;
+        Cl.nlp += (long)nscale * nch;
+        Cl.nfold += (long)ndir * ((ntr[p] + 255) / 256);
+    }
+    Cl.o_vp = S.add(npulse * sizeof(VjpPulseDev));
+    Cl.o_ck = S.add(npulse * sizeof(BlochCkDev));
+    Cl.o_lp = S.add(npulse * sizeof(long));
+    Cl.o_fb = S.add(Cl.nfold * sizeof(SimBlock));
+    std::copy(vp.begin(), vp.end(), S.at<VjpPulseDev>(Cl.o_vp));
+    std::copy(ckr.begin(), ckr.end(), S.at<BlochCkDev>(Cl.o_ck));
+    std::copy(lp.begin(), lp.end(), S.at<long>(Cl.o_lp));
+    SimBlock* fb = S.at<SimBlock>(Cl.o_fb);
+    for (int p = 0; p < npulse; ++p)
+        for (int d = 0; d < ndir; ++d)
+            for (int k = 0; k < (ntr[p] + 255) / 256; ++k) *fb++ = SimBlock{p, d, k, 0};
+}
+
+// what came down as R double2 -> the two halves the caller wants
+void unpack_halves(size_t n, const double* h, double* a, double* b) {
+    for (size_t k = 0; k < n; ++k) {
+        if (a) a[k] = h[2 * k];
+        if (b) b[k] = h[2 * k + 1];
+    }
+}
+
+}  // namespace
+
+void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                     const double* m0z, int ebcast, const double* const w[3], const double* const t[3],
+                                     const double* rw, const double* const wf[3], const double* const tf[3], double* loss,
+                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SchedGnCall Cl;
+    TrainStaged& Ts = Cl.Ts;
+    BlochStaged& B = Ts.B;
+    bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                nscale, scales, 0, m0x, m0y, m0z);
+    train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
+    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf);
+    Staging& S = B.S;
+    const long O = B.O, R = roff[npulse];
+    const bool want_g = ggain != nullptr, want_m0 = gmx != nullptr, echo_t = w[0] != nullptr, fin_t = wf[0] != nullptr;
+    long nwg = 0;                                                         // workgroups of the period's tangent
+    const size_t o_qb = want_g ? train_jvp_table(Ts, nscale, 1, nwg) : 0;
+    // even counts: the partials after them stay 16-byte aligned
+    const size_t NL = ((size_t)npulse + 1) & ~size_t(1), O3 = want_m0 ? ((size_t)O * 3 + 1) & ~size_t(1) : 0;
+    const size_t W = (size_t)Ts.W, LP = ((size_t)Cl.nlp + 1) & ~size_t(1);
+    S.upload(((size_t)R * 2 + NL + O3 + (size_t)Cl.npart * 2 + LP + W + (want_g ? W : 0) + (size_t)Cl.nck) * 8, st);
+    double2* grad = S.dev<double2>(S.o_out);
+    double* dloss = reinterpret_cast<double*>(grad + R);
+    double* gm = dloss + NL;
+    double2* part = reinterpret_cast<double2*>(gm + O3);
+    double* lpart = reinterpret_cast<double*>(part + Cl.npart);
+    double* ws = lpart + LP;
+    double* dws = want_g ? ws + W : nullptr;
+    double* ck = ws + W + (want_g ? W : 0);
+    train_launch_prop(Ts, st, ws);
+    if (want_g) train_launch_prop_dgain(Ts, st, o_qb, nwg, dws);
+    const double* wed = echo_t ? S.dev<const double>(Cl.o_we) : nullptr;
+    const double* ted = echo_t ? S.dev<const double>(Cl.o_te) : nullptr;
+    hipLaunchKernelGGL(k_bloch_train_run_sched_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, S.dev<const double2>(Ts.o_rep),
+                       S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
+                       S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(Cl.o_vp),
+                       S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const long>(Cl.o_lp), S.dev<const double>(B.o_m0), demod, ebcast, wed,
+                       ted, Cl.PE, fin_t ? S.dev<const double>(Cl.o_wf) : nullptr, fin_t ? S.dev<const double>(Cl.o_tf) : nullptr, O,
+                       ck, part, want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr, want_m0 ? gm + 2 * O : nullptr, lpart);
+    hipLaunchKernelGGL(k_bloch_train_sched_gn_fold, dim3((unsigned)Cl.nfold), dim3(256), 0, st, part, Cl.npart,
+                       S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const SimBlock>(Cl.o_fb), nscale, 1, grad, lpart,
+                       S.dev<const long>(Cl.o_lp), dloss);
+    std::vector<double> h((size_t)R * 2 + NL + O3);
+    S.download(h.data(), h.size() * 8, st);
+    unpack_halves((size_t)R, h.data(), ggain, gphi);
+    std::copy(h.data() + 2 * R, h.data() + 2 * R + npulse, loss);
+    if (want_m0) {
+        const double* hm = h.data() + 2 * R + NL;
+        std::copy(hm, hm + O, gmx);
+        std::copy(hm + O, hm + 2 * O, gmy);
+        std::copy(hm + 2 * O, hm + 3 * O, gmz);
+    }
+}
+
+void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                    const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                    const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                    const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                    const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                    const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                    const double* m0z, int ebcast, const double* const w[3], const double* rw,
+                                    const double* const wf[3], int ndir, const double* dgain, const double* dphi, double* hgain,
+                                    double* hphi) {
+    MBFIR_HIP(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SchedGnCall Cl;
+    TrainStaged& Ts = Cl.Ts;
+    BlochStaged& B = Ts.B;
+    bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                nscale, scales, 0, m0x, m0y, m0z);
+    train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
+    const double* const none[3] = {nullptr, nullptr, nullptr};
+    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, ndir, w, none, rw, wf, none);
+    Staging& S = B.S;
+    const long O = B.O;
+    const size_t D = (size_t)ndir * roff[npulse], W = (size_t)Ts.W, K = (size_t)ndir;
+    const size_t o_g = dgain ? S.add(D * 8) : 0, o_p = dphi ? S.add(D * 8) : 0;
+    const size_t o_jb = sim_group_table(S, ndir);
+    if (dgain) std::copy(dgain, dgain + D, S.at<double>(o_g));
+    if (dphi) std::copy(dphi, dphi + D, S.at<double>(o_p));
+    const bool tang = dgain != nullptr || hgain != nullptr;               // the planes' tangents in the gain are needed
+    long nwg = 0;
+    const size_t o_qb = tang ? train_jvp_table(Ts, nscale, 1, nwg) : 0;
+    S.upload((D * 2 + K * (size_t)Cl.npart * 2 + W + (tang ? W : 0) + 2 * K * (size_t)Cl.nck) * 8, st);
+    double2* out = S.dev<double2>(S.o_out);
+    double2* part = out + D;
+    double* ws = reinterpret_cast<double*>(part + K * (size_t)Cl.npart);
+    double* dws = tang ? ws + W : nullptr;
+    double* ck = ws + W + (tang ? W : 0);
+    train_launch_prop(Ts, st, ws);
+    if (tang) train_launch_prop_dgain(Ts, st, o_qb, nwg, dws);
+    hipLaunchKernelGGL(k_bloch_train_run_sched_gn, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, ws, dws,
+                       S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr,
+                       S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_jb),
+                       S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const double>(B.o_m0),
+                       dgain ? S.dev<const double>(o_g) : nullptr, dphi ? S.dev<const double>(o_p) : nullptr, demod, ebcast, ndir,
+                       w[0] ? S.dev<const double>(Cl.o_we) : nullptr, Cl.PE, wf[0] ? S.dev<const double>(Cl.o_wf) : nullptr, O, Cl.nck,
+                       Cl.npart, ck, part);
+    hipLaunchKernelGGL(k_bloch_train_sched_gn_fold, dim3((unsigned)Cl.nfold), dim3(256), 0, st, part, Cl.npart,
+                       S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const SimBlock>(Cl.o_fb), nscale, ndir, out, nullptr,
+                       S.dev<const long>(Cl.o_lp), nullptr);
+    std::vector<double> h(D * 2);
+    S.download(h.data(), h.size() * 8, st);
+    unpack_halves(D, h.data(), hgain, hphi);
+}
+
+}  // namespace mbfir

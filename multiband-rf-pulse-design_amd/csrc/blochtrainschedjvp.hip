@@ -31,25 +31,8 @@ namespace mbfir {
 #define TSJ_K 1
 #endif
 
-// du = Z(+phi) dm + dp J u, in place.  Every product and sum where it is written (contraction off), here and below, so that a
-// direction's bits depend neither on its slot in a group nor on what else the call was given.
-__device__ __forceinline__ void train_sj_in(double c, double s, double dp, const double u[3], double d[3]) {
-#pragma clang fp contract(off)
-    train_zp(c, s, d);
-    d[0] = fma(-dp, u[1], d[0]);
-    d[1] = fma(dp, u[0], d[1]);
-}
-// o = M du + dg gv - (turn ? dp J n : 0) for a column-major M: one chain of fma from the first product M[i] du[0].
-__device__ __forceinline__ void train_sj_map(const double* M, const double gv[3], const double n[3], double dg, double dp, bool turn,
-                                             const double du[3], double o[3]) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) o[i] = fma(dg, gv[i], fma(M[6 + i], du[2], fma(M[3 + i], du[1], M[i] * du[0])));
-    if (turn) {
-        o[0] = fma(dp, n[1], o[0]);
-        o[1] = fma(-dp, n[0], o[1]);
-    }
-}
+// train_sj_in and train_sj_map, the two statements of a direction's repetition, are in sim_dev.h, shared with the fused products of
+// the schedule (blochtrainschedgn.hip).
 
 // blocks: the forward table (pulse, scale, chunk of 256 points) times the direction groups (pad).  ws: the primal planes; dws: their
 // tangents in the gain, laid out alike (null: no gains direction).  rep, gidx, m0, demod: k_bloch_train_run's.  dgain / dphi (either

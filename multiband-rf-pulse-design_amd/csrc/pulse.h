@@ -224,6 +224,32 @@ void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* 
                               const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
                               const double* rw, const double* const wf[3], int ndir, const double* v_re, const double* v_im,
                               double* h_re, double* h_im);
+// Fused least-squares and Gauss-Newton products of bloch_train_batch_run in its schedule, the gain and the RF phase of every
+// repetition (blochtrainschedgn.hip k_bloch_train_run_sched_lsq, k_bloch_train_run_sched_gn, k_bloch_train_sched_gn_fold with the
+// shipped k_bloch_train_prop and k_bloch_train_prop_dgain): the inputs, weights and targets of bloch_train_lsq_batch_run /
+// bloch_train_gn_batch_run.  lsq: loss per pulse, ggain / gphi per repetition (either null: not wanted), dL/dm0 when wanted; gn:
+// dgain / dphi (either null: zeros) and hgain / hphi (either null: not wanted), direction k of pulse p at ndir roff[p] + k ntr_p.
+// One upload, three launches and the fold (the period's tangent is skipped when no gains half is given or wanted), one download.
+void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                     const double* m0z, int ebcast, const double* const w[3], const double* const t[3],
+                                     const double* rw, const double* const wf[3], const double* const tf[3], double* loss,
+                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz);
+void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                    const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                    const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                    const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                    const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                    const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                    const double* m0z, int ebcast, const double* const w[3], const double* rw,
+                                    const double* const wf[3], int ndir, const double* dgain, const double* dphi, double* hgain,
+                                    double* hphi);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1

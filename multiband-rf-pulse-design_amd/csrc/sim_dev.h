@@ -722,6 +722,51 @@ void train_launch_prop_jvp(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nw
 // tangents in the gain, laid out as the primal planes.  Shared by the schedule's adjoint and its tangent (blochtrainschedjvp.hip).
 void train_launch_prop_dgain(TrainStaged& Ts, hipStream_t st, size_t o_qb, long nwg, double* dws);
 
+// What the schedule's adjoint (blochtrainsched.hip) and tangent (blochtrainschedjvp.hip) share with the fused
+// products of the schedule (blochtrainschedgn.hip), moved here from the two files token for token.
+// a . (M (J u) - J n) for a column-major M and n = M u + meq b: a repetition's share of dL / dphi through one of its two maps.
+// Every product and sum where it is written (contraction off), so that the share has the same bits whatever else the call wants.
+__device__ __forceinline__ double train_sched_dphi(const double* M, const double a[3], const double u[3], const double n[3]) {
+#pragma clang fp contract(off)
+    double p = fma(a[1], n[0], -(a[0] * n[1]));                           // -a . J n
+    p = -p;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p = fma(a[i], fma(M[3 + i], u[0], -(M[i] * u[1])), p);
+    return p;
+}
+// a . (M (J u)) alone: the demodulated echo is not turned back, so it has no J n term.
+__device__ __forceinline__ double train_sched_dphi_demod(const double* M, const double a[3], const double u[3]) {
+#pragma clang fp contract(off)
+    double p = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) p = fma(a[i], fma(M[3 + i], u[0], -(M[i] * u[1])), p);
+    return p;
+}
+__device__ __forceinline__ double train_sched_dot(const double a[3], const double v[3]) {
+#pragma clang fp contract(off)
+    return fma(a[2], v[2], fma(a[1], v[1], a[0] * v[0]));
+}
+
+// du = Z(+phi) dm + dp J u, in place.  Every product and sum where it is written (contraction off), here and below, so that a
+// direction's bits depend neither on its slot in a group nor on what else the call was given.
+__device__ __forceinline__ void train_sj_in(double c, double s, double dp, const double u[3], double d[3]) {
+#pragma clang fp contract(off)
+    train_zp(c, s, d);
+    d[0] = fma(-dp, u[1], d[0]);
+    d[1] = fma(dp, u[0], d[1]);
+}
+// o = M du + dg gv - (turn ? dp J n : 0) for a column-major M: one chain of fma from the first product M[i] du[0].
+__device__ __forceinline__ void train_sj_map(const double* M, const double gv[3], const double n[3], double dg, double dp, bool turn,
+                                             const double du[3], double o[3]) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = fma(dg, gv[i], fma(M[6 + i], du[2], fma(M[3 + i], du[1], M[i] * du[0])));
+    if (turn) {
+        o[0] = fma(dp, n[1], o[0]);
+        o[1] = fma(-dp, n[0], o[1]);
+    }
+}
+
 // The sections the train's fused calls add after train_stage and train_vjp_stage (blochtraingn.hip train_gn_stage, t* null for gn):
 // the weights and targets, the repetitions' factors, the loss partials' offsets and the fold's table; nlp loss partials, ngf
 // workgroups of the fold.  train_launch_run_lsq and train_launch_lsq_fold launch k_bloch_train_run_lsq and k_bloch_train_gn_fold (one

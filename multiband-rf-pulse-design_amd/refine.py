@@ -12,6 +12,9 @@ taking each step as one bloch_ss_lm_step_batch call.
 refine_bloch_train_batch runs the loop on bloch_train_lsq_batch / bloch_train_gn_batch, the echoes of a pulse train (DESIGN 8ab);
 refine_bloch_train_lm_batch is that loop with both solvers, the device one taking each step as one bloch_train_lm_step_batch call
 (DESIGN 8ac).
+refine_bloch_train_sched_batch refines the train's schedule, the gain and the RF phase of every repetition, on
+bloch_train_lsq_sched_batch / bloch_train_gn_sched_batch: a schedule has 2 ntr real unknowns, so each step forms the dense H
+with one gn call and solves (H + mu I) d = -g by a Cholesky factorisation on the host instead of conjugate gradients.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -368,3 +371,114 @@ def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, r
     calls = dict(lsq=0, gn=0, lm=0) if solver == "device" else dict(lsq=0, gn=0)
     infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(calls)) for _ in range(P)]
     return _lm_loop(b1s, infos, lsq, gn, lm if solver == "device" else step, iters, mu0)
+
+
+def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), iters=5, mu0=None,
+                                   rep_weights=None, targets_final=None, weights_final=None, phases=np.pi, gains=1.0, echo=None,
+                                   scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+    """Lock-step Levenberg-Marquardt on the schedule of a pulse train, the gain and the RF phase of every repetition, with the pulses
+    held fixed: _lm_loop on bloch_train_lsq_sched_batch / bloch_train_gn_sched_batch.  pulses, df, dp, targets, weights,
+    rep_weights, targets_final, weights_final, echo, scales, m0, meq and demod as for refine_bloch_train_batch; ntr: an int, the pulses
+    of a call share it; phases / gains: the starting schedule, as bloch_train_batch takes them.  vary: ("gains", "phases"),
+    ("gains",) or ("phases",): the part that moves; the iterate is the real vector [gains; phases] restricted to it, of length n =
+    ntr x len(vary).  Each step forms H once per accepted iterate (one gn call with the n unit directions, kept while steps are
+    refused: H does not depend on mu), symmetrises it, solves (H + mu I) d = -g by a dense Cholesky factorisation on the host and
+    evaluates one lsq call at the trial.  iters and mu0 as for refine_batch (mu0 None: 1e-3 times the Rayleigh quotient <g, H g> /
+    <g, g>, one gn call).  Returns (schedules, infos): per pulse (gains, phases), float64 of shape (ntr,), and refine_batch's info
+    dict ('calls' counts 'lsq' and 'gn').  Without "gains" in vary the period's tangent is never launched.  A pulse refined in a
+    batch has the bits of the same pulse refined alone."""
+    who = "refine_bloch_train_sched_batch"
+    mb = importlib.import_module(__package__)
+    pulses = list(pulses)
+    P = len(pulses)
+    if P == 0:
+        raise ValueError("%s: no pulses" % who)
+    vg, vp = mb._sched_vary(who, vary)
+    if iters < 0:
+        raise ValueError("%s: iters must be at least 0" % who)
+    if targets is None and targets_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
+        if v is not None and len(list(v)) != P:
+            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+    n = mb._train_ints(who, "ntr", ntr, P)
+    if any(e != n[0] for e in n):
+        raise ValueError("%s: the pulses of a call must share ntr" % who)
+    if n[0] < 1:
+        raise ValueError("%s: ntr of pulse 0 must be at least 1" % who)
+    N = n[0]
+    g0 = [np.array(v, dtype=np.float64) for v in mb._train_tables(who, "gains", gains, n, False)]
+    p0 = [np.array(v, dtype=np.float64) for v in mb._train_tables(who, "phases", phases, n, True)]
+    each_m0 = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
+
+    def grid(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P and all(np.ndim(e) >= 1 for e in v) else v
+
+    def pick(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P else v
+
+    def sub(v, idx):
+        return None if v is None else [v[q] for q in idx]
+
+    def sched(q, x):
+        """the iterate of pulse q -> (gains, phases)"""
+        return (x[:N] if vg else g0[q]), (x[N:] if vg and vp else x if vp else p0[q])
+
+    def kw(idx, x_of):
+        sc = [sched(q, x_of[q]) for q in idx]
+        return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=[s[1] for s in sc],
+                    gains=[s[0] for s in sc], echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+
+    def args(idx):
+        return [pulses[q] for q in idx], grid(df, idx), grid(dp, idx), N
+
+    def halves(v):
+        return (v[..., :N] if vg else None), (v[..., N:] if vg and vp else v if vp else None)
+
+    def join(a, b):
+        return np.concatenate([v for v in (a, b) if v is not None], -1)
+
+    def lsq(idx, x_of):
+        for q in idx:
+            infos[q]["calls"]["lsq"] += 1
+        res = mb.bloch_train_lsq_sched_batch(*args(idx), sub(targets, idx), sub(weights, idx), targets_final=sub(targets_final, idx),
+                                             grad_gains=vg, grad_phases=vp, **kw(idx, x_of))
+        return [(r[0], join(r[1], r[2])) for r in res]
+
+    def gn_dirs(idx, dirs):
+        """H along dirs[q] ((n,) or (K, n)) of every pulse of idx at the current iterate, the two halves joined"""
+        for q in idx:
+            infos[q]["calls"]["gn"] += 1
+        hv = [halves(dirs[q]) for q in idx]
+        res = mb.bloch_train_gn_sched_batch(*args(idx), sub(weights, idx), tangents_gains=[h[0] for h in hv] if vg else None,
+                                            tangents_phases=[h[1] for h in hv] if vp else None, prod_gains=vg, prod_phases=vp,
+                                            **kw(idx, xs))
+        return [join(a, b) for a, b in res]
+
+    def gn(idx, v_of):
+        return gn_dirs(idx, v_of)
+
+    eye = np.eye(N * (int(vg) + int(vp)))
+    held = {}                                                                    # q -> (the iterate H was formed at, H)
+
+    def step(idx, grad, mu):
+        need = [q for q in idx if q not in held or held[q][0] is not xs[q]]
+        if need:
+            for q, H in zip(need, gn_dirs(need, {q: eye for q in need})):
+                held[q] = (xs[q], (H + H.T) / 2)
+        trial, broke = {}, {}
+        for q in idx:
+            try:
+                c = np.linalg.cholesky(held[q][1] + mu[q] * eye)
+                trial[q], broke[q] = xs[q] + np.linalg.solve(c.T, np.linalg.solve(c, -grad[q])), False
+            except np.linalg.LinAlgError:                                        # not positive definite to rounding: a refused step
+                trial[q], broke[q] = xs[q], True
+        ok = [q for q in idx if not broke[q]]
+        at = dict(zip(ok, lsq(ok, trial))) if ok else {}
+        return [(trial[q],) + (at[q] if q in at else (np.inf, grad[q])) + (broke[q],) for q in idx]
+
+    xs = [join(g0[q] if vg else None, p0[q] if vp else None) for q in range(P)]
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    xs, infos = _lm_loop(xs, infos, lsq, gn, step, iters, mu0)
+    return [tuple(np.array(v) for v in sched(q, xs[q])) for q in range(P)], infos
