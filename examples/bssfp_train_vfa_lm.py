@@ -7,7 +7,10 @@ same transverse magnetisation at the lactate points: the target is the mean over
 textbook schedule, point by point, so a flat echo train has zero loss.  Starting from that schedule it prints the schedule, the
 losses of the accepted steps and the echo amplitudes before and after.  A result, not a criterion.  No plots.
 
-    python examples/bssfp_train_vfa_lm.py [--tr 6.0] [--ntr 16] [--t1 30] [--t2 2] [--steps 5]
+    python examples/bssfp_train_vfa_lm.py [--tr 6.0] [--ntr 16] [--t1 30] [--t2 2] [--steps 5] [--solver host|device]
+
+--solver device takes the steps through mbfir.refine_bloch_train_sched_lm_batch: conjugate gradients on the
+device in the call that evaluates the trial, one call and one set of propagator sweeps per accepted step.
 """
 import argparse
 import os
@@ -24,6 +27,7 @@ ap.add_argument("--ntr", type=int, default=16)
 ap.add_argument("--t1", type=float, default=30.0, help="s")
 ap.add_argument("--t2", type=float, default=2.0, help="s")
 ap.add_argument("--steps", type=int, default=5, help="accepted Levenberg-Marquardt steps at the most")
+ap.add_argument("--solver", choices=("host", "device"), default="host", help="dense Cholesky on the host, or CG on the device")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -70,9 +74,15 @@ show("textbook schedule atan(1 / sqrt(N - k - 1))", gains)
 mx, my = echoes(gains)
 target = (mx.mean(0)[:, None], my.mean(0)[:, None], 0.0)                # (nf, npos) planes: the same at every repetition
 weights = (1.0, 1.0, 0.0)                                               # the transverse components only
-(sch,), (info,) = mbfir.refine_bloch_train_sched_batch([pulse], df, pos, N, [target], [weights], vary=("gains",), iters=args.steps,
-                                                       gains=gains, **kw)
+if args.solver == "host":
+    (sch,), (info,) = mbfir.refine_bloch_train_sched_batch([pulse], df, pos, N, [target], [weights], vary=("gains",), iters=args.steps,
+                                                           gains=gains, **kw)
+else:
+    (sch,), (info,) = mbfir.refine_bloch_train_sched_lm_batch([pulse], df, pos, N, [target], [weights], vary=("gains",),
+                                                              iters=args.steps, gains=gains, solver="device", cg=N, **kw)
 print("losses of the accepted steps: " + " ".join("%.4e" % v for v in info["losses"]))
 print("status %s, %d refused steps, last mu %.2e, device calls: %d lsq, %d gn" % (info["status"], info["refused"], info["mu"],
-                                                                                   info["calls"]["lsq"], info["calls"]["gn"]))
-show("after refine_bloch_train_sched_batch on the gains", sch[0])
+                                                                                   info["calls"]["lsq"], info["calls"]["gn"])
+      + (", %d lm" % info["calls"]["lm"] if "lm" in info["calls"] else ""))
+show("after refine_bloch_train_sched_batch on the gains" if args.solver == "host" else
+     "after refine_bloch_train_sched_lm_batch(solver='device') on the gains", sch[0])

@@ -976,6 +976,47 @@ int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff
                                     const double* tz, const double* tfx, const double* tfy, const double* tfz, double* d_re,
                                     double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
                                     double* g_im);
+/* mbfir_bloch_train_lm_step_sched_batch: the Levenberg-Marquardt step of the train's schedule, the gain and the RF phase of every
+ * repetition.  One call evaluates and solves at the same schedule, so the propagators of a schedule are computed once:
+ *   1. with targets, loss / ggain / gphi: L, dL/dgains and dL/dphases at the call's schedule, with the bits of
+ *      mbfir_bloch_train_lsq_sched_batch;
+ *   2. conjugate gradients on (H + mu[p] I) d = b from d = 0, H = J' W J restricted to the varied halves as
+ *      mbfir_bloch_train_gn_sched_batch applies it at that schedule, at most cg iterations, while <r, r> > rtol <b, b>.
+ * There is no trial at schedule + d: a trial has other gains and tables, which the host stages; evaluating the trial with the next
+ * call solves the next step at the same time.  The arguments through tfz are those of mbfir_bloch_train_lsq_sched_batch; all six
+ * target planes may be NULL (solve only; loss, ggain, gphi may then be NULL).  bgain / bphi: the right-hand side, laid out as cosphi;
+ * both NULL with targets: b = -g of 1., negated exactly and left on the device; given: used, and 1. is still returned.  dgain / dphi:
+ * the step, laid out as cosphi; either NULL marks that half as not varied (not both): its direction is zeros, its product is never
+ * read, its b and g must be NULL, and without the gains the period's tangent is not launched.  ncg, rr, gg, status per pulse as for
+ * mbfir_bloch_train_lm_step_batch (0: the tolerance was reached, 1: the cap cg was reached, 2: breakdown, a <p, (H + mu I) p> that
+ * is not finite or not > 0).  cg = 0 with targets is mbfir_bloch_train_lsq_sched_batch and d = 0.  The inner product runs over the
+ * varied halves by a fixed tree; no atomics.  H p has the bits of mbfir_bloch_train_gn_sched_batch on the same p.  One upload, a
+ * chain of launches (up to five, then two per CG iteration), one download; the host reads nothing in between.  A pulse's outputs
+ * depend only on the pulse, its grids, its train, weights, targets, m0, b, mu, cg, rtol and the scale list: not on the batch, its
+ * order, or when its neighbours stop.  The checks are those of mbfir_bloch_train_batch, then those the two calls above share at
+ * ndir = 1 (ebcast, the weights, both terms absent, both halves NULL, the sizes at two checkpointed states).  Targets are optional
+ * here, so the weights are checked in mbfir_bloch_train_gn_sched_batch's wording ("the echo weights are given together or not at
+ * all", "the final weights ...") and two of mbfir_bloch_train_lsq_sched_batch's messages cannot occur: "the echo / final weights and
+ * targets are given together or not at all" (the target messages below take its place) and "the loss plane is null" (a NULL loss
+ * with targets is "a required array is null"); "both halves NULL" reads "neither the gains nor the phases vary: dgain and dphi are
+ * both null".  Then: mu or a required output NULL ("a required array is null"); a negative or non-finite mu ("a damping mu is
+ * negative or not finite", as in mbfir_bloch_train_lm_step_batch); cg < 0; a negative or NaN rtol; sections that overflow; a b or g for a half that does
+ * not vary; a target triple only partly given, a target for a term that has no weights, or, when a target is given, none for a term
+ * that has weights; b given for one varied half only; neither targets nor b.  No device work is done before they pass.  A NULL
+ * context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                          const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                          const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                          const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                          const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                          const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                          const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
+                                          const double* wy, const double* wz, const double* tx, const double* ty, const double* tz,
+                                          const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* tfx,
+                                          const double* tfy, const double* tfz, const double* bgain, const double* bphi,
+                                          const double* mu, int cg, double rtol, double* dgain, double* dphi, int* ncg, double* rr,
+                                          double* gg, int* status, double* loss, double* ggain, double* gphi);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

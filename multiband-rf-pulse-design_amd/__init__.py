@@ -201,6 +201,10 @@ SYMBOLS = {
                                                   _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                                  [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 7 +
                                                  [_dp] * 3 + [C.c_int, C.c_double] + [_dp] * 8 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "mbfir_bloch_train_lm_step_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp,
+                                                        C.c_int, _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                       [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] +
+                                                       [_dp] * 16 + [C.c_int, C.c_double] + [_dp] * 2 + [_ip, _dp, _dp, _ip] + [_dp] * 3),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -3116,8 +3120,106 @@ def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=
     return _lm_result(rfs, out)
 
 
+def bloch_train_lm_step_sched_batch(pulses, df, dp, ntr, weights, mu, *, vary=("gains", "phases"), b=None, targets=None,
+                                    targets_final=None, cg=8, rtol=1e-6, rep_weights=None, weights_final=None, phases=np.pi, gains=1.0,
+                                    echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+    """The Levenberg-Marquardt step of a train's schedule, the gain and the RF phase of every repetition, evaluated and solved at the
+    same schedule in one device call (mbfir_bloch_train_lm_step_sched_batch), so that the propagators of a
+    schedule are swept once for both.  pulses, df, dp, ntr, weights, rep_weights, weights_final, phases, gains, echo, scales, m0, meq
+    and demod as for bloch_train_gn_sched_batch.  With targets and / or targets_final (as for bloch_train_lsq_sched_batch: one for
+    every term that has weights) the loss and the gradient at the call's schedule come back with the bits of
+    bloch_train_lsq_sched_batch.  Then conjugate gradients on (H + mu I) d = b from d = 0, H = J' W J restricted to the halves vary
+    names (("gains", "phases"), ("gains",) or ("phases",)), as bloch_train_gn_sched_batch applies it at that schedule; mu: a number
+    >= 0 or one per pulse; cg and rtol as for abr_lm_step_batch; cg = 0 evaluates only.  b: None (with targets: the negated gradient,
+    which never leaves the device) or per pulse a pair (b_gains, b_phases) of float64 (ntr,) arrays, None in the place of a half that
+    does not vary.  There is no trial at schedule + d: a trial has other gains, so its own sweeps; evaluate it with the next call,
+    which solves the next step too.  Returns a list of (d_gains, d_phases, info) per pulse, None for a half not varied; info holds
+    'ncg', 'rr', 'gg' and 'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss', 'grad_gains' and 'grad_phases' (None for a
+    half not varied).  Without "gains" in vary the period's tangent is never launched.  Deterministic: a pulse's results depend only
+    on the pulse, its grids, its train, weights, targets, m0, b, mu, cg, rtol and the scales, not on the batch or when its neighbours
+    stop."""
+    who = "bloch_train_lm_step_sched_batch"
+    vg, vp = _sched_vary(who, vary)
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr = Tn.A, Tn.ntr
+    P = A.P
+    if weights is None and weights_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    if targets is not None and weights is None:
+        raise ValueError("%s: targets are given for an echo term that has no weights" % who)
+    if targets_final is not None and weights_final is None:
+        raise ValueError("%s: targets_final are given for a final term that has no weights" % who)
+    evalu = targets is not None or targets_final is not None
+    if evalu and ((weights is not None and targets is None) or (weights_final is not None and targets_final is None)):
+        raise ValueError("%s: with targets, every term that has weights needs its own" % who)
+    if not evalu and b is None:
+        raise ValueError("%s: neither targets nor a right-hand side b is given" % who)
+    try:
+        m = _vec(np.broadcast_to(np.asarray(mu, dtype=np.float64), (P,)))
+    except ValueError:
+        raise ValueError("%s: mu must be a number or one number per pulse" % who) from None
+    if not np.all(np.isfinite(m)) or np.any(m < 0):
+        raise ValueError("%s: a damping mu is negative or not finite" % who)
+    if int(cg) != cg or cg < 0:
+        raise ValueError("%s: cg must be an integer, at least 0" % who)
+    if not rtol >= 0:
+        raise ValueError("%s: rtol is negative or not a number" % who)
+    bplanes = [None, None]
+    if b is not None:
+        b = list(b)
+        if len(b) != P:
+            raise ValueError("%s: %d right-hand sides for %d pulses" % (who, len(b), P))
+        halves = [[], []]
+        for q, pair in enumerate(b):
+            if not isinstance(pair, (tuple, list)) or len(pair) != 2:
+                raise ValueError("%s: the right-hand side of pulse %d must be a pair (b_gains, b_phases)" % (who, q))
+            for i, (name, on) in enumerate((("gains", vg), ("phases", vp))):
+                if (pair[i] is not None) != on:
+                    raise ValueError("%s: the right-hand side of pulse %d has %s for the %s, which %s" %
+                                     (who, q, "a half" if not on else "None", name, "vary" if on else "do not vary"))
+                if on:
+                    v = np.asarray(pair[i], dtype=np.float64)
+                    if v.shape != (ntr[q],):
+                        raise ValueError("%s: the %s half of the right-hand side of pulse %d has shape %s, not (%d,)" %
+                                         (who, name, q, v.shape, ntr[q]))
+                    halves[i].append(v)
+        bplanes = [_vec(np.concatenate(h)) if on else None for h, on in zip(halves, (vg, vp))]
+    nul = C.cast(None, _dp)
+    eb, w, t = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets)
+    t = [nul] * 3 if t is None else t
+    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    rw = _train_rep_weights(who, rep_weights, ntr)
+    m0p = _bloch_m0(A, m0)
+    roff = _offsets(ntr)
+    R = int(roff[-1])
+    d = [np.zeros(R) if on else None for on in (vg, vp)]
+    st = [np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
+    loss = np.zeros(P) if evalu else None
+    g = [np.zeros(R) if on and evalu else None for on in (vg, vp)]
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_lm_step_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
+                                                              *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+                                                              *[_plane(v) for v in wf + tf],
+                                                              *[_plane(nul if v is None else v) for v in bplanes], _ptr(m), int(cg),
+                                                              C.c_double(float(rtol)),
+                                                              *[_plane(nul if v is None else v) for v in d + st + [loss] + g])
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    cut = lambda v, q: None if v is None else v[roff[q]:roff[q + 1]].copy()
+    res = []
+    for q in range(P):
+        info = dict(ncg=int(st[0][q]), rr=float(st[1][q]), gg=float(st[2][q]), status=LM_STATUS[int(st[3][q])])
+        if evalu:
+            info.update(loss=float(loss[q]), grad_gains=cut(g[0], q), grad_phases=cut(g[1], q))
+        res.append((cut(d[0], q), cut(d[1], q), info))
+    return res
+
+
 from .refine import (refine_batch, refine_bloch_batch, refine_bloch_ss_batch, refine_bloch_train_batch,   # noqa: E402  (batched
-                     refine_bloch_train_lm_batch, refine_bloch_train_sched_batch)                          # Levenberg-Marquardt on the calls above)
+                     refine_bloch_train_lm_batch, refine_bloch_train_sched_batch,                          # Levenberg-Marquardt on the calls above)
+                     refine_bloch_train_sched_lm_batch)
 
 
 def jvp_group():

@@ -2439,6 +2439,64 @@ int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff
                                                  g_im));
 }
 
+// The schedule's step (blochtrainschedlm.hip): bloch_train_check, then the checks mbfir_bloch_train_lsq_sched_batch and
+// mbfir_bloch_train_gn_sched_batch at ndir = 1 share, in their order and with their messages (ebcast, the weights, both terms absent,
+// both halves absent, the sizes at two checkpointed states), bloch_lm_check's for its own arrays, mu, cg and rtol, then the halves
+// (nothing given for a half that does not vary), the targets as mbfir_bloch_train_lm_step_batch checks them, and the right-hand side.
+int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                          const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                          const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                          const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                          const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                          const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                          const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
+                                          const double* wy, const double* wz, const double* tx, const double* ty, const double* tz,
+                                          const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* tfx,
+                                          const double* tfy, const double* tfz, const double* bgain, const double* bphi,
+                                          const double* mu, int cg, double rtol, double* dgain, double* dphi, int* ncg, double* rr,
+                                          double* gg, int* status, double* loss, double* ggain, double* gphi) {
+    if (!ctx) return MBFIR_E_ARG;
+    const char* who = "bloch_train_lm_step_sched_batch";
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, arrays, ntr, roff,
+                                        cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
+        return e;
+    if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
+    const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
+    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
+    if (!dgain && !dphi) return bad("neither the gains nor the phases vary: dgain and dphi are both null");
+    const double* const w[3] = {wx, wy, wz};
+    const double* const wf[3] = {wfx, wfy, wfz};
+    if (const int e = bloch_train_sched_gn_check(ctx, who, npulse, nscale, 1, 2, ntr, roff, ncomb.data(), npoint.data(), ebcast, w, rw,
+                                                 wf))
+        return e;
+    const bool tg_e = tx || ty || tz, tg_f = tfx || tfy || tfz, targets = tg_e || tg_f;
+    const bool own = mu && ncg && rr && gg && status && (!targets || (loss && (!dgain || ggain) && (!dphi || gphi)));
+    if (const int e = bloch_lm_check(ctx, who, own, true, npulse, roff, mu, cg, rtol)) return e;
+    if ((!dgain && (bgain || ggain)) || (!dphi && (bphi || gphi)))
+        return bad("a right-hand side or a gradient is given for a half that does not vary");
+    if (tg_e && !(tx && ty && tz)) return bad("tx, ty and tz are given together or not at all");
+    if (tg_f && !(tfx && tfy && tfz)) return bad("tfx, tfy and tfz are given together or not at all");
+    if ((tg_e && !any_e) || (tg_f && !any_f)) return bad("a target is given for a term that has no weights");
+    if (targets && ((any_e && !tg_e) || (any_f && !tg_f))) return bad("a term that has weights has no target while the other has one");
+    if ((bgain || bphi) && ((dgain && !bgain) || (dphi && !bphi)))
+        return bad("the right-hand side is given for every half that varies or not at all");
+    if (!targets && !bgain && !bphi) return bad("neither targets nor a right-hand side is given");
+    const double* const t[3] = {tx, ty, tz};
+    const double* const tf[3] = {tfx, tfy, tfz};
+    MBFIR_TRY(ctx, bloch_train_lm_step_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                       tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                                       scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y,
+                                                       m0z, ebcast, w, t, rw, wf, tf, bgain, bphi, mu, cg, rtol, dgain, dphi, ncg, rr,
+                                                       gg, status, loss, ggain, gphi));
+}
+
 int mbfir_test_jvp_group(void) { return jvp_group(); }
 int mbfir_test_bloch_jvp_group(void) { return bloch_jvp_group(); }
 

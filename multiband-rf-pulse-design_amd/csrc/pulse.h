@@ -384,6 +384,24 @@ void bloch_train_lm_step_batch_run(int device, void* stream, int npulse, const l
                                    const double* b_im, const double* mu, int cg, double rtol, const double* const t[3],
                                    const double* const tf[3], double* d_re, double* d_im, int* ncg, double* rr, double* gg,
                                    int* status, double* loss, double* g_re, double* g_im);
+// The Levenberg-Marquardt step of the train's schedule on the device (blochtrainschedlm.hip k_bloch_train_lm_sched_init,
+// k_bloch_train_lm_sched_run, k_bloch_train_lm_sched_step with the shipped k_bloch_train_prop, k_bloch_train_prop_dgain and, with
+// targets, k_bloch_train_run_sched_lsq and k_bloch_train_sched_gn_fold): with targets (t[0] or tf[0] not null) the loss
+// and gradient of bloch_train_lsq_sched_batch_run at the call's schedule, then CG on (H + mu I) d = b per pulse, H as
+// bloch_train_gn_sched_batch_run applies it there, restricted to the halves whose dgain / dphi is not null; bgain / bphi both null: b
+// is the negated gradient, left on the device (loss, ggain, gphi may be null without targets).
+void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re,
+                                         const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                         const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                         const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                         const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                         const long* roff, const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                         const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                         const double* m0y, const double* m0z, int ebcast, const double* const w[3],
+                                         const double* const t[3], const double* rw, const double* const wf[3],
+                                         const double* const tf[3], const double* bgain, const double* bphi, const double* mu, int cg,
+                                         double rtol, double* dgain, double* dphi, int* ncg, double* rr, double* gg, int* status,
+                                         double* loss, double* ggain, double* gphi);
 // What mbfir_test_flip_stages adds to a search (include/mbfir.h says what each block holds): the overrides, the selected candidates
 // and the host blocks the search's per-workgroup bests, the report and the stages go to (interleaved re, im where complex).
 struct FlipStages {

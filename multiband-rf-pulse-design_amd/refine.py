@@ -15,6 +15,8 @@ refine_bloch_train_lm_batch is that loop with both solvers, the device one takin
 refine_bloch_train_sched_batch refines the train's schedule, the gain and the RF phase of every repetition, on
 bloch_train_lsq_sched_batch / bloch_train_gn_sched_batch: a schedule has 2 ntr real unknowns, so each step forms the dense H
 with one gn call and solves (H + mu I) d = -g by a Cholesky factorisation on the host instead of conjugate gradients.
+refine_bloch_train_sched_lm_batch is that loop with both solvers, the device one on bloch_train_lm_step_sched_batch, which evaluates a
+trial and solves the next step in the same call.
 Every per-pulse scalar is host arithmetic on that pulse's own numbers, and the device calls return bits that do not depend on the
 batch, so a pulse refined in a batch has the bits of the same pulse refined alone."""
 import importlib
@@ -480,5 +482,132 @@ def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
 
     xs = [join(g0[q] if vg else None, p0[q] if vp else None) for q in range(P)]
     infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0)) for _ in range(P)]
+    xs, infos = _lm_loop(xs, infos, lsq, gn, step, iters, mu0)
+    return [tuple(np.array(v) for v in sched(q, xs[q])) for q in range(P)], infos
+
+
+def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), iters=5, mu0=None,
+                                      rep_weights=None, targets_final=None, weights_final=None, phases=np.pi, gains=1.0, echo=None,
+                                      scales=(1.0,), m0=None, meq=1.0, demod=False, solver="host", cg=8, rtol=1e-6, ctx=None):
+    """refine_bloch_train_sched_batch with both solvers; arguments and return value as for that function.  solver:
+    'host' is refine_bloch_train_sched_batch, bit for bit, infos included (cg and rtol are not used).  'device' takes the steps with
+    bloch_train_lm_step_sched_batch, which evaluates and solves at the same schedule, through the same _lm_loop: the call that
+    evaluates a trial x + d also solves, speculatively, the next step at the trial with the damping the loop will use if the trial is
+    accepted (mu / 3), so an accepted iterate costs one call and one set of propagator sweeps where the host solver runs two.  The
+    speculative d is kept per pulse, keyed by the iterate and by mu; a pulse without a valid one (the first step, or after a refused
+    step) takes part in one solve-only call with b = -grad first.  cg: CG iterations per step at the most (n = ntr x len(vary)
+    reaches the exact step to rounding), stopped once |residual|^2 <= rtol |g|^2; a CG breakdown counts as a refused step.
+    'calls' then counts the fused calls under 'lm'.  The speculative solve of a call is skipped (cg = 0) when every trial in it would
+    end its pulse's refinement; in a batch whose pulses are at different steps (after refusals) a pulse on its last trial still
+    pays the cg rounds its neighbours need, and their result is dropped.  The speculative d is never part of a result, so a pulse
+    refined in a batch has the bits of the same pulse refined alone."""
+    who = "refine_bloch_train_sched_lm_batch"
+    mb = importlib.import_module(__package__)
+    if solver not in ("host", "device"):
+        raise ValueError("%s: solver must be 'host' or 'device', not %r" % (who, solver))
+    if solver == "host":
+        return refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, vary=vary, iters=iters, mu0=mu0,
+                                              rep_weights=rep_weights, targets_final=targets_final, weights_final=weights_final,
+                                              phases=phases, gains=gains, echo=echo, scales=scales, m0=m0, meq=meq, demod=demod, ctx=ctx)
+    pulses = list(pulses)
+    P = len(pulses)
+    if P == 0:
+        raise ValueError("%s: no pulses" % who)
+    vg, vp = mb._sched_vary(who, vary)
+    if iters < 0 or cg < 1:
+        raise ValueError("%s: iters must be at least 0 and cg at least 1" % who)
+    if targets is None and targets_final is None:
+        raise ValueError("%s: neither an echo term nor a final term is given" % who)
+    for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
+        if v is not None and len(list(v)) != P:
+            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+    n = mb._train_ints(who, "ntr", ntr, P)
+    if any(e != n[0] for e in n):
+        raise ValueError("%s: the pulses of a call must share ntr" % who)
+    if n[0] < 1:
+        raise ValueError("%s: ntr of pulse 0 must be at least 1" % who)
+    N = n[0]
+    g0 = [np.array(v, dtype=np.float64) for v in mb._train_tables(who, "gains", gains, n, False)]
+    p0 = [np.array(v, dtype=np.float64) for v in mb._train_tables(who, "phases", phases, n, True)]
+    each_m0 = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
+
+    def grid(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P and all(np.ndim(e) >= 1 for e in v) else v
+
+    def pick(v, idx):
+        return [v[q] for q in idx] if isinstance(v, list) and len(v) == P else v
+
+    def sub(v, idx):
+        return None if v is None else [v[q] for q in idx]
+
+    def sched(q, x):
+        """the iterate of pulse q -> (gains, phases)"""
+        return (x[:N] if vg else g0[q]), (x[N:] if vg and vp else x if vp else p0[q])
+
+    def kw(idx, x_of):
+        sc = [sched(q, x_of[q]) for q in idx]
+        return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=[s[1] for s in sc],
+                    gains=[s[0] for s in sc], echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+
+    def args(idx):
+        return [pulses[q] for q in idx], grid(df, idx), grid(dp, idx), N
+
+    def halves(v):
+        return (v[..., :N] if vg else None), (v[..., N:] if vg and vp else v if vp else None)
+
+    def join(a, b):
+        return np.concatenate([v for v in (a, b) if v is not None], -1)
+
+    def lsq(idx, x_of):
+        for q in idx:
+            infos[q]["calls"]["lsq"] += 1
+        res = mb.bloch_train_lsq_sched_batch(*args(idx), sub(targets, idx), sub(weights, idx), targets_final=sub(targets_final, idx),
+                                             grad_gains=vg, grad_phases=vp, **kw(idx, x_of))
+        return [(r[0], join(r[1], r[2])) for r in res]
+
+    def gn(idx, v_of):
+        for q in idx:
+            infos[q]["calls"]["gn"] += 1
+        hv = [halves(v_of[q]) for q in idx]
+        res = mb.bloch_train_gn_sched_batch(*args(idx), sub(weights, idx), tangents_gains=[h[0] for h in hv] if vg else None,
+                                            tangents_phases=[h[1] for h in hv] if vp else None, prod_gains=vg, prod_phases=vp,
+                                            **kw(idx, xs))
+        return [join(a, b) for a, b in res]
+
+    def lm(idx, x_of, mus, b_of, evaluate, cg=cg):
+        """one fused call over idx at the schedules x_of: [(d, info)], d the two varied halves joined"""
+        for q in idx:
+            infos[q]["calls"]["lm"] += 1
+        res = mb.bloch_train_lm_step_sched_batch(*args(idx), sub(weights, idx), [mus[q] for q in idx], vary=vary,
+                                                 b=None if b_of is None else [halves(b_of[q]) for q in idx],
+                                                 targets=sub(targets, idx) if evaluate else None,
+                                                 targets_final=sub(targets_final, idx) if evaluate else None, cg=cg, rtol=rtol,
+                                                 **kw(idx, x_of))
+        return [(join(dg, dp_), info) for dg, dp_, info in res]
+
+    held = {}                                       # q -> (the iterate the step was solved at, its mu, d, whether CG broke down)
+
+    def step(idx, grad, mu):
+        need = [q for q in idx if q not in held or held[q][0] is not xs[q] or held[q][1] != mu[q]]
+        if need:                                    # the first step, or after a refusal: solve only, b = -grad
+            for q, (d, info) in zip(need, lm(need, xs, mu, {q: -grad[q] for q in need}, False)):
+                held[q] = (xs[q], mu[q], d, info["status"] == "breakdown")
+        broke = {q: held[q][3] for q in idx}
+        trial = {q: xs[q] if broke[q] else xs[q] + held[q][2] for q in idx}
+        ok = [q for q in idx if not broke[q]]
+        at = {}
+        if ok:                                      # evaluate the trials and solve the next step at each, at the next mu
+            nxt = {q: mu[q] / 3 for q in ok}
+            # a trial that ends its pulse's refinement if accepted needs no next step: when that holds for every pulse of the call,
+            # the call evaluates only (cg is the call's, not a pulse's, so one pulse with steps left keeps the solve for all)
+            ends = all(len(infos[q]["losses"]) >= iters for q in ok)
+            for q, (d, info) in zip(ok, lm(ok, trial, nxt, None, True, 0 if ends else cg)):
+                at[q] = (info["loss"], join(info["grad_gains"], info["grad_phases"]))
+                held[q] = (trial[q], nxt[q], d, info["status"] == "breakdown")
+        return [(trial[q],) + (at[q] if q in at else (np.inf, grad[q])) + (broke[q],) for q in idx]
+
+    xs = [join(g0[q] if vg else None, p0[q] if vp else None) for q in range(P)]
+    infos = [dict(losses=[], mu=None, status="iters", refused=0, calls=dict(lsq=0, gn=0, lm=0)) for _ in range(P)]
     xs, infos = _lm_loop(xs, infos, lsq, gn, step, iters, mu0)
     return [tuple(np.array(v) for v in sched(q, xs[q])) for q in range(P)], infos
