@@ -11,8 +11,10 @@ bands left alone, with unit weights.  Two optimisers run from the designed perio
 Both move every sample of the period: the two halves are not tied to b and -b and the dead-time samples are free, which the report
 shows (a tied design takes the chain rule g_b = g[first half] - g[second half] instead, as bssfp_steady_refine.py's autograd does).
 Prints the losses, the worst in-band ranges per band and gain, and the device calls each optimiser made.  No plots.
+With --magnitude the same goal is put on (|Mxy|, mz): the designed |Mxy| and mz at gain 1.0 in the lactate band, 0 and
+1 elsewhere; the band's phase is then free.  Every call of both optimisers is made with magnitude=True.
 
-    python examples/bssfp_steady_lm.py [--iters 6] [--cg 8] [--steps 20] [--tr 6.0] [--t1 30] [--t2 2] [--solver host]
+    python examples/bssfp_steady_lm.py [--iters 6] [--cg 8] [--steps 20] [--tr 6.0] [--t1 30] [--t2 2] [--solver host] [--magnitude]
 """
 import argparse
 import os
@@ -32,6 +34,7 @@ ap.add_argument("--tr", type=float, default=6.0, help="ms")
 ap.add_argument("--t1", type=float, default=30.0, help="s")
 ap.add_argument("--t2", type=float, default=2.0, help="s")
 ap.add_argument("--solver", choices=("host", "device"), default="host", help="where the Levenberg-Marquardt step is solved")
+ap.add_argument("--magnitude", action="store_true", help="fit (|Mxy|, mz) instead of (mx, my, mz)")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -70,11 +73,14 @@ def steady(b):
 designed = steady(period0)
 target = tuple(np.where(ex[None, :], designed[c][1][None, :], 1.0 if c == 2 else 0.0)[:, :, None] * np.ones((3, 1, 1)) for c in range(3))
 weight = (1.0, 1.0, 1.0)
+mag = dict(magnitude=True) if args.magnitude else {}
+if args.magnitude:
+    target, weight = (np.hypot(target[0], target[1]), target[2]), (1.0, 1.0)
 
 
 def lsq(b):
     calls["lsq"] += 1
-    (L, g), = mbfir.bloch_ss_lsq_batch([(b,) + rest], df, 0.0, [target], [weight], scales=scales)
+    (L, g), = mbfir.bloch_ss_lsq_batch([(b,) + rest], df, 0.0, [target], [weight], scales=scales, **mag)
     return L, g
 
 
@@ -98,7 +104,7 @@ print("steady state of %d samples (%.2f ms) in TR %.2f ms, T1 %.0f s, T2 %.1f s,
 report("designed", period0)
 
 (b_lm,), (info,) = mbfir.refine_bloch_ss_batch([(period0,) + rest], df, 0.0, [target], [weight], scales=scales, iters=args.iters,
-                                               cg=args.cg, solver=args.solver)
+                                               cg=args.cg, solver=args.solver, **mag)
 print("Levenberg-Marquardt: losses %s; status %s, %d refused, last mu %.3g; device calls %s"
       % (" ".join("%.6g" % v for v in info["losses"]), info["status"], info["refused"], info["mu"], info["calls"]))
 report("Levenberg-Marquardt, %d steps" % (len(info["losses"]) - 1), b_lm)

@@ -7,8 +7,11 @@ print it) and the device calls of each run beside the calls the two-call paths o
 specsat_relax_refine.py take for the same products: two per loss and gradient (bloch_batch, bloch_vjp_batch) and two per
 Gauss-Newton product (bloch_jvp_batch, bloch_vjp_batch).  On this case Gauss-Newton does not beat L-BFGS per simulation (DESIGN
 8q); the two results are printed side by side so that this stays visible.  No plots.
+With --magnitude the fit is on (|Mxy|, mz): |sin| of the scaled flip angle beside its cosine, the same weights on
+both, every call made with magnitude=True; the printed loss is then sum w ((|Mxy| - target)^2 + (mz - target)^2).
 
     python examples/specsat_relax_lm.py [--steps 8] [--cg 12] [--lbfgs 20] [--t1 1.0] [--t2 0.06] [--wpass 1] [--n 260] [--solver host|device]
+                                        [--magnitude]
 """
 import argparse
 import math
@@ -30,6 +33,7 @@ ap.add_argument("--t2", type=float, default=0.06, help="s")
 ap.add_argument("--wpass", type=float, default=1.0, help="weight of the untouched band")
 ap.add_argument("--n", type=int, default=260)
 ap.add_argument("--solver", choices=("host", "device"), default="host", help="where the step's conjugate gradients run")
+ap.add_argument("--magnitude", action="store_true", help="fit (|Mxy|, mz) instead of mz alone")
 args = ap.parse_args()
 n, T, d1, d2 = args.n, 26.0, 0.05, 0.001                                # specsat_H1_dualband.m:4-13
 B0 = 127794577 / (42.577e6)
@@ -53,13 +57,17 @@ w = np.broadcast_to(np.repeat([1.0, args.wpass, 1.0], K)[None, :, None], target.
 gr, tp = np.zeros(len(rf0)), dt * 1e-3
 rest = (gr, tp, args.t1, args.t2, "H-1")
 targets, weights = (0.0, 0.0, target), (0.0, 0.0, w)                    # mz alone is fitted
+mag = dict(magnitude=True) if args.magnitude else {}
+if args.magnitude:
+    txy = np.stack([np.repeat([abs(math.sin(s * fa * math.pi / 180)) for fa in mb_FA], K) for s in scales])[:, :, None]
+    targets, weights = (txy, target), (w, w)
 b0 = np.asarray(rf0, dtype=np.complex128)
 
 
 
 def refine(solver):
     (b,), (i,) = mbfir.refine_bloch_batch([(b0,) + rest], df, 0.0, [targets], [weights], scales=scales, iters=args.steps, cg=args.cg,
-                                          rtol=1e-4, solver=solver)
+                                          rtol=1e-4, solver=solver, **mag)
     return b, i
 
 
@@ -85,14 +93,14 @@ evals = [0]
 def closure():
     """sum w r^2 = 2 L and its gradient from one bloch_lsq_batch call"""
     evals[0] += 1
-    (L, g), = mbfir.bloch_lsq_batch([(tb.detach().numpy(),) + rest], df, 0.0, [targets], [weights], scales=scales)
+    (L, g), = mbfir.bloch_lsq_batch([(tb.detach().numpy(),) + rest], df, 0.0, [targets], [weights], scales=scales, **mag)
     tb.grad = torch.tensor(2 * g)
     return torch.tensor(2 * L)
 
 
 opt.step(closure)
 b_lb = tb.detach().numpy()
-(L_lb, _), = mbfir.bloch_lsq_batch([(b_lb,) + rest], df, 0.0, [targets], [weights], scales=scales)
+(L_lb, _), = mbfir.bloch_lsq_batch([(b_lb,) + rest], df, 0.0, [targets], [weights], scales=scales, **mag)
 print("start                 loss %.6g" % (2 * info["losses"][0]))
 print("Levenberg-Marquardt   loss %.6g   %s; %d refused steps; the two-call paths take %s%d; peak |b1| %.5f G"
       % (2 * info["losses"][-1], count(calls), info["refused"], "at most " if "lm" in calls else "", 2 * (calls["lsq"] + calls["gn"] + (1 + args.cg) * calls.get("lm", 0)),

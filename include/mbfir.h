@@ -944,6 +944,66 @@ int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, c
                                  const double* wz, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
                                  const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
                                  double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im);
+/* Magnitude targets: the six calls mbfir_bloch_lsq_batch, mbfir_bloch_gn_batch, mbfir_bloch_lm_step_batch,
+ * mbfir_bloch_ss_lsq_batch, mbfir_bloch_ss_gn_batch and mbfir_bloch_ss_lm_step_batch each have a twin that fits the transverse
+ * magnitude |Mxy| and mz instead of the vector (mx, my, mz).  With m the end point (mode 0) or the steady state (mode 1) of a point,
+ *     rho = sqrt(mx mx + my my)   (each product, the sum and the root rounded once: np.sqrt(mx * mx + my * my) on the forward
+ *                                  call's output has its bits)
+ *     u   = (mx, my) / rho, and (0, 0) where rho = 0
+ *     L   = 1/2 sum w_xy (rho - t_xy)^2 + w_z (mz - t_z)^2
+ *     g   = J' c,      c = (w_xy (rho - t_xy) u_x, w_xy (rho - t_xy) u_y, w_z (mz - t_z))
+ *     H v = J' U' W U J v:  c = (w_xy (u . dm_xy) u_x, w_xy (u . dm_xy) u_y, w_z dm_z),  dm = J v
+ * A twin takes its component call's arguments with wx, wy, wz replaced by the pair wxy, wz and tx, ty, tz by the pair txy, tz, the
+ * planes laid out as before (O entries each); every other argument, the outputs, the launches, the transfers and the guarantees
+ * on the bits are the component call's, and so are the argument checks, their order and their messages ("only partly given"
+ * refers to the pair: "txy and tz are given together or not at all").  rho = 0 is not an error: the transverse term then adds
+ * 1/2 w_xy t_xy^2 to L and exact zeros to g and H v.  A negative t_xy is accepted.  Fitting |Mxy| alone is w_z = 0.  L and g are
+ * those of the component call at the target (t_xy u_x, t_xy u_y, t_z) with the weights (w_xy, w_xy, w_z); H is not the component
+ * call's at any weights: it drops the curvature across u. */
+int mbfir_bloch_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                              const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                              const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                              const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                              int nscale, const double* scales, const double* m0x, const double* m0y, const double* m0z,
+                              const double* wxy, const double* wz, const double* txy, const double* tz, double* loss, double* g_re,
+                              double* g_im);
+int mbfir_bloch_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                             const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                             int nscale, const double* scales, const double* m0x, const double* m0y, const double* m0z,
+                             const double* wxy, const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re,
+                             double* h_im);
+int mbfir_bloch_ss_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                 const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                 const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                 const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                 const double* dz, int nscale, const double* scales, const double* wxy, const double* wz,
+                                 const double* txy, const double* tz, double* loss, double* g_re, double* g_im, double* mx,
+                                 double* my, double* mz);
+int mbfir_bloch_ss_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                const double* dz, int nscale, const double* scales, const double* wxy, const double* wz, int ndir,
+                                const double* v_re, const double* v_im, double* h_re, double* h_im);
+int mbfir_bloch_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                  const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                  const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                  const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                  const double* dz, int nscale, const double* scales, const double* m0x, const double* m0y,
+                                  const double* m0z, const double* wxy, const double* wz, const double* b_re, const double* b_im,
+                                  const double* mu, int cg, double rtol, const double* txy, const double* tz, double* d_re,
+                                  double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                                  double* g_im);
+int mbfir_bloch_ss_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const double* wxy, const double* wz,
+                                     const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                                     const double* txy, const double* tz, double* d_re, double* d_im, int* ncg, double* rr,
+                                     double* gg, int* status, double* loss, double* g_re, double* g_im);
 /* mbfir_bloch_train_lm_step_batch: the step above for the echoes of a pulse train (mbfir_bloch_train_batch): conjugate
  * gradients on (H + mu[p] I) d = b from d = 0, H = J' W J as in mbfir_bloch_train_gn_batch at the call's b1, train, weights, rw and
  * scales (echo term, final term, the scales' and gains' chain rule), at most cg iterations, while <r, r> > rtol <b, b>.  The

@@ -88,6 +88,9 @@ _lp = C.POINTER(C.c_long)
 _lib = None
 
 # every symbol include/mbfir.h declares: name -> (restype, argtypes)
+# the context and the forward arguments of the Bloch calls, up to the scale list
+_BLOCH_HEAD = [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, _dp, _dp,
+               C.c_int, _dp]
 SYMBOLS = {
     "mbfir_create": (C.c_void_p, [C.c_int]),
     "mbfir_destroy": (None, [C.c_void_p]),
@@ -197,6 +200,15 @@ SYMBOLS = {
     "mbfir_bloch_ss_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                                _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] + [_dp] * 6 + [C.c_int, C.c_double] +
                                               [_dp] * 5 + [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    # the magnitude twins: the pairs (wxy, wz) and (txy, tz) where the calls above take triples
+    "mbfir_bloch_lsq_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 10),
+    "mbfir_bloch_gn_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 5 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_ss_lsq_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 10),
+    "mbfir_bloch_ss_gn_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 2 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_lm_step_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 8 + [C.c_int, C.c_double] + [_dp] * 4 +
+                                      [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "mbfir_bloch_ss_lm_step_mag_batch": (C.c_int, _BLOCH_HEAD + [_dp] * 5 + [C.c_int, C.c_double] + [_dp] * 4 +
+                                         [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
     "mbfir_bloch_train_lm_step_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
                                                   _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                                  [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] + [_dp] * 7 +
@@ -1684,18 +1696,20 @@ def bloch_ss_jvp_batch(pulses, df, dp, tangents, *, scales=(1.0,), ctx=None):
     return res
 
 
-def _bloch_planes(who, what, triples, A, weights=False):
+def _bloch_planes(who, what, triples, A, weights=False, magnitude=False):
     """triples: per pulse (x, y, z), each of shape (S, nf, npos), or (nf, npos) for every scale, or a scalar -> the three
-    concatenated planes of the C call in the layout of bloch_batch's mode-0 outputs"""
+    concatenated planes of the C call in the layout of bloch_batch's mode-0 outputs; magnitude: per pulse a pair (xy, z) -> the two
+    planes of the magnitude calls"""
     triples = list(triples)
+    n, form = (2, "pair (xy, z)") if magnitude else (3, "triple (x, y, z)")
     if len(triples) != A.P:
-        raise ValueError("%s: %d %s triples for %d pulses" % (who, len(triples), what, A.P))
-    planes = [[], [], []]
+        raise ValueError("%s: %d %s %ss for %d pulses" % (who, len(triples), what, form.split()[0], A.P))
+    planes = [[] for _ in range(n)]
     for q, tri in enumerate(triples):
-        if not isinstance(tri, (tuple, list)) or len(tri) != 3:
-            raise ValueError("%s: the %ss of pulse %d must be a triple (x, y, z)" % (who, what, q))
+        if not isinstance(tri, (tuple, list)) or len(tri) != n:
+            raise ValueError("%s: the %ss of pulse %d must be a %s" % (who, what, q, form))
         shape = (A.S, A.nf[q], A.npos[q])
-        for c in range(3):
+        for c in range(n):
             v = np.asarray(tri[c], dtype=np.float64)
             if v.shape != shape and v.shape != shape[1:] and v.shape != ():
                 raise ValueError("%s: a %s of pulse %d has shape %s, not %s, %s or a scalar" % (who, what, q, v.shape, shape, shape[1:]))
@@ -2140,53 +2154,57 @@ def bloch_train_jacobian_sched_batch(pulses, df, dp, ntr, **kw):
                                        tangents_phases=[np.concatenate([zero, eye])] * P, **kw)
 
 
-def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, ctx=None):
+def bloch_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, magnitude=False, ctx=None):
     """Loss and gradient of a weighted least-squares fit of bloch_batch's end point (mode 0), relaxation included, in one device
     call (mbfir_bloch_lsq_batch): pulses, df, dp, scales and m0 as for bloch_batch.  targets and weights: per
     pulse a triple (x, y, z) for (mx, my, mz), each entry of the shape (S, nf, npos) that bloch_batch returns, or (nf, npos) for
     every scale, or a scalar (weights >= 0).  Returns a list of (L, grad) per pulse: L = 1/2 sum w_c (m_c - t_c)^2 over the three
     components, the points and the scales, and grad = dL/dRe b1 + i dL/dIm b1, complex (ntime,).  Nothing of point size comes back
     from the device.  Deterministic: a pulse's L and grad bits depend only on the pulse, its grids, targets, weights, m0 and the
-    scales.  gr, tp, t1, t2, df, dp and m0 are not differentiated."""
+    scales.  gr, tp, t1, t2, df, dp and m0 are not differentiated.  magnitude: fit (|Mxy|, mz) instead of (mx, my, mz): targets and weights are then pairs (xy, z)
+    per pulse, each entry shaped as before, L = 1/2 sum w_xy (rho - t_xy)^2 + w_z (mz - t_z)^2 with rho = sqrt(mx mx + my my), and
+    weights=(w, 0) fits |Mxy| alone; rho = 0 at a point is not an error."""
     who = "bloch_lsq_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
-    t = _bloch_planes(who, "target", targets, A)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
+    t = _bloch_planes(who, "target", targets, A, magnitude=magnitude)
     T = sum(A.nt)
     loss, grad = np.zeros(A.P), [np.zeros(T) for _ in range(2)]
     m0p = _bloch_m0(A, m0)
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_lsq_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + t], _ptr(loss),
-                                              _ptr(grad[0]), _ptr(grad[1]))
+    fn = load_library().mbfir_bloch_lsq_mag_batch if magnitude else load_library().mbfir_bloch_lsq_batch
+    rc = fn(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + t], _ptr(loss), _ptr(grad[0]), _ptr(grad[1]))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
     return _lsq_result([range(n) for n in A.nt], loss, grad)
 
 
-def bloch_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), m0=None, ctx=None):
+def bloch_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), m0=None, magnitude=False, ctx=None):
     """Gauss-Newton products of the fit of bloch_lsq_batch, in one device call (mbfir_bloch_gn_batch): H v = sum_s s J_s' W_s J_s
     (s v) for J = dm / db1 (real-linear in v) and W the weights; arguments as for bloch_lsq_batch, with tangents as bloch_jvp_batch
     takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every pulse.  Returns per pulse a
     complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real inner product Re sum conj(u) v.  A product's
-    bits depend only on its pulse, grids, weights, direction, m0 and the scales: not on the batch or the direction's place among K."""
+    bits depend only on its pulse, grids, weights, direction, m0 and the scales: not on the batch or the direction's place among K.
+    magnitude: the products of bloch_lsq_batch(magnitude=True)'s fit, H = J' U' W U J with U the projection on the transverse
+    direction u = (mx, my) / rho and on z; weights are then pairs (xy, z) per pulse."""
     who = "bloch_gn_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
     rfs = [range(n) for n in A.nt]
     K, keep, vplanes = _tangents(who, tangents, rfs)
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
     h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
     m0p = _bloch_m0(A, m0)
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_gn_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w], K,
-                                             *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
+    fn = load_library().mbfir_bloch_gn_mag_batch if magnitude else load_library().mbfir_bloch_gn_batch
+    rc = fn(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w], K, *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
     return _gn_result(rfs, K, keep, h)
 
 
-def bloch_ss_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), steady=False, ctx=None):
+def bloch_ss_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), steady=False, magnitude=False, ctx=None):
     """Loss and gradient of a weighted least-squares fit of bloch_batch's steady state (mode 1) in one device call
     (mbfir_bloch_ss_lsq_batch): pulses (each one period), df, dp and scales as for bloch_ss_vjp_batch; targets and
     weights as for bloch_lsq_batch: per pulse a triple (x, y, z) for (mx, my, mz), each entry of the shape (S, nf, npos) that
@@ -2195,19 +2213,21 @@ def bloch_ss_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), stead
     (ntime,); with steady, a list of (L, grad, (mx, my, mz)), the last being the steady state with bloch_batch(mode=1)'s bits, of
     which the residual is formed.  Without steady nothing of point size comes back from the device.  There is no m0.  Deterministic:
     a pulse's L and grad bits depend only on the pulse, its grids, targets, weights and the scales.  The error grows with
-    ||(I - A)^-1||, about T1 / TR.  gr, tp, t1, t2, df and dp are not differentiated."""
+    ||(I - A)^-1||, about T1 / TR.  gr, tp, t1, t2, df and dp are not differentiated.  magnitude: as for bloch_lsq_batch, of the
+    steady state: targets and weights are pairs (xy, z) per pulse, and rho is formed of the M that steady returns."""
     who = "bloch_ss_lsq_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
     P, S, nf, npos = A.P, A.S, A.nf, A.npos
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
-    t = _bloch_planes(who, "target", targets, A)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
+    t = _bloch_planes(who, "target", targets, A, magnitude=magnitude)
     T = sum(A.nt)
     loss, grad = np.zeros(P), [np.zeros(T) for _ in range(2)]
     ooff = _offsets([S * f * k for f, k in zip(nf, npos)])
     out = [np.zeros(int(ooff[-1])) for _ in range(3)] if steady else [C.cast(None, _dp)] * 3
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_ss_lsq_batch(ctx._h, *A.head, *[_ptr(v) for v in w + t], _ptr(loss), _ptr(grad[0]),
-                                                 _ptr(grad[1]), *[_ptr(v) if steady else v for v in out])
+    fn = load_library().mbfir_bloch_ss_lsq_mag_batch if magnitude else load_library().mbfir_bloch_ss_lsq_batch
+    rc = fn(ctx._h, *A.head, *[_ptr(v) for v in w + t], _ptr(loss), _ptr(grad[0]), _ptr(grad[1]),
+            *[_ptr(v) if steady else v for v in out])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2217,22 +2237,23 @@ def bloch_ss_lsq_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), stead
     return [res[q] + (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in out),) for q in range(P)]
 
 
-def bloch_ss_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), ctx=None):
+def bloch_ss_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), magnitude=False, ctx=None):
     """Gauss-Newton products of the fit of bloch_ss_lsq_batch, in one device call (mbfir_bloch_ss_gn_batch): H v = sum_s s J_s' W_s
     J_s (s v) for J = dM / db1 of the steady state (real-linear in v) and W the weights; arguments as for bloch_ss_lsq_batch, with
     tangents as bloch_ss_jvp_batch takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every
     pulse.  Returns per pulse a complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real inner product Re
     sum conj(u) v.  A product's bits depend only on its pulse, grids, weights, direction and the scales: not on the batch or the
-    direction's place among K."""
+    direction's place among K.  magnitude: the products of bloch_ss_lsq_batch(magnitude=True)'s fit, as for bloch_gn_batch; weights
+    are then pairs (xy, z) per pulse."""
     who = "bloch_ss_gn_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
     rfs = [range(n) for n in A.nt]
     K, keep, vplanes = _tangents(who, tangents, rfs)
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
     h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_ss_gn_batch(ctx._h, *A.head, *[_ptr(v) for v in w], K, *[_ptr(v) for v in vplanes], _ptr(h[0]),
-                                                _ptr(h[1]))
+    fn = load_library().mbfir_bloch_ss_gn_mag_batch if magnitude else load_library().mbfir_bloch_ss_gn_batch
+    rc = fn(ctx._h, *A.head, *[_ptr(v) for v in w], K, *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -3015,7 +3036,8 @@ def abr2_lm_step_batch(pulses, x, y, rhs, weights, mu, *, targets=None, cg=8, rt
     return _lm_result(rfs, out)
 
 
-def bloch_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), m0=None, ctx=None):
+def bloch_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), m0=None, magnitude=False,
+                        ctx=None):
     """abr_lm_step_batch for bloch_batch's model, relaxation included (mbfir_bloch_lm_step_batch): conjugate
     gradients on (H + mu I) d = rhs from d = 0, H = sum_s s J_s' W_s J_s (s .) as bloch_gn_batch applies it, solved on the device in
     one call.  pulses, df, dp, weights, scales and m0 as for bloch_gn_batch; rhs: per pulse a complex (n,) array; mu: a number >= 0
@@ -3023,27 +3045,30 @@ def bloch_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8,
     come back too, with the bits of bloch_lsq_batch there.  Returns a list of (d, info) per pulse: info holds 'ncg', 'rr', 'gg' and
     'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.  The host reads nothing between the iterations, so
     cg is also a launch count.  Deterministic: a pulse's results depend only on the pulse, its grids, weights, targets, m0, rhs, mu,
-    cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    cg, rtol and the scales, not on the batch or when its neighbours stop.  magnitude: the step of the magnitude fit (DESIGN section
+    8ah): H as bloch_gn_batch(magnitude=True) applies it, the trial's loss and gradient with the bits of
+    bloch_lsq_batch(magnitude=True); weights and targets are then pairs (xy, z) per pulse."""
     who = "bloch_lm_step_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
     rfs = [range(n) for n in A.nt]
     bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
-    t = [None] * 3 if targets is None else _bloch_planes(who, "target", targets, A)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
+    t = [None] * len(w) if targets is None else _bloch_planes(who, "target", targets, A, magnitude=magnitude)
     P, T = A.P, sum(A.nt)
     out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
     out += [None, None, None] if targets is None else [np.zeros(P), np.zeros(T), np.zeros(T)]
     m0p = _bloch_m0(A, m0)
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_lm_step_batch(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + bplanes], _ptr(m),
-                                                  cg, C.c_double(rtol), *[_plane(v) for v in t + out])
+    fn = load_library().mbfir_bloch_lm_step_mag_batch if magnitude else load_library().mbfir_bloch_lm_step_batch
+    rc = fn(ctx._h, *A.head, *[_plane(v) for v in m0p], *[_ptr(v) for v in w + bplanes], _ptr(m), cg, C.c_double(rtol),
+            *[_plane(v) for v in t + out])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
     return _lm_result(rfs, out)
 
 
-def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), ctx=None):
+def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg=8, rtol=1e-6, scales=(1.0,), magnitude=False, ctx=None):
     """bloch_lm_step_batch for the steady state of the period, bloch_batch's mode 1 (mbfir_bloch_ss_lm_step_batch, DESIGN section
     8v): conjugate gradients on (H + mu I) d = rhs from d = 0, H = sum_s s J_s' W_s J_s (s .) as bloch_ss_gn_batch applies it, solved
     on the device in one call.  pulses (each one period), df, dp, weights and scales as for bloch_ss_gn_batch; rhs: per pulse a
@@ -3052,19 +3077,20 @@ def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg
     (d, info) per pulse: info holds 'ncg', 'rr', 'gg' and 'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.
     There is no m0.  b1 is fixed within the solve, so (I - A)^-1 and the steady state are computed once per call.  The host reads
     nothing between the iterations, so cg is also a launch count.  Deterministic: a pulse's results depend only on the pulse, its
-    grids, weights, targets, rhs, mu, cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    grids, weights, targets, rhs, mu, cg, rtol and the scales, not on the batch or when its neighbours stop.  magnitude: as for
+    bloch_lm_step_batch, on bloch_ss_gn_batch(magnitude=True) and bloch_ss_lsq_batch(magnitude=True)."""
     who = "bloch_ss_lm_step_batch"
     A = _BlochArgs(who, pulses, df, dp, scales)
     rfs = [range(n) for n in A.nt]
     bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
-    w = _bloch_planes(who, "weight", weights, A, weights=True)
-    t = [None] * 3 if targets is None else _bloch_planes(who, "target", targets, A)
+    w = _bloch_planes(who, "weight", weights, A, weights=True, magnitude=magnitude)
+    t = [None] * len(w) if targets is None else _bloch_planes(who, "target", targets, A, magnitude=magnitude)
     P, T = A.P, sum(A.nt)
     out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
     out += [None, None, None] if targets is None else [np.zeros(P), np.zeros(T), np.zeros(T)]
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_ss_lm_step_batch(ctx._h, *A.head, *[_ptr(v) for v in w + bplanes], _ptr(m), cg, C.c_double(rtol),
-                                                     *[_plane(v) for v in t + out])
+    fn = load_library().mbfir_bloch_ss_lm_step_mag_batch if magnitude else load_library().mbfir_bloch_ss_lm_step_batch
+    rc = fn(ctx._h, *A.head, *[_ptr(v) for v in w + bplanes], _ptr(m), cg, C.c_double(rtol), *[_plane(v) for v in t + out])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)

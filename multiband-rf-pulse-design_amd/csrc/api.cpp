@@ -2034,6 +2034,9 @@ int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const d
 // one), m0, the 3 O weights (O: the forward call's output entries), ndir, and that ndir times the T b1 samples, the partials (one per
 // workgroup and sample, per direction) and the checkpoints (at most 2^56 entries each) and the workgroups of the sweep and of the
 // fold (at most 2^31 - 1 each) fit.  0, or MBFIR_E_ARG with ctx->err set.
+// The six calls below have magnitude twins (mbfir_bloch_*_mag_batch) that take pairs (xy, z) where they take triples:
+// each pair of twins is one body, `mag` telling which; with it the pair lies in (wx, wy) and (tx, ty), wz and tz are null and are
+// not asked for, and every check, its place and its message are the same.
 static int bloch_gn_check(mbfir_ctx* ctx, const char* who, bool planes, const char* what, const double* m0x, const double* m0y,
                           const double* m0z, int npulse, int nscale, const double* wx, const double* wy, const double* wz, int ndir,
                           const long* toff, const long* npoint) {
@@ -2046,8 +2049,8 @@ static int bloch_gn_check(mbfir_ctx* ctx, const char* who, bool planes, const ch
         nblk += (npoint[p] + 255) / 256 * nscale;
         nfold += (toff[p + 1] - toff[p] + 255) / 256;
     }
-    for (const double* w : {wx, wy, wz})
-        for (long i = 0; i < O; ++i)
+    for (const double* w : {wx, wy, wz})                       // the magnitude calls have two planes: their wz is null
+        for (long i = 0; w && i < O; ++i)
             if (!(w[i] >= 0) || !std::isfinite(w[i])) return bad("a weight is negative or not finite");
     if (ndir < 1) return bad("ndir must be at least 1");
     if (!vjp_partials_fit(npulse, nscale, toff, npoint) || !bloch_checkpoints_fit(npulse, nscale, toff, npoint))
@@ -2063,6 +2066,27 @@ static int bloch_gn_check(mbfir_ctx* ctx, const char* who, bool planes, const ch
     return 0;
 }
 
+static int bloch_lsq_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                                const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                const double* dy, const double* dz, int nscale, const double* scales, const double* m0x,
+                                const double* m0y, const double* m0z, const double* wx, const double* wy, const double* wz,
+                                const double* tx, const double* ty, const double* tz, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, who, wx && wy && (mag || wz) && tx && ty && (mag || tz) && loss && g_re && g_im,
+                                     "a weight, target, loss or gradient plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, 1,
+                                     toff, npoint.data()))
+        return e;
+    MBFIR_TRY(ctx, bloch_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                       gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz, tx,
+                                       ty, tz, loss, g_re, g_im, mag));
+}
 int mbfir_bloch_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                           const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
                           const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
@@ -2070,84 +2094,131 @@ int mbfir_bloch_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const do
                           const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
                           const double* wz, const double* tx, const double* ty, const double* tz, double* loss, double* g_re,
                           double* g_im) {
+    return bloch_lsq_batch_call(ctx, "bloch_lsq_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma,
+                                nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz, tx, ty, tz,
+                                loss, g_re, g_im);
+}
+int mbfir_bloch_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                              const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                              const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                              const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                              int nscale, const double* scales, const double* m0x, const double* m0y, const double* m0z,
+                              const double* wxy, const double* wz, const double* txy, const double* tz, double* loss, double* g_re,
+                              double* g_im) {
+    return bloch_lsq_batch_call(ctx, "bloch_lsq_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wxy, wz, nullptr,
+                                txy, tz, nullptr, loss, g_re, g_im);
+}
+
+static int bloch_gn_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                               const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                               const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                               const long* foff, const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                               const double* dz, int nscale, const double* scales, const double* m0x, const double* m0y,
+                               const double* m0z, const double* wx, const double* wy, const double* wz, int ndir,
+                               const double* v_re, const double* v_im, double* h_re, double* h_im) {
     if (!ctx) return MBFIR_E_ARG;
     std::vector<long> npoint;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
                                         arrays, npoint))
         return e;
-    if (const int e = bloch_gn_check(ctx, "bloch_lsq_batch", wx && wy && wz && tx && ty && tz && loss && g_re && g_im,
-                                     "a weight, target, loss or gradient plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, 1,
+    if (const int e = bloch_gn_check(ctx, who, wx && wy && (mag || wz) && v_re && v_im && h_re && h_im,
+                                     "a weight, direction or product plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, ndir,
                                      toff, npoint.data()))
         return e;
-    MBFIR_TRY(ctx, bloch_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
-                                       gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz, tx,
-                                       ty, tz, loss, g_re, g_im));
+    MBFIR_TRY(ctx, bloch_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                      gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz,
+                                      ndir, v_re, v_im, h_re, h_im, mag));
 }
-
 int mbfir_bloch_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
                          const double* gy, const double* gz, const long* tsoff, const double* tsteps, const double* t1,
                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
                          const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                          const double* m0x, const double* m0y, const double* m0z, const double* wx, const double* wy,
                          const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im) {
-    if (!ctx) return MBFIR_E_ARG;
-    std::vector<long> npoint;
-    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
-                                        arrays, npoint))
-        return e;
-    if (const int e = bloch_gn_check(ctx, "bloch_gn_batch", wx && wy && wz && v_re && v_im && h_re && h_im,
-                                     "a weight, direction or product plane is null", m0x, m0y, m0z, npulse, nscale, wx, wy, wz, ndir,
-                                     toff, npoint.data()))
-        return e;
-    MBFIR_TRY(ctx, bloch_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
-                                      gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz,
-                                      ndir, v_re, v_im, h_re, h_im));
+    return bloch_gn_batch_call(ctx, "bloch_gn_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma,
+                               nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy, wz, ndir, v_re,
+                               v_im, h_re, h_im);
+}
+int mbfir_bloch_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                             const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                             int nscale, const double* scales, const double* m0x, const double* m0y, const double* m0z,
+                             const double* wxy, const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re,
+                             double* h_im) {
+    return bloch_gn_batch_call(ctx, "bloch_gn_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                               gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wxy, wz, nullptr,
+                               ndir, v_re, v_im, h_re, h_im);
 }
 
 // The steady state's least-squares products (blochssgn.hip): mbfir_bloch_batch's checks at mode 1, then the call's own
 // planes, M given whole or not at all, then bloch_gn_check's (no m0): the weights, ndir, the partials, the checkpoints and the
 // workgroup counts; gn also one plane of (I - A)^-1 per workgroup, as mbfir_bloch_ss_jvp_batch bounds it.
-int mbfir_bloch_ss_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
-                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
-                             const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
-                             const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
-                             double* mz) {
+static int bloch_ss_lsq_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                                   const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                   const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                   const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                   const double* dy, const double* dz, int nscale, const double* scales, const double* wx,
+                                   const double* wy, const double* wz, const double* tx, const double* ty, const double* tz,
+                                   double* loss, double* g_re, double* g_im, double* mx, double* my, double* mz) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_lsq_batch: ") + why; return MBFIR_E_ARG; };
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_ss_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
                                         arrays, npoint))
         return e;
-    if (!(wx && wy && wz && tx && ty && tz && loss && g_re && g_im)) return bad("a weight, target, loss or gradient plane is null");
+    if (!(wx && wy && (mag || wz) && tx && ty && (mag || tz) && loss && g_re && g_im))
+        return bad("a weight, target, loss or gradient plane is null");
     if ((mx || my || mz) && !(mx && my && mz)) return bad("mx, my and mz are given together or not at all");
-    if (const int e = bloch_gn_check(ctx, "bloch_ss_lsq_batch", true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff,
+    if (const int e = bloch_gn_check(ctx, who, true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff,
                                      npoint.data()))
         return e;
     MBFIR_TRY(ctx, bloch_ss_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
                                           t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, tx, ty, tz,
-                                          loss, g_re, g_im, mx, my, mz));
+                                          loss, g_re, g_im, mx, my, mz, mag));
+}
+int mbfir_bloch_ss_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                             const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                             const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                             const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                             int nscale, const double* scales, const double* wx, const double* wy, const double* wz,
+                             const double* tx, const double* ty, const double* tz, double* loss, double* g_re, double* g_im,
+                             double* mx, double* my, double* mz) {
+    return bloch_ss_lsq_batch_call(ctx, "bloch_ss_lsq_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                   gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, tx, ty, tz, loss,
+                                   g_re, g_im, mx, my, mz);
+}
+int mbfir_bloch_ss_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                 const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                 const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                 const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                 const double* dz, int nscale, const double* scales, const double* wxy, const double* wz,
+                                 const double* txy, const double* tz, double* loss, double* g_re, double* g_im, double* mx,
+                                 double* my, double* mz) {
+    return bloch_ss_lsq_batch_call(ctx, "bloch_ss_lsq_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                   t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wxy, wz, nullptr, txy, tz,
+                                   nullptr, loss, g_re, g_im, mx, my, mz);
 }
 
-int mbfir_bloch_ss_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
-                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
-                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
-                            const double* v_im, double* h_re, double* h_im) {
+static int bloch_ss_gn_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                                  const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                  const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                  const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                  const double* dy, const double* dz, int nscale, const double* scales, const double* wx,
+                                  const double* wy, const double* wz, int ndir, const double* v_re, const double* v_im,
+                                  double* h_re, double* h_im) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_gn_batch: ") + why; return MBFIR_E_ARG; };
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_ss_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 1,
                                         arrays, npoint))
         return e;
-    if (!(wx && wy && wz && v_re && v_im && h_re && h_im)) return bad("a weight, direction or product plane is null");
-    if (const int e = bloch_gn_check(ctx, "bloch_ss_gn_batch", true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, ndir, toff,
+    if (!(wx && wy && (mag || wz) && v_re && v_im && h_re && h_im)) return bad("a weight, direction or product plane is null");
+    if (const int e = bloch_gn_check(ctx, who, true, "", nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, ndir, toff,
                                      npoint.data()))
         return e;
     long nblk = 0;                                              // bloch_gn_check has bounded it times ndir by 2^31 - 1
@@ -2155,7 +2226,27 @@ int mbfir_bloch_ss_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const 
     if (nblk * ndir > (1L << 56) / 2304) return bad("the output size or the workgroup count overflows");
     MBFIR_TRY(ctx, bloch_ss_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
                                          t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, ndir, v_re,
-                                         v_im, h_re, h_im));
+                                         v_im, h_re, h_im, mag));
+}
+int mbfir_bloch_ss_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir,
+                            const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    return bloch_ss_gn_batch_call(ctx, "bloch_ss_gn_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                  gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, ndir, v_re, v_im,
+                                  h_re, h_im);
+}
+int mbfir_bloch_ss_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                const double* dz, int nscale, const double* scales, const double* wxy, const double* wz, int ndir,
+                                const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    return bloch_ss_gn_batch_call(ctx, "bloch_ss_gn_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2,
+                                  gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wxy, wz, nullptr, ndir, v_re,
+                                  v_im, h_re, h_im);
 }
 
 // What the least-squares calls check after abr_batch_check, in this order: their own arrays, the profile, the O weights (O: the
@@ -2312,10 +2403,11 @@ int mbfir_abr2_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* roff, const
 // on the checkpoints (96 doubles per sample) and on the fold's workgroups are the tighter ones today: the last check states what
 // this call's own sections need and does not rely on them.
 static int bloch_lm_check(mbfir_ctx* ctx, const char* who, bool arrays, bool targets_ok, int npulse, const long* toff,
-                          const double* mu, int cg, double rtol) {
+                          const double* mu, int cg, double rtol, bool mag = false) {
     auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     if (!arrays) return bad("a required array is null");
-    if (!targets_ok) return bad("tx, ty and tz are given together or not at all");
+    if (!targets_ok)
+        return bad(mag ? "txy and tz are given together or not at all" : "tx, ty and tz are given together or not at all");
     for (int p = 0; p < npulse; ++p)
         if (!(mu[p] >= 0) || !std::isfinite(mu[p])) return bad("a damping mu is negative or not finite");
     if (cg < 0) return bad("cg must be at least 0");
@@ -2325,6 +2417,33 @@ static int bloch_lm_check(mbfir_ctx* ctx, const char* who, bool arrays, bool tar
     return 0;
 }
 
+static int bloch_lm_step_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                                    const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                    const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                    const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                    const double* dy, const double* dz, int nscale, const double* scales, const double* m0x,
+                                    const double* m0y, const double* m0z, const double* wx, const double* wy, const double* wz,
+                                    const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* tx,
+                                    const double* ty, const double* tz, double* d_re, double* d_im, int* ncg, double* rr,
+                                    double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
+                                        arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, who, wx && wy && (mag || wz), "a weight, direction or product plane is null", m0x,
+                                     m0y, m0z, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
+        return e;
+    const bool targets = tx || ty || tz;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
+    if (const int e = bloch_lm_check(ctx, who, own, !targets || (tx && ty && (mag || tz)), npulse, toff, mu, cg, rtol, mag))
+        return e;
+    MBFIR_TRY(ctx, bloch_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                           t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx,
+                                           wy, wz, b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
+                                           g_im, mag));
+}
 int mbfir_bloch_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
@@ -2334,27 +2453,58 @@ int mbfir_bloch_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, cons
                               const double* mu, int cg, double rtol, const double* tx, const double* ty, const double* tz,
                               double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
                               double* g_im) {
-    if (!ctx) return MBFIR_E_ARG;
-    std::vector<long> npoint;
-    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale, 0,
-                                        arrays, npoint))
-        return e;
-    if (const int e = bloch_gn_check(ctx, "bloch_lm_step_batch", wx && wy && wz, "a weight, direction or product plane is null", m0x,
-                                     m0y, m0z, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
-        return e;
-    const bool targets = tx || ty || tz;
-    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
-    if (const int e = bloch_lm_check(ctx, "bloch_lm_step_batch", own, !targets || (tx && ty && tz), npulse, toff, mu, cg, rtol))
-        return e;
-    MBFIR_TRY(ctx, bloch_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
-                                           t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx,
-                                           wy, wz, b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
-                                           g_im));
+    return bloch_lm_step_batch_call(ctx, "bloch_lm_step_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                    t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wx, wy,
+                                    wz, b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im);
+}
+int mbfir_bloch_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                  const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                  const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                  const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                  const double* dz, int nscale, const double* scales, const double* m0x, const double* m0y,
+                                  const double* m0z, const double* wxy, const double* wz, const double* b_re, const double* b_im,
+                                  const double* mu, int cg, double rtol, const double* txy, const double* tz, double* d_re,
+                                  double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                                  double* g_im) {
+    return bloch_lm_step_batch_call(ctx, "bloch_lm_step_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1,
+                                    t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, m0x, m0y, m0z, wxy, wz,
+                                    nullptr, b_re, b_im, mu, cg, rtol, txy, tz, nullptr, d_re, d_im, ncg, rr, gg, status, loss,
+                                    g_re, g_im);
 }
 
 // The steady state's step (blochssgn.hip): mbfir_bloch_batch's checks at mode 1, bloch_gn_check's at ndir = 1 (no m0),
 // bloch_lm_check's, and one plane of (I - A)^-1 and M (12 x 256 doubles) per forward workgroup.
+static int bloch_ss_lm_step_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff, const double* b1_re,
+                                       const double* b1_im, const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                       const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                       const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                       const double* dy, const double* dz, int nscale, const double* scales, const double* wx,
+                                       const double* wy, const double* wz, const double* b_re, const double* b_im, const double* mu,
+                                       int cg, double rtol, const double* tx, const double* ty, const double* tz, double* d_re,
+                                       double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
+                                       double* g_im) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const char* why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
+    if (const int e = bloch_batch_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+                                        1, arrays, npoint))
+        return e;
+    if (const int e = bloch_gn_check(ctx, who, wx && wy && (mag || wz), "a weight, direction or product plane is null",
+                                     nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
+        return e;
+    const bool targets = tx || ty || tz;
+    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
+    if (const int e = bloch_lm_check(ctx, who, own, !targets || (tx && ty && (mag || tz)), npulse, toff, mu, cg, rtol, mag))
+        return e;
+    long nblk = 0;                                              // bloch_gn_check has bounded it by 2^31 - 1
+    for (int p = 0; p < npulse; ++p) nblk += (npoint[p] + 255) / 256 * nscale;
+    if (nblk > (1L << 56) / 3072) return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_ss_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                              t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz,
+                                              b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
+                                              g_im, mag));
+}
 int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                  const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                  const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
@@ -2363,27 +2513,22 @@ int mbfir_bloch_ss_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, c
                                  const double* wz, const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
                                  const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
                                  double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im) {
-    if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const char* why) { ctx->err = std::string("bloch_ss_lm_step_batch: ") + why; return MBFIR_E_ARG; };
-    std::vector<long> npoint;
-    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales;
-    if (const int e = bloch_batch_check(ctx, "bloch_ss_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
-                                        1, arrays, npoint))
-        return e;
-    if (const int e = bloch_gn_check(ctx, "bloch_ss_lm_step_batch", wx && wy && wz, "a weight, direction or product plane is null",
-                                     nullptr, nullptr, nullptr, npulse, nscale, wx, wy, wz, 1, toff, npoint.data()))
-        return e;
-    const bool targets = tx || ty || tz;
-    const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
-    if (const int e = bloch_lm_check(ctx, "bloch_ss_lm_step_batch", own, !targets || (tx && ty && tz), npulse, toff, mu, cg, rtol))
-        return e;
-    long nblk = 0;                                              // bloch_gn_check has bounded it by 2^31 - 1
-    for (int p = 0; p < npulse; ++p) nblk += (npoint[p] + 255) / 256 * nscale;
-    if (nblk > (1L << 56) / 3072) return bad("the output size or the workgroup count overflows");
-    MBFIR_TRY(ctx, bloch_ss_lm_step_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
-                                              t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz,
-                                              b_re, b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re,
-                                              g_im));
+    return bloch_ss_lm_step_batch_call(ctx, "bloch_ss_lm_step_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                       t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wx, wy, wz, b_re,
+                                       b_im, mu, cg, rtol, tx, ty, tz, d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im);
+}
+int mbfir_bloch_ss_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                     const double* dz, int nscale, const double* scales, const double* wxy, const double* wz,
+                                     const double* b_re, const double* b_im, const double* mu, int cg, double rtol,
+                                     const double* txy, const double* tz, double* d_re, double* d_im, int* ncg, double* rr,
+                                     double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    return bloch_ss_lm_step_batch_call(ctx, "bloch_ss_lm_step_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                       tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, wxy, wz,
+                                       nullptr, b_re, b_im, mu, cg, rtol, txy, tz, nullptr, d_re, d_im, ncg, rr, gg, status, loss,
+                                       g_re, g_im);
 }
 
 // The train's step (blochtrainlm.hip): bloch_train_check, the checks of mbfir_bloch_train_gn_batch at ndir = 1 with their

@@ -18,6 +18,12 @@
 // zero through the fold's factor.
 // LDS: the staged rows (16 KB) and the reduction tile (34 KB), as k_bloch_vjp_batch.  The staged (dnx, dny) row of gn is live only in
 // the forward sweep and the tile only after it, so the row lies in the tile's storage.
+// Magnitude twins: k_bloch_lsq_batch_mag, k_bloch_gn_batch_mag and k_bloch_lm_sweep_mag fit (|Mxy|, mz) with pairs of
+// weights (w_xy, w_z) and targets (t_xy, t_z).  They are the same sweeps with the other seed (bloch_gn_sweeps<TANGENT, MAG>;
+// sim_dev.h bloch_mag_dir, bloch_mag_seed): rho = sqrt(mx mx + my my), u = (mx, my) / rho (0 where rho = 0),
+//   lsq: c = (w_xy (rho - t_xy) u, w_z (mz - t_z));   gn: c = (w_xy (u . dm_xy) u, w_z dm_z).
+// k_bloch_lsq_batch_mag's forward step is bloch_fwd_step_batch (sim_dev.h): bloch_fwd_step with R v rounded as k_bloch_batch's own
+// sweep rounds it, so that the end point, and with it rho, has the forward call's bits.
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
@@ -30,7 +36,7 @@ namespace mbfir {
 // (lsq); vd: the ntime samples of the direction (gn).  wpart: this workgroup's ntime partials; wck: its checkpoints (at its thread);
 // lpart: its loss partial (lsq).  The staging of the rows, the checkpoints, the reverse loop and the reduction are those of
 // k_bloch_vjp_batch, whose own loops stay where they are.
-template <bool TANGENT>
+template <bool TANGENT, bool MAG = false>
 __device__ __forceinline__ void bloch_gn_sweeps(const double* __restrict__ in, const double2* __restrict__ vd, long t_off, int ntime,
                                                 double sc, double gamma, double px, double py, double pz, double dfv, bool live,
                                                 double m[3], const double w[3], const double tg[3], double2* __restrict__ wpart,
@@ -85,6 +91,8 @@ __device__ __forceinline__ void bloch_gn_sweeps(const double* __restrict__ in, c
                 dm[2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
                 rot_vec(R, m, o);
                 m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
+            } else if (MAG) {
+                bloch_fwd_step_batch(s, rotz, m);                         // the end point with bloch_batch's own bits
             } else {
                 bloch_fwd_step(s, rotz, m);
             }
@@ -92,9 +100,24 @@ __device__ __forceinline__ void bloch_gn_sweeps(const double* __restrict__ in, c
     }
     const int row = tid >> 4, ln = tid & 15;                              // reduction: 16 lanes per row of the tile
     double l[3];
-    if (TANGENT) {
+    if (TANGENT && MAG) {                                                 // the tangent branch carries the primal m beside dm
+        const BlochMagDir D = bloch_mag_dir(m[0], m[1]);
+        bloch_mag_seed(D, w, D.ux * dm[0] + D.uy * dm[1], dm[2], live, l);
+        __syncthreads();                                                  // the direction row is read no more: the tile is free
+    } else if (TANGENT) {
         l[0] = live ? w[0] * dm[0] : 0.0; l[1] = live ? w[1] * dm[1] : 0.0; l[2] = live ? w[2] * dm[2] : 0.0;
         __syncthreads();                                                  // the direction row is read no more: the tile is free
+    } else if (MAG) {
+        const BlochMagDir D = bloch_mag_dir(m[0], m[1]);
+        const double r0 = D.rho - tg[0], r2 = m[2] - tg[1];
+        bloch_mag_seed(D, w, r0, r2, live, l);
+        red[tid] = live ? 0.5 * (w[0] * (r0 * r0) + w[1] * (r2 * r2)) : 0.0;      // the loss: row 0 of the tile
+        __syncthreads();
+        double sum = 0;                                                   // every row of threads sums row 0; thread 0 stores
+        for (int k = 0; k < 16; ++k) sum += red[ln + 16 * k];
+        for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
+        if (tid == 0) *lpart = sum;
+        __syncthreads();
     } else {
         const double r0 = m[0] - tg[0], r1 = m[1] - tg[1], r2 = m[2] - tg[2];
         l[0] = live ? w[0] * r0 : 0.0; l[1] = live ? w[1] * r1 : 0.0; l[2] = live ? w[2] * r2 : 0.0;
@@ -170,13 +193,15 @@ __device__ __forceinline__ BlochGnPoint bloch_gn_point(const SimBlock& bk, const
 // k_bloch_batch writes mx / my / mz in mode 0.  vp, cks: the partials' and the checkpoints' descriptors of (pulse, direction) at
 // pulse ndir + direction (lsq: ndir = 1); lp: a pulse's first loss partial, its workgroup (scale, chunk) at scale nch + chunk.
 // v (interleaved): direction k of pulse p at ndir t_off + k ntime, as k_bloch_jvp_batch takes it.
-__global__ __launch_bounds__(256) void k_bloch_lsq_batch(const double* __restrict__ in, const double* __restrict__ df,
-                                                         const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                         const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
-                                                         const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
-                                                         const long* __restrict__ lp, const double* __restrict__ m0,
-                                                         const double* __restrict__ w, const double* __restrict__ tg, long O,
-                                                         double2* __restrict__ part, double* ck, double* __restrict__ lpart) {
+// MAG: w and tg are two planes each, (xy, z), and the seed is the magnitude fit's.
+template <bool MAG>
+__device__ __forceinline__ void bloch_lsq_body(const double* __restrict__ in, const double* __restrict__ df,
+                                               const double* __restrict__ pos3, const double* __restrict__ scales,
+                                               const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                               const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+                                               const long* __restrict__ lp, const double* __restrict__ m0,
+                                               const double* __restrict__ w, const double* __restrict__ tg, long O,
+                                               double2* __restrict__ part, double* ck, double* __restrict__ lpart) {
     const SimBlock bk = blocks[blockIdx.x];
     const BlochPulseDev P = pulses[bk.pulse];
     const VjpPulseDev V = vp[bk.pulse];
@@ -184,21 +209,39 @@ __global__ __launch_bounds__(256) void k_bloch_lsq_batch(const double* __restric
     BlochGnPoint G = bloch_gn_point(bk, P, df, pos3, m0);
     const long wg = (long)bk.scale * V.nch + bk.chunk;                   // the workgroup among its pulse's
     double wv[3] = {0, 0, 0}, tv[3] = {0, 0, 0};
-    if (G.live) {
+    if (G.live && MAG) {
+        wv[0] = w[G.o]; wv[1] = w[O + G.o];
+        tv[0] = tg[G.o]; tv[1] = tg[O + G.o];
+    } else if (G.live) {
         wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o];
         tv[0] = tg[G.o]; tv[1] = tg[O + G.o]; tv[2] = tg[2 * O + G.o];
     }
-    bloch_gn_sweeps<false>(in, nullptr, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, G.live, G.m, wv, tv,
-                           part + V.p_off + wg * V.n, ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, lpart + lp[bk.pulse] + wg);
+    bloch_gn_sweeps<false, MAG>(in, nullptr, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, G.live, G.m, wv,
+                                tv, part + V.p_off + wg * V.n, ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x,
+                                lpart + lp[bk.pulse] + wg);
+}
+__global__ __launch_bounds__(256) void k_bloch_lsq_batch(const double* __restrict__ in, const double* __restrict__ df,
+    const double* __restrict__ pos3, const double* __restrict__ scales, const BlochPulseDev* __restrict__ pulses,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const long* __restrict__ lp, const double* __restrict__ m0, const double* __restrict__ w, const double* __restrict__ tg, long O,
+    double2* __restrict__ part, double* ck, double* __restrict__ lpart) {
+    bloch_lsq_body<false>(in, df, pos3, scales, pulses, blocks, vp, cks, lp, m0, w, tg, O, part, ck, lpart);
+}
+__global__ __launch_bounds__(256) void k_bloch_lsq_batch_mag(const double* __restrict__ in, const double* __restrict__ df,
+    const double* __restrict__ pos3, const double* __restrict__ scales, const BlochPulseDev* __restrict__ pulses,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const long* __restrict__ lp, const double* __restrict__ m0, const double* __restrict__ w, const double* __restrict__ tg, long O,
+    double2* __restrict__ part, double* ck, double* __restrict__ lpart) {
+    bloch_lsq_body<true>(in, df, pos3, scales, pulses, blocks, vp, cks, lp, m0, w, tg, O, part, ck, lpart);
 }
 
-__global__ __launch_bounds__(256) void k_bloch_gn_batch(const double* __restrict__ in, const double* __restrict__ df,
-                                                        const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                        const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
-                                                        const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
-                                                        const double* __restrict__ m0, const double* __restrict__ w, long O,
-                                                        const double2* __restrict__ v, int ndir, double2* __restrict__ part,
-                                                        double* ck) {
+template <bool MAG>
+__device__ __forceinline__ void bloch_gn_body(const double* __restrict__ in, const double* __restrict__ df,
+                                              const double* __restrict__ pos3, const double* __restrict__ scales,
+                                              const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                              const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+                                              const double* __restrict__ m0, const double* __restrict__ w, long O,
+                                              const double2* __restrict__ v, int ndir, double2* __restrict__ part, double* ck) {
     const SimBlock bk = blocks[blockIdx.x];
     const BlochPulseDev P = pulses[bk.pulse];
     const VjpPulseDev V = vp[(long)bk.pulse * ndir + bk.pad];
@@ -207,11 +250,23 @@ __global__ __launch_bounds__(256) void k_bloch_gn_batch(const double* __restrict
     const long wg = (long)bk.scale * V.nch + bk.chunk;
     double wv[3] = {0, 0, 0};
     const double tv[3] = {0, 0, 0};
-    if (G.live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
-    bloch_gn_sweeps<true>(in, v + (long)ndir * P.t_off + (long)bk.pad * P.ntime, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px,
-                          G.py, G.pz, G.dfv, G.live, G.m, wv, tv, part + V.p_off + wg * V.n,
-                          ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, nullptr);
+    if (G.live && MAG) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; }
+    else if (G.live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
+    bloch_gn_sweeps<true, MAG>(in, v + (long)ndir * P.t_off + (long)bk.pad * P.ntime, P.t_off, P.ntime, scales[bk.scale], P.gamma,
+                               G.px, G.py, G.pz, G.dfv, G.live, G.m, wv, tv, part + V.p_off + wg * V.n,
+                               ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, nullptr);
 }
+#define BLOCH_GN_KERNEL(NAME, MAG)                                                                                                  \
+    __global__ __launch_bounds__(256) void NAME(                                                                                     \
+        const double* __restrict__ in, const double* __restrict__ df, const double* __restrict__ pos3,                               \
+        const double* __restrict__ scales, const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,            \
+        const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0,                       \
+        const double* __restrict__ w, long O, const double2* __restrict__ v, int ndir, double2* __restrict__ part, double* ck) {     \
+        bloch_gn_body<MAG>(in, df, pos3, scales, pulses, blocks, vp, cks, m0, w, O, v, ndir, part, ck);                              \
+    }
+BLOCH_GN_KERNEL(k_bloch_gn_batch, false)
+BLOCH_GN_KERNEL(k_bloch_gn_batch_mag, true)
+#undef BLOCH_GN_KERNEL
 
 // out[r_off + t] = (-(gamma dt_t) X, +(gamma dt_t) Y), (X, Y) = k_bloch_vjp_fold's sum of the partials of one (pulse, direction):
 // one thread per sample, one workgroup per (pulse, direction, 256 samples) from its own table (SimBlock: entry of vp, 0, chunk of
@@ -248,13 +303,14 @@ __global__ __launch_bounds__(256) void k_bloch_gn_fold(const double2* __restrict
 
 // The sweeps of k_bloch_gn_batch at ndir = 1 for the pulses that still run: the forward call's block table, the direction the
 // device's p (laid out as b1 is).
-__global__ __launch_bounds__(256) void k_bloch_lm_sweep(const double* __restrict__ in, const double* __restrict__ df,
-                                                        const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                        const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
-                                                        const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
-                                                        const double* __restrict__ m0, const double* __restrict__ w, long O,
-                                                        const double2* __restrict__ v, const LmState* __restrict__ st,
-                                                        double2* __restrict__ part, double* ck) {
+template <bool MAG>
+__device__ __forceinline__ void bloch_lm_sweep_body(const double* __restrict__ in, const double* __restrict__ df,
+                                                    const double* __restrict__ pos3, const double* __restrict__ scales,
+                                                    const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,
+                                                    const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+                                                    const double* __restrict__ m0, const double* __restrict__ w, long O,
+                                                    const double2* __restrict__ v, const LmState* __restrict__ st,
+                                                    double2* __restrict__ part, double* ck) {
     const SimBlock bk = blocks[blockIdx.x];
     if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
     const BlochPulseDev P = pulses[bk.pulse];
@@ -264,10 +320,23 @@ __global__ __launch_bounds__(256) void k_bloch_lm_sweep(const double* __restrict
     const long wg = (long)bk.scale * V.nch + bk.chunk;
     double wv[3] = {0, 0, 0};
     const double tv[3] = {0, 0, 0};
-    if (G.live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
-    bloch_gn_sweeps<true>(in, v + P.t_off, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, G.live, G.m, wv, tv,
-                          part + V.p_off + wg * V.n, ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, nullptr);
+    if (G.live && MAG) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; }
+    else if (G.live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
+    bloch_gn_sweeps<true, MAG>(in, v + P.t_off, P.t_off, P.ntime, scales[bk.scale], P.gamma, G.px, G.py, G.pz, G.dfv, G.live, G.m, wv,
+                               tv, part + V.p_off + wg * V.n, ck + K.c_off + wg * K.ng * BLOCH_CK + threadIdx.x, nullptr);
 }
+#define BLOCH_LM_SWEEP_KERNEL(NAME, MAG)                                                                                            \
+    __global__ __launch_bounds__(256) void NAME(                                                                                     \
+        const double* __restrict__ in, const double* __restrict__ df, const double* __restrict__ pos3,                               \
+        const double* __restrict__ scales, const BlochPulseDev* __restrict__ pulses, const SimBlock* __restrict__ blocks,            \
+        const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0,                       \
+        const double* __restrict__ w, long O, const double2* __restrict__ v, const LmState* __restrict__ st,                         \
+        double2* __restrict__ part, double* ck) {                                                                                    \
+        bloch_lm_sweep_body<MAG>(in, df, pos3, scales, pulses, blocks, vp, cks, m0, w, O, v, st, part, ck);                          \
+    }
+BLOCH_LM_SWEEP_KERNEL(k_bloch_lm_sweep, false)
+BLOCH_LM_SWEEP_KERNEL(k_bloch_lm_sweep_mag, true)
+#undef BLOCH_LM_SWEEP_KERNEL
 
 // k_lm_step (simgn.hip) with H p of sample t formed as k_bloch_gn_fold forms it: one CG iteration of one pulse per workgroup, after
 // its sweep.  H p = (-(f X), f Y), (X, Y) = abr_vjp_fold_sum of the partials and f = gamma dt_t; ap = H p + mu p (kept in hp),
@@ -338,11 +407,13 @@ __global__ __launch_bounds__(256) void k_bloch_lm_trial(const double* __restrict
 // to a whole double2), then the partials, the loss partials and the checkpoints, which stay on the device.
 // The sections the least-squares calls add to the forward staging, filled (pointers into B.S taken before this are stale), and the
 // sizes of what stays on the device.  tg null: no targets; v_re null: no directions, and the sweep's table is the forward one.
+// mag: the magnitude fits' pairs (xy, z) in w[0], w[1] and tg[0], tg[1]: two planes per section.
 BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int nscale, const double* const w[3],
-                               const double* const tg[3], int ndir, const double* v_re, const double* v_im) {
+                               const double* const tg[3], int ndir, const double* v_re, const double* v_im, bool mag) {
     Staging& S = B.S;
     BlochGnSections G;
     const long O = B.O, T = toff[npulse];
+    const int nplane = mag ? 2 : 3;
     std::vector<VjpPulseDev> vp((size_t)npulse * ndir);
     std::vector<BlochCkDev> ck((size_t)npulse * ndir);
     std::vector<long> lp(npulse);
@@ -358,15 +429,15 @@ BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int
         }
         G.nfold += (long)ndir * ((n + 255) / 256);
     }
-    G.o_w = S.add((size_t)O * 24);
-    if (tg) G.o_t = S.add((size_t)O * 24);
+    G.o_w = S.add((size_t)O * 8 * nplane);
+    if (tg) G.o_t = S.add((size_t)O * 8 * nplane);
     if (v_re) G.o_v = S.add((size_t)ndir * T * 16);
     G.o_vp = S.add(vp.size() * sizeof(VjpPulseDev));
     G.o_ck = S.add(ck.size() * sizeof(BlochCkDev));
     G.o_lp = S.add(npulse * sizeof(long));
     G.o_fb = S.add(G.nfold * sizeof(SimBlock));
     G.o_jb = v_re ? sim_group_table(S, ndir) : S.o_bk;
-    for (int c = 0; c < 3; ++c) {
+    for (int c = 0; c < nplane; ++c) {
         std::copy(w[c], w[c] + O, S.at<double>(G.o_w) + c * O);
         if (tg) std::copy(tg[c], tg[c] + O, S.at<double>(G.o_t) + c * O);
     }
@@ -401,9 +472,10 @@ void bloch_lm_trial_launch(hipStream_t st, const double* in, const double2* d, l
 namespace {
 // k_bloch_lsq_batch on the input rows `in` (the staged ones, or a trial's) and the fold into grad and loss.
 void bloch_lsq_launch(BlochStaged& B, const BlochGnSections& G, int nscale, const double* in, double2* part, double* cks,
-                      double* lpart, double2* grad, double* loss, hipStream_t st) {
+                      double* lpart, double2* grad, double* loss, hipStream_t st, bool mag) {
     Staging& S = B.S;
-    hipLaunchKernelGGL(k_bloch_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+    hipLaunchKernelGGL(mag ? k_bloch_lsq_batch_mag : k_bloch_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, in,
+                       S.dev<const double>(B.o_df),
                        S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                        S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(G.o_vp), S.dev<const BlochCkDev>(G.o_ck),
                        S.dev<const long>(G.o_lp), S.dev<const double>(B.o_m0), S.dev<const double>(G.o_w),
@@ -418,7 +490,7 @@ void bloch_gn_run(int device, void* stream, int npulse, const long* toff, const 
                   const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
                   const double* dx, const double* dy, const double* dz, int nscale, const double* scales, const double* m0x,
                   const double* m0y, const double* m0z, const double* const w[3], const double* const tg[3], int ndir,
-                  const double* v_re, const double* v_im, double* loss, double* o_re, double* o_im) {
+                  const double* v_re, const double* v_im, double* loss, double* o_re, double* o_im, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool lsq = tg != nullptr;
@@ -426,7 +498,7 @@ void bloch_gn_run(int device, void* stream, int npulse, const long* toff, const 
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     Staging& S = B.S;
-    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, tg, ndir, v_re, v_im);
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, tg, ndir, v_re, v_im, mag);
     const long O = B.O;
     const long R = (long)ndir * toff[npulse], nl = lsq ? (npulse + 1) / 2 : 0;      // double2 entries of the results and of the losses
     S.upload(((size_t)R + nl + G.npart) * 16 + ((size_t)(lsq ? G.nlp : 0) + G.nck) * 8, st);
@@ -436,9 +508,10 @@ void bloch_gn_run(int device, void* stream, int npulse, const long* toff, const 
     double* lpart = reinterpret_cast<double*>(part + G.npart);
     double* cks = lpart + (lsq ? G.nlp : 0);
     if (lsq) {
-        bloch_lsq_launch(B, G, nscale, S.dev<const double>(B.o_in), part, cks, lpart, res, dloss, st);
+        bloch_lsq_launch(B, G, nscale, S.dev<const double>(B.o_in), part, cks, lpart, res, dloss, st, mag);
     } else {
-        hipLaunchKernelGGL(k_bloch_gn_batch, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, S.dev<const double>(B.o_in),
+        hipLaunchKernelGGL(mag ? k_bloch_gn_batch_mag : k_bloch_gn_batch, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st,
+                           S.dev<const double>(B.o_in),
                            S.dev<const double>(B.o_df), S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc),
                            S.dev<const BlochPulseDev>(S.o_pd), S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp),
                            S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(B.o_m0), S.dev<const double>(G.o_w), O,
@@ -460,11 +533,11 @@ void bloch_lsq_batch_run(int device, void* stream, int npulse, const long* toff,
                          int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                          const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                          const double* wy, const double* wz, const double* tx, const double* ty, const double* tz, double* loss,
-                         double* g_re, double* g_im) {
+                         double* g_re, double* g_im, bool mag) {
     const double* const w[3] = {wx, wy, wz};
     const double* const tg[3] = {tx, ty, tz};
     bloch_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff,
-                 dx, dy, dz, nscale, scales, m0x, m0y, m0z, w, tg, 1, nullptr, nullptr, loss, g_re, g_im);
+                 dx, dy, dz, nscale, scales, m0x, m0y, m0z, w, tg, 1, nullptr, nullptr, loss, g_re, g_im, mag);
 }
 
 void bloch_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
@@ -473,10 +546,10 @@ void bloch_gn_batch_run(int device, void* stream, int npulse, const long* toff, 
                         int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                         const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                         const double* wy, const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re,
-                        double* h_im) {
+                        double* h_im, bool mag) {
     const double* const w[3] = {wx, wy, wz};
     bloch_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff,
-                 dx, dy, dz, nscale, scales, m0x, m0y, m0z, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im);
+                 dx, dy, dz, nscale, scales, m0x, m0y, m0z, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im, mag);
 }
 
 // Host side of mbfir_bloch_lm_step_batch (arguments checked by api.cpp): the forward staging and bloch_gn_stage at ndir = 1 with b as
@@ -492,7 +565,7 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
                              const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                              const double* wy, const double* wz, const double* b_re, const double* b_im, const double* mu, int cg,
                              double rtol, const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
-                             double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im) {
+                             double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool trial = tx != nullptr;
@@ -502,7 +575,7 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     Staging& S = B.S;
-    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im);
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im, mag);
     const size_t o_mu = S.add((size_t)npulse * 8);
     std::copy(mu, mu + npulse, S.at<double>(o_mu));
     const long T = toff[npulse];
@@ -526,7 +599,8 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
     const double* in = S.dev<const double>(B.o_in);
     lm_init_launch(st, npulse, vp, S.dev<const double>(o_mu), cg, rtol, p, d, r, state);
     for (int k = 0; k < cg; ++k) {                                // rounds of a pulse that has stopped are early exits
-        hipLaunchKernelGGL(k_bloch_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+        hipLaunchKernelGGL(mag ? k_bloch_lm_sweep_mag : k_bloch_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in,
+                           S.dev<const double>(B.o_df),
                            S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                            S.dev<const SimBlock>(G.o_jb), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(B.o_m0),
                            S.dev<const double>(G.o_w), B.O, p, state, part, cks);
@@ -535,7 +609,7 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
     }
     if (trial) {
         hipLaunchKernelGGL(k_bloch_lm_trial, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, st, in, d, T, rows);
-        bloch_lsq_launch(B, G, nscale, rows, part, cks, lpart, grad, dloss, st);
+        bloch_lsq_launch(B, G, nscale, rows, part, cks, lpart, grad, dloss, st, mag);
     }
     std::vector<char> h(b_down);
     S.download(h.data(), b_down, st);

@@ -20,6 +20,9 @@
 // and the tile only after it, so the row lies in the tile's storage.
 // The Levenberg-Marquardt step solved on the device with these products (k_bloch_ss_lm_prep, k_bloch_ss_lm_sweep and
 // the host side of mbfir_bloch_ss_lm_step_batch) follows the two kernels.
+// The three sweep kernels lie in blochssgn_kernels.inc, which is included twice: as the component fits above, and as the magnitude
+// fits of (|Mxy|, mz) (k_bloch_ss_lsq_batch_mag, k_bloch_ss_gn_batch_mag, k_bloch_ss_lm_sweep_mag), which differ in the
+// block that makes c: c = (w_xy (rho - t_xy) u, w_z (M_z - t_z)) or (w_xy (u . dM_xy) u, w_z dM_z), rho = |M_xy|, u = M_xy / rho.
 #include "dev_common.h"
 #include "pulse.h"
 #include "sim_dev.h"
@@ -88,162 +91,6 @@ __device__ __forceinline__ void bloch_ss_reverse(double (*sst)[8], double* red, 
     }
 }
 
-// in, df, pos3, scales, pulses, blocks, vp, cks, part, ck, mx / my / mz: k_bloch_ss_vjp_batch's.  w, tg: three planes of O entries
-// each (x, y, z), laid out as k_bloch_batch writes mx / my / mz in mode 1.  lp: a pulse's first loss partial, its workgroup (scale,
-// chunk) at scale nch + chunk.
-__global__ __launch_bounds__(256) void k_bloch_ss_lsq_batch(const double* __restrict__ in, const double* __restrict__ df,
-                                                            const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                            const BlochPulseDev* __restrict__ pulses,
-                                                            const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp,
-                                                            const BlochCkDev* __restrict__ cks, const long* __restrict__ lp,
-                                                            const double* __restrict__ w, const double* __restrict__ tg, long O,
-                                                            double2* __restrict__ part, double* ck, double* __restrict__ lpart,
-                                                            double* __restrict__ mx, double* __restrict__ my,
-                                                            double* __restrict__ mz) {
-    __shared__ double sst[BLOCH_CH][8];
-    __shared__ __align__(16) double red[2 * VJP_T * VJP_ROW];
-    static_assert(BLOCH_CH % VJP_T == 0, "a group of samples lies within one staged tile");
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const VjpPulseDev V = vp[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const double sc = scales[bk.scale], gamma = P.gamma;
-    const int ntime = P.ntime;
-    const BlochSsPoint G = bloch_ss_point(bk, P, df, pos3);
-    const double px = G.px, py = G.py, pz = G.pz, dfv = G.dfv;
-    const bool live = G.live;
-    const long wg = (long)bk.scale * V.nch + bk.chunk;                   // the workgroup among its pulse's
-    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
-    // a thread past the end of the grid sweeps the first point with a zero seed and contributes exact zeros
-    double m[3], l[3];
-    {
-        double inv[9];
-        bloch_ss_pass0(sst, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, inv, m);
-        double wv[3] = {0, 0, 0}, tv[3] = {0, 0, 0};
-        if (live) {
-            wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o];
-            tv[0] = tg[G.o]; tv[1] = tg[O + G.o]; tv[2] = tg[2 * O + G.o];
-        }
-        const double r0 = m[0] - tv[0], r1 = m[1] - tv[1], r2 = m[2] - tv[2];      // the residual of mode 1's own M
-        const double c0 = live ? wv[0] * r0 : 0.0, c1 = live ? wv[1] * r1 : 0.0, c2 = live ? wv[2] * r2 : 0.0;
-        for (int j = 0; j < 3; ++j) l[j] = inv[3 * j] * c0 + inv[3 * j + 1] * c1 + inv[3 * j + 2] * c2;      // lambda = inv' c
-        red[tid] = live ? 0.5 * (wv[0] * (r0 * r0) + wv[1] * (r1 * r1) + wv[2] * (r2 * r2)) : 0.0;      // the loss: row 0 of the tile
-    }
-    if (live && mx) { mx[G.o] = m[0]; my[G.o] = m[1]; mz[G.o] = m[2]; }
-    {
-        __syncthreads();
-        const int ln = tid & 15;
-        double sum = 0;                                                   // every row of threads sums row 0; thread 0 stores
-        for (int k = 0; k < 16; ++k) sum += red[ln + 16 * k];
-        for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
-        if (tid == 0) lpart[lp[bk.pulse] + wg] = sum;
-        __syncthreads();
-    }
-    const int tlast = (ntime - 1) / BLOCH_CH * BLOCH_CH;
-    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-        if (t0 != tlast || t0 != 0) bloch_ss_stage(sst, in, P.t_off, ntime, t0, sc, gamma);      // pass 0 left the last tile staged
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (VJP_T - 1)) == 0) {                                 // m before sample t0 + q: the group's checkpoint
-                double* c = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
-                c[0] = m[0]; c[256] = m[1]; c[512] = m[2];
-            }
-            const double* s = sst[q];
-            bloch_fwd_step(s, bloch_rotz(s, px, py, pz, dfv), m);
-        }
-    }
-    bloch_ss_reverse(sst, red, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, live, l, part + V.p_off + wg * V.n, wck);
-}
-
-// As k_bloch_ss_lsq_batch without targets; blocks: the forward table repeated per direction, the direction in SimBlock::pad; vp,
-// cks: the descriptors of (pulse, direction) at pulse ndir + direction; v (interleaved): direction k of pulse p at ndir t_off + k
-// ntime, as k_bloch_jvp_batch takes it; sinv: BLOCH_SSINV doubles per workgroup, written and read back coalesced by the same thread.
-__global__ __launch_bounds__(256) void k_bloch_ss_gn_batch(const double* __restrict__ in, const double* __restrict__ df,
-                                                           const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                           const BlochPulseDev* __restrict__ pulses,
-                                                           const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp,
-                                                           const BlochCkDev* __restrict__ cks, const double* __restrict__ w, long O,
-                                                           const double2* __restrict__ v, int ndir, double2* __restrict__ part,
-                                                           double* ck, double* sinv) {
-    __shared__ double sst[BLOCH_CH][8];
-    __shared__ __align__(16) double red[2 * VJP_T * VJP_ROW];
-    static_assert(BLOCH_CH % VJP_T == 0, "a group of samples lies within one staged tile");
-    static_assert(sizeof(double2) * BLOCH_CH <= sizeof(double) * 2 * VJP_T * VJP_ROW, "the direction row fits in the tile");
-    double2* sdn = reinterpret_cast<double2*>(red);                   // (dnx, dny) of the staged rows: forward sweep only
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const VjpPulseDev V = vp[(long)bk.pulse * ndir + bk.pad];
-    const BlochCkDev K = cks[(long)bk.pulse * ndir + bk.pad];
-    const double sc = scales[bk.scale], gamma = P.gamma;
-    const int ntime = P.ntime;
-    const BlochSsPoint G = bloch_ss_point(bk, P, df, pos3);
-    const double px = G.px, py = G.py, pz = G.pz, dfv = G.dfv;
-    const bool live = G.live;
-    const long wg = (long)bk.scale * V.nch + bk.chunk;
-    const double2* vd = v + (long)ndir * P.t_off + (long)bk.pad * ntime;
-    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
-    double* winv = sinv + (long)blockIdx.x * BLOCH_SSINV + tid;
-    double m[3], dm[3] = {0, 0, 0};
-    {
-        double inv[9];
-        bloch_ss_pass0(sst, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, inv, m);
-        for (int e = 0; e < 9; ++e) winv[e * 256] = inv[e];               // read back by this thread alone
-    }
-    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-        __syncthreads();
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        if (tid < cnt) {
-            const double* s = in + BLOCH_IN * (P.t_off + t0 + tid);
-            const double dt = s[8];
-            sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                  // rotx of the pulse b1 s, as k_bloch_batch forms it
-            sst[tid][1] = ((s[1] * sc) * gamma) * dt;                     // roty
-            for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
-            const double2 d = vd[t0 + tid];
-            sdn[tid] = make_double2(((-(d.x * sc)) * gamma) * dt, ((d.y * sc) * gamma) * dt);      // as k_bloch_jvp_batch stages it
-        }
-        __syncthreads();
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (VJP_T - 1)) == 0) {                                 // m before sample t0 + q: the group's checkpoint
-                double* c = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
-                c[0] = m[0]; c[256] = m[1]; c[512] = m[2];
-            }
-            const double* s = sst[q];
-            const double rotz = bloch_rotz(s, px, py, pz, dfv);
-            Rot3 R;
-            BlochTrig tr;
-            bloch_rotmat_trig<true>(s[0], s[1], rotz, R, tr);
-            const double e1 = s[6], e2 = s[7];
-            BlochJvpShared W;
-            bloch_jvp_shared(s[0], s[1], rotz, tr, m, W);
-            const double2 dn = sdn[q];
-            const double nd = s[0] * dn.x + s[1] * dn.y;
-            double o[3];
-            rot_vec(R, dm, o);
-            dm[0] = e2 * (o[0] + (nd * W.U[0] + dn.x * W.Vx[0] + dn.y * W.Vy[0]));
-            dm[1] = e2 * (o[1] + (nd * W.U[1] + dn.x * W.Vx[1] + dn.y * W.Vy[1]));
-            dm[2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
-            rot_vec(R, m, o);
-            m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
-        }
-    }
-    double l[3];
-    {
-        double inv[9], wv[3] = {0, 0, 0};
-        for (int e = 0; e < 9; ++e) inv[e] = winv[e * 256];
-        if (live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
-        double c[3];
-        for (int i = 0; i < 3; ++i) {
-            const double d = inv[i] * dm[0] + inv[3 + i] * dm[1] + inv[6 + i] * dm[2];      // dM = inv d
-            c[i] = live ? wv[i] * d : 0.0;
-        }
-        for (int j = 0; j < 3; ++j) l[j] = inv[3 * j] * c[0] + inv[3 * j + 1] * c[1] + inv[3 * j + 2] * c[2];      // lambda = inv' c
-    }
-    __syncthreads();                                                      // the direction row is read no more: the tile is free
-    bloch_ss_reverse(sst, red, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, live, l, part + V.p_off + wg * V.n, wck);
-}
-
 // ------------------------------------------------------------------------------------------------
 // The Levenberg-Marquardt step of the steady state on the device, the twin of blochgn.hip's: conjugate
 // gradients on (H + mu I) d = b per pulse, H p by the sweep of k_bloch_ss_gn_batch on the device's own p, everything else of an
@@ -273,91 +120,19 @@ __global__ __launch_bounds__(256) void k_bloch_ss_lm_prep(const double* __restri
     for (int e = 0; e < 3; ++e) wpl[(9 + e) * 256] = m[e];
 }
 
-// k_bloch_ss_gn_batch at ndir = 1 for the pulses that still run, pass 0 taken from k_bloch_ss_lm_prep's plane: the forward call's
-// block table, the direction the device's p (laid out as b1 is).  The forward loop stages every tile itself, as the shipped one
-// does; the loop, the cotangent and the reverse sweep are the shipped kernel's statements.
-__global__ __launch_bounds__(256) void k_bloch_ss_lm_sweep(const double* __restrict__ in, const double* __restrict__ df,
-                                                           const double* __restrict__ pos3, const double* __restrict__ scales,
-                                                           const BlochPulseDev* __restrict__ pulses,
-                                                           const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp,
-                                                           const BlochCkDev* __restrict__ cks, const double* __restrict__ w, long O,
-                                                           const double2* __restrict__ v, const LmState* __restrict__ st,
-                                                           double2* __restrict__ part, double* ck,
-                                                           const double* __restrict__ plane) {
-    __shared__ double sst[BLOCH_CH][8];
-    __shared__ __align__(16) double red[2 * VJP_T * VJP_ROW];
-    static_assert(BLOCH_CH % VJP_T == 0, "a group of samples lies within one staged tile");
-    static_assert(sizeof(double2) * BLOCH_CH <= sizeof(double) * 2 * VJP_T * VJP_ROW, "the direction row fits in the tile");
-    double2* sdn = reinterpret_cast<double2*>(red);                   // (dnx, dny) of the staged rows: forward sweep only
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
-    const BlochPulseDev P = pulses[bk.pulse];
-    const VjpPulseDev V = vp[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const double sc = scales[bk.scale], gamma = P.gamma;
-    const int ntime = P.ntime;
-    const BlochSsPoint G = bloch_ss_point(bk, P, df, pos3);
-    const double px = G.px, py = G.py, pz = G.pz, dfv = G.dfv;
-    const bool live = G.live;
-    const long wg = (long)bk.scale * V.nch + bk.chunk;
-    const double2* vd = v + P.t_off;
-    double* wck = ck + K.c_off + wg * K.ng * BLOCH_CK + tid;
-    const double* wpl = plane + (long)blockIdx.x * BLOCH_SSLM_PLANE + tid;
-    double m[3], dm[3] = {0, 0, 0};
-    for (int e = 0; e < 3; ++e) m[e] = wpl[(9 + e) * 256];               // M of pass 0, written by this thread of the prep launch
-    for (int t0 = 0; t0 < ntime; t0 += BLOCH_CH) {
-        __syncthreads();
-        const int cnt = min(BLOCH_CH, ntime - t0);
-        if (tid < cnt) {
-            const double* s = in + BLOCH_IN * (P.t_off + t0 + tid);
-            const double dt = s[8];
-            sst[tid][0] = ((-(s[0] * sc)) * gamma) * dt;                  // rotx of the pulse b1 s, as k_bloch_batch forms it
-            sst[tid][1] = ((s[1] * sc) * gamma) * dt;                     // roty
-            for (int e = 2; e < 8; ++e) sst[tid][e] = s[e];
-            const double2 d = vd[t0 + tid];
-            sdn[tid] = make_double2(((-(d.x * sc)) * gamma) * dt, ((d.y * sc) * gamma) * dt);      // as k_bloch_jvp_batch stages it
-        }
-        __syncthreads();
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (VJP_T - 1)) == 0) {                                 // m before sample t0 + q: the group's checkpoint
-                double* c = wck + (long)((t0 + q) / VJP_T) * BLOCH_CK;
-                c[0] = m[0]; c[256] = m[1]; c[512] = m[2];
-            }
-            const double* s = sst[q];
-            const double rotz = bloch_rotz(s, px, py, pz, dfv);
-            Rot3 R;
-            BlochTrig tr;
-            bloch_rotmat_trig<true>(s[0], s[1], rotz, R, tr);
-            const double e1 = s[6], e2 = s[7];
-            BlochJvpShared W;
-            bloch_jvp_shared(s[0], s[1], rotz, tr, m, W);
-            const double2 dn = sdn[q];
-            const double nd = s[0] * dn.x + s[1] * dn.y;
-            double o[3];
-            rot_vec(R, dm, o);
-            dm[0] = e2 * (o[0] + (nd * W.U[0] + dn.x * W.Vx[0] + dn.y * W.Vy[0]));
-            dm[1] = e2 * (o[1] + (nd * W.U[1] + dn.x * W.Vx[1] + dn.y * W.Vy[1]));
-            dm[2] = e1 * (o[2] + (nd * W.U[2] + dn.x * W.Vx[2] + dn.y * W.Vy[2]));
-            rot_vec(R, m, o);
-            m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = e1 * o[2] + (1 - e1);
-        }
-    }
-    double l[3];
-    {
-        double inv[9], wv[3] = {0, 0, 0};
-        for (int e = 0; e < 9; ++e) inv[e] = wpl[e * 256];
-        if (live) { wv[0] = w[G.o]; wv[1] = w[O + G.o]; wv[2] = w[2 * O + G.o]; }
-        double c[3];
-        for (int i = 0; i < 3; ++i) {
-            const double d = inv[i] * dm[0] + inv[3 + i] * dm[1] + inv[6 + i] * dm[2];      // dM = inv d
-            c[i] = live ? wv[i] * d : 0.0;
-        }
-        for (int j = 0; j < 3; ++j) l[j] = inv[3 * j] * c[0] + inv[3 * j + 1] * c[1] + inv[3 * j + 2] * c[2];      // lambda = inv' c
-    }
-    __syncthreads();                                                      // the direction row is read no more: the tile is free
-    bloch_ss_reverse(sst, red, in, P.t_off, ntime, sc, gamma, px, py, pz, dfv, live, l, part + V.p_off + wg * V.n, wck);
-}
+// ------------------------------------------------------------------------------------------------
+// k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch and k_bloch_ss_lm_sweep, then their magnitude twins k_bloch_ss_lsq_batch_mag,
+// k_bloch_ss_gn_batch_mag and k_bloch_ss_lm_sweep_mag: one text, blochssgn_kernels.inc, compiled twice.
+#define BLOCH_SS_KERNEL(name) name
+#define BLOCH_SS_MAG false
+#include "blochssgn_kernels.inc"
+#undef BLOCH_SS_MAG
+#undef BLOCH_SS_KERNEL
+#define BLOCH_SS_KERNEL(name) name##_mag
+#define BLOCH_SS_MAG true
+#include "blochssgn_kernels.inc"
+#undef BLOCH_SS_MAG
+#undef BLOCH_SS_KERNEL
 
 // ------------------------------------------------------------------------------------------------
 // Host side of mbfir_bloch_ss_lsq_batch / mbfir_bloch_ss_gn_batch (arguments checked by api.cpp): the forward call's staging
@@ -371,7 +146,7 @@ void bloch_ss_gn_run(int device, void* stream, int npulse, const long* toff, con
                      const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
                      const long* poff, const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
                      const double* const w[3], const double* const tg[3], int ndir, const double* v_re, const double* v_im,
-                     double* loss, double* o_re, double* o_im, double* mx, double* my, double* mz) {
+                     double* loss, double* o_re, double* o_im, double* mx, double* my, double* mz, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool lsq = tg != nullptr, want_m = lsq && mx != nullptr;
@@ -379,7 +154,7 @@ void bloch_ss_gn_run(int device, void* stream, int npulse, const long* toff, con
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 1, nullptr, nullptr, nullptr);
     Staging& S = B.S;
-    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, tg, ndir, v_re, v_im);
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, tg, ndir, v_re, v_im, mag);
     const long O = B.O;
     const long R = (long)ndir * toff[npulse], nl = lsq ? (npulse + 1) / 2 : 0;      // double2 entries of the results and of the losses
     const size_t O3 = lsq ? ((size_t)O * 3 + 1) & ~size_t(1) : 0;                  // an even count: the partials stay 16-byte aligned
@@ -395,13 +170,15 @@ void bloch_ss_gn_run(int device, void* stream, int npulse, const long* toff, con
     double* sinv = cks + G.nck;
     const double* in = S.dev<const double>(B.o_in);
     if (lsq) {
-        hipLaunchKernelGGL(k_bloch_ss_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+        hipLaunchKernelGGL(mag ? k_bloch_ss_lsq_batch_mag : k_bloch_ss_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, in,
+                           S.dev<const double>(B.o_df),
                            S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                            S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(G.o_vp), S.dev<const BlochCkDev>(G.o_ck),
                            S.dev<const long>(G.o_lp), S.dev<const double>(G.o_w), S.dev<const double>(G.o_t), O, part, cks, lpart,
                            want_m ? pm : nullptr, want_m ? pm + O : nullptr, want_m ? pm + 2 * O : nullptr);
     } else {
-        hipLaunchKernelGGL(k_bloch_ss_gn_batch, dim3((unsigned)nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+        hipLaunchKernelGGL(mag ? k_bloch_ss_gn_batch_mag : k_bloch_ss_gn_batch, dim3((unsigned)nblk), dim3(256), 0, st, in,
+                           S.dev<const double>(B.o_df),
                            S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                            S.dev<const SimBlock>(G.o_jb), S.dev<const VjpPulseDev>(G.o_vp), S.dev<const BlochCkDev>(G.o_ck),
                            S.dev<const double>(G.o_w), O, S.dev<const double2>(G.o_v), ndir, part, cks, sinv);
@@ -428,11 +205,11 @@ void bloch_ss_lsq_batch_run(int device, void* stream, int npulse, const long* to
                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                             const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
                             const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
-                            double* mz) {
+                            double* mz, bool mag) {
     const double* const w[3] = {wx, wy, wz};
     const double* const tg[3] = {tx, ty, tz};
     bloch_ss_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid,
-                    poff, dx, dy, dz, nscale, scales, w, tg, 1, nullptr, nullptr, loss, g_re, g_im, mx, my, mz);
+                    poff, dx, dy, dz, nscale, scales, w, tg, 1, nullptr, nullptr, loss, g_re, g_im, mx, my, mz, mag);
 }
 
 void bloch_ss_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
@@ -440,10 +217,10 @@ void bloch_ss_gn_batch_run(int device, void* stream, int npulse, const long* tof
                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
-                           const double* v_im, double* h_re, double* h_im) {
+                           const double* v_im, double* h_re, double* h_im, bool mag) {
     const double* const w[3] = {wx, wy, wz};
     bloch_ss_gn_run(device, stream, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid,
-                    poff, dx, dy, dz, nscale, scales, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im, nullptr, nullptr, nullptr);
+                    poff, dx, dy, dz, nscale, scales, w, nullptr, ndir, v_re, v_im, nullptr, h_re, h_im, nullptr, nullptr, nullptr, mag);
 }
 
 // Host side of mbfir_bloch_ss_lm_step_batch (arguments checked by api.cpp): the forward staging at mode 1 and bloch_gn_stage at
@@ -460,7 +237,7 @@ void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long
                                 int nscale, const double* scales, const double* wx, const double* wy, const double* wz,
                                 const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* tx,
                                 const double* ty, const double* tz, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
-                                int* status, double* loss, double* g_re, double* g_im) {
+                                int* status, double* loss, double* g_re, double* g_im, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool trial = tx != nullptr;
@@ -470,7 +247,7 @@ void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 1, nullptr, nullptr, nullptr);
     Staging& S = B.S;
-    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im);
+    const BlochGnSections G = bloch_gn_stage(B, npulse, toff, nscale, w, trial ? tg : nullptr, 1, b_re, b_im, mag);
     const size_t o_mu = S.add((size_t)npulse * 8);
     std::copy(mu, mu + npulse, S.at<double>(o_mu));
     const long T = toff[npulse];
@@ -500,7 +277,8 @@ void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long
                        S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                        S.dev<const SimBlock>(S.o_bk), state, plane);      // cg = 0: no pulse runs, every workgroup returns at once
     for (int k = 0; k < cg; ++k) {                                // rounds of a pulse that has stopped are early exits
-        hipLaunchKernelGGL(k_bloch_ss_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in, S.dev<const double>(B.o_df),
+        hipLaunchKernelGGL(mag ? k_bloch_ss_lm_sweep_mag : k_bloch_ss_lm_sweep, dim3((unsigned)S.nblk), dim3(256), 0, st, in,
+                           S.dev<const double>(B.o_df),
                            S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                            S.dev<const SimBlock>(G.o_jb), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const double>(G.o_w), B.O, p,
                            state, part, cks, plane);
@@ -509,7 +287,8 @@ void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long
     }
     if (trial) {
         bloch_lm_trial_launch(st, in, d, T, rows);
-        hipLaunchKernelGGL(k_bloch_ss_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, rows, S.dev<const double>(B.o_df),
+        hipLaunchKernelGGL(mag ? k_bloch_ss_lsq_batch_mag : k_bloch_ss_lsq_batch, dim3((unsigned)S.nblk), dim3(256), 0, st, rows,
+                           S.dev<const double>(B.o_df),
                            S.dev<const double>(B.o_pos), S.dev<const double>(S.o_sc), S.dev<const BlochPulseDev>(S.o_pd),
                            S.dev<const SimBlock>(S.o_bk), vp, S.dev<const BlochCkDev>(G.o_ck), S.dev<const long>(G.o_lp),
                            S.dev<const double>(G.o_w), S.dev<const double>(G.o_t), B.O, part, cks, lpart, nullptr, nullptr, nullptr);

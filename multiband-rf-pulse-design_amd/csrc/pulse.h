@@ -261,13 +261,13 @@ void bloch_ss_lsq_batch_run(int device, void* stream, int npulse, const long* to
                             int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                             const double* scales, const double* wx, const double* wy, const double* wz, const double* tx,
                             const double* ty, const double* tz, double* loss, double* g_re, double* g_im, double* mx, double* my,
-                            double* mz);
+                            double* mz, bool mag = false);
 void bloch_ss_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                            const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                            const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
                            int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                            const double* scales, const double* wx, const double* wy, const double* wz, int ndir, const double* v_re,
-                           const double* v_im, double* h_re, double* h_im);
+                           const double* v_im, double* h_re, double* h_im, bool mag = false);
 // Adjoints with respect to rf and to the gradient waveform (simgradg.hip k_abr_vjp_rfg_batch, k_abr2_vjp_rfg_batch,
 // k_abr_vjp_rfg_fold): as the calls above, plus gg (1D) or ggx / ggy (2D): dL / d g per rf sample, laid out as g, summed over the
 // pulse's points and scales (no factor s: a scale multiplies rf).  A null g / gx / gy differentiates at its default.
@@ -318,20 +318,23 @@ void abr2_gn_batch_run(int device, void* stream, int npulse, const long* roff, c
 // directions (as bloch_jvp_batch_run takes them) in the forward outputs' layout.  lsq: loss per pulse and the gradient per b1
 // sample; gn: sum_s s J_s' W_s J_s (s v), pulse p from ndir toff[p], direction-major.  One upload, two launches, one download of
 // b1 size; the partials and the checkpoints stay on the device.
+// mag, here and in the steady state's and the Levenberg-Marquardt steps' calls below: the magnitude fit of (|Mxy|, mz).
+// The pair of weights (w_xy, w_z) comes in (wx, wy) and the pair of targets (t_xy, t_z) in (tx, ty); wz and tz are not read.  The
+// staging, the launches and the downloads are the component calls'; only the kernels of the sweeps are the magnitude twins.
 void bloch_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                          const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                          const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
                          int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                          const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                          const double* wy, const double* wz, const double* tx, const double* ty, const double* tz, double* loss,
-                         double* g_re, double* g_im);
+                         double* g_re, double* g_im, bool mag = false);
 void bloch_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                         const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                         const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
                         int npgrid, const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
                         const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                         const double* wy, const double* wz, int ndir, const double* v_re, const double* v_im, double* h_re,
-                        double* h_im);
+                        double* h_im, bool mag = false);
 // The Levenberg-Marquardt step on the device (simgn.hip): CG on (H + mu I) d = b per pulse and, with t_re, the loss and gradient at
 // rf + d (loss, g_re, g_im may be null without one).
 void abr_lm_step_batch_run(int device, void* stream, int npulse, const long* roff, const double* rf_re, const double* rf_im,
@@ -355,7 +358,7 @@ void bloch_lm_step_batch_run(int device, void* stream, int npulse, const long* t
                              const double* scales, const double* m0x, const double* m0y, const double* m0z, const double* wx,
                              const double* wy, const double* wz, const double* b_re, const double* b_im, const double* mu, int cg,
                              double rtol, const double* tx, const double* ty, const double* tz, double* d_re, double* d_im, int* ncg,
-                             double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im);
+                             double* rr, double* gg, int* status, double* loss, double* g_re, double* g_im, bool mag = false);
 // The Levenberg-Marquardt step of the steady state on the device (blochssgn.hip k_bloch_ss_lm_prep, k_bloch_ss_lm_sweep with
 // blochgn.hip's k_bloch_lm_step, k_bloch_lm_trial and simgn.hip's k_lm_init): CG on (H + mu I) d = b per pulse, H as
 // bloch_ss_gn_batch_run applies it, and, with tx / ty / tz, the loss and gradient of bloch_ss_lsq_batch_run at b1 + d (loss, g_re,
@@ -367,7 +370,7 @@ void bloch_ss_lm_step_batch_run(int device, void* stream, int npulse, const long
                                 int nscale, const double* scales, const double* wx, const double* wy, const double* wz,
                                 const double* b_re, const double* b_im, const double* mu, int cg, double rtol, const double* tx,
                                 const double* ty, const double* tz, double* d_re, double* d_im, int* ncg, double* rr, double* gg,
-                                int* status, double* loss, double* g_re, double* g_im);
+                                int* status, double* loss, double* g_re, double* g_im, bool mag = false);
 // The Levenberg-Marquardt step of the pulse train on the device (blochtrainlm.hip k_bloch_train_lm_prep, k_bloch_train_lm_jvp,
 // k_bloch_train_lm_run, k_bloch_train_lm_pvjp, k_bloch_train_lm_step with the shipped k_bloch_train_prop, simgn.hip's k_lm_init and, for
 // the trial, blochgn.hip's k_bloch_lm_trial and the kernels of bloch_train_lsq_batch_run): CG on (H + mu I) d = b per

@@ -1411,8 +1411,48 @@ struct BlochGnSections {
     size_t o_w = 0, o_t = 0, o_v = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0, o_jb = 0;
     long npart = 0, nck = 0, nlp = 0, nfold = 0;        // double2 partials, checkpoint doubles, loss partials, workgroups of the fold
 };
+// mag: w and tg hold two planes each, (xy, z), and the sections are two planes long.
 BlochGnSections bloch_gn_stage(BlochStaged& B, int npulse, const long* toff, int nscale, const double* const w[3],
-                               const double* const tg[3], int ndir, const double* v_re, const double* v_im);
+                               const double* const tg[3], int ndir, const double* v_re, const double* v_im, bool mag = false);
+
+// The transverse magnitude of the magnitude fits and its direction: rho = sqrt(mx mx + my my), every operation rounded
+// once and none contracted, so that np.sqrt(mx * mx + my * my) on the forward call's output has its bits; u = (mx, my) / rho, and
+// (0, 0) where rho is 0.
+struct BlochMagDir {
+    double rho, ux, uy;
+};
+__device__ __forceinline__ BlochMagDir bloch_mag_dir(double mx, double my) {
+#pragma clang fp contract(off)                                            // the products are rounded before the sum: no fma
+    BlochMagDir D;
+    const double xx = mx * mx, yy = my * my;
+    D.rho = __dsqrt_rn(xx + yy);
+    const bool pos = D.rho > 0;
+    D.ux = pos ? mx / D.rho : 0.0;
+    D.uy = pos ? my / D.rho : 0.0;
+    return D;
+}
+// bloch_fwd_step with the rounding k_bloch_batch's own sweep has, for the magnitude lsq kernel of the end point, whose rho has to have
+// the bits of np.sqrt(mx * mx + my * my) of the forward call's output.  The two sweeps are the same expressions, but the compiler
+// contracts R v differently in them: k_bloch_batch rounds the product with v[1] and fuses the other two, o_i = fma(R_i2, v2,
+// fma(R_i0, v0, R_i1 v1)), bloch_fwd_step's callers round the one with v[0]; m ends an ulp or two apart at some points.  Everything
+// else of a step (rotz, the rotation matrix, the decay and the recovery fma(e1, o_2, 1 - e1)) comes out alike in both, so stating
+// R v with explicit fma is enough; tests/test_blochmag_gpu.py holds the end points equal bit for bit on every case.
+__device__ __forceinline__ void bloch_fwd_step_batch(const double* s, double rotz, double m[3]) {
+    Rot3 R;
+    bloch_rotmat(s[0], s[1], rotz, R);
+    const double e1 = s[6], e2 = s[7];
+    double o[3];
+    for (int i = 0; i < 3; ++i) o[i] = fma(R.m[6 + i], m[2], fma(R.m[i], m[0], R.m[3 + i] * m[1]));
+    m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = fma(e1, o[2], 1 - e1);
+}
+// The cotangent of the magnitude fits from the pair of weights w = (w_xy, w_z): lsq with a = rho - t_xy and b = mz - t_z, gn with
+// a = u . dm_xy and b = dm_z.  c = (w_xy a u_x, w_xy a u_y, w_z b); a dead thread's is zero.
+__device__ __forceinline__ void bloch_mag_seed(const BlochMagDir& D, const double w[3], double a, double b, bool live, double c[3]) {
+    const double wa = w[0] * a;
+    c[0] = live ? wa * D.ux : 0.0;
+    c[1] = live ? wa * D.uy : 0.0;
+    c[2] = live ? w[1] * b : 0.0;
+}
 // Launches k_bloch_gn_fold (blochgn.hip) on nfold workgroups; lpart, lp, loss as the kernel takes them (loss null: no loss sum).
 void bloch_gn_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
                           const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* out,

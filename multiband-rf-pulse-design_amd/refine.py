@@ -182,7 +182,7 @@ def _lm_loop(rfs, infos, lsq, gn, step, iters, mu0):
 
 
 def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=None, iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
-                       steady_state=False, ctx=None):
+                       steady_state=False, magnitude=False, ctx=None):
     """refine_batch for bloch_batch's model, relaxation included: the same lock-step Levenberg-Marquardt / CG loop
     on bloch_lsq_batch and bloch_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, of which only b1 changes; df, dp:
     one grid shared by every pulse or a list of one per pulse; targets, weights, scales and m0 (None, one (mx, my, mz), or a list
@@ -191,26 +191,29 @@ def refine_bloch_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), m0=No
     step in one bloch_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as a
     refused step.  steady_state: fit the steady state of the period (bloch_batch's mode 1) instead of the end point, on
     bloch_ss_lsq_batch and bloch_ss_gn_batch; each pulse is then one period, targets and weights lie as mode 1's outputs
-    do, there is no m0, and the solver is 'host' (refine_bloch_ss_batch has both solvers).  A pulse refined in a batch has the bits
-    of the same pulse refined alone."""
+    do, there is no m0, and the solver is 'host' (refine_bloch_ss_batch has both solvers).  magnitude: fit (|Mxy|, mz) instead of
+    (mx, my, mz): targets and weights are pairs (xy, z) per pulse, every call of the loop is made with magnitude=True,
+    and both solvers work.  A pulse refined in a batch has the bits of the same pulse refined alone."""
     return _refine_bloch("refine_bloch_batch", False, pulses, df, dp, targets, weights, scales, m0, iters, cg, mu0, rtol, solver,
-                         steady_state, ctx)
+                         steady_state, magnitude, ctx)
 
 
 def refine_bloch_ss_batch(pulses, df, dp, targets, weights, *, scales=(1.0,), iters=5, cg=8, mu0=None, rtol=1e-6, solver="host",
-                          ctx=None):
+                          magnitude=False, ctx=None):
     """refine_bloch_batch(steady_state=True) with both solvers: the lock-step Levenberg-Marquardt / CG loop on the
     steady state of the period, bloch_batch's mode 1.  pulses: (b1, gr, tp, t1, t2, nucleus) each, one period, of which only b1
     changes; df, dp, targets, weights and scales as for bloch_ss_lsq_batch; iters, cg, mu0 and rtol as for refine_batch; there is no
     m0.  Returns (b1s, infos) as refine_batch does.  solver: 'host' runs the CG recurrence on the host, one bloch_ss_gn_batch call
     per iteration, and returns the bits and the 'calls' of refine_bloch_batch(steady_state=True); 'device' solves and tries each
     step in one bloch_ss_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG breakdown counting as
-    a refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    a refused step.  magnitude: as for refine_bloch_batch.  A pulse refined in a batch has the bits of the same pulse refined
+    alone."""
     return _refine_bloch("refine_bloch_ss_batch", True, pulses, df, dp, targets, weights, scales, None, iters, cg, mu0, rtol, solver,
-                         True, ctx)
+                         True, magnitude, ctx)
 
 
-def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, iters, cg, mu0, rtol, solver, steady_state, ctx):
+def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, iters, cg, mu0, rtol, solver, steady_state, magnitude,
+                  ctx):
     """The body of refine_bloch_batch and refine_bloch_ss_batch; who: the entry point, for the messages; ss_device: whether the
     steady state's device step may be taken."""
     mb = importlib.import_module(__package__)
@@ -225,7 +228,8 @@ def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, 
                          "solver='device')" % who)
     targets, weights = list(targets), list(weights)
     if len(targets) != P or len(weights) != P:
-        raise ValueError("%s: %d target and %d weight triples for %d pulses" % (who, len(targets), len(weights), P))
+        raise ValueError("%s: %d target and %d weight %s for %d pulses"
+                         % (who, len(targets), len(weights), "pairs" if magnitude else "triples", P))
     if iters < 0 or cg < 1:
         raise ValueError("%s: iters must be at least 0 and cg at least 1" % who)
     if solver not in ("host", "device"):
@@ -241,9 +245,10 @@ def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, 
         return [(b1_of[q],) + rest[q] for q in idx], grid(df, idx), grid(dp, idx)
 
     def kw(idx):
+        mag = dict(magnitude=True) if magnitude else {}                          # without it the calls are the ones they were
         if steady_state:
-            return dict(scales=scales, ctx=ctx)
-        return dict(scales=scales, m0=[m0[q] for q in idx] if each else m0, ctx=ctx)
+            return dict(scales=scales, ctx=ctx, **mag)
+        return dict(scales=scales, m0=[m0[q] for q in idx] if each else m0, ctx=ctx, **mag)
 
     def lsq(idx, b1_of):
         for q in idx:
