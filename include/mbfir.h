@@ -1365,6 +1365,21 @@ int mbfir_test_fold(const double* w, int m, int fold, long* out);
  *     nfix receives the number of replaced pivots; Lh / Ll (optional, n x n) the Cholesky factor.            */
 int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs,
                        const double* bh, const double* bl, double* xh, double* xl, int* nfix, double* Lh, double* Ll);
+/*  mbfir_test_ddstages: the same double-double kernels stage by stage.  H, U, X, b as for mbfir_test_ddsolve, padded to np = n rounded up
+ *  to 64 (identity past n, zero coupling); pivtol the pivot rule's threshold; form the triangular-solve kernel: 0 the single
+ *  workgroup (no flags), 1 one workgroup per 32-row block, 2 the 64-row blocks with the inverses of the diagonal blocks; nsolve >= 1
+ *  solves on ONE flag array with the epochs 1 .. nsolve, each from a fresh copy of b.  The launches are a solve's own, in order: the
+ *  rank-k update, the factorisation (the block inverses for form 2 only), the solves.  Read back after each group, full padded size:
+ *    Hh, Hl (np x np) the updated matrix; d0 (np); Lh, Ll (np x np) the same buffers after the factorisation (the factor in the lower
+ *    triangle); Lth, Ltl (np x np) its transpose; ri (2 x np: high words, low words) the reciprocal diagonal; dinv (2 x np / 64 x 64 x 64:
+ *    high words, low words) the block inverses; xh, xl (nsolve x 2 x np) the solutions; counter (2 ints): the pivot counter after the
+ *    factorisation and after the last solve (replaced pivots + 2^20 per lost hand-off).
+ *  Hl, d0, Lth, Ltl, ri, dinv and the rows nrhs .. 1 of every solution go to the device as the caller filled them and come back after
+ *  the launches: what no launch writes holds on exit what it held on entry.  A bad argument is MBFIR_E_ARG with a message, before
+ *  anything is launched. */
+int mbfir_test_ddstages(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
+                        const double* bl, double pivtol, int form, int nsolve, double* Hh, double* Hl, double* d0, double* Lh, double* Ll,
+                        double* Lth, double* Ltl, double* ri, double* dinv, double* xh, double* xl, int* counter);
 /*  mbfir_test_capsolve: the capacitance form of the extended-precision KKT solve (capkkt.hip) stage by stage -- for nlanes
  *  independent problems (H_w + U' diag(X) U) dx = (a + b) + U' diag(X) t, laid out as a lock-step unit lays its lanes out, exactly the
  *  launches a solve issues: the factorisation of H_w (M = L^-1), Yt = U M', Zt = Yt M, S = Yt Yt' + X^-1, the factorisation of S

@@ -264,6 +264,8 @@ SYMBOLS = {
                                        [_dp] * 9 + [_lp] + [_dp] * 6 + [_lp, _lp]),
     "mbfir_test_fold": (C.c_int, [_dp, C.c_int, C.c_int, C.POINTER(C.c_long)]),
     "mbfir_test_ddsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, _dp, _dp, _ip, _dp, _dp]),
+    "mbfir_test_ddstages": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_double, C.c_int, C.c_int,
+                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "mbfir_test_capsolve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _ip, C.c_int, C.c_int, C.c_int, _ip, _dp, _dp, _dp, _dp, _dp, _dp,
                                       _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _ip]),
     "mbfir_test_mfma_peak": (C.c_int, [C.c_void_p, _dp, _dp]),
@@ -3295,7 +3297,44 @@ def test_ddsolve(H, U, X, bh, bl, ctx=None, factor=False):
     return xh, xl, nfix.value
 
 
-CAP_SENTINEL = -7.25          # what test_capsolve's output arrays hold on entry (a masked lane's still hold it on return)
+DD_FORMS = {"single": 0, "mw": 1, "bi": 2}          # k_dd_trsv, k_dd_trsv_mw, k_dd_trsv_bi
+DD_SYNC_LOST = 1 << 20                              # what a lost hand-off adds to the pivot counter (dev_common.h)
+DDSTAGES_OUT = ("Hh", "Hl", "d0", "Lh", "Ll", "Lth", "Ltl", "ri", "dinv", "xh", "xl")
+
+
+def test_ddstages(H, U, X, bh, bl, *, pivtol=1e-28, form="mw", nsolve=1, sentinel=np.nan, ctx=None):
+    """The double-double kernels of ddlin.hip stage by stage (mbfir_test_ddstages): the rank-k update H + U' diag(X) U, the blocked
+    Cholesky factorisation (for form 'bi' with the inverses of the 64 x 64 diagonal blocks) and `nsolve` solves of b (nrhs x n, hi / lo)
+    by the kernel `form` names ('single' | 'mw' | 'bi') on one flag array, epochs 1 .. nsolve.  Returns a dict, everything at the
+    padded size np = n rounded up to 64 and pre-filled with `sentinel` where a kernel is to write: Hh, Hl (np, np) after the update;
+    d0 (np); Lh, Ll (np, np) the same buffers after the factorisation; Lth, Ltl (np, np); ri (2, np); dinv (2, np / 64, 64, 64);
+    xh, xl (nsolve, 2, np); counter (2: after the factorisation, after the solves).  The arguments are checked by the library: a
+    bad one raises ValueError with its message."""
+    ctx = ctx or get_context()
+    H = np.ascontiguousarray(H, dtype=np.float64)
+    n = int(H.shape[0])
+    U = np.ascontiguousarray(U, dtype=np.float64).reshape(-1, n)
+    X = _vec(X)
+    bh = np.ascontiguousarray(np.atleast_2d(bh), dtype=np.float64)
+    bl = np.ascontiguousarray(np.atleast_2d(bl), dtype=np.float64)
+    if form not in DD_FORMS:
+        raise ValueError("form must be one of %s" % (sorted(DD_FORMS),))
+    npd, ns = -(-n // 64) * 64, max(int(nsolve), 1)
+    shapes = dict(Hh=(npd, npd), Hl=(npd, npd), d0=(npd,), Lh=(npd, npd), Ll=(npd, npd), Lth=(npd, npd), Ltl=(npd, npd), ri=(2, npd),
+                  dinv=(2, npd // 64, 64, 64), xh=(ns, 2, npd), xl=(ns, 2, npd))
+    out = {name: np.full(shapes[name], sentinel, dtype=np.float64) for name in DDSTAGES_OUT}
+    counter = np.full(2, -1, dtype=np.int32)
+    rc = load_library().mbfir_test_ddstages(ctx._h, n, U.shape[0], _ptr(H), _ptr(U), _ptr(X), bh.shape[0], _ptr(bh), _ptr(bl), float(pivtol),
+                                            DD_FORMS[form], int(nsolve), *[_ptr(out[name]) for name in DDSTAGES_OUT],
+                                            counter.ctypes.data_as(_ip))
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    out["counter"] = counter
+    return out
+
+
+CAP_SENTINEL = -7.25         # what test_capsolve's output arrays hold on entry (a masked lane's still hold it on return)
 CAPSOLVE_OUT = ("M", "Yt", "Zt", "S", "Ms", "rhs_w", "y", "w", "zeta", "dx")
 
 

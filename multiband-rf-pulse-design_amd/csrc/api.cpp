@@ -800,6 +800,27 @@ int mbfir_test_ddsolve(mbfir_ctx* ctx, int n, int k, const double* H, const doub
     if (!ctx || n < 1 || k < 0 || nrhs < 1 || nrhs > 2 || !H || !bh || !bl || !xh || !xl || !nfix) return MBFIR_E_ARG;
     MBFIR_TRY(ctx, ctx->solver->test_ddsolve(n, k, H, U, X, nrhs, bh, bl, xh, xl, nfix, Lh, Ll));
 }
+int mbfir_test_ddstages(mbfir_ctx* ctx, int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
+                        const double* bl, double pivtol, int form, int nsolve, double* Hh, double* Hl, double* d0, double* Lh, double* Ll,
+                        double* Lth, double* Ltl, double* ri, double* dinv, double* xh, double* xl, int* counter) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "mbfir_test_ddstages: " + why; return MBFIR_E_ARG; };
+    if (n < 1 || n > 4096) return bad("n must be 1 .. 4096");
+    if (k < 0) return bad("k < 0");
+    if (nrhs < 1 || nrhs > 2) return bad("nrhs must be 1 or 2");
+    if (form < 0 || form > 2) return bad("form must be 0 (single), 1 (mw) or 2 (bi)");
+    if (nsolve < 1 || nsolve > 64) return bad("nsolve must be 1 .. 64");
+    if (!H || (k > 0 && (!U || !X)) || !bh || !bl || !Hh || !Hl || !d0 || !Lh || !Ll || !Lth || !Ltl || !ri || !dinv || !xh || !xl || !counter)
+        return bad("null array");
+    try {
+        DdStagesIO io;
+        io.n = n; io.k = k; io.nrhs = nrhs; io.form = form; io.nsolve = nsolve; io.pivtol = pivtol; io.H = H; io.U = U; io.X = X; io.bh = bh; io.bl = bl;
+        io.Hh = Hh; io.Hl = Hl; io.d0 = d0; io.Lh = Lh; io.Ll = Ll; io.Lth = Lth; io.Ltl = Ltl; io.ri = ri; io.dinv = dinv; io.xh = xh; io.xl = xl;
+        io.counter = counter;
+        ctx->solver->test_ddstages(io);
+        return 0;
+    } catch (const std::exception& e) { ctx->err = e.what(); return MBFIR_E_HIP; }
+}
 int mbfir_test_capsolve(mbfir_ctx* ctx, int n, int nlanes, const int* k, int kp, int nrhs, int hsolve_form, const int* mask,
                         const double* H, const double* U, const double* X, const double* a, const double* b, const double* t,
                         double* M, double* Yt, double* Zt, double* S, double* Ms, double* rhs_w, double* y, double* w,

@@ -129,6 +129,16 @@ struct CapSolveIO {
     int* flag = nullptr;
 };
 
+// mbfir_test_ddstages (include/mbfir.h): the launches of ddlin.hip with every stage read back, np = n rounded up to 64
+struct DdStagesIO {
+    int n = 0, k = 0, nrhs = 1, form = 1, nsolve = 1;          // form: 0 k_dd_trsv, 1 k_dd_trsv_mw, 2 k_dd_trsv_bi
+    double pivtol = 0.0;
+    const double *H = nullptr, *U = nullptr, *X = nullptr, *bh = nullptr, *bl = nullptr;
+    double *Hh = nullptr, *Hl = nullptr, *d0 = nullptr, *Lh = nullptr, *Ll = nullptr, *Lth = nullptr, *Ltl = nullptr, *ri = nullptr,
+           *dinv = nullptr, *xh = nullptr, *xl = nullptr;
+    int* counter = nullptr;
+};
+
 class Solver {
 public:
     explicit Solver(int device);
@@ -171,6 +181,9 @@ public:
     void test_unit_ddkkt(const std::vector<const TrigProgram*>& Ps, const SolveOpts& o, const UnitDdKkt& io);
     void test_ddsolve(int n, int k, const double* H, const double* U, const double* X, int nrhs, const double* bh,
                       const double* bl, double* xh, double* xl, int* nfix, double* Lh_out = nullptr, double* Ll_out = nullptr);
+    // the same kernels stage by stage: the update, the factorisation (with the block inverses), nsolve solves in a chosen form on one
+    // flag array, everything read back at the padded size
+    void test_ddstages(const DdStagesIO& io);
     // the capacitance form of the extended-precision solve: the launches of its build and of one pass of its solve, for nlanes
     // problems laid out as a lock-step unit lays them out, every intermediate returned
     void test_capsolve(const CapSolveIO& io);

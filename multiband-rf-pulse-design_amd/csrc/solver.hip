@@ -5254,6 +5254,74 @@ void Solver::test_ddsolve(int n, int k, const double* Hh, const double* U, const
         for (int j = 0; j < n; ++j) { xh[(size_t)v * n + j] = B[v * ldv + j]; xl[(size_t)v * n + j] = Bl[v * ldv + j]; }
 }
 
+// The double-double kernels of ddlin.hip stage by stage (mbfir_test_ddstages checks the arguments): the padding of test_ddsolve
+// (identity past n, zero coupling), then the production launches in order -- dd_syrk_launch, dd_chol_launch (the block inverses for
+// form 2 only), nsolve calls of dd_trsv_launch on ONE flag array with the epochs 1 .. nsolve, each from a fresh copy of the right-hand
+// sides -- and a read-back after every group, full padded size.  Hl, d0, Lth / Ltl, ri, dinv and the rows nrhs .. 1 of every solution
+// go to the device as the caller filled them: what no launch writes comes back as it went in.
+void Solver::test_ddstages(const DdStagesIO& io) {
+    Impl& S = *impl;
+    MBFIR_HIP(hipSetDevice(S.device));
+    const int n = io.n, k = io.k, nrhs = io.nrhs;
+    const size_t np = round_up(n, 64), ldv = np, nn = np * np * 8;
+    std::vector<double> Hp(np * np, 0.0), Up((size_t)std::max(k, 1) * np, 0.0);
+    for (size_t i = 0; i < np; ++i) Hp[i * np + i] = 1.0;
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) Hp[i * np + j] = io.H[(size_t)i * n + j];
+    for (int r = 0; r < k; ++r)
+        for (int j = 0; j < n; ++j) Up[r * np + j] = io.U[(size_t)r * n + j];
+    DevBuf dH(nn), dHl(nn), dLt(nn), dLtl(nn), dU(Up.size() * 8), dX((size_t)std::max(k, 1) * 8), dri(2 * np * 8), dd0(np * 8),
+        dB(2 * ldv * 8), dBl(2 * ldv * 8), df(16), dinv(2 * np * 64 * 8), dflags(sizeof(int) * (2 * np / 32 + 8));
+    MBFIR_HIP(hipMemcpyAsync(dH.p, Hp.data(), nn, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dHl.p, io.Hl, nn, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dLt.p, io.Lth, nn, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dLtl.p, io.Ltl, nn, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dri.p, io.ri, 2 * np * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dd0.p, io.d0, np * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dinv.p, io.dinv, 2 * np * 64 * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemcpyAsync(dU.p, Up.data(), Up.size() * 8, hipMemcpyHostToDevice, S.st));
+    if (k > 0) MBFIR_HIP(hipMemcpyAsync(dX.p, io.X, (size_t)k * 8, hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemsetAsync(df.p, 0, 16, S.st));
+    MBFIR_HIP(hipMemcpyAsync(df.as<int>() + 1, &k, sizeof(int), hipMemcpyHostToDevice, S.st));
+    MBFIR_HIP(hipMemsetAsync(dflags.p, 0, sizeof(int) * (2 * np / 32 + 8), S.st));
+    // 1: the rank-k update
+    dd_syrk_launch(dU.as<double>(), int(np), dX.as<double>(), df.as<int>() + 1, int(np), dH.as<double>(), dHl.as<double>(), S.st);
+    MBFIR_HIP(hipMemcpyAsync(io.Hh, dH.p, nn, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.Hl, dHl.p, nn, hipMemcpyDeviceToHost, S.st));
+    // 2: the factorisation
+    double* dinvp = io.form == 2 ? dinv.as<double>() : nullptr;
+    dd_chol_launch(dH.as<double>(), dHl.as<double>(), dLt.as<double>(), dLtl.as<double>(), dri.as<double>(), dri.as<double>() + np,
+                   dd0.as<double>(), int(np), io.pivtol, df.as<int>(), S.st, dinvp);
+    MBFIR_HIP(hipMemcpyAsync(io.Lh, dH.p, nn, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.Ll, dHl.p, nn, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.Lth, dLt.p, nn, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.Ltl, dLtl.p, nn, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.ri, dri.p, 2 * np * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.d0, dd0.p, np * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.dinv, dinv.p, 2 * np * 64 * 8, hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipMemcpyAsync(io.counter, df.p, sizeof(int), hipMemcpyDeviceToHost, S.st));
+    // 3: the solves, every one from the caller's right-hand sides, on the same flags
+    for (int s = 0; s < io.nsolve; ++s) {
+        double* xh = io.xh + (size_t)s * 2 * ldv;
+        double* xl = io.xl + (size_t)s * 2 * ldv;
+        for (int v = 0; v < nrhs; ++v)
+            for (size_t j = 0; j < np; ++j) {
+                xh[v * ldv + j] = j < size_t(n) ? io.bh[(size_t)v * n + j] : 0.0;
+                xl[v * ldv + j] = j < size_t(n) ? io.bl[(size_t)v * n + j] : 0.0;
+            }
+        MBFIR_HIP(hipMemcpyAsync(dB.p, xh, 2 * ldv * 8, hipMemcpyHostToDevice, S.st));
+        MBFIR_HIP(hipMemcpyAsync(dBl.p, xl, 2 * ldv * 8, hipMemcpyHostToDevice, S.st));
+        dd_trsv_launch(dH.as<double>(), dHl.as<double>(), dLt.as<double>(), dLtl.as<double>(), dri.as<double>(), dri.as<double>() + np,
+                       int(np), dB.as<double>(), dBl.as<double>(), nrhs, int(ldv), S.st, io.form == 0 ? nullptr : dflags.as<int>(), s + 1,
+                       df.as<int>(), dinvp);
+        MBFIR_HIP(hipMemcpyAsync(xh, dB.p, 2 * ldv * 8, hipMemcpyDeviceToHost, S.st));
+        MBFIR_HIP(hipMemcpyAsync(xl, dBl.p, 2 * ldv * 8, hipMemcpyDeviceToHost, S.st));
+    }
+    MBFIR_HIP(hipMemcpyAsync(io.counter + 1, df.p, sizeof(int), hipMemcpyDeviceToHost, S.st));
+    MBFIR_HIP(hipStreamSynchronize(S.st));
+    MBFIR_HIP(hipGetLastError());
+}
+
 // The capacitance form of the extended-precision solve as build_H and one pass of kkt_solve_dd launch it (mbfir_test_capsolve checks
 // the arguments).  One arena per lane, lanes lane_bytes apart, kcnt and the pivot counters in the lane's arena, the mask in lane 0's.
 // A single problem runs as a single design does (no lane stride, no kcnt, the launches carry its own k); several run as a unit (the
