@@ -13,8 +13,12 @@ result at the same --tr, --ntr and --weight, and the losses and device calls of 
 criterion.  No plots.  --solver host (the default) runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration
 (56 device calls at the defaults); --solver device solves and tries every step in one bloch_train_lm_step_batch call
 (mbfir.refine_bloch_train_lm_batch).  The last line counts the device calls of the fit.
+With --magnitude the echo term asks for |Mxy| alone: at the lactate points the echo amplitude of every
+repetition after the first --skip ones should be the mean amplitude over those repetitions of the starting pulse, the echo's phase
+being free, and the final term is the same Mz = 1; every call of the fit is made with magnitude=True and pairs (xy, z).
 
     python examples/bssfp_train_lm.py [--tr 6.0] [--ntr 64] [--iters 5] [--cg 8] [--weight 10] [--skip 8] [--solver host|device]
+                                      [--magnitude]
 """
 import argparse
 import os
@@ -36,6 +40,7 @@ ap.add_argument("--cg", type=int, default=8)
 ap.add_argument("--weight", type=float, default=10.0)
 ap.add_argument("--skip", type=int, default=8)
 ap.add_argument("--solver", choices=("host", "device"), default="host")
+ap.add_argument("--magnitude", action="store_true", help="fit (|Mxy|, mz) of the echoes instead of (mx, my, mz)")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -94,11 +99,14 @@ S, nf = len(scales), len(df)
 on = np.zeros((S, nf, 1))
 on[:, lac] = 1.0
 target = (ex[:, args.skip:].mean(1) * on, ey[:, args.skip:].mean(1) * on, 0.0)       # the mean demodulated echo, per (gain, point)
+weight, target_final, weight_final, mag = (on, on, 0.0), (0.0, 0.0, 1.0), (0.0, 0.0, args.weight * (1 - on)), {}
+if args.magnitude:                                                      # the mean echo amplitude, per (gain, point); pairs (xy, z)
+    target, weight = (np.hypot(ex, ey)[:, args.skip:].mean(1) * on, 0.0), (on, 0.0)
+    target_final, weight_final, mag = (0.0, 1.0), (0.0, args.weight * (1 - on)), dict(magnitude=True)
 t0 = time.perf_counter()
-(b1_lm,), (info,) = mbfir.refine_bloch_train_lm_batch([pulse(b1)], df, dp, N, [target], [(on, on, 0.0)], rep_weights=rw,
-                                                       targets_final=[(0.0, 0.0, 1.0)],
-                                                       weights_final=[(0.0, 0.0, args.weight * (1 - on))], demod=True,
-                                                       iters=args.iters, cg=args.cg, solver=args.solver, **kw)
+(b1_lm,), (info,) = mbfir.refine_bloch_train_lm_batch([pulse(b1)], df, dp, N, [target], [weight], rep_weights=rw,
+                                                       targets_final=[target_final], weights_final=[weight_final], demod=True,
+                                                       iters=args.iters, cg=args.cg, solver=args.solver, **kw, **mag)
 ms = (time.perf_counter() - t0) * 1e3
 print("Levenberg-Marquardt (%s solver): %d accepted steps, %d refused, losses %s, calls %s: %d device calls, %.1f ms" %
       (args.solver, len(info["losses"]) - 1, info["refused"], " ".join("%.6g" % v for v in info["losses"]), info["calls"],

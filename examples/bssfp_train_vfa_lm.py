@@ -7,10 +7,13 @@ same transverse magnetisation at the lactate points: the target is the mean over
 textbook schedule, point by point, so a flat echo train has zero loss.  Starting from that schedule it prints the schedule, the
 losses of the accepted steps and the echo amplitudes before and after.  A result, not a criterion.  No plots.
 
-    python examples/bssfp_train_vfa_lm.py [--tr 6.0] [--ntr 16] [--t1 30] [--t2 2] [--steps 5] [--solver host|device]
+    python examples/bssfp_train_vfa_lm.py [--tr 6.0] [--ntr 16] [--t1 30] [--t2 2] [--steps 5] [--solver host|device] [--magnitude]
 
 --solver device takes the steps through mbfir.refine_bloch_train_sched_lm_batch: conjugate gradients on the
 device in the call that evaluates the trial, one call and one set of propagator sweeps per accepted step.
+With --magnitude the goal is one constant |Mxy| for every echo: the target is the mean over the repetitions and
+the points of the textbook schedule's echo amplitude, one number, and the echo's phase is free; every call is made with
+magnitude=True and pairs (xy, z).
 """
 import argparse
 import os
@@ -28,6 +31,7 @@ ap.add_argument("--t1", type=float, default=30.0, help="s")
 ap.add_argument("--t2", type=float, default=2.0, help="s")
 ap.add_argument("--steps", type=int, default=5, help="accepted Levenberg-Marquardt steps at the most")
 ap.add_argument("--solver", choices=("host", "device"), default="host", help="dense Cholesky on the host, or CG on the device")
+ap.add_argument("--magnitude", action="store_true", help="fit one constant |Mxy| for every echo instead of (mx, my)")
 args = ap.parse_args()
 B0, n, T, FA, d1, d2 = 14.0, 100, 4.0, 60.0, 0.01, 0.005               # bSSFP_pulse_sb_mb.m:9-15
 pick, sel = [5, 0, 2, 3, 1], 4                                          # urea, pyruvate, alanine, pyruvate hydrate, lactate
@@ -73,13 +77,17 @@ print("%d repetitions of %.3f ms pulse + %.3f ms dead time (TR %.1f ms), T1 %.0f
 show("textbook schedule atan(1 / sqrt(N - k - 1))", gains)
 mx, my = echoes(gains)
 target = (mx.mean(0)[:, None], my.mean(0)[:, None], 0.0)                # (nf, npos) planes: the same at every repetition
-weights = (1.0, 1.0, 0.0)                                               # the transverse components only
+weights, mag = (1.0, 1.0, 0.0), {}                                      # the transverse components only
+if args.magnitude:                                                      # one constant |Mxy| for every echo and point; pairs (xy, z)
+    target, weights = (float(np.hypot(mx, my).mean()), 0.0), (1.0, 0.0)
+    mag = dict(magnitude=True)
+    print("magnitude target: |Mxy| = %.4f at every echo and point" % target[0])
 if args.solver == "host":
     (sch,), (info,) = mbfir.refine_bloch_train_sched_batch([pulse], df, pos, N, [target], [weights], vary=("gains",), iters=args.steps,
-                                                           gains=gains, **kw)
+                                                           gains=gains, **kw, **mag)
 else:
     (sch,), (info,) = mbfir.refine_bloch_train_sched_lm_batch([pulse], df, pos, N, [target], [weights], vary=("gains",),
-                                                              iters=args.steps, gains=gains, solver="device", cg=N, **kw)
+                                                              iters=args.steps, gains=gains, solver="device", cg=N, **kw, **mag)
 print("losses of the accepted steps: " + " ".join("%.4e" % v for v in info["losses"]))
 print("status %s, %d refused steps, last mu %.2e, device calls: %d lsq, %d gn" % (info["status"], info["refused"], info["mu"],
                                                                                    info["calls"]["lsq"], info["calls"]["gn"])

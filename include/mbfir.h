@@ -1077,6 +1077,95 @@ int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long
                                           const double* tfy, const double* tfz, const double* bgain, const double* bphi,
                                           const double* mu, int cg, double rtol, double* dgain, double* dphi, int* ncg, double* rr,
                                           double* gg, int* status, double* loss, double* ggain, double* gphi);
+/* Magnitude targets for the pulse train: the six train calls mbfir_bloch_train_lsq_batch, mbfir_bloch_train_gn_batch,
+ * mbfir_bloch_train_lm_step_batch, mbfir_bloch_train_lsq_sched_batch, mbfir_bloch_train_gn_sched_batch and
+ * mbfir_bloch_train_lm_step_sched_batch each have a twin that fits the echo amplitude |Mxy| and the z component of every echo, and of
+ * the final state, instead of the vectors.  The formulas are those of the magnitude twins above, applied once per echo
+ * and once at m_N.  With e echo k as mbfir_bloch_train_batch returns it under the call's demod, or m_N,
+ *     rho = sqrt(ex ex + ey ey)   (each product, the sum and the root rounded once: np.sqrt(ex * ex + ey * ey) on the forward
+ *                                  call's output has its bits)
+ *     u   = (ex, ey) / rho, and (0, 0) where rho = 0
+ *     L   = 1/2 sum_s sum_k rw_k sum_points [w_xy (rho_k - t_xy)^2 + w_z (e_kz - t_z)^2]
+ *         + 1/2 sum_s sum_points [wf_xy (rho_N - tf_xy)^2 + wf_z (m_Nz - tf_z)^2]
+ *     lsq: ce_k = rw_k (w_xy (rho_k - t_xy) u_x, w_xy (rho_k - t_xy) u_y, w_z (e_kz - t_z)), cf likewise with wf, tf
+ *     gn:  ce_k = rw_k (w_xy (u . de_xy) u_x, w_xy (u . de_xy) u_y, w_z de_z), cf likewise with dm_N
+ * A twin takes its component call's arguments with every weight triple replaced by a pair (wxy, wz) and every target triple by a
+ * pair (txy, tz), for the echo term and for the final term, the planes laid out as before (ebcast as before); one call fits
+ * magnitudes in both terms.  Every other argument, the outputs, the launches, the transfers, the guarantees on the bits and the
+ * argument checks, their order and their messages are the component call's ("only partly given" refers to the pair).  rho = 0 is not
+ * an error: the transverse term then adds 1/2 rw_k w_xy t_xy^2 to L and exact zeros to the gradients and to H v.  A negative t_xy
+ * is accepted.  H drops the curvature of rho across u. */
+int mbfir_bloch_train_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                    const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                    const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                    const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                    const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                    const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                    const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wxy,
+                                    const double* wz, const double* txy, const double* tz, const double* rw, const double* wfxy,
+                                    const double* wfz, const double* tfxy, const double* tfz, double* loss, double* g_re,
+                                    double* g_im, double* gmx, double* gmy, double* gmz);
+int mbfir_bloch_train_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                   const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                   const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                   const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                   const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                   const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                   const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                   const double* m0y, const double* m0z, int ebcast, const double* wxy, const double* wz,
+                                   const double* rw, const double* wfxy, const double* wfz, int ndir, const double* v_re,
+                                   const double* v_im, double* h_re, double* h_im);
+int mbfir_bloch_train_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                        const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                        const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                        int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                        const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                        const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                        const int* gidx, const long* goff, const double* gains, const int* echo,
+                                        const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                        int ebcast, const double* wxy, const double* wz, const double* rw, const double* wfxy,
+                                        const double* wfz, const double* b_re, const double* b_im, const double* mu, int cg,
+                                        double rtol, const double* txy, const double* tz, const double* tfxy, const double* tfz,
+                                        double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss,
+                                        double* g_re, double* g_im);
+int mbfir_bloch_train_lsq_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                          const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                          int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                          const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                          const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                          const int* gidx, const long* goff, const double* gains, const int* echo,
+                                          const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                          int ebcast, const double* wxy, const double* wz, const double* txy, const double* tz,
+                                          const double* rw, const double* wfxy, const double* wfz, const double* tfxy,
+                                          const double* tfz, double* loss, double* ggain, double* gphi, double* gmx, double* gmy,
+                                          double* gmz);
+int mbfir_bloch_train_gn_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                         const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                         const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                         int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                         const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                         const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                         const int* gidx, const long* goff, const double* gains, const int* echo,
+                                         const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                         int ebcast, const double* wxy, const double* wz, const double* rw, const double* wfxy,
+                                         const double* wfz, int ndir, const double* dgain, const double* dphi, double* hgain,
+                                         double* hphi);
+int mbfir_bloch_train_lm_step_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re,
+                                              const double* b1_im, const double* gx, const double* gy, const double* gz,
+                                              const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                                              const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                                              const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                                              const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                              const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                              const int* echo, const double* meq, int demod, const double* m0x,
+                                              const double* m0y, const double* m0z, int ebcast, const double* wxy,
+                                              const double* wz, const double* txy, const double* tz, const double* rw,
+                                              const double* wfxy, const double* wfz, const double* tfxy, const double* tfz,
+                                              const double* bgain, const double* bphi, const double* mu, int cg, double rtol,
+                                              double* dgain, double* dphi, int* ncg, double* rr, double* gg, int* status,
+                                              double* loss, double* ggain, double* gphi);
 /* mbfir_test_jvp_group (host only): the directions one workgroup of the two calls above carries (a compile-time constant). */
 int mbfir_test_jvp_group(void);
 /* mbfir_test_sim_blocks (host only): the workgroup table of the three calls above for pulses of ntime[p] samples and npoint[p]

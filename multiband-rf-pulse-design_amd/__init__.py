@@ -91,6 +91,8 @@ _lib = None
 # the context and the forward arguments of the Bloch calls, up to the scale list
 _BLOCH_HEAD = [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp, _dp, _dp,
                C.c_int, _dp]
+# the train's fused calls through ebcast: the Bloch head, the train's tables, demod, m0 and ebcast
+_TRAIN_HEAD = _BLOCH_HEAD + [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int]
 SYMBOLS = {
     "mbfir_create": (C.c_void_p, [C.c_int]),
     "mbfir_destroy": (None, [C.c_void_p]),
@@ -217,6 +219,15 @@ SYMBOLS = {
                                                         C.c_int, _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                                        [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 3 + [C.c_int] +
                                                        [_dp] * 16 + [C.c_int, C.c_double] + [_dp] * 2 + [_ip, _dp, _dp, _ip] + [_dp] * 3),
+    # the train's magnitude twins: pairs where the six train calls above take triples
+    "mbfir_bloch_train_lsq_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 15),
+    "mbfir_bloch_train_gn_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 5 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_train_lsq_sched_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 15),
+    "mbfir_bloch_train_gn_sched_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 5 + [C.c_int] + [_dp] * 4),
+    "mbfir_bloch_train_lm_step_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 5 + [_dp] * 3 + [C.c_int, C.c_double] + [_dp] * 6 +
+                                            [_ip, _dp, _dp, _ip, _dp, _dp, _dp]),
+    "mbfir_bloch_train_lm_step_sched_mag_batch": (C.c_int, _TRAIN_HEAD + [_dp] * 12 + [C.c_int, C.c_double] + [_dp] * 2 +
+                                                  [_ip, _dp, _dp, _ip] + [_dp] * 3),
     "mbfir_abr_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _dp, C.c_int, _dp,
                                           _dp, _dp, _dp, _dp, _dp, _dp]),
     "mbfir_abr2_vjp_rfg_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp, _dp, C.c_int, _lp, _dp,
@@ -2262,20 +2273,22 @@ def bloch_ss_gn_batch(pulses, df, dp, tangents, weights, *, scales=(1.0,), magni
     return _gn_result(rfs, K, keep, h)
 
 
-def _train_echo_planes(who, A, ntr, weights, targets):
+def _train_echo_planes(who, A, ntr, weights, targets, magnitude=False):
     """The echo term of the train's fused calls.  weights / targets (None: no targets, the products): per pulse a triple whose entries
     are shaped (S, ntr, nf, npos), or (S, nf, npos) / (nf, npos) / a scalar for every repetition -> (ebcast, weight planes, target
-    planes): the broadcast form (the planes laid out as the final state's) when no pulse gives a repetition axis."""
+    planes): the broadcast form (the planes laid out as the final state's) when no pulse gives a repetition axis.  magnitude: per
+    pulse a pair (xy, z) -> the two planes of the magnitude calls."""
+    n, form = (2, "pair (xy, z)") if magnitude else (3, "triple (x, y, z)")
     sets = [("weight", weights)] + ([("target", targets)] if targets is not None else [])
     arrs = []
     for what, triples in sets:
         triples = list(triples)
         if len(triples) != A.P:
-            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(triples), what, A.P))
+            raise ValueError("%s: %d %s %ss for %d pulses" % (who, len(triples), what, form.split()[0], A.P))
         per = []
         for q, tri in enumerate(triples):
-            if not isinstance(tri, (tuple, list)) or len(tri) != 3:
-                raise ValueError("%s: the %ss of pulse %d must be a triple (x, y, z)" % (who, what, q))
+            if not isinstance(tri, (tuple, list)) or len(tri) != n:
+                raise ValueError("%s: the %ss of pulse %d must be a %s" % (who, what, q, form))
             full = (A.S, ntr[q], A.nf[q], A.npos[q])
             short = (A.S, A.nf[q], A.npos[q])
             vs = [np.asarray(v, dtype=np.float64) for v in tri]
@@ -2290,7 +2303,7 @@ def _train_echo_planes(who, A, ntr, weights, targets):
     ebcast = not any(v.ndim == 4 for per in arrs for vs in per for v in vs)
     out = []
     for per in arrs:
-        planes = [[], [], []]
+        planes = [[] for _ in range(n)]
         for q, vs in enumerate(per):
             short = (A.S, A.nf[q], A.npos[q])
             for c, v in enumerate(vs):
@@ -2314,7 +2327,8 @@ def _train_rep_weights(who, rep_weights, ntr):
 
 
 def bloch_train_lsq_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
-                          phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, grad_m0=False, ctx=None):
+                          phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, grad_m0=False,
+                          magnitude=False, ctx=None):
     """Loss and gradient of a weighted least-squares fit of bloch_train_batch's echoes and final state in one device call
     (mbfir_bloch_train_lsq_batch): pulses, df, dp, ntr, phases, gains, echo, scales, m0, meq and demod as for
     bloch_train_batch.  targets and weights: per pulse a triple (x, y, z) whose entries have the echoes' shape (S, ntr, nf, npos), or
@@ -2326,7 +2340,11 @@ def bloch_train_lsq_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=
     grad = dL/dRe b1 + i dL/dIm b1 of the period's samples, complex (ntime,), with bloch_train_vjp_batch's conventions; with
     grad_m0, (L, grad, (gmx, gmy, gmz)), dL/dm0 of shape (S, nf, npos) each.  Nothing echo-sized comes back from the device.
     Deterministic: a pulse's bits depend only on the pulse, its grids, its train, its planes and the scales; targets equal to
-    bloch_train_batch's own output give L == 0.0 and a gradient of exact zeros."""
+    bloch_train_batch's own output give L == 0.0 and a gradient of exact zeros.  magnitude: fit (|Mxy|, mz) of every echo and of the
+    final state instead of the vectors (mbfir_bloch_train_lsq_mag_batch): targets, weights, targets_final and
+    weights_final are then pairs (xy, z) per pulse, with the shapes a triple's entries may have; rho = sqrt(ex ex + ey ey) has the
+    bits of np.sqrt(ex * ex + ey * ey) on bloch_train_batch's output under the same demod, a point with rho == 0 adds
+    1/2 rw w_xy t_xy^2 to L and exact zeros to the gradient, and a negative t_xy is taken as it is."""
     who = "bloch_train_lsq_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
@@ -2338,19 +2356,20 @@ def bloch_train_lsq_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=
     if targets is None and targets_final is None:
         raise ValueError("%s: neither an echo term nor a final term is given" % who)
     nul = C.cast(None, _dp)
-    eb, w, t = (0, [nul] * 3, [nul] * 3) if targets is None else _train_echo_planes(who, A, ntr, weights, targets)
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
-    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    npl = 2 if magnitude else 3
+    eb, w, t = (0, [nul] * npl, [nul] * npl) if targets is None else _train_echo_planes(who, A, ntr, weights, targets, magnitude)
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
+    tf = [nul] * npl if targets_final is None else _bloch_planes(who, "final target", targets_final, A, magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     T = sum(A.nt)
     loss, grad = np.zeros(P), [np.zeros(T) for _ in range(2)]
     gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_lsq_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
-                                                    *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
-                                                    *[_plane(v) for v in wf + tf], _ptr(loss), _ptr(grad[0]), _ptr(grad[1]),
-                                                    *[_plane(v) for v in gm])
+    fn = load_library().mbfir_bloch_train_lsq_mag_batch if magnitude else load_library().mbfir_bloch_train_lsq_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf + tf], _ptr(loss), _ptr(grad[0]), _ptr(grad[1]), *[_plane(v) for v in gm])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2361,14 +2380,17 @@ def bloch_train_lsq_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=
 
 
 def bloch_train_gn_batch(pulses, df, dp, ntr, tangents, weights, *, rep_weights=None, weights_final=None, phases=np.pi, gains=1.0,
-                         echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+                         echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, magnitude=False, ctx=None):
     """Gauss-Newton products of the fit of bloch_train_lsq_batch in one device call (mbfir_bloch_train_gn_batch):
     H v = J' W J v for J the Jacobian of (echoes, final state) in the period's b1 (real-linear in v, the scales' and gains' chain
     rule included) and W the weights, rep_weights included; arguments as for bloch_train_lsq_batch without the targets, tangents as
     bloch_train_jvp_batch takes them: per pulse a complex (n,) direction or K of them of shape (K, n), the same K for every pulse.
     weights None: no echo term.  Returns per pulse a complex (n,) array, or (K, n).  H is symmetric positive semidefinite in the real
     inner product Re sum conj(u) v.  A product's bits depend only on its pulse, grids, train, weights, direction and the scales:
-    not on the batch, on K or on the direction's place among K.  m0 is not a variable."""
+    not on the batch, on K or on the direction's place among K.  m0 is not a variable.  magnitude: the products of
+    bloch_train_lsq_batch(magnitude=True)'s fit (mbfir_bloch_train_gn_mag_batch), H = J' U' W U J with U the
+    projection on the transverse direction of every primal echo and of m_N; weights and weights_final are then pairs (xy, z).  It is
+    the Gauss-Newton matrix of the residual (rho - t_xy, e_z - t_z) and drops the curvature of rho across u."""
     who = "bloch_train_gn_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr = Tn.A, Tn.ntr
@@ -2377,15 +2399,17 @@ def bloch_train_gn_batch(pulses, df, dp, ntr, tangents, weights, *, rep_weights=
     rfs = [range(n) for n in A.nt]
     K, keep, vplanes = _tangents(who, tangents, rfs)
     nul = C.cast(None, _dp)
-    eb, w, _ = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None)
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    npl = 2 if magnitude else 3
+    eb, w, _ = (0, [nul] * npl, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None, magnitude)
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     h = [np.zeros(K * sum(A.nt)) for _ in range(2)]
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_gn_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w],
-                                                   _plane(nul if rw is None else rw), *[_plane(v) for v in wf], K,
-                                                   *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
+    fn = load_library().mbfir_bloch_train_gn_mag_batch if magnitude else load_library().mbfir_bloch_train_gn_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf], K, *[_ptr(v) for v in vplanes], _ptr(h[0]), _ptr(h[1]))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2394,7 +2418,7 @@ def bloch_train_gn_batch(pulses, df, dp, ntr, tangents, weights, *, rep_weights=
 
 def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
                                 phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, grad_gains=True,
-                                grad_phases=True, grad_m0=False, ctx=None):
+                                grad_phases=True, grad_m0=False, magnitude=False, ctx=None):
     """Loss and gradient in the schedule of a weighted least-squares fit of bloch_train_batch's echoes and final state in one device
     call (mbfir_bloch_train_lsq_sched_batch): every argument through demod as for bloch_train_lsq_batch, the loss
     being that call's L.  Returns a list of (L, grad_gains, grad_phases) per pulse: dL/dgains[k] and dL/dphases[k] (per radian) of
@@ -2405,7 +2429,9 @@ def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_we
     device, and with point-sized targets and weights nothing echo-sized goes up.  The period is swept once more per (scale,
     distinct gain) for the gains, not at all for the phases.  Deterministic: a pulse's bits depend only on the pulse, its grids, its
     train, its planes and the scales, and a wanted half does not depend on whether the other was asked for; targets equal to
-    bloch_train_batch's own output give L == 0.0 and gradients of exact zeros."""
+    bloch_train_batch's own output give L == 0.0 and gradients of exact zeros.  magnitude: as for bloch_train_lsq_batch, the fit of
+    (|Mxy|, mz) of every echo and of the final state (mbfir_bloch_train_lsq_sched_mag_batch); targets and weights
+    are then pairs (xy, z) per pulse."""
     who = "bloch_train_lsq_sched_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
@@ -2419,9 +2445,11 @@ def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_we
     if not grad_gains and not grad_phases:
         raise ValueError("%s: neither the gradient in the gains nor the gradient in the phases is wanted" % who)
     nul = C.cast(None, _dp)
-    eb, w, t = (0, [nul] * 3, [nul] * 3) if targets is None else _train_echo_planes(who, A, ntr, weights, targets)
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
-    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    npl = 2 if magnitude else 3
+    eb, w, t = (0, [nul] * npl, [nul] * npl) if targets is None else _train_echo_planes(who, A, ntr, weights, targets, magnitude)
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
+    tf = [nul] * npl if targets_final is None else _bloch_planes(who, "final target", targets_final, A, magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     roff = _offsets(ntr)
@@ -2430,11 +2458,10 @@ def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_we
     gp = np.zeros(int(roff[-1])) if grad_phases else None
     gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_lsq_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
-                                                          *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
-                                                          *[_plane(v) for v in wf + tf], _ptr(loss),
-                                                          nul if gg is None else _ptr(gg), nul if gp is None else _ptr(gp),
-                                                          *[_plane(v) for v in gm])
+    fn = load_library().mbfir_bloch_train_lsq_sched_mag_batch if magnitude else load_library().mbfir_bloch_train_lsq_sched_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf + tf], _ptr(loss), nul if gg is None else _ptr(gg), nul if gp is None else _ptr(gp),
+            *[_plane(v) for v in gm])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2447,7 +2474,7 @@ def bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, *, rep_we
 
 def bloch_train_gn_sched_batch(pulses, df, dp, ntr, weights, *, tangents_gains=None, tangents_phases=None, rep_weights=None,
                                weights_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False,
-                               prod_gains=None, prod_phases=None, ctx=None):
+                               prod_gains=None, prod_phases=None, magnitude=False, ctx=None):
     """Gauss-Newton products of the fit of bloch_train_lsq_sched_batch in one device call (mbfir_bloch_train_gn_sched_batch, DESIGN
     section 8af): H v = J' W J v for J the Jacobian of (echoes, final state) in the schedule (gains, phases) and W the weights,
     rep_weights included; arguments as for bloch_train_lsq_sched_batch without the targets.  tangents_gains / tangents_phases: as
@@ -2459,7 +2486,8 @@ def bloch_train_gn_sched_batch(pulses, df, dp, ntr, weights, *, tangents_gains=N
     semidefinite.  The period is swept once more per (scale, distinct gain) only when a gains direction or the gains half is asked
     for.  A product's bits depend only on its pulse, grids, train, weights, direction and the scales: not on the batch, on K, on
     the direction's place among K, on whether an all-zero half was passed as None, or on whether the other half was asked for.  m0
-    is not a variable."""
+    is not a variable.  magnitude: the products of bloch_train_lsq_sched_batch(magnitude=True)'s fit
+    (mbfir_bloch_train_gn_sched_mag_batch), as for bloch_train_gn_batch; weights are then pairs (xy, z)."""
     who = "bloch_train_gn_sched_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr = Tn.A, Tn.ntr
@@ -2483,18 +2511,20 @@ def bloch_train_gn_sched_batch(pulses, df, dp, ntr, weights, *, tangents_gains=N
     if not want_g and not want_p:
         raise ValueError("%s: neither the product's gains half nor its phases half is wanted" % who)
     nul = C.cast(None, _dp)
-    eb, w, _ = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None)
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
+    npl = 2 if magnitude else 3
+    eb, w, _ = (0, [nul] * npl, None) if weights is None else _train_echo_planes(who, A, ntr, weights, None, magnitude)
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     roff = _offsets(ntr)
     hg = np.zeros(K * int(roff[-1])) if want_g else None
     hp = np.zeros(K * int(roff[-1])) if want_p else None
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_gn_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
-                                                         *[_plane(v) for v in w], _plane(nul if rw is None else rw),
-                                                         *[_plane(v) for v in wf], K, *[nul if v is None else _ptr(v) for v in parts],
-                                                         nul if hg is None else _ptr(hg), nul if hp is None else _ptr(hp))
+    fn = load_library().mbfir_bloch_train_gn_sched_mag_batch if magnitude else load_library().mbfir_bloch_train_gn_sched_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf], K, *[nul if v is None else _ptr(v) for v in parts], nul if hg is None else _ptr(hg),
+            nul if hp is None else _ptr(hp))
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -2516,13 +2546,13 @@ def _sched_vary(who, vary):
 
 
 def bloch_train_normal_sched_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), rep_weights=None,
-                                   targets_final=None, weights_final=None, **kw):
+                                   targets_final=None, weights_final=None, magnitude=False, **kw):
     """Loss, gradient and dense Gauss-Newton matrix of the fit of bloch_train_lsq_sched_batch in the schedule:
     one bloch_train_lsq_sched_batch call and one bloch_train_gn_sched_batch call with the n unit directions, n = ntr x len(vary), the
     gains first.  The pulses of a call share ntr (an int).  vary: ("gains", "phases"), ("gains",) or ("phases",); without "gains" the
     period's tangent is never launched.  Keywords as bloch_train_lsq_sched_batch's, without the grad_ flags.  Returns per pulse
     (L, g, H): g float64 of length n, H of shape (n, n), row j the product H e_j as the device returned it (symmetric to rounding;
-    the caller symmetrises)."""
+    the caller symmetrises).  magnitude: both calls with magnitude=True, targets and weights pairs (xy, z)."""
     who = "bloch_train_normal_sched_batch"
     for k in ("grad_gains", "grad_phases", "grad_m0", "tangents_gains", "tangents_phases", "prod_gains", "prod_phases"):
         if k in kw:
@@ -2536,6 +2566,8 @@ def bloch_train_normal_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
     if n[0] < 1:
         raise ValueError("%s: ntr of pulse 0 must be at least 1" % who)
     N = n[0]
+    if magnitude:                                         # without it, exactly the calls made before the flag existed
+        kw = dict(kw, magnitude=True)
     lsq = bloch_train_lsq_sched_batch(pulses, df, dp, ntr, targets, weights, rep_weights=rep_weights, targets_final=targets_final,
                                       weights_final=weights_final, grad_gains=vg, grad_phases=vp, **kw)
     eye, zero = np.eye(N), np.zeros((N, N))
@@ -3101,7 +3133,7 @@ def bloch_ss_lm_step_batch(pulses, df, dp, rhs, weights, mu, *, targets=None, cg
 
 def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=None, rep_weights=None, targets_final=None,
                               weights_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, cg=8,
-                              rtol=1e-6, ctx=None):
+                              rtol=1e-6, magnitude=False, ctx=None):
     """bloch_lm_step_batch for the echoes of a pulse train, bloch_train_batch's model (mbfir_bloch_train_lm_step_batch, DESIGN section
     8ac): conjugate gradients on (H + mu I) d = rhs from d = 0, H = J' W J as bloch_train_gn_batch applies it (echo term, rep_weights,
     final term, the scales' and gains' chain rule), solved on the device in one call.  pulses (each one period), df, dp, ntr,
@@ -3112,7 +3144,9 @@ def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=
     ('rtol', 'cg' or 'breakdown'), and with targets 'loss' and 'grad'.  b1 is fixed within the solve, so the propagators' planes
     and the checkpoints of the period's adjoint are computed once per call.  The host reads nothing between the iterations, so cg is
     also a launch count.  Deterministic: a pulse's results depend only on the pulse, its grids, its train, weights, targets, m0, rhs,
-    mu, cg, rtol and the scales, not on the batch or when its neighbours stop."""
+    mu, cg, rtol and the scales, not on the batch or when its neighbours stop.  magnitude: the step of the magnitude fit
+    (mbfir_bloch_train_lm_step_mag_batch): H as bloch_train_gn_batch(magnitude=True) applies it, the trial's loss
+    and gradient with the bits of bloch_train_lsq_batch(magnitude=True); weights and targets are then pairs (xy, z) per pulse."""
     who = "bloch_train_lm_step_batch"
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
     A, ntr = Tn.A, Tn.ntr
@@ -3128,20 +3162,21 @@ def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=
     rfs = [range(n) for n in A.nt]
     bplanes, m, cg, rtol = _lm_args(who, rfs, rhs, mu, cg, rtol)
     nul = C.cast(None, _dp)
-    eb, w, t = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets)
-    t = [nul] * 3 if t is None else t
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
-    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    npl = 2 if magnitude else 3
+    eb, w, t = (0, [nul] * npl, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets, magnitude)
+    t = [nul] * npl if t is None else t
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
+    tf = [nul] * npl if targets_final is None else _bloch_planes(who, "final target", targets_final, A, magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     P, T = A.P, sum(A.nt)
     out = [np.zeros(T), np.zeros(T), np.zeros(P, dtype=np.int32), np.zeros(P), np.zeros(P), np.zeros(P, dtype=np.int32)]
     out += [np.zeros(P), np.zeros(T), np.zeros(T)] if trial else [None, None, None]
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_lm_step_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
-                                                        *[_plane(v) for v in w], _plane(nul if rw is None else rw),
-                                                        *[_plane(v) for v in wf], *[_ptr(v) for v in bplanes], _ptr(m), cg,
-                                                        C.c_double(rtol), *[_plane(v) for v in t + tf + out])
+    fn = load_library().mbfir_bloch_train_lm_step_mag_batch if magnitude else load_library().mbfir_bloch_train_lm_step_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf], *[_ptr(v) for v in bplanes], _ptr(m), cg, C.c_double(rtol), *[_plane(v) for v in t + tf + out])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)
@@ -3150,7 +3185,7 @@ def bloch_train_lm_step_batch(pulses, df, dp, ntr, rhs, weights, mu, *, targets=
 
 def bloch_train_lm_step_sched_batch(pulses, df, dp, ntr, weights, mu, *, vary=("gains", "phases"), b=None, targets=None,
                                     targets_final=None, cg=8, rtol=1e-6, rep_weights=None, weights_final=None, phases=np.pi, gains=1.0,
-                                    echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+                                    echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, magnitude=False, ctx=None):
     """The Levenberg-Marquardt step of a train's schedule, the gain and the RF phase of every repetition, evaluated and solved at the
     same schedule in one device call (mbfir_bloch_train_lm_step_sched_batch), so that the propagators of a
     schedule are swept once for both.  pulses, df, dp, ntr, weights, rep_weights, weights_final, phases, gains, echo, scales, m0, meq
@@ -3165,7 +3200,9 @@ def bloch_train_lm_step_sched_batch(pulses, df, dp, ntr, weights, mu, *, vary=("
     'ncg', 'rr', 'gg' and 'status' ('rtol', 'cg' or 'breakdown'), and with targets 'loss', 'grad_gains' and 'grad_phases' (None for a
     half not varied).  Without "gains" in vary the period's tangent is never launched.  Deterministic: a pulse's results depend only
     on the pulse, its grids, its train, weights, targets, m0, b, mu, cg, rtol and the scales, not on the batch or when its neighbours
-    stop."""
+    stop.  magnitude: the step of the magnitude fit (mbfir_bloch_train_lm_step_sched_mag_batch): the evaluation
+    with the bits of bloch_train_lsq_sched_batch(magnitude=True), H as bloch_train_gn_sched_batch(magnitude=True) applies it; weights
+    and targets are then pairs (xy, z) per pulse."""
     who = "bloch_train_lm_step_sched_batch"
     vg, vp = _sched_vary(who, vary)
     Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
@@ -3213,10 +3250,12 @@ def bloch_train_lm_step_sched_batch(pulses, df, dp, ntr, weights, mu, *, vary=("
                     halves[i].append(v)
         bplanes = [_vec(np.concatenate(h)) if on else None for h, on in zip(halves, (vg, vp))]
     nul = C.cast(None, _dp)
-    eb, w, t = (0, [nul] * 3, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets)
-    t = [nul] * 3 if t is None else t
-    wf = [nul] * 3 if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True)
-    tf = [nul] * 3 if targets_final is None else _bloch_planes(who, "final target", targets_final, A)
+    npl = 2 if magnitude else 3
+    eb, w, t = (0, [nul] * npl, None) if weights is None else _train_echo_planes(who, A, ntr, weights, targets, magnitude)
+    t = [nul] * npl if t is None else t
+    wf = [nul] * npl if weights_final is None else _bloch_planes(who, "final weight", weights_final, A, weights=True,
+                                                                 magnitude=magnitude)
+    tf = [nul] * npl if targets_final is None else _bloch_planes(who, "final target", targets_final, A, magnitude=magnitude)
     rw = _train_rep_weights(who, rep_weights, ntr)
     m0p = _bloch_m0(A, m0)
     roff = _offsets(ntr)
@@ -3226,12 +3265,11 @@ def bloch_train_lm_step_sched_batch(pulses, df, dp, ntr, weights, mu, *, vary=("
     loss = np.zeros(P) if evalu else None
     g = [np.zeros(R) if on and evalu else None for on in (vg, vp)]
     ctx = ctx or get_context()
-    rc = load_library().mbfir_bloch_train_lm_step_sched_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb,
-                                                              *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
-                                                              *[_plane(v) for v in wf + tf],
-                                                              *[_plane(nul if v is None else v) for v in bplanes], _ptr(m), int(cg),
-                                                              C.c_double(float(rtol)),
-                                                              *[_plane(nul if v is None else v) for v in d + st + [loss] + g])
+    lib = load_library()
+    fn = lib.mbfir_bloch_train_lm_step_sched_mag_batch if magnitude else lib.mbfir_bloch_train_lm_step_sched_batch
+    rc = fn(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p], eb, *[_plane(v) for v in w + t], _plane(nul if rw is None else rw),
+            *[_plane(v) for v in wf + tf], *[_plane(nul if v is None else v) for v in bplanes], _ptr(m), int(cg),
+            C.c_double(float(rtol)), *[_plane(nul if v is None else v) for v in d + st + [loss] + g])
     if rc == E_ARG:
         raise ValueError(ctx.last_error())
     _check(ctx, rc)

@@ -1790,6 +1790,10 @@ int mbfir_bloch_train_jvp_sched_batch(mbfir_ctx* ctx, int npulse, const long* to
 
 int mbfir_test_bloch_train_sched_jvp_group() { return bloch_train_sched_jvp_group(); }
 
+// The six train calls below (lsq, gn and the device step, in b1 and in the schedule) have magnitude twins (mbfir_bloch_train_*_mag_batch,
+// DESIGN 8ai) that take pairs (xy, z) where they take triples: each pair of twins is one body, `mag` telling which; with it a pair lies
+// in the first two entries of its triple, the third is null and is not asked for, and every check, its place and its message are
+// the same.
 // The train's fused products (blochtraingn.hip).  What both calls check after bloch_train_check, in this order: ebcast,
 // the echo and final planes given whole or not at all and not both absent, the outputs, then (bloch_train_gn_check) the sizes, before
 // any plane is read: the adjoint's partials, checkpoints and workgroups (bloch_train_vjp_fits) and, per direction, the planes' tangents and
@@ -1826,33 +1830,37 @@ static int bloch_train_gn_check(mbfir_ctx* ctx, const char* who, int npulse, int
     if (toff[npulse] > (1L << 56) / ndir || wsp > (1L << 56) || part > (1L << 56) || ckr > (1L << 56) || wgr > 2147483647L ||
         wgf > 2147483647L)
         return bad("the output size or the workgroup count overflows");
-    for (int c = 0; c < 3; ++c)
-        if ((w[0] && neg(w[c], ebcast ? O : E)) || (wf[0] && neg(wf[c], O))) return bad("a weight is negative or not finite");
+    for (int c = 0; c < 3; ++c)                                           // the magnitude calls have two planes: their third is null
+        if ((w[0] && w[c] && neg(w[c], ebcast ? O : E)) || (wf[0] && wf[c] && neg(wf[c], O)))
+            return bad("a weight is negative or not finite");
     if (rw && neg(rw, roff[npulse])) return bad("a repetition weight is negative or not finite");
     return 0;
 }
 
-int mbfir_bloch_train_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
-                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
-                                int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
-                                const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
-                                const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
-                                const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
-                                const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
-                                const double* tfz, double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz) {
+static int bloch_train_lsq_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                      const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                      const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                      const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                                      int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                      int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                      const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                      const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                      const double* m0z, int ebcast, const double* wx, const double* wy, const double* wz,
+                                      const double* tx, const double* ty, const double* tz, const double* rw, const double* wfx,
+                                      const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                      const double* tfz, double* loss, double* g_re, double* g_im, double* gmx, double* gmy,
+                                      double* gmz) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lsq_batch: " + why; return MBFIR_E_ARG; };
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
                         roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_train_check(ctx, "bloch_train_lsq_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
                                         arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
-    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && wz && tx && ty && tz;
-    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && wfz && tfx && tfy && tfz;
+    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && (mag || wz) && tx && ty && (mag || tz);
+    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && (mag || wfz) && tfx && tfy && (mag || tfz);
     if (any_e && !all_e) return bad("the echo weights and targets are given together or not at all");
     if (any_f && !all_f) return bad("the final weights and targets are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
@@ -1862,42 +1870,78 @@ int mbfir_bloch_train_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
     const double* const t[3] = {tx, ty, tz};
     const double* const wf[3] = {wfx, wfy, wfz};
     const double* const tf[3] = {tfx, tfy, tfz};
-    if (const int e = bloch_train_gn_check(ctx, "bloch_train_lsq_batch", npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
+    if (const int e = bloch_train_gn_check(ctx, who, npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
                                            npoint.data(), ebcast, w, rw, wf))
         return e;
     MBFIR_TRY(ctx, bloch_train_lsq_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
                                              t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
                                              cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, t, rw, wf,
-                                             tf, loss, g_re, g_im, gmx, gmy, gmz));
+                                             tf, loss, g_re, g_im, gmx, gmy, gmz, mag));
+}
+int mbfir_bloch_train_lsq_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
+                                const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                const double* tfz, double* loss, double* g_re, double* g_im, double* gmx, double* gmy,
+                                double* gmz) {
+    return bloch_train_lsq_batch_call(ctx, "bloch_train_lsq_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                      t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
+                                      cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, wx, wy, wz, tx,
+                                      ty, tz, rw, wfx, wfy, wfz, tfx, tfy, tfz, loss, g_re, g_im, gmx, gmy, gmz);
+}
+int mbfir_bloch_train_lsq_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                    const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                    const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                    const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                    const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                    const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                    const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wxy,
+                                    const double* wz, const double* txy, const double* tz, const double* rw, const double* wfxy,
+                                    const double* wfz, const double* tfxy, const double* tfz, double* loss, double* g_re,
+                                    double* g_im, double* gmx, double* gmy, double* gmz) {
+    return bloch_train_lsq_batch_call(ctx, "bloch_train_lsq_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                      tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
+                                      roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, wxy, wz,
+                                      nullptr, txy, tz, nullptr, rw, wfxy, wfz, nullptr, tfxy, tfz, nullptr, loss, g_re, g_im,
+                                      gmx, gmy, gmz);
 }
 
-int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
-                               const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
-                               int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
-                               const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
-                               const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
-                               const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz, int ndir,
-                               const double* v_re, const double* v_im, double* h_re, double* h_im) {
+static int bloch_train_gn_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                     const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                     const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                     const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                                     int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                     int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                     const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
+                                     const double* m0z, int ebcast, const double* wx, const double* wy, const double* wz,
+                                     const double* rw, const double* wfx, const double* wfy, const double* wfz, int ndir,
+                                     const double* v_re, const double* v_im, double* h_re, double* h_im) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_gn_batch: " + why; return MBFIR_E_ARG; };
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
                         roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_train_check(ctx, "bloch_train_gn_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff, nscale,
                                         arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint, ncomb))
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
     const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
-    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
-    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (any_e && !(wx && wy && (mag || wz))) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && (mag || wfz))) return bad("the final weights are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
     if (!v_re || !v_im || !h_re || !h_im) return bad("a direction or product plane is null");
     if (ndir < 1) return bad("ndir must be at least 1");
     const double* const w[3] = {wx, wy, wz};
     const double* const wf[3] = {wfx, wfy, wfz};
-    if (const int e = bloch_train_gn_check(ctx, "bloch_train_gn_batch", npulse, nscale, ndir, toff, ntr, roff, ncomb.data(),
+    if (const int e = bloch_train_gn_check(ctx, who, npulse, nscale, ndir, toff, ntr, roff, ncomb.data(),
                                            npoint.data(), ebcast, w, rw, wf))
         return e;
     if (!bloch_train_jvp_fits(npulse, nscale, ndir, toff, ntr, ncomb.data(), npoint.data()))
@@ -1905,7 +1949,37 @@ int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, con
     MBFIR_TRY(ctx, bloch_train_gn_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
                                             t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
                                             cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, rw, wf, ndir,
-                                            v_re, v_im, h_re, h_im));
+                                            v_re, v_im, h_re, h_im, mag));
+}
+int mbfir_bloch_train_gn_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                               const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                               const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                               const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                               const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                               const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                               const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz,
+                               int ndir, const double* v_re, const double* v_im, double* h_re, double* h_im) {
+    return bloch_train_gn_batch_call(ctx, "bloch_train_gn_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps,
+                                     t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr, roff,
+                                     cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, wx, wy, wz, rw,
+                                     wfx, wfy, wfz, ndir, v_re, v_im, h_re, h_im);
+}
+int mbfir_bloch_train_gn_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                   const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                   const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                   const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                   const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                   const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                   const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                   const double* m0y, const double* m0z, int ebcast, const double* wxy, const double* wz,
+                                   const double* rw, const double* wfxy, const double* wfz, int ndir, const double* v_re,
+                                   const double* v_im, double* h_re, double* h_im) {
+    return bloch_train_gn_batch_call(ctx, "bloch_train_gn_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                     tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
+                                     roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, wxy, wz,
+                                     nullptr, rw, wfxy, wfz, nullptr, ndir, v_re, v_im, h_re, h_im);
 }
 
 // The fused products of the train's schedule (blochtrainschedgn.hip).  What both calls check after bloch_train_check, in
@@ -1946,36 +2020,39 @@ static int bloch_train_sched_gn_check(mbfir_ctx* ctx, const char* who, int npuls
     if (roff[npulse] > (1L << 56) / ndir || wsp > (1L << 56) || part > (1L << 56) || ckr > (1L << 56) || wgp > 2147483647L ||
         wgr > 2147483647L || wgf > 2147483647L)
         return bad("the output size or the workgroup count overflows");
-    for (int c = 0; c < 3; ++c)
-        if ((w[0] && neg(w[c], ebcast ? O : E)) || (wf[0] && neg(wf[c], O))) return bad("a weight is negative or not finite");
+    for (int c = 0; c < 3; ++c)                                           // the magnitude calls have two planes: their third is null
+        if ((w[0] && w[c] && neg(w[c], ebcast ? O : E)) || (wf[0] && wf[c] && neg(wf[c], O)))
+            return bad("a weight is negative or not finite");
     if (rw && neg(rw, roff[npulse])) return bad("a repetition weight is negative or not finite");
     return 0;
 }
 
-int mbfir_bloch_train_lsq_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                                      const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                                      const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
-                                      const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
-                                      const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
-                                      const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
-                                      const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
-                                      const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
-                                      const double* wz, const double* tx, const double* ty, const double* tz, const double* rw,
-                                      const double* wfx, const double* wfy, const double* wfz, const double* tfx, const double* tfy,
-                                      const double* tfz, double* loss, double* ggain, double* gphi, double* gmx, double* gmy,
-                                      double* gmz) {
+static int bloch_train_lsq_sched_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                            const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                            const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                            const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                            const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
+                                            const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
+                                            const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                            const double* gains, const int* echo, const double* meq, int demod,
+                                            const double* m0x, const double* m0y, const double* m0z, int ebcast,
+                                            const double* wx, const double* wy, const double* wz, const double* tx,
+                                            const double* ty, const double* tz, const double* rw, const double* wfx,
+                                            const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                            const double* tfz, double* loss, double* ggain, double* gphi, double* gmx,
+                                            double* gmy, double* gmz) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lsq_sched_batch: " + why; return MBFIR_E_ARG; };
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
                         roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_train_check(ctx, "bloch_train_lsq_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
                                         nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
                                         ncomb))
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
-    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && wz && tx && ty && tz;
-    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && wfz && tfx && tfy && tfz;
+    const bool any_e = wx || wy || wz || tx || ty || tz, all_e = wx && wy && (mag || wz) && tx && ty && (mag || tz);
+    const bool any_f = wfx || wfy || wfz || tfx || tfy || tfz, all_f = wfx && wfy && (mag || wfz) && tfx && tfy && (mag || tfz);
     if (any_e && !all_e) return bad("the echo weights and targets are given together or not at all");
     if (any_f && !all_f) return bad("the final weights and targets are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
@@ -1986,51 +2063,121 @@ int mbfir_bloch_train_lsq_sched_batch(mbfir_ctx* ctx, int npulse, const long* to
     const double* const t[3] = {tx, ty, tz};
     const double* const wf[3] = {wfx, wfy, wfz};
     const double* const tf[3] = {tfx, tfy, tfz};
-    if (const int e = bloch_train_sched_gn_check(ctx, "bloch_train_lsq_sched_batch", npulse, nscale, 1, 1, ntr, roff, ncomb.data(),
+    if (const int e = bloch_train_sched_gn_check(ctx, who, npulse, nscale, 1, 1, ntr, roff, ncomb.data(),
                                                  npoint.data(), ebcast, w, rw, wf))
         return e;
     MBFIR_TRY(ctx, bloch_train_lsq_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
                                                    tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
                                                    ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z,
-                                                   ebcast, w, t, rw, wf, tf, loss, ggain, gphi, gmx, gmy, gmz));
+                                                   ebcast, w, t, rw, wf, tf, loss, ggain, gphi, gmx, gmy, gmz, mag));
+}
+int mbfir_bloch_train_lsq_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                      const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                      const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                      const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                      const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                      const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                      const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                      const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
+                                      const double* wy, const double* wz, const double* tx, const double* ty, const double* tz,
+                                      const double* rw, const double* wfx, const double* wfy, const double* wfz,
+                                      const double* tfx, const double* tfy, const double* tfz, double* loss, double* ggain,
+                                      double* gphi, double* gmx, double* gmy, double* gmz) {
+    return bloch_train_lsq_sched_batch_call(ctx, "bloch_train_lsq_sched_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz,
+                                            tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                            scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y,
+                                            m0z, ebcast, wx, wy, wz, tx, ty, tz, rw, wfx, wfy, wfz, tfx, tfy, tfz, loss, ggain,
+                                            gphi, gmx, gmy, gmz);
+}
+int mbfir_bloch_train_lsq_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                          const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                          int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                          const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                          const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                          const int* gidx, const long* goff, const double* gains, const int* echo,
+                                          const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                          int ebcast, const double* wxy, const double* wz, const double* txy, const double* tz,
+                                          const double* rw, const double* wfxy, const double* wfz, const double* tfxy,
+                                          const double* tfz, double* loss, double* ggain, double* gphi, double* gmx, double* gmy,
+                                          double* gmz) {
+    return bloch_train_lsq_sched_batch_call(ctx, "bloch_train_lsq_sched_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz,
+                                            tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                            scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y,
+                                            m0z, ebcast, wxy, wz, nullptr, txy, tz, nullptr, rw, wfxy, wfz, nullptr, tfxy, tfz,
+                                            nullptr, loss, ggain, gphi, gmx, gmy, gmz);
 }
 
-int mbfir_bloch_train_gn_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
-                                     const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
-                                     const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
-                                     const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
-                                     const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
-                                     const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
-                                     const double* wz, const double* rw, const double* wfx, const double* wfy, const double* wfz,
-                                     int ndir, const double* dgain, const double* dphi, double* hgain, double* hphi) {
+static int bloch_train_gn_sched_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                           const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                           const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                           const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                                           int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                           int nscale, const double* scales, const int* ntr, const long* roff,
+                                           const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                           const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                           const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                           const double* wz, const double* rw, const double* wfx, const double* wfy,
+                                           const double* wfz, int ndir, const double* dgain, const double* dphi, double* hgain,
+                                           double* hphi) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_gn_sched_batch: " + why; return MBFIR_E_ARG; };
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
                         roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_train_check(ctx, "bloch_train_gn_sched_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
                                         nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
                                         ncomb))
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
     const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
-    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
-    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (any_e && !(wx && wy && (mag || wz))) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && (mag || wfz))) return bad("the final weights are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
     if (!hgain && !hphi) return bad("neither the product's gains half nor its phases half is wanted");
     if (!dgain && !dphi) return bad("no direction is given: dgain and dphi are both null");
     if (ndir < 1) return bad("ndir must be at least 1");
     const double* const w[3] = {wx, wy, wz};
     const double* const wf[3] = {wfx, wfy, wfz};
-    if (const int e = bloch_train_sched_gn_check(ctx, "bloch_train_gn_sched_batch", npulse, nscale, ndir, 2, ntr, roff, ncomb.data(),
+    if (const int e = bloch_train_sched_gn_check(ctx, who, npulse, nscale, ndir, 2, ntr, roff, ncomb.data(),
                                                  npoint.data(), ebcast, w, rw, wf))
         return e;
     MBFIR_TRY(ctx, bloch_train_gn_sched_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
                                                   tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales,
                                                   ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast,
-                                                  w, rw, wf, ndir, dgain, dphi, hgain, hphi));
+                                                  w, rw, wf, ndir, dgain, dphi, hgain, hphi, mag));
+}
+int mbfir_bloch_train_gn_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                     const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                     const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                     const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                     const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                     const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                     const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                     const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
+                                     const double* wy, const double* wz, const double* rw, const double* wfx, const double* wfy,
+                                     const double* wfz, int ndir, const double* dgain, const double* dphi, double* hgain,
+                                     double* hphi) {
+    return bloch_train_gn_sched_batch_call(ctx, "bloch_train_gn_sched_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz,
+                                           tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                           scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z,
+                                           ebcast, wx, wy, wz, rw, wfx, wfy, wfz, ndir, dgain, dphi, hgain, hphi);
+}
+int mbfir_bloch_train_gn_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                         const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                         const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                         int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                         const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                         const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                         const int* gidx, const long* goff, const double* gains, const int* echo,
+                                         const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                         int ebcast, const double* wxy, const double* wz, const double* rw, const double* wfxy,
+                                         const double* wfz, int ndir, const double* dgain, const double* dphi, double* hgain,
+                                         double* hphi) {
+    return bloch_train_gn_sched_batch_call(ctx, "bloch_train_gn_sched_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz,
+                                           tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                           scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z,
+                                           ebcast, wxy, wz, nullptr, rw, wfxy, wfz, nullptr, ndir, dgain, dphi, hgain, hphi);
 }
 
 int mbfir_bloch_prop_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im, const double* gx,
@@ -2555,45 +2702,48 @@ int mbfir_bloch_ss_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* tof
 // The train's step (blochtrainlm.hip): bloch_train_check, the checks of mbfir_bloch_train_gn_batch at ndir = 1 with their
 // messages and order (ebcast, the weights, the sizes), bloch_lm_check's for its own arrays, mu, cg and rtol, then the targets:
 // each triple whole or absent, and, when any is given, one for every term that has weights and none for a term that has not.
-int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                                    const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
-                                    const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
-                                    const double* df, int npgrid, const long* poff, const double* dx, const double* dy,
-                                    const double* dz, int nscale, const double* scales, const int* ntr, const long* roff,
-                                    const double* cosphi, const double* sinphi, const int* gidx, const long* goff, const double* gains,
-                                    const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
-                                    const double* m0z, int ebcast, const double* wx, const double* wy, const double* wz,
-                                    const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* b_re,
-                                    const double* b_im, const double* mu, int cg, double rtol, const double* tx, const double* ty,
-                                    const double* tz, const double* tfx, const double* tfy, const double* tfz, double* d_re,
-                                    double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss, double* g_re,
-                                    double* g_im) {
+static int bloch_train_lm_step_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                          const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                          const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                          const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
+                                          int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                          int nscale, const double* scales, const int* ntr, const long* roff,
+                                          const double* cosphi, const double* sinphi, const int* gidx, const long* goff,
+                                          const double* gains, const int* echo, const double* meq, int demod, const double* m0x,
+                                          const double* m0y, const double* m0z, int ebcast, const double* wx, const double* wy,
+                                          const double* wz, const double* rw, const double* wfx, const double* wfy,
+                                          const double* wfz, const double* b_re, const double* b_im, const double* mu, int cg,
+                                          double rtol, const double* tx, const double* ty, const double* tz, const double* tfx,
+                                          const double* tfy, const double* tfz, double* d_re, double* d_im, int* ncg, double* rr,
+                                          double* gg, int* status, double* loss, double* g_re, double* g_im) {
     if (!ctx) return MBFIR_E_ARG;
-    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_lm_step_batch: " + why; return MBFIR_E_ARG; };
+    auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
                         roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
-    if (const int e = bloch_train_check(ctx, "bloch_train_lm_step_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+    if (const int e = bloch_train_check(ctx, who, npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
                                         nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
                                         ncomb))
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
     const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
-    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
-    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (any_e && !(wx && wy && (mag || wz))) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && (mag || wfz))) return bad("the final weights are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
     const double* const w[3] = {wx, wy, wz};
     const double* const wf[3] = {wfx, wfy, wfz};
-    if (const int e = bloch_train_gn_check(ctx, "bloch_train_lm_step_batch", npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
+    if (const int e = bloch_train_gn_check(ctx, who, npulse, nscale, 1, toff, ntr, roff, ncomb.data(),
                                            npoint.data(), ebcast, w, rw, wf))
         return e;
     if (!bloch_train_jvp_fits(npulse, nscale, 1, toff, ntr, ncomb.data(), npoint.data()))
         return bad("the output size or the workgroup count overflows");
     const bool tg_e = tx || ty || tz, tg_f = tfx || tfy || tfz, targets = tg_e || tg_f;
     const bool own = b_re && b_im && mu && d_re && d_im && ncg && rr && gg && status && (!targets || (loss && g_re && g_im));
-    if (const int e = bloch_lm_check(ctx, "bloch_train_lm_step_batch", own, true, npulse, toff, mu, cg, rtol)) return e;
-    if (tg_e && !(tx && ty && tz)) return bad("tx, ty and tz are given together or not at all");
-    if (tg_f && !(tfx && tfy && tfz)) return bad("tfx, tfy and tfz are given together or not at all");
+    if (const int e = bloch_lm_check(ctx, who, own, true, npulse, toff, mu, cg, rtol)) return e;
+    if (tg_e && !(tx && ty && (mag || tz)))
+        return bad(mag ? "txy and tz are given together or not at all" : "tx, ty and tz are given together or not at all");
+    if (tg_f && !(tfx && tfy && (mag || tfz)))
+        return bad(mag ? "tfxy and tfz are given together or not at all" : "tfx, tfy and tfz are given together or not at all");
     if ((tg_e && !any_e) || (tg_f && !any_f)) return bad("a target is given for a term that has no weights");
     if (targets && ((any_e && !tg_e) || (any_f && !tg_f))) return bad("a term that has weights has no target while the other has one");
     const double* const t[3] = {tx, ty, tz};
@@ -2602,28 +2752,68 @@ int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff
                                                  tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
                                                  roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, w, rw,
                                                  wf, b_re, b_im, mu, cg, rtol, t, tf, d_re, d_im, ncg, rr, gg, status, loss, g_re,
-                                                 g_im));
+                                                 g_im, mag));
+}
+int mbfir_bloch_train_lm_step_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                    const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                    const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
+                                    const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
+                                    const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
+                                    const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
+                                    const long* goff, const double* gains, const int* echo, const double* meq, int demod,
+                                    const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
+                                    const double* wy, const double* wz, const double* rw, const double* wfx, const double* wfy,
+                                    const double* wfz, const double* b_re, const double* b_im, const double* mu, int cg,
+                                    double rtol, const double* tx, const double* ty, const double* tz, const double* tfx,
+                                    const double* tfy, const double* tfz, double* d_re, double* d_im, int* ncg, double* rr,
+                                    double* gg, int* status, double* loss, double* g_re, double* g_im) {
+    return bloch_train_lm_step_batch_call(ctx, "bloch_train_lm_step_batch", false, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                          tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
+                                          roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, ebcast, wx,
+                                          wy, wz, rw, wfx, wfy, wfz, b_re, b_im, mu, cg, rtol, tx, ty, tz, tfx, tfy, tfz, d_re,
+                                          d_im, ncg, rr, gg, status, loss, g_re, g_im);
+}
+int mbfir_bloch_train_lm_step_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                        const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                        const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                        int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                        const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                        const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                        const int* gidx, const long* goff, const double* gains, const int* echo,
+                                        const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                        int ebcast, const double* wxy, const double* wz, const double* rw, const double* wfxy,
+                                        const double* wfz, const double* b_re, const double* b_im, const double* mu, int cg,
+                                        double rtol, const double* txy, const double* tz, const double* tfxy, const double* tfz,
+                                        double* d_re, double* d_im, int* ncg, double* rr, double* gg, int* status, double* loss,
+                                        double* g_re, double* g_im) {
+    return bloch_train_lm_step_batch_call(ctx, "bloch_train_lm_step_mag_batch", true, npulse, toff, b1_re, b1_im, gx, gy, gz,
+                                          tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
+                                          scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z,
+                                          ebcast, wxy, wz, nullptr, rw, wfxy, wfz, nullptr, b_re, b_im, mu, cg, rtol, txy, tz,
+                                          nullptr, tfxy, tfz, nullptr, d_re, d_im, ncg, rr, gg, status, loss, g_re, g_im);
 }
 
 // The schedule's step (blochtrainschedlm.hip): bloch_train_check, then the checks mbfir_bloch_train_lsq_sched_batch and
 // mbfir_bloch_train_gn_sched_batch at ndir = 1 share, in their order and with their messages (ebcast, the weights, both terms absent,
 // both halves absent, the sizes at two checkpointed states), bloch_lm_check's for its own arrays, mu, cg and rtol, then the halves
 // (nothing given for a half that does not vary), the targets as mbfir_bloch_train_lm_step_batch checks them, and the right-hand side.
-int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
-                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
-                                          const double* tsteps, const double* t1, const double* t2, const double* gamma, int nfgrid,
-                                          const long* foff, const double* df, int npgrid, const long* poff, const double* dx,
-                                          const double* dy, const double* dz, int nscale, const double* scales, const int* ntr,
-                                          const long* roff, const double* cosphi, const double* sinphi, const int* gidx,
-                                          const long* goff, const double* gains, const int* echo, const double* meq, int demod,
-                                          const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* wx,
-                                          const double* wy, const double* wz, const double* tx, const double* ty, const double* tz,
-                                          const double* rw, const double* wfx, const double* wfy, const double* wfz, const double* tfx,
-                                          const double* tfy, const double* tfz, const double* bgain, const double* bphi,
-                                          const double* mu, int cg, double rtol, double* dgain, double* dphi, int* ncg, double* rr,
-                                          double* gg, int* status, double* loss, double* ggain, double* gphi) {
+static int bloch_train_lm_step_sched_batch_call(mbfir_ctx* ctx, const char* who, bool mag, int npulse, const long* toff,
+                                                const double* b1_re, const double* b1_im, const double* gx, const double* gy,
+                                                const double* gz, const long* tsoff, const double* tsteps, const double* t1,
+                                                const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                                const double* df, int npgrid, const long* poff, const double* dx,
+                                                const double* dy, const double* dz, int nscale, const double* scales,
+                                                const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                                const int* gidx, const long* goff, const double* gains, const int* echo,
+                                                const double* meq, int demod, const double* m0x, const double* m0y,
+                                                const double* m0z, int ebcast, const double* wx, const double* wy,
+                                                const double* wz, const double* tx, const double* ty, const double* tz,
+                                                const double* rw, const double* wfx, const double* wfy, const double* wfz,
+                                                const double* tfx, const double* tfy, const double* tfz, const double* bgain,
+                                                const double* bphi, const double* mu, int cg, double rtol, double* dgain,
+                                                double* dphi, int* ncg, double* rr, double* gg, int* status, double* loss,
+                                                double* ggain, double* gphi) {
     if (!ctx) return MBFIR_E_ARG;
-    const char* who = "bloch_train_lm_step_sched_batch";
     auto bad = [&](const std::string& why) { ctx->err = std::string(who) + ": " + why; return MBFIR_E_ARG; };
     std::vector<long> npoint, ncomb;
     const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
@@ -2633,8 +2823,8 @@ int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long
         return e;
     if (ebcast != 0 && ebcast != 1) return bad("ebcast must be 0 or 1");
     const bool any_e = wx || wy || wz, any_f = wfx || wfy || wfz;
-    if (any_e && !(wx && wy && wz)) return bad("the echo weights are given together or not at all");
-    if (any_f && !(wfx && wfy && wfz)) return bad("the final weights are given together or not at all");
+    if (any_e && !(wx && wy && (mag || wz))) return bad("the echo weights are given together or not at all");
+    if (any_f && !(wfx && wfy && (mag || wfz))) return bad("the final weights are given together or not at all");
     if (!any_e && !any_f) return bad("neither an echo term nor a final term is given");
     if (!dgain && !dphi) return bad("neither the gains nor the phases vary: dgain and dphi are both null");
     const double* const w[3] = {wx, wy, wz};
@@ -2647,8 +2837,10 @@ int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long
     if (const int e = bloch_lm_check(ctx, who, own, true, npulse, roff, mu, cg, rtol)) return e;
     if ((!dgain && (bgain || ggain)) || (!dphi && (bphi || gphi)))
         return bad("a right-hand side or a gradient is given for a half that does not vary");
-    if (tg_e && !(tx && ty && tz)) return bad("tx, ty and tz are given together or not at all");
-    if (tg_f && !(tfx && tfy && tfz)) return bad("tfx, tfy and tfz are given together or not at all");
+    if (tg_e && !(tx && ty && (mag || tz)))
+        return bad(mag ? "txy and tz are given together or not at all" : "tx, ty and tz are given together or not at all");
+    if (tg_f && !(tfx && tfy && (mag || tfz)))
+        return bad(mag ? "tfxy and tfz are given together or not at all" : "tfx, tfy and tfz are given together or not at all");
     if ((tg_e && !any_e) || (tg_f && !any_f)) return bad("a target is given for a term that has no weights");
     if (targets && ((any_e && !tg_e) || (any_f && !tg_f))) return bad("a term that has weights has no target while the other has one");
     if ((bgain || bphi) && ((dgain && !bgain) || (dphi && !bphi)))
@@ -2660,7 +2852,48 @@ int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long
                                                        tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale,
                                                        scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y,
                                                        m0z, ebcast, w, t, rw, wf, tf, bgain, bphi, mu, cg, rtol, dgain, dphi, ncg, rr,
-                                                       gg, status, loss, ggain, gphi));
+                                                       gg, status, loss, ggain, gphi, mag));
+}
+int mbfir_bloch_train_lm_step_sched_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                          const double* gx, const double* gy, const double* gz, const long* tsoff,
+                                          const double* tsteps, const double* t1, const double* t2, const double* gamma,
+                                          int nfgrid, const long* foff, const double* df, int npgrid, const long* poff,
+                                          const double* dx, const double* dy, const double* dz, int nscale, const double* scales,
+                                          const int* ntr, const long* roff, const double* cosphi, const double* sinphi,
+                                          const int* gidx, const long* goff, const double* gains, const int* echo,
+                                          const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                          int ebcast, const double* wx, const double* wy, const double* wz, const double* tx,
+                                          const double* ty, const double* tz, const double* rw, const double* wfx,
+                                          const double* wfy, const double* wfz, const double* tfx, const double* tfy,
+                                          const double* tfz, const double* bgain, const double* bphi, const double* mu, int cg,
+                                          double rtol, double* dgain, double* dphi, int* ncg, double* rr, double* gg,
+                                          int* status, double* loss, double* ggain, double* gphi) {
+    return bloch_train_lm_step_sched_batch_call(ctx, "bloch_train_lm_step_sched_batch", false, npulse, toff, b1_re, b1_im, gx,
+                                                gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                                                nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod,
+                                                m0x, m0y, m0z, ebcast, wx, wy, wz, tx, ty, tz, rw, wfx, wfy, wfz, tfx, tfy, tfz,
+                                                bgain, bphi, mu, cg, rtol, dgain, dphi, ncg, rr, gg, status, loss, ggain, gphi);
+}
+int mbfir_bloch_train_lm_step_sched_mag_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re,
+                                              const double* b1_im, const double* gx, const double* gy, const double* gz,
+                                              const long* tsoff, const double* tsteps, const double* t1, const double* t2,
+                                              const double* gamma, int nfgrid, const long* foff, const double* df, int npgrid,
+                                              const long* poff, const double* dx, const double* dy, const double* dz, int nscale,
+                                              const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                              const double* sinphi, const int* gidx, const long* goff, const double* gains,
+                                              const int* echo, const double* meq, int demod, const double* m0x,
+                                              const double* m0y, const double* m0z, int ebcast, const double* wxy,
+                                              const double* wz, const double* txy, const double* tz, const double* rw,
+                                              const double* wfxy, const double* wfz, const double* tfxy, const double* tfz,
+                                              const double* bgain, const double* bphi, const double* mu, int cg, double rtol,
+                                              double* dgain, double* dphi, int* ncg, double* rr, double* gg, int* status,
+                                              double* loss, double* ggain, double* gphi) {
+    return bloch_train_lm_step_sched_batch_call(ctx, "bloch_train_lm_step_sched_mag_batch", true, npulse, toff, b1_re, b1_im, gx,
+                                                gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
+                                                nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod,
+                                                m0x, m0y, m0z, ebcast, wxy, wz, nullptr, txy, tz, nullptr, rw, wfxy, wfz,
+                                                nullptr, tfxy, tfz, nullptr, bgain, bphi, mu, cg, rtol, dgain, dphi, ncg, rr, gg,
+                                                status, loss, ggain, gphi);
 }
 
 int mbfir_test_jvp_group(void) { return jvp_group(); }

@@ -26,174 +26,13 @@ namespace mbfir {
 // k_bloch_train_run_gn's body and its switch TGN_HOIST are in sim_dev.h (bloch_train_run_gn_body), shared with the device
 // Levenberg-Marquardt step (blochtrainlm.hip).
 
-// blocks, ws, cw, cks, ck, gmx..: k_bloch_train_run_vjp's.  rw (null: ones): the repetitions' factors, laid out as rep.  we / te
-// (null: no echo term): the echo weights and targets, three planes PE entries apart, pulse p from e_off (ebcast 0) or o_off
-// (ebcast 1).  wf / tf (null: no final term): three planes PO apart, where the final planes lie.  lpart: one loss partial per
-// workgroup, workgroup (scale, chunk) of pulse p at lp[p] + scale nch + chunk.
-__global__ __launch_bounds__(256) void k_bloch_train_run_lsq(
-    const double* __restrict__ ws, const double2* __restrict__ rep, const int* __restrict__ gidx, const double* __restrict__ rw,
-    const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains, const SimBlock* __restrict__ blocks,
-    const BlochCkDev* __restrict__ cks, const long* __restrict__ lp, const double* __restrict__ m0, int demod, int ebcast,
-    const double* __restrict__ we, const double* __restrict__ te, long PE, const double* __restrict__ wf,
-    const double* __restrict__ tf, long PO, double* ck, double* cw, double* __restrict__ gmx, double* __restrict__ gmy,
-    double* __restrict__ gmz, double* __restrict__ lpart) {
-    __shared__ double2 scs[256];
-    __shared__ double srw[256];
-    __shared__ int sgi[256];
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const int ntr = Tr.ntr, G = Tr.ngain;
-    const double meq = Tr.meq;
-    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
-    const bool live = pair < npair;                                       // a thread past the end of the grid contributes nothing
-    const long blk = (long)bk.scale * npair + pair;
-    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
-    const double* wb = ws + Tr.w_off + comb0;
-    double* cb = cw + Tr.w_off + comb0;
-    const long nch = (npair + 255) / 256;
-    double* wck = ck + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK + tid;
-    double m[3] = {0, 0, 1}, W[TRAIN_ENT], acc[TRAIN_ENT];
-    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
-#pragma unroll
-    for (int e = 0; e < TRAIN_ENT; ++e) acc[e] = 0;
-    if (G == 1) {                                                         // one distinct gain: the planes are loaded once
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
-    }
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int cnt = min(256, ntr - k0);
-        if (tid < cnt) {
-            scs[tid] = rep[Tr.r_off + k0 + tid];
-            sgi[tid] = gidx[Tr.r_off + k0 + tid];
-            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
-        }
-        __syncthreads();
-    };
-    // m_k -> m_{k+1} from u_k = Z(+phi_k) m_k (in v), with the planes of the repetition in W[0 .. 11]
-    auto advance = [&](double c, double s, double v[3]) {
-        double n[3];
-        train_affine(W, W + 9, meq, v, n);
-        train_zm(c, s, n);
-        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
-    };
-    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints
-        stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (TRV_T - 1)) == 0) {                                 // m before repetition k0 + q
-                double* w = wck + (long)((k0 + q) / TRV_T) * BLOCH_CK;
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-            }
-            if (G != 1) {
-                const double* wg = wb + (long)sgi[q] * TRAIN_ENT * npair;
-#pragma unroll
-                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-            }
-            train_zp(scs[q].x, scs[q].y, m);
-            advance(scs[q].x, scs[q].y, m);
-        }
-    }
-    double l[3] = {0, 0, 0}, ls = 0;
-    if (live && wf) {                                                     // lambda_N = wf (m_N - tf), and the final loss
-        const long o = P.o_off + blk;
-        const double w0 = wf[o], w1 = wf[PO + o], w2 = wf[2 * PO + o];
-        const double r0 = m[0] - tf[o], r1 = m[1] - tf[PO + o], r2 = m[2] - tf[2 * PO + o];
-        l[0] = w0 * r0; l[1] = w1 * r1; l[2] = w2 * r2;
-        ls = 0.5 * (w0 * (r0 * r0) + w1 * (r1 * r1) + w2 * (r2 * r2));
-    }
-    // the weights and targets of repetition k at wp[k kstr], tp[k kstr]
-    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
-    const double* wp = we ? we + eo : nullptr;
-    const double* tp = we ? te + eo : nullptr;
-    const int klast = (ntr - 1) / 256 * 256;
-    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
-        if (k0 != klast) stage(k0);                                       // the forward walk left the last tile staged
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
-            const int ge = min(g0 + TRV_T, cnt);
-            double us[TRV_T][3], mm[3];                                   // us[j] = u of repetition k0 + g0 + j
-            const double* w = wck + (long)((k0 + g0) / TRV_T) * BLOCH_CK;
-            mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
-#pragma unroll
-            for (int j = 0; j < TRV_T; ++j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    train_zp(c, s, mm);
-                    us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
-                    if (g0 + j + 1 < ge) {
-                        if (G != 1) {
-                            const double* wg = wb + (long)sgi[g0 + j] * TRAIN_ENT * npair;
-#pragma unroll
-                            for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-                        }
-                        advance(c, s, mm);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = TRV_T - 1; j >= 0; --j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    const long go = (long)sgi[g0 + j] * TRAIN_ENT * npair;
-                    if (G != 1) {
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) { W[e] = wb[go + e * npair]; acc[e] = 0; }
-                    }
-                    const double* u = us[j];
-                    double a[3] = {l[0], l[1], l[2]};
-                    train_zp(c, s, a);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        acc[i] += a[i] * u[0]; acc[3 + i] += a[i] * u[1]; acc[6 + i] += a[i] * u[2];
-                        acc[9 + i] += meq * a[i];
-                        l[i] = W[3 * i] * a[0] + W[3 * i + 1] * a[1] + W[3 * i + 2] * a[2];           // A' a
-                    }
-                    if (wp) {
-                        const long ko = (long)(k0 + g0 + j) * kstr;
-                        const double rk = srw[g0 + j];
-                        double e[3], ae[3];
-                        train_affine(W + 12, W + 21, meq, u, e);          // the echo, as k_bloch_train_run forms it
-                        if (!demod) train_zm(c, s, e);
-                        double q2 = 0;
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            const double wi = wp[ko + i * PE], r = e[i] - tp[ko + i * PE];
-                            ae[i] = rk * (wi * r);                        // ce_k = rw_k w r
-                            q2 += wi * (r * r);
-                        }
-                        ls += rk * (0.5 * q2);
-                        if (!demod) train_zp(c, s, ae);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            acc[12 + i] += ae[i] * u[0]; acc[15 + i] += ae[i] * u[1]; acc[18 + i] += ae[i] * u[2];
-                            acc[21 + i] += meq * ae[i];
-                            l[i] += W[12 + 3 * i] * ae[0] + W[13 + 3 * i] * ae[1] + W[14 + 3 * i] * ae[2];       // A_e' ae
-                        }
-                    }
-                    train_zm(c, s, l);
-                    if (G != 1) {                                         // the thread's own column of the repetition's gain
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) cb[go + e * npair] += acc[e];
-                    }
-                }
-            }
-        }
-    }
-    const double sum = lm_block_sum(live ? ls : 0.0, reinterpret_cast<double*>(scs));         // 256 doubles of the 512 of scs
-    if (tid == 0) lpart[lp[bk.pulse] + (long)bk.scale * nch + bk.chunk] = sum;
-    if (!live) return;
-    if (G == 1) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) cb[e * npair] = acc[e];
-    }
-    if (gmx) { const long o = P.o_off + blk; gmx[o] = l[0]; gmy[o] = l[1]; gmz[o] = l[2]; }
-}
+// k_bloch_train_run_lsq: blochtraingn_lsq.inc as it is.  Its magnitude twin k_bloch_train_run_lsq_mag is the same text
+// in blochtrainmag.hip: a second kernel with this one's LDS arrays in this file gave this one another LDS layout.
+#define TRAIN_LSQ_KERNEL(name) name
+#define TRAIN_MAG false
+#include "blochtraingn_lsq.inc"
+#undef TRAIN_LSQ_KERNEL
+#undef TRAIN_MAG
 
 // blocks: the forward table times the directions (pad).  dws: the tangent planes of k_bloch_train_prop_jvp, ndir directions.  cw:
 // direction d's cotangent planes from d WT; ck: direction d's checkpoints from 2 d CK, a group 2 x 3 x 256 doubles (m, then dm).
@@ -206,6 +45,16 @@ __global__ __launch_bounds__(256) void k_bloch_train_run_gn(
     double* cw) {
     bloch_train_run_gn_body(blocks[blockIdx.x], ws, dws, rep, gidx, rw, pulses, trains, cks, m0, demod, ebcast, ndir, we, PE, wf, PO, WT, CK, ck,
                             cw);
+}
+// The magnitude twin: we / wf are two planes (xy, z), PE / PO apart.
+__global__ __launch_bounds__(256) void k_bloch_train_run_gn_mag(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0, int demod, int ebcast,
+    int ndir, const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long WT, long CK, double* ck,
+    double* cw) {
+    bloch_train_run_gn_body_mag(blocks[blockIdx.x], ws, dws, rep, gidx, rw, pulses, trains, cks, m0, demod, ebcast, ndir, we, PE, wf, PO, WT,
+                                CK, ck, cw);
 }
 
 // out[ndir r_off + d n + t] = k_bloch_train_vjp_fold's value from direction d's partials (part + d NP): one thread per sample, one
@@ -242,34 +91,22 @@ __global__ __launch_bounds__(256) void k_bloch_train_gn_fold(const double2* __re
 // tangent's table; one upload, the launches, one download.  The output region is what comes down (the gradient or the products, the
 // loss, dL / dm0), then what stays on the device: the planes, their tangents (gn), their cotangents per direction, the partials
 // per direction, the loss partials and the checkpoints.
-namespace {
-
-size_t add_triple(Staging& S, const double* x, const double* y, const double* z, long n) {
-    const size_t o = S.add(x ? (size_t)n * 24 : 0);
-    if (x) {
-        double* d = S.at<double>(o);
-        std::copy(x, x + n, d);
-        std::copy(y, y + n, d + n);
-        std::copy(z, z + n, d + 2 * n);
-    }
-    return o;
-}
-
-}  // namespace
-
-// The sections after train_stage: t* null for gn.
+// The sections after train_stage: t* null for gn.  mag: w, t, wf and tf hold two planes each, (xy, z), and the sections
+// are two planes long.
 void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
                     const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
-                    const double* const tf[3]) {
+                    const double* const tf[3], bool mag) {
     TrainStaged& Ts = Cl.Ts;
     BlochStaged& B = Ts.B;
     Staging& S = B.S;
     Cl.V = train_vjp_stage(Ts, npulse, toff, nscale, ntr);
     Cl.PE = ebcast ? B.O : Ts.E;
-    Cl.o_we = add_triple(S, w[0], w[1], w[2], Cl.PE);
-    Cl.o_te = add_triple(S, t[0], t[1], t[2], Cl.PE);
-    Cl.o_wf = add_triple(S, wf[0], wf[1], wf[2], B.O);
-    Cl.o_tf = add_triple(S, tf[0], tf[1], tf[2], B.O);
+    const int np = mag ? 2 : 3;
+    Cl.mag = mag;
+    Cl.o_we = add_planes(S, w, Cl.PE, np);
+    Cl.o_te = add_planes(S, t, Cl.PE, np);
+    Cl.o_wf = add_planes(S, wf, B.O, np);
+    Cl.o_tf = add_planes(S, tf, B.O, np);
     Cl.o_rw = S.add(rw ? (size_t)roff[npulse] * 8 : 0);
     if (rw) std::copy(rw, rw + roff[npulse], S.at<double>(Cl.o_rw));
     std::vector<long> lp(npulse);
@@ -287,7 +124,7 @@ void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, c
             for (int k = 0; k < (B.ntime[p] + 255) / 256; ++k) *gf++ = SimBlock{p, d, k, 0};
 }
 
-// k_bloch_train_run_lsq on the staged sections of Cl with the planes ws, and k_bloch_train_gn_fold at one direction with the loss sum,
+// k_bloch_train_run_lsq (Cl.mag: k_bloch_train_run_lsq_mag) on the staged sections of Cl with the planes ws, and k_bloch_train_gn_fold at one direction with the loss sum,
 // on the input rows `in` (null: the staged ones): the launches of bloch_train_lsq_batch_run, which the device step's trial repeats.
 void train_launch_run_lsq(TrainGnCall& Cl, hipStream_t st, int demod, int ebcast, bool echo, bool rep, bool fin, const double* ws,
                           double* ck, double* cw, double* gm, double* lpart) {
@@ -296,6 +133,16 @@ void train_launch_run_lsq(TrainGnCall& Cl, hipStream_t st, int demod, int ebcast
     Staging& S = B.S;
     const TrainVjpSections& V = Cl.V;
     const long O = B.O;
+    if (Cl.mag) {
+        train_run_lsq_mag_launch(st, (long)S.nblk, ws, S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi),
+                                 rep ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
+                                 S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr),
+                                 S.dev<const long>(Cl.o_lp), S.dev<const double>(B.o_m0), demod, ebcast,
+                                 echo ? S.dev<const double>(Cl.o_we) : nullptr, echo ? S.dev<const double>(Cl.o_te) : nullptr, Cl.PE,
+                                 fin ? S.dev<const double>(Cl.o_wf) : nullptr, fin ? S.dev<const double>(Cl.o_tf) : nullptr, O, ck, cw,
+                                 gm, gm ? gm + O : nullptr, gm ? gm + 2 * O : nullptr, lpart);
+        return;
+    }
     hipLaunchKernelGGL(k_bloch_train_run_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
                        S.dev<const int>(Ts.o_gi), rep ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
                        S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr),
@@ -323,7 +170,7 @@ void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long*
                                const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
                                const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
                                const double* const t[3], const double* rw, const double* const wf[3], const double* const tf[3],
-                               double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz) {
+                               double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     TrainGnCall Cl;
@@ -332,7 +179,7 @@ void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long*
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
-    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf);
+    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf, mag);
     Staging& S = B.S;
     const TrainVjpSections& V = Cl.V;
     const long O = B.O, T = toff[npulse];
@@ -375,7 +222,7 @@ void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* 
                               const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
                               const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
                               const double* rw, const double* const wf[3], int ndir, const double* v_re, const double* v_im,
-                              double* h_re, double* h_im) {
+                              double* h_re, double* h_im, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     TrainGnCall Cl;
@@ -385,7 +232,7 @@ void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* 
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
     const double* const none[3] = {nullptr, nullptr, nullptr};
-    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, ndir, w, none, rw, wf, none);
+    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, ndir, w, none, rw, wf, none, mag);
     Staging& S = B.S;
     const TrainVjpSections& V = Cl.V;
     const long O = B.O;
@@ -405,7 +252,7 @@ void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* 
     MBFIR_HIP(hipMemsetAsync(cw, 0, K * W * 8, st));             // upload does not zero the output region
     train_launch_prop(Ts, st, ws);
     train_launch_prop_jvp(Ts, st, o_qb, nwq, o_v, ndir, dws);
-    hipLaunchKernelGGL(k_bloch_train_run_gn, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, ws, dws,
+    hipLaunchKernelGGL(mag ? k_bloch_train_run_gn_mag : k_bloch_train_run_gn, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, ws, dws,
                        S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr,
                        S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_jb),
                        S.dev<const BlochCkDev>(V.o_ckr), S.dev<const double>(B.o_m0), demod, ebcast, ndir,

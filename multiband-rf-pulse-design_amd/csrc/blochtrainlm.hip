@@ -60,6 +60,17 @@ __global__ __launch_bounds__(256) void k_bloch_train_lm_run(
     if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
     bloch_train_run_gn_body(bk, ws, dws, rep, gidx, rw, pulses, trains, cks, m0, demod, ebcast, 1, we, PE, wf, PO, 0, 0, ck, cw);
 }
+// The magnitude twin: k_bloch_train_run_gn_mag's body; we / wf are two planes (xy, z), PE / PO apart.
+__global__ __launch_bounds__(256) void k_bloch_train_lm_run_mag(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0, int demod, int ebcast,
+    const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, const LmState* __restrict__ st, double* ck,
+    double* cw) {
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    bloch_train_run_gn_body_mag(bk, ws, dws, rep, gidx, rw, pulses, trains, cks, m0, demod, ebcast, 1, we, PE, wf, PO, 0, 0, ck, cw);
+}
 
 // blocks, cw, part, ck: k_bloch_train_prop_vjp's; ck holds the checkpoints of k_bloch_train_lm_prep.
 __global__ __launch_bounds__(256) void k_bloch_train_lm_pvjp(const double* __restrict__ in, const double* __restrict__ df,
@@ -148,7 +159,7 @@ void bloch_train_lm_step_batch_run(int device, void* stream, int npulse, const l
                                    const double* const w[3], const double* rw, const double* const wf[3], const double* b_re,
                                    const double* b_im, const double* mu, int cg, double rtol, const double* const t[3],
                                    const double* const tf[3], double* d_re, double* d_im, int* ncg, double* rr, double* gg,
-                                   int* status, double* loss, double* g_re, double* g_im) {
+                                   int* status, double* loss, double* g_re, double* g_im, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool trial = t[0] != nullptr || tf[0] != nullptr;
@@ -158,7 +169,7 @@ void bloch_train_lm_step_batch_run(int device, void* stream, int npulse, const l
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
-    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf);
+    train_gn_stage(Cl, npulse, toff, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf, mag);
     Staging& S = B.S;
     const TrainVjpSections& V = Cl.V;
     const long O = B.O, T = toff[npulse];
@@ -206,7 +217,7 @@ void bloch_train_lm_step_batch_run(int device, void* stream, int npulse, const l
         MBFIR_HIP(hipMemsetAsync(cw, 0, W * 8, st));              // the walk accumulates into the cotangent planes
         hipLaunchKernelGGL(k_bloch_train_lm_jvp, dim3((unsigned)nwq), dim3(256), 0, st, in, ddf, dpos, amp, pd, tr,
                            S.dev<const SimBlock>(o_qb), p, state, dws);
-        hipLaunchKernelGGL(k_bloch_train_lm_run, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, S.dev<const double2>(Ts.o_rep),
+        hipLaunchKernelGGL(mag ? k_bloch_train_lm_run_mag : k_bloch_train_lm_run, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, S.dev<const double2>(Ts.o_rep),
                            S.dev<const int>(Ts.o_gi), has_rw ? S.dev<const double>(Cl.o_rw) : nullptr, pd, tr,
                            S.dev<const SimBlock>(o_jb), S.dev<const BlochCkDev>(V.o_ckr), S.dev<const double>(B.o_m0), demod, ebcast,
                            has_e ? S.dev<const double>(Cl.o_we) : nullptr, Cl.PE, has_f ? S.dev<const double>(Cl.o_wf) : nullptr, O,

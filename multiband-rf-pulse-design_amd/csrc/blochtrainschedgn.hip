@@ -30,188 +30,13 @@ namespace mbfir {
 // k_bloch_train_run_sched_gn's body, its switch TSGN_HOIST and train_sg_back are in sim_dev.h (bloch_train_run_sched_gn_body), shared
 // with the schedule's device Levenberg-Marquardt step (blochtrainschedlm.hip).
 
-// blocks, ws, dws (null: the gains' half of every partial is zero), rep, gidx, vp, cks, ck, part, gmx ..: k_bloch_train_run_sched's.
-// rw (null: ones), we / te (null: no echo term), PE, wf / tf (null: no final term), PO, ebcast, lp, lpart: k_bloch_train_run_lsq's.
-__global__ __launch_bounds__(256) void k_bloch_train_run_sched_lsq(
-    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
-    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
-    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
-    const long* __restrict__ lp, const double* __restrict__ m0, int demod, int ebcast, const double* __restrict__ we,
-    const double* __restrict__ te, long PE, const double* __restrict__ wf, const double* __restrict__ tf, long PO, double* ck,
-    double2* __restrict__ part, double* __restrict__ gmx, double* __restrict__ gmy, double* __restrict__ gmz,
-    double* __restrict__ lpart) {
-    __shared__ double2 scs[256];
-    __shared__ double srw[256];
-    __shared__ int sgi[256];
-    __shared__ double red[2 * VJP_T * VJP_ROW];
-    static_assert(TRV_T == VJP_T, "a group of repetitions fills the tile's VJP_T x 2 rows");
-    const int tid = threadIdx.x;
-    const SimBlock bk = blocks[blockIdx.x];
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const VjpPulseDev V = vp[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const int ntr = Tr.ntr, G = Tr.ngain;
-    const double meq = Tr.meq;
-    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
-    const bool live = pair < npair;                                       // a thread past the end of the grid: the barriers only
-    const long blk = (long)bk.scale * npair + pair;
-    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
-    const double* wb = ws + Tr.w_off + comb0;
-    const double* db = dws ? dws + Tr.w_off + comb0 : nullptr;
-    const long nch = (npair + 255) / 256;
-    double* wck = ck + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK + tid;
-    double2* wpart = part + V.p_off + ((long)bk.scale * nch + bk.chunk) * ntr;
-    const int row = tid >> 4, ln = tid & 15;                              // reduction: 16 lanes per row of the tile
-    double m[3] = {0, 0, 1}, W[TRAIN_ENT], dW[TRAIN_ENT];
-    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
-#pragma unroll
-    for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = 0;
-    if (G == 1) {                                                         // one distinct gain: the planes are loaded once
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
-        if (db) {
-#pragma unroll
-            for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[e * npair];
-        }
-    }
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int cnt = min(256, ntr - k0);
-        if (tid < cnt) {
-            scs[tid] = rep[Tr.r_off + k0 + tid];
-            sgi[tid] = gidx[Tr.r_off + k0 + tid];
-            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
-        }
-        __syncthreads();
-    };
-    // m_k -> m_{k+1} from u_k = Z(+phi_k) m_k (in v), with the planes of the repetition in W[0 .. 11]
-    auto advance = [&](double c, double s, double v[3]) {
-        double n[3];
-        train_affine(W, W + 9, meq, v, n);
-        train_zm(c, s, n);
-        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
-    };
-    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints
-        stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (TRV_T - 1)) == 0) {                                 // m before repetition k0 + q
-                double* w = wck + (long)((k0 + q) / TRV_T) * BLOCH_CK;
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-            }
-            if (G != 1) {
-                const double* wg = wb + (long)sgi[q] * TRAIN_ENT * npair;
-#pragma unroll
-                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-            }
-            train_zp(scs[q].x, scs[q].y, m);
-            advance(scs[q].x, scs[q].y, m);
-        }
-    }
-    double l[3] = {0, 0, 0}, ls = 0;
-    if (live && wf) {                                                     // lambda_N = wf (m_N - tf), and the final loss
-        const long o = P.o_off + blk;
-        const double w0 = wf[o], w1 = wf[PO + o], w2 = wf[2 * PO + o];
-        const double r0 = m[0] - tf[o], r1 = m[1] - tf[PO + o], r2 = m[2] - tf[2 * PO + o];
-        l[0] = w0 * r0; l[1] = w1 * r1; l[2] = w2 * r2;
-        ls = 0.5 * (w0 * (r0 * r0) + w1 * (r1 * r1) + w2 * (r2 * r2));
-    }
-    // the weights and targets of repetition k at wp[k kstr], tp[k kstr]
-    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
-    const double* wp = we ? we + eo : nullptr;
-    const double* tp = we ? te + eo : nullptr;
-    const int klast = (ntr - 1) / 256 * 256;
-    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
-        if (k0 != klast) stage(k0);                                       // the forward walk left the last tile staged
-        const int cnt = min(256, ntr - k0);
-        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
-            const int ge = min(g0 + TRV_T, cnt);
-            if (live) {
-                double us[TRV_T][3], mm[3];                               // us[j] = u of repetition k0 + g0 + j
-                const double* w = wck + (long)((k0 + g0) / TRV_T) * BLOCH_CK;
-                mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
-#pragma unroll
-                for (int j = 0; j < TRV_T; ++j) {
-                    if (g0 + j < ge) {
-                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                        train_zp(c, s, mm);
-                        us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
-                        if (g0 + j + 1 < ge) {
-                            if (G != 1) {
-                                const double* wg = wb + (long)sgi[g0 + j] * TRAIN_ENT * npair;
-#pragma unroll
-                                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-                            }
-                            advance(c, s, mm);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = TRV_T - 1; j >= 0; --j) {
-                    if (g0 + j < ge) {
-                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                        const long go = (long)sgi[g0 + j] * TRAIN_ENT * npair;
-                        if (G != 1) {
-#pragma unroll
-                            for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[go + e * npair];
-                            if (db) {
-#pragma unroll
-                                for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[go + e * npair];
-                            }
-                        }
-                        const double* u = us[j];
-                        double a[3] = {l[0], l[1], l[2]}, n[3], dn[3];
-                        train_zp(c, s, a);
-                        train_affine(W, W + 9, meq, u, n);
-                        train_affine(dW, dW + 9, meq, u, dn);
-                        double gp = train_sched_dphi(W, a, u, n), gg = train_sched_dot(a, dn);
-                        train_sg_back(W, a, l);                           // A' a
-                        if (wp) {
-                            const long ko = (long)(k0 + g0 + j) * kstr;
-                            const double rk = srw[g0 + j];
-                            double e[3], ae[3], le[3];
-                            train_affine(W + 12, W + 21, meq, u, n);      // ne, and the echo as k_bloch_train_run forms it
-                            e[0] = n[0]; e[1] = n[1]; e[2] = n[2];
-                            if (!demod) train_zm(c, s, e);
-                            double q2 = 0;
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) {
-                                const double wi = wp[ko + i * PE], r = e[i] - tp[ko + i * PE];
-                                ae[i] = rk * (wi * r);                    // ce_k = rw_k w r
-                                q2 += wi * (r * r);
-                            }
-                            ls += rk * (0.5 * q2);
-                            if (!demod) train_zp(c, s, ae);
-                            train_affine(dW + 12, dW + 21, meq, u, dn);
-                            gg += train_sched_dot(ae, dn);
-                            gp += demod ? train_sched_dphi_demod(W + 12, ae, u) : train_sched_dphi(W + 12, ae, u, n);
-                            train_sg_back(W + 12, ae, le);                // A_e' ae
-                            l[0] += le[0]; l[1] += le[1]; l[2] += le[2];
-                        }
-                        train_zm(c, s, l);
-                        red[(2 * j) * VJP_ROW + tid] = gg;
-                        red[(2 * j + 1) * VJP_ROW + tid] = gp;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < TRV_T; ++j)
-                    if (g0 + j < ge) { red[(2 * j) * VJP_ROW + tid] = 0.0; red[(2 * j + 1) * VJP_ROW + tid] = 0.0; }
-            }
-            __syncthreads();
-            double sum = 0;                                               // row = 2 (repetition - g0) + (0: gain, 1: phase); rows past ge are not stored
-            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
-            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
-            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + k0 + g0)[row] = sum;
-            __syncthreads();
-        }
-    }
-    const double sum = lm_block_sum(live ? ls : 0.0, red);                // 256 doubles of the tile, free after the last group
-    if (tid == 0) lpart[lp[bk.pulse] + (long)bk.scale * nch + bk.chunk] = sum;
-    if (live && gmx) { const long o = P.o_off + blk; gmx[o] = l[0]; gmy[o] = l[1]; gmz[o] = l[2]; }
-}
+// k_bloch_train_run_sched_lsq: blochtrainschedgn_lsq.inc as it is.  Its magnitude twin k_bloch_train_run_sched_lsq_mag
+// is the same text in blochtrainmag.hip: a second kernel with this one's LDS arrays in this file gave this one another LDS layout.
+#define TRAIN_LSQ_KERNEL(name) name
+#define TRAIN_MAG false
+#include "blochtrainschedgn_lsq.inc"
+#undef TRAIN_LSQ_KERNEL
+#undef TRAIN_MAG
 
 // blocks: the forward table times the directions (pad).  dws (null: no gains direction and no gains output), rep, gidx, m0, demod:
 // k_bloch_train_run_sched_jvp's; dgain / dphi (either null: zeros): direction d of a pulse at ndir r_off + d ntr.  rw, we, PE, wf,
@@ -226,6 +51,17 @@ __global__ __launch_bounds__(256) void k_bloch_train_run_sched_gn(
     double2* __restrict__ part) {
     bloch_train_run_sched_gn_body(blocks[blockIdx.x], ws, dws, rep, gidx, rw, pulses, trains, vp, cks, m0, dgain, dphi, demod, ebcast, ndir,
                                   we, PE, wf, PO, CK, NP, ck, part);
+}
+// The magnitude twin: we / wf are two planes (xy, z), PE / PO apart.
+__global__ __launch_bounds__(256) void k_bloch_train_run_sched_gn_mag(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const double* __restrict__ m0, const double* __restrict__ dgain, const double* __restrict__ dphi, int demod, int ebcast, int ndir,
+    const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long CK, long NP, double* ck,
+    double2* __restrict__ part) {
+    bloch_train_run_sched_gn_body_mag(blocks[blockIdx.x], ws, dws, rep, gidx, rw, pulses, trains, vp, cks, m0, dgain, dphi, demod, ebcast,
+                                      ndir, we, PE, wf, PO, CK, NP, ck, part);
 }
 
 // out[ndir r_off + d n + k] = k_bloch_train_sched_fold's value from direction d's partials (part + d NP): one thread per repetition,
@@ -267,7 +103,12 @@ void train_sched_lsq_launch(hipStream_t st, long nblk, const double* ws, const d
                             const double* rw, const BlochPulseDev* pulses, const TrainPulseDev* trains, const SimBlock* blocks,
                             const VjpPulseDev* vp, const BlochCkDev* cks, const long* lp, const double* m0, int demod, int ebcast,
                             const double* we, const double* te, long PE, const double* wf, const double* tf, long PO, double* ck,
-                            double2* part, double* lpart) {
+                            double2* part, double* lpart, bool mag) {
+    if (mag) {
+        train_sched_lsq_mag_launch(st, nblk, ws, dws, rep, gidx, rw, pulses, trains, blocks, vp, cks, lp, m0, demod, ebcast, we, te, PE,
+                                   wf, tf, PO, ck, part, nullptr, nullptr, nullptr, lpart);
+        return;
+    }
     hipLaunchKernelGGL(k_bloch_train_run_sched_lsq, dim3((unsigned)nblk), dim3(256), 0, st, ws, dws, rep, gidx, rw, pulses, trains,
                        blocks, vp, cks, lp, m0, demod, ebcast, we, te, PE, wf, tf, PO, ck, part, nullptr, nullptr, nullptr, lpart);
 }
@@ -284,32 +125,20 @@ void train_sched_gn_fold_launch(hipStream_t st, long nfold, const double2* part,
 // directions; one upload, the launches, one download.  The output region is what comes down (the gradient halves or the products as
 // double2, the loss, dL / dm0), then what stays on the device: the partials per direction, the loss partials, the primal planes,
 // their tangents in the gain and the checkpoints per direction.
-namespace {
-
-size_t add_triple(Staging& S, const double* const v[3], long n) {
-    const size_t o = S.add(v[0] ? (size_t)n * 24 : 0);
-    if (v[0]) {
-        double* d = S.at<double>(o);
-        for (int c = 0; c < 3; ++c) std::copy(v[c], v[c] + n, d + (size_t)c * n);
-    }
-    return o;
-}
-
-}  // namespace
-
 // SchedGnCall (sim_dev.h): the sections both calls, and the schedule's device step (blochtrainschedlm.hip), add after train_stage;
 // t* null for gn.
 void sched_gn_stage(SchedGnCall& Cl, int npulse, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
                     const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
-                    const double* const tf[3]) {
+                    const double* const tf[3], bool mag) {
     TrainStaged& Ts = Cl.Ts;
     BlochStaged& B = Ts.B;
     Staging& S = B.S;
+    const int np = mag ? 2 : 3;
     Cl.PE = ebcast ? B.O : Ts.E;
-    Cl.o_we = add_triple(S, w, Cl.PE);
-    Cl.o_te = add_triple(S, t, Cl.PE);
-    Cl.o_wf = add_triple(S, wf, B.O);
-    Cl.o_tf = add_triple(S, tf, B.O);
+    Cl.o_we = add_planes(S, w, Cl.PE, np);
+    Cl.o_te = add_planes(S, t, Cl.PE, np);
+    Cl.o_wf = add_planes(S, wf, B.O, np);
+    Cl.o_tf = add_planes(S, tf, B.O, np);
     Cl.o_rw = S.add(rw ? (size_t)roff[npulse] * 8 : 0);
     if (rw) std::copy(rw, rw + roff[npulse], S.at<double>(Cl.o_rw));
     std::vector<VjpPulseDev> vp(npulse);
@@ -359,7 +188,7 @@ void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const
                                      const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
                                      const double* m0z, int ebcast, const double* const w[3], const double* const t[3],
                                      const double* rw, const double* const wf[3], const double* const tf[3], double* loss,
-                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz) {
+                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     SchedGnCall Cl;
@@ -368,7 +197,7 @@ void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
-    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf);
+    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf, mag);
     Staging& S = B.S;
     const long O = B.O, R = roff[npulse];
     const bool want_g = ggain != nullptr, want_m0 = gmx != nullptr, echo_t = w[0] != nullptr, fin_t = wf[0] != nullptr;
@@ -390,12 +219,23 @@ void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const
     if (want_g) train_launch_prop_dgain(Ts, st, o_qb, nwg, dws);
     const double* wed = echo_t ? S.dev<const double>(Cl.o_we) : nullptr;
     const double* ted = echo_t ? S.dev<const double>(Cl.o_te) : nullptr;
-    hipLaunchKernelGGL(k_bloch_train_run_sched_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, S.dev<const double2>(Ts.o_rep),
-                       S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
-                       S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk), S.dev<const VjpPulseDev>(Cl.o_vp),
-                       S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const long>(Cl.o_lp), S.dev<const double>(B.o_m0), demod, ebcast, wed,
-                       ted, Cl.PE, fin_t ? S.dev<const double>(Cl.o_wf) : nullptr, fin_t ? S.dev<const double>(Cl.o_tf) : nullptr, O,
-                       ck, part, want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr, want_m0 ? gm + 2 * O : nullptr, lpart);
+    const double* wfd = fin_t ? S.dev<const double>(Cl.o_wf) : nullptr;
+    const double* tfd = fin_t ? S.dev<const double>(Cl.o_tf) : nullptr;
+    if (mag) {
+        train_sched_lsq_mag_launch(st, (long)S.nblk, ws, dws, S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi),
+                                   rw ? S.dev<const double>(Cl.o_rw) : nullptr, S.dev<const BlochPulseDev>(S.o_pd),
+                                   S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk),
+                                   S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const long>(Cl.o_lp),
+                                   S.dev<const double>(B.o_m0), demod, ebcast, wed, ted, Cl.PE, wfd, tfd, O, ck, part,
+                                   want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr, want_m0 ? gm + 2 * O : nullptr, lpart);
+    } else {
+        hipLaunchKernelGGL(k_bloch_train_run_sched_lsq, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws,
+                           S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr,
+                           S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(S.o_bk),
+                           S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const long>(Cl.o_lp),
+                           S.dev<const double>(B.o_m0), demod, ebcast, wed, ted, Cl.PE, wfd, tfd, O, ck, part,
+                           want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr, want_m0 ? gm + 2 * O : nullptr, lpart);
+    }
     hipLaunchKernelGGL(k_bloch_train_sched_gn_fold, dim3((unsigned)Cl.nfold), dim3(256), 0, st, part, Cl.npart,
                        S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const SimBlock>(Cl.o_fb), nscale, 1, grad, lpart,
                        S.dev<const long>(Cl.o_lp), dloss);
@@ -420,7 +260,7 @@ void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const 
                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
                                     const double* m0z, int ebcast, const double* const w[3], const double* rw,
                                     const double* const wf[3], int ndir, const double* dgain, const double* dphi, double* hgain,
-                                    double* hphi) {
+                                    double* hphi, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     SchedGnCall Cl;
@@ -430,7 +270,7 @@ void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const 
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
     const double* const none[3] = {nullptr, nullptr, nullptr};
-    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, ndir, w, none, rw, wf, none);
+    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, ndir, w, none, rw, wf, none, mag);
     Staging& S = B.S;
     const long O = B.O;
     const size_t D = (size_t)ndir * roff[npulse], W = (size_t)Ts.W, K = (size_t)ndir;
@@ -449,7 +289,7 @@ void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const 
     double* ck = ws + W + (tang ? W : 0);
     train_launch_prop(Ts, st, ws);
     if (tang) train_launch_prop_dgain(Ts, st, o_qb, nwg, dws);
-    hipLaunchKernelGGL(k_bloch_train_run_sched_gn, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, ws, dws,
+    hipLaunchKernelGGL(mag ? k_bloch_train_run_sched_gn_mag : k_bloch_train_run_sched_gn, dim3((unsigned)(S.nblk * ndir)), dim3(256), 0, st, ws, dws,
                        S.dev<const double2>(Ts.o_rep), S.dev<const int>(Ts.o_gi), rw ? S.dev<const double>(Cl.o_rw) : nullptr,
                        S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr), S.dev<const SimBlock>(o_jb),
                        S.dev<const VjpPulseDev>(Cl.o_vp), S.dev<const BlochCkDev>(Cl.o_ck), S.dev<const double>(B.o_m0),

@@ -68,6 +68,19 @@ __global__ __launch_bounds__(256) void k_bloch_train_lm_sched_run(
     bloch_train_run_sched_gn_body(bk, ws, dws, rep, gidx, rw, pulses, trains, vp, cks, m0, pg, pp, demod, ebcast, 1, we, PE, wf, PO, 0, 0,
                                   ck, part);
 }
+// The magnitude twin: k_bloch_train_run_sched_gn_mag's body; we / wf are two planes (xy, z), PE / PO apart.
+__global__ __launch_bounds__(256) void k_bloch_train_lm_sched_run_mag(
+    const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep, const int* __restrict__ gidx,
+    const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses, const TrainPulseDev* __restrict__ trains,
+    const SimBlock* __restrict__ blocks, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
+    const double* __restrict__ m0, const double* __restrict__ pg, const double* __restrict__ pp, int demod, int ebcast,
+    const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, const LmState* __restrict__ st, double* ck,
+    double2* __restrict__ part) {
+    const SimBlock bk = blocks[blockIdx.x];
+    if (!st[bk.pulse].run) return;                               // uniform over the workgroup, written by an earlier launch
+    bloch_train_run_sched_gn_body_mag(bk, ws, dws, rep, gidx, rw, pulses, trains, vp, cks, m0, pg, pp, demod, ebcast, 1, we, PE, wf, PO, 0,
+                                      0, ck, part);
+}
 
 // k_bloch_train_lm_step (blochtrainlm.hip) with H p of repetition k formed as k_bloch_train_sched_gn_fold forms it (chunks, then
 // scales, in index order), the half that does not vary masked to exact zero.  One workgroup per pulse, one CG iteration; a pAp that
@@ -144,7 +157,7 @@ void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, c
                                          const double* const t[3], const double* rw, const double* const wf[3],
                                          const double* const tf[3], const double* bgain, const double* bphi, const double* mu, int cg,
                                          double rtol, double* dgain, double* dphi, int* ncg, double* rr, double* gg, int* status,
-                                         double* loss, double* ggain, double* gphi) {
+                                         double* loss, double* ggain, double* gphi, bool mag) {
     MBFIR_HIP(hipSetDevice(device));
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool vg = dgain != nullptr, vp = dphi != nullptr, eval = t[0] != nullptr || tf[0] != nullptr;
@@ -155,7 +168,7 @@ void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, c
     bloch_stage(B, npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff, tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz,
                 nscale, scales, 0, m0x, m0y, m0z);
     train_stage(Ts, npulse, nscale, scales, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq);
-    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf);      // bloch_train_lsq_sched_batch_run's own staging
+    sched_gn_stage(Cl, npulse, nscale, ntr, roff, ebcast, 1, w, t, rw, wf, tf, mag);      // bloch_train_lsq_sched_batch_run's own staging
     Staging& S = B.S;
     const long O = B.O, R = roff[npulse], PE = Cl.PE, npart = Cl.npart, nck = Cl.nck, nlp = Cl.nlp, nfold = Cl.nfold;
     const size_t o_we = Cl.o_we, o_te = Cl.o_te, o_wf = Cl.o_wf, o_tf = Cl.o_tf, o_rw = Cl.o_rw, o_vp = Cl.o_vp, o_ck = Cl.o_ck;
@@ -202,7 +215,7 @@ void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, c
         train_sched_lsq_launch(st, (long)S.nblk, ws, dws, rep, gi, rwd, pd, tr, S.dev<const SimBlock>(S.o_bk), vpv, ckd,
                                S.dev<const long>(o_lp), m0d, demod, ebcast, t[0] ? wed : nullptr,
                                t[0] ? S.dev<const double>(o_te) : nullptr, PE, tf[0] ? wfd : nullptr,
-                               tf[0] ? S.dev<const double>(o_tf) : nullptr, O, ck, part, lpart);
+                               tf[0] ? S.dev<const double>(o_tf) : nullptr, O, ck, part, lpart, mag);
         train_sched_gn_fold_launch(st, nfold, part, npart, vpv, S.dev<const SimBlock>(o_fb), nscale, grad, lpart,
                                    S.dev<const long>(o_lp), dloss);
     }
@@ -210,7 +223,7 @@ void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, c
                        bgain ? S.dev<const double>(o_bg) : nullptr, bphi ? S.dev<const double>(o_bp) : nullptr, grad, vg ? 1 : 0,
                        vp ? 1 : 0, pg, pp, d, r, state);
     for (int k = 0; k < cg; ++k) {                                // rounds of a pulse that has stopped are early exits
-        hipLaunchKernelGGL(k_bloch_train_lm_sched_run, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, rep, gi, rwd, pd, tr,
+        hipLaunchKernelGGL(mag ? k_bloch_train_lm_sched_run_mag : k_bloch_train_lm_sched_run, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, dws, rep, gi, rwd, pd, tr,
                            S.dev<const SimBlock>(o_jb), vpv, ckd, m0d, vg ? pg : nullptr, vp ? pp : nullptr, demod, ebcast, wed, PE,
                            wfd, O, state, ck, part);
         hipLaunchKernelGGL(k_bloch_train_lm_sched_step, dim3((unsigned)npulse), dim3(256), 0, st, part, vpv, nscale, cg, rtol,

@@ -206,6 +206,8 @@ void bloch_train_jvp_sched_batch_run(int device, void* stream, int npulse, const
 // cosphi; wf / tf: the final weights and targets (wf[0] null: no final term).  lsq: loss per pulse, the gradient per b1 sample,
 // gm* = dL / dm0 (all null: not downloaded).  gn: ndir directions per pulse as bloch_train_jvp_batch_run takes them, h_* = J' W J v
 // in the same layout.  One upload, one download; nothing echo-sized comes down.
+// mag (here, in the schedule's two calls and in the two train steps below): the magnitude fits of (|Mxy|, mz) per echo
+// and at the final state, by the kernels' _mag twins; w, t, wf and tf hold pairs (xy, z) in their first two entries.
 void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
@@ -214,7 +216,7 @@ void bloch_train_lsq_batch_run(int device, void* stream, int npulse, const long*
                                const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
                                const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
                                const double* const t[3], const double* rw, const double* const wf[3], const double* const tf[3],
-                               double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+                               double* loss, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz, bool mag = false);
 void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                               const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                               const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
@@ -223,7 +225,7 @@ void bloch_train_gn_batch_run(int device, void* stream, int npulse, const long* 
                               const int* gidx, const long* goff, const double* gains, const int* echo, const double* meq, int demod,
                               const double* m0x, const double* m0y, const double* m0z, int ebcast, const double* const w[3],
                               const double* rw, const double* const wf[3], int ndir, const double* v_re, const double* v_im,
-                              double* h_re, double* h_im);
+                              double* h_re, double* h_im, bool mag = false);
 // Fused least-squares and Gauss-Newton products of bloch_train_batch_run in its schedule, the gain and the RF phase of every
 // repetition (blochtrainschedgn.hip k_bloch_train_run_sched_lsq, k_bloch_train_run_sched_gn, k_bloch_train_sched_gn_fold with the
 // shipped k_bloch_train_prop and k_bloch_train_prop_dgain): the inputs, weights and targets of bloch_train_lsq_batch_run /
@@ -239,7 +241,7 @@ void bloch_train_lsq_sched_batch_run(int device, void* stream, int npulse, const
                                      const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
                                      const double* m0z, int ebcast, const double* const w[3], const double* const t[3],
                                      const double* rw, const double* const wf[3], const double* const tf[3], double* loss,
-                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz);
+                                     double* ggain, double* gphi, double* gmx, double* gmy, double* gmz, bool mag = false);
 void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                     const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                     const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
@@ -249,7 +251,7 @@ void bloch_train_gn_sched_batch_run(int device, void* stream, int npulse, const 
                                     const int* echo, const double* meq, int demod, const double* m0x, const double* m0y,
                                     const double* m0z, int ebcast, const double* const w[3], const double* rw,
                                     const double* const wf[3], int ndir, const double* dgain, const double* dphi, double* hgain,
-                                    double* hphi);
+                                    double* hphi, bool mag = false);
 // Least-squares products of bloch_batch_run's steady state (mode 1; blochssgn.hip k_bloch_ss_lsq_batch, k_bloch_ss_gn_batch, with
 // blochgn.hip's k_bloch_gn_fold): the forward call's inputs (no m0), the weights and the targets or the ndir directions in
 // the mode-1 outputs' layout, as bloch_lsq_batch_run / bloch_gn_batch_run take them.  lsq: loss per pulse, the gradient per b1
@@ -386,7 +388,7 @@ void bloch_train_lm_step_batch_run(int device, void* stream, int npulse, const l
                                    const double* const w[3], const double* rw, const double* const wf[3], const double* b_re,
                                    const double* b_im, const double* mu, int cg, double rtol, const double* const t[3],
                                    const double* const tf[3], double* d_re, double* d_im, int* ncg, double* rr, double* gg,
-                                   int* status, double* loss, double* g_re, double* g_im);
+                                   int* status, double* loss, double* g_re, double* g_im, bool mag = false);
 // The Levenberg-Marquardt step of the train's schedule on the device (blochtrainschedlm.hip k_bloch_train_lm_sched_init,
 // k_bloch_train_lm_sched_run, k_bloch_train_lm_sched_step with the shipped k_bloch_train_prop, k_bloch_train_prop_dgain and, with
 // targets, k_bloch_train_run_sched_lsq and k_bloch_train_sched_gn_fold): with targets (t[0] or tf[0] not null) the loss
@@ -404,7 +406,7 @@ void bloch_train_lm_step_sched_batch_run(int device, void* stream, int npulse, c
                                          const double* const t[3], const double* rw, const double* const wf[3],
                                          const double* const tf[3], const double* bgain, const double* bphi, const double* mu, int cg,
                                          double rtol, double* dgain, double* dphi, int* ncg, double* rr, double* gg, int* status,
-                                         double* loss, double* ggain, double* gphi);
+                                         double* loss, double* ggain, double* gphi, bool mag = false);
 // What mbfir_test_flip_stages adds to a search (include/mbfir.h says what each block holds): the overrides, the selected candidates
 // and the host blocks the search's per-workgroup bests, the report and the stages go to (interleaved re, im where complex).
 struct FlipStages {

@@ -767,6 +767,16 @@ __device__ __forceinline__ void train_sj_map(const double* M, const double gv[3]
     }
 }
 
+// A section of weights or targets of the train's fused calls (train_gn_stage, sched_gn_stage): np planes of n entries each, three
+// (x, y, z) or, with magnitude targets, two (xy, z); nothing where v[0] is null.
+inline size_t add_planes(Staging& S, const double* const v[3], long n, int np) {
+    const size_t o = S.add(v[0] ? (size_t)n * np * 8 : 0);
+    if (v[0]) {
+        double* d = S.at<double>(o);
+        for (int c = 0; c < np; ++c) std::copy(v[c], v[c] + n, d + (size_t)c * n);
+    }
+    return o;
+}
 // The sections the train's fused calls add after train_stage and train_vjp_stage (blochtraingn.hip train_gn_stage, t* null for gn):
 // the weights and targets, the repetitions' factors, the loss partials' offsets and the fold's table; nlp loss partials, ngf
 // workgroups of the fold.  train_launch_run_lsq and train_launch_lsq_fold launch k_bloch_train_run_lsq and k_bloch_train_gn_fold (one
@@ -776,10 +786,11 @@ struct TrainGnCall {
     TrainVjpSections V;
     size_t o_we = 0, o_te = 0, o_rw = 0, o_wf = 0, o_tf = 0, o_lp = 0, o_gf = 0;
     long PE = 0, nlp = 0, ngf = 0;
+    bool mag = false;                   // the magnitude fits: the weight and target sections are two planes, (xy, z)
 };
 void train_gn_stage(TrainGnCall& Cl, int npulse, const long* toff, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
                     const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
-                    const double* const tf[3]);
+                    const double* const tf[3], bool mag = false);
 void train_launch_run_lsq(TrainGnCall& Cl, hipStream_t st, int demod, int ebcast, bool echo, bool rep, bool fin, const double* ws,
                           double* ck, double* cw, double* gm, double* lpart);
 void train_launch_lsq_fold(TrainGnCall& Cl, hipStream_t st, int nscale, const double2* part, const double* in, double2* grad,
@@ -907,173 +918,7 @@ __device__ __forceinline__ void bloch_train_prop_jvp_body(const SimBlock bk, con
         }
 }
 
-// k_bloch_train_run_gn for the workgroup bk = (pulse, scale, chunk of 256 points, direction).
-__device__ __forceinline__ void bloch_train_run_gn_body(
-    const SimBlock bk, const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep,
-    const int* __restrict__ gidx, const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses,
-    const TrainPulseDev* __restrict__ trains, const BlochCkDev* __restrict__ cks, const double* __restrict__ m0, int demod, int ebcast,
-    int ndir, const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long WT, long CK, double* ck,
-    double* cw) {
-    __shared__ double2 scs[256];
-    __shared__ double srw[256];
-    __shared__ int sgi[256];
-    const int tid = threadIdx.x;
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const int ntr = Tr.ntr, G = Tr.ngain, dir = bk.pad;
-    const double meq = Tr.meq;
-    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
-    const bool live = pair < npair;
-    const long blk = (long)bk.scale * npair + pair;
-    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
-    const double* wb = ws + Tr.w_off + comb0;
-    // direction dir of the scale's first combination; a combination is ndir directions of TRAIN_ENT npair doubles
-    const double* db = dws + (long)ndir * Tr.w_off + ((long)bk.scale * G * ndir + dir) * TRAIN_ENT * npair + (live ? pair : 0);
-    const long gstr = (long)TRAIN_ENT * npair, dgstr = (long)ndir * gstr;
-    double* cb = cw + (long)dir * WT + Tr.w_off + comb0;
-    const long nch = (npair + 255) / 256;
-    double* wck = ck + 2 * ((long)dir * CK + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK) + tid;
-    const bool hoist = TGN_HOIST && G == 1;
-    double m[3] = {0, 0, 1}, dm[3] = {0, 0, 0}, W[TRAIN_ENT], acc[TRAIN_ENT];
-    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
-#pragma unroll
-    for (int e = 0; e < TRAIN_ENT; ++e) acc[e] = 0;
-    if (hoist) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
-    }
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int cnt = min(256, ntr - k0);
-        if (tid < cnt) {
-            scs[tid] = rep[Tr.r_off + k0 + tid];
-            sgi[tid] = gidx[Tr.r_off + k0 + tid];
-            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
-        }
-        __syncthreads();
-    };
-    // (m_k, dm_k) -> (m_{k+1}, dm_{k+1}) from (u_k, du_k) (in v, dv), with the planes of the repetition in W[0 .. 11] and its tangent
-    // planes at dg, as k_bloch_train_run_jvp steps them
-    auto advance = [&](double c, double s, const double* dg, double v[3], double dv[3]) {
-        double dW[12], n[3], dn[3];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) dW[e] = dg[e * npair];
-        train_affine_jvp(W, dW, dW + 9, meq, v, dv, dn);
-        train_zm(c, s, dn);
-        train_affine(W, W + 9, meq, v, n);
-        train_zm(c, s, n);
-        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
-        dv[0] = dn[0]; dv[1] = dn[1]; dv[2] = dn[2];
-    };
-    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints of m and dm
-        stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (TRV_T - 1)) == 0) {                                 // (m, dm) before repetition k0 + q
-                double* w = wck + (long)((k0 + q) / TRV_T) * (2 * BLOCH_CK);
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-                w[768] = dm[0]; w[1024] = dm[1]; w[1280] = dm[2];
-            }
-            if (!hoist) {
-                const double* wg = wb + (long)sgi[q] * gstr;
-#pragma unroll
-                for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-            }
-            train_zp(scs[q].x, scs[q].y, m);
-            train_zp(scs[q].x, scs[q].y, dm);
-            advance(scs[q].x, scs[q].y, db + (long)sgi[q] * dgstr, m, dm);
-        }
-    }
-    double l[3] = {0, 0, 0};
-    if (live && wf) {                                                     // lambda_N = wf dm_N
-        const long o = P.o_off + blk;
-        l[0] = wf[o] * dm[0]; l[1] = wf[PO + o] * dm[1]; l[2] = wf[2 * PO + o] * dm[2];
-    }
-    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
-    const double* wp = we ? we + eo : nullptr;
-    const int klast = (ntr - 1) / 256 * 256;
-    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
-        if (k0 != klast) stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
-            const int ge = min(g0 + TRV_T, cnt);
-            double us[TRV_T][3], dus[TRV_T][3], mm[3], dmm[3];            // (u, du) of repetition k0 + g0 + j
-            const double* w = wck + (long)((k0 + g0) / TRV_T) * (2 * BLOCH_CK);
-            mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
-            dmm[0] = w[768]; dmm[1] = w[1024]; dmm[2] = w[1280];
-#pragma unroll
-            for (int j = 0; j < TRV_T; ++j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    train_zp(c, s, mm);
-                    train_zp(c, s, dmm);
-                    us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
-                    dus[j][0] = dmm[0]; dus[j][1] = dmm[1]; dus[j][2] = dmm[2];
-                    if (g0 + j + 1 < ge) {
-                        if (!hoist) {
-                            const double* wg = wb + (long)sgi[g0 + j] * gstr;
-#pragma unroll
-                            for (int e = 0; e < 12; ++e) W[e] = wg[e * npair];
-                        }
-                        advance(c, s, db + (long)sgi[g0 + j] * dgstr, mm, dmm);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = TRV_T - 1; j >= 0; --j) {
-                if (g0 + j < ge) {
-                    const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                    const long go = (long)sgi[g0 + j] * gstr;
-                    if (!hoist) {
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) { W[e] = wb[go + e * npair]; acc[e] = 0; }
-                    }
-                    const double* u = us[j];
-                    double a[3] = {l[0], l[1], l[2]};
-                    train_zp(c, s, a);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) {
-                        acc[i] += a[i] * u[0]; acc[3 + i] += a[i] * u[1]; acc[6 + i] += a[i] * u[2];
-                        acc[9 + i] += meq * a[i];
-                        l[i] = W[3 * i] * a[0] + W[3 * i + 1] * a[1] + W[3 * i + 2] * a[2];           // A' a
-                    }
-                    if (wp) {
-                        const long ko = (long)(k0 + g0 + j) * kstr;
-                        const double rk = srw[g0 + j];
-                        const double* dk = db + (long)sgi[g0 + j] * dgstr + 12 * npair;
-                        double dW[12], ae[3];
-#pragma unroll
-                        for (int e = 0; e < 12; ++e) dW[e] = dk[e * npair];
-                        train_affine_jvp(W + 12, dW, dW + 9, meq, u, dus[j], ae);      // decho, as k_bloch_train_run_jvp forms it
-                        if (!demod) train_zm(c, s, ae);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) ae[i] = rk * (wp[ko + i * PE] * ae[i]);       // ce_k = rw_k w decho_k
-                        if (!demod) train_zp(c, s, ae);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            acc[12 + i] += ae[i] * u[0]; acc[15 + i] += ae[i] * u[1]; acc[18 + i] += ae[i] * u[2];
-                            acc[21 + i] += meq * ae[i];
-                            l[i] += W[12 + 3 * i] * ae[0] + W[13 + 3 * i] * ae[1] + W[14 + 3 * i] * ae[2];       // A_e' ae
-                        }
-                    }
-                    train_zm(c, s, l);
-                    if (!hoist) {                                         // the thread's own column of the repetition's gain
-#pragma unroll
-                        for (int e = 0; e < TRAIN_ENT; ++e) cb[go + e * npair] += acc[e];
-                    }
-                }
-            }
-        }
-    }
-    if (!live) return;
-    if (hoist) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) cb[e * npair] = acc[e];
-    }
-}
+// k_bloch_train_run_gn's body, bloch_train_run_gn_body, is in blochtrain_gn_bodies.inc, included below bloch_mag_seed.
 
 // What the schedule's device Levenberg-Marquardt step (blochtrainschedlm.hip) shares with the fused products of the
 // schedule (blochtrainschedgn.hip): the body of k_bloch_train_run_sched_gn, moved here token for token with the
@@ -1094,194 +939,7 @@ __device__ __forceinline__ void train_sg_back(const double* M, const double a[3]
     for (int i = 0; i < 3; ++i) o[i] = fma(M[3 * i + 2], a[2], fma(M[3 * i + 1], a[1], M[3 * i] * a[0]));
 }
 
-// k_bloch_train_run_sched_gn for the workgroup bk = (pulse, scale, chunk of 256 points, direction).
-__device__ __forceinline__ void bloch_train_run_sched_gn_body(
-    const SimBlock bk, const double* __restrict__ ws, const double* __restrict__ dws, const double2* __restrict__ rep,
-    const int* __restrict__ gidx, const double* __restrict__ rw, const BlochPulseDev* __restrict__ pulses,
-    const TrainPulseDev* __restrict__ trains, const VjpPulseDev* __restrict__ vp, const BlochCkDev* __restrict__ cks,
-    const double* __restrict__ m0, const double* __restrict__ dgain, const double* __restrict__ dphi, int demod, int ebcast, int ndir,
-    const double* __restrict__ we, long PE, const double* __restrict__ wf, long PO, long CK, long NP, double* ck,
-    double2* __restrict__ part) {
-    __shared__ double2 scs[256];
-    __shared__ double2 sdr[256];                                          // (dg_k, dp_k) of the workgroup's direction
-    __shared__ double srw[256];
-    __shared__ int sgi[256];
-    __shared__ double red[2 * VJP_T * VJP_ROW];
-    static_assert(TRV_T == VJP_T, "a group of repetitions fills the tile's VJP_T x 2 rows");
-    const int tid = threadIdx.x;
-    const BlochPulseDev P = pulses[bk.pulse];
-    const TrainPulseDev Tr = trains[bk.pulse];
-    const VjpPulseDev V = vp[bk.pulse];
-    const BlochCkDev K = cks[bk.pulse];
-    const int ntr = Tr.ntr, G = Tr.ngain, dir = bk.pad;
-    const double meq = Tr.meq;
-    const long npair = (long)P.nf * P.npos, pair = (long)bk.chunk * 256 + tid;
-    const bool live = pair < npair;                                       // a thread past the end of the grid: the barriers only
-    const long blk = (long)bk.scale * npair + pair;
-    const long comb0 = (long)bk.scale * G * TRAIN_ENT * npair + (live ? pair : 0);
-    const double* wb = ws + Tr.w_off + comb0;
-    const double* db = dws ? dws + Tr.w_off + comb0 : nullptr;
-    const long gstr = (long)TRAIN_ENT * npair;
-    const long nch = (npair + 255) / 256;
-    double* wck = ck + 2 * ((long)dir * CK + K.c_off + ((long)bk.scale * nch + bk.chunk) * K.ng * BLOCH_CK) + tid;
-    double2* wpart = part + (long)dir * NP + V.p_off + ((long)bk.scale * nch + bk.chunk) * ntr;
-    const long sbase = (long)ndir * Tr.r_off + (long)dir * ntr;           // the direction's first repetition in dgain / dphi
-    const int row = tid >> 4, ln = tid & 15;
-    const bool hoist = TSGN_HOIST && G == 1;
-    double m[3] = {0, 0, 1}, dm[3] = {0, 0, 0}, W[TRAIN_ENT], dW[TRAIN_ENT];
-    if (live) { const double* mi = m0 + 3 * (P.m_off + blk); m[0] = mi[0]; m[1] = mi[1]; m[2] = mi[2]; }
-#pragma unroll
-    for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = 0;
-    if (hoist) {
-#pragma unroll
-        for (int e = 0; e < TRAIN_ENT; ++e) W[e] = wb[e * npair];
-        if (db) {
-#pragma unroll
-            for (int e = 0; e < TRAIN_ENT; ++e) dW[e] = db[e * npair];
-        }
-    }
-    auto stage = [&](int k0) {
-        __syncthreads();
-        const int cnt = min(256, ntr - k0);
-        if (tid < cnt) {
-            const long o = sbase + k0 + tid;
-            scs[tid] = rep[Tr.r_off + k0 + tid];
-            sgi[tid] = gidx[Tr.r_off + k0 + tid];
-            srw[tid] = rw ? rw[Tr.r_off + k0 + tid] : 1.0;
-            sdr[tid] = make_double2(dgain ? dgain[o] : 0.0, dphi ? dphi[o] : 0.0);
-        }
-        __syncthreads();
-    };
-    // the state's half of the planes of the gain at go, and of their tangents, into W[0 .. 11] and dW[0 .. 11]
-    auto load_state = [&](long go) {
-        if (hoist) return;
-#pragma unroll
-        for (int e = 0; e < 12; ++e) W[e] = wb[go + e * npair];
-        if (db) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) dW[e] = db[go + e * npair];
-        }
-    };
-    // (m_k, dm_k) -> (m_{k+1}, dm_{k+1}) from (u_k, du_k) (in v, dv), as k_bloch_train_run_sched_jvp steps them
-    auto advance = [&](double c, double s, double2 d, double v[3], double dv[3]) {
-        double n[3], gn[3], dn[3];
-        train_affine(W, W + 9, meq, v, n);
-        train_affine(dW, dW + 9, meq, v, gn);                             // dA u + meq dB (zeros without the tangent planes)
-        train_sj_map(W, gn, n, d.x, d.y, true, dv, dn);
-        train_zm(c, s, dn);
-        train_zm(c, s, n);
-        v[0] = n[0]; v[1] = n[1]; v[2] = n[2];
-        dv[0] = dn[0]; dv[1] = dn[1]; dv[2] = dn[2];
-    };
-    for (int k0 = 0; k0 < ntr; k0 += 256) {                               // forwards: the checkpoints of m and dm
-        stage(k0);
-        const int cnt = min(256, ntr - k0);
-        if (!live) continue;
-        for (int q = 0; q < cnt; ++q) {
-            if ((q & (TRV_T - 1)) == 0) {                                 // (m, dm) before repetition k0 + q
-                double* w = wck + (long)((k0 + q) / TRV_T) * (2 * BLOCH_CK);
-                w[0] = m[0]; w[256] = m[1]; w[512] = m[2];
-                w[768] = dm[0]; w[1024] = dm[1]; w[1280] = dm[2];
-            }
-            const double c = scs[q].x, s = scs[q].y;
-            load_state((long)sgi[q] * gstr);
-            train_zp(c, s, m);
-            train_sj_in(c, s, sdr[q].y, m, dm);
-            advance(c, s, sdr[q], m, dm);
-        }
-    }
-    double l[3] = {0, 0, 0};
-    if (live && wf) {                                                     // lambda_N = wf dm_N
-        const long o = P.o_off + blk;
-        l[0] = wf[o] * dm[0]; l[1] = wf[PO + o] * dm[1]; l[2] = wf[2 * PO + o] * dm[2];
-    }
-    const long eo = ebcast ? P.o_off + blk : Tr.e_off + (long)bk.scale * ntr * npair + pair, kstr = ebcast ? 0 : npair;
-    const double* wp = we ? we + eo : nullptr;
-    const int klast = (ntr - 1) / 256 * 256;
-    for (int k0 = klast; k0 >= 0; k0 -= 256) {                            // backwards, group by group
-        if (k0 != klast) stage(k0);                                       // the forward walk left the last tile staged
-        const int cnt = min(256, ntr - k0);
-        for (int g0 = (cnt - 1) / TRV_T * TRV_T; g0 >= 0; g0 -= TRV_T) {
-            const int ge = min(g0 + TRV_T, cnt);
-            if (live) {
-                double us[TRV_T][3], dus[TRV_T][3], mm[3], dmm[3];        // (u, du) of repetition k0 + g0 + j
-                const double* w = wck + (long)((k0 + g0) / TRV_T) * (2 * BLOCH_CK);
-                mm[0] = w[0]; mm[1] = w[256]; mm[2] = w[512];
-                dmm[0] = w[768]; dmm[1] = w[1024]; dmm[2] = w[1280];
-#pragma unroll
-                for (int j = 0; j < TRV_T; ++j) {
-                    if (g0 + j < ge) {
-                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                        const double2 d = sdr[g0 + j];
-                        train_zp(c, s, mm);
-                        train_sj_in(c, s, d.y, mm, dmm);
-                        us[j][0] = mm[0]; us[j][1] = mm[1]; us[j][2] = mm[2];
-                        dus[j][0] = dmm[0]; dus[j][1] = dmm[1]; dus[j][2] = dmm[2];
-                        if (g0 + j + 1 < ge) {
-                            load_state((long)sgi[g0 + j] * gstr);
-                            advance(c, s, d, mm, dmm);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = TRV_T - 1; j >= 0; --j) {
-                    if (g0 + j < ge) {
-                        const double c = scs[g0 + j].x, s = scs[g0 + j].y;
-                        const long go = (long)sgi[g0 + j] * gstr;
-                        const double* u = us[j];
-                        double gg = 0, gp = 0, le[3] = {0, 0, 0};
-                        if (wp) {                                         // the echo's half first: its planes are dead before the state's
-                            const long ko = (long)(k0 + g0 + j) * kstr;
-                            const double rk = srw[g0 + j];
-                            const double2 d = sdr[g0 + j];
-                            if (!hoist) {
-#pragma unroll
-                                for (int e = 12; e < TRAIN_ENT; ++e) W[e] = wb[go + e * npair];
-                                if (db) {
-#pragma unroll
-                                    for (int e = 12; e < TRAIN_ENT; ++e) dW[e] = db[go + e * npair];
-                                }
-                            }
-                            double ne[3], ge3[3], ae[3];
-                            train_affine(W + 12, W + 21, meq, u, ne);
-                            train_affine(dW + 12, dW + 21, meq, u, ge3);  // dA_e u + meq dB_e
-                            train_sj_map(W + 12, ge3, ne, d.x, d.y, !demod, dus[j], ae);      // decho, as k_bloch_train_run_sched_jvp forms it
-                            if (!demod) train_zm(c, s, ae);
-#pragma unroll
-                            for (int i = 0; i < 3; ++i) ae[i] = rk * (wp[ko + i * PE] * ae[i]);       // ce_k = rw_k w decho_k
-                            if (!demod) train_zp(c, s, ae);
-                            gg = train_sched_dot(ae, ge3);
-                            gp = demod ? train_sched_dphi_demod(W + 12, ae, u) : train_sched_dphi(W + 12, ae, u, ne);
-                            train_sg_back(W + 12, ae, le);                // A_e' ae
-                        }
-                        load_state(go);
-                        double a[3] = {l[0], l[1], l[2]}, n[3], dn[3];
-                        train_zp(c, s, a);
-                        train_affine(W, W + 9, meq, u, n);
-                        train_affine(dW, dW + 9, meq, u, dn);
-                        gp += train_sched_dphi(W, a, u, n);
-                        gg += train_sched_dot(a, dn);
-                        train_sg_back(W, a, l);                           // A' a
-                        l[0] += le[0]; l[1] += le[1]; l[2] += le[2];
-                        train_zm(c, s, l);
-                        red[(2 * j) * VJP_ROW + tid] = gg;
-                        red[(2 * j + 1) * VJP_ROW + tid] = gp;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < TRV_T; ++j)
-                    if (g0 + j < ge) { red[(2 * j) * VJP_ROW + tid] = 0.0; red[(2 * j + 1) * VJP_ROW + tid] = 0.0; }
-            }
-            __syncthreads();
-            double sum = 0;                                               // row = 2 (repetition - g0) + (0: gain, 1: phase); rows past ge are not stored
-            for (int k = 0; k < 16; ++k) sum += red[row * VJP_ROW + ln + 16 * k];
-            for (int off = 8; off > 0; off >>= 1) sum += __shfl_down(sum, off, 16);
-            if (ln == 0 && row < 2 * (ge - g0)) reinterpret_cast<double*>(wpart + k0 + g0)[row] = sum;
-            __syncthreads();
-        }
-    }
-}
+// k_bloch_train_run_sched_gn's body, bloch_train_run_sched_gn_body, is in blochtrain_gn_bodies.inc, included below bloch_mag_seed.
 
 // The thread of k_bloch_train_prop_vjp: wave = column of [A | B], lane = point, for the workgroup bk = (pulse, combination, chunk of
 // 64 points) of the period adjoint's table.
@@ -1446,13 +1104,27 @@ __device__ __forceinline__ void bloch_fwd_step_batch(const double* s, double rot
     m[0] = e2 * o[0]; m[1] = e2 * o[1]; m[2] = fma(e1, o[2], 1 - e1);
 }
 // The cotangent of the magnitude fits from the pair of weights w = (w_xy, w_z): lsq with a = rho - t_xy and b = mz - t_z, gn with
-// a = u . dm_xy and b = dm_z.  c = (w_xy a u_x, w_xy a u_y, w_z b); a dead thread's is zero.
+// a = u . dm_xy and b = dm_z.  c = (w_xy a u_x, w_xy a u_y, w_z b); a dead thread's is zero.  Only w[0] and w[1] are read: the
+// train's twins pass an array of two.
 __device__ __forceinline__ void bloch_mag_seed(const BlochMagDir& D, const double w[3], double a, double b, bool live, double c[3]) {
     const double wa = w[0] * a;
     c[0] = live ? wa * D.ux : 0.0;
     c[1] = live ? wa * D.uy : 0.0;
     c[2] = live ? w[1] * b : 0.0;
 }
+// The bodies of the two Gauss-Newton walks of the pulse train, bloch_train_run_gn_body and
+// bloch_train_run_sched_gn_body, twice: as they are, the component fits, and as ..._mag, the magnitude fits of
+// (|Mxy|, mz) per echo and at the final state.  Plain text on both sides, as blochssgn_kernels.inc is.
+#define TRAIN_GN_BODY(name) name
+#define TRAIN_MAG false
+#include "blochtrain_gn_bodies.inc"
+#undef TRAIN_GN_BODY
+#undef TRAIN_MAG
+#define TRAIN_GN_BODY(name) name##_mag
+#define TRAIN_MAG true
+#include "blochtrain_gn_bodies.inc"
+#undef TRAIN_GN_BODY
+#undef TRAIN_MAG
 // Launches k_bloch_gn_fold (blochgn.hip) on nfold workgroups; lpart, lp, loss as the kernel takes them (loss null: no loss sum).
 void bloch_gn_fold_launch(hipStream_t st, long nfold, const double2* part, const VjpPulseDev* vp, const SimBlock* blocks,
                           const double* scales, int nscale, const double* in, const BlochPulseDev* pulses, double2* out,
@@ -1510,16 +1182,29 @@ struct SchedGnCall {
     size_t o_we = 0, o_te = 0, o_rw = 0, o_wf = 0, o_tf = 0, o_vp = 0, o_ck = 0, o_lp = 0, o_fb = 0;
     long PE = 0, npart = 0, nck = 0, nlp = 0, nfold = 0;      // per direction: double2 partials, checkpoint doubles of one state
 };
+// mag: w, t, wf and tf hold two planes each, (xy, z), and the sections are two planes long.
 void sched_gn_stage(SchedGnCall& Cl, int npulse, int nscale, const int* ntr, const long* roff, int ebcast, int ndir,
                     const double* const w[3], const double* const t[3], const double* rw, const double* const wf[3],
-                    const double* const tf[3]);
-// Launch k_bloch_train_run_sched_lsq (no dL / dm0) and k_bloch_train_sched_gn_fold (one direction, with the loss sum) of
+                    const double* const tf[3], bool mag = false);
+// Launch k_bloch_train_run_sched_lsq (mag: k_bloch_train_run_sched_lsq_mag; no dL / dm0) and k_bloch_train_sched_gn_fold (one direction, with the loss sum) of
 // blochtrainschedgn.hip for the schedule's device step (blochtrainschedlm.hip); arguments as the kernels take them.
 void train_sched_lsq_launch(hipStream_t st, long nblk, const double* ws, const double* dws, const double2* rep, const int* gidx,
                             const double* rw, const BlochPulseDev* pulses, const TrainPulseDev* trains, const SimBlock* blocks,
                             const VjpPulseDev* vp, const BlochCkDev* cks, const long* lp, const double* m0, int demod, int ebcast,
                             const double* we, const double* te, long PE, const double* wf, const double* tf, long PO, double* ck,
-                            double2* part, double* lpart);
+                            double2* part, double* lpart, bool mag = false);
+// Launch the magnitude twins of the two lsq walks (blochtrainmag.hip) on nblk workgroups; arguments as the kernels take
+// them, the weights and targets two planes (xy, z) each.
+void train_run_lsq_mag_launch(hipStream_t st, long nblk, const double* ws, const double2* rep, const int* gidx, const double* rw,
+                              const BlochPulseDev* pulses, const TrainPulseDev* trains, const SimBlock* blocks, const BlochCkDev* cks,
+                              const long* lp, const double* m0, int demod, int ebcast, const double* we, const double* te, long PE,
+                              const double* wf, const double* tf, long PO, double* ck, double* cw, double* gmx, double* gmy,
+                              double* gmz, double* lpart);
+void train_sched_lsq_mag_launch(hipStream_t st, long nblk, const double* ws, const double* dws, const double2* rep, const int* gidx,
+                                const double* rw, const BlochPulseDev* pulses, const TrainPulseDev* trains, const SimBlock* blocks,
+                                const VjpPulseDev* vp, const BlochCkDev* cks, const long* lp, const double* m0, int demod, int ebcast,
+                                const double* we, const double* te, long PE, const double* wf, const double* tf, long PO, double* ck,
+                                double2* part, double* gmx, double* gmy, double* gmz, double* lpart);
 void train_sched_gn_fold_launch(hipStream_t st, long nfold, const double2* part, long NP, const VjpPulseDev* vp, const SimBlock* blocks,
                                 int nscale, double2* out, const double* lpart, const long* lp, double* loss);
 

@@ -281,33 +281,37 @@ def _refine_bloch(who, ss_device, pulses, df, dp, targets, weights, scales, m0, 
 
 def refine_bloch_train_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
                              phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, iters=5, cg=8, mu0=None,
-                             rtol=1e-6, solver="host", ctx=None):
+                             rtol=1e-6, solver="host", magnitude=False, ctx=None):
     """refine_batch for bloch_train_batch's model: the same lock-step Levenberg-Marquardt / CG loop on
     bloch_train_lsq_batch and bloch_train_gn_batch.  pulses: (b1, gr, tp, t1, t2, nucleus) each, one period, of which only b1
     changes; df, dp: one grid shared by every pulse or a list of one per pulse; ntr, targets, weights, rep_weights, targets_final,
     weights_final, phases, gains, echo, scales, m0, meq and demod as for bloch_train_lsq_batch, what is given per pulse as a Python
     list of one entry per pulse; iters, cg, mu0 and rtol as for refine_batch.  Returns (b1s, infos) as refine_batch does.  solver:
     'host' runs the CG recurrence on the host, one bloch_train_gn_batch call per iteration; this entry point has no device step
-    (refine_bloch_train_lm_batch has both solvers).  A pulse refined in a batch has the bits of the same pulse refined
-    alone."""
+    (refine_bloch_train_lm_batch has both solvers).  magnitude: fit (|Mxy|, mz) of every echo and of the final state
+    instead of the vectors: targets, weights, targets_final and weights_final are pairs (xy, z) per pulse and every call
+    of the loop is made with magnitude=True.  A pulse refined in a batch has the bits of the same pulse refined alone."""
     return _refine_bloch_train("refine_bloch_train_batch", False, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final,
-                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx)
+                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, magnitude,
+                               ctx)
 
 
 def refine_bloch_train_lm_batch(pulses, df, dp, ntr, targets, weights, *, rep_weights=None, targets_final=None, weights_final=None,
                                 phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None, meq=1.0, demod=False, iters=5, cg=8,
-                                mu0=None, rtol=1e-6, solver="host", ctx=None):
+                                mu0=None, rtol=1e-6, solver="host", magnitude=False, ctx=None):
     """refine_bloch_train_batch with both solvers: the lock-step Levenberg-Marquardt / CG loop on the echoes of a
     pulse train; arguments and return value as for refine_bloch_train_batch.  solver: 'host' runs the CG recurrence on the host, one
     bloch_train_gn_batch call per iteration, and returns the bits and the 'calls' of refine_bloch_train_batch; 'device' solves and
     tries each step in one bloch_train_lm_step_batch call over the active pulses ('calls' then counts them under 'lm'), a CG
-    breakdown counting as a refused step.  A pulse refined in a batch has the bits of the same pulse refined alone."""
+    breakdown counting as a refused step.  magnitude: as for refine_bloch_train_batch, with both solvers.  A pulse refined in a batch
+    has the bits of the same pulse refined alone."""
     return _refine_bloch_train("refine_bloch_train_lm_batch", True, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final,
-                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx)
+                               weights_final, phases, gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, magnitude,
+                               ctx)
 
 
 def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, rep_weights, targets_final, weights_final, phases,
-                        gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, ctx):
+                        gains, echo, scales, m0, meq, demod, iters, cg, mu0, rtol, solver, magnitude, ctx):
     """The body of refine_bloch_train_batch and refine_bloch_train_lm_batch; who: the entry point, for the messages; device_ok:
     whether the device step may be taken."""
     mb = importlib.import_module(__package__)
@@ -329,7 +333,8 @@ def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, r
         raise ValueError("%s: neither an echo term nor a final term is given" % who)
     for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
         if v is not None and len(list(v)) != P:
-            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+            raise ValueError("%s: %d %s %s for %d pulses" % (who, len(list(v)), what, "pairs" if magnitude else "triples", P))
+    mag = dict(magnitude=True) if magnitude else {}                              # without it the calls are the ones they were
     rest = [tuple(p[1:]) for p in pulses]
     b1s = [np.array(p[0], dtype=np.complex128).ravel() for p in pulses]
     each_m0 = isinstance(m0, list) and len(m0) == P and all(isinstance(t, tuple) and len(t) == 3 for t in m0)
@@ -347,7 +352,7 @@ def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, r
     def kw(idx):
         return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=pick(phases, idx),
                     gains=pick(gains, idx), echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
-                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx, **mag)
 
     def args(idx, b1_of):
         return [(b1_of[q],) + rest[q] for q in idx], grid(df, idx), grid(dp, idx), pick(ntr, idx)
@@ -382,7 +387,7 @@ def _refine_bloch_train(who, device_ok, pulses, df, dp, ntr, targets, weights, r
 
 def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), iters=5, mu0=None,
                                    rep_weights=None, targets_final=None, weights_final=None, phases=np.pi, gains=1.0, echo=None,
-                                   scales=(1.0,), m0=None, meq=1.0, demod=False, ctx=None):
+                                   scales=(1.0,), m0=None, meq=1.0, demod=False, magnitude=False, ctx=None):
     """Lock-step Levenberg-Marquardt on the schedule of a pulse train, the gain and the RF phase of every repetition, with the pulses
     held fixed: _lm_loop on bloch_train_lsq_sched_batch / bloch_train_gn_sched_batch.  pulses, df, dp, targets, weights,
     rep_weights, targets_final, weights_final, echo, scales, m0, meq and demod as for refine_bloch_train_batch; ntr: an int, the pulses
@@ -392,8 +397,10 @@ def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
     refused: H does not depend on mu), symmetrises it, solves (H + mu I) d = -g by a dense Cholesky factorisation on the host and
     evaluates one lsq call at the trial.  iters and mu0 as for refine_batch (mu0 None: 1e-3 times the Rayleigh quotient <g, H g> /
     <g, g>, one gn call).  Returns (schedules, infos): per pulse (gains, phases), float64 of shape (ntr,), and refine_batch's info
-    dict ('calls' counts 'lsq' and 'gn').  Without "gains" in vary the period's tangent is never launched.  A pulse refined in a
-    batch has the bits of the same pulse refined alone."""
+    dict ('calls' counts 'lsq' and 'gn').  Without "gains" in vary the period's tangent is never launched.  magnitude: fit
+    (|Mxy|, mz) of every echo and of the final state instead of the vectors: targets and weights are pairs (xy, z) per
+    pulse and every call of the loop is made with magnitude=True.  A pulse refined in a batch has the bits of the same pulse refined
+    alone."""
     who = "refine_bloch_train_sched_batch"
     mb = importlib.import_module(__package__)
     pulses = list(pulses)
@@ -407,7 +414,8 @@ def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
         raise ValueError("%s: neither an echo term nor a final term is given" % who)
     for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
         if v is not None and len(list(v)) != P:
-            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+            raise ValueError("%s: %d %s %s for %d pulses" % (who, len(list(v)), what, "pairs" if magnitude else "triples", P))
+    mag = dict(magnitude=True) if magnitude else {}                              # without it the calls are the ones they were
     n = mb._train_ints(who, "ntr", ntr, P)
     if any(e != n[0] for e in n):
         raise ValueError("%s: the pulses of a call must share ntr" % who)
@@ -435,7 +443,7 @@ def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
         sc = [sched(q, x_of[q]) for q in idx]
         return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=[s[1] for s in sc],
                     gains=[s[0] for s in sc], echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
-                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx, **mag)
 
     def args(idx):
         return [pulses[q] for q in idx], grid(df, idx), grid(dp, idx), N
@@ -493,7 +501,8 @@ def refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, *, var
 
 def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, vary=("gains", "phases"), iters=5, mu0=None,
                                       rep_weights=None, targets_final=None, weights_final=None, phases=np.pi, gains=1.0, echo=None,
-                                      scales=(1.0,), m0=None, meq=1.0, demod=False, solver="host", cg=8, rtol=1e-6, ctx=None):
+                                      scales=(1.0,), m0=None, meq=1.0, demod=False, solver="host", cg=8, rtol=1e-6, magnitude=False,
+                                      ctx=None):
     """refine_bloch_train_sched_batch with both solvers; arguments and return value as for that function.  solver:
     'host' is refine_bloch_train_sched_batch, bit for bit, infos included (cg and rtol are not used).  'device' takes the steps with
     bloch_train_lm_step_sched_batch, which evaluates and solves at the same schedule, through the same _lm_loop: the call that
@@ -505,7 +514,8 @@ def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, 
     'calls' then counts the fused calls under 'lm'.  The speculative solve of a call is skipped (cg = 0) when every trial in it would
     end its pulse's refinement; in a batch whose pulses are at different steps (after refusals) a pulse on its last trial still
     pays the cg rounds its neighbours need, and their result is dropped.  The speculative d is never part of a result, so a pulse
-    refined in a batch has the bits of the same pulse refined alone."""
+    refined in a batch has the bits of the same pulse refined alone.  magnitude: as for refine_bloch_train_sched_batch, with both
+    solvers."""
     who = "refine_bloch_train_sched_lm_batch"
     mb = importlib.import_module(__package__)
     if solver not in ("host", "device"):
@@ -513,7 +523,8 @@ def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, 
     if solver == "host":
         return refine_bloch_train_sched_batch(pulses, df, dp, ntr, targets, weights, vary=vary, iters=iters, mu0=mu0,
                                               rep_weights=rep_weights, targets_final=targets_final, weights_final=weights_final,
-                                              phases=phases, gains=gains, echo=echo, scales=scales, m0=m0, meq=meq, demod=demod, ctx=ctx)
+                                              phases=phases, gains=gains, echo=echo, scales=scales, m0=m0, meq=meq, demod=demod,
+                                              magnitude=magnitude, ctx=ctx)
     pulses = list(pulses)
     P = len(pulses)
     if P == 0:
@@ -525,7 +536,8 @@ def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, 
         raise ValueError("%s: neither an echo term nor a final term is given" % who)
     for what, v in (("targets", targets), ("weights", weights), ("targets_final", targets_final), ("weights_final", weights_final)):
         if v is not None and len(list(v)) != P:
-            raise ValueError("%s: %d %s triples for %d pulses" % (who, len(list(v)), what, P))
+            raise ValueError("%s: %d %s %s for %d pulses" % (who, len(list(v)), what, "pairs" if magnitude else "triples", P))
+    mag = dict(magnitude=True) if magnitude else {}                              # without it the calls are the ones they were
     n = mb._train_ints(who, "ntr", ntr, P)
     if any(e != n[0] for e in n):
         raise ValueError("%s: the pulses of a call must share ntr" % who)
@@ -553,7 +565,7 @@ def refine_bloch_train_sched_lm_batch(pulses, df, dp, ntr, targets, weights, *, 
         sc = [sched(q, x_of[q]) for q in idx]
         return dict(rep_weights=pick(rep_weights, idx), weights_final=sub(weights_final, idx), phases=[s[1] for s in sc],
                     gains=[s[0] for s in sc], echo=pick(echo, idx), scales=scales, m0=[m0[q] for q in idx] if each_m0 else m0,
-                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx)
+                    meq=pick(meq, idx) if isinstance(meq, list) else meq, demod=demod, ctx=ctx, **mag)
 
     def args(idx):
         return [pulses[q] for q in idx], grid(df, idx), grid(dp, idx), N
