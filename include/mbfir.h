@@ -538,6 +538,35 @@ int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
                                 const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
                                 const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
                                 const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz);
+/* ---- Adjoint of the pulse train with respect to b1, the gradient waveform and the off-resonance --------------------------------------
+ * mbfir_bloch_train_vjp_batch plus, for the same loss, dL/dgx, dL/dgy, dL/dgz of the period's samples and dL/ddf.  gr and df enter
+ * a period only through a sample's precession angle about z, which neither the RF phase nor the gain of a repetition touches, so
+ * the repetitions are walked exactly as mbfir_bloch_train_vjp_batch walks them.  It takes that call's arguments in order, then
+ *   ggx / ggy / ggz: one double per sample of every pulse, laid out as gx / gy / gz, in the units of the waveform, summed over the
+ *     points, the scales, the gains and the repetitions without a factor (scale and gain multiply b1, not gr); all three required.
+ *     A NULL gx / gy / gz is differentiated at zero; a component is exactly zero where no position has that axis.
+ *   gdf: dL/ddf of every (scale, frequency, position) in the layout of the final planes, summed over the repetitions; the caller
+ *     sums over whatever shares an off-resonance.  NULL = not wanted.
+ * g_re / g_im equal mbfir_bloch_train_vjp_batch's to rounding (not promised to the bit); gmx / gmy / gmz have its bits.  One upload,
+ * four launches (five with gdf), one download: the propagator launch and the walk of the repetitions as in
+ * mbfir_bloch_train_vjp_batch; the period's samples swept forwards and backwards once per (pulse, scale, distinct gain, 64 points),
+ * which leaves five partials per (workgroup, sample) and, with gdf, one double per (scale, distinct gain, point); the folds over
+ * chunks and combinations.  No atomics: the bits of every result depend only on the pulse, its grids, its train, its cotangents
+ * and the scale list, and not on whether gdf or gm* is wanted.  tp, t1, t2, the positions, meq and the scales are not
+ * differentiated.
+ * The argument checks and their MBFIR_E_ARG messages are those of mbfir_bloch_train_vjp_batch, in its order; then a NULL ggx / ggy /
+ * ggz and a partial, workspace or workgroup count that overflows.  Each names bloch_train_vjp_gr_batch in mbfir_last_error and no
+ * device work is done before they pass.  A NULL context returns MBFIR_E_ARG. */
+int mbfir_bloch_train_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                   const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                   const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                   const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                   int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                   const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                   const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                   const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
+                                   const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz, double* ggx,
+                                   double* ggy, double* ggz, double* gdf);
 /* ---- Adjoint of the pulse train with respect to its schedule: the gain and the RF phase of every repetition ------------------------
  * For the loss of mbfir_bloch_train_vjp_batch, L = sum_k <ce_k, echo_k> + <cf, m_N>, the gradients dL/dgains[k] and dL/dphi_k of
  * every repetition k (repetition k plays gains[k] exp(i phi_k) b1), both summed over the scales and the points, and dL/dm0.  It

@@ -160,6 +160,9 @@ SYMBOLS = {
     "mbfir_bloch_train_vjp_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
                                               _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                              [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
+    "mbfir_bloch_train_vjp_gr_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int, _lp,
+                                                 _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
+                                                [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 18),
     "mbfir_bloch_train_vjp_sched_batch": (C.c_int, [C.c_void_p, C.c_int, _lp, _dp, _dp, _dp, _dp, _dp, _lp, _dp, _dp, _dp, _dp, C.c_int,
                                                     _lp, _dp, C.c_int, _lp, _dp, _dp, _dp, C.c_int, _dp] +
                                                    [_ip, _lp, _dp, _dp, _ip, _lp, _dp, _ip, _dp, C.c_int] + [_dp] * 14),
@@ -1937,6 +1940,54 @@ def bloch_train_vjp_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np
     if not grad_m0:
         return res
     return [(res[q], tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm)) for q in range(P)]
+
+
+def bloch_train_vjp_gr_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
+                             meq=1.0, demod=False, grad_m0=False, grad_df=False, ctx=None):
+    """The adjoint of bloch_train_batch with respect to b1, the gradient waveform gr of the period and, on request, the initial
+    magnetisation and the off-resonance df (mbfir_bloch_train_vjp_gr_batch): arguments as
+    bloch_train_vjp_batch.  Returns one (grad_b1, grad_gr) per pulse: grad_b1 as bloch_train_vjp_batch returns it (equal to
+    rounding, not promised to the bit), and grad_gr real of shape (ntime, 3), column a = dL/dg_a of the period's samples in the
+    units of gr, summed over the points, the repetitions, the scales and the gains without a factor (scale and gain multiply b1,
+    not gr); a column whose axis the pulse does not play is the derivative at a zero gradient, and is exactly zero where the
+    positions lack that axis too.  With grad_m0 and / or grad_df further members follow in that order: (gmx, gmy, gmz) with
+    bloch_train_vjp_batch's bits, and grad_df of shape (S, nf, npos), dL/ddf per scale, frequency and position, summed over the
+    repetitions: the caller sums over whatever shares an off-resonance.  One upload, four launches (five with grad_df), one
+    download.  Deterministic: the bits of every result depend only on the pulse, its grids, its train, its cotangents and the
+    scales.  tp, t1, t2, dp, meq and the scales are not differentiated (the gains and the phases: bloch_train_vjp_sched_batch)."""
+    who = "bloch_train_vjp_gr_batch"
+    Tn = _TrainArgs(who, pulses, df, dp, ntr, phases, gains, echo, scales, meq, demod)
+    A, ntr, ooff = Tn.A, Tn.ntr, Tn.ooff
+    P, S, nf, npos = A.P, A.S, A.nf, A.npos
+    if cot is None and cot_final is None:
+        raise ValueError("%s: neither echo cotangents nor final cotangents are given" % who)
+    ce = _train_cotangents(who, "echo", cot, A, [(n,) for n in ntr])
+    cf = _train_cotangents(who, "final", cot_final, A, [()] * P)
+    toff = _offsets(A.nt)
+    nul = C.cast(None, _dp)
+    m0p = _bloch_m0(A, m0)
+    grad = [np.zeros(int(toff[-1])) for _ in range(5)]                  # Re, Im of b1; gx, gy, gz
+    gm = [np.zeros(int(ooff[-1])) for _ in range(3)] if grad_m0 else [nul] * 3
+    gd = np.zeros(int(ooff[-1])) if grad_df else nul
+    ctx = ctx or get_context()
+    rc = load_library().mbfir_bloch_train_vjp_gr_batch(ctx._h, *A.head, *Tn.tail, *[_plane(v) for v in m0p],
+                                                       *([nul] * 3 if ce is None else [_ptr(v) for v in ce]),
+                                                       *([nul] * 3 if cf is None else [_ptr(v) for v in cf]), _ptr(grad[0]),
+                                                       _ptr(grad[1]), *[_plane(v) for v in gm], *[_ptr(v) for v in grad[2:]],
+                                                       _ptr(gd) if grad_df else gd)
+    if rc == E_ARG:
+        raise ValueError(ctx.last_error())
+    _check(ctx, rc)
+    g_all, gg = grad[0] + 1j * grad[1], np.stack(grad[2:], 1)
+    res = []
+    for q in range(P):
+        out = (g_all[toff[q]:toff[q + 1]], gg[toff[q]:toff[q + 1]])
+        if grad_m0:
+            out += (tuple(v[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]) for v in gm),)
+        if grad_df:
+            out += (gd[ooff[q]:ooff[q + 1]].reshape(S, nf[q], npos[q]),)
+        res.append(out)
+    return res
 
 
 def bloch_train_vjp_sched_batch(pulses, df, dp, ntr, cot, *, cot_final=None, phases=np.pi, gains=1.0, echo=None, scales=(1.0,),

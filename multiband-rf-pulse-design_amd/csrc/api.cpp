@@ -1619,6 +1619,55 @@ int mbfir_bloch_train_vjp_batch(mbfir_ctx* ctx, int npulse, const long* toff, co
                                              cfy, cfz, g_re, g_im, gmx, gmy, gmz));
 }
 
+// The train's adjoint in b1, gr and df (blochtrainvjpg.hip) keeps five doubles per (combination, chunk of 64 points,
+// sample), the rf pair and the three g components, and one double per (combination, point) for dL / d df: false when a count
+// overflows or exceeds 2^54 (the partials) or 2^56 (the workspace).
+static bool bloch_train_gr_fits(int npulse, const long* toff, const long* ncomb, const long* npoint) {
+    long part = 0, dfw = 0;
+    for (int p = 0; p < npulse; ++p) {
+        long w, a, d;
+        if (__builtin_mul_overflow(ncomb[p], (npoint[p] + 63) / 64, &w) || __builtin_mul_overflow(w, toff[p + 1] - toff[p], &a) ||
+            __builtin_add_overflow(part, a, &part) || __builtin_mul_overflow(ncomb[p], npoint[p], &d) ||
+            __builtin_add_overflow(dfw, d, &dfw))
+            return false;
+    }
+    return part <= (1L << 54) && dfw <= (1L << 56);
+}
+
+int mbfir_bloch_train_vjp_gr_batch(mbfir_ctx* ctx, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                   const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                   const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                   const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                   int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                   const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                   const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                   const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
+                                   const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz, double* ggx,
+                                   double* ggy, double* ggz, double* gdf) {
+    if (!ctx) return MBFIR_E_ARG;
+    auto bad = [&](const std::string& why) { ctx->err = "bloch_train_vjp_gr_batch: " + why; return MBFIR_E_ARG; };
+    std::vector<long> npoint, ncomb;
+    const bool arrays = toff && b1_re && b1_im && tsoff && tsteps && t1 && t2 && gamma && foff && df && poff && scales && ntr &&
+                        roff && cosphi && sinphi && gidx && goff && gains && echo && meq;
+    if (const int e = bloch_train_check(ctx, "bloch_train_vjp_gr_batch", npulse, toff, tsoff, t1, t2, nfgrid, foff, npgrid, poff,
+                                        nscale, arrays, ntr, roff, cosphi, sinphi, gidx, goff, gains, echo, meq, m0x, m0y, m0z, npoint,
+                                        ncomb))
+        return e;
+    if ((cex || cey || cez) && !(cex && cey && cez)) return bad("the echo cotangents are given together or not at all");
+    if ((cfx || cfy || cfz) && !(cfx && cfy && cfz)) return bad("the final cotangents are given together or not at all");
+    if (!cex && !cfx) return bad("neither echo cotangents nor final cotangents are given");
+    if (!g_re || !g_im) return bad("a gradient plane is null");
+    if ((gmx || gmy || gmz) && !(gmx && gmy && gmz)) return bad("gmx, gmy and gmz are given together or not at all");
+    if (!ggx || !ggy || !ggz) return bad("a plane of the gradient waveform's gradient (ggx, ggy, ggz) is null");
+    if (!bloch_train_vjp_fits(npulse, nscale, toff, ntr, ncomb.data(), npoint.data()) ||
+        !bloch_train_gr_fits(npulse, toff, ncomb.data(), npoint.data()))
+        return bad("the output size or the workgroup count overflows");
+    MBFIR_TRY(ctx, bloch_train_vjp_gr_batch_run(ctx->device, ctx->solver->stream(), npulse, toff, b1_re, b1_im, gx, gy, gz, tsoff,
+                                                tsteps, t1, t2, gamma, nfgrid, foff, df, npgrid, poff, dx, dy, dz, nscale, scales, ntr,
+                                                roff, cosphi, sinphi, gidx, goff, gains, echo, meq, demod, m0x, m0y, m0z, cex, cey, cez,
+                                                cfx, cfy, cfz, g_re, g_im, gmx, gmy, gmz, ggx, ggy, ggz, gdf));
+}
+
 // The train's adjoint in its schedule (blochtrainsched.hip) keeps one double2 partial per (scale, chunk of 256 points,
 // repetition), 3 x 256 checkpoint doubles per (scale, chunk of 256 points, group of 8 repetitions) and the propagators' planes
 // twice (bloch_prop_check has bounded them once), and launches one workgroup per (combination, chunk of 64 points): false when a

@@ -261,6 +261,17 @@ void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream
                        S.dev<const VjpPulseDev>(V.o_vp), S.dev<const BlochCkDev>(V.o_ckp), cw, part, ck);
 }
 
+void train_launch_run_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* ws, int demod, const double* ce,
+                          const double* cf, double* ck, double* cw, double* gm) {
+    Staging& S = Ts.B.S;
+    const long O = Ts.B.O, E = Ts.E;
+    hipLaunchKernelGGL(k_bloch_train_run_vjp, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
+                       S.dev<const int>(Ts.o_gi), S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr),
+                       S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr), S.dev<const double>(Ts.B.o_m0), demod, ce,
+                       ce ? ce + E : nullptr, ce ? ce + 2 * E : nullptr, cf, cf ? cf + O : nullptr, cf ? cf + 2 * O : nullptr, ck, cw,
+                       gm, gm ? gm + O : nullptr, gm ? gm + 2 * O : nullptr);
+}
+
 void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
                                const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
                                const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff, const double* df,
@@ -309,12 +320,7 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
     const double* ced = cex ? S.dev<const double>(o_ce) : nullptr;
     const double* cfd = cfx ? S.dev<const double>(o_cf) : nullptr;
     const bool want_m0 = gmx != nullptr;
-    hipLaunchKernelGGL(k_bloch_train_run_vjp, dim3((unsigned)S.nblk), dim3(256), 0, st, ws, S.dev<const double2>(Ts.o_rep),
-                       S.dev<const int>(Ts.o_gi), S.dev<const BlochPulseDev>(S.o_pd), S.dev<const TrainPulseDev>(Ts.o_tr),
-                       S.dev<const SimBlock>(S.o_bk), S.dev<const BlochCkDev>(V.o_ckr), S.dev<const double>(B.o_m0), demod, ced,
-                       ced ? ced + E : nullptr, ced ? ced + 2 * E : nullptr, cfd, cfd ? cfd + O : nullptr,
-                       cfd ? cfd + 2 * O : nullptr, ck1, cw, want_m0 ? gm : nullptr, want_m0 ? gm + O : nullptr,
-                       want_m0 ? gm + 2 * O : nullptr);
+    train_launch_run_vjp(Ts, V, st, ws, demod, ced, cfd, ck1, cw, want_m0 ? gm : nullptr);
     train_launch_prop_vjp(Ts, V, st, cw, part, ck2);
     hipLaunchKernelGGL(k_bloch_train_vjp_fold, dim3((unsigned)V.nfold), dim3(256), 0, st, part, S.dev<const VjpPulseDev>(V.o_vp),
                        S.dev<const SimBlock>(V.o_fb), S.dev<const double>(Ts.o_amp), S.dev<const TrainPulseDev>(Ts.o_tr), nscale,

@@ -151,6 +151,22 @@ void bloch_train_vjp_batch_run(int device, void* stream, int npulse, const long*
                                const double* m0x, const double* m0y, const double* m0z, const double* cex, const double* cey,
                                const double* cez, const double* cfx, const double* cfy, const double* cfz, double* g_re, double* g_im,
                                double* gmx, double* gmy, double* gmz);
+// bloch_train_vjp_batch_run plus the adjoint with respect to the gradient waveform and the off-resonance (blochtrainvjpg.hip
+// k_bloch_train_prop_vjp_gr, k_bloch_train_vjp_gr_fold, k_bloch_train_vjp_df_fold after the shipped k_bloch_train_prop and
+// k_bloch_train_run_vjp): ggx / ggy / ggz: dL / d gx, gy, gz per sample of the period, laid out as gx / gy / gz, summed
+// over the points, the scales and the gains without a factor (a null gx / gy / gz is differentiated at zero); gdf: dL / d df per
+// (scale, frequency, position) in the final planes' layout, summed over the scale's distinct gains (null: not formed).  One upload,
+// four launches (five with gdf), one download.
+void bloch_train_vjp_gr_batch_run(int device, void* stream, int npulse, const long* toff, const double* b1_re, const double* b1_im,
+                                  const double* gx, const double* gy, const double* gz, const long* tsoff, const double* tsteps,
+                                  const double* t1, const double* t2, const double* gamma, int nfgrid, const long* foff,
+                                  const double* df, int npgrid, const long* poff, const double* dx, const double* dy, const double* dz,
+                                  int nscale, const double* scales, const int* ntr, const long* roff, const double* cosphi,
+                                  const double* sinphi, const int* gidx, const long* goff, const double* gains, const int* echo,
+                                  const double* meq, int demod, const double* m0x, const double* m0y, const double* m0z,
+                                  const double* cex, const double* cey, const double* cez, const double* cfx, const double* cfy,
+                                  const double* cfz, double* g_re, double* g_im, double* gmx, double* gmy, double* gmz, double* ggx,
+                                  double* ggy, double* ggz, double* gdf);
 // Adjoint of bloch_train_batch_run with respect to the gain and the RF phase of every repetition (blochtrainsched.hip
 // k_bloch_train_prop_dgain, k_bloch_train_run_sched, k_bloch_train_sched_fold after blochtrain.hip's k_bloch_train_prop):
 // bloch_train_vjp_batch_run's inputs; ggain / gphi: one entry per repetition, laid out as cosphi (either null: not wanted, not

@@ -714,6 +714,11 @@ TrainVjpSections train_vjp_stage(TrainStaged& Ts, int npulse, const long* toff, 
 // train_launch_prop): the input rows on the device, null for the staged ones; the device step's trial passes the rows at b1 + d.
 void train_launch_prop_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* cw, double2* part, double* ck,
                            const double* in = nullptr);
+// Launches k_bloch_train_run_vjp (blochtrainvjp.hip) on the forward table, for the adjoint in gr and df too (blochtrainvjpg.hip, DESIGN
+// 8aj): ws the propagators' planes, ce / cf the three echo / final cotangent planes one after the other on the device (null: none),
+// ck its checkpoints, cw the planes' cotangents (zero on entry), gm the three planes of dL / d m0 (null: not wanted).
+void train_launch_run_vjp(TrainStaged& Ts, const TrainVjpSections& V, hipStream_t st, const double* ws, int demod, const double* ce,
+                          const double* cf, double* ck, double* cw, double* gm);
 // The table of the period's tangent (blochtrainjvp.hip): k_bloch_train_prop_vjp's order, once per direction group; nwg receives its
 // workgroups.  train_launch_prop_jvp launches k_bloch_train_prop_jvp on it: v the packed directions' section, dws the tangent planes.
 size_t train_jvp_table(TrainStaged& Ts, int nscale, int ndir, long& nwg);

@@ -21,6 +21,8 @@ has the forward-mode tangent in both, one mbfir.bloch_train_jvp_batch call with 
 may be float64 tensors of shape (ntr,) that require grad: the backward then has one mbfir.bloch_train_vjp_sched_batch call for the
 schedule's per-repetition gradients (section 8ad); with forward_mode=True the schedule has its forward-mode tangent as well, one
 mbfir.bloch_train_jvp_sched_batch call with one direction (section 8ae), and without it such a tangent raises NotImplementedError.
+Its gr and df may be float64 tensors that require grad as `bloch`'s may: the backward is then one mbfir.bloch_train_vjp_gr_batch
+call for every gradient that is wanted (section 8aj); a forward-mode tangent for either raises NotImplementedError.
 
     rf = torch.tensor(rf0, dtype=torch.complex128, requires_grad=True)
     g = torch.tensor(g0, dtype=torch.complex128, requires_grad=True)       # or an array: a constant
@@ -607,6 +609,110 @@ def _train_sched_forward_function():
     return BlochTrainSchedForward
 
 
+@functools.lru_cache(maxsize=None)
+def _train_g_function():
+    """BlochTrain with gr and / or df as inputs of the graph: the forward is BlochTrain's, the backward one
+    mbfir.bloch_train_vjp_gr_batch call for every gradient that is wanted, or the shipped
+    mbfir.bloch_train_vjp_batch call when neither gr nor df needs one.  rest: (tp, t1, t2, nucleus)."""
+    import torch
+
+    import mbfir
+
+    class BlochTrainG(torch.autograd.Function):
+        @staticmethod
+        def forward(b1, m0, gr, df, rest, dp, ntr, kw, final):
+            if torch.is_tensor(gr) and gr.requires_grad and (gr.dtype != torch.float64 or gr.dim() not in (1, 2) or
+                                                             (gr.dim() == 2 and gr.shape[1] > 3)):
+                raise ValueError("torchsim: a gr that requires grad must be a float64 tensor of shape (n,) or (n, 1..3)")
+            if torch.is_tensor(df) and df.requires_grad and (df.dtype != torch.float64 or df.dim() != 1):
+                raise ValueError("torchsim: a df that requires grad must be a float64 tensor of shape (nf,)")
+            return _train_function().forward(b1, m0, (_host(gr, np.float64),) + rest, _host(df, np.float64), dp, ntr, kw, final)
+
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            b1, m0, gr, df, rest, dp, ntr, kw, final = inputs
+            ctx.args = (_host(m0, np.float64), (_host(gr, np.float64),) + rest, _host(df, np.float64), dp, ntr, kw, final)
+            ctx.m0_like = (m0.shape, m0.device) if torch.is_tensor(m0) else None          # where the gradients go
+            ctx.gr_like = (gr.shape, gr.device) if torch.is_tensor(gr) else None
+            ctx.df_like = (df.shape, df.device) if torch.is_tensor(df) else None
+            ctx.save_for_backward(b1)
+
+        @staticmethod
+        def jvp(ctx, *tangents):
+            raise NotImplementedError("torchsim: the forward-mode tangent of bloch_train with respect to gr or df is not implemented "
+                                      "(reverse mode is)")
+
+        @staticmethod
+        def backward(ctx, *cots):
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            want_b1, want_m0, want_gr, want_df = ctx.needs_input_grad[:4]
+            cot = tuple(_host(c, np.float64) for c in cots)
+            args = ([(_host(b1, np.complex128),) + rest], df, dp, ntr, [cot[:3]])
+            kws = dict(kw, cot_final=[cot[3:]] if final else None, m0=None if m0h is None else tuple(m0h), grad_m0=want_m0)
+            gm = ggr = gdf = None
+            if not (want_gr or want_df):                                # the b1 call, with its bits
+                res, = mbfir.bloch_train_vjp_batch(*args, **kws)
+                grad, gm = res if want_m0 else (res, None)
+            else:
+                res, = mbfir.bloch_train_vjp_gr_batch(*args, grad_df=want_df, **kws)
+                grad = res[0]
+                gm = res[2] if want_m0 else None
+                if want_gr:                                             # cut to the axes gr has
+                    shape, dev = ctx.gr_like
+                    k = shape[1] if len(shape) == 2 else 1
+                    ggr = torch.from_numpy(np.ascontiguousarray(res[1][:, :k]).reshape(shape)).to(dev)
+                if want_df:                                             # one df serves every scale and position: their sum
+                    gdf = torch.from_numpy(np.ascontiguousarray(res[-1].sum(axis=(0, 2))).reshape(ctx.df_like[0])).to(ctx.df_like[1])
+            gb = torch.from_numpy(np.ascontiguousarray(grad)).to(b1.device) if want_b1 else None
+            if want_m0:                                                 # one m0 serves every scale: its gradient is their sum
+                gm = torch.from_numpy(np.stack([v.sum(0) for v in gm]).reshape(ctx.m0_like[0])).to(ctx.m0_like[1])
+            return gb, gm, ggr, gdf, None, None, None, None, None
+
+    return BlochTrainG
+
+
+@functools.lru_cache(maxsize=None)
+def _train_g_forward_function():
+    """BlochTrainG with the forward-mode tangent in b1 and in a tensor m0, one mbfir.bloch_train_jvp_batch call with one direction
+    (DESIGN section 8aa); a tangent for gr or df raises NotImplementedError."""
+    import torch
+
+    import mbfir
+
+    base = _train_g_function()
+
+    class BlochTrainGForward(base):
+        @staticmethod
+        def setup_context(ctx, inputs, output):
+            base.setup_context(ctx, inputs, output)
+            ctx.save_for_forward(inputs[0])
+            ctx.out_like = tuple((o.shape, o.device) for o in output)
+            ctx.set_materialize_grads(False)                            # a gr or df without a tangent arrives as None, not as zeros
+
+        @staticmethod
+        def backward(ctx, *cots):                                       # the parent's, on the zeros it would have been handed
+            cots = tuple(torch.zeros(s, dtype=torch.float64, device=d) if c is None else c for c, (s, d) in zip(cots, ctx.out_like))
+            return base.backward(ctx, *cots)
+
+        @staticmethod
+        def jvp(ctx, v, vm0, vgr, vdf, *_):
+            if vgr is not None or vdf is not None:
+                raise NotImplementedError("torchsim: the forward-mode tangent of bloch_train with respect to gr or df is not "
+                                          "implemented (reverse mode is)")
+            b1, = ctx.saved_tensors
+            m0h, rest, df, dp, ntr, kw, final = ctx.args
+            b1h = _host(b1, np.complex128)
+            vh = np.zeros_like(b1h) if v is None else _host(v, np.complex128)
+            dm0 = None if vm0 is None else [tuple(_host(vm0, np.float64))]
+            tan, = mbfir.bloch_train_jvp_batch([(b1h,) + rest], df, dp, ntr, [vh], tangents_m0=dm0,
+                                               m0=None if m0h is None else tuple(m0h), final=final, **dict(kw))
+            planes = tan[0] + tan[1] if final else tan
+            return tuple(torch.from_numpy(np.ascontiguousarray(t)).to(b1.device) for t in planes)
+
+    return BlochTrainGForward
+
+
 def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi, gains=1.0, echo=None, scales=(1.0,), m0=None,
                 meq=1.0, demod=False, final=False, forward_mode=False):
     """The echoes (mx, my, mz) of mbfir.bloch_train_batch([(b1, gr, tp, t1, t2, nucleus)], df, dp, ntr, ...), each a float64 tensor
@@ -622,9 +728,27 @@ def bloch_train(b1, gr, tp, t1, t2, df, dp, ntr, *, nucleus="C-13", phases=np.pi
     mbfir.bloch_train_vjp_sched_batch call (section 8ad), next to the call for b1 and m0 when those need gradients too.  A
     forward-mode tangent in the schedule raises NotImplementedError unless forward_mode is set: then the tangent in the gains, the
     phases and m0 is one mbfir.bloch_train_jvp_sched_batch call with one direction (section 8ae), summed with one
-    mbfir.bloch_train_jvp_batch call when b1 has a tangent too; reverse mode keeps its calls and its bits."""
+    mbfir.bloch_train_jvp_batch call when b1 has a tangent too; reverse mode keeps its calls and its bits.
+    gr and df may be float64 tensors that require grad, gr of shape (n,) or (n, 1..3) and df of shape (nf,) (another dtype or shape
+    raises ValueError): then they are differentiated in reverse mode as well, gr's gradient cut to its shape and df's summed over
+    the scales and positions, and the backward is one mbfir.bloch_train_vjp_gr_batch call for every gradient that is wanted
+    (section 8aj); a backward that needs neither makes the b1 call.  A forward-mode tangent for gr or df raises
+    NotImplementedError, with and without forward_mode, and so does a gr or df in the graph together with gains or phases in the
+    graph: no call differentiates both."""
     if m0 is not None and not hasattr(m0, "detach"):
         m0 = np.stack([np.asarray(v, dtype=np.float64) for v in m0])
+    if any(_in_graph(v) for v in (gr, df)):                             # inputs of the graph (section 8aj)
+        if any(_in_graph(v) for v in (gains, phases)):
+            raise NotImplementedError("torchsim: bloch_train differentiates gr and df, or the gains and the phases, not both in one "
+                                      "call: no gradient would be dropped silently, so detach one of the two groups")
+        kw = (("phases", _host(phases, np.float64)), ("gains", _host(gains, np.float64)), ("echo", echo), ("scales", tuple(scales)),
+              ("meq", float(meq)), ("demod", bool(demod)))
+        gr = gr if hasattr(gr, "detach") else _host(gr, np.float64)
+        df = df if hasattr(df, "detach") else _host(df, np.float64)
+        fn = _train_g_forward_function() if forward_mode else _train_g_function()
+        out = fn.apply(b1, m0, gr, df, (_host(tp, np.float64), float(t1), float(t2), nucleus), _host(dp, np.float64), int(ntr), kw,
+                       bool(final))
+        return (out[:3], out[3:]) if final else out
     if any(_in_graph(v) for v in (gains, phases)):
         kw = (("echo", echo), ("scales", tuple(scales)), ("meq", float(meq)), ("demod", bool(demod)))
         rest = (_host(gr, np.float64), _host(tp, np.float64), float(t1), float(t2), nucleus)
